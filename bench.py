@@ -1,7 +1,14 @@
 #!/usr/bin/env python3
 """Headline benchmark: Msamples/s on data/scene.obj, 1920x1080 @ 256 spp (BASELINE.json configs[1]).
 
-    python bench.py --gpus N --steps K --warmup W [--config c2|c4] [--scaling strong|weak]
+    python bench.py --gpus N --steps K --warmup W [--config c2|c4] [--scaling strong|weak] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints one JSON line with the headline figure.  `--full` adds what
+the headline does not need: the CPU baseline, the roofline of the trace kernel, the one-shot call, the two-pipeline
+schedule, the C3 / C5 stand-ins, the C4 frame and the scaling probe (`--no-cpu`, `--no-oneshot`, `--no-other` drop
+parts of it).  `--dump-outputs DIR` writes the RGB8 frame of the last timed step to DIR/frame_rgb8.npy as float32 (a
+fixed, seeded sample of its pixels when the whole frame would exceed 64 MB; DIR/frame_rgb8_pixels.npy then holds their
+flat indices), so that two builds can be compared output for output: the inputs are the same in every run.
 
 With N > 1 and no WORLD_SIZE in the environment this process starts N rank processes itself (a
 `python -m torch.distributed.run` child, before anything here touches a GPU) and relays rank 0's JSON line;
@@ -115,6 +122,26 @@ def load_profile(name):
         with open(path) as f:
             return json.load(f)
     return None
+
+
+DUMP_BYTES = 64 << 20          # --dump-outputs: at most this much in all
+DUMP_SAMPLE_PIXELS = 2 << 20   # pixels kept when the whole frame would not fit (seeded, the same in every run)
+
+
+def dump_frame(out_dir, frame):
+    """--dump-outputs: the [w, h, 3] RGB8 frame the timed path returned, as float32.  A frame larger than DUMP_BYTES is
+    reduced to a fixed sample of its pixels (numpy seed 0), whose flat indices go to frame_rgb8_pixels.npy."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    rgb = frame.cpu().numpy().astype(np.float32)
+    pix_path = os.path.join(out_dir, "frame_rgb8_pixels.npy")
+    if rgb.nbytes > DUMP_BYTES:
+        pix = np.sort(np.random.default_rng(0).choice(rgb.shape[0] * rgb.shape[1], DUMP_SAMPLE_PIXELS, replace=False))
+        rgb = rgb.reshape(-1, 3)[pix]
+        np.save(pix_path, pix.astype(np.float64))
+    elif os.path.exists(pix_path):
+        os.remove(pix_path)                  # left by an earlier, larger frame in the same directory
+    np.save(os.path.join(out_dir, "frame_rgb8.npy"), rgb)
 
 
 class stdout_to_stderr:
@@ -289,9 +316,14 @@ def main():
     ap.add_argument("--spp", type=int, default=0)
     ap.add_argument("--cpu-rows", type=int, default=240, help="rows of the frame timed on the CPU oracle (240 rows = 66 M samples: about 10 s on 16 cores)")
     ap.add_argument("--other-cpu-rows", type=int, default=6, help="rows of the C3 / C5 stand-in frames timed on the CPU oracle (6 rows spread over the frame at full spp: 10-20 s each on 16 cores)")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-other", action="store_true", help="skip the C3/C5 stand-ins, the C4 frame and the scaling probe (N = 1 only)")
-    ap.add_argument("--no-oneshot", action="store_true", help="skip the one-shot call's wall time (profiling runs: keeps the launch count per step)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: CPU baseline, roofline, one-shot call, two-pipeline schedule, "
+                         "other configurations and scaling probe (N = 1 only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the frame of the last timed step to DIR/frame_rgb8.npy (float32)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-other", action="store_true", help="with --full: skip the C3/C5 stand-ins, the C4 frame and the scaling probe (N = 1 only)")
+    ap.add_argument("--no-oneshot", action="store_true", help="with --full: skip the one-shot call's wall time (profiling runs: keeps the launch count per step)")
     ap.add_argument("--force-dist", action="store_true", help="initialise RCCL and gather even with one rank (self-test)")
     ap.add_argument("--backend", choices=["nccl", "gloo"], default="nccl", help="nccl = RCCL over xGMI (the product path); gloo only for plumbing tests")
     ap.add_argument("--oversubscribe", action="store_true",
@@ -300,6 +332,8 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be positive")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be positive and --warmup not negative")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args))
 
@@ -308,12 +342,13 @@ def main():
         print(f"bench.py: --gpus {args.gpus} but WORLD_SIZE={world_env}: the launcher and the flag disagree", file=sys.stderr)
         sys.exit(2)
     single = world_env == 1 and not args.force_dist          # CPU baseline, roofline and the other configurations are N = 1 figures
+    full = single and args.full                              # everything but the headline: --full only
     cw, ch, cspp = CONFIGS[args.config]
     w, h, base_spp = args.width or cw, args.height or ch, args.spp or cspp
     cpu = cnt = None
-    with_other = single and not args.no_other and args.config == "c2" and not (args.width or args.height or args.spp)
+    with_other = full and not args.no_other and args.config == "c2" and not (args.width or args.height or args.spp)
     other_text, other_cpu = {}, {}
-    if not args.no_cpu and single:
+    if full and not args.no_cpu:
         # The CPU legs run FIRST, before anything touches the GPU: they are ~10 s of host work each, and with them out of the way
         # the GPU phase of the run is one contiguous block that an outside utilisation sampler can see.
         cpu, cnt = cpu_baseline(w, h, base_spp, args.cpu_rows)
@@ -353,7 +388,7 @@ def main():
     bih = sqt.BIH(sqt.Mesh.from_obj(os.path.join(data, "scene.obj"), data))
     cam = sqt.load_camera(os.path.join(data, "camera"))
     scene = sqt.DeviceScene(bih, local_rank)                 # resident in HBM before the timed region
-    scene.enable_timing()                                    # hipEvents around every sq_trace_rays launch, on its stream
+    scene.enable_timing()                                    # hipEvents around every sq_trace_rays launch, on its stream (in every run, so that the timed steps stay the same with and without --full)
     spp = base_spp * world if args.scaling == "weak" else base_spp
     events = [] if use_dist else None
 
@@ -396,6 +431,8 @@ def main():
     value = samples_per_step * args.steps / elapsed / 1e6
 
     if rank == 0:
+        if args.dump_outputs:
+            dump_frame(args.dump_outputs, frame)
         out = {
             "metric": "Msamples/s (whole node) at 1080p/256spp on data/scene.obj",
             "value": round(value, 2), "unit": "Msamples/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -417,7 +454,7 @@ def main():
                             "per_rank_ms": [min(rms), max(rms)], "gather_ms": [min(gms), max(gms)],
                             "what": "per frame, from events on each rank's stream: its own rows rendered (per_rank_ms) and the "
                                     "all_gather + de-interleave that follows (gather_ms; includes waiting for the slowest rank); [min, max] over ranks"}
-        if single and not args.no_oneshot and args.config == "c2" and not (args.width or args.height or args.spp):
+        if full and not args.no_oneshot and args.config == "c2" and not (args.width or args.height or args.spp):
             # SURVEY 8(d) asks for the rate with the scene upload included as well: the one-shot drop-in call
             # (upload + workspace + render + copy back over PCIe), second call timed.  Reported beside `value`, never as it.
             sqt.render_rgb8(bih, cam, spp, (w, h))
@@ -426,7 +463,7 @@ def main():
             dt = time.perf_counter() - t1
             out["one_shot_call"] = {"ms": round(dt * 1e3, 2), "msamples_per_s": round(samples_per_step / dt / 1e6, 1),
                                     "what": "sq_render_rgb8: scene upload + render + 6.2 MB copy back, host buffers in and out"}
-        if single and with_other and not args.no_oneshot and args.config == "c2" and not (args.width or args.height or args.spp):
+        if with_other and not args.no_oneshot:
             # (not in --no-other runs: those are the profiling commands, whose per-kernel averages must stay those of the serial schedule)
             # The same frames with the library's two-pipeline schedule (option overlap = 2: even and odd sample batches on two
             # streams, one pipeline's launches filling the other's ramp-downs and per-sample kernels).  Same image bit for bit.
@@ -449,7 +486,7 @@ def main():
                 scene.set_option("overlap", 0)
         if cpu is not None:
             out["cpu_baseline"] = cpu
-        if single and launches:
+        if full and launches:
             # Roofline of the dominant kernel, sq_trace_rays.  The 0.3 MB scene lives in LDS, so HBM is not what binds it
             # (measured traffic is ~2 % of the HBM peak); the resource that binds is the VALU pipe.  VALU wave-instructions by class,
             # active cycles and thread cycles come from separate rocprofv3 --pmc passes of this same command on THIS build

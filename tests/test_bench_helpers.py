@@ -1,4 +1,4 @@
-"""bench.py's pure helpers (no GPU): the class-priced VALU figure, the staleness check of counter files, the build id."""
+"""bench.py's pure helpers (no GPU): the class-priced VALU figure, the staleness check of counter files, the build id, the output dump."""
 import importlib
 import importlib.util
 import json
@@ -53,3 +53,27 @@ def test_build_id_is_the_hash_of_the_sources_and_is_in_the_library():
     spec.loader.exec_module(bm)
     assert sqt.build_id() == bm.source_id() and not bm.stale()                     # the in-tree library is built from the sources that are here
     assert bm.source_id(("-DX=1",)) != bm.source_id()                              # a variant build has another identity
+
+
+def test_dump_frame_writes_the_frame_as_float32_within_the_budget(tmp_path):
+    """--dump-outputs: a frame that fits is written whole; a larger one as the same seeded sample of its pixels in every run."""
+    import numpy as np
+    import torch
+    b = _bench()
+    g = np.random.default_rng(7)
+    small = torch.from_numpy(g.integers(0, 256, (40, 72, 3), dtype=np.uint8))
+    b.dump_frame(str(tmp_path), small)
+    got = np.load(tmp_path / "frame_rgb8.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, small.numpy().astype(np.float32))
+    assert not (tmp_path / "frame_rgb8_pixels.npy").exists()
+    big = torch.from_numpy(g.integers(0, 256, (2400, 2400, 3), dtype=np.uint8))    # 69 MB as float32
+    for d in ("a", "b"):
+        b.dump_frame(str(tmp_path / d), big)
+    rgb, pix = np.load(tmp_path / "a" / "frame_rgb8.npy"), np.load(tmp_path / "a" / "frame_rgb8_pixels.npy")
+    assert rgb.dtype == np.float32 and pix.dtype == np.float64
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= 64 << 20
+    assert np.array_equal(rgb, big.numpy().reshape(-1, 3)[pix.astype(np.int64)].astype(np.float32))
+    assert np.array_equal(pix, np.load(tmp_path / "b" / "frame_rgb8_pixels.npy"))
+    assert len(np.unique(pix)) == len(pix) == b.DUMP_SAMPLE_PIXELS
+    b.dump_frame(str(tmp_path / "a"), small)                                         # a smaller frame into the same directory
+    assert not (tmp_path / "a" / "frame_rgb8_pixels.npy").exists()

@@ -560,7 +560,7 @@ def test_bench_launches_its_own_ranks(sqt):
     import json
     import subprocess
     import sys
-    common = ["--steps", "1", "--warmup", "1", "--no-cpu", "--no-other", "--width", "96", "--height", "64", "--spp", "8"]
+    common = ["--steps", "1", "--warmup", "1", "--full", "--no-cpu", "--no-other", "--width", "96", "--height", "64", "--spp", "8"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     one = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1"] + common, env=env,
                          stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
@@ -591,6 +591,27 @@ def test_bench_launches_its_own_ranks(sqt):
     assert j1["n_gpus"] == 1 and j2["n_gpus"] == 2 and j2["scaling"] == "strong" and "not_a_measurement" in j2
     assert j2["config"]["samples_per_step"] == j1["config"]["samples_per_step"] == 96 * 64 * 8      # the SAME frame, shared
     assert j2["config"]["nonblack_pixels"] == j1["config"]["nonblack_pixels"] > 0                   # and the same image
+
+
+def test_plain_bench_times_the_steps_and_dumps_the_last_frame(sqt, tmp_path):
+    """A plain `python bench.py` run: the headline line only (nothing of --full), `--steps` timed steps, and --dump-outputs
+    writes the frame of the timed path, which is the golden image of the same frame."""
+    import subprocess
+    import sys
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--width", "64", "--height", "64", "--spp", "4", "--dump-outputs", str(tmp_path)],
+                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-2000:]
+    j = json.loads(p.stdout.strip().splitlines()[-1])
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in j, key
+    assert j["steps"] == 3 and j["warmup"] == 1 and j["ms_per_step"] > 0
+    assert abs(j["value"] - j["config"]["samples_per_step"] / j["ms_per_step"] / 1e3) <= 0.02 * j["value"] + 0.01
+    for key in ("roofline", "cpu_baseline", "one_shot_call", "overlapped_schedule", "other_configs"):
+        assert key not in j, key
+    got = np.load(tmp_path / "frame_rgb8.npy")
+    assert got.dtype == np.float32 and not (tmp_path / "frame_rgb8_pixels.npy").exists()
+    assert np.array_equal(got, np.load(os.path.join(GOLDEN, "scene_64x64_4spp_rgb8.npy")).astype(np.float32))
 
 
 def test_culling_slab_test_on_the_device_is_the_one_the_lemma_is_about(sqt):

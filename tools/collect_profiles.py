@@ -56,7 +56,7 @@ def trace_sum(tots, counter):
 
 
 if "headline" in what:
-    bench = ["python", "bench.py", "--no-other"]
+    bench = ["python", "bench.py", "--full", "--no-other"]
     d = os.path.join(OUT, "trace")
     shutil.rmtree(d, ignore_errors=True)
     rc = subprocess.call(["timeout", "-k", "10", "500", "rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "--"] +
@@ -69,8 +69,8 @@ if "headline" in what:
     tots = [pmc("h_sqa", SQ_A, one), pmc("h_sqb", SQ_B, one), pmc("h_tcc", TCC, one), pmc("h_fetch", "FETCH_SIZE", one), pmc("h_write", "WRITE_SIZE", one),
             pmc("h_mixa", MIX_A, one), pmc("h_mixb", MIX_B, one)]
     write_summary(os.path.join(OUT, "pmc_headline.txt"),
-                  "# rocprofv3 --pmc <one group per pass> -- python bench.py --no-other --no-cpu --no-oneshot --steps 1 --warmup 0 ; every sq_ kernel of ONE headline frame", tots)
-    res = {"command": "python bench.py --no-other --no-cpu --no-oneshot --steps 1 --warmup 0", "workload": [1920, 1080, 256], "build_id": BUILD_ID,
+                  "# rocprofv3 --pmc <one group per pass> -- python bench.py --full --no-other --no-cpu --no-oneshot --steps 1 --warmup 0 ; every sq_ kernel of ONE headline frame", tots)
+    res = {"command": "python bench.py --full --no-other --no-cpu --no-oneshot --steps 1 --warmup 0", "workload": [1920, 1080, 256], "build_id": BUILD_ID,
            "what": "sq_trace_rays, sums over the launches of ONE frame (1920x1080 @ 256 spp); one rocprofv3 --pmc pass per counter group"}
     for c in SQ_A.split() + SQ_B.split() + MIX_A.split() + MIX_B.split():
         v, n = trace_sum(tots, c)

@@ -7,11 +7,11 @@ OUT=$GRAFT_REPO_ROOT/gpurun_out/profiles_$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python bench.py --steps 3 --warmup 1 > $OUT/bench_under_trace.log 2>&1
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python bench.py --full --steps 3 --warmup 1 > $OUT/bench_under_trace.log 2>&1
 echo "trace rc=$?"
 cp $OUT/trace/*/*kernel_stats.csv $OUT/kernel_stats.csv
 for C in FETCH_SIZE WRITE_SIZE; do
-  timeout -k 10 400 rocprofv3 --pmc $C --kernel-include-regex "sq_" --output-format csv -d $OUT/pmc_$C -- python bench.py --steps 1 --warmup 0 --no-cpu > $OUT/pmc_$C.log 2>&1
+  timeout -k 10 400 rocprofv3 --pmc $C --kernel-include-regex "sq_" --output-format csv -d $OUT/pmc_$C -- python bench.py --full --steps 1 --warmup 0 --no-cpu > $OUT/pmc_$C.log 2>&1
   echo "pmc $C rc=$?"
 done
 python - <<PY

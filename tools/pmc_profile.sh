@@ -14,7 +14,7 @@ for CTRS in "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST
             "GRBM_GUI_ACTIVE TCC_HIT_sum TCC_MISS_sum TCP_TOTAL_CACHE_ACCESSES_sum TCP_TCC_READ_REQ_sum" \
             "FETCH_SIZE" "WRITE_SIZE"; do
   i=$((i+1))
-  timeout -k 10 300 rocprofv3 --pmc $CTRS --kernel-include-regex "sq_" --output-format csv -d $OUT/pass$i -- python bench.py --no-cpu "$@" > $OUT/pass$i.log 2>&1
+  timeout -k 10 300 rocprofv3 --pmc $CTRS --kernel-include-regex "sq_" --output-format csv -d $OUT/pass$i -- python bench.py --full --no-cpu "$@" > $OUT/pass$i.log 2>&1
   echo "pass $i ($CTRS) rc=$?"
 done
 python - <<PY

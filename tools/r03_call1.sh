@@ -8,7 +8,7 @@ export TMPDIR=/tmp
 O=gpurun_out
 mkdir -p $O
 echo "== pytest -m gpu"; ( time timeout -k 10 900 python -m pytest tests -m gpu -x -q ) > $O/r03a_pytest.log 2>&1; rc=$?; tail -3 $O/r03a_pytest.log; [ $rc -ne 0 ] && exit $rc
-echo "== bench"; timeout -k 10 600 python bench.py --steps 5 --warmup 2 > $O/r03a_bench.json 2> $O/r03a_bench.err; rc=$?; echo "rc=$rc"; cut -c1-400 $O/r03a_bench.json; [ $rc -ne 0 ] && exit $rc
+echo "== bench"; timeout -k 10 600 python bench.py --full --steps 5 --warmup 2 > $O/r03a_bench.json 2> $O/r03a_bench.err; rc=$?; echo "rc=$rc"; cut -c1-400 $O/r03a_bench.json; [ $rc -ne 0 ] && exit $rc
 echo "== op_rate"; timeout -k 10 120 tools/ubench/op_rate > $O/r03a_op_rate.txt 2>&1; echo "rc=$?"; tail -5 $O/r03a_op_rate.txt
 echo "== streaming variants"
 for scene in blob6 hf708; do for i in 1 2; do
