@@ -98,6 +98,22 @@ int32_t sq_shard_global_row(int32_t local_row, sq_shard sh);
 int sq_render_rows_device(sq_device_scene* s, const sq_camera* cam, int32_t samples, int32_t w, int32_t h,
                           int32_t cast, sq_shard sh, float* d_avg, uint8_t* d_rgb, void* hip_stream);
 
+/* Progressive rendering: the samples [k_begin, k_end) of the `samples`-sample frame.  Seeds come from `samples` exactly as in
+ * a whole-frame render (src/Lib.hs:85), and a pixel's value is a left fold over its samples in order (src/Lib.hs:88), so a
+ * frame rendered in consecutive ranges [0, k1) [k1, k2) ... [kn, samples) is bit for bit the frame of one call.
+ *  d_sum : required; a DEVICE buffer of rows*h*3 floats laid out like d_avg.  On entry it holds the per-pixel fold over the
+ *          samples [0, k_begin), as an earlier call left it (ignored when k_begin == 0); on return the fold over [0, k_end).
+ *          A pixel whose primary ray misses gets +0 sums (the fold of black samples).
+ *  d_avg / d_rgb : optional (either or both may be NULL); they receive (1 / (float)k_end) *^ sum and its tonemap.  With
+ *          k_end == samples this is bit for bit what sq_render_rows_device writes for the same arguments.
+ * Refused with an error code before anything is enqueued (every buffer left as it was): k_begin < 0, k_end <= k_begin,
+ * k_end > samples, d_sum == NULL, d_sum == d_avg, and every refusal of sq_render_rows_device (bad shard, the LDS-height
+ * limits, ...).  Like sq_render_rows_device the call only enqueues work on hip_stream; the calls of one frame must be
+ * ordered by the caller (one stream).  sq_render_rows_device is the case [0, samples) without d_sum. */
+int sq_render_rows_device_range(sq_device_scene* s, const sq_camera* cam, int32_t samples, int32_t w, int32_t h,
+                                int32_t cast, sq_shard sh, int32_t k_begin, int32_t k_end,
+                                float* d_sum, float* d_avg, uint8_t* d_rgb, void* hip_stream);
+
 /* Timing of the dominant kernel measured with hipEvents on the stream it was launched on:
  * average duration in ms over the launches since the last reset, and the launch count. */
 int  sq_kernel_timing(sq_device_scene* s, double* avg_ms, int64_t* launches, const char** kernel_name);

@@ -10,7 +10,7 @@ import os
 import sys
 import time
 
-from . import BIH, Mesh, Settings, lib, load_camera, render
+from . import BIH, Mesh, Settings, lib, load_camera, render, render_progressive, write_png
 
 
 def parse_dimensions(text):
@@ -19,6 +19,16 @@ def parse_dimensions(text):
     except ValueError:
         raise argparse.ArgumentTypeError("expected W,H")
     return (w, h)
+
+
+def positive_int(text):
+    try:
+        v = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError("expected a positive integer")
+    if v < 1:
+        raise argparse.ArgumentTypeError("expected a positive integer")
+    return v
 
 
 def build_parser():
@@ -33,6 +43,9 @@ def build_parser():
     p.add_argument("--debug", action="store_true", help="Run in debug mode")
     p.add_argument("--debugpath", default="", help="File to write debug info to")
     p.add_argument("--cast", action="store_true", help="Raycast instead of raytracing (i.e. don't bounce rays)")
+    # not a flag of the reference: progressive previews (the final image is the same bytes as without it)
+    p.add_argument("--preview-every", type=positive_int, default=None, metavar="K",
+                   help="Overwrite the savepath with a preview after every K samples (default: no previews)")
     return p
 
 
@@ -67,7 +80,12 @@ def main(argv=None):
     t0 = time.time()
     print("Started at " + time.strftime("%H:%M:%S%p UTC", time.gmtime(t0)).lower().replace("utc", "UTC"))
     os.makedirs(os.path.dirname(os.path.abspath(settings.savePath)), exist_ok=True)
-    render(bih, cam, settings)
+    if a.preview_every is None:
+        render(bih, cam, settings)
+    else:
+        for done, img in render_progressive(bih, cam, settings.samples, settings.dimensions, a.preview_every, settings.cast):
+            write_png(settings.savePath, img)
+            print(f"Preview: {done}/{settings.samples} samples written to {settings.savePath}")
     t1 = time.time()
     print("Finished at " + time.strftime("%H:%M:%S%p UTC", time.gmtime(t1)).lower().replace("utc", "UTC"))
     print(f"Took {t1 - t0:.6f}s")

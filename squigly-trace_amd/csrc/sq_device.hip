@@ -96,6 +96,11 @@ struct Frame {
     int32_t row_block, shard, n_shards, local_rows;
     int32_t tile_rows, tiles_x;   // primary rays are enumerated in tiles of tile_rows x (64 / tile_rows) pixels (primary_tile), tiles_x per tile row
     float* out_avg; uint8_t* out_rgb;
+    // the samples [k_begin, k_end) of the frame this call renders (a whole frame: [0, samples)); `sum`: the caller's per-pixel fold
+    // (sq_render_rows_device_range, 3 floats per local pixel), read where the fold starts when k_begin > 0 and written where it
+    // ends; nullptr = the fold lives in the workspace only
+    int32_t k_begin, k_end;
+    float* sum;
     int32_t diag;             // option "coresidency": the per-sample kernels and the trace kernel count who runs beside whom (sq_get_stats 24..27)
 };
 __device__ __forceinline__ void pixel_coords(const Frame& F, int pix, int& y, int& x) {   // 32-bit: cheap div/mod
@@ -126,6 +131,18 @@ __device__ __forceinline__ void pixel_coords(const Frame& F, long long pix, int&
     y = (blk * F.n_shards + F.shard) * F.row_block + (j - blk * F.row_block);
 }
 
+// Where a pixel's fold starts: +0 on a fresh frame, else what the caller's earlier range call left in F.sum (src/Lib.hs:88 is a left
+// fold, so resuming it from its exact fp32 partial sum gives the bits of one uninterrupted fold).
+__device__ __forceinline__ f3 fold_start(const Frame& F, long long pix) {
+    if (F.k_begin == 0) return sq::mk(0, 0, 0);
+    const float* p = F.sum + pix * 3;
+    return sq::mk(p[0], p[1], p[2]);
+}
+// A pixel whose primary ray misses folds black samples: its sum is +0 whatever range is rendered.
+__device__ __forceinline__ void store_miss_sum(const Frame& F, long long pix) {
+    if (F.sum) { float* p = F.sum + pix * 3; p[0] = 0.0f; p[1] = 0.0f; p[2] = 0.0f; }
+}
+
 // ----------------------------------------------------------------------------------------------
 // Variant 1: one lane per pixel, everything in one kernel (cross-check variant; also raycast mode)
 // ----------------------------------------------------------------------------------------------
@@ -143,6 +160,7 @@ __global__ void __launch_bounds__(kBlock) sq_render_pixels(const SceneView S, co
     f3 sum = sq::mk(0, 0, 0);                                           // sum = foldl (+) 0
     const Hit h0 = trace_one(S, N, o0, d0, stk, kBlock);
     if (h0.tri >= 0) {
+        sum = fold_start(F, pix);
         const Surface s0 = surface_of(S, h0.tri);
         const f3 p0 = o0 + sq::scale(h0.t, d0);
         if (F.cast) {                                                   // raycast, src/Lib.hs:141-151
@@ -151,11 +169,11 @@ __global__ void __launch_bounds__(kBlock) sq_render_pixels(const SceneView S, co
             const Hit sh = trace_one(S, N, p0, light - p0, stk, kBlock);
             f3 c = sq::mk(0, 0, 0);
             if (!(sh.tri >= 0 && !(hit_dist(p0, light - p0, sh.t) > dl))) c = sq::scale(2 / dl, s0.surf);
-            for (int k = 0; k < n; ++k) sum = sum + c;
+            for (int k = F.k_begin; k < F.k_end; ++k) sum = sum + c;
         } else {
             const long long rix = (long long)n * ((long long)x + (long long)y * (long long)F.w);   // src/Lib.hs:85
 #pragma unroll 1
-            for (int k = 0; k < n; ++k) {                               // raytrace gen scene ray 0, src/Lib.hs:127-137
+            for (int k = F.k_begin; k < F.k_end; ++k) {                 // raytrace gen scene ray 0, src/Lib.hs:127-137
                 uint32_t n0, n1, n2;
                 sq::tfgen3(rix + k, n0, n1, n2);
                 f3 L1 = sq::mk(0, 0, 0);
@@ -174,7 +192,8 @@ __global__ void __launch_bounds__(kBlock) sq_render_pixels(const SceneView S, co
             }
         }
     }
-    const f3 avg = sq::scale(1 / (float)n, sum);                        // src/Lib.hs:88
+    if (F.sum) { float* o = F.sum + pix * 3; o[0] = sum.x; o[1] = sum.y; o[2] = sum.z; }
+    const f3 avg = sq::scale(1 / (float)F.k_end, sum);                  // src/Lib.hs:88
     if (F.out_avg) { float* o = F.out_avg + pix * 3; o[0] = avg.x; o[1] = avg.y; o[2] = avg.z; }
     if (F.out_rgb) tonemap(avg, F.out_rgb + pix * 3);
 }
@@ -255,8 +274,9 @@ __global__ void __launch_bounds__(kBlock) sq_primary(const SceneView S, const Fr
     const int a = wave_append(W.n_active, in && h0.tri >= 0);
     if (a >= 0) {
         W.px_pixel[a] = (int32_t)pix; W.px_t0[a] = h0.t; W.px_tri0[a] = h0.tri;
-        W.px_sum[3 * a] = 0.0f; W.px_sum[3 * a + 1] = 0.0f; W.px_sum[3 * a + 2] = 0.0f;
-    }
+        const f3 s0 = fold_start(F, pix);
+        W.px_sum[3 * a] = s0.x; W.px_sum[3 * a + 1] = s0.y; W.px_sum[3 * a + 2] = s0.z;
+    } else if (in) store_miss_sum(F, pix);
 }
 
 struct Pixel0 { f3 p0, d0; Surface s0; int y, x; };
@@ -357,7 +377,7 @@ __global__ void __launch_bounds__(kBlock) sq_primary_gen(const Frame F, const Wo
         W.dir[pix] = make_float4(d.x, d.y, d.z, 0.0f);
     }
 }
-__global__ void __launch_bounds__(kBlock) sq_primary_store(const Work W, long long total) {
+__global__ void __launch_bounds__(kBlock) sq_primary_store(const Frame F, const Work W, long long total) {
     for (long long base = (long long)blockIdx.x * kBlock; base < total; base += (long long)gridDim.x * kBlock) {   // whole waves stay together (ballot)
         const long long pix = base + threadIdx.x;
         const bool in = pix < total;
@@ -365,8 +385,9 @@ __global__ void __launch_bounds__(kBlock) sq_primary_store(const Work W, long lo
         const int a = wave_append(W.n_active, in && hit.y >= 0);
         if (a >= 0) {
             W.px_pixel[a] = (int32_t)pix; W.px_t0[a] = __int_as_float(hit.x); W.px_tri0[a] = hit.y;
-            W.px_sum[3 * a] = 0.0f; W.px_sum[3 * a + 1] = 0.0f; W.px_sum[3 * a + 2] = 0.0f;
-        }
+            const f3 s0 = fold_start(F, pix);
+            W.px_sum[3 * a] = s0.x; W.px_sum[3 * a + 1] = s0.y; W.px_sum[3 * a + 2] = s0.z;
+        } else if (in) store_miss_sum(F, pix);
     }
 }
 
@@ -463,7 +484,8 @@ __device__ __forceinline__ f3 shade2_radiance(const SceneView& S, const Work& W,
     return s0.surf * L1 + s0.emit;
 }
 
-// sum outcomes, in sample order (src/Lib.hs:88); on the last batch: avg, tonemap, store.
+// sum outcomes, in sample order (src/Lib.hs:88); on the call's last batch: the fold to F.sum (range calls), avg over the k_end
+// samples folded so far, tonemap, store.
 // GROUPED: see the comment in the loop; two kernels because the grouped loop's registers cost the plain one a third of its waves.
 template <bool GROUPED>
 __global__ void __launch_bounds__(kBlock) sq_accumulate(const SceneView S, const Frame F, const Work W, int k_count, int last) {
@@ -507,8 +529,9 @@ __global__ void __launch_bounds__(kBlock) sq_accumulate(const SceneView S, const
             }
         }
         if (!last) { W.px_sum[3 * a] = sum.x; W.px_sum[3 * a + 1] = sum.y; W.px_sum[3 * a + 2] = sum.z; continue; }
-        const f3 avg = sq::scale(1 / (float)F.samples, sum);
         const long long pix = W.px_pixel[a];
+        if (F.sum) { float* o = F.sum + pix * 3; o[0] = sum.x; o[1] = sum.y; o[2] = sum.z; }
+        const f3 avg = sq::scale(1 / (float)F.k_end, sum);
         if (F.out_avg) { float* o = F.out_avg + pix * 3; o[0] = avg.x; o[1] = avg.y; o[2] = avg.z; }
         if (F.out_rgb) tonemap(avg, F.out_rgb + pix * 3);
     }
@@ -647,8 +670,9 @@ __global__ void __launch_bounds__(kResidentBlock) sq_primary_resident(const Scen
         const int a = wave_append(W.n_active, in && h0.tri >= 0);
         if (a >= 0) {
             W.px_pixel[a] = (int32_t)pix; W.px_t0[a] = h0.t; W.px_tri0[a] = h0.tri;
-            W.px_sum[3 * a] = 0.0f; W.px_sum[3 * a + 1] = 0.0f; W.px_sum[3 * a + 2] = 0.0f;
-        }
+            const f3 s0 = fold_start(F, pix);
+            W.px_sum[3 * a] = s0.x; W.px_sum[3 * a + 1] = s0.y; W.px_sum[3 * a + 2] = s0.z;
+        } else if (in) store_miss_sum(F, pix);
     }
 }
 
@@ -1585,8 +1609,9 @@ int launch_frame(sq_device_scene* s, const Frame& F, hipStream_t stream) {
         return timed([&] { hipLaunchKernelGGL(sq_render_pixels<StackT>, dim3((unsigned)px_blocks), dim3(kBlock), px_lds, stream, S, F); }, "sq_render_pixels", stream);
     }
     // ---- wavefront pipeline ----
-    // at least one sample of every pixel per batch, never more slots than the frame has samples
-    const int64_t slots = std::max<int64_t>(pixels, std::min<int64_t>(s->opt_slots, (int64_t)pixels * F.samples));
+    const int n_call = F.k_end - F.k_begin;                              // the samples this call renders (a whole frame: F.samples)
+    // at least one sample of every pixel per batch, never more slots than the call has samples
+    const int64_t slots = std::max<int64_t>(pixels, std::min<int64_t>(s->opt_slots, (int64_t)pixels * n_call));
     if (ensure_workspace(s, pixels, slots)) return 1;
     const Work& W = s->work;
     const int64_t have_slots = W.slot_capacity;
@@ -1596,7 +1621,7 @@ int launch_frame(sq_device_scene* s, const Frame& F, hipStream_t stream) {
     // Opt-in (sq_set_option "overlap"): measured +3 % on the headline frame (105.5 -> 102.3 ms) -- the kernels do
     // run side by side, but the chip is VALU-bound as a whole, so each slows the other down by what it gains;
     // and trace-launch durations then include that interference, which blurs the per-kernel roofline figure.
-    const bool overlap = s->opt_overlap && F.samples >= 2 && have_slots >= 2 * pixels;
+    const bool overlap = s->opt_overlap && n_call >= 2 && have_slots >= 2 * pixels;
     const int tracks = overlap ? 2 : 1;
     const int64_t track_slots = have_slots / tracks;
     Work Wt[2] = { W, W };
@@ -1607,12 +1632,9 @@ int launch_frame(sq_device_scene* s, const Frame& F, hipStream_t stream) {
     }
     // samples per batch: as many as a track holds, split evenly (few large launches: a small trace launch
     // wastes its ramp-up and drain, and the second-bounce launches only carry a few percent of the slots)
-    const int max_batch = (int)std::max<int64_t>(1, std::min<int64_t>(F.samples, track_slots / pixels));
-    const int n_batches = std::max(tracks, (F.samples + max_batch - 1) / max_batch);
-    const int batch = (F.samples + n_batches - 1) / n_batches;
-    if (F.out_avg) SQ_HIP(hipMemsetAsync(F.out_avg, 0, (size_t)pixels * 3 * sizeof(float), stream));   // pixels whose primary ray misses: black
-    if (F.out_rgb) SQ_HIP(hipMemsetAsync(F.out_rgb, 0, (size_t)pixels * 3, stream));
-    SQ_HIP(hipMemsetAsync(W.n_active, 0, 128 * sizeof(int32_t), stream));
+    const int max_batch = (int)std::max<int64_t>(1, std::min<int64_t>(n_call, track_slots / pixels));
+    const int n_batches = std::max(tracks, (n_call + max_batch - 1) / max_batch);
+    const int batch = (n_call + n_batches - 1) / n_batches;
     // persistent trace kernel geometry.  Resident form: the whole scene (branches, leaves, unique vertices,
     // 16-bit indexed triangles) plus every lane's stack fits in the 160 KB of one CU -> one 1024-thread
     // workgroup per CU, no global traffic except ray fetch and hit store.  Streaming form otherwise.
@@ -1680,6 +1702,10 @@ int launch_frame(sq_device_scene* s, const Frame& F, hipStream_t stream) {
         static_lds_checked = true;
     }
     P.launched = 1;                                                    // planned; what follows fails only on HIP errors
+    // nothing is enqueued before this point, so a refusal above leaves every buffer as it was
+    if (F.out_avg) SQ_HIP(hipMemsetAsync(F.out_avg, 0, (size_t)pixels * 3 * sizeof(float), stream));   // pixels whose primary ray misses: black
+    if (F.out_rgb) SQ_HIP(hipMemsetAsync(F.out_rgb, 0, (size_t)pixels * 3, stream));
+    SQ_HIP(hipMemsetAsync(W.n_active, 0, 128 * sizeof(int32_t), stream));
     // primary rays: once per pixel.  With a resident scene they are traced out of LDS as well.
     const bool primary_pooled = s->opt_primary_pooled && pool;          // ... or through the pooled trace kernel, below
     if (primary_pooled) {
@@ -1735,7 +1761,7 @@ int launch_frame(sq_device_scene* s, const Frame& F, hipStream_t stream) {
         hipLaunchKernelGGL(sq_primary_gen, dim3(aux_blocks), dim3(kBlock), 0, stream, F, W, pixels);
         SQ_HIP(hipGetLastError());
         if (launch_trace(Wp, 1, 0, stream)) return 1;
-        hipLaunchKernelGGL(sq_primary_store, dim3(aux_blocks), dim3(kBlock), 0, stream, W, pixels);
+        hipLaunchKernelGGL(sq_primary_store, dim3(aux_blocks), dim3(kBlock), 0, stream, F, W, pixels);
         SQ_HIP(hipGetLastError());
     }
     // once per frame: the depth-0 mirror ray of every active pixel (reused by every sample that mirrors).  In the plain
@@ -1750,8 +1776,9 @@ int launch_frame(sq_device_scene* s, const Frame& F, hipStream_t stream) {
         hipLaunchKernelGGL(sq_mirror1_store, dim3(aux_blocks), dim3(kBlock), 0, stream, W, 0ll);
         SQ_HIP(hipGetLastError());
     }
-    auto k0_of = [&](int i) { return i * batch; };
-    auto kc_of = [&](int i) { return std::max(0, std::min(batch, F.samples - i * batch)); };
+    // batch i holds the samples [k0_of(i), k0_of(i) + kc_of(i)) of [k_begin, k_end); the call's last batch ends the fold (sq_accumulate)
+    auto k0_of = [&](int i) { return F.k_begin + i * batch; };
+    auto kc_of = [&](int i) { return std::max(0, std::min(batch, n_call - i * batch)); };
     int n_real = 0;
     while (n_real < n_batches && kc_of(n_real) > 0) ++n_real;
     if (!overlap) {
@@ -1768,7 +1795,7 @@ int launch_frame(sq_device_scene* s, const Frame& F, hipStream_t stream) {
                 if (level == 0) hipLaunchKernelGGL(sq_shade1, pp_grid(kc), dim3(kBlock), 0, stream, S, F, W, kc);
                 SQ_HIP(hipGetLastError());
             }
-            SQ_LAUNCH_ACCUMULATE( dim3(aux_blocks), dim3(kBlock), 0, stream, S, F, W, kc, (k0 + kc >= F.samples) ? 1 : 0);
+            SQ_LAUNCH_ACCUMULATE( dim3(aux_blocks), dim3(kBlock), 0, stream, S, F, W, kc, (k0 + kc >= F.k_end) ? 1 : 0);
             SQ_HIP(hipGetLastError());
         }
         return 0;
@@ -1877,14 +1904,17 @@ int launch_frame(sq_device_scene* s, const Frame& F, hipStream_t stream) {
 
 }  // namespace
 
-extern "C" int sq_render_rows_device(sq_device_scene* s, const sq_camera* cam, int32_t samples, int32_t w, int32_t h,
-                                     int32_t cast, sq_shard sh, float* d_avg, uint8_t* d_rgb, void* hip_stream) {
+namespace {
+// Both render entry points: the samples [k_begin, k_end) of the `samples`-sample frame.  d_sum = nullptr (sq_render_rows_device) keeps
+// the fold in the workspace; the caller has checked everything that is specific to its own entry point.
+int render_rows(sq_device_scene* s, const sq_camera* cam, int32_t samples, int32_t w, int32_t h, int32_t cast, sq_shard sh,
+                int32_t k_begin, int32_t k_end, float* d_sum, float* d_avg, uint8_t* d_rgb, void* hip_stream) {
     if (!s || !cam) return sq_set_error("null argument");
     if (samples < 1 || w < 1 || h < 1) return sq_set_error("samples, width and height must be positive (got %d, %d, %d)", samples, w, h);
     const int32_t rows = sq_shard_rows(w, sh);
     if (rows < 0) return sq_set_error("bad shard {row_block=%d, shard=%d, n_shards=%d}", sh.row_block, sh.shard, sh.n_shards);
     if (rows == 0) return 0;                    // an empty shard (more shards than row blocks) has nothing to render
-    if (!d_avg && !d_rgb) return sq_set_error("no output buffer");
+    if (!d_avg && !d_rgb && !d_sum) return sq_set_error("no output buffer");
     SQ_HIP(hipSetDevice(s->device));
     Frame F{};
     std::memcpy(F.cam_pos, cam->pos, sizeof F.cam_pos);
@@ -1899,9 +1929,26 @@ extern "C" int sq_render_rows_device(sq_device_scene* s, const sq_camera* cam, i
         F.tiles_x = (h + tw - 1) / tw;
     }
     F.out_avg = d_avg; F.out_rgb = d_rgb;
+    F.k_begin = k_begin; F.k_end = k_end; F.sum = d_sum;
     F.diag = s->opt_coresidency ? std::max(1, s->n_cu - 8) : 0;   // "beside" = while all but a handful of the CUs hold a live trace workgroup
     hipStream_t stream = (hipStream_t)hip_stream;
     return s->small_index ? launch_frame<uint16_t>(s, F, stream) : launch_frame<uint32_t>(s, F, stream);
+}
+}  // namespace
+
+extern "C" int sq_render_rows_device(sq_device_scene* s, const sq_camera* cam, int32_t samples, int32_t w, int32_t h,
+                                     int32_t cast, sq_shard sh, float* d_avg, uint8_t* d_rgb, void* hip_stream) {
+    return render_rows(s, cam, samples, w, h, cast, sh, 0, samples, nullptr, d_avg, d_rgb, hip_stream);
+}
+
+extern "C" int sq_render_rows_device_range(sq_device_scene* s, const sq_camera* cam, int32_t samples, int32_t w, int32_t h,
+                                           int32_t cast, sq_shard sh, int32_t k_begin, int32_t k_end,
+                                           float* d_sum, float* d_avg, uint8_t* d_rgb, void* hip_stream) {
+    if (k_begin < 0 || k_end <= k_begin || k_end > samples)
+        return sq_set_error("bad sample range [%d, %d) of a %d-sample frame (need 0 <= k_begin < k_end <= samples)", k_begin, k_end, samples);
+    if (!d_sum) return sq_set_error("d_sum is required: it carries the per-pixel fold from one range call to the next");
+    if ((void*)d_sum == (void*)d_avg) return sq_set_error("d_sum and d_avg must be different buffers");
+    return render_rows(s, cam, samples, w, h, cast, sh, k_begin, k_end, d_sum, d_avg, d_rgb, hip_stream);
 }
 
 extern "C" int sq_kernel_timing(sq_device_scene* s, double* avg_ms, int64_t* launches, const char** name) {

@@ -23,12 +23,9 @@ class DeviceScene:
     def set_option(self, key, value):
         N.check(N.lib().sq_set_option(self._h, key.encode(), int(value)))
 
-    def render_rows(self, cam, samples, w, h, cast=False, shard=(None, 0, 1), want_avg=True, want_rgb=True,
-                    stream=None, out_avg=None, out_rgb=None):
-        """Enqueue the render of this shard's rows; returns (avg, rgb) CUDA tensors [rows, h, 3].
-
-        shard = (row_block, shard_index, n_shards); row_block None = all rows in one block.
-        """
+    def _outputs(self, w, h, shard, want_avg, want_rgb, stream, out_avg, out_rgb):
+        """(sq_shard, rows, out_avg, out_rgb, stream) of a render_rows* call: the shard's row count, the output tensors
+        (allocated unless given or not wanted) and the stream (default: the device's current one)."""
         rb, si, ns = shard
         sh = N.Shard(int(w if rb is None else rb), int(si), int(ns))
         rows = N.lib().sq_shard_rows(w, sh)
@@ -40,8 +37,39 @@ class DeviceScene:
         if want_rgb and out_rgb is None:
             out_rgb = torch.empty((rows, h, 3), dtype=torch.uint8, device=dev)
         st = stream if stream is not None else torch.cuda.current_stream(dev)
+        return sh, rows, out_avg, out_rgb, st
+
+    def render_rows(self, cam, samples, w, h, cast=False, shard=(None, 0, 1), want_avg=True, want_rgb=True,
+                    stream=None, out_avg=None, out_rgb=None):
+        """Enqueue the render of this shard's rows; returns (avg, rgb) CUDA tensors [rows, h, 3].
+
+        shard = (row_block, shard_index, n_shards); row_block None = all rows in one block.
+        """
+        sh, _, out_avg, out_rgb, st = self._outputs(w, h, shard, want_avg, want_rgb, stream, out_avg, out_rgb)
         N.check(N.lib().sq_render_rows_device(
             self._h, C.byref(cam), samples, w, h, int(bool(cast)), sh,
+            out_avg.data_ptr() if out_avg is not None else None,
+            out_rgb.data_ptr() if out_rgb is not None else None,
+            C.c_void_p(st.cuda_stream)))
+        return out_avg, out_rgb
+
+    def render_rows_range(self, cam, samples, w, h, k_begin, k_end, sums, cast=False, shard=(None, 0, 1), want_avg=True,
+                          want_rgb=True, stream=None, out_avg=None, out_rgb=None):
+        """Enqueue the samples [k_begin, k_end) of the `samples`-sample frame (sq_render_rows_device_range); returns (avg, rgb)
+        of the k_end samples folded so far.
+
+        sums: float32 CUDA tensor [rows, h, 3] on this device, the per-pixel fold over [0, k_begin) on entry (ignored when
+        k_begin == 0) and over [0, k_end) once the stream gets there.
+        """
+        sh, rows, out_avg, out_rgb, st = self._outputs(w, h, shard, want_avg, want_rgb, stream, out_avg, out_rgb)
+        if sums is None:
+            raise N.SquiglyError("render_rows_range needs a sums tensor")
+        if (tuple(sums.shape) != (rows, h, 3) or sums.dtype != torch.float32 or not sums.is_contiguous()
+                or sums.device != torch.device("cuda", self.device)):
+            raise N.SquiglyError(f"sums must be a contiguous float32 tensor of shape {(rows, h, 3)} on cuda:{self.device}, "
+                                 f"got {sums.dtype} {tuple(sums.shape)} on {sums.device}")
+        N.check(N.lib().sq_render_rows_device_range(
+            self._h, C.byref(cam), samples, w, h, int(bool(cast)), sh, int(k_begin), int(k_end), sums.data_ptr(),
             out_avg.data_ptr() if out_avg is not None else None,
             out_rgb.data_ptr() if out_rgb is not None else None,
             C.c_void_p(st.cuda_stream)))
@@ -82,3 +110,61 @@ class DeviceScene:
         self._h = None
 
     __del__ = close
+
+
+class Progressive:
+    """A frame rendered a few samples at a time (DeviceScene.render_rows_range), bit-exact to one render_rows call.
+
+    Owns -- or adopts, to resume a checkpoint -- the [rows, h, 3] float32 fold `sums` and the count `done` of samples folded
+    into it.  `step(n)` renders the next min(n, samples - done) samples and returns the (avg, rgb) preview of the first
+    `done` samples; to checkpoint, copy `sums` and `done` away, and pass them back in to resume, in this process or another.
+    """
+
+    def __init__(self, dscene, cam, samples, w, h, cast=False, shard=(None, 0, 1), sums=None, done=0):
+        samples, done = int(samples), int(done)
+        if samples < 1:
+            raise ValueError(f"samples must be positive, got {samples}")
+        if not 0 <= done <= samples:
+            raise ValueError(f"done must be in [0, {samples}], got {done}")
+        rb, si, ns = shard
+        rows = N.lib().sq_shard_rows(w, N.Shard(int(w if rb is None else rb), int(si), int(ns)))
+        if rows < 0:
+            raise N.SquiglyError(f"bad shard {shard}")
+        dev = torch.device("cuda", dscene.device)
+        if sums is None:
+            if done:
+                raise ValueError("resuming (done > 0) needs the sums of the first `done` samples")
+            sums = torch.empty((rows, h, 3), dtype=torch.float32, device=dev)
+        else:   # adopts a matching CUDA tensor as it is; anything else (a host copy) is copied to the device
+            sums = torch.as_tensor(sums, dtype=torch.float32, device=dev).contiguous()
+            if tuple(sums.shape) != (rows, h, 3):
+                raise ValueError(f"sums must have shape {(rows, h, 3)}, got {tuple(sums.shape)}")
+        self.dscene, self.cam, self.samples, self.w, self.h = dscene, cam, samples, int(w), int(h)
+        self.cast, self.shard = bool(cast), shard
+        self._sums, self._done = sums, done
+
+    @property
+    def sums(self):
+        """The per-pixel fold over the first `done` samples (float32 CUDA tensor [rows, h, 3])."""
+        return self._sums
+
+    @property
+    def done(self):
+        """Samples folded into `sums` so far."""
+        return self._done
+
+    @property
+    def finished(self):
+        return self._done >= self.samples
+
+    def step(self, n, stream=None):
+        """Enqueue the next min(n, samples - done) samples; returns the (avg, rgb) CUDA tensors of the first `done` samples."""
+        if self.finished:
+            raise RuntimeError(f"the frame is finished: all {self.samples} samples are rendered")
+        if int(n) < 1:
+            raise ValueError(f"a step renders at least one sample, got {n}")
+        k_end = min(self._done + int(n), self.samples)
+        avg, rgb = self.dscene.render_rows_range(self.cam, self.samples, self.w, self.h, self._done, k_end, self._sums,
+                                                 cast=self.cast, shard=self.shard, stream=stream)
+        self._done = k_end
+        return avg, rgb

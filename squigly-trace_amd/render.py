@@ -43,6 +43,24 @@ def render_f32(bih, cam, samples, dimensions, cast=False) -> np.ndarray:
     return out
 
 
+def render_progressive(bih, cam, samples, dimensions, step, cast=False, device=0):
+    """The frame of render_rgb8, `step` samples at a time: yields (done, rgb8) after every step, rgb8 being the (w, h, 3) uint8
+    image of the first `done` samples.  The last image (done == samples) is bit for bit that of render_rgb8 (DeviceScene,
+    Progressive: one device, the scene uploaded once)."""
+    from .device import DeviceScene, Progressive       # torch: only the resident-scene path needs it
+    w, h = dimensions
+    if int(step) < 1:
+        raise ValueError(f"step must be positive, got {step}")
+    ds = DeviceScene(bih, device)
+    try:
+        p = Progressive(ds, cam, samples, w, h, cast=cast)
+        while not p.finished:
+            _, rgb = p.step(step)
+            yield p.done, rgb.cpu().numpy()
+    finally:
+        ds.close()
+
+
 def render(bih, cam, settings: Settings):
     """Lib.render: compute the image and write it to settings.savePath."""
     img = render_rgb8(bih, cam, settings.samples, settings.dimensions, settings.cast)
