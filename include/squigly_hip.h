@@ -114,6 +114,23 @@ int sq_render_rows_device_range(sq_device_scene* s, const sq_camera* cam, int32_
                                 int32_t cast, sq_shard sh, int32_t k_begin, int32_t k_end,
                                 float* d_sum, float* d_avg, uint8_t* d_rgb, void* hip_stream);
 
+/* Many views of one scene in one call: a frame of n_views views is exactly n_views single-view frames.  View i is bit for bit what
+ * sq_render_rows_device_range writes for cams[i] with the same other arguments (the seed of sample k of pixel (y, x) is
+ * samples * (x + y * w) + k in every view, src/Lib.hs:85), in every kernel form, schedule and option.  All views share one primary
+ * pass and one pair of trace launches per sample batch, so the fixed cost of a call (about 1.6 ms) is paid once, not n_views times.
+ *  cams  : HOST array of n_views cameras; read during the call only (the caller may reuse it on return).
+ *  d_sum, d_avg, d_rgb : DEVICE buffers, view-major [n_views][rows][h][3] with rows = sq_shard_rows(w, sh); block i is byte for byte
+ *          what a single-view call writes for cams[i].  [k_begin, k_end) means what it means in sq_render_rows_device_range;
+ *          d_sum may be NULL only when [k_begin, k_end) == [0, samples).  d_avg and d_rgb are optional.
+ * Refused with an error code before anything is enqueued (every buffer left as it was): n_views < 1, cams == NULL,
+ * n_views * rows * h > INT32_MAX, and every refusal of sq_render_rows_device_range (bad range, d_sum == d_avg, no output buffer,
+ * bad shard, the LDS-height limits).  n_views == 1 takes exactly the single-view path.
+ * Like the other entry points the call only enqueues work on hip_stream.  The calls on one scene share its workspace and camera
+ * table, so they must be ordered on one stream. */
+int sq_render_views_device(sq_device_scene* s, const sq_camera* cams, int32_t n_views, int32_t samples, int32_t w, int32_t h,
+                           int32_t cast, sq_shard sh, int32_t k_begin, int32_t k_end,
+                           float* d_sum, float* d_avg, uint8_t* d_rgb, void* hip_stream);
+
 /* Timing of the dominant kernel measured with hipEvents on the stream it was launched on:
  * average duration in ms over the launches since the last reset, and the launch count. */
 int  sq_kernel_timing(sq_device_scene* s, double* avg_ms, int64_t* launches, const char** kernel_name);

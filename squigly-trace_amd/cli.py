@@ -10,7 +10,8 @@ import os
 import sys
 import time
 
-from . import BIH, Mesh, Settings, lib, load_camera, render, render_progressive, write_png
+from . import BIH, Mesh, Settings, camera_from_text, lib, load_camera, render, render_progressive, render_views_rgb8, write_png
+from ._native import SquiglyError
 
 
 def parse_dimensions(text):
@@ -31,6 +32,48 @@ def positive_int(text):
     return v
 
 
+def parse_views(text):
+    """The cameras of a views file: the reference's camera format (src/Obj.hs:60-70) repeated, each pair of non-blank lines one
+    camera (position, then rotation angles).  Raises ValueError for an odd line count, a line that does not parse or no camera."""
+    lines = [ln.strip() for ln in text.splitlines() if ln.strip()]
+    if not lines:
+        raise ValueError("no camera in the views file")
+    if len(lines) % 2:
+        raise ValueError(f"{len(lines)} non-blank lines: a camera is two lines (position, rotation)")
+    cams = []
+    for i in range(0, len(lines), 2):
+        for ln in lines[i:i + 2]:
+            try:
+                ok = len([float(v) for v in ln.split()]) == 3
+            except ValueError:
+                ok = False
+            if not ok:
+                raise ValueError(f"camera {i // 2}: expected three numbers, got {ln!r}")
+        try:
+            cams.append(camera_from_text((lines[i] + "\n" + lines[i + 1] + "\n").encode()))
+        except SquiglyError as e:
+            raise ValueError(f"camera {i // 2}: {e}")
+    return cams
+
+
+def views_file(path):
+    try:
+        with open(path) as f:
+            text = f.read()
+    except OSError as e:
+        raise argparse.ArgumentTypeError(f"cannot read {path}: {e}")
+    try:
+        return parse_views(text)
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(f"{path}: {e}")
+
+
+def view_paths(save_path, n):
+    """Where the CLI writes the images of n views: <savepath stem>_<i:04d><ext>."""
+    stem, ext = os.path.splitext(save_path)
+    return [f"{stem}_{i:04d}{ext}" for i in range(n)]
+
+
 def build_parser():
     p = argparse.ArgumentParser(prog="squigly-trace", description="A cute raytracer",
                                 epilog="squigly-trace was made by Ruko (https://github.com/rukokarasu/)")
@@ -46,14 +89,25 @@ def build_parser():
     # not a flag of the reference: progressive previews (the final image is the same bytes as without it)
     p.add_argument("--preview-every", type=positive_int, default=None, metavar="K",
                    help="Overwrite the savepath with a preview after every K samples (default: no previews)")
+    p.add_argument("--views", type=views_file, default=None, metavar="FILE",
+                   help="Render every camera of FILE (pairs of camera lines) in one call into <savepath stem>_<i:04d><ext>; "
+                        "-c is not read")
     return p
 
 
+def parse_args(argv=None):
+    p = build_parser()
+    a = p.parse_args(argv)
+    if a.views is not None and a.preview_every is not None:
+        p.error("--views cannot be combined with --preview-every")
+    return a
+
+
 def main(argv=None):
-    a = build_parser().parse_args(argv)
+    a = parse_args(argv)
     settings = Settings(samples=a.samples, dimensions=a.dimensions, savePath=a.savepath, objPath=a.objpath,
                         cameraPath=a.camerapath, debug=a.debug, debugPath=a.debugpath, cast=a.cast)
-    cam = load_camera(settings.cameraPath)                      # app/Main.hs:38
+    cam = load_camera(settings.cameraPath) if a.views is None else None   # app/Main.hs:38
     mesh = Mesh.from_obj(settings.objPath, "./data")            # loadTris, app/Main.hs:58-61 + src/Obj.hs:52
     if settings.debug:                                          # src/Obj.hs:55-57: print (head objs); print mats
         first, mats = mesh.debug_show()
@@ -80,7 +134,12 @@ def main(argv=None):
     t0 = time.time()
     print("Started at " + time.strftime("%H:%M:%S%p UTC", time.gmtime(t0)).lower().replace("utc", "UTC"))
     os.makedirs(os.path.dirname(os.path.abspath(settings.savePath)), exist_ok=True)
-    if a.preview_every is None:
+    if a.views is not None:
+        imgs = render_views_rgb8(bih, a.views, settings.samples, settings.dimensions, settings.cast)
+        for path, img in zip(view_paths(settings.savePath, len(imgs)), imgs):
+            write_png(path, img)
+        print(f"Wrote {len(imgs)} views to {view_paths(settings.savePath, 1)[0]} ...")
+    elif a.preview_every is None:
         render(bih, cam, settings)
     else:
         for done, img in render_progressive(bih, cam, settings.samples, settings.dimensions, a.preview_every, settings.cast):

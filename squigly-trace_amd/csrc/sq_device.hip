@@ -102,7 +102,32 @@ struct Frame {
     int32_t k_begin, k_end;
     float* sum;
     int32_t diag;             // option "coresidency": the per-sample kernels and the trace kernel count who runs beside whom (sq_get_stats 24..27)
+    // multi-view frames (sq_render_views_device, the kernels' MV instantiations): n_views views of view_pixels = local_rows * h pixels,
+    // view-major, so a pixel index runs over [0, n_views * view_pixels); cams = the scene's camera table, kCamWords floats per view
+    // (pos, rot).  A single-view frame has n_views = 1 and reads cam_pos / cam_rot.
+    int32_t n_views, view_pixels;
+    const float* cams;
 };
+constexpr int kCamWords = 12;     // a view's entry in the camera table: pos[3], rot[9]
+struct ViewCam { f3 pos; float rot[9]; };
+// The camera of view v.  UNIFORM: v is the same in every lane of the wave (a primary-ray tile), so the 48 bytes come through scalar loads.
+template <bool UNIFORM>
+__device__ __forceinline__ ViewCam view_cam(const Frame& F, int v) {
+    ViewCam c;
+    if constexpr (UNIFORM) {
+        v = __builtin_amdgcn_readfirstlane(v);
+        const __attribute__((address_space(4))) float* p = (const __attribute__((address_space(4))) float*)(F.cams + (long long)kCamWords * v);
+        c.pos = sq::mk(p[0], p[1], p[2]);
+#pragma unroll
+        for (int i = 0; i < 9; ++i) c.rot[i] = p[3 + i];
+    } else {
+        const float4* p = reinterpret_cast<const float4*>(F.cams + (long long)kCamWords * v);   // 48-B entries: 16-B aligned
+        const float4 a = p[0], b = p[1], d = p[2];
+        c.pos = sq::mk(a.x, a.y, a.z);
+        c.rot[0] = a.w; c.rot[1] = b.x; c.rot[2] = b.y; c.rot[3] = b.z; c.rot[4] = b.w; c.rot[5] = d.x; c.rot[6] = d.y; c.rot[7] = d.z; c.rot[8] = d.w;
+    }
+    return c;
+}
 __device__ __forceinline__ void pixel_coords(const Frame& F, int pix, int& y, int& x) {   // 32-bit: cheap div/mod
     const int j = pix / F.h;
     x = pix - j * F.h;
@@ -130,6 +155,21 @@ __device__ __forceinline__ void pixel_coords(const Frame& F, long long pix, int&
     const int blk = j / F.row_block;
     y = (blk * F.n_shards + F.shard) * F.row_block + (j - blk * F.row_block);
 }
+// Multi-view frames: the view of a pixel index, and (y, x) of the pixel within its view.  Every view has the same pixels and seeds.
+__device__ __forceinline__ int view_coords(const Frame& F, int pix, int& y, int& x) {   // px_pixel: n_views * view_pixels <= INT32_MAX
+    const int v = pix / F.view_pixels;
+    pixel_coords(F, pix - v * F.view_pixels, y, x);
+    return v;
+}
+// The q-th primary ray of a multi-view frame, q in [0, n_views * primary_padded(F)): every view's tiles are padded to whole waves, so a
+// wave never spans two views and its camera is wave-uniform.  Returns the pixel index (-1 for padding); `view` = its view.
+__device__ __forceinline__ long long primary_tile_views(const Frame& F, long long q, int& view) {
+    const long long per = primary_padded(F);
+    view = (int)(q / per);
+    if (view >= F.n_views) return -1;                                   // past the last view (a launch's last workgroup)
+    const long long local = primary_tile(F, q - (long long)view * per);
+    return local >= 0 ? (long long)view * F.view_pixels + local : -1;
+}
 
 // Where a pixel's fold starts: +0 on a fresh frame, else what the caller's earlier range call left in F.sum (src/Lib.hs:88 is a left
 // fold, so resuming it from its exact fp32 partial sum gives the bits of one uninterrupted fold).
@@ -146,16 +186,24 @@ __device__ __forceinline__ void store_miss_sum(const Frame& F, long long pix) {
 // ----------------------------------------------------------------------------------------------
 // Variant 1: one lane per pixel, everything in one kernel (cross-check variant; also raycast mode)
 // ----------------------------------------------------------------------------------------------
-template <typename StackT>
+// MV: a multi-view frame (pixels are enumerated linearly, so the lanes of a wave may belong to two views: per-lane camera reads)
+template <typename StackT, bool MV>
 __global__ void __launch_bounds__(kBlock) sq_render_pixels(const SceneView S, const Frame F) {
     extern __shared__ float4 lds_raw[];
     SQ_LDS StackT* stk = to_lds<StackT>(lds_raw) + threadIdx.x;
     const long long pix = (long long)blockIdx.x * kBlock + threadIdx.x;
-    if (pix >= (long long)F.local_rows * F.h) return;
-    int y, x; pixel_coords(F, pix, y, x);
+    int y, x; f3 o0, d0;
+    if constexpr (MV) {
+        if (pix >= (long long)F.n_views * F.view_pixels) return;
+        const ViewCam c = view_cam<false>(F, view_coords(F, (int)pix, y, x));
+        o0 = c.pos; d0 = primary_dir(c.rot, F.w, F.h, y, x);
+    } else {
+        if (pix >= (long long)F.local_rows * F.h) return;
+        pixel_coords(F, pix, y, x);
+        o0 = sq::mk(F.cam_pos[0], F.cam_pos[1], F.cam_pos[2]);
+        d0 = primary_dir(F.cam_rot, F.w, F.h, y, x);
+    }
     const GlobalNodes N{ S.branches, S.cull_child, S.cull_child != nullptr };
-    const f3 o0 = sq::mk(F.cam_pos[0], F.cam_pos[1], F.cam_pos[2]);
-    const f3 d0 = primary_dir(F.cam_rot, F.w, F.h, y, x);
     const int n = F.samples;
     f3 sum = sq::mk(0, 0, 0);                                           // sum = foldl (+) 0
     const Hit h0 = trace_one(S, N, o0, d0, stk, kBlock);
@@ -258,18 +306,28 @@ __device__ __forceinline__ int wave_append(int32_t* counter, bool want) {
 }
 
 // Primary rays: trace once per pixel, compact the pixels that hit.
-template <typename StackT>
+template <typename StackT, bool MV>
 __global__ void __launch_bounds__(kBlock) sq_primary(const SceneView S, const Frame F, const Work W) {
     extern __shared__ float4 lds_raw[];
     SQ_LDS StackT* stk = to_lds<StackT>(lds_raw) + threadIdx.x;
     const long long q = (long long)blockIdx.x * kBlock + threadIdx.x;
-    const long long pix = q < primary_padded(F) ? primary_tile(F, q) : -1;
+    int view = 0;
+    long long pix;
+    if constexpr (MV) pix = q < primary_padded(F) * F.n_views ? primary_tile_views(F, q, view) : -1;
+    else pix = q < primary_padded(F) ? primary_tile(F, q) : -1;
     const bool in = pix >= 0;
     Hit h0; h0.tri = -1; h0.t = 0;
     if (in) {
-        int y, x; pixel_coords(F, pix, y, x);
+        int y, x;
         const GlobalNodes N{ S.branches, S.cull_child, S.cull_child != nullptr };
-        h0 = trace_one(S, N, sq::mk(F.cam_pos[0], F.cam_pos[1], F.cam_pos[2]), primary_dir(F.cam_rot, F.w, F.h, y, x), stk, kBlock);
+        if constexpr (MV) {
+            pixel_coords(F, pix - (long long)view * F.view_pixels, y, x);
+            const ViewCam c = view_cam<true>(F, view);
+            h0 = trace_one(S, N, c.pos, primary_dir(c.rot, F.w, F.h, y, x), stk, kBlock);
+        } else {
+            pixel_coords(F, pix, y, x);
+            h0 = trace_one(S, N, sq::mk(F.cam_pos[0], F.cam_pos[1], F.cam_pos[2]), primary_dir(F.cam_rot, F.w, F.h, y, x), stk, kBlock);
+        }
     }
     const int a = wave_append(W.n_active, in && h0.tri >= 0);
     if (a >= 0) {
@@ -280,11 +338,19 @@ __global__ void __launch_bounds__(kBlock) sq_primary(const SceneView S, const Fr
 }
 
 struct Pixel0 { f3 p0, d0; Surface s0; int y, x; };
+// MV: the pixel's view comes from its index, and its camera from the table (once per active pixel, not per sample)
+template <bool MV>
 __device__ __forceinline__ Pixel0 load_pixel0(const SceneView& S, const Frame& F, const Work& W, int a) {
     Pixel0 P;
-    pixel_coords(F, (int)W.px_pixel[a], P.y, P.x);
-    P.d0 = primary_dir(F.cam_rot, F.w, F.h, P.y, P.x);
-    P.p0 = sq::mk(F.cam_pos[0], F.cam_pos[1], F.cam_pos[2]) + sq::scale(W.px_t0[a], P.d0);   // intersectPoint, src/Geometry.hs:134
+    if constexpr (MV) {
+        const ViewCam c = view_cam<false>(F, view_coords(F, (int)W.px_pixel[a], P.y, P.x));
+        P.d0 = primary_dir(c.rot, F.w, F.h, P.y, P.x);
+        P.p0 = c.pos + sq::scale(W.px_t0[a], P.d0);
+    } else {
+        pixel_coords(F, (int)W.px_pixel[a], P.y, P.x);
+        P.d0 = primary_dir(F.cam_rot, F.w, F.h, P.y, P.x);
+        P.p0 = sq::mk(F.cam_pos[0], F.cam_pos[1], F.cam_pos[2]) + sq::scale(W.px_t0[a], P.d0);   // intersectPoint, src/Geometry.hs:134
+    }
     P.s0 = surface_of(S, W.px_tri0[a]);
     return P;
 }
@@ -303,11 +369,12 @@ __device__ __forceinline__ int2 slot_hit(const float4& org) { return make_int2(_
 // One thread per active pixel (blockIdx.y splits the samples of a pixel when a frame has few pixels): everything that is
 // the same for every sample of a pixel -- the pixel's coordinates, primary direction, hit point, surface, seed base -- is
 // computed once, not 256 times; consecutive threads still write consecutive slots (sid = k * A + a).
+template <bool MV>
 __global__ void __launch_bounds__(kBlock) sq_gen_bounce1(const SceneView S, const Frame F, const Work W, int k_base, int k_count) {
     const int A = *W.n_active;
     diag_aux_wave(W, F.diag, true);
     for (int a = blockIdx.x * kBlock + threadIdx.x; a < A; a += gridDim.x * kBlock) {
-        const Pixel0 P = load_pixel0(S, F, W, a);
+        const Pixel0 P = load_pixel0<MV>(S, F, W, a);
         const bool absorbing = absorbs(S, P.s0);
         const f3 rad_absorbing = P.s0.surf * sq::mk(0, 0, 0) + P.s0.emit;
         const long long rix = (long long)F.samples * ((long long)P.x + (long long)P.y * (long long)F.w);   // src/Lib.hs:85
@@ -341,10 +408,11 @@ __global__ void __launch_bounds__(kBlock) sq_gen_bounce1(const SceneView S, cons
 // The depth-0 mirror ray of every active pixel, once per frame (slot a = active pixel a).
 // `base`: first of the *n_active slots the mirror rays use (0 when they have a launch of their own, the spare region
 // behind the sample slots when they ride at the head of the first bounce launch).
+template <bool MV>
 __global__ void __launch_bounds__(kBlock) sq_mirror1_gen(const SceneView S, const Frame F, const Work W, long long base) {
     const int A = *W.n_active;
     for (int a = blockIdx.x * kBlock + threadIdx.x; a < A; a += gridDim.x * kBlock) {
-        const Pixel0 P = load_pixel0(S, F, W, a);
+        const Pixel0 P = load_pixel0<MV>(S, F, W, a);
         const long long sl = base + a;
         if (absorbs(S, P.s0)) { W.state[sl] = kDone; continue; }
         const f3 d1 = mirror_dir(P.d0, P.s0);
@@ -367,14 +435,24 @@ __global__ void __launch_bounds__(kBlock) sq_mirror1_store(const Work W, long lo
 // k_count = 1, then the hits are compacted into the active-pixel list exactly as sq_primary does.  The one-ray-per-lane walk of
 // sq_primary(_resident) lasts as long as its most expensive wave (64 neighbouring pixels on dense geometry: 0.5 ms on the headline
 // scene however small the shard); the pooled leaf phase walks such a wave faster.  W.n_active[48] is the launch's queue length.
+template <bool MV>
 __global__ void __launch_bounds__(kBlock) sq_primary_gen(const Frame F, const Work W, long long total) {
     if (blockIdx.x == 0 && threadIdx.x == 0) W.n_active[48] = (int32_t)total;
     for (long long pix = (long long)blockIdx.x * kBlock + threadIdx.x; pix < total; pix += (long long)gridDim.x * kBlock) {
-        int y, x; pixel_coords(F, pix, y, x);
-        const f3 d = primary_dir(F.cam_rot, F.w, F.h, y, x);
-        W.state[pix] = kRay1;
-        W.org[pix] = make_float4(F.cam_pos[0], F.cam_pos[1], F.cam_pos[2], 0.0f);
-        W.dir[pix] = make_float4(d.x, d.y, d.z, 0.0f);
+        int y, x;
+        if constexpr (MV) {
+            const ViewCam c = view_cam<false>(F, view_coords(F, (int)pix, y, x));
+            const f3 d = primary_dir(c.rot, F.w, F.h, y, x);
+            W.state[pix] = kRay1;
+            W.org[pix] = make_float4(c.pos.x, c.pos.y, c.pos.z, 0.0f);
+            W.dir[pix] = make_float4(d.x, d.y, d.z, 0.0f);
+        } else {
+            pixel_coords(F, pix, y, x);
+            const f3 d = primary_dir(F.cam_rot, F.w, F.h, y, x);
+            W.state[pix] = kRay1;
+            W.org[pix] = make_float4(F.cam_pos[0], F.cam_pos[1], F.cam_pos[2], 0.0f);
+            W.dir[pix] = make_float4(d.x, d.y, d.z, 0.0f);
+        }
     }
 }
 __global__ void __launch_bounds__(kBlock) sq_primary_store(const Frame F, const Work W, long long total) {
@@ -391,18 +469,27 @@ __global__ void __launch_bounds__(kBlock) sq_primary_store(const Frame F, const 
     }
 }
 
+// Multi-view frames: copies a chunk of cameras into the scene's camera table.  The cameras travel as kernel arguments, which are
+// captured when the launch is enqueued: the table is filled in stream order, and the caller's array is not read after the call.
+constexpr int kCamChunk = 64;                 // cameras per staging launch: 64 x 48 B = 3 KB of arguments (the limit is 4 KB)
+struct CamChunk { float v[kCamWords * kCamChunk]; };
+__global__ void __launch_bounds__(kBlock) sq_stage_cams(float* table, int n, const CamChunk C) {
+    for (int i = threadIdx.x; i < kCamWords * n; i += kBlock) table[i] = C.v[i];
+}
+
 // After ray 1: a miss finishes the sample; a hit either finishes it (absorbing surface) or puts ray 2 in the slot.
 // One thread per active pixel, like sq_gen_bounce1: the primary surface, the hit point and the pixel's mirror ray and its hit
 // are per-pixel values.  It waits on memory two thirds of its time, so a slot's state byte decides what else is read (nothing
 // for a finished slot, the generator words for a mirrored one, ray and hit for a traced one), the state and generator words
 // are requested two samples ahead and the rest one sample ahead.
+template <bool MV>
 __global__ void __launch_bounds__(kBlock) sq_shade1(const SceneView S, const Frame F, const Work W, int k_count) {
     const int A = *W.n_active;
     diag_aux_wave(W, F.diag, true);
     struct First { uint8_t st; float4 org; };     // org: .xy = the hit the trace kernel left (traced slots), .w = n1
     struct Second { float4 dir; };                // .w = n2.  Ray 1 starts at the pixel's primary hit point P.p0 (sq_gen_bounce1 stored that very value): no origin is re-read
     for (int a = blockIdx.x * kBlock + threadIdx.x; a < A; a += gridDim.x * kBlock) {
-        const Pixel0 P = load_pixel0(S, F, W, a);
+        const Pixel0 P = load_pixel0<MV>(S, F, W, a);
         const Surface& s0 = P.s0;
         const f3 d1_mirror = mirror_dir(P.d0, P.s0);
         const int2 hit_mirror = make_int2(__float_as_int(W.px_mt[a]), W.px_mtri[a]);
@@ -649,7 +736,7 @@ __device__ __forceinline__ void stage_resident_scene(const SceneView& S, int n_b
 // Primary rays with the scene in LDS (the resident form): same per-ray code as sq_primary, but a branch or triangle costs an
 // LDS read instead of an L2 round trip.  A primary ray is a chain of ~200 dependent reads, so on small frames -- one rank's
 // share of a frame at 8 ranks -- the launch is as long as that chain: 0.58 ms from L2, 0.1-0.2 ms from LDS.
-template <typename StackT>
+template <typename StackT, bool MV>
 __global__ void __launch_bounds__(kResidentBlock) sq_primary_resident(const SceneView S, const Frame F, const Work W, int stack_cap) {
     extern __shared__ float4 lds_raw[];
     char* lds = reinterpret_cast<char*>(lds_raw);
@@ -658,14 +745,24 @@ __global__ void __launch_bounds__(kResidentBlock) sq_primary_resident(const Scen
     ResidentNodes N; ResidentTris G;
     stage_resident_scene<kResidentBlock>(S, S.n_branches, lds, L, N, G);
     __syncthreads();
-    const long long total = primary_padded(F);
+    const long long total = MV ? primary_padded(F) * F.n_views : primary_padded(F);
     for (long long base = (long long)blockIdx.x * kResidentBlock; base < total; base += (long long)gridDim.x * kResidentBlock) {
-        const long long pix = primary_tile(F, base + threadIdx.x);          // (total is a multiple of 64: whole waves)
+        int view = 0;
+        long long pix;                                                      // (total is a multiple of 64: whole waves)
+        if constexpr (MV) pix = primary_tile_views(F, base + threadIdx.x, view);
+        else pix = primary_tile(F, base + threadIdx.x);
         const bool in = pix >= 0;
         Hit h0; h0.tri = -1; h0.t = 0;
         if (in) {
-            int y, x; pixel_coords(F, pix, y, x);
-            h0 = trace_one(S, N, G, S.rroot, sq::mk(F.cam_pos[0], F.cam_pos[1], F.cam_pos[2]), primary_dir(F.cam_rot, F.w, F.h, y, x), stk, kResidentBlock);
+            int y, x;
+            if constexpr (MV) {
+                pixel_coords(F, pix - (long long)view * F.view_pixels, y, x);
+                const ViewCam c = view_cam<true>(F, view);
+                h0 = trace_one(S, N, G, S.rroot, c.pos, primary_dir(c.rot, F.w, F.h, y, x), stk, kResidentBlock);
+            } else {
+                pixel_coords(F, pix, y, x);
+                h0 = trace_one(S, N, G, S.rroot, sq::mk(F.cam_pos[0], F.cam_pos[1], F.cam_pos[2]), primary_dir(F.cam_rot, F.w, F.h, y, x), stk, kResidentBlock);
+            }
         }
         const int a = wave_append(W.n_active, in && h0.tri >= 0);
         if (a >= 0) {
@@ -1146,6 +1243,8 @@ struct sq_device_scene {
     sq_plan plan{}; bool has_plan = false;   // what the last frame's launch_frame chose (sq_last_plan)
     // second stream of the overlapped schedule (launch_frame) and its event pool
     hipStream_t aux = nullptr; std::vector<hipEvent_t> events;
+    // multi-view frames: the camera table (kCamWords floats per view, grow-only), filled on the call's stream
+    float* d_cams = nullptr; int64_t cams_cap = 0;
     int64_t opt_overlap = 0, opt_aux_blocks_per_cu = 0;
     int64_t opt_pool = 1, opt_refill_min = 12, opt_flush_min = 40, opt_guided = 1, opt_primary_resident = 1, opt_pixel_major = -1, opt_cull = 1, opt_descend_extra = 2, opt_descend_lanes = 16, opt_primary_pooled = 0, opt_coresidency = 0, opt_trace_prio = 0, opt_aux_low_priority = 1, opt_aux_polite = 0, opt_incremental = 1, opt_primary_tiles = 1;
 };
@@ -1511,6 +1610,7 @@ extern "C" void sq_scene_free(sq_device_scene* s) {
     if (s->d_work) cache_give(s->device, s->d_work, s->work_bytes);
     for (hipEvent_t e : s->events) (void)hipEventDestroy(e);
     if (s->aux) (void)hipStreamDestroy(s->aux);
+    (void)hipFree(s->d_cams);
     delete s;
 }
 
@@ -1575,12 +1675,38 @@ int ensure_workspace(sq_device_scene* s, int64_t pixels, int64_t slots) {
     return 0;
 }
 
-template <typename StackT>
-int launch_frame(sq_device_scene* s, const Frame& F, hipStream_t stream) {
+// The camera table of a multi-view frame: room for n views (grow-only).  Growing frees the old table, which waits for the
+// device, so the table a previous frame still reads is not freed under it.
+int ensure_cam_table(sq_device_scene* s, int64_t n) {
+    if (n <= s->cams_cap) return 0;
+    const int64_t cap = std::max<int64_t>((n + 63) / 64 * 64, 2 * s->cams_cap);
+    if (s->d_cams) { SQ_HIP(hipFree(s->d_cams)); s->d_cams = nullptr; s->cams_cap = 0; }
+    SQ_HIP(hipMalloc(&s->d_cams, (size_t)cap * kCamWords * sizeof(float)));
+    s->cams_cap = cap;
+    return 0;
+}
+// Enqueues the copy of a multi-view frame's cameras into its table F.cams (nothing for a single-view frame: cams = nullptr).
+int stage_cams(sq_device_scene* s, const Frame& F, const sq_camera* cams, hipStream_t stream) {
+    (void)s;
+    if (!cams) return 0;
+    static_assert(sizeof(sq_camera) == kCamWords * sizeof(float), "sq_camera is one camera-table entry");
+    for (int i0 = 0; i0 < F.n_views; i0 += kCamChunk) {
+        const int n = std::min(kCamChunk, F.n_views - i0);
+        CamChunk c{};
+        std::memcpy(c.v, cams + i0, (size_t)n * sizeof(sq_camera));
+        hipLaunchKernelGGL(sq_stage_cams, dim3(1), dim3(kBlock), 0, stream, const_cast<float*>(F.cams) + (long long)kCamWords * i0, n, c);
+        SQ_HIP(hipGetLastError());
+    }
+    return 0;
+}
+
+// MV: a multi-view frame; `cams` (host, F.n_views of them) are staged into the scene's camera table F.cams once the frame is planned.
+template <typename StackT, bool MV>
+int launch_frame(sq_device_scene* s, const Frame& F, hipStream_t stream, const sq_camera* cams) {
     SceneView S = s->view;
     if (!s->opt_cull) S.cull_o2max = -1.0f;                            // no ray is inside the culling limits: every leaf is tested
     if (!s->opt_incremental) S.incremental_ok = 0;                     // resident form: every branch step tests both children from the branch's own box
-    const long long pixels = (long long)F.local_rows * F.h;
+    const long long pixels = (long long)F.n_views * F.local_rows * F.h;   // every view's pixels, view-major
     const int stack_cap = std::max(S.height, 1);
     const size_t px_lds = (size_t)kBlock * stack_cap * sizeof(StackT);
     const long long px_blocks = (pixels + kBlock - 1) / kBlock;
@@ -1604,9 +1730,10 @@ int launch_frame(sq_device_scene* s, const Frame& F, hipStream_t stream) {
         return 0;
     };
     if (s->opt_variant == 1 || F.cast) {
-        if (px_lds > 64 * 1024) SQ_HIP(hipFuncSetAttribute((const void*)sq_render_pixels<StackT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)px_lds));
+        if (px_lds > 64 * 1024) SQ_HIP(hipFuncSetAttribute((const void*)sq_render_pixels<StackT, MV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)px_lds));
         P.launched = 1;
-        return timed([&] { hipLaunchKernelGGL(sq_render_pixels<StackT>, dim3((unsigned)px_blocks), dim3(kBlock), px_lds, stream, S, F); }, "sq_render_pixels", stream);
+        if (stage_cams(s, F, cams, stream)) return 1;
+        return timed([&] { hipLaunchKernelGGL((sq_render_pixels<StackT, MV>), dim3((unsigned)px_blocks), dim3(kBlock), px_lds, stream, S, F); }, "sq_render_pixels", stream);
     }
     // ---- wavefront pipeline ----
     const int n_call = F.k_end - F.k_begin;                              // the samples this call renders (a whole frame: F.samples)
@@ -1692,7 +1819,7 @@ int launch_frame(sq_device_scene* s, const Frame& F, hipStream_t stream) {
         // where a violation is an error code, rather than by the device-side trap, where it would be a GPU abort.
         const void* fns[5] = { (const void*)sq_trace_rays<StackT, true, kResidentBlock, false, true>, (const void*)sq_trace_rays<StackT, true, kResidentBlock, true, true>,
                                (const void*)sq_trace_rays<StackT, true, kResidentBlock, false, false>, (const void*)sq_trace_rays<StackT, true, kResidentBlock, true, false>,
-                               (const void*)sq_primary_resident<StackT> };
+                               (const void*)sq_primary_resident<StackT, MV> };
         for (const void* fn : fns) {
             hipFuncAttributes attr{};
             SQ_HIP(hipFuncGetAttributes(&attr, fn));
@@ -1703,6 +1830,7 @@ int launch_frame(sq_device_scene* s, const Frame& F, hipStream_t stream) {
     }
     P.launched = 1;                                                    // planned; what follows fails only on HIP errors
     // nothing is enqueued before this point, so a refusal above leaves every buffer as it was
+    if (stage_cams(s, F, cams, stream)) return 1;                       // multi-view: before every kernel that reads the table (e_setup below)
     if (F.out_avg) SQ_HIP(hipMemsetAsync(F.out_avg, 0, (size_t)pixels * 3 * sizeof(float), stream));   // pixels whose primary ray misses: black
     if (F.out_rgb) SQ_HIP(hipMemsetAsync(F.out_rgb, 0, (size_t)pixels * 3, stream));
     SQ_HIP(hipMemsetAsync(W.n_active, 0, 128 * sizeof(int32_t), stream));
@@ -1711,12 +1839,12 @@ int launch_frame(sq_device_scene* s, const Frame& F, hipStream_t stream) {
     if (primary_pooled) {
     } else if (resident && s->opt_primary_resident) {
         const TraceLds Lp = trace_lds_layout(S.n_branches, true, S.n_verts, S.n_tris, kResidentBlock, stack_cap, (int)sizeof(StackT), false);
-        SQ_HIP(hipFuncSetAttribute((const void*)sq_primary_resident<StackT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)Lp.total));
-        const long long need = (primary_padded(F) + kResidentBlock - 1) / kResidentBlock;
-        hipLaunchKernelGGL(sq_primary_resident<StackT>, dim3((unsigned)std::min<long long>(s->n_cu, need)), dim3(kResidentBlock), Lp.total, stream, S, F, W, stack_cap);
+        SQ_HIP(hipFuncSetAttribute((const void*)sq_primary_resident<StackT, MV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)Lp.total));
+        const long long need = (primary_padded(F) * F.n_views + kResidentBlock - 1) / kResidentBlock;
+        hipLaunchKernelGGL((sq_primary_resident<StackT, MV>), dim3((unsigned)std::min<long long>(s->n_cu, need)), dim3(kResidentBlock), Lp.total, stream, S, F, W, stack_cap);
     } else {
-        if (px_lds > 64 * 1024) SQ_HIP(hipFuncSetAttribute((const void*)sq_primary<StackT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)px_lds));
-        hipLaunchKernelGGL(sq_primary<StackT>, dim3((unsigned)((primary_padded(F) + kBlock - 1) / kBlock)), dim3(kBlock), px_lds, stream, S, F, W);
+        if (px_lds > 64 * 1024) SQ_HIP(hipFuncSetAttribute((const void*)sq_primary<StackT, MV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)px_lds));
+        hipLaunchKernelGGL((sq_primary<StackT, MV>), dim3((unsigned)((primary_padded(F) * F.n_views + kBlock - 1) / kBlock)), dim3(kBlock), px_lds, stream, S, F, W);
     }
     SQ_HIP(hipGetLastError());
     const int aux_blocks = s->n_cu * (int)(s->opt_aux_blocks_per_cu ? s->opt_aux_blocks_per_cu : 8);
@@ -1758,7 +1886,7 @@ int launch_frame(sq_device_scene* s, const Frame& F, hipStream_t stream) {
     if (primary_pooled) {
         Work Wp = W; Wp.n_active = W.n_active + 48;                     // the launch's queue is the shard's pixels, not the active ones
         SQ_HIP(hipMemsetAsync(W.head[0], 0, 32 * sizeof(int32_t), stream));
-        hipLaunchKernelGGL(sq_primary_gen, dim3(aux_blocks), dim3(kBlock), 0, stream, F, W, pixels);
+        hipLaunchKernelGGL(sq_primary_gen<MV>, dim3(aux_blocks), dim3(kBlock), 0, stream, F, W, pixels);
         SQ_HIP(hipGetLastError());
         if (launch_trace(Wp, 1, 0, stream)) return 1;
         hipLaunchKernelGGL(sq_primary_store, dim3(aux_blocks), dim3(kBlock), 0, stream, F, W, pixels);
@@ -1770,7 +1898,7 @@ int launch_frame(sq_device_scene* s, const Frame& F, hipStream_t stream) {
     const bool mirror_rides = !overlap;
     if (!mirror_rides) {
         SQ_HIP(hipMemsetAsync(W.head[0], 0, 32 * sizeof(int32_t), stream));
-        hipLaunchKernelGGL(sq_mirror1_gen, dim3(aux_blocks), dim3(kBlock), 0, stream, S, F, W, 0ll);
+        hipLaunchKernelGGL(sq_mirror1_gen<MV>, dim3(aux_blocks), dim3(kBlock), 0, stream, S, F, W, 0ll);
         SQ_HIP(hipGetLastError());
         if (launch_trace(W, 1, 0, stream)) return 1;
         hipLaunchKernelGGL(sq_mirror1_store, dim3(aux_blocks), dim3(kBlock), 0, stream, W, 0ll);
@@ -1785,14 +1913,14 @@ int launch_frame(sq_device_scene* s, const Frame& F, hipStream_t stream) {
         for (int i = 0; i < n_real; ++i) {
             const int k0 = k0_of(i), kc = kc_of(i);
             SQ_HIP(hipMemsetAsync(W.head[0], 0, 32 * sizeof(int32_t), stream));     // both dequeue cursors
-            hipLaunchKernelGGL(sq_gen_bounce1, pp_grid(kc), dim3(kBlock), 0, stream, S, F, W, k0, kc);
+            hipLaunchKernelGGL(sq_gen_bounce1<MV>, pp_grid(kc), dim3(kBlock), 0, stream, S, F, W, k0, kc);
             SQ_HIP(hipGetLastError());
             const bool front = mirror_rides && i == 0;
-            if (front) hipLaunchKernelGGL(sq_mirror1_gen, dim3(aux_blocks), dim3(kBlock), 0, stream, S, F, W, (long long)W.slot_capacity);
+            if (front) hipLaunchKernelGGL(sq_mirror1_gen<MV>, dim3(aux_blocks), dim3(kBlock), 0, stream, S, F, W, (long long)W.slot_capacity);
             for (int level = 0; level < 2; ++level) {
                 if (launch_trace(W, kc, level, stream, front && level == 0)) return 1;
                 if (front && level == 0) hipLaunchKernelGGL(sq_mirror1_store, dim3(aux_blocks), dim3(kBlock), 0, stream, W, (long long)W.slot_capacity);
-                if (level == 0) hipLaunchKernelGGL(sq_shade1, pp_grid(kc), dim3(kBlock), 0, stream, S, F, W, kc);
+                if (level == 0) hipLaunchKernelGGL(sq_shade1<MV>, pp_grid(kc), dim3(kBlock), 0, stream, S, F, W, kc);
                 SQ_HIP(hipGetLastError());
             }
             SQ_LAUNCH_ACCUMULATE( dim3(aux_blocks), dim3(kBlock), 0, stream, S, F, W, kc, (k0 + kc >= F.k_end) ? 1 : 0);
@@ -1834,10 +1962,10 @@ int launch_frame(sq_device_scene* s, const Frame& F, hipStream_t stream) {
             const Work& V = Wt[i & 1];
             const int k0 = k0_of(i), kc = kc_of(i);
             SQ_HIP(hipMemsetAsync(V.head[0], 0, 32 * sizeof(int32_t), on));
-            hipLaunchKernelGGL(sq_gen_bounce1, pp_grid(kc), dim3(kBlock), 0, on, S, F, V, k0, kc);
+            hipLaunchKernelGGL(sq_gen_bounce1<MV>, pp_grid(kc), dim3(kBlock), 0, on, S, F, V, k0, kc);
             SQ_HIP(hipGetLastError());
             if (launch_trace(V, kc, 0, on)) return 1;
-            hipLaunchKernelGGL(sq_shade1, pp_grid(kc), dim3(kBlock), 0, on, S, F, V, kc);
+            hipLaunchKernelGGL(sq_shade1<MV>, pp_grid(kc), dim3(kBlock), 0, on, S, F, V, kc);
             SQ_HIP(hipGetLastError());
             if (launch_trace(V, kc, 1, on)) return 1;
             if (i > 0) SQ_HIP(hipStreamWaitEvent(on, eAcc[(size_t)i - 1], 0));
@@ -1859,7 +1987,7 @@ int launch_frame(sq_device_scene* s, const Frame& F, hipStream_t stream) {
     auto gen = [&](int i) -> int {                          // on X
         const Work& V = Wt[i & 1];
         SQ_HIP(hipMemsetAsync(V.head[0], 0, 32 * sizeof(int32_t), X));
-        hipLaunchKernelGGL(sq_gen_bounce1, pp_grid(kc_of(i)), dim3(kBlock), 0, X, S, F, V, k0_of(i), kc_of(i));
+        hipLaunchKernelGGL(sq_gen_bounce1<MV>, pp_grid(kc_of(i)), dim3(kBlock), 0, X, S, F, V, k0_of(i), kc_of(i));
         SQ_HIP(hipGetLastError());
         SQ_HIP(hipEventRecord(eG[(size_t)i], X));
         return 0;
@@ -1872,7 +2000,7 @@ int launch_frame(sq_device_scene* s, const Frame& F, hipStream_t stream) {
     };
     auto shade1 = [&](int i) -> int {                       // on X
         SQ_HIP(hipStreamWaitEvent(X, eT1[(size_t)i], 0));
-        hipLaunchKernelGGL(sq_shade1, pp_grid(kc_of(i)), dim3(kBlock), 0, X, S, F, Wt[i & 1], kc_of(i));
+        hipLaunchKernelGGL(sq_shade1<MV>, pp_grid(kc_of(i)), dim3(kBlock), 0, X, S, F, Wt[i & 1], kc_of(i));
         SQ_HIP(hipGetLastError());
         SQ_HIP(hipEventRecord(eS1[(size_t)i], X));
         return 0;
@@ -1905,9 +2033,10 @@ int launch_frame(sq_device_scene* s, const Frame& F, hipStream_t stream) {
 }  // namespace
 
 namespace {
-// Both render entry points: the samples [k_begin, k_end) of the `samples`-sample frame.  d_sum = nullptr (sq_render_rows_device) keeps
-// the fold in the workspace; the caller has checked everything that is specific to its own entry point.
-int render_rows(sq_device_scene* s, const sq_camera* cam, int32_t samples, int32_t w, int32_t h, int32_t cast, sq_shard sh,
+// Every render entry point: the samples [k_begin, k_end) of the `samples`-sample frame of n_views cameras (view-major buffers).  d_sum =
+// nullptr (sq_render_rows_device) keeps the fold in the workspace; the caller has checked everything that is specific to its own entry
+// point.  One camera takes the single-view kernels; more take their multi-view instantiations and the scene's camera table.
+int render_rows(sq_device_scene* s, const sq_camera* cam, int32_t n_views, int32_t samples, int32_t w, int32_t h, int32_t cast, sq_shard sh,
                 int32_t k_begin, int32_t k_end, float* d_sum, float* d_avg, uint8_t* d_rgb, void* hip_stream) {
     if (!s || !cam) return sq_set_error("null argument");
     if (samples < 1 || w < 1 || h < 1) return sq_set_error("samples, width and height must be positive (got %d, %d, %d)", samples, w, h);
@@ -1931,14 +2060,18 @@ int render_rows(sq_device_scene* s, const sq_camera* cam, int32_t samples, int32
     F.out_avg = d_avg; F.out_rgb = d_rgb;
     F.k_begin = k_begin; F.k_end = k_end; F.sum = d_sum;
     F.diag = s->opt_coresidency ? std::max(1, s->n_cu - 8) : 0;   // "beside" = while all but a handful of the CUs hold a live trace workgroup
+    F.n_views = n_views; F.view_pixels = rows * h; F.cams = nullptr;
     hipStream_t stream = (hipStream_t)hip_stream;
-    return s->small_index ? launch_frame<uint16_t>(s, F, stream) : launch_frame<uint32_t>(s, F, stream);
+    if (n_views == 1) return s->small_index ? launch_frame<uint16_t, false>(s, F, stream, nullptr) : launch_frame<uint32_t, false>(s, F, stream, nullptr);
+    if (ensure_cam_table(s, n_views)) return 1;
+    F.cams = s->d_cams;
+    return s->small_index ? launch_frame<uint16_t, true>(s, F, stream, cam) : launch_frame<uint32_t, true>(s, F, stream, cam);
 }
 }  // namespace
 
 extern "C" int sq_render_rows_device(sq_device_scene* s, const sq_camera* cam, int32_t samples, int32_t w, int32_t h,
                                      int32_t cast, sq_shard sh, float* d_avg, uint8_t* d_rgb, void* hip_stream) {
-    return render_rows(s, cam, samples, w, h, cast, sh, 0, samples, nullptr, d_avg, d_rgb, hip_stream);
+    return render_rows(s, cam, 1, samples, w, h, cast, sh, 0, samples, nullptr, d_avg, d_rgb, hip_stream);
 }
 
 extern "C" int sq_render_rows_device_range(sq_device_scene* s, const sq_camera* cam, int32_t samples, int32_t w, int32_t h,
@@ -1948,7 +2081,24 @@ extern "C" int sq_render_rows_device_range(sq_device_scene* s, const sq_camera* 
         return sq_set_error("bad sample range [%d, %d) of a %d-sample frame (need 0 <= k_begin < k_end <= samples)", k_begin, k_end, samples);
     if (!d_sum) return sq_set_error("d_sum is required: it carries the per-pixel fold from one range call to the next");
     if ((void*)d_sum == (void*)d_avg) return sq_set_error("d_sum and d_avg must be different buffers");
-    return render_rows(s, cam, samples, w, h, cast, sh, k_begin, k_end, d_sum, d_avg, d_rgb, hip_stream);
+    return render_rows(s, cam, 1, samples, w, h, cast, sh, k_begin, k_end, d_sum, d_avg, d_rgb, hip_stream);
+}
+
+extern "C" int sq_render_views_device(sq_device_scene* s, const sq_camera* cams, int32_t n_views, int32_t samples, int32_t w, int32_t h,
+                                      int32_t cast, sq_shard sh, int32_t k_begin, int32_t k_end,
+                                      float* d_sum, float* d_avg, uint8_t* d_rgb, void* hip_stream) {
+    if (!s) return sq_set_error("null argument");
+    if (!cams) return sq_set_error("cams is NULL");
+    if (n_views < 1) return sq_set_error("n_views must be at least 1 (got %d)", n_views);
+    if (k_begin < 0 || k_end <= k_begin || k_end > samples)
+        return sq_set_error("bad sample range [%d, %d) of a %d-sample frame (need 0 <= k_begin < k_end <= samples)", k_begin, k_end, samples);
+    if (!d_sum && (k_begin != 0 || k_end != samples))
+        return sq_set_error("d_sum is required for a part [%d, %d) of a %d-sample frame: it carries the per-pixel fold", k_begin, k_end, samples);
+    if (d_sum && (void*)d_sum == (void*)d_avg) return sq_set_error("d_sum and d_avg must be different buffers");
+    const int32_t rows = sq_shard_rows(w, sh);
+    if (rows > 0 && h > 0 && (int64_t)n_views * rows * h > INT32_MAX)   // pixel indices (px_pixel) are 32-bit
+        return sq_set_error("%d views of %d x %d pixels exceed 2^31 - 1 pixels in one call", n_views, rows, h);
+    return render_rows(s, cams, n_views, samples, w, h, cast, sh, k_begin, k_end, d_sum, d_avg, d_rgb, hip_stream);
 }
 
 extern "C" int sq_kernel_timing(sq_device_scene* s, double* avg_ms, int64_t* launches, const char** name) {

@@ -23,19 +23,21 @@ class DeviceScene:
     def set_option(self, key, value):
         N.check(N.lib().sq_set_option(self._h, key.encode(), int(value)))
 
-    def _outputs(self, w, h, shard, want_avg, want_rgb, stream, out_avg, out_rgb):
+    def _outputs(self, w, h, shard, want_avg, want_rgb, stream, out_avg, out_rgb, views=None):
         """(sq_shard, rows, out_avg, out_rgb, stream) of a render_rows* call: the shard's row count, the output tensors
-        (allocated unless given or not wanted) and the stream (default: the device's current one)."""
+        (allocated unless given or not wanted) and the stream (default: the device's current one).  views: the tensors get a
+        leading dimension of that many views (render_views)."""
         rb, si, ns = shard
         sh = N.Shard(int(w if rb is None else rb), int(si), int(ns))
         rows = N.lib().sq_shard_rows(w, sh)
         if rows < 0:
             raise N.SquiglyError(f"bad shard {shard}")
         dev = torch.device("cuda", self.device)
+        shape = (rows, h, 3) if views is None else (views, rows, h, 3)
         if want_avg and out_avg is None:
-            out_avg = torch.empty((rows, h, 3), dtype=torch.float32, device=dev)
+            out_avg = torch.empty(shape, dtype=torch.float32, device=dev)
         if want_rgb and out_rgb is None:
-            out_rgb = torch.empty((rows, h, 3), dtype=torch.uint8, device=dev)
+            out_rgb = torch.empty(shape, dtype=torch.uint8, device=dev)
         st = stream if stream is not None else torch.cuda.current_stream(dev)
         return sh, rows, out_avg, out_rgb, st
 
@@ -70,6 +72,33 @@ class DeviceScene:
                                  f"got {sums.dtype} {tuple(sums.shape)} on {sums.device}")
         N.check(N.lib().sq_render_rows_device_range(
             self._h, C.byref(cam), samples, w, h, int(bool(cast)), sh, int(k_begin), int(k_end), sums.data_ptr(),
+            out_avg.data_ptr() if out_avg is not None else None,
+            out_rgb.data_ptr() if out_rgb is not None else None,
+            C.c_void_p(st.cuda_stream)))
+        return out_avg, out_rgb
+
+    def render_views(self, cams, samples, w, h, cast=False, shard=(None, 0, 1), k_begin=0, k_end=None, sums=None, want_avg=True,
+                     want_rgb=True, stream=None, out_avg=None, out_rgb=None):
+        """Enqueue the frames of many cameras in one call (sq_render_views_device); returns (avg, rgb) CUDA tensors
+        [n_views, rows, h, 3].  View i is bit for bit render_rows_range of cams[i] with the same other arguments.
+
+        k_begin, k_end: the sample range, [0, samples) by default (k_end None = samples).  sums: float32 CUDA tensor
+        [n_views, rows, h, 3] carrying the per-pixel fold as in render_rows_range; it may be None only for [0, samples).
+        """
+        cams = list(cams)
+        if not cams:
+            raise ValueError("render_views needs at least one camera")
+        n = len(cams)
+        k_end = int(samples) if k_end is None else int(k_end)
+        sh, rows, out_avg, out_rgb, st = self._outputs(w, h, shard, want_avg, want_rgb, stream, out_avg, out_rgb, views=n)
+        if sums is not None and (tuple(sums.shape) != (n, rows, h, 3) or sums.dtype != torch.float32 or not sums.is_contiguous()
+                                 or sums.device != torch.device("cuda", self.device)):
+            raise N.SquiglyError(f"sums must be a contiguous float32 tensor of shape {(n, rows, h, 3)} on cuda:{self.device}, "
+                                 f"got {sums.dtype} {tuple(sums.shape)} on {sums.device}")
+        table = (N.Camera * n)(*cams)
+        N.check(N.lib().sq_render_views_device(
+            self._h, table, n, samples, w, h, int(bool(cast)), sh, int(k_begin), k_end,
+            sums.data_ptr() if sums is not None else None,
             out_avg.data_ptr() if out_avg is not None else None,
             out_rgb.data_ptr() if out_rgb is not None else None,
             C.c_void_p(st.cuda_stream)))

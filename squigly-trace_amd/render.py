@@ -61,6 +61,24 @@ def render_progressive(bih, cam, samples, dimensions, step, cast=False, device=0
         ds.close()
 
 
+def render_views_rgb8(bih, cams, samples, dimensions, cast=False, device=0) -> np.ndarray:
+    """The image of render_rgb8 for every camera of `cams`, rendered in one call (DeviceScene.render_views): shape (n, w, h, 3)
+    uint8, view i bit for bit render_rgb8 of cams[i]."""
+    cams = list(cams)
+    if not cams:
+        raise ValueError("render_views_rgb8 needs at least one camera")
+    import torch
+    from .device import DeviceScene
+    w, h = dimensions
+    ds = DeviceScene(bih, device)
+    try:
+        _, rgb = ds.render_views(cams, samples, w, h, cast=cast, want_avg=False)
+        torch.cuda.synchronize(ds.device)
+        return rgb.cpu().numpy()
+    finally:
+        ds.close()
+
+
 def render(bih, cam, settings: Settings):
     """Lib.render: compute the image and write it to settings.savePath."""
     img = render_rgb8(bih, cam, settings.samples, settings.dimensions, settings.cast)
