@@ -131,11 +131,33 @@ int sq_render_views_device(sq_device_scene* s, const sq_camera* cams, int32_t n_
                            int32_t cast, sq_shard sh, int32_t k_begin, int32_t k_end,
                            float* d_sum, float* d_avg, uint8_t* d_rgb, void* hip_stream);
 
+/* Ray queries on a resident scene: intersectBIH (src/BIH.hs:11,101-141), the `intersect` of Scene (src/Geometry.hs:62-65), of
+ * each of n rays.  d_org, d_dir: DEVICE float[n][3] on the scene's device.  Results, per ray:
+ *  d_tri   : required; the hit triangle's index in sq_scene.tris (leaf order = BIH.flatten, src/BIH.hs:50-52); -1 = Nothing.
+ *  d_dist  : optional; dist = norm (intersectPoint - origin) (src/Geometry.hs:71-75,141).
+ *  d_point : optional, float[n][3]; intersectPoint = o + t *^ d (src/Geometry.hs:134).
+ * point and dist are the expressions the traversal itself compares, bit for bit the reference's.  A miss writes tri = -1,
+ * dist = +inf and point = (+0, +0, +0).  Option "variant" picks the form: 2 (default) queues the rays in the workspace slots and
+ * runs one level of the planned trace kernel (options pool, resident, trace_blocks_per_cu, cull, profile, timing and slots act as
+ * for frames; a query runs in chunks of at most `slots` rays); 1 = one lane per ray, which takes the taller trees of the per-pixel
+ * kernel.  Every form gives the same bits.
+ * Refused with an error code before anything is enqueued (every buffer left as it was): s == NULL, n < 0, n > 0 with d_org, d_dir
+ * or d_tri NULL, any two of the given ranges overlapping, and the LDS-height limits of a frame of the same form.  n == 0 returns 0
+ * and enqueues nothing.  The call only enqueues work on hip_stream; it shares the scene's workspace, so the queries and frames of
+ * one scene must be ordered on one stream. */
+int sq_intersect_rays_device(sq_device_scene* s, const float* d_org, const float* d_dir, int64_t n,
+                             int32_t* d_tri, float* d_dist, float* d_point, void* hip_stream);
+/* The primary ray of every pixel of a shard (makeRay, src/Lib.hs:107-114), computed on the device exactly as the renderer traces it:
+ * sq_intersect_rays_device of them gives the renderer's own primary hits.  d_org, d_dir: DEVICE float[rows][h][3], laid out like
+ * d_avg, rows = sq_shard_rows(w, sh).  Refused: a NULL argument, w or h < 1, a bad shard, overlapping d_org and d_dir. */
+int sq_camera_rays_device(sq_device_scene* s, const sq_camera* cam, int32_t w, int32_t h, sq_shard sh,
+                          float* d_org, float* d_dir, void* hip_stream);
+
 /* Timing of the dominant kernel measured with hipEvents on the stream it was launched on:
  * average duration in ms over the launches since the last reset, and the launch count. */
 int  sq_kernel_timing(sq_device_scene* s, double* avg_ms, int64_t* launches, const char** kernel_name);
 void sq_kernel_timing_reset(sq_device_scene* s);
-/* Cumulative statistics of the trace kernel since the last reset (synchronises the device), n <= 32:
+/* Cumulative statistics of the trace kernel, over the render and query calls since the last reset (synchronises the device), n <= 32:
  * out[0] = rays traced; out[1..23] = lane-occupancy counters, rare-path counts and per-section wave cycles of the
  * profile build, filled only with option "profile" = 1 (tools/gpu_pool.py prints them). */
 int  sq_get_stats(sq_device_scene* s, uint64_t* out, int32_t n, int32_t reset);
@@ -190,10 +212,10 @@ int  sq_get_stats(sq_device_scene* s, uint64_t* out, int32_t n, int32_t reset);
  *                        (tmin, tmax) of the reference's slab test down the tree instead of testing both children from scratch */
 int  sq_set_option(sq_device_scene* s, const char* key, int64_t value);
 
-/* The launch plan of the scene's last sq_render_rows_device call (read only; diagnostics and tests): which kernel forms it
- * chose and the sizes they were chosen by.  Filled as the call plans the frame, so after a refused call (an error code
- * such as "BIH height ... needs ... LDS") it holds what was planned up to the refusal and launched = 0.  Returns non-zero
- * when the scene has not planned a frame yet. */
+/* The launch plan of the scene's last render or query call (read only; diagnostics and tests): which kernel forms it
+ * chose and the sizes they were chosen by.  Filled as the call plans the frame or query, so after a refused call (an error code
+ * such as "BIH height ... needs ... LDS") it holds what was planned up to the refusal and launched = 0.  A query
+ * (sq_intersect_rays_device) has primary_form SQ_PRIMARY_NONE.  Returns non-zero when the scene has not planned a call yet. */
 enum { SQ_FORM_PER_PIXEL = 0, SQ_FORM_RESIDENT = 1, SQ_FORM_STREAMING_SIX_WAVE = 2, SQ_FORM_STREAMING_PLAIN = 3 };
 enum { SQ_PRIMARY_NONE = 0, SQ_PRIMARY_PER_LANE = 1, SQ_PRIMARY_RESIDENT = 2, SQ_PRIMARY_POOLED = 3 };
 typedef struct {

@@ -20,7 +20,7 @@ def release_cached_memory() -> None:
 
 def __getattr__(name):
     # torch is only needed for the resident-scene path
-    if name in ("DeviceScene", "Progressive"):
+    if name in ("DeviceScene", "Progressive", "Hits"):
         from . import device
         return getattr(device, name)
     if name in ("dist",):

@@ -469,6 +469,70 @@ __global__ void __launch_bounds__(kBlock) sq_primary_store(const Frame F, const 
     }
 }
 
+// ----------------------------------------------------------------------------------------------
+// Ray queries (sq_intersect_rays_device): intersectBIH of caller-given rays, src/BIH.hs:101-141
+// ----------------------------------------------------------------------------------------------
+// One chunk of a query: n rays, [n][3] floats each for origin and direction; tri is required, dist and point optional.
+struct RayQuery {
+    const float* org; const float* dir;
+    int32_t* tri; float* dist; float* point;
+    long long n;
+};
+__device__ __forceinline__ f3 load3(const float* p, long long i) { return sq::mk(p[3 * i], p[3 * i + 1], p[3 * i + 2]); }
+// Maybe Intersection { intersectPoint = o + t *^ d, dist = norm (point - o), surface } (src/Geometry.hs:71-75,134,141), from the very
+// expressions the traversal compares (hit_dist); Nothing is tri = -1, dist = +inf, point = (+0, +0, +0).
+__device__ __forceinline__ void store_ray_hit(const RayQuery& Q, long long i, f3 o, f3 d, Hit h) {
+    const bool hit = h.tri >= 0;
+    Q.tri[i] = hit ? h.tri : -1;
+    if (Q.dist) Q.dist[i] = hit ? hit_dist(o, d, h.t) : __builtin_inff();
+    if (Q.point) {
+        const f3 p = hit ? o + sq::scale(h.t, d) : sq::mk(0, 0, 0);
+        float* q = Q.point + 3 * i; q[0] = p.x; q[1] = p.y; q[2] = p.z;
+    }
+}
+// Default form, before the trace launch: the chunk's rays into the first n workspace slots as first-level rays of a one-level
+// queue (k_count = 1, as sq_primary_gen does for the primary rays); W.n_active[48] is the launch's queue length.
+__global__ void __launch_bounds__(kBlock) sq_rays_stage(const RayQuery Q, const Work W) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) W.n_active[48] = (int32_t)Q.n;
+    for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < Q.n; i += (long long)gridDim.x * kBlock) {
+        const f3 o = load3(Q.org, i), d = load3(Q.dir, i);
+        W.state[i] = kRay1;
+        W.org[i] = make_float4(o.x, o.y, o.z, 0.0f);
+        W.dir[i] = make_float4(d.x, d.y, d.z, 0.0f);
+    }
+}
+// ... and after it: the hit the trace kernel left in each slot, with the caller's ray, into tri / dist / point.
+__global__ void __launch_bounds__(kBlock) sq_rays_store(const RayQuery Q, const Work W) {
+    for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < Q.n; i += (long long)gridDim.x * kBlock) {
+        const int2 hit = slot_hit(W.org[i]);
+        Hit h; h.t = __int_as_float(hit.x); h.tri = hit.y;
+        store_ray_hit(Q, i, load3(Q.org, i), load3(Q.dir, i), h);
+    }
+}
+// Variant 1: one lane per ray, the whole query in one kernel (the per-lane walk of sq_primary; the cross-check of the default form,
+// and the form that takes the taller trees of the per-pixel kernel).
+template <typename StackT>
+__global__ void __launch_bounds__(kBlock) sq_intersect_lanes(const SceneView S, const RayQuery Q) {
+    extern __shared__ float4 lds_raw[];
+    SQ_LDS StackT* stk = to_lds<StackT>(lds_raw) + threadIdx.x;
+    const long long i = (long long)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= Q.n) return;
+    const GlobalNodes N{ S.branches, S.cull_child, S.cull_child != nullptr };
+    const f3 o = load3(Q.org, i), d = load3(Q.dir, i);
+    store_ray_hit(Q, i, o, d, trace_one(S, N, o, d, stk, kBlock));
+}
+// sq_camera_rays_device: the primary ray of every pixel of a shard (makeRay, src/Lib.hs:107-114), by the renderer's own primary_dir,
+// laid out like a frame's d_avg ([rows][h][3], local row-major pixel index).
+__global__ void __launch_bounds__(kBlock) sq_camera_rays(const Frame F, float* org, float* dir, long long total) {
+    for (long long pix = (long long)blockIdx.x * kBlock + threadIdx.x; pix < total; pix += (long long)gridDim.x * kBlock) {
+        int y, x;
+        pixel_coords(F, pix, y, x);
+        const f3 d = primary_dir(F.cam_rot, F.w, F.h, y, x);
+        float* o = org + 3 * pix; o[0] = F.cam_pos[0]; o[1] = F.cam_pos[1]; o[2] = F.cam_pos[2];
+        float* q = dir + 3 * pix; q[0] = d.x; q[1] = d.y; q[2] = d.z;
+    }
+}
+
 // Multi-view frames: copies a chunk of cameras into the scene's camera table.  The cameras travel as kernel arguments, which are
 // captured when the launch is enqueued: the table is filled in stream order, and the caller's array is not read after the call.
 constexpr int kCamChunk = 64;                 // cameras per staging launch: 64 x 48 B = 3 KB of arguments (the limit is 4 KB)
@@ -1700,68 +1764,33 @@ int stage_cams(sq_device_scene* s, const Frame& F, const sq_camera* cams, hipStr
     return 0;
 }
 
-// MV: a multi-view frame; `cams` (host, F.n_views of them) are staged into the scene's camera table F.cams once the frame is planned.
+// Enqueues fn's launch; with option "timing" brackets it with hipEvents for sq_kernel_timing.
+template <typename Fn>
+int timed_launch(sq_device_scene* s, Fn&& fn, const char* name, hipStream_t on) {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (s->opt_timing) { SQ_HIP(hipEventCreate(&e0)); SQ_HIP(hipEventCreate(&e1)); SQ_HIP(hipEventRecord(e0, on)); }
+    fn();
+    SQ_HIP(hipGetLastError());
+    if (s->opt_timing) {
+        SQ_HIP(hipEventRecord(e1, on)); s->pending.emplace_back(e0, e1); s->last_kernel = name;
+        if (s->pending.size() > 8192) SQ_HIP(sq_kernel_timing(s, nullptr, nullptr, nullptr) ? hipErrorUnknown : hipSuccess);   // fold, bounded memory
+    }
+    return 0;
+}
+
+// The persistent trace kernel of a frame's wavefront pipeline or of a ray query: its form and launch geometry (plan_trace).
+struct TracePlan {
+    bool resident = false, pool = false;
+    int n_lds = 0, stack_cap = 0, trace_blocks = 0, trace_threads = 0;
+    const void* trace_fn = nullptr;
+    size_t tr_lds = 0;
+};
+// Chooses the trace form -- resident, streaming six-wave or streaming plain -- its LDS layout and workgroups per CU, and fills the
+// trace fields of s->plan.  Refuses (an error code, nothing enqueued) a tree whose stacks do not fit the streaming form's LDS.
+// MV: the frame's primary-ray kernel whose static LDS is checked with the resident kernels (a query plans with MV = false).
 template <typename StackT, bool MV>
-int launch_frame(sq_device_scene* s, const Frame& F, hipStream_t stream, const sq_camera* cams) {
-    SceneView S = s->view;
-    if (!s->opt_cull) S.cull_o2max = -1.0f;                            // no ray is inside the culling limits: every leaf is tested
-    if (!s->opt_incremental) S.incremental_ok = 0;                     // resident form: every branch step tests both children from the branch's own box
-    const long long pixels = (long long)F.n_views * F.local_rows * F.h;   // every view's pixels, view-major
-    const int stack_cap = std::max(S.height, 1);
-    const size_t px_lds = (size_t)kBlock * stack_cap * sizeof(StackT);
-    const long long px_blocks = (pixels + kBlock - 1) / kBlock;
+int plan_trace(sq_device_scene* s, const SceneView& S, int stack_cap, TracePlan& T) {
     sq_plan& P = s->plan;
-    P = sq_plan{};
-    P.variant = (int32_t)s->opt_variant; P.stack_word_bytes = (int32_t)sizeof(StackT); P.height = S.height; P.stack_cap = stack_cap;
-    P.pixel_lds_bytes = (int32_t)px_lds; P.packed_leaves = S.packed_leaves; P.n_emitters = S.n_emitters;
-    P.trace_form = SQ_FORM_PER_PIXEL; P.primary_form = SQ_PRIMARY_NONE;
-    s->has_plan = true;
-    if (px_blocks > 0x7fffffffLL) return sq_set_error("image too large for one launch");
-    if (px_lds > 160 * 1024) return sq_set_error("BIH height %d needs %zu B of LDS stack per workgroup (max 163840)", S.height, px_lds);
-    auto timed = [&](auto&& fn, const char* name, hipStream_t on) -> int {
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        if (s->opt_timing) { SQ_HIP(hipEventCreate(&e0)); SQ_HIP(hipEventCreate(&e1)); SQ_HIP(hipEventRecord(e0, on)); }
-        fn();
-        SQ_HIP(hipGetLastError());
-        if (s->opt_timing) {
-            SQ_HIP(hipEventRecord(e1, on)); s->pending.emplace_back(e0, e1); s->last_kernel = name;
-            if (s->pending.size() > 8192) SQ_HIP(sq_kernel_timing(s, nullptr, nullptr, nullptr) ? hipErrorUnknown : hipSuccess);   // fold, bounded memory
-        }
-        return 0;
-    };
-    if (s->opt_variant == 1 || F.cast) {
-        if (px_lds > 64 * 1024) SQ_HIP(hipFuncSetAttribute((const void*)sq_render_pixels<StackT, MV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)px_lds));
-        P.launched = 1;
-        if (stage_cams(s, F, cams, stream)) return 1;
-        return timed([&] { hipLaunchKernelGGL((sq_render_pixels<StackT, MV>), dim3((unsigned)px_blocks), dim3(kBlock), px_lds, stream, S, F); }, "sq_render_pixels", stream);
-    }
-    // ---- wavefront pipeline ----
-    const int n_call = F.k_end - F.k_begin;                              // the samples this call renders (a whole frame: F.samples)
-    // at least one sample of every pixel per batch, never more slots than the call has samples
-    const int64_t slots = std::max<int64_t>(pixels, std::min<int64_t>(s->opt_slots, (int64_t)pixels * n_call));
-    if (ensure_workspace(s, pixels, slots)) return 1;
-    const Work& W = s->work;
-    const int64_t have_slots = W.slot_capacity;
-    // Overlapped schedule: the sample batches alternate between two halves of the workspace ("tracks"); every
-    // trace launch stays on the caller's stream, in the order T1(a) T1(b) T2(a) T2(b), while the per-sample
-    // kernels (RNG + bounce, shading, accumulation) run on a second stream beside them, ordered by events.
-    // Opt-in (sq_set_option "overlap"): measured +3 % on the headline frame (105.5 -> 102.3 ms) -- the kernels do
-    // run side by side, but the chip is VALU-bound as a whole, so each slows the other down by what it gains;
-    // and trace-launch durations then include that interference, which blurs the per-kernel roofline figure.
-    const bool overlap = s->opt_overlap && n_call >= 2 && have_slots >= 2 * pixels;
-    const int tracks = overlap ? 2 : 1;
-    const int64_t track_slots = have_slots / tracks;
-    Work Wt[2] = { W, W };
-    if (overlap) {
-        Work& V = Wt[1];
-        V.state += track_slots; V.org += track_slots; V.dir += track_slots; V.rad += 3 * track_slots;
-        V.head[0] = W.n_active + 64 + 16; V.head[1] = W.n_active + 64 + 32;
-    }
-    // samples per batch: as many as a track holds, split evenly (few large launches: a small trace launch
-    // wastes its ramp-up and drain, and the second-bounce launches only carry a few percent of the slots)
-    const int max_batch = (int)std::max<int64_t>(1, std::min<int64_t>(n_call, track_slots / pixels));
-    const int n_batches = std::max(tracks, (n_call + max_batch - 1) / max_batch);
-    const int batch = (n_call + n_batches - 1) / n_batches;
     // persistent trace kernel geometry.  Resident form: the whole scene (branches, leaves, unique vertices,
     // 16-bit indexed triangles) plus every lane's stack fits in the 160 KB of one CU -> one 1024-thread
     // workgroup per CU, no global traffic except ray fetch and hit store.  Streaming form otherwise.
@@ -1810,7 +1839,6 @@ int launch_frame(sq_device_scene* s, const Frame& F, hipStream_t stream, const s
     const size_t tr_lds = L.total;
     P.trace_form = resident ? SQ_FORM_RESIDENT : trace_fn == (const void*)sq_trace_rays_dense<StackT> ? SQ_FORM_STREAMING_SIX_WAVE : SQ_FORM_STREAMING_PLAIN;
     P.blocks_per_cu = trace_blocks / s->n_cu; P.n_lds = n_lds; P.trace_lds_bytes = (int32_t)tr_lds;
-    P.primary_form = (s->opt_primary_pooled && pool) ? SQ_PRIMARY_POOLED : (resident && s->opt_primary_resident) ? SQ_PRIMARY_RESIDENT : SQ_PRIMARY_PER_LANE;
     if (tr_lds > 64 * 1024) SQ_HIP(hipFuncSetAttribute(trace_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tr_lds));
     static bool static_lds_checked = false;                           // per StackT instantiation; once per process is enough
     if (resident && !static_lds_checked) {
@@ -1828,6 +1856,93 @@ int launch_frame(sq_device_scene* s, const Frame& F, hipStream_t stream, const s
         }
         static_lds_checked = true;
     }
+    T.resident = resident; T.pool = pool; T.n_lds = n_lds; T.stack_cap = stack_cap;
+    T.trace_blocks = trace_blocks; T.trace_threads = trace_threads; T.trace_fn = trace_fn; T.tr_lds = tr_lds;
+    return 0;
+}
+
+// One launch of the planned trace kernel over the queue of W: *W.n_active x kc slots (+ *W.n_active front slots with the mirror
+// rays).  queue_rays x kc sizes its reservations: a frame's pixels (every pixel may be active), a query chunk's rays.
+int launch_trace_kernel(sq_device_scene* s, const SceneView& S, const TracePlan& T, const Work& W, int64_t queue_rays, int kc, int level,
+                        hipStream_t on, bool with_mirror_rays) {
+    const bool resident = T.resident;
+    const int trace_blocks = T.trace_blocks, trace_threads = T.trace_threads;
+    // a launch with few slots (the per-pixel mirror rays) takes small reservations, or only a few waves get any
+    const int max_chunk = resident ? kChunkResident : kChunkStreaming;
+    const int64_t per_wave = queue_rays * (int64_t)kc / std::max(1, trace_blocks * (trace_threads / 64));
+    const int chunk = (int)std::min<int64_t>(max_chunk, std::max<int64_t>(64, (per_wave / 8) / 64 * 64));
+    // queue order: a pixel's samples in a row pays once the triangles no longer fit the L2s (rays that start at one point
+    // share their first leaves: 1M-triangle scene +2.5 %), and costs 1-7 % below that (strided queue reads)
+    const bool pixel_major = s->opt_pixel_major < 0 ? (!resident && (size_t)S.n_tris * sizeof(DevTri) > ((size_t)4 << 20)) : s->opt_pixel_major != 0;
+    int guide_shift = 2;                                            // log2(4 x waves of the launch), rounded up
+    while ((1ll << guide_shift) < 4ll * trace_blocks * (trace_threads / 64)) ++guide_shift;
+    if (!((s->opt_guided >> level) & 1)) guide_shift = 62;         // bit 0: first bounce level (and the mirror / primary launches), bit 1: second
+    TraceArgs A{ W.org, W.dir, W.state, level == 0 ? (int32_t)kRay1 : (int32_t)kRay2, (long long)s->work.slot_capacity, with_mirror_rays ? 1 : 0,
+                 W.n_active, kc, W.head[level], T.n_lds, T.stack_cap, (int32_t)s->opt_straggler, chunk, guide_shift,
+                 (int32_t)s->opt_refill_min, (int32_t)s->opt_flush_min, (int32_t)s->opt_descend_extra, (int32_t)s->opt_descend_lanes,
+                 (int32_t)(s->opt_coresidency ? 1 : 0), (int32_t)s->opt_trace_prio, (int32_t)pixel_major, W.stats };
+    SceneView Sv = S;
+    return timed_launch(s, [&] {
+        void* kargs[] = { (void*)&Sv, (void*)&A };
+        (void)hipLaunchKernel(T.trace_fn, dim3(trace_blocks), dim3(trace_threads), kargs, T.tr_lds, on);
+    }, "sq_trace_rays", on);
+}
+
+// MV: a multi-view frame; `cams` (host, F.n_views of them) are staged into the scene's camera table F.cams once the frame is planned.
+template <typename StackT, bool MV>
+int launch_frame(sq_device_scene* s, const Frame& F, hipStream_t stream, const sq_camera* cams) {
+    SceneView S = s->view;
+    if (!s->opt_cull) S.cull_o2max = -1.0f;                            // no ray is inside the culling limits: every leaf is tested
+    if (!s->opt_incremental) S.incremental_ok = 0;                     // resident form: every branch step tests both children from the branch's own box
+    const long long pixels = (long long)F.n_views * F.local_rows * F.h;   // every view's pixels, view-major
+    const int stack_cap = std::max(S.height, 1);
+    const size_t px_lds = (size_t)kBlock * stack_cap * sizeof(StackT);
+    const long long px_blocks = (pixels + kBlock - 1) / kBlock;
+    sq_plan& P = s->plan;
+    P = sq_plan{};
+    P.variant = (int32_t)s->opt_variant; P.stack_word_bytes = (int32_t)sizeof(StackT); P.height = S.height; P.stack_cap = stack_cap;
+    P.pixel_lds_bytes = (int32_t)px_lds; P.packed_leaves = S.packed_leaves; P.n_emitters = S.n_emitters;
+    P.trace_form = SQ_FORM_PER_PIXEL; P.primary_form = SQ_PRIMARY_NONE;
+    s->has_plan = true;
+    if (px_blocks > 0x7fffffffLL) return sq_set_error("image too large for one launch");
+    if (px_lds > 160 * 1024) return sq_set_error("BIH height %d needs %zu B of LDS stack per workgroup (max 163840)", S.height, px_lds);
+    if (s->opt_variant == 1 || F.cast) {
+        if (px_lds > 64 * 1024) SQ_HIP(hipFuncSetAttribute((const void*)sq_render_pixels<StackT, MV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)px_lds));
+        P.launched = 1;
+        if (stage_cams(s, F, cams, stream)) return 1;
+        return timed_launch(s, [&] { hipLaunchKernelGGL((sq_render_pixels<StackT, MV>), dim3((unsigned)px_blocks), dim3(kBlock), px_lds, stream, S, F); }, "sq_render_pixels", stream);
+    }
+    // ---- wavefront pipeline ----
+    const int n_call = F.k_end - F.k_begin;                              // the samples this call renders (a whole frame: F.samples)
+    // at least one sample of every pixel per batch, never more slots than the call has samples
+    const int64_t slots = std::max<int64_t>(pixels, std::min<int64_t>(s->opt_slots, (int64_t)pixels * n_call));
+    if (ensure_workspace(s, pixels, slots)) return 1;
+    const Work& W = s->work;
+    const int64_t have_slots = W.slot_capacity;
+    // Overlapped schedule: the sample batches alternate between two halves of the workspace ("tracks"); every
+    // trace launch stays on the caller's stream, in the order T1(a) T1(b) T2(a) T2(b), while the per-sample
+    // kernels (RNG + bounce, shading, accumulation) run on a second stream beside them, ordered by events.
+    // Opt-in (sq_set_option "overlap"): measured +3 % on the headline frame (105.5 -> 102.3 ms) -- the kernels do
+    // run side by side, but the chip is VALU-bound as a whole, so each slows the other down by what it gains;
+    // and trace-launch durations then include that interference, which blurs the per-kernel roofline figure.
+    const bool overlap = s->opt_overlap && n_call >= 2 && have_slots >= 2 * pixels;
+    const int tracks = overlap ? 2 : 1;
+    const int64_t track_slots = have_slots / tracks;
+    Work Wt[2] = { W, W };
+    if (overlap) {
+        Work& V = Wt[1];
+        V.state += track_slots; V.org += track_slots; V.dir += track_slots; V.rad += 3 * track_slots;
+        V.head[0] = W.n_active + 64 + 16; V.head[1] = W.n_active + 64 + 32;
+    }
+    // samples per batch: as many as a track holds, split evenly (few large launches: a small trace launch
+    // wastes its ramp-up and drain, and the second-bounce launches only carry a few percent of the slots)
+    const int max_batch = (int)std::max<int64_t>(1, std::min<int64_t>(n_call, track_slots / pixels));
+    const int n_batches = std::max(tracks, (n_call + max_batch - 1) / max_batch);
+    const int batch = (n_call + n_batches - 1) / n_batches;
+    TracePlan TP;
+    if (plan_trace<StackT, MV>(s, S, stack_cap, TP)) return 1;
+    const bool resident = TP.resident, pool = TP.pool;
+    P.primary_form = (s->opt_primary_pooled && pool) ? SQ_PRIMARY_POOLED : (resident && s->opt_primary_resident) ? SQ_PRIMARY_RESIDENT : SQ_PRIMARY_PER_LANE;
     P.launched = 1;                                                    // planned; what follows fails only on HIP errors
     // nothing is enqueued before this point, so a refusal above leaves every buffer as it was
     if (stage_cams(s, F, cams, stream)) return 1;                       // multi-view: before every kernel that reads the table (e_setup below)
@@ -1864,24 +1979,7 @@ int launch_frame(sq_device_scene* s, const Frame& F, hipStream_t stream, const s
         return dim3((unsigned)bx, (unsigned)ks);
     };
     auto launch_trace = [&](const Work& W, int kc, int level, hipStream_t on, bool with_mirror_rays = false) -> int {
-        // a launch with few slots (the per-pixel mirror rays) takes small reservations, or only a few waves get any
-        const int max_chunk = resident ? kChunkResident : kChunkStreaming;
-        const int64_t per_wave = pixels * (int64_t)kc / std::max(1, trace_blocks * (trace_threads / 64));
-        const int chunk = (int)std::min<int64_t>(max_chunk, std::max<int64_t>(64, (per_wave / 8) / 64 * 64));
-        // queue order: a pixel's samples in a row pays once the triangles no longer fit the L2s (rays that start at one point
-        // share their first leaves: 1M-triangle scene +2.5 %), and costs 1-7 % below that (strided queue reads)
-        const bool pixel_major = s->opt_pixel_major < 0 ? (!resident && (size_t)S.n_tris * sizeof(DevTri) > ((size_t)4 << 20)) : s->opt_pixel_major != 0;
-        int guide_shift = 2;                                            // log2(4 x waves of the launch), rounded up
-        while ((1ll << guide_shift) < 4ll * trace_blocks * (trace_threads / 64)) ++guide_shift;
-        if (!((s->opt_guided >> level) & 1)) guide_shift = 62;         // bit 0: first bounce level (and the mirror / primary launches), bit 1: second
-        TraceArgs A{ W.org, W.dir, W.state, level == 0 ? (int32_t)kRay1 : (int32_t)kRay2, (long long)s->work.slot_capacity, with_mirror_rays ? 1 : 0,
-                     W.n_active, kc, W.head[level], n_lds, stack_cap, (int32_t)s->opt_straggler, chunk, guide_shift,
-                     (int32_t)s->opt_refill_min, (int32_t)s->opt_flush_min, (int32_t)s->opt_descend_extra, (int32_t)s->opt_descend_lanes,
-                     (int32_t)(s->opt_coresidency ? 1 : 0), (int32_t)s->opt_trace_prio, (int32_t)pixel_major, W.stats };
-        return timed([&] {
-            void* kargs[] = { (void*)&S, (void*)&A };
-            (void)hipLaunchKernel(trace_fn, dim3(trace_blocks), dim3(trace_threads), kargs, tr_lds, on);
-        }, "sq_trace_rays", on);
+        return launch_trace_kernel(s, S, TP, W, pixels, kc, level, on, with_mirror_rays);
     };
     if (primary_pooled) {
         Work Wp = W; Wp.n_active = W.n_active + 48;                     // the launch's queue is the shard's pixels, not the active ones
@@ -2099,6 +2197,110 @@ extern "C" int sq_render_views_device(sq_device_scene* s, const sq_camera* cams,
     if (rows > 0 && h > 0 && (int64_t)n_views * rows * h > INT32_MAX)   // pixel indices (px_pixel) are 32-bit
         return sq_set_error("%d views of %d x %d pixels exceed 2^31 - 1 pixels in one call", n_views, rows, h);
     return render_rows(s, cams, n_views, samples, w, h, cast, sh, k_begin, k_end, d_sum, d_avg, d_rgb, hip_stream);
+}
+
+namespace {
+constexpr long long kLaneChunk = 1ll << 30;   // rays per launch of the per-lane query kernel (2^22 workgroups)
+// The query's rays [c0, c0 + m).
+RayQuery query_part(const RayQuery& Q, long long c0, long long m) {
+    RayQuery C = Q;
+    C.org += 3 * c0; C.dir += 3 * c0; C.tri += c0;
+    if (C.dist) C.dist += c0;
+    if (C.point) C.point += 3 * c0;
+    C.n = m;
+    return C;
+}
+// sq_intersect_rays_device once its arguments are checked (Q.n > 0).  Plans like a frame (s->plan, the same LDS refusals), then
+// variant 1 runs the per-lane kernel and the default form runs chunks of stage -> one level of the trace kernel -> store.
+template <typename StackT>
+int intersect_rays(sq_device_scene* s, const RayQuery& Q, hipStream_t stream) {
+    SceneView S = s->view;
+    if (!s->opt_cull) S.cull_o2max = -1.0f;                            // as in launch_frame
+    if (!s->opt_incremental) S.incremental_ok = 0;
+    const int stack_cap = std::max(S.height, 1);
+    const size_t px_lds = (size_t)kBlock * stack_cap * sizeof(StackT);
+    sq_plan& P = s->plan;
+    P = sq_plan{};
+    P.variant = (int32_t)s->opt_variant; P.stack_word_bytes = (int32_t)sizeof(StackT); P.height = S.height; P.stack_cap = stack_cap;
+    P.pixel_lds_bytes = (int32_t)px_lds; P.packed_leaves = S.packed_leaves; P.n_emitters = S.n_emitters;
+    P.trace_form = SQ_FORM_PER_PIXEL; P.primary_form = SQ_PRIMARY_NONE;
+    s->has_plan = true;
+    if (s->opt_variant == 1) {
+        if (px_lds > 160 * 1024) return sq_set_error("BIH height %d needs %zu B of LDS stack per workgroup (max 163840)", S.height, px_lds);
+        if (px_lds > 64 * 1024) SQ_HIP(hipFuncSetAttribute((const void*)sq_intersect_lanes<StackT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)px_lds));
+        P.launched = 1;
+        for (long long c0 = 0; c0 < Q.n; c0 += kLaneChunk) {
+            const RayQuery C = query_part(Q, c0, std::min(kLaneChunk, Q.n - c0));
+            if (timed_launch(s, [&] { hipLaunchKernelGGL(sq_intersect_lanes<StackT>, dim3((unsigned)((C.n + kBlock - 1) / kBlock)), dim3(kBlock), px_lds, stream, S, C); },
+                             "sq_intersect_lanes", stream)) return 1;
+        }
+        return 0;
+    }
+    TracePlan TP;
+    if (plan_trace<StackT, false>(s, S, stack_cap, TP)) return 1;
+    // Chunks of at most `slots` rays (and what the workspace holds; the option caps the slots at 2^29, so a chunk's queue positions and
+    // the trace kernel's 32-bit cursor never overflow).  One slot per ray: 45 B, against 40 B of caller arrays per ray.
+    if (ensure_workspace(s, 1, std::min<int64_t>(s->opt_slots, Q.n))) return 1;
+    const Work& W = s->work;
+    const long long chunk = std::min<long long>(s->opt_slots, W.slot_capacity);
+    Work Wq = W; Wq.n_active = W.n_active + 48;                         // the launch's queue length, written by sq_rays_stage
+    P.launched = 1;                                                    // planned; what follows fails only on HIP errors
+    for (long long c0 = 0; c0 < Q.n; c0 += chunk) {
+        const RayQuery C = query_part(Q, c0, std::min(chunk, Q.n - c0));
+        const dim3 grid((unsigned)std::min<long long>((C.n + kBlock - 1) / kBlock, (long long)s->n_cu * 8));
+        SQ_HIP(hipMemsetAsync(W.head[0], 0, 32 * sizeof(int32_t), stream));     // both dequeue cursors
+        hipLaunchKernelGGL(sq_rays_stage, grid, dim3(kBlock), 0, stream, C, W);
+        SQ_HIP(hipGetLastError());
+        if (launch_trace_kernel(s, S, TP, Wq, C.n, 1, 0, stream, false)) return 1;
+        hipLaunchKernelGGL(sq_rays_store, grid, dim3(kBlock), 0, stream, C, W);
+        SQ_HIP(hipGetLastError());
+    }
+    return 0;
+}
+bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + nb && y < x + na;
+}
+}  // namespace
+
+extern "C" int sq_intersect_rays_device(sq_device_scene* s, const float* d_org, const float* d_dir, int64_t n,
+                                        int32_t* d_tri, float* d_dist, float* d_point, void* hip_stream) {
+    if (!s) return sq_set_error("null argument");
+    if (n < 0) return sq_set_error("n must be >= 0 (got %lld)", (long long)n);
+    if (n == 0) return 0;
+    if (!d_org || !d_dir || !d_tri) return sq_set_error("d_org, d_dir and d_tri are required");
+    if (n > (INT64_MAX / 12)) return sq_set_error("%lld rays are too many", (long long)n);
+    const size_t n3 = (size_t)n * 12, n1 = (size_t)n * 4;
+    const struct { const char* name; const void* p; size_t bytes; } r[5] = {
+        { "d_org", d_org, n3 }, { "d_dir", d_dir, n3 }, { "d_tri", d_tri, n1 }, { "d_dist", d_dist, n1 }, { "d_point", d_point, n3 } };
+    for (int i = 0; i < 5; ++i)
+        for (int j = i + 1; j < 5; ++j)
+            if (r[i].p && r[j].p && ranges_overlap(r[i].p, r[i].bytes, r[j].p, r[j].bytes))
+                return sq_set_error("%s and %s overlap", r[i].name, r[j].name);
+    SQ_HIP(hipSetDevice(s->device));
+    const RayQuery Q{ d_org, d_dir, d_tri, d_dist, d_point, (long long)n };
+    hipStream_t stream = (hipStream_t)hip_stream;
+    return s->small_index ? intersect_rays<uint16_t>(s, Q, stream) : intersect_rays<uint32_t>(s, Q, stream);
+}
+
+extern "C" int sq_camera_rays_device(sq_device_scene* s, const sq_camera* cam, int32_t w, int32_t h, sq_shard sh,
+                                     float* d_org, float* d_dir, void* hip_stream) {
+    if (!s || !cam || !d_org || !d_dir) return sq_set_error("null argument");
+    if (w < 1 || h < 1) return sq_set_error("width and height must be positive (got %d, %d)", w, h);
+    const int32_t rows = sq_shard_rows(w, sh);
+    if (rows < 0) return sq_set_error("bad shard {row_block=%d, shard=%d, n_shards=%d}", sh.row_block, sh.shard, sh.n_shards);
+    if (rows == 0) return 0;                    // an empty shard has no pixels
+    const long long total = (long long)rows * h;
+    if (ranges_overlap(d_org, (size_t)total * 12, d_dir, (size_t)total * 12)) return sq_set_error("d_org and d_dir overlap");
+    SQ_HIP(hipSetDevice(s->device));
+    Frame F{};
+    std::memcpy(F.cam_pos, cam->pos, sizeof F.cam_pos);
+    std::memcpy(F.cam_rot, cam->rot, sizeof F.cam_rot);
+    F.w = w; F.h = h; F.row_block = sh.row_block; F.shard = sh.shard; F.n_shards = sh.n_shards; F.local_rows = rows;
+    const dim3 grid((unsigned)std::min<long long>((total + kBlock - 1) / kBlock, (long long)s->n_cu * 8));
+    hipLaunchKernelGGL(sq_camera_rays, grid, dim3(kBlock), 0, (hipStream_t)hip_stream, F, d_org, d_dir, total);
+    SQ_HIP(hipGetLastError());
+    return 0;
 }
 
 extern "C" int sq_kernel_timing(sq_device_scene* s, double* avg_ms, int64_t* launches, const char** name) {

@@ -3,11 +3,28 @@
 PyTorch is used only for device memory and streams (plumbing); every pixel is produced by the HIP
 kernels in csrc/sq_device.hip through the C-ABI of include/squigly_hip.h.
 """
+import collections
 import ctypes as C
 
 import torch
 
 from . import _native as N
+
+Hits = collections.namedtuple("Hits", ["tri", "dist", "point"])
+Hits.__doc__ = """Results of DeviceScene.intersect: Maybe Intersection (src/Geometry.hs:71-75) per ray; tri = -1 is Nothing."""
+
+
+def _ray_shape(origins, directions):
+    """The common [..., 3] shape of a query's origins and directions; SquiglyError before any device work otherwise."""
+    shapes = []
+    for name, a in (("origins", origins), ("directions", directions)):
+        shape = tuple(a.shape) if hasattr(a, "shape") else tuple(torch.as_tensor(a).shape)
+        if len(shape) < 1 or shape[-1] != 3:
+            raise N.SquiglyError(f"{name} must have shape [..., 3], got {shape}")
+        shapes.append(shape)
+    if shapes[0] != shapes[1]:
+        raise N.SquiglyError(f"origins {shapes[0]} and directions {shapes[1]} must have the same shape")
+    return shapes[0]
 
 
 class DeviceScene:
@@ -103,6 +120,49 @@ class DeviceScene:
             out_rgb.data_ptr() if out_rgb is not None else None,
             C.c_void_p(st.cuda_stream)))
         return out_avg, out_rgb
+
+    def intersect(self, origins, directions, want_dist=True, want_point=True, stream=None, out=None):
+        """intersectBIH of each ray (sq_intersect_rays_device); returns Hits(tri, dist, point) CUDA tensors, enqueued on `stream`.
+
+        origins, directions: any [..., 3] arrays of one shape (numpy, a CPU or CUDA tensor, lists); they are converted to
+        contiguous float32 on this device, so float64 input is rounded to the nearest float32 first.  tri (int32) and dist
+        (float32) have the leading shape, point (float32) the whole shape; tri is the index into bih.tris (leaf order), -1 on a
+        miss, where dist = +inf and point = (+0, +0, +0).  want_dist / want_point = False leave that field None.
+        out: Hits whose tensors (contiguous, right shape and dtype, on this device; None = allocate) receive the results.
+        """
+        shape = _ray_shape(origins, directions)
+        dev = torch.device("cuda", self.device)
+        st = stream if stream is not None else torch.cuda.current_stream(dev)
+        lead = shape[:-1]
+        out = Hits(*(out if out is not None else (None, None, None)))
+        for name, t, want, tshape, dtype in (("tri", out.tri, True, lead, torch.int32), ("dist", out.dist, want_dist, lead, torch.float32),
+                                             ("point", out.point, want_point, shape, torch.float32)):
+            if t is not None and want and (tuple(t.shape) != tuple(tshape) or t.dtype != dtype or not t.is_contiguous() or t.device != dev):
+                raise N.SquiglyError(f"out.{name} must be a contiguous {dtype} tensor of shape {tuple(tshape)} on {dev}, "
+                                     f"got {t.dtype} {tuple(t.shape)} on {t.device}")
+        with torch.cuda.stream(st):      # temporaries are allocated and freed in the order of the call's stream
+            o = torch.as_tensor(origins, device=dev).to(torch.float32).contiguous()
+            d = torch.as_tensor(directions, device=dev).to(torch.float32).contiguous()
+            tri = out.tri if out.tri is not None else torch.empty(lead, dtype=torch.int32, device=dev)
+            dist = (out.dist if out.dist is not None else torch.empty(lead, dtype=torch.float32, device=dev)) if want_dist else None
+            point = (out.point if out.point is not None else torch.empty(shape, dtype=torch.float32, device=dev)) if want_point else None
+            N.check(N.lib().sq_intersect_rays_device(
+                self._h, o.data_ptr(), d.data_ptr(), int(o.numel() // 3), tri.data_ptr(),
+                dist.data_ptr() if dist is not None else None, point.data_ptr() if point is not None else None,
+                C.c_void_p(st.cuda_stream)))
+        return Hits(tri, dist, point)
+
+    def camera_rays(self, cam, w, h, shard=(None, 0, 1), stream=None):
+        """The primary ray of every pixel of the shard, as the renderer traces it (sq_camera_rays_device): (origins,
+        directions) float32 CUDA tensors [rows, h, 3].  ds.intersect(*ds.camera_rays(cam, w, h)) is the frame's depth and
+        triangle-id buffer."""
+        sh, rows, _, _, st = self._outputs(w, h, shard, False, False, stream, None, None)
+        dev = torch.device("cuda", self.device)
+        o = torch.empty((rows, h, 3), dtype=torch.float32, device=dev)
+        d = torch.empty((rows, h, 3), dtype=torch.float32, device=dev)
+        N.check(N.lib().sq_camera_rays_device(self._h, C.byref(cam), int(w), int(h), sh, o.data_ptr(), d.data_ptr(),
+                                              C.c_void_p(st.cuda_stream)))
+        return o, d
 
     def enable_timing(self, on=True):
         """Bracket every launch of the dominant kernel with hipEvents (read back by kernel_timing)."""
