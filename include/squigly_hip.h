@@ -114,6 +114,51 @@ int sq_render_rows_device_range(sq_device_scene* s, const sq_camera* cam, int32_
                                 int32_t cast, sq_shard sh, int32_t k_begin, int32_t k_end,
                                 float* d_sum, float* d_avg, uint8_t* d_rgb, void* hip_stream);
 
+/* Adaptive sampling, the mechanism: sq_render_rows_device_range for the pixels of a mask only, with the statistics a stopping rule
+ * needs.  All buffers are DEVICE buffers laid out like d_avg (rows = sq_shard_rows(w, sh); d_mask, d_count: rows*h entries; d_sum,
+ * d_sum2, d_avg: rows*h*3 floats; d_rgb: rows*h*3 bytes).  A pixel p is LIVE in the call iff
+ *      (d_mask == NULL || d_mask[p] != 0)  and  (k_begin == 0 || d_count == NULL || d_count[p] == k_begin).
+ * The second clause keeps every fold a prefix of the pixel's samples: a pixel that an earlier range left out cannot resume with a
+ * gap.  Without d_count the caller answers for that.
+ *  live pixel : exactly what sq_render_rows_device_range does (d_sum required, in/out; d_avg / d_rgb optional, (1 / (float)k_end) *^
+ *          sum and its tonemap; a primary miss gives +0 sums, avg 0, rgb 0), and in addition
+ *          d_sum2  (optional, in/out like d_sum; ignored on entry when k_begin == 0): per channel the left fold q = q + r * r over
+ *                  the pixel's sample radiances r in sample order, the product rounded to fp32 before the add; +0 for a miss;
+ *          d_count (optional): set to k_end.
+ *          The seed of sample k does not depend on the call (src/Lib.hs:85), so a pixel that stops after n samples holds bit for
+ *          bit the reference's fold over the first n samples of the `samples`-sample frame.
+ *  dead pixel : nothing is written, in any of the five output buffers (the call clears nothing up front), and it costs no ray, no
+ *          random number and no slot.  All live pixels advance in lockstep over [k_begin, k_end).
+ * With d_mask, d_sum2 and d_count all NULL the call is sq_render_rows_device_range: same bits, same launches.  A call in which no
+ * pixel is live is valid, returns 0 and changes no buffer; the call cannot know that without waiting for the device, so it enqueues
+ * its (empty) launches all the same and sq_last_plan reports launched = 1.
+ * Refused before anything is enqueued (every buffer left as it was): everything sq_render_rows_device_range refuses, and any two
+ * of the given buffers overlapping.  Works with every option sq_render_rows_device_range works with; multi-view frames have no
+ * masked form. */
+int sq_render_rows_device_masked(sq_device_scene* s, const sq_camera* cam, int32_t samples, int32_t w, int32_t h,
+                                 int32_t cast, sq_shard sh, int32_t k_begin, int32_t k_end,
+                                 const uint8_t* d_mask, float* d_sum, float* d_sum2, int32_t* d_count,
+                                 float* d_avg, uint8_t* d_rgb, void* hip_stream);
+
+/* Adaptive sampling, one producer of masks: a stopping rule on the two moments, as a kernel so that every caller gets the same
+ * bits.  For every pixel with d_mask[p] != 0, with n = (float)d_count[p] and s_c, q_c the three channels of d_sum, d_sum2, every
+ * operation a single fp32 operation in this order:
+ *      lhs_c = n * q_c - s_c * s_c            rhs_c = s_c * s_c + eps * (n * n)
+ *      L = (lhs_0 + lhs_1) + lhs_2            R = (rhs_0 + rhs_1) + rhs_2
+ *      converged  iff  d_count[p] >= 2  and  L <= ((n - 1) * (tol * tol)) * R
+ * i.e. the squared standard error of the pixel's mean colour, summed over the channels, is at most tol^2 * (|mean|^2 + 3 * eps).
+ * A converged pixel gets d_mask[p] = 0; a NaN anywhere compares false, so such a pixel stays live; *d_live (one int32 on the
+ * device) receives the number of pixels still live.  d_sum, d_sum2 and d_count are only read; nothing of the scene is read (s names
+ * the device).
+ * THE RULE IS A HEURISTIC.  It sees only the samples taken so far: a pixel whose samples were all equal -- on a scene lit by a
+ * small emitter a sample is black or bright, so typically all black -- has L = 0 and counts as converged however many bright
+ * samples were still to come.  The length of the first range is the caller's guard against that.  The mechanism above is exact
+ * whatever mask it is given.
+ * Refused: a NULL argument, n_pixels < 0, tol or eps negative or NaN.  The call only enqueues work on hip_stream. */
+int sq_adaptive_update_device(sq_device_scene* s, int64_t n_pixels, const float* d_sum, const float* d_sum2,
+                              const int32_t* d_count, float tol, float eps,
+                              uint8_t* d_mask, int32_t* d_live, void* hip_stream);
+
 /* Many views of one scene in one call: a frame of n_views views is exactly n_views single-view frames.  View i is bit for bit what
  * sq_render_rows_device_range writes for cams[i] with the same other arguments (the seed of sample k of pixel (y, x) is
  * samples * (x + y * w) + k in every view, src/Lib.hs:85), in every kernel form, schedule and option.  All views share one primary

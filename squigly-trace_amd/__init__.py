@@ -5,7 +5,7 @@ Import with importlib (the directory name contains a hyphen):
 """
 from ._native import Camera, Shard, SquiglyError, lib, LIB_PATH, EXPORTED_SYMBOLS, debug_eval, build_id  # noqa: F401
 from .scene import BIH, Mesh, load_camera, camera_from_text, rot_matrix_rads       # noqa: F401
-from .render import Settings, render, render_rgb8, render_f32, render_progressive, render_views_rgb8   # noqa: F401
+from .render import Settings, render, render_rgb8, render_f32, render_progressive, render_adaptive, render_views_rgb8   # noqa: F401
 from .png import write_png                                                          # noqa: F401
 
 
@@ -20,7 +20,7 @@ def release_cached_memory() -> None:
 
 def __getattr__(name):
     # torch is only needed for the resident-scene path
-    if name in ("DeviceScene", "Progressive", "Hits"):
+    if name in ("DeviceScene", "Progressive", "Adaptive", "Hits", "rule_reference"):
         from . import device
         return getattr(device, name)
     if name in ("dist",):

@@ -87,6 +87,8 @@ def lib():
     L.sq_shard_global_row.restype = i32
     L.sq_render_rows_device.argtypes = [vp, C.POINTER(Camera), i32, i32, i32, i32, Shard, vp, vp, vp]
     L.sq_render_rows_device_range.argtypes = [vp, C.POINTER(Camera), i32, i32, i32, i32, Shard, i32, i32, vp, vp, vp, vp]
+    L.sq_render_rows_device_masked.argtypes = [vp, C.POINTER(Camera), i32, i32, i32, i32, Shard, i32, i32, vp, vp, vp, vp, vp, vp, vp]
+    L.sq_adaptive_update_device.argtypes = [vp, C.c_int64, vp, vp, vp, C.c_float, C.c_float, vp, vp, vp]
     L.sq_render_views_device.argtypes = [vp, C.POINTER(Camera), i32, i32, i32, i32, i32, Shard, i32, i32, vp, vp, vp, vp]
     L.sq_intersect_rays_device.argtypes = [vp, vp, vp, C.c_int64, vp, vp, vp, vp]
     L.sq_camera_rays_device.argtypes = [vp, C.POINTER(Camera), i32, i32, Shard, vp, vp, vp]
@@ -170,7 +172,7 @@ def check(rc):
 EXPORTED_SYMBOLS = [
     # include/squigly_hip.h
     "sq_render_rgb8", "sq_render_f32", "sq_scene_upload", "sq_scene_free", "sq_shard_rows",
-    "sq_shard_global_row", "sq_render_rows_device", "sq_render_rows_device_range", "sq_render_views_device", "sq_intersect_rays_device", "sq_camera_rays_device", "sq_kernel_timing", "sq_kernel_timing_reset",
+    "sq_shard_global_row", "sq_render_rows_device", "sq_render_rows_device_range", "sq_render_rows_device_masked", "sq_adaptive_update_device", "sq_render_views_device", "sq_intersect_rays_device", "sq_camera_rays_device", "sq_kernel_timing", "sq_kernel_timing_reset",
     "sq_set_option", "sq_get_stats", "sq_last_plan", "sq_debug_eval", "sq_device_count", "sq_abi_version", "sq_build_id", "sq_last_error",
     # include/squigly_host.h
     "sq_mesh_from_obj", "sq_mesh_from_text", "sq_mesh_from_arrays", "sq_mesh_num_tris",

@@ -10,7 +10,7 @@ import os
 import sys
 import time
 
-from . import BIH, Mesh, Settings, camera_from_text, lib, load_camera, render, render_progressive, render_views_rgb8, write_png
+from . import BIH, Mesh, Settings, camera_from_text, lib, load_camera, render, render_adaptive, render_progressive, render_views_rgb8, write_png
 from ._native import SquiglyError
 
 
@@ -29,6 +29,16 @@ def positive_int(text):
         raise argparse.ArgumentTypeError("expected a positive integer")
     if v < 1:
         raise argparse.ArgumentTypeError("expected a positive integer")
+    return v
+
+
+def nonneg_float(text):
+    try:
+        v = float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError("expected a number >= 0")
+    if not v >= 0:
+        raise argparse.ArgumentTypeError("expected a number >= 0")
     return v
 
 
@@ -92,6 +102,14 @@ def build_parser():
     p.add_argument("--views", type=views_file, default=None, metavar="FILE",
                    help="Render every camera of FILE (pairs of camera lines) in one call into <savepath stem>_<i:04d><ext>; "
                         "-c is not read")
+    # not flags of the reference either: adaptive sampling (pixels stop once the stopping rule calls them done)
+    p.add_argument("--adaptive", type=nonneg_float, default=None, metavar="TOL",
+                   help="Adaptive sampling: a pixel stops once the standard error of its mean colour is at most TOL times "
+                        "its colour (plus --adaptive-eps); a heuristic, --adaptive-first is its guard")
+    p.add_argument("--adaptive-first", type=positive_int, default=8, metavar="N", help="Samples every pixel gets before the rule is asked (default 8)")
+    p.add_argument("--adaptive-step", type=positive_int, default=8, metavar="N", help="Samples per later step (default 8)")
+    p.add_argument("--adaptive-eps", type=nonneg_float, default=1.0, metavar="E", help="Absolute floor of the rule, in squared radiance per channel (default 1.0)")
+    p.add_argument("--counts", default=None, metavar="FILE", help="With --adaptive: write the per-pixel sample counts to FILE (.npy, int32)")
     return p
 
 
@@ -100,6 +118,10 @@ def parse_args(argv=None):
     a = p.parse_args(argv)
     if a.views is not None and a.preview_every is not None:
         p.error("--views cannot be combined with --preview-every")
+    if a.adaptive is not None and (a.views is not None or a.preview_every is not None):
+        p.error("--adaptive cannot be combined with --views or --preview-every")
+    if a.counts is not None and a.adaptive is None:
+        p.error("--counts needs --adaptive")
     return a
 
 
@@ -139,6 +161,15 @@ def main(argv=None):
         for path, img in zip(view_paths(settings.savePath, len(imgs)), imgs):
             write_png(path, img)
         print(f"Wrote {len(imgs)} views to {view_paths(settings.savePath, 1)[0]} ...")
+    elif a.adaptive is not None:
+        import numpy as np
+        for done, live, spent, img, counts in render_adaptive(bih, cam, settings.samples, settings.dimensions, a.adaptive, eps=a.adaptive_eps,
+                                                              first=a.adaptive_first, step=a.adaptive_step, cast=settings.cast):
+            print(f"Adaptive {done}/{settings.samples} live {live} spent {spent}")
+        write_png(settings.savePath, img)
+        if a.counts is not None:
+            with open(a.counts, "wb") as f:                     # the name as given (np.save would append .npy to a path)
+                np.save(f, counts.astype(np.int32))
     elif a.preview_every is None:
         render(bih, cam, settings)
     else:

@@ -107,6 +107,10 @@ struct Frame {
     // (pos, rot).  A single-view frame has n_views = 1 and reads cam_pos / cam_rot.
     int32_t n_views, view_pixels;
     const float* cams;
+    // masked calls (sq_render_rows_device_masked, the kernels' AD instantiations; read by no other instantiation): `mask` = the
+    // caller's per-pixel mask (nullptr = every pixel), `sum2` = its fold of r * r, laid out and carried like `sum` (nullptr = none),
+    // `count` = its per-pixel sample counts (nullptr = none).  pixel_live() says which pixels such a call renders.
+    const uint8_t* mask; float* sum2; int32_t* count;
 };
 constexpr int kCamWords = 12;     // a view's entry in the camera table: pos[3], rot[9]
 struct ViewCam { f3 pos; float rot[9]; };
@@ -182,12 +186,40 @@ __device__ __forceinline__ f3 fold_start(const Frame& F, long long pix) {
 __device__ __forceinline__ void store_miss_sum(const Frame& F, long long pix) {
     if (F.sum) { float* p = F.sum + pix * 3; p[0] = 0.0f; p[1] = 0.0f; p[2] = 0.0f; }
 }
+// Masked calls.  Is the pixel live, i.e. does this call render it?  Its mask byte is set, and its fold stays a prefix: a pixel that an
+// earlier range left out (its count is not k_begin) does not resume with a gap.  Everything else in a masked call follows from
+// this one answer: a dead pixel gets no ray, no slot and no store.
+__device__ __forceinline__ bool pixel_live(const Frame& F, long long pix) {
+    if (F.mask && F.mask[pix] == 0) return false;
+    return F.k_begin == 0 || !F.count || F.count[pix] == F.k_begin;
+}
+// Where the fold of r * r starts (F.sum2 given): like fold_start.
+__device__ __forceinline__ f3 fold_start2(const Frame& F, long long pix) {
+    if (F.k_begin == 0) return sq::mk(0, 0, 0);
+    const float* p = F.sum2 + pix * 3;
+    return sq::mk(p[0], p[1], p[2]);
+}
+// A live pixel's sample count after the call.
+__device__ __forceinline__ void store_count(const Frame& F, long long pix) {
+    if (F.count) F.count[pix] = F.k_end;
+}
+// A live pixel whose primary ray misses: +0 in both folds, the count, and black -- a masked call clears no buffer up front (its
+// dead pixels keep what they hold), so the primary kernels write the black of their own misses.
+__device__ __forceinline__ void store_live_miss(const Frame& F, long long pix) {
+    store_miss_sum(F, pix);
+    if (F.sum2) { float* p = F.sum2 + pix * 3; p[0] = 0.0f; p[1] = 0.0f; p[2] = 0.0f; }
+    store_count(F, pix);
+    if (F.out_avg) { float* p = F.out_avg + pix * 3; p[0] = 0.0f; p[1] = 0.0f; p[2] = 0.0f; }
+    if (F.out_rgb) { uint8_t* p = F.out_rgb + pix * 3; p[0] = 0; p[1] = 0; p[2] = 0; }
+}
 
 // ----------------------------------------------------------------------------------------------
 // Variant 1: one lane per pixel, everything in one kernel (cross-check variant; also raycast mode)
 // ----------------------------------------------------------------------------------------------
 // MV: a multi-view frame (pixels are enumerated linearly, so the lanes of a wave may belong to two views: per-lane camera reads)
-template <typename StackT, bool MV>
+// AD: a masked call (single-view): dead pixels leave before the first ray -- nothing wave-wide follows, every lane walks alone --
+// and live ones also fold r * r and store their count.
+template <typename StackT, bool MV, bool AD = false>
 __global__ void __launch_bounds__(kBlock) sq_render_pixels(const SceneView S, const Frame F) {
     extern __shared__ float4 lds_raw[];
     SQ_LDS StackT* stk = to_lds<StackT>(lds_raw) + threadIdx.x;
@@ -199,6 +231,7 @@ __global__ void __launch_bounds__(kBlock) sq_render_pixels(const SceneView S, co
         o0 = c.pos; d0 = primary_dir(c.rot, F.w, F.h, y, x);
     } else {
         if (pix >= (long long)F.local_rows * F.h) return;
+        if constexpr (AD) { if (!pixel_live(F, pix)) return; }
         pixel_coords(F, pix, y, x);
         o0 = sq::mk(F.cam_pos[0], F.cam_pos[1], F.cam_pos[2]);
         d0 = primary_dir(F.cam_rot, F.w, F.h, y, x);
@@ -206,9 +239,11 @@ __global__ void __launch_bounds__(kBlock) sq_render_pixels(const SceneView S, co
     const GlobalNodes N{ S.branches, S.cull_child, S.cull_child != nullptr };
     const int n = F.samples;
     f3 sum = sq::mk(0, 0, 0);                                           // sum = foldl (+) 0
+    f3 sum2 = sq::mk(0, 0, 0);                                          // AD with F.sum2: the same fold of r * r
     const Hit h0 = trace_one(S, N, o0, d0, stk, kBlock);
     if (h0.tri >= 0) {
         sum = fold_start(F, pix);
+        if constexpr (AD) { if (F.sum2) sum2 = fold_start2(F, pix); }
         const Surface s0 = surface_of(S, h0.tri);
         const f3 p0 = o0 + sq::scale(h0.t, d0);
         if (F.cast) {                                                   // raycast, src/Lib.hs:141-151
@@ -218,6 +253,7 @@ __global__ void __launch_bounds__(kBlock) sq_render_pixels(const SceneView S, co
             f3 c = sq::mk(0, 0, 0);
             if (!(sh.tri >= 0 && !(hit_dist(p0, light - p0, sh.t) > dl))) c = sq::scale(2 / dl, s0.surf);
             for (int k = F.k_begin; k < F.k_end; ++k) sum = sum + c;
+            if constexpr (AD) { if (F.sum2) for (int k = F.k_begin; k < F.k_end; ++k) sum2 = sum2 + c * c; }
         } else {
             const long long rix = (long long)n * ((long long)x + (long long)y * (long long)F.w);   // src/Lib.hs:85
 #pragma unroll 1
@@ -236,9 +272,15 @@ __global__ void __launch_bounds__(kBlock) sq_render_pixels(const SceneView S, co
                     if (h2.tri >= 0) { const Surface s2 = surface_of(S, h2.tri); L2 = s2.surf * sq::mk(0, 0, 0) + s2.emit; }
                     L1 = s1.surf * L2 + s1.emit;
                 }
-                sum = sum + (s0.surf * L1 + s0.emit);
+                const f3 r = s0.surf * L1 + s0.emit;
+                sum = sum + r;
+                if constexpr (AD) sum2 = sum2 + r * r;
             }
         }
+    }
+    if constexpr (AD) {
+        if (F.sum2) { float* o = F.sum2 + pix * 3; o[0] = sum2.x; o[1] = sum2.y; o[2] = sum2.z; }
+        store_count(F, pix);
     }
     if (F.sum) { float* o = F.sum + pix * 3; o[0] = sum.x; o[1] = sum.y; o[2] = sum.z; }
     const f3 avg = sq::scale(1 / (float)F.k_end, sum);                  // src/Lib.hs:88
@@ -276,6 +318,7 @@ struct Work {                 // device workspace of one frame (HBM)
     int32_t* head[2];         // dequeue cursors of the persistent trace kernel, one per bounce level
     unsigned long long* stats;  // cumulative trace-kernel statistics (TraceArgs::stats)
     int64_t  slot_capacity;
+    float*   px_sum2;         // masked calls that carry second moments: running ordered sum of r * r per active pixel, 3 floats (else nullptr)
 };
 // Slot states.  kRay1 / kRay2: the slot holds a bounce ray of depth 1 / 2 for the trace launch of that level;
 // kMirror: the sample mirrors at depth 0 and shares the pixel's mirror ray (traced once per pixel); kDone: its radiance is in `rad`.
@@ -305,8 +348,27 @@ __device__ __forceinline__ int wave_append(int32_t* counter, bool want) {
     return want ? base + __popcll(m & ((1ull << lane) - 1ull)) : -1;
 }
 
+// A pixel joins the active list: its primary hit and where its fold starts.  AD: a masked call's live pixel, also its count and,
+// when the call carries second moments, where that fold starts.
+template <bool AD>
+__device__ __forceinline__ void store_active(const Frame& F, const Work& W, int a, long long pix, float t, int tri) {
+    W.px_pixel[a] = (int32_t)pix; W.px_t0[a] = t; W.px_tri0[a] = tri;
+    const f3 s0 = fold_start(F, pix);
+    W.px_sum[3 * a] = s0.x; W.px_sum[3 * a + 1] = s0.y; W.px_sum[3 * a + 2] = s0.z;
+    if constexpr (AD) {
+        if (F.sum2) { const f3 q0 = fold_start2(F, pix); W.px_sum2[3 * a] = q0.x; W.px_sum2[3 * a + 1] = q0.y; W.px_sum2[3 * a + 2] = q0.z; }
+        store_count(F, pix);
+    }
+}
+// ... or does not: its primary ray misses.
+template <bool AD>
+__device__ __forceinline__ void store_miss(const Frame& F, long long pix) {
+    if constexpr (AD) store_live_miss(F, pix); else store_miss_sum(F, pix);
+}
+
 // Primary rays: trace once per pixel, compact the pixels that hit.
-template <typename StackT, bool MV>
+// AD (here and in the other primary passes): a masked call; a dead pixel's lane is treated like the padding of an edge tile.
+template <typename StackT, bool MV, bool AD = false>
 __global__ void __launch_bounds__(kBlock) sq_primary(const SceneView S, const Frame F, const Work W) {
     extern __shared__ float4 lds_raw[];
     SQ_LDS StackT* stk = to_lds<StackT>(lds_raw) + threadIdx.x;
@@ -315,7 +377,8 @@ __global__ void __launch_bounds__(kBlock) sq_primary(const SceneView S, const Fr
     long long pix;
     if constexpr (MV) pix = q < primary_padded(F) * F.n_views ? primary_tile_views(F, q, view) : -1;
     else pix = q < primary_padded(F) ? primary_tile(F, q) : -1;
-    const bool in = pix >= 0;
+    bool in = pix >= 0;
+    if constexpr (AD) in = in && pixel_live(F, pix);
     Hit h0; h0.tri = -1; h0.t = 0;
     if (in) {
         int y, x;
@@ -330,11 +393,8 @@ __global__ void __launch_bounds__(kBlock) sq_primary(const SceneView S, const Fr
         }
     }
     const int a = wave_append(W.n_active, in && h0.tri >= 0);
-    if (a >= 0) {
-        W.px_pixel[a] = (int32_t)pix; W.px_t0[a] = h0.t; W.px_tri0[a] = h0.tri;
-        const f3 s0 = fold_start(F, pix);
-        W.px_sum[3 * a] = s0.x; W.px_sum[3 * a + 1] = s0.y; W.px_sum[3 * a + 2] = s0.z;
-    } else if (in) store_miss_sum(F, pix);
+    if (a >= 0) store_active<AD>(F, W, a, pix, h0.t, h0.tri);
+    else if (in) store_miss<AD>(F, pix);
 }
 
 struct Pixel0 { f3 p0, d0; Surface s0; int y, x; };
@@ -435,11 +495,13 @@ __global__ void __launch_bounds__(kBlock) sq_mirror1_store(const Work W, long lo
 // k_count = 1, then the hits are compacted into the active-pixel list exactly as sq_primary does.  The one-ray-per-lane walk of
 // sq_primary(_resident) lasts as long as its most expensive wave (64 neighbouring pixels on dense geometry: 0.5 ms on the headline
 // scene however small the shard); the pooled leaf phase walks such a wave faster.  W.n_active[48] is the launch's queue length.
-template <bool MV>
+// AD: a dead pixel's slot is flagged kDone, so it is not in the launch's queue and sq_primary_store skips it.
+template <bool MV, bool AD = false>
 __global__ void __launch_bounds__(kBlock) sq_primary_gen(const Frame F, const Work W, long long total) {
     if (blockIdx.x == 0 && threadIdx.x == 0) W.n_active[48] = (int32_t)total;
     for (long long pix = (long long)blockIdx.x * kBlock + threadIdx.x; pix < total; pix += (long long)gridDim.x * kBlock) {
         int y, x;
+        if constexpr (AD) { if (!pixel_live(F, pix)) { W.state[pix] = kDone; continue; } }
         if constexpr (MV) {
             const ViewCam c = view_cam<false>(F, view_coords(F, (int)pix, y, x));
             const f3 d = primary_dir(c.rot, F.w, F.h, y, x);
@@ -455,17 +517,16 @@ __global__ void __launch_bounds__(kBlock) sq_primary_gen(const Frame F, const Wo
         }
     }
 }
+template <bool AD = false>
 __global__ void __launch_bounds__(kBlock) sq_primary_store(const Frame F, const Work W, long long total) {
     for (long long base = (long long)blockIdx.x * kBlock; base < total; base += (long long)gridDim.x * kBlock) {   // whole waves stay together (ballot)
         const long long pix = base + threadIdx.x;
-        const bool in = pix < total;
+        bool in = pix < total;
+        if constexpr (AD) in = in && W.state[pix] == kRay1;              // what sq_primary_gen<AD> decided (the trace kernel leaves the state byte alone)
         const int2 hit = in ? slot_hit(W.org[pix]) : make_int2(0, -1);
         const int a = wave_append(W.n_active, in && hit.y >= 0);
-        if (a >= 0) {
-            W.px_pixel[a] = (int32_t)pix; W.px_t0[a] = __int_as_float(hit.x); W.px_tri0[a] = hit.y;
-            const f3 s0 = fold_start(F, pix);
-            W.px_sum[3 * a] = s0.x; W.px_sum[3 * a + 1] = s0.y; W.px_sum[3 * a + 2] = s0.z;
-        } else if (in) store_miss_sum(F, pix);
+        if (a >= 0) store_active<AD>(F, W, a, pix, __int_as_float(hit.x), hit.y);
+        else if (in) store_miss<AD>(F, pix);
     }
 }
 
@@ -638,11 +699,15 @@ __device__ __forceinline__ f3 shade2_radiance(const SceneView& S, const Work& W,
 // sum outcomes, in sample order (src/Lib.hs:88); on the call's last batch: the fold to F.sum (range calls), avg over the k_end
 // samples folded so far, tonemap, store.
 // GROUPED: see the comment in the loop; two kernels because the grouped loop's registers cost the plain one a third of its waves.
-template <bool GROUPED>
+// MOM2: the call carries second moments (F.sum2, W.px_sum2): every radiance r also adds r * r, each product rounded before its add,
+// to a second fold.  A template parameter, so that every other frame runs the instruction stream it ran without it.
+template <bool GROUPED, bool MOM2 = false>
 __global__ void __launch_bounds__(kBlock) sq_accumulate(const SceneView S, const Frame F, const Work W, int k_count, int last) {
     const int A = *W.n_active;
     for (int a = blockIdx.x * kBlock + threadIdx.x; a < A; a += gridDim.x * kBlock) {
         f3 sum = sq::mk(W.px_sum[3 * a], W.px_sum[3 * a + 1], W.px_sum[3 * a + 2]);
+        f3 sum2 = sq::mk(0, 0, 0);
+        if constexpr (MOM2) sum2 = sq::mk(W.px_sum2[3 * a], W.px_sum2[3 * a + 1], W.px_sum2[3 * a + 2]);
         const Surface s0 = surface_of(S, W.px_tri0[a]);
         // The sum is the reference's left fold over the samples (src/Lib.hs:88): one dependent add per sample.  With fewer active
         // pixels than threads (one rank's share of a frame at 8 ranks) a thread is a chain of `samples` memory round trips and the
@@ -667,6 +732,7 @@ __global__ void __launch_bounds__(kBlock) sq_accumulate(const SceneView S, const
                     const long long sid = (long long)(k0 + j) * A + a;
                     const f3 rad = (st[j] == kRay2) ? shade2_radiance(S, W, sid, s0) : sq::mk(rx[j], ry[j], rz[j]);
                     sum = sum + rad;
+                    if constexpr (MOM2) sum2 = sum2 + rad * rad;
                 }
             }
         } else {
@@ -677,7 +743,12 @@ __global__ void __launch_bounds__(kBlock) sq_accumulate(const SceneView S, const
                 if (k + 1 < k_count) st = W.state[sid + A];
                 const f3 rad = (cur == kRay2) ? shade2_radiance(S, W, sid, s0) : sq::mk(W.rad[3 * sid], W.rad[3 * sid + 1], W.rad[3 * sid + 2]);
                 sum = sum + rad;
+                if constexpr (MOM2) sum2 = sum2 + rad * rad;
             }
+        }
+        if constexpr (MOM2) {
+            if (!last) { W.px_sum2[3 * a] = sum2.x; W.px_sum2[3 * a + 1] = sum2.y; W.px_sum2[3 * a + 2] = sum2.z; }
+            else { float* o = F.sum2 + (long long)W.px_pixel[a] * 3; o[0] = sum2.x; o[1] = sum2.y; o[2] = sum2.z; }
         }
         if (!last) { W.px_sum[3 * a] = sum.x; W.px_sum[3 * a + 1] = sum.y; W.px_sum[3 * a + 2] = sum.z; continue; }
         const long long pix = W.px_pixel[a];
@@ -800,7 +871,7 @@ __device__ __forceinline__ void stage_resident_scene(const SceneView& S, int n_b
 // Primary rays with the scene in LDS (the resident form): same per-ray code as sq_primary, but a branch or triangle costs an
 // LDS read instead of an L2 round trip.  A primary ray is a chain of ~200 dependent reads, so on small frames -- one rank's
 // share of a frame at 8 ranks -- the launch is as long as that chain: 0.58 ms from L2, 0.1-0.2 ms from LDS.
-template <typename StackT, bool MV>
+template <typename StackT, bool MV, bool AD = false>
 __global__ void __launch_bounds__(kResidentBlock) sq_primary_resident(const SceneView S, const Frame F, const Work W, int stack_cap) {
     extern __shared__ float4 lds_raw[];
     char* lds = reinterpret_cast<char*>(lds_raw);
@@ -815,7 +886,8 @@ __global__ void __launch_bounds__(kResidentBlock) sq_primary_resident(const Scen
         long long pix;                                                      // (total is a multiple of 64: whole waves)
         if constexpr (MV) pix = primary_tile_views(F, base + threadIdx.x, view);
         else pix = primary_tile(F, base + threadIdx.x);
-        const bool in = pix >= 0;
+        bool in = pix >= 0;
+        if constexpr (AD) in = in && pixel_live(F, pix);
         Hit h0; h0.tri = -1; h0.t = 0;
         if (in) {
             int y, x;
@@ -829,11 +901,8 @@ __global__ void __launch_bounds__(kResidentBlock) sq_primary_resident(const Scen
             }
         }
         const int a = wave_append(W.n_active, in && h0.tri >= 0);
-        if (a >= 0) {
-            W.px_pixel[a] = (int32_t)pix; W.px_t0[a] = h0.t; W.px_tri0[a] = h0.tri;
-            const f3 s0 = fold_start(F, pix);
-            W.px_sum[3 * a] = s0.x; W.px_sum[3 * a + 1] = s0.y; W.px_sum[3 * a + 2] = s0.z;
-        } else if (in) store_miss_sum(F, pix);
+        if (a >= 0) store_active<AD>(F, W, a, pix, h0.t, h0.tri);
+        else if (in) store_miss<AD>(F, pix);
     }
 }
 
@@ -1309,6 +1378,8 @@ struct sq_device_scene {
     hipStream_t aux = nullptr; std::vector<hipEvent_t> events;
     // multi-view frames: the camera table (kCamWords floats per view, grow-only), filled on the call's stream
     float* d_cams = nullptr; int64_t cams_cap = 0;
+    // masked calls with second moments: Work::px_sum2, 3 floats per pixel (grow-only; no other call allocates or reads it)
+    float* d_px_sum2 = nullptr; int64_t px_sum2_cap = 0;
     int64_t opt_overlap = 0, opt_aux_blocks_per_cu = 0;
     int64_t opt_pool = 1, opt_refill_min = 12, opt_flush_min = 40, opt_guided = 1, opt_primary_resident = 1, opt_pixel_major = -1, opt_cull = 1, opt_descend_extra = 2, opt_descend_lanes = 16, opt_primary_pooled = 0, opt_coresidency = 0, opt_trace_prio = 0, opt_aux_low_priority = 1, opt_aux_polite = 0, opt_incremental = 1, opt_primary_tiles = 1;
 };
@@ -1675,6 +1746,7 @@ extern "C" void sq_scene_free(sq_device_scene* s) {
     for (hipEvent_t e : s->events) (void)hipEventDestroy(e);
     if (s->aux) (void)hipStreamDestroy(s->aux);
     (void)hipFree(s->d_cams);
+    (void)hipFree(s->d_px_sum2);
     delete s;
 }
 
@@ -1747,6 +1819,14 @@ int ensure_cam_table(sq_device_scene* s, int64_t n) {
     if (s->d_cams) { SQ_HIP(hipFree(s->d_cams)); s->d_cams = nullptr; s->cams_cap = 0; }
     SQ_HIP(hipMalloc(&s->d_cams, (size_t)cap * kCamWords * sizeof(float)));
     s->cams_cap = cap;
+    return 0;
+}
+// Work::px_sum2 of a masked call that carries second moments: room for `pixels` pixels (grow-only, freed as the camera table is).
+int ensure_px_sum2(sq_device_scene* s, int64_t pixels) {
+    if (pixels <= s->px_sum2_cap) return 0;
+    if (s->d_px_sum2) { SQ_HIP(hipFree(s->d_px_sum2)); s->d_px_sum2 = nullptr; s->px_sum2_cap = 0; }
+    SQ_HIP(hipMalloc(&s->d_px_sum2, (size_t)pixels * 3 * sizeof(float)));
+    s->px_sum2_cap = pixels;
     return 0;
 }
 // Enqueues the copy of a multi-view frame's cameras into its table F.cams (nothing for a single-view frame: cams = nullptr).
@@ -1904,12 +1984,18 @@ int launch_frame(sq_device_scene* s, const Frame& F, hipStream_t stream, const s
     P.pixel_lds_bytes = (int32_t)px_lds; P.packed_leaves = S.packed_leaves; P.n_emitters = S.n_emitters;
     P.trace_form = SQ_FORM_PER_PIXEL; P.primary_form = SQ_PRIMARY_NONE;
     s->has_plan = true;
+    // a masked call (sq_render_rows_device_masked with a mask, second moments or counts) takes the AD instantiations of the kernels that
+    // decide who is active, and clears no buffer; every other call takes the instantiations, and the memsets, it always took
+    constexpr bool kAD = !MV;                                          // multi-view frames have no masked form
+    const bool ad = kAD && (F.mask || F.sum2 || F.count);
+    const bool mom2 = ad && F.sum2;
     if (px_blocks > 0x7fffffffLL) return sq_set_error("image too large for one launch");
     if (px_lds > 160 * 1024) return sq_set_error("BIH height %d needs %zu B of LDS stack per workgroup (max 163840)", S.height, px_lds);
     if (s->opt_variant == 1 || F.cast) {
-        if (px_lds > 64 * 1024) SQ_HIP(hipFuncSetAttribute((const void*)sq_render_pixels<StackT, MV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)px_lds));
+        if (px_lds > 64 * 1024) SQ_HIP(hipFuncSetAttribute(ad ? (const void*)sq_render_pixels<StackT, MV, kAD> : (const void*)sq_render_pixels<StackT, MV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)px_lds));
         P.launched = 1;
         if (stage_cams(s, F, cams, stream)) return 1;
+        if (ad) return timed_launch(s, [&] { hipLaunchKernelGGL((sq_render_pixels<StackT, MV, kAD>), dim3((unsigned)px_blocks), dim3(kBlock), px_lds, stream, S, F); }, "sq_render_pixels", stream);
         return timed_launch(s, [&] { hipLaunchKernelGGL((sq_render_pixels<StackT, MV>), dim3((unsigned)px_blocks), dim3(kBlock), px_lds, stream, S, F); }, "sq_render_pixels", stream);
     }
     // ---- wavefront pipeline ----
@@ -1917,6 +2003,8 @@ int launch_frame(sq_device_scene* s, const Frame& F, hipStream_t stream, const s
     // at least one sample of every pixel per batch, never more slots than the call has samples
     const int64_t slots = std::max<int64_t>(pixels, std::min<int64_t>(s->opt_slots, (int64_t)pixels * n_call));
     if (ensure_workspace(s, pixels, slots)) return 1;
+    if (mom2 && ensure_px_sum2(s, pixels)) return 1;
+    s->work.px_sum2 = mom2 ? s->d_px_sum2 : nullptr;
     const Work& W = s->work;
     const int64_t have_slots = W.slot_capacity;
     // Overlapped schedule: the sample batches alternate between two halves of the workspace ("tracks"); every
@@ -1946,26 +2034,31 @@ int launch_frame(sq_device_scene* s, const Frame& F, hipStream_t stream, const s
     P.launched = 1;                                                    // planned; what follows fails only on HIP errors
     // nothing is enqueued before this point, so a refusal above leaves every buffer as it was
     if (stage_cams(s, F, cams, stream)) return 1;                       // multi-view: before every kernel that reads the table (e_setup below)
-    if (F.out_avg) SQ_HIP(hipMemsetAsync(F.out_avg, 0, (size_t)pixels * 3 * sizeof(float), stream));   // pixels whose primary ray misses: black
-    if (F.out_rgb) SQ_HIP(hipMemsetAsync(F.out_rgb, 0, (size_t)pixels * 3, stream));
+    // (a masked call's dead pixels keep what they hold: its primary kernels write the black of the live misses, store_live_miss)
+    if (F.out_avg && !ad) SQ_HIP(hipMemsetAsync(F.out_avg, 0, (size_t)pixels * 3 * sizeof(float), stream));   // pixels whose primary ray misses: black
+    if (F.out_rgb && !ad) SQ_HIP(hipMemsetAsync(F.out_rgb, 0, (size_t)pixels * 3, stream));
     SQ_HIP(hipMemsetAsync(W.n_active, 0, 128 * sizeof(int32_t), stream));
     // primary rays: once per pixel.  With a resident scene they are traced out of LDS as well.
     const bool primary_pooled = s->opt_primary_pooled && pool;          // ... or through the pooled trace kernel, below
     if (primary_pooled) {
     } else if (resident && s->opt_primary_resident) {
         const TraceLds Lp = trace_lds_layout(S.n_branches, true, S.n_verts, S.n_tris, kResidentBlock, stack_cap, (int)sizeof(StackT), false);
-        SQ_HIP(hipFuncSetAttribute((const void*)sq_primary_resident<StackT, MV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)Lp.total));
+        SQ_HIP(hipFuncSetAttribute(ad ? (const void*)sq_primary_resident<StackT, MV, kAD> : (const void*)sq_primary_resident<StackT, MV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)Lp.total));
         const long long need = (primary_padded(F) * F.n_views + kResidentBlock - 1) / kResidentBlock;
-        hipLaunchKernelGGL((sq_primary_resident<StackT, MV>), dim3((unsigned)std::min<long long>(s->n_cu, need)), dim3(kResidentBlock), Lp.total, stream, S, F, W, stack_cap);
+        if (ad) hipLaunchKernelGGL((sq_primary_resident<StackT, MV, kAD>), dim3((unsigned)std::min<long long>(s->n_cu, need)), dim3(kResidentBlock), Lp.total, stream, S, F, W, stack_cap);
+        else hipLaunchKernelGGL((sq_primary_resident<StackT, MV>), dim3((unsigned)std::min<long long>(s->n_cu, need)), dim3(kResidentBlock), Lp.total, stream, S, F, W, stack_cap);
     } else {
-        if (px_lds > 64 * 1024) SQ_HIP(hipFuncSetAttribute((const void*)sq_primary<StackT, MV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)px_lds));
-        hipLaunchKernelGGL((sq_primary<StackT, MV>), dim3((unsigned)((primary_padded(F) * F.n_views + kBlock - 1) / kBlock)), dim3(kBlock), px_lds, stream, S, F, W);
+        if (px_lds > 64 * 1024) SQ_HIP(hipFuncSetAttribute(ad ? (const void*)sq_primary<StackT, MV, kAD> : (const void*)sq_primary<StackT, MV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)px_lds));
+        if (ad) hipLaunchKernelGGL((sq_primary<StackT, MV, kAD>), dim3((unsigned)((primary_padded(F) * F.n_views + kBlock - 1) / kBlock)), dim3(kBlock), px_lds, stream, S, F, W);
+        else hipLaunchKernelGGL((sq_primary<StackT, MV>), dim3((unsigned)((primary_padded(F) * F.n_views + kBlock - 1) / kBlock)), dim3(kBlock), px_lds, stream, S, F, W);
     }
     SQ_HIP(hipGetLastError());
     const int aux_blocks = s->n_cu * (int)(s->opt_aux_blocks_per_cu ? s->opt_aux_blocks_per_cu : 8);
     // sq_accumulate: the grouped loop when the shard has no more pixels than the launch has threads (every thread at most one pixel)
     const bool acc_grouped = pixels <= (long long)aux_blocks * kBlock;
-#define SQ_LAUNCH_ACCUMULATE(...) do { if (acc_grouped) hipLaunchKernelGGL(sq_accumulate<true>, __VA_ARGS__); else hipLaunchKernelGGL(sq_accumulate<false>, __VA_ARGS__); } while (0)
+#define SQ_LAUNCH_ACCUMULATE(...) do { \
+        if (mom2) { if (acc_grouped) hipLaunchKernelGGL((sq_accumulate<true, true>), __VA_ARGS__); else hipLaunchKernelGGL((sq_accumulate<false, true>), __VA_ARGS__); } \
+        else if (acc_grouped) hipLaunchKernelGGL(sq_accumulate<true>, __VA_ARGS__); else hipLaunchKernelGGL(sq_accumulate<false>, __VA_ARGS__); } while (0)
     // per-sample kernels that run one thread per active pixel: x covers the pixels, y splits a pixel's samples when the
     // frame has too few pixels to fill the chip (one rank's share of a frame, small frames)
     auto pp_grid = [&](int kc) {
@@ -1984,10 +2077,12 @@ int launch_frame(sq_device_scene* s, const Frame& F, hipStream_t stream, const s
     if (primary_pooled) {
         Work Wp = W; Wp.n_active = W.n_active + 48;                     // the launch's queue is the shard's pixels, not the active ones
         SQ_HIP(hipMemsetAsync(W.head[0], 0, 32 * sizeof(int32_t), stream));
-        hipLaunchKernelGGL(sq_primary_gen<MV>, dim3(aux_blocks), dim3(kBlock), 0, stream, F, W, pixels);
+        if (ad) hipLaunchKernelGGL((sq_primary_gen<MV, kAD>), dim3(aux_blocks), dim3(kBlock), 0, stream, F, W, pixels);
+        else hipLaunchKernelGGL(sq_primary_gen<MV>, dim3(aux_blocks), dim3(kBlock), 0, stream, F, W, pixels);
         SQ_HIP(hipGetLastError());
         if (launch_trace(Wp, 1, 0, stream)) return 1;
-        hipLaunchKernelGGL(sq_primary_store, dim3(aux_blocks), dim3(kBlock), 0, stream, F, W, pixels);
+        if (ad) hipLaunchKernelGGL(sq_primary_store<kAD>, dim3(aux_blocks), dim3(kBlock), 0, stream, F, W, pixels);
+        else hipLaunchKernelGGL(sq_primary_store<false>, dim3(aux_blocks), dim3(kBlock), 0, stream, F, W, pixels);
         SQ_HIP(hipGetLastError());
     }
     // once per frame: the depth-0 mirror ray of every active pixel (reused by every sample that mirrors).  In the plain
@@ -2135,13 +2230,25 @@ namespace {
 // nullptr (sq_render_rows_device) keeps the fold in the workspace; the caller has checked everything that is specific to its own entry
 // point.  One camera takes the single-view kernels; more take their multi-view instantiations and the scene's camera table.
 int render_rows(sq_device_scene* s, const sq_camera* cam, int32_t n_views, int32_t samples, int32_t w, int32_t h, int32_t cast, sq_shard sh,
-                int32_t k_begin, int32_t k_end, float* d_sum, float* d_avg, uint8_t* d_rgb, void* hip_stream) {
+                int32_t k_begin, int32_t k_end, float* d_sum, float* d_avg, uint8_t* d_rgb, void* hip_stream,
+                const uint8_t* d_mask = nullptr, float* d_sum2 = nullptr, int32_t* d_count = nullptr) {
     if (!s || !cam) return sq_set_error("null argument");
     if (samples < 1 || w < 1 || h < 1) return sq_set_error("samples, width and height must be positive (got %d, %d, %d)", samples, w, h);
     const int32_t rows = sq_shard_rows(w, sh);
     if (rows < 0) return sq_set_error("bad shard {row_block=%d, shard=%d, n_shards=%d}", sh.row_block, sh.shard, sh.n_shards);
     if (rows == 0) return 0;                    // an empty shard (more shards than row blocks) has nothing to render
     if (!d_avg && !d_rgb && !d_sum) return sq_set_error("no output buffer");
+    if (d_mask || d_sum2 || d_count) {   // a masked call: no two of its buffers may overlap (a live pixel's stores would be another pixel's mask, count or fold)
+        const size_t px = (size_t)rows * (size_t)h;
+        const struct { const char* name; const void* p; size_t bytes; } b[6] = {
+            { "d_mask", d_mask, px }, { "d_sum", d_sum, px * 12 }, { "d_sum2", d_sum2, px * 12 }, { "d_count", d_count, px * 4 },
+            { "d_avg", d_avg, px * 12 }, { "d_rgb", d_rgb, px * 3 } };
+        for (int i = 0; i < 6; ++i) for (int j = i + 1; j < 6; ++j) {
+            if (!b[i].p || !b[j].p) continue;
+            const uintptr_t a0 = (uintptr_t)b[i].p, a1 = a0 + b[i].bytes, c0 = (uintptr_t)b[j].p, c1 = c0 + b[j].bytes;
+            if (a0 < c1 && c0 < a1) return sq_set_error("%s and %s overlap", b[i].name, b[j].name);
+        }
+    }
     SQ_HIP(hipSetDevice(s->device));
     Frame F{};
     std::memcpy(F.cam_pos, cam->pos, sizeof F.cam_pos);
@@ -2159,6 +2266,7 @@ int render_rows(sq_device_scene* s, const sq_camera* cam, int32_t n_views, int32
     F.k_begin = k_begin; F.k_end = k_end; F.sum = d_sum;
     F.diag = s->opt_coresidency ? std::max(1, s->n_cu - 8) : 0;   // "beside" = while all but a handful of the CUs hold a live trace workgroup
     F.n_views = n_views; F.view_pixels = rows * h; F.cams = nullptr;
+    F.mask = d_mask; F.sum2 = d_sum2; F.count = d_count;
     hipStream_t stream = (hipStream_t)hip_stream;
     if (n_views == 1) return s->small_index ? launch_frame<uint16_t, false>(s, F, stream, nullptr) : launch_frame<uint32_t, false>(s, F, stream, nullptr);
     if (ensure_cam_table(s, n_views)) return 1;
@@ -2175,11 +2283,62 @@ extern "C" int sq_render_rows_device(sq_device_scene* s, const sq_camera* cam, i
 extern "C" int sq_render_rows_device_range(sq_device_scene* s, const sq_camera* cam, int32_t samples, int32_t w, int32_t h,
                                            int32_t cast, sq_shard sh, int32_t k_begin, int32_t k_end,
                                            float* d_sum, float* d_avg, uint8_t* d_rgb, void* hip_stream) {
+    return sq_render_rows_device_masked(s, cam, samples, w, h, cast, sh, k_begin, k_end, nullptr, d_sum, nullptr, nullptr, d_avg, d_rgb, hip_stream);
+}
+
+// The range call is this call without a mask, second moments and counts.
+extern "C" int sq_render_rows_device_masked(sq_device_scene* s, const sq_camera* cam, int32_t samples, int32_t w, int32_t h,
+                                            int32_t cast, sq_shard sh, int32_t k_begin, int32_t k_end,
+                                            const uint8_t* d_mask, float* d_sum, float* d_sum2, int32_t* d_count,
+                                            float* d_avg, uint8_t* d_rgb, void* hip_stream) {
     if (k_begin < 0 || k_end <= k_begin || k_end > samples)
         return sq_set_error("bad sample range [%d, %d) of a %d-sample frame (need 0 <= k_begin < k_end <= samples)", k_begin, k_end, samples);
     if (!d_sum) return sq_set_error("d_sum is required: it carries the per-pixel fold from one range call to the next");
     if ((void*)d_sum == (void*)d_avg) return sq_set_error("d_sum and d_avg must be different buffers");
-    return render_rows(s, cam, 1, samples, w, h, cast, sh, k_begin, k_end, d_sum, d_avg, d_rgb, hip_stream);
+    return render_rows(s, cam, 1, samples, w, h, cast, sh, k_begin, k_end, d_sum, d_avg, d_rgb, hip_stream, d_mask, d_sum2, d_count);
+}
+
+// The stopping rule of the adaptive sampler (squigly_hip.h): one thread per pixel; every operation is one fp32 operation, in the
+// header's order (the build has -ffp-contract=off).  A wave counts its live pixels with a ballot and adds them with one atomic.
+__global__ void __launch_bounds__(kBlock) sq_adaptive_update(long long n_pixels, const float* sum, const float* sum2, const int32_t* count,
+                                                             float tol, float eps, uint8_t* mask, int32_t* live_out) {
+    const long long p = (long long)blockIdx.x * kBlock + threadIdx.x;
+    bool live = false;
+    if (p < n_pixels && mask[p] != 0) {
+        const int32_t c = count[p];
+        const float n = (float)c;
+        float L = 0.0f, R = 0.0f;
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) {
+            const float sc = sum[3 * p + ch], qc = sum2[3 * p + ch];
+            const float ss = sc * sc;
+            const float lhs = n * qc - ss, rhs = ss + eps * (n * n);
+            L = ch == 0 ? lhs : L + lhs;
+            R = ch == 0 ? rhs : R + rhs;
+        }
+        const bool converged = c >= 2 && L <= ((n - 1.0f) * (tol * tol)) * R;   // a NaN compares false: the pixel stays live
+        if (converged) mask[p] = 0;
+        live = !converged;
+    }
+    const unsigned long long m = sq_ballot(live);                       // every lane of the wave gets here
+    if ((threadIdx.x & 63) == 0 && m != 0) atomicAdd(live_out, __popcll(m));
+}
+
+extern "C" int sq_adaptive_update_device(sq_device_scene* s, int64_t n_pixels, const float* d_sum, const float* d_sum2,
+                                         const int32_t* d_count, float tol, float eps,
+                                         uint8_t* d_mask, int32_t* d_live, void* hip_stream) {
+    if (n_pixels < 0) return sq_set_error("n_pixels must not be negative (got %lld)", (long long)n_pixels);
+    if (!(tol >= 0.0f) || !(eps >= 0.0f)) return sq_set_error("tol and eps must be numbers >= 0 (got %g, %g)", (double)tol, (double)eps);
+    if (!s || !d_sum || !d_sum2 || !d_count || !d_mask || !d_live) return sq_set_error("null argument");
+    const long long blocks = ((long long)n_pixels + kBlock - 1) / kBlock;
+    if (blocks > 0x7fffffffLL) return sq_set_error("too many pixels for one launch");
+    SQ_HIP(hipSetDevice(s->device));
+    hipStream_t stream = (hipStream_t)hip_stream;
+    SQ_HIP(hipMemsetAsync(d_live, 0, sizeof(int32_t), stream));
+    if (blocks == 0) return 0;
+    hipLaunchKernelGGL(sq_adaptive_update, dim3((unsigned)blocks), dim3(kBlock), 0, stream, (long long)n_pixels, d_sum, d_sum2, d_count, tol, eps, d_mask, d_live);
+    SQ_HIP(hipGetLastError());
+    return 0;
 }
 
 extern "C" int sq_render_views_device(sq_device_scene* s, const sq_camera* cams, int32_t n_views, int32_t samples, int32_t w, int32_t h,

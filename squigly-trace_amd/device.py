@@ -94,6 +94,67 @@ class DeviceScene:
             C.c_void_p(st.cuda_stream)))
         return out_avg, out_rgb
 
+    def _frame_tensor(self, name, t, shape, dtype):
+        """t if it is a contiguous `dtype` tensor of `shape` on this device; SquiglyError otherwise."""
+        if (tuple(t.shape) != tuple(shape) or t.dtype != dtype or not t.is_contiguous()
+                or t.device != torch.device("cuda", self.device)):
+            raise N.SquiglyError(f"{name} must be a contiguous {dtype} tensor of shape {tuple(shape)} on cuda:{self.device}, "
+                                 f"got {t.dtype} {tuple(t.shape)} on {t.device}")
+        return t
+
+    def render_rows_masked(self, cam, samples, w, h, k_begin, k_end, sums, mask=None, sums2=None, counts=None, cast=False,
+                           shard=(None, 0, 1), want_avg=True, want_rgb=True, stream=None, out_avg=None, out_rgb=None):
+        """render_rows_range for the live pixels only (sq_render_rows_device_masked); returns (avg, rgb).
+
+        mask: uint8 CUDA tensor [rows, h], a pixel is rendered iff its byte is not 0 (None = every pixel) and, when counts is
+        given and k_begin > 0, counts[pixel] == k_begin.  sums2: float32 [rows, h, 3], the fold of r * r carried like sums.
+        counts: int32 [rows, h], set to k_end for the pixels rendered.  Pixels that are not rendered keep what every buffer
+        holds -- avg and rgb too, so pass out_avg / out_rgb to keep a picture across calls (fresh ones are zero-filled).
+        With mask, sums2 and counts all None this is render_rows_range.
+        """
+        given_avg, given_rgb = out_avg is not None, out_rgb is not None
+        sh, rows, out_avg, out_rgb, st = self._outputs(w, h, shard, want_avg, want_rgb, stream, out_avg, out_rgb)
+        if sums is None:
+            raise N.SquiglyError("render_rows_masked needs a sums tensor")
+        self._frame_tensor("sums", sums, (rows, h, 3), torch.float32)
+        if mask is not None:
+            self._frame_tensor("mask", mask, (rows, h), torch.uint8)
+        if sums2 is not None:
+            self._frame_tensor("sums2", sums2, (rows, h, 3), torch.float32)
+        if counts is not None:
+            self._frame_tensor("counts", counts, (rows, h), torch.int32)
+        if mask is not None or sums2 is not None or counts is not None:      # a masked call clears nothing: no stale memory in fresh outputs
+            with torch.cuda.stream(st):
+                if out_avg is not None and not given_avg:
+                    out_avg.zero_()
+                if out_rgb is not None and not given_rgb:
+                    out_rgb.zero_()
+        ptr = lambda t: t.data_ptr() if t is not None else None               # noqa: E731
+        N.check(N.lib().sq_render_rows_device_masked(
+            self._h, C.byref(cam), samples, w, h, int(bool(cast)), sh, int(k_begin), int(k_end), ptr(mask), sums.data_ptr(),
+            ptr(sums2), ptr(counts), ptr(out_avg), ptr(out_rgb), C.c_void_p(st.cuda_stream)))
+        return out_avg, out_rgb
+
+    def adaptive_update(self, sums, sums2, counts, mask, tol, eps, stream=None):
+        """The built-in stopping rule (sq_adaptive_update_device) on the pixels whose mask byte is set: a converged pixel's byte
+        is cleared.  Returns the number of pixels still live (waits for the stream).  A heuristic: see include/squigly_hip.h."""
+        dev = torch.device("cuda", self.device)
+        st = stream if stream is not None else torch.cuda.current_stream(dev)
+        shape = tuple(mask.shape)
+        self._frame_tensor("mask", mask, shape, torch.uint8)
+        self._frame_tensor("sums", sums, shape + (3,), torch.float32)
+        self._frame_tensor("sums2", sums2, shape + (3,), torch.float32)
+        self._frame_tensor("counts", counts, shape, torch.int32)
+        if mask.numel() == 0:
+            return 0
+        with torch.cuda.stream(st):
+            live = torch.empty(1, dtype=torch.int32, device=dev)
+            N.check(N.lib().sq_adaptive_update_device(self._h, int(mask.numel()), sums.data_ptr(), sums2.data_ptr(), counts.data_ptr(),
+                                                      float(tol), float(eps), mask.data_ptr(), live.data_ptr(),
+                                                      C.c_void_p(st.cuda_stream)))
+            st.synchronize()
+            return int(live.item())
+
     def render_views(self, cams, samples, w, h, cast=False, shard=(None, 0, 1), k_begin=0, k_end=None, sums=None, want_avg=True,
                      want_rgb=True, stream=None, out_avg=None, out_rgb=None):
         """Enqueue the frames of many cameras in one call (sq_render_views_device); returns (avg, rgb) CUDA tensors
@@ -257,3 +318,137 @@ class Progressive:
                                                  cast=self.cast, shard=self.shard, stream=stream)
         self._done = k_end
         return avg, rgb
+
+
+def rule_reference(sums, sums2, counts, mask, tol, eps):
+    """The stopping rule of sq_adaptive_update_device restated in numpy float32, operation for operation: returns the new
+    mask (uint8) of host arrays sums, sums2 [..., 3], counts, mask [...].  What the tests hold the kernel to."""
+    import numpy as np
+    f = np.float32
+    with np.errstate(all="ignore"):
+        s, q = np.asarray(sums, f), np.asarray(sums2, f)
+        c = np.asarray(counts, np.int32)
+        n = c.astype(f)
+        ss = s * s
+        lhs = n[..., None] * q - ss
+        rhs = ss + f(eps) * (n * n)[..., None]
+        L = (lhs[..., 0] + lhs[..., 1]) + lhs[..., 2]
+        R = (rhs[..., 0] + rhs[..., 1]) + rhs[..., 2]
+        converged = (c >= 2) & (L <= ((n - f(1)) * (f(tol) * f(tol))) * R)
+    return ((np.asarray(mask) != 0) & ~converged).astype(np.uint8)
+
+
+class Adaptive:
+    """A frame whose pixels stop receiving samples once a stopping rule calls them done (DeviceScene.render_rows_masked).
+
+    Owns -- or adopts, to resume a checkpoint -- the folds `sums` and `sums2` [rows, h, 3], the per-pixel sample `counts` and
+    the `mask` of live pixels [rows, h], and `done`, the end of the last range rendered.  `step()` renders the next range
+    (`first` samples, then `step` at a time) for the live pixels, applies the rule and returns the (avg, rgb) picture, in
+    which a pixel that stopped after n samples keeps the mean of its first n samples: bit for bit the reference's fold over
+    the first n samples of the `samples`-sample frame.  rule: a callable (sums, sums2, counts, mask) -> new mask instead of
+    the built-in rule (DeviceScene.adaptive_update with tol, eps), which is a heuristic -- a pixel that has seen nothing but
+    black after `first` samples stops.  A pixel the rule switches back on after it was left out of a range stays out: its
+    fold would have a gap.  To checkpoint, copy the four tensors and `done` away and pass them back in.
+    """
+
+    def __init__(self, dscene, cam, samples, w, h, tol, eps=1.0, first=8, step=8, cast=False, shard=(None, 0, 1), rule=None,
+                 sums=None, sums2=None, counts=None, mask=None, done=0):
+        samples, done, first, step = int(samples), int(done), int(first), int(step)
+        tol, eps = float(tol), float(eps)
+        if samples < 1:
+            raise ValueError(f"samples must be positive, got {samples}")
+        if not tol >= 0 or not eps >= 0:
+            raise ValueError(f"tol and eps must be numbers >= 0, got {tol}, {eps}")
+        if first < 1 or step < 1:
+            raise ValueError(f"first and step must be positive, got {first}, {step}")
+        if not 0 <= done <= samples:
+            raise ValueError(f"done must be in [0, {samples}], got {done}")
+        if rule is not None and not callable(rule):
+            raise ValueError("rule must be callable: (sums, sums2, counts, mask) -> mask")
+        if done and (sums is None or sums2 is None or counts is None or mask is None):
+            raise ValueError("resuming (done > 0) needs sums, sums2, counts and mask as the checkpoint left them")
+        rb, si, ns = shard
+        rows = N.lib().sq_shard_rows(w, N.Shard(int(w if rb is None else rb), int(si), int(ns)))
+        if rows < 0:
+            raise N.SquiglyError(f"bad shard {shard}")
+        dev = torch.device("cuda", dscene.device)
+
+        def adopt(name, t, shape, dtype, fill):   # a matching CUDA tensor as it is; a host copy is copied to the device
+            if t is None:
+                return torch.full(shape, fill, dtype=dtype, device=dev)
+            t = torch.as_tensor(t, dtype=dtype, device=dev).contiguous()
+            if tuple(t.shape) != shape:
+                raise ValueError(f"{name} must have shape {shape}, got {tuple(t.shape)}")
+            return t
+        self._sums = adopt("sums", sums, (rows, h, 3), torch.float32, 0)
+        self._sums2 = adopt("sums2", sums2, (rows, h, 3), torch.float32, 0)
+        self._counts = adopt("counts", counts, (rows, h), torch.int32, 0)
+        self._mask = adopt("mask", mask, (rows, h), torch.uint8, 1)
+        self.dscene, self.cam, self.samples, self.w, self.h = dscene, cam, samples, int(w), int(h)
+        self.tol, self.eps, self.first, self.step_size = tol, eps, first, step
+        self.cast, self.shard, self.rule = bool(cast), shard, rule
+        self._done = done
+        self._avg = torch.zeros((rows, h, 3), dtype=torch.float32, device=dev)
+        self._rgb = torch.zeros((rows, h, 3), dtype=torch.uint8, device=dev)
+        if done:
+            self._restore_picture()
+        self._live = self._count_live()
+
+    def _count_live(self):
+        live = self._mask != 0
+        if self._done:
+            live &= self._counts == self._done           # a pixel left behind cannot resume (the gap guard of the masked call)
+        return int(live.sum().item())
+
+    def _restore_picture(self):
+        """avg and rgb of a checkpoint: (1 / (float)count) *^ sum, as the call that last rendered the pixel wrote it (numpy's
+        float32 division and product are the device's correctly rounded ones), and the device's own tonemap of it."""
+        import numpy as np
+        c = self._counts.cpu().numpy()
+        s = self._sums.cpu().numpy()
+        with np.errstate(all="ignore"):
+            avg = (np.float32(1) / np.maximum(c, 1).astype(np.float32))[..., None] * s
+        avg[c == 0] = 0
+        rgb = N.debug_eval("tonemap", avg.reshape(-1, 3), device=self.dscene.device).reshape(avg.shape)
+        rgb[c == 0] = 0
+        self._avg.copy_(torch.from_numpy(np.ascontiguousarray(avg)))
+        self._rgb.copy_(torch.from_numpy(np.ascontiguousarray(rgb)))
+
+    sums = property(lambda self: self._sums, doc="Per-pixel fold of the sample radiances over the pixel's first counts samples.")
+    sums2 = property(lambda self: self._sums2, doc="Per-pixel fold of r * r over the same samples.")
+    counts = property(lambda self: self._counts, doc="Samples each pixel has received (int32 CUDA tensor [rows, h]).")
+    mask = property(lambda self: self._mask, doc="1 = the pixel is still live (uint8 CUDA tensor [rows, h]).")
+    done = property(lambda self: self._done, doc="End of the last sample range rendered.")
+    live = property(lambda self: self._live, doc="Pixels the next step would render.")
+
+    @property
+    def finished(self):
+        return self._live == 0 or self._done >= self.samples
+
+    @property
+    def samples_spent(self):
+        """Samples rendered so far, over all pixels (waits for the device)."""
+        return int(self._counts.sum(dtype=torch.int64).item())
+
+    def step(self, stream=None):
+        """Render the next range for the live pixels and apply the rule; returns the (avg, rgb) CUDA tensors of the frame."""
+        if self.finished:
+            raise RuntimeError("the frame is finished: no pixel is live" if self._live == 0
+                               else f"the frame is finished: all {self.samples} samples are rendered")
+        k_end = min(self._done + (self.first if self._done == 0 else self.step_size), self.samples)
+        self.dscene.render_rows_masked(self.cam, self.samples, self.w, self.h, self._done, k_end, self._sums, mask=self._mask,
+                                       sums2=self._sums2, counts=self._counts, cast=self.cast, shard=self.shard, stream=stream,
+                                       out_avg=self._avg, out_rgb=self._rgb)
+        self._done = k_end
+        if self.rule is None:
+            self._live = self.dscene.adaptive_update(self._sums, self._sums2, self._counts, self._mask, self.tol, self.eps,
+                                                     stream=stream)
+        else:
+            st = stream if stream is not None else torch.cuda.current_stream(self._mask.device)
+            with torch.cuda.stream(st):
+                new = torch.as_tensor(self.rule(self._sums, self._sums2, self._counts, self._mask), device=self._mask.device)
+                if tuple(new.shape) != tuple(self._mask.shape):
+                    raise ValueError(f"rule must return a mask of shape {tuple(self._mask.shape)}, got {tuple(new.shape)}")
+                self._mask.copy_((new != 0).to(torch.uint8))
+                self._live = self._count_live()
+        return self._avg, self._rgb

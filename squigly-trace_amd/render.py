@@ -61,6 +61,27 @@ def render_progressive(bih, cam, samples, dimensions, step, cast=False, device=0
         ds.close()
 
 
+def render_adaptive(bih, cam, samples, dimensions, tol, eps=1.0, first=8, step=8, cast=False, device=0, rule=None):
+    """The frame of render_rgb8 with adaptive sampling (DeviceScene, Adaptive): yields (done, live, spent, rgb8, counts) after
+    every step -- the end of the range rendered, the pixels still live, the samples spent so far, the (w, h, 3) uint8 image and
+    the (w, h) int32 per-pixel sample counts.  A pixel that stopped after n samples shows the mean of its first n samples, so
+    with first >= samples (one step, every pixel live) the image is bit for bit that of render_rgb8."""
+    from .device import Adaptive, DeviceScene          # torch: only the resident-scene path needs it
+    w, h = dimensions
+    if int(first) < 1 or int(step) < 1:
+        raise ValueError(f"first and step must be positive, got {first}, {step}")
+    if not float(tol) >= 0 or not float(eps) >= 0:
+        raise ValueError(f"tol and eps must be numbers >= 0, got {tol}, {eps}")
+    ds = DeviceScene(bih, device)
+    try:
+        a = Adaptive(ds, cam, samples, w, h, tol, eps=eps, first=first, step=step, cast=cast, rule=rule)
+        while not a.finished:
+            _, rgb = a.step()
+            yield a.done, a.live, a.samples_spent, rgb.cpu().numpy(), a.counts.cpu().numpy()
+    finally:
+        ds.close()
+
+
 def render_views_rgb8(bih, cams, samples, dimensions, cast=False, device=0) -> np.ndarray:
     """The image of render_rgb8 for every camera of `cams`, rendered in one call (DeviceScene.render_views): shape (n, w, h, 3)
     uint8, view i bit for bit render_rgb8 of cams[i]."""

@@ -1,0 +1,620 @@
+"""Adaptive sampling (sq_render_rows_device_masked, sq_adaptive_update_device, DeviceScene.render_rows_masked / adaptive_update,
+Adaptive, render_adaptive and the CLI's --adaptive): a masked range call renders exactly the live pixels, each of which holds bit
+for bit the oracle's left folds of r and r * r over its own prefix of the frame's samples (src/Lib.hs:85-88); every other pixel
+keeps what every buffer held.  All comparisons are on bits."""
+import ctypes as C
+import os
+import sys
+
+import numpy as np
+import pytest
+
+from conftest import ROOT
+from test_gpu_progressive import DEFAULTS, OPTION_TUPLES, THREADS, canon, ibits, overflow_room, set_options, soup
+
+pytestmark = pytest.mark.gpu
+f32 = np.float32
+SENT = {"sums": 7.25, "sums2": 5.5, "avg": -3.5, "rgb": 123, "counts": 77}
+assert DEFAULTS["variant"] == 2
+
+
+@pytest.fixture(scope="module")
+def dev(sqt, product_scene):
+    assert sqt.device_count() >= 1, "no HIP device: the product has no CPU fallback"
+    bih, _, _ = product_scene
+    ds = sqt.DeviceScene(bih, 0)
+    yield ds
+    ds.close()
+
+
+_SAMPLES = {}
+
+
+def oracle_samples(ob, cam_o, n, w, h, k_hi=None, cast=False, key=None):
+    """[k_hi, w, h, 3] float32: the radiance of sample k of pixel (y, x) of the n-sample frame (a cast frame: its cast colour)."""
+    k_hi = n if k_hi is None else k_hi
+    ck = (key, n, w, h, k_hi, cast)
+    if key is not None and ck in _SAMPLES:
+        return _SAMPLES[ck]
+    if cast:   # the cast colour of a pixel is the oracle's 1-sample cast frame (1 / 1 * c == c)
+        c, _, _ = ob.render(cam_o, 1, w, h, cast=True, threads=THREADS)
+        s = np.broadcast_to(c, (k_hi,) + c.shape).copy()
+    else:
+        s = np.array([[[ob.sample_radiance(cam_o, n, w, h, y, x, k) for x in range(h)] for y in range(w)] for k in range(k_hi)], f32)
+    if key is not None:
+        _SAMPLES[ck] = s
+    return s
+
+
+def fold(samples, a, b, s=None, q=None):
+    """The float32 left folds of r and of r * r (the product rounded before the add) over the samples [a, b), continued from s, q."""
+    s = np.zeros(samples.shape[1:], f32) if s is None else s.copy()
+    q = np.zeros(samples.shape[1:], f32) if q is None else q.copy()
+    with np.errstate(all="ignore"):
+        for k in range(a, b):
+            r = samples[k]
+            s = s + r
+            q = q + r * r
+    return s, q
+
+
+def tonemap_image(O, avg):
+    return np.array([[O.tonemap(tuple(float(v) for v in px)) for px in row] for row in avg], np.uint8)
+
+
+def avg_of(sums, counts):
+    with np.errstate(all="ignore"):
+        return (f32(1) / np.maximum(counts, 1).astype(f32))[..., None] * sums
+
+
+def buffers(rows, h):
+    """The five output buffers of a masked call, filled with sentinels."""
+    import torch
+    mk = lambda shape, dt, v: torch.full(shape, v, dtype=dt, device="cuda:0")  # noqa: E731
+    return {"sums": mk((rows, h, 3), torch.float32, SENT["sums"]), "sums2": mk((rows, h, 3), torch.float32, SENT["sums2"]),
+            "counts": mk((rows, h), torch.int32, SENT["counts"]), "avg": mk((rows, h, 3), torch.float32, SENT["avg"]),
+            "rgb": mk((rows, h, 3), torch.uint8, SENT["rgb"])}
+
+
+def masked(ds, cam, n, w, h, a, b, B, mask, with_counts=True, with_sums2=True, **kw):
+    import torch
+    m = None if mask is None else torch.from_numpy(np.ascontiguousarray(mask, np.uint8)).cuda()
+    ds.render_rows_masked(cam, n, w, h, a, b, B["sums"], mask=m, sums2=B["sums2"] if with_sums2 else None,
+                          counts=B["counts"] if with_counts else None, out_avg=B["avg"], out_rgb=B["rgb"], **kw)
+    torch.cuda.synchronize()
+
+
+def host(B):
+    return {k: v.cpu().numpy() for k, v in B.items()}
+
+
+def option_kw(opts):
+    if opts == "pool0":
+        return {"pool": 0}
+    if opts == "cast":
+        return {}
+    return dict(zip(("variant", "resident", "profile", "overlap", "primary_pooled"), opts))
+
+
+# ---- 1. null arguments are the range call --------------------------------------------------------------------------------
+@pytest.mark.parametrize("small_slots", [False, True])
+@pytest.mark.parametrize("opts", OPTION_TUPLES + ("pool0", "cast"))
+def test_null_arguments_are_the_range_call(sqt, product_scene, dev, opts, small_slots):
+    import torch
+    _, cam, _ = product_scene
+    w, h, n = 40, 30, 9
+    cast = opts == "cast"
+    set_options(dev, slots=(w * h * 2) if small_slots else (512 << 20), **option_kw(opts))
+    try:
+        s1, s2 = (torch.full((w, h, 3), 7.25, dtype=torch.float32, device="cuda:0") for _ in range(2))
+        for a, b in ((0, 4), (4, 9)):
+            a1, r1 = dev.render_rows_range(cam, n, w, h, a, b, s1, cast=cast)
+            a2, r2 = dev.render_rows_masked(cam, n, w, h, a, b, s2, cast=cast)
+            torch.cuda.synchronize()
+            assert np.array_equal(ibits(a1), ibits(a2)), (opts, b, "avg")
+            assert torch.equal(r1, r2), (opts, b, "rgb")
+            assert np.array_equal(ibits(s1), ibits(s2)), (opts, b, "sums")
+        a0, r0 = dev.render_rows(cam, n, w, h, cast=cast)
+        torch.cuda.synchronize()
+        assert np.array_equal(ibits(a0), ibits(a2)) and torch.equal(r0, r2)
+    finally:
+        set_options(dev)
+
+
+# ---- 2. all-ones mask, moments on ------------------------------------------------------------------------------------------
+def moments_check(sqt, O, ds, cam_p, ob, cam_o, w, h, n, bounds, nan_ok=False, key=None, mask_none=False):
+    import torch
+    samples = oracle_samples(ob, cam_o, n, w, h, key=key)
+    cmp = canon if nan_ok else ibits
+    B = buffers(w, h)
+    s = q = None
+    for a, b in zip(bounds, bounds[1:]):
+        masked(ds, cam_p, n, w, h, a, b, B, None if mask_none else np.ones((w, h), np.uint8))
+        s, q = fold(samples, a, b, s, q)
+        assert np.array_equal(cmp(B["sums"]), cmp(s)), ("sums", b)
+        assert np.array_equal(cmp(B["sums2"]), cmp(q)), ("sums2", b)
+        assert (B["counts"].cpu().numpy() == b).all(), ("counts", b)
+        want_avg = f32(1) / f32(b) * s
+        assert np.array_equal(cmp(B["avg"]), cmp(want_avg)), ("avg", b)
+        assert np.array_equal(B["rgb"].cpu().numpy(), tonemap_image(O, want_avg)), ("rgb", b)
+    a1, r1 = ds.render_rows(cam_p, n, w, h)
+    torch.cuda.synchronize()
+    assert np.array_equal(cmp(a1), cmp(B["avg"])) and torch.equal(r1, B["rgb"])
+    miss = np.array([[not ob.intersect(*O.make_ray(w, h, y, x, cam_o)).hit for x in range(h)] for y in range(w)])
+    assert (ibits(B["sums"])[miss] == 0).all() and (ibits(B["sums2"])[miss] == 0).all()      # +0 bits, not -0 or NaN
+    return s, q, miss, B
+
+
+@pytest.mark.parametrize("opts", [{}, {"variant": 1}, {"resident": 0}, {"primary_resident": 0}, {"primary_pooled": 1}, {"overlap": 1},
+                                  {"overlap": 2, "primary_pooled": 1}, {"pool": 0}, {"small_slots": 1}, {"mask_none": 1},
+                                  {"mask_none": 1, "variant": 1}])
+def test_full_mask_with_moments_follows_the_oracle_folds(sqt, O, product_scene, oracle_scene, dev, opts):
+    _, cam, _ = product_scene
+    ob, ocam, _ = oracle_scene
+    w, h, n = 24, 20, 6
+    opts = dict(opts)
+    if opts.pop("small_slots", 0):
+        opts["slots"] = w * h * 2
+    pr = opts.pop("primary_resident", 1)
+    mask_none = bool(opts.pop("mask_none", 0))                        # d_mask == NULL with moments and counts: every pixel is live
+    set_options(dev, **opts)
+    dev.set_option("primary_resident", pr)
+    try:
+        s, q, miss, _ = moments_check(sqt, O, dev, cam, ob, ocam, w, h, n, [0, 1, 4, 6], key="scene", mask_none=mask_none)
+        assert miss.any() and (q > 0).any()
+    finally:
+        set_options(dev)
+        dev.set_option("primary_resident", 1)
+
+
+@pytest.mark.parametrize("which", ["soup", "overflow"])
+def test_moments_on_mirrors_emitters_and_overflow(sqt, O, which):
+    bih, ob, cam_p, cam_o = soup(sqt, O, 4, 12) if which == "soup" else overflow_room(sqt, O)
+    ds = sqt.DeviceScene(bih, 0)
+    try:
+        s, q, _, _ = moments_check(sqt, O, ds, cam_p, ob, cam_o, 24, 20, 6, [0, 1, 4, 6], nan_ok=True, key=which)
+        if which == "overflow":
+            assert np.isnan(s).any() and np.isnan(q).any()              # NaN reaches both folds
+        else:
+            assert (q > 0).any()
+        ds.set_option("overlap", 2)
+        moments_check(sqt, O, ds, cam_p, ob, cam_o, 24, 20, 6, [0, 3, 6], nan_ok=True, key=which)
+        ds.set_option("overlap", 0)
+        ds.set_option("variant", 1)
+        moments_check(sqt, O, ds, cam_p, ob, cam_o, 24, 20, 6, [0, 2, 6], nan_ok=True, key=which)
+    finally:
+        ds.close()
+
+
+# ---- 3. random masks ---------------------------------------------------------------------------------------------------------
+def random_masks_check(sqt, O, ds, cam_p, samples, w, h, n, k1, k2, seed, rows=None, cast=False, shard=(None, 0, 1), nan_ok=False):
+    """Sentinel-filled buffers; [0, k1) under a random mask, [k1, k2) under a random subset of it."""
+    rows = list(range(w)) if rows is None else rows
+    samples = samples[:, rows]
+    R = len(rows)
+    rng = np.random.default_rng(seed)
+    m1 = (rng.random((R, h)) < 0.5).astype(np.uint8) * rng.integers(1, 256, (R, h)).astype(np.uint8)      # any non-zero byte counts
+    m2 = ((m1 != 0) & (rng.random((R, h)) < 0.5)).astype(np.uint8)
+    assert 0 < (m2 != 0).sum() < (m1 != 0).sum() < R * h
+    B = buffers(R, h)
+    masked(ds, cam_p, n, w, h, 0, k1, B, m1, cast=cast, shard=shard)
+    masked(ds, cam_p, n, w, h, k1, k2, B, m2, cast=cast, shard=shard)
+    got = host(B)
+    s1, q1 = fold(samples, 0, k1)
+    s2, q2 = fold(samples, k1, k2, s1, q1)
+    live1, live2 = m1 != 0, m2 != 0
+    want = {"sums": np.full((R, h, 3), SENT["sums"], f32), "sums2": np.full((R, h, 3), SENT["sums2"], f32),
+            "counts": np.full((R, h), SENT["counts"], np.int32)}
+    for live, s, q, k in ((live1, s1, q1, k1), (live2, s2, q2, k2)):
+        want["sums"][live], want["sums2"][live], want["counts"][live] = s[live], q[live], k
+    want["avg"] = avg_of(want["sums"], want["counts"])
+    want["avg"][~live1] = SENT["avg"]
+    want["rgb"] = tonemap_image(O, want["avg"])
+    want["rgb"][~live1] = SENT["rgb"]
+    cmp = canon if nan_ok else ibits
+    for name in ("sums", "sums2", "avg"):
+        bad = np.argwhere(cmp(got[name]) != cmp(want[name]))
+        assert len(bad) == 0, (name, len(bad), bad[:3].tolist())
+    assert np.array_equal(got["counts"], want["counts"]), "counts"
+    assert np.array_equal(got["rgb"], want["rgb"]), "rgb"
+
+
+@pytest.mark.parametrize("small_slots", [False, True])
+@pytest.mark.parametrize("opts", OPTION_TUPLES + ("pool0", "cast"))
+def test_random_masks(sqt, O, product_scene, oracle_scene, dev, opts, small_slots):
+    _, cam, _ = product_scene
+    ob, ocam, _ = oracle_scene
+    w, h, n, k1, k2 = 24, 20, 8, 3, 7
+    cast = opts == "cast"
+    samples = oracle_samples(ob, ocam, n, w, h, k_hi=k2, cast=cast, key="scene")
+    set_options(dev, slots=(w * h * 2) if small_slots else (512 << 20), **option_kw(opts))
+    try:
+        random_masks_check(sqt, O, dev, cam, samples, w, h, n, k1, k2, seed=11 + small_slots, cast=cast)
+    finally:
+        set_options(dev)
+
+
+def test_random_masks_per_lane_primary_rays(sqt, O, product_scene, oracle_scene, dev):
+    _, cam, _ = product_scene
+    ob, ocam, _ = oracle_scene
+    w, h, n, k1, k2 = 24, 20, 8, 3, 7
+    samples = oracle_samples(ob, ocam, n, w, h, k_hi=k2, key="scene")
+    set_options(dev)
+    dev.set_option("primary_resident", 0)
+    try:
+        random_masks_check(sqt, O, dev, cam, samples, w, h, n, k1, k2, seed=5)
+        assert dev.last_plan()["primary_form"] == "per_lane"
+    finally:
+        dev.set_option("primary_resident", 1)
+
+
+@pytest.mark.parametrize("variant", [2, 1])
+def test_random_masks_on_shards(sqt, O, product_scene, oracle_scene, dev, variant):
+    from importlib import import_module
+    d = import_module("squigly-trace_amd.dist")
+    _, cam, _ = product_scene
+    ob, ocam, _ = oracle_scene
+    w, h, n, k1, k2 = 24, 20, 8, 3, 7
+    samples = oracle_samples(ob, ocam, n, w, h, k_hi=k2, key="scene")
+    set_options(dev, variant=variant)
+    try:
+        for r in range(3):
+            random_masks_check(sqt, O, dev, cam, samples, w, h, n, k1, k2, seed=20 + r, rows=d.shard_rows(w, 2, r, 3), shard=(2, r, 3))
+    finally:
+        set_options(dev)
+
+
+def test_random_masks_with_32_bit_stack_words(sqt, O):
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import gen_scenes as G
+    obj, sq, camt = G.heightfield_scene(130)
+    bih = sqt.BIH(sqt.Mesh.from_text(obj, sq))
+    assert bih.scene.n_tris > 0x8000
+    ob = O.BIH(O.tris_from_text(obj, sq))
+    cam, ocam = sqt.camera_from_text(camt), O.camera_from_text(camt)
+    w, h, n, k1, k2 = 16, 12, 5, 2, 4
+    samples = oracle_samples(ob, ocam, n, w, h, k_hi=k2)
+    ds = sqt.DeviceScene(bih, 0)
+    try:
+        for variant in (2, 1):
+            ds.set_option("variant", variant)
+            random_masks_check(sqt, O, ds, cam, samples, w, h, n, k1, k2, seed=31 + variant)
+            plan = ds.last_plan()
+            assert plan["stack_word_bytes"] == 4
+            if variant == 2:
+                assert plan["trace_form"] in ("streaming_six_wave", "streaming_plain")
+    finally:
+        ds.close()
+
+
+# ---- 4. the gap guard --------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("variant", [2, 1])
+def test_gap_guard(sqt, O, product_scene, oracle_scene, dev, variant):
+    _, cam, _ = product_scene
+    ob, ocam, _ = oracle_scene
+    w, h, n = 24, 20, 12
+    samples = oracle_samples(ob, ocam, n, w, h, key="scene")
+    out = np.zeros((w, h), bool)
+    out[5:15, 4:16] = True                                            # the pixels left out of [4, 8)
+    assert (np.abs(samples[8:12][:, out]).sum() > 0) and (np.abs(samples[4:8][:, out]).sum() > 0)
+    ones = np.ones((w, h), np.uint8)
+    set_options(dev, variant=variant)
+    try:
+        B = buffers(w, h)
+        masked(dev, cam, n, w, h, 0, 4, B, ones)
+        first = host(B)
+        masked(dev, cam, n, w, h, 4, 8, B, (~out).astype(np.uint8))
+        masked(dev, cam, n, w, h, 8, 12, B, ones)                      # masked in again, d_count given: skipped
+        got = host(B)
+        s4, q4 = fold(samples, 0, 4)
+        s12, q12 = fold(samples, 4, 12, s4, q4)
+        assert (got["counts"][out] == 4).all() and (got["counts"][~out] == 12).all()
+        for name in first:
+            assert np.array_equal(got[name][out].view(np.uint8), first[name][out].view(np.uint8)), name     # untouched since [0, 4)
+        assert np.array_equal(ibits(got["sums"][out]), ibits(s4[out])) and np.array_equal(ibits(got["sums2"][out]), ibits(q4[out]))
+        assert np.array_equal(ibits(got["sums"][~out]), ibits(s12[~out])) and np.array_equal(ibits(got["sums2"][~out]), ibits(q12[~out]))
+        # without d_count nothing guards the fold: the call renders the pixel (the caller's responsibility, squigly_hip.h)
+        masked(dev, cam, n, w, h, 8, 12, B, out.astype(np.uint8), with_counts=False)
+        got = host(B)
+        sg, qg = fold(samples, 8, 12, s4, q4)                           # a fold with the gap [4, 8)
+        assert np.array_equal(ibits(got["sums"][out]), ibits(sg[out])) and np.array_equal(ibits(got["sums2"][out]), ibits(qg[out]))
+        assert (got["counts"][out] == 4).all()                           # no d_count in that call: not written either
+        assert np.array_equal(ibits(got["avg"][out]), ibits((f32(1) / f32(12) * sg)[out]))
+        assert np.array_equal(ibits(got["sums"][~out]), ibits(s12[~out]))
+    finally:
+        set_options(dev)
+
+
+# ---- 5. empty masks ----------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("opts", [{}, {"variant": 1}, {"resident": 0}, {"primary_pooled": 1}, {"overlap": 2}, {"cast": 1}])
+def test_empty_mask_changes_nothing(sqt, product_scene, dev, opts):
+    _, cam, _ = product_scene
+    w, h, n = 24, 20, 6
+    opts = dict(opts)
+    cast = bool(opts.pop("cast", 0))
+    set_options(dev, **opts)
+    try:
+        for a, b in ((0, 3), (3, 6)):
+            B = buffers(w, h)
+            keep = host(B)
+            masked(dev, cam, n, w, h, a, b, B, np.zeros((w, h), np.uint8), cast=cast)
+            # documented in squigly_hip.h: the call cannot know that no pixel is live without waiting for the device, so it
+            # enqueues its (empty) launches and reports launched = 1
+            assert dev.last_plan()["launched"] == 1
+            got = host(B)
+            for name in keep:
+                assert np.array_equal(got[name].view(np.uint8), keep[name].view(np.uint8)), (opts, name)
+        # ... and a mask of ones whose counts all differ from k_begin is as empty
+        B = buffers(w, h)
+        keep = host(B)
+        masked(dev, cam, n, w, h, 3, 6, B, np.ones((w, h), np.uint8), cast=cast)       # counts hold the sentinel 77, not 3
+        got = host(B)
+        for name in keep:
+            assert np.array_equal(got[name].view(np.uint8), keep[name].view(np.uint8)), (opts, name)
+    finally:
+        set_options(dev)
+
+
+# ---- 6. the rule on the device -----------------------------------------------------------------------------------------------
+def rule_check(sqt, ds, sums, sums2, counts, mask, tol, eps):
+    import torch
+    t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dt)).cuda()        # noqa: E731
+    ts, tq, tc, tm = t(sums, f32), t(sums2, f32), t(counts, np.int32), t(mask, np.uint8)
+    live = ds.adaptive_update(ts, tq, tc, tm, tol, eps)
+    want = sqt.rule_reference(sums, sums2, counts, mask, tol, eps)
+    got = tm.cpu().numpy()                                            # a converged pixel's byte is cleared, a live one keeps its byte
+    assert np.array_equal(got, np.where(want != 0, mask, 0)), np.argwhere(got != np.where(want != 0, mask, 0))[:4].tolist()
+    assert live == int(want.sum())
+    assert np.array_equal(ibits(ts), ibits(sums)) and np.array_equal(ibits(tq), ibits(sums2)) and np.array_equal(tc.cpu().numpy(), counts)
+    return want
+
+
+def test_rule_on_the_device_equals_the_numpy_restatement(sqt, O, product_scene, oracle_scene, dev):
+    _, cam, _ = product_scene
+    ob, ocam, _ = oracle_scene
+    set_options(dev)
+    w, h, n = 24, 20, 6
+    _, _, _, B = moments_check(sqt, O, dev, cam, ob, ocam, w, h, n, [0, 6], key="scene")
+    g = host(B)
+    for tol, eps in ((0.5, 1.0), (0.0, 0.0), (2.0, 0.0), (0.05, 100.0)):
+        want = rule_check(sqt, dev, g["sums"], g["sums2"], g["counts"], np.ones((w, h), np.uint8), tol, eps)
+    assert 0 < rule_check(sqt, dev, g["sums"], g["sums2"], g["counts"], np.ones((w, h), np.uint8), 0.5, 1.0).sum() < w * h
+    del want
+    # adversarial values: every bit pattern class in both moments (NaN, inf, denormals, negative sums), odd counts, odd masks
+    rng = np.random.default_rng(7)
+    N = 64 * 37 + 5                                                     # a last wave that is not full
+    special = np.array([0.0, -0.0, np.inf, -np.inf, np.nan, 1e-45, -1e-45, 1e-38, 3e38, -3e38, 1.0, -1.0, 100.0, 4097.0, 8392704.0], f32)
+    sums = rng.integers(0, 2 ** 32, (N, 3), dtype=np.uint64).astype(np.uint32).view(f32)
+    sums2 = rng.integers(0, 2 ** 32, (N, 3), dtype=np.uint64).astype(np.uint32).view(f32)
+    pick = rng.random((N, 3)) < 0.5
+    sums[pick] = special[rng.integers(0, len(special), pick.sum())]
+    pick = rng.random((N, 3)) < 0.5
+    sums2[pick] = special[rng.integers(0, len(special), pick.sum())]
+    tame = rng.random(N) < 0.4                                          # plausible statistics of n samples in [0, 100]
+    counts = rng.choice(np.array([0, 1, 2, 3, 8, 64, 1000, (1 << 24) + 1, -5], np.int32), N)
+    for i in np.flatnonzero(tame):
+        c = max(int(counts[i]), 1) if counts[i] < 2000 else 16
+        r = (rng.random((c, 3)) < 0.3) * rng.uniform(0, 100, (c, 3))
+        r = r.astype(f32)
+        sums[i], sums2[i] = fold(r[:, None, :], 0, c)[0][0], fold(r[:, None, :], 0, c)[1][0]
+        counts[i] = c if rng.random() < 0.9 else 1
+    mask = rng.choice(np.array([0, 1, 1, 200], np.uint8), N)
+    for tol, eps in ((0.5, 1.0), (0.0, 0.0), (1e-20, 1e-30), (3e19, 3e38)):
+        want = rule_check(sqt, dev, sums, sums2, counts, mask, tol, eps)
+        assert (want[mask == 0] == 0).all()
+    assert 0 < rule_check(sqt, dev, sums, sums2, counts, mask, 0.5, 1.0).sum() < (mask != 0).sum()
+    L = sqt.lib()
+    one = C.c_void_p(16)
+    assert L.sq_adaptive_update_device(dev._h, 4, None, one, one, 0.5, 1.0, one, one, None) != 0      # refused before any launch
+    assert rule_check(sqt, dev, sums[:0], sums2[:0], counts[:0], mask[:0], 0.5, 1.0).size == 0           # no pixel: live = 0
+
+
+# ---- 7. end to end ----------------------------------------------------------------------------------------------------------
+def simulate(sqt, samples, n, tol, eps, first, step, rule=None):
+    """Adaptive restated in numpy on the oracle's samples: (sums, sums2, counts, mask, spent, steps)."""
+    w, h = samples.shape[1:3]
+    s, q = np.zeros((w, h, 3), f32), np.zeros((w, h, 3), f32)
+    counts, mask = np.zeros((w, h), np.int32), np.ones((w, h), np.uint8)
+    done, steps = 0, []
+    while done < n and (mask != 0).any():
+        k_end = min(done + (first if done == 0 else step), n)
+        live = mask != 0
+        s2, q2 = fold(samples, done, k_end, s, q)
+        s[live], q[live], counts[live] = s2[live], q2[live], k_end
+        done = k_end
+        mask = sqt.rule_reference(s, q, counts, mask, tol, eps) if rule is None else rule(s, q, counts, mask)
+        steps.append((done, int((mask != 0).sum()), int(counts.sum())))
+    return s, q, counts, mask, steps
+
+
+def test_adaptive_end_to_end_equals_the_simulation_on_oracle_samples(sqt, O, product_scene, oracle_scene, dev):
+    import torch
+    _, cam, _ = product_scene
+    ob, ocam, _ = oracle_scene
+    w, h, n, tol, eps, first, step = 24, 20, 64, 0.5, 1.0, 8, 8
+    samples = oracle_samples(ob, ocam, n, w, h, key="scene64")
+    s, q, counts, mask, steps = simulate(sqt, samples, n, tol, eps, first, step)
+    values, freq = np.unique(counts, return_counts=True)
+    print(f"[adaptive] oracle simulation: counts {dict(zip(values.tolist(), freq.tolist()))}, spent {int(counts.sum())} of {w * h * n}")
+    # the oracle alone must make the test meaningful
+    assert len(values) >= 3, "fewer than three distinct per-pixel counts"
+    assert (counts == first).any(), "no pixel stops after the first step"
+    assert (counts == n).any(), "no pixel runs to the end"
+    assert int(counts.sum()) < w * h * n // 2, "the rule saves less than half of the samples"
+    set_options(dev)
+    a = sqt.Adaptive(dev, cam, n, w, h, tol, eps=eps, first=first, step=step)
+    assert (a.done, a.live, a.finished, a.samples_spent) == (0, w * h, False, 0)
+    seen = []
+    while not a.finished:
+        avg, rgb = a.step()
+        seen.append((a.done, a.live, a.samples_spent))
+    torch.cuda.synchronize()
+    assert seen == steps
+    with pytest.raises(RuntimeError):
+        a.step()
+    assert np.array_equal(a.counts.cpu().numpy(), counts)
+    assert np.array_equal(a.mask.cpu().numpy(), mask)
+    assert np.array_equal(ibits(a.sums), ibits(s)) and np.array_equal(ibits(a.sums2), ibits(q))
+    want_avg = avg_of(s, counts)
+    assert np.array_equal(ibits(avg), ibits(want_avg))
+    assert np.array_equal(rgb.cpu().numpy(), tonemap_image(O, want_avg))
+    assert a.samples_spent == int(counts.sum())
+    # a rule of the caller's instead: stop the left half after the first step, never the right half
+    def halves(sums, sums2, cnt, m):
+        out = torch.ones_like(m) if hasattr(m, "cpu") else np.ones_like(m)
+        out[: w // 2] = 0
+        return out
+    b = sqt.Adaptive(dev, cam, 20, w, h, tol, first=4, step=8, rule=halves)
+    while not b.finished:
+        b.step()
+    torch.cuda.synchronize()
+    c = b.counts.cpu().numpy()
+    assert (c[: w // 2] == 4).all() and (c[w // 2:] == 20).all() and b.done == 20 and b.live == (w - w // 2) * h
+    s20 = oracle_samples(ob, ocam, 20, w, h, key="scene20")
+    sb, qb, cb, _, _ = simulate(sqt, s20, 20, tol, 1.0, 4, 8, rule=halves)
+    assert np.array_equal(cb, c) and np.array_equal(ibits(b.sums), ibits(sb)) and np.array_equal(ibits(b.sums2), ibits(qb))
+
+
+# ---- 8. refusals -------------------------------------------------------------------------------------------------------------
+def test_refusals_leave_every_buffer_untouched(sqt, product_scene, dev):
+    import torch
+    import tree_padding as TP
+    bih, cam, _ = product_scene
+    set_options(dev)
+    w, h, n = 16, 12, 4
+    L = sqt.lib()
+    sh = sqt.Shard(w, 0, 1)
+    B = buffers(w, h)
+    B["mask"] = torch.ones((w, h), dtype=torch.uint8, device="cuda:0")
+    big = torch.full((w * h * 3 * 2,), 9.5, dtype=torch.float32, device="cuda:0")          # two overlapping views of one buffer
+    keep = {k: v.clone() for k, v in B.items()}
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    P = {k: v.data_ptr() for k, v in B.items()}
+
+    def call(ds_h, kb, ke, shard=sh, samples=n, **over):
+        p = {**P, **over}
+        return L.sq_render_rows_device_masked(ds_h, C.byref(cam), samples, w, h, 0, shard, kb, ke, p["mask"], p["sums"], p["sums2"],
+                                              p["counts"], p["avg"], p["rgb"], stream)
+
+    assert call(dev._h, 0, n) == 0                                       # the arguments are fine: every refusal below is its own
+    assert call(dev._h, 0, n, sums=big.data_ptr(), sums2=big.data_ptr() + 12 * w * h) == 0              # adjacent is not overlapping
+    torch.cuda.synchronize()
+    for k, v in keep.items():
+        B[k].copy_(v)
+    rng_err, ovl = b"bad sample range", b"overlap"
+    cases = {
+        "k_begin < 0": ((-1, 2), {}, rng_err), "k_end == k_begin": ((2, 2), {}, rng_err), "k_end < k_begin": ((3, 1), {}, rng_err),
+        "k_end > samples": ((0, n + 1), {}, rng_err),
+        "d_sum NULL": ((0, n), {"sums": None}, b"d_sum is required"), "d_sum == d_avg": ((0, n), {"avg": P["sums"]}, b"d_sum and d_avg"),
+        "d_sum2 == d_sum": ((0, n), {"sums2": P["sums"]}, ovl), "d_sum2 == d_avg": ((0, n), {"sums2": P["avg"]}, ovl),
+        "d_count == d_mask": ((0, n), {"counts": P["mask"]}, ovl), "d_rgb inside d_sum2": ((0, n), {"rgb": P["sums2"] + 8}, ovl),
+        "d_mask inside d_sum": ((0, n), {"mask": P["sums"] + 4 * w * h}, ovl),
+        "d_sum2 overlaps d_sum": ((0, n), {"sums": big.data_ptr(), "sums2": big.data_ptr() + 12 * w * h - 4}, ovl),
+        "d_count == d_rgb, no mask": ((0, n), {"mask": None, "sums2": None, "counts": P["rgb"]}, ovl),
+    }
+    for what, ((kb, ke), over, msg) in cases.items():
+        assert call(dev._h, kb, ke, **over) != 0, what
+        assert msg in L.sq_last_error(), (what, L.sq_last_error())
+    assert call(dev._h, 0, n, shard=sqt.Shard(2, 3, 3)) != 0
+    assert b"bad shard" in L.sq_last_error()
+    # LDS-height limits: 200 frames fit the per-pixel kernel's 256 lanes but not the streaming form's 512 (refused after the
+    # workspace is planned); 400 fit no form
+    for height, variant in ((200, 2), (400, 1), (400, 2)):
+        ds = sqt.DeviceScene(TP.full_stack(bih, height, 0, TP.LEFT), 0)
+        try:
+            ds.set_option("variant", variant)
+            assert call(ds._h, 1, n) != 0
+            assert f"BIH height {height} needs".encode() in L.sq_last_error(), L.sq_last_error()
+            assert ds.last_plan()["launched"] == 0
+            torch.cuda.synchronize()
+        finally:
+            ds.close()
+    with pytest.raises(sqt.SquiglyError):
+        dev.render_rows_masked(cam, n, w, h, 0, n, None)
+    with pytest.raises(sqt.SquiglyError):
+        dev.render_rows_masked(cam, n, w, h, 0, n, B["sums"], mask=B["counts"])                           # wrong dtype
+    with pytest.raises(sqt.SquiglyError):
+        dev.render_rows_masked(cam, n, w, h, 0, n, B["sums"], counts=B["counts"][:4])
+    torch.cuda.synchronize()
+    for k, v in keep.items():
+        assert torch.equal(B[k], v), k
+
+
+# ---- 9. checkpoint / resume, render_adaptive, CLI ----------------------------------------------------------------------------
+def test_resume_from_a_host_checkpoint_in_a_new_scene(sqt, product_scene):
+    import torch
+    bih, cam, _ = product_scene
+    w, h, n, tol = 24, 20, 40, 0.5
+    ds = sqt.DeviceScene(bih, 0)
+    whole = sqt.Adaptive(ds, cam, n, w, h, tol)
+    while not whole.finished:
+        avg, rgb = whole.step()
+    torch.cuda.synchronize()
+    want = {"sums": whole.sums.cpu().numpy(), "sums2": whole.sums2.cpu().numpy(), "counts": whole.counts.cpu().numpy(),
+            "mask": whole.mask.cpu().numpy(), "avg": avg.cpu().numpy(), "rgb": rgb.cpu().numpy()}
+    assert len(np.unique(want["counts"])) >= 3
+    p = sqt.Adaptive(ds, cam, n, w, h, tol)
+    p.step()
+    p.step()
+    torch.cuda.synchronize()
+    saved = [t.cpu().numpy().copy() for t in (p.sums, p.sums2, p.counts, p.mask)]
+    saved_done, saved_live = p.done, p.live
+    assert saved_done == 16 and 0 < saved_live < w * h
+    del p, whole
+    ds.close()
+    ds = sqt.DeviceScene(bih, 0)
+    try:
+        for form in ("numpy", "cuda"):
+            ck = [a.copy() for a in saved] if form == "numpy" else [torch.from_numpy(a.copy()).cuda() for a in saved]
+            r = sqt.Adaptive(ds, cam, n, w, h, tol, sums=ck[0], sums2=ck[1], counts=ck[2], mask=ck[3], done=saved_done)
+            assert (r.done, r.live, r.finished) == (saved_done, saved_live, False)
+            if form == "cuda":
+                assert r.sums is ck[0] and r.mask is ck[3]               # matching CUDA tensors are adopted, not copied
+            while not r.finished:
+                avg, rgb = r.step()
+            torch.cuda.synchronize()
+            got = {"sums": r.sums, "sums2": r.sums2, "counts": r.counts, "mask": r.mask, "avg": avg, "rgb": rgb}
+            for k, v in want.items():
+                assert np.array_equal(got[k].cpu().numpy().view(np.uint8), v.view(np.uint8)), (form, k)
+        with pytest.raises(ValueError):
+            sqt.Adaptive(ds, cam, n, w, h, tol, sums=saved[0][:3], sums2=saved[1], counts=saved[2], mask=saved[3], done=saved_done)
+    finally:
+        ds.close()
+
+
+def test_render_adaptive_with_one_full_step_is_render_rgb8(sqt, product_scene):
+    bih, cam, _ = product_scene
+    seen = list(sqt.render_adaptive(bih, cam, 5, (20, 16), 0.5, first=5))
+    assert len(seen) == 1
+    done, live, spent, img, counts = seen[0]
+    assert done == 5 and spent == 5 * 20 * 16 and 0 <= live <= 20 * 16
+    assert img.shape == (20, 16, 3) and img.dtype == np.uint8 and counts.shape == (20, 16) and (counts == 5).all()
+    assert np.array_equal(img, sqt.render_rgb8(bih, cam, 5, (20, 16)))
+
+
+def test_cli_adaptive(sqt, tmp_path, monkeypatch, capsys):
+    from importlib import import_module
+    cli = import_module("squigly-trace_amd.cli")
+    monkeypatch.chdir(ROOT)                                          # the reference's default obj and camera paths are relative
+    plain, full, adap, cfile = (str(tmp_path / f) for f in ("plain.png", "full.png", "adaptive.png", "counts.npy"))
+    assert cli.main(["-s", "8", "-d", "64,64", "-p", plain]) == 0
+    assert "Adaptive" not in capsys.readouterr().out
+    assert cli.main(["-s", "8", "-d", "64,64", "--adaptive", "0.5", "--adaptive-first", "8", "-p", full]) == 0
+    lines = [ln for ln in capsys.readouterr().out.splitlines() if ln.startswith("Adaptive")]
+    assert len(lines) == 1 and lines[0].split()[:2] == ["Adaptive", "8/8"] and lines[0].split()[-2:] == ["spent", str(8 * 64 * 64)], lines
+    with open(plain, "rb") as f1, open(full, "rb") as f2:
+        assert f1.read() == f2.read()
+    assert cli.main(["-s", "32", "-d", "64,64", "--adaptive", "0.5", "--adaptive-first", "8", "--adaptive-step", "8", "-p", adap,
+                     "--counts", cfile]) == 0
+    lines = [ln.split() for ln in capsys.readouterr().out.splitlines() if ln.startswith("Adaptive")]
+    assert all(len(ln) == 6 and ln[2] == "live" and ln[4] == "spent" for ln in lines), lines
+    assert [ln[1] for ln in lines] == [f"{k}/32" for k in range(8, 8 * len(lines) + 1, 8)] and 1 <= len(lines) <= 4
+    live = [int(ln[3]) for ln in lines]
+    spent = [int(ln[5]) for ln in lines]
+    assert all(a >= b for a, b in zip(live, live[1:])) and live[0] <= 64 * 64
+    assert lines[-1][1] == "32/32" or live[-1] == 0
+    assert spent[0] == 8 * 64 * 64 and all(b - a == 8 * l for a, b, l in zip(spent, spent[1:], live))
+    counts = np.load(cfile)
+    assert counts.dtype == np.int32 and counts.shape == (64, 64)
+    assert set(np.unique(counts).tolist()) <= {8, 16, 24, 32} and int(counts.sum()) == spent[-1]
+    assert os.path.getsize(adap) > 0
