@@ -68,7 +68,9 @@ typedef struct {
  * rgbFloatToPixelRGB of each pixel (src/Lib.hs:93-104).  cast != 0 selects raycast (src/Lib.hs:141-151).
  * With one device the finished frame is copied straight into `out`; with several, each shard is staged and de-interleaved.  Either way
  * nothing is written to `out` unless every device's render succeeded.  SQ_ONESHOT_TIMING=1 prints the call's stages (scene
- * upload, buffers, render, copy back, free) on stderr. */
+ * upload, buffers, render, copy back, free) on stderr.
+ * Size: every device's shard is one sq_render_rows_device call and has that call's limits (below); a frame that is too large for the
+ * devices it is spread over is refused before a scene is uploaded ("device D (shard I of G): R x H pixels exceed ..."). */
 int sq_render_rgb8(const sq_scene* scene, const sq_camera* cam, int32_t samples, int32_t w, int32_t h,
                    int32_t cast, uint8_t* out);
 /* out_avg: w*h*3 floats = the pre-tonemap `avg` of src/Lib.hs:88 (for tolerance checks). */
@@ -94,7 +96,14 @@ int32_t sq_shard_global_row(int32_t local_row, sq_shard sh);
 
 /* d_avg (float, rows*h*3) and d_rgb (uint8, rows*h*3) are DEVICE pointers on the scene's device;
  * either may be NULL.  hip_stream is a hipStream_t (NULL = the null stream); the call only enqueues
- * work on it and returns (no synchronisation). */
+ * work on it and returns (no synchronisation).
+ * FRAME SIZE.  Pixel indices are 32-bit, so one call -- this one, the range, masked and views calls below -- takes at most
+ * 2^31 - 1 pixels (rows * h, times n_views), e.g. 46340 x 46340; buffer offsets are 64-bit, so the buffers of such a call may pass
+ * 4 GB.  That is the limit of the per-pixel kernel (option "variant" = 1, and every cast frame).  The wavefront form (the default)
+ * indexes its active pixels and its ray queue with 32-bit numbers that reach three times the pixel count, and takes at most 2^29
+ * pixels per call (536 870 912, e.g. 16384 x 32768), which is also the cap of option "slots".  A larger call is refused before the
+ * device is touched, every buffer left as it was: "R x H pixels exceed 2^31 - 1 pixels in one call", or "... exceed 2^29 pixels in
+ * one call of the wavefront form ...".  Larger images are rendered as several shards (sq_shard): the limit is per call. */
 int sq_render_rows_device(sq_device_scene* s, const sq_camera* cam, int32_t samples, int32_t w, int32_t h,
                           int32_t cast, sq_shard sh, float* d_avg, uint8_t* d_rgb, void* hip_stream);
 
@@ -154,7 +163,8 @@ int sq_render_rows_device_masked(sq_device_scene* s, const sq_camera* cam, int32
  * small emitter a sample is black or bright, so typically all black -- has L = 0 and counts as converged however many bright
  * samples were still to come.  The length of the first range is the caller's guard against that.  The mechanism above is exact
  * whatever mask it is given.
- * Refused: a NULL argument, n_pixels < 0, tol or eps negative or NaN.  The call only enqueues work on hip_stream. */
+ * Refused: a NULL argument, n_pixels < 0, tol or eps negative or NaN, and n_pixels > 2^32 - 256 (one thread per pixel in one launch;
+ * the kernel's own indices are 64-bit, so buffers past 2^31 elements are fine).  The call only enqueues work on hip_stream. */
 int sq_adaptive_update_device(sq_device_scene* s, int64_t n_pixels, const float* d_sum, const float* d_sum2,
                               const int32_t* d_count, float tol, float eps,
                               uint8_t* d_mask, int32_t* d_live, void* hip_stream);
@@ -168,7 +178,7 @@ int sq_adaptive_update_device(sq_device_scene* s, int64_t n_pixels, const float*
  *          what a single-view call writes for cams[i].  [k_begin, k_end) means what it means in sq_render_rows_device_range;
  *          d_sum may be NULL only when [k_begin, k_end) == [0, samples).  d_avg and d_rgb are optional.
  * Refused with an error code before anything is enqueued (every buffer left as it was): n_views < 1, cams == NULL,
- * n_views * rows * h > INT32_MAX, and every refusal of sq_render_rows_device_range (bad range, d_sum == d_avg, no output buffer,
+ * n_views * rows * h > INT32_MAX (2^29 in the wavefront form: FRAME SIZE above), and every refusal of sq_render_rows_device_range (bad range, d_sum == d_avg, no output buffer,
  * bad shard, the LDS-height limits).  n_views == 1 takes exactly the single-view path.
  * Like the other entry points the call only enqueues work on hip_stream.  The calls on one scene share its workspace and camera
  * table, so they must be ordered on one stream. */
@@ -187,14 +197,17 @@ int sq_render_views_device(sq_device_scene* s, const sq_camera* cams, int32_t n_
  * for frames; a query runs in chunks of at most `slots` rays); 1 = one lane per ray, which takes the taller trees of the per-pixel
  * kernel.  Every form gives the same bits.
  * Refused with an error code before anything is enqueued (every buffer left as it was): s == NULL, n < 0, n > 0 with d_org, d_dir
- * or d_tri NULL, any two of the given ranges overlapping, and the LDS-height limits of a frame of the same form.  n == 0 returns 0
+ * or d_tri NULL, any two of the given ranges overlapping, and the LDS-height limits of a frame of the same form.  Any n that memory
+ * holds is taken: ray indices and offsets are 64-bit, variant 1 runs launches of 2^30 rays and the default form chunks of at most
+ * `slots` <= 2^29 rays.  n == 0 returns 0
  * and enqueues nothing.  The call only enqueues work on hip_stream; it shares the scene's workspace, so the queries and frames of
  * one scene must be ordered on one stream. */
 int sq_intersect_rays_device(sq_device_scene* s, const float* d_org, const float* d_dir, int64_t n,
                              int32_t* d_tri, float* d_dist, float* d_point, void* hip_stream);
 /* The primary ray of every pixel of a shard (makeRay, src/Lib.hs:107-114), computed on the device exactly as the renderer traces it:
  * sq_intersect_rays_device of them gives the renderer's own primary hits.  d_org, d_dir: DEVICE float[rows][h][3], laid out like
- * d_avg, rows = sq_shard_rows(w, sh).  Refused: a NULL argument, w or h < 1, a bad shard, overlapping d_org and d_dir. */
+ * d_avg, rows = sq_shard_rows(w, sh).  Refused: a NULL argument, w or h < 1, a bad shard, overlapping d_org and d_dir.  No size limit
+ * but memory: pixel indices are 64-bit here, and a fixed grid strides over them. */
 int sq_camera_rays_device(sq_device_scene* s, const sq_camera* cam, int32_t w, int32_t h, sq_shard sh,
                           float* d_org, float* d_dir, void* hip_stream);
 
@@ -209,7 +222,8 @@ int  sq_get_stats(sq_device_scene* s, uint64_t* out, int32_t n, int32_t reset);
 /* Tunables; every setting produces identical bits.  Keys:
  *   "variant"            1 = one-lane-per-pixel kernel, 2 = wavefront pipeline (default)
  *   "slots"              sample slots of the frame workspace (default 512 Mi at 45 B each = 24 GB of the
- *                        288 GB; a frame with fewer samples allocates only what it needs)
+ *                        288 GB; a frame with fewer samples allocates only what it needs), 1 .. 2^29: slot numbers and the
+ *                        trace kernel's queue cursor are 32-bit
  *   "resident"           1 = keep the whole scene in LDS when it fits (default), 0 = always stream
  *   "lds_node_kb"        streaming form: KB of LDS for the top of the tree (default 32; the six-wave build takes what its third of the LDS leaves)
  *   "pool"               1 = pooled trace kernel (default): a wave tests the triangles of all its open leaves as a pool of

@@ -20,7 +20,8 @@ def release_cached_memory() -> None:
 
 def __getattr__(name):
     # torch is only needed for the resident-scene path
-    if name in ("DeviceScene", "Progressive", "Adaptive", "Hits", "rule_reference"):
+    if name in ("DeviceScene", "Progressive", "Adaptive", "Hits", "rule_reference", "frame_size_error", "MAX_CALL_PIXELS",
+                "MAX_WAVEFRONT_PIXELS"):
         from . import device
         return getattr(device, name)
     if name in ("dist",):

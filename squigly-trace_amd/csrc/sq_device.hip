@@ -2031,6 +2031,10 @@ int launch_frame(sq_device_scene* s, const Frame& F, hipStream_t stream, const s
     if (plan_trace<StackT, MV>(s, S, stack_cap, TP)) return 1;
     const bool resident = TP.resident, pool = TP.pool;
     P.primary_form = (s->opt_primary_pooled && pool) ? SQ_PRIMARY_POOLED : (resident && s->opt_primary_resident) ? SQ_PRIMARY_RESIDENT : SQ_PRIMARY_PER_LANE;
+    // the per-lane primary pass is one launch with a thread per tile lane, padding included (a narrow frame's edge tiles are mostly
+    // padding: up to 64 lanes per pixel at h = 1), and a launch has at most 2^32 - 1 threads; the other two passes stride over a fixed grid
+    if (P.primary_form == SQ_PRIMARY_PER_LANE && (primary_padded(F) * F.n_views + kBlock - 1) / kBlock * kBlock > 0xffffffffLL)
+        return sq_set_error("image too large for one launch of the primary rays (%lld tile lanes; at most 2^32 - 1)", primary_padded(F) * F.n_views);
     P.launched = 1;                                                    // planned; what follows fails only on HIP errors
     // nothing is enqueued before this point, so a refusal above leaves every buffer as it was
     if (stage_cams(s, F, cams, stream)) return 1;                       // multi-view: before every kernel that reads the table (e_setup below)
@@ -2226,6 +2230,29 @@ int launch_frame(sq_device_scene* s, const Frame& F, hipStream_t stream, const s
 }  // namespace
 
 namespace {
+// The largest frames a call takes.  Pixel indices are 32-bit wherever they are stored (Work::px_pixel, Frame::view_pixels)
+// or divided (pixel_coords), so no call takes more than INT32_MAX pixels.  The wavefront form also indexes its active-pixel list and
+// its ray queue with 32-bit values that reach 3 x pixels (px_sum[3 * a]), pixels + one grid stride (the `a` loops) and twice the slots
+// (the trace kernel's cursor, with the mirror rays in front): they hold while pixels <= 2^29, which is also the cap of option "slots".
+constexpr int64_t kMaxCallPixels = INT32_MAX, kMaxWavefrontPixels = (int64_t)1 << 29;
+// Sets the refusal of a call of n_views x rows x h pixels that is too large for its form (wavefront: not the per-pixel kernel) and
+// returns non-zero; 0 when the size is fine.  Everything in 64 bits; touches no device.
+int refuse_frame_size(int64_t n_views, int64_t rows, int64_t h, bool wavefront) {
+    if (rows <= 0 || h <= 0 || n_views <= 0) return 0;
+    const int64_t view_rows = n_views * rows;                           // each factor is below 2^31: below 2^62
+    const bool huge = view_rows > kMaxCallPixels || view_rows * h > kMaxCallPixels;
+    const int64_t pixels = huge ? 0 : view_rows * h;
+    if (n_views > 1) {
+        if (huge) return sq_set_error("%lld views of %lld x %lld pixels exceed 2^31 - 1 pixels in one call", (long long)n_views, (long long)rows, (long long)h);
+        if (wavefront && pixels > kMaxWavefrontPixels)
+            return sq_set_error("%lld views of %lld x %lld pixels exceed 2^29 pixels in one call of the wavefront form (variant 1 takes 2^31 - 1)", (long long)n_views, (long long)rows, (long long)h);
+        return 0;
+    }
+    if (huge) return sq_set_error("%lld x %lld pixels exceed 2^31 - 1 pixels in one call", (long long)rows, (long long)h);
+    if (wavefront && pixels > kMaxWavefrontPixels)
+        return sq_set_error("%lld x %lld pixels exceed 2^29 pixels in one call of the wavefront form (variant 1 and cast frames take 2^31 - 1)", (long long)rows, (long long)h);
+    return 0;
+}
 // Every render entry point: the samples [k_begin, k_end) of the `samples`-sample frame of n_views cameras (view-major buffers).  d_sum =
 // nullptr (sq_render_rows_device) keeps the fold in the workspace; the caller has checked everything that is specific to its own entry
 // point.  One camera takes the single-view kernels; more take their multi-view instantiations and the scene's camera table.
@@ -2238,6 +2265,7 @@ int render_rows(sq_device_scene* s, const sq_camera* cam, int32_t n_views, int32
     if (rows < 0) return sq_set_error("bad shard {row_block=%d, shard=%d, n_shards=%d}", sh.row_block, sh.shard, sh.n_shards);
     if (rows == 0) return 0;                    // an empty shard (more shards than row blocks) has nothing to render
     if (!d_avg && !d_rgb && !d_sum) return sq_set_error("no output buffer");
+    if (refuse_frame_size(n_views, rows, h, s->opt_variant != 1 && !cast)) return 1;   // before any 32-bit product of rows and h, and before the device is touched
     if (d_mask || d_sum2 || d_count) {   // a masked call: no two of its buffers may overlap (a live pixel's stores would be another pixel's mask, count or fold)
         const size_t px = (size_t)rows * (size_t)h;
         const struct { const char* name; const void* p; size_t bytes; } b[6] = {
@@ -2330,8 +2358,9 @@ extern "C" int sq_adaptive_update_device(sq_device_scene* s, int64_t n_pixels, c
     if (n_pixels < 0) return sq_set_error("n_pixels must not be negative (got %lld)", (long long)n_pixels);
     if (!(tol >= 0.0f) || !(eps >= 0.0f)) return sq_set_error("tol and eps must be numbers >= 0 (got %g, %g)", (double)tol, (double)eps);
     if (!s || !d_sum || !d_sum2 || !d_count || !d_mask || !d_live) return sq_set_error("null argument");
+    // one thread per pixel in one launch of whole workgroups, and a launch has at most 2^32 - 1 threads; the kernel itself is 64-bit throughout
+    if (n_pixels > 0xffffffffLL / kBlock * kBlock) return sq_set_error("too many pixels for one launch (%lld; at most 2^32 - 256)", (long long)n_pixels);
     const long long blocks = ((long long)n_pixels + kBlock - 1) / kBlock;
-    if (blocks > 0x7fffffffLL) return sq_set_error("too many pixels for one launch");
     SQ_HIP(hipSetDevice(s->device));
     hipStream_t stream = (hipStream_t)hip_stream;
     SQ_HIP(hipMemsetAsync(d_live, 0, sizeof(int32_t), stream));
@@ -2353,8 +2382,7 @@ extern "C" int sq_render_views_device(sq_device_scene* s, const sq_camera* cams,
         return sq_set_error("d_sum is required for a part [%d, %d) of a %d-sample frame: it carries the per-pixel fold", k_begin, k_end, samples);
     if (d_sum && (void*)d_sum == (void*)d_avg) return sq_set_error("d_sum and d_avg must be different buffers");
     const int32_t rows = sq_shard_rows(w, sh);
-    if (rows > 0 && h > 0 && (int64_t)n_views * rows * h > INT32_MAX)   // pixel indices (px_pixel) are 32-bit
-        return sq_set_error("%d views of %d x %d pixels exceed 2^31 - 1 pixels in one call", n_views, rows, h);
+    if (refuse_frame_size(n_views, rows, h, false)) return 1;          // pixel indices (px_pixel) are 32-bit; render_rows adds the wavefront form's limit
     return render_rows(s, cams, n_views, samples, w, h, cast, sh, k_begin, k_end, d_sum, d_avg, d_rgb, hip_stream);
 }
 
@@ -2624,6 +2652,9 @@ int render_oneshot(const sq_scene* scene, const sq_camera* cam, int32_t samples,
     const int G = (int)devices.size();
     std::vector<OneshotPart> parts((size_t)G);
     for (int g = 0; g < G; ++g) { parts[(size_t)g].device = devices[(size_t)g]; parts[(size_t)g].shard = sq_shard{ G == 1 ? w : kOneshotRowBlock, g, G }; }
+    for (const OneshotPart& P : parts)                             // a shard too large for one call: refused before a scene is uploaded or a buffer allocated
+        if (refuse_frame_size(1, sq_shard_rows(w, P.shard), h, !cast))
+            return sq_set_error("device %d (shard %d of %d): %s", P.device, P.shard.shard, G, std::string(sq_last_error()).c_str());
     auto run = [&](OneshotPart& P) {
         P.rc = oneshot_part(scene, cam, samples, w, h, cast, out_avg != nullptr, out_rgb != nullptr, P);
         if (P.rc) P.error = sq_last_error();                      // the message is thread-local: carry it out

@@ -14,6 +14,35 @@ Hits = collections.namedtuple("Hits", ["tri", "dist", "point"])
 Hits.__doc__ = """Results of DeviceScene.intersect: Maybe Intersection (src/Geometry.hs:71-75) per ray; tri = -1 is Nothing."""
 
 
+# The largest frame one call takes (include/squigly_hip.h, DESIGN.md 4.13): pixel indices are 32-bit, and the wavefront form's
+# active-pixel list and ray queue hold while a call has at most 2^29 pixels.
+MAX_CALL_PIXELS = 2 ** 31 - 1
+MAX_WAVEFRONT_PIXELS = 2 ** 29
+
+
+def frame_size_error(rows, h, views=1, wavefront=False):
+    """The library's refusal of a call of views x rows x h pixels, word for word, or None when the size is accepted.
+    wavefront: the call takes the wavefront form (option "variant" = 2, not a cast frame)."""
+    rows, h, views = int(rows), int(h), int(views)
+    if rows <= 0 or h <= 0 or views <= 0:
+        return None
+    pixels = views * rows * h
+    what = f"{views} views of {rows} x {h} pixels" if views > 1 else f"{rows} x {h} pixels"
+    if pixels > MAX_CALL_PIXELS:
+        return f"{what} exceed 2^31 - 1 pixels in one call"
+    if wavefront and pixels > MAX_WAVEFRONT_PIXELS:
+        other = "variant 1" if views > 1 else "variant 1 and cast frames"
+        return f"{what} exceed 2^29 pixels in one call of the wavefront form ({other} take{'s' if views > 1 else ''} 2^31 - 1)"
+    return None
+
+
+def _check_frame_size(dscene, rows, h, cast, views=1):
+    """SquiglyError, before anything is allocated, for a frame the library would refuse for its size."""
+    msg = frame_size_error(rows, h, views, getattr(dscene, "_variant", 2) != 1 and not cast)
+    if msg:
+        raise N.SquiglyError(msg)
+
+
 def _ray_shape(origins, directions):
     """The common [..., 3] shape of a query's origins and directions; SquiglyError before any device work otherwise."""
     shapes = []
@@ -39,8 +68,10 @@ class DeviceScene:
 
     def set_option(self, key, value):
         N.check(N.lib().sq_set_option(self._h, key.encode(), int(value)))
+        if key == "variant":
+            self._variant = int(value)       # which size limit a frame has (_check_frame_size)
 
-    def _outputs(self, w, h, shard, want_avg, want_rgb, stream, out_avg, out_rgb, views=None):
+    def _outputs(self, w, h, shard, want_avg, want_rgb, stream, out_avg, out_rgb, views=None, cast=False, frame=True):
         """(sq_shard, rows, out_avg, out_rgb, stream) of a render_rows* call: the shard's row count, the output tensors
         (allocated unless given or not wanted) and the stream (default: the device's current one).  views: the tensors get a
         leading dimension of that many views (render_views)."""
@@ -49,6 +80,8 @@ class DeviceScene:
         rows = N.lib().sq_shard_rows(w, sh)
         if rows < 0:
             raise N.SquiglyError(f"bad shard {shard}")
+        if frame:                              # frame: a render call (camera_rays has no limit but memory)
+            _check_frame_size(self, rows, h, cast, 1 if views is None else views)
         dev = torch.device("cuda", self.device)
         shape = (rows, h, 3) if views is None else (views, rows, h, 3)
         if want_avg and out_avg is None:
@@ -64,7 +97,7 @@ class DeviceScene:
 
         shard = (row_block, shard_index, n_shards); row_block None = all rows in one block.
         """
-        sh, _, out_avg, out_rgb, st = self._outputs(w, h, shard, want_avg, want_rgb, stream, out_avg, out_rgb)
+        sh, _, out_avg, out_rgb, st = self._outputs(w, h, shard, want_avg, want_rgb, stream, out_avg, out_rgb, cast=cast)
         N.check(N.lib().sq_render_rows_device(
             self._h, C.byref(cam), samples, w, h, int(bool(cast)), sh,
             out_avg.data_ptr() if out_avg is not None else None,
@@ -80,7 +113,7 @@ class DeviceScene:
         sums: float32 CUDA tensor [rows, h, 3] on this device, the per-pixel fold over [0, k_begin) on entry (ignored when
         k_begin == 0) and over [0, k_end) once the stream gets there.
         """
-        sh, rows, out_avg, out_rgb, st = self._outputs(w, h, shard, want_avg, want_rgb, stream, out_avg, out_rgb)
+        sh, rows, out_avg, out_rgb, st = self._outputs(w, h, shard, want_avg, want_rgb, stream, out_avg, out_rgb, cast=cast)
         if sums is None:
             raise N.SquiglyError("render_rows_range needs a sums tensor")
         if (tuple(sums.shape) != (rows, h, 3) or sums.dtype != torch.float32 or not sums.is_contiguous()
@@ -113,7 +146,7 @@ class DeviceScene:
         With mask, sums2 and counts all None this is render_rows_range.
         """
         given_avg, given_rgb = out_avg is not None, out_rgb is not None
-        sh, rows, out_avg, out_rgb, st = self._outputs(w, h, shard, want_avg, want_rgb, stream, out_avg, out_rgb)
+        sh, rows, out_avg, out_rgb, st = self._outputs(w, h, shard, want_avg, want_rgb, stream, out_avg, out_rgb, cast=cast)
         if sums is None:
             raise N.SquiglyError("render_rows_masked needs a sums tensor")
         self._frame_tensor("sums", sums, (rows, h, 3), torch.float32)
@@ -168,7 +201,7 @@ class DeviceScene:
             raise ValueError("render_views needs at least one camera")
         n = len(cams)
         k_end = int(samples) if k_end is None else int(k_end)
-        sh, rows, out_avg, out_rgb, st = self._outputs(w, h, shard, want_avg, want_rgb, stream, out_avg, out_rgb, views=n)
+        sh, rows, out_avg, out_rgb, st = self._outputs(w, h, shard, want_avg, want_rgb, stream, out_avg, out_rgb, views=n, cast=cast)
         if sums is not None and (tuple(sums.shape) != (n, rows, h, 3) or sums.dtype != torch.float32 or not sums.is_contiguous()
                                  or sums.device != torch.device("cuda", self.device)):
             raise N.SquiglyError(f"sums must be a contiguous float32 tensor of shape {(n, rows, h, 3)} on cuda:{self.device}, "
@@ -217,7 +250,7 @@ class DeviceScene:
         """The primary ray of every pixel of the shard, as the renderer traces it (sq_camera_rays_device): (origins,
         directions) float32 CUDA tensors [rows, h, 3].  ds.intersect(*ds.camera_rays(cam, w, h)) is the frame's depth and
         triangle-id buffer."""
-        sh, rows, _, _, st = self._outputs(w, h, shard, False, False, stream, None, None)
+        sh, rows, _, _, st = self._outputs(w, h, shard, False, False, stream, None, None, frame=False)
         dev = torch.device("cuda", self.device)
         o = torch.empty((rows, h, 3), dtype=torch.float32, device=dev)
         d = torch.empty((rows, h, 3), dtype=torch.float32, device=dev)
@@ -280,6 +313,7 @@ class Progressive:
         rows = N.lib().sq_shard_rows(w, N.Shard(int(w if rb is None else rb), int(si), int(ns)))
         if rows < 0:
             raise N.SquiglyError(f"bad shard {shard}")
+        _check_frame_size(dscene, rows, h, cast)
         dev = torch.device("cuda", dscene.device)
         if sums is None:
             if done:
@@ -371,6 +405,7 @@ class Adaptive:
         rows = N.lib().sq_shard_rows(w, N.Shard(int(w if rb is None else rb), int(si), int(ns)))
         if rows < 0:
             raise N.SquiglyError(f"bad shard {shard}")
+        _check_frame_size(dscene, rows, h, cast)
         dev = torch.device("cuda", dscene.device)
 
         def adopt(name, t, shape, dtype, fill):   # a matching CUDA tensor as it is; a host copy is copied to the device
