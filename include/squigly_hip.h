@@ -211,6 +211,43 @@ int sq_intersect_rays_device(sq_device_scene* s, const float* d_org, const float
 int sq_camera_rays_device(sq_device_scene* s, const sq_camera* cam, int32_t w, int32_t h, sq_shard sh,
                           float* d_org, float* d_dir, void* hip_stream);
 
+/* Radiance queries on a resident scene: Lib.raytrace (src/Lib.hs:127-137) of caller-given rays with caller-given seed bases.  Per ray
+ * i of n, d_sum receives the left fold, in sample order, of
+ *      raytrace (mkTFGen (seed_i + k)) scene (Ray org_i dir_i) 0          for k in [k_begin, k_end)
+ * started from +0 (k_begin == 0) or from what d_sum holds (k_begin > 0): src/Lib.hs:86-88 with the caller's ray and seed base.
+ *  d_org, d_dir : DEVICE float[n][3] on the scene's device, as in sq_intersect_rays_device.
+ *  d_seed : DEVICE int64[n], required.  The generator of sample k of ray i is mkTFGen (seed_i + k), the sum taken in two's-complement
+ *          64 bits.  With seed_i = samples * (x + y * w) and the ray of sq_camera_rays_device this is sample k of pixel (y, x) of the
+ *          `samples`-sample frame.
+ *  d_sum  : DEVICE float[n][3], required, in/out exactly like d_sum of sq_render_rows_device_range.
+ *  d_avg  : optional, float[n][3]; receives (1 / (float)k_end) *^ sum.
+ *  d_rgb  : optional, uint8[n][3]; its tonemap rgbFloatToPixelRGB (src/Lib.hs:93-104).
+ * A ray that hits nothing gets +0 sums, avg 0, rgb 0.  With k_begin = 0, k_end = 1 d_sum is 0 + raytrace gen scene ray 0: the plain
+ * Lib.raytrace.  Consecutive ranges [0, k1) [k1, k2) ... on the same rays give bit for bit the sum of one call [0, kn).  Every ray is
+ * independent of the batch it travels in: permuting the batch permutes the results, and a batch of one equals its entry.
+ * Any n that memory holds is taken: the call runs in chunks of rays, each chunk a frame of its own of one row (so within FRAME SIZE:
+ * at most `slots` <= 2^29 rays in the wavefront form, 2^30 in variant 1), sample batches inside a chunk as in a frame.  n == 0
+ * returns 0 and enqueues nothing.
+ * Forms: option "variant" 2 (default) runs the wavefront pipeline -- a primary pass over the caller's rays (64 consecutive rays per
+ * wave), then exactly a frame's kernels, the mirror rays once per ray; 1 = one lane per ray in one kernel (the form for the taller
+ * trees).  Every option that leaves a frame's bits alone leaves these alone (pool, resident, trace_blocks_per_cu, cull,
+ * primary_resident, primary_pooled, overlap, slots, pixel_major, guided, profile, timing), and sq_last_plan reports the call like a
+ * frame's (the plan of its last chunk; every chunk plans alike).
+ * Refused with an error code before anything is enqueued (every buffer left as it was): s == NULL; n < 0; n > 0 with d_org, d_dir,
+ * d_seed or d_sum NULL; k_begin < 0 or k_end <= k_begin; any two of the six ranges overlapping; and the LDS-height limits of a frame
+ * of the same form, with the same message.  The call only enqueues work on hip_stream; it shares the scene's workspace, so the
+ * queries and frames of one scene must be ordered on one stream. */
+int sq_raytrace_rays_device(sq_device_scene* s, const float* d_org, const float* d_dir, const int64_t* d_seed, int64_t n,
+                            int32_t k_begin, int32_t k_end,
+                            float* d_sum, float* d_avg, uint8_t* d_rgb, void* hip_stream);
+/* Lib.raycast (src/Lib.hs:141-151, the hard-coded light at (0, 3, -1) included) of each of n rays: d_rad (DEVICE float[n][3],
+ * required) receives raycast scene (Ray org_i dir_i), (+0, +0, +0) for a miss or a shadowed point.  No random input and no fold.
+ * One kernel, one lane per ray, in every "variant" (as cast frames); launches of at most 2^30 rays.  Refused like
+ * sq_raytrace_rays_device, minus seeds and ranges: s == NULL, n < 0, n > 0 with d_org, d_dir or d_rad NULL, overlapping ranges,
+ * the LDS-height limit of the per-pixel kernel. */
+int sq_raycast_rays_device(sq_device_scene* s, const float* d_org, const float* d_dir, int64_t n,
+                           float* d_rad, void* hip_stream);
+
 /* Timing of the dominant kernel measured with hipEvents on the stream it was launched on:
  * average duration in ms over the launches since the last reset, and the launch count. */
 int  sq_kernel_timing(sq_device_scene* s, double* avg_ms, int64_t* launches, const char** kernel_name);

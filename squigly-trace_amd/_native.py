@@ -92,6 +92,8 @@ def lib():
     L.sq_render_views_device.argtypes = [vp, C.POINTER(Camera), i32, i32, i32, i32, i32, Shard, i32, i32, vp, vp, vp, vp]
     L.sq_intersect_rays_device.argtypes = [vp, vp, vp, C.c_int64, vp, vp, vp, vp]
     L.sq_camera_rays_device.argtypes = [vp, C.POINTER(Camera), i32, i32, Shard, vp, vp, vp]
+    L.sq_raytrace_rays_device.argtypes = [vp, vp, vp, vp, C.c_int64, i32, i32, vp, vp, vp, vp]
+    L.sq_raycast_rays_device.argtypes = [vp, vp, vp, C.c_int64, vp, vp]
     L.sq_kernel_timing.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_char_p)]
     L.sq_kernel_timing_reset.argtypes = [vp]
     L.sq_kernel_timing_reset.restype = None
@@ -172,7 +174,7 @@ def check(rc):
 EXPORTED_SYMBOLS = [
     # include/squigly_hip.h
     "sq_render_rgb8", "sq_render_f32", "sq_scene_upload", "sq_scene_free", "sq_shard_rows",
-    "sq_shard_global_row", "sq_render_rows_device", "sq_render_rows_device_range", "sq_render_rows_device_masked", "sq_adaptive_update_device", "sq_render_views_device", "sq_intersect_rays_device", "sq_camera_rays_device", "sq_kernel_timing", "sq_kernel_timing_reset",
+    "sq_shard_global_row", "sq_render_rows_device", "sq_render_rows_device_range", "sq_render_rows_device_masked", "sq_adaptive_update_device", "sq_render_views_device", "sq_intersect_rays_device", "sq_camera_rays_device", "sq_raytrace_rays_device", "sq_raycast_rays_device", "sq_kernel_timing", "sq_kernel_timing_reset",
     "sq_set_option", "sq_get_stats", "sq_last_plan", "sq_debug_eval", "sq_device_count", "sq_abi_version", "sq_build_id", "sq_last_error",
     # include/squigly_host.h
     "sq_mesh_from_obj", "sq_mesh_from_text", "sq_mesh_from_arrays", "sq_mesh_num_tris",

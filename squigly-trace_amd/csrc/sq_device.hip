@@ -16,6 +16,9 @@
 // traced again, and folded into a per-sample radiance; radiances are summed per pixel in sample order.
 // Every value is computed by the same fp32 expression tree as the reference.
 // The one-lane-per-pixel kernel sq_render_pixels serves raycast mode and is a cross-check variant.
+// Radiance queries (sq_raytrace_rays_device, sq_raycast_rays_device: Lib.raytrace / Lib.raycast of caller-given rays, src/Lib.hs:127-151)
+// run the same pipeline from a third ray source: the sq_*_rays kernels read origin, direction and seed base from the caller's arrays
+// where the frames' kernels read the camera.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -112,6 +115,18 @@ struct Frame {
     // `count` = its per-pixel sample counts (nullptr = none).  pixel_live() says which pixels such a call renders.
     const uint8_t* mask; float* sum2; int32_t* count;
 };
+// Radiance queries (sq_raytrace_rays_device / sq_raycast_rays_device, the kernels' kSrcRays instantiations): a frame plus the caller's
+// rays and seed bases.  A chunk of m rays is a frame of one row and m columns (local_rows = 1, h = m, tile_rows = 1), so "pixel" i is
+// ray i of the chunk: origin ray_org[3 i ..], direction ray_dir[3 i ..], and the generator of its sample k is mkTFGen (ray_seed[i] + k)
+// (nullptr in a raycast query, which draws nothing).  A type of its own, and the argument of the query kernels only: three more
+// pointers in Frame, which every kernel takes by value, moved the SGPR counts of five of the frames' kernels.
+struct RayFrame : Frame {
+    const float* ray_org; const float* ray_dir; const long long* ray_seed;
+};
+// Where a kernel's primary rays come from: the frame's camera (makeRay, src/Lib.hs:107-114), the camera table of a multi-view frame,
+// or the caller's arrays.  The kernels that exist for frames keep their bool MV (false = kSrcCamera, true = kSrcViews: a bool template
+// argument converts to these very values); the query kernels (sq_*_rays) instantiate the same bodies with kSrcRays.
+constexpr int kSrcCamera = 0, kSrcViews = 1, kSrcRays = 2;
 constexpr int kCamWords = 12;     // a view's entry in the camera table: pos[3], rot[9]
 struct ViewCam { f3 pos; float rot[9]; };
 // The camera of view v.  UNIFORM: v is the same in every lane of the wave (a primary-ray tile), so the 48 bytes come through scalar loads.
@@ -175,6 +190,8 @@ __device__ __forceinline__ long long primary_tile_views(const Frame& F, long lon
     return local >= 0 ? (long long)view * F.view_pixels + local : -1;
 }
 
+__device__ __forceinline__ f3 load3(const float* p, long long i) { return sq::mk(p[3 * i], p[3 * i + 1], p[3 * i + 2]); }
+
 // Where a pixel's fold starts: +0 on a fresh frame, else what the caller's earlier range call left in F.sum (src/Lib.hs:88 is a left
 // fold, so resuming it from its exact fp32 partial sum gives the bits of one uninterrupted fold).
 __device__ __forceinline__ f3 fold_start(const Frame& F, long long pix) {
@@ -219,13 +236,19 @@ __device__ __forceinline__ void store_live_miss(const Frame& F, long long pix) {
 // MV: a multi-view frame (pixels are enumerated linearly, so the lanes of a wave may belong to two views: per-lane camera reads)
 // AD: a masked call (single-view): dead pixels leave before the first ray -- nothing wave-wide follows, every lane walks alone --
 // and live ones also fold r * r and store their count.
-template <typename StackT, bool MV, bool AD = false>
-__global__ void __launch_bounds__(kBlock) sq_render_pixels(const SceneView S, const Frame F) {
+// SRC = kSrcRays (sq_render_pixels_rays): lane i takes the caller's ray i and seed base; its cast branch is raycast itself, not a fold.
+template <typename StackT, int SRC, bool AD, typename FrameT>
+__device__ __forceinline__ void render_pixels_body(const SceneView& S, const FrameT& F) {
+    constexpr bool MV = SRC == kSrcViews;
     extern __shared__ float4 lds_raw[];
     SQ_LDS StackT* stk = to_lds<StackT>(lds_raw) + threadIdx.x;
     const long long pix = (long long)blockIdx.x * kBlock + threadIdx.x;
     int y, x; f3 o0, d0;
-    if constexpr (MV) {
+    if constexpr (SRC == kSrcRays) {
+        if (pix >= (long long)F.h) return;
+        y = 0; x = 0;
+        o0 = load3(F.ray_org, pix); d0 = load3(F.ray_dir, pix);
+    } else if constexpr (MV) {
         if (pix >= (long long)F.n_views * F.view_pixels) return;
         const ViewCam c = view_cam<false>(F, view_coords(F, (int)pix, y, x));
         o0 = c.pos; d0 = primary_dir(c.rot, F.w, F.h, y, x);
@@ -252,10 +275,13 @@ __global__ void __launch_bounds__(kBlock) sq_render_pixels(const SceneView S, co
             const Hit sh = trace_one(S, N, p0, light - p0, stk, kBlock);
             f3 c = sq::mk(0, 0, 0);
             if (!(sh.tri >= 0 && !(hit_dist(p0, light - p0, sh.t) > dl))) c = sq::scale(2 / dl, s0.surf);
-            for (int k = F.k_begin; k < F.k_end; ++k) sum = sum + c;
+            if constexpr (SRC == kSrcRays) sum = c;                       // raycast scene ray: no samples, no fold
+            else for (int k = F.k_begin; k < F.k_end; ++k) sum = sum + c;
             if constexpr (AD) { if (F.sum2) for (int k = F.k_begin; k < F.k_end; ++k) sum2 = sum2 + c * c; }
         } else {
-            const long long rix = (long long)n * ((long long)x + (long long)y * (long long)F.w);   // src/Lib.hs:85
+            long long rix;
+            if constexpr (SRC == kSrcRays) rix = F.ray_seed[pix];       // the caller's seed base
+            else rix = (long long)n * ((long long)x + (long long)y * (long long)F.w);   // src/Lib.hs:85
 #pragma unroll 1
             for (int k = F.k_begin; k < F.k_end; ++k) {                 // raytrace gen scene ray 0, src/Lib.hs:127-137
                 uint32_t n0, n1, n2;
@@ -287,6 +313,10 @@ __global__ void __launch_bounds__(kBlock) sq_render_pixels(const SceneView S, co
     if (F.out_avg) { float* o = F.out_avg + pix * 3; o[0] = avg.x; o[1] = avg.y; o[2] = avg.z; }
     if (F.out_rgb) tonemap(avg, F.out_rgb + pix * 3);
 }
+template <typename StackT, bool MV, bool AD = false>
+__global__ void __launch_bounds__(kBlock) sq_render_pixels(const SceneView S, const Frame F) { render_pixels_body<StackT, MV, AD>(S, F); }
+template <typename StackT>
+__global__ void __launch_bounds__(kBlock) sq_render_pixels_rays(const SceneView S, const RayFrame F) { render_pixels_body<StackT, kSrcRays, false>(S, F); }
 
 // ----------------------------------------------------------------------------------------------
 // Variant 2 (default): wavefront pipeline
@@ -368,14 +398,17 @@ __device__ __forceinline__ void store_miss(const Frame& F, long long pix) {
 
 // Primary rays: trace once per pixel, compact the pixels that hit.
 // AD (here and in the other primary passes): a masked call; a dead pixel's lane is treated like the padding of an edge tile.
-template <typename StackT, bool MV, bool AD = false>
-__global__ void __launch_bounds__(kBlock) sq_primary(const SceneView S, const Frame F, const Work W) {
+// kSrcRays: no image to tile -- the caller's rays in index order, 64 consecutive rays per wave.
+template <typename StackT, int SRC, bool AD, typename FrameT>
+__device__ __forceinline__ void primary_body(const SceneView& S, const FrameT& F, const Work& W) {
+    constexpr bool MV = SRC == kSrcViews;
     extern __shared__ float4 lds_raw[];
     SQ_LDS StackT* stk = to_lds<StackT>(lds_raw) + threadIdx.x;
     const long long q = (long long)blockIdx.x * kBlock + threadIdx.x;
     int view = 0;
     long long pix;
-    if constexpr (MV) pix = q < primary_padded(F) * F.n_views ? primary_tile_views(F, q, view) : -1;
+    if constexpr (SRC == kSrcRays) pix = q < (long long)F.h ? q : -1;
+    else if constexpr (MV) pix = q < primary_padded(F) * F.n_views ? primary_tile_views(F, q, view) : -1;
     else pix = q < primary_padded(F) ? primary_tile(F, q) : -1;
     bool in = pix >= 0;
     if constexpr (AD) in = in && pixel_live(F, pix);
@@ -383,7 +416,9 @@ __global__ void __launch_bounds__(kBlock) sq_primary(const SceneView S, const Fr
     if (in) {
         int y, x;
         const GlobalNodes N{ S.branches, S.cull_child, S.cull_child != nullptr };
-        if constexpr (MV) {
+        if constexpr (SRC == kSrcRays) {
+            h0 = trace_one(S, N, load3(F.ray_org, pix), load3(F.ray_dir, pix), stk, kBlock);
+        } else if constexpr (MV) {
             pixel_coords(F, pix - (long long)view * F.view_pixels, y, x);
             const ViewCam c = view_cam<true>(F, view);
             h0 = trace_one(S, N, c.pos, primary_dir(c.rot, F.w, F.h, y, x), stk, kBlock);
@@ -396,13 +431,25 @@ __global__ void __launch_bounds__(kBlock) sq_primary(const SceneView S, const Fr
     if (a >= 0) store_active<AD>(F, W, a, pix, h0.t, h0.tri);
     else if (in) store_miss<AD>(F, pix);
 }
+template <typename StackT, bool MV, bool AD = false>
+__global__ void __launch_bounds__(kBlock) sq_primary(const SceneView S, const Frame F, const Work W) { primary_body<StackT, MV, AD>(S, F, W); }
+template <typename StackT>
+__global__ void __launch_bounds__(kBlock) sq_primary_rays(const SceneView S, const RayFrame F, const Work W) { primary_body<StackT, kSrcRays, false>(S, F, W); }
 
 struct Pixel0 { f3 p0, d0; Surface s0; int y, x; };
-// MV: the pixel's view comes from its index, and its camera from the table (once per active pixel, not per sample)
-template <bool MV>
-__device__ __forceinline__ Pixel0 load_pixel0(const SceneView& S, const Frame& F, const Work& W, int a) {
+// Everything the kernels downstream of the primary pass know about active pixel a, and the one place where they learn it.
+// kSrcViews: the pixel's view comes from its index, and its camera from the table (once per active pixel, not per sample).
+// kSrcRays: the "pixel" is the caller's ray px_pixel[a]; y and x stay unset (its seed base comes from seed_base, not from coordinates).
+template <int SRC, typename FrameT>
+__device__ __forceinline__ Pixel0 load_pixel0(const SceneView& S, const FrameT& F, const Work& W, int a) {
+    constexpr bool MV = SRC == kSrcViews;
     Pixel0 P;
-    if constexpr (MV) {
+    if constexpr (SRC == kSrcRays) {
+        const long long i = W.px_pixel[a];
+        P.y = 0; P.x = 0;
+        P.d0 = load3(F.ray_dir, i);
+        P.p0 = load3(F.ray_org, i) + sq::scale(W.px_t0[a], P.d0);           // intersectPoint, src/Geometry.hs:134
+    } else if constexpr (MV) {
         const ViewCam c = view_cam<false>(F, view_coords(F, (int)W.px_pixel[a], P.y, P.x));
         P.d0 = primary_dir(c.rot, F.w, F.h, P.y, P.x);
         P.p0 = c.pos + sq::scale(W.px_t0[a], P.d0);
@@ -413,6 +460,13 @@ __device__ __forceinline__ Pixel0 load_pixel0(const SceneView& S, const Frame& F
     }
     P.s0 = surface_of(S, W.px_tri0[a]);
     return P;
+}
+// The seed base of active pixel a: the generator of its sample k is mkTFGen (seed_base + k).  A frame's rule is src/Lib.hs:85;
+// a query's is the caller's array.
+template <int SRC, typename FrameT>
+__device__ __forceinline__ long long seed_base(const FrameT& F, const Work& W, int a, const Pixel0& P) {
+    if constexpr (SRC == kSrcRays) return F.ray_seed[W.px_pixel[a]];
+    else return (long long)F.samples * ((long long)P.x + (long long)P.y * (long long)F.w);   // src/Lib.hs:85
 }
 // surfColor == 0 (an emitter such as data/scene.sq:13-15) makes `surfColor * raytrace ...` exactly +0
 // whenever the nested radiance is finite and >= +0, so the nested rays need not be traced.  Only used
@@ -429,15 +483,15 @@ __device__ __forceinline__ int2 slot_hit(const float4& org) { return make_int2(_
 // One thread per active pixel (blockIdx.y splits the samples of a pixel when a frame has few pixels): everything that is
 // the same for every sample of a pixel -- the pixel's coordinates, primary direction, hit point, surface, seed base -- is
 // computed once, not 256 times; consecutive threads still write consecutive slots (sid = k * A + a).
-template <bool MV>
-__global__ void __launch_bounds__(kBlock) sq_gen_bounce1(const SceneView S, const Frame F, const Work W, int k_base, int k_count) {
+template <int SRC, typename FrameT>
+__device__ __forceinline__ void gen_bounce1_body(const SceneView& S, const FrameT& F, const Work& W, int k_base, int k_count) {
     const int A = *W.n_active;
     diag_aux_wave(W, F.diag, true);
     for (int a = blockIdx.x * kBlock + threadIdx.x; a < A; a += gridDim.x * kBlock) {
-        const Pixel0 P = load_pixel0<MV>(S, F, W, a);
+        const Pixel0 P = load_pixel0<SRC>(S, F, W, a);
         const bool absorbing = absorbs(S, P.s0);
         const f3 rad_absorbing = P.s0.surf * sq::mk(0, 0, 0) + P.s0.emit;
-        const long long rix = (long long)F.samples * ((long long)P.x + (long long)P.y * (long long)F.w);   // src/Lib.hs:85
+        const long long rix = seed_base<SRC>(F, W, a, P);
         for (int kl = blockIdx.y; kl < k_count; kl += gridDim.y) {
             const long long sid = (long long)kl * A + a;
             if (absorbing) {
@@ -464,15 +518,18 @@ __global__ void __launch_bounds__(kBlock) sq_gen_bounce1(const SceneView S, cons
     }
     diag_aux_wave(W, F.diag, false);
 }
+template <bool MV>
+__global__ void __launch_bounds__(kBlock) sq_gen_bounce1(const SceneView S, const Frame F, const Work W, int k_base, int k_count) { gen_bounce1_body<MV>(S, F, W, k_base, k_count); }
+__global__ void __launch_bounds__(kBlock) sq_gen_bounce1_rays(const SceneView S, const RayFrame F, const Work W, int k_base, int k_count) { gen_bounce1_body<kSrcRays>(S, F, W, k_base, k_count); }
 
 // The depth-0 mirror ray of every active pixel, once per frame (slot a = active pixel a).
 // `base`: first of the *n_active slots the mirror rays use (0 when they have a launch of their own, the spare region
 // behind the sample slots when they ride at the head of the first bounce launch).
-template <bool MV>
-__global__ void __launch_bounds__(kBlock) sq_mirror1_gen(const SceneView S, const Frame F, const Work W, long long base) {
+template <int SRC, typename FrameT>
+__device__ __forceinline__ void mirror1_gen_body(const SceneView& S, const FrameT& F, const Work& W, long long base) {
     const int A = *W.n_active;
     for (int a = blockIdx.x * kBlock + threadIdx.x; a < A; a += gridDim.x * kBlock) {
-        const Pixel0 P = load_pixel0<MV>(S, F, W, a);
+        const Pixel0 P = load_pixel0<SRC>(S, F, W, a);
         const long long sl = base + a;
         if (absorbs(S, P.s0)) { W.state[sl] = kDone; continue; }
         const f3 d1 = mirror_dir(P.d0, P.s0);
@@ -481,6 +538,9 @@ __global__ void __launch_bounds__(kBlock) sq_mirror1_gen(const SceneView S, cons
         W.dir[sl] = make_float4(d1.x, d1.y, d1.z, 0.0f);
     }
 }
+template <bool MV>
+__global__ void __launch_bounds__(kBlock) sq_mirror1_gen(const SceneView S, const Frame F, const Work W, long long base) { mirror1_gen_body<MV>(S, F, W, base); }
+__global__ void __launch_bounds__(kBlock) sq_mirror1_gen_rays(const SceneView S, const RayFrame F, const Work W, long long base) { mirror1_gen_body<kSrcRays>(S, F, W, base); }
 __global__ void __launch_bounds__(kBlock) sq_mirror1_store(const Work W, long long base) {
     const int A = *W.n_active;
     for (int a = blockIdx.x * kBlock + threadIdx.x; a < A; a += gridDim.x * kBlock) {
@@ -517,6 +577,16 @@ __global__ void __launch_bounds__(kBlock) sq_primary_gen(const Frame F, const Wo
         }
     }
 }
+// ... of a radiance query: the caller's rays as they are (no camera, so nothing of sq_primary_gen is shared).
+__global__ void __launch_bounds__(kBlock) sq_primary_gen_rays(const RayFrame F, const Work W, long long total) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) W.n_active[48] = (int32_t)total;
+    for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < total; i += (long long)gridDim.x * kBlock) {
+        const f3 o = load3(F.ray_org, i), d = load3(F.ray_dir, i);
+        W.state[i] = kRay1;
+        W.org[i] = make_float4(o.x, o.y, o.z, 0.0f);
+        W.dir[i] = make_float4(d.x, d.y, d.z, 0.0f);
+    }
+}
 template <bool AD = false>
 __global__ void __launch_bounds__(kBlock) sq_primary_store(const Frame F, const Work W, long long total) {
     for (long long base = (long long)blockIdx.x * kBlock; base < total; base += (long long)gridDim.x * kBlock) {   // whole waves stay together (ballot)
@@ -539,7 +609,6 @@ struct RayQuery {
     int32_t* tri; float* dist; float* point;
     long long n;
 };
-__device__ __forceinline__ f3 load3(const float* p, long long i) { return sq::mk(p[3 * i], p[3 * i + 1], p[3 * i + 2]); }
 // Maybe Intersection { intersectPoint = o + t *^ d, dist = norm (point - o), surface } (src/Geometry.hs:71-75,134,141), from the very
 // expressions the traversal compares (hit_dist); Nothing is tri = -1, dist = +inf, point = (+0, +0, +0).
 __device__ __forceinline__ void store_ray_hit(const RayQuery& Q, long long i, f3 o, f3 d, Hit h) {
@@ -607,14 +676,15 @@ __global__ void __launch_bounds__(kBlock) sq_stage_cams(float* table, int n, con
 // are per-pixel values.  It waits on memory two thirds of its time, so a slot's state byte decides what else is read (nothing
 // for a finished slot, the generator words for a mirrored one, ray and hit for a traced one), the state and generator words
 // are requested two samples ahead and the rest one sample ahead.
-template <bool MV>
-__global__ void __launch_bounds__(kBlock) sq_shade1(const SceneView S, const Frame F, const Work W, int k_count) {
+// (The body takes its arguments by value, as the kernel does: by reference the multi-view kernel's SGPR spills went from 25 to 30.)
+template <int SRC, typename FrameT>
+__device__ __forceinline__ void shade1_body(const SceneView S, const FrameT F, const Work W, int k_count) {
     const int A = *W.n_active;
     diag_aux_wave(W, F.diag, true);
     struct First { uint8_t st; float4 org; };     // org: .xy = the hit the trace kernel left (traced slots), .w = n1
     struct Second { float4 dir; };                // .w = n2.  Ray 1 starts at the pixel's primary hit point P.p0 (sq_gen_bounce1 stored that very value): no origin is re-read
     for (int a = blockIdx.x * kBlock + threadIdx.x; a < A; a += gridDim.x * kBlock) {
-        const Pixel0 P = load_pixel0<MV>(S, F, W, a);
+        const Pixel0 P = load_pixel0<SRC>(S, F, W, a);
         const Surface& s0 = P.s0;
         const f3 d1_mirror = mirror_dir(P.d0, P.s0);
         const int2 hit_mirror = make_int2(__float_as_int(W.px_mt[a]), W.px_mtri[a]);
@@ -683,6 +753,9 @@ __global__ void __launch_bounds__(kBlock) sq_shade1(const SceneView S, const Fra
     }
     diag_aux_wave(W, F.diag, false);
 }
+template <bool MV>
+__global__ void __launch_bounds__(kBlock) sq_shade1(const SceneView S, const Frame F, const Work W, int k_count) { shade1_body<MV>(S, F, W, k_count); }
+__global__ void __launch_bounds__(kBlock) sq_shade1_rays(const SceneView S, const RayFrame F, const Work W, int k_count) { shade1_body<kSrcRays>(S, F, W, k_count); }
 
 // After ray 2: L2 = s2*0 + e2 (or black), L1 = s1*L2 + e1, L0 = s0*L1 + e0   (src/Lib.hs:135-137).
 // Not a kernel of its own: the 8 % of the slots that still hold a second bounce ray are folded where their radiance is
@@ -871,8 +944,9 @@ __device__ __forceinline__ void stage_resident_scene(const SceneView& S, int n_b
 // Primary rays with the scene in LDS (the resident form): same per-ray code as sq_primary, but a branch or triangle costs an
 // LDS read instead of an L2 round trip.  A primary ray is a chain of ~200 dependent reads, so on small frames -- one rank's
 // share of a frame at 8 ranks -- the launch is as long as that chain: 0.58 ms from L2, 0.1-0.2 ms from LDS.
-template <typename StackT, bool MV, bool AD = false>
-__global__ void __launch_bounds__(kResidentBlock) sq_primary_resident(const SceneView S, const Frame F, const Work W, int stack_cap) {
+template <typename StackT, int SRC, bool AD, typename FrameT>
+__device__ __forceinline__ void primary_resident_body(const SceneView& S, const FrameT& F, const Work& W, int stack_cap) {
+    constexpr bool MV = SRC == kSrcViews;
     extern __shared__ float4 lds_raw[];
     char* lds = reinterpret_cast<char*>(lds_raw);
     const TraceLds L = trace_lds_layout(S.n_branches, true, S.n_verts, S.n_tris, kResidentBlock, stack_cap, (int)sizeof(StackT), false);
@@ -884,14 +958,17 @@ __global__ void __launch_bounds__(kResidentBlock) sq_primary_resident(const Scen
     for (long long base = (long long)blockIdx.x * kResidentBlock; base < total; base += (long long)gridDim.x * kResidentBlock) {
         int view = 0;
         long long pix;                                                      // (total is a multiple of 64: whole waves)
-        if constexpr (MV) pix = primary_tile_views(F, base + threadIdx.x, view);
+        if constexpr (SRC == kSrcRays) pix = base + threadIdx.x < (long long)F.h ? base + threadIdx.x : -1;   // index order, as in sq_primary_rays
+        else if constexpr (MV) pix = primary_tile_views(F, base + threadIdx.x, view);
         else pix = primary_tile(F, base + threadIdx.x);
         bool in = pix >= 0;
         if constexpr (AD) in = in && pixel_live(F, pix);
         Hit h0; h0.tri = -1; h0.t = 0;
         if (in) {
             int y, x;
-            if constexpr (MV) {
+            if constexpr (SRC == kSrcRays) {
+                h0 = trace_one(S, N, G, S.rroot, load3(F.ray_org, pix), load3(F.ray_dir, pix), stk, kResidentBlock);
+            } else if constexpr (MV) {
                 pixel_coords(F, pix - (long long)view * F.view_pixels, y, x);
                 const ViewCam c = view_cam<true>(F, view);
                 h0 = trace_one(S, N, G, S.rroot, c.pos, primary_dir(c.rot, F.w, F.h, y, x), stk, kResidentBlock);
@@ -905,6 +982,10 @@ __global__ void __launch_bounds__(kResidentBlock) sq_primary_resident(const Scen
         else if (in) store_miss<AD>(F, pix);
     }
 }
+template <typename StackT, bool MV, bool AD = false>
+__global__ void __launch_bounds__(kResidentBlock) sq_primary_resident(const SceneView S, const Frame F, const Work W, int stack_cap) { primary_resident_body<StackT, MV, AD>(S, F, W, stack_cap); }
+template <typename StackT>
+__global__ void __launch_bounds__(kResidentBlock) sq_primary_resident_rays(const SceneView S, const RayFrame F, const Work W, int stack_cap) { primary_resident_body<StackT, kSrcRays, false>(S, F, W, stack_cap); }
 
 template <typename StackT, bool RESIDENT, int BLOCK, bool PROFILE, bool POOL>
 __device__ __forceinline__ void trace_rays_body(const SceneView& S, const TraceArgs& A) {
@@ -1858,6 +1939,30 @@ int timed_launch(sq_device_scene* s, Fn&& fn, const char* name, hipStream_t on) 
     return 0;
 }
 
+// The kernels of a ray source: the frames' own (bool MV) for kSrcCamera / kSrcViews, the query kernels for kSrcRays.  The two sets have
+// the same arguments but for the frame's type (FrameT), so launch_frame's schedules do not know which they enqueue.
+template <typename StackT, int SRC> struct SrcKernels {
+    using FrameT = Frame;
+    static constexpr bool MV = SRC == kSrcViews;
+    static constexpr auto render_pixels = &sq_render_pixels<StackT, MV>;
+    static constexpr auto primary = &sq_primary<StackT, MV>;
+    static constexpr auto primary_resident = &sq_primary_resident<StackT, MV>;
+    static constexpr auto primary_gen = &sq_primary_gen<MV>;
+    static constexpr auto gen_bounce1 = &sq_gen_bounce1<MV>;
+    static constexpr auto mirror1_gen = &sq_mirror1_gen<MV>;
+    static constexpr auto shade1 = &sq_shade1<MV>;
+};
+template <typename StackT> struct SrcKernels<StackT, kSrcRays> {
+    using FrameT = RayFrame;
+    static constexpr auto render_pixels = &sq_render_pixels_rays<StackT>;
+    static constexpr auto primary = &sq_primary_rays<StackT>;
+    static constexpr auto primary_resident = &sq_primary_resident_rays<StackT>;
+    static constexpr auto primary_gen = &sq_primary_gen_rays;
+    static constexpr auto gen_bounce1 = &sq_gen_bounce1_rays;
+    static constexpr auto mirror1_gen = &sq_mirror1_gen_rays;
+    static constexpr auto shade1 = &sq_shade1_rays;
+};
+
 // The persistent trace kernel of a frame's wavefront pipeline or of a ray query: its form and launch geometry (plan_trace).
 struct TracePlan {
     bool resident = false, pool = false;
@@ -1867,8 +1972,8 @@ struct TracePlan {
 };
 // Chooses the trace form -- resident, streaming six-wave or streaming plain -- its LDS layout and workgroups per CU, and fills the
 // trace fields of s->plan.  Refuses (an error code, nothing enqueued) a tree whose stacks do not fit the streaming form's LDS.
-// MV: the frame's primary-ray kernel whose static LDS is checked with the resident kernels (a query plans with MV = false).
-template <typename StackT, bool MV>
+// SRC: the frame's primary-ray kernel whose static LDS is checked with the resident kernels (an intersection query plans with kSrcCamera).
+template <typename StackT, int SRC>
 int plan_trace(sq_device_scene* s, const SceneView& S, int stack_cap, TracePlan& T) {
     sq_plan& P = s->plan;
     // persistent trace kernel geometry.  Resident form: the whole scene (branches, leaves, unique vertices,
@@ -1927,7 +2032,7 @@ int plan_trace(sq_device_scene* s, const SceneView& S, int stack_cap, TracePlan&
         // where a violation is an error code, rather than by the device-side trap, where it would be a GPU abort.
         const void* fns[5] = { (const void*)sq_trace_rays<StackT, true, kResidentBlock, false, true>, (const void*)sq_trace_rays<StackT, true, kResidentBlock, true, true>,
                                (const void*)sq_trace_rays<StackT, true, kResidentBlock, false, false>, (const void*)sq_trace_rays<StackT, true, kResidentBlock, true, false>,
-                               (const void*)sq_primary_resident<StackT, MV> };
+                               (const void*)SrcKernels<StackT, SRC>::primary_resident };
         for (const void* fn : fns) {
             hipFuncAttributes attr{};
             SQ_HIP(hipFuncGetAttributes(&attr, fn));
@@ -1968,9 +2073,12 @@ int launch_trace_kernel(sq_device_scene* s, const SceneView& S, const TracePlan&
     }, "sq_trace_rays", on);
 }
 
-// MV: a multi-view frame; `cams` (host, F.n_views of them) are staged into the scene's camera table F.cams once the frame is planned.
-template <typename StackT, bool MV>
-int launch_frame(sq_device_scene* s, const Frame& F, hipStream_t stream, const sq_camera* cams) {
+// kSrcViews: a multi-view frame; `cams` (host, F.n_views of them) are staged into the scene's camera table F.cams once the frame is planned.
+// kSrcRays: a chunk of a radiance query (radiance_rays): a frame of one row whose "pixels" are the caller's rays F.ray_org / ray_dir / ray_seed.
+template <typename StackT, int SRC>
+int launch_frame(sq_device_scene* s, const typename SrcKernels<StackT, SRC>::FrameT& F, hipStream_t stream, const sq_camera* cams) {
+    constexpr bool MV = SRC == kSrcViews;
+    using K = SrcKernels<StackT, SRC>;
     SceneView S = s->view;
     if (!s->opt_cull) S.cull_o2max = -1.0f;                            // no ray is inside the culling limits: every leaf is tested
     if (!s->opt_incremental) S.incremental_ok = 0;                     // resident form: every branch step tests both children from the branch's own box
@@ -1986,17 +2094,17 @@ int launch_frame(sq_device_scene* s, const Frame& F, hipStream_t stream, const s
     s->has_plan = true;
     // a masked call (sq_render_rows_device_masked with a mask, second moments or counts) takes the AD instantiations of the kernels that
     // decide who is active, and clears no buffer; every other call takes the instantiations, and the memsets, it always took
-    constexpr bool kAD = !MV;                                          // multi-view frames have no masked form
+    constexpr bool kAD = SRC == kSrcCamera;                            // multi-view frames and queries have no masked form
     const bool ad = kAD && (F.mask || F.sum2 || F.count);
     const bool mom2 = ad && F.sum2;
     if (px_blocks > 0x7fffffffLL) return sq_set_error("image too large for one launch");
     if (px_lds > 160 * 1024) return sq_set_error("BIH height %d needs %zu B of LDS stack per workgroup (max 163840)", S.height, px_lds);
     if (s->opt_variant == 1 || F.cast) {
-        if (px_lds > 64 * 1024) SQ_HIP(hipFuncSetAttribute(ad ? (const void*)sq_render_pixels<StackT, MV, kAD> : (const void*)sq_render_pixels<StackT, MV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)px_lds));
+        if (px_lds > 64 * 1024) SQ_HIP(hipFuncSetAttribute(ad ? (const void*)sq_render_pixels<StackT, MV, kAD> : (const void*)K::render_pixels, hipFuncAttributeMaxDynamicSharedMemorySize, (int)px_lds));
         P.launched = 1;
         if (stage_cams(s, F, cams, stream)) return 1;
         if (ad) return timed_launch(s, [&] { hipLaunchKernelGGL((sq_render_pixels<StackT, MV, kAD>), dim3((unsigned)px_blocks), dim3(kBlock), px_lds, stream, S, F); }, "sq_render_pixels", stream);
-        return timed_launch(s, [&] { hipLaunchKernelGGL((sq_render_pixels<StackT, MV>), dim3((unsigned)px_blocks), dim3(kBlock), px_lds, stream, S, F); }, "sq_render_pixels", stream);
+        return timed_launch(s, [&] { hipLaunchKernelGGL(K::render_pixels, dim3((unsigned)px_blocks), dim3(kBlock), px_lds, stream, S, F); }, "sq_render_pixels", stream);
     }
     // ---- wavefront pipeline ----
     const int n_call = F.k_end - F.k_begin;                              // the samples this call renders (a whole frame: F.samples)
@@ -2028,7 +2136,7 @@ int launch_frame(sq_device_scene* s, const Frame& F, hipStream_t stream, const s
     const int n_batches = std::max(tracks, (n_call + max_batch - 1) / max_batch);
     const int batch = (n_call + n_batches - 1) / n_batches;
     TracePlan TP;
-    if (plan_trace<StackT, MV>(s, S, stack_cap, TP)) return 1;
+    if (plan_trace<StackT, SRC>(s, S, stack_cap, TP)) return 1;
     const bool resident = TP.resident, pool = TP.pool;
     P.primary_form = (s->opt_primary_pooled && pool) ? SQ_PRIMARY_POOLED : (resident && s->opt_primary_resident) ? SQ_PRIMARY_RESIDENT : SQ_PRIMARY_PER_LANE;
     // the per-lane primary pass is one launch with a thread per tile lane, padding included (a narrow frame's edge tiles are mostly
@@ -2047,14 +2155,14 @@ int launch_frame(sq_device_scene* s, const Frame& F, hipStream_t stream, const s
     if (primary_pooled) {
     } else if (resident && s->opt_primary_resident) {
         const TraceLds Lp = trace_lds_layout(S.n_branches, true, S.n_verts, S.n_tris, kResidentBlock, stack_cap, (int)sizeof(StackT), false);
-        SQ_HIP(hipFuncSetAttribute(ad ? (const void*)sq_primary_resident<StackT, MV, kAD> : (const void*)sq_primary_resident<StackT, MV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)Lp.total));
+        SQ_HIP(hipFuncSetAttribute(ad ? (const void*)sq_primary_resident<StackT, MV, kAD> : (const void*)K::primary_resident, hipFuncAttributeMaxDynamicSharedMemorySize, (int)Lp.total));
         const long long need = (primary_padded(F) * F.n_views + kResidentBlock - 1) / kResidentBlock;
         if (ad) hipLaunchKernelGGL((sq_primary_resident<StackT, MV, kAD>), dim3((unsigned)std::min<long long>(s->n_cu, need)), dim3(kResidentBlock), Lp.total, stream, S, F, W, stack_cap);
-        else hipLaunchKernelGGL((sq_primary_resident<StackT, MV>), dim3((unsigned)std::min<long long>(s->n_cu, need)), dim3(kResidentBlock), Lp.total, stream, S, F, W, stack_cap);
+        else hipLaunchKernelGGL(K::primary_resident, dim3((unsigned)std::min<long long>(s->n_cu, need)), dim3(kResidentBlock), Lp.total, stream, S, F, W, stack_cap);
     } else {
-        if (px_lds > 64 * 1024) SQ_HIP(hipFuncSetAttribute(ad ? (const void*)sq_primary<StackT, MV, kAD> : (const void*)sq_primary<StackT, MV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)px_lds));
+        if (px_lds > 64 * 1024) SQ_HIP(hipFuncSetAttribute(ad ? (const void*)sq_primary<StackT, MV, kAD> : (const void*)K::primary, hipFuncAttributeMaxDynamicSharedMemorySize, (int)px_lds));
         if (ad) hipLaunchKernelGGL((sq_primary<StackT, MV, kAD>), dim3((unsigned)((primary_padded(F) * F.n_views + kBlock - 1) / kBlock)), dim3(kBlock), px_lds, stream, S, F, W);
-        else hipLaunchKernelGGL((sq_primary<StackT, MV>), dim3((unsigned)((primary_padded(F) * F.n_views + kBlock - 1) / kBlock)), dim3(kBlock), px_lds, stream, S, F, W);
+        else hipLaunchKernelGGL(K::primary, dim3((unsigned)((primary_padded(F) * F.n_views + kBlock - 1) / kBlock)), dim3(kBlock), px_lds, stream, S, F, W);
     }
     SQ_HIP(hipGetLastError());
     const int aux_blocks = s->n_cu * (int)(s->opt_aux_blocks_per_cu ? s->opt_aux_blocks_per_cu : 8);
@@ -2082,7 +2190,7 @@ int launch_frame(sq_device_scene* s, const Frame& F, hipStream_t stream, const s
         Work Wp = W; Wp.n_active = W.n_active + 48;                     // the launch's queue is the shard's pixels, not the active ones
         SQ_HIP(hipMemsetAsync(W.head[0], 0, 32 * sizeof(int32_t), stream));
         if (ad) hipLaunchKernelGGL((sq_primary_gen<MV, kAD>), dim3(aux_blocks), dim3(kBlock), 0, stream, F, W, pixels);
-        else hipLaunchKernelGGL(sq_primary_gen<MV>, dim3(aux_blocks), dim3(kBlock), 0, stream, F, W, pixels);
+        else hipLaunchKernelGGL(K::primary_gen, dim3(aux_blocks), dim3(kBlock), 0, stream, F, W, pixels);
         SQ_HIP(hipGetLastError());
         if (launch_trace(Wp, 1, 0, stream)) return 1;
         if (ad) hipLaunchKernelGGL(sq_primary_store<kAD>, dim3(aux_blocks), dim3(kBlock), 0, stream, F, W, pixels);
@@ -2095,7 +2203,7 @@ int launch_frame(sq_device_scene* s, const Frame& F, hipStream_t stream, const s
     const bool mirror_rides = !overlap;
     if (!mirror_rides) {
         SQ_HIP(hipMemsetAsync(W.head[0], 0, 32 * sizeof(int32_t), stream));
-        hipLaunchKernelGGL(sq_mirror1_gen<MV>, dim3(aux_blocks), dim3(kBlock), 0, stream, S, F, W, 0ll);
+        hipLaunchKernelGGL(K::mirror1_gen, dim3(aux_blocks), dim3(kBlock), 0, stream, S, F, W, 0ll);
         SQ_HIP(hipGetLastError());
         if (launch_trace(W, 1, 0, stream)) return 1;
         hipLaunchKernelGGL(sq_mirror1_store, dim3(aux_blocks), dim3(kBlock), 0, stream, W, 0ll);
@@ -2110,14 +2218,14 @@ int launch_frame(sq_device_scene* s, const Frame& F, hipStream_t stream, const s
         for (int i = 0; i < n_real; ++i) {
             const int k0 = k0_of(i), kc = kc_of(i);
             SQ_HIP(hipMemsetAsync(W.head[0], 0, 32 * sizeof(int32_t), stream));     // both dequeue cursors
-            hipLaunchKernelGGL(sq_gen_bounce1<MV>, pp_grid(kc), dim3(kBlock), 0, stream, S, F, W, k0, kc);
+            hipLaunchKernelGGL(K::gen_bounce1, pp_grid(kc), dim3(kBlock), 0, stream, S, F, W, k0, kc);
             SQ_HIP(hipGetLastError());
             const bool front = mirror_rides && i == 0;
-            if (front) hipLaunchKernelGGL(sq_mirror1_gen<MV>, dim3(aux_blocks), dim3(kBlock), 0, stream, S, F, W, (long long)W.slot_capacity);
+            if (front) hipLaunchKernelGGL(K::mirror1_gen, dim3(aux_blocks), dim3(kBlock), 0, stream, S, F, W, (long long)W.slot_capacity);
             for (int level = 0; level < 2; ++level) {
                 if (launch_trace(W, kc, level, stream, front && level == 0)) return 1;
                 if (front && level == 0) hipLaunchKernelGGL(sq_mirror1_store, dim3(aux_blocks), dim3(kBlock), 0, stream, W, (long long)W.slot_capacity);
-                if (level == 0) hipLaunchKernelGGL(sq_shade1<MV>, pp_grid(kc), dim3(kBlock), 0, stream, S, F, W, kc);
+                if (level == 0) hipLaunchKernelGGL(K::shade1, pp_grid(kc), dim3(kBlock), 0, stream, S, F, W, kc);
                 SQ_HIP(hipGetLastError());
             }
             SQ_LAUNCH_ACCUMULATE( dim3(aux_blocks), dim3(kBlock), 0, stream, S, F, W, kc, (k0 + kc >= F.k_end) ? 1 : 0);
@@ -2159,10 +2267,10 @@ int launch_frame(sq_device_scene* s, const Frame& F, hipStream_t stream, const s
             const Work& V = Wt[i & 1];
             const int k0 = k0_of(i), kc = kc_of(i);
             SQ_HIP(hipMemsetAsync(V.head[0], 0, 32 * sizeof(int32_t), on));
-            hipLaunchKernelGGL(sq_gen_bounce1<MV>, pp_grid(kc), dim3(kBlock), 0, on, S, F, V, k0, kc);
+            hipLaunchKernelGGL(K::gen_bounce1, pp_grid(kc), dim3(kBlock), 0, on, S, F, V, k0, kc);
             SQ_HIP(hipGetLastError());
             if (launch_trace(V, kc, 0, on)) return 1;
-            hipLaunchKernelGGL(sq_shade1<MV>, pp_grid(kc), dim3(kBlock), 0, on, S, F, V, kc);
+            hipLaunchKernelGGL(K::shade1, pp_grid(kc), dim3(kBlock), 0, on, S, F, V, kc);
             SQ_HIP(hipGetLastError());
             if (launch_trace(V, kc, 1, on)) return 1;
             if (i > 0) SQ_HIP(hipStreamWaitEvent(on, eAcc[(size_t)i - 1], 0));
@@ -2184,7 +2292,7 @@ int launch_frame(sq_device_scene* s, const Frame& F, hipStream_t stream, const s
     auto gen = [&](int i) -> int {                          // on X
         const Work& V = Wt[i & 1];
         SQ_HIP(hipMemsetAsync(V.head[0], 0, 32 * sizeof(int32_t), X));
-        hipLaunchKernelGGL(sq_gen_bounce1<MV>, pp_grid(kc_of(i)), dim3(kBlock), 0, X, S, F, V, k0_of(i), kc_of(i));
+        hipLaunchKernelGGL(K::gen_bounce1, pp_grid(kc_of(i)), dim3(kBlock), 0, X, S, F, V, k0_of(i), kc_of(i));
         SQ_HIP(hipGetLastError());
         SQ_HIP(hipEventRecord(eG[(size_t)i], X));
         return 0;
@@ -2197,7 +2305,7 @@ int launch_frame(sq_device_scene* s, const Frame& F, hipStream_t stream, const s
     };
     auto shade1 = [&](int i) -> int {                       // on X
         SQ_HIP(hipStreamWaitEvent(X, eT1[(size_t)i], 0));
-        hipLaunchKernelGGL(sq_shade1<MV>, pp_grid(kc_of(i)), dim3(kBlock), 0, X, S, F, Wt[i & 1], kc_of(i));
+        hipLaunchKernelGGL(K::shade1, pp_grid(kc_of(i)), dim3(kBlock), 0, X, S, F, Wt[i & 1], kc_of(i));
         SQ_HIP(hipGetLastError());
         SQ_HIP(hipEventRecord(eS1[(size_t)i], X));
         return 0;
@@ -2296,10 +2404,10 @@ int render_rows(sq_device_scene* s, const sq_camera* cam, int32_t n_views, int32
     F.n_views = n_views; F.view_pixels = rows * h; F.cams = nullptr;
     F.mask = d_mask; F.sum2 = d_sum2; F.count = d_count;
     hipStream_t stream = (hipStream_t)hip_stream;
-    if (n_views == 1) return s->small_index ? launch_frame<uint16_t, false>(s, F, stream, nullptr) : launch_frame<uint32_t, false>(s, F, stream, nullptr);
+    if (n_views == 1) return s->small_index ? launch_frame<uint16_t, kSrcCamera>(s, F, stream, nullptr) : launch_frame<uint32_t, kSrcCamera>(s, F, stream, nullptr);
     if (ensure_cam_table(s, n_views)) return 1;
     F.cams = s->d_cams;
-    return s->small_index ? launch_frame<uint16_t, true>(s, F, stream, cam) : launch_frame<uint32_t, true>(s, F, stream, cam);
+    return s->small_index ? launch_frame<uint16_t, kSrcViews>(s, F, stream, cam) : launch_frame<uint32_t, kSrcViews>(s, F, stream, cam);
 }
 }  // namespace
 
@@ -2424,7 +2532,7 @@ int intersect_rays(sq_device_scene* s, const RayQuery& Q, hipStream_t stream) {
         return 0;
     }
     TracePlan TP;
-    if (plan_trace<StackT, false>(s, S, stack_cap, TP)) return 1;
+    if (plan_trace<StackT, kSrcCamera>(s, S, stack_cap, TP)) return 1;
     // Chunks of at most `slots` rays (and what the workspace holds; the option caps the slots at 2^29, so a chunk's queue positions and
     // the trace kernel's 32-bit cursor never overflow).  One slot per ray: 45 B, against 40 B of caller arrays per ray.
     if (ensure_workspace(s, 1, std::min<int64_t>(s->opt_slots, Q.n))) return 1;
@@ -2488,6 +2596,100 @@ extern "C" int sq_camera_rays_device(sq_device_scene* s, const sq_camera* cam, i
     hipLaunchKernelGGL(sq_camera_rays, grid, dim3(kBlock), 0, (hipStream_t)hip_stream, F, d_org, d_dir, total);
     SQ_HIP(hipGetLastError());
     return 0;
+}
+
+// ----------------------------------------------------------------------------------------------
+// Radiance queries (sq_raytrace_rays_device, sq_raycast_rays_device): raytrace / raycast of caller-given rays, src/Lib.hs:127-151
+// ----------------------------------------------------------------------------------------------
+namespace {
+// A query's arrays: n rays, [n][3] floats for origin, direction, sum (raycast: the radiance), avg and [n][3] bytes for rgb; seed [n].
+struct RadianceQuery {
+    const float* org; const float* dir; const long long* seed;
+    float* sum; float* avg; uint8_t* rgb;
+    long long n;
+};
+// Rays per chunk of a query of n > 0 rays: every chunk is a frame of its own, so it stays within a frame's limits -- 2^29 "pixels" and
+// one sample of every pixel in the workspace's `slots` (1 .. 2^29) in the wavefront form, a launch of 2^30 lanes in the per-lane form.
+// Plain 64-bit host arithmetic: chunk c covers the rays [c * chunk, min(n, (c + 1) * chunk)), the last one may be short.
+long long radiance_chunk_rays(long long n, long long slots, bool wavefront) {
+    const long long cap = wavefront ? std::min<long long>(std::max<long long>(slots, 1), kMaxWavefrontPixels) : kLaneChunk;
+    return std::min(n, cap);
+}
+// The query's rays [c0, c0 + m): all six arrays advance together (elements, not bytes).
+RadianceQuery radiance_part(const RadianceQuery& Q, long long c0, long long m) {
+    RadianceQuery C = Q;
+    C.org += 3 * c0; C.dir += 3 * c0; C.sum += 3 * c0;
+    if (C.seed) C.seed += c0;
+    if (C.avg) C.avg += 3 * c0;
+    if (C.rgb) C.rgb += 3 * c0;
+    C.n = m;
+    return C;
+}
+// A checked query (Q.n > 0): chunk by chunk a ray-source frame through launch_frame -- its plan, refusals, forms and schedules.  Every
+// chunk has the same plan, and the first is the largest, so a refusal comes from the first chunk, before anything is enqueued.
+template <typename StackT>
+int radiance_rays(sq_device_scene* s, const RadianceQuery& Q, int32_t k_begin, int32_t k_end, bool cast, hipStream_t stream) {
+    const long long chunk = radiance_chunk_rays(Q.n, s->opt_slots, s->opt_variant != 1 && !cast);
+    for (long long c0 = 0; c0 < Q.n; c0 += chunk) {
+        const RadianceQuery C = radiance_part(Q, c0, std::min(chunk, Q.n - c0));
+        RayFrame F{};
+        F.samples = k_end; F.w = 1; F.h = (int32_t)C.n; F.cast = cast ? 1 : 0;
+        F.row_block = 1; F.shard = 0; F.n_shards = 1; F.local_rows = 1;
+        F.tile_rows = 1; F.tiles_x = (int32_t)((C.n + 63) / 64);          // primary_padded: the chunk padded to whole waves
+        F.out_avg = C.avg; F.out_rgb = C.rgb;
+        F.k_begin = k_begin; F.k_end = k_end; F.sum = C.sum;
+        F.diag = s->opt_coresidency ? std::max(1, s->n_cu - 8) : 0;
+        F.n_views = 1; F.view_pixels = (int32_t)C.n; F.cams = nullptr;
+        F.ray_org = C.org; F.ray_dir = C.dir; F.ray_seed = C.seed;
+        if (launch_frame<StackT, kSrcRays>(s, F, stream, nullptr)) return 1;
+    }
+    return 0;
+}
+// The argument checks the two queries share; r = the ranges that must not overlap (NULL = not given).
+struct NamedRange { const char* name; const void* p; size_t bytes; };
+int refuse_overlaps(const NamedRange* r, int count) {
+    for (int i = 0; i < count; ++i)
+        for (int j = i + 1; j < count; ++j)
+            if (r[i].p && r[j].p && ranges_overlap(r[i].p, r[i].bytes, r[j].p, r[j].bytes))
+                return sq_set_error("%s and %s overlap", r[i].name, r[j].name);
+    return 0;
+}
+}  // namespace
+
+extern "C" int sq_raytrace_rays_device(sq_device_scene* s, const float* d_org, const float* d_dir, const int64_t* d_seed, int64_t n,
+                                       int32_t k_begin, int32_t k_end,
+                                       float* d_sum, float* d_avg, uint8_t* d_rgb, void* hip_stream) {
+    if (!s) return sq_set_error("null argument");
+    if (n < 0) return sq_set_error("n must be >= 0 (got %lld)", (long long)n);
+    if (k_begin < 0 || k_end <= k_begin) return sq_set_error("bad sample range [%d, %d) (need 0 <= k_begin < k_end)", k_begin, k_end);
+    if (n == 0) return 0;
+    if (!d_org || !d_dir || !d_seed || !d_sum) return sq_set_error("d_org, d_dir, d_seed and d_sum are required");
+    if (n > (INT64_MAX / 12)) return sq_set_error("%lld rays are too many", (long long)n);
+    const size_t n3 = (size_t)n * 12;
+    const NamedRange r[6] = { { "d_org", d_org, n3 }, { "d_dir", d_dir, n3 }, { "d_seed", d_seed, (size_t)n * 8 },
+                              { "d_sum", d_sum, n3 }, { "d_avg", d_avg, n3 }, { "d_rgb", d_rgb, (size_t)n * 3 } };
+    if (refuse_overlaps(r, 6)) return 1;
+    SQ_HIP(hipSetDevice(s->device));
+    static_assert(sizeof(long long) == sizeof(int64_t), "seed bases are 64-bit");
+    const RadianceQuery Q{ d_org, d_dir, (const long long*)d_seed, d_sum, d_avg, d_rgb, (long long)n };
+    hipStream_t stream = (hipStream_t)hip_stream;
+    return s->small_index ? radiance_rays<uint16_t>(s, Q, k_begin, k_end, false, stream) : radiance_rays<uint32_t>(s, Q, k_begin, k_end, false, stream);
+}
+
+extern "C" int sq_raycast_rays_device(sq_device_scene* s, const float* d_org, const float* d_dir, int64_t n,
+                                      float* d_rad, void* hip_stream) {
+    if (!s) return sq_set_error("null argument");
+    if (n < 0) return sq_set_error("n must be >= 0 (got %lld)", (long long)n);
+    if (n == 0) return 0;
+    if (!d_org || !d_dir || !d_rad) return sq_set_error("d_org, d_dir and d_rad are required");
+    if (n > (INT64_MAX / 12)) return sq_set_error("%lld rays are too many", (long long)n);
+    const size_t n3 = (size_t)n * 12;
+    const NamedRange r[3] = { { "d_org", d_org, n3 }, { "d_dir", d_dir, n3 }, { "d_rad", d_rad, n3 } };
+    if (refuse_overlaps(r, 3)) return 1;
+    SQ_HIP(hipSetDevice(s->device));
+    const RadianceQuery Q{ d_org, d_dir, nullptr, d_rad, nullptr, nullptr, (long long)n };
+    hipStream_t stream = (hipStream_t)hip_stream;
+    return s->small_index ? radiance_rays<uint16_t>(s, Q, 0, 1, true, stream) : radiance_rays<uint32_t>(s, Q, 0, 1, true, stream);
 }
 
 extern "C" int sq_kernel_timing(sq_device_scene* s, double* avg_ms, int64_t* launches, const char** name) {

@@ -13,6 +13,9 @@ from . import _native as N
 Hits = collections.namedtuple("Hits", ["tri", "dist", "point"])
 Hits.__doc__ = """Results of DeviceScene.intersect: Maybe Intersection (src/Geometry.hs:71-75) per ray; tri = -1 is Nothing."""
 
+Radiance = collections.namedtuple("Radiance", ["sum", "avg", "rgb"])
+Radiance.__doc__ = """Results of DeviceScene.raytrace per ray: the fold of its sample radiances, (1 / k_end) * sum, and its tonemap."""
+
 
 # The largest frame one call takes (include/squigly_hip.h, DESIGN.md 4.13): pixel indices are 32-bit, and the wavefront form's
 # active-pixel list and ray queue hold while a call has at most 2^29 pixels.
@@ -54,6 +57,32 @@ def _ray_shape(origins, directions):
     if shapes[0] != shapes[1]:
         raise N.SquiglyError(f"origins {shapes[0]} and directions {shapes[1]} must have the same shape")
     return shapes[0]
+
+
+def frame_seeds(samples, w, h, shard=(None, 0, 1), device=None):
+    """The seed bases of a frame's pixels (src/Lib.hs:85): an int64 tensor [rows, h] holding samples * (x + y * w) for the global
+    row y of every local row of the shard (sq_shard_global_row) and every column x.  With them
+    ds.raytrace(*ds.camera_rays(cam, w, h, shard), seeds=frame_seeds(samples, w, h, shard), samples=samples) is the frame.
+    Pure integer arithmetic: device=None builds the tensor on the CPU."""
+    samples, w, h = int(samples), int(w), int(h)
+    if samples < 1 or w < 1 or h < 1:
+        raise N.SquiglyError(f"samples, width and height must be positive (got {samples}, {w}, {h})")
+    rb, si, ns = shard
+    rb, si, ns = int(w if rb is None else rb), int(si), int(ns)
+    if rb <= 0 or ns <= 0 or si < 0 or si >= ns:
+        raise N.SquiglyError(f"bad shard {shard}")
+    blocks = torch.arange(si, (w + rb - 1) // rb, ns, dtype=torch.int64, device=device)       # this shard's row blocks
+    y = (blocks[:, None] * rb + torch.arange(rb, dtype=torch.int64, device=device)[None, :]).reshape(-1)
+    y = y[y < w]                                                                             # the image's last block may be short
+    x = torch.arange(h, dtype=torch.int64, device=device)
+    return samples * (x[None, :] + y[:, None] * w)
+
+
+def _lead_count(lead):
+    n = 1
+    for v in lead:
+        n *= int(v)
+    return n
 
 
 class DeviceScene:
@@ -257,6 +286,74 @@ class DeviceScene:
         N.check(N.lib().sq_camera_rays_device(self._h, C.byref(cam), int(w), int(h), sh, o.data_ptr(), d.data_ptr(),
                                               C.c_void_p(st.cuda_stream)))
         return o, d
+
+    def raytrace(self, origins, directions, seeds=None, samples=1, k_range=None, sums=None, want_avg=True, want_rgb=False,
+                 stream=None):
+        """Lib.raytrace of each ray (sq_raytrace_rays_device): returns Radiance(sum, avg, rgb) CUDA tensors, enqueued on `stream`.
+
+        origins, directions: any [..., 3] arrays of one shape, converted as in `intersect` (float64 is rounded to float32 first).
+        seeds: int64 [...] seed bases; sample k of a ray draws from mkTFGen (seed + k).  None means samples * i for the i-th ray in
+        row-major order -- distinct generators for every sample of the batch, NOT a frame's rule unless w == h (see frame_seeds).
+        k_range = (k_begin, k_end): the samples folded by this call, (0, samples) by default.  sums: float32 CUDA tensor [..., 3]
+        carrying the fold as in render_rows_range; required when k_begin > 0, updated in place, allocated otherwise.
+        sum is the left fold of the sample radiances, avg = (1 / k_end) * sum (None unless want_avg), rgb its tonemap (uint8, None
+        unless want_rgb).  A ray that hits nothing gets zeros.
+        """
+        shape = _ray_shape(origins, directions)
+        lead = shape[:-1]
+        n = _lead_count(lead)
+        dev = torch.device("cuda", self.device)
+        samples = int(samples)
+        if samples < 1:
+            raise N.SquiglyError(f"samples must be positive, got {samples}")
+        k_begin, k_end = (0, samples) if k_range is None else (int(k_range[0]), int(k_range[1]))
+        if k_begin < 0 or k_end <= k_begin or k_end >= 2 ** 31:
+            raise N.SquiglyError(f"bad sample range [{k_begin}, {k_end}) (need 0 <= k_begin < k_end)")
+        if seeds is not None:
+            sshape = tuple(seeds.shape) if hasattr(seeds, "shape") else tuple(torch.as_tensor(seeds).shape)
+            if sshape != tuple(lead):
+                raise N.SquiglyError(f"seeds must have shape {tuple(lead)}, got {sshape}")
+            sdtype = seeds.dtype if isinstance(seeds, torch.Tensor) else torch.as_tensor(seeds).dtype
+            if sdtype not in (torch.int64, torch.int32, torch.int16, torch.int8, torch.uint8):
+                raise N.SquiglyError(f"seeds must be integers (int64), got {sdtype}")
+        if sums is None:
+            if k_begin > 0:
+                raise N.SquiglyError("raytrace needs the sums of the samples [0, k_begin) when k_range starts above 0")
+        else:
+            if not isinstance(sums, torch.Tensor):
+                raise N.SquiglyError("sums must be a CUDA tensor: it is updated in place")
+            self._frame_tensor("sums", sums, shape, torch.float32)
+        st = stream if stream is not None else torch.cuda.current_stream(dev)
+        with torch.cuda.stream(st):      # temporaries are allocated and freed in the order of the call's stream
+            o = torch.as_tensor(origins, device=dev).to(torch.float32).contiguous()
+            d = torch.as_tensor(directions, device=dev).to(torch.float32).contiguous()
+            if seeds is None:
+                sd = (samples * torch.arange(n, dtype=torch.int64, device=dev)).reshape(lead)
+            else:
+                sd = torch.as_tensor(seeds, device=dev).to(torch.int64).contiguous()
+            if sums is None:
+                sums = torch.empty(shape, dtype=torch.float32, device=dev)
+            avg = torch.empty(shape, dtype=torch.float32, device=dev) if want_avg else None
+            rgb = torch.empty(shape, dtype=torch.uint8, device=dev) if want_rgb else None
+            N.check(N.lib().sq_raytrace_rays_device(
+                self._h, o.data_ptr(), d.data_ptr(), sd.data_ptr(), n, k_begin, k_end, sums.data_ptr(),
+                avg.data_ptr() if avg is not None else None, rgb.data_ptr() if rgb is not None else None,
+                C.c_void_p(st.cuda_stream)))
+        return Radiance(sums, avg, rgb)
+
+    def raycast(self, origins, directions, stream=None):
+        """Lib.raycast of each ray (sq_raycast_rays_device, the light at (0, 3, -1)): a float32 CUDA tensor [..., 3], zeros for a
+        miss or a shadowed point.  origins, directions as in `intersect`."""
+        shape = _ray_shape(origins, directions)
+        dev = torch.device("cuda", self.device)
+        st = stream if stream is not None else torch.cuda.current_stream(dev)
+        with torch.cuda.stream(st):
+            o = torch.as_tensor(origins, device=dev).to(torch.float32).contiguous()
+            d = torch.as_tensor(directions, device=dev).to(torch.float32).contiguous()
+            rad = torch.empty(shape, dtype=torch.float32, device=dev)
+            N.check(N.lib().sq_raycast_rays_device(self._h, o.data_ptr(), d.data_ptr(), _lead_count(shape[:-1]), rad.data_ptr(),
+                                                   C.c_void_p(st.cuda_stream)))
+        return rad
 
     def enable_timing(self, on=True):
         """Bracket every launch of the dominant kernel with hipEvents (read back by kernel_timing)."""
