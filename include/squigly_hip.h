@@ -79,7 +79,8 @@ int sq_render_f32(const sq_scene* scene, const sq_camera* cam, int32_t samples, 
 
 /* Frame workspaces (15 GB for a 1080p frame at 256 spp, at most 24 GB) are kept, one block per device, when a scene is
  * freed, so that repeated one-shot calls do not re-allocate them (a hipMalloc right after the hipFree of a block
- * that large can wait seconds for the driver to scrub it).  This hands them back to the driver. */
+ * that large can wait seconds for the driver to scrub it).  So is the largest table of generator words (option "rng_table_mb"),
+ * filled as it is: its entries do not depend on the scene.  This hands them back to the driver. */
 void sq_release_cached_memory(void);
 
 /* ---- resident API: scene stays in HBM, output stays on the device (bench, multi-GPU) ---- */
@@ -304,9 +305,25 @@ int  sq_get_stats(sq_device_scene* s, uint64_t* out, int32_t n, int32_t reset);
  *                        changes; 0: every leaf the reference visits is tested
  *   "primary_tiles"      1 (default): the primary rays of a shard are enumerated in tiles (8 x 8 pixels on a whole image, 2 x 32 with
  *                        row blocks of 2) so that the 64 rays of a wave stay together in both image directions; 0: 64 pixels of a row
+ *   "rng_table_mb"       budget in MiB of the scene's table of generator words (default 24576 = 24 GiB of the 288 GB, 0 = no table).  A
+ *                        sample's three random words are tfgen3(seed), seed = samples * (x + y * w) + k: they depend on nothing but the
+ *                        seed, so a resident scene keeps them, 12 bytes per seed, for the seeds [0, n_cover), n_cover =
+ *                        sq_rng_table_cover(w, h, samples, budget) (squigly_host.h) of the largest frame it has rendered, and the
+ *                        RNG + bounce kernel reads them instead of running Threefish-256 for every sample of every frame; a pixel
+ *                        whose seeds are not all below n_cover computes them as before.  The table is allocated and filled by the
+ *                        first wavefront frame that can use more seeds than it holds (the 1920 x 1080 frame at 256 spp: 943 M seeds =
+ *                        11.3 GB; at 512 spp 22.6 GB; 3840 x 2160 at 1024 spp would take 181 GB and gets the first 24 GiB), always
+ *                        behind the frame workspace, and a failed allocation only means no table.  Radiance queries read the table
+ *                        the scene has and never grow it; the one-shot calls and the one-lane-per-pixel kernels build and read none
  *   "incremental"        only in builds with -DSQ_RES_INCREMENTAL=1 (measured and rejected): the resident form carries
  *                        (tmin, tmax) of the reference's slab test down the tree instead of testing both children from scratch */
 int  sq_set_option(sq_device_scene* s, const char* key, int64_t value);
+
+/* The scene's table of generator words (option "rng_table_mb"; tests and diagnostics): copies the entries [first, first + count) --
+ * three uint32 per seed, tfgen3(seed) -- to the HOST array out_words and returns the number of seeds the table holds; count = 0
+ * only asks for that number (0 = the scene has no table).  Returns -1 (sq_last_error) when the range is not inside the table.
+ * Waits for the table's fill, not for the device. */
+int64_t sq_scene_rng_table(sq_device_scene* s, int64_t first, int64_t count, uint32_t* out_words);
 
 /* The launch plan of the scene's last render or query call (read only; diagnostics and tests): which kernel forms it
  * chose and the sizes they were chosen by.  Filled as the call plans the frame or query, so after a refused call (an error code

@@ -60,6 +60,14 @@ int  sq_cull_boxes(const sq_scene* scene, float* boxes, float ray_limits[3]);
 /* The binary16 encoding the resident kernels keep such a box in: the nearest value >= x (up != 0) or <= x, never subnormal. */
 uint32_t sq_half_outward(float x, int32_t up);
 
+/* The table of generator words of a resident scene (squigly_hip.h, option "rng_table_mb"): how many seeds [0, n_cover) it holds
+ * for a frame of w rows x h columns at `samples` samples under a budget of budget_bytes.  The frame's seeds are
+ * samples * (x + y * w) + k (src/Lib.hs:85-86), so it can use samples * ((w - 1) * w + h) of them -- w * h * samples for a square
+ * frame, more when the frame has more rows than columns, fewer when it has more columns than rows -- and the table holds
+ * budget_bytes / 12 at most: n_cover is the smaller of the two, 0 for a budget below one entry or a non-positive argument.
+ * Pure 64-bit host arithmetic (the product is formed in 128 bits); the device code decides by this very function. */
+int64_t sq_rng_table_cover(int32_t w, int32_t h, int32_t samples, int64_t budget_bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -98,6 +98,10 @@ def lib():
     L.sq_kernel_timing_reset.argtypes = [vp]
     L.sq_kernel_timing_reset.restype = None
     L.sq_set_option.argtypes = [vp, C.c_char_p, C.c_int64]
+    L.sq_scene_rng_table.argtypes = [vp, C.c_int64, C.c_int64, vp]
+    L.sq_scene_rng_table.restype = C.c_int64
+    L.sq_rng_table_cover.argtypes = [i32, i32, i32, C.c_int64]
+    L.sq_rng_table_cover.restype = C.c_int64
     L.sq_get_stats.argtypes = [vp, C.POINTER(C.c_uint64), i32, i32]
     L.sq_last_plan.argtypes = [vp, C.POINTER(Plan)]
     L.sq_debug_eval.argtypes = [i32, i32, vp, vp, C.c_int64, vp]
@@ -175,10 +179,10 @@ EXPORTED_SYMBOLS = [
     # include/squigly_hip.h
     "sq_render_rgb8", "sq_render_f32", "sq_scene_upload", "sq_scene_free", "sq_shard_rows",
     "sq_shard_global_row", "sq_render_rows_device", "sq_render_rows_device_range", "sq_render_rows_device_masked", "sq_adaptive_update_device", "sq_render_views_device", "sq_intersect_rays_device", "sq_camera_rays_device", "sq_raytrace_rays_device", "sq_raycast_rays_device", "sq_kernel_timing", "sq_kernel_timing_reset",
-    "sq_set_option", "sq_get_stats", "sq_last_plan", "sq_debug_eval", "sq_device_count", "sq_abi_version", "sq_build_id", "sq_last_error",
+    "sq_set_option", "sq_scene_rng_table", "sq_get_stats", "sq_last_plan", "sq_debug_eval", "sq_device_count", "sq_abi_version", "sq_build_id", "sq_last_error",
     # include/squigly_host.h
     "sq_mesh_from_obj", "sq_mesh_from_text", "sq_mesh_from_arrays", "sq_mesh_num_tris",
     "sq_mesh_num_materials", "sq_mesh_tris", "sq_mesh_materials", "sq_mesh_free", "sq_camera_from_file",
-    "sq_camera_from_text", "sq_rot_matrix_rads", "sq_release_cached_memory", "sq_mesh_debug_show", "sq_bih_build", "sq_bih_build_device", "sq_cull_boxes", "sq_half_outward", "sq_bih_scene", "sq_bih_height",
+    "sq_camera_from_text", "sq_rot_matrix_rads", "sq_release_cached_memory", "sq_mesh_debug_show", "sq_bih_build", "sq_bih_build_device", "sq_cull_boxes", "sq_half_outward", "sq_rng_table_cover", "sq_bih_scene", "sq_bih_height",
     "sq_bih_num_leaves", "sq_bih_longest_leaf", "sq_bih_free",
 ]

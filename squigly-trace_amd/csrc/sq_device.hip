@@ -479,48 +479,112 @@ __device__ __forceinline__ void store_rad(const Work& W, long long sid, f3 L) {
 }
 __device__ __forceinline__ int2 slot_hit(const float4& org) { return make_int2(__float_as_int(org.x), __float_as_int(org.y)); }   // what the trace kernel left in org.xy
 
+// The scene's table of generator words (sq_device_scene::rng): entry `seed` holds tfgen3(seed) as three words, 12 bytes, for the
+// seeds [0, cover).  A lane reads it in runs of kRngRun consecutive seeds (its pixel's next samples): 48 contiguous bytes.
+constexpr int kRngRun = 4;
+constexpr size_t kRngPad = 256;               // bytes behind the last entry: a run that starts below `cover` is read whole
+struct RngView { const uint32_t* words; long long cover; };   // words = nullptr: no table, every lane computes
+struct RngRun { uint32_t w[3 * kRngRun]; };
+// The run of the seeds [seed, seed + kRngRun): three 16-byte loads when the run is 16-byte aligned (seed % 4 == 0), words otherwise.
+__device__ __forceinline__ RngRun rng_load_run(const uint32_t* words, long long seed) {
+    RngRun r;
+    const uint32_t* p = words + 3 * seed;
+    if ((seed & 3) == 0) {
+        const uint4* q = reinterpret_cast<const uint4*>(p);
+        const uint4 a = q[0], b = q[1], c = q[2];
+        r.w[0] = a.x; r.w[1] = a.y; r.w[2] = a.z; r.w[3] = a.w; r.w[4] = b.x; r.w[5] = b.y; r.w[6] = b.z; r.w[7] = b.w;
+        r.w[8] = c.x; r.w[9] = c.y; r.w[10] = c.z; r.w[11] = c.w;
+    } else {
+#pragma unroll
+        for (int i = 0; i < 3 * kRngRun; ++i) r.w[i] = p[i];
+    }
+    return r;
+}
+// Fills the runs [quad_begin, quad_end) of the table: one thread per run, tfgen3 of its four seeds, three 16-byte stores (a wave
+// writes 3 KB in a row).  The last run may reach into the padding behind the table.
+__global__ void __launch_bounds__(kBlock) sq_rng_fill(uint32_t* words, long long quad_begin, long long quad_end) {
+    for (long long q = quad_begin + (long long)blockIdx.x * kBlock + threadIdx.x; q < quad_end; q += (long long)gridDim.x * kBlock) {
+        uint32_t w[3 * kRngRun];
+#pragma unroll
+        for (int j = 0; j < kRngRun; ++j) sq::tfgen3(q * kRngRun + j, w[3 * j], w[3 * j + 1], w[3 * j + 2]);
+        uint4* o = reinterpret_cast<uint4*>(words + 3 * kRngRun * q);
+        o[0] = make_uint4(w[0], w[1], w[2], w[3]); o[1] = make_uint4(w[4], w[5], w[6], w[7]); o[2] = make_uint4(w[8], w[9], w[10], w[11]);
+    }
+}
+
 // Depth-0 bounce of every sample of the batch: RNG, bounceRay, ray 1 into slot sid (src/Lib.hs:133-134).
 // One thread per active pixel (blockIdx.y splits the samples of a pixel when a frame has few pixels): everything that is
 // the same for every sample of a pixel -- the pixel's coordinates, primary direction, hit point, surface, seed base -- is
 // computed once, not 256 times; consecutive threads still write consecutive slots (sid = k * A + a).
+// The generator words of a sample come from the scene's table R when all the pixel's seeds [rix, rix + samples) lie in it, and
+// from tfgen3 otherwise (no table, a seed row past its cover, a query's negative or huge seed): the same words either way.
+// Neighbouring lanes are neighbouring pixels, samples * 12 bytes apart in the table, so a lane takes its samples in runs of
+// kRngRun (a blockIdx.y gets a contiguous range of runs) and requests the next run before it works on the current one.
 template <int SRC, typename FrameT>
-__device__ __forceinline__ void gen_bounce1_body(const SceneView& S, const FrameT& F, const Work& W, int k_base, int k_count) {
+__device__ __forceinline__ void gen_bounce1_body(const SceneView& S, const FrameT& F, const Work& W, int k_base, int k_count, const RngView R) {
     const int A = *W.n_active;
     diag_aux_wave(W, F.diag, true);
+    const int n_runs = (k_count + kRngRun - 1) / kRngRun, runs_per_y = (n_runs + (int)gridDim.y - 1) / (int)gridDim.y;
+    const int g_begin = min(n_runs, (int)blockIdx.y * runs_per_y), g_end = min(n_runs, g_begin + runs_per_y);
     for (int a = blockIdx.x * kBlock + threadIdx.x; a < A; a += gridDim.x * kBlock) {
         const Pixel0 P = load_pixel0<SRC>(S, F, W, a);
-        const bool absorbing = absorbs(S, P.s0);
         const f3 rad_absorbing = P.s0.surf * sq::mk(0, 0, 0) + P.s0.emit;
         const long long rix = seed_base<SRC>(F, W, a, P);
-        for (int kl = blockIdx.y; kl < k_count; kl += gridDim.y) {
-            const long long sid = (long long)kl * A + a;
-            if (absorbing) {
+        if (absorbs(S, P.s0)) {
+            for (int kl = g_begin * kRngRun; kl < min(k_count, g_end * kRngRun); ++kl) {
+                const long long sid = (long long)kl * A + a;
                 store_rad(W, sid, rad_absorbing);
                 W.state[sid] = kDone;
-                continue;
             }
-            uint32_t n0, n1, n2;
+            continue;
+        }
+        const long long first = rix + k_base;                           // the seed of kl = 0: mkTFGen (rix + k), src/Lib.hs:86
 #ifdef SQ_DIAG_COHERENT   // timing experiment only (WRONG image): every pixel draws the same numbers, so neighbouring rays are parallel
-            sq::tfgen3((long long)(k_base + kl), n0, n1, n2);
+        const bool use = false;
 #else
-            sq::tfgen3(rix + (k_base + kl), n0, n1, n2);                // mkTFGen (rix + k), src/Lib.hs:86
+        const bool use = R.words != nullptr && rix >= 0 && rix <= R.cover - (long long)F.samples;
 #endif
-            if (!scatters(P.s0, n0)) {                                  // mirror: traced once per pixel (sq_mirror1_*); the slot only carries n1, n2
-                W.state[sid] = kMirror;
-                *reinterpret_cast<float2*>(reinterpret_cast<float*>(W.org + sid) + 2) = make_float2(__uint_as_float(n2), __uint_as_float(n1));   // .z = n2, .w = n1
-                continue;
+        RngRun next{};
+        if (use && g_begin < g_end) next = rng_load_run(R.words, first + (long long)g_begin * kRngRun);
+        for (int g = g_begin; g < g_end; ++g) {
+            RngRun cur = next;
+            if (use && g + 1 < g_end) next = rng_load_run(R.words, first + (long long)(g + 1) * kRngRun);
+#pragma unroll 1                                                   // one copy of the sample's code: unrolled, four Threefish blocks interleave into 256 VGPRs
+            for (int kl = g * kRngRun; kl < min(k_count, (g + 1) * kRngRun); ++kl) {
+                const long long sid = (long long)kl * A + a;
+                uint32_t n0, n1, n2;
+                if (use) {                                              // the run's first entry, then the run moves up by one
+                    n0 = cur.w[0]; n1 = cur.w[1]; n2 = cur.w[2];
+#pragma unroll
+                    for (int i = 0; i + 3 < 3 * kRngRun; ++i) cur.w[i] = cur.w[i + 3];
+                } else {
+#ifdef SQ_DIAG_COHERENT
+                    sq::tfgen3((long long)(k_base + kl), n0, n1, n2);
+#else
+                    // the seed steps by one per iteration; seen as such, the optimiser turns the Threefish block's seed-dependent
+                    // sums into induction variables of this loop (256 VGPRs and scratch): the empty asm hides the recurrence
+                    long long seed = first + kl;
+                    asm volatile("" : "+v"(seed));
+                    sq::tfgen3(seed, n0, n1, n2);
+#endif
+                }
+                if (!scatters(P.s0, n0)) {                              // mirror: traced once per pixel (sq_mirror1_*); the slot only carries n1, n2
+                    W.state[sid] = kMirror;
+                    *reinterpret_cast<float2*>(reinterpret_cast<float*>(W.org + sid) + 2) = make_float2(__uint_as_float(n2), __uint_as_float(n1));   // .z = n2, .w = n1
+                    continue;
+                }
+                const f3 d1 = scatter_dir(P.d0, P.s0, n0, n1);
+                W.state[sid] = kRay1;
+                W.org[sid] = make_float4(P.p0.x, P.p0.y, P.p0.z, __uint_as_float(n1));
+                W.dir[sid] = make_float4(d1.x, d1.y, d1.z, __uint_as_float(n2));
             }
-            const f3 d1 = scatter_dir(P.d0, P.s0, n0, n1);
-            W.state[sid] = kRay1;
-            W.org[sid] = make_float4(P.p0.x, P.p0.y, P.p0.z, __uint_as_float(n1));
-            W.dir[sid] = make_float4(d1.x, d1.y, d1.z, __uint_as_float(n2));
         }
     }
     diag_aux_wave(W, F.diag, false);
 }
 template <bool MV>
-__global__ void __launch_bounds__(kBlock) sq_gen_bounce1(const SceneView S, const Frame F, const Work W, int k_base, int k_count) { gen_bounce1_body<MV>(S, F, W, k_base, k_count); }
-__global__ void __launch_bounds__(kBlock) sq_gen_bounce1_rays(const SceneView S, const RayFrame F, const Work W, int k_base, int k_count) { gen_bounce1_body<kSrcRays>(S, F, W, k_base, k_count); }
+__global__ void __launch_bounds__(kBlock, 6) sq_gen_bounce1(const SceneView S, const Frame F, const Work W, int k_base, int k_count, const RngView R) { gen_bounce1_body<MV>(S, F, W, k_base, k_count, R); }
+__global__ void __launch_bounds__(kBlock, 6) sq_gen_bounce1_rays(const SceneView S, const RayFrame F, const Work W, int k_base, int k_count, const RngView R) { gen_bounce1_body<kSrcRays>(S, F, W, k_base, k_count, R); }
 
 // The depth-0 mirror ray of every active pixel, once per frame (slot a = active pixel a).
 // `base`: first of the *n_active slots the mirror rays use (0 when they have a launch of their own, the spare region
@@ -1440,6 +1504,10 @@ __global__ void sq_debug_kernel(int op, const void* a, const void* b, long long 
 // ----------------------------------------------------------------------------------------------
 // Host: scene validation + upload
 // ----------------------------------------------------------------------------------------------
+// A filled table of generator words: entries [0, cover) (RngView), kRngPad bytes of padding behind them.  Nothing writes to a block
+// once it is filled, so a scene that adopts one only has to be ordered after `filled`, the event recorded behind the fill.
+struct RngTable { uint32_t* words = nullptr; size_t bytes = 0; int64_t cover = 0; hipEvent_t filled = nullptr; };
+constexpr int64_t kRngTableDefaultMb = 24576;   // option "rng_table_mb": 24 GiB = 2^31 seeds (squigly_hip.h)
 struct sq_device_scene {
     int device = 0;
     SceneView view{};
@@ -1462,6 +1530,9 @@ struct sq_device_scene {
     // masked calls with second moments: Work::px_sum2, 3 floats per pixel (grow-only; no other call allocates or reads it)
     float* d_px_sum2 = nullptr; int64_t px_sum2_cap = 0;
     int64_t opt_overlap = 0, opt_aux_blocks_per_cu = 0;
+    // the table of generator words (grow-only, allocated after the workspace; ensure_rng_table) and its budget in MB (0 = none)
+    RngTable rng{};
+    int64_t opt_rng_table_mb = kRngTableDefaultMb;
     int64_t opt_pool = 1, opt_refill_min = 12, opt_flush_min = 40, opt_guided = 1, opt_primary_resident = 1, opt_pixel_major = -1, opt_cull = 1, opt_descend_extra = 2, opt_descend_lanes = 16, opt_primary_pooled = 0, opt_coresidency = 0, opt_trace_prio = 0, opt_aux_low_priority = 1, opt_aux_polite = 0, opt_incremental = 1, opt_primary_tiles = 1;
 };
 
@@ -1809,12 +1880,39 @@ void cache_give(int device, void* ptr, size_t bytes) { // keeps the larger block
     }
     if (drop) (void)hipFree(drop);
 }
+// ... and so do the tables of generator words, whose entries do not depend on the scene: the next scene that needs no more
+// seeds than the kept block holds takes it as it is, filled.
+RngTable g_rng_cache[64];
+void rng_free(RngTable& t) {                            // hipFree waits for the device: no kernel still reads the block
+    if (t.words) (void)hipFree(t.words);
+    if (t.filled) (void)hipEventDestroy(t.filled);
+    t = RngTable{};
+}
+bool rng_cache_take(int device, int64_t cover, RngTable* out) {   // a block that holds at least `cover` seeds
+    std::lock_guard<std::mutex> lock(g_cache_mutex);
+    RngTable& c = g_rng_cache[device & 63];
+    if (!c.words || c.cover < cover) return false;
+    *out = c; c = RngTable{};
+    return true;
+}
+void rng_cache_give(int device, RngTable& t) {          // keeps the block with more seeds, frees the other
+    RngTable drop = t;
+    t = RngTable{};
+    {
+        std::lock_guard<std::mutex> lock(g_cache_mutex);
+        RngTable& c = g_rng_cache[device & 63];
+        if (drop.cover > c.cover) std::swap(drop, c);
+    }
+    rng_free(drop);
+}
 }  // namespace
 extern "C" void sq_release_cached_memory(void) {
     for (int d = 0; d < 64; ++d) {
         size_t got = 0;
         void* p = cache_take(d, 0, &got);
-        if (p && hipSetDevice(d) == hipSuccess) (void)hipFree(p);
+        RngTable t;
+        const bool have_table = rng_cache_take(d, 0, &t);
+        if ((p || have_table) && hipSetDevice(d) == hipSuccess) { (void)hipFree(p); rng_free(t); }
     }
 }
 
@@ -1824,6 +1922,7 @@ extern "C" void sq_scene_free(sq_device_scene* s) {
     for (auto& p : s->pending) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
     (void)hipFree(s->d_arena);
     if (s->d_work) cache_give(s->device, s->d_work, s->work_bytes);
+    if (s->rng.words) rng_cache_give(s->device, s->rng);
     for (hipEvent_t e : s->events) (void)hipEventDestroy(e);
     if (s->aux) (void)hipStreamDestroy(s->aux);
     (void)hipFree(s->d_cams);
@@ -1875,6 +1974,10 @@ int ensure_workspace(sq_device_scene* s, int64_t pixels, int64_t slots) {
         if (hipMalloc(&s->d_work, off) == hipSuccess) break;
         (void)hipGetLastError();
         s->d_work = nullptr;
+        // the workspace comes first: the tables of generator words (this scene's, the kept one) go before the slots are halved
+        RngTable kept;
+        const bool have_kept = rng_cache_take(s->device, 0, &kept);
+        if (s->rng.words || have_kept) { rng_free(s->rng); rng_free(kept); continue; }
         if (slots <= pixels) return sq_set_error("hipMalloc(%zu B) for the frame workspace failed", off);
         slots = std::max<int64_t>(pixels, slots / 2);
     }
@@ -1890,6 +1993,41 @@ int ensure_workspace(sq_device_scene* s, int64_t pixels, int64_t slots) {
     W.slot_capacity = slots;
     s->work_bytes = block_bytes; s->work_pixels = pixels; s->work_slots = slots;
     return 0;
+}
+
+// The table of generator words a frame of F's shape reads on `stream`: the scene's table, grown first -- behind the workspace, so it
+// never takes memory the workspace wanted -- when the frame can use more seeds than it holds (sq_rng_table_cover).  A larger table
+// is a new block filled from seed 0: keeping the old entries would need a copy as long as both blocks live, a fill costs about
+// 2 ms per 100 M seeds, and a scene grows its table once per larger frame shape.  Failing to allocate is not an error: the scene
+// keeps the table it has (or none), and the lanes it does not cover compute their words.  grow = false (a radiance query, whose
+// seeds the host does not know) takes the table as it is.
+RngView ensure_rng_table(sq_device_scene* s, const Frame& F, hipStream_t stream, bool grow) {
+    const int64_t budget = s->opt_rng_table_mb << 20;
+    if (budget <= 0) return RngView{ nullptr, 0 };
+    RngTable& T = s->rng;
+    const int64_t want = grow ? sq_rng_table_cover(F.w, F.h, F.samples, budget) : 0;
+    if (want > T.cover) {
+        RngTable N;
+        if (!rng_cache_take(s->device, want, &N)) {
+            N.cover = want;
+            N.bytes = (size_t)want * 12 + kRngPad;
+            const long long quads = (want + kRngRun - 1) / kRngRun;
+            static_assert(kRngPad >= 12 * kRngRun, "the last run of a table is filled and read whole");
+            if (hipMalloc((void**)&N.words, N.bytes) != hipSuccess || hipEventCreateWithFlags(&N.filled, hipEventDisableTiming) != hipSuccess) {
+                (void)hipGetLastError();
+                rng_free(N);
+            } else {
+                const long long blocks = std::min<long long>((quads + kBlock - 1) / kBlock, (long long)s->n_cu * 64);
+                hipLaunchKernelGGL(sq_rng_fill, dim3((unsigned)blocks), dim3(kBlock), 0, stream, N.words, 0ll, quads);
+                if (hipGetLastError() != hipSuccess || hipEventRecord(N.filled, stream) != hipSuccess) { (void)hipGetLastError(); rng_free(N); }
+            }
+        }
+        if (N.words) { rng_free(T); T = N; }        // the old block: freed once the device is idle, so no earlier frame still reads it
+    }
+    if (!T.words) return RngView{ nullptr, 0 };
+    // whichever stream filled the block (this scene's earlier frame, another scene's): this frame's reads come after the fill
+    if (hipStreamWaitEvent(stream, T.filled, 0) != hipSuccess) { (void)hipGetLastError(); return RngView{ nullptr, 0 }; }
+    return RngView{ T.words, (long long)std::min<int64_t>(T.cover, budget / 12) };
 }
 
 // The camera table of a multi-view frame: room for n views (grow-only).  Growing frees the old table, which waits for the
@@ -2146,6 +2284,7 @@ int launch_frame(sq_device_scene* s, const typename SrcKernels<StackT, SRC>::Fra
     P.launched = 1;                                                    // planned; what follows fails only on HIP errors
     // nothing is enqueued before this point, so a refusal above leaves every buffer as it was
     if (stage_cams(s, F, cams, stream)) return 1;                       // multi-view: before every kernel that reads the table (e_setup below)
+    const RngView R = ensure_rng_table(s, F, stream, SRC != kSrcRays);   // allocated behind the workspace; its fill and the wait for it come before every sq_gen_bounce1 (e_setup below)
     // (a masked call's dead pixels keep what they hold: its primary kernels write the black of the live misses, store_live_miss)
     if (F.out_avg && !ad) SQ_HIP(hipMemsetAsync(F.out_avg, 0, (size_t)pixels * 3 * sizeof(float), stream));   // pixels whose primary ray misses: black
     if (F.out_rgb && !ad) SQ_HIP(hipMemsetAsync(F.out_rgb, 0, (size_t)pixels * 3, stream));
@@ -2218,7 +2357,7 @@ int launch_frame(sq_device_scene* s, const typename SrcKernels<StackT, SRC>::Fra
         for (int i = 0; i < n_real; ++i) {
             const int k0 = k0_of(i), kc = kc_of(i);
             SQ_HIP(hipMemsetAsync(W.head[0], 0, 32 * sizeof(int32_t), stream));     // both dequeue cursors
-            hipLaunchKernelGGL(K::gen_bounce1, pp_grid(kc), dim3(kBlock), 0, stream, S, F, W, k0, kc);
+            hipLaunchKernelGGL(K::gen_bounce1, pp_grid(kc), dim3(kBlock), 0, stream, S, F, W, k0, kc, R);
             SQ_HIP(hipGetLastError());
             const bool front = mirror_rides && i == 0;
             if (front) hipLaunchKernelGGL(K::mirror1_gen, dim3(aux_blocks), dim3(kBlock), 0, stream, S, F, W, (long long)W.slot_capacity);
@@ -2267,7 +2406,7 @@ int launch_frame(sq_device_scene* s, const typename SrcKernels<StackT, SRC>::Fra
             const Work& V = Wt[i & 1];
             const int k0 = k0_of(i), kc = kc_of(i);
             SQ_HIP(hipMemsetAsync(V.head[0], 0, 32 * sizeof(int32_t), on));
-            hipLaunchKernelGGL(K::gen_bounce1, pp_grid(kc), dim3(kBlock), 0, on, S, F, V, k0, kc);
+            hipLaunchKernelGGL(K::gen_bounce1, pp_grid(kc), dim3(kBlock), 0, on, S, F, V, k0, kc, R);
             SQ_HIP(hipGetLastError());
             if (launch_trace(V, kc, 0, on)) return 1;
             hipLaunchKernelGGL(K::shade1, pp_grid(kc), dim3(kBlock), 0, on, S, F, V, kc);
@@ -2292,7 +2431,7 @@ int launch_frame(sq_device_scene* s, const typename SrcKernels<StackT, SRC>::Fra
     auto gen = [&](int i) -> int {                          // on X
         const Work& V = Wt[i & 1];
         SQ_HIP(hipMemsetAsync(V.head[0], 0, 32 * sizeof(int32_t), X));
-        hipLaunchKernelGGL(K::gen_bounce1, pp_grid(kc_of(i)), dim3(kBlock), 0, X, S, F, V, k0_of(i), kc_of(i));
+        hipLaunchKernelGGL(K::gen_bounce1, pp_grid(kc_of(i)), dim3(kBlock), 0, X, S, F, V, k0_of(i), kc_of(i), R);
         SQ_HIP(hipGetLastError());
         SQ_HIP(hipEventRecord(eG[(size_t)i], X));
         return 0;
@@ -2692,6 +2831,22 @@ extern "C" int sq_raycast_rays_device(sq_device_scene* s, const float* d_org, co
     return s->small_index ? radiance_rays<uint16_t>(s, Q, 0, 1, true, stream) : radiance_rays<uint32_t>(s, Q, 0, 1, true, stream);
 }
 
+extern "C" int64_t sq_scene_rng_table(sq_device_scene* s, int64_t first, int64_t count, uint32_t* out_words) {
+    if (!s) { sq_set_error("null argument"); return -1; }
+    const int64_t cover = s->rng.words ? s->rng.cover : 0;
+    if (count == 0) return cover;
+    if (!out_words || first < 0 || count < 0 || first > cover || count > cover - first) {
+        sq_set_error("entries [%lld, %lld + %lld) are not in the scene's table of %lld seeds", (long long)first, (long long)first, (long long)count, (long long)cover);
+        return -1;
+    }
+    if (hipSetDevice(s->device) != hipSuccess || hipEventSynchronize(s->rng.filled) != hipSuccess ||
+        hipMemcpy(out_words, s->rng.words + 3 * first, (size_t)count * 12, hipMemcpyDeviceToHost) != hipSuccess) {
+        sq_set_error("copying the table's entries failed: %s", hipGetErrorString(hipGetLastError()));
+        return -1;
+    }
+    return cover;
+}
+
 extern "C" int sq_kernel_timing(sq_device_scene* s, double* avg_ms, int64_t* launches, const char** name) {
     if (!s) return sq_set_error("null argument");
     SQ_HIP(hipSetDevice(s->device));
@@ -2740,6 +2895,7 @@ extern "C" int sq_set_option(sq_device_scene* s, const char* key, int64_t value)
     if (!std::strcmp(key, "lds_node_kb")) { if (value < 0 || value > 128) return sq_set_error("lds_node_kb must be in 0..128"); s->opt_lds_node_kb = value; return 0; }
     if (!std::strcmp(key, "trace_blocks_per_cu")) { if (value < 0 || value > 8) return sq_set_error("trace_blocks_per_cu must be in 0..8"); s->opt_trace_blocks_per_cu = value; return 0; }
     if (!std::strcmp(key, "overlap")) { if (value < 0 || value > 2) return sq_set_error("overlap must be 0, 1 or 2"); s->opt_overlap = value; return 0; }
+    if (!std::strcmp(key, "rng_table_mb")) { if (value < 0 || value > (1ll << 20)) return sq_set_error("rng_table_mb must be in 0..2^20"); s->opt_rng_table_mb = value; return 0; }
     if (!std::strcmp(key, "pool")) { s->opt_pool = value ? 1 : 0; return 0; }
     if (!std::strcmp(key, "guided")) { if (value < 0 || value > 3) return sq_set_error("guided must be in 0..3"); s->opt_guided = value; return 0; }
     if (!std::strcmp(key, "primary_resident")) { s->opt_primary_resident = value ? 1 : 0; return 0; }
@@ -2786,6 +2942,7 @@ int oneshot_part(const sq_scene* scene, const sq_camera* cam, int32_t samples, i
     const auto t0 = now();
     sq_device_scene* s = nullptr;
     if (sq_scene_upload(scene, P.device, &s)) return 1;
+    s->opt_rng_table_mb = 0;                    // one scene per frame: filling a table costs more than the one frame saves
     const auto t1 = now();
     auto t2 = t1, t3 = t1, t4 = t1;
     const size_t npx = (size_t)rows * (size_t)h * 3;

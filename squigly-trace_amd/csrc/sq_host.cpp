@@ -574,3 +574,13 @@ extern "C" uint32_t sq_half_outward(float x, int32_t up_) {
     }
     return neg ? (hb | 0x8000u) : hb;
 }
+
+// Seeds [0, n_cover) that a scene's table of generator words holds for a w x h frame at `samples` (squigly_host.h): what the frame
+// can use -- one past its largest seed, samples * (x + y * w) + samples - 1 at x = h - 1, y = w - 1 (src/Lib.hs:85-86) -- capped by
+// the budget at 12 bytes per seed.  The product is taken in 128 bits: three factors below 2^31 reach 2^93.
+extern "C" int64_t sq_rng_table_cover(int32_t w, int32_t h, int32_t samples, int64_t budget_bytes) {
+    if (w < 1 || h < 1 || samples < 1 || budget_bytes < 12) return 0;
+    const unsigned __int128 span = (unsigned __int128)samples * ((unsigned __int128)(w - 1) * (unsigned __int128)w + (unsigned __int128)h);
+    const unsigned __int128 cap = (unsigned __int128)(budget_bytes / 12);
+    return (int64_t)(span < cap ? span : cap);
+}

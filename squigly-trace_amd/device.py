@@ -100,6 +100,16 @@ class DeviceScene:
         if key == "variant":
             self._variant = int(value)       # which size limit a frame has (_check_frame_size)
 
+    def rng_table(self, first=0, count=0):
+        """sq_scene_rng_table: (seeds the scene's table of generator words holds, its entries [first, first + count) as a uint32
+        numpy array [count, 3])."""
+        import numpy as np
+        out = np.empty((int(count), 3), np.uint32)
+        cover = N.lib().sq_scene_rng_table(self._h, int(first), int(count), out.ctypes.data)
+        if cover < 0:
+            raise N.SquiglyError(N.lib().sq_last_error().decode(errors="replace"))
+        return int(cover), out
+
     def _outputs(self, w, h, shard, want_avg, want_rgb, stream, out_avg, out_rgb, views=None, cast=False, frame=True):
         """(sq_shard, rows, out_avg, out_rgb, stream) of a render_rows* call: the shard's row count, the output tensors
         (allocated unless given or not wanted) and the stream (default: the device's current one).  views: the tensors get a
