@@ -259,7 +259,7 @@ void sq_kernel_timing_reset(sq_device_scene* s);
 int  sq_get_stats(sq_device_scene* s, uint64_t* out, int32_t n, int32_t reset);
 /* Tunables; every setting produces identical bits.  Keys:
  *   "variant"            1 = one-lane-per-pixel kernel, 2 = wavefront pipeline (default)
- *   "slots"              sample slots of the frame workspace (default 512 Mi at 45 B each = 24 GB of the
+ *   "slots"              sample slots of the frame workspace (default 512 Mi at 37 B each = 20 GB of the
  *                        288 GB; a frame with fewer samples allocates only what it needs), 1 .. 2^29: slot numbers and the
  *                        trace kernel's queue cursor are 32-bit
  *   "resident"           1 = keep the whole scene in LDS when it fits (default), 0 = always stream

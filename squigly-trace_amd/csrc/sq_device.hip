@@ -333,25 +333,31 @@ struct Work {                 // device workspace of one frame (HBM)
     // per sample slot sid = k_local * A + a : the ray queue is dense in sid, dead entries are flagged
     uint8_t* state;           // one byte per slot: kDone / kRay1 / kMirror / kRay2.  The trace kernel's refill scan, shade1 and
                               //   sq_accumulate look at this byte first and touch a slot's 32 other bytes only if they need them
-    // 45 bytes per slot (round 2: 61).  A slot's two quads are reused as the sample moves on:
+    // 37 bytes per slot (round 2: 61; 45 while a finished sample's radiance went through HBM).  A slot's two quads are reused as
+    // the sample moves on:
     //   org : ray origin.xyz while the ray waits in the queue; the trace kernel puts the ray's HIT into .xy (t bits, triangle)
     //         when it is done with it -- nothing reads an origin after that (ray 1 starts at the pixel's primary hit point, which
     //         sq_shade1 recomputes).  .w = n1 of the sample's generator until sq_shade1 has used it; a kMirror slot, which holds
     //         no ray of its own, keeps n2 in .z as well.
     //   dir : ray direction.xyz.  .w = n2 of the generator (first bounce level), then the triangle hit by ray 1 (second level).
-    // The radiance of a finished sample keeps an array of its own: folded into the origin quad as well (33 bytes per slot) the
-    // frame measured 0.4 ms slower -- sq_accumulate and sq_shade1 are bound by the bytes they move, and 16-byte records carry
-    // 12 bytes of radiance (profiles/r03f_slots_ab.txt).
+    // A sample that ends at the first bounce level (92 % of them) leaves no radiance in HBM: its radiance is a function of the
+    // pixel's primary surface and of the triangle ray 1 hit (level1_radiance), so sq_shade1 stores that triangle and sq_accumulate,
+    // which holds the primary surface anyway, evaluates it -- 4 bytes written and read where the radiance took 12.  The triangle
+    // keeps a dense array of its own: both kernels are bound by the bytes they move, and read out of the 16-byte origin records
+    // (where the trace kernel left it) it would cost sq_accumulate a whole record per sample (the lesson of
+    // profiles/r03f_slots_ab.txt, where 16-byte records carrying 12 bytes of radiance lost 0.4 ms).
     float4*  org;
     float4*  dir;
-    float*   rad;             // finished sample radiance, 3 floats
+    int32_t* tri1;            // finished sample (kDone): the triangle its ray 1 hit, -1 = a miss.  Not read for the samples of an
+                              //   absorbing pixel, which all finish at depth 0: sq_accumulate sees that from the pixel's surface
     int32_t* head[2];         // dequeue cursors of the persistent trace kernel, one per bounce level
     unsigned long long* stats;  // cumulative trace-kernel statistics (TraceArgs::stats)
     int64_t  slot_capacity;
     float*   px_sum2;         // masked calls that carry second moments: running ordered sum of r * r per active pixel, 3 floats (else nullptr)
 };
 // Slot states.  kRay1 / kRay2: the slot holds a bounce ray of depth 1 / 2 for the trace launch of that level;
-// kMirror: the sample mirrors at depth 0 and shares the pixel's mirror ray (traced once per pixel); kDone: its radiance is in `rad`.
+// kMirror: the sample mirrors at depth 0 and shares the pixel's mirror ray (traced once per pixel); kDone: it ended at the first
+// bounce level (or at depth 0, on an absorbing pixel) and `tri1` says on what.
 constexpr uint8_t kDone = 0, kRay1 = 1, kMirror = 2, kRay2 = 3;
 
 // Diagnostic (option "coresidency", off by default; results unchanged): does a wave of a per-sample kernel run BESIDE the
@@ -474,8 +480,24 @@ __device__ __forceinline__ long long seed_base(const FrameT& F, const Work& W, i
 __device__ __forceinline__ bool absorbs(const SceneView& S, const Surface& s) {
     return S.nonneg_materials && s.surf.x == 0.0f && s.surf.y == 0.0f && s.surf.z == 0.0f;
 }
-__device__ __forceinline__ void store_rad(const Work& W, long long sid, f3 L) {
-    W.rad[3 * sid] = L.x; W.rad[3 * sid + 1] = L.y; W.rad[3 * sid + 2] = L.z;
+// A sample ends at the first bounce level: ray 1 missed (tri1 = -1, raytrace ... 1 = black), or hit triangle tri1 and nothing
+// beyond that hit can add light (an absorbing surface, or no emitter within reach of ray 2).
+__device__ __forceinline__ void finish_level1(const Work& W, long long sid, int tri1) {
+    W.tri1[sid] = tri1;
+    W.state[sid] = kDone;
+}
+// The radiance of a sample whose primary ray hits s0 and ends there: an absorbing pixel, or a first bounce that misses.
+__device__ __forceinline__ f3 level0_radiance(const Surface& s0) { return s0.surf * sq::mk(0, 0, 0) + s0.emit; }
+// ... and of one that finish_level1 ended on a hit: L1 = s1*0 + e1, L0 = s0*L1 + e0 (src/Lib.hs:135-137).  Shade1 is what
+// that takes of the hit triangle's surface record (surface_of), so that the caller can request it ahead.
+struct Shade1 { f3 surf, emit; };
+__device__ __forceinline__ Shade1 shade1_of(const SceneView& S, int tri) {
+    const float4* q = S.surfs + 3 * (size_t)tri;
+    return Shade1{ sq::mk(q[1].x, q[1].y, q[1].z), sq::mk(q[2].x, q[2].y, q[2].z) };
+}
+__device__ __forceinline__ f3 level1_radiance(const Surface& s0, const Shade1& s1) {
+    const f3 L1 = s1.surf * sq::mk(0, 0, 0) + s1.emit;
+    return s0.surf * L1 + s0.emit;
 }
 __device__ __forceinline__ int2 slot_hit(const float4& org) { return make_int2(__float_as_int(org.x), __float_as_int(org.y)); }   // what the trace kernel left in org.xy
 
@@ -528,14 +550,9 @@ __device__ __forceinline__ void gen_bounce1_body(const SceneView& S, const Frame
     const int g_begin = min(n_runs, (int)blockIdx.y * runs_per_y), g_end = min(n_runs, g_begin + runs_per_y);
     for (int a = blockIdx.x * kBlock + threadIdx.x; a < A; a += gridDim.x * kBlock) {
         const Pixel0 P = load_pixel0<SRC>(S, F, W, a);
-        const f3 rad_absorbing = P.s0.surf * sq::mk(0, 0, 0) + P.s0.emit;
         const long long rix = seed_base<SRC>(F, W, a, P);
-        if (absorbs(S, P.s0)) {
-            for (int kl = g_begin * kRngRun; kl < min(k_count, g_end * kRngRun); ++kl) {
-                const long long sid = (long long)kl * A + a;
-                store_rad(W, sid, rad_absorbing);
-                W.state[sid] = kDone;
-            }
+        if (absorbs(S, P.s0)) {                                         // no ray, and nothing else per sample: sq_accumulate knows the pixel absorbs
+            for (int kl = g_begin * kRngRun; kl < min(k_count, g_end * kRngRun); ++kl) W.state[(long long)kl * A + a] = kDone;
             continue;
         }
         const long long first = rix + k_base;                           // the seed of kl = 0: mkTFGen (rix + k), src/Lib.hs:86
@@ -749,7 +766,7 @@ __device__ __forceinline__ void shade1_body(const SceneView S, const FrameT F, c
     struct Second { float4 dir; };                // .w = n2.  Ray 1 starts at the pixel's primary hit point P.p0 (sq_gen_bounce1 stored that very value): no origin is re-read
     for (int a = blockIdx.x * kBlock + threadIdx.x; a < A; a += gridDim.x * kBlock) {
         const Pixel0 P = load_pixel0<SRC>(S, F, W, a);
-        const Surface& s0 = P.s0;
+        if (absorbs(S, P.s0)) continue;                                 // every slot of the pixel is kDone since sq_gen_bounce1
         const f3 d1_mirror = mirror_dir(P.d0, P.s0);
         const int2 hit_mirror = make_int2(__float_as_int(W.px_mt[a]), W.px_mtri[a]);
         const int step = gridDim.y;
@@ -776,18 +793,9 @@ __device__ __forceinline__ void shade1_body(const SceneView S, const FrameT F, c
             if (cur.st == kMirror) { d1 = d1_mirror; p0 = P.p0; hit = hit_mirror; }          // the pixel's mirror ray and its hit
             else { d1 = sq::mk(q.dir.x, q.dir.y, q.dir.z); p0 = P.p0; hit = slot_hit(cur.org); }
             const int tri1 = hit.y;
-            if (tri1 < 0) {                                             // raytrace ... 1 = black
-                store_rad(W, sid, s0.surf * sq::mk(0, 0, 0) + s0.emit);
-                W.state[sid] = kDone;
-                continue;
-            }
+            if (tri1 < 0) { finish_level1(W, sid, -1); continue; }      // raytrace ... 1 = black
             const Surface s1 = surface_of(S, tri1);
-            if (absorbs(S, s1)) {
-                const f3 L1 = s1.surf * sq::mk(0, 0, 0) + s1.emit;
-                store_rad(W, sid, s0.surf * L1 + s0.emit);
-                W.state[sid] = kDone;
-                continue;
-            }
+            if (absorbs(S, s1)) { finish_level1(W, sid, tri1); continue; }
             const f3 p1 = p0 + sq::scale(__int_as_float(hit.x), d1);
             const f3 d2 = bounce_dir(d1, s1, r.x, r.y);                 // gen advanced by one: x = u = p(n1), v = p(n2)
             // Ray 2 is the last one: all it contributes is L2 = s2*0 + e2, the emission of whatever it hits
@@ -803,12 +811,7 @@ __device__ __forceinline__ void shade1_body(const SceneView S, const FrameT F, c
                     float t_unused;
                     may_reach = moller_trumbore(p1, d2, sq::mk(tp[0], tp[1], tp[2]), sq::mk(tp[3], tp[4], tp[5]), sq::mk(tp[6], tp[7], tp[8]), t_unused);
                 }
-                if (!may_reach) {
-                    const f3 L1 = s1.surf * sq::mk(0, 0, 0) + s1.emit;
-                    store_rad(W, sid, s0.surf * L1 + s0.emit);
-                    W.state[sid] = kDone;
-                    continue;
-                }
+                if (!may_reach) { finish_level1(W, sid, tri1); continue; }    // L2 = +0: L1 is what an absorbing s1 gives
             }
             W.state[sid] = kRay2;
             W.org[sid] = make_float4(p1.x, p1.y, p1.z, 0.0f);
@@ -848,39 +851,46 @@ __global__ void __launch_bounds__(kBlock) sq_accumulate(const SceneView S, const
         const Surface s0 = surface_of(S, W.px_tri0[a]);
         // The sum is the reference's left fold over the samples (src/Lib.hs:88): one dependent add per sample.  With fewer active
         // pixels than threads (one rank's share of a frame at 8 ranks) a thread is a chain of `samples` memory round trips and the
-        // launch lasts as long as that chain: there (GROUPED, chosen by the host from the shard's pixel count) the states and radiances of 16 samples are requested together (a slot that
-        // still holds a second bounce ray has no radiance yet; what is read there is not used) and then added in order -- 384 ->
-        // 280 us on such a share.  A whole frame is bound by the bytes it moves and keeps the one-sample-ahead loop (0.83 ms;
-        // the grouped loop takes 0.98 ... 1.58 ms there with groups of 2 ... 16: profiles/r03l_accumulate_groups.txt).
-        if constexpr (GROUPED) {
+        // launch lasts as long as that chain: there (GROUPED, chosen by the host from the shard's pixel count) the states and triangles of 16 samples are requested together, then
+        // their surface records (a slot that still holds a second bounce ray has no triangle yet; what is read there is not used),
+        // and the radiances are added in order -- 384 -> 280 us on such a share when the radiances themselves were read.  A whole
+        // frame is bound by the bytes it moves and keeps a loop with one request per sample (the grouped loop took 0.98 ... 1.58 ms
+        // against 0.83 ms there with groups of 2 ... 16: profiles/r03l_accumulate_groups.txt).
+        const f3 rad0 = level0_radiance(s0);
+        auto add = [&](f3 rad) { sum = sum + rad; if constexpr (MOM2) sum2 = sum2 + rad * rad; };
+        // What a slot says about its finished sample: its state and, for kDone, the triangle of finish_level1.  `at` requests the
+        // surface record for it: triangle 0's where none is needed (a miss, or kRay2, whose tri1 entry is stale), so that the
+        // request does not depend on a branch.
+        struct Fin { uint8_t st; int tri; };
+        auto fin_of = [&](long long sid) { Fin f; f.st = W.state[sid]; f.tri = W.tri1[sid]; return f; };
+        auto hit1 = [](const Fin& f) { return f.st == kDone && f.tri >= 0; };
+        auto at = [&](const Fin& f) { return shade1_of(S, hit1(f) ? f.tri : 0); };
+        if (absorbs(S, s0)) {                                           // every sample ended at depth 0 (sq_gen_bounce1): nothing to read
+            for (int k = 0; k < k_count; ++k) add(rad0);
+        } else if constexpr (GROUPED) {
             constexpr int kAccGroup = 16;
             for (int k0 = 0; k0 < k_count; k0 += kAccGroup) {
-                uint8_t st[kAccGroup]; float rx[kAccGroup], ry[kAccGroup], rz[kAccGroup];
+                Fin f[kAccGroup]; f3 r[kAccGroup];
 #pragma unroll
-                for (int j = 0; j < kAccGroup; ++j) {
-                    const int k = min(k0 + j, k_count - 1);             // past the end: the last sample again, dropped below
-                    const long long sid = (long long)k * A + a;
-                    st[j] = W.state[sid];
-                    rx[j] = W.rad[3 * sid]; ry[j] = W.rad[3 * sid + 1]; rz[j] = W.rad[3 * sid + 2];
-                }
+                for (int j = 0; j < kAccGroup; ++j) f[j] = fin_of((long long)min(k0 + j, k_count - 1) * A + a);   // past the end: the last sample again, dropped below
+#pragma unroll
+                for (int j = 0; j < kAccGroup; ++j) r[j] = hit1(f[j]) ? level1_radiance(s0, at(f[j])) : rad0;
 #pragma unroll
                 for (int j = 0; j < kAccGroup; ++j) {
                     if (k0 + j >= k_count) break;
                     const long long sid = (long long)(k0 + j) * A + a;
-                    const f3 rad = (st[j] == kRay2) ? shade2_radiance(S, W, sid, s0) : sq::mk(rx[j], ry[j], rz[j]);
-                    sum = sum + rad;
-                    if constexpr (MOM2) sum2 = sum2 + rad * rad;
+                    add(f[j].st == kRay2 ? shade2_radiance(S, W, sid, s0) : r[j]);
                 }
             }
         } else {
-            uint8_t st = k_count > 0 ? W.state[a] : kDone;             // the next slot's state is requested one sample ahead
+            Fin next{ kDone, -1 };                                      // the next slot is requested one sample ahead
+            if (k_count > 0) next = fin_of(a);
             for (int k = 0; k < k_count; ++k) {
                 const long long sid = (long long)k * A + a;
-                const uint8_t cur = st;
-                if (k + 1 < k_count) st = W.state[sid + A];
-                const f3 rad = (cur == kRay2) ? shade2_radiance(S, W, sid, s0) : sq::mk(W.rad[3 * sid], W.rad[3 * sid + 1], W.rad[3 * sid + 2]);
-                sum = sum + rad;
-                if constexpr (MOM2) sum2 = sum2 + rad * rad;
+                const Fin cur = next;
+                if (k + 1 < k_count) next = fin_of(sid + A);
+                const Shade1 s1 = at(cur);
+                add(cur.st == kRay2 ? shade2_radiance(S, W, sid, s0) : hit1(cur) ? level1_radiance(s0, s1) : rad0);
             }
         }
         if constexpr (MOM2) {
@@ -1956,7 +1966,7 @@ int ensure_workspace(sq_device_scene* s, int64_t pixels, int64_t slots) {
     auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
     if (s->d_work) { cache_give(s->device, s->d_work, s->work_bytes); s->d_work = nullptr; s->work_pixels = s->work_slots = 0; }
     size_t block_bytes = 0;
-    size_t off = 0, o_cnt = 0, o_stats = 0, o_pix = 0, o_t0 = 0, o_tri0 = 0, o_sum = 0, o_mt = 0, o_mtri = 0, o_state = 0, o_org = 0, o_dir = 0, o_rad = 0;
+    size_t off = 0, o_cnt = 0, o_stats = 0, o_pix = 0, o_t0 = 0, o_tri0 = 0, o_sum = 0, o_mt = 0, o_mtri = 0, o_state = 0, o_org = 0, o_dir = 0, o_tri1 = 0;
     for (;;) {
         off = 0;
         auto take = [&](size_t bytes) { size_t o = off; off += al(bytes); return o; };
@@ -1964,10 +1974,10 @@ int ensure_workspace(sq_device_scene* s, int64_t pixels, int64_t slots) {
         o_pix = take(pixels * 4); o_t0 = take(pixels * 4); o_tri0 = take(pixels * 4); o_sum = take(pixels * 12);
         o_mt = take(pixels * 4); o_mtri = take(pixels * 4);
         // + pixels: the mirror rays' spare region behind the sample slots (state and the two ray quads)
-        o_state = take(slots + pixels); o_org = take((slots + pixels) * 16); o_dir = take((slots + pixels) * 16); o_rad = take(slots * 12);
+        o_state = take(slots + pixels); o_org = take((slots + pixels) * 16); o_dir = take((slots + pixels) * 16); o_tri1 = take(slots * 4);
         // every array has its own, ordered place in the block: a slip here would be a GPU fault, not an error code
         if (!(o_cnt < o_stats && o_stats < o_pix && o_pix < o_t0 && o_t0 < o_tri0 && o_tri0 < o_sum && o_sum < o_mt && o_mt < o_mtri &&
-              o_mtri < o_state && o_state < o_org && o_org < o_dir && o_dir < o_rad && o_rad < off))
+              o_mtri < o_state && o_state < o_org && o_org < o_dir && o_dir < o_tri1 && o_tri1 < off))
             return sq_set_error("internal error: frame workspace layout");
         block_bytes = off;
         if ((s->d_work = cache_take(s->device, off, &block_bytes)) != nullptr) break;
@@ -1989,7 +1999,7 @@ int ensure_workspace(sq_device_scene* s, int64_t pixels, int64_t slots) {
     if (hipMemset(W.stats, 0, kStatSlots * sizeof(unsigned long long)) != hipSuccess) return sq_set_error("hipMemset failed");
     W.px_pixel = (int32_t*)(base + o_pix); W.px_t0 = (float*)(base + o_t0); W.px_tri0 = (int32_t*)(base + o_tri0); W.px_sum = (float*)(base + o_sum);
     W.px_mt = (float*)(base + o_mt); W.px_mtri = (int32_t*)(base + o_mtri);
-    W.state = (uint8_t*)(base + o_state); W.org = (float4*)(base + o_org); W.dir = (float4*)(base + o_dir); W.rad = (float*)(base + o_rad);
+    W.state = (uint8_t*)(base + o_state); W.org = (float4*)(base + o_org); W.dir = (float4*)(base + o_dir); W.tri1 = (int32_t*)(base + o_tri1);
     W.slot_capacity = slots;
     s->work_bytes = block_bytes; s->work_pixels = pixels; s->work_slots = slots;
     return 0;
@@ -2265,7 +2275,7 @@ int launch_frame(sq_device_scene* s, const typename SrcKernels<StackT, SRC>::Fra
     Work Wt[2] = { W, W };
     if (overlap) {
         Work& V = Wt[1];
-        V.state += track_slots; V.org += track_slots; V.dir += track_slots; V.rad += 3 * track_slots;
+        V.state += track_slots; V.org += track_slots; V.dir += track_slots; V.tri1 += track_slots;
         V.head[0] = W.n_active + 64 + 16; V.head[1] = W.n_active + 64 + 32;
     }
     // samples per batch: as many as a track holds, split evenly (few large launches: a small trace launch
@@ -2673,7 +2683,7 @@ int intersect_rays(sq_device_scene* s, const RayQuery& Q, hipStream_t stream) {
     TracePlan TP;
     if (plan_trace<StackT, kSrcCamera>(s, S, stack_cap, TP)) return 1;
     // Chunks of at most `slots` rays (and what the workspace holds; the option caps the slots at 2^29, so a chunk's queue positions and
-    // the trace kernel's 32-bit cursor never overflow).  One slot per ray: 45 B, against 40 B of caller arrays per ray.
+    // the trace kernel's 32-bit cursor never overflow).  One slot per ray: 37 B, against 40 B of caller arrays per ray.
     if (ensure_workspace(s, 1, std::min<int64_t>(s->opt_slots, Q.n))) return 1;
     const Work& W = s->work;
     const long long chunk = std::min<long long>(s->opt_slots, W.slot_capacity);
