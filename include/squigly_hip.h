@@ -315,8 +315,7 @@ int  sq_get_stats(sq_device_scene* s, uint64_t* out, int32_t n, int32_t reset);
  *                        11.3 GB; at 512 spp 22.6 GB; 3840 x 2160 at 1024 spp would take 181 GB and gets the first 24 GiB), always
  *                        behind the frame workspace, and a failed allocation only means no table.  Radiance queries read the table
  *                        the scene has and never grow it; the one-shot calls and the one-lane-per-pixel kernels build and read none
- *   "incremental"        only in builds with -DSQ_RES_INCREMENTAL=1 (measured and rejected): the resident form carries
- *                        (tmin, tmax) of the reference's slab test down the tree instead of testing both children from scratch */
+ *   "incremental"        accepted, no effect: the variant it switched was removed (last built by commit 4abd717) */
 int  sq_set_option(sq_device_scene* s, const char* key, int64_t value);
 
 /* The scene's table of generator words (option "rng_table_mb"; tests and diagnostics): copies the entries [first, first + count) --

@@ -49,10 +49,7 @@ using namespace sqd;
 
 constexpr int kBlock = 256;        // per-pixel / per-sample kernels
 constexpr int kTraceBlock = 512;   // persistent trace kernel, streaming form: 8 waves share one LDS copy of the top of the tree
-#ifndef SQ_RESIDENT_BLOCK
-#define SQ_RESIDENT_BLOCK 1024       // diagnostic builds: 768 / 512 = three / two waves per SIMD (how the frame time follows occupancy)
-#endif
-constexpr int kResidentBlock = SQ_RESIDENT_BLOCK; // persistent trace kernel, resident form: one workgroup per CU owns the whole scene in LDS
+constexpr int kResidentBlock = 1024; // persistent trace kernel, resident form: one workgroup per CU owns the whole scene in LDS
 constexpr int kOneshotRowBlock = 2; // rows per block when a one-shot call shards a frame over devices (balance: squigly-trace_amd/dist.py)
 // Slots a wave reserves from the queue per atomic (multiple of 256 for the resident form).  Every reservation stalls
 // the wave for the atomic's round trip and then for the flag loads of the scan, and a sparse chunk (8 % of the slots
@@ -63,32 +60,17 @@ constexpr int kOneshotRowBlock = 2; // rows per block when a one-shot call shard
 // at the end of the queue makes the tail longer than the stalls it saves (-7 % at 1920x1080@16).
 constexpr int kChunkResident = 512, kChunkStreaming = 128;
 using LiveT = uint8_t;             // a live slot's index within its chunk
-#ifndef SQ_POOL_KW
-#define SQ_POOL_KW 1
-// Instruction-arbitration priority of a trace wave (s_setprio): bits 1..0 in its return / branch steps, bits 3..2 in its leaf scan and pair
-// windows (and the store / refill that follows them).  4 = priority 1 in the windows, 0 in the steps: with the flat steps the headline
-// frame takes 52.4-52.5 ms instead of 53.3-53.4 (levels 1, 2 and 3 alike; raising the STEPS instead costs 0.5 ms), one rank's share at
-// 8 ranks 8.09 -> 7.98 ms, the streaming form +-0 (profiles/r03zz5_setprio_flat.txt, r03zz6_setprio_stream.txt).  Round 2 had measured
-// -0.5 % for the same setting on the kernels of its time and left it off.  -DSQ_SETPRIO=0 builds without it.
-#ifndef SQ_SETPRIO
-#define SQ_SETPRIO 4
-#endif
-#endif
 constexpr int kStatSlots = 32;            // sq_get_stats
-#ifndef SQ_STAGE_BATCHED
-#define SQ_STAGE_BATCHED 1
-#endif
-constexpr int kPoolWindows = SQ_POOL_KW;   // pooled trace kernel: pair windows a wave works on at a time
-#ifndef SQ_POOL_TPL
-#define SQ_POOL_TPL 2
-#endif
-// Pooled trace kernel: triangles a lane tests per window.  Two for the resident form (one owner lookup and one set of pulls
-// serve two tests: 83.0 -> 80.5 ms on the headline frame, same run); one for the streaming form, whose loads want the
-// registers (the 1M-triangle scene loses 14 % with two).
-#ifndef SQ_POOL_TPL_STREAM
-#define SQ_POOL_TPL_STREAM 2
-#endif
-constexpr int kPoolTrisResident = SQ_POOL_TPL, kPoolTrisStreaming = SQ_POOL_TPL_STREAM;
+constexpr int kPoolWindows = 1;    // pooled trace kernel: pair windows a wave works on at a time
+// Instruction-arbitration priority of a trace wave (s_setprio) in its return / branch steps, and in its leaf scan and pair windows (and
+// the store / refill that follows them).  Priority 1 in the windows, 0 in the steps: with the flat steps the headline frame takes
+// 52.4-52.5 ms instead of 53.3-53.4 (levels 1, 2 and 3 alike; raising the STEPS instead costs 0.5 ms), one rank's share at 8 ranks
+// 8.09 -> 7.98 ms, the streaming form +-0 (profiles/r03zz5_setprio_flat.txt, r03zz6_setprio_stream.txt).  Round 2 had measured
+// -0.5 % for the same setting on the kernels of its time and left it off.
+constexpr int kPrioSteps = 0, kPrioWindows = 1;
+// Pooled trace kernel: triangles a lane tests per window.  Two in both forms: one owner lookup and one set of pulls serve two tests
+// (resident form: 83.0 -> 80.5 ms on the headline frame, same run).
+constexpr int kPoolTrisResident = 2, kPoolTrisStreaming = 2;
 
 // ----------------------------------------------------------------------------------------------
 // Frame description shared by the kernels
@@ -556,11 +538,7 @@ __device__ __forceinline__ void gen_bounce1_body(const SceneView& S, const Frame
             continue;
         }
         const long long first = rix + k_base;                           // the seed of kl = 0: mkTFGen (rix + k), src/Lib.hs:86
-#ifdef SQ_DIAG_COHERENT   // timing experiment only (WRONG image): every pixel draws the same numbers, so neighbouring rays are parallel
-        const bool use = false;
-#else
         const bool use = R.words != nullptr && rix >= 0 && rix <= R.cover - (long long)F.samples;
-#endif
         RngRun next{};
         if (use && g_begin < g_end) next = rng_load_run(R.words, first + (long long)g_begin * kRngRun);
         for (int g = g_begin; g < g_end; ++g) {
@@ -575,15 +553,11 @@ __device__ __forceinline__ void gen_bounce1_body(const SceneView& S, const Frame
 #pragma unroll
                     for (int i = 0; i + 3 < 3 * kRngRun; ++i) cur.w[i] = cur.w[i + 3];
                 } else {
-#ifdef SQ_DIAG_COHERENT
-                    sq::tfgen3((long long)(k_base + kl), n0, n1, n2);
-#else
                     // the seed steps by one per iteration; seen as such, the optimiser turns the Threefish block's seed-dependent
                     // sums into induction variables of this loop (256 VGPRs and scratch): the empty asm hides the recurrence
                     long long seed = first + kl;
                     asm volatile("" : "+v"(seed));
                     sq::tfgen3(seed, n0, n1, n2);
-#endif
                 }
                 if (!scatters(P.s0, n0)) {                              // mirror: traced once per pixel (sq_mirror1_*); the slot only carries n1, n2
                     W.state[sid] = kMirror;
@@ -929,7 +903,7 @@ struct TraceArgs {
     int32_t descend_extra, descend_lanes;   // pooled form: further branch steps per iteration for lanes that keep descending, and how many such lanes it takes
     int32_t diag;                // option "coresidency": keep the gauge of live workgroups in stats[24]
     int32_t prio;                // option "trace_prio": s_setprio level of the trace kernel's waves when they start (0 = leave it; the pooled
-                                 //   kernel then sets its own levels per phase, SQ_SETPRIO, so it only lasts in pool = 0 launches), for the overlapped
+                                 //   kernel then sets its own levels per phase, kPrioSteps / kPrioWindows, so it only lasts in pool = 0 launches), for the overlapped
                                  //   schedules: per-sample kernels that share a SIMD with a trace workgroup then only get the issue
                                  //   slots the trace waves leave free
     int32_t pixel_major;         // queue ORDER: 0 = slot order (sample-major: neighbouring pixels, one sample each), 1 = all samples
@@ -969,23 +943,12 @@ __device__ __forceinline__ void stage_resident_scene(const SceneView& S, int n_b
     SQ_LDS v2i* lrefs = to_lds<v2i>(lds + L.refs);
     SQ_LDS v4f* lv = to_lds<v4f>(lds + L.verts);
     SQ_LDS v4us* lt = to_lds<v4us>(lds + L.trix);
-    SQ_LDS v2f* lboxes = to_lds<v2f>(lds + L.quads + 16u * (uint32_t)n_branches);   // kTailLayout: 24-byte boxes behind the 16-byte tails
-    if constexpr (ResidentNodes::kTailLayout) {
-        for (int i = threadIdx.x; i < n_branches; i += BLOCK) {
-            const uint32_t* r = S.rbranch + 10 * (size_t)i;
-            lquads[i] = v4f{ __uint_as_float(r[3]), __uint_as_float(r[7]), __uint_as_float(r[8]), __uint_as_float(r[9]) };
-            lboxes[3 * i] = v2f{ __uint_as_float(r[0]), __uint_as_float(r[1]) };
-            lboxes[3 * i + 1] = v2f{ __uint_as_float(r[2]), __uint_as_float(r[4]) };
-            lboxes[3 * i + 2] = v2f{ __uint_as_float(r[5]), __uint_as_float(r[6]) };
-        }
-    } else
     for (int i = threadIdx.x; i < n_branches; i += BLOCK) {
         const uint32_t* r = S.rbranch + 10 * (size_t)i;
         lquads[i] = v4f{ __uint_as_float(r[0]), __uint_as_float(r[1]), __uint_as_float(r[2]), __uint_as_float(r[3]) };
         lquads[n_branches + i] = v4f{ __uint_as_float(r[4]), __uint_as_float(r[5]), __uint_as_float(r[6]), __uint_as_float(r[7]) };
         lrefs[i] = v2i{ (int)r[8], (int)r[9] };
     }
-#if SQ_STAGE_BATCHED
     // Several loads in flight per thread before the first LDS store (the plain loops wait for every load before the next is issued):
     // a trace launch's staging is on the path of every launch, and a rank's share of a frame at 8 ranks has three launches in 8.5 ms.
     for (int base = threadIdx.x; base < S.n_verts; base += BLOCK * 4) {
@@ -1002,15 +965,8 @@ __device__ __forceinline__ void stage_resident_scene(const SceneView& S, int n_b
 #pragma unroll
         for (int k = 0; k < 8; ++k) { const int i = base + k * BLOCK; if (i < S.n_tris) lt[i] = v4us{ (unsigned short)(t[k].x * 16u), (unsigned short)(t[k].y * 16u), (unsigned short)(t[k].z * 16u), t[k].w }; }
     }
-#else
-    for (int i = threadIdx.x; i < S.n_verts; i += BLOCK) { const float4 v = S.verts4[i]; lv[i] = v4f{ v.x, v.y, v.z, v.w }; }
-    for (int i = threadIdx.x; i < S.n_tris; i += BLOCK) {                  // vertex indices become byte offsets into the vertex table
-        const ushort4 t = S.trix[i];
-        lt[i] = v4us{ (unsigned short)(t.x * 16u), (unsigned short)(t.y * 16u), (unsigned short)(t.z * 16u), t.w };
-    }
-#endif
     if (threadIdx.x < ResidentTris::kRunPad) lt[S.n_tris + threadIdx.x] = v4us{ 0, 0, 0, 0 };
-    N = ResidentNodes{ lquads, lquads + n_branches, lrefs, lboxes, S.cull_child16 != nullptr, S.cull_child16, S.rtail, S.incremental_ok != 0 };
+    N = ResidentNodes{ lquads, lquads + n_branches, lrefs, S.cull_child16 != nullptr, S.cull_child16 };
     G = ResidentTris{ lt };
     if ((uintptr_t)lv != 0) __builtin_trap();                              // the kernels that use this have no static LDS: dynamic LDS starts at address 0
 }
@@ -1079,11 +1035,7 @@ __device__ __forceinline__ void trace_rays_body(const SceneView& S, const TraceA
         root_ref = S.rroot;
     } else {
         for (int i = threadIdx.x; i < 3 * A.n_lds; i += BLOCK) { const float4 q = S.branches[i]; lquads[i] = v4f{ q.x, q.y, q.z, q.w }; }
-#if SQ_STREAM_CULL16
-        N = HybridNodes{ lquads, HybridNodes::kMerged ? S.branches_m : S.branches, (uint32_t)A.n_lds, S.cull_child != nullptr, S.cull_child16 };
-#else
-        N = HybridNodes{ lquads, S.branches, (uint32_t)A.n_lds, S.cull_child != nullptr, S.cull_child };
-#endif
+        N = HybridNodes{ lquads, S.branches_m, (uint32_t)A.n_lds, S.cull_child != nullptr };
         G = GlobalTris{ S.tris, S.leaves, S.packed_leaves != 0, (size_t)S.n_tris * sizeof(DevTri) > ((size_t)4 << 20) };
         root_ref = S.root_ref;
     }
@@ -1168,8 +1120,7 @@ __device__ __forceinline__ void trace_rays_body(const SceneView& S, const TraceA
         // leaf order, with the very comparison of the one-lane leaf loop (minimumBy's rule, src/BIH.hs:105-109) --
         // the arithmetic of mollerTrumbore does not depend on the lane that runs it.
         constexpr int KW = kPoolWindows;
-        constexpr bool kFlat = (RESIDENT ? !ResidentNodes::kBoxInRegisters && !ResidentNodes::kIncremental : (SQ_FLAT_STREAM != 0) && (SQ_STREAM_CULL16 != 0) && !HybridNodes::kBoxInRegisters)
-                               && !PROFILE && (SQ_FLAT_STEPS != 0) && (SQ_DESCEND_PREFETCH == 0);
+        constexpr bool kFlat = RESIDENT && !PROFILE;   // the flat steps (sq_scene.h): the resident form only, DESIGN.md 4.8
         bool flat_ok = false;               // wave-uniform (kFlat): every ray of the wave is safe and the scene has culling boxes
         SQ_LDS uint8_t* tab = to_lds<uint8_t>(lds + L.tab) + (threadIdx.x >> 6) * (64 * KW);   // this wave's window-head tables
         for (int k = 0; k < KW; ++k) tab[k * 64 + lane] = 0;
@@ -1178,7 +1129,6 @@ __device__ __forceinline__ void trace_rays_body(const SceneView& S, const TraceA
         bool carry = false;                 // wave-uniform: the previous iteration left queued pairs untested
         unsigned int pl_hit = 0, pl_hslow = 0;
         TravProf prof{};
-        BranchPf pf; pf.idx = 0xffffffffu; pf.cb_ok = false;   // near-child prefetch (SQ_DESCEND_PREFETCH; unused and optimised away when off)
         // PROFILE: wave time per section of the loop (s_memtime ticks = shader cycles; the stamps themselves cost ~10 %)
         unsigned long long tsec[8] = { 0, 0, 0, 0, 0, 0, 0, 0 }, tlast = PROFILE ? __builtin_amdgcn_s_memtime() : 0;
         auto stamp = [&](int sec) { if (PROFILE) { const unsigned long long now = __builtin_amdgcn_s_memtime(); tsec[sec] += now - tlast; tlast = now; } };
@@ -1196,17 +1146,7 @@ __device__ __forceinline__ void trace_rays_body(const SceneView& S, const TraceA
                 if (exhausted && m == ~0ull) break;
             }
             stamp(0);
-#ifdef SQ_EXTRA_VALU   // timing experiment (results unchanged): N more independent integer VALU instructions per iteration of a wave
-            { int x0 = lane, x1 = lane + 1, x2 = lane + 2, x3 = lane + 3;
-#pragma unroll
-              for (int e = 0; e < SQ_EXTRA_VALU / 4; ++e) {
-                  asm volatile("v_add_u32 %0, %0, %1" : "+v"(x0) : "v"(lane)); asm volatile("v_add_u32 %0, %0, %1" : "+v"(x1) : "v"(lane));
-                  asm volatile("v_add_u32 %0, %0, %1" : "+v"(x2) : "v"(lane)); asm volatile("v_add_u32 %0, %0, %1" : "+v"(x3) : "v"(lane)); }
-              asm volatile("" :: "v"(x0), "v"(x1), "v"(x2), "v"(x3)); }
-#endif
-#if SQ_SETPRIO         // instruction-arbitration priority of a wave in its return / branch steps (results unchanged)
-            __builtin_amdgcn_s_setprio(SQ_SETPRIO & 3);
-#endif
+            __builtin_amdgcn_s_setprio(kPrioSteps);                         // return / branch steps (results unchanged)
             if (PROFILE) pl_unw += (T.mode == M_UNWIND);
             if constexpr (kFlat) {
                 // the return step with three exec regions (the step, COMBINE, FAR) instead of six nested ones: DONE, the pop and the
@@ -1226,9 +1166,9 @@ __device__ __forceinline__ void trace_rays_body(const SceneView& S, const TraceA
             stamp(1);
             if (PROFILE) pl_desc += (T.mode == M_DESCEND);
             if constexpr (kFlat) {
-                if (T.mode == M_DESCEND) { if (flat_ok) trav_descend_flat<NodeSrc, StackT>(T, N, stk, BLOCK); else trav_descend(T, N, stk, BLOCK, &pf); }
+                if (T.mode == M_DESCEND) { if (flat_ok) trav_descend_flat<NodeSrc, StackT>(T, N, stk, BLOCK); else trav_descend(T, N, stk, BLOCK); }
             } else
-            if (T.mode == M_DESCEND) trav_descend(T, N, stk, BLOCK, &pf);
+            if (T.mode == M_DESCEND) trav_descend(T, N, stk, BLOCK);
             // With the culling boxes a ray takes four branch steps per leaf it opens: lanes that are still descending take up
             // to `descend_extra` more steps in this iteration (while at least `descend_lanes` of them are), instead of paying a
             // whole iteration -- return step, leaf scan, windows -- per branch step.
@@ -1236,15 +1176,13 @@ __device__ __forceinline__ void trace_rays_body(const SceneView& S, const TraceA
                 if (__popcll(sq_ballot(T.mode == M_DESCEND)) < A.descend_lanes) break;
                 if (PROFILE) pl_desc += (T.mode == M_DESCEND);
                 if constexpr (kFlat) {
-                    if (T.mode == M_DESCEND) { if (flat_ok) trav_descend_flat<NodeSrc, StackT>(T, N, stk, BLOCK); else trav_descend(T, N, stk, BLOCK, &pf); }
+                    if (T.mode == M_DESCEND) { if (flat_ok) trav_descend_flat<NodeSrc, StackT>(T, N, stk, BLOCK); else trav_descend(T, N, stk, BLOCK); }
                 } else
-                if (T.mode == M_DESCEND) trav_descend(T, N, stk, BLOCK, &pf);
+                if (T.mode == M_DESCEND) trav_descend(T, N, stk, BLOCK);
             }
             stamp(2);
-#if SQ_SETPRIO         // ... and in its leaf scan and pair windows (bits 3..2)
-            __builtin_amdgcn_s_setprio((SQ_SETPRIO >> 2) & 3);
-#endif
-            if constexpr (kFlat && RESIDENT) {                              // open the leaf (src/BIH.hs:105): Nothing so far -- as selects
+            __builtin_amdgcn_s_setprio(kPrioWindows);                       // ... leaf scan and pair windows
+            if constexpr (kFlat) {                                         // open the leaf (src/BIH.hs:105): Nothing so far -- as selects
                 const bool open = T.mode == M_LEAF;                         // (a resident leaf reference decodes without a load)
                 const int2 lf = G.leaf(T.cur);
                 lf_first = open ? lf.x : lf_first; lf_cnt = open ? lf.y : lf_cnt; T.R.tri = open ? -1 : T.R.tri;
@@ -1368,12 +1306,6 @@ __device__ __forceinline__ void trace_rays_body(const SceneView& S, const TraceA
                     tri[k] = p + lane_pull(tb, src);
                     po[k] = sq::mk(lane_pull(T.o.x, src), lane_pull(T.o.y, src), lane_pull(T.o.z, src));
                     pd[k] = sq::mk(lane_pull(T.d.x, src), lane_pull(T.d.y, src), lane_pull(T.d.z, src));
-#ifdef SQ_EXTRA_PULLS   // timing experiment only (results unchanged): what do N more ds_bpermute per window cost, with no VALU attached?
-                    { int sink;
-#pragma unroll
-                      for (int e = 0; e < SQ_EXTRA_PULLS; ++e) asm volatile("ds_bpermute_b32 %0, %1, %2" : "=v"(sink) : "v"(src), "v"(tri[k]));
-                      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-#endif
                     hit[k] = p < P;                                         // so far: the pair exists
                     if (!hit[k]) tri[k] = 0;                                // lanes past the last pair test triangle 0 and drop the answer
                 }
@@ -1543,7 +1475,7 @@ struct sq_device_scene {
     // the table of generator words (grow-only, allocated after the workspace; ensure_rng_table) and its budget in MB (0 = none)
     RngTable rng{};
     int64_t opt_rng_table_mb = kRngTableDefaultMb;
-    int64_t opt_pool = 1, opt_refill_min = 12, opt_flush_min = 40, opt_guided = 1, opt_primary_resident = 1, opt_pixel_major = -1, opt_cull = 1, opt_descend_extra = 2, opt_descend_lanes = 16, opt_primary_pooled = 0, opt_coresidency = 0, opt_trace_prio = 0, opt_aux_low_priority = 1, opt_aux_polite = 0, opt_incremental = 1, opt_primary_tiles = 1;
+    int64_t opt_pool = 1, opt_refill_min = 12, opt_flush_min = 40, opt_guided = 1, opt_primary_resident = 1, opt_pixel_major = -1, opt_cull = 1, opt_descend_extra = 2, opt_descend_lanes = 16, opt_primary_pooled = 0, opt_coresidency = 0, opt_trace_prio = 0, opt_aux_low_priority = 1, opt_aux_polite = 0, opt_primary_tiles = 1;
 };
 
 namespace {
@@ -1781,7 +1713,7 @@ extern "C" int sq_scene_upload(const sq_scene* sc, int32_t device, sq_device_sce
         root_ref = enc(root_ref);
     }
     // Streaming form: branch record + its children's binary16 culling boxes as ONE packed 80-byte record (SceneView::branches_m,
-    // HybridNodes::kMerged).  Measured at 64 spp, same process, as a launch option: 1M-triangle scene
+    // HybridNodes).  Measured at 64 spp, same process, as a launch option: 1M-triangle scene
     // trace launches 23.04 -> 22.62 ms, 82k-triangle scene +-0; the same records padded to one 128-byte line each were 16-21 %
     // SLOWER (26.7 / 23.1 ms): the form lives on what stays in L2, i.e. on the table's footprint, not on lines per visit
     // (profiles/r03t_merged_branches_ab.txt)
@@ -2110,6 +2042,24 @@ template <typename StackT> struct SrcKernels<StackT, kSrcRays> {
     static constexpr auto mirror1_gen = &sq_mirror1_gen_rays;
     static constexpr auto shade1 = &sq_shade1_rays;
 };
+// The kernels of one call's wavefront pipeline, chosen once: the ray source's set; in a masked call (single-view frames only: multi-view
+// frames and queries have no masked form) the AD instantiations of the kernels that decide who is active; and sq_accumulate by second
+// moments and by its loop form.
+template <typename StackT, int SRC> struct PipelineKernels : SrcKernels<StackT, SRC> {
+    using K0 = SrcKernels<StackT, SRC>;
+    std::remove_const_t<decltype(K0::primary)> primary = K0::primary;
+    std::remove_const_t<decltype(K0::primary_resident)> primary_resident = K0::primary_resident;
+    std::remove_const_t<decltype(K0::primary_gen)> primary_gen = K0::primary_gen;
+    void (*primary_store)(Frame, Work, long long);
+    void (*accumulate)(SceneView, Frame, Work, int, int);
+    PipelineKernels(bool ad, bool mom2, bool acc_grouped) {
+        if constexpr (SRC == kSrcCamera) if (ad) {
+            primary_resident = &sq_primary_resident<StackT, false, true>; primary = &sq_primary<StackT, false, true>; primary_gen = &sq_primary_gen<false, true>;
+        }
+        primary_store = ad ? &sq_primary_store<true> : &sq_primary_store<false>;
+        accumulate = mom2 ? (acc_grouped ? &sq_accumulate<true, true> : &sq_accumulate<false, true>) : (acc_grouped ? &sq_accumulate<true> : &sq_accumulate<false>);
+    }
+};
 
 // The persistent trace kernel of a frame's wavefront pipeline or of a ray query: its form and launch geometry (plan_trace).
 struct TracePlan {
@@ -2194,6 +2144,23 @@ int plan_trace(sq_device_scene* s, const SceneView& S, int stack_cap, TracePlan&
     return 0;
 }
 
+// What a frame and an intersection query do first, alike: the scene view with the options applied, the per-lane stacks' size, and the
+// fixed part of s->plan.
+template <typename StackT>
+SceneView begin_plan(sq_device_scene* s, int& stack_cap, size_t& px_lds) {
+    SceneView S = s->view;
+    if (!s->opt_cull) S.cull_o2max = -1.0f;                            // no ray is inside the culling limits: every leaf is tested
+    stack_cap = std::max(S.height, 1);
+    px_lds = (size_t)kBlock * stack_cap * sizeof(StackT);
+    sq_plan& P = s->plan;
+    P = sq_plan{};
+    P.variant = (int32_t)s->opt_variant; P.stack_word_bytes = (int32_t)sizeof(StackT); P.height = S.height; P.stack_cap = stack_cap;
+    P.pixel_lds_bytes = (int32_t)px_lds; P.packed_leaves = S.packed_leaves; P.n_emitters = S.n_emitters;
+    P.trace_form = SQ_FORM_PER_PIXEL; P.primary_form = SQ_PRIMARY_NONE;
+    s->has_plan = true;
+    return S;
+}
+
 // One launch of the planned trace kernel over the queue of W: *W.n_active x kc slots (+ *W.n_active front slots with the mirror
 // rays).  queue_rays x kc sizes its reservations: a frame's pixels (every pixel may be active), a query chunk's rays.
 int launch_trace_kernel(sq_device_scene* s, const SceneView& S, const TracePlan& T, const Work& W, int64_t queue_rays, int kc, int level,
@@ -2225,34 +2192,24 @@ int launch_trace_kernel(sq_device_scene* s, const SceneView& S, const TracePlan&
 // kSrcRays: a chunk of a radiance query (radiance_rays): a frame of one row whose "pixels" are the caller's rays F.ray_org / ray_dir / ray_seed.
 template <typename StackT, int SRC>
 int launch_frame(sq_device_scene* s, const typename SrcKernels<StackT, SRC>::FrameT& F, hipStream_t stream, const sq_camera* cams) {
-    constexpr bool MV = SRC == kSrcViews;
-    using K = SrcKernels<StackT, SRC>;
-    SceneView S = s->view;
-    if (!s->opt_cull) S.cull_o2max = -1.0f;                            // no ray is inside the culling limits: every leaf is tested
-    if (!s->opt_incremental) S.incremental_ok = 0;                     // resident form: every branch step tests both children from the branch's own box
-    const long long pixels = (long long)F.n_views * F.local_rows * F.h;   // every view's pixels, view-major
-    const int stack_cap = std::max(S.height, 1);
-    const size_t px_lds = (size_t)kBlock * stack_cap * sizeof(StackT);
-    const long long px_blocks = (pixels + kBlock - 1) / kBlock;
+    int stack_cap; size_t px_lds;
+    const SceneView S = begin_plan<StackT>(s, stack_cap, px_lds);
     sq_plan& P = s->plan;
-    P = sq_plan{};
-    P.variant = (int32_t)s->opt_variant; P.stack_word_bytes = (int32_t)sizeof(StackT); P.height = S.height; P.stack_cap = stack_cap;
-    P.pixel_lds_bytes = (int32_t)px_lds; P.packed_leaves = S.packed_leaves; P.n_emitters = S.n_emitters;
-    P.trace_form = SQ_FORM_PER_PIXEL; P.primary_form = SQ_PRIMARY_NONE;
-    s->has_plan = true;
+    const long long pixels = (long long)F.n_views * F.local_rows * F.h;   // every view's pixels, view-major
+    const long long px_blocks = (pixels + kBlock - 1) / kBlock;
     // a masked call (sq_render_rows_device_masked with a mask, second moments or counts) takes the AD instantiations of the kernels that
     // decide who is active, and clears no buffer; every other call takes the instantiations, and the memsets, it always took
-    constexpr bool kAD = SRC == kSrcCamera;                            // multi-view frames and queries have no masked form
-    const bool ad = kAD && (F.mask || F.sum2 || F.count);
+    const bool ad = SRC == kSrcCamera && (F.mask || F.sum2 || F.count);
     const bool mom2 = ad && F.sum2;
     if (px_blocks > 0x7fffffffLL) return sq_set_error("image too large for one launch");
     if (px_lds > 160 * 1024) return sq_set_error("BIH height %d needs %zu B of LDS stack per workgroup (max 163840)", S.height, px_lds);
     if (s->opt_variant == 1 || F.cast) {
-        if (px_lds > 64 * 1024) SQ_HIP(hipFuncSetAttribute(ad ? (const void*)sq_render_pixels<StackT, MV, kAD> : (const void*)K::render_pixels, hipFuncAttributeMaxDynamicSharedMemorySize, (int)px_lds));
+        auto render_pixels = SrcKernels<StackT, SRC>::render_pixels;
+        if constexpr (SRC == kSrcCamera) if (ad) render_pixels = &sq_render_pixels<StackT, false, true>;
+        if (px_lds > 64 * 1024) SQ_HIP(hipFuncSetAttribute((const void*)render_pixels, hipFuncAttributeMaxDynamicSharedMemorySize, (int)px_lds));
         P.launched = 1;
         if (stage_cams(s, F, cams, stream)) return 1;
-        if (ad) return timed_launch(s, [&] { hipLaunchKernelGGL((sq_render_pixels<StackT, MV, kAD>), dim3((unsigned)px_blocks), dim3(kBlock), px_lds, stream, S, F); }, "sq_render_pixels", stream);
-        return timed_launch(s, [&] { hipLaunchKernelGGL(K::render_pixels, dim3((unsigned)px_blocks), dim3(kBlock), px_lds, stream, S, F); }, "sq_render_pixels", stream);
+        return timed_launch(s, [&] { hipLaunchKernelGGL(render_pixels, dim3((unsigned)px_blocks), dim3(kBlock), px_lds, stream, S, F); }, "sq_render_pixels", stream);
     }
     // ---- wavefront pipeline ----
     const int n_call = F.k_end - F.k_begin;                              // the samples this call renders (a whole frame: F.samples)
@@ -2285,6 +2242,9 @@ int launch_frame(sq_device_scene* s, const typename SrcKernels<StackT, SRC>::Fra
     const int batch = (n_call + n_batches - 1) / n_batches;
     TracePlan TP;
     if (plan_trace<StackT, SRC>(s, S, stack_cap, TP)) return 1;
+    const int aux_blocks = s->n_cu * (int)(s->opt_aux_blocks_per_cu ? s->opt_aux_blocks_per_cu : 8);
+    // sq_accumulate: the grouped loop when the shard has no more pixels than the launch has threads (every thread at most one pixel)
+    const PipelineKernels<StackT, SRC> K(ad, mom2, pixels <= (long long)aux_blocks * kBlock);
     const bool resident = TP.resident, pool = TP.pool;
     P.primary_form = (s->opt_primary_pooled && pool) ? SQ_PRIMARY_POOLED : (resident && s->opt_primary_resident) ? SQ_PRIMARY_RESIDENT : SQ_PRIMARY_PER_LANE;
     // the per-lane primary pass is one launch with a thread per tile lane, padding included (a narrow frame's edge tiles are mostly
@@ -2299,27 +2259,17 @@ int launch_frame(sq_device_scene* s, const typename SrcKernels<StackT, SRC>::Fra
     if (F.out_avg && !ad) SQ_HIP(hipMemsetAsync(F.out_avg, 0, (size_t)pixels * 3 * sizeof(float), stream));   // pixels whose primary ray misses: black
     if (F.out_rgb && !ad) SQ_HIP(hipMemsetAsync(F.out_rgb, 0, (size_t)pixels * 3, stream));
     SQ_HIP(hipMemsetAsync(W.n_active, 0, 128 * sizeof(int32_t), stream));
-    // primary rays: once per pixel.  With a resident scene they are traced out of LDS as well.
-    const bool primary_pooled = s->opt_primary_pooled && pool;          // ... or through the pooled trace kernel, below
-    if (primary_pooled) {
-    } else if (resident && s->opt_primary_resident) {
+    // primary rays: once per pixel.  With a resident scene they are traced out of LDS as well ...
+    if (P.primary_form == SQ_PRIMARY_RESIDENT) {
         const TraceLds Lp = trace_lds_layout(S.n_branches, true, S.n_verts, S.n_tris, kResidentBlock, stack_cap, (int)sizeof(StackT), false);
-        SQ_HIP(hipFuncSetAttribute(ad ? (const void*)sq_primary_resident<StackT, MV, kAD> : (const void*)K::primary_resident, hipFuncAttributeMaxDynamicSharedMemorySize, (int)Lp.total));
+        SQ_HIP(hipFuncSetAttribute((const void*)K.primary_resident, hipFuncAttributeMaxDynamicSharedMemorySize, (int)Lp.total));
         const long long need = (primary_padded(F) * F.n_views + kResidentBlock - 1) / kResidentBlock;
-        if (ad) hipLaunchKernelGGL((sq_primary_resident<StackT, MV, kAD>), dim3((unsigned)std::min<long long>(s->n_cu, need)), dim3(kResidentBlock), Lp.total, stream, S, F, W, stack_cap);
-        else hipLaunchKernelGGL(K::primary_resident, dim3((unsigned)std::min<long long>(s->n_cu, need)), dim3(kResidentBlock), Lp.total, stream, S, F, W, stack_cap);
-    } else {
-        if (px_lds > 64 * 1024) SQ_HIP(hipFuncSetAttribute(ad ? (const void*)sq_primary<StackT, MV, kAD> : (const void*)K::primary, hipFuncAttributeMaxDynamicSharedMemorySize, (int)px_lds));
-        if (ad) hipLaunchKernelGGL((sq_primary<StackT, MV, kAD>), dim3((unsigned)((primary_padded(F) * F.n_views + kBlock - 1) / kBlock)), dim3(kBlock), px_lds, stream, S, F, W);
-        else hipLaunchKernelGGL(K::primary, dim3((unsigned)((primary_padded(F) * F.n_views + kBlock - 1) / kBlock)), dim3(kBlock), px_lds, stream, S, F, W);
+        hipLaunchKernelGGL(K.primary_resident, dim3((unsigned)std::min<long long>(s->n_cu, need)), dim3(kResidentBlock), Lp.total, stream, S, F, W, stack_cap);
+    } else if (P.primary_form == SQ_PRIMARY_PER_LANE) {
+        if (px_lds > 64 * 1024) SQ_HIP(hipFuncSetAttribute((const void*)K.primary, hipFuncAttributeMaxDynamicSharedMemorySize, (int)px_lds));
+        hipLaunchKernelGGL(K.primary, dim3((unsigned)((primary_padded(F) * F.n_views + kBlock - 1) / kBlock)), dim3(kBlock), px_lds, stream, S, F, W);
     }
     SQ_HIP(hipGetLastError());
-    const int aux_blocks = s->n_cu * (int)(s->opt_aux_blocks_per_cu ? s->opt_aux_blocks_per_cu : 8);
-    // sq_accumulate: the grouped loop when the shard has no more pixels than the launch has threads (every thread at most one pixel)
-    const bool acc_grouped = pixels <= (long long)aux_blocks * kBlock;
-#define SQ_LAUNCH_ACCUMULATE(...) do { \
-        if (mom2) { if (acc_grouped) hipLaunchKernelGGL((sq_accumulate<true, true>), __VA_ARGS__); else hipLaunchKernelGGL((sq_accumulate<false, true>), __VA_ARGS__); } \
-        else if (acc_grouped) hipLaunchKernelGGL(sq_accumulate<true>, __VA_ARGS__); else hipLaunchKernelGGL(sq_accumulate<false>, __VA_ARGS__); } while (0)
     // per-sample kernels that run one thread per active pixel: x covers the pixels, y splits a pixel's samples when the
     // frame has too few pixels to fill the chip (one rank's share of a frame, small frames)
     auto pp_grid = [&](int kc) {
@@ -2332,30 +2282,13 @@ int launch_frame(sq_device_scene* s, const typename SrcKernels<StackT, SRC>::Fra
         const long long ks = std::max<long long>(1, std::min<long long>(std::min(kc, 64), (want_threads + pixels - 1) / std::max<long long>(pixels, 1)));
         return dim3((unsigned)bx, (unsigned)ks);
     };
-    auto launch_trace = [&](const Work& W, int kc, int level, hipStream_t on, bool with_mirror_rays = false) -> int {
-        return launch_trace_kernel(s, S, TP, W, pixels, kc, level, on, with_mirror_rays);
-    };
-    if (primary_pooled) {
+    if (P.primary_form == SQ_PRIMARY_POOLED) {                          // ... or through the pooled trace kernel
         Work Wp = W; Wp.n_active = W.n_active + 48;                     // the launch's queue is the shard's pixels, not the active ones
         SQ_HIP(hipMemsetAsync(W.head[0], 0, 32 * sizeof(int32_t), stream));
-        if (ad) hipLaunchKernelGGL((sq_primary_gen<MV, kAD>), dim3(aux_blocks), dim3(kBlock), 0, stream, F, W, pixels);
-        else hipLaunchKernelGGL(K::primary_gen, dim3(aux_blocks), dim3(kBlock), 0, stream, F, W, pixels);
+        hipLaunchKernelGGL(K.primary_gen, dim3(aux_blocks), dim3(kBlock), 0, stream, F, W, pixels);
         SQ_HIP(hipGetLastError());
-        if (launch_trace(Wp, 1, 0, stream)) return 1;
-        if (ad) hipLaunchKernelGGL(sq_primary_store<kAD>, dim3(aux_blocks), dim3(kBlock), 0, stream, F, W, pixels);
-        else hipLaunchKernelGGL(sq_primary_store<false>, dim3(aux_blocks), dim3(kBlock), 0, stream, F, W, pixels);
-        SQ_HIP(hipGetLastError());
-    }
-    // once per frame: the depth-0 mirror ray of every active pixel (reused by every sample that mirrors).  In the plain
-    // schedule these rays ride at the head of the first batch's first bounce launch (slots behind the sample slots,
-    // dequeued first); the overlapped schedules give them a launch of their own, before the tracks split.
-    const bool mirror_rides = !overlap;
-    if (!mirror_rides) {
-        SQ_HIP(hipMemsetAsync(W.head[0], 0, 32 * sizeof(int32_t), stream));
-        hipLaunchKernelGGL(K::mirror1_gen, dim3(aux_blocks), dim3(kBlock), 0, stream, S, F, W, 0ll);
-        SQ_HIP(hipGetLastError());
-        if (launch_trace(W, 1, 0, stream)) return 1;
-        hipLaunchKernelGGL(sq_mirror1_store, dim3(aux_blocks), dim3(kBlock), 0, stream, W, 0ll);
+        if (launch_trace_kernel(s, S, TP, Wp, pixels, 1, 0, stream, false)) return 1;
+        hipLaunchKernelGGL(K.primary_store, dim3(aux_blocks), dim3(kBlock), 0, stream, F, W, pixels);
         SQ_HIP(hipGetLastError());
     }
     // batch i holds the samples [k0_of(i), k0_of(i) + kc_of(i)) of [k_begin, k_end); the call's last batch ends the fold (sq_accumulate)
@@ -2363,25 +2296,49 @@ int launch_frame(sq_device_scene* s, const typename SrcKernels<StackT, SRC>::Fra
     auto kc_of = [&](int i) { return std::max(0, std::min(batch, n_call - i * batch)); };
     int n_real = 0;
     while (n_real < n_batches && kc_of(n_real) > 0) ++n_real;
+    // The steps of batch i, each on the stream `on` and over the batch's track Wt[i & 1]; the schedules below say only which stream a
+    // step goes on and which events order it.
+    auto launched = []() -> int { SQ_HIP(hipGetLastError()); return 0; };
+    auto gen = [&](int i, hipStream_t on) -> int {
+        SQ_HIP(hipMemsetAsync(Wt[i & 1].head[0], 0, 32 * sizeof(int32_t), on));     // both dequeue cursors
+        hipLaunchKernelGGL(K.gen_bounce1, pp_grid(kc_of(i)), dim3(kBlock), 0, on, S, F, Wt[i & 1], k0_of(i), kc_of(i), R);
+        return launched();
+    };
+    auto trace = [&](int i, int level, hipStream_t on, bool with_mirror) -> int { return launch_trace_kernel(s, S, TP, Wt[i & 1], pixels, kc_of(i), level, on, with_mirror); };
+    auto shade = [&](int i, hipStream_t on) -> int {
+        hipLaunchKernelGGL(K.shade1, pp_grid(kc_of(i)), dim3(kBlock), 0, on, S, F, Wt[i & 1], kc_of(i));
+        return launched();
+    };
+    auto accumulate = [&](int i, hipStream_t on, bool last) -> int {     // in batch order: the per-pixel sum is ordered (src/Lib.hs:88)
+        hipLaunchKernelGGL(K.accumulate, dim3(aux_blocks), dim3(kBlock), 0, on, S, F, Wt[i & 1], kc_of(i), last ? 1 : 0);
+        return launched();
+    };
+    // Once per frame, on the caller's stream: the depth-0 mirror ray of every active pixel (reused by every sample that mirrors),
+    // generated into the slots from `base` on and, once traced, stored per pixel.
+    auto mirror_gen = [&](long long base) -> int {
+        hipLaunchKernelGGL(K.mirror1_gen, dim3(aux_blocks), dim3(kBlock), 0, stream, S, F, W, base);
+        return launched();
+    };
+    auto mirror_store = [&](long long base) -> int {
+        hipLaunchKernelGGL(sq_mirror1_store, dim3(aux_blocks), dim3(kBlock), 0, stream, W, base);
+        return launched();
+    };
     if (!overlap) {
+        // Plain schedule: everything on the caller's stream, batch after batch.  The mirror rays ride in front of batch 0, level 0
+        // (slots behind the sample slots, dequeued first) instead of having a launch, and a ramp-down, of their own.
+        const long long front = (long long)W.slot_capacity;
         for (int i = 0; i < n_real; ++i) {
-            const int k0 = k0_of(i), kc = kc_of(i);
-            SQ_HIP(hipMemsetAsync(W.head[0], 0, 32 * sizeof(int32_t), stream));     // both dequeue cursors
-            hipLaunchKernelGGL(K::gen_bounce1, pp_grid(kc), dim3(kBlock), 0, stream, S, F, W, k0, kc, R);
-            SQ_HIP(hipGetLastError());
-            const bool front = mirror_rides && i == 0;
-            if (front) hipLaunchKernelGGL(K::mirror1_gen, dim3(aux_blocks), dim3(kBlock), 0, stream, S, F, W, (long long)W.slot_capacity);
-            for (int level = 0; level < 2; ++level) {
-                if (launch_trace(W, kc, level, stream, front && level == 0)) return 1;
-                if (front && level == 0) hipLaunchKernelGGL(sq_mirror1_store, dim3(aux_blocks), dim3(kBlock), 0, stream, W, (long long)W.slot_capacity);
-                if (level == 0) hipLaunchKernelGGL(K::shade1, pp_grid(kc), dim3(kBlock), 0, stream, S, F, W, kc);
-                SQ_HIP(hipGetLastError());
-            }
-            SQ_LAUNCH_ACCUMULATE( dim3(aux_blocks), dim3(kBlock), 0, stream, S, F, W, kc, (k0 + kc >= F.k_end) ? 1 : 0);
-            SQ_HIP(hipGetLastError());
+            if (gen(i, stream)) return 1;
+            if (i == 0 && mirror_gen(front)) return 1;
+            if (trace(i, 0, stream, i == 0)) return 1;
+            if (i == 0 && mirror_store(front)) return 1;
+            if (shade(i, stream) || trace(i, 1, stream, false) || accumulate(i, stream, i == n_real - 1)) return 1;
         }
         return 0;
     }
+    // The overlapped schedules give the mirror rays a launch of their own, before the tracks split.
+    SQ_HIP(hipMemsetAsync(W.head[0], 0, 32 * sizeof(int32_t), stream));
+    if (mirror_gen(0) || launch_trace_kernel(s, S, TP, W, pixels, 1, 0, stream, false) || mirror_store(0)) return 1;
     if (!s->aux) {
         // The second stream carries the per-sample kernels (overlap 1) or the odd batches (overlap 2).  Lowest priority: when a
         // trace launch and a per-sample kernel become ready together, the trace workgroups (one per CU, all of its LDS) must be
@@ -2413,71 +2370,57 @@ int launch_frame(sq_device_scene* s, const typename SrcKernels<StackT, SRC>::Fra
         SQ_HIP(hipStreamWaitEvent(X, e_setup2, 0));
         for (int i = 0; i < n_real; ++i) {
             const hipStream_t on = (i & 1) ? X : stream;
-            const Work& V = Wt[i & 1];
-            const int k0 = k0_of(i), kc = kc_of(i);
-            SQ_HIP(hipMemsetAsync(V.head[0], 0, 32 * sizeof(int32_t), on));
-            hipLaunchKernelGGL(K::gen_bounce1, pp_grid(kc), dim3(kBlock), 0, on, S, F, V, k0, kc, R);
-            SQ_HIP(hipGetLastError());
-            if (launch_trace(V, kc, 0, on)) return 1;
-            hipLaunchKernelGGL(K::shade1, pp_grid(kc), dim3(kBlock), 0, on, S, F, V, kc);
-            SQ_HIP(hipGetLastError());
-            if (launch_trace(V, kc, 1, on)) return 1;
+            if (gen(i, on) || trace(i, 0, on, false) || shade(i, on) || trace(i, 1, on, false)) return 1;
             if (i > 0) SQ_HIP(hipStreamWaitEvent(on, eAcc[(size_t)i - 1], 0));
-            SQ_LAUNCH_ACCUMULATE( dim3(aux_blocks), dim3(kBlock), 0, on, S, F, V, kc, i == n_real - 1 ? 1 : 0);
-            SQ_HIP(hipGetLastError());
+            if (accumulate(i, on, i == n_real - 1)) return 1;
             SQ_HIP(hipEventRecord(eAcc[(size_t)i], on));
         }
         SQ_HIP(hipEventRecord(e_done2, X));
         SQ_HIP(hipStreamWaitEvent(stream, e_done2, 0));
         return 0;
     }
-    // the four events of a batch: G = its rays are generated, T1 / T2 = a trace level is done, S1 = ray 2 is in the slots
+    // Overlap 1: the trace launches on the caller's stream, the per-sample kernels on X.  The four events of a batch: G = its rays are
+    // generated, T1 / T2 = a trace level is done, S1 = ray 2 is in the slots
     std::vector<hipEvent_t> eG((size_t)n_real), eT1((size_t)n_real), eS1((size_t)n_real), eT2((size_t)n_real);
     for (int i = 0; i < n_real; ++i) if (new_event(&eG[(size_t)i]) || new_event(&eT1[(size_t)i]) || new_event(&eS1[(size_t)i]) || new_event(&eT2[(size_t)i])) return 1;
     hipEvent_t e_setup, e_done;
     if (new_event(&e_setup) || new_event(&e_done)) return 1;
     SQ_HIP(hipEventRecord(e_setup, stream));
     SQ_HIP(hipStreamWaitEvent(X, e_setup, 0));
-    auto gen = [&](int i) -> int {                          // on X
-        const Work& V = Wt[i & 1];
-        SQ_HIP(hipMemsetAsync(V.head[0], 0, 32 * sizeof(int32_t), X));
-        hipLaunchKernelGGL(K::gen_bounce1, pp_grid(kc_of(i)), dim3(kBlock), 0, X, S, F, V, k0_of(i), kc_of(i), R);
-        SQ_HIP(hipGetLastError());
+    auto gen_x = [&](int i) -> int {
+        if (gen(i, X)) return 1;
         SQ_HIP(hipEventRecord(eG[(size_t)i], X));
         return 0;
     };
-    auto trace = [&](int i, int level) -> int {             // on the caller's stream
+    auto trace_s = [&](int i, int level) -> int {
         SQ_HIP(hipStreamWaitEvent(stream, level == 0 ? eG[(size_t)i] : eS1[(size_t)i], 0));
-        if (launch_trace(Wt[i & 1], kc_of(i), level, stream)) return 1;
+        if (trace(i, level, stream, false)) return 1;
         SQ_HIP(hipEventRecord(level == 0 ? eT1[(size_t)i] : eT2[(size_t)i], stream));
         return 0;
     };
-    auto shade1 = [&](int i) -> int {                       // on X
+    auto shade_x = [&](int i) -> int {
         SQ_HIP(hipStreamWaitEvent(X, eT1[(size_t)i], 0));
-        hipLaunchKernelGGL(K::shade1, pp_grid(kc_of(i)), dim3(kBlock), 0, X, S, F, Wt[i & 1], kc_of(i));
-        SQ_HIP(hipGetLastError());
+        if (shade(i, X)) return 1;
         SQ_HIP(hipEventRecord(eS1[(size_t)i], X));
         return 0;
     };
-    auto finish = [&](int i) -> int {                       // on X, in batch order: the per-pixel sum is ordered (src/Lib.hs:88)
+    auto finish_x = [&](int i) -> int {
         SQ_HIP(hipStreamWaitEvent(X, eT2[(size_t)i], 0));
-        SQ_LAUNCH_ACCUMULATE( dim3(aux_blocks), dim3(kBlock), 0, X, S, F, Wt[i & 1], kc_of(i), i == n_real - 1 ? 1 : 0);
-        SQ_HIP(hipGetLastError());
-        if (i + 2 < n_real) return gen(i + 2);              // the track is free again
-        return 0;
+        if (accumulate(i, X, i == n_real - 1)) return 1;
+        return i + 2 < n_real ? gen_x(i + 2) : 0;              // the track is free again
     };
-    if (gen(0)) return 1;
-    if (n_real > 1 && gen(1)) return 1;
+    if (gen_x(0)) return 1;
+    if (n_real > 1 && gen_x(1)) return 1;
     for (int a = 0; a < n_real; a += 2) {
         const int b = a + 1 < n_real ? a + 1 : -1;
-        if (trace(a, 0)) return 1;
-        if (b >= 0 && trace(b, 0)) return 1;
-        if (shade1(a)) return 1;
-        if (b >= 0 && shade1(b)) return 1;
-        if (trace(a, 1)) return 1;
-        if (b >= 0 && trace(b, 1)) return 1;
-        if (finish(a)) return 1;
-        if (b >= 0 && finish(b)) return 1;
+        if (trace_s(a, 0)) return 1;
+        if (b >= 0 && trace_s(b, 0)) return 1;
+        if (shade_x(a)) return 1;
+        if (b >= 0 && shade_x(b)) return 1;
+        if (trace_s(a, 1)) return 1;
+        if (b >= 0 && trace_s(b, 1)) return 1;
+        if (finish_x(a)) return 1;
+        if (b >= 0 && finish_x(b)) return 1;
     }
     SQ_HIP(hipEventRecord(e_done, X));
     SQ_HIP(hipStreamWaitEvent(stream, e_done, 0));
@@ -2510,6 +2453,25 @@ int refuse_frame_size(int64_t n_views, int64_t rows, int64_t h, bool wavefront) 
         return sq_set_error("%lld x %lld pixels exceed 2^29 pixels in one call of the wavefront form (variant 1 and cast frames take 2^31 - 1)", (long long)rows, (long long)h);
     return 0;
 }
+bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + nb && y < x + na;
+}
+// The check every entry point makes of its device buffers: r = the ranges of which no two may overlap (NULL = not given).
+struct NamedRange { const char* name; const void* p; size_t bytes; };
+int refuse_overlaps(const NamedRange* r, int count) {
+    for (int i = 0; i < count; ++i)
+        for (int j = i + 1; j < count; ++j)
+            if (r[i].p && r[j].p && ranges_overlap(r[i].p, r[i].bytes, r[j].p, r[j].bytes))
+                return sq_set_error("%s and %s overlap", r[i].name, r[j].name);
+    return 0;
+}
+// The camera and shard fields of the frame of a shard of `rows` local rows.
+void set_camera(Frame& F, const sq_camera* cam, int32_t w, int32_t h, sq_shard sh, int32_t rows) {
+    std::memcpy(F.cam_pos, cam->pos, sizeof F.cam_pos);
+    std::memcpy(F.cam_rot, cam->rot, sizeof F.cam_rot);
+    F.w = w; F.h = h; F.row_block = sh.row_block; F.shard = sh.shard; F.n_shards = sh.n_shards; F.local_rows = rows;
+}
 // Every render entry point: the samples [k_begin, k_end) of the `samples`-sample frame of n_views cameras (view-major buffers).  d_sum =
 // nullptr (sq_render_rows_device) keeps the fold in the workspace; the caller has checked everything that is specific to its own entry
 // point.  One camera takes the single-view kernels; more take their multi-view instantiations and the scene's camera table.
@@ -2525,21 +2487,14 @@ int render_rows(sq_device_scene* s, const sq_camera* cam, int32_t n_views, int32
     if (refuse_frame_size(n_views, rows, h, s->opt_variant != 1 && !cast)) return 1;   // before any 32-bit product of rows and h, and before the device is touched
     if (d_mask || d_sum2 || d_count) {   // a masked call: no two of its buffers may overlap (a live pixel's stores would be another pixel's mask, count or fold)
         const size_t px = (size_t)rows * (size_t)h;
-        const struct { const char* name; const void* p; size_t bytes; } b[6] = {
-            { "d_mask", d_mask, px }, { "d_sum", d_sum, px * 12 }, { "d_sum2", d_sum2, px * 12 }, { "d_count", d_count, px * 4 },
-            { "d_avg", d_avg, px * 12 }, { "d_rgb", d_rgb, px * 3 } };
-        for (int i = 0; i < 6; ++i) for (int j = i + 1; j < 6; ++j) {
-            if (!b[i].p || !b[j].p) continue;
-            const uintptr_t a0 = (uintptr_t)b[i].p, a1 = a0 + b[i].bytes, c0 = (uintptr_t)b[j].p, c1 = c0 + b[j].bytes;
-            if (a0 < c1 && c0 < a1) return sq_set_error("%s and %s overlap", b[i].name, b[j].name);
-        }
+        const NamedRange b[6] = { { "d_mask", d_mask, px }, { "d_sum", d_sum, px * 12 }, { "d_sum2", d_sum2, px * 12 }, { "d_count", d_count, px * 4 },
+                                  { "d_avg", d_avg, px * 12 }, { "d_rgb", d_rgb, px * 3 } };
+        if (refuse_overlaps(b, 6)) return 1;
     }
     SQ_HIP(hipSetDevice(s->device));
     Frame F{};
-    std::memcpy(F.cam_pos, cam->pos, sizeof F.cam_pos);
-    std::memcpy(F.cam_rot, cam->rot, sizeof F.cam_rot);
-    F.samples = samples; F.w = w; F.h = h; F.cast = cast ? 1 : 0;
-    F.row_block = sh.row_block; F.shard = sh.shard; F.n_shards = sh.n_shards; F.local_rows = rows;
+    set_camera(F, cam, w, h, sh, rows);
+    F.samples = samples; F.cast = cast ? 1 : 0;
     {   // primary-ray tiles: as tall as the adjacency of local rows allows (8 x 8 on a whole image, 2 x 32 with blocks of 2 rows)
         const int rb = sh.n_shards <= 1 ? 8 : sh.row_block;
         F.tile_rows = rb >= 8 && rb % 8 == 0 ? 8 : rb >= 4 && rb % 4 == 0 ? 4 : rb >= 2 && rb % 2 == 0 ? 2 : 1;
@@ -2658,17 +2613,9 @@ RayQuery query_part(const RayQuery& Q, long long c0, long long m) {
 // variant 1 runs the per-lane kernel and the default form runs chunks of stage -> one level of the trace kernel -> store.
 template <typename StackT>
 int intersect_rays(sq_device_scene* s, const RayQuery& Q, hipStream_t stream) {
-    SceneView S = s->view;
-    if (!s->opt_cull) S.cull_o2max = -1.0f;                            // as in launch_frame
-    if (!s->opt_incremental) S.incremental_ok = 0;
-    const int stack_cap = std::max(S.height, 1);
-    const size_t px_lds = (size_t)kBlock * stack_cap * sizeof(StackT);
+    int stack_cap; size_t px_lds;
+    const SceneView S = begin_plan<StackT>(s, stack_cap, px_lds);
     sq_plan& P = s->plan;
-    P = sq_plan{};
-    P.variant = (int32_t)s->opt_variant; P.stack_word_bytes = (int32_t)sizeof(StackT); P.height = S.height; P.stack_cap = stack_cap;
-    P.pixel_lds_bytes = (int32_t)px_lds; P.packed_leaves = S.packed_leaves; P.n_emitters = S.n_emitters;
-    P.trace_form = SQ_FORM_PER_PIXEL; P.primary_form = SQ_PRIMARY_NONE;
-    s->has_plan = true;
     if (s->opt_variant == 1) {
         if (px_lds > 160 * 1024) return sq_set_error("BIH height %d needs %zu B of LDS stack per workgroup (max 163840)", S.height, px_lds);
         if (px_lds > 64 * 1024) SQ_HIP(hipFuncSetAttribute((const void*)sq_intersect_lanes<StackT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)px_lds));
@@ -2701,10 +2648,6 @@ int intersect_rays(sq_device_scene* s, const RayQuery& Q, hipStream_t stream) {
     }
     return 0;
 }
-bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + nb && y < x + na;
-}
 }  // namespace
 
 extern "C" int sq_intersect_rays_device(sq_device_scene* s, const float* d_org, const float* d_dir, int64_t n,
@@ -2715,12 +2658,8 @@ extern "C" int sq_intersect_rays_device(sq_device_scene* s, const float* d_org, 
     if (!d_org || !d_dir || !d_tri) return sq_set_error("d_org, d_dir and d_tri are required");
     if (n > (INT64_MAX / 12)) return sq_set_error("%lld rays are too many", (long long)n);
     const size_t n3 = (size_t)n * 12, n1 = (size_t)n * 4;
-    const struct { const char* name; const void* p; size_t bytes; } r[5] = {
-        { "d_org", d_org, n3 }, { "d_dir", d_dir, n3 }, { "d_tri", d_tri, n1 }, { "d_dist", d_dist, n1 }, { "d_point", d_point, n3 } };
-    for (int i = 0; i < 5; ++i)
-        for (int j = i + 1; j < 5; ++j)
-            if (r[i].p && r[j].p && ranges_overlap(r[i].p, r[i].bytes, r[j].p, r[j].bytes))
-                return sq_set_error("%s and %s overlap", r[i].name, r[j].name);
+    const NamedRange r[5] = { { "d_org", d_org, n3 }, { "d_dir", d_dir, n3 }, { "d_tri", d_tri, n1 }, { "d_dist", d_dist, n1 }, { "d_point", d_point, n3 } };
+    if (refuse_overlaps(r, 5)) return 1;
     SQ_HIP(hipSetDevice(s->device));
     const RayQuery Q{ d_org, d_dir, d_tri, d_dist, d_point, (long long)n };
     hipStream_t stream = (hipStream_t)hip_stream;
@@ -2738,9 +2677,7 @@ extern "C" int sq_camera_rays_device(sq_device_scene* s, const sq_camera* cam, i
     if (ranges_overlap(d_org, (size_t)total * 12, d_dir, (size_t)total * 12)) return sq_set_error("d_org and d_dir overlap");
     SQ_HIP(hipSetDevice(s->device));
     Frame F{};
-    std::memcpy(F.cam_pos, cam->pos, sizeof F.cam_pos);
-    std::memcpy(F.cam_rot, cam->rot, sizeof F.cam_rot);
-    F.w = w; F.h = h; F.row_block = sh.row_block; F.shard = sh.shard; F.n_shards = sh.n_shards; F.local_rows = rows;
+    set_camera(F, cam, w, h, sh, rows);
     const dim3 grid((unsigned)std::min<long long>((total + kBlock - 1) / kBlock, (long long)s->n_cu * 8));
     hipLaunchKernelGGL(sq_camera_rays, grid, dim3(kBlock), 0, (hipStream_t)hip_stream, F, d_org, d_dir, total);
     SQ_HIP(hipGetLastError());
@@ -2792,15 +2729,6 @@ int radiance_rays(sq_device_scene* s, const RadianceQuery& Q, int32_t k_begin, i
         F.ray_org = C.org; F.ray_dir = C.dir; F.ray_seed = C.seed;
         if (launch_frame<StackT, kSrcRays>(s, F, stream, nullptr)) return 1;
     }
-    return 0;
-}
-// The argument checks the two queries share; r = the ranges that must not overlap (NULL = not given).
-struct NamedRange { const char* name; const void* p; size_t bytes; };
-int refuse_overlaps(const NamedRange* r, int count) {
-    for (int i = 0; i < count; ++i)
-        for (int j = i + 1; j < count; ++j)
-            if (r[i].p && r[j].p && ranges_overlap(r[i].p, r[i].bytes, r[j].p, r[j].bytes))
-                return sq_set_error("%s and %s overlap", r[i].name, r[j].name);
     return 0;
 }
 }  // namespace
@@ -2910,7 +2838,7 @@ extern "C" int sq_set_option(sq_device_scene* s, const char* key, int64_t value)
     if (!std::strcmp(key, "guided")) { if (value < 0 || value > 3) return sq_set_error("guided must be in 0..3"); s->opt_guided = value; return 0; }
     if (!std::strcmp(key, "primary_resident")) { s->opt_primary_resident = value ? 1 : 0; return 0; }
     if (!std::strcmp(key, "cull")) { s->opt_cull = value ? 1 : 0; return 0; }
-    if (!std::strcmp(key, "incremental")) { s->opt_incremental = value ? 1 : 0; return 0; }
+    if (!std::strcmp(key, "incremental")) return 0;   // accepted, no effect: the incremental slab test was removed
     if (!std::strcmp(key, "primary_tiles")) { s->opt_primary_tiles = value ? 1 : 0; return 0; }
     if (!std::strcmp(key, "primary_pooled")) { s->opt_primary_pooled = value != 0; return 0; }
     if (!std::strcmp(key, "coresidency")) { s->opt_coresidency = value != 0; return 0; }
