@@ -50,11 +50,12 @@ typedef struct {
 } sq_scene;
 /* Every lane keeps `height` stack frames in LDS, 2 bytes each when the scene has < 0x8000 branches and < 0x8000 triangles,
  * else 4.  Largest heights, measured (tests/test_gpu_limits.py), with 2 / 4 byte frames:
- *   per-pixel kernel (variant 1, every cast frame)      320 / 160   (256 lanes x height x word <= 160 KB)
+ *   per-pixel kernel (variant 1, cast frames *)         320 / 160   (256 lanes x height x word <= 160 KB)
  *   wavefront pipeline, streaming trace form            158 / 79    (512 lanes; 159 / 79 with option "pool" = 0)
  *   streaming six-wave build (3 workgroups per CU)       46 / 23    (taller trees take the plain build)
  *   resident form                                       whatever leaves the scene itself room in 160 KB (data/scene.obj: 13;
  *                                                       14 with option "pool" = 0)
+ * (*) with option "cast_wavefront" = 1 a cast frame has the wavefront pipeline's limits.
  * A taller tree is refused on the host before any launch: the render call returns non-zero and sq_last_error() says
  * "BIH height H needs N B of LDS ...". */
 
@@ -100,7 +101,7 @@ int32_t sq_shard_global_row(int32_t local_row, sq_shard sh);
  * work on it and returns (no synchronisation).
  * FRAME SIZE.  Pixel indices are 32-bit, so one call -- this one, the range, masked and views calls below -- takes at most
  * 2^31 - 1 pixels (rows * h, times n_views), e.g. 46340 x 46340; buffer offsets are 64-bit, so the buffers of such a call may pass
- * 4 GB.  That is the limit of the per-pixel kernel (option "variant" = 1, and every cast frame).  The wavefront form (the default)
+ * 4 GB.  That is the limit of the per-pixel kernel (option "variant" = 1, and cast frames unless option "cast_wavefront" is 1).  The wavefront form (the default)
  * indexes its active pixels and its ray queue with 32-bit numbers that reach three times the pixel count, and takes at most 2^29
  * pixels per call (536 870 912, e.g. 16384 x 32768), which is also the cap of option "slots".  A larger call is refused before the
  * device is touched, every buffer left as it was: "R x H pixels exceed 2^31 - 1 pixels in one call", or "... exceed 2^29 pixels in
@@ -241,13 +242,43 @@ int sq_camera_rays_device(sq_device_scene* s, const sq_camera* cam, int32_t w, i
 int sq_raytrace_rays_device(sq_device_scene* s, const float* d_org, const float* d_dir, const int64_t* d_seed, int64_t n,
                             int32_t k_begin, int32_t k_end,
                             float* d_sum, float* d_avg, uint8_t* d_rgb, void* hip_stream);
-/* Lib.raycast (src/Lib.hs:141-151, the hard-coded light at (0, 3, -1) included) of each of n rays: d_rad (DEVICE float[n][3],
- * required) receives raycast scene (Ray org_i dir_i), (+0, +0, +0) for a miss or a shadowed point.  No random input and no fold.
- * One kernel, one lane per ray, in every "variant" (as cast frames); launches of at most 2^30 rays.  Refused like
+/* Lib.raycast (src/Lib.hs:141-151) of each of n rays under the scene's lights (sq_scene_set_lights below; the reference's hard-coded
+ * light at (0, 3, -1) unless set): d_rad (DEVICE float[n][3], required) receives T of sq_scene_set_lights -- with the reference's
+ * light, raycast scene (Ray org_i dir_i) -- and (+0, +0, +0) for a miss; a light that is shadowed at the point adds (+0, +0, +0).
+ * No random input and no fold.  One kernel, one lane per ray, in launches of at most 2^30 rays, as cast frames: in "variant" 1, and
+ * in "variant" 2 unless option "cast_wavefront" is 1, which runs chunks of at most `slots` rays as a wavefront instead.  Refused like
  * sq_raytrace_rays_device, minus seeds and ranges: s == NULL, n < 0, n > 0 with d_org, d_dir or d_rad NULL, overlapping ranges,
- * the LDS-height limit of the per-pixel kernel. */
+ * and the LDS-height limit of the form that runs (the per-pixel kernel's; with "cast_wavefront" = 1 the wavefront form's, with its
+ * message). */
 int sq_raycast_rays_device(sq_device_scene* s, const float* d_org, const float* d_dir, int64_t n,
                            float* d_rad, void* hip_stream);
+
+/* Caller-given point lights for the scene's cast computations: sq_render_rows_device, its _range and _masked forms and
+ * sq_render_views_device, each with cast != 0, and sq_raycast_rays_device.  (The one-shot calls upload a scene of their own and keep
+ * the reference's light.)  Under the lights L_0 ... L_{m-1} the radiance T of a ray is raycast (src/Lib.hs:141-151) with the light
+ * made a parameter, every operation a single fp32 operation in this order; `inter` is the ray's intersectBIH, a miss gives
+ * (+0, +0, +0) and evaluates no light:
+ *      p     = intersectPoint inter
+ *      dl_i  = norm (p - pos_i)                                       -- (x*x + y*y) + z*z, sqrt
+ *      sh_i  = intersectBIH (Ray p (pos_i - p))                       -- the direction is not normalised
+ *      lit_i = not (sh_i is a hit and not (dist sh_i > dl_i))         -- a NaN compares false
+ *      c_i   = lit_i ? V3 (power_i.x / dl_i) (power_i.y / dl_i) (power_i.z / dl_i) * surfColor  :  (+0, +0, +0)
+ *      T     = c_0;  T = T + c_i  for i = 1 .. m-1                    -- left fold in the caller's order, shadowed terms added too
+ * and everything after T is as it was: a frame's fold sum = sum + T per sample of [k_begin, k_end), a masked call's
+ * sum2 = sum2 + T * T, avg and the tonemap; a raycast query stores T.  With the single light { (0, 3, -1), (2, 2, 2) } T is bit for
+ * bit the reference's value.  Coordinates and powers are not checked (NaN and infinite values are inputs like any other).
+ *  lights : HOST array of n_lights lights, read during the call only; the scene keeps a copy for sq_scene_get_lights and enqueues
+ *          the update of its device table on hip_stream, so the call is ordered like every other call on the scene (one stream): a
+ *          frame enqueued before it keeps the lights it had.
+ *  lights == NULL && n_lights == 0 restores the reference's light: a scene on which this function was never called, or which was
+ *          reset, launches exactly the kernels it launched before this function existed.
+ * Refused with a message, nothing changed: s == NULL, n_lights < 0, n_lights > 4096, n_lights > 0 with lights == NULL,
+ * n_lights == 0 with lights != NULL. */
+typedef struct { float pos[3]; float power[3]; } sq_light;   /* the reference's light: pos (0, 3, -1), power (2, 2, 2) */
+int     sq_scene_set_lights(sq_device_scene* s, const sq_light* lights, int32_t n_lights, void* hip_stream);
+/* The scene's lights (one, the reference's, unless set): returns the count and copies min(count, cap) of them to the HOST array
+ * out (which may be NULL when cap <= 0); -1 (sq_last_error) for s == NULL. */
+int32_t sq_scene_get_lights(sq_device_scene* s, sq_light* out, int32_t cap);
 
 /* Timing of the dominant kernel measured with hipEvents on the stream it was launched on:
  * average duration in ms over the launches since the last reset, and the launch count. */
@@ -315,6 +346,11 @@ int  sq_get_stats(sq_device_scene* s, uint64_t* out, int32_t n, int32_t reset);
  *                        11.3 GB; at 512 spp 22.6 GB; 3840 x 2160 at 1024 spp would take 181 GB and gets the first 24 GiB), always
  *                        behind the frame workspace, and a failed allocation only means no table.  Radiance queries read the table
  *                        the scene has and never grow it; the one-shot calls and the one-lane-per-pixel kernels build and read none
+ *   "cast_wavefront"     0 (default): cast frames and raycast queries run one lane per ray in one kernel; 1 (with "variant" 2): they run
+ *                        as a wavefront -- the frame's own primary pass, then per batch of lights (as many as the slots hold, at least
+ *                        one) one shadow ray per (active pixel, light) through one level of the planned trace kernel and an ordered
+ *                        fold; frame sizes, tree heights and refusal messages are then the wavefront form's, sq_last_plan reports the
+ *                        planned trace_form and primary_form, and "overlap" is ignored
  *   "incremental"        accepted, no effect: the variant it switched was removed (last built by commit 4abd717) */
 int  sq_set_option(sq_device_scene* s, const char* key, int64_t value);
 
@@ -332,11 +368,11 @@ enum { SQ_FORM_PER_PIXEL = 0, SQ_FORM_RESIDENT = 1, SQ_FORM_STREAMING_SIX_WAVE =
 enum { SQ_PRIMARY_NONE = 0, SQ_PRIMARY_PER_LANE = 1, SQ_PRIMARY_RESIDENT = 2, SQ_PRIMARY_POOLED = 3 };
 typedef struct {
     int32_t launched;          /* 1 = the frame was enqueued, 0 = refused while planning */
-    int32_t variant;           /* option "variant" (a cast frame always runs the per-pixel kernel: trace_form 0) */
+    int32_t variant;           /* option "variant" (a cast frame runs the per-pixel kernel, trace_form 0, unless "cast_wavefront" is 1) */
     int32_t stack_word_bytes;  /* 2 (uint16_t frames: < 0x8000 branches and triangles) or 4 */
     int32_t height;            /* BIH height */
     int32_t stack_cap;         /* frames per lane */
-    int32_t trace_form;        /* SQ_FORM_*; SQ_FORM_PER_PIXEL for variant 1 and cast frames */
+    int32_t trace_form;        /* SQ_FORM_*; SQ_FORM_PER_PIXEL for variant 1 and for cast frames without "cast_wavefront" */
     int32_t blocks_per_cu;     /* trace workgroups per CU (0 with the per-pixel kernel) */
     int32_t n_lds;             /* streaming forms: branches of the tree's top kept in LDS; resident: all branches */
     int32_t trace_lds_bytes;   /* dynamic LDS of one trace workgroup (0 with the per-pixel kernel) */

@@ -37,6 +37,14 @@ class Shard(C.Structure):
     _fields_ = [("row_block", C.c_int32), ("shard", C.c_int32), ("n_shards", C.c_int32)]
 
 
+class Light(C.Structure):
+    """sq_light: a point light, position and RGB power (the reference's: (0, 3, -1), (2, 2, 2))."""
+    _fields_ = [("pos", C.c_float * 3), ("power", C.c_float * 3)]
+
+
+MAX_LIGHTS = 4096      # sq_scene_set_lights refuses more
+
+
 class Plan(C.Structure):
     """sq_plan (include/squigly_hip.h): the launch plan of a scene's last frame."""
     _fields_ = [(n, C.c_int32) for n in ("launched", "variant", "stack_word_bytes", "height", "stack_cap", "trace_form",
@@ -94,6 +102,9 @@ def lib():
     L.sq_camera_rays_device.argtypes = [vp, C.POINTER(Camera), i32, i32, Shard, vp, vp, vp]
     L.sq_raytrace_rays_device.argtypes = [vp, vp, vp, vp, C.c_int64, i32, i32, vp, vp, vp, vp]
     L.sq_raycast_rays_device.argtypes = [vp, vp, vp, C.c_int64, vp, vp]
+    L.sq_scene_set_lights.argtypes = [vp, vp, i32, vp]
+    L.sq_scene_get_lights.argtypes = [vp, vp, i32]
+    L.sq_scene_get_lights.restype = i32
     L.sq_kernel_timing.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_char_p)]
     L.sq_kernel_timing_reset.argtypes = [vp]
     L.sq_kernel_timing_reset.restype = None
@@ -141,6 +152,41 @@ def lib():
     return L
 
 
+# The reference's hard-coded light (src/Lib.hs:141-151) as a row of DeviceScene.lights: position, then RGB power.
+REFERENCE_LIGHT = ((0.0, 3.0, -1.0), (2.0, 2.0, 2.0))
+
+
+def lights_array(lights):
+    """The float32 [n, 6] array (pos, power) of DeviceScene.set_lights' argument: an array-like [n, 6], or a sequence of
+    (pos, power) pairs, power a scalar or three numbers.  SquiglyError for any other shape, no light or more than MAX_LIGHTS."""
+    try:
+        seq = list(lights)
+    except TypeError:
+        raise SquiglyError(f"lights must be an [n, 6] array or a sequence of (pos, power) pairs, got {type(lights).__name__}")
+    if len(seq) == 0:
+        raise SquiglyError("lights must hold at least one light (None restores the reference's light)")
+    if len(seq) > MAX_LIGHTS:
+        raise SquiglyError(f"{len(seq)} lights are too many (at most {MAX_LIGHTS})")
+    rows = []
+    for i, item in enumerate(seq):
+        try:
+            if len(item) == 2:                        # (pos, power)
+                pos = np.asarray(item[0], np.float32).reshape(-1)
+                power = np.asarray(item[1], np.float32).reshape(-1)
+                if power.size == 1:
+                    power = np.repeat(power, 3)
+                row = np.concatenate([pos, power]) if pos.size == 3 and power.size == 3 else None
+            else:
+                row = np.asarray(item, np.float32).reshape(-1)
+        except (TypeError, ValueError):
+            row = None
+        if row is None or row.shape != (6,):
+            raise SquiglyError(f"light {i}: expected (pos, power) with three coordinates and a power of one or three numbers, "
+                               f"or six numbers, got {item!r}")
+        rows.append(row)
+    return np.ascontiguousarray(np.stack(rows), np.float32)
+
+
 OPS = {"sqrt": 0, "div": 1, "sin": 2, "cos": 3, "acos": 4, "atan": 5, "unit_float": 6, "tfgen3": 7, "tonemap": 8, "rcp_sweep": 9, "cull_slab": 10}
 
 
@@ -178,7 +224,7 @@ def check(rc):
 EXPORTED_SYMBOLS = [
     # include/squigly_hip.h
     "sq_render_rgb8", "sq_render_f32", "sq_scene_upload", "sq_scene_free", "sq_shard_rows",
-    "sq_shard_global_row", "sq_render_rows_device", "sq_render_rows_device_range", "sq_render_rows_device_masked", "sq_adaptive_update_device", "sq_render_views_device", "sq_intersect_rays_device", "sq_camera_rays_device", "sq_raytrace_rays_device", "sq_raycast_rays_device", "sq_kernel_timing", "sq_kernel_timing_reset",
+    "sq_shard_global_row", "sq_render_rows_device", "sq_render_rows_device_range", "sq_render_rows_device_masked", "sq_adaptive_update_device", "sq_render_views_device", "sq_intersect_rays_device", "sq_camera_rays_device", "sq_raytrace_rays_device", "sq_raycast_rays_device", "sq_scene_set_lights", "sq_scene_get_lights", "sq_kernel_timing", "sq_kernel_timing_reset",
     "sq_set_option", "sq_scene_rng_table", "sq_get_stats", "sq_last_plan", "sq_debug_eval", "sq_device_count", "sq_abi_version", "sq_build_id", "sq_last_error",
     # include/squigly_host.h
     "sq_mesh_from_obj", "sq_mesh_from_text", "sq_mesh_from_arrays", "sq_mesh_num_tris",

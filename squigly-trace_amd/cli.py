@@ -42,6 +42,19 @@ def nonneg_float(text):
     return v
 
 
+def parse_light(text):
+    """A point light of --light: X,Y,Z (power 2, the reference's), X,Y,Z,P or X,Y,Z,R,G,B -> ((x, y, z), (r, g, b)).  The value may
+    stand in parentheses, (X,Y,Z), which keeps a negative X from looking like an option on the command line."""
+    try:
+        v = [float(t) for t in text.strip("()").split(",")]
+    except ValueError:
+        v = []
+    if len(v) not in (3, 4, 6):
+        raise argparse.ArgumentTypeError("expected X,Y,Z or X,Y,Z,P or X,Y,Z,R,G,B")
+    power = (2.0, 2.0, 2.0) if len(v) == 3 else (v[3],) * 3 if len(v) == 4 else tuple(v[3:])
+    return (tuple(v[:3]), power)
+
+
 def parse_views(text):
     """The cameras of a views file: the reference's camera format (src/Obj.hs:60-70) repeated, each pair of non-blank lines one
     camera (position, then rotation angles).  Raises ValueError for an odd line count, a line that does not parse or no camera."""
@@ -110,6 +123,11 @@ def build_parser():
     p.add_argument("--adaptive-step", type=positive_int, default=8, metavar="N", help="Samples per later step (default 8)")
     p.add_argument("--adaptive-eps", type=nonneg_float, default=1.0, metavar="E", help="Absolute floor of the rule, in squared radiance per channel (default 1.0)")
     p.add_argument("--counts", default=None, metavar="FILE", help="With --adaptive: write the per-pixel sample counts to FILE (.npy, int32)")
+    # not a flag of the reference: where the light of --cast is (the reference's is fixed at 0,3,-1 with power 2)
+    p.add_argument("--light", type=parse_light, action="append", default=None, metavar="X,Y,Z[,P|,R,G,B]",
+                   help="With --cast: a point light at X,Y,Z with power P (default 2) or R,G,B; repeat for several lights, "
+                        "added in the order given (default: one light at 0,3,-1). A value that starts with a minus sign "
+                        "is written --light=-1,2,3 or --light '(-1,2,3)'")
     return p
 
 
@@ -122,6 +140,8 @@ def parse_args(argv=None):
         p.error("--adaptive cannot be combined with --views or --preview-every")
     if a.counts is not None and a.adaptive is None:
         p.error("--counts needs --adaptive")
+    if a.light is not None and not a.cast:
+        p.error("--light needs --cast")
     return a
 
 
@@ -157,23 +177,26 @@ def main(argv=None):
     print("Started at " + time.strftime("%H:%M:%S%p UTC", time.gmtime(t0)).lower().replace("utc", "UTC"))
     os.makedirs(os.path.dirname(os.path.abspath(settings.savePath)), exist_ok=True)
     if a.views is not None:
-        imgs = render_views_rgb8(bih, a.views, settings.samples, settings.dimensions, settings.cast)
+        imgs = render_views_rgb8(bih, a.views, settings.samples, settings.dimensions, settings.cast, lights=a.light)
         for path, img in zip(view_paths(settings.savePath, len(imgs)), imgs):
             write_png(path, img)
         print(f"Wrote {len(imgs)} views to {view_paths(settings.savePath, 1)[0]} ...")
     elif a.adaptive is not None:
         import numpy as np
         for done, live, spent, img, counts in render_adaptive(bih, cam, settings.samples, settings.dimensions, a.adaptive, eps=a.adaptive_eps,
-                                                              first=a.adaptive_first, step=a.adaptive_step, cast=settings.cast):
+                                                              first=a.adaptive_first, step=a.adaptive_step, cast=settings.cast, lights=a.light):
             print(f"Adaptive {done}/{settings.samples} live {live} spent {spent}")
         write_png(settings.savePath, img)
         if a.counts is not None:
             with open(a.counts, "wb") as f:                     # the name as given (np.save would append .npy to a path)
                 np.save(f, counts.astype(np.int32))
-    elif a.preview_every is None:
+    elif a.preview_every is None and a.light is None:
         render(bih, cam, settings)
+    elif a.preview_every is None:                               # caller-given lights live on a resident scene: one step of all samples
+        for _, img in render_progressive(bih, cam, settings.samples, settings.dimensions, settings.samples, settings.cast, lights=a.light):
+            write_png(settings.savePath, img)
     else:
-        for done, img in render_progressive(bih, cam, settings.samples, settings.dimensions, a.preview_every, settings.cast):
+        for done, img in render_progressive(bih, cam, settings.samples, settings.dimensions, a.preview_every, settings.cast, lights=a.light):
             write_png(settings.savePath, img)
             print(f"Preview: {done}/{settings.samples} samples written to {settings.savePath}")
     t1 = time.time()

@@ -7,6 +7,7 @@
 //   emissive shade, radiance fold    src/Lib.hs:135-137                      sq_shade1, sq_accumulate
 //   ordered per-pixel accumulation   src/Lib.hs:85-88                        sq_accumulate
 //   atan tonemap                     src/Lib.hs:93-104                       sq_accumulate
+//   raycast under caller-given lights src/Lib.hs:141-151                     sq_cast_pixels; sq_cast_gen, sq_cast_fold (wavefront form)
 //
 // Pipeline ("wavefront" form of renderPixel):  every sample of a pixel shoots the same primary ray
 // (src/Lib.hs:81-87), so it is traced once per pixel and the pixels that hit are compacted (wave ballot +
@@ -880,6 +881,148 @@ __global__ void __launch_bounds__(kBlock) sq_accumulate(const SceneView S, const
     }
 }
 
+// ----------------------------------------------------------------------------------------------
+// Caller-given point lights (sq_scene_set_lights): raycast with the light a parameter, src/Lib.hs:141-151
+// ----------------------------------------------------------------------------------------------
+// The lit kernels' own argument (Frame, RayFrame, SceneView, Work and TraceArgs stay as the tuned kernels take them): the scene's light
+// table, kLightWords floats per light (pos, power: an sq_light), and how many it holds; the wavefront form's per-active-pixel carry
+// of T between light batches (3 floats, in the workspace) and the lights [l_begin, l_end) of this batch.
+constexpr int kLightWords = 6;
+constexpr int kMaxLights = 4096;              // sq_scene_set_lights refuses more
+struct Lights { const float* table; int32_t n; float* carry; int32_t l_begin, l_end; };
+struct Light { f3 pos, power; };
+__device__ __forceinline__ Light light_of(const Lights& L, int l) {   // l is the same in every lane: scalar loads
+    const float* p = L.table + kLightWords * l;
+    return Light{ sq::mk(p[0], p[1], p[2]), sq::mk(p[3], p[4], p[5]) };
+}
+// c_i of squigly_hip.h: what light Li adds at the point p of a surface s0, given the hit `sh` of the shadow ray (Ray p (pos - p)).
+__device__ __forceinline__ f3 light_term(const Light& Li, f3 p, const Surface& s0, Hit sh) {
+    const float dl = sq::norm(p - Li.pos);
+    if (sh.tri >= 0 && !(hit_dist(p, Li.pos - p, sh.t) > dl)) return sq::mk(0, 0, 0);   // maybe True (\pos -> dist pos > dl)
+    return sq::mk(Li.power.x / dl, Li.power.y / dl, Li.power.z / dl) * s0.surf;
+}
+// The end of a pixel's fold: the caller's sum, avg over the k_end samples folded so far (src/Lib.hs:88) and its tonemap.
+__device__ __forceinline__ void store_fold(const Frame& F, long long pix, f3 sum) {
+    if (F.sum) { float* o = F.sum + pix * 3; o[0] = sum.x; o[1] = sum.y; o[2] = sum.z; }
+    const f3 avg = sq::scale(1 / (float)F.k_end, sum);
+    if (F.out_avg) { float* o = F.out_avg + pix * 3; o[0] = avg.x; o[1] = avg.y; o[2] = avg.z; }
+    if (F.out_rgb) tonemap(avg, F.out_rgb + pix * 3);
+}
+// T folded into a pixel's sums, once per sample of [k_begin, k_end); a raycast query (kSrcRays) stores T itself: no samples, no fold.
+template <int SRC>
+__device__ __forceinline__ void fold_cast_samples(const Frame& F, f3 T, f3& sum, f3& sum2, bool mom2) {
+    if constexpr (SRC == kSrcRays) sum = T;
+    else for (int k = F.k_begin; k < F.k_end; ++k) sum = sum + T;
+    if (mom2) for (int k = F.k_begin; k < F.k_end; ++k) sum2 = sum2 + T * T;
+}
+
+// Per-lane form (option "cast_wavefront" = 0, or "variant" = 1): sq_render_pixels' cast branch with a loop over the light table.
+template <typename StackT, int SRC, bool AD, typename FrameT>
+__device__ __forceinline__ void cast_pixels_body(const SceneView& S, const FrameT& F, const Lights& L) {
+    extern __shared__ float4 lds_raw[];
+    SQ_LDS StackT* stk = to_lds<StackT>(lds_raw) + threadIdx.x;
+    const long long pix = (long long)blockIdx.x * kBlock + threadIdx.x;
+    int y, x; f3 o0, d0;
+    if constexpr (SRC == kSrcRays) {
+        if (pix >= (long long)F.h) return;
+        o0 = load3(F.ray_org, pix); d0 = load3(F.ray_dir, pix);
+    } else if constexpr (SRC == kSrcViews) {
+        if (pix >= (long long)F.n_views * F.view_pixels) return;
+        const ViewCam c = view_cam<false>(F, view_coords(F, (int)pix, y, x));
+        o0 = c.pos; d0 = primary_dir(c.rot, F.w, F.h, y, x);
+    } else {
+        if (pix >= (long long)F.local_rows * F.h) return;
+        if constexpr (AD) { if (!pixel_live(F, pix)) return; }
+        pixel_coords(F, pix, y, x);
+        o0 = sq::mk(F.cam_pos[0], F.cam_pos[1], F.cam_pos[2]);
+        d0 = primary_dir(F.cam_rot, F.w, F.h, y, x);
+    }
+    const GlobalNodes N{ S.branches, S.cull_child, S.cull_child != nullptr };
+    f3 sum = sq::mk(0, 0, 0), sum2 = sq::mk(0, 0, 0);
+    const Hit h0 = trace_one(S, N, o0, d0, stk, kBlock);
+    if (h0.tri >= 0) {
+        sum = fold_start(F, pix);
+        if constexpr (AD) { if (F.sum2) sum2 = fold_start2(F, pix); }
+        const Surface s0 = surface_of(S, h0.tri);
+        const f3 p0 = o0 + sq::scale(h0.t, d0);
+        f3 T = sq::mk(0, 0, 0);
+#pragma unroll 1
+        for (int l = 0; l < L.n; ++l) {
+            const Light Li = light_of(L, l);
+            const f3 c = light_term(Li, p0, s0, trace_one(S, N, p0, Li.pos - p0, stk, kBlock));
+            T = l == 0 ? c : T + c;                                     // the fold starts at c_0, not at +0
+        }
+        fold_cast_samples<SRC>(F, T, sum, sum2, AD && F.sum2 != nullptr);
+    }
+    if constexpr (AD) {
+        if (F.sum2) { float* o = F.sum2 + pix * 3; o[0] = sum2.x; o[1] = sum2.y; o[2] = sum2.z; }
+        store_count(F, pix);
+    }
+    store_fold(F, pix, sum);
+}
+template <typename StackT, bool MV, bool AD = false>
+__global__ void __launch_bounds__(kBlock) sq_cast_pixels(const SceneView S, const Frame F, const Lights L) { cast_pixels_body<StackT, MV, AD>(S, F, L); }
+template <typename StackT>
+__global__ void __launch_bounds__(kBlock) sq_cast_pixels_rays(const SceneView S, const RayFrame F, const Lights L) { cast_pixels_body<StackT, kSrcRays, false>(S, F, L); }
+
+// Wavefront form (option "cast_wavefront" = 1): the lights play the role of a frame's samples.  After the frame's own primary pass,
+// per batch of lights [l_begin, l_end): sq_cast_gen writes the shadow ray of (active pixel a, light l) into slot (l - l_begin) * A + a,
+// one level of the trace kernel traces them, and sq_cast_fold folds the batch's terms in order into T.
+// One thread per active pixel; blockIdx.y splits the batch's lights when the frame has few pixels.
+template <int SRC, typename FrameT>
+__device__ __forceinline__ void cast_gen_body(const SceneView& S, const FrameT& F, const Work& W, const Lights& L) {
+    const int A = *W.n_active;
+    for (int a = blockIdx.x * kBlock + threadIdx.x; a < A; a += gridDim.x * kBlock) {
+        const Pixel0 P = load_pixel0<SRC>(S, F, W, a);
+        for (int l = L.l_begin + (int)blockIdx.y; l < L.l_end; l += (int)gridDim.y) {
+            const long long sid = (long long)(l - L.l_begin) * A + a;
+            const f3 d = light_of(L, l).pos - P.p0;                      // not normalised: the reference's is not
+            W.state[sid] = kRay1;
+            W.org[sid] = make_float4(P.p0.x, P.p0.y, P.p0.z, 0.0f);
+            W.dir[sid] = make_float4(d.x, d.y, d.z, 0.0f);
+        }
+    }
+}
+template <bool MV>
+__global__ void __launch_bounds__(kBlock) sq_cast_gen(const SceneView S, const Frame F, const Work W, const Lights L) { cast_gen_body<MV>(S, F, W, L); }
+__global__ void __launch_bounds__(kBlock) sq_cast_gen_rays(const SceneView S, const RayFrame F, const Work W, const Lights L) { cast_gen_body<kSrcRays>(S, F, W, L); }
+// ... and after the trace launch: T = c_0, T = T + c_l in the caller's order, carried from batch to batch in L.carry; on the last
+// batch (`last`) the sample fold and the pixel's stores, as sq_accumulate does them (a masked call's count is set since the
+// primary pass, store_active; the misses are black since then too).
+template <int SRC, typename FrameT>
+__device__ __forceinline__ void cast_fold_body(const SceneView& S, const FrameT& F, const Work& W, const Lights& L, int last) {
+    const int A = *W.n_active;
+    for (int a = blockIdx.x * kBlock + threadIdx.x; a < A; a += gridDim.x * kBlock) {
+        const Pixel0 P = load_pixel0<SRC>(S, F, W, a);
+        f3 T = sq::mk(0, 0, 0);
+        if (L.l_begin > 0) T = sq::mk(L.carry[3 * a], L.carry[3 * a + 1], L.carry[3 * a + 2]);
+        for (int l = L.l_begin; l < L.l_end; ++l) {
+            const int2 hit = slot_hit(W.org[(long long)(l - L.l_begin) * A + a]);
+            Hit sh; sh.t = __int_as_float(hit.x); sh.tri = hit.y;
+            const f3 c = light_term(light_of(L, l), P.p0, P.s0, sh);
+            T = l == 0 ? c : T + c;
+        }
+        if (!last) { L.carry[3 * a] = T.x; L.carry[3 * a + 1] = T.y; L.carry[3 * a + 2] = T.z; continue; }
+        const long long pix = W.px_pixel[a];
+        const bool mom2 = F.sum2 != nullptr;
+        f3 sum = sq::mk(W.px_sum[3 * a], W.px_sum[3 * a + 1], W.px_sum[3 * a + 2]), sum2 = sq::mk(0, 0, 0);
+        if (mom2) sum2 = sq::mk(W.px_sum2[3 * a], W.px_sum2[3 * a + 1], W.px_sum2[3 * a + 2]);
+        fold_cast_samples<SRC>(F, T, sum, sum2, mom2);
+        if (mom2) { float* o = F.sum2 + pix * 3; o[0] = sum2.x; o[1] = sum2.y; o[2] = sum2.z; }
+        store_fold(F, pix, sum);
+    }
+}
+template <bool MV>
+__global__ void __launch_bounds__(kBlock) sq_cast_fold(const SceneView S, const Frame F, const Work W, const Lights L, int last) { cast_fold_body<MV>(S, F, W, L, last); }
+__global__ void __launch_bounds__(kBlock) sq_cast_fold_rays(const SceneView S, const RayFrame F, const Work W, const Lights L, int last) { cast_fold_body<kSrcRays>(S, F, W, L, last); }
+
+// Copies a chunk of lights into the scene's light table: by value, as sq_stage_cams stages cameras.
+constexpr int kLightChunk = 128;              // lights per staging launch: 128 x 24 B = 3 KB of arguments
+struct LightChunk { float v[kLightWords * kLightChunk]; };
+__global__ void __launch_bounds__(kBlock) sq_stage_lights(float* table, int n, const LightChunk C) {
+    for (int i = threadIdx.x; i < kLightWords * n; i += kBlock) table[i] = C.v[i];
+}
+
 // The dominant kernel.  Persistent: each wave reserves a chunk of the (dense) ray queue with one
 // atomic, compacts the chunk's live entries with ballots into a small LDS list, and each lane pulls
 // its next ray from that list as soon as the previous one is finished, so a wave's lanes stay busy
@@ -1475,6 +1618,13 @@ struct sq_device_scene {
     // the table of generator words (grow-only, allocated after the workspace; ensure_rng_table) and its budget in MB (0 = none)
     RngTable rng{};
     int64_t opt_rng_table_mb = kRngTableDefaultMb;
+    // caller-given lights (sq_scene_set_lights): the host copy (the reference's light until set, and after a reset), whether it was set,
+    // the device table (kMaxLights entries, allocated on first need, filled in stream order) and whether it holds the host copy;
+    // cast_carry = the wavefront form's carry of T, 3 floats per pixel at the end of the workspace block
+    std::vector<sq_light> lights{ sq_light{ { 0.0f, 3.0f, -1.0f }, { 2.0f, 2.0f, 2.0f } } };
+    bool lights_set = false, lights_staged = false;
+    float* d_lights = nullptr; float* cast_carry = nullptr;
+    int64_t opt_cast_wavefront = 0;
     int64_t opt_pool = 1, opt_refill_min = 12, opt_flush_min = 40, opt_guided = 1, opt_primary_resident = 1, opt_pixel_major = -1, opt_cull = 1, opt_descend_extra = 2, opt_descend_lanes = 16, opt_primary_pooled = 0, opt_coresidency = 0, opt_trace_prio = 0, opt_aux_low_priority = 1, opt_aux_polite = 0, opt_primary_tiles = 1;
 };
 
@@ -1869,6 +2019,7 @@ extern "C" void sq_scene_free(sq_device_scene* s) {
     if (s->aux) (void)hipStreamDestroy(s->aux);
     (void)hipFree(s->d_cams);
     (void)hipFree(s->d_px_sum2);
+    (void)hipFree(s->d_lights);
     delete s;
 }
 
@@ -1898,7 +2049,7 @@ int ensure_workspace(sq_device_scene* s, int64_t pixels, int64_t slots) {
     auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
     if (s->d_work) { cache_give(s->device, s->d_work, s->work_bytes); s->d_work = nullptr; s->work_pixels = s->work_slots = 0; }
     size_t block_bytes = 0;
-    size_t off = 0, o_cnt = 0, o_stats = 0, o_pix = 0, o_t0 = 0, o_tri0 = 0, o_sum = 0, o_mt = 0, o_mtri = 0, o_state = 0, o_org = 0, o_dir = 0, o_tri1 = 0;
+    size_t off = 0, o_cnt = 0, o_stats = 0, o_pix = 0, o_t0 = 0, o_tri0 = 0, o_sum = 0, o_mt = 0, o_mtri = 0, o_state = 0, o_org = 0, o_dir = 0, o_tri1 = 0, o_carry = 0;
     for (;;) {
         off = 0;
         auto take = [&](size_t bytes) { size_t o = off; off += al(bytes); return o; };
@@ -1907,9 +2058,10 @@ int ensure_workspace(sq_device_scene* s, int64_t pixels, int64_t slots) {
         o_mt = take(pixels * 4); o_mtri = take(pixels * 4);
         // + pixels: the mirror rays' spare region behind the sample slots (state and the two ray quads)
         o_state = take(slots + pixels); o_org = take((slots + pixels) * 16); o_dir = take((slots + pixels) * 16); o_tri1 = take(slots * 4);
+        o_carry = take(pixels * 12);                                    // behind everything else: no other array moves for it
         // every array has its own, ordered place in the block: a slip here would be a GPU fault, not an error code
         if (!(o_cnt < o_stats && o_stats < o_pix && o_pix < o_t0 && o_t0 < o_tri0 && o_tri0 < o_sum && o_sum < o_mt && o_mt < o_mtri &&
-              o_mtri < o_state && o_state < o_org && o_org < o_dir && o_dir < o_tri1 && o_tri1 < off))
+              o_mtri < o_state && o_state < o_org && o_org < o_dir && o_dir < o_tri1 && o_tri1 < o_carry && o_carry < off))
             return sq_set_error("internal error: frame workspace layout");
         block_bytes = off;
         if ((s->d_work = cache_take(s->device, off, &block_bytes)) != nullptr) break;
@@ -1933,6 +2085,7 @@ int ensure_workspace(sq_device_scene* s, int64_t pixels, int64_t slots) {
     W.px_mt = (float*)(base + o_mt); W.px_mtri = (int32_t*)(base + o_mtri);
     W.state = (uint8_t*)(base + o_state); W.org = (float4*)(base + o_org); W.dir = (float4*)(base + o_dir); W.tri1 = (int32_t*)(base + o_tri1);
     W.slot_capacity = slots;
+    s->cast_carry = (float*)(base + o_carry);
     s->work_bytes = block_bytes; s->work_pixels = pixels; s->work_slots = slots;
     return 0;
 }
@@ -2005,6 +2158,28 @@ int stage_cams(sq_device_scene* s, const Frame& F, const sq_camera* cams, hipStr
     return 0;
 }
 
+// The scene's light table: room for kMaxLights lights, allocated once (96 KB), so a later sq_scene_set_lights never frees a table that
+// an enqueued frame still reads.
+int ensure_light_table(sq_device_scene* s) {
+    if (s->d_lights) return 0;
+    SQ_HIP(hipMalloc((void**)&s->d_lights, (size_t)kMaxLights * kLightWords * sizeof(float)));
+    return 0;
+}
+// Enqueues the copy of `lights` into the scene's light table on `stream`.  The lights travel as kernel arguments, captured when the
+// launch is enqueued: the table changes in stream order, and the host array is not read after the call.
+int stage_lights(sq_device_scene* s, const std::vector<sq_light>& lights, hipStream_t stream) {
+    static_assert(sizeof(sq_light) == kLightWords * sizeof(float), "sq_light is one light-table entry");
+    const int n_all = (int)lights.size();
+    for (int i0 = 0; i0 < n_all; i0 += kLightChunk) {
+        const int n = std::min(kLightChunk, n_all - i0);
+        LightChunk c{};
+        std::memcpy(c.v, lights.data() + i0, (size_t)n * sizeof(sq_light));
+        hipLaunchKernelGGL(sq_stage_lights, dim3(1), dim3(kBlock), 0, stream, s->d_lights + (long long)kLightWords * i0, n, c);
+        SQ_HIP(hipGetLastError());
+    }
+    return 0;
+}
+
 // Enqueues fn's launch; with option "timing" brackets it with hipEvents for sq_kernel_timing.
 template <typename Fn>
 int timed_launch(sq_device_scene* s, Fn&& fn, const char* name, hipStream_t on) {
@@ -2031,6 +2206,9 @@ template <typename StackT, int SRC> struct SrcKernels {
     static constexpr auto gen_bounce1 = &sq_gen_bounce1<MV>;
     static constexpr auto mirror1_gen = &sq_mirror1_gen<MV>;
     static constexpr auto shade1 = &sq_shade1<MV>;
+    static constexpr auto cast_pixels = &sq_cast_pixels<StackT, MV>;
+    static constexpr auto cast_gen = &sq_cast_gen<MV>;
+    static constexpr auto cast_fold = &sq_cast_fold<MV>;
 };
 template <typename StackT> struct SrcKernels<StackT, kSrcRays> {
     using FrameT = RayFrame;
@@ -2041,6 +2219,9 @@ template <typename StackT> struct SrcKernels<StackT, kSrcRays> {
     static constexpr auto gen_bounce1 = &sq_gen_bounce1_rays;
     static constexpr auto mirror1_gen = &sq_mirror1_gen_rays;
     static constexpr auto shade1 = &sq_shade1_rays;
+    static constexpr auto cast_pixels = &sq_cast_pixels_rays<StackT>;
+    static constexpr auto cast_gen = &sq_cast_gen_rays;
+    static constexpr auto cast_fold = &sq_cast_fold_rays;
 };
 // The kernels of one call's wavefront pipeline, chosen once: the ray source's set; in a masked call (single-view frames only: multi-view
 // frames and queries have no masked form) the AD instantiations of the kernels that decide who is active; and sq_accumulate by second
@@ -2203,7 +2384,19 @@ int launch_frame(sq_device_scene* s, const typename SrcKernels<StackT, SRC>::Fra
     const bool mom2 = ad && F.sum2;
     if (px_blocks > 0x7fffffffLL) return sq_set_error("image too large for one launch");
     if (px_lds > 160 * 1024) return sq_set_error("BIH height %d needs %zu B of LDS stack per workgroup (max 163840)", S.height, px_lds);
-    if (s->opt_variant == 1 || F.cast) {
+    // a cast frame: the per-lane form, or (option "cast_wavefront" with variant 2) the wavefront form with the lights as its samples
+    const bool cast_wave = F.cast && s->opt_variant == 2 && s->opt_cast_wavefront;
+    const int n_lights = (int)s->lights.size();
+    if (F.cast && !cast_wave && s->lights_set) {                       // caller-given lights, per-lane: sq_cast_pixels beside sq_render_pixels
+        auto cast_pixels = SrcKernels<StackT, SRC>::cast_pixels;
+        if constexpr (SRC == kSrcCamera) if (ad) cast_pixels = &sq_cast_pixels<StackT, false, true>;
+        if (px_lds > 64 * 1024) SQ_HIP(hipFuncSetAttribute((const void*)cast_pixels, hipFuncAttributeMaxDynamicSharedMemorySize, (int)px_lds));
+        P.launched = 1;
+        if (stage_cams(s, F, cams, stream)) return 1;
+        const Lights L{ s->d_lights, n_lights, nullptr, 0, n_lights };
+        return timed_launch(s, [&] { hipLaunchKernelGGL(cast_pixels, dim3((unsigned)px_blocks), dim3(kBlock), px_lds, stream, S, F, L); }, "sq_cast_pixels", stream);
+    }
+    if (s->opt_variant == 1 || (F.cast && !cast_wave)) {
         auto render_pixels = SrcKernels<StackT, SRC>::render_pixels;
         if constexpr (SRC == kSrcCamera) if (ad) render_pixels = &sq_render_pixels<StackT, false, true>;
         if (px_lds > 64 * 1024) SQ_HIP(hipFuncSetAttribute((const void*)render_pixels, hipFuncAttributeMaxDynamicSharedMemorySize, (int)px_lds));
@@ -2212,7 +2405,8 @@ int launch_frame(sq_device_scene* s, const typename SrcKernels<StackT, SRC>::Fra
         return timed_launch(s, [&] { hipLaunchKernelGGL(render_pixels, dim3((unsigned)px_blocks), dim3(kBlock), px_lds, stream, S, F); }, "sq_render_pixels", stream);
     }
     // ---- wavefront pipeline ----
-    const int n_call = F.k_end - F.k_begin;                              // the samples this call renders (a whole frame: F.samples)
+    // the samples this call renders (a whole frame: F.samples); in a cast frame the lights take the samples' place in the slots
+    const int n_call = cast_wave ? n_lights : F.k_end - F.k_begin;
     // at least one sample of every pixel per batch, never more slots than the call has samples
     const int64_t slots = std::max<int64_t>(pixels, std::min<int64_t>(s->opt_slots, (int64_t)pixels * n_call));
     if (ensure_workspace(s, pixels, slots)) return 1;
@@ -2226,7 +2420,7 @@ int launch_frame(sq_device_scene* s, const typename SrcKernels<StackT, SRC>::Fra
     // Opt-in (sq_set_option "overlap"): measured +3 % on the headline frame (105.5 -> 102.3 ms) -- the kernels do
     // run side by side, but the chip is VALU-bound as a whole, so each slows the other down by what it gains;
     // and trace-launch durations then include that interference, which blurs the per-kernel roofline figure.
-    const bool overlap = s->opt_overlap && n_call >= 2 && have_slots >= 2 * pixels;
+    const bool overlap = s->opt_overlap && !cast_wave && n_call >= 2 && have_slots >= 2 * pixels;
     const int tracks = overlap ? 2 : 1;
     const int64_t track_slots = have_slots / tracks;
     Work Wt[2] = { W, W };
@@ -2251,10 +2445,15 @@ int launch_frame(sq_device_scene* s, const typename SrcKernels<StackT, SRC>::Fra
     // padding: up to 64 lanes per pixel at h = 1), and a launch has at most 2^32 - 1 threads; the other two passes stride over a fixed grid
     if (P.primary_form == SQ_PRIMARY_PER_LANE && (primary_padded(F) * F.n_views + kBlock - 1) / kBlock * kBlock > 0xffffffffLL)
         return sq_set_error("image too large for one launch of the primary rays (%lld tile lanes; at most 2^32 - 1)", primary_padded(F) * F.n_views);
+    if (cast_wave && ensure_light_table(s)) return 1;
     P.launched = 1;                                                    // planned; what follows fails only on HIP errors
     // nothing is enqueued before this point, so a refusal above leaves every buffer as it was
     if (stage_cams(s, F, cams, stream)) return 1;                       // multi-view: before every kernel that reads the table (e_setup below)
-    const RngView R = ensure_rng_table(s, F, stream, SRC != kSrcRays);   // allocated behind the workspace; its fill and the wait for it come before every sq_gen_bounce1 (e_setup below)
+    if (cast_wave && !s->lights_staged) {                               // never set: the table receives the reference's light
+        if (stage_lights(s, s->lights, stream)) return 1;
+        s->lights_staged = true;
+    }
+    const RngView R = cast_wave ? RngView{ nullptr, 0 } : ensure_rng_table(s, F, stream, SRC != kSrcRays);   // allocated behind the workspace; its fill and the wait for it come before every sq_gen_bounce1 (e_setup below)
     // (a masked call's dead pixels keep what they hold: its primary kernels write the black of the live misses, store_live_miss)
     if (F.out_avg && !ad) SQ_HIP(hipMemsetAsync(F.out_avg, 0, (size_t)pixels * 3 * sizeof(float), stream));   // pixels whose primary ray misses: black
     if (F.out_rgb && !ad) SQ_HIP(hipMemsetAsync(F.out_rgb, 0, (size_t)pixels * 3, stream));
@@ -2290,6 +2489,21 @@ int launch_frame(sq_device_scene* s, const typename SrcKernels<StackT, SRC>::Fra
         if (launch_trace_kernel(s, S, TP, Wp, pixels, 1, 0, stream, false)) return 1;
         hipLaunchKernelGGL(K.primary_store, dim3(aux_blocks), dim3(kBlock), 0, stream, F, W, pixels);
         SQ_HIP(hipGetLastError());
+    }
+    if (cast_wave) {
+        // Light batch i holds the lights [i * batch, i * batch + kc): shadow rays into the slots, one level of the trace kernel, fold.
+        // Everything on the caller's stream ("overlap" is for sample batches).
+        for (int i = 0; i * batch < n_lights; ++i) {
+            const int l0 = i * batch, kc = std::min(batch, n_lights - l0);
+            const Lights L{ s->d_lights, n_lights, s->cast_carry, l0, l0 + kc };
+            SQ_HIP(hipMemsetAsync(W.head[0], 0, 32 * sizeof(int32_t), stream));     // both dequeue cursors
+            hipLaunchKernelGGL((SrcKernels<StackT, SRC>::cast_gen), pp_grid(kc), dim3(kBlock), 0, stream, S, F, W, L);
+            SQ_HIP(hipGetLastError());
+            if (launch_trace_kernel(s, S, TP, W, pixels, kc, 0, stream, false)) return 1;
+            hipLaunchKernelGGL((SrcKernels<StackT, SRC>::cast_fold), dim3(aux_blocks), dim3(kBlock), 0, stream, S, F, W, L, l0 + kc == n_lights ? 1 : 0);
+            SQ_HIP(hipGetLastError());
+        }
+        return 0;
     }
     // batch i holds the samples [k0_of(i), k0_of(i) + kc_of(i)) of [k_begin, k_end); the call's last batch ends the fold (sq_accumulate)
     auto k0_of = [&](int i) { return F.k_begin + i * batch; };
@@ -2484,7 +2698,7 @@ int render_rows(sq_device_scene* s, const sq_camera* cam, int32_t n_views, int32
     if (rows < 0) return sq_set_error("bad shard {row_block=%d, shard=%d, n_shards=%d}", sh.row_block, sh.shard, sh.n_shards);
     if (rows == 0) return 0;                    // an empty shard (more shards than row blocks) has nothing to render
     if (!d_avg && !d_rgb && !d_sum) return sq_set_error("no output buffer");
-    if (refuse_frame_size(n_views, rows, h, s->opt_variant != 1 && !cast)) return 1;   // before any 32-bit product of rows and h, and before the device is touched
+    if (refuse_frame_size(n_views, rows, h, s->opt_variant != 1 && (!cast || s->opt_cast_wavefront))) return 1;   // before any 32-bit product of rows and h, and before the device is touched
     if (d_mask || d_sum2 || d_count) {   // a masked call: no two of its buffers may overlap (a live pixel's stores would be another pixel's mask, count or fold)
         const size_t px = (size_t)rows * (size_t)h;
         const NamedRange b[6] = { { "d_mask", d_mask, px }, { "d_sum", d_sum, px * 12 }, { "d_sum2", d_sum2, px * 12 }, { "d_count", d_count, px * 4 },
@@ -2715,7 +2929,7 @@ RadianceQuery radiance_part(const RadianceQuery& Q, long long c0, long long m) {
 // chunk has the same plan, and the first is the largest, so a refusal comes from the first chunk, before anything is enqueued.
 template <typename StackT>
 int radiance_rays(sq_device_scene* s, const RadianceQuery& Q, int32_t k_begin, int32_t k_end, bool cast, hipStream_t stream) {
-    const long long chunk = radiance_chunk_rays(Q.n, s->opt_slots, s->opt_variant != 1 && !cast);
+    const long long chunk = radiance_chunk_rays(Q.n, s->opt_slots, s->opt_variant != 1 && (!cast || s->opt_cast_wavefront));
     for (long long c0 = 0; c0 < Q.n; c0 += chunk) {
         const RadianceQuery C = radiance_part(Q, c0, std::min(chunk, Q.n - c0));
         RayFrame F{};
@@ -2767,6 +2981,29 @@ extern "C" int sq_raycast_rays_device(sq_device_scene* s, const float* d_org, co
     const RadianceQuery Q{ d_org, d_dir, nullptr, d_rad, nullptr, nullptr, (long long)n };
     hipStream_t stream = (hipStream_t)hip_stream;
     return s->small_index ? radiance_rays<uint16_t>(s, Q, 0, 1, true, stream) : radiance_rays<uint32_t>(s, Q, 0, 1, true, stream);
+}
+
+extern "C" int sq_scene_set_lights(sq_device_scene* s, const sq_light* lights, int32_t n_lights, void* hip_stream) {
+    if (!s) return sq_set_error("null argument");
+    if (n_lights < 0) return sq_set_error("n_lights must be >= 0 (got %d)", n_lights);
+    if (n_lights > kMaxLights) return sq_set_error("%d lights are too many (at most %d)", n_lights, kMaxLights);
+    if (n_lights > 0 && !lights) return sq_set_error("lights is NULL with n_lights = %d", n_lights);
+    if (n_lights == 0 && lights) return sq_set_error("n_lights is 0 with lights given (NULL and 0 restore the reference's light)");
+    SQ_HIP(hipSetDevice(s->device));
+    if (ensure_light_table(s)) return 1;
+    std::vector<sq_light> v;
+    if (n_lights > 0) v.assign(lights, lights + n_lights);
+    else v.assign(1, sq_light{ { 0.0f, 3.0f, -1.0f }, { 2.0f, 2.0f, 2.0f } });   // src/Lib.hs:141-151
+    if (stage_lights(s, v, (hipStream_t)hip_stream)) return 1;
+    s->lights.swap(v);
+    s->lights_set = n_lights > 0; s->lights_staged = true;
+    return 0;
+}
+extern "C" int32_t sq_scene_get_lights(sq_device_scene* s, sq_light* out, int32_t cap) {
+    if (!s) { sq_set_error("null argument"); return -1; }
+    const int32_t n = (int32_t)s->lights.size();
+    if (out && cap > 0) std::memcpy(out, s->lights.data(), (size_t)std::min(n, cap) * sizeof(sq_light));
+    return n;
 }
 
 extern "C" int64_t sq_scene_rng_table(sq_device_scene* s, int64_t first, int64_t count, uint32_t* out_words) {
@@ -2834,6 +3071,7 @@ extern "C" int sq_set_option(sq_device_scene* s, const char* key, int64_t value)
     if (!std::strcmp(key, "trace_blocks_per_cu")) { if (value < 0 || value > 8) return sq_set_error("trace_blocks_per_cu must be in 0..8"); s->opt_trace_blocks_per_cu = value; return 0; }
     if (!std::strcmp(key, "overlap")) { if (value < 0 || value > 2) return sq_set_error("overlap must be 0, 1 or 2"); s->opt_overlap = value; return 0; }
     if (!std::strcmp(key, "rng_table_mb")) { if (value < 0 || value > (1ll << 20)) return sq_set_error("rng_table_mb must be in 0..2^20"); s->opt_rng_table_mb = value; return 0; }
+    if (!std::strcmp(key, "cast_wavefront")) { s->opt_cast_wavefront = value ? 1 : 0; return 0; }
     if (!std::strcmp(key, "pool")) { s->opt_pool = value ? 1 : 0; return 0; }
     if (!std::strcmp(key, "guided")) { if (value < 0 || value > 3) return sq_set_error("guided must be in 0..3"); s->opt_guided = value; return 0; }
     if (!std::strcmp(key, "primary_resident")) { s->opt_primary_resident = value ? 1 : 0; return 0; }

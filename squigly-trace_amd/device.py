@@ -25,7 +25,7 @@ MAX_WAVEFRONT_PIXELS = 2 ** 29
 
 def frame_size_error(rows, h, views=1, wavefront=False):
     """The library's refusal of a call of views x rows x h pixels, word for word, or None when the size is accepted.
-    wavefront: the call takes the wavefront form (option "variant" = 2, not a cast frame)."""
+    wavefront: the call takes the wavefront form (option "variant" = 2; a cast frame only with option "cast_wavefront" = 1)."""
     rows, h, views = int(rows), int(h), int(views)
     if rows <= 0 or h <= 0 or views <= 0:
         return None
@@ -41,7 +41,7 @@ def frame_size_error(rows, h, views=1, wavefront=False):
 
 def _check_frame_size(dscene, rows, h, cast, views=1):
     """SquiglyError, before anything is allocated, for a frame the library would refuse for its size."""
-    msg = frame_size_error(rows, h, views, getattr(dscene, "_variant", 2) != 1 and not cast)
+    msg = frame_size_error(rows, h, views, getattr(dscene, "_variant", 2) != 1 and (not cast or getattr(dscene, "_cast_wavefront", 0) != 0))
     if msg:
         raise N.SquiglyError(msg)
 
@@ -99,6 +99,30 @@ class DeviceScene:
         N.check(N.lib().sq_set_option(self._h, key.encode(), int(value)))
         if key == "variant":
             self._variant = int(value)       # which size limit a frame has (_check_frame_size)
+        if key == "cast_wavefront":
+            self._cast_wavefront = int(bool(value))
+
+    def set_lights(self, lights, stream=None):
+        """The point lights of the scene's cast frames and raycast queries (sq_scene_set_lights), in the order their terms are
+        added.  lights: an array-like [n, 6] (pos, power), or a sequence of (pos, power) pairs with power a scalar or three
+        numbers; None restores the reference's light (REFERENCE_LIGHT).  The update is enqueued on `stream` like a frame, and
+        the argument may be reused as soon as the call returns."""
+        table = None if lights is None else N.lights_array(lights)      # shape and count errors come before any device work
+        dev = torch.device("cuda", self.device)
+        st = stream if stream is not None else torch.cuda.current_stream(dev)
+        N.check(N.lib().sq_scene_set_lights(self._h, None if table is None else table.ctypes.data, 0 if table is None else len(table),
+                                            C.c_void_p(st.cuda_stream)))
+
+    @property
+    def lights(self):
+        """The scene's lights as a float32 numpy array [n, 6] (pos, power), from the library's copy (sq_scene_get_lights)."""
+        import numpy as np
+        n = N.lib().sq_scene_get_lights(self._h, None, 0)
+        if n < 0:
+            raise N.SquiglyError(N.lib().sq_last_error().decode(errors="replace"))
+        out = np.empty((n, 6), np.float32)
+        N.lib().sq_scene_get_lights(self._h, out.ctypes.data, n)
+        return out
 
     def rng_table(self, first=0, count=0):
         """sq_scene_rng_table: (seeds the scene's table of generator words holds, its entries [first, first + count) as a uint32
@@ -352,8 +376,8 @@ class DeviceScene:
         return Radiance(sums, avg, rgb)
 
     def raycast(self, origins, directions, stream=None):
-        """Lib.raycast of each ray (sq_raycast_rays_device, the light at (0, 3, -1)): a float32 CUDA tensor [..., 3], zeros for a
-        miss or a shadowed point.  origins, directions as in `intersect`."""
+        """Lib.raycast of each ray (sq_raycast_rays_device) under the scene's lights (set_lights; the reference's light at
+        (0, 3, -1) unless set): a float32 CUDA tensor [..., 3], zeros for a miss or a point every light is shadowed at.  origins, directions as in `intersect`."""
         shape = _ray_shape(origins, directions)
         dev = torch.device("cuda", self.device)
         st = stream if stream is not None else torch.cuda.current_stream(dev)
