@@ -4,6 +4,8 @@
  * Haskell host would keep calling unchanged.  No GHC exists in the build or GPU images, so the
  * same functions are provided in C++ (squigly-trace_amd/csrc/sq_host.cpp) with identical
  * arithmetic, and produce exactly the arrays that squigly_hip.h consumes.
+ * Also here, with no counterpart in the reference: the culling boxes, and a window on the scene packer, the host half of
+ * sq_scene_upload(), so that what the kernels will read can be inspected on a machine without a GPU.
  * All citations are relative to the reference repository root.
  */
 #ifndef SQUIGLY_HOST_H
@@ -55,10 +57,24 @@ void sq_bih_free(sq_bih* b);
  * ray_limits[2], |o|^2 <= ray_limits[0] and finite o, d, 1/d, o/d that FAILS the fp32 slab test of a node's box is
  * rejected by the reference's mollerTrumbore (src/Geometry.hs:117-142) for every triangle of that node, so the node
  * returns Nothing (src/BIH.hs:105-109) without testing them.  The error analysis is in csrc/sq_host.cpp; leaves it does
- * not cover get an infinite box, and ray_limits[0] < 0 says no ray may be culled.  sq_scene_upload() calls this. */
+ * not cover get an infinite box, and ray_limits[0] < 0 says no ray may be culled.  The scene packer below calls this. */
 int  sq_cull_boxes(const sq_scene* scene, float* boxes, float ray_limits[3]);
 /* The binary16 encoding the resident kernels keep such a box in: the nearest value >= x (up != 0) or <= x, never subnormal. */
 uint32_t sq_half_outward(float x, int32_t up);
+
+/* The scene packer: everything sq_scene_upload() computes from a scene before it touches a device -- validation, the
+ * breadth-first branch table, triangle / surface / material records, the 16-bit indexed and resident encodings, the culling
+ * tables, the merged branch records, the emitter list and the flags that choose a kernel form.  sq_scene_upload() copies exactly
+ * these arrays to the device.  Needs no GPU.  Arrays go by the name of the SceneView member they feed (csrc/sq_scene.h):
+ * branches, leaves, tris, tri_mat, surfs, mats, verts4, trix, rbranch, emitters, cull_child, cull_child16, branches_m; `data`
+ * points into the packed scene and lives as long as it.  Scalars: n_branches, n_leaves, height, root_ref, rroot, packed_leaves,
+ * nonneg_materials, finite_geometry, n_emitters, n_verts, small_index, and cull_o2max / cull_d2min / cull_d2max as the bits
+ * of the float.  An unknown name returns non-zero. */
+typedef struct sq_packed sq_packed;
+int   sq_scene_pack(const sq_scene* scene, sq_packed** out);
+int   sq_packed_array(const sq_packed* p, const char* name, const void** data, size_t* bytes);
+int   sq_packed_scalar(const sq_packed* p, const char* name, int64_t* value);
+void  sq_packed_free(sq_packed* p);
 
 /* The table of generator words of a resident scene (squigly_hip.h, option "rng_table_mb"): how many seeds [0, n_cover) it holds
  * for a frame of w rows x h columns at `samples` samples under a budget of budget_bytes.  The frame's seeds are

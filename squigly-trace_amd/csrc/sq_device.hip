@@ -31,12 +31,12 @@
 #include <chrono>
 #include <thread>
 #include <type_traits>
-#include <unordered_map>
 #include <vector>
 
 #include "../../include/squigly_hip.h"
 #include "../../include/squigly_host.h"
 #include "sq_error.h"
+#include "sq_pack.h"
 #include "sq_scene.h"
 
 using sq::f3;
@@ -1587,7 +1587,7 @@ __global__ void sq_debug_kernel(int op, const void* a, const void* b, long long 
 }
 
 // ----------------------------------------------------------------------------------------------
-// Host: scene validation + upload
+// Host: scene upload (validation and packing: sq_host.cpp, sq_pack.h)
 // ----------------------------------------------------------------------------------------------
 // A filled table of generator words: entries [0, cover) (RngView), kRngPad bytes of padding behind them.  Nothing writes to a block
 // once it is filled, so a scene that adopts one only has to be ordered after `filled`, the event recorded behind the fill.
@@ -1596,9 +1596,8 @@ constexpr int64_t kRngTableDefaultMb = 24576;   // option "rng_table_mb": 24 GiB
 struct sq_device_scene {
     int device = 0;
     SceneView view{};
-    void* d_arena = nullptr;      // every d_* array below lives in this one allocation
-    void *d_branches = nullptr, *d_leaves = nullptr, *d_tris = nullptr, *d_mats = nullptr, *d_verts = nullptr, *d_trix = nullptr, *d_rbranch = nullptr, *d_emitters = nullptr, *d_tri_mat = nullptr, *d_surfs = nullptr, *d_cull_child = nullptr, *d_cull16 = nullptr, *d_rtail = nullptr, *d_branches_m5 = nullptr;
-    int height = 0; bool small_index = false; int n_cu = 256; int64_t n_grown = 0;
+    void* d_arena = nullptr;      // every array of `view` lives in this one allocation
+    int height = 0; bool small_index = false; int n_cu = 256;
     // workspace (grow-only)
     Work work{}; void* d_work = nullptr; size_t work_bytes = 0; int64_t work_pixels = 0, work_slots = 0;
     // timing of the dominant kernel
@@ -1628,323 +1627,50 @@ struct sq_device_scene {
     int64_t opt_pool = 1, opt_refill_min = 12, opt_flush_min = 40, opt_guided = 1, opt_primary_resident = 1, opt_pixel_major = -1, opt_cull = 1, opt_descend_extra = 2, opt_descend_lanes = 16, opt_primary_pooled = 0, opt_coresidency = 0, opt_trace_prio = 0, opt_aux_low_priority = 1, opt_aux_polite = 0, opt_primary_tiles = 1;
 };
 
-namespace {
-
-// Walks the pre-order array once; checks that it is a well-formed tree, that every index is in
-// range, and computes the height.  A malformed tree would otherwise fault on the GPU.
-int validate_tree(const sq_scene& sc, int& height, std::vector<int32_t>& depth_of) {
-    const int32_t n = sc.n_nodes;
-    if (n < 1) return sq_set_error("scene has no nodes");
-    depth_of.assign((size_t)n, 0);
-    struct Fr { int32_t node, stage; };
-    std::vector<Fr> st;
-    st.push_back({ 0, 0 });
-    int32_t next = 0;      // next unvisited pre-order index
-    depth_of[0] = 1;
-    height = 0;
-    while (!st.empty()) {
-        const int32_t node = st.back().node; const int stage = st.back().stage;
-        const sq_node& nd = sc.nodes[node];
-        const int kind = nd.kind & 3;
-        if (stage == 0) {
-            if (node != next) return sq_set_error("node %d is not in pre-order position (expected %d)", node, next);
-            ++next;
-            const int dep = depth_of[(size_t)node];
-            if (dep > height) height = dep;
-            if (kind == 3) {
-                const int64_t cnt = nd.kind >> 2, first = nd.link;
-                if (cnt < 0 || first < 0 || first + cnt > sc.n_tris) return sq_set_error("leaf %d has triangle range [%lld,+%lld) outside 0..%d", node, (long long)first, (long long)cnt, sc.n_tris);
-                st.pop_back();
-                continue;
-            }
-            if ((nd.kind >> 2) != 0) return sq_set_error("branch %d has stray bits in kind", node);
-            if (node + 1 >= n) return sq_set_error("branch %d has no left child", node);
-            st.back().stage = 1;
-            depth_of[(size_t)node + 1] = dep + 1;
-            st.push_back({ node + 1, 0 });
-        } else if (stage == 1) {
-            if (nd.link != next) return sq_set_error("branch %d: right child link %d, expected %d", node, nd.link, next);
-            if (nd.link >= n) return sq_set_error("branch %d: right child %d out of range", node, nd.link);
-            st.back().stage = 2;
-            depth_of[(size_t)nd.link] = depth_of[(size_t)node] + 1;
-            st.push_back({ nd.link, 0 });
-        } else st.pop_back();
-    }
-    if (next != n) return sq_set_error("tree covers %d of %d nodes", next, n);
-    return 0;
-}
-
-}  // namespace
-
 extern "C" int sq_scene_upload(const sq_scene* sc, int32_t device, sq_device_scene** out) {
-    if (!sc || !out) return sq_set_error("null argument");
-    if (!sc->nodes || sc->n_nodes < 1) return sq_set_error("scene has no nodes");
-    if (sc->n_tris < 0 || sc->n_mats < 0 || (sc->n_tris && !sc->tris) || (sc->n_mats && !sc->mats)) return sq_set_error("bad triangle/material arrays");
-    for (int32_t i = 0; i < sc->n_tris; ++i)
-        if (sc->tris[i].mat < 0 || sc->tris[i].mat >= sc->n_mats) return sq_set_error("triangle %d: material %d outside 0..%d", i, sc->tris[i].mat, sc->n_mats - 1);
+    if (sq_check_scene_args(sc, out)) return 1;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return sq_set_error("no HIP device available (this library has no CPU fallback)");
     if (device < 0 || device >= ndev) return sq_set_error("device %d outside 0..%d", device, ndev - 1);
-    int height = 0; std::vector<int32_t> depth;
-    if (validate_tree(*sc, height, depth)) return 1;
-    if (sc->height && sc->height != height) return sq_set_error("scene.height = %d but the tree has height %d", sc->height, height);
-
-    // Re-pack.  Leaves keep pre-order numbering; branches are numbered breadth-first (stable within a
-    // level) so the top of the tree is a prefix of the branch table.  Each branch carries its traversal box.
-    const int32_t n = sc->n_nodes;
-    std::vector<uint32_t> ref((size_t)n);
-    int32_t nb = 0, nl = 0;
-    {
-        std::vector<std::vector<int32_t>> by_depth((size_t)height + 1);
-        for (int32_t i = 0; i < n; ++i) {
-            if ((sc->nodes[i].kind & 3) == 3) ref[(size_t)i] = (uint32_t)nl++ | kLeafBit;
-            else by_depth[(size_t)depth[(size_t)i]].push_back(i);
-        }
-        for (auto& level : by_depth) for (int32_t i : level) ref[(size_t)i] = (uint32_t)nb++;
-    }
-    std::vector<DevBranch> br((size_t)nb);
-    std::vector<int> br_axis((size_t)nb);
-    std::vector<uint32_t> br_grown((size_t)nb, 0u);     // kGrownLeft | kGrownRight (sq_scene.h), for the incremental slab test
-    bool incremental_ok = true;                         // no child interval is inverted anywhere in the tree
-    std::vector<DevLeaf> lf((size_t)nl);
-    std::vector<sq_bounds> box((size_t)n);
-    box[0] = sc->root;
-    for (int32_t i = 0; i < n; ++i) {                   // pre-order: parents come before children
-        const sq_node& nd = sc->nodes[i];
-        const int kind = nd.kind & 3;
-        if (kind == 3) { lf[ref[(size_t)i] & ~kLeafBit] = { nd.link, nd.kind >> 2 }; continue; }
-        const sq_bounds& b = box[(size_t)i];
-        DevBranch& d = br[ref[(size_t)i]];
-        for (int c = 0; c < 3; ++c) { d.lo[c] = b.lo[c]; d.hi[c] = b.hi[c]; }
-        d.lmax = d.lmax2 = nd.lmax; d.rmin = d.rmin2 = nd.rmin; br_axis[ref[(size_t)i]] = kind;
-        d.left = ref[(size_t)i + 1]; d.right = ref[(size_t)nd.link];
-        {   // how the children's planes sit in this branch's interval on the split axis (NaN fails every comparison)
-            const float lo = b.lo[kind], hi = b.hi[kind];
-            if (!(lo <= hi) || !(lo <= nd.lmax) || !(nd.rmin <= hi)) incremental_ok = false;
-            br_grown[ref[(size_t)i]] = (nd.lmax > hi ? kGrownLeft : 0u) | (nd.rmin < lo ? kGrownRight : 0u);
-        }
-        sq_bounds l = b, r = b;                          // src/BIH.hs:130-141
-        l.hi[kind] = nd.lmax; r.lo[kind] = nd.rmin;
-        box[(size_t)i + 1] = l; box[(size_t)nd.link] = r;
-    }
-    std::vector<DevTri> tr((size_t)sc->n_tris); std::vector<int32_t> tri_mat((size_t)sc->n_tris);
-    for (int32_t i = 0; i < sc->n_tris; ++i) {
-        const sq_tri& t = sc->tris[i]; DevTri& d = tr[(size_t)i];
-        for (int c = 0; c < 3; ++c) { d.v0[c] = t.v0[c]; d.e1[c] = t.v1[c] - t.v0[c]; d.e2[c] = t.v2[c] - t.v0[c]; }
-        tri_mat[(size_t)i] = t.mat;
-    }
-    tr.resize((size_t)sc->n_tris + GlobalTris::kRunPad);                   // zero triangles: get_run may read past the last one
-    std::vector<DevSurf> sf((size_t)sc->n_tris);
-    std::vector<DevMat> mt((size_t)sc->n_mats);
-    bool nonneg = true;
-    for (int32_t i = 0; i < sc->n_mats; ++i) {
-        const sq_material& m = sc->mats[i];
-        mt[(size_t)i] = { m.reflective, m.surf[0], m.surf[1], m.surf[2], m.emissive, m.emit[0], m.emit[1], m.emit[2] };
-        const float comp[8] = { m.reflective, m.surf[0], m.surf[1], m.surf[2], m.emissive, m.emit[0], m.emit[1], m.emit[2] };
-        for (float c : comp) { uint32_t bits; std::memcpy(&bits, &c, 4); if ((bits >> 31) || !(c == c) || c > 3.0e38f) nonneg = false; }
-    }
-    // The s == 0 shortcuts (absorbs()) replace `0 * L` by +0, which is only the reference's value while the nested
-    // radiance L is finite (0 * inf = NaN, src/Lib.hs:135).  Components <= 3e38 do not bound the PRODUCTS: the emission
-    // `emissive *^ emitColor` (src/Lib.hs:136) and `surf * L + e` one level down can overflow.  L <= max_s * max_e + max_e
-    // with max_e the largest emission (as the fp32 product the kernels use) and max_s the largest surface component;
-    // the shortcuts stay on only if that bound, evaluated in double, is comfortably finite in fp32.
-    if (nonneg) {
-        double max_e = 0.0, max_s = 0.0;
-        for (int32_t i = 0; i < sc->n_mats; ++i) {
-            const sq_material& m = sc->mats[i];
-            for (int k = 0; k < 3; ++k) {
-                const float e = m.emissive * m.emit[k];
-                if (!(e - e == 0.0f)) nonneg = false;                    // the product itself is inf
-                max_e = std::max(max_e, (double)e); max_s = std::max(max_s, (double)m.surf[k]);
-            }
-        }
-        if (!(max_s * max_e + max_e <= 3.0e38)) nonneg = false;
-    }
-    for (int32_t i = 0; i < sc->n_tris; ++i) {                       // per-triangle shading record (surface_of)
-        const DevTri& d = tr[(size_t)i]; const sq_material& m = sc->mats[sc->tris[i].mat]; DevSurf& o = sf[(size_t)i];
-        const f3 nrm = sq::cross(sq::mk(d.e1[0], d.e1[1], d.e1[2]), sq::mk(d.e2[0], d.e2[1], d.e2[2]));
-        const f3 em = sq::scale(m.emissive, sq::mk(m.emit[0], m.emit[1], m.emit[2]));
-        o.n[0] = nrm.x; o.n[1] = nrm.y; o.n[2] = nrm.z; o.reflective = m.reflective;
-        o.surf[0] = m.surf[0]; o.surf[1] = m.surf[1]; o.surf[2] = m.surf[2]; o.pad0 = 0;
-        o.emit[0] = em.x; o.emit[1] = em.y; o.emit[2] = em.z; o.pad1 = 0;
-    }
-    // Indexed form for LDS residency: unique vertices (bitwise) + 16-bit indices, when they fit.
-    std::vector<float> uverts; std::vector<uint16_t> trix;
-    {
-        struct Key { uint32_t a, b, c; bool operator==(const Key& o) const { return a == o.a && b == o.b && c == o.c; } };
-        struct KeyHash { size_t operator()(const Key& k) const { return ((size_t)k.a * 0x9E3779B1u) ^ ((size_t)k.b * 0x85EBCA77u) ^ ((size_t)k.c * 0xC2B2AE3Du); } };
-        std::unordered_map<Key, uint32_t, KeyHash> ids;
-        bool fits = sc->n_mats <= 65535;
-        std::vector<uint32_t> idx((size_t)sc->n_tris * 3);
-        for (int32_t i = 0; i < sc->n_tris && fits; ++i) {
-            const float* vs[3] = { sc->tris[i].v0, sc->tris[i].v1, sc->tris[i].v2 };
-            for (int k = 0; k < 3; ++k) {
-                Key key; std::memcpy(&key.a, &vs[k][0], 4); std::memcpy(&key.b, &vs[k][1], 4); std::memcpy(&key.c, &vs[k][2], 4);
-                auto it = ids.find(key);
-                if (it == ids.end()) {
-                    if (ids.size() >= 65535) { fits = false; break; }
-                    it = ids.emplace(key, (uint32_t)ids.size()).first;
-                    uverts.insert(uverts.end(), vs[k], vs[k] + 3); uverts.push_back(0.0f);
-                }
-                idx[(size_t)i * 3 + k] = it->second;
-            }
-        }
-        if (fits) {
-            trix.resize((size_t)sc->n_tris * 4);
-            for (int32_t i = 0; i < sc->n_tris; ++i) {
-                for (int k = 0; k < 3; ++k) trix[(size_t)i * 4 + k] = (uint16_t)idx[(size_t)i * 3 + k];
-                trix[(size_t)i * 4 + 3] = (uint16_t)sc->tris[i].mat;
-            }
-        } else { uverts.clear(); }
-    }
-    // Culling boxes (include/squigly_host.h: sq_cull_boxes), per pre-order node.
-    std::vector<float> cbox((size_t)n * 6); float cull_limits[3] = { -1.0f, 0.25f, 1.5624f };
-    if (sq_cull_boxes(sc, cbox.data(), cull_limits)) return 1;
-    // Resident encoding of the branches (see sq_scene.h): needs encodable leaves and a 24-bit index space.
-    std::vector<uint32_t> rbranch; uint32_t rroot = 0;
-    {
-        bool ok = !trix.empty() && nb < (1 << 24) && sc->n_tris < (1 << 24);
-        for (int32_t i = 0; i < nl && ok; ++i) ok = lf[(size_t)i].count <= 31;
-        auto enc = [&](uint32_t r) -> uint32_t {
-            if (!(r & kLeafBit)) return r;
-            const DevLeaf& L = lf[r & ~kLeafBit];
-            return kLeafBit | ((uint32_t)L.count << 24) | (uint32_t)L.first;
-        };
-        if (ok) {
-            rbranch.resize((size_t)nb * 10);
-            for (int32_t i = 0; i < nb; ++i) {
-                const DevBranch& d = br[(size_t)i];
-                uint32_t* r = &rbranch[(size_t)i * 10];
-                std::memcpy(r, d.lo, 12); std::memcpy(r + 3, &d.lmax, 4); std::memcpy(r + 4, d.hi, 12); std::memcpy(r + 7, &d.rmin, 4);
-                r[8] = enc(d.left) | ((uint32_t)br_axis[(size_t)i] << 29); r[9] = enc(d.right) | (br_grown[(size_t)i] << 29);   // kAxisMask bits: axis | grown children
-            }
-            rroot = enc(ref[0]);
-        } else { trix.clear(); }
-    }
-    // Streaming forms: the culling boxes of a branch's two children, with the branch (GlobalNodes / HybridNodes)
-    std::vector<float> cull_child;
-    if (cull_limits[0] >= 0.0f && nb > 0) {
-        cull_child.resize((size_t)nb * 16);
-        for (int32_t i = 0; i < n; ++i) {
-            if ((sc->nodes[i].kind & 3) == 3) continue;
-            float* o = &cull_child[(size_t)ref[(size_t)i] * 16];
-            const float* l = &cbox[(size_t)(i + 1) * 6]; const float* r = &cbox[(size_t)sc->nodes[i].link * 6];
-            o[0] = l[0]; o[1] = l[1]; o[2] = l[2]; o[3] = 0; o[4] = l[3]; o[5] = l[4]; o[6] = l[5]; o[7] = 0;
-            o[8] = r[0]; o[9] = r[1]; o[10] = r[2]; o[11] = 0; o[12] = r[3]; o[13] = r[4]; o[14] = r[5]; o[15] = 0;
-        }
-    }
-    std::vector<uint32_t> rtail;                                      // resident form: a return's data per branch, one quad
-    for (size_t b = 0; b * 10 < rbranch.size(); ++b) { const uint32_t* r = &rbranch[b * 10]; rtail.insert(rtail.end(), { r[3], r[7], r[8], r[9] }); }
-    std::vector<uint32_t> cull16;                                     // the same boxes as binary16 pairs, for the resident form
-    if (!cull_child.empty()) {
-        cull16.resize((size_t)nb * 8, 0u);
-        for (int32_t b = 0; b < nb; ++b) for (int side = 0; side < 2; ++side) {
-            const float* bx = &cull_child[(size_t)b * 16 + (size_t)side * 8];
-            for (int c = 0; c < 3; ++c) cull16[(size_t)b * 8 + (size_t)side * 4 + (size_t)c] = sq_half_outward(bx[c], 0) | (sq_half_outward(bx[4 + c], 1) << 16);
-        }
-    }
-    // Streaming form: leaf references carry (first, count) themselves when they fit, which saves the dependent
-    // leaf-table load of every leaf visit.
-    bool packed_leaves = sc->n_tris < (1 << 24);
-    for (int32_t i = 0; i < nl && packed_leaves; ++i) packed_leaves = lf[(size_t)i].count <= 31;
-    if (nb >= (1 << 29) || nl >= (1 << 29)) { sq_set_error("scene has %d branches and %d leaves; the device layout holds 2^29 of each", nb, nl); return 1; }
-    uint32_t root_ref = ref[0];
-    {
-        auto enc = [&](uint32_t r) -> uint32_t {
-            if (!packed_leaves || !(r & kLeafBit)) return r;
-            const DevLeaf& L = lf[r & ~kLeafBit];
-            return kLeafBit | ((uint32_t)L.count << 24) | (uint32_t)L.first;
-        };
-        for (int32_t i = 0; i < nb; ++i) {
-            DevBranch& d = br[(size_t)i];
-            d.left = enc(d.left) | ((uint32_t)br_axis[(size_t)i] << 29);   // kAxisMask bits
-            d.right = enc(d.right);
-        }
-        root_ref = enc(root_ref);
-    }
-    // Streaming form: branch record + its children's binary16 culling boxes as ONE packed 80-byte record (SceneView::branches_m,
-    // HybridNodes).  Measured at 64 spp, same process, as a launch option: 1M-triangle scene
-    // trace launches 23.04 -> 22.62 ms, 82k-triangle scene +-0; the same records padded to one 128-byte line each were 16-21 %
-    // SLOWER (26.7 / 23.1 ms): the form lives on what stays in L2, i.e. on the table's footprint, not on lines per visit
-    // (profiles/r03t_merged_branches_ab.txt)
-    std::vector<uint32_t> br_m5;
-    br_m5.assign((size_t)nb * 20, 0u);                    // (a scene without culling boxes keeps zeros there: they are never read)
-    for (int32_t b = 0; b < nb; ++b) {
-        std::memcpy(&br_m5[(size_t)b * 20], &br[(size_t)b], 48);
-        if (!cull16.empty()) std::memcpy(&br_m5[(size_t)b * 20 + 12], &cull16[(size_t)b * 8], 32);
-    }
-    // Emissive triangles (for the last-bounce shortcut of sq_shade1).  Disabled (-1) when a material value is not
-    // finite (then s*0 + e is not exactly +0 for non-emitters) or when the list is long enough to cost more than it saves.
-    std::vector<int32_t> emitters; int32_t n_emitters = -1;
-    {
-        bool finite = true;
-        std::vector<char> emits((size_t)sc->n_mats, 0);
-        for (int32_t i = 0; i < sc->n_mats; ++i) {
-            const sq_material& m = sc->mats[i];
-            const float comp[8] = { m.reflective, m.surf[0], m.surf[1], m.surf[2], m.emissive, m.emit[0], m.emit[1], m.emit[2] };
-            for (float c : comp) if (!(c - c == 0.0f)) finite = false;
-            for (int k = 0; k < 3; ++k) { const float e = m.emissive * m.emit[k]; uint32_t bits; std::memcpy(&bits, &e, 4); if (bits != 0u) emits[(size_t)i] = 1; }
-        }
-        for (int32_t i = 0; i < sc->n_tris; ++i) if (emits[(size_t)sc->tris[i].mat]) emitters.push_back(i);
-        if (finite && emitters.size() <= 64) n_emitters = (int32_t)emitters.size();
-    }
+    PackedScene P;
+    if (sq_pack_scene(*sc, P)) return 1;
     SQ_HIP(hipSetDevice(device));
     sq_device_scene* s = new sq_device_scene;
-    s->device = device; s->height = height;
-    s->small_index = nb < 0x8000 && sc->n_tris < 0x8000;
+    s->device = device; s->height = P.height; s->small_index = P.small_index;
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) s->n_cu = prop.multiProcessorCount;
     // One arena for every array of the scene: one hipMalloc, one host-packed hipMemcpy and (sq_scene_free) one hipFree
     // instead of thirteen of each -- the one-shot calls upload and free a scene per frame, and at the CLI's default frame
     // (540 x 540 at 10 samples) those calls were a third of the call's time.  Every array starts on a 256-byte boundary.
-    struct Piece { void** dst; const void* src; size_t bytes, off; };
-    std::vector<Piece> pieces;
-    size_t arena_bytes = 0;
-    auto up = [&](void** dst, const void* src, size_t bytes) {
-        pieces.push_back(Piece{ dst, src, bytes, arena_bytes });
-        arena_bytes += ((bytes ? bytes : 16) + 255) & ~(size_t)255;
-    };
-    up(&s->d_branches, br.data(), br.size() * sizeof(DevBranch)); up(&s->d_leaves, lf.data(), lf.size() * sizeof(DevLeaf));
-    up(&s->d_tris, tr.data(), tr.size() * sizeof(DevTri)); up(&s->d_tri_mat, tri_mat.data(), tri_mat.size() * sizeof(int32_t));
-    up(&s->d_surfs, sf.data(), sf.size() * sizeof(DevSurf)); up(&s->d_mats, mt.data(), mt.size() * sizeof(DevMat));
-    up(&s->d_verts, uverts.data(), uverts.size() * sizeof(float)); up(&s->d_trix, trix.data(), trix.size() * sizeof(uint16_t));
-    up(&s->d_rbranch, rbranch.data(), rbranch.size() * sizeof(uint32_t));
-    up(&s->d_emitters, emitters.data(), emitters.size() * sizeof(int32_t));
-    if (!cull_child.empty()) up(&s->d_cull_child, cull_child.data(), cull_child.size() * sizeof(float));
-    if (!cull16.empty()) up(&s->d_cull16, cull16.data(), cull16.size() * sizeof(uint32_t));
-    up(&s->d_rtail, rtail.data(), rtail.size() * sizeof(uint32_t));
-    if (!br_m5.empty()) up(&s->d_branches_m5, br_m5.data(), br_m5.size() * sizeof(uint32_t));
-    {
-        std::vector<unsigned char> staging(arena_bytes, 0);
-        for (const Piece& pc : pieces) if (pc.bytes) std::memcpy(staging.data() + pc.off, pc.src, pc.bytes);
-        if (hipMalloc(&s->d_arena, arena_bytes) != hipSuccess) { sq_scene_free(s); return sq_set_error("hipMalloc(%zu) for the scene failed", arena_bytes); }
-        if (hipMemcpy(s->d_arena, staging.data(), arena_bytes, hipMemcpyHostToDevice) != hipSuccess) { sq_scene_free(s); return sq_set_error("hipMemcpy H2D of the scene failed"); }
-        for (const Piece& pc : pieces) *pc.dst = (char*)s->d_arena + pc.off;
-    }
+    // The table: each SceneView member and its vector, in arena order; an empty optional array takes no room and stays nullptr.
     SceneView& v = s->view;
-    v.branches = (const float4*)s->d_branches; v.leaves = (const int2*)s->d_leaves;
-    v.tris = (const float*)s->d_tris; v.tri_mat = (const int32_t*)s->d_tri_mat; v.mats = (const float4*)s->d_mats; v.surfs = (const float4*)s->d_surfs;
+    auto arrays = [&](auto&& f) {
+        f(v.branches, P.branches, false); f(v.leaves, P.leaves, false); f(v.tris, P.tris, false); f(v.tri_mat, P.tri_mat, false);
+        f(v.surfs, P.surfs, false); f(v.mats, P.mats, false); f(v.verts4, P.verts4, false); f(v.trix, P.trix, false);
+        f(v.rbranch, P.rbranch, false); f(v.emitters, P.emitters, false);
+        f(v.cull_child, P.cull_child, true); f(v.cull_child16, P.cull_child16, true); f(v.branches_m, P.branches_m, true);
+    };
+    auto slot = [](size_t bytes) { return ((bytes ? bytes : 16) + 255) & ~(size_t)255; };
+    size_t arena_bytes = 0;
+    arrays([&](auto&, const auto& vec, bool optional) { if (!optional || !vec.empty()) arena_bytes += slot(vec.size() * sizeof(vec[0])); });
+    if (hipMalloc(&s->d_arena, arena_bytes) != hipSuccess) { sq_scene_free(s); return sq_set_error("hipMalloc(%zu) for the scene failed", arena_bytes); }
+    std::vector<unsigned char> staging(arena_bytes, 0);
+    size_t off = 0;
+    arrays([&](auto& member, const auto& vec, bool optional) {
+        if (optional && vec.empty()) return;
+        const size_t bytes = vec.size() * sizeof(vec[0]);
+        if (bytes) std::memcpy(staging.data() + off, vec.data(), bytes);
+        member = reinterpret_cast<std::remove_reference_t<decltype(member)>>((const char*)s->d_arena + off);
+        off += slot(bytes);
+    });
+    if (hipMemcpy(s->d_arena, staging.data(), arena_bytes, hipMemcpyHostToDevice) != hipSuccess) { sq_scene_free(s); return sq_set_error("hipMemcpy H2D of the scene failed"); }
+    if (P.trix.empty()) v.trix = nullptr;                  // "not encodable" (the slot stays, so that later arrays keep their offsets)
     for (int c = 0; c < 3; ++c) { v.root_lo[c] = sc->root.lo[c]; v.root_hi[c] = sc->root.hi[c]; }
-    v.root_ref = root_ref; v.packed_leaves = packed_leaves ? 1 : 0;
-    v.n_branches = nb; v.n_leaves = nl; v.n_tris = sc->n_tris; v.n_mats = sc->n_mats;
-    v.height = height; v.nonneg_materials = nonneg ? 1 : 0;
-    {
-        bool fin = true;
-        auto ok = [](float c) { return c - c == 0.0f; };
-        for (const DevBranch& d : br) for (int c = 0; c < 3; ++c) fin = fin && ok(d.lo[c]) && ok(d.hi[c]);
-        for (const DevBranch& d : br) fin = fin && ok(d.lmax) && ok(d.rmin);
-        for (int c = 0; c < 3; ++c) fin = fin && ok(sc->root.lo[c]) && ok(sc->root.hi[c]);
-        for (int32_t i = 0; i < sc->n_tris && fin; ++i) for (int c = 0; c < 3; ++c) fin = fin && ok(sc->tris[i].v0[c]) && ok(sc->tris[i].v1[c]) && ok(sc->tris[i].v2[c]);
-        v.finite_geometry = fin ? 1 : 0;
-    }
-    v.verts4 = (const float4*)s->d_verts; v.trix = trix.empty() ? nullptr : (const ushort4*)s->d_trix; v.n_verts = (int32_t)(uverts.size() / 4);
-    v.rbranch = (const uint32_t*)s->d_rbranch; v.rroot = rroot;
-    v.emitters = (const int32_t*)s->d_emitters; v.n_emitters = n_emitters;
-    v.cull_o2max = cull_limits[0]; v.cull_d2min = cull_limits[1]; v.cull_d2max = cull_limits[2];
-    v.incremental_ok = (incremental_ok && v.finite_geometry) ? 1 : 0;
-    v.branches_m = (const float4*)s->d_branches_m5;
-    s->n_grown = 0; for (uint32_t g : br_grown) s->n_grown += (g & 1u) + (g >> 1);
-    v.cull_child = (const float4*)s->d_cull_child; v.cull_child16 = (const uint4*)s->d_cull16; v.rtail = (const uint4*)s->d_rtail;
+    v.root_ref = P.root_ref; v.packed_leaves = P.packed_leaves; v.rroot = P.rroot;
+    v.n_branches = P.nb; v.n_leaves = P.nl; v.n_tris = sc->n_tris; v.n_mats = sc->n_mats; v.n_verts = P.n_verts; v.n_emitters = P.n_emitters;
+    v.height = P.height; v.nonneg_materials = P.nonneg_materials; v.finite_geometry = P.finite_geometry;
+    v.cull_o2max = P.cull_limits[0]; v.cull_d2min = P.cull_limits[1]; v.cull_d2max = P.cull_limits[2];
+    v.rtail = nullptr; v.incremental_ok = 0;               // unread by every kernel (sq_scene.h)
     *out = s;
     return 0;
 }

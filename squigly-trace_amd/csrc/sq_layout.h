@@ -1,0 +1,40 @@
+// sq_layout.h — the records and bit positions of the device-resident scene, free of any HIP include: what the host packer
+// (sq_host.cpp, sq_pack.h) writes and the kernels (sq_scene.h) read.  Citations are relative to the reference repository root.
+#pragma once
+#include <stdint.h>
+namespace sqd {
+constexpr uint32_t kLeafBit = 0x80000000u;   // child reference: leaf index | kLeafBit, or branch index
+
+// HBM layout (read-only during a render).  Branches are numbered breadth-first so that the top
+// of the tree is a prefix of the table (that prefix is what gets staged in LDS).
+struct DevBranch {          // 48 B, three 16-byte quads
+    float lo[3]; float lmax;    // traversal box of THIS branch: root bounds clipped along the path (src/BIH.hs:130-141)
+    float hi[3]; float rmin;
+    float lmax2, rmin2;         // the third quad alone serves a return into this branch (planes, axis, children):
+    uint32_t left, right;       //   one 16-byte load instead of three.  Bits 30..29 of `left` hold the split axis.
+};
+struct DevLeaf { int32_t first, count; };
+struct DevTri {             // 36 B: v0 | e1 = v1 - v0 | e2 = v2 - v0 (same rounding as src/Geometry.hs:130-131).
+    float v0[3];            // Unpadded on purpose: the streaming kernel is bound by L2/MALL/HBM bytes on large
+    float e1[3];            // scenes; the material index lives in its own array because only shading needs it.
+    float e2[3];
+};
+struct DevMat { float reflective, sr, sg, sb, emissive, er, eg, eb; };   // 32 B
+struct DevSurf {            // 48 B, three quads: everything shading needs from a hit triangle behind ONE index
+    float n[3], reflective;     // normal = e1 x e2 (src/Geometry.hs:79-80) | Material.reflective
+    float surf[3], pad0;        // surfColor
+    float emit[3], pad1;        // emissive *^ emitColor (src/Lib.hs:136), the same fp32 products as on the device
+};
+static_assert(sizeof(DevBranch) == 48 && sizeof(DevLeaf) == 8 && sizeof(DevTri) == 36 && sizeof(DevMat) == 32 && sizeof(DevSurf) == 48,
+              "the device records have the sizes their comments promise");
+
+constexpr int kAxisShift = 29;                                 // a branch's reference words keep two flag bits each at 30..29:
+constexpr uint32_t kAxisMask = 3u << kAxisShift;               //   the LEFT word the split axis,
+// the RIGHT word of the resident form "the left / the right child's box GROWS", i.e. the plane that replaces one of this branch's
+// own (lmax for hi[axis], rmin for lo[axis], src/BIH.hs:130-141) lies outside this branch's box.  That happens where
+// lmax = max + 0.001 or rmin = min - 0.001 (src/BIH.hs:92-95) passes a plane of the root box that no ancestor has clipped yet
+// (5 of scene.obj's 1278 children).  The packer still sets them (the removed incremental slab test read them);
+// every reader masks them off.
+constexpr uint32_t kGrownLeft = 1u, kGrownRight = 2u;
+constexpr int kTriRunPad = 3;   // zero triangles after the last one, so that a run of loads may start at any triangle (GlobalTris::kRunPad)
+}  // namespace sqd

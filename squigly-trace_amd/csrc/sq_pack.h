@@ -1,0 +1,36 @@
+// sq_pack.h — the scene packer (sq_host.cpp): everything sq_scene_upload decides and lays out before it touches a device.
+// Plain host C++, no HIP include, so it runs, is tested (tests/test_pack.py) and is sanitized on a CPU.
+#pragma once
+#include <cstdint>
+#include <vector>
+
+#include "../../include/squigly_hip.h"
+#include "sq_layout.h"
+
+struct PackedScene {
+    // one vector per device array, named after the SceneView member it feeds (sq_scene.h)
+    std::vector<sqd::DevBranch> branches;           // breadth-first; left / right are the references the streaming forms read
+    std::vector<sqd::DevLeaf> leaves;               // pre-order
+    std::vector<sqd::DevTri> tris;                  // leaf order, then kTriRunPad zero records
+    std::vector<int32_t> tri_mat;
+    std::vector<sqd::DevSurf> surfs;
+    std::vector<sqd::DevMat> mats;
+    std::vector<float> verts4;                      // unique vertices, 4 floats each; empty unless 16-bit indices fit
+    std::vector<uint16_t> trix;                     // 4 per triangle; empty unless the resident form can be encoded
+    std::vector<uint32_t> rbranch;                  // 10 words per branch, with trix
+    std::vector<int32_t> emitters;
+    std::vector<float> cull_child;                  // 16 floats per branch; empty when nothing may be culled
+    std::vector<uint32_t> cull_child16;             // 8 words per branch, with cull_child
+    std::vector<uint32_t> branches_m;               // 20 words per branch
+    int32_t nb = 0, nl = 0, height = 0;
+    uint32_t root_ref = 0, rroot = 0;
+    bool packed_leaves = false, nonneg_materials = false, finite_geometry = false;
+    int32_t n_emitters = -1, n_verts = 0;
+    float cull_limits[3] = { -1.0f, 0.25f, 1.5624f };   // SceneView::cull_o2max, cull_d2min, cull_d2max
+    bool small_index = false;                       // < 0x8000 branches and triangles: 2-byte stack words
+};
+
+// The checks sq_scene_upload and sq_scene_pack make on their arguments before anything else: 0, or sq_set_error.
+int sq_check_scene_args(const sq_scene* sc, const void* out);
+// Validates the tree and fills `out`: 0, or sq_set_error.  `sc` has passed sq_check_scene_args.
+int sq_pack_scene(const sq_scene& sc, PackedScene& out);

@@ -5,12 +5,11 @@
 #include <stdint.h>
 #include <type_traits>
 
+#include "sq_layout.h"
 #include "sq_math.h"
 
 namespace sqd {
 using sq::f3;
-
-constexpr uint32_t kLeafBit = 0x80000000u;   // child reference: leaf index | kLeafBit, or branch index
 
 // Builtin vector types and explicit LDS (address space 3) pointers: a load through an LDS-qualified
 // pointer is always a ds_read, never a flat load, and cannot be merged with a global pointer.
@@ -20,27 +19,6 @@ typedef float v2f __attribute__((ext_vector_type(2)));
 typedef unsigned short v4us __attribute__((ext_vector_type(4)));
 #define SQ_LDS __attribute__((address_space(3)))
 template <typename T> __device__ __forceinline__ SQ_LDS T* to_lds(void* generic) { return (SQ_LDS T*)generic; }
-
-// HBM layout (read-only during a render).  Branches are numbered breadth-first so that the top
-// of the tree is a prefix of the table (that prefix is what gets staged in LDS).
-struct DevBranch {          // 48 B, three 16-byte quads
-    float lo[3]; float lmax;    // traversal box of THIS branch: root bounds clipped along the path (src/BIH.hs:130-141)
-    float hi[3]; float rmin;
-    float lmax2, rmin2;         // the third quad alone serves a return into this branch (planes, axis, children):
-    uint32_t left, right;       //   one 16-byte load instead of three.  Bits 30..29 of `left` hold the split axis.
-};
-struct DevLeaf { int32_t first, count; };
-struct DevTri {             // 36 B: v0 | e1 = v1 - v0 | e2 = v2 - v0 (same rounding as src/Geometry.hs:130-131).
-    float v0[3];            // Unpadded on purpose: the streaming kernel is bound by L2/MALL/HBM bytes on large
-    float e1[3];            // scenes; the material index lives in its own array because only shading needs it.
-    float e2[3];
-};
-struct DevMat { float reflective, sr, sg, sb, emissive, er, eg, eb; };   // 32 B
-struct DevSurf {            // 48 B, three quads: everything shading needs from a hit triangle behind ONE index
-    float n[3], reflective;     // normal = e1 x e2 (src/Geometry.hs:79-80) | Material.reflective
-    float surf[3], pad0;        // surfColor
-    float emit[3], pad1;        // emissive *^ emitColor (src/Lib.hs:136), the same fp32 products as on the device
-};
 
 struct SceneView {
     const float4* branches;   // 3 quads per branch
@@ -69,12 +47,11 @@ struct SceneView {
     // skips the leaf's triangles -- mollerTrumbore would reject them all.  cull_o2max < 0: nothing is culled.
     float cull_o2max, cull_d2min, cull_d2max;
     const float4* cull_child; // streaming form: 4 quads per branch, the culling boxes (lo, hi) of its left and of its right child; or nullptr
-    const uint4* rtail;       // resident form: (lmax, rmin, left word, right word) per branch.  Read by no kernel since the global-tail variant was removed.
+    const uint4* rtail;       // always nullptr: read by no kernel and filled by no upload, it only holds the kernel-argument layout
     const uint4* cull_child16; // 2 quads per branch, the same boxes as binary16 pairs (x, y, z, unused), left child then right; or nullptr
     const float4* branches_m;  // streaming form: the 48-byte branch record and the 32 bytes of its children's binary16 culling boxes as ONE
                                //   packed record of 5 quads (HybridNodes): a visit touches 1.5 lines on average instead of 2.3
-    int32_t incremental_ok;    // 1: every child interval of the tree is regular or grown (kGrownLeft / kGrownRight) and the geometry is
-                               // finite.  Read by no kernel since the incremental slab test was removed.
+    int32_t incremental_ok;    // always 0: like rtail, it only holds the kernel-argument layout
 };
 
 struct Hit { float t; int32_t tri; };   // tri < 0 : Nothing.  dist is derived from t on demand (hit_dist)
@@ -294,13 +271,7 @@ template <> struct StackTraits<uint32_t> { static constexpr uint32_t flag = 0x80
 struct BranchData { v4f q0, q1; int axis; uint32_t left, right; };   // q0 = lo.xyz,lmax ; q1 = hi.xyz,rmin
 
 struct BranchTail { float lmax, rmin; int axis; uint32_t left, right; };   // what a return into a branch needs
-constexpr uint32_t kAxisMask = 0x60000000u;     // bits 30..29 of a branch's LEFT reference word: the split axis
-// Resident form, bits 30..29 of the RIGHT reference word: "the left / the right child's box GROWS", i.e. the plane that
-// replaces one of this branch's own (lmax for hi[axis], rmin for lo[axis], src/BIH.hs:130-141) lies outside this branch's box.
-// That happens where lmax = max + 0.001 or rmin = min - 0.001 (src/BIH.hs:92-95) passes a plane of the root box that no
-// ancestor has clipped yet (5 of scene.obj's 1278 children).  The upload still sets them (the removed incremental slab test read
-// them); every reader masks them off.
-constexpr uint32_t kGrownLeft = 1u, kGrownRight = 2u;
+// (kAxisMask, kGrownLeft / kGrownRight: bits 30..29 of a branch's reference words, sq_layout.h)
 __device__ __forceinline__ BranchTail unpack_tail(v4f q2) {
     const uint32_t l = __float_as_uint(q2.z);
     return BranchTail{ q2.x, q2.y, (int)((l >> 29) & 3u), l & ~kAxisMask, __float_as_uint(q2.w) };
@@ -433,7 +404,7 @@ struct GlobalTris {
         }
     }
     __device__ __forceinline__ void get1(int i, f3& v0, f3& e1, f3& e2) const { get_n<1>(i, &v0, &e1, &e2); }   // two 16-byte loads + one dword
-    static constexpr int kRunPad = 3;            // zero triangles after the last one (upload), so a run may start at any triangle
+    static constexpr int kRunPad = kTriRunPad;   // zero triangles after the last one (sq_layout.h), so a run may start at any triangle
     template <int N>
     __device__ __forceinline__ void get_run(int i, f3* v0, f3* e1, f3* e2) const { get_n<N>(i, v0, e1, e2); }
     __device__ __forceinline__ int2 leaf(uint32_t ref) const {

@@ -379,12 +379,9 @@ def test_config_c4_shard_of_eight(sqt, product_scene, oracle_scene, dev):
         assert np.array_equal(rgb[j:j + 1].cpu().numpy(), o8)
 
 
-@pytest.mark.parametrize("seed,n_emit", [(1, 3), (2, 0), (3, 70), (4, 12), (5, 64), (6, 65)])
-def test_random_soups_with_mirrors_and_emitters(sqt, O, seed, n_emit):
-    """Random triangle soups with diffuse, half-mirror, full-mirror and emissive triangles: exercises the
-    once-per-pixel mirror ray, the last-bounce emitter test (few emitters), its off switch (70 > 64 emitters),
-    a scene without emitters, occluded emitters, and COMBINE frames on overlapping geometry.  64 emitters is the longest
-    list the shortcut takes (csrc/sq_device.hip, sq_scene_upload), 65 turns it off."""
+def _emitter_soup(sqt, seed, n_emit):
+    """A soup of 400 triangles with diffuse, half-mirror and full-mirror materials and n_emit emitting triangles:
+    (tris, mats, v, mat).  tests/test_pack.py packs the same soups on the CPU."""
     rng = np.random.default_rng(seed)
     n = 400
     c = rng.uniform(-1.5, 1.5, (n, 1, 3))
@@ -398,6 +395,17 @@ def test_random_soups_with_mirrors_and_emitters(sqt, O, seed, n_emit):
     mat[rng.choice(n, n_emit, replace=False)] = 3
     tris = np.zeros(n, sqt._native.TRI_DTYPE)
     tris["v0"], tris["v1"], tris["v2"], tris["mat"] = v[:, 0], v[:, 1], v[:, 2], mat
+    return tris, mats, v, mat
+
+
+@pytest.mark.parametrize("seed,n_emit", [(1, 3), (2, 0), (3, 70), (4, 12), (5, 64), (6, 65)])
+def test_random_soups_with_mirrors_and_emitters(sqt, O, seed, n_emit):
+    """Random triangle soups with diffuse, half-mirror, full-mirror and emissive triangles: exercises the
+    once-per-pixel mirror ray, the last-bounce emitter test (few emitters), its off switch (70 > 64 emitters),
+    a scene without emitters, occluded emitters, and COMBINE frames on overlapping geometry.  64 emitters is the longest
+    list the shortcut takes (csrc/sq_host.cpp, the packer's emitter_list), 65 turns it off."""
+    tris, mats, v, mat = _emitter_soup(sqt, seed, n_emit)
+    n = len(tris)
     bih = sqt.BIH(sqt.Mesh.from_arrays(tris, mats))
     ot = np.zeros(n, O.TRI_DTYPE)
     ot["a"], ot["b"], ot["c"] = v[:, 0], v[:, 1], v[:, 2]

@@ -1,0 +1,364 @@
+"""The scene packer (csrc/sq_host.cpp, sq_pack_scene) through its C-ABI window (sq_scene_pack, include/squigly_host.h): every
+array sq_scene_upload copies to the device and every flag that chooses a kernel form, on the CPU.
+
+* bit-equality with the commit the packer was lifted from: tests/golden/pack_digests.json holds byte counts, SHA-256 digests
+  and scalars of every fixture scene as that commit's sq_scene_upload produced them;
+* structure, independent of that commit: the branch table decodes back to the caller's tree, the tables agree with each other;
+* the material and geometry flags on both sides of their bounds; every refusal with its exact text;
+* the packer under AddressSanitizer and UndefinedBehaviorSanitizer, as a stand-alone program (tests/pack_main.cpp).
+
+Not covered: the 2^24-triangle switch (a scene of that size needs gigabytes and far more than a few seconds to build).
+"""
+import ctypes as C
+import hashlib
+import json
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import tree_padding as TP
+from conftest import DATA, GOLDEN, ROOT
+
+ARRAYS = ["branches", "leaves", "tris", "tri_mat", "surfs", "mats", "verts4", "trix", "rbranch", "emitters", "cull_child",
+          "cull_child16", "branches_m"]
+SCALARS = ["n_branches", "n_leaves", "height", "root_ref", "rroot", "packed_leaves", "nonneg_materials", "finite_geometry",
+           "n_emitters", "n_verts", "cull_o2max", "cull_d2min", "cull_d2max", "small_index"]
+LEAF_BIT, AXIS_MASK, RUN_PAD = 0x80000000, 0x60000000, 3
+BRANCH = np.dtype([("lo", "<f4", 3), ("lmax", "<f4"), ("hi", "<f4", 3), ("rmin", "<f4"), ("lmax2", "<f4"), ("rmin2", "<f4"),
+                   ("left", "<u4"), ("right", "<u4")])
+SQ_TEXT = b"newmtl A\nreflective 0 1 1 1\nemissive 1 1 1 1\n"
+
+
+def pack(sqt, holder):
+    """sq_scene_pack of holder.scene (the holder keeps the arrays alive): ({array name: bytes}, {scalar name: int})."""
+    L, h = sqt.lib(), C.c_void_p()
+    sqt._native.check(L.sq_scene_pack(C.byref(holder.scene), C.byref(h)))
+    try:
+        arrays, scalars = {}, {}
+        for name in ARRAYS:
+            data, n = C.c_void_p(), C.c_size_t()
+            assert L.sq_packed_array(h, name.encode(), C.byref(data), C.byref(n)) == 0, name
+            arrays[name] = C.string_at(data, n.value) if n.value else b""
+        for name in SCALARS:
+            v = C.c_int64()
+            assert L.sq_packed_scalar(h, name.encode(), C.byref(v)) == 0, name
+            scalars[name] = v.value
+        assert L.sq_packed_array(h, b"rtail", C.byref(data), C.byref(n)) != 0          # unknown names are refused
+        assert L.sq_packed_scalar(h, b"incremental_ok", C.byref(v)) != 0
+    finally:
+        L.sq_packed_free(h)
+    return arrays, scalars
+
+
+def refusal(sqt, scene_ref, out_ref=None):
+    h = C.c_void_p()
+    assert sqt.lib().sq_scene_pack(scene_ref, C.byref(h) if out_ref is None else out_ref) != 0
+    return sqt.lib().sq_last_error().decode()
+
+
+class RawScene:
+    """An sq_scene over arrays given as they are (no builder): nodes as (kind, lmax, rmin, link) rows."""
+
+    def __init__(self, sqt, nodes, tris=None, mats=None, root=((-1, -1, -1), (1, 1, 1)), height=0):
+        N = sqt._native
+        self.nodes = np.array(nodes, N.NODE_DTYPE)
+        self.tris = np.zeros(0, N.TRI_DTYPE) if tris is None else tris
+        self.mats = np.zeros(0, N.MAT_DTYPE) if mats is None else mats
+        sc = self.scene = N.Scene()
+        sc.root.lo[:], sc.root.hi[:] = root[0], root[1]
+        sc.nodes, sc.n_nodes = self.nodes.ctypes.data, len(self.nodes)
+        sc.tris, sc.n_tris = (self.tris.ctypes.data if len(self.tris) else None), len(self.tris)
+        sc.mats, sc.n_mats = (self.mats.ctypes.data if len(self.mats) else None), len(self.mats)
+        sc.height = height
+
+
+def one_triangle(sqt, material=None, n_mats=1, v=((0, 0, 0), (1, 0, 0), (0, 1, 0)), **kw):
+    """A single leaf over one triangle of material 0; material: {field: value} over a plain grey material."""
+    N = sqt._native
+    tris = np.zeros(1, N.TRI_DTYPE)
+    tris["v0"], tris["v1"], tris["v2"] = v
+    mats = np.zeros(n_mats, N.MAT_DTYPE)
+    mats["surf"] = 0.5
+    for k, val in (material or {}).items():
+        mats[k][0] = val
+    return RawScene(sqt, [(3 | (1 << 2), 0, 0, 0)], tris, mats, **kw)
+
+
+def disjoint_triangles(sqt, n):
+    """n triangles on a grid that share no vertex: 3 n unique vertices."""
+    N = sqt._native
+    i = np.arange(n)
+    x, y = (i % 256).astype(np.float32), (i // 256).astype(np.float32)
+    tris = np.zeros(n, N.TRI_DTYPE)
+    tris["v0"] = np.stack([x, y, 0 * x], 1)
+    tris["v1"] = np.stack([x + 0.5, y, 0 * x], 1)
+    tris["v2"] = np.stack([x, y + 0.5, 0 * x + 0.25], 1)
+    mats = np.zeros(1, N.MAT_DTYPE)
+    mats["surf"] = 0.5
+    return sqt.BIH(sqt.Mesh.from_arrays(tris, mats))
+
+
+def fixture_scenes(sqt, O):
+    """{name: object with .scene}: data/scene.obj and the smallest scenes on each side of every switch of the packer."""
+    from test_gpu_limits import _big_leaf
+    from test_gpu_parity import _emitter_soup
+    base = sqt.BIH(sqt.Mesh.from_obj(os.path.join(DATA, "scene.obj"), DATA))
+    cam_o = O.load_camera(os.path.join(DATA, "camera"))
+    out = {"scene_obj": base,
+           "padded": TP.PaddedScene(base, TP.root_chain(5)),
+           "verts_65535": disjoint_triangles(sqt, 21845), "verts_65536": disjoint_triangles(sqt, 21846),
+           "empty": sqt.BIH(sqt.Mesh.from_text(b"mtllib s.sq\n", SQ_TEXT)),
+           "one_branch": sqt.BIH(sqt.Mesh.from_text(b"mtllib s.sq\no X\nv -1 0 -1\nv 1 0 -1\nv 0 1 1\nusemtl A\n" + b"f 1 2 3\n" * 20, SQ_TEXT))}
+    for count in (31, 32):
+        out[f"leaf_{count}"] = sqt.BIH(sqt.Mesh.from_arrays(*_big_leaf(sqt, O, base, cam_o, count)))
+    for seed, n_emit in ((5, 64), (6, 65)):
+        out[f"emitters_{n_emit}"] = sqt.BIH(sqt.Mesh.from_arrays(*_emitter_soup(sqt, seed, n_emit)[:2]))
+    return out
+
+
+@pytest.fixture(scope="module")
+def fixtures(sqt, O):
+    return fixture_scenes(sqt, O)
+
+
+@pytest.fixture(scope="module")
+def packed(sqt, fixtures):
+    return {name: pack(sqt, f) for name, f in fixtures.items()}
+
+
+def digest_of(arrays, scalars):
+    return {"arrays": {k: {"bytes": len(v), "sha256": hashlib.sha256(v).hexdigest()} for k, v in arrays.items()}, "scalars": scalars}
+
+
+# ---- bit-equality with the commit the packer came from ----
+
+def test_fixtures_sit_on_both_sides_of_every_switch(fixtures, packed):
+    s = {k: v[1] for k, v in packed.items()}
+    a = {k: v[0] for k, v in packed.items()}
+    assert s["verts_65535"]["n_verts"] == 65535 and len(a["verts_65535"]["trix"]) > 0
+    assert s["verts_65536"]["n_verts"] == 0 and len(a["verts_65536"]["trix"]) == 0 and len(a["verts_65536"]["verts4"]) == 0
+    assert fixtures["leaf_31"].longest_leaf == 31 and s["leaf_31"]["packed_leaves"] == 1 and len(a["leaf_31"]["rbranch"]) > 0
+    assert fixtures["leaf_32"].longest_leaf == 32 and s["leaf_32"]["packed_leaves"] == 0 and len(a["leaf_32"]["rbranch"]) == 0
+    assert len(a["leaf_32"]["trix"]) == 0 and s["leaf_32"]["n_verts"] > 0      # the vertices stay, the index form goes
+    assert s["emitters_64"]["n_emitters"] == 64 and s["emitters_65"]["n_emitters"] == -1 and len(a["emitters_65"]["emitters"]) == 65 * 4
+    assert (s["empty"]["n_branches"], s["empty"]["n_leaves"], len(a["empty"]["tris"])) == (0, 1, RUN_PAD * 36)
+    assert s["empty"]["cull_o2max"] == np.float32(-1).view(np.uint32) and a["empty"]["cull_child"] == b""
+    assert (s["one_branch"]["n_branches"], s["one_branch"]["n_leaves"], s["one_branch"]["height"]) == (1, 2, 2)
+
+
+def test_packed_bytes_equal_the_recorded_ones(packed):
+    """Every array (byte count, SHA-256) and every scalar of every fixture scene is what the recorded commit's
+    sq_scene_upload built (the JSON says which commit and how)."""
+    golden = json.load(open(os.path.join(GOLDEN, "pack_digests.json")))
+    assert golden["commit"].startswith("d305fd1")
+    assert set(golden["scenes"]) == set(packed)
+    for name, (arrays, scalars) in packed.items():
+        got, want = digest_of(arrays, scalars), golden["scenes"][name]
+        assert set(want["arrays"]) == set(ARRAYS) and set(want["scalars"]) == set(SCALARS)
+        for k in ARRAYS:
+            assert got["arrays"][k] == want["arrays"][k], (name, k)
+        assert got["scalars"] == want["scalars"], name
+
+
+@pytest.mark.parametrize("n_mats,fits", [(65535, True), (65536, False)])
+def test_material_count_switch(sqt, n_mats, fits):
+    """The 16-bit material index of a trix record: 65535 materials fit, 65536 do not (too large for a recorded fixture)."""
+    arrays, scalars = pack(sqt, one_triangle(sqt, n_mats=n_mats))
+    assert (len(arrays["trix"]) == 8) == fits and (scalars["n_verts"] == 3) == fits and len(arrays["mats"]) == 32 * n_mats
+
+
+# ---- structure ----
+
+def decode_tree(branches, leaves, scalars):
+    """The pre-order sq_node rows the branch table stands for, and the branch number at each pre-order position (-1: leaf)."""
+    rows, number = [], []
+    todo = [("visit", scalars["root_ref"])]
+    while todo:
+        what, x = todo.pop()
+        if what == "link":                                 # the left subtree of rows[x] is complete: its right child comes next
+            rows[x][3] = len(rows)
+            continue
+        if x & LEAF_BIT:
+            first, count = ((x & 0xFFFFFF, (x >> 24) & 31) if scalars["packed_leaves"] else
+                            (int(leaves[x & ~LEAF_BIT][0]), int(leaves[x & ~LEAF_BIT][1])))
+            rows.append([3 | (count << 2), np.float32(0), np.float32(0), first]); number.append(-1)
+            continue
+        b = branches[x]
+        rows.append([(int(b["left"]) >> 29) & 3, b["lmax"], b["rmin"], -1]); number.append(x)
+        todo += [("visit", int(b["right"])), ("link", len(rows) - 1), ("visit", int(b["left"]) & ~AXIS_MASK)]
+    return rows, np.array(number)
+
+
+@pytest.mark.parametrize("name", ["scene_obj", "padded"])
+def test_tables_decode_to_the_tree_and_agree_with_each_other(sqt, fixtures, packed, name):
+    nodes = fixtures[name].nodes
+    arrays, s = packed[name]
+    branches = np.frombuffer(arrays["branches"], BRANCH)
+    leaves = np.frombuffer(arrays["leaves"], "<i4").reshape(-1, 2)
+    nb = s["n_branches"]
+    assert len(branches) == nb and len(leaves) == s["n_leaves"] and nb + s["n_leaves"] == len(nodes)
+    rows, number = decode_tree(branches, leaves, s)
+    assert len(rows) == len(nodes)
+    for field, col in (("kind", 0), ("lmax", 1), ("rmin", 2), ("link", 3)):
+        want = nodes[field]
+        got = np.array([r[col] for r in rows], want.dtype)
+        assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), field
+    num, _ = TP.bfs_branch_numbers(nodes)                  # breadth-first, stable within a level
+    assert np.array_equal(number, num)
+    assert np.array_equal(branches["lmax2"].view(np.uint32), branches["lmax"].view(np.uint32))
+    assert np.array_equal(branches["rmin2"].view(np.uint32), branches["rmin"].view(np.uint32))
+    words = np.frombuffer(arrays["branches"], "<u4").reshape(nb, 12)
+    # rbranch: lo, lmax | hi, rmin | left word, right word (whose bits 30..29 are its own: the grown children)
+    rb = np.frombuffer(arrays["rbranch"], "<u4").reshape(nb, 10)
+    assert s["packed_leaves"] == 1
+    assert np.array_equal(rb[:, :8], words[:, :8]) and np.array_equal(rb[:, 8], words[:, 10])
+    assert np.array_equal(rb[:, 9] & ~np.uint32(AXIS_MASK), words[:, 11])
+    # branches_m: the branch record, then the binary16 culling boxes of its children
+    bm = np.frombuffer(arrays["branches_m"], "<u4").reshape(nb, 20)
+    c16 = np.frombuffer(arrays["cull_child16"], "<u4").reshape(nb, 8)
+    assert np.array_equal(bm[:, :12], words) and np.array_equal(bm[:, 12:], c16)
+    # cull_child16 is sq_half_outward of cull_child: lo down, hi up, the fourth word of a box unused
+    cc = np.frombuffer(arrays["cull_child"], "<f4").reshape(nb, 2, 2, 4)
+    half = sqt.lib().sq_half_outward
+    want16 = np.zeros((nb, 2, 4), np.uint32)
+    for b in range(nb):
+        for side in range(2):
+            for c in range(3):
+                want16[b, side, c] = half(float(cc[b, side, 0, c]), 0) | (half(float(cc[b, side, 1, c]), 1) << 16)
+    assert np.array_equal(c16.reshape(nb, 2, 4), want16) and not cc[..., 3].any()
+    boxes, limits = (fixtures[name].cull_boxes() if name == "padded" else (None, None))
+    if boxes is not None:                                  # ... and cull_child is sq_cull_boxes of the two children, by branch number
+        br = np.nonzero(num >= 0)[0]
+        assert np.array_equal(cc[num[br], 0, :, :3].reshape(-1, 6), boxes[br + 1])
+        assert np.array_equal(cc[num[br], 1, :, :3].reshape(-1, 6), boxes[nodes["link"][br]])
+        assert np.float32(limits[0]).view(np.uint32) == s["cull_o2max"]
+    n_tris = fixtures[name].scene.n_tris
+    assert len(arrays["tris"]) == (n_tris + RUN_PAD) * 36 and not any(arrays["tris"][n_tris * 36:])
+    assert len(arrays["trix"]) == n_tris * 8
+
+
+def test_resident_tables_come_and_go_together(packed):
+    """trix, rbranch and rroot are the resident encoding: all there or all absent.  (rroot alone cannot say which: it is the
+    root's reference, and a root that is a branch has number 0.)"""
+    for name, (arrays, s) in packed.items():
+        assert (len(arrays["trix"]) == 0) == (len(arrays["rbranch"]) == 0) or s["n_branches"] == 0, name
+        if len(arrays["trix"]) == 0:
+            assert s["rroot"] == 0, name
+        if s["rroot"] != 0:
+            assert len(arrays["trix"]) > 0 and s["rroot"] & LEAF_BIT, name
+        assert len(arrays["tris"]) % 36 == 0 and not any(arrays["tris"][-RUN_PAD * 36:]), name
+
+
+# ---- flags ----
+
+def test_material_values_that_clear_nonneg_materials(sqt):
+    flag = lambda **m: pack(sqt, one_triangle(sqt, m))[1]["nonneg_materials"]
+    assert flag() == 1
+    assert flag(reflective=-0.0) == 0 and flag(surf=(0.5, -0.0, 0.5)) == 0
+    assert flag(emissive=np.nan) == 0 and flag(surf=(0.5, 0.5, np.nan)) == 0
+    assert flag(surf=(3.1e38, 0, 0)) == 0 and flag(surf=(3.0e38, 0, 0)) == 1
+    assert flag(emissive=1e30, emit=(1e30, 0, 0)) == 0                       # every component finite, the product inf
+    # max_s * max_e + max_e against 3e38, with max_s = 1: 2 * 1.49e38 is below, 2 * 1.51e38 above; every component <= 3e38
+    assert flag(surf=(1, 0, 0), emissive=1.0, emit=(1.49e38, 0, 0)) == 1
+    assert flag(surf=(1, 0, 0), emissive=1.0, emit=(1.51e38, 0, 0)) == 0
+    assert flag(surf=(0, 0, 0), emissive=1.0, emit=(2.9e38, 0, 0)) == 1      # the same bound with max_s = 0
+
+
+def test_geometry_values_that_clear_finite_geometry(sqt):
+    assert pack(sqt, one_triangle(sqt))[1]["finite_geometry"] == 1
+    assert pack(sqt, one_triangle(sqt, v=((0, 0, 0), (1, np.nan, 0), (0, 1, 0))))[1]["finite_geometry"] == 0
+    assert pack(sqt, one_triangle(sqt, root=((-1, -1, -1), (1, np.inf, 1))))[1]["finite_geometry"] == 0
+    leaf = (3, 0, 0, 0)
+    assert pack(sqt, RawScene(sqt, [(0, 0.5, -0.5, 2), leaf, leaf]))[1]["finite_geometry"] == 1
+    assert pack(sqt, RawScene(sqt, [(0, np.inf, -0.5, 2), leaf, leaf]))[1]["finite_geometry"] == 0
+
+
+def test_emitter_list_and_its_off_switch(sqt):
+    n = lambda **m: pack(sqt, one_triangle(sqt, m))[1]["n_emitters"]
+    assert n() == 0 and n(emissive=2.0, emit=(1, 0, 0)) == 1
+    assert n(emissive=2.0, emit=(-0.0, 0, 0)) == 1                           # not exactly +0
+    assert n(emissive=np.inf, emit=(1, 1, 1)) == -1 and n(surf=(np.nan, 0, 0)) == -1
+
+
+# ---- refusals ----
+
+LEAF1 = (3 | (1 << 2), 0, 0, 0)
+
+
+def test_argument_refusals(sqt):
+    N = sqt._native
+    good = one_triangle(sqt)
+    assert refusal(sqt, None) == "null argument"
+    assert refusal(sqt, C.byref(good.scene), out_ref=C.POINTER(C.c_void_p)()) == "null argument"
+    sc = one_triangle(sqt); sc.scene.nodes = None
+    assert refusal(sqt, C.byref(sc.scene)) == "scene has no nodes"
+    sc = one_triangle(sqt); sc.scene.n_nodes = 0
+    assert refusal(sqt, C.byref(sc.scene)) == "scene has no nodes"
+    for field, value in (("n_tris", -1), ("n_mats", -1), ("tris", None), ("mats", None)):
+        sc = one_triangle(sqt); setattr(sc.scene, field, value)
+        assert refusal(sqt, C.byref(sc.scene)) == "bad triangle/material arrays", field
+    for mat in (1, -1):
+        sc = one_triangle(sqt); sc.tris["mat"][0] = mat
+        assert refusal(sqt, C.byref(sc.scene)) == f"triangle 0: material {mat} outside 0..0"
+    assert N.lib().sq_last_error() != b""
+
+
+def test_tree_refusals(sqt):
+    """Every message validate_tree can give (its "scene has no nodes" and "not in pre-order position" cannot be reached:
+    the argument check and the link check come first) and the height check."""
+    leaf0 = (3, 0, 0, 0)
+    tri = one_triangle(sqt)
+    cases = [([(3 | (2 << 2), 0, 0, 0)], "leaf 0 has triangle range [0,+2) outside 0..1"),
+             ([(3 | (1 << 2), 0, 0, 1)], "leaf 0 has triangle range [1,+1) outside 0..1"),
+             ([(3, 0, 0, -1)], "leaf 0 has triangle range [-1,+0) outside 0..1"),
+             ([(3 | (-1 << 2), 0, 0, 0)], "leaf 0 has triangle range [0,+-1) outside 0..1"),
+             ([(1 | (1 << 2), 0, 0, 2), leaf0, leaf0], "branch 0 has stray bits in kind"),
+             ([(0, 0, 0, 1)], "branch 0 has no left child"),
+             ([(0, 0, 0, 2), leaf0, (1, 0, 0, 4)], "branch 2 has no left child"),
+             ([(0, 0, 0, 1), leaf0, leaf0], "branch 0: right child link 1, expected 2"),
+             ([(0, 0, 0, 3), leaf0, leaf0], "branch 0: right child link 3, expected 2"),
+             ([(0, 0, 0, 2), leaf0], "branch 0: right child 2 out of range"),
+             ([leaf0, leaf0], "tree covers 1 of 2 nodes"),
+             ([(0, 0, 0, 2), leaf0, leaf0, leaf0], "tree covers 3 of 4 nodes")]
+    for nodes, message in cases:
+        sc = RawScene(sqt, nodes, tri.tris, tri.mats)
+        assert refusal(sqt, C.byref(sc.scene)) == message, nodes
+    sc = RawScene(sqt, [(0, 0, 0, 2), leaf0, leaf0], tri.tris, tri.mats, height=3)
+    assert refusal(sqt, C.byref(sc.scene)) == "scene.height = 3 but the tree has height 2"
+    sc.scene.height = 2
+    assert pack(sqt, sc)[1]["height"] == 2
+
+
+def test_upload_checks_the_device_before_the_tree(sqt):
+    """sq_scene_upload: the argument and material checks, then the device, then the packer.  Without a device a malformed
+    tree still reports the missing device, and a bad material index is reported before that."""
+    def upload_error(sc):
+        h = C.c_void_p()
+        assert sqt.lib().sq_scene_upload(C.byref(sc.scene), 0, C.byref(h)) != 0
+        return sqt.lib().sq_last_error().decode()
+    tri = one_triangle(sqt)
+    malformed = RawScene(sqt, [(3, 0, 0, 0), (3, 0, 0, 0)], tri.tris, tri.mats)
+    both = RawScene(sqt, [(3, 0, 0, 0), (3, 0, 0, 0)], tri.tris.copy(), tri.mats)
+    both.tris["mat"][0] = 5
+    assert upload_error(both) == "triangle 0: material 5 outside 0..0"
+    if sqt.device_count() == 0:
+        assert upload_error(malformed) == "no HIP device available (this library has no CPU fallback)"
+    else:
+        assert upload_error(malformed) == "tree covers 1 of 2 nodes"
+
+
+# ---- sanitizers ----
+
+def test_packer_under_address_and_undefined_behaviour_sanitizers(tmp_path):
+    """tests/pack_main.cpp (its own main: load data/scene.obj, build, pack, read every array through the window, free) compiled
+    with sq_host.cpp under -fsanitize=address,undefined and run as a child process: exit 0, nothing on stderr."""
+    exe = str(tmp_path / "pack_main")
+    csrc = os.path.join(ROOT, "squigly-trace_amd", "csrc")
+    subprocess.check_call(["g++", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined",
+                           "-static-libasan", "-static-libubsan",      # the runtimes inside the program: nothing to order at load time
+                           os.path.join(csrc, "sq_host.cpp"), os.path.join(ROOT, "tests", "pack_main.cpp"), "-o", exe])
+    r = subprocess.run([exe, os.path.join(DATA, "scene.obj"), DATA], capture_output=True)
+    assert r.returncode == 0 and r.stderr == b"", (r.returncode, r.stderr[-2000:])
+    assert r.stdout.startswith(b"packed 13 arrays")
