@@ -14,6 +14,14 @@
  *  - all input arrays are caller-owned, read-only, valid for the duration of the call.
  *  - nothing is written to an output buffer on failure.
  *  - there is NO CPU fallback: without a usable HIP device every render entry point fails.
+ *  - a call that takes a hip_stream may be given any stream of the scene's device, non-blocking ones (hipStreamNonBlocking) with work
+ *    pending on them included: everything the call launches, clears or copies is ordered behind that stream's earlier work and in
+ *    front of its later work, and host arguments are read before the call returns (tests/test_gpu_streams.py holds every such call
+ *    to that).  A WARM call only enqueues.  A call that needs more room than the scene has -- its first frame or query, a larger
+ *    frame (workspace, table of generator words), more views (camera table), the first masked call with second moments -- allocates
+ *    on the host, and where it outgrows a block it frees the old one, which waits for the device: such a call still orders all its
+ *    work on hip_stream (the clearing of a new workspace included; no call touches the null stream unless that is the stream it was
+ *    given), but it may block the host until earlier work, on any stream, is done.  The entry points that can wait say HOST WAIT.
  *  - citations are relative to the reference repository root.
  */
 #ifndef SQUIGLY_HIP_H
@@ -105,7 +113,9 @@ int32_t sq_shard_global_row(int32_t local_row, sq_shard sh);
  * indexes its active pixels and its ray queue with 32-bit numbers that reach three times the pixel count, and takes at most 2^29
  * pixels per call (536 870 912, e.g. 16384 x 32768), which is also the cap of option "slots".  A larger call is refused before the
  * device is touched, every buffer left as it was: "R x H pixels exceed 2^31 - 1 pixels in one call", or "... exceed 2^29 pixels in
- * one call of the wavefront form ...".  Larger images are rendered as several shards (sq_shard): the limit is per call. */
+ * one call of the wavefront form ...".  Larger images are rendered as several shards (sq_shard): the limit is per call.
+ * HOST WAIT (the preamble's last convention): a wavefront call that outgrows the scene's workspace or its table of generator words
+ * allocates, and may block the host while the old block is freed; a warm call only enqueues. */
 int sq_render_rows_device(sq_device_scene* s, const sq_camera* cam, int32_t samples, int32_t w, int32_t h,
                           int32_t cast, sq_shard sh, float* d_avg, uint8_t* d_rgb, void* hip_stream);
 
@@ -120,7 +130,8 @@ int sq_render_rows_device(sq_device_scene* s, const sq_camera* cam, int32_t samp
  * Refused with an error code before anything is enqueued (every buffer left as it was): k_begin < 0, k_end <= k_begin,
  * k_end > samples, d_sum == NULL, d_sum == d_avg, and every refusal of sq_render_rows_device (bad shard, the LDS-height
  * limits, ...).  Like sq_render_rows_device the call only enqueues work on hip_stream; the calls of one frame must be
- * ordered by the caller (one stream).  sq_render_rows_device is the case [0, samples) without d_sum. */
+ * ordered by the caller (one stream).  sq_render_rows_device is the case [0, samples) without d_sum.  HOST WAIT: as for
+ * sq_render_rows_device. */
 int sq_render_rows_device_range(sq_device_scene* s, const sq_camera* cam, int32_t samples, int32_t w, int32_t h,
                                 int32_t cast, sq_shard sh, int32_t k_begin, int32_t k_end,
                                 float* d_sum, float* d_avg, uint8_t* d_rgb, void* hip_stream);
@@ -145,7 +156,8 @@ int sq_render_rows_device_range(sq_device_scene* s, const sq_camera* cam, int32_
  * its (empty) launches all the same and sq_last_plan reports launched = 1.
  * Refused before anything is enqueued (every buffer left as it was): everything sq_render_rows_device_range refuses, and any two
  * of the given buffers overlapping.  Works with every option sq_render_rows_device_range works with; multi-view frames have no
- * masked form. */
+ * masked form.  HOST WAIT: as for sq_render_rows_device, and a wavefront call with d_sum2 that outgrows the scene's second-moment
+ * buffer (the first one, a larger frame) allocates it and may block the host likewise. */
 int sq_render_rows_device_masked(sq_device_scene* s, const sq_camera* cam, int32_t samples, int32_t w, int32_t h,
                                  int32_t cast, sq_shard sh, int32_t k_begin, int32_t k_end,
                                  const uint8_t* d_mask, float* d_sum, float* d_sum2, int32_t* d_count,
@@ -183,7 +195,8 @@ int sq_adaptive_update_device(sq_device_scene* s, int64_t n_pixels, const float*
  * n_views * rows * h > INT32_MAX (2^29 in the wavefront form: FRAME SIZE above), and every refusal of sq_render_rows_device_range (bad range, d_sum == d_avg, no output buffer,
  * bad shard, the LDS-height limits).  n_views == 1 takes exactly the single-view path.
  * Like the other entry points the call only enqueues work on hip_stream.  The calls on one scene share its workspace and camera
- * table, so they must be ordered on one stream. */
+ * table, so they must be ordered on one stream.  HOST WAIT: as for sq_render_rows_device, and a call with more views than the
+ * scene's camera table holds allocates a larger table and may block the host while the old one is freed. */
 int sq_render_views_device(sq_device_scene* s, const sq_camera* cams, int32_t n_views, int32_t samples, int32_t w, int32_t h,
                            int32_t cast, sq_shard sh, int32_t k_begin, int32_t k_end,
                            float* d_sum, float* d_avg, uint8_t* d_rgb, void* hip_stream);
@@ -203,7 +216,8 @@ int sq_render_views_device(sq_device_scene* s, const sq_camera* cams, int32_t n_
  * holds is taken: ray indices and offsets are 64-bit, variant 1 runs launches of 2^30 rays and the default form chunks of at most
  * `slots` <= 2^29 rays.  n == 0 returns 0
  * and enqueues nothing.  The call only enqueues work on hip_stream; it shares the scene's workspace, so the queries and frames of
- * one scene must be ordered on one stream. */
+ * one scene must be ordered on one stream.  HOST WAIT (the preamble's last convention): a default-form query that outgrows the
+ * scene's workspace allocates, and may block the host while the old block is freed. */
 int sq_intersect_rays_device(sq_device_scene* s, const float* d_org, const float* d_dir, int64_t n,
                              int32_t* d_tri, float* d_dist, float* d_point, void* hip_stream);
 /* The primary ray of every pixel of a shard (makeRay, src/Lib.hs:107-114), computed on the device exactly as the renderer traces it:
@@ -238,7 +252,8 @@ int sq_camera_rays_device(sq_device_scene* s, const sq_camera* cam, int32_t w, i
  * Refused with an error code before anything is enqueued (every buffer left as it was): s == NULL; n < 0; n > 0 with d_org, d_dir,
  * d_seed or d_sum NULL; k_begin < 0 or k_end <= k_begin; any two of the six ranges overlapping; and the LDS-height limits of a frame
  * of the same form, with the same message.  The call only enqueues work on hip_stream; it shares the scene's workspace, so the
- * queries and frames of one scene must be ordered on one stream. */
+ * queries and frames of one scene must be ordered on one stream.  HOST WAIT: a wavefront query that outgrows the scene's workspace
+ * allocates, and may block the host while the old block is freed (queries never grow the table of generator words). */
 int sq_raytrace_rays_device(sq_device_scene* s, const float* d_org, const float* d_dir, const int64_t* d_seed, int64_t n,
                             int32_t k_begin, int32_t k_end,
                             float* d_sum, float* d_avg, uint8_t* d_rgb, void* hip_stream);
@@ -249,7 +264,7 @@ int sq_raytrace_rays_device(sq_device_scene* s, const float* d_org, const float*
  * in "variant" 2 unless option "cast_wavefront" is 1, which runs chunks of at most `slots` rays as a wavefront instead.  Refused like
  * sq_raytrace_rays_device, minus seeds and ranges: s == NULL, n < 0, n > 0 with d_org, d_dir or d_rad NULL, overlapping ranges,
  * and the LDS-height limit of the form that runs (the per-pixel kernel's; with "cast_wavefront" = 1 the wavefront form's, with its
- * message). */
+ * message).  HOST WAIT: with "cast_wavefront" = 1, as for sq_raytrace_rays_device; the per-lane form never waits. */
 int sq_raycast_rays_device(sq_device_scene* s, const float* d_org, const float* d_dir, int64_t n,
                            float* d_rad, void* hip_stream);
 

@@ -1768,8 +1768,9 @@ namespace {
 
 // Carves the frame workspace out of one allocation (grow-only; allocation happens outside timed steps after warm-up).
 // If the device cannot give `slots` sample slots the request is halved (down to one sample per pixel): the frame
-// then simply runs in more batches.
-int ensure_workspace(sq_device_scene* s, int64_t pixels, int64_t slots) {
+// then simply runs in more batches.  A new block's statistics are cleared on `stream`, the call's own: in front of every kernel of the
+// call that counts into them, whichever stream the caller gave (a non-blocking one is not ordered against the null stream).
+int ensure_workspace(sq_device_scene* s, int64_t pixels, int64_t slots, hipStream_t stream) {
     if (pixels <= s->work_pixels && slots <= s->work_slots && s->d_work) return 0;
     pixels = std::max(pixels, s->work_pixels); slots = std::max(slots, s->work_slots);
     auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
@@ -1806,7 +1807,7 @@ int ensure_workspace(sq_device_scene* s, int64_t pixels, int64_t slots) {
     int32_t* cnt = (int32_t*)(base + o_cnt);
     W.n_active = cnt; W.head[0] = cnt + 16; W.head[1] = cnt + 32;      // separate cache lines
     W.stats = (unsigned long long*)(base + o_stats);
-    if (hipMemset(W.stats, 0, kStatSlots * sizeof(unsigned long long)) != hipSuccess) return sq_set_error("hipMemset failed");
+    if (hipMemsetAsync(W.stats, 0, kStatSlots * sizeof(unsigned long long), stream) != hipSuccess) return sq_set_error("hipMemsetAsync failed");
     W.px_pixel = (int32_t*)(base + o_pix); W.px_t0 = (float*)(base + o_t0); W.px_tri0 = (int32_t*)(base + o_tri0); W.px_sum = (float*)(base + o_sum);
     W.px_mt = (float*)(base + o_mt); W.px_mtri = (int32_t*)(base + o_mtri);
     W.state = (uint8_t*)(base + o_state); W.org = (float4*)(base + o_org); W.dir = (float4*)(base + o_dir); W.tri1 = (int32_t*)(base + o_tri1);
@@ -2135,7 +2136,7 @@ int launch_frame(sq_device_scene* s, const typename SrcKernels<StackT, SRC>::Fra
     const int n_call = cast_wave ? n_lights : F.k_end - F.k_begin;
     // at least one sample of every pixel per batch, never more slots than the call has samples
     const int64_t slots = std::max<int64_t>(pixels, std::min<int64_t>(s->opt_slots, (int64_t)pixels * n_call));
-    if (ensure_workspace(s, pixels, slots)) return 1;
+    if (ensure_workspace(s, pixels, slots, stream)) return 1;
     if (mom2 && ensure_px_sum2(s, pixels)) return 1;
     s->work.px_sum2 = mom2 ? s->d_px_sum2 : nullptr;
     const Work& W = s->work;
@@ -2571,7 +2572,7 @@ int intersect_rays(sq_device_scene* s, const RayQuery& Q, hipStream_t stream) {
     if (plan_trace<StackT, kSrcCamera>(s, S, stack_cap, TP)) return 1;
     // Chunks of at most `slots` rays (and what the workspace holds; the option caps the slots at 2^29, so a chunk's queue positions and
     // the trace kernel's 32-bit cursor never overflow).  One slot per ray: 37 B, against 40 B of caller arrays per ray.
-    if (ensure_workspace(s, 1, std::min<int64_t>(s->opt_slots, Q.n))) return 1;
+    if (ensure_workspace(s, 1, std::min<int64_t>(s->opt_slots, Q.n), stream)) return 1;
     const Work& W = s->work;
     const long long chunk = std::min<long long>(s->opt_slots, W.slot_capacity);
     Work Wq = W; Wq.n_active = W.n_active + 48;                         // the launch's queue length, written by sq_rays_stage

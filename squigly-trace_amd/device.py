@@ -147,11 +147,12 @@ class DeviceScene:
             _check_frame_size(self, rows, h, cast, 1 if views is None else views)
         dev = torch.device("cuda", self.device)
         shape = (rows, h, 3) if views is None else (views, rows, h, 3)
-        if want_avg and out_avg is None:
-            out_avg = torch.empty(shape, dtype=torch.float32, device=dev)
-        if want_rgb and out_rgb is None:
-            out_rgb = torch.empty(shape, dtype=torch.uint8, device=dev)
         st = stream if stream is not None else torch.cuda.current_stream(dev)
+        with torch.cuda.stream(st):      # allocated in the order of the call's stream: a block another stream still has work on is not taken
+            if want_avg and out_avg is None:
+                out_avg = torch.empty(shape, dtype=torch.float32, device=dev)
+            if want_rgb and out_rgb is None:
+                out_rgb = torch.empty(shape, dtype=torch.uint8, device=dev)
         return sh, rows, out_avg, out_rgb, st
 
     def render_rows(self, cam, samples, w, h, cast=False, shard=(None, 0, 1), want_avg=True, want_rgb=True,
@@ -315,8 +316,9 @@ class DeviceScene:
         triangle-id buffer."""
         sh, rows, _, _, st = self._outputs(w, h, shard, False, False, stream, None, None, frame=False)
         dev = torch.device("cuda", self.device)
-        o = torch.empty((rows, h, 3), dtype=torch.float32, device=dev)
-        d = torch.empty((rows, h, 3), dtype=torch.float32, device=dev)
+        with torch.cuda.stream(st):      # as in _outputs: the rays are allocated in the order of the call's stream
+            o = torch.empty((rows, h, 3), dtype=torch.float32, device=dev)
+            d = torch.empty((rows, h, 3), dtype=torch.float32, device=dev)
         N.check(N.lib().sq_camera_rays_device(self._h, C.byref(cam), int(w), int(h), sh, o.data_ptr(), d.data_ptr(),
                                               C.c_void_p(st.cuda_stream)))
         return o, d
