@@ -295,6 +295,35 @@ int     sq_scene_set_lights(sq_device_scene* s, const sq_light* lights, int32_t 
  * out (which may be NULL when cap <= 0); -1 (sq_last_error) for s == NULL. */
 int32_t sq_scene_get_lights(sq_device_scene* s, sq_light* out, int32_t cap);
 
+/* Caller-given path depth for the scene's path-traced computations: sq_render_rows_device, its _range and _masked forms and
+ * sq_render_views_device, each with cast == 0, and sq_raytrace_rays_device.  (Cast frames and sq_raycast_rays_device ignore it; the
+ * one-shot calls upload a scene of their own and keep depth 3.)  A scene has a depth D, 1 <= D <= 8, 3 until set.  Under depth D the
+ * radiance of a sample is L(0) of the ray chain below: raytrace (src/Lib.hs:127-137) with `bounces > 2` made `bounces > D - 1`, every
+ * operation a single fp32 operation in this order.  inter_b is the intersectBIH of ray b; n_0 ... n_7 are the first eight outputs of
+ * the sample's generator mkTFGen seed, the low then high halves of the four words of its one Threefish block:
+ *      L(b) = black (+0, +0, +0)                                   if b >= D
+ *           = black                                                if inter_b is Nothing
+ *           = surfColor_b * L(b+1) + emissive_b *^ emitColor_b     otherwise      -- the product with black IS formed at b = D - 1
+ *      ray_{b+1} = bounceRay gen_b ray_b inter_b                    -- src/Lib.hs:155-181: x and u from n_b, v from n_{b+1};
+ *                                                                     origin = intersectPoint inter_b
+ * and everything after the sample's radiance is as it was: the ordered fold into sum, a masked call's sum2 = sum2 + r * r, counts,
+ * avg and the tonemap.  D = 3 is the reference, bit for bit.  D = 1 is direct emission only and traces no bounce ray.  D <= 8 because
+ * bounce b reads n_b and n_{b+1} and the last bounce is b = D - 2: no path leaves the generator's first block.  Non-finite and
+ * negative materials are inputs like any other (inf * 0 is the NaN the expression says).
+ * The depth is host state that the next call's planning reads: the set call enqueues nothing and needs no stream, and a frame enqueued
+ * before it keeps the depth it had.  Option "variant" picks the form as for every frame: 2 (default) runs a wavefront around the
+ * planned trace kernel, one trace launch per level (frame sizes, tree heights and refusal messages are the wavefront form's, sq_last_plan
+ * reports trace_form and primary_form, "overlap" is ignored); 1 = one lane per pixel, one kernel.  At depth 3 both run exactly the
+ * kernels and launches they ran before this function existed, unless option "deep" is 1.
+ * HOST WAIT: the scene's first wavefront call under a depth other than 3 (or under "deep") allocates the per-slot path state, 4 (D - 1)
+ * bytes per slot and 8 more from D = 4 on, and so does a later one that needs more (more slots, a larger depth); it may block the host
+ * while the old block is freed.  A failed allocation is an error code before anything is enqueued.  Such calls read the table of
+ * generator words the scene has and never grow it.
+ * Refused with a message, nothing changed: s == NULL, depth < 1, depth > 8. */
+int     sq_scene_set_depth(sq_device_scene* s, int32_t depth);
+/* The scene's depth; -1 (sq_last_error) for s == NULL. */
+int32_t sq_scene_get_depth(sq_device_scene* s);
+
 /* Timing of the dominant kernel measured with hipEvents on the stream it was launched on:
  * average duration in ms over the launches since the last reset, and the launch count. */
 int  sq_kernel_timing(sq_device_scene* s, double* avg_ms, int64_t* launches, const char** kernel_name);
@@ -366,6 +395,9 @@ int  sq_get_stats(sq_device_scene* s, uint64_t* out, int32_t n, int32_t reset);
  *                        one) one shadow ray per (active pixel, light) through one level of the planned trace kernel and an ordered
  *                        fold; frame sizes, tree heights and refusal messages are then the wavefront form's, sq_last_plan reports the
  *                        planned trace_form and primary_form, and "overlap" is ignored
+ *   "deep"               0 (default): a scene at depth 3 (sq_scene_set_depth) runs the three-level kernels, every other depth the
+ *                        generic-depth ones; 1: depth 3 runs the generic-depth kernels too -- same bits, so that the generic pipeline
+ *                        can be held to the reference and timed against the tuned one
  *   "incremental"        accepted, no effect: the variant it switched was removed (last built by commit 4abd717) */
 int  sq_set_option(sq_device_scene* s, const char* key, int64_t value);
 

@@ -43,6 +43,7 @@ class Light(C.Structure):
 
 
 MAX_LIGHTS = 4096      # sq_scene_set_lights refuses more
+MAX_DEPTH = 8          # sq_scene_set_depth refuses more: a path's random words come from one Threefish block
 
 
 class Plan(C.Structure):
@@ -105,6 +106,9 @@ def lib():
     L.sq_scene_set_lights.argtypes = [vp, vp, i32, vp]
     L.sq_scene_get_lights.argtypes = [vp, vp, i32]
     L.sq_scene_get_lights.restype = i32
+    L.sq_scene_set_depth.argtypes = [vp, i32]
+    L.sq_scene_get_depth.argtypes = [vp]
+    L.sq_scene_get_depth.restype = i32
     L.sq_kernel_timing.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_char_p)]
     L.sq_kernel_timing_reset.argtypes = [vp]
     L.sq_kernel_timing_reset.restype = None
@@ -192,6 +196,16 @@ def lights_array(lights):
     return np.ascontiguousarray(np.stack(rows), np.float32)
 
 
+def depth_value(depth):
+    """The int of a path depth (DeviceScene.set_depth, depth= of the render functions); SquiglyError for anything that is not an
+    integer in 1 .. MAX_DEPTH (a bool and a float, integral or not, are not integers here)."""
+    if isinstance(depth, bool) or not isinstance(depth, (int, np.integer)):
+        raise SquiglyError(f"depth must be an integer in 1..{MAX_DEPTH}, got {depth!r}")
+    if not 1 <= int(depth) <= MAX_DEPTH:
+        raise SquiglyError(f"depth must be in 1..{MAX_DEPTH} (got {int(depth)})")
+    return int(depth)
+
+
 OPS = {"sqrt": 0, "div": 1, "sin": 2, "cos": 3, "acos": 4, "atan": 5, "unit_float": 6, "tfgen3": 7, "tonemap": 8, "rcp_sweep": 9, "cull_slab": 10}
 
 
@@ -229,7 +243,7 @@ def check(rc):
 EXPORTED_SYMBOLS = [
     # include/squigly_hip.h
     "sq_render_rgb8", "sq_render_f32", "sq_scene_upload", "sq_scene_free", "sq_shard_rows",
-    "sq_shard_global_row", "sq_render_rows_device", "sq_render_rows_device_range", "sq_render_rows_device_masked", "sq_adaptive_update_device", "sq_render_views_device", "sq_intersect_rays_device", "sq_camera_rays_device", "sq_raytrace_rays_device", "sq_raycast_rays_device", "sq_scene_set_lights", "sq_scene_get_lights", "sq_kernel_timing", "sq_kernel_timing_reset",
+    "sq_shard_global_row", "sq_render_rows_device", "sq_render_rows_device_range", "sq_render_rows_device_masked", "sq_adaptive_update_device", "sq_render_views_device", "sq_intersect_rays_device", "sq_camera_rays_device", "sq_raytrace_rays_device", "sq_raycast_rays_device", "sq_scene_set_lights", "sq_scene_get_lights", "sq_scene_set_depth", "sq_scene_get_depth", "sq_kernel_timing", "sq_kernel_timing_reset",
     "sq_set_option", "sq_scene_rng_table", "sq_get_stats", "sq_last_plan", "sq_debug_eval", "sq_device_count", "sq_abi_version", "sq_build_id", "sq_last_error",
     # include/squigly_host.h
     "sq_mesh_from_obj", "sq_mesh_from_text", "sq_mesh_from_arrays", "sq_mesh_num_tris",

@@ -80,8 +80,12 @@ def build(force=False, extra=(), out=None):
     subprocess.check_call(cmd)
     # the reference's executable (app/Main.hs) over the C-ABI
     os.makedirs(os.path.dirname(CLI), exist_ok=True)
-    subprocess.check_call(["g++", "-O2", "-std=c++17", os.path.join(CSRC, "cli_main.cpp"), "-o", CLI,
-                           "-L" + HERE, "-lsquigly_hip", "-Wl,-rpath,$ORIGIN/..", "-Wl,-rpath,/opt/rocm/lib",
+    # (its --depth path copies a device frame back: the HIP runtime's host API, from the ROCm tree hipcc belongs to)
+    import shutil
+    rocm = os.path.dirname(os.path.dirname(os.path.realpath(shutil.which(hipcc()) or hipcc())))
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-D__HIP_PLATFORM_AMD__", "-I" + os.path.join(rocm, "include"),
+                           os.path.join(CSRC, "cli_main.cpp"), "-o", CLI,
+                           "-L" + HERE, "-lsquigly_hip", "-L" + os.path.join(rocm, "lib"), "-lamdhip64", "-Wl,-rpath,$ORIGIN/..", "-Wl,-rpath,/opt/rocm/lib", "-Wl,-rpath," + os.path.join(rocm, "lib"),
                            "-Wl,--allow-shlib-undefined"])
     return OUT
 

@@ -42,6 +42,16 @@ def nonneg_float(text):
     return v
 
 
+def path_depth(text):
+    try:
+        v = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError("expected an integer in 1..8")
+    if not 1 <= v <= 8:
+        raise argparse.ArgumentTypeError("expected an integer in 1..8")
+    return v
+
+
 def parse_light(text):
     """A point light of --light: X,Y,Z (power 2, the reference's), X,Y,Z,P or X,Y,Z,R,G,B -> ((x, y, z), (r, g, b)).  The value may
     stand in parentheses, (X,Y,Z), which keeps a negative X from looking like an option on the command line."""
@@ -128,6 +138,9 @@ def build_parser():
                    help="With --cast: a point light at X,Y,Z with power P (default 2) or R,G,B; repeat for several lights, "
                         "added in the order given (default: one light at 0,3,-1). A value that starts with a minus sign "
                         "is written --light=-1,2,3 or --light '(-1,2,3)'")
+    # not a flag of the reference: how many rays long a path is (the reference's is fixed at 3)
+    p.add_argument("--depth", type=path_depth, default=None, metavar="N",
+                   help="Rays per path, 1..8: 1 = emission only, 2 = direct light, 3 = the reference's (default); not with --cast")
     return p
 
 
@@ -142,6 +155,8 @@ def parse_args(argv=None):
         p.error("--counts needs --adaptive")
     if a.light is not None and not a.cast:
         p.error("--light needs --cast")
+    if a.depth is not None and a.cast:
+        p.error("--depth cannot be combined with --cast (a cast image has no paths)")
     return a
 
 
@@ -177,26 +192,29 @@ def main(argv=None):
     print("Started at " + time.strftime("%H:%M:%S%p UTC", time.gmtime(t0)).lower().replace("utc", "UTC"))
     os.makedirs(os.path.dirname(os.path.abspath(settings.savePath)), exist_ok=True)
     if a.views is not None:
-        imgs = render_views_rgb8(bih, a.views, settings.samples, settings.dimensions, settings.cast, lights=a.light)
+        imgs = render_views_rgb8(bih, a.views, settings.samples, settings.dimensions, settings.cast, lights=a.light, depth=a.depth)
         for path, img in zip(view_paths(settings.savePath, len(imgs)), imgs):
             write_png(path, img)
         print(f"Wrote {len(imgs)} views to {view_paths(settings.savePath, 1)[0]} ...")
     elif a.adaptive is not None:
         import numpy as np
         for done, live, spent, img, counts in render_adaptive(bih, cam, settings.samples, settings.dimensions, a.adaptive, eps=a.adaptive_eps,
-                                                              first=a.adaptive_first, step=a.adaptive_step, cast=settings.cast, lights=a.light):
+                                                              first=a.adaptive_first, step=a.adaptive_step, cast=settings.cast, lights=a.light,
+                                                              depth=a.depth):
             print(f"Adaptive {done}/{settings.samples} live {live} spent {spent}")
         write_png(settings.savePath, img)
         if a.counts is not None:
             with open(a.counts, "wb") as f:                     # the name as given (np.save would append .npy to a path)
                 np.save(f, counts.astype(np.int32))
-    elif a.preview_every is None and a.light is None:
+    elif a.preview_every is None and a.light is None and a.depth is None:
         render(bih, cam, settings)
-    elif a.preview_every is None:                               # caller-given lights live on a resident scene: one step of all samples
-        for _, img in render_progressive(bih, cam, settings.samples, settings.dimensions, settings.samples, settings.cast, lights=a.light):
+    elif a.preview_every is None:                               # caller-given lights and depths live on a resident scene: one step of all samples
+        for _, img in render_progressive(bih, cam, settings.samples, settings.dimensions, settings.samples, settings.cast, lights=a.light,
+                                         depth=a.depth):
             write_png(settings.savePath, img)
     else:
-        for done, img in render_progressive(bih, cam, settings.samples, settings.dimensions, a.preview_every, settings.cast, lights=a.light):
+        for done, img in render_progressive(bih, cam, settings.samples, settings.dimensions, a.preview_every, settings.cast, lights=a.light,
+                                            depth=a.depth):
             write_png(settings.savePath, img)
             print(f"Preview: {done}/{settings.samples} samples written to {settings.savePath}")
     t1 = time.time()

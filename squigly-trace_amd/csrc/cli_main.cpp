@@ -1,11 +1,12 @@
 // squigly-trace — the reference's executable (app/Main.hs:13-75) over the C-ABI.
 //
 //   squigly-trace [--samples N|-s N] [--dimensions W,H|-d W,H] [--savepath F|-p F] [--objpath F]
-//                 [--camerapath F|-c F] [--debug] [--debugpath F] [--cast]
+//                 [--camerapath F|-c F] [--debug] [--debugpath F] [--cast] [--depth N]
 //
 // Same flags, defaults and printouts as the Haskell program; the render itself is sq_render_rgb8, i.e. the
 // foreign call that replaces src/Lib.hs:73-74.  The material file named by `mtllib` is read from ./data/
-// (src/Obj.hs:52).  PNG output (role of massiv-io's writeImage, src/Lib.hs:75): 8-bit RGB, stored deflate.
+// (src/Obj.hs:52).  --depth N (not a flag of the reference: rays per path, 1..8, the reference's is 3) renders on a resident scene
+// instead (sq_scene_set_depth, sq_render_rows_device), on device 0, and copies the frame back with the HIP runtime.  PNG output (role of massiv-io's writeImage, src/Lib.hs:75): 8-bit RGB, stored deflate.
 #include <chrono>
 #include <cstdint>
 #include <cstdio>
@@ -14,6 +15,8 @@
 #include <ctime>
 #include <string>
 #include <vector>
+
+#include <hip/hip_runtime_api.h>
 
 #include "../../include/squigly_host.h"
 
@@ -62,13 +65,31 @@ std::string show_time(std::time_t t) {           // formatTime defaultTimeLocale
     std::strftime(buf, sizeof buf, "%H:%M:%S", &g);
     return std::string(buf) + (g.tm_hour < 12 ? "am" : "pm") + " UTC";
 }
+// --depth: the frame of a resident scene under depth `depth` into img (w * h * 3 bytes).  The C-ABI leaves the frame on the device;
+// hipMemcpy brings it back (and waits for the null stream the frame was enqueued on).  Prints what failed.
+bool render_resident(const sq_scene* sc, const sq_camera* cam, int samples, int w, int h, int depth, uint8_t* img) {
+    sq_device_scene* ds = nullptr;
+    if (sq_scene_upload(sc, 0, &ds)) { std::fprintf(stderr, "squigly-trace: render: %s\n", sq_last_error()); return false; }
+    void* d_rgb = nullptr;
+    const size_t bytes = (size_t)(w > 0 ? w : 0) * (size_t)(h > 0 ? h : 0) * 3;
+    bool ok = true;
+    auto lib = [&](int rc) { if (ok && rc != 0) { std::fprintf(stderr, "squigly-trace: render: %s\n", sq_last_error()); ok = false; } };
+    auto hip = [&](hipError_t e, const char* what) { if (ok && e != hipSuccess) { std::fprintf(stderr, "squigly-trace: render: %s: %s\n", what, hipGetErrorString(e)); ok = false; } };
+    lib(sq_scene_set_depth(ds, depth));
+    hip(hipMalloc(&d_rgb, bytes ? bytes : 1), "hipMalloc");
+    if (ok) lib(sq_render_rows_device(ds, cam, samples, w, h, 0, sq_shard{ w > 0 ? w : 1, 0, 1 }, nullptr, (uint8_t*)d_rgb, nullptr));
+    if (ok) hip(hipMemcpy(img, d_rgb, bytes, hipMemcpyDeviceToHost), "hipMemcpy");
+    if (d_rgb) (void)hipFree(d_rgb);
+    sq_scene_free(ds);
+    return ok;
+}
 int fail(const char* what) { std::fprintf(stderr, "squigly-trace: %s: %s\n", what, sq_last_error()); return 1; }
 
 }  // namespace
 
 int main(int argc, char** argv) {
     // defaults: app/Main.hs:14-30
-    int samples = 10, w = 540, h = 540; bool debug = false, cast = false;
+    int samples = 10, w = 540, h = 540, depth = 0; bool debug = false, cast = false;   // depth 0: not given
     std::string save = "./render/result.png", objp = "./data/scene.obj", camp = "./data/camera", dbgp;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i], val; bool has = false;
@@ -83,15 +104,22 @@ int main(int argc, char** argv) {
         else if (a == "--debugpath") dbgp = need();
         else if (a == "--debug") debug = true;
         else if (a == "--cast") cast = true;
+        else if (a == "--depth") {
+            char* end = nullptr; const char* v = need(); const long d = std::strtol(v, &end, 10);
+            if (end == v || *end || d < 1 || d > 8) { std::fprintf(stderr, "--depth wants an integer in 1..8 (got %s)\n", v); return 2; }
+            depth = (int)d;
+        }
         else if (a == "--help" || a == "-?") {
             std::puts("squigly-trace was made by Ruko (https://github.com/rukokarasu/)\nA cute raytracer\n"
                       "  -s --samples=INT        How many samples per pixel to trace\n  -d --dimensions=INT,INT Dimensions of the resulting image\n"
                       "  -p --savepath=FILE      Where to save the output\n     --objpath=FILE       File to load .obj from\n"
                       "  -c --camerapath=FILE    File to load camera data from\n     --debug              Run in debug mode\n"
-                      "     --debugpath=FILE     File to write debug info to\n     --cast               Raycast instead of raytracing (i.e. don't bounce rays)");
+                      "     --debugpath=FILE     File to write debug info to\n     --cast               Raycast instead of raytracing (i.e. don't bounce rays)\n"
+                      "     --depth=INT          Rays per path, 1..8 (default 3, the reference's); not with --cast");
             return 0;
         } else { std::fprintf(stderr, "Unknown flag: %s\n", a.c_str()); return 2; }
     }
+    if (depth && cast) { std::fprintf(stderr, "--depth cannot be combined with --cast (a cast image has no paths)\n"); return 2; }
     sq_camera cam;
     if (sq_camera_from_file(camp.c_str(), &cam)) return fail("Failed to parse camera");        // app/Main.hs:38
     sq_mesh* mesh = nullptr;
@@ -123,7 +151,8 @@ int main(int argc, char** argv) {
     std::printf("Started at %s\n", show_time(std::chrono::system_clock::to_time_t(t0)).c_str());
     sq_scene sc; sq_bih_scene(bih, &sc);
     std::vector<uint8_t> img((size_t)(w > 0 ? w : 0) * (size_t)(h > 0 ? h : 0) * 3);
-    if (sq_render_rgb8(&sc, &cam, samples, w, h, cast ? 1 : 0, img.data())) return fail("render");  // src/Lib.hs:73-74
+    if (depth) { if (!render_resident(&sc, &cam, samples, w, h, depth, img.data())) return 1; }
+    else if (sq_render_rgb8(&sc, &cam, samples, w, h, cast ? 1 : 0, img.data())) return fail("render");  // src/Lib.hs:73-74
     if (!write_png(save.c_str(), img.data(), w, h)) { std::fprintf(stderr, "squigly-trace: cannot write %s\n", save.c_str()); return 1; }
     const auto t1 = std::chrono::system_clock::now();
     std::printf("Finished at %s\n", show_time(std::chrono::system_clock::to_time_t(t1)).c_str());

@@ -1587,6 +1587,244 @@ __global__ void sq_debug_kernel(int op, const void* a, const void* b, long long 
 }
 
 // ----------------------------------------------------------------------------------------------
+// Caller-given path depth (sq_scene_set_depth): raytrace with `bounces > 2` made `bounces > D - 1`, src/Lib.hs:127-137
+// ----------------------------------------------------------------------------------------------
+// A path of depth D is the rays 0 .. D-1; bounce b makes ray b + 1 from the generator words n_b (x and u) and n_{b+1} (v), so the
+// last bounce, b = D - 2, reads n_{D-1}: with D <= 8 every word comes from the generator's one Threefish block.
+constexpr int kMaxDepth = 8;
+// Word i (0 .. 7) of a generator whose block is c: the low, then the high half of each of its four words (tfgen3 keeps 0 .. 2).
+__device__ __forceinline__ uint32_t tf_word(const uint64_t c[4], int i) {
+    const uint64_t w = i < 2 ? c[0] : i < 4 ? c[1] : i < 6 ? c[2] : c[3];
+    return (i & 1) ? (uint32_t)(w >> 32) : (uint32_t)w;
+}
+// The radiance of a path from its triangles: tr[b] = the triangle ray b hit, b = 1 .. kMaxDepth - 1, -1 from the path's end on (a
+// miss, or the depth); s0 = the surface ray 0 hit.  L(b) = surfColor_b * L(b+1) + emissive_b *^ emitColor_b from the innermost hit
+// outwards, starting from black: the product with black is formed at the innermost level, as the reference forms it.
+__device__ __forceinline__ f3 path_radiance(const SceneView& S, const Surface& s0, const int (&tr)[kMaxDepth]) {
+    f3 L = sq::mk(0, 0, 0);
+#pragma unroll
+    for (int b = kMaxDepth - 1; b >= 1; --b)
+        if (tr[b] >= 0) { const Shade1 q = shade1_of(S, tr[b]); L = q.surf * L + q.emit; }
+    return s0.surf * L + s0.emit;
+}
+
+// Per-lane form (option "variant" = 1): sq_render_pixels' raytrace branch with a loop over the levels.  A lane keeps the triangles
+// of its path (registers: the level is matched by selects, not by an index) and folds L from the innermost level outwards.
+template <typename StackT, int SRC, bool AD, typename FrameT>
+__device__ __forceinline__ void render_pixels_deep_body(const SceneView& S, const FrameT& F, const int depth) {
+    extern __shared__ float4 lds_raw[];
+    SQ_LDS StackT* stk = to_lds<StackT>(lds_raw) + threadIdx.x;
+    const long long pix = (long long)blockIdx.x * kBlock + threadIdx.x;
+    int y = 0, x = 0; f3 o0, d0;
+    if constexpr (SRC == kSrcRays) {
+        if (pix >= (long long)F.h) return;
+        o0 = load3(F.ray_org, pix); d0 = load3(F.ray_dir, pix);
+    } else if constexpr (SRC == kSrcViews) {
+        if (pix >= (long long)F.n_views * F.view_pixels) return;
+        const ViewCam c = view_cam<false>(F, view_coords(F, (int)pix, y, x));
+        o0 = c.pos; d0 = primary_dir(c.rot, F.w, F.h, y, x);
+    } else {
+        if (pix >= (long long)F.local_rows * F.h) return;
+        if constexpr (AD) { if (!pixel_live(F, pix)) return; }
+        pixel_coords(F, pix, y, x);
+        o0 = sq::mk(F.cam_pos[0], F.cam_pos[1], F.cam_pos[2]);
+        d0 = primary_dir(F.cam_rot, F.w, F.h, y, x);
+    }
+    const GlobalNodes N{ S.branches, S.cull_child, S.cull_child != nullptr };
+    f3 sum = sq::mk(0, 0, 0), sum2 = sq::mk(0, 0, 0);
+    const Hit h0 = trace_one(S, N, o0, d0, stk, kBlock);
+    if (h0.tri >= 0) {
+        sum = fold_start(F, pix);
+        if constexpr (AD) { if (F.sum2) sum2 = fold_start2(F, pix); }
+        const Surface s0 = surface_of(S, h0.tri);
+        const f3 p0 = o0 + sq::scale(h0.t, d0);
+        long long rix;
+        if constexpr (SRC == kSrcRays) rix = F.ray_seed[pix];
+        else rix = (long long)F.samples * ((long long)x + (long long)y * (long long)F.w);   // src/Lib.hs:85
+#pragma unroll 1
+        for (int k = F.k_begin; k < F.k_end; ++k) {
+            long long seed = rix + k;
+            asm volatile("" : "+v"(seed));                              // as in sq_gen_bounce1: the block is not an induction of this loop
+            uint64_t c[4];
+            sq::threefish256_key_only((uint64_t)seed, c);
+            int tr[kMaxDepth];
+#pragma unroll
+            for (int i = 0; i < kMaxDepth; ++i) tr[i] = -1;
+            f3 o = p0, d = d0; Surface sb = s0;
+#pragma unroll 1
+            for (int b = 1; b < depth; ++b) {                           // ray b = bounceRay gen_{b-1} ray_{b-1} inter_{b-1}
+                const f3 nd = bounce_dir(d, sb, tf_word(c, b - 1), tf_word(c, b));
+                const Hit h = trace_one(S, N, o, nd, stk, kBlock);
+                if (h.tri < 0) break;
+#pragma unroll
+                for (int i = 1; i < kMaxDepth; ++i) tr[i] = i == b ? h.tri : tr[i];
+                sb = surface_of(S, h.tri);
+                o = o + sq::scale(h.t, nd); d = nd;                     // intersectPoint, src/Geometry.hs:134
+            }
+            const f3 r = path_radiance(S, s0, tr);
+            sum = sum + r;
+            if constexpr (AD) sum2 = sum2 + r * r;
+        }
+    }
+    if constexpr (AD) {
+        if (F.sum2) { float* o = F.sum2 + pix * 3; o[0] = sum2.x; o[1] = sum2.y; o[2] = sum2.z; }
+        store_count(F, pix);
+    }
+    store_fold(F, pix, sum);
+}
+template <typename StackT, bool MV, bool AD = false>
+__global__ void __launch_bounds__(kBlock) sq_render_pixels_deep(const SceneView S, const Frame F, const int depth) { render_pixels_deep_body<StackT, MV, AD>(S, F, depth); }
+template <typename StackT>
+__global__ void __launch_bounds__(kBlock) sq_render_pixels_deep_rays(const SceneView S, const RayFrame F, const int depth) { render_pixels_deep_body<StackT, kSrcRays, false>(S, F, depth); }
+
+// Wavefront form: the levels go through the planned trace kernel one after the other.  A slot's state byte alternates between the
+// two values the trace kernel knows: ray b waits as kRay1 when b is odd and as kRay2 when b is even, so the launch of one level never
+// takes the rays the bounce kernel has just written for the next.  After the frame's own primary pass, per batch of samples:
+// sq_deep_gen (ray 1), then for b = 1 .. D-1 a trace launch and sq_deep_bounce (records the triangle ray b hit; finishes the slot or
+// writes ray b + 1), then sq_deep_fold.
+// The deep kernels' own argument (Frame, SceneView, Work and TraceArgs stay as the tuned kernels take them).  Per slot, in a block of
+// the scene's own (sq_device_scene::d_deep), 64-bit offsets throughout:
+//   trail : D - 1 arrays of `cap` triangles, level-major; trail[(b-1) * cap + sid] = the triangle ray b hit, -1 = a miss or "nothing
+//           below this level adds light" (an absorbing surface, no emitter within the last ray's reach), which reads as a miss below it.
+//           Written level by level up to the path's end; sq_deep_fold reads it down to the first -1.
+//   oxy   : x and y of the origin of the ray in the slot (D >= 4 only).  The trace kernel puts the hit over org.xy, and
+//           intersectPoint = o + t *^ d needs the origin; z stays in org.z.  Ray 1 starts at the pixel's primary hit point, which
+//           sq_deep_bounce recomputes as sq_shade1 does, and the last ray's hit point is never formed.
+// The words n_1, n_2 ride in the w of the slot's two quads as in the three-level pipeline; n_b, n_{b+1} of a bounce b >= 2 are
+// recomputed from the sample's seed: one Threefish block per slot that is still alive there (8 % of the slots at b = 2 in the
+// shipped room) moves no byte, where keeping n_3 .. n_{D-1} would write 4 (D - 3) bytes for every slot of the batch.
+struct Deep { int32_t depth, level; int32_t* trail; float2* oxy; long long cap; };
+
+// Bounce 0 of every sample of the batch: sq_gen_bounce1 without the shared mirror ray (a sample that mirrors gets a ray of its own).
+template <int SRC, typename FrameT>
+__device__ __forceinline__ void deep_gen_body(const SceneView& S, const FrameT& F, const Work& W, int k_base, int k_count, const RngView R) {
+    const int A = *W.n_active;
+    for (int a = blockIdx.x * kBlock + threadIdx.x; a < A; a += gridDim.x * kBlock) {
+        const Pixel0 P = load_pixel0<SRC>(S, F, W, a);
+        const long long rix = seed_base<SRC>(F, W, a, P);
+        const bool dead = absorbs(S, P.s0);                             // no ray: sq_deep_fold knows the pixel absorbs
+        const f3 d1_mirror = mirror_dir(P.d0, P.s0);
+        const long long first = rix + k_base;
+        const bool use = R.words != nullptr && rix >= 0 && rix <= R.cover - (long long)F.samples;   // the table is read, never grown
+#pragma unroll 1
+        for (int kl = blockIdx.y; kl < k_count; kl += gridDim.y) {
+            const long long sid = (long long)kl * A + a;
+            if (dead) { W.state[sid] = kDone; continue; }
+            uint32_t n0, n1, n2;
+            if (use) { const uint32_t* p = R.words + 3 * (first + kl); n0 = p[0]; n1 = p[1]; n2 = p[2]; }
+            else {
+                long long seed = first + kl;
+                asm volatile("" : "+v"(seed));
+                sq::tfgen3(seed, n0, n1, n2);
+            }
+            const f3 d1 = scatters(P.s0, n0) ? scatter_dir(P.d0, P.s0, n0, n1) : d1_mirror;
+            W.state[sid] = kRay1;
+            W.org[sid] = make_float4(P.p0.x, P.p0.y, P.p0.z, __uint_as_float(n1));
+            W.dir[sid] = make_float4(d1.x, d1.y, d1.z, __uint_as_float(n2));
+        }
+    }
+}
+template <bool MV>
+__global__ void __launch_bounds__(kBlock) sq_deep_gen(const SceneView S, const Frame F, const Work W, int k_base, int k_count, const RngView R) { deep_gen_body<MV>(S, F, W, k_base, k_count, R); }
+__global__ void __launch_bounds__(kBlock) sq_deep_gen_rays(const SceneView S, const RayFrame F, const Work W, int k_base, int k_count, const RngView R) { deep_gen_body<kSrcRays>(S, F, W, k_base, k_count, R); }
+
+// After the trace launch of level b = D.level (1 .. depth - 1): the slot's hit goes into the trail; a miss, the last level, an absorbing
+// surface or a last ray that can reach no emitter finishes the slot, anything else puts ray b + 1 into it.  One thread per active pixel.
+template <int SRC, typename FrameT>
+__device__ __forceinline__ void deep_bounce_body(const SceneView S, const FrameT F, const Work W, int k_base, int k_count, const Deep D) {
+    const int A = *W.n_active;
+    const int b = D.level;
+    const uint8_t mine = (b & 1) ? kRay1 : kRay2, next = (b & 1) ? kRay2 : kRay1;
+    int32_t* trail_b = D.trail + (long long)(b - 1) * D.cap;
+    for (int a = blockIdx.x * kBlock + threadIdx.x; a < A; a += gridDim.x * kBlock) {
+        const Pixel0 P = load_pixel0<SRC>(S, F, W, a);
+        if (absorbs(S, P.s0)) continue;                                 // every slot of the pixel is kDone since sq_deep_gen
+        const long long first = seed_base<SRC>(F, W, a, P) + k_base;
+#pragma unroll 1
+        for (int kl = blockIdx.y; kl < k_count; kl += gridDim.y) {
+            const long long sid = (long long)kl * A + a;
+            if (W.state[sid] != mine) continue;
+            const float4 org = W.org[sid];
+            const int2 hit = slot_hit(org);
+            const int tri = hit.y >= 0 ? hit.y : -1;
+            trail_b[sid] = tri;
+            if (tri < 0 || b + 1 >= D.depth) { W.state[sid] = kDone; continue; }   // black below, by a miss or by the depth
+            const Surface sb = surface_of(S, tri);
+            if (absorbs(S, sb)) { trail_b[sid + D.cap] = -1; W.state[sid] = kDone; continue; }
+            const float4 dir = W.dir[sid];
+            const f3 d = sq::mk(dir.x, dir.y, dir.z);
+            f3 o = P.p0;
+            if (b > 1) { const float2 xy = D.oxy[sid]; o = sq::mk(xy.x, xy.y, org.z); }
+            const f3 p = o + sq::scale(__int_as_float(hit.x), d);       // intersectPoint, src/Geometry.hs:134
+            uint32_t nu = __float_as_uint(org.w), nv = __float_as_uint(dir.w);   // (n_1, n_2)
+            if (b > 1) {
+                long long seed = first + kl;
+                asm volatile("" : "+v"(seed));
+                uint64_t c[4];
+                sq::threefish256_key_only((uint64_t)seed, c);
+                nu = tf_word(c, b); nv = tf_word(c, b + 1);
+            }
+            const f3 nd = bounce_dir(d, sb, nu, nv);
+            // Ray b + 1 is the last one when b + 2 == depth: all it adds is the emission of what it hits, so, as in sq_shade1, a ray
+            // whose own triangle test rejects every emitter (finite materials: n_emitters >= 0) need not be traced.
+            if (b + 2 == D.depth && S.n_emitters >= 0) {
+                bool may_reach = false;
+                for (int j = 0; j < S.n_emitters && !may_reach; ++j) {
+                    const float* tp = S.tris + 9 * (size_t)S.emitters[j];
+                    float t_unused;
+                    may_reach = moller_trumbore(p, nd, sq::mk(tp[0], tp[1], tp[2]), sq::mk(tp[3], tp[4], tp[5]), sq::mk(tp[6], tp[7], tp[8]), t_unused);
+                }
+                if (!may_reach) { trail_b[sid + D.cap] = -1; W.state[sid] = kDone; continue; }
+            }
+            if (b + 2 < D.depth) D.oxy[sid] = make_float2(p.x, p.y);    // a later bounce forms this ray's hit point
+            W.state[sid] = next;
+            W.org[sid] = make_float4(p.x, p.y, p.z, 0.0f);
+            W.dir[sid] = make_float4(nd.x, nd.y, nd.z, 0.0f);
+        }
+    }
+}
+template <bool MV>
+__global__ void __launch_bounds__(kBlock) sq_deep_bounce(const SceneView S, const Frame F, const Work W, int k_base, int k_count, const Deep D) { deep_bounce_body<MV>(S, F, W, k_base, k_count, D); }
+__global__ void __launch_bounds__(kBlock) sq_deep_bounce_rays(const SceneView S, const RayFrame F, const Work W, int k_base, int k_count, const Deep D) { deep_bounce_body<kSrcRays>(S, F, W, k_base, k_count, D); }
+
+// The batch's samples folded in order, one thread per active pixel: each sample's radiance is rebuilt from its trail, inside out
+// (path_radiance), and added to the pixel's sums; on the call's last batch the pixel's stores, as sq_accumulate does them.
+__global__ void __launch_bounds__(kBlock) sq_deep_fold(const SceneView S, const Frame F, const Work W, int k_count, int last, const Deep D) {
+    const int A = *W.n_active;
+    const bool mom2 = W.px_sum2 != nullptr;
+    for (int a = blockIdx.x * kBlock + threadIdx.x; a < A; a += gridDim.x * kBlock) {
+        f3 sum = sq::mk(W.px_sum[3 * a], W.px_sum[3 * a + 1], W.px_sum[3 * a + 2]), sum2 = sq::mk(0, 0, 0);
+        if (mom2) sum2 = sq::mk(W.px_sum2[3 * a], W.px_sum2[3 * a + 1], W.px_sum2[3 * a + 2]);
+        const Surface s0 = surface_of(S, W.px_tri0[a]);
+        const f3 rad0 = level0_radiance(s0);
+        const bool flat = D.depth < 2 || absorbs(S, s0);                // every sample ends at level 0: nothing was traced, nothing to read
+        for (int k = 0; k < k_count; ++k) {
+            f3 rad = rad0;
+            if (!flat) {
+                const long long sid = (long long)k * A + a;
+                int tr[kMaxDepth];
+#pragma unroll
+                for (int i = 0; i < kMaxDepth; ++i) tr[i] = -1;
+                bool more = true;
+#pragma unroll
+                for (int b = 1; b < kMaxDepth; ++b) {
+                    if (more && b < D.depth) { tr[b] = D.trail[(long long)(b - 1) * D.cap + sid]; more = tr[b] >= 0; }
+                }
+                rad = path_radiance(S, s0, tr);
+            }
+            sum = sum + rad;
+            if (mom2) sum2 = sum2 + rad * rad;
+        }
+        if (mom2) {
+            if (!last) { W.px_sum2[3 * a] = sum2.x; W.px_sum2[3 * a + 1] = sum2.y; W.px_sum2[3 * a + 2] = sum2.z; }
+            else { float* o = F.sum2 + (long long)W.px_pixel[a] * 3; o[0] = sum2.x; o[1] = sum2.y; o[2] = sum2.z; }
+        }
+        if (!last) { W.px_sum[3 * a] = sum.x; W.px_sum[3 * a + 1] = sum.y; W.px_sum[3 * a + 2] = sum.z; continue; }
+        store_fold(F, W.px_pixel[a], sum);
+    }
+}
+
+// ----------------------------------------------------------------------------------------------
 // Host: scene upload (validation and packing: sq_host.cpp, sq_pack.h)
 // ----------------------------------------------------------------------------------------------
 // A filled table of generator words: entries [0, cover) (RngView), kRngPad bytes of padding behind them.  Nothing writes to a block
@@ -1624,6 +1862,10 @@ struct sq_device_scene {
     bool lights_set = false, lights_staged = false;
     float* d_lights = nullptr; float* cast_carry = nullptr;
     int64_t opt_cast_wavefront = 0;
+    // caller-given path depth (sq_scene_set_depth) and option "deep"; d_deep = the wavefront form's per-slot state beyond the three-level
+    // pipeline's (Deep: trail, oxy), allocated by the first deep call that needs it (grow-only; a scene that stays at depth 3 has none)
+    int32_t depth = 3; int64_t opt_deep = 0;
+    void* d_deep = nullptr; size_t deep_bytes = 0;
     int64_t opt_pool = 1, opt_refill_min = 12, opt_flush_min = 40, opt_guided = 1, opt_primary_resident = 1, opt_pixel_major = -1, opt_cull = 1, opt_descend_extra = 2, opt_descend_lanes = 16, opt_primary_pooled = 0, opt_coresidency = 0, opt_trace_prio = 0, opt_aux_low_priority = 1, opt_aux_polite = 0, opt_primary_tiles = 1;
 };
 
@@ -1746,6 +1988,7 @@ extern "C" void sq_scene_free(sq_device_scene* s) {
     (void)hipFree(s->d_cams);
     (void)hipFree(s->d_px_sum2);
     (void)hipFree(s->d_lights);
+    (void)hipFree(s->d_deep);
     delete s;
 }
 
@@ -1870,6 +2113,18 @@ int ensure_px_sum2(sq_device_scene* s, int64_t pixels) {
     s->px_sum2_cap = pixels;
     return 0;
 }
+// The bytes of Deep a slot takes under depth D: a triangle per bounce level, and from D = 4 on the x and y of the ray's origin.
+size_t deep_slot_bytes(int depth) { return depth < 2 ? 0 : (size_t)(depth - 1) * 4 + (depth >= 4 ? 8 : 0); }
+// The scene's Deep block: room for `slots` slots under `depth` (grow-only, freed as the camera table is: hipFree waits for the device,
+// so a block an enqueued frame still uses is not freed under it).
+int ensure_deep(sq_device_scene* s, int64_t slots, int depth) {
+    const size_t need = (size_t)slots * deep_slot_bytes(depth);
+    if (need <= s->deep_bytes) return 0;
+    if (s->d_deep) { SQ_HIP(hipFree(s->d_deep)); s->d_deep = nullptr; s->deep_bytes = 0; }
+    if (hipMalloc(&s->d_deep, need) != hipSuccess) { (void)hipGetLastError(); s->d_deep = nullptr; return sq_set_error("hipMalloc(%zu B) for the path trails of depth %d failed", need, depth); }
+    s->deep_bytes = need;
+    return 0;
+}
 // Enqueues the copy of a multi-view frame's cameras into its table F.cams (nothing for a single-view frame: cams = nullptr).
 int stage_cams(sq_device_scene* s, const Frame& F, const sq_camera* cams, hipStream_t stream) {
     (void)s;
@@ -1936,6 +2191,9 @@ template <typename StackT, int SRC> struct SrcKernels {
     static constexpr auto cast_pixels = &sq_cast_pixels<StackT, MV>;
     static constexpr auto cast_gen = &sq_cast_gen<MV>;
     static constexpr auto cast_fold = &sq_cast_fold<MV>;
+    static constexpr auto render_pixels_deep = &sq_render_pixels_deep<StackT, MV>;
+    static constexpr auto deep_gen = &sq_deep_gen<MV>;
+    static constexpr auto deep_bounce = &sq_deep_bounce<MV>;
 };
 template <typename StackT> struct SrcKernels<StackT, kSrcRays> {
     using FrameT = RayFrame;
@@ -1949,6 +2207,9 @@ template <typename StackT> struct SrcKernels<StackT, kSrcRays> {
     static constexpr auto cast_pixels = &sq_cast_pixels_rays<StackT>;
     static constexpr auto cast_gen = &sq_cast_gen_rays;
     static constexpr auto cast_fold = &sq_cast_fold_rays;
+    static constexpr auto render_pixels_deep = &sq_render_pixels_deep_rays<StackT>;
+    static constexpr auto deep_gen = &sq_deep_gen_rays;
+    static constexpr auto deep_bounce = &sq_deep_bounce_rays;
 };
 // The kernels of one call's wavefront pipeline, chosen once: the ray source's set; in a masked call (single-view frames only: multi-view
 // frames and queries have no masked form) the AD instantiations of the kernels that decide who is active; and sq_accumulate by second
@@ -2114,6 +2375,9 @@ int launch_frame(sq_device_scene* s, const typename SrcKernels<StackT, SRC>::Fra
     // a cast frame: the per-lane form, or (option "cast_wavefront" with variant 2) the wavefront form with the lights as its samples
     const bool cast_wave = F.cast && s->opt_variant == 2 && s->opt_cast_wavefront;
     const int n_lights = (int)s->lights.size();
+    // a path-traced frame or query under a depth other than 3 (or under option "deep"): the generic-depth kernels
+    const int depth = s->depth;
+    const bool deep = !F.cast && (depth != 3 || s->opt_deep);
     if (F.cast && !cast_wave && s->lights_set) {                       // caller-given lights, per-lane: sq_cast_pixels beside sq_render_pixels
         auto cast_pixels = SrcKernels<StackT, SRC>::cast_pixels;
         if constexpr (SRC == kSrcCamera) if (ad) cast_pixels = &sq_cast_pixels<StackT, false, true>;
@@ -2122,6 +2386,14 @@ int launch_frame(sq_device_scene* s, const typename SrcKernels<StackT, SRC>::Fra
         if (stage_cams(s, F, cams, stream)) return 1;
         const Lights L{ s->d_lights, n_lights, nullptr, 0, n_lights };
         return timed_launch(s, [&] { hipLaunchKernelGGL(cast_pixels, dim3((unsigned)px_blocks), dim3(kBlock), px_lds, stream, S, F, L); }, "sq_cast_pixels", stream);
+    }
+    if (s->opt_variant == 1 && deep) {                                  // per-lane: sq_render_pixels_deep beside sq_render_pixels
+        auto render_deep = SrcKernels<StackT, SRC>::render_pixels_deep;
+        if constexpr (SRC == kSrcCamera) if (ad) render_deep = &sq_render_pixels_deep<StackT, false, true>;
+        if (px_lds > 64 * 1024) SQ_HIP(hipFuncSetAttribute((const void*)render_deep, hipFuncAttributeMaxDynamicSharedMemorySize, (int)px_lds));
+        P.launched = 1;
+        if (stage_cams(s, F, cams, stream)) return 1;
+        return timed_launch(s, [&] { hipLaunchKernelGGL(render_deep, dim3((unsigned)px_blocks), dim3(kBlock), px_lds, stream, S, F, depth); }, "sq_render_pixels_deep", stream);
     }
     if (s->opt_variant == 1 || (F.cast && !cast_wave)) {
         auto render_pixels = SrcKernels<StackT, SRC>::render_pixels;
@@ -2147,7 +2419,7 @@ int launch_frame(sq_device_scene* s, const typename SrcKernels<StackT, SRC>::Fra
     // Opt-in (sq_set_option "overlap"): measured +3 % on the headline frame (105.5 -> 102.3 ms) -- the kernels do
     // run side by side, but the chip is VALU-bound as a whole, so each slows the other down by what it gains;
     // and trace-launch durations then include that interference, which blurs the per-kernel roofline figure.
-    const bool overlap = s->opt_overlap && !cast_wave && n_call >= 2 && have_slots >= 2 * pixels;
+    const bool overlap = s->opt_overlap && !cast_wave && !deep && n_call >= 2 && have_slots >= 2 * pixels;
     const int tracks = overlap ? 2 : 1;
     const int64_t track_slots = have_slots / tracks;
     Work Wt[2] = { W, W };
@@ -2173,6 +2445,7 @@ int launch_frame(sq_device_scene* s, const typename SrcKernels<StackT, SRC>::Fra
     if (P.primary_form == SQ_PRIMARY_PER_LANE && (primary_padded(F) * F.n_views + kBlock - 1) / kBlock * kBlock > 0xffffffffLL)
         return sq_set_error("image too large for one launch of the primary rays (%lld tile lanes; at most 2^32 - 1)", primary_padded(F) * F.n_views);
     if (cast_wave && ensure_light_table(s)) return 1;
+    if (deep && ensure_deep(s, W.slot_capacity, depth)) return 1;
     P.launched = 1;                                                    // planned; what follows fails only on HIP errors
     // nothing is enqueued before this point, so a refusal above leaves every buffer as it was
     if (stage_cams(s, F, cams, stream)) return 1;                       // multi-view: before every kernel that reads the table (e_setup below)
@@ -2180,7 +2453,7 @@ int launch_frame(sq_device_scene* s, const typename SrcKernels<StackT, SRC>::Fra
         if (stage_lights(s, s->lights, stream)) return 1;
         s->lights_staged = true;
     }
-    const RngView R = cast_wave ? RngView{ nullptr, 0 } : ensure_rng_table(s, F, stream, SRC != kSrcRays);   // allocated behind the workspace; its fill and the wait for it come before every sq_gen_bounce1 (e_setup below)
+    const RngView R = cast_wave ? RngView{ nullptr, 0 } : ensure_rng_table(s, F, stream, SRC != kSrcRays && !deep);   // allocated behind the workspace; its fill and the wait for it come before every sq_gen_bounce1 (e_setup below)
     // (a masked call's dead pixels keep what they hold: its primary kernels write the black of the live misses, store_live_miss)
     if (F.out_avg && !ad) SQ_HIP(hipMemsetAsync(F.out_avg, 0, (size_t)pixels * 3 * sizeof(float), stream));   // pixels whose primary ray misses: black
     if (F.out_rgb && !ad) SQ_HIP(hipMemsetAsync(F.out_rgb, 0, (size_t)pixels * 3, stream));
@@ -2228,6 +2501,32 @@ int launch_frame(sq_device_scene* s, const typename SrcKernels<StackT, SRC>::Fra
             SQ_HIP(hipGetLastError());
             if (launch_trace_kernel(s, S, TP, W, pixels, kc, 0, stream, false)) return 1;
             hipLaunchKernelGGL((SrcKernels<StackT, SRC>::cast_fold), dim3(aux_blocks), dim3(kBlock), 0, stream, S, F, W, L, l0 + kc == n_lights ? 1 : 0);
+            SQ_HIP(hipGetLastError());
+        }
+        return 0;
+    }
+    if (deep) {
+        // Sample batch i holds the samples [k0, k0 + kc): ray 1 into the slots, then level by level a trace launch and the bounce behind
+        // it, then the ordered fold.  Everything on the caller's stream ("overlap" is for the three-level pipeline).
+        const long long cap = (long long)W.slot_capacity;
+        float2* const oxy = (float2*)s->d_deep;
+        int32_t* const trail = (int32_t*)((char*)s->d_deep + (depth >= 4 ? (size_t)cap * sizeof(float2) : 0));
+        for (int i = 0; i * batch < n_call; ++i) {
+            const int k0 = F.k_begin + i * batch, kc = std::min(batch, n_call - i * batch);
+            if (depth >= 2) {
+                SQ_HIP(hipMemsetAsync(W.head[0], 0, 32 * sizeof(int32_t), stream));     // both dequeue cursors
+                hipLaunchKernelGGL((SrcKernels<StackT, SRC>::deep_gen), pp_grid(kc), dim3(kBlock), 0, stream, S, F, W, k0, kc, R);
+                SQ_HIP(hipGetLastError());
+            }
+            for (int b = 1; b < depth; ++b) {
+                const Deep D{ depth, b, trail, oxy, cap };
+                if (b >= 3) SQ_HIP(hipMemsetAsync(W.head[0], 0, 32 * sizeof(int32_t), stream));   // a cursor's second use
+                if (launch_trace_kernel(s, S, TP, W, pixels, kc, (b - 1) & 1, stream, false)) return 1;
+                hipLaunchKernelGGL((SrcKernels<StackT, SRC>::deep_bounce), pp_grid(kc), dim3(kBlock), 0, stream, S, F, W, k0, kc, D);
+                SQ_HIP(hipGetLastError());
+            }
+            const Deep D{ depth, 0, trail, oxy, cap };
+            hipLaunchKernelGGL(sq_deep_fold, dim3(aux_blocks), dim3(kBlock), 0, stream, S, F, W, kc, (i + 1) * batch >= n_call ? 1 : 0, D);
             SQ_HIP(hipGetLastError());
         }
         return 0;
@@ -2733,6 +3032,17 @@ extern "C" int32_t sq_scene_get_lights(sq_device_scene* s, sq_light* out, int32_
     return n;
 }
 
+extern "C" int sq_scene_set_depth(sq_device_scene* s, int32_t depth) {
+    if (!s) return sq_set_error("null argument");
+    if (depth < 1 || depth > kMaxDepth) return sq_set_error("depth must be in 1..%d (got %d)", kMaxDepth, depth);
+    s->depth = depth;
+    return 0;
+}
+extern "C" int32_t sq_scene_get_depth(sq_device_scene* s) {
+    if (!s) { sq_set_error("null argument"); return -1; }
+    return s->depth;
+}
+
 extern "C" int64_t sq_scene_rng_table(sq_device_scene* s, int64_t first, int64_t count, uint32_t* out_words) {
     if (!s) { sq_set_error("null argument"); return -1; }
     const int64_t cover = s->rng.words ? s->rng.cover : 0;
@@ -2799,6 +3109,7 @@ extern "C" int sq_set_option(sq_device_scene* s, const char* key, int64_t value)
     if (!std::strcmp(key, "overlap")) { if (value < 0 || value > 2) return sq_set_error("overlap must be 0, 1 or 2"); s->opt_overlap = value; return 0; }
     if (!std::strcmp(key, "rng_table_mb")) { if (value < 0 || value > (1ll << 20)) return sq_set_error("rng_table_mb must be in 0..2^20"); s->opt_rng_table_mb = value; return 0; }
     if (!std::strcmp(key, "cast_wavefront")) { s->opt_cast_wavefront = value ? 1 : 0; return 0; }
+    if (!std::strcmp(key, "deep")) { s->opt_deep = value ? 1 : 0; return 0; }
     if (!std::strcmp(key, "pool")) { s->opt_pool = value ? 1 : 0; return 0; }
     if (!std::strcmp(key, "guided")) { if (value < 0 || value > 3) return sq_set_error("guided must be in 0..3"); s->opt_guided = value; return 0; }
     if (!std::strcmp(key, "primary_resident")) { s->opt_primary_resident = value ? 1 : 0; return 0; }

@@ -124,6 +124,21 @@ class DeviceScene:
         N.lib().sq_scene_get_lights(self._h, out.ctypes.data, n)
         return out
 
+    def set_depth(self, depth):
+        """The path depth D of the scene's path-traced frames and raytrace queries (sq_scene_set_depth): a path is D rays long,
+        1 <= D <= 8; 3 is the reference's (src/Lib.hs:129) and every scene's until set.  Host state that the next call reads:
+        nothing is enqueued.  Cast frames and raycast ignore it."""
+        d = N.depth_value(depth)                                        # refused before any device work
+        N.check(N.lib().sq_scene_set_depth(self._h, d))
+
+    @property
+    def depth(self):
+        """The scene's path depth (sq_scene_get_depth)."""
+        d = N.lib().sq_scene_get_depth(self._h)
+        if d < 0:
+            raise N.SquiglyError(N.lib().sq_last_error().decode(errors="replace"))
+        return int(d)
+
     def rng_table(self, first=0, count=0):
         """sq_scene_rng_table: (seeds the scene's table of generator words holds, its entries [first, first + count) as a uint32
         numpy array [count, 3])."""
@@ -428,15 +443,36 @@ class DeviceScene:
     __del__ = close
 
 
+def _checkpoint_depth(dscene, depth):
+    """The path depth a Progressive / Adaptive frame runs under: the scene's.  depth: what a checkpoint carried (None = a fresh
+    frame, or a checkpoint from before depths existed, which is the scene's own); SquiglyError when the scene has another."""
+    have = dscene.depth
+    if depth is not None and N.depth_value(depth) != have:
+        raise N.SquiglyError(f"the checkpoint was rendered under depth {int(depth)}, the scene has depth {have}: "
+                             f"set_depth({int(depth)}) first")
+    return have
+
+
+def _same_depth(frame):
+    if frame.cast:
+        return
+    have = frame.dscene.depth
+    if have != frame.depth:
+        raise N.SquiglyError(f"the frame was begun under depth {frame.depth}, the scene now has depth {have}")
+
+
 class Progressive:
     """A frame rendered a few samples at a time (DeviceScene.render_rows_range), bit-exact to one render_rows call.
 
     Owns -- or adopts, to resume a checkpoint -- the [rows, h, 3] float32 fold `sums` and the count `done` of samples folded
     into it.  `step(n)` renders the next min(n, samples - done) samples and returns the (avg, rgb) preview of the first
-    `done` samples; to checkpoint, copy `sums` and `done` away, and pass them back in to resume, in this process or another.
+    `done` samples; to checkpoint, copy `sums` and `done` away, and pass them back in to resume, in this process or another.  A checkpoint
+    also carries `depth`, the scene's path depth when the frame began: pass it back in as depth=, and a scene under another depth
+    refuses to resume it (a fold that mixes depths is no frame); so does step() once the scene's depth was changed under the frame.
+    A cast frame has no paths: its `depth` is None and it ignores the scene's.
     """
 
-    def __init__(self, dscene, cam, samples, w, h, cast=False, shard=(None, 0, 1), sums=None, done=0):
+    def __init__(self, dscene, cam, samples, w, h, cast=False, shard=(None, 0, 1), sums=None, done=0, depth=None):
         samples, done = int(samples), int(done)
         if samples < 1:
             raise ValueError(f"samples must be positive, got {samples}")
@@ -447,6 +483,7 @@ class Progressive:
         if rows < 0:
             raise N.SquiglyError(f"bad shard {shard}")
         _check_frame_size(dscene, rows, h, cast)
+        self.depth = None if cast else _checkpoint_depth(dscene, depth)      # a cast frame has no paths: it ignores the depth
         dev = torch.device("cuda", dscene.device)
         if sums is None:
             if done:
@@ -480,6 +517,7 @@ class Progressive:
             raise RuntimeError(f"the frame is finished: all {self.samples} samples are rendered")
         if int(n) < 1:
             raise ValueError(f"a step renders at least one sample, got {n}")
+        _same_depth(self)
         k_end = min(self._done + int(n), self.samples)
         avg, rgb = self.dscene.render_rows_range(self.cam, self.samples, self.w, self.h, self._done, k_end, self._sums,
                                                  cast=self.cast, shard=self.shard, stream=stream)
@@ -515,11 +553,12 @@ class Adaptive:
     the first n samples of the `samples`-sample frame.  rule: a callable (sums, sums2, counts, mask) -> new mask instead of
     the built-in rule (DeviceScene.adaptive_update with tol, eps), which is a heuristic -- a pixel that has seen nothing but
     black after `first` samples stops.  A pixel the rule switches back on after it was left out of a range stays out: its
-    fold would have a gap.  To checkpoint, copy the four tensors and `done` away and pass them back in.
+    fold would have a gap.  To checkpoint, copy the four tensors, `done` and `depth` away and pass them back in (depth as in
+    Progressive: a scene under another path depth refuses to resume).
     """
 
     def __init__(self, dscene, cam, samples, w, h, tol, eps=1.0, first=8, step=8, cast=False, shard=(None, 0, 1), rule=None,
-                 sums=None, sums2=None, counts=None, mask=None, done=0):
+                 sums=None, sums2=None, counts=None, mask=None, done=0, depth=None):
         samples, done, first, step = int(samples), int(done), int(first), int(step)
         tol, eps = float(tol), float(eps)
         if samples < 1:
@@ -539,6 +578,7 @@ class Adaptive:
         if rows < 0:
             raise N.SquiglyError(f"bad shard {shard}")
         _check_frame_size(dscene, rows, h, cast)
+        self.depth = None if cast else _checkpoint_depth(dscene, depth)      # a cast frame has no paths: it ignores the depth
         dev = torch.device("cuda", dscene.device)
 
         def adopt(name, t, shape, dtype, fill):   # a matching CUDA tensor as it is; a host copy is copied to the device
@@ -603,6 +643,7 @@ class Adaptive:
         if self.finished:
             raise RuntimeError("the frame is finished: no pixel is live" if self._live == 0
                                else f"the frame is finished: all {self.samples} samples are rendered")
+        _same_depth(self)
         k_end = min(self._done + (self.first if self._done == 0 else self.step_size), self.samples)
         self.dscene.render_rows_masked(self.cam, self.samples, self.w, self.h, self._done, k_end, self._sums, mask=self._mask,
                                        sums2=self._sums2, counts=self._counts, cast=self.cast, shard=self.shard, stream=stream,

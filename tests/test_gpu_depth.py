@@ -1,0 +1,449 @@
+"""Caller-given path depth on the GPU (sq_scene_set_depth, DeviceScene.set_depth): queries, folds, frames, masked and multi-view
+calls under a depth D equal the restatement of include/squigly_hip.h's formula (tests/depth_restatement.py, pinned to the oracle at
+D = 3 by tests/test_depth.py) bit for bit, in the per-lane form and around every trace form; option "deep" holds the generic-depth
+kernels to the C oracle's goldens at D = 3; and a scene back at depth 3 runs what it ran before."""
+import ctypes as C
+import os
+
+import numpy as np
+import pytest
+
+import depth_restatement as DR
+import tree_padding as TP
+from conftest import DATA, GOLDEN
+from test_gpu_raytrace import ROTATED, primary_form_of, raytrace, set_options as set_ray_options
+from test_gpu_rays import SCENE_FORMS, ibits, nan_eq
+
+pytestmark = pytest.mark.gpu
+f32 = np.float32
+DEPTHS = (1, 2, 4, 5, 8)            # 4 and 5 end on either parity of the alternating queue state; 8 reaches n_7
+FORM_IDS = [f"{f}-{'-'.join(f'{k}{v}' for k, v in o.items()) or 'default'}" for o, f in SCENE_FORMS]
+
+
+def set_options(ds, depth=3, deep=0, **opts):
+    set_ray_options(ds, **opts)
+    ds.set_option("deep", deep)
+    ds.set_option("cast_wavefront", 0)
+    ds.set_depth(depth)
+
+
+def from_zero(r):
+    with np.errstate(all="ignore"):
+        return (f32(0) + r).astype(f32)                               # a one-sample fold: 0 + r
+
+
+def camera(sqt, which):
+    return sqt.camera_from_text(open(os.path.join(DATA, "camera"), "rb").read() if which == "camera" else ROTATED)
+
+
+def tonemaps(O, avg):
+    return np.array([O.tonemap(a) for a in avg.reshape(-1, 3)], np.uint8).reshape(avg.shape)
+
+
+class Scene:
+    pass
+
+
+def open_case(sqt, which):
+    s = Scene()
+    s.c = DR.case(which)
+    s.paths = DR.case_paths(s.c)
+    s.ds = sqt.DeviceScene(s.c.bih, 0)
+    return s
+
+
+@pytest.fixture(scope="module")
+def bright(sqt):
+    s = open_case(sqt, "bright")
+    yield s
+    s.ds.close()
+
+
+@pytest.fixture(scope="module")
+def shipped(sqt):
+    s = open_case(sqt, "shipped")
+    yield s
+    s.ds.close()
+
+
+# ---- 1. queries ------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("which", ("bright", "shipped"))
+@pytest.mark.parametrize("opts, form", SCENE_FORMS, ids=FORM_IDS)
+def test_one_sample_equals_the_restatement_at_every_depth_in_every_form(request, which, opts, form):
+    s = request.getfixturevalue(which)
+    c, ds = s.c, s.ds
+    try:
+        for slots in (512 << 20, 1024):                               # 1024: the 4000 rays run as four chunks
+            for depth in DEPTHS:
+                set_options(ds, depth=depth, **{**opts, "slots": slots})
+                assert ds.depth == depth
+                got = raytrace(ds, c.o, c.d, c.s)[0]
+                want = from_zero(DR.radiances(s.paths, depth))
+                ok = nan_eq(got, want).all(-1)
+                assert ok.all(), (which, form, slots, depth, int((~ok).sum()), np.nonzero(~ok)[0][:8])
+                plan = ds.last_plan()
+                assert plan["trace_form"] == form and plan["launched"] == 1 and plan["primary_form"] == primary_form_of(form, opts), plan
+    finally:
+        set_options(ds)
+
+
+# ---- 2. folds --------------------------------------------------------------------------------------------------------
+def test_a_fold_of_eight_samples_at_depth_5_in_ranges_and_batches(sqt, O, bright):
+    import torch
+    c = bright.c
+    idx = np.arange(0, len(c.o), 4)                                   # 1000 rays, every family
+    o, d, sd = c.o[idx], c.d[idx], c.s[idx]
+    rs = [DR.radiances([bright.paths[i] for i in idx], 5)] + [DR.radiances(DR.paths(c.ob, c.flat, o, d, sd, k=k), 5) for k in range(1, 8)]
+    want_sum = np.zeros_like(rs[0])
+    with np.errstate(all="ignore"):
+        for r in rs:
+            want_sum = (want_sum + r).astype(f32)
+        want_avg = ((f32(1) / f32(8)) * want_sum).astype(f32)
+    want_rgb = tonemaps(O, want_avg)
+    assert (want_sum != 0).any(-1).mean() > 0.3
+    for opts in ({}, {"variant": 1}, {"resident": 0, "trace_blocks_per_cu": 1}):
+        ds = sqt.DeviceScene(c.bih, 0)                                # a workspace that never held more: 3 samples per batch
+        try:
+            set_options(ds, depth=5, slots=3 * len(o), **opts)
+            ds.reset_timing()
+            ds.enable_timing(True)
+            whole = raytrace(ds, o, d, sd, samples=8, want_rgb=True)
+            launches = ds.kernel_timing()[1]
+            ds.enable_timing(False)
+            if opts.get("variant") != 1:                              # batches of 3, 3 and 2 samples, four trace launches each
+                assert launches == 3 * 4, launches
+            for g, e, name in zip(whole, (want_sum, want_avg, want_rgb), ("sum", "avg", "rgb")):
+                assert nan_eq(g, e).all() if g.dtype == f32 else np.array_equal(g, e), (opts, name)
+            sums = None
+            for k0, k1 in ((0, 3), (3, 8)):
+                r = ds.raytrace(o, d, seeds=sd, samples=8, k_range=(k0, k1), sums=sums, want_rgb=True)
+                sums = r.sum
+            torch.cuda.synchronize()
+            for g, e in zip(r, whole):
+                assert np.array_equal(g.cpu().numpy().view(np.uint8), e.view(np.uint8)), opts
+        finally:
+            ds.close()
+
+
+# ---- 3. frames -------------------------------------------------------------------------------------------------------
+PRIMARY_FORMS = (({}, "resident"), ({"primary_resident": 0}, "per_lane"), ({"primary_pooled": 1}, "pooled"), ({"variant": 1}, "none"))
+
+
+@pytest.mark.parametrize("cam_name", ("camera", "rotated"))
+@pytest.mark.parametrize("w, h", ((16, 24), (40, 72)))
+def test_a_frame_equals_the_restatements_frame_and_the_query_of_its_rays(sqt, O, bright, w, h, cam_name):
+    import torch
+    ds, spp = bright.ds, 3
+    cam = camera(sqt, cam_name)
+    fp = DR.frame_case("bright", cam_name, w, h, spp)
+    try:
+        for depth in (2, 5, 8):
+            _, _, avg_all = DR.fold_frame(fp, depth)
+            avg_all = avg_all.reshape(w, h, 3)
+            assert avg_all.any()
+            for shard in ((None, 0, 1), (2, 1, 3)):
+                want = avg_all[DR.shard_rows(w, shard)]
+                want_rgb = tonemaps(O, want)
+                for opts, primary in PRIMARY_FORMS:
+                    set_options(ds, depth=depth, **opts)
+                    avg, rgb = ds.render_rows(cam, spp, w, h, shard=shard)
+                    torch.cuda.synchronize()
+                    what = (depth, shard, opts)
+                    assert ds.last_plan()["primary_form"] == primary and ds.last_plan()["launched"] == 1, what
+                    assert np.array_equal(ibits(avg.cpu().numpy()), ibits(want)), what
+                    assert np.array_equal(rgb.cpu().numpy(), want_rgb), what
+                set_options(ds, depth=depth)
+                q = ds.raytrace(*ds.camera_rays(cam, w, h, shard=shard), seeds=sqt.frame_seeds(spp, w, h, shard=shard, device="cuda:0"),
+                                samples=spp, want_rgb=True)
+                torch.cuda.synchronize()
+                assert np.array_equal(ibits(q.avg.cpu().numpy()), ibits(want)) and np.array_equal(q.rgb.cpu().numpy(), want_rgb), (depth, shard)
+    finally:
+        set_options(ds)
+
+
+# ---- 4. the generic pipeline against the C oracle itself -------------------------------------------------------------
+@pytest.mark.parametrize("opts, form", SCENE_FORMS, ids=FORM_IDS)
+def test_deep_1_at_depth_3_equals_the_goldens_and_deep_0(sqt, shipped, opts, form):
+    import torch
+    ds = shipped.ds
+    cam = camera(sqt, "camera")
+    try:
+        for w, h, spp in ((64, 64, 4), (40, 72, 3)):
+            set_options(ds, deep=1, **opts)
+            avg, rgb = ds.render_rows(cam, spp, w, h)
+            torch.cuda.synchronize()
+            assert ds.last_plan()["trace_form"] == form
+            avg, rgb = avg.cpu().numpy(), rgb.cpu().numpy()
+            assert np.array_equal(ibits(avg), ibits(np.load(os.path.join(GOLDEN, f"scene_{w}x{h}_{spp}spp_avg.npy")).reshape(avg.shape))), (form, w, h)
+            if (w, h) == (64, 64):
+                assert np.array_equal(rgb, np.load(os.path.join(GOLDEN, "scene_64x64_4spp_rgb8.npy")).reshape(rgb.shape)), form
+            set_options(ds, deep=0, **opts)
+            avg0, rgb0 = ds.render_rows(cam, spp, w, h)
+            torch.cuda.synchronize()
+            assert np.array_equal(ibits(avg0.cpu().numpy()), ibits(avg)) and np.array_equal(rgb0.cpu().numpy(), rgb), (form, w, h)
+    finally:
+        set_options(ds)
+
+
+# ---- 5. masked calls and views ---------------------------------------------------------------------------------------
+def test_a_masked_call_at_depth_4_holds_the_restatements_moments_and_leaves_dead_pixels_alone(sqt, bright):
+    import torch
+    ds, w, h, spp, depth = bright.ds, 16, 24, 3, 4
+    cam = camera(sqt, "camera")
+    want_sum, want_sum2, _ = DR.fold_frame(DR.frame_case("bright", "camera", w, h, spp), depth)
+    want_sum, want_sum2 = want_sum.reshape(w, h, 3), want_sum2.reshape(w, h, 3)
+    live = (np.add.outer(np.arange(w), np.arange(h)) % 2 == 0)
+    assert (want_sum2[live] != 0).any(-1).mean() > 0.3
+    try:
+        for opts in ({}, {"variant": 1}, {"resident": 0, "trace_blocks_per_cu": 1}):
+            set_options(ds, depth=depth, **opts)
+            mask = torch.from_numpy(live.astype(np.uint8)).cuda()
+            sums = torch.full((w, h, 3), 5.5, dtype=torch.float32, device="cuda:0")
+            sums2 = torch.full((w, h, 3), -6.5, dtype=torch.float32, device="cuda:0")
+            counts = torch.full((w, h), 77, dtype=torch.int32, device="cuda:0")
+            avg = torch.full((w, h, 3), 8.25, dtype=torch.float32, device="cuda:0")
+            rgb = torch.full((w, h, 3), 99, dtype=torch.uint8, device="cuda:0")
+            ds.render_rows_masked(cam, spp, w, h, 0, spp, sums, mask=mask, sums2=sums2, counts=counts, out_avg=avg, out_rgb=rgb)
+            torch.cuda.synchronize()
+            s, q, n = sums.cpu().numpy(), sums2.cpu().numpy(), counts.cpu().numpy()
+            assert np.array_equal(ibits(s[live]), ibits(want_sum[live])), opts
+            assert np.array_equal(ibits(q[live]), ibits(want_sum2[live])), opts
+            assert (n[live] == spp).all()
+            assert (s[~live] == 5.5).all() and (q[~live] == -6.5).all() and (n[~live] == 77).all(), opts
+            assert (avg.cpu().numpy()[~live] == 8.25).all() and (rgb.cpu().numpy()[~live] == 99).all(), opts
+    finally:
+        set_options(ds)
+
+
+def test_two_cameras_in_one_views_call_equal_their_single_view_frames(sqt, bright):
+    import torch
+    ds, w, h, spp = bright.ds, 16, 24, 3
+    cams = [camera(sqt, "camera"), camera(sqt, "rotated")]
+    try:
+        for opts in ({}, {"variant": 1}):
+            set_options(ds, depth=4, **opts)
+            avg, rgb = ds.render_views(cams, spp, w, h)
+            singles = [ds.render_rows(c, spp, w, h) for c in cams]
+            torch.cuda.synchronize()
+            for i, (a, r) in enumerate(singles):
+                assert np.array_equal(ibits(avg[i].cpu().numpy()), ibits(a.cpu().numpy())) and torch.equal(rgb[i], r), (opts, i)
+            _, _, want = DR.fold_frame(DR.frame_case("bright", "rotated", w, h, spp), 4)
+            assert np.array_equal(ibits(avg[1].cpu().numpy()), ibits(want.reshape(w, h, 3))), opts
+    finally:
+        set_options(ds)
+
+
+# ---- 6. odd materials ------------------------------------------------------------------------------------------------
+def test_infinite_negative_and_zero_materials_at_depth_4(sqt):
+    c = DR.case("odd")
+    want = from_zero(DR.radiances(DR.case_paths(c), 4))
+    assert np.isnan(want).any() and len(c.o) == 500
+    ds = sqt.DeviceScene(c.bih, 0)
+    try:
+        for opts in ({}, {"variant": 1}, {"resident": 0, "trace_blocks_per_cu": 1}):
+            set_options(ds, depth=4, **opts)
+            got = raytrace(ds, c.o, c.d, c.s)[0]
+            ok = nan_eq(got, want).all(-1)
+            assert ok.all(), (opts, int((~ok).sum()), np.nonzero(~ok)[0][:8])
+            assert ds.last_plan()["n_emitters"] == -1
+    finally:
+        ds.close()
+
+
+# ---- 7. tall trees ---------------------------------------------------------------------------------------------------
+def test_tall_tree_per_lane_form_at_depth_5_and_the_default_form_is_refused(sqt, shipped):
+    import torch
+    c = shipped.c
+    cam = camera(sqt, "camera")
+    cd = shipped.ds.camera_rays(cam, 32, 24)[1].cpu().numpy().reshape(-1, 3)
+    axis, side = TP.near_side(cd)
+    height = 200                                                      # 2-byte words: the per-lane kernel takes it, the wavefront form does not
+    ps = TP.full_stack(c.bih, height, axis, side)
+    assert ps.height == height
+    idx = np.concatenate([np.arange(i * DR.N_RAYS, i * DR.N_RAYS + 300) for i in range(4)])
+    o, d, sd = c.o[idx], c.d[idx], c.s[idx]
+    want = from_zero(DR.radiances([shipped.paths[i] for i in idx], 5))    # the padding is transparent
+    ds = sqt.DeviceScene(ps, 0)
+    try:
+        set_options(ds, depth=5, variant=1)
+        got = raytrace(ds, o, d, sd)[0]
+        assert nan_eq(got, want).all(), int((~nan_eq(got, want)).any(-1).sum())
+        assert ds.last_plan()["trace_form"] == "per_pixel" and ds.last_plan()["height"] == height
+        set_options(ds, depth=5)
+        sums = torch.full((len(o), 3), 7.5, dtype=torch.float32, device="cuda:0")
+        avg = torch.full((len(o), 3), -3.25, dtype=torch.float32, device="cuda:0")
+        to, td, ts = torch.from_numpy(o).cuda(), torch.from_numpy(d).cuda(), torch.from_numpy(sd).cuda()
+        rc = sqt.lib().sq_raytrace_rays_device(ds._h, to.data_ptr(), td.data_ptr(), ts.data_ptr(), len(o), 0, 1, sums.data_ptr(),
+                                               avg.data_ptr(), None, C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        assert rc != 0 and f"BIH height {height} needs" in sqt.lib().sq_last_error().decode()
+        torch.cuda.synchronize()
+        assert (sums == 7.5).all() and (avg == -3.25).all()
+        assert ds.last_plan()["launched"] == 0
+    finally:
+        ds.close()
+
+
+# ---- 8. depth 3 is untouched -----------------------------------------------------------------------------------------
+def test_depth_3_after_depth_5_is_the_golden_and_cast_ignores_the_depth(sqt, shipped):
+    import torch
+    c = shipped.c
+    cam = camera(sqt, "camera")
+    golden = np.load(os.path.join(GOLDEN, "scene_64x64_4spp_avg.npy"))
+    ds = sqt.DeviceScene(c.bih, 0)
+    try:
+        set_options(ds)
+        assert ds.depth == 3
+        first, _ = ds.render_rows(cam, 4, 64, 64)
+        cast3, _ = ds.render_rows(cam, 2, 64, 64, cast=True)
+        rc3 = ds.raycast(c.o, c.d)
+        torch.cuda.synchronize()
+        cover = ds.rng_table()[0]
+        assert cover > 0
+        ds.set_depth(5)
+        assert ds.depth == 5
+        # a larger frame, whose seeds the table covers in part (a depth-3 frame would grow it): sq_deep_gen reads the table for some
+        # pixels and computes the words of the others; the per-lane form, which reads no table, is held to the restatement above
+        deep, deep8 = ds.render_rows(cam, 4, 96, 96)
+        cast5, _ = ds.render_rows(cam, 2, 64, 64, cast=True)
+        rc5 = ds.raycast(c.o, c.d)
+        torch.cuda.synchronize()
+        assert deep.cpu().numpy().any()
+        assert 0 < cover < 4 * 96 * 96
+        assert ds.rng_table()[0] == cover
+        ds.set_option("variant", 1)
+        lane, lane8 = ds.render_rows(cam, 4, 96, 96)
+        ds.set_option("variant", 2)
+        torch.cuda.synchronize()
+        assert np.array_equal(ibits(deep.cpu().numpy()), ibits(lane.cpu().numpy())) and torch.equal(deep8, lane8)
+        assert torch.equal(cast5, cast3) and np.array_equal(ibits(rc5.cpu().numpy()), ibits(rc3.cpu().numpy())) and cast3.any()
+        ds.set_depth(3)
+        assert ds.depth == 3
+        ds.reset_timing()
+        ds.enable_timing(True)
+        again, _ = ds.render_rows(cam, 4, 64, 64)
+        torch.cuda.synchronize()
+        assert ds.kernel_timing()[1] == 2                               # the three-level pipeline's two trace launches
+        ds.enable_timing(False)
+        assert ds.rng_table()[0] == cover
+        for a in (first, again):
+            assert np.array_equal(ibits(a.cpu().numpy()), ibits(golden.reshape(64, 64, 3)))
+    finally:
+        ds.close()
+
+
+# ---- 9. streams ------------------------------------------------------------------------------------------------------
+def test_a_deep_frame_and_a_deep_query_on_a_gated_side_stream(sqt, O, product_scene, oracle_scene):
+    import torch
+    import test_gpu_streams as S
+    env = S.Env(sqt, torch, O, product_scene[0], oracle_scene[0])
+    try:
+        for form in ("default", "variant1", "resident0"):
+            env.set_options(env.ds, **S.FORMS[form])
+            env.ds.set_depth(5)
+            frames = S.drive(env, S.job_frames(env, env.ds), env.side, f"deep frames-{form}")
+            rays = S.drive(env, S.job_raytrace(env, env.ds), env.side, f"deep raytrace-{form}")
+            assert frames["avg0"].any() and rays["rsum"].any()
+            env.ds.set_depth(3)
+            torch.cuda.synchronize()
+            three = S.plain(env, S.job_frames(env, env.ds))[0]
+            assert np.array_equal(S.bits(three["avg0"]), S.bits(S.golden("scene_64x64_4spp_avg.npy").reshape(three["avg0"].shape)))
+            assert not np.array_equal(S.bits(three["avg0"]), S.bits(frames["avg0"]))       # the deep frame was deep
+    finally:
+        env.ds.set_depth(3)
+        env.set_options(env.ds)
+        env.close()
+
+
+# ---- 10. refusals ----------------------------------------------------------------------------------------------------
+def test_depth_0_and_9_through_the_c_call_change_nothing(sqt, bright):
+    L, ds = sqt.lib(), bright.ds
+    set_options(ds, depth=4)
+    for bad in (0, 9, -3, 1 << 20):
+        assert L.sq_scene_set_depth(ds._h, bad) != 0
+        assert b"depth" in L.sq_last_error()
+        assert L.sq_scene_get_depth(ds._h) == 4 and ds.depth == 4
+    with pytest.raises(sqt.SquiglyError):
+        ds.set_depth(9)
+    assert ds.depth == 4
+    set_options(ds)
+    assert ds.depth == 3
+
+
+def test_progressive_and_adaptive_carry_the_depth(sqt, bright):
+    import torch
+    ds, w, h, spp = bright.ds, 16, 24, 3
+    cam = camera(sqt, "camera")
+    device = __import__("importlib").import_module("squigly-trace_amd.device")
+    _, _, want = DR.fold_frame(DR.frame_case("bright", "camera", w, h, spp), 5)
+    try:
+        set_options(ds, depth=5)
+        p = device.Progressive(ds, cam, spp, w, h)
+        assert p.depth == 5
+        p.step(1)
+        sums, done = p.sums.clone(), p.done
+        ds.set_depth(3)
+        with pytest.raises(sqt.SquiglyError, match="depth"):
+            p.step(1)
+        with pytest.raises(sqt.SquiglyError, match="depth"):
+            device.Progressive(ds, cam, spp, w, h, sums=sums, done=done, depth=5)
+        with pytest.raises(sqt.SquiglyError, match="depth"):
+            device.Adaptive(ds, cam, spp, w, h, 0.1, depth=5)
+        ds.set_depth(5)
+        r = device.Progressive(ds, cam, spp, w, h, sums=sums, done=done, depth=5)
+        avg, _ = r.step(2)
+        torch.cuda.synchronize()
+        assert r.finished and np.array_equal(ibits(avg.cpu().numpy()), ibits(want.reshape(w, h, 3)))
+        a = device.Adaptive(ds, cam, spp, w, h, 0.0, first=spp)
+        assert a.depth == 5
+        avg, _ = a.step()
+        torch.cuda.synchronize()
+        assert np.array_equal(ibits(avg.cpu().numpy()), ibits(want.reshape(w, h, 3)))
+        # a cast frame has no paths: it neither records the depth nor minds a change of it
+        set_options(ds, depth=5)
+        pc = device.Progressive(ds, cam, spp, w, h, cast=True)
+        pc.step(1)
+        ds.set_depth(2)
+        cast_avg, _ = pc.step(2)
+        whole, _ = ds.render_rows(cam, spp, w, h, cast=True)
+        torch.cuda.synchronize()
+        assert pc.depth is None and torch.equal(cast_avg, whole) and whole.any()
+        device.Progressive(ds, cam, spp, w, h, cast=True, sums=pc.sums, done=1, depth=7)
+    finally:
+        set_options(ds)
+
+
+# ---- 11. the CLIs ----------------------------------------------------------------------------------------------------
+def test_both_clis_render_a_depth_frame_equal_to_the_device_scenes(sqt, tmp_path, product_scene):
+    """--depth N through the C++ executable (a child process) and through the Python CLI: the PNG holds the frame that a DeviceScene
+    under set_depth(N) renders of data/scene.obj, and differs from the depth-3 frame."""
+    import subprocess
+    import torch
+    from PIL import Image
+    from conftest import ROOT
+    bih, cam, _ = product_scene
+    ds = sqt.DeviceScene(bih, 0)
+    try:
+        want = {}
+        for depth in (3, 5, 1):
+            ds.set_depth(depth)
+            want[depth] = ds.render_rows(cam, 4, 48, 40, want_avg=False)[1].cpu().numpy()
+        torch.cuda.synchronize()
+    finally:
+        ds.close()
+    assert want[5].any() and not np.array_equal(want[5], want[3]) and not np.array_equal(want[1], want[3])
+    exe = os.path.join(ROOT, "squigly-trace_amd", "bin", "squigly-trace")
+    out = str(tmp_path / "depth.png")
+    cli = __import__("importlib").import_module("squigly-trace_amd.cli")
+    cwd = os.getcwd()
+    for depth in (5, 1):
+        r = subprocess.run([exe, "-s", "4", "-d", "48,40", "-p", out, "--depth", str(depth)], cwd=ROOT, capture_output=True, text=True, timeout=120)
+        assert r.returncode == 0, r.stderr
+        assert np.array_equal(np.array(Image.open(out).convert("RGB")), want[depth]), ("c++", depth)
+        os.remove(out)
+        os.chdir(ROOT)
+        try:
+            assert cli.main(["-s", "4", "-d", "48,40", "-p", out, f"--depth={depth}"]) == 0
+        finally:
+            os.chdir(cwd)
+        assert np.array_equal(np.array(Image.open(out).convert("RGB")), want[depth]), ("python", depth)
+        os.remove(out)
