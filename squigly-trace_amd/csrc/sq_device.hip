@@ -1591,7 +1591,7 @@ __global__ void sq_debug_kernel(int op, const void* a, const void* b, long long 
 // ----------------------------------------------------------------------------------------------
 // A path of depth D is the rays 0 .. D-1; bounce b makes ray b + 1 from the generator words n_b (x and u) and n_{b+1} (v), so the
 // last bounce, b = D - 2, reads n_{D-1}: with D <= 8 every word comes from the generator's one Threefish block.
-constexpr int kMaxDepth = 8;
+constexpr int kMaxDepth = kDeepestPath;
 // Word i (0 .. 7) of a generator whose block is c: the low, then the high half of each of its four words (tfgen3 keeps 0 .. 2).
 __device__ __forceinline__ uint32_t tf_word(const uint64_t c[4], int i) {
     const uint64_t w = i < 2 ? c[0] : i < 4 ? c[1] : i < 6 ? c[2] : c[3];
@@ -1836,6 +1836,7 @@ struct sq_device_scene {
     SceneView view{};
     void* d_arena = nullptr;      // every array of `view` lives in this one allocation
     int height = 0; bool small_index = false; int n_cu = 256;
+    int shortcut_depth = 0;       // PackedScene's: a launch at a greater depth runs with the s == 0 shortcuts off (launch_frame)
     // workspace (grow-only)
     Work work{}; void* d_work = nullptr; size_t work_bytes = 0; int64_t work_pixels = 0, work_slots = 0;
     // timing of the dominant kernel
@@ -1878,7 +1879,7 @@ extern "C" int sq_scene_upload(const sq_scene* sc, int32_t device, sq_device_sce
     if (sq_pack_scene(*sc, P)) return 1;
     SQ_HIP(hipSetDevice(device));
     sq_device_scene* s = new sq_device_scene;
-    s->device = device; s->height = P.height; s->small_index = P.small_index;
+    s->device = device; s->height = P.height; s->small_index = P.small_index; s->shortcut_depth = P.shortcut_depth;
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) s->n_cu = prop.multiProcessorCount;
     // One arena for every array of the scene: one hipMalloc, one host-packed hipMemcpy and (sq_scene_free) one hipFree
@@ -2362,7 +2363,11 @@ int launch_trace_kernel(sq_device_scene* s, const SceneView& S, const TracePlan&
 template <typename StackT, int SRC>
 int launch_frame(sq_device_scene* s, const typename SrcKernels<StackT, SRC>::FrameT& F, hipStream_t stream, const sq_camera* cams) {
     int stack_cap; size_t px_lds;
-    const SceneView S = begin_plan<StackT>(s, stack_cap, px_lds);
+    SceneView S = begin_plan<StackT>(s, stack_cap, px_lds);
+    // nonneg_materials bounds the radiance below an absorbing surface for the reference's depth.  A deeper path nests more products,
+    // one of which may be inf where the bound still held: 0 * inf is NaN in the reference, so past the packer's shortcut_depth
+    // (sq_host.cpp, material_flags) the generic-depth kernels of this launch take no s == 0 shortcut.
+    if (!F.cast && s->depth > 3 && s->depth > s->shortcut_depth) S.nonneg_materials = 0;
     sq_plan& P = s->plan;
     const long long pixels = (long long)F.n_views * F.local_rows * F.h;   // every view's pixels, view-major
     const long long px_blocks = (pixels + kBlock - 1) / kBlock;

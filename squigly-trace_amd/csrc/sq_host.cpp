@@ -686,6 +686,7 @@ struct Packer {
     // (absorbs()) on: every component >= +0 and <= 3e38, every emission product finite, and the bound max_s * max_e + max_e on a
     // nested radiance (in double; max_e the largest fp32 emission product, max_s the largest surface component) comfortably finite
     // in fp32 -- 0 * inf would be NaN in the reference (src/Lib.hs:135-136; DESIGN.md 3, "The surfColor == 0 shortcut and overflow").
+    // That bound is one product deep, the reference's depth; shortcut_depth says how much deeper the same reasoning still holds.
     void material_flags() {
         static_assert(sizeof(sq_material) == sizeof(DevMat), "a material is copied as it is");
         P.mats.resize((size_t)sc.n_mats);
@@ -701,6 +702,16 @@ struct Packer {
             }
         }
         P.nonneg_materials = nonneg && max_s * max_e + max_e <= 3.0e38;
+        // That is the reference's depth, 3: one product below a path's level 0.  Under depth D a path nests D - 2 of them, and
+        // max_e * (1 + max_s + ... + max_s^(D-2)) bounds them all.  shortcut_depth is the largest D the bound holds for (0: none); a
+        // launch at a greater depth runs with the shortcuts off.  A sum that overflows or is NaN (0 * inf) fails the comparison.
+        P.shortcut_depth = 0;
+        double sum = 1.0, power = 1.0;
+        for (int depth = 3; P.nonneg_materials && depth <= kDeepestPath; ++depth) {
+            power *= max_s; sum += power;
+            if (!(max_e * sum <= 3.0e38)) break;
+            P.shortcut_depth = depth;
+        }
     }
     // Triangles as (v0, e1, e2) and the per-triangle shading record (surface_of).
     void triangles_and_surfaces() {
@@ -847,7 +858,7 @@ extern "C" int sq_packed_scalar(const sq_packed* P, const char* name, int64_t* v
         { "n_branches", P->nb }, { "n_leaves", P->nl }, { "height", P->height }, { "root_ref", P->root_ref }, { "rroot", P->rroot },
         { "packed_leaves", P->packed_leaves }, { "nonneg_materials", P->nonneg_materials }, { "finite_geometry", P->finite_geometry },
         { "n_emitters", P->n_emitters }, { "n_verts", P->n_verts }, { "cull_o2max", lim[0] }, { "cull_d2min", lim[1] }, { "cull_d2max", lim[2] },
-        { "small_index", P->small_index } };
+        { "small_index", P->small_index }, { "shortcut_depth", P->shortcut_depth } };
     for (const auto& s : all) if (!std::strcmp(name, s.name)) { *value = s.value; return 0; }
     return sq_set_error("no packed scalar '%s'", name);
 }

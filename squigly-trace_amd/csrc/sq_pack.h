@@ -7,6 +7,8 @@
 #include "../../include/squigly_hip.h"
 #include "sq_layout.h"
 
+constexpr int kDeepestPath = 8;                     // the largest depth sq_scene_set_depth takes
+
 struct PackedScene {
     // one vector per device array, named after the SceneView member it feeds (sq_scene.h)
     std::vector<sqd::DevBranch> branches;           // breadth-first; left / right are the references the streaming forms read
@@ -26,6 +28,7 @@ struct PackedScene {
     uint32_t root_ref = 0, rroot = 0;
     bool packed_leaves = false, nonneg_materials = false, finite_geometry = false;
     int32_t n_emitters = -1, n_verts = 0;
+    int32_t shortcut_depth = 0;                     // the largest path depth (<= kDeepestPath) whose nested products nonneg_materials' bound covers
     float cull_limits[3] = { -1.0f, 0.25f, 1.5624f };   // SceneView::cull_o2max, cull_d2min, cull_d2max
     bool small_index = false;                       // < 0x8000 branches and triangles: 2-byte stack words
 };

@@ -39,7 +39,10 @@ struct SceneView {
     uint32_t rroot;           // root reference in resident encoding
     int32_t n_verts;
     int32_t height;           // BIH.height; a traversal never holds more than height-1 frames
-    int32_t nonneg_materials; // 1 if every material component is >= +0 (enables the exact s == 0 shortcuts)
+    int32_t nonneg_materials; // 1 if every material component is >= +0 and the one nested product of a depth-3 path cannot overflow
+                              // (enables the exact s == 0 shortcuts).  The uploaded view holds this depth-3 value; launch_frame
+                              // clears it in the copy it hands to a deeper launch's kernels where the packer's shortcut_depth says
+                              // so (sq_device.hip), so whatever shades at a depth above 3 takes its view from launch_frame
     int32_t finite_geometry;  // 1 if every vertex and box coordinate is finite (v_min/v_max slabs need NaN-free planes)
     const int32_t* emitters;  // triangles whose emission `emissive *^ emitColor` is not exactly (+0,+0,+0)
     int32_t n_emitters;       // their number, or -1 when the last-bounce shortcut is disabled (see sq_shade1)

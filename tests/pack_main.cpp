@@ -22,7 +22,7 @@ int main(int argc, char** argv) {
     const char* arrays[] = { "branches", "leaves", "tris", "tri_mat", "surfs", "mats", "verts4", "trix", "rbranch", "emitters",
                              "cull_child", "cull_child16", "branches_m" };
     const char* scalars[] = { "n_branches", "n_leaves", "height", "root_ref", "rroot", "packed_leaves", "nonneg_materials", "finite_geometry",
-                              "n_emitters", "n_verts", "cull_o2max", "cull_d2min", "cull_d2max", "small_index" };
+                              "n_emitters", "n_verts", "cull_o2max", "cull_d2min", "cull_d2max", "small_index", "shortcut_depth" };
     size_t total = 0; uint64_t sum = 0; int n_arrays = 0;
     for (const char* name : arrays) {
         const void* data = nullptr; size_t bytes = 0;

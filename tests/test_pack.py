@@ -266,6 +266,46 @@ def test_material_values_that_clear_nonneg_materials(sqt):
     assert flag(surf=(0, 0, 0), emissive=1.0, emit=(2.9e38, 0, 0)) == 1      # the same bound with max_s = 0
 
 
+def shortcut_depth(sqt, holder):
+    """The packer's shortcut_depth (not among SCALARS: the recorded digests are older than it)."""
+    L, h, v = sqt.lib(), C.c_void_p(), C.c_int64()
+    sqt._native.check(L.sq_scene_pack(C.byref(holder.scene), C.byref(h)))
+    try:
+        assert L.sq_packed_scalar(h, b"shortcut_depth", C.byref(v)) == 0
+    finally:
+        L.sq_packed_free(h)
+    return v.value
+
+
+def test_shortcut_depth_is_the_deepest_path_whose_nested_products_stay_finite(sqt):
+    """nonneg_materials bounds one product, the reference's depth 3.  A path of depth D nests D - 2, and the s == 0 shortcuts of the
+    generic-depth kernels stay exact while max_e * (1 + max_s + ... + max_s^(D-2)) <= 3e38: shortcut_depth is the largest such D
+    up to 8, at least 3 where nonneg_materials holds, 0 where it does not.  The expected value is that sum in exact rationals."""
+    from fractions import Fraction
+    depth = lambda **m: shortcut_depth(sqt, one_triangle(sqt, m))
+    assert depth() == 8                                                       # no emission: nothing to overflow
+    assert depth(surf=(0.5, -0.0, 0.5)) == 0 and depth(emissive=np.nan) == 0  # nonneg_materials off
+    assert depth(surf=(1, 0, 0), emissive=1.0, emit=(1.51e38, 0, 0)) == 0     # ... by its own bound
+    assert depth(surf=(1, 0, 0), emissive=1.0, emit=(1.49e38, 0, 0)) == 3     # 2 e <= 3e38 < 3 e
+    assert depth(surf=(1, 0, 0), emissive=1.0, emit=(4.4e37, 0, 0)) == 7      # 6 e <= 3e38 < 7 e
+    assert depth(surf=(1, 0, 0), emissive=1.0, emit=(3.7e37, 0, 0)) == 8      # 7 e <= 3e38
+    assert depth(surf=(1e10, 0, 0), emissive=1.0, emit=(1e18, 0, 0)) == 4     # 1e18 * 1e20 fits, 1e18 * 1e30 does not
+    assert depth(surf=(3e38, 3e38, 3e38), emissive=1e-3, emit=(1, 0, 0)) == 3 # every power stays finite in double
+    assert depth(surf=(3e38, 0, 0), emissive=0.0, emit=(3e38, 0, 0)) == 8
+    for s in (0.0, 0.5, 1.0, 2.0, 1e5, 1e10, 1e19, 3e38):
+        for e in (0.0, 1e-30, 1.0, 1e10, 1e20, 1e30, 1e37, 2.9e38):
+            fs, fe = Fraction(float(np.float32(s))), Fraction(float(np.float32(e)))
+            holds = [D for D in range(3, 9) if fe * sum(fs ** i for i in range(D - 1)) <= Fraction(3.0e38)]
+            want = 0
+            for D in range(3, 9):                                             # the bound grows with D: the first failure ends it
+                if D not in holds:
+                    break
+                want = D
+            holder = one_triangle(sqt, dict(surf=(s, 0, 0), emissive=1.0, emit=(e, 0, 0)))
+            assert shortcut_depth(sqt, holder) == want, (s, e)
+            assert pack(sqt, holder)[1]["nonneg_materials"] == (want >= 3), (s, e)
+
+
 def test_geometry_values_that_clear_finite_geometry(sqt):
     assert pack(sqt, one_triangle(sqt))[1]["finite_geometry"] == 1
     assert pack(sqt, one_triangle(sqt, v=((0, 0, 0), (1, np.nan, 0), (0, 1, 0))))[1]["finite_geometry"] == 0
