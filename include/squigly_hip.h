@@ -330,7 +330,8 @@ int  sq_kernel_timing(sq_device_scene* s, double* avg_ms, int64_t* launches, con
 void sq_kernel_timing_reset(sq_device_scene* s);
 /* Cumulative statistics of the trace kernel, over the render and query calls since the last reset (synchronises the device), n <= 32:
  * out[0] = rays traced; out[1..23] = lane-occupancy counters, rare-path counts and per-section wave cycles of the
- * profile build, filled only with option "profile" = 1 (tools/gpu_pool.py prints them). */
+ * profile build, filled only with option "profile" = 1 (tools/gpu_pool.py prints them); out[28] = first-bounce rays that
+ * level-1 culling (option "level1_cull") did not queue. */
 int  sq_get_stats(sq_device_scene* s, uint64_t* out, int32_t n, int32_t reset);
 /* Tunables; every setting produces identical bits.  Keys:
  *   "variant"            1 = one-lane-per-pixel kernel, 2 = wavefront pipeline (default)
@@ -378,6 +379,11 @@ int  sq_get_stats(sq_device_scene* s, uint64_t* out, int32_t n, int32_t reset);
  *   "cull"               1 (default): a ray inside the limits of sq_cull_boxes (squigly_host.h) that misses a leaf's culling box
  *                        skips the leaf's triangle tests -- the reference's mollerTrumbore would reject them all, so no bit
  *                        changes; 0: every leaf the reference visits is tested
+ *   "level1_cull"        1 (default): a path-traced frame or query at depth 3 does not queue the scattered first-bounce ray of a
+ *                        sample that provably ends with the radiance of a first-bounce miss (no emitter on the ray, no mirroring
+ *                        surface on it, no emitter within reach of the second bounce: csrc/sq_host.cpp, level1_tables) -- no bit
+ *                        changes; 0: every such ray is traced.  sq_get_stats slot 28 counts the rays dropped, sq_last_plan says
+ *                        whether the frame used it
  *   "primary_tiles"      1 (default): the primary rays of a shard are enumerated in tiles (8 x 8 pixels on a whole image, 2 x 32 with
  *                        row blocks of 2) so that the 64 rays of a wave stay together in both image directions; 0: 64 pixels of a row
  *   "rng_table_mb"       budget in MiB of the scene's table of generator words (default 24576 = 24 GiB of the 288 GB, 0 = no table).  A
@@ -427,6 +433,7 @@ typedef struct {
     int32_t primary_form;      /* SQ_PRIMARY_*: how the primary rays of a wavefront frame were traced (NONE with the per-pixel kernel) */
     int32_t packed_leaves;     /* streaming forms: leaf references carry count << 24 | first (every leaf <= 31 triangles) */
     int32_t n_emitters;        /* length of the last-bounce emitter list, -1 = shortcut off (> 64 emitters or non-finite materials) */
+    int32_t level1_cull;       /* 1 = the frame's first-bounce rays went through level-1 culling (option "level1_cull" and the scene's preconditions) */
 } sq_plan;
 int  sq_last_plan(sq_device_scene* s, sq_plan* out);
 

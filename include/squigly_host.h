@@ -69,8 +69,10 @@ uint32_t sq_half_outward(float x, int32_t up);
  * branches, leaves, tris, tri_mat, surfs, mats, verts4, trix, rbranch, emitters, cull_child, cull_child16, branches_m; `data`
  * points into the packed scene and lives as long as it.  Scalars: n_branches, n_leaves, height, root_ref, rroot, packed_leaves,
  * nonneg_materials, finite_geometry, n_emitters, n_verts, small_index, shortcut_depth (the largest path depth at which
- * nonneg_materials still holds; 0: none), and cull_o2max / cull_d2min / cull_d2max as the bits of the float.  An unknown name
- * returns non-zero. */
+ * nonneg_materials still holds; 0: none), and cull_o2max / cull_d2min / cull_d2max as the bits of the float.  The first-bounce
+ * reduction (option "level1_cull"): array "level1" is the Level1Cull record sq_gen_bounce1 takes (csrc/sq_layout.h), scalars
+ * level1_on (its preconditions hold) and level1_zero (s.surf * 0 + s.emit is bitwise +0 outside the emitter list).  An unknown
+ * name returns non-zero. */
 typedef struct sq_packed sq_packed;
 int   sq_scene_pack(const sq_scene* scene, sq_packed** out);
 int   sq_packed_array(const sq_packed* p, const char* name, const void** data, size_t* bytes);

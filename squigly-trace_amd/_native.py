@@ -50,7 +50,7 @@ class Plan(C.Structure):
     """sq_plan (include/squigly_hip.h): the launch plan of a scene's last frame."""
     _fields_ = [(n, C.c_int32) for n in ("launched", "variant", "stack_word_bytes", "height", "stack_cap", "trace_form",
                                           "blocks_per_cu", "n_lds", "trace_lds_bytes", "pixel_lds_bytes", "primary_form",
-                                          "packed_leaves", "n_emitters")]
+                                          "packed_leaves", "n_emitters", "level1_cull")]
 
 
 TRACE_FORMS = {0: "per_pixel", 1: "resident", 2: "streaming_six_wave", 3: "streaming_plain"}

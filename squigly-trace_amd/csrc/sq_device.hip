@@ -348,6 +348,7 @@ constexpr uint8_t kDone = 0, kRay1 = 1, kMirror = 2, kRay2 = 3;
 // CU, so a per-sample wave that starts (stats[26]) or ends (stats[27]) while at least `full` of them are live shares its CU
 // with one.  stats[25] counts the per-sample waves that looked.
 constexpr int kDiagGauge = 24, kDiagWaves = 25, kDiagStartBeside = 26, kDiagEndBeside = 27;
+constexpr int kStatLevel1Culled = 28;       // sq_get_stats 28: first-bounce rays sq_gen_bounce1 did not queue (level-1 culling)
 __device__ __forceinline__ void diag_aux_wave(const Work& W, int diag, bool at_start) {
     if (!diag || (threadIdx.x & 63) != 0) return;
     const unsigned long long live = atomicAdd(&W.stats[kDiagGauge], 0ull);
@@ -517,6 +518,64 @@ __global__ void __launch_bounds__(kBlock) sq_rng_fill(uint32_t* words, long long
     }
 }
 
+// Level-1 culling (sq_host.cpp, level1_tables, has the lemma): does the half-plane { p0 + t d1 + s nd : t >= 0, s real } provably
+// miss the box [lo - m, hi + m]?  Binary64 on the exact fp32 values; either separation must hold by more than 1e-9 of the scale.
+__device__ __forceinline__ bool halfplane_misses_box(f3 p0, f3 d1, f3 nd, const double* lo, const double* hi, double m) {
+    const double px[3] = { p0.x, p0.y, p0.z }, dx[3] = { d1.x, d1.y, d1.z }, nx[3] = { nd.x, nd.y, nd.z };
+    double g[3], h[3], scale = 0.0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { g[k] = 0.5 * (lo[k] + hi[k]) - px[k]; h[k] = 0.5 * (hi[k] - lo[k]) + m; scale += __builtin_fabs(g[k]) + h[k]; }
+    const double tol = 1e-9 * scale;
+    const double N[3] = { dx[1] * nx[2] - dx[2] * nx[1], dx[2] * nx[0] - dx[0] * nx[2], dx[0] * nx[1] - dx[1] * nx[0] };
+    const double dist = __builtin_fabs(N[0] * g[0] + N[1] * g[1] + N[2] * g[2]);
+    const double rad = __builtin_fabs(N[0]) * h[0] + __builtin_fabs(N[1]) * h[1] + __builtin_fabs(N[2]) * h[2];
+    if (dist > rad + tol) return true;                                  // the whole box on one side of the plane
+    const double f = (dx[0] * nx[0] + dx[1] * nx[1] + dx[2] * nx[2]) / (nx[0] * nx[0] + nx[1] * nx[1] + nx[2] * nx[2]);
+    const double w[3] = { dx[0] - f * nx[0], dx[1] - f * nx[1], dx[2] - f * nx[2] };
+    const double side = w[0] * g[0] + w[1] * g[1] + w[2] * g[2] + __builtin_fabs(w[0]) * h[0] + __builtin_fabs(w[1]) * h[1] + __builtin_fabs(w[2]) * h[2];
+    return side < -tol;                                                 // the whole box behind ray 1, seen across nd
+}
+// May the scattered ray 1 = (p0, d1) of a sample whose generator goes on with n1, n2 be dropped, the sample finished as a
+// first-bounce miss?  Conditions (1)-(3) of the lemma; p0_ok: |p0|^2 is inside the lemma's limit (per pixel).
+__device__ __forceinline__ bool level1_culled(const SceneView& S, const Level1Cull& C, bool p0_ok, f3 p0, f3 d1, uint32_t n1, uint32_t n2) {
+    const float eps = 0.0001f, inf = __builtin_inff();
+    // ray 1 inside the limits of sq_cull_boxes (as trav_begin decides Trav::cull)
+    const f3 df = sq::mk(1.0f / d1.x, 1.0f / d1.y, 1.0f / d1.z);
+    const f3 nodf = sq::mk(-p0.x * df.x, -p0.y * df.y, -p0.z * df.z);
+    const float dd = sq::dot(d1, d1);
+    if (!(p0_ok && finite3(d1) && finite3(df) && finite3(nodf) && dd >= C.d2min && dd <= C.d2max)) return false;
+    // (2) the box of everything that would mirror: the class of the smallest value >= unit_float(n1), if any
+    const float un1 = sq::unit_float(n1);
+    bool has = false; float b[6] = { 0, 0, 0, 0, 0, 0 };
+#pragma unroll
+    for (int c = kLevel1Classes - 1; c >= 0; --c) {
+        if (c < C.n_classes && C.class_val[c] >= un1) {
+            has = true;
+#pragma unroll
+            for (int k = 0; k < 6; ++k) b[k] = C.class_box[c][k];
+        }
+    }
+    if (has && cull_slab(b, df, nodf)) return false;
+    // the direction of ray 2 up to its sign
+    const f3 nd = random_vector(n1, n2);
+    const float nn = sq::dot(nd, nd);
+    if (!(nn >= C.d2min && nn <= C.d2max)) return false;
+    // (1) no emitter accepts ray 1; and the smallest determinant with which one could accept ray 2
+    float amin = inf;
+    for (int j = 0; j < S.n_emitters; ++j) {
+        const float* tp = S.tris + 9 * (size_t)S.emitters[j];
+        const f3 v0 = sq::mk(tp[0], tp[1], tp[2]), e1 = sq::mk(tp[3], tp[4], tp[5]), e2 = sq::mk(tp[6], tp[7], tp[8]);
+        float t_unused;
+        if (moller_trumbore(p0, d1, v0, e1, e2, t_unused)) return false;
+        const float a = sq::dot(e1, sq::cross(nd, e2));                 // moller_trumbore's `a` for (any origin, nd); -nd gives -a
+        if (!(a > -eps && a < eps)) amin = sq::hmin(amin, __builtin_fabsf(a));
+    }
+    if (amin == inf) return true;                                       // every emitter rejects +-nd by its determinant alone
+    if (!(amin < inf)) return false;
+    // (3)
+    return halfplane_misses_box(p0, d1, nd, C.em_lo, C.em_hi, C.em_rho * ((double)eps / (double)amin) + C.em_add);
+}
+
 // Depth-0 bounce of every sample of the batch: RNG, bounceRay, ray 1 into slot sid (src/Lib.hs:133-134).
 // One thread per active pixel (blockIdx.y splits the samples of a pixel when a frame has few pixels): everything that is
 // the same for every sample of a pixel -- the pixel's coordinates, primary direction, hit point, surface, seed base -- is
@@ -526,8 +585,9 @@ __global__ void __launch_bounds__(kBlock) sq_rng_fill(uint32_t* words, long long
 // Neighbouring lanes are neighbouring pixels, samples * 12 bytes apart in the table, so a lane takes its samples in runs of
 // kRngRun (a blockIdx.y gets a contiguous range of runs) and requests the next run before it works on the current one.
 template <int SRC, typename FrameT>
-__device__ __forceinline__ void gen_bounce1_body(const SceneView& S, const FrameT& F, const Work& W, int k_base, int k_count, const RngView R) {
+__device__ __forceinline__ void gen_bounce1_body(const SceneView& S, const FrameT& F, const Work& W, int k_base, int k_count, const RngView R, const Level1Cull& C) {
     const int A = *W.n_active;
+    unsigned int n_culled = 0;
     diag_aux_wave(W, F.diag, true);
     const int n_runs = (k_count + kRngRun - 1) / kRngRun, runs_per_y = (n_runs + (int)gridDim.y - 1) / (int)gridDim.y;
     const int g_begin = min(n_runs, (int)blockIdx.y * runs_per_y), g_end = min(n_runs, g_begin + runs_per_y);
@@ -540,6 +600,7 @@ __device__ __forceinline__ void gen_bounce1_body(const SceneView& S, const Frame
         }
         const long long first = rix + k_base;                           // the seed of kl = 0: mkTFGen (rix + k), src/Lib.hs:86
         const bool use = R.words != nullptr && rix >= 0 && rix <= R.cover - (long long)F.samples;
+        const bool p0_ok = C.on && finite3(P.p0) && sq::dot(P.p0, P.p0) <= C.o2max;   // level-1 culling: the pixel's share of ray 1's limits
         RngRun next{};
         if (use && g_begin < g_end) next = rng_load_run(R.words, first + (long long)g_begin * kRngRun);
         for (int g = g_begin; g < g_end; ++g) {
@@ -566,17 +627,27 @@ __device__ __forceinline__ void gen_bounce1_body(const SceneView& S, const Frame
                     continue;
                 }
                 const f3 d1 = scatter_dir(P.d0, P.s0, n0, n1);
+                // Level-1 culling: nothing ray 1 can hit changes the sample's radiance, which is that of a first-bounce miss
+                if (C.on && level1_culled(S, C, p0_ok, P.p0, d1, n1, n2)) { finish_level1(W, sid, -1); ++n_culled; continue; }
                 W.state[sid] = kRay1;
                 W.org[sid] = make_float4(P.p0.x, P.p0.y, P.p0.z, __uint_as_float(n1));
                 W.dir[sid] = make_float4(d1.x, d1.y, d1.z, __uint_as_float(n2));
             }
         }
     }
+    if (C.on) {                                                         // rays culled, one atomic per wave (the loop above has ended for all its lanes)
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) n_culled += __shfl_xor(n_culled, o);
+        if ((threadIdx.x & 63) == 0 && n_culled) atomicAdd(&W.stats[kStatLevel1Culled], (unsigned long long)n_culled);
+    }
     diag_aux_wave(W, F.diag, false);
 }
+// Four waves per SIMD (118 VGPRs, no scratch): with the level-1 culling test inlined, six (80 VGPRs) spill 38 registers and five
+// (96) spill 22; the headline frame measured 43.2 / 42.1 / 41.7 ms at six / five / four
+constexpr int kGen1Waves = 4;
 template <bool MV>
-__global__ void __launch_bounds__(kBlock, 6) sq_gen_bounce1(const SceneView S, const Frame F, const Work W, int k_base, int k_count, const RngView R) { gen_bounce1_body<MV>(S, F, W, k_base, k_count, R); }
-__global__ void __launch_bounds__(kBlock, 6) sq_gen_bounce1_rays(const SceneView S, const RayFrame F, const Work W, int k_base, int k_count, const RngView R) { gen_bounce1_body<kSrcRays>(S, F, W, k_base, k_count, R); }
+__global__ void __launch_bounds__(kBlock, kGen1Waves) sq_gen_bounce1(const SceneView S, const Frame F, const Work W, int k_base, int k_count, const RngView R, const Level1Cull C) { gen_bounce1_body<MV>(S, F, W, k_base, k_count, R, C); }
+__global__ void __launch_bounds__(kBlock, kGen1Waves) sq_gen_bounce1_rays(const SceneView S, const RayFrame F, const Work W, int k_base, int k_count, const RngView R, const Level1Cull C) { gen_bounce1_body<kSrcRays>(S, F, W, k_base, k_count, R, C); }
 
 // The depth-0 mirror ray of every active pixel, once per frame (slot a = active pixel a).
 // `base`: first of the *n_active slots the mirror rays use (0 when they have a launch of their own, the spare region
@@ -1836,6 +1907,7 @@ struct sq_device_scene {
     SceneView view{};
     void* d_arena = nullptr;      // every array of `view` lives in this one allocation
     int height = 0; bool small_index = false; int n_cu = 256;
+    Level1Cull level1{};          // PackedScene's: the first-bounce reduction's tables (sq_gen_bounce1)
     int shortcut_depth = 0;       // PackedScene's: a launch at a greater depth runs with the s == 0 shortcuts off (launch_frame)
     // workspace (grow-only)
     Work work{}; void* d_work = nullptr; size_t work_bytes = 0; int64_t work_pixels = 0, work_slots = 0;
@@ -1867,7 +1939,7 @@ struct sq_device_scene {
     // pipeline's (Deep: trail, oxy), allocated by the first deep call that needs it (grow-only; a scene that stays at depth 3 has none)
     int32_t depth = 3; int64_t opt_deep = 0;
     void* d_deep = nullptr; size_t deep_bytes = 0;
-    int64_t opt_pool = 1, opt_refill_min = 12, opt_flush_min = 40, opt_guided = 1, opt_primary_resident = 1, opt_pixel_major = -1, opt_cull = 1, opt_descend_extra = 2, opt_descend_lanes = 16, opt_primary_pooled = 0, opt_coresidency = 0, opt_trace_prio = 0, opt_aux_low_priority = 1, opt_aux_polite = 0, opt_primary_tiles = 1;
+    int64_t opt_pool = 1, opt_refill_min = 12, opt_flush_min = 40, opt_guided = 1, opt_primary_resident = 1, opt_pixel_major = -1, opt_cull = 1, opt_descend_extra = 2, opt_descend_lanes = 16, opt_primary_pooled = 0, opt_coresidency = 0, opt_trace_prio = 0, opt_aux_low_priority = 1, opt_aux_polite = 0, opt_primary_tiles = 1, opt_level1_cull = 1;
 };
 
 extern "C" int sq_scene_upload(const sq_scene* sc, int32_t device, sq_device_scene** out) {
@@ -1879,7 +1951,7 @@ extern "C" int sq_scene_upload(const sq_scene* sc, int32_t device, sq_device_sce
     if (sq_pack_scene(*sc, P)) return 1;
     SQ_HIP(hipSetDevice(device));
     sq_device_scene* s = new sq_device_scene;
-    s->device = device; s->height = P.height; s->small_index = P.small_index; s->shortcut_depth = P.shortcut_depth;
+    s->device = device; s->height = P.height; s->small_index = P.small_index; s->shortcut_depth = P.shortcut_depth; s->level1 = P.level1;
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) s->n_cu = prop.multiProcessorCount;
     // One arena for every array of the scene: one hipMalloc, one host-packed hipMemcpy and (sq_scene_free) one hipFree
@@ -2544,9 +2616,13 @@ int launch_frame(sq_device_scene* s, const typename SrcKernels<StackT, SRC>::Fra
     // The steps of batch i, each on the stream `on` and over the batch's track Wt[i & 1]; the schedules below say only which stream a
     // step goes on and which events order it.
     auto launched = []() -> int { SQ_HIP(hipGetLastError()); return 0; };
+    // Level-1 culling (sq_host.cpp, level1_tables): the three-level pipeline only, and only with the shortcuts its lemma builds on
+    Level1Cull L1 = s->level1;
+    L1.on = L1.on && s->opt_level1_cull && S.n_emitters >= 0 && S.nonneg_materials && S.finite_geometry;
+    P.level1_cull = L1.on;
     auto gen = [&](int i, hipStream_t on) -> int {
         SQ_HIP(hipMemsetAsync(Wt[i & 1].head[0], 0, 32 * sizeof(int32_t), on));     // both dequeue cursors
-        hipLaunchKernelGGL(K.gen_bounce1, pp_grid(kc_of(i)), dim3(kBlock), 0, on, S, F, Wt[i & 1], k0_of(i), kc_of(i), R);
+        hipLaunchKernelGGL(K.gen_bounce1, pp_grid(kc_of(i)), dim3(kBlock), 0, on, S, F, Wt[i & 1], k0_of(i), kc_of(i), R, L1);
         return launched();
     };
     auto trace = [&](int i, int level, hipStream_t on, bool with_mirror) -> int { return launch_trace_kernel(s, S, TP, Wt[i & 1], pixels, kc_of(i), level, on, with_mirror); };
@@ -3119,6 +3195,7 @@ extern "C" int sq_set_option(sq_device_scene* s, const char* key, int64_t value)
     if (!std::strcmp(key, "guided")) { if (value < 0 || value > 3) return sq_set_error("guided must be in 0..3"); s->opt_guided = value; return 0; }
     if (!std::strcmp(key, "primary_resident")) { s->opt_primary_resident = value ? 1 : 0; return 0; }
     if (!std::strcmp(key, "cull")) { s->opt_cull = value ? 1 : 0; return 0; }
+    if (!std::strcmp(key, "level1_cull")) { s->opt_level1_cull = value ? 1 : 0; return 0; }
     if (!std::strcmp(key, "incremental")) return 0;   // accepted, no effect: the incremental slab test was removed
     if (!std::strcmp(key, "primary_tiles")) { s->opt_primary_tiles = value ? 1 : 0; return 0; }
     if (!std::strcmp(key, "primary_pooled")) { s->opt_primary_pooled = value != 0; return 0; }

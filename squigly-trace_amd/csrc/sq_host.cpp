@@ -507,11 +507,28 @@ extern "C" void sq_bih_free(sq_bih* b) { delete b; }
 namespace {
 inline float f_down(double x) { float f = (float)x; if ((double)f > x) f = std::nextafterf(f, -INFINITY); return f; }
 inline float f_up(double x) { float f = (float)x; if ((double)f < x) f = std::nextafterf(f, INFINITY); return f; }
+constexpr double kLemmaU = 5.9604644775390625e-8, kLemmaD = 1.25, kLemmaPmax = 29.0;
+const double kLemmaEps = (double)0.0001f;
+// The lengths the derivation above names, of one triangle: E1 = |e1|, E2 = |e2| (the kernels' rounded edges), V0 = |v0|, P = E1 E2 D.
+struct TriNorms { double E1, E2, V0, P; };
+inline TriNorms tri_norms(const sq_tri& t) {
+    double E1 = 0, E2 = 0, V0 = 0;
+    for (int c = 0; c < 3; ++c) {
+        const float e1 = t.v1[c] - t.v0[c], e2 = t.v2[c] - t.v0[c];        // the kernels' edges (src/Geometry.hs:130-131)
+        E1 += (double)e1 * e1; E2 += (double)e2 * e2; V0 += (double)t.v0[c] * t.v0[c];
+    }
+    E1 = std::sqrt(E1); E2 = std::sqrt(E2); V0 = std::sqrt(V0);
+    return TriNorms{ E1, E2, V0, E1 * E2 * kLemmaD };
+}
+// rho (with the margin's 32 and 6) for rays whose origin lies within `reach` of the coordinate origin, so that S <= reach + V0
+inline double lemma_rho(const TriNorms& q, double reach) {
+    return 32.0 * (kLemmaU / kLemmaEps) * q.P * (reach + q.V0 + q.E1 + q.E2) + 6.0 * kLemmaU * (q.E1 + q.E2);
+}
 }
 extern "C" int sq_cull_boxes(const sq_scene* sc, float* boxes, float ray_limits[3]) {
     if (!sc || !boxes || !ray_limits) return sq_set_error("null argument");
     const int32_t n = sc->n_nodes;
-    const double u = 5.9604644775390625e-8, eps = (double)0.0001f, kD = 1.25, kPmax = 29.0;
+    const double u = kLemmaU, kPmax = kLemmaPmax;
     const float inf = INFINITY;
     auto disable = [&]() { for (int32_t i = 0; i < n; ++i) { float* b = boxes + 6 * (size_t)i; b[0] = b[1] = b[2] = -inf; b[3] = b[4] = b[5] = inf; }
                            ray_limits[0] = -1.0f; ray_limits[1] = 0.25f; ray_limits[2] = 1.5624f; return 0; };
@@ -539,16 +556,11 @@ extern "C" int sq_cull_boxes(const sq_scene* sc, float* boxes, float ray_limits[
         double lo[3] = { 1e300, 1e300, 1e300 }, hi[3] = { -1e300, -1e300, -1e300 }, m = 0.0; bool ok = cnt > 0;
         for (int32_t k = first; k < first + cnt && ok; ++k) {
             const sq_tri& t = sc->tris[k];
-            double E1 = 0, E2 = 0, V0 = 0;
-            for (int c = 0; c < 3; ++c) {
-                const float e1 = t.v1[c] - t.v0[c], e2 = t.v2[c] - t.v0[c];        // the kernels' edges (src/Geometry.hs:130-131)
-                E1 += (double)e1 * e1; E2 += (double)e2 * e2; V0 += (double)t.v0[c] * t.v0[c];
+            for (int c = 0; c < 3; ++c)
                 for (const float* v : { t.v0, t.v1, t.v2 }) { lo[c] = std::min(lo[c], (double)v[c]); hi[c] = std::max(hi[c], (double)v[c]); }
-            }
-            E1 = std::sqrt(E1); E2 = std::sqrt(E2); V0 = std::sqrt(V0);
-            const double P = E1 * E2 * kD;
-            if (!(P <= kPmax)) { ok = false; break; }
-            m = std::max(m, 32.0 * (u / eps) * P * (omax + V0 + E1 + E2) + 6.0 * u * (E1 + E2));
+            const TriNorms q = tri_norms(t);
+            if (!(q.P <= kPmax)) { ok = false; break; }
+            m = std::max(m, lemma_rho(q, omax));
         }
         if (!ok) { b[0] = b[1] = b[2] = -inf; b[3] = b[4] = b[5] = inf; continue; }
         m += 8.0 * u * (vmax_inf + m + omax) + 1e-20;
@@ -809,6 +821,117 @@ struct Packer {
         for (int32_t i = 0; i < sc.n_tris; ++i) if (std::memcmp(P.surfs[(size_t)i].emit, zero, sizeof zero) != 0) P.emitters.push_back(i);
         P.n_emitters = (finite_materials && P.emitters.size() <= 64) ? (int32_t)P.emitters.size() : -1;
     }
+    // ---- Level-1 culling: the fourth exact reduction of the ray count (no counterpart in the reference) ----
+    // A depth-0 sample that scatters shoots ray 1 = (p0, d1).  sq_gen_bounce1 holds the generator's next words n1, n2, which decide
+    // everything random about the rest of the path: the surface ray 1 hits scatters iff reflective < unit_float(n1), and then ray 2
+    // leaves the computed hit point p1 = fl(p0 + fl(t^ d1)) along +-nd, nd = randomVector(n1, n2), the sign alone depending on the
+    // unknown normal.  The sample is finished at once, as a first-bounce miss, when
+    //   (1) mollerTrumbore(p0, d1, e) rejects every emitter e                      (the very function the traversal calls),
+    //   (2) ray 1 is inside the limits of sq_cull_boxes and fails the slab test of the box of its mirror class, and
+    //   (3) the half-plane H = { p0 + t d1 + s nd : t >= 0, s real } misses the emitters' box grown by the margin below.
+    // LEMMA.  Under the preconditions (nonneg_materials, finite materials and geometry, at most 64 emitters, level1_zero, every
+    // non-emissive triangle and every emitter with P <= 29, R1 <= 2^20) such a sample's radiance has the bits of level0_radiance(s0).
+    // Proof.  By (1) whatever the traversal returns for ray 1 is no emitter.  A miss gives level0_radiance(s0) by
+    //   definition.  Otherwise let T be the hit triangle, s1 its surface: s1.emit is (+0, +0, +0).  If ray 2 is not traced, or hits
+    //   no emitter, L1 = s1.surf * 0 + s1.emit, bitwise (+0, +0, +0) by level1_zero, and s0.surf * L1 + s0.emit is level0_radiance(s0).
+    //   So it is enough that no emitter accepts ray 2.
+    //   (2): class c holds every triangle with reflective >= v, v the smallest of the scene's values that is >= unit_float(n1)
+    //   (merged classes hold more), i.e. every triangle that would mirror.  Its box is the union of their culling boxes, so by the
+    //   culling lemma above (and its remark on unions) mollerTrumbore rejects them all for ray 1: T scatters, ray 2 = (p1, +-nd).
+    //   Where p1 can be: the lemma's exact solution X = p0 + t d1 of the accepted test lies within rho_T of T, so |X| <= vmax +
+    //   rho_T and |t| |d1| <= omax + vmax + rho_T =: reach.  The computed t^ = fl(fl(1/a^) Nt^) obeys
+    //   |t^ - t| <= |Nt^ - Nt|/|a^| + |t| |a - a^|/|a^| + 2.01u |t^| <= 8u S E1 E2/eps + r_T |t| + 2.01u |t^|,  r_T = 7u P_T/eps <= 1/8,
+    //   so Y = p0 + t^ d1, a point of ray 1 with t^ > 0, has |Y| <= vmax + g1, g1 = max_T rho_T + 1.01 (r_T reach + rho_T), and
+    //   |p1 - Y| <= u (|t^ d1| + |p1|) <= delta1 = 4u (2 (vmax + g1) + omax); |p1| <= R1 = vmax + g1 + delta1.
+    //   (3): let e accept (p1, +-nd) with computed determinant a^ (its magnitude is the same for both signs, and it depends on nd
+    //   and e alone, so the kernel evaluates it; |a^| < eps rejects outright).  The derivation above uses of `eps` only that it
+    //   bounds |a^| from below, so it holds with alpha = |a^| >= eps in its place: some point p1 + s (+-nd), s >= 0, lies within
+    //   (eps/alpha) rho'_e + 6u (E1 + E2) of e, rho'_e = 32 (u/eps) P_e (R1 + V0 + E1 + E2) (S <= R1 + V0; |nd|^2 is checked against
+    //   the lemma's limits by the kernel).  Then Y + s (+-nd), a point of H, lies within that plus delta1 of e, inside the emitters'
+    //   vertex box grown by em_rho (eps/amin) + em_add, amin the smallest accepted |a^|: H meets the grown box.  Contrapositive: (3)
+    //   means every emitter rejects ray 2.                                                                                       QED
+    // The kernel tests (3) in binary64 on the exact fp32 values: H lies in the plane through p0 with normal N = d1 x nd and on the
+    // side (x - p0).w >= 0 of it, w = d1 - (d1.nd / nd.nd) nd.  The computed N, w are within 1e-15 |d1| (|nd|) of the exact ones and
+    // every x of the box has |x - p0| <= scale = |g|_1 + |h|_1 (g = centre - p0, h = half extents), so "the box lies strictly on one
+    // side of the plane" or "strictly on the negative side of w", each by more than 1e-9 scale, proves H misses the box.
+    // tests/test_level1_cull.py restates all of this in numpy and searches for counter-examples against the oracle's mollerTrumbore.
+    void level1_tables() {
+        Level1Cull& L = P.level1; L = Level1Cull{};
+        std::vector<char> emits((size_t)sc.n_tris, 0);
+        for (int32_t e : P.emitters) emits[(size_t)e] = 1;
+        P.level1_zero = true;
+        for (int32_t i = 0; i < sc.n_tris; ++i) {
+            if (emits[(size_t)i]) continue;
+            const DevSurf& d = P.surfs[(size_t)i];
+            float l1[3]; static const float zero[3] = { 0.0f, 0.0f, 0.0f };
+            for (int k = 0; k < 3; ++k) l1[k] = d.surf[k] * 0.0f + d.emit[k];     // level1_radiance's L1, the same fp32 operations
+            if (std::memcmp(l1, zero, sizeof zero) != 0) P.level1_zero = false;
+        }
+        if (P.n_emitters < 0 || !P.nonneg_materials || !P.finite_geometry || !finite_materials || !P.level1_zero || !(P.cull_limits[0] >= 0.0f)) return;
+        const double u = kLemmaU, eps = kLemmaEps;
+        double vmax_inf = 0.0, vmax2 = 0.0;
+        for (int32_t i = 0; i < sc.n_tris; ++i)
+            for (const float* v : { sc.tris[i].v0, sc.tris[i].v1, sc.tris[i].v2 }) {
+                double q = 0.0;
+                for (int c = 0; c < 3; ++c) { vmax_inf = std::max(vmax_inf, std::fabs((double)v[c])); q += (double)v[c] * v[c]; }
+                vmax2 = std::max(vmax2, q);
+            }
+        const double vmax = std::sqrt(vmax2), omax = 2.0 * vmax * (1.0 + 1e-12);          // as sq_cull_boxes
+        // where p1 can be
+        double g1 = 0.0;
+        for (int32_t i = 0; i < sc.n_tris; ++i) {
+            if (emits[(size_t)i]) continue;
+            const TriNorms q = tri_norms(sc.tris[i]);
+            if (!(q.P <= kLemmaPmax)) return;
+            const double rho = lemma_rho(q, omax), r = 7.0 * u * q.P / eps;
+            g1 = std::max(g1, rho + 1.01 * (r * (omax + vmax + rho) + rho));
+        }
+        const double delta1 = 4.0 * u * (2.0 * (vmax + g1) + omax) * (1.0 + 1e-6), R1 = vmax + g1 + delta1;
+        if (!(R1 <= 1048576.0)) return;
+        // the emitters' box and its margin
+        double six = 0.0;
+        for (int c = 0; c < 3; ++c) { L.em_lo[c] = P.emitters.empty() ? 0.0 : 1e300; L.em_hi[c] = P.emitters.empty() ? 0.0 : -1e300; }
+        for (int32_t e : P.emitters) {
+            const sq_tri& t = sc.tris[e];
+            const TriNorms q = tri_norms(t);
+            if (!(q.P <= kLemmaPmax)) return;
+            L.em_rho = std::max(L.em_rho, 32.0 * (u / eps) * q.P * (R1 + q.V0 + q.E1 + q.E2));
+            six = std::max(six, 6.0 * u * (q.E1 + q.E2));
+            for (const float* v : { t.v0, t.v1, t.v2 })
+                for (int c = 0; c < 3; ++c) {
+                    L.em_lo[c] = std::min(L.em_lo[c], (double)v[c]);
+                    L.em_hi[c] = std::max(L.em_hi[c], (double)v[c]);
+                }
+        }
+        L.em_add = six + delta1 + 1e-20;
+        // mirror classes: the scene's distinct `reflective` values, the largest kLevel1Classes - 1 on their own and the rest merged
+        // upward into the lowest class (its box then holds every triangle)
+        std::vector<float> vals;
+        for (int32_t i = 0; i < sc.n_tris; ++i) vals.push_back(P.surfs[(size_t)i].reflective);
+        std::sort(vals.begin(), vals.end()); vals.erase(std::unique(vals.begin(), vals.end()), vals.end());
+        const size_t nv = vals.size(), nc = std::min<size_t>(nv, (size_t)kLevel1Classes);
+        L.n_classes = (int32_t)nc;
+        for (size_t c = 0; c < nc; ++c) {
+            L.class_val[c] = vals[nv - nc + c];
+            const float from = (c == 0) ? vals[0] : L.class_val[c];
+            float* b = L.class_box[c];
+            b[0] = b[1] = b[2] = INFINITY; b[3] = b[4] = b[5] = -INFINITY;     // empty until a triangle joins
+            for (int32_t i = 0; i < sc.n_tris; ++i) {
+                if (!(P.surfs[(size_t)i].reflective >= from)) continue;
+                const sq_tri& t = sc.tris[i];
+                const TriNorms q = tri_norms(t);
+                if (!(q.P <= kLemmaPmax)) { b[0] = b[1] = b[2] = -INFINITY; b[3] = b[4] = b[5] = INFINITY; break; }
+                double m = lemma_rho(q, omax);
+                m += 8.0 * u * (vmax_inf + m + omax) + 1e-20;                    // the slab test's own rounding, as sq_cull_boxes
+                for (int k = 0; k < 3; ++k) {
+                    const double lo = std::min({ (double)t.v0[k], (double)t.v1[k], (double)t.v2[k] }), hi = std::max({ (double)t.v0[k], (double)t.v1[k], (double)t.v2[k] });
+                    b[k] = std::min(b[k], f_down(lo - m)); b[3 + k] = std::max(b[3 + k], f_up(hi + m));
+                }
+            }
+        }
+        L.o2max = P.cull_limits[0]; L.d2min = P.cull_limits[1]; L.d2max = P.cull_limits[2];
+        L.on = 1;
+    }
     void geometry_flags() {                                 // v_min / v_max slabs need NaN-free planes
         bool fin = finite3(sc.root.lo) && finite3(sc.root.hi);
         for (const DevBranch& d : P.branches) fin = fin && finite3(d.lo) && finite3(d.hi) && finite(d.lmax) && finite(d.rmin);
@@ -828,7 +951,7 @@ int sq_pack_scene(const sq_scene& sc, PackedScene& out) {
     if (sc.height && sc.height != out.height) return sq_set_error("scene.height = %d but the tree has height %d", sc.height, out.height);
     k.renumber(); k.branch_boxes(); k.material_flags(); k.triangles_and_surfaces(); k.vertex_index_form(); k.resident_encoding();
     if (k.culling_tables() || k.leaf_references()) return 1;
-    k.merged_records(); k.emitter_list(); k.geometry_flags();
+    k.merged_records(); k.emitter_list(); k.geometry_flags(); k.level1_tables();
     return 0;
 }
 
@@ -849,6 +972,7 @@ extern "C" int sq_packed_array(const sq_packed* P, const char* name, const void*
     is("branches", P->branches); is("leaves", P->leaves); is("tris", P->tris); is("tri_mat", P->tri_mat); is("surfs", P->surfs);
     is("mats", P->mats); is("verts4", P->verts4); is("trix", P->trix); is("rbranch", P->rbranch); is("emitters", P->emitters);
     is("cull_child", P->cull_child); is("cull_child16", P->cull_child16); is("branches_m", P->branches_m);
+    if (!found && !std::strcmp(name, "level1")) { found = true; *data = &P->level1; *bytes = sizeof P->level1; }
     return found ? 0 : sq_set_error("no packed array '%s'", name);
 }
 extern "C" int sq_packed_scalar(const sq_packed* P, const char* name, int64_t* value) {
@@ -858,7 +982,7 @@ extern "C" int sq_packed_scalar(const sq_packed* P, const char* name, int64_t* v
         { "n_branches", P->nb }, { "n_leaves", P->nl }, { "height", P->height }, { "root_ref", P->root_ref }, { "rroot", P->rroot },
         { "packed_leaves", P->packed_leaves }, { "nonneg_materials", P->nonneg_materials }, { "finite_geometry", P->finite_geometry },
         { "n_emitters", P->n_emitters }, { "n_verts", P->n_verts }, { "cull_o2max", lim[0] }, { "cull_d2min", lim[1] }, { "cull_d2max", lim[2] },
-        { "small_index", P->small_index }, { "shortcut_depth", P->shortcut_depth } };
+        { "small_index", P->small_index }, { "shortcut_depth", P->shortcut_depth }, { "level1_zero", P->level1_zero }, { "level1_on", P->level1.on } };
     for (const auto& s : all) if (!std::strcmp(name, s.name)) { *value = s.value; return 0; }
     return sq_set_error("no packed scalar '%s'", name);
 }

@@ -36,5 +36,17 @@ constexpr uint32_t kAxisMask = 3u << kAxisShift;               //   the LEFT wor
 // (5 of scene.obj's 1278 children).  The packer still sets them (the removed incremental slab test read them);
 // every reader masks them off.
 constexpr uint32_t kGrownLeft = 1u, kGrownRight = 2u;
+// The first-bounce reduction (sq_host.cpp, "Level-1 culling"; read by sq_gen_bounce1 alone, as a kernel argument of its own):
+// a scattered ray 1 whose sample provably ends with the radiance of a first-bounce miss is never queued.
+constexpr int kLevel1Classes = 4;
+struct Level1Cull {
+    int32_t on;                              // 0: nothing is culled (a precondition fails, or option "level1_cull" is 0)
+    int32_t n_classes;                       // mirror classes in use, ascending by value
+    float o2max, d2min, d2max;               // the culling lemma's limits on a ray (sq_cull_boxes), here for ray 1 and for +-randomVector
+    float class_val[kLevel1Classes];         // class c: every triangle that mirrors when unit_float(n1) <= class_val[c] ...
+    float class_box[kLevel1Classes][6];      // ... lies in this culling box (lo.xyz, hi.xyz; infinite where the lemma does not reach)
+    double em_lo[3], em_hi[3];               // bounding box of the emissive triangles' vertices
+    double em_rho, em_add;                   // its margin for a ray 2 whose smallest accepted |determinant| is a: em_rho * (eps / a) + em_add
+};
 constexpr int kTriRunPad = 3;   // zero triangles after the last one, so that a run of loads may start at any triangle (GlobalTris::kRunPad)
 }  // namespace sqd

@@ -205,14 +205,18 @@ __device__ __forceinline__ Surface surface_of(const SceneView& S, int tri) {
 
 // bounceRay (src/Lib.hs:155-160): `ref < x` scatters, otherwise mirrors; x is the first draw of `gen`.
 __device__ __forceinline__ bool scatters(const Surface& s, uint32_t nu) { return s.reflective < sq::unit_float(nu); }
-// scatterRay (src/Lib.hs:166-172): u is the SAME draw nu as x (same `gen`); v is the next draw nv.
-__device__ __forceinline__ f3 scatter_dir(f3 d, const Surface& s, uint32_t nu, uint32_t nv) {
+// randomVector (src/Lib.hs:192-198) of the draws nu, nv.
+__device__ __forceinline__ f3 random_vector(uint32_t nu, uint32_t nv) {
     const float u = sq::unit_float(nu), v = sq::unit_float(nv);
     const float th = 2 * sq::kPi * u;
     const float ph = sq::facos(2 * v - 1);
     float sth, cth, sph, cph;
     sq::fsincos(th, sth, cth); sq::fsincos(ph, sph, cph);
-    const f3 nd = sq::mk(cth * sph, sth * sph, cph);                    // randomVector, src/Lib.hs:192-198
+    return sq::mk(cth * sph, sth * sph, cph);
+}
+// scatterRay (src/Lib.hs:166-172): u is the SAME draw nu as x (same `gen`); v is the next draw nv.
+__device__ __forceinline__ f3 scatter_dir(f3 d, const Surface& s, uint32_t nu, uint32_t nv) {
+    const f3 nd = random_vector(nu, nv);
     const float old_ = sq::hsignum(sq::dot(d, s.n)), new_ = sq::hsignum(sq::dot(nd, s.n));
     return (old_ == new_) ? -nd : nd;
 }
