@@ -324,6 +324,39 @@ int     sq_scene_set_depth(sq_device_scene* s, int32_t depth);
 /* The scene's depth; -1 (sq_last_error) for s == NULL. */
 int32_t sq_scene_get_depth(sq_device_scene* s);
 
+/* Caller-given sky for the scene's path-traced computations: the radiance of a ray that leaves the scene.  It applies where the depth
+ * applies: sq_render_rows_device, its _range and _masked forms and sq_render_views_device, each with cast == 0, and
+ * sq_raytrace_rays_device, at every depth from 1 to 8, in "variant" 2 and 1, every trace form and every primary form.  (Cast frames and
+ * sq_raycast_rays_device ignore it; the one-shot calls upload a scene of their own and have no sky.)  Under a sky the radiance of a
+ * sample is L(0) of sq_scene_set_depth's chain with one line changed, every operation a single fp32 operation in this order; d_b is
+ * the direction of ray b exactly as it was traced (for b = 0 primary_dir of the pixel, or the caller's direction), not normalised
+ * beforehand:
+ *      L(b) = black (+0, +0, +0)                                   if b >= D
+ *           = sky(d_b)                                             if inter_b is Nothing          -- without a sky: black
+ *           = surfColor_b * L(b+1) + emissive_b *^ emitColor_b     otherwise
+ *      sky(d):  n = sqrt((d.x*d.x + d.y*d.y) + d.z*d.z);  u = d.z / n;  t = 0.5 * u + 0.5
+ *               sky_c = down_c + t * (up_c - down_c)               for c = x, y, z
+ * up is the radiance seen looking along +z, down along -z; up == down is a constant sky (up_c - down_c is +0, so sky = down for every
+ * finite non-zero d).  Values are not checked, as with light powers: NaN, infinite and negative components, d = 0 (t is NaN) and
+ * inf - inf are inputs like any other, and the expression's own NaN and inf are the result.  Everything after the sample's radiance is
+ * as it was: the ordered fold into sum, a masked call's sum2 = sum2 + r * r, counts, avg and the tonemap.
+ * A pixel or query ray whose ray 0 misses no longer gets the constant black: its fold adds sky(d_0) once for each k of
+ * [k_begin, k_end), k_end - k_begin single additions from where the pixel's fold starts (not one multiplication), and it gets sum2,
+ * count, avg and the tonemapped RGB like any other pixel.  A dead pixel of a masked call is still written nowhere.
+ * The sky is host state that the next call's planning reads, like the depth: the set call enqueues nothing and takes no stream, and a
+ * frame enqueued before it keeps the sky it had.  Under a sky a call runs the generic-depth kernels at every depth, D = 3 included,
+ * whatever option "deep" says, without the absorbing-surface shortcut and the last ray's emitter pre-test (neither is an identity
+ * under a sky), and sq_last_plan reports as for a deep call.  A wavefront call under a sky keeps 4 more bytes per slot of path state
+ * than sq_scene_set_depth names (t of the ray that missed; D >= 2), allocated as described there (HOST WAIT).
+ *  sky == NULL: no sky (the reference).  A scene that was never given a sky, or was reset with NULL, launches exactly the kernels and
+ *          launches it launched before this function existed.  A sky of all +0 is a sky, not the unset state: it differs from black on
+ *          a ray with d = 0.
+ * Refused with a message, nothing changed: s == NULL. */
+typedef struct { float up[3]; float down[3]; } sq_sky;     /* radiance seen looking along +z / along -z */
+int     sq_scene_set_sky(sq_device_scene* s, const sq_sky* sky);
+/* 1 = a sky is set (copied to out, which may be NULL), 0 = none (out untouched), -1 (sq_last_error) for s == NULL. */
+int     sq_scene_get_sky(sq_device_scene* s, sq_sky* out);
+
 /* Timing of the dominant kernel measured with hipEvents on the stream it was launched on:
  * average duration in ms over the launches since the last reset, and the launch count. */
 int  sq_kernel_timing(sq_device_scene* s, double* avg_ms, int64_t* launches, const char** kernel_name);
@@ -432,7 +465,7 @@ typedef struct {
     int32_t pixel_lds_bytes;   /* dynamic LDS of one 256-thread workgroup of the per-pixel kernel / per-lane primary rays */
     int32_t primary_form;      /* SQ_PRIMARY_*: how the primary rays of a wavefront frame were traced (NONE with the per-pixel kernel) */
     int32_t packed_leaves;     /* streaming forms: leaf references carry count << 24 | first (every leaf <= 31 triangles) */
-    int32_t n_emitters;        /* length of the last-bounce emitter list, -1 = shortcut off (> 64 emitters or non-finite materials) */
+    int32_t n_emitters;        /* length of the last-bounce emitter list, -1 = shortcut off (> 64 emitters, non-finite materials, or a call under a sky) */
     int32_t level1_cull;       /* 1 = the frame's first-bounce rays went through level-1 culling (option "level1_cull" and the scene's preconditions) */
 } sq_plan;
 int  sq_last_plan(sq_device_scene* s, sq_plan* out);

@@ -109,6 +109,8 @@ def lib():
     L.sq_scene_set_depth.argtypes = [vp, i32]
     L.sq_scene_get_depth.argtypes = [vp]
     L.sq_scene_get_depth.restype = i32
+    L.sq_scene_set_sky.argtypes = [vp, vp]
+    L.sq_scene_get_sky.argtypes = [vp, vp]
     L.sq_kernel_timing.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_char_p)]
     L.sq_kernel_timing_reset.argtypes = [vp]
     L.sq_kernel_timing_reset.restype = None
@@ -206,6 +208,36 @@ def depth_value(depth):
     return int(depth)
 
 
+def sky_value(up, down=None):
+    """The float32 array [2, 3] (up, down) of DeviceScene.set_sky's arguments and of sky= of the render functions: up and down are
+    three numbers each, down = None is up once more (a constant sky).  The values are not checked (NaN, infinite and negative
+    components are inputs like any other); SquiglyError for anything that is not three numbers."""
+    rows = []
+    for name, v in (("up", up), ("down", up if down is None else down)):
+        try:
+            row = np.asarray(v, np.float32).reshape(-1)
+        except (TypeError, ValueError):
+            row = None
+        if row is None or row.shape != (3,) or isinstance(v, (str, bytes)):
+            raise SquiglyError(f"sky {name}: expected three numbers (R, G, B), got {v!r}")
+        rows.append(row)
+    return np.ascontiguousarray(np.stack(rows), np.float32)
+
+
+def sky_pair(sky):
+    """sky= of the render functions and of a checkpoint -- None, three numbers (a constant sky) or (up, down) -- as None or the
+    float32 array [2, 3]."""
+    if sky is None:
+        return None
+    try:
+        n = len(sky)
+    except TypeError:
+        raise SquiglyError(f"sky must be None, three numbers or (up, down), got {sky!r}")
+    if n == 2:
+        return sky_value(sky[0], sky[1])
+    return sky_value(sky)
+
+
 OPS = {"sqrt": 0, "div": 1, "sin": 2, "cos": 3, "acos": 4, "atan": 5, "unit_float": 6, "tfgen3": 7, "tonemap": 8, "rcp_sweep": 9, "cull_slab": 10}
 
 
@@ -243,7 +275,7 @@ def check(rc):
 EXPORTED_SYMBOLS = [
     # include/squigly_hip.h
     "sq_render_rgb8", "sq_render_f32", "sq_scene_upload", "sq_scene_free", "sq_shard_rows",
-    "sq_shard_global_row", "sq_render_rows_device", "sq_render_rows_device_range", "sq_render_rows_device_masked", "sq_adaptive_update_device", "sq_render_views_device", "sq_intersect_rays_device", "sq_camera_rays_device", "sq_raytrace_rays_device", "sq_raycast_rays_device", "sq_scene_set_lights", "sq_scene_get_lights", "sq_scene_set_depth", "sq_scene_get_depth", "sq_kernel_timing", "sq_kernel_timing_reset",
+    "sq_shard_global_row", "sq_render_rows_device", "sq_render_rows_device_range", "sq_render_rows_device_masked", "sq_adaptive_update_device", "sq_render_views_device", "sq_intersect_rays_device", "sq_camera_rays_device", "sq_raytrace_rays_device", "sq_raycast_rays_device", "sq_scene_set_lights", "sq_scene_get_lights", "sq_scene_set_depth", "sq_scene_get_depth", "sq_scene_set_sky", "sq_scene_get_sky", "sq_kernel_timing", "sq_kernel_timing_reset",
     "sq_set_option", "sq_scene_rng_table", "sq_get_stats", "sq_last_plan", "sq_debug_eval", "sq_device_count", "sq_abi_version", "sq_build_id", "sq_last_error",
     # include/squigly_host.h
     "sq_mesh_from_obj", "sq_mesh_from_text", "sq_mesh_from_arrays", "sq_mesh_num_tris",

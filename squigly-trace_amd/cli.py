@@ -65,6 +65,18 @@ def parse_light(text):
     return (tuple(v[:3]), power)
 
 
+def parse_sky(text):
+    """The sky of --sky: R,G,B (a constant sky) or R,G,B,R,G,B (up, then down) -> ((r, g, b), (r, g, b)).  The value may stand in
+    parentheses, as with --light."""
+    try:
+        v = [float(t) for t in text.strip("()").split(",")]
+    except ValueError:
+        v = []
+    if len(v) not in (3, 6):
+        raise argparse.ArgumentTypeError("expected R,G,B or R,G,B,R,G,B")
+    return (tuple(v[:3]), tuple(v[3:]) if len(v) == 6 else tuple(v[:3]))
+
+
 def parse_views(text):
     """The cameras of a views file: the reference's camera format (src/Obj.hs:60-70) repeated, each pair of non-blank lines one
     camera (position, then rotation angles).  Raises ValueError for an odd line count, a line that does not parse or no camera."""
@@ -141,6 +153,10 @@ def build_parser():
     # not a flag of the reference: how many rays long a path is (the reference's is fixed at 3)
     p.add_argument("--depth", type=path_depth, default=None, metavar="N",
                    help="Rays per path, 1..8: 1 = emission only, 2 = direct light, 3 = the reference's (default); not with --cast")
+    # not a flag of the reference: what a ray that leaves the scene sees (the reference's is black)
+    p.add_argument("--sky", type=parse_sky, default=None, metavar="R,G,B[,R,G,B]",
+                   help="Radiance of a ray that leaves the scene: looking up (+z), then looking down (-z; default the same: "
+                        "a constant sky), blended by the ray's direction (default: none, black); not with --cast")
     return p
 
 
@@ -157,6 +173,8 @@ def parse_args(argv=None):
         p.error("--light needs --cast")
     if a.depth is not None and a.cast:
         p.error("--depth cannot be combined with --cast (a cast image has no paths)")
+    if a.sky is not None and a.cast:
+        p.error("--sky cannot be combined with --cast (a cast image has no sky)")
     return a
 
 
@@ -192,7 +210,7 @@ def main(argv=None):
     print("Started at " + time.strftime("%H:%M:%S%p UTC", time.gmtime(t0)).lower().replace("utc", "UTC"))
     os.makedirs(os.path.dirname(os.path.abspath(settings.savePath)), exist_ok=True)
     if a.views is not None:
-        imgs = render_views_rgb8(bih, a.views, settings.samples, settings.dimensions, settings.cast, lights=a.light, depth=a.depth)
+        imgs = render_views_rgb8(bih, a.views, settings.samples, settings.dimensions, settings.cast, lights=a.light, depth=a.depth, sky=a.sky)
         for path, img in zip(view_paths(settings.savePath, len(imgs)), imgs):
             write_png(path, img)
         print(f"Wrote {len(imgs)} views to {view_paths(settings.savePath, 1)[0]} ...")
@@ -200,21 +218,21 @@ def main(argv=None):
         import numpy as np
         for done, live, spent, img, counts in render_adaptive(bih, cam, settings.samples, settings.dimensions, a.adaptive, eps=a.adaptive_eps,
                                                               first=a.adaptive_first, step=a.adaptive_step, cast=settings.cast, lights=a.light,
-                                                              depth=a.depth):
+                                                              depth=a.depth, sky=a.sky):
             print(f"Adaptive {done}/{settings.samples} live {live} spent {spent}")
         write_png(settings.savePath, img)
         if a.counts is not None:
             with open(a.counts, "wb") as f:                     # the name as given (np.save would append .npy to a path)
                 np.save(f, counts.astype(np.int32))
-    elif a.preview_every is None and a.light is None and a.depth is None:
+    elif a.preview_every is None and a.light is None and a.depth is None and a.sky is None:
         render(bih, cam, settings)
-    elif a.preview_every is None:                               # caller-given lights and depths live on a resident scene: one step of all samples
+    elif a.preview_every is None:                               # caller-given lights, depths and skies live on a resident scene: one step of all samples
         for _, img in render_progressive(bih, cam, settings.samples, settings.dimensions, settings.samples, settings.cast, lights=a.light,
-                                         depth=a.depth):
+                                         depth=a.depth, sky=a.sky):
             write_png(settings.savePath, img)
     else:
         for done, img in render_progressive(bih, cam, settings.samples, settings.dimensions, a.preview_every, settings.cast, lights=a.light,
-                                            depth=a.depth):
+                                            depth=a.depth, sky=a.sky):
             write_png(settings.savePath, img)
             print(f"Preview: {done}/{settings.samples} samples written to {settings.savePath}")
     t1 = time.time()

@@ -1,7 +1,7 @@
 // squigly-trace — the reference's executable (app/Main.hs:13-75) over the C-ABI.
 //
 //   squigly-trace [--samples N|-s N] [--dimensions W,H|-d W,H] [--savepath F|-p F] [--objpath F]
-//                 [--camerapath F|-c F] [--debug] [--debugpath F] [--cast] [--depth N]
+//                 [--camerapath F|-c F] [--debug] [--debugpath F] [--cast] [--depth N] [--sky R,G,B[,R,G,B]]
 //
 // Same flags, defaults and printouts as the Haskell program; the render itself is sq_render_rgb8, i.e. the
 // foreign call that replaces src/Lib.hs:73-74.  The material file named by `mtllib` is read from ./data/
@@ -65,9 +65,10 @@ std::string show_time(std::time_t t) {           // formatTime defaultTimeLocale
     std::strftime(buf, sizeof buf, "%H:%M:%S", &g);
     return std::string(buf) + (g.tm_hour < 12 ? "am" : "pm") + " UTC";
 }
-// --depth: the frame of a resident scene under depth `depth` into img (w * h * 3 bytes).  The C-ABI leaves the frame on the device;
+// --depth, --sky: the frame of a resident scene under depth `depth` (0: the scene's own, 3) and the sky `sky` (NULL: none) into img
+// (w * h * 3 bytes).  The C-ABI leaves the frame on the device;
 // hipMemcpy brings it back (and waits for the null stream the frame was enqueued on).  Prints what failed.
-bool render_resident(const sq_scene* sc, const sq_camera* cam, int samples, int w, int h, int depth, uint8_t* img) {
+bool render_resident(const sq_scene* sc, const sq_camera* cam, int samples, int w, int h, int depth, const sq_sky* sky, uint8_t* img) {
     sq_device_scene* ds = nullptr;
     if (sq_scene_upload(sc, 0, &ds)) { std::fprintf(stderr, "squigly-trace: render: %s\n", sq_last_error()); return false; }
     void* d_rgb = nullptr;
@@ -75,7 +76,8 @@ bool render_resident(const sq_scene* sc, const sq_camera* cam, int samples, int 
     bool ok = true;
     auto lib = [&](int rc) { if (ok && rc != 0) { std::fprintf(stderr, "squigly-trace: render: %s\n", sq_last_error()); ok = false; } };
     auto hip = [&](hipError_t e, const char* what) { if (ok && e != hipSuccess) { std::fprintf(stderr, "squigly-trace: render: %s: %s\n", what, hipGetErrorString(e)); ok = false; } };
-    lib(sq_scene_set_depth(ds, depth));
+    if (depth) lib(sq_scene_set_depth(ds, depth));
+    if (sky) lib(sq_scene_set_sky(ds, sky));
     hip(hipMalloc(&d_rgb, bytes ? bytes : 1), "hipMalloc");
     if (ok) lib(sq_render_rows_device(ds, cam, samples, w, h, 0, sq_shard{ w > 0 ? w : 1, 0, 1 }, nullptr, (uint8_t*)d_rgb, nullptr));
     if (ok) hip(hipMemcpy(img, d_rgb, bytes, hipMemcpyDeviceToHost), "hipMemcpy");
@@ -90,6 +92,7 @@ int fail(const char* what) { std::fprintf(stderr, "squigly-trace: %s: %s\n", wha
 int main(int argc, char** argv) {
     // defaults: app/Main.hs:14-30
     int samples = 10, w = 540, h = 540, depth = 0; bool debug = false, cast = false;   // depth 0: not given
+    sq_sky sky{}; bool has_sky = false;
     std::string save = "./render/result.png", objp = "./data/scene.obj", camp = "./data/camera", dbgp;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i], val; bool has = false;
@@ -109,17 +112,26 @@ int main(int argc, char** argv) {
             if (end == v || *end || d < 1 || d > 8) { std::fprintf(stderr, "--depth wants an integer in 1..8 (got %s)\n", v); return 2; }
             depth = (int)d;
         }
+        else if (a == "--sky") {                                           // up, then down (default the same: a constant sky)
+            const char* v = need(); float c[6]; char extra;
+            const int n = std::sscanf(v, "%f,%f,%f,%f,%f,%f%c", &c[0], &c[1], &c[2], &c[3], &c[4], &c[5], &extra);
+            if (n != 3 && n != 6) { std::fprintf(stderr, "--sky wants R,G,B or R,G,B,R,G,B (got %s)\n", v); return 2; }
+            for (int j = 0; j < 3; ++j) { sky.up[j] = c[j]; sky.down[j] = n == 6 ? c[3 + j] : c[j]; }
+            has_sky = true;
+        }
         else if (a == "--help" || a == "-?") {
             std::puts("squigly-trace was made by Ruko (https://github.com/rukokarasu/)\nA cute raytracer\n"
                       "  -s --samples=INT        How many samples per pixel to trace\n  -d --dimensions=INT,INT Dimensions of the resulting image\n"
                       "  -p --savepath=FILE      Where to save the output\n     --objpath=FILE       File to load .obj from\n"
                       "  -c --camerapath=FILE    File to load camera data from\n     --debug              Run in debug mode\n"
                       "     --debugpath=FILE     File to write debug info to\n     --cast               Raycast instead of raytracing (i.e. don't bounce rays)\n"
-                      "     --depth=INT          Rays per path, 1..8 (default 3, the reference's); not with --cast");
+                      "     --depth=INT          Rays per path, 1..8 (default 3, the reference's); not with --cast\n"
+                      "     --sky=R,G,B[,R,G,B]  Radiance of a ray that leaves the scene, looking up (+z) and down (-z, default the same); not with --cast");
             return 0;
         } else { std::fprintf(stderr, "Unknown flag: %s\n", a.c_str()); return 2; }
     }
     if (depth && cast) { std::fprintf(stderr, "--depth cannot be combined with --cast (a cast image has no paths)\n"); return 2; }
+    if (has_sky && cast) { std::fprintf(stderr, "--sky cannot be combined with --cast (a cast image has no sky)\n"); return 2; }
     sq_camera cam;
     if (sq_camera_from_file(camp.c_str(), &cam)) return fail("Failed to parse camera");        // app/Main.hs:38
     sq_mesh* mesh = nullptr;
@@ -151,7 +163,7 @@ int main(int argc, char** argv) {
     std::printf("Started at %s\n", show_time(std::chrono::system_clock::to_time_t(t0)).c_str());
     sq_scene sc; sq_bih_scene(bih, &sc);
     std::vector<uint8_t> img((size_t)(w > 0 ? w : 0) * (size_t)(h > 0 ? h : 0) * 3);
-    if (depth) { if (!render_resident(&sc, &cam, samples, w, h, depth, img.data())) return 1; }
+    if (depth || has_sky) { if (!render_resident(&sc, &cam, samples, w, h, depth, has_sky ? &sky : nullptr, img.data())) return 1; }
     else if (sq_render_rgb8(&sc, &cam, samples, w, h, cast ? 1 : 0, img.data())) return fail("render");  // src/Lib.hs:73-74
     if (!write_png(save.c_str(), img.data(), w, h)) { std::fprintf(stderr, "squigly-trace: cannot write %s\n", save.c_str()); return 1; }
     const auto t1 = std::chrono::system_clock::now();

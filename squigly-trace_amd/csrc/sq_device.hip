@@ -214,6 +214,39 @@ __device__ __forceinline__ void store_live_miss(const Frame& F, long long pix) {
 }
 
 // ----------------------------------------------------------------------------------------------
+// Caller-given sky (sq_scene_set_sky): the radiance of a ray that leaves the scene
+// ----------------------------------------------------------------------------------------------
+// The kernels' SKY instantiations take it by value; every other instantiation is handed an empty one and reads nothing of it.
+struct Sky { float up[3], down[3]; };
+// t of a ray's direction as it was traced (not normalised beforehand): every operation a single fp32 operation in this order.
+__device__ __forceinline__ float sky_t(f3 d) {
+    const float n = sq::fsqrt((d.x * d.x + d.y * d.y) + d.z * d.z);
+    const float u = d.z / n;
+    return 0.5f * u + 0.5f;
+}
+__device__ __forceinline__ f3 sky_at(const Sky& K, float t) {
+    return sq::mk(K.down[0] + t * (K.up[0] - K.down[0]), K.down[1] + t * (K.up[1] - K.down[1]), K.down[2] + t * (K.up[2] - K.down[2]));
+}
+__device__ __forceinline__ void store_fold(const Frame& F, long long pix, f3 sum);
+// A (live) pixel whose primary ray misses under a sky: sky(d_0) folded once per sample of [k_begin, k_end) from where the pixel's
+// fold starts -- single additions, not one multiplication -- and everything a hit pixel's fold ends with.
+template <bool AD>
+__device__ __forceinline__ void store_miss_sky(const Frame& F, long long pix, const Sky& K, f3 d0) {
+    const f3 c = sky_at(K, sky_t(d0));
+    f3 sum = fold_start(F, pix);
+    for (int k = F.k_begin; k < F.k_end; ++k) sum = sum + c;
+    if constexpr (AD) {
+        if (F.sum2) {
+            f3 sum2 = fold_start2(F, pix);
+            for (int k = F.k_begin; k < F.k_end; ++k) sum2 = sum2 + c * c;
+            float* o = F.sum2 + pix * 3; o[0] = sum2.x; o[1] = sum2.y; o[2] = sum2.z;
+        }
+        store_count(F, pix);
+    }
+    store_fold(F, pix, sum);
+}
+
+// ----------------------------------------------------------------------------------------------
 // Variant 1: one lane per pixel, everything in one kernel (cross-check variant; also raycast mode)
 // ----------------------------------------------------------------------------------------------
 // MV: a multi-view frame (pixels are enumerated linearly, so the lanes of a wave may belong to two views: per-lane camera reads)
@@ -389,8 +422,9 @@ __device__ __forceinline__ void store_miss(const Frame& F, long long pix) {
 // Primary rays: trace once per pixel, compact the pixels that hit.
 // AD (here and in the other primary passes): a masked call; a dead pixel's lane is treated like the padding of an edge tile.
 // kSrcRays: no image to tile -- the caller's rays in index order, 64 consecutive rays per wave.
-template <typename StackT, int SRC, bool AD, typename FrameT>
-__device__ __forceinline__ void primary_body(const SceneView& S, const FrameT& F, const Work& W) {
+// SKY (here and in the other primary passes): a miss folds sky(d_0) instead of storing black.
+template <typename StackT, int SRC, bool AD, bool SKY, typename FrameT>
+__device__ __forceinline__ void primary_body(const SceneView& S, const FrameT& F, const Work& W, const Sky& K) {
     constexpr bool MV = SRC == kSrcViews;
     extern __shared__ float4 lds_raw[];
     SQ_LDS StackT* stk = to_lds<StackT>(lds_raw) + threadIdx.x;
@@ -403,28 +437,37 @@ __device__ __forceinline__ void primary_body(const SceneView& S, const FrameT& F
     bool in = pix >= 0;
     if constexpr (AD) in = in && pixel_live(F, pix);
     Hit h0; h0.tri = -1; h0.t = 0;
+    f3 d0 = sq::mk(0, 0, 0);
     if (in) {
         int y, x;
         const GlobalNodes N{ S.branches, S.cull_child, S.cull_child != nullptr };
         if constexpr (SRC == kSrcRays) {
-            h0 = trace_one(S, N, load3(F.ray_org, pix), load3(F.ray_dir, pix), stk, kBlock);
+            const f3 o0 = load3(F.ray_org, pix);
+            d0 = load3(F.ray_dir, pix);
+            h0 = trace_one(S, N, o0, d0, stk, kBlock);
         } else if constexpr (MV) {
             pixel_coords(F, pix - (long long)view * F.view_pixels, y, x);
             const ViewCam c = view_cam<true>(F, view);
-            h0 = trace_one(S, N, c.pos, primary_dir(c.rot, F.w, F.h, y, x), stk, kBlock);
+            d0 = primary_dir(c.rot, F.w, F.h, y, x);
+            h0 = trace_one(S, N, c.pos, d0, stk, kBlock);
         } else {
             pixel_coords(F, pix, y, x);
-            h0 = trace_one(S, N, sq::mk(F.cam_pos[0], F.cam_pos[1], F.cam_pos[2]), primary_dir(F.cam_rot, F.w, F.h, y, x), stk, kBlock);
+            d0 = primary_dir(F.cam_rot, F.w, F.h, y, x);
+            h0 = trace_one(S, N, sq::mk(F.cam_pos[0], F.cam_pos[1], F.cam_pos[2]), d0, stk, kBlock);
         }
     }
     const int a = wave_append(W.n_active, in && h0.tri >= 0);
     if (a >= 0) store_active<AD>(F, W, a, pix, h0.t, h0.tri);
-    else if (in) store_miss<AD>(F, pix);
+    else if (in) { if constexpr (SKY) store_miss_sky<AD>(F, pix, K, d0); else store_miss<AD>(F, pix); }
 }
 template <typename StackT, bool MV, bool AD = false>
-__global__ void __launch_bounds__(kBlock) sq_primary(const SceneView S, const Frame F, const Work W) { primary_body<StackT, MV, AD>(S, F, W); }
+__global__ void __launch_bounds__(kBlock) sq_primary(const SceneView S, const Frame F, const Work W) { primary_body<StackT, MV, AD, false>(S, F, W, Sky{}); }
 template <typename StackT>
-__global__ void __launch_bounds__(kBlock) sq_primary_rays(const SceneView S, const RayFrame F, const Work W) { primary_body<StackT, kSrcRays, false>(S, F, W); }
+__global__ void __launch_bounds__(kBlock) sq_primary_rays(const SceneView S, const RayFrame F, const Work W) { primary_body<StackT, kSrcRays, false, false>(S, F, W, Sky{}); }
+template <typename StackT, bool MV, bool AD = false>
+__global__ void __launch_bounds__(kBlock) sq_primary_sky(const SceneView S, const Frame F, const Work W, const Sky K) { primary_body<StackT, MV, AD, true>(S, F, W, K); }
+template <typename StackT>
+__global__ void __launch_bounds__(kBlock) sq_primary_sky_rays(const SceneView S, const RayFrame F, const Work W, const Sky K) { primary_body<StackT, kSrcRays, false, true>(S, F, W, K); }
 
 struct Pixel0 { f3 p0, d0; Surface s0; int y, x; };
 // Everything the kernels downstream of the primary pass know about active pixel a, and the one place where they learn it.
@@ -724,6 +767,19 @@ __global__ void __launch_bounds__(kBlock) sq_primary_store(const Frame F, const 
         const int a = wave_append(W.n_active, in && hit.y >= 0);
         if (a >= 0) store_active<AD>(F, W, a, pix, __int_as_float(hit.x), hit.y);
         else if (in) store_miss<AD>(F, pix);
+    }
+}
+// ... under a sky: d_0 is the direction sq_primary_gen put into the slot, which the trace kernel leaves as it took it.
+template <bool AD = false>
+__global__ void __launch_bounds__(kBlock) sq_primary_store_sky(const Frame F, const Work W, long long total, const Sky K) {
+    for (long long base = (long long)blockIdx.x * kBlock; base < total; base += (long long)gridDim.x * kBlock) {
+        const long long pix = base + threadIdx.x;
+        bool in = pix < total;
+        if constexpr (AD) in = in && W.state[pix] == kRay1;
+        const int2 hit = in ? slot_hit(W.org[pix]) : make_int2(0, -1);
+        const int a = wave_append(W.n_active, in && hit.y >= 0);
+        if (a >= 0) store_active<AD>(F, W, a, pix, __int_as_float(hit.x), hit.y);
+        else if (in) { const float4 d = W.dir[pix]; store_miss_sky<AD>(F, pix, K, sq::mk(d.x, d.y, d.z)); }
     }
 }
 
@@ -1188,8 +1244,8 @@ __device__ __forceinline__ void stage_resident_scene(const SceneView& S, int n_b
 // Primary rays with the scene in LDS (the resident form): same per-ray code as sq_primary, but a branch or triangle costs an
 // LDS read instead of an L2 round trip.  A primary ray is a chain of ~200 dependent reads, so on small frames -- one rank's
 // share of a frame at 8 ranks -- the launch is as long as that chain: 0.58 ms from L2, 0.1-0.2 ms from LDS.
-template <typename StackT, int SRC, bool AD, typename FrameT>
-__device__ __forceinline__ void primary_resident_body(const SceneView& S, const FrameT& F, const Work& W, int stack_cap) {
+template <typename StackT, int SRC, bool AD, bool SKY, typename FrameT>
+__device__ __forceinline__ void primary_resident_body(const SceneView& S, const FrameT& F, const Work& W, int stack_cap, const Sky& K) {
     constexpr bool MV = SRC == kSrcViews;
     extern __shared__ float4 lds_raw[];
     char* lds = reinterpret_cast<char*>(lds_raw);
@@ -1208,28 +1264,37 @@ __device__ __forceinline__ void primary_resident_body(const SceneView& S, const 
         bool in = pix >= 0;
         if constexpr (AD) in = in && pixel_live(F, pix);
         Hit h0; h0.tri = -1; h0.t = 0;
+        f3 d0 = sq::mk(0, 0, 0);
         if (in) {
             int y, x;
             if constexpr (SRC == kSrcRays) {
-                h0 = trace_one(S, N, G, S.rroot, load3(F.ray_org, pix), load3(F.ray_dir, pix), stk, kResidentBlock);
+                const f3 o0 = load3(F.ray_org, pix);
+                d0 = load3(F.ray_dir, pix);
+                h0 = trace_one(S, N, G, S.rroot, o0, d0, stk, kResidentBlock);
             } else if constexpr (MV) {
                 pixel_coords(F, pix - (long long)view * F.view_pixels, y, x);
                 const ViewCam c = view_cam<true>(F, view);
-                h0 = trace_one(S, N, G, S.rroot, c.pos, primary_dir(c.rot, F.w, F.h, y, x), stk, kResidentBlock);
+                d0 = primary_dir(c.rot, F.w, F.h, y, x);
+                h0 = trace_one(S, N, G, S.rroot, c.pos, d0, stk, kResidentBlock);
             } else {
                 pixel_coords(F, pix, y, x);
-                h0 = trace_one(S, N, G, S.rroot, sq::mk(F.cam_pos[0], F.cam_pos[1], F.cam_pos[2]), primary_dir(F.cam_rot, F.w, F.h, y, x), stk, kResidentBlock);
+                d0 = primary_dir(F.cam_rot, F.w, F.h, y, x);
+                h0 = trace_one(S, N, G, S.rroot, sq::mk(F.cam_pos[0], F.cam_pos[1], F.cam_pos[2]), d0, stk, kResidentBlock);
             }
         }
         const int a = wave_append(W.n_active, in && h0.tri >= 0);
         if (a >= 0) store_active<AD>(F, W, a, pix, h0.t, h0.tri);
-        else if (in) store_miss<AD>(F, pix);
+        else if (in) { if constexpr (SKY) store_miss_sky<AD>(F, pix, K, d0); else store_miss<AD>(F, pix); }
     }
 }
 template <typename StackT, bool MV, bool AD = false>
-__global__ void __launch_bounds__(kResidentBlock) sq_primary_resident(const SceneView S, const Frame F, const Work W, int stack_cap) { primary_resident_body<StackT, MV, AD>(S, F, W, stack_cap); }
+__global__ void __launch_bounds__(kResidentBlock) sq_primary_resident(const SceneView S, const Frame F, const Work W, int stack_cap) { primary_resident_body<StackT, MV, AD, false>(S, F, W, stack_cap, Sky{}); }
 template <typename StackT>
-__global__ void __launch_bounds__(kResidentBlock) sq_primary_resident_rays(const SceneView S, const RayFrame F, const Work W, int stack_cap) { primary_resident_body<StackT, kSrcRays, false>(S, F, W, stack_cap); }
+__global__ void __launch_bounds__(kResidentBlock) sq_primary_resident_rays(const SceneView S, const RayFrame F, const Work W, int stack_cap) { primary_resident_body<StackT, kSrcRays, false, false>(S, F, W, stack_cap, Sky{}); }
+template <typename StackT, bool MV, bool AD = false>
+__global__ void __launch_bounds__(kResidentBlock) sq_primary_resident_sky(const SceneView S, const Frame F, const Work W, int stack_cap, const Sky K) { primary_resident_body<StackT, MV, AD, true>(S, F, W, stack_cap, K); }
+template <typename StackT>
+__global__ void __launch_bounds__(kResidentBlock) sq_primary_resident_sky_rays(const SceneView S, const RayFrame F, const Work W, int stack_cap, const Sky K) { primary_resident_body<StackT, kSrcRays, false, true>(S, F, W, stack_cap, K); }
 
 template <typename StackT, bool RESIDENT, int BLOCK, bool PROFILE, bool POOL>
 __device__ __forceinline__ void trace_rays_body(const SceneView& S, const TraceArgs& A) {
@@ -1670,9 +1735,10 @@ __device__ __forceinline__ uint32_t tf_word(const uint64_t c[4], int i) {
 }
 // The radiance of a path from its triangles: tr[b] = the triangle ray b hit, b = 1 .. kMaxDepth - 1, -1 from the path's end on (a
 // miss, or the depth); s0 = the surface ray 0 hit.  L(b) = surfColor_b * L(b+1) + emissive_b *^ emitColor_b from the innermost hit
-// outwards, starting from black: the product with black is formed at the innermost level, as the reference forms it.
-__device__ __forceinline__ f3 path_radiance(const SceneView& S, const Surface& s0, const int (&tr)[kMaxDepth]) {
-    f3 L = sq::mk(0, 0, 0);
+// outwards, starting from `inner`: black where the depth ends the path, and where a ray misses without a sky; sky(d) of the ray that
+// missed under one.  The product with it is formed at the innermost level, as the reference forms it.
+__device__ __forceinline__ f3 path_radiance(const SceneView& S, const Surface& s0, const int (&tr)[kMaxDepth], f3 inner) {
+    f3 L = inner;
 #pragma unroll
     for (int b = kMaxDepth - 1; b >= 1; --b)
         if (tr[b] >= 0) { const Shade1 q = shade1_of(S, tr[b]); L = q.surf * L + q.emit; }
@@ -1681,8 +1747,9 @@ __device__ __forceinline__ f3 path_radiance(const SceneView& S, const Surface& s
 
 // Per-lane form (option "variant" = 1): sq_render_pixels' raytrace branch with a loop over the levels.  A lane keeps the triangles
 // of its path (registers: the level is matched by selects, not by an index) and folds L from the innermost level outwards.
-template <typename StackT, int SRC, bool AD, typename FrameT>
-__device__ __forceinline__ void render_pixels_deep_body(const SceneView& S, const FrameT& F, const int depth) {
+// SKY: a ray that misses ends its path on sky(d) of that ray; a pixel whose ray 0 misses folds sky(d_0) once per sample.
+template <typename StackT, int SRC, bool AD, bool SKY, typename FrameT>
+__device__ __forceinline__ void render_pixels_deep_body(const SceneView& S, const FrameT& F, const int depth, const Sky& K) {
     extern __shared__ float4 lds_raw[];
     SQ_LDS StackT* stk = to_lds<StackT>(lds_raw) + threadIdx.x;
     const long long pix = (long long)blockIdx.x * kBlock + threadIdx.x;
@@ -1722,17 +1789,26 @@ __device__ __forceinline__ void render_pixels_deep_body(const SceneView& S, cons
 #pragma unroll
             for (int i = 0; i < kMaxDepth; ++i) tr[i] = -1;
             f3 o = p0, d = d0; Surface sb = s0;
+            f3 inner = sq::mk(0, 0, 0);
 #pragma unroll 1
             for (int b = 1; b < depth; ++b) {                           // ray b = bounceRay gen_{b-1} ray_{b-1} inter_{b-1}
                 const f3 nd = bounce_dir(d, sb, tf_word(c, b - 1), tf_word(c, b));
                 const Hit h = trace_one(S, N, o, nd, stk, kBlock);
-                if (h.tri < 0) break;
+                if (h.tri < 0) { if constexpr (SKY) inner = sky_at(K, sky_t(nd)); break; }
 #pragma unroll
                 for (int i = 1; i < kMaxDepth; ++i) tr[i] = i == b ? h.tri : tr[i];
                 sb = surface_of(S, h.tri);
                 o = o + sq::scale(h.t, nd); d = nd;                     // intersectPoint, src/Geometry.hs:134
             }
-            const f3 r = path_radiance(S, s0, tr);
+            const f3 r = path_radiance(S, s0, tr, inner);
+            sum = sum + r;
+            if constexpr (AD) sum2 = sum2 + r * r;
+        }
+    } else if constexpr (SKY) {
+        sum = fold_start(F, pix);
+        if constexpr (AD) { if (F.sum2) sum2 = fold_start2(F, pix); }
+        const f3 r = sky_at(K, sky_t(d0));
+        for (int k = F.k_begin; k < F.k_end; ++k) {
             sum = sum + r;
             if constexpr (AD) sum2 = sum2 + r * r;
         }
@@ -1744,9 +1820,13 @@ __device__ __forceinline__ void render_pixels_deep_body(const SceneView& S, cons
     store_fold(F, pix, sum);
 }
 template <typename StackT, bool MV, bool AD = false>
-__global__ void __launch_bounds__(kBlock) sq_render_pixels_deep(const SceneView S, const Frame F, const int depth) { render_pixels_deep_body<StackT, MV, AD>(S, F, depth); }
+__global__ void __launch_bounds__(kBlock) sq_render_pixels_deep(const SceneView S, const Frame F, const int depth) { render_pixels_deep_body<StackT, MV, AD, false>(S, F, depth, Sky{}); }
 template <typename StackT>
-__global__ void __launch_bounds__(kBlock) sq_render_pixels_deep_rays(const SceneView S, const RayFrame F, const int depth) { render_pixels_deep_body<StackT, kSrcRays, false>(S, F, depth); }
+__global__ void __launch_bounds__(kBlock) sq_render_pixels_deep_rays(const SceneView S, const RayFrame F, const int depth) { render_pixels_deep_body<StackT, kSrcRays, false, false>(S, F, depth, Sky{}); }
+template <typename StackT, bool MV, bool AD = false>
+__global__ void __launch_bounds__(kBlock) sq_render_pixels_deep_sky(const SceneView S, const Frame F, const int depth, const Sky K) { render_pixels_deep_body<StackT, MV, AD, true>(S, F, depth, K); }
+template <typename StackT>
+__global__ void __launch_bounds__(kBlock) sq_render_pixels_deep_sky_rays(const SceneView S, const RayFrame F, const int depth, const Sky K) { render_pixels_deep_body<StackT, kSrcRays, false, true>(S, F, depth, K); }
 
 // Wavefront form: the levels go through the planned trace kernel one after the other.  A slot's state byte alternates between the
 // two values the trace kernel knows: ray b waits as kRay1 when b is odd and as kRay2 when b is even, so the launch of one level never
@@ -1765,6 +1845,10 @@ __global__ void __launch_bounds__(kBlock) sq_render_pixels_deep_rays(const Scene
 // recomputed from the sample's seed: one Threefish block per slot that is still alive there (8 % of the slots at b = 2 in the
 // shipped room) moves no byte, where keeping n_3 .. n_{D-1} would write 4 (D - 3) bytes for every slot of the batch.
 struct Deep { int32_t depth, level; int32_t* trail; float2* oxy; long long cap; };
+// Under a sky (the SKY instantiations' further argument; Deep keeps its layout): the sky, and per slot
+//   tmiss : t of the ray that missed (sky_t of its direction as traced), written by sq_deep_bounce where it writes the trail's -1
+//           and read by sq_deep_fold behind that -1.  4 bytes where the radiance would take 12: no radiance travels through HBM.
+struct DeepSky { Sky sky; float* tmiss; };
 
 // Bounce 0 of every sample of the batch: sq_gen_bounce1 without the shared mirror ray (a sample that mirrors gets a ray of its own).
 template <int SRC, typename FrameT>
@@ -1801,8 +1885,8 @@ __global__ void __launch_bounds__(kBlock) sq_deep_gen_rays(const SceneView S, co
 
 // After the trace launch of level b = D.level (1 .. depth - 1): the slot's hit goes into the trail; a miss, the last level, an absorbing
 // surface or a last ray that can reach no emitter finishes the slot, anything else puts ray b + 1 into it.  One thread per active pixel.
-template <int SRC, typename FrameT>
-__device__ __forceinline__ void deep_bounce_body(const SceneView S, const FrameT F, const Work W, int k_base, int k_count, const Deep D) {
+template <int SRC, bool SKY, typename FrameT>
+__device__ __forceinline__ void deep_bounce_body(const SceneView S, const FrameT F, const Work W, int k_base, int k_count, const Deep D, const DeepSky K) {
     const int A = *W.n_active;
     const int b = D.level;
     const uint8_t mine = (b & 1) ? kRay1 : kRay2, next = (b & 1) ? kRay2 : kRay1;
@@ -1819,7 +1903,8 @@ __device__ __forceinline__ void deep_bounce_body(const SceneView S, const FrameT
             const int2 hit = slot_hit(org);
             const int tri = hit.y >= 0 ? hit.y : -1;
             trail_b[sid] = tri;
-            if (tri < 0 || b + 1 >= D.depth) { W.state[sid] = kDone; continue; }   // black below, by a miss or by the depth
+            if constexpr (SKY) { if (tri < 0) { const float4 dm = W.dir[sid]; K.tmiss[sid] = sky_t(sq::mk(dm.x, dm.y, dm.z)); } }
+            if (tri < 0 || b + 1 >= D.depth) { W.state[sid] = kDone; continue; }   // nothing below, by a miss or by the depth
             const Surface sb = surface_of(S, tri);
             if (absorbs(S, sb)) { trail_b[sid + D.cap] = -1; W.state[sid] = kDone; continue; }
             const float4 dir = W.dir[sid];
@@ -1855,8 +1940,11 @@ __device__ __forceinline__ void deep_bounce_body(const SceneView S, const FrameT
     }
 }
 template <bool MV>
-__global__ void __launch_bounds__(kBlock) sq_deep_bounce(const SceneView S, const Frame F, const Work W, int k_base, int k_count, const Deep D) { deep_bounce_body<MV>(S, F, W, k_base, k_count, D); }
-__global__ void __launch_bounds__(kBlock) sq_deep_bounce_rays(const SceneView S, const RayFrame F, const Work W, int k_base, int k_count, const Deep D) { deep_bounce_body<kSrcRays>(S, F, W, k_base, k_count, D); }
+__global__ void __launch_bounds__(kBlock) sq_deep_bounce(const SceneView S, const Frame F, const Work W, int k_base, int k_count, const Deep D) { deep_bounce_body<MV, false>(S, F, W, k_base, k_count, D, DeepSky{}); }
+__global__ void __launch_bounds__(kBlock) sq_deep_bounce_rays(const SceneView S, const RayFrame F, const Work W, int k_base, int k_count, const Deep D) { deep_bounce_body<kSrcRays, false>(S, F, W, k_base, k_count, D, DeepSky{}); }
+template <bool MV>
+__global__ void __launch_bounds__(kBlock) sq_deep_bounce_sky(const SceneView S, const Frame F, const Work W, int k_base, int k_count, const Deep D, const DeepSky K) { deep_bounce_body<MV, true>(S, F, W, k_base, k_count, D, K); }
+__global__ void __launch_bounds__(kBlock) sq_deep_bounce_sky_rays(const SceneView S, const RayFrame F, const Work W, int k_base, int k_count, const Deep D, const DeepSky K) { deep_bounce_body<kSrcRays, true>(S, F, W, k_base, k_count, D, K); }
 
 // The batch's samples folded in order, one thread per active pixel: each sample's radiance is rebuilt from its trail, inside out
 // (path_radiance), and added to the pixel's sums; on the call's last batch the pixel's stores, as sq_accumulate does them.
@@ -1881,7 +1969,43 @@ __global__ void __launch_bounds__(kBlock) sq_deep_fold(const SceneView S, const 
                 for (int b = 1; b < kMaxDepth; ++b) {
                     if (more && b < D.depth) { tr[b] = D.trail[(long long)(b - 1) * D.cap + sid]; more = tr[b] >= 0; }
                 }
-                rad = path_radiance(S, s0, tr);
+                rad = path_radiance(S, s0, tr, sq::mk(0, 0, 0));
+            }
+            sum = sum + rad;
+            if (mom2) sum2 = sum2 + rad * rad;
+        }
+        if (mom2) {
+            if (!last) { W.px_sum2[3 * a] = sum2.x; W.px_sum2[3 * a + 1] = sum2.y; W.px_sum2[3 * a + 2] = sum2.z; }
+            else { float* o = F.sum2 + (long long)W.px_pixel[a] * 3; o[0] = sum2.x; o[1] = sum2.y; o[2] = sum2.z; }
+        }
+        if (!last) { W.px_sum[3 * a] = sum.x; W.px_sum[3 * a + 1] = sum.y; W.px_sum[3 * a + 2] = sum.z; continue; }
+        store_fold(F, W.px_pixel[a], sum);
+    }
+}
+// ... under a sky.  A kernel of its own, the same loop: as a shared template body sq_deep_fold came out with other registers.
+__global__ void __launch_bounds__(kBlock) sq_deep_fold_sky(const SceneView S, const Frame F, const Work W, int k_count, int last, const Deep D, const DeepSky K) {
+    const int A = *W.n_active;
+    const bool mom2 = W.px_sum2 != nullptr;
+    for (int a = blockIdx.x * kBlock + threadIdx.x; a < A; a += gridDim.x * kBlock) {
+        f3 sum = sq::mk(W.px_sum[3 * a], W.px_sum[3 * a + 1], W.px_sum[3 * a + 2]), sum2 = sq::mk(0, 0, 0);
+        if (mom2) sum2 = sq::mk(W.px_sum2[3 * a], W.px_sum2[3 * a + 1], W.px_sum2[3 * a + 2]);
+        const Surface s0 = surface_of(S, W.px_tri0[a]);
+        const f3 rad0 = level0_radiance(s0);
+        const bool flat = D.depth < 2 || absorbs(S, s0);                // every sample ends at level 0: nothing was traced, nothing to read
+        for (int k = 0; k < k_count; ++k) {
+            f3 rad = rad0;
+            if (!flat) {
+                const long long sid = (long long)k * A + a;
+                int tr[kMaxDepth];
+#pragma unroll
+                for (int i = 0; i < kMaxDepth; ++i) tr[i] = -1;
+                bool more = true;
+#pragma unroll
+                for (int b = 1; b < kMaxDepth; ++b) {
+                    if (more && b < D.depth) { tr[b] = D.trail[(long long)(b - 1) * D.cap + sid]; more = tr[b] >= 0; }
+                }
+                // under a sky a -1 is a miss and nothing else (launch_frame turns the shortcuts off): behind it, t of the ray that missed
+                rad = path_radiance(S, s0, tr, more ? sq::mk(0, 0, 0) : sky_at(K.sky, K.tmiss[sid]));
             }
             sum = sum + rad;
             if (mom2) sum2 = sum2 + rad * rad;
@@ -1939,6 +2063,8 @@ struct sq_device_scene {
     // pipeline's (Deep: trail, oxy), allocated by the first deep call that needs it (grow-only; a scene that stays at depth 3 has none)
     int32_t depth = 3; int64_t opt_deep = 0;
     void* d_deep = nullptr; size_t deep_bytes = 0;
+    // caller-given sky (sq_scene_set_sky): host state read by the next call's planning, like the depth; it travels by value (Sky)
+    sq_sky sky{}; bool sky_set = false;
     int64_t opt_pool = 1, opt_refill_min = 12, opt_flush_min = 40, opt_guided = 1, opt_primary_resident = 1, opt_pixel_major = -1, opt_cull = 1, opt_descend_extra = 2, opt_descend_lanes = 16, opt_primary_pooled = 0, opt_coresidency = 0, opt_trace_prio = 0, opt_aux_low_priority = 1, opt_aux_polite = 0, opt_primary_tiles = 1, opt_level1_cull = 1;
 };
 
@@ -2186,12 +2312,13 @@ int ensure_px_sum2(sq_device_scene* s, int64_t pixels) {
     s->px_sum2_cap = pixels;
     return 0;
 }
-// The bytes of Deep a slot takes under depth D: a triangle per bounce level, and from D = 4 on the x and y of the ray's origin.
-size_t deep_slot_bytes(int depth) { return depth < 2 ? 0 : (size_t)(depth - 1) * 4 + (depth >= 4 ? 8 : 0); }
+// The bytes of Deep a slot takes under depth D: a triangle per bounce level, and from D = 4 on the x and y of the ray's origin;
+// under a sky also t of the ray that missed (DeepSky::tmiss), behind the trail.
+size_t deep_slot_bytes(int depth, bool sky) { return depth < 2 ? 0 : (size_t)(depth - 1) * 4 + (depth >= 4 ? 8 : 0) + (sky ? 4 : 0); }
 // The scene's Deep block: room for `slots` slots under `depth` (grow-only, freed as the camera table is: hipFree waits for the device,
 // so a block an enqueued frame still uses is not freed under it).
-int ensure_deep(sq_device_scene* s, int64_t slots, int depth) {
-    const size_t need = (size_t)slots * deep_slot_bytes(depth);
+int ensure_deep(sq_device_scene* s, int64_t slots, int depth, bool sky) {
+    const size_t need = (size_t)slots * deep_slot_bytes(depth, sky);
     if (need <= s->deep_bytes) return 0;
     if (s->d_deep) { SQ_HIP(hipFree(s->d_deep)); s->d_deep = nullptr; s->deep_bytes = 0; }
     if (hipMalloc(&s->d_deep, need) != hipSuccess) { (void)hipGetLastError(); s->d_deep = nullptr; return sq_set_error("hipMalloc(%zu B) for the path trails of depth %d failed", need, depth); }
@@ -2267,6 +2394,10 @@ template <typename StackT, int SRC> struct SrcKernels {
     static constexpr auto render_pixels_deep = &sq_render_pixels_deep<StackT, MV>;
     static constexpr auto deep_gen = &sq_deep_gen<MV>;
     static constexpr auto deep_bounce = &sq_deep_bounce<MV>;
+    static constexpr auto primary_sky = &sq_primary_sky<StackT, MV>;
+    static constexpr auto primary_resident_sky = &sq_primary_resident_sky<StackT, MV>;
+    static constexpr auto render_pixels_deep_sky = &sq_render_pixels_deep_sky<StackT, MV>;
+    static constexpr auto deep_bounce_sky = &sq_deep_bounce_sky<MV>;
 };
 template <typename StackT> struct SrcKernels<StackT, kSrcRays> {
     using FrameT = RayFrame;
@@ -2283,6 +2414,10 @@ template <typename StackT> struct SrcKernels<StackT, kSrcRays> {
     static constexpr auto render_pixels_deep = &sq_render_pixels_deep_rays<StackT>;
     static constexpr auto deep_gen = &sq_deep_gen_rays;
     static constexpr auto deep_bounce = &sq_deep_bounce_rays;
+    static constexpr auto primary_sky = &sq_primary_sky_rays<StackT>;
+    static constexpr auto primary_resident_sky = &sq_primary_resident_sky_rays<StackT>;
+    static constexpr auto render_pixels_deep_sky = &sq_render_pixels_deep_sky_rays<StackT>;
+    static constexpr auto deep_bounce_sky = &sq_deep_bounce_sky_rays;
 };
 // The kernels of one call's wavefront pipeline, chosen once: the ray source's set; in a masked call (single-view frames only: multi-view
 // frames and queries have no masked form) the AD instantiations of the kernels that decide who is active; and sq_accumulate by second
@@ -2294,10 +2429,16 @@ template <typename StackT, int SRC> struct PipelineKernels : SrcKernels<StackT, 
     std::remove_const_t<decltype(K0::primary_gen)> primary_gen = K0::primary_gen;
     void (*primary_store)(Frame, Work, long long);
     void (*accumulate)(SceneView, Frame, Work, int, int);
+    // under a sky (their further argument is the sky): the primary passes whose miss store folds sky(d_0)
+    std::remove_const_t<decltype(K0::primary_sky)> primary_sky = K0::primary_sky;
+    std::remove_const_t<decltype(K0::primary_resident_sky)> primary_resident_sky = K0::primary_resident_sky;
+    void (*primary_store_sky)(Frame, Work, long long, Sky);
     PipelineKernels(bool ad, bool mom2, bool acc_grouped) {
         if constexpr (SRC == kSrcCamera) if (ad) {
             primary_resident = &sq_primary_resident<StackT, false, true>; primary = &sq_primary<StackT, false, true>; primary_gen = &sq_primary_gen<false, true>;
+            primary_resident_sky = &sq_primary_resident_sky<StackT, false, true>; primary_sky = &sq_primary_sky<StackT, false, true>;
         }
+        primary_store_sky = ad ? &sq_primary_store_sky<true> : &sq_primary_store_sky<false>;
         primary_store = ad ? &sq_primary_store<true> : &sq_primary_store<false>;
         accumulate = mom2 ? (acc_grouped ? &sq_accumulate<true, true> : &sq_accumulate<false, true>) : (acc_grouped ? &sq_accumulate<true> : &sq_accumulate<false>);
     }
@@ -2370,9 +2511,9 @@ int plan_trace(sq_device_scene* s, const SceneView& S, int stack_cap, TracePlan&
         // ResidentTris takes a vertex's byte offset for its LDS address: the vertex table must sit at LDS address 0, i.e. the
         // kernels that stage a resident scene must own no static __shared__ (their dynamic LDS then starts at 0).  Checked here,
         // where a violation is an error code, rather than by the device-side trap, where it would be a GPU abort.
-        const void* fns[5] = { (const void*)sq_trace_rays<StackT, true, kResidentBlock, false, true>, (const void*)sq_trace_rays<StackT, true, kResidentBlock, true, true>,
+        const void* fns[6] = { (const void*)sq_trace_rays<StackT, true, kResidentBlock, false, true>, (const void*)sq_trace_rays<StackT, true, kResidentBlock, true, true>,
                                (const void*)sq_trace_rays<StackT, true, kResidentBlock, false, false>, (const void*)sq_trace_rays<StackT, true, kResidentBlock, true, false>,
-                               (const void*)SrcKernels<StackT, SRC>::primary_resident };
+                               (const void*)SrcKernels<StackT, SRC>::primary_resident, (const void*)SrcKernels<StackT, SRC>::primary_resident_sky };
         for (const void* fn : fns) {
             hipFuncAttributes attr{};
             SQ_HIP(hipFuncGetAttributes(&attr, fn));
@@ -2440,6 +2581,12 @@ int launch_frame(sq_device_scene* s, const typename SrcKernels<StackT, SRC>::Fra
     // one of which may be inf where the bound still held: 0 * inf is NaN in the reference, so past the packer's shortcut_depth
     // (sq_host.cpp, material_flags) the generic-depth kernels of this launch take no s == 0 shortcut.
     if (!F.cast && s->depth > 3 && s->depth > s->shortcut_depth) S.nonneg_materials = 0;
+    // Under a sky neither the absorbing-surface shortcut nor the last ray's emitter pre-test is an identity as it stands (the last ray
+    // adds the sky when it misses; 0 * sky is NaN for an infinite sky): this launch's generic-depth kernels take neither.
+    const bool sky = !F.cast && s->sky_set;
+    if (sky) { S.nonneg_materials = 0; S.n_emitters = -1; s->plan.n_emitters = -1; }
+    Sky KS{};
+    if (sky) { std::memcpy(KS.up, s->sky.up, sizeof KS.up); std::memcpy(KS.down, s->sky.down, sizeof KS.down); }
     sq_plan& P = s->plan;
     const long long pixels = (long long)F.n_views * F.local_rows * F.h;   // every view's pixels, view-major
     const long long px_blocks = (pixels + kBlock - 1) / kBlock;
@@ -2454,7 +2601,7 @@ int launch_frame(sq_device_scene* s, const typename SrcKernels<StackT, SRC>::Fra
     const int n_lights = (int)s->lights.size();
     // a path-traced frame or query under a depth other than 3 (or under option "deep"): the generic-depth kernels
     const int depth = s->depth;
-    const bool deep = !F.cast && (depth != 3 || s->opt_deep);
+    const bool deep = !F.cast && (depth != 3 || s->opt_deep || sky);
     if (F.cast && !cast_wave && s->lights_set) {                       // caller-given lights, per-lane: sq_cast_pixels beside sq_render_pixels
         auto cast_pixels = SrcKernels<StackT, SRC>::cast_pixels;
         if constexpr (SRC == kSrcCamera) if (ad) cast_pixels = &sq_cast_pixels<StackT, false, true>;
@@ -2463,6 +2610,14 @@ int launch_frame(sq_device_scene* s, const typename SrcKernels<StackT, SRC>::Fra
         if (stage_cams(s, F, cams, stream)) return 1;
         const Lights L{ s->d_lights, n_lights, nullptr, 0, n_lights };
         return timed_launch(s, [&] { hipLaunchKernelGGL(cast_pixels, dim3((unsigned)px_blocks), dim3(kBlock), px_lds, stream, S, F, L); }, "sq_cast_pixels", stream);
+    }
+    if (s->opt_variant == 1 && sky) {                                   // per-lane under a sky
+        auto render_sky = SrcKernels<StackT, SRC>::render_pixels_deep_sky;
+        if constexpr (SRC == kSrcCamera) if (ad) render_sky = &sq_render_pixels_deep_sky<StackT, false, true>;
+        if (px_lds > 64 * 1024) SQ_HIP(hipFuncSetAttribute((const void*)render_sky, hipFuncAttributeMaxDynamicSharedMemorySize, (int)px_lds));
+        P.launched = 1;
+        if (stage_cams(s, F, cams, stream)) return 1;
+        return timed_launch(s, [&] { hipLaunchKernelGGL(render_sky, dim3((unsigned)px_blocks), dim3(kBlock), px_lds, stream, S, F, depth, KS); }, "sq_render_pixels_deep_sky", stream);
     }
     if (s->opt_variant == 1 && deep) {                                  // per-lane: sq_render_pixels_deep beside sq_render_pixels
         auto render_deep = SrcKernels<StackT, SRC>::render_pixels_deep;
@@ -2522,7 +2677,7 @@ int launch_frame(sq_device_scene* s, const typename SrcKernels<StackT, SRC>::Fra
     if (P.primary_form == SQ_PRIMARY_PER_LANE && (primary_padded(F) * F.n_views + kBlock - 1) / kBlock * kBlock > 0xffffffffLL)
         return sq_set_error("image too large for one launch of the primary rays (%lld tile lanes; at most 2^32 - 1)", primary_padded(F) * F.n_views);
     if (cast_wave && ensure_light_table(s)) return 1;
-    if (deep && ensure_deep(s, W.slot_capacity, depth)) return 1;
+    if (deep && ensure_deep(s, W.slot_capacity, depth, sky)) return 1;
     P.launched = 1;                                                    // planned; what follows fails only on HIP errors
     // nothing is enqueued before this point, so a refusal above leaves every buffer as it was
     if (stage_cams(s, F, cams, stream)) return 1;                       // multi-view: before every kernel that reads the table (e_setup below)
@@ -2538,12 +2693,14 @@ int launch_frame(sq_device_scene* s, const typename SrcKernels<StackT, SRC>::Fra
     // primary rays: once per pixel.  With a resident scene they are traced out of LDS as well ...
     if (P.primary_form == SQ_PRIMARY_RESIDENT) {
         const TraceLds Lp = trace_lds_layout(S.n_branches, true, S.n_verts, S.n_tris, kResidentBlock, stack_cap, (int)sizeof(StackT), false);
-        SQ_HIP(hipFuncSetAttribute((const void*)K.primary_resident, hipFuncAttributeMaxDynamicSharedMemorySize, (int)Lp.total));
+        SQ_HIP(hipFuncSetAttribute(sky ? (const void*)K.primary_resident_sky : (const void*)K.primary_resident, hipFuncAttributeMaxDynamicSharedMemorySize, (int)Lp.total));
         const long long need = (primary_padded(F) * F.n_views + kResidentBlock - 1) / kResidentBlock;
-        hipLaunchKernelGGL(K.primary_resident, dim3((unsigned)std::min<long long>(s->n_cu, need)), dim3(kResidentBlock), Lp.total, stream, S, F, W, stack_cap);
+        if (sky) hipLaunchKernelGGL(K.primary_resident_sky, dim3((unsigned)std::min<long long>(s->n_cu, need)), dim3(kResidentBlock), Lp.total, stream, S, F, W, stack_cap, KS);
+        else hipLaunchKernelGGL(K.primary_resident, dim3((unsigned)std::min<long long>(s->n_cu, need)), dim3(kResidentBlock), Lp.total, stream, S, F, W, stack_cap);
     } else if (P.primary_form == SQ_PRIMARY_PER_LANE) {
-        if (px_lds > 64 * 1024) SQ_HIP(hipFuncSetAttribute((const void*)K.primary, hipFuncAttributeMaxDynamicSharedMemorySize, (int)px_lds));
-        hipLaunchKernelGGL(K.primary, dim3((unsigned)((primary_padded(F) * F.n_views + kBlock - 1) / kBlock)), dim3(kBlock), px_lds, stream, S, F, W);
+        if (px_lds > 64 * 1024) SQ_HIP(hipFuncSetAttribute(sky ? (const void*)K.primary_sky : (const void*)K.primary, hipFuncAttributeMaxDynamicSharedMemorySize, (int)px_lds));
+        if (sky) hipLaunchKernelGGL(K.primary_sky, dim3((unsigned)((primary_padded(F) * F.n_views + kBlock - 1) / kBlock)), dim3(kBlock), px_lds, stream, S, F, W, KS);
+        else hipLaunchKernelGGL(K.primary, dim3((unsigned)((primary_padded(F) * F.n_views + kBlock - 1) / kBlock)), dim3(kBlock), px_lds, stream, S, F, W);
     }
     SQ_HIP(hipGetLastError());
     // per-sample kernels that run one thread per active pixel: x covers the pixels, y splits a pixel's samples when the
@@ -2564,7 +2721,8 @@ int launch_frame(sq_device_scene* s, const typename SrcKernels<StackT, SRC>::Fra
         hipLaunchKernelGGL(K.primary_gen, dim3(aux_blocks), dim3(kBlock), 0, stream, F, W, pixels);
         SQ_HIP(hipGetLastError());
         if (launch_trace_kernel(s, S, TP, Wp, pixels, 1, 0, stream, false)) return 1;
-        hipLaunchKernelGGL(K.primary_store, dim3(aux_blocks), dim3(kBlock), 0, stream, F, W, pixels);
+        if (sky) hipLaunchKernelGGL(K.primary_store_sky, dim3(aux_blocks), dim3(kBlock), 0, stream, F, W, pixels, KS);
+        else hipLaunchKernelGGL(K.primary_store, dim3(aux_blocks), dim3(kBlock), 0, stream, F, W, pixels);
         SQ_HIP(hipGetLastError());
     }
     if (cast_wave) {
@@ -2588,6 +2746,7 @@ int launch_frame(sq_device_scene* s, const typename SrcKernels<StackT, SRC>::Fra
         const long long cap = (long long)W.slot_capacity;
         float2* const oxy = (float2*)s->d_deep;
         int32_t* const trail = (int32_t*)((char*)s->d_deep + (depth >= 4 ? (size_t)cap * sizeof(float2) : 0));
+        const DeepSky DS{ KS, sky && depth >= 2 ? (float*)(trail + (size_t)(depth - 1) * cap) : nullptr };
         for (int i = 0; i * batch < n_call; ++i) {
             const int k0 = F.k_begin + i * batch, kc = std::min(batch, n_call - i * batch);
             if (depth >= 2) {
@@ -2599,11 +2758,13 @@ int launch_frame(sq_device_scene* s, const typename SrcKernels<StackT, SRC>::Fra
                 const Deep D{ depth, b, trail, oxy, cap };
                 if (b >= 3) SQ_HIP(hipMemsetAsync(W.head[0], 0, 32 * sizeof(int32_t), stream));   // a cursor's second use
                 if (launch_trace_kernel(s, S, TP, W, pixels, kc, (b - 1) & 1, stream, false)) return 1;
-                hipLaunchKernelGGL((SrcKernels<StackT, SRC>::deep_bounce), pp_grid(kc), dim3(kBlock), 0, stream, S, F, W, k0, kc, D);
+                if (sky) hipLaunchKernelGGL((SrcKernels<StackT, SRC>::deep_bounce_sky), pp_grid(kc), dim3(kBlock), 0, stream, S, F, W, k0, kc, D, DS);
+                else hipLaunchKernelGGL((SrcKernels<StackT, SRC>::deep_bounce), pp_grid(kc), dim3(kBlock), 0, stream, S, F, W, k0, kc, D);
                 SQ_HIP(hipGetLastError());
             }
             const Deep D{ depth, 0, trail, oxy, cap };
-            hipLaunchKernelGGL(sq_deep_fold, dim3(aux_blocks), dim3(kBlock), 0, stream, S, F, W, kc, (i + 1) * batch >= n_call ? 1 : 0, D);
+            if (sky) hipLaunchKernelGGL(sq_deep_fold_sky, dim3(aux_blocks), dim3(kBlock), 0, stream, S, F, W, kc, (i + 1) * batch >= n_call ? 1 : 0, D, DS);
+            else hipLaunchKernelGGL(sq_deep_fold, dim3(aux_blocks), dim3(kBlock), 0, stream, S, F, W, kc, (i + 1) * batch >= n_call ? 1 : 0, D);
             SQ_HIP(hipGetLastError());
         }
         return 0;
@@ -3122,6 +3283,18 @@ extern "C" int sq_scene_set_depth(sq_device_scene* s, int32_t depth) {
 extern "C" int32_t sq_scene_get_depth(sq_device_scene* s) {
     if (!s) { sq_set_error("null argument"); return -1; }
     return s->depth;
+}
+
+extern "C" int sq_scene_set_sky(sq_device_scene* s, const sq_sky* sky) {
+    if (!s) return sq_set_error("null argument");
+    if (sky) s->sky = *sky;
+    s->sky_set = sky != nullptr;
+    return 0;
+}
+extern "C" int sq_scene_get_sky(sq_device_scene* s, sq_sky* out) {
+    if (!s) { sq_set_error("null argument"); return -1; }
+    if (s->sky_set && out) *out = s->sky;
+    return s->sky_set ? 1 : 0;
 }
 
 extern "C" int64_t sq_scene_rng_table(sq_device_scene* s, int64_t first, int64_t count, uint32_t* out_words) {

@@ -139,6 +139,29 @@ class DeviceScene:
             raise N.SquiglyError(N.lib().sq_last_error().decode(errors="replace"))
         return int(d)
 
+    def set_sky(self, up, down=None):
+        """The sky of the scene's path-traced frames and raytrace queries (sq_scene_set_sky): the radiance of a ray that leaves
+        the scene, `up` seen looking along +z and `down` along -z (three numbers each; down = None: a constant sky, down = up).
+        set_sky(None) resets the scene to no sky, the reference's black.  Host state that the next call reads: nothing is
+        enqueued.  Cast frames and raycast ignore it."""
+        if up is None:
+            if down is not None:
+                raise N.SquiglyError("set_sky(None) resets the sky and takes no down")
+            N.check(N.lib().sq_scene_set_sky(self._h, None))
+            return
+        table = N.sky_value(up, down)                                   # refused before any device work
+        N.check(N.lib().sq_scene_set_sky(self._h, table.ctypes.data))
+
+    @property
+    def sky(self):
+        """The scene's sky (sq_scene_get_sky): None, or (up, down), two tuples of three floats."""
+        import numpy as np
+        out = np.zeros((2, 3), np.float32)
+        r = N.lib().sq_scene_get_sky(self._h, out.ctypes.data)
+        if r < 0:
+            raise N.SquiglyError(N.lib().sq_last_error().decode(errors="replace"))
+        return None if r == 0 else (tuple(float(v) for v in out[0]), tuple(float(v) for v in out[1]))
+
     def rng_table(self, first=0, count=0):
         """sq_scene_rng_table: (seeds the scene's table of generator words holds, its entries [first, first + count) as a uint32
         numpy array [count, 3])."""
@@ -462,6 +485,32 @@ def _same_depth(frame):
         raise N.SquiglyError(f"the frame was begun under depth {frame.depth}, the scene now has depth {have}")
 
 
+SCENE_SKY = object()     # sky= of Progressive / Adaptive: a fresh frame, which runs under the scene's sky whatever it is
+
+
+def _sky_bits(sky):
+    """A sky as bytes, so that two skies are the same when their bits are (a NaN component equals itself); None = no sky."""
+    pair = N.sky_pair(sky)
+    return None if pair is None else pair.tobytes()
+
+
+def _checkpoint_sky(dscene, sky):
+    """The sky a Progressive / Adaptive frame runs under: the scene's.  sky: SCENE_SKY for a fresh frame, else what a checkpoint
+    carried (None = no sky); SquiglyError when the scene has another."""
+    have = dscene.sky
+    if sky is not SCENE_SKY and _sky_bits(sky) != _sky_bits(have):
+        raise N.SquiglyError(f"the checkpoint was rendered under the sky {sky!r}, the scene has {have!r}: set_sky first")
+    return have
+
+
+def _same_sky(frame):
+    if frame.cast:
+        return
+    have = frame.dscene.sky
+    if _sky_bits(have) != _sky_bits(frame.sky):
+        raise N.SquiglyError(f"the frame was begun under the sky {frame.sky!r}, the scene now has {have!r}")
+
+
 class Progressive:
     """A frame rendered a few samples at a time (DeviceScene.render_rows_range), bit-exact to one render_rows call.
 
@@ -470,10 +519,12 @@ class Progressive:
     `done` samples; to checkpoint, copy `sums` and `done` away, and pass them back in to resume, in this process or another.  A checkpoint
     also carries `depth`, the scene's path depth when the frame began: pass it back in as depth=, and a scene under another depth
     refuses to resume it (a fold that mixes depths is no frame); so does step() once the scene's depth was changed under the frame.
-    A cast frame has no paths: its `depth` is None and it ignores the scene's.
+    A cast frame has no paths: its `depth` is None and it ignores the scene's.  The scene's sky (DeviceScene.set_sky) is treated
+    exactly like the depth: `sky` records it (None or (up, down)), a checkpoint passes it back in as sky=, and a scene under
+    another sky refuses to resume or to step.
     """
 
-    def __init__(self, dscene, cam, samples, w, h, cast=False, shard=(None, 0, 1), sums=None, done=0, depth=None):
+    def __init__(self, dscene, cam, samples, w, h, cast=False, shard=(None, 0, 1), sums=None, done=0, depth=None, sky=SCENE_SKY):
         samples, done = int(samples), int(done)
         if samples < 1:
             raise ValueError(f"samples must be positive, got {samples}")
@@ -485,6 +536,7 @@ class Progressive:
             raise N.SquiglyError(f"bad shard {shard}")
         _check_frame_size(dscene, rows, h, cast)
         self.depth = None if cast else _checkpoint_depth(dscene, depth)      # a cast frame has no paths: it ignores the depth
+        self.sky = None if cast else _checkpoint_sky(dscene, sky)            # ... and the sky
         dev = torch.device("cuda", dscene.device)
         if sums is None:
             if done:
@@ -519,6 +571,7 @@ class Progressive:
         if int(n) < 1:
             raise ValueError(f"a step renders at least one sample, got {n}")
         _same_depth(self)
+        _same_sky(self)
         k_end = min(self._done + int(n), self.samples)
         avg, rgb = self.dscene.render_rows_range(self.cam, self.samples, self.w, self.h, self._done, k_end, self._sums,
                                                  cast=self.cast, shard=self.shard, stream=stream)
@@ -555,11 +608,11 @@ class Adaptive:
     the built-in rule (DeviceScene.adaptive_update with tol, eps), which is a heuristic -- a pixel that has seen nothing but
     black after `first` samples stops.  A pixel the rule switches back on after it was left out of a range stays out: its
     fold would have a gap.  To checkpoint, copy the four tensors, `done` and `depth` away and pass them back in (depth as in
-    Progressive: a scene under another path depth refuses to resume).
+    Progressive: a scene under another path depth refuses to resume), and `sky` likewise as sky=.
     """
 
     def __init__(self, dscene, cam, samples, w, h, tol, eps=1.0, first=8, step=8, cast=False, shard=(None, 0, 1), rule=None,
-                 sums=None, sums2=None, counts=None, mask=None, done=0, depth=None):
+                 sums=None, sums2=None, counts=None, mask=None, done=0, depth=None, sky=SCENE_SKY):
         samples, done, first, step = int(samples), int(done), int(first), int(step)
         tol, eps = float(tol), float(eps)
         if samples < 1:
@@ -580,6 +633,7 @@ class Adaptive:
             raise N.SquiglyError(f"bad shard {shard}")
         _check_frame_size(dscene, rows, h, cast)
         self.depth = None if cast else _checkpoint_depth(dscene, depth)      # a cast frame has no paths: it ignores the depth
+        self.sky = None if cast else _checkpoint_sky(dscene, sky)            # ... and the sky
         dev = torch.device("cuda", dscene.device)
 
         def adopt(name, t, shape, dtype, fill):   # a matching CUDA tensor as it is; a host copy is copied to the device
@@ -645,6 +699,7 @@ class Adaptive:
             raise RuntimeError("the frame is finished: no pixel is live" if self._live == 0
                                else f"the frame is finished: all {self.samples} samples are rendered")
         _same_depth(self)
+        _same_sky(self)
         k_end = min(self._done + (self.first if self._done == 0 else self.step_size), self.samples)
         self.dscene.render_rows_masked(self.cam, self.samples, self.w, self.h, self._done, k_end, self._sums, mask=self._mask,
                                        sums2=self._sums2, counts=self._counts, cast=self.cast, shard=self.shard, stream=stream,

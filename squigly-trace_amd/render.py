@@ -43,24 +43,29 @@ def render_f32(bih, cam, samples, dimensions, cast=False) -> np.ndarray:
     return out
 
 
-def render_progressive(bih, cam, samples, dimensions, step, cast=False, device=0, lights=None, depth=None):
+def render_progressive(bih, cam, samples, dimensions, step, cast=False, device=0, lights=None, depth=None, sky=None):
     """The frame of render_rgb8, `step` samples at a time: yields (done, rgb8) after every step, rgb8 being the (w, h, 3) uint8
     image of the first `done` samples.  The last image (done == samples) is bit for bit that of render_rgb8 (DeviceScene,
     Progressive: one device, the scene uploaded once).  lights: the point lights of a cast frame (DeviceScene.set_lights; None = the
     reference's light).  depth: the path depth of a path-traced frame (DeviceScene.set_depth; None = the reference's 3, which is
-    what render_rgb8 computes); a depth is refused before anything is uploaded when it is not an integer in 1..8."""
+    what render_rgb8 computes); a depth is refused before anything is uploaded when it is not an integer in 1..8.  sky: the sky of a
+    path-traced frame (DeviceScene.set_sky): three numbers (a constant sky) or (up, down); None = no sky, the reference's black.
+    Refused before anything is uploaded when it is neither."""
     from .device import DeviceScene, Progressive       # torch: only the resident-scene path needs it
     w, h = dimensions
     if int(step) < 1:
         raise ValueError(f"step must be positive, got {step}")
     if depth is not None:
         N.depth_value(depth)
+    sky = N.sky_pair(sky)
     ds = DeviceScene(bih, device)
     try:
         if lights is not None:
             ds.set_lights(lights)
         if depth is not None:
             ds.set_depth(depth)
+        if sky is not None:
+            ds.set_sky(sky[0], sky[1])
         p = Progressive(ds, cam, samples, w, h, cast=cast)
         while not p.finished:
             _, rgb = p.step(step)
@@ -70,11 +75,11 @@ def render_progressive(bih, cam, samples, dimensions, step, cast=False, device=0
 
 
 def render_adaptive(bih, cam, samples, dimensions, tol, eps=1.0, first=8, step=8, cast=False, device=0, rule=None, lights=None,
-                    depth=None):
+                    depth=None, sky=None):
     """The frame of render_rgb8 with adaptive sampling (DeviceScene, Adaptive): yields (done, live, spent, rgb8, counts) after
     every step -- the end of the range rendered, the pixels still live, the samples spent so far, the (w, h, 3) uint8 image and
     the (w, h) int32 per-pixel sample counts.  A pixel that stopped after n samples shows the mean of its first n samples, so
-    with first >= samples (one step, every pixel live) the image is bit for bit that of render_rgb8.  lights, depth: as in
+    with first >= samples (one step, every pixel live) the image is bit for bit that of render_rgb8.  lights, depth, sky: as in
     render_progressive."""
     from .device import Adaptive, DeviceScene          # torch: only the resident-scene path needs it
     w, h = dimensions
@@ -84,12 +89,15 @@ def render_adaptive(bih, cam, samples, dimensions, tol, eps=1.0, first=8, step=8
         raise ValueError(f"tol and eps must be numbers >= 0, got {tol}, {eps}")
     if depth is not None:
         N.depth_value(depth)
+    sky = N.sky_pair(sky)
     ds = DeviceScene(bih, device)
     try:
         if lights is not None:
             ds.set_lights(lights)
         if depth is not None:
             ds.set_depth(depth)
+        if sky is not None:
+            ds.set_sky(sky[0], sky[1])
         a = Adaptive(ds, cam, samples, w, h, tol, eps=eps, first=first, step=step, cast=cast, rule=rule)
         while not a.finished:
             _, rgb = a.step()
@@ -98,14 +106,16 @@ def render_adaptive(bih, cam, samples, dimensions, tol, eps=1.0, first=8, step=8
         ds.close()
 
 
-def render_views_rgb8(bih, cams, samples, dimensions, cast=False, device=0, lights=None, depth=None) -> np.ndarray:
+def render_views_rgb8(bih, cams, samples, dimensions, cast=False, device=0, lights=None, depth=None, sky=None) -> np.ndarray:
     """The image of render_rgb8 for every camera of `cams`, rendered in one call (DeviceScene.render_views): shape (n, w, h, 3)
-    uint8, view i bit for bit render_rgb8 of cams[i].  lights, depth: as in render_progressive (every view has the same lights and depth)."""
+    uint8, view i bit for bit render_rgb8 of cams[i].  lights, depth, sky: as in render_progressive (every view has the same lights, depth
+    and sky)."""
     cams = list(cams)
     if not cams:
         raise ValueError("render_views_rgb8 needs at least one camera")
     if depth is not None:
         N.depth_value(depth)
+    sky = N.sky_pair(sky)
     import torch
     from .device import DeviceScene
     w, h = dimensions
@@ -115,6 +125,8 @@ def render_views_rgb8(bih, cams, samples, dimensions, cast=False, device=0, ligh
             ds.set_lights(lights)
         if depth is not None:
             ds.set_depth(depth)
+        if sky is not None:
+            ds.set_sky(sky[0], sky[1])
         _, rgb = ds.render_views(cams, samples, w, h, cast=cast, want_avg=False)
         torch.cuda.synchronize(ds.device)
         return rgb.cpu().numpy()
