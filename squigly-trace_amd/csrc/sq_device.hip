@@ -18,8 +18,8 @@
 // Every value is computed by the same fp32 expression tree as the reference.
 // The one-lane-per-pixel kernel sq_render_pixels serves raycast mode and is a cross-check variant.
 // Radiance queries (sq_raytrace_rays_device, sq_raycast_rays_device: Lib.raytrace / Lib.raycast of caller-given rays, src/Lib.hs:127-151)
-// run the same pipeline from a third ray source: the sq_*_rays kernels read origin, direction and seed base from the caller's arrays
-// where the frames' kernels read the camera.
+// run the same pipeline from a third ray source: the kernels' kSrcRays instantiations read origin, direction and seed base from the caller's
+// arrays where the frames' instantiations read the camera.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -88,7 +88,7 @@ struct Frame {
     int32_t k_begin, k_end;
     float* sum;
     int32_t diag;             // option "coresidency": the per-sample kernels and the trace kernel count who runs beside whom (sq_get_stats 24..27)
-    // multi-view frames (sq_render_views_device, the kernels' MV instantiations): n_views views of view_pixels = local_rows * h pixels,
+    // multi-view frames (sq_render_views_device, the kernels' kSrcViews instantiations): n_views views of view_pixels = local_rows * h pixels,
     // view-major, so a pixel index runs over [0, n_views * view_pixels); cams = the scene's camera table, kCamWords floats per view
     // (pos, rot).  A single-view frame has n_views = 1 and reads cam_pos / cam_rot.
     int32_t n_views, view_pixels;
@@ -107,9 +107,9 @@ struct RayFrame : Frame {
     const float* ray_org; const float* ray_dir; const long long* ray_seed;
 };
 // Where a kernel's primary rays come from: the frame's camera (makeRay, src/Lib.hs:107-114), the camera table of a multi-view frame,
-// or the caller's arrays.  The kernels that exist for frames keep their bool MV (false = kSrcCamera, true = kSrcViews: a bool template
-// argument converts to these very values); the query kernels (sq_*_rays) instantiate the same bodies with kSrcRays.
+// or the caller's arrays.  Every kernel family is one __global__ template keyed by it ("One entry point per body"): FrameOf<SRC> is the frame it takes.
 constexpr int kSrcCamera = 0, kSrcViews = 1, kSrcRays = 2;
+template <int SRC> using FrameOf = std::conditional_t<SRC == kSrcRays, RayFrame, Frame>;
 constexpr int kCamWords = 12;     // a view's entry in the camera table: pos[3], rot[9]
 struct ViewCam { f3 pos; float rot[9]; };
 // The camera of view v.  UNIFORM: v is the same in every lane of the wave (a primary-ray tile), so the 48 bytes come through scalar loads.
@@ -218,6 +218,10 @@ __device__ __forceinline__ void store_live_miss(const Frame& F, long long pix) {
 // ----------------------------------------------------------------------------------------------
 // The kernels' SKY instantiations take it by value; every other instantiation is handed an empty one and reads nothing of it.
 struct Sky { float up[3], down[3]; };
+// A kernel under a sky takes it as a trailing argument pack of one (Sky, or DeepSky in the generic-depth pipeline); without a sky the
+// pack is empty, the kernel has no such argument, and its body is handed an empty value of the type.
+template <typename T> __device__ __forceinline__ T sky_arg() { return T{}; }
+template <typename T> __device__ __forceinline__ const T& sky_arg(const T& k) { return k; }
 // t of a ray's direction as it was traced (not normalised beforehand): every operation a single fp32 operation in this order.
 __device__ __forceinline__ float sky_t(f3 d) {
     const float n = sq::fsqrt((d.x * d.x + d.y * d.y) + d.z * d.z);
@@ -252,7 +256,7 @@ __device__ __forceinline__ void store_miss_sky(const Frame& F, long long pix, co
 // MV: a multi-view frame (pixels are enumerated linearly, so the lanes of a wave may belong to two views: per-lane camera reads)
 // AD: a masked call (single-view): dead pixels leave before the first ray -- nothing wave-wide follows, every lane walks alone --
 // and live ones also fold r * r and store their count.
-// SRC = kSrcRays (sq_render_pixels_rays): lane i takes the caller's ray i and seed base; its cast branch is raycast itself, not a fold.
+// SRC = kSrcRays: lane i takes the caller's ray i and seed base; its cast branch is raycast itself, not a fold.
 template <typename StackT, int SRC, bool AD, typename FrameT>
 __device__ __forceinline__ void render_pixels_body(const SceneView& S, const FrameT& F) {
     constexpr bool MV = SRC == kSrcViews;
@@ -329,10 +333,8 @@ __device__ __forceinline__ void render_pixels_body(const SceneView& S, const Fra
     if (F.out_avg) { float* o = F.out_avg + pix * 3; o[0] = avg.x; o[1] = avg.y; o[2] = avg.z; }
     if (F.out_rgb) tonemap(avg, F.out_rgb + pix * 3);
 }
-template <typename StackT, bool MV, bool AD = false>
-__global__ void __launch_bounds__(kBlock) sq_render_pixels(const SceneView S, const Frame F) { render_pixels_body<StackT, MV, AD>(S, F); }
-template <typename StackT>
-__global__ void __launch_bounds__(kBlock) sq_render_pixels_rays(const SceneView S, const RayFrame F) { render_pixels_body<StackT, kSrcRays, false>(S, F); }
+template <typename StackT, int SRC, bool AD>
+__global__ void __launch_bounds__(kBlock) sq_render_pixels(const SceneView S, const FrameOf<SRC> F) { render_pixels_body<StackT, SRC, AD>(S, F); }
 
 // ----------------------------------------------------------------------------------------------
 // Variant 2 (default): wavefront pipeline
@@ -460,14 +462,10 @@ __device__ __forceinline__ void primary_body(const SceneView& S, const FrameT& F
     if (a >= 0) store_active<AD>(F, W, a, pix, h0.t, h0.tri);
     else if (in) { if constexpr (SKY) store_miss_sky<AD>(F, pix, K, d0); else store_miss<AD>(F, pix); }
 }
-template <typename StackT, bool MV, bool AD = false>
-__global__ void __launch_bounds__(kBlock) sq_primary(const SceneView S, const Frame F, const Work W) { primary_body<StackT, MV, AD, false>(S, F, W, Sky{}); }
-template <typename StackT>
-__global__ void __launch_bounds__(kBlock) sq_primary_rays(const SceneView S, const RayFrame F, const Work W) { primary_body<StackT, kSrcRays, false, false>(S, F, W, Sky{}); }
-template <typename StackT, bool MV, bool AD = false>
-__global__ void __launch_bounds__(kBlock) sq_primary_sky(const SceneView S, const Frame F, const Work W, const Sky K) { primary_body<StackT, MV, AD, true>(S, F, W, K); }
-template <typename StackT>
-__global__ void __launch_bounds__(kBlock) sq_primary_sky_rays(const SceneView S, const RayFrame F, const Work W, const Sky K) { primary_body<StackT, kSrcRays, false, true>(S, F, W, K); }
+template <typename StackT, int SRC, bool AD, typename... SkyT>
+__global__ void __launch_bounds__(kBlock) sq_primary(const SceneView S, const FrameOf<SRC> F, const Work W, const SkyT... K) {
+    primary_body<StackT, SRC, AD, sizeof...(SkyT) != 0>(S, F, W, sky_arg<Sky>(K...));
+}
 
 struct Pixel0 { f3 p0, d0; Surface s0; int y, x; };
 // Everything the kernels downstream of the primary pass know about active pixel a, and the one place where they learn it.
@@ -688,9 +686,8 @@ __device__ __forceinline__ void gen_bounce1_body(const SceneView& S, const Frame
 // Four waves per SIMD (118 VGPRs, no scratch): with the level-1 culling test inlined, six (80 VGPRs) spill 38 registers and five
 // (96) spill 22; the headline frame measured 43.2 / 42.1 / 41.7 ms at six / five / four
 constexpr int kGen1Waves = 4;
-template <bool MV>
-__global__ void __launch_bounds__(kBlock, kGen1Waves) sq_gen_bounce1(const SceneView S, const Frame F, const Work W, int k_base, int k_count, const RngView R, const Level1Cull C) { gen_bounce1_body<MV>(S, F, W, k_base, k_count, R, C); }
-__global__ void __launch_bounds__(kBlock, kGen1Waves) sq_gen_bounce1_rays(const SceneView S, const RayFrame F, const Work W, int k_base, int k_count, const RngView R, const Level1Cull C) { gen_bounce1_body<kSrcRays>(S, F, W, k_base, k_count, R, C); }
+template <int SRC>
+__global__ void __launch_bounds__(kBlock, kGen1Waves) sq_gen_bounce1(const SceneView S, const FrameOf<SRC> F, const Work W, int k_base, int k_count, const RngView R, const Level1Cull C) { gen_bounce1_body<SRC>(S, F, W, k_base, k_count, R, C); }
 
 // The depth-0 mirror ray of every active pixel, once per frame (slot a = active pixel a).
 // `base`: first of the *n_active slots the mirror rays use (0 when they have a launch of their own, the spare region
@@ -708,9 +705,8 @@ __device__ __forceinline__ void mirror1_gen_body(const SceneView& S, const Frame
         W.dir[sl] = make_float4(d1.x, d1.y, d1.z, 0.0f);
     }
 }
-template <bool MV>
-__global__ void __launch_bounds__(kBlock) sq_mirror1_gen(const SceneView S, const Frame F, const Work W, long long base) { mirror1_gen_body<MV>(S, F, W, base); }
-__global__ void __launch_bounds__(kBlock) sq_mirror1_gen_rays(const SceneView S, const RayFrame F, const Work W, long long base) { mirror1_gen_body<kSrcRays>(S, F, W, base); }
+template <int SRC>
+__global__ void __launch_bounds__(kBlock) sq_mirror1_gen(const SceneView S, const FrameOf<SRC> F, const Work W, long long base) { mirror1_gen_body<SRC>(S, F, W, base); }
 __global__ void __launch_bounds__(kBlock) sq_mirror1_store(const Work W, long long base) {
     const int A = *W.n_active;
     for (int a = blockIdx.x * kBlock + threadIdx.x; a < A; a += gridDim.x * kBlock) {
@@ -726,19 +722,26 @@ __global__ void __launch_bounds__(kBlock) sq_mirror1_store(const Work W, long lo
 // sq_primary(_resident) lasts as long as its most expensive wave (64 neighbouring pixels on dense geometry: 0.5 ms on the headline
 // scene however small the shard); the pooled leaf phase walks such a wave faster.  W.n_active[48] is the launch's queue length.
 // AD: a dead pixel's slot is flagged kDone, so it is not in the launch's queue and sq_primary_store skips it.
-template <bool MV, bool AD = false>
-__global__ void __launch_bounds__(kBlock) sq_primary_gen(const Frame F, const Work W, long long total) {
+// kSrcRays: the caller's rays as they are.
+template <int SRC, bool AD>
+__global__ void __launch_bounds__(kBlock) sq_primary_gen(const FrameOf<SRC> F, const Work W, long long total) {
     if (blockIdx.x == 0 && threadIdx.x == 0) W.n_active[48] = (int32_t)total;
     for (long long pix = (long long)blockIdx.x * kBlock + threadIdx.x; pix < total; pix += (long long)gridDim.x * kBlock) {
-        int y, x;
         if constexpr (AD) { if (!pixel_live(F, pix)) { W.state[pix] = kDone; continue; } }
-        if constexpr (MV) {
+        if constexpr (SRC == kSrcRays) {
+            const f3 o = load3(F.ray_org, pix), d = load3(F.ray_dir, pix);
+            W.state[pix] = kRay1;
+            W.org[pix] = make_float4(o.x, o.y, o.z, 0.0f);
+            W.dir[pix] = make_float4(d.x, d.y, d.z, 0.0f);
+        } else if constexpr (SRC == kSrcViews) {
+            int y, x;
             const ViewCam c = view_cam<false>(F, view_coords(F, (int)pix, y, x));
             const f3 d = primary_dir(c.rot, F.w, F.h, y, x);
             W.state[pix] = kRay1;
             W.org[pix] = make_float4(c.pos.x, c.pos.y, c.pos.z, 0.0f);
             W.dir[pix] = make_float4(d.x, d.y, d.z, 0.0f);
         } else {
+            int y, x;
             pixel_coords(F, pix, y, x);
             const f3 d = primary_dir(F.cam_rot, F.w, F.h, y, x);
             W.state[pix] = kRay1;
@@ -747,18 +750,9 @@ __global__ void __launch_bounds__(kBlock) sq_primary_gen(const Frame F, const Wo
         }
     }
 }
-// ... of a radiance query: the caller's rays as they are (no camera, so nothing of sq_primary_gen is shared).
-__global__ void __launch_bounds__(kBlock) sq_primary_gen_rays(const RayFrame F, const Work W, long long total) {
-    if (blockIdx.x == 0 && threadIdx.x == 0) W.n_active[48] = (int32_t)total;
-    for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < total; i += (long long)gridDim.x * kBlock) {
-        const f3 o = load3(F.ray_org, i), d = load3(F.ray_dir, i);
-        W.state[i] = kRay1;
-        W.org[i] = make_float4(o.x, o.y, o.z, 0.0f);
-        W.dir[i] = make_float4(d.x, d.y, d.z, 0.0f);
-    }
-}
-template <bool AD = false>
-__global__ void __launch_bounds__(kBlock) sq_primary_store(const Frame F, const Work W, long long total) {
+// Under a sky a miss folds sky(d_0): d_0 is the direction sq_primary_gen put into the slot, which the trace kernel leaves as it took it.
+template <bool AD, typename... SkyT>
+__global__ void __launch_bounds__(kBlock) sq_primary_store(const Frame F, const Work W, long long total, const SkyT... K) {
     for (long long base = (long long)blockIdx.x * kBlock; base < total; base += (long long)gridDim.x * kBlock) {   // whole waves stay together (ballot)
         const long long pix = base + threadIdx.x;
         bool in = pix < total;
@@ -766,20 +760,10 @@ __global__ void __launch_bounds__(kBlock) sq_primary_store(const Frame F, const 
         const int2 hit = in ? slot_hit(W.org[pix]) : make_int2(0, -1);
         const int a = wave_append(W.n_active, in && hit.y >= 0);
         if (a >= 0) store_active<AD>(F, W, a, pix, __int_as_float(hit.x), hit.y);
-        else if (in) store_miss<AD>(F, pix);
-    }
-}
-// ... under a sky: d_0 is the direction sq_primary_gen put into the slot, which the trace kernel leaves as it took it.
-template <bool AD = false>
-__global__ void __launch_bounds__(kBlock) sq_primary_store_sky(const Frame F, const Work W, long long total, const Sky K) {
-    for (long long base = (long long)blockIdx.x * kBlock; base < total; base += (long long)gridDim.x * kBlock) {
-        const long long pix = base + threadIdx.x;
-        bool in = pix < total;
-        if constexpr (AD) in = in && W.state[pix] == kRay1;
-        const int2 hit = in ? slot_hit(W.org[pix]) : make_int2(0, -1);
-        const int a = wave_append(W.n_active, in && hit.y >= 0);
-        if (a >= 0) store_active<AD>(F, W, a, pix, __int_as_float(hit.x), hit.y);
-        else if (in) { const float4 d = W.dir[pix]; store_miss_sky<AD>(F, pix, K, sq::mk(d.x, d.y, d.z)); }
+        else if (in) {
+            if constexpr (sizeof...(SkyT) != 0) { const float4 d = W.dir[pix]; store_miss_sky<AD>(F, pix, K..., sq::mk(d.x, d.y, d.z)); }
+            else store_miss<AD>(F, pix);
+        }
     }
 }
 
@@ -922,9 +906,8 @@ __device__ __forceinline__ void shade1_body(const SceneView S, const FrameT F, c
     }
     diag_aux_wave(W, F.diag, false);
 }
-template <bool MV>
-__global__ void __launch_bounds__(kBlock) sq_shade1(const SceneView S, const Frame F, const Work W, int k_count) { shade1_body<MV>(S, F, W, k_count); }
-__global__ void __launch_bounds__(kBlock) sq_shade1_rays(const SceneView S, const RayFrame F, const Work W, int k_count) { shade1_body<kSrcRays>(S, F, W, k_count); }
+template <int SRC>
+__global__ void __launch_bounds__(kBlock) sq_shade1(const SceneView S, const FrameOf<SRC> F, const Work W, int k_count) { shade1_body<SRC>(S, F, W, k_count); }
 
 // After ray 2: L2 = s2*0 + e2 (or black), L1 = s1*L2 + e1, L0 = s0*L1 + e0   (src/Lib.hs:135-137).
 // Not a kernel of its own: the 8 % of the slots that still hold a second bounce ray are folded where their radiance is
@@ -1087,10 +1070,8 @@ __device__ __forceinline__ void cast_pixels_body(const SceneView& S, const Frame
     }
     store_fold(F, pix, sum);
 }
-template <typename StackT, bool MV, bool AD = false>
-__global__ void __launch_bounds__(kBlock) sq_cast_pixels(const SceneView S, const Frame F, const Lights L) { cast_pixels_body<StackT, MV, AD>(S, F, L); }
-template <typename StackT>
-__global__ void __launch_bounds__(kBlock) sq_cast_pixels_rays(const SceneView S, const RayFrame F, const Lights L) { cast_pixels_body<StackT, kSrcRays, false>(S, F, L); }
+template <typename StackT, int SRC, bool AD>
+__global__ void __launch_bounds__(kBlock) sq_cast_pixels(const SceneView S, const FrameOf<SRC> F, const Lights L) { cast_pixels_body<StackT, SRC, AD>(S, F, L); }
 
 // Wavefront form (option "cast_wavefront" = 1): the lights play the role of a frame's samples.  After the frame's own primary pass,
 // per batch of lights [l_begin, l_end): sq_cast_gen writes the shadow ray of (active pixel a, light l) into slot (l - l_begin) * A + a,
@@ -1110,9 +1091,8 @@ __device__ __forceinline__ void cast_gen_body(const SceneView& S, const FrameT& 
         }
     }
 }
-template <bool MV>
-__global__ void __launch_bounds__(kBlock) sq_cast_gen(const SceneView S, const Frame F, const Work W, const Lights L) { cast_gen_body<MV>(S, F, W, L); }
-__global__ void __launch_bounds__(kBlock) sq_cast_gen_rays(const SceneView S, const RayFrame F, const Work W, const Lights L) { cast_gen_body<kSrcRays>(S, F, W, L); }
+template <int SRC>
+__global__ void __launch_bounds__(kBlock) sq_cast_gen(const SceneView S, const FrameOf<SRC> F, const Work W, const Lights L) { cast_gen_body<SRC>(S, F, W, L); }
 // ... and after the trace launch: T = c_0, T = T + c_l in the caller's order, carried from batch to batch in L.carry; on the last
 // batch (`last`) the sample fold and the pixel's stores, as sq_accumulate does them (a masked call's count is set since the
 // primary pass, store_active; the misses are black since then too).
@@ -1139,9 +1119,8 @@ __device__ __forceinline__ void cast_fold_body(const SceneView& S, const FrameT&
         store_fold(F, pix, sum);
     }
 }
-template <bool MV>
-__global__ void __launch_bounds__(kBlock) sq_cast_fold(const SceneView S, const Frame F, const Work W, const Lights L, int last) { cast_fold_body<MV>(S, F, W, L, last); }
-__global__ void __launch_bounds__(kBlock) sq_cast_fold_rays(const SceneView S, const RayFrame F, const Work W, const Lights L, int last) { cast_fold_body<kSrcRays>(S, F, W, L, last); }
+template <int SRC>
+__global__ void __launch_bounds__(kBlock) sq_cast_fold(const SceneView S, const FrameOf<SRC> F, const Work W, const Lights L, int last) { cast_fold_body<SRC>(S, F, W, L, last); }
 
 // Copies a chunk of lights into the scene's light table: by value, as sq_stage_cams stages cameras.
 constexpr int kLightChunk = 128;              // lights per staging launch: 128 x 24 B = 3 KB of arguments
@@ -1258,7 +1237,7 @@ __device__ __forceinline__ void primary_resident_body(const SceneView& S, const 
     for (long long base = (long long)blockIdx.x * kResidentBlock; base < total; base += (long long)gridDim.x * kResidentBlock) {
         int view = 0;
         long long pix;                                                      // (total is a multiple of 64: whole waves)
-        if constexpr (SRC == kSrcRays) pix = base + threadIdx.x < (long long)F.h ? base + threadIdx.x : -1;   // index order, as in sq_primary_rays
+        if constexpr (SRC == kSrcRays) pix = base + threadIdx.x < (long long)F.h ? base + threadIdx.x : -1;   // index order, as in sq_primary
         else if constexpr (MV) pix = primary_tile_views(F, base + threadIdx.x, view);
         else pix = primary_tile(F, base + threadIdx.x);
         bool in = pix >= 0;
@@ -1287,14 +1266,10 @@ __device__ __forceinline__ void primary_resident_body(const SceneView& S, const 
         else if (in) { if constexpr (SKY) store_miss_sky<AD>(F, pix, K, d0); else store_miss<AD>(F, pix); }
     }
 }
-template <typename StackT, bool MV, bool AD = false>
-__global__ void __launch_bounds__(kResidentBlock) sq_primary_resident(const SceneView S, const Frame F, const Work W, int stack_cap) { primary_resident_body<StackT, MV, AD, false>(S, F, W, stack_cap, Sky{}); }
-template <typename StackT>
-__global__ void __launch_bounds__(kResidentBlock) sq_primary_resident_rays(const SceneView S, const RayFrame F, const Work W, int stack_cap) { primary_resident_body<StackT, kSrcRays, false, false>(S, F, W, stack_cap, Sky{}); }
-template <typename StackT, bool MV, bool AD = false>
-__global__ void __launch_bounds__(kResidentBlock) sq_primary_resident_sky(const SceneView S, const Frame F, const Work W, int stack_cap, const Sky K) { primary_resident_body<StackT, MV, AD, true>(S, F, W, stack_cap, K); }
-template <typename StackT>
-__global__ void __launch_bounds__(kResidentBlock) sq_primary_resident_sky_rays(const SceneView S, const RayFrame F, const Work W, int stack_cap, const Sky K) { primary_resident_body<StackT, kSrcRays, false, true>(S, F, W, stack_cap, K); }
+template <typename StackT, int SRC, bool AD, typename... SkyT>
+__global__ void __launch_bounds__(kResidentBlock) sq_primary_resident(const SceneView S, const FrameOf<SRC> F, const Work W, int stack_cap, const SkyT... K) {
+    primary_resident_body<StackT, SRC, AD, sizeof...(SkyT) != 0>(S, F, W, stack_cap, sky_arg<Sky>(K...));
+}
 
 template <typename StackT, bool RESIDENT, int BLOCK, bool PROFILE, bool POOL>
 __device__ __forceinline__ void trace_rays_body(const SceneView& S, const TraceArgs& A) {
@@ -1819,14 +1794,10 @@ __device__ __forceinline__ void render_pixels_deep_body(const SceneView& S, cons
     }
     store_fold(F, pix, sum);
 }
-template <typename StackT, bool MV, bool AD = false>
-__global__ void __launch_bounds__(kBlock) sq_render_pixels_deep(const SceneView S, const Frame F, const int depth) { render_pixels_deep_body<StackT, MV, AD, false>(S, F, depth, Sky{}); }
-template <typename StackT>
-__global__ void __launch_bounds__(kBlock) sq_render_pixels_deep_rays(const SceneView S, const RayFrame F, const int depth) { render_pixels_deep_body<StackT, kSrcRays, false, false>(S, F, depth, Sky{}); }
-template <typename StackT, bool MV, bool AD = false>
-__global__ void __launch_bounds__(kBlock) sq_render_pixels_deep_sky(const SceneView S, const Frame F, const int depth, const Sky K) { render_pixels_deep_body<StackT, MV, AD, true>(S, F, depth, K); }
-template <typename StackT>
-__global__ void __launch_bounds__(kBlock) sq_render_pixels_deep_sky_rays(const SceneView S, const RayFrame F, const int depth, const Sky K) { render_pixels_deep_body<StackT, kSrcRays, false, true>(S, F, depth, K); }
+template <typename StackT, int SRC, bool AD, typename... SkyT>
+__global__ void __launch_bounds__(kBlock) sq_render_pixels_deep(const SceneView S, const FrameOf<SRC> F, const int depth, const SkyT... K) {
+    render_pixels_deep_body<StackT, SRC, AD, sizeof...(SkyT) != 0>(S, F, depth, sky_arg<Sky>(K...));
+}
 
 // Wavefront form: the levels go through the planned trace kernel one after the other.  A slot's state byte alternates between the
 // two values the trace kernel knows: ray b waits as kRay1 when b is odd and as kRay2 when b is even, so the launch of one level never
@@ -1879,9 +1850,8 @@ __device__ __forceinline__ void deep_gen_body(const SceneView& S, const FrameT& 
         }
     }
 }
-template <bool MV>
-__global__ void __launch_bounds__(kBlock) sq_deep_gen(const SceneView S, const Frame F, const Work W, int k_base, int k_count, const RngView R) { deep_gen_body<MV>(S, F, W, k_base, k_count, R); }
-__global__ void __launch_bounds__(kBlock) sq_deep_gen_rays(const SceneView S, const RayFrame F, const Work W, int k_base, int k_count, const RngView R) { deep_gen_body<kSrcRays>(S, F, W, k_base, k_count, R); }
+template <int SRC>
+__global__ void __launch_bounds__(kBlock) sq_deep_gen(const SceneView S, const FrameOf<SRC> F, const Work W, int k_base, int k_count, const RngView R) { deep_gen_body<SRC>(S, F, W, k_base, k_count, R); }
 
 // After the trace launch of level b = D.level (1 .. depth - 1): the slot's hit goes into the trail; a miss, the last level, an absorbing
 // surface or a last ray that can reach no emitter finishes the slot, anything else puts ray b + 1 into it.  One thread per active pixel.
@@ -1939,16 +1909,17 @@ __device__ __forceinline__ void deep_bounce_body(const SceneView S, const FrameT
         }
     }
 }
-template <bool MV>
-__global__ void __launch_bounds__(kBlock) sq_deep_bounce(const SceneView S, const Frame F, const Work W, int k_base, int k_count, const Deep D) { deep_bounce_body<MV, false>(S, F, W, k_base, k_count, D, DeepSky{}); }
-__global__ void __launch_bounds__(kBlock) sq_deep_bounce_rays(const SceneView S, const RayFrame F, const Work W, int k_base, int k_count, const Deep D) { deep_bounce_body<kSrcRays, false>(S, F, W, k_base, k_count, D, DeepSky{}); }
-template <bool MV>
-__global__ void __launch_bounds__(kBlock) sq_deep_bounce_sky(const SceneView S, const Frame F, const Work W, int k_base, int k_count, const Deep D, const DeepSky K) { deep_bounce_body<MV, true>(S, F, W, k_base, k_count, D, K); }
-__global__ void __launch_bounds__(kBlock) sq_deep_bounce_sky_rays(const SceneView S, const RayFrame F, const Work W, int k_base, int k_count, const Deep D, const DeepSky K) { deep_bounce_body<kSrcRays, true>(S, F, W, k_base, k_count, D, K); }
+template <int SRC, typename... SkyT>
+__global__ void __launch_bounds__(kBlock) sq_deep_bounce(const SceneView S, const FrameOf<SRC> F, const Work W, int k_base, int k_count, const Deep D, const SkyT... K) {
+    // (not through sky_arg: the body takes the DeepSky by value, and a copy of a copy gave the sky instantiations another register allocation)
+    if constexpr (sizeof...(SkyT) != 0) deep_bounce_body<SRC, true>(S, F, W, k_base, k_count, D, K...);
+    else deep_bounce_body<SRC, false>(S, F, W, k_base, k_count, D, DeepSky{});
+}
 
 // The batch's samples folded in order, one thread per active pixel: each sample's radiance is rebuilt from its trail, inside out
 // (path_radiance), and added to the pixel's sums; on the call's last batch the pixel's stores, as sq_accumulate does them.
-__global__ void __launch_bounds__(kBlock) sq_deep_fold(const SceneView S, const Frame F, const Work W, int k_count, int last, const Deep D) {
+template <typename... SkyT>
+__global__ void __launch_bounds__(kBlock) sq_deep_fold(const SceneView S, const Frame F, const Work W, int k_count, int last, const Deep D, const SkyT... K) {
     const int A = *W.n_active;
     const bool mom2 = W.px_sum2 != nullptr;
     for (int a = blockIdx.x * kBlock + threadIdx.x; a < A; a += gridDim.x * kBlock) {
@@ -1969,43 +1940,11 @@ __global__ void __launch_bounds__(kBlock) sq_deep_fold(const SceneView S, const 
                 for (int b = 1; b < kMaxDepth; ++b) {
                     if (more && b < D.depth) { tr[b] = D.trail[(long long)(b - 1) * D.cap + sid]; more = tr[b] >= 0; }
                 }
-                rad = path_radiance(S, s0, tr, sq::mk(0, 0, 0));
-            }
-            sum = sum + rad;
-            if (mom2) sum2 = sum2 + rad * rad;
-        }
-        if (mom2) {
-            if (!last) { W.px_sum2[3 * a] = sum2.x; W.px_sum2[3 * a + 1] = sum2.y; W.px_sum2[3 * a + 2] = sum2.z; }
-            else { float* o = F.sum2 + (long long)W.px_pixel[a] * 3; o[0] = sum2.x; o[1] = sum2.y; o[2] = sum2.z; }
-        }
-        if (!last) { W.px_sum[3 * a] = sum.x; W.px_sum[3 * a + 1] = sum.y; W.px_sum[3 * a + 2] = sum.z; continue; }
-        store_fold(F, W.px_pixel[a], sum);
-    }
-}
-// ... under a sky.  A kernel of its own, the same loop: as a shared template body sq_deep_fold came out with other registers.
-__global__ void __launch_bounds__(kBlock) sq_deep_fold_sky(const SceneView S, const Frame F, const Work W, int k_count, int last, const Deep D, const DeepSky K) {
-    const int A = *W.n_active;
-    const bool mom2 = W.px_sum2 != nullptr;
-    for (int a = blockIdx.x * kBlock + threadIdx.x; a < A; a += gridDim.x * kBlock) {
-        f3 sum = sq::mk(W.px_sum[3 * a], W.px_sum[3 * a + 1], W.px_sum[3 * a + 2]), sum2 = sq::mk(0, 0, 0);
-        if (mom2) sum2 = sq::mk(W.px_sum2[3 * a], W.px_sum2[3 * a + 1], W.px_sum2[3 * a + 2]);
-        const Surface s0 = surface_of(S, W.px_tri0[a]);
-        const f3 rad0 = level0_radiance(s0);
-        const bool flat = D.depth < 2 || absorbs(S, s0);                // every sample ends at level 0: nothing was traced, nothing to read
-        for (int k = 0; k < k_count; ++k) {
-            f3 rad = rad0;
-            if (!flat) {
-                const long long sid = (long long)k * A + a;
-                int tr[kMaxDepth];
-#pragma unroll
-                for (int i = 0; i < kMaxDepth; ++i) tr[i] = -1;
-                bool more = true;
-#pragma unroll
-                for (int b = 1; b < kMaxDepth; ++b) {
-                    if (more && b < D.depth) { tr[b] = D.trail[(long long)(b - 1) * D.cap + sid]; more = tr[b] >= 0; }
-                }
-                // under a sky a -1 is a miss and nothing else (launch_frame turns the shortcuts off): behind it, t of the ray that missed
-                rad = path_radiance(S, s0, tr, more ? sq::mk(0, 0, 0) : sky_at(K.sky, K.tmiss[sid]));
+                if constexpr (sizeof...(SkyT) != 0) {
+                    // under a sky a -1 is a miss and nothing else (launch_frame turns the shortcuts off): behind it, t of the ray that missed
+                    const DeepSky& DS = sky_arg<DeepSky>(K...);
+                    rad = path_radiance(S, s0, tr, more ? sq::mk(0, 0, 0) : sky_at(DS.sky, DS.tmiss[sid]));
+                } else rad = path_radiance(S, s0, tr, sq::mk(0, 0, 0));
             }
             sum = sum + rad;
             if (mom2) sum2 = sum2 + rad * rad;
@@ -2376,73 +2315,20 @@ int timed_launch(sq_device_scene* s, Fn&& fn, const char* name, hipStream_t on) 
     return 0;
 }
 
-// The kernels of a ray source: the frames' own (bool MV) for kSrcCamera / kSrcViews, the query kernels for kSrcRays.  The two sets have
-// the same arguments but for the frame's type (FrameT), so launch_frame's schedules do not know which they enqueue.
-template <typename StackT, int SRC> struct SrcKernels {
-    using FrameT = Frame;
-    static constexpr bool MV = SRC == kSrcViews;
-    static constexpr auto render_pixels = &sq_render_pixels<StackT, MV>;
-    static constexpr auto primary = &sq_primary<StackT, MV>;
-    static constexpr auto primary_resident = &sq_primary_resident<StackT, MV>;
-    static constexpr auto primary_gen = &sq_primary_gen<MV>;
-    static constexpr auto gen_bounce1 = &sq_gen_bounce1<MV>;
-    static constexpr auto mirror1_gen = &sq_mirror1_gen<MV>;
-    static constexpr auto shade1 = &sq_shade1<MV>;
-    static constexpr auto cast_pixels = &sq_cast_pixels<StackT, MV>;
-    static constexpr auto cast_gen = &sq_cast_gen<MV>;
-    static constexpr auto cast_fold = &sq_cast_fold<MV>;
-    static constexpr auto render_pixels_deep = &sq_render_pixels_deep<StackT, MV>;
-    static constexpr auto deep_gen = &sq_deep_gen<MV>;
-    static constexpr auto deep_bounce = &sq_deep_bounce<MV>;
-    static constexpr auto primary_sky = &sq_primary_sky<StackT, MV>;
-    static constexpr auto primary_resident_sky = &sq_primary_resident_sky<StackT, MV>;
-    static constexpr auto render_pixels_deep_sky = &sq_render_pixels_deep_sky<StackT, MV>;
-    static constexpr auto deep_bounce_sky = &sq_deep_bounce_sky<MV>;
-};
-template <typename StackT> struct SrcKernels<StackT, kSrcRays> {
-    using FrameT = RayFrame;
-    static constexpr auto render_pixels = &sq_render_pixels_rays<StackT>;
-    static constexpr auto primary = &sq_primary_rays<StackT>;
-    static constexpr auto primary_resident = &sq_primary_resident_rays<StackT>;
-    static constexpr auto primary_gen = &sq_primary_gen_rays;
-    static constexpr auto gen_bounce1 = &sq_gen_bounce1_rays;
-    static constexpr auto mirror1_gen = &sq_mirror1_gen_rays;
-    static constexpr auto shade1 = &sq_shade1_rays;
-    static constexpr auto cast_pixels = &sq_cast_pixels_rays<StackT>;
-    static constexpr auto cast_gen = &sq_cast_gen_rays;
-    static constexpr auto cast_fold = &sq_cast_fold_rays;
-    static constexpr auto render_pixels_deep = &sq_render_pixels_deep_rays<StackT>;
-    static constexpr auto deep_gen = &sq_deep_gen_rays;
-    static constexpr auto deep_bounce = &sq_deep_bounce_rays;
-    static constexpr auto primary_sky = &sq_primary_sky_rays<StackT>;
-    static constexpr auto primary_resident_sky = &sq_primary_resident_sky_rays<StackT>;
-    static constexpr auto render_pixels_deep_sky = &sq_render_pixels_deep_sky_rays<StackT>;
-    static constexpr auto deep_bounce_sky = &sq_deep_bounce_sky_rays;
-};
-// The kernels of one call's wavefront pipeline, chosen once: the ray source's set; in a masked call (single-view frames only: multi-view
-// frames and queries have no masked form) the AD instantiations of the kernels that decide who is active; and sq_accumulate by second
-// moments and by its loop form.
-template <typename StackT, int SRC> struct PipelineKernels : SrcKernels<StackT, SRC> {
-    using K0 = SrcKernels<StackT, SRC>;
-    std::remove_const_t<decltype(K0::primary)> primary = K0::primary;
-    std::remove_const_t<decltype(K0::primary_resident)> primary_resident = K0::primary_resident;
-    std::remove_const_t<decltype(K0::primary_gen)> primary_gen = K0::primary_gen;
-    void (*primary_store)(Frame, Work, long long);
-    void (*accumulate)(SceneView, Frame, Work, int, int);
-    // under a sky (their further argument is the sky): the primary passes whose miss store folds sky(d_0)
-    std::remove_const_t<decltype(K0::primary_sky)> primary_sky = K0::primary_sky;
-    std::remove_const_t<decltype(K0::primary_resident_sky)> primary_resident_sky = K0::primary_resident_sky;
-    void (*primary_store_sky)(Frame, Work, long long, Sky);
-    PipelineKernels(bool ad, bool mom2, bool acc_grouped) {
-        if constexpr (SRC == kSrcCamera) if (ad) {
-            primary_resident = &sq_primary_resident<StackT, false, true>; primary = &sq_primary<StackT, false, true>; primary_gen = &sq_primary_gen<false, true>;
-            primary_resident_sky = &sq_primary_resident_sky<StackT, false, true>; primary_sky = &sq_primary_sky<StackT, false, true>;
-        }
-        primary_store_sky = ad ? &sq_primary_store_sky<true> : &sq_primary_store_sky<false>;
-        primary_store = ad ? &sq_primary_store<true> : &sq_primary_store<false>;
-        accumulate = mom2 ? (acc_grouped ? &sq_accumulate<true, true> : &sq_accumulate<false, true>) : (acc_grouped ? &sq_accumulate<true> : &sq_accumulate<false>);
-    }
-};
+// A call's run-time choices as the kernels' compile-time ones, where it launches (every family is one template: sq_shade1<SRC>, ...).
+// with_ad: fn(std::bool_constant<ad>); only single-view frames (CAN_AD) have masked calls, so nothing else instantiates AD kernels.
+// with_sky: fn(k) under a sky, fn() without: the kernel's trailing argument pack.  with_ad_sky: fn(ad, k) or fn(ad).
+template <bool CAN_AD, typename Fn>
+int with_ad(bool ad, Fn&& fn) {
+    if constexpr (CAN_AD) if (ad) return fn(std::true_type{});
+    return fn(std::false_type{});
+}
+template <typename SkyT, typename Fn>
+int with_sky(bool sky, const SkyT& k, Fn&& fn) { return sky ? fn(k) : fn(); }
+template <bool CAN_AD, typename SkyT, typename Fn>
+int with_ad_sky(bool ad, bool sky, const SkyT& k, Fn&& fn) {
+    return with_ad<CAN_AD>(ad, [&](auto AD) { return sky ? fn(AD, k) : fn(AD); });
+}
 
 // The persistent trace kernel of a frame's wavefront pipeline or of a ray query: its form and launch geometry (plan_trace).
 struct TracePlan {
@@ -2453,7 +2339,7 @@ struct TracePlan {
 };
 // Chooses the trace form -- resident, streaming six-wave or streaming plain -- its LDS layout and workgroups per CU, and fills the
 // trace fields of s->plan.  Refuses (an error code, nothing enqueued) a tree whose stacks do not fit the streaming form's LDS.
-// SRC: the frame's primary-ray kernel whose static LDS is checked with the resident kernels (an intersection query plans with kSrcCamera).
+// SRC: the frame's resident primary-ray kernels, whose static LDS is checked with the trace kernels' (an intersection query plans with kSrcCamera).
 template <typename StackT, int SRC>
 int plan_trace(sq_device_scene* s, const SceneView& S, int stack_cap, TracePlan& T) {
     sq_plan& P = s->plan;
@@ -2513,7 +2399,7 @@ int plan_trace(sq_device_scene* s, const SceneView& S, int stack_cap, TracePlan&
         // where a violation is an error code, rather than by the device-side trap, where it would be a GPU abort.
         const void* fns[6] = { (const void*)sq_trace_rays<StackT, true, kResidentBlock, false, true>, (const void*)sq_trace_rays<StackT, true, kResidentBlock, true, true>,
                                (const void*)sq_trace_rays<StackT, true, kResidentBlock, false, false>, (const void*)sq_trace_rays<StackT, true, kResidentBlock, true, false>,
-                               (const void*)SrcKernels<StackT, SRC>::primary_resident, (const void*)SrcKernels<StackT, SRC>::primary_resident_sky };
+                               (const void*)sq_primary_resident<StackT, SRC, false>, (const void*)sq_primary_resident<StackT, SRC, false, Sky> };
         for (const void* fn : fns) {
             hipFuncAttributes attr{};
             SQ_HIP(hipFuncGetAttributes(&attr, fn));
@@ -2574,7 +2460,7 @@ int launch_trace_kernel(sq_device_scene* s, const SceneView& S, const TracePlan&
 // kSrcViews: a multi-view frame; `cams` (host, F.n_views of them) are staged into the scene's camera table F.cams once the frame is planned.
 // kSrcRays: a chunk of a radiance query (radiance_rays): a frame of one row whose "pixels" are the caller's rays F.ray_org / ray_dir / ray_seed.
 template <typename StackT, int SRC>
-int launch_frame(sq_device_scene* s, const typename SrcKernels<StackT, SRC>::FrameT& F, hipStream_t stream, const sq_camera* cams) {
+int launch_frame(sq_device_scene* s, const FrameOf<SRC>& F, hipStream_t stream, const sq_camera* cams) {
     int stack_cap; size_t px_lds;
     SceneView S = begin_plan<StackT>(s, stack_cap, px_lds);
     // nonneg_materials bounds the radiance below an absorbing surface for the reference's depth.  A deeper path nests more products,
@@ -2602,39 +2488,24 @@ int launch_frame(sq_device_scene* s, const typename SrcKernels<StackT, SRC>::Fra
     // a path-traced frame or query under a depth other than 3 (or under option "deep"): the generic-depth kernels
     const int depth = s->depth;
     const bool deep = !F.cast && (depth != 3 || s->opt_deep || sky);
-    if (F.cast && !cast_wave && s->lights_set) {                       // caller-given lights, per-lane: sq_cast_pixels beside sq_render_pixels
-        auto cast_pixels = SrcKernels<StackT, SRC>::cast_pixels;
-        if constexpr (SRC == kSrcCamera) if (ad) cast_pixels = &sq_cast_pixels<StackT, false, true>;
-        if (px_lds > 64 * 1024) SQ_HIP(hipFuncSetAttribute((const void*)cast_pixels, hipFuncAttributeMaxDynamicSharedMemorySize, (int)px_lds));
+    // The per-lane forms: one kernel, one lane per pixel.  The branches below choose the kernel and what follows S and F in its arguments.
+    constexpr bool kCanAd = SRC == kSrcCamera;
+    auto launch_per_lane = [&](auto kernel, const char* name, auto... args) -> int {
+        if (px_lds > 64 * 1024) SQ_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)px_lds));
         P.launched = 1;
         if (stage_cams(s, F, cams, stream)) return 1;
+        return timed_launch(s, [&] { hipLaunchKernelGGL(kernel, dim3((unsigned)px_blocks), dim3(kBlock), px_lds, stream, S, F, args...); }, name, stream);
+    };
+    if (F.cast && !cast_wave && s->lights_set) {                       // caller-given lights: sq_cast_pixels beside sq_render_pixels
         const Lights L{ s->d_lights, n_lights, nullptr, 0, n_lights };
-        return timed_launch(s, [&] { hipLaunchKernelGGL(cast_pixels, dim3((unsigned)px_blocks), dim3(kBlock), px_lds, stream, S, F, L); }, "sq_cast_pixels", stream);
+        return with_ad<kCanAd>(ad, [&](auto AD) { return launch_per_lane(sq_cast_pixels<StackT, SRC, AD()>, "sq_cast_pixels", L); });
     }
-    if (s->opt_variant == 1 && sky) {                                   // per-lane under a sky
-        auto render_sky = SrcKernels<StackT, SRC>::render_pixels_deep_sky;
-        if constexpr (SRC == kSrcCamera) if (ad) render_sky = &sq_render_pixels_deep_sky<StackT, false, true>;
-        if (px_lds > 64 * 1024) SQ_HIP(hipFuncSetAttribute((const void*)render_sky, hipFuncAttributeMaxDynamicSharedMemorySize, (int)px_lds));
-        P.launched = 1;
-        if (stage_cams(s, F, cams, stream)) return 1;
-        return timed_launch(s, [&] { hipLaunchKernelGGL(render_sky, dim3((unsigned)px_blocks), dim3(kBlock), px_lds, stream, S, F, depth, KS); }, "sq_render_pixels_deep_sky", stream);
-    }
-    if (s->opt_variant == 1 && deep) {                                  // per-lane: sq_render_pixels_deep beside sq_render_pixels
-        auto render_deep = SrcKernels<StackT, SRC>::render_pixels_deep;
-        if constexpr (SRC == kSrcCamera) if (ad) render_deep = &sq_render_pixels_deep<StackT, false, true>;
-        if (px_lds > 64 * 1024) SQ_HIP(hipFuncSetAttribute((const void*)render_deep, hipFuncAttributeMaxDynamicSharedMemorySize, (int)px_lds));
-        P.launched = 1;
-        if (stage_cams(s, F, cams, stream)) return 1;
-        return timed_launch(s, [&] { hipLaunchKernelGGL(render_deep, dim3((unsigned)px_blocks), dim3(kBlock), px_lds, stream, S, F, depth); }, "sq_render_pixels_deep", stream);
-    }
-    if (s->opt_variant == 1 || (F.cast && !cast_wave)) {
-        auto render_pixels = SrcKernels<StackT, SRC>::render_pixels;
-        if constexpr (SRC == kSrcCamera) if (ad) render_pixels = &sq_render_pixels<StackT, false, true>;
-        if (px_lds > 64 * 1024) SQ_HIP(hipFuncSetAttribute((const void*)render_pixels, hipFuncAttributeMaxDynamicSharedMemorySize, (int)px_lds));
-        P.launched = 1;
-        if (stage_cams(s, F, cams, stream)) return 1;
-        return timed_launch(s, [&] { hipLaunchKernelGGL(render_pixels, dim3((unsigned)px_blocks), dim3(kBlock), px_lds, stream, S, F); }, "sq_render_pixels", stream);
-    }
+    if (s->opt_variant == 1 && deep)                                    // a depth other than 3, or a sky: sq_render_pixels_deep beside sq_render_pixels
+        return with_ad_sky<kCanAd>(ad, sky, KS, [&](auto AD, auto... K) {
+            return launch_per_lane(sq_render_pixels_deep<StackT, SRC, AD(), decltype(K)...>, sizeof...(K) ? "sq_render_pixels_deep_sky" : "sq_render_pixels_deep", depth, K...);
+        });
+    if (s->opt_variant == 1 || (F.cast && !cast_wave))
+        return with_ad<kCanAd>(ad, [&](auto AD) { return launch_per_lane(sq_render_pixels<StackT, SRC, AD()>, "sq_render_pixels"); });
     // ---- wavefront pipeline ----
     // the samples this call renders (a whole frame: F.samples); in a cast frame the lights take the samples' place in the slots
     const int n_call = cast_wave ? n_lights : F.k_end - F.k_begin;
@@ -2668,8 +2539,11 @@ int launch_frame(sq_device_scene* s, const typename SrcKernels<StackT, SRC>::Fra
     TracePlan TP;
     if (plan_trace<StackT, SRC>(s, S, stack_cap, TP)) return 1;
     const int aux_blocks = s->n_cu * (int)(s->opt_aux_blocks_per_cu ? s->opt_aux_blocks_per_cu : 8);
-    // sq_accumulate: the grouped loop when the shard has no more pixels than the launch has threads (every thread at most one pixel)
-    const PipelineKernels<StackT, SRC> K(ad, mom2, pixels <= (long long)aux_blocks * kBlock);
+    // sq_accumulate, by second moments and by its loop form: the grouped loop when the shard has no more pixels than the launch has
+    // threads (every thread at most one pixel)
+    const bool acc_grouped = pixels <= (long long)aux_blocks * kBlock;
+    void (*const accumulate_kernel)(SceneView, Frame, Work, int, int) =
+        mom2 ? (acc_grouped ? &sq_accumulate<true, true> : &sq_accumulate<false, true>) : (acc_grouped ? &sq_accumulate<true> : &sq_accumulate<false>);
     const bool resident = TP.resident, pool = TP.pool;
     P.primary_form = (s->opt_primary_pooled && pool) ? SQ_PRIMARY_POOLED : (resident && s->opt_primary_resident) ? SQ_PRIMARY_RESIDENT : SQ_PRIMARY_PER_LANE;
     // the per-lane primary pass is one launch with a thread per tile lane, padding included (a narrow frame's edge tiles are mostly
@@ -2693,14 +2567,20 @@ int launch_frame(sq_device_scene* s, const typename SrcKernels<StackT, SRC>::Fra
     // primary rays: once per pixel.  With a resident scene they are traced out of LDS as well ...
     if (P.primary_form == SQ_PRIMARY_RESIDENT) {
         const TraceLds Lp = trace_lds_layout(S.n_branches, true, S.n_verts, S.n_tris, kResidentBlock, stack_cap, (int)sizeof(StackT), false);
-        SQ_HIP(hipFuncSetAttribute(sky ? (const void*)K.primary_resident_sky : (const void*)K.primary_resident, hipFuncAttributeMaxDynamicSharedMemorySize, (int)Lp.total));
         const long long need = (primary_padded(F) * F.n_views + kResidentBlock - 1) / kResidentBlock;
-        if (sky) hipLaunchKernelGGL(K.primary_resident_sky, dim3((unsigned)std::min<long long>(s->n_cu, need)), dim3(kResidentBlock), Lp.total, stream, S, F, W, stack_cap, KS);
-        else hipLaunchKernelGGL(K.primary_resident, dim3((unsigned)std::min<long long>(s->n_cu, need)), dim3(kResidentBlock), Lp.total, stream, S, F, W, stack_cap);
+        if (with_ad_sky<kCanAd>(ad, sky, KS, [&](auto AD, auto... K) -> int {
+                const auto kernel = sq_primary_resident<StackT, SRC, AD(), decltype(K)...>;
+                SQ_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)Lp.total));
+                hipLaunchKernelGGL(kernel, dim3((unsigned)std::min<long long>(s->n_cu, need)), dim3(kResidentBlock), Lp.total, stream, S, F, W, stack_cap, K...);
+                return 0;
+            })) return 1;
     } else if (P.primary_form == SQ_PRIMARY_PER_LANE) {
-        if (px_lds > 64 * 1024) SQ_HIP(hipFuncSetAttribute(sky ? (const void*)K.primary_sky : (const void*)K.primary, hipFuncAttributeMaxDynamicSharedMemorySize, (int)px_lds));
-        if (sky) hipLaunchKernelGGL(K.primary_sky, dim3((unsigned)((primary_padded(F) * F.n_views + kBlock - 1) / kBlock)), dim3(kBlock), px_lds, stream, S, F, W, KS);
-        else hipLaunchKernelGGL(K.primary, dim3((unsigned)((primary_padded(F) * F.n_views + kBlock - 1) / kBlock)), dim3(kBlock), px_lds, stream, S, F, W);
+        if (with_ad_sky<kCanAd>(ad, sky, KS, [&](auto AD, auto... K) -> int {
+                const auto kernel = sq_primary<StackT, SRC, AD(), decltype(K)...>;
+                if (px_lds > 64 * 1024) SQ_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)px_lds));
+                hipLaunchKernelGGL(kernel, dim3((unsigned)((primary_padded(F) * F.n_views + kBlock - 1) / kBlock)), dim3(kBlock), px_lds, stream, S, F, W, K...);
+                return 0;
+            })) return 1;
     }
     SQ_HIP(hipGetLastError());
     // per-sample kernels that run one thread per active pixel: x covers the pixels, y splits a pixel's samples when the
@@ -2718,11 +2598,13 @@ int launch_frame(sq_device_scene* s, const typename SrcKernels<StackT, SRC>::Fra
     if (P.primary_form == SQ_PRIMARY_POOLED) {                          // ... or through the pooled trace kernel
         Work Wp = W; Wp.n_active = W.n_active + 48;                     // the launch's queue is the shard's pixels, not the active ones
         SQ_HIP(hipMemsetAsync(W.head[0], 0, 32 * sizeof(int32_t), stream));
-        hipLaunchKernelGGL(K.primary_gen, dim3(aux_blocks), dim3(kBlock), 0, stream, F, W, pixels);
+        with_ad<kCanAd>(ad, [&](auto AD) { hipLaunchKernelGGL((sq_primary_gen<SRC, AD()>), dim3(aux_blocks), dim3(kBlock), 0, stream, F, W, pixels); return 0; });
         SQ_HIP(hipGetLastError());
         if (launch_trace_kernel(s, S, TP, Wp, pixels, 1, 0, stream, false)) return 1;
-        if (sky) hipLaunchKernelGGL(K.primary_store_sky, dim3(aux_blocks), dim3(kBlock), 0, stream, F, W, pixels, KS);
-        else hipLaunchKernelGGL(K.primary_store, dim3(aux_blocks), dim3(kBlock), 0, stream, F, W, pixels);
+        with_ad_sky<kCanAd>(ad, sky, KS, [&](auto AD, auto... K) {
+            hipLaunchKernelGGL((sq_primary_store<AD(), decltype(K)...>), dim3(aux_blocks), dim3(kBlock), 0, stream, F, W, pixels, K...);
+            return 0;
+        });
         SQ_HIP(hipGetLastError());
     }
     if (cast_wave) {
@@ -2732,10 +2614,10 @@ int launch_frame(sq_device_scene* s, const typename SrcKernels<StackT, SRC>::Fra
             const int l0 = i * batch, kc = std::min(batch, n_lights - l0);
             const Lights L{ s->d_lights, n_lights, s->cast_carry, l0, l0 + kc };
             SQ_HIP(hipMemsetAsync(W.head[0], 0, 32 * sizeof(int32_t), stream));     // both dequeue cursors
-            hipLaunchKernelGGL((SrcKernels<StackT, SRC>::cast_gen), pp_grid(kc), dim3(kBlock), 0, stream, S, F, W, L);
+            hipLaunchKernelGGL(sq_cast_gen<SRC>, pp_grid(kc), dim3(kBlock), 0, stream, S, F, W, L);
             SQ_HIP(hipGetLastError());
             if (launch_trace_kernel(s, S, TP, W, pixels, kc, 0, stream, false)) return 1;
-            hipLaunchKernelGGL((SrcKernels<StackT, SRC>::cast_fold), dim3(aux_blocks), dim3(kBlock), 0, stream, S, F, W, L, l0 + kc == n_lights ? 1 : 0);
+            hipLaunchKernelGGL(sq_cast_fold<SRC>, dim3(aux_blocks), dim3(kBlock), 0, stream, S, F, W, L, l0 + kc == n_lights ? 1 : 0);
             SQ_HIP(hipGetLastError());
         }
         return 0;
@@ -2751,20 +2633,18 @@ int launch_frame(sq_device_scene* s, const typename SrcKernels<StackT, SRC>::Fra
             const int k0 = F.k_begin + i * batch, kc = std::min(batch, n_call - i * batch);
             if (depth >= 2) {
                 SQ_HIP(hipMemsetAsync(W.head[0], 0, 32 * sizeof(int32_t), stream));     // both dequeue cursors
-                hipLaunchKernelGGL((SrcKernels<StackT, SRC>::deep_gen), pp_grid(kc), dim3(kBlock), 0, stream, S, F, W, k0, kc, R);
+                hipLaunchKernelGGL(sq_deep_gen<SRC>, pp_grid(kc), dim3(kBlock), 0, stream, S, F, W, k0, kc, R);
                 SQ_HIP(hipGetLastError());
             }
             for (int b = 1; b < depth; ++b) {
                 const Deep D{ depth, b, trail, oxy, cap };
                 if (b >= 3) SQ_HIP(hipMemsetAsync(W.head[0], 0, 32 * sizeof(int32_t), stream));   // a cursor's second use
                 if (launch_trace_kernel(s, S, TP, W, pixels, kc, (b - 1) & 1, stream, false)) return 1;
-                if (sky) hipLaunchKernelGGL((SrcKernels<StackT, SRC>::deep_bounce_sky), pp_grid(kc), dim3(kBlock), 0, stream, S, F, W, k0, kc, D, DS);
-                else hipLaunchKernelGGL((SrcKernels<StackT, SRC>::deep_bounce), pp_grid(kc), dim3(kBlock), 0, stream, S, F, W, k0, kc, D);
+                with_sky(sky, DS, [&](auto... K) { hipLaunchKernelGGL((sq_deep_bounce<SRC, decltype(K)...>), pp_grid(kc), dim3(kBlock), 0, stream, S, F, W, k0, kc, D, K...); return 0; });
                 SQ_HIP(hipGetLastError());
             }
             const Deep D{ depth, 0, trail, oxy, cap };
-            if (sky) hipLaunchKernelGGL(sq_deep_fold_sky, dim3(aux_blocks), dim3(kBlock), 0, stream, S, F, W, kc, (i + 1) * batch >= n_call ? 1 : 0, D, DS);
-            else hipLaunchKernelGGL(sq_deep_fold, dim3(aux_blocks), dim3(kBlock), 0, stream, S, F, W, kc, (i + 1) * batch >= n_call ? 1 : 0, D);
+            with_sky(sky, DS, [&](auto... K) { hipLaunchKernelGGL(sq_deep_fold<decltype(K)...>, dim3(aux_blocks), dim3(kBlock), 0, stream, S, F, W, kc, (i + 1) * batch >= n_call ? 1 : 0, D, K...); return 0; });
             SQ_HIP(hipGetLastError());
         }
         return 0;
@@ -2783,22 +2663,22 @@ int launch_frame(sq_device_scene* s, const typename SrcKernels<StackT, SRC>::Fra
     P.level1_cull = L1.on;
     auto gen = [&](int i, hipStream_t on) -> int {
         SQ_HIP(hipMemsetAsync(Wt[i & 1].head[0], 0, 32 * sizeof(int32_t), on));     // both dequeue cursors
-        hipLaunchKernelGGL(K.gen_bounce1, pp_grid(kc_of(i)), dim3(kBlock), 0, on, S, F, Wt[i & 1], k0_of(i), kc_of(i), R, L1);
+        hipLaunchKernelGGL(sq_gen_bounce1<SRC>, pp_grid(kc_of(i)), dim3(kBlock), 0, on, S, F, Wt[i & 1], k0_of(i), kc_of(i), R, L1);
         return launched();
     };
     auto trace = [&](int i, int level, hipStream_t on, bool with_mirror) -> int { return launch_trace_kernel(s, S, TP, Wt[i & 1], pixels, kc_of(i), level, on, with_mirror); };
     auto shade = [&](int i, hipStream_t on) -> int {
-        hipLaunchKernelGGL(K.shade1, pp_grid(kc_of(i)), dim3(kBlock), 0, on, S, F, Wt[i & 1], kc_of(i));
+        hipLaunchKernelGGL(sq_shade1<SRC>, pp_grid(kc_of(i)), dim3(kBlock), 0, on, S, F, Wt[i & 1], kc_of(i));
         return launched();
     };
     auto accumulate = [&](int i, hipStream_t on, bool last) -> int {     // in batch order: the per-pixel sum is ordered (src/Lib.hs:88)
-        hipLaunchKernelGGL(K.accumulate, dim3(aux_blocks), dim3(kBlock), 0, on, S, F, Wt[i & 1], kc_of(i), last ? 1 : 0);
+        hipLaunchKernelGGL(accumulate_kernel, dim3(aux_blocks), dim3(kBlock), 0, on, S, F, Wt[i & 1], kc_of(i), last ? 1 : 0);
         return launched();
     };
     // Once per frame, on the caller's stream: the depth-0 mirror ray of every active pixel (reused by every sample that mirrors),
     // generated into the slots from `base` on and, once traced, stored per pixel.
     auto mirror_gen = [&](long long base) -> int {
-        hipLaunchKernelGGL(K.mirror1_gen, dim3(aux_blocks), dim3(kBlock), 0, stream, S, F, W, base);
+        hipLaunchKernelGGL(sq_mirror1_gen<SRC>, dim3(aux_blocks), dim3(kBlock), 0, stream, S, F, W, base);
         return launched();
     };
     auto mirror_store = [&](long long base) -> int {

@@ -5,7 +5,9 @@ hold the kernels to is this restatement of include/squigly_hip.h's formula -- in
 from the oracle, every other operation is a single float32 operation written out here -- and tests/test_depth.py pins it to the oracle
 itself at D = 3: sqo_sample_radiance bit for bit on the rays the GPU tests use, sqo_render on a frame.
 
-A path does not depend on the depth it is cut at: `path` walks it once to the largest depth and `radiance` folds any prefix of it."""
+A path does not depend on the depth it is cut at: `path` walks it once to the largest depth and `radiance` folds any prefix of it.
+Nor does it depend on what a miss is worth: `path` is also sky_restatement's walk, which keeps the direction of the ray that missed
+(`miss`), and the shared inputs below are walked once, for both modules."""
 import functools
 import importlib
 import os
@@ -35,8 +37,9 @@ def random01(n):
     return f32(f32(0) + f32(f32(1) * f32(f32(n) / f32(4294967296.0))))
 
 
-def path(ob, flat, words, o, d, depth=MAX_DEPTH):
-    """The triangles (records of flat = ob.flatten()) the rays 0 .. depth-1 of a path hit, None where the path ends on a miss.
+def path(ob, flat, words, o, d, depth=MAX_DEPTH, miss=None):
+    """The triangles (records of flat = ob.flatten()) the rays 0 .. depth-1 of a path hit; where the path ends on a miss, None, or
+    miss(d) of the direction of the ray that missed, exactly as it was traced.
     ob: pyoracle.BIH; words = pyoracle.tfgen_words(seed); o, d: ray 0."""
     L = O.lib()
     trail = []
@@ -45,7 +48,7 @@ def path(ob, flat, words, o, d, depth=MAX_DEPTH):
         for b in range(depth):
             h = ob.intersect(o, d)
             if not h.hit:
-                trail.append(None)
+                trail.append(None if miss is None else miss(d))
                 break
             t = flat[h.tri]
             trail.append(t)
@@ -77,21 +80,26 @@ def raytrace(ob, flat, words, o, d, depth):
     return radiance(path(ob, flat, words, o, d, depth), depth)
 
 
-def paths(ob, flat, o, d, seeds, k=0, depth=MAX_DEPTH):
+def paths(ob, flat, o, d, seeds, k=0, depth=MAX_DEPTH, miss=None):
     """The path of every ray i with the generator mkTFGen (seeds[i] + k)."""
-    return [path(ob, flat, O.tfgen_words(int(seeds[i]) + k), o[i], d[i], depth) for i in range(len(o))]
+    return [path(ob, flat, O.tfgen_words(int(seeds[i]) + k), o[i], d[i], depth, miss) for i in range(len(o))]
+
+
+def plain(trails):
+    """Paths walked with their misses kept (`miss`), read as paths walked without: None wherever one holds no triangle record."""
+    return [[t if isinstance(t, np.void) else None for t in trail] for trail in trails]
 
 
 def radiances(trails, depth):
     return np.array([radiance(t, depth) for t in trails], f32).reshape(len(trails), 3)
 
 
-def frame_paths(ob, flat, cam, spp, w, h, rows=None):
+def frame_paths(ob, flat, cam, spp, w, h, rows=None, miss=None):
     """paths[k][j * h + x] of sample k of pixel (y, x) of the spp-sample frame, y over `rows` (default: all w rows); the seed is
     spp * (x + y * w) + k (src/Lib.hs:85)."""
     rows = range(w) if rows is None else rows
     rays = [(y, x) + O.make_ray(w, h, y, x, cam) for y in rows for x in range(h)]
-    return [[path(ob, flat, O.tfgen_words(spp * (x + y * w) + k), o, d) for (y, x, o, d) in rays] for k in range(spp)]
+    return [[path(ob, flat, O.tfgen_words(spp * (x + y * w) + k), o, d, miss=miss) for (y, x, o, d) in rays] for k in range(spp)]
 
 
 def fold_frame(trails_by_sample, depth, n=None):
@@ -170,18 +178,20 @@ def case(which):
 
 
 def case_paths(c, k=0):
-    """The paths of the case's rays under the generators mkTFGen (seed + k), walked once."""
+    """The paths of the case's rays under the generators mkTFGen (seed + k), walked once: sky_restatement.case_paths' walk, which
+    keeps the misses, with each Miss read as None."""
+    import sky_restatement as SR                                        # (it imports this module)
     if k not in c.paths:
-        c.paths[k] = paths(c.ob, c.flat, c.o, c.d, c.s, k=k)
+        c.paths[k] = plain(SR.case_paths(c, k))
     return c.paths[k]
 
 
 @functools.lru_cache(maxsize=None)
 def frame_case(which, camera, w, h, spp):
-    """frame_paths of the whole w x h frame at spp samples under data/camera ("camera") or the rotated camera."""
-    c = case(which)
-    text = open(os.path.join(DATA, "camera"), "rb").read() if camera == "camera" else ROTATED
-    return frame_paths(c.ob, c.flat, O.camera_from_text(text), spp, w, h)
+    """frame_paths of the whole w x h frame at spp samples under data/camera ("camera") or the rotated camera: sky_restatement.frame_case's
+    walk with each Miss read as None."""
+    import sky_restatement as SR
+    return [plain(trails) for trails in SR.frame_case(which, camera, w, h, spp)]
 
 
 def shard_rows(w, shard):

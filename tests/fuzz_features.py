@@ -34,6 +34,7 @@ import pyoracle as O  # noqa: E402
 O.lib()
 import fuzz_gpu as F  # noqa: E402  (loads the product library, as it does for its own campaign)
 import depth_restatement as DR  # noqa: E402
+import sky_restatement as SR  # noqa: E402
 from test_gpu_lights import Restatement, avg_of, fold as fold_cast  # noqa: E402
 from test_gpu_rays import check_hits, oracle_hits  # noqa: E402
 from test_gpu_raytrace import oracle_raycast, oracle_raytrace, positive_zeros  # noqa: E402
@@ -166,10 +167,11 @@ def product_bih(c):
 
 
 def frame_paths(c, second=False):
-    """depth_restatement.frame_paths of the case's shard under its first or second camera, walked once to MAX_DEPTH."""
+    """depth_restatement.frame_paths of the case's shard under its first or second camera, walked once to MAX_DEPTH: the walk
+    sky_restatement keeps for the case, with each Miss read as None."""
     key = "_paths2" if second else "_paths"
     if not hasattr(c, key):
-        setattr(c, key, DR.frame_paths(c.ob, c.flat, c.ocam2 if second else c.ocam, c.spp, c.w, c.h, rows=c.rows))
+        setattr(c, key, [DR.plain(trails) for trails in SR.fuzz_frame_paths(c, second)])
     return getattr(c, key)
 
 
@@ -208,8 +210,7 @@ def radiance_rays(c):
 
 def ray_paths(c):
     if not hasattr(c, "_ray_paths"):
-        o, d, s = radiance_rays(c)
-        c._ray_paths = DR.paths(c.ob, c.flat, o, d, s)
+        c._ray_paths = DR.plain(SR.fuzz_ray_paths(c))
     return c._ray_paths
 
 

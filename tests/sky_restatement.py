@@ -1,8 +1,8 @@
 """Lib.raytrace under a path depth D and a caller-given sky (sq_scene_set_sky), restated in numpy float32 from the oracle's primitives.
 
 include/squigly_hip.h's chain with one line changed: a ray that intersects nothing returns sky(d) of its direction as traced, where
-depth_restatement (and the reference) say black.  The walk is depth_restatement.path's, ray for ray, but a path that ends on a miss
-keeps the direction of the ray that missed (`Miss`), which `DR.path` drops.  tests/test_sky.py pins this module to depth_restatement
+depth_restatement (and the reference) say black.  The walk is depth_restatement.path itself, told to keep the direction of the ray
+that missed (`Miss`) where it would end a path on None.  tests/test_sky.py pins this module to depth_restatement
 -- and through it to the oracle -- with no sky, and judges what the shared inputs cover; tests/test_gpu_sky.py holds the kernels to it.
 
 A sky is None or (up, down), three float32 each."""
@@ -46,30 +46,7 @@ def sky_of(sky, d):
 
 def path(ob, flat, words, o, d, depth=MAX_DEPTH):
     """depth_restatement.path with the miss kept: the triangles the rays 0 .. depth-1 hit, a Miss where the path ends on one."""
-    L = O.lib()
-    trail = []
-    o, d = np.asarray(o, f32), np.asarray(d, f32)
-    with np.errstate(all="ignore"):
-        for b in range(depth):
-            h = ob.intersect(o, d)
-            if not h.hit:
-                trail.append(Miss(d))
-                break
-            t = flat[h.tri]
-            trail.append(t)
-            if b + 1 >= depth:
-                break
-            nrm = DR.cross((t["b"] + -t["a"]).astype(f32), (t["c"] + -t["a"]).astype(f32))
-            if t["reflective"] < DR.random01(words[b]):
-                v = L.sqo_random_vector(words[b], words[b + 1], 0)
-                nd = np.array([v.x, v.y, v.z], f32)
-                if DR.signum(DR.dot(d, nrm)) == DR.signum(DR.dot(nd, nrm)):
-                    nd = -nd
-            else:
-                dn = (nrm / f32(np.sqrt(DR.dot(nrm, nrm)))).astype(f32)
-                nd = (d + -(f32(f32(2) * DR.dot(dn, d)) * dn).astype(f32)).astype(f32)
-            o, d = np.array([h.point.x, h.point.y, h.point.z], f32), nd
-    return trail
+    return DR.path(ob, flat, words, o, d, depth, miss=Miss)
 
 
 def radiance(trail, depth, sky):
@@ -86,7 +63,7 @@ def radiance(trail, depth, sky):
 
 
 def paths(ob, flat, o, d, seeds, k=0, depth=MAX_DEPTH):
-    return [path(ob, flat, O.tfgen_words(int(seeds[i]) + k), o[i], d[i], depth) for i in range(len(o))]
+    return DR.paths(ob, flat, o, d, seeds, k, depth, miss=Miss)
 
 
 def radiances(trails, depth, sky):
@@ -107,9 +84,7 @@ def absorbing_above_miss(trail, depth):
 
 def frame_paths(ob, flat, cam, spp, w, h, rows=None):
     """depth_restatement.frame_paths with the misses kept."""
-    rows = range(w) if rows is None else rows
-    rays = [(y, x) + O.make_ray(w, h, y, x, cam) for y in rows for x in range(h)]
-    return [[path(ob, flat, O.tfgen_words(spp * (x + y * w) + k), o, d) for (y, x, o, d) in rays] for k in range(spp)]
+    return DR.frame_paths(ob, flat, cam, spp, w, h, rows, miss=Miss)
 
 
 def fold_frame(trails_by_sample, depth, sky, n=None, start=None, start2=None):
@@ -125,7 +100,8 @@ def fold_frame(trails_by_sample, depth, sky, n=None, start=None, start2=None):
     return s, q, avg
 
 
-# ---- the inputs the sky tests share: depth_restatement's cases, walked once more with the misses kept ----------------------------
+# ---- the inputs the sky tests share: depth_restatement's cases and fuzz_features'.  Their one walk is made here, with the misses
+# ---- kept; the depth view of it reads each Miss as None (depth_restatement.plain) -----------------------------------------------
 def case_paths(c, k=0):
     """The paths of a depth_restatement.case's rays under the generators mkTFGen (seed + k), walked once."""
     if not hasattr(c, "sky_paths"):
