@@ -448,7 +448,8 @@ int64_t sq_scene_rng_table(sq_device_scene* s, int64_t first, int64_t count, uin
 
 /* The launch plan of the scene's last render or query call (read only; diagnostics and tests): which kernel forms it
  * chose and the sizes they were chosen by.  Filled as the call plans the frame or query, so after a refused call (an error code
- * such as "BIH height ... needs ... LDS") it holds what was planned up to the refusal and launched = 0.  A query
+ * such as "BIH height ... needs ... LDS") it holds what was planned up to the refusal and launched = 0; a call is planned before it
+ * touches the device, so a refused call has allocated, freed and cleared nothing (squigly_host.h: sq_plan_call plans without a GPU).  A query
  * (sq_intersect_rays_device) has primary_form SQ_PRIMARY_NONE.  Returns non-zero when the scene has not planned a call yet. */
 enum { SQ_FORM_PER_PIXEL = 0, SQ_FORM_RESIDENT = 1, SQ_FORM_STREAMING_SIX_WAVE = 2, SQ_FORM_STREAMING_PLAIN = 3 };
 enum { SQ_PRIMARY_NONE = 0, SQ_PRIMARY_PER_LANE = 1, SQ_PRIMARY_RESIDENT = 2, SQ_PRIMARY_POOLED = 3 };

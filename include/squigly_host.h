@@ -4,8 +4,9 @@
  * Haskell host would keep calling unchanged.  No GHC exists in the build or GPU images, so the
  * same functions are provided in C++ (squigly-trace_amd/csrc/sq_host.cpp) with identical
  * arithmetic, and produce exactly the arrays that squigly_hip.h consumes.
- * Also here, with no counterpart in the reference: the culling boxes, and a window on the scene packer, the host half of
- * sq_scene_upload(), so that what the kernels will read can be inspected on a machine without a GPU.
+ * Also here, with no counterpart in the reference: the culling boxes, a window on the scene packer, the host half of
+ * sq_scene_upload(), so that what the kernels will read can be inspected on a machine without a GPU, and a window on the call
+ * planner, the host half of every render and query call.
  * All citations are relative to the reference repository root.
  */
 #ifndef SQUIGLY_HOST_H
@@ -78,6 +79,35 @@ int   sq_scene_pack(const sq_scene* scene, sq_packed** out);
 int   sq_packed_array(const sq_packed* p, const char* name, const void** data, size_t* bytes);
 int   sq_packed_scalar(const sq_packed* p, const char* name, int64_t* value);
 void  sq_packed_free(sq_packed* p);
+
+/* The call planner: everything a render or query call decides before it touches the device -- kernel forms, LDS carve-up, slots,
+ * batches, grids, reservation sizes, the workspace layout and every refusal -- from a few numbers.  Needs no GPU; the device code
+ * plans by the same functions (csrc/sq_plan.h).  Inputs go by name and value:
+ *   options    the names of sq_set_option, with its ranges and refusals (default: the option's default);
+ *   scene      the names of sq_packed_scalar: n_branches, n_verts, height, small_index, packed_leaves, n_emitters, nonneg_materials,
+ *              finite_geometry, shortcut_depth, level1_on; and n_tris (sq_scene.n_tris), trix (the packed array "trix" is not empty);
+ *   device     n_cu, the compute units;
+ *   state      depth (sq_scene_set_depth), sky (1: a sky is set), lights_set (1: sq_scene_set_lights gave lights), n_lights;
+ *   the call   source (0 camera, 1 views, 2 caller-given rays), cast, masked (a mask, second moments or counts are given), mom2 (second
+ *              moments are), n_views, local_rows, h, tile_rows, tiles_x (the tiling of the primary rays: 8 rows x 8 columns on a whole
+ *              image, 1 x 64 with option primary_tiles 0 and for rays), k_begin, k_end; a chunk of a radiance query is a frame of one
+ *              row, h = the chunk's rays, and total_rays = the query's rays asks for chunk_rays, the rays per chunk;
+ *              query = 1 with n_rays: an intersection query.
+ * have_slots: the sample slots the workspace holds (the allocation may have halved the plan's `slots`); 0 = what the plan wants.
+ * Outputs: *plan as sq_last_plan would give it, and the named scalars of the plan and of its schedule for have_slots:
+ *   path (0 per-lane cast with lights, 1 per-lane deep, 2 per-lane plain, 3 wavefront cast, 4 wavefront deep, 5 three-level pipeline,
+ *   6 per-lane query, 7 wavefront query), ad, mom2, sky, deep, nonneg_materials, n_emitters, cull_off, pixels, px_blocks, px_lds, n_call,
+ *   slots, trace_form, resident, pool, profile, dense, n_lds, stack_cap, trace_blocks, trace_threads, tr_lds, primary_grid, primary_lds,
+ *   aux_blocks, acc_grouped, level1_cull, deep_slot_bytes, need_lights, need_sum2, need_deep, rng_table, rng_grow, chunk_rays;
+ *   have_slots, overlap, tracks, track_slots, batch, n_batches, n_real, query_chunk, tail_kc (the samples of the last batch);
+ *   pp_grid_x, pp_grid_y (per-sample kernels of a full batch), tail_pp_grid_x, tail_pp_grid_y; chunk_0, chunk_1, guide_shift_0,
+ *   guide_shift_1, pixel_major (a full batch's trace launches at bounce level 0 and 1), tail_chunk, lone_chunk (a launch of one ray per pixel);
+ *   ws_cnt ... ws_carry, ws_total (byte offsets of the workspace's arrays, in order: cnt, stats, pix, t0, tri0, sum, mt, mtri, state, org,
+ *   dir, tri1, carry) and deep_oxy, deep_trail, deep_tmiss (of the deep block; -1: none).
+ * Returns 0; 1 when the planner refuses the call (sq_last_error has the call's own refusal, *plan what was planned up to it with
+ * launched = 0, the scalars are 0); 2 for an unknown name or a value no call could have. */
+int sq_plan_call(const char* const* in_names, const int64_t* in_values, int32_t n_in, int64_t have_slots,
+                 sq_plan* plan, const char* const* out_names, int64_t* out_values, int32_t n_out);
 
 /* The table of generator words of a resident scene (squigly_hip.h, option "rng_table_mb"): how many seeds [0, n_cover) it holds
  * for a frame of w rows x h columns at `samples` samples under a budget of budget_bytes.  The frame's seeds are

@@ -152,6 +152,9 @@ def lib():
     L.sq_packed_scalar.argtypes = [vp, C.c_char_p, C.POINTER(C.c_int64)]
     L.sq_packed_free.argtypes = [vp]
     L.sq_packed_free.restype = None
+    if hasattr(L, "sq_plan_call"):       # (a library from before the planner's window, timed against this one through SQ_LIB_PATH, has none)
+        L.sq_plan_call.argtypes = [C.POINTER(C.c_char_p), C.POINTER(C.c_int64), i32, C.c_int64, C.POINTER(Plan),
+                                   C.POINTER(C.c_char_p), C.POINTER(C.c_int64), i32]
     L.sq_bih_scene.argtypes = [vp, C.POINTER(Scene)]
     L.sq_bih_scene.restype = None
     for f in ("height", "num_leaves", "longest_leaf"):
@@ -280,6 +283,6 @@ EXPORTED_SYMBOLS = [
     # include/squigly_host.h
     "sq_mesh_from_obj", "sq_mesh_from_text", "sq_mesh_from_arrays", "sq_mesh_num_tris",
     "sq_mesh_num_materials", "sq_mesh_tris", "sq_mesh_materials", "sq_mesh_free", "sq_camera_from_file",
-    "sq_camera_from_text", "sq_rot_matrix_rads", "sq_release_cached_memory", "sq_mesh_debug_show", "sq_bih_build", "sq_bih_build_device", "sq_cull_boxes", "sq_half_outward", "sq_scene_pack", "sq_packed_array", "sq_packed_scalar", "sq_packed_free", "sq_rng_table_cover", "sq_bih_scene", "sq_bih_height",
+    "sq_camera_from_text", "sq_rot_matrix_rads", "sq_release_cached_memory", "sq_mesh_debug_show", "sq_bih_build", "sq_bih_build_device", "sq_cull_boxes", "sq_half_outward", "sq_scene_pack", "sq_packed_array", "sq_packed_scalar", "sq_packed_free", "sq_plan_call", "sq_rng_table_cover", "sq_bih_scene", "sq_bih_height",
     "sq_bih_num_leaves", "sq_bih_longest_leaf", "sq_bih_free",
 ]

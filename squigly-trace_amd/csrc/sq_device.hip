@@ -37,6 +37,7 @@
 #include "../../include/squigly_host.h"
 #include "sq_error.h"
 #include "sq_pack.h"
+#include "sq_plan.h"
 #include "sq_scene.h"
 
 using sq::f3;
@@ -48,21 +49,7 @@ using namespace sqd;
         if (e_ != hipSuccess) return sq_set_error("%s failed: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
 
-constexpr int kBlock = 256;        // per-pixel / per-sample kernels
-constexpr int kTraceBlock = 512;   // persistent trace kernel, streaming form: 8 waves share one LDS copy of the top of the tree
-constexpr int kResidentBlock = 1024; // persistent trace kernel, resident form: one workgroup per CU owns the whole scene in LDS
 constexpr int kOneshotRowBlock = 2; // rows per block when a one-shot call shards a frame over devices (balance: squigly-trace_amd/dist.py)
-// Slots a wave reserves from the queue per atomic (multiple of 256 for the resident form).  Every reservation stalls
-// the wave for the atomic's round trip and then for the flag loads of the scan, and a sparse chunk (8 % of the slots
-// are live at the second bounce level) serves only part of the idle lanes: 64 -> 128 -> 256 -> 512 slots measured
-// 4340 -> 5110 -> 5520 -> 5605 Msamples/s on the headline frame (768: 5520).  The per-wave list of live slots holds
-// one byte per entry, an index within its 256-slot block (512 B of LDS per wave).
-// The streaming form keeps 128: its rays are 5-10x longer, and on a frame of a few spp a wave that sits on 256 slots
-// at the end of the queue makes the tail longer than the stalls it saves (-7 % at 1920x1080@16).
-constexpr int kChunkResident = 512, kChunkStreaming = 128;
-using LiveT = uint8_t;             // a live slot's index within its chunk
-constexpr int kStatSlots = 32;            // sq_get_stats
-constexpr int kPoolWindows = 1;    // pooled trace kernel: pair windows a wave works on at a time
 // Instruction-arbitration priority of a trace wave (s_setprio) in its return / branch steps, and in its leaf scan and pair windows (and
 // the store / refill that follows them).  Priority 1 in the windows, 0 in the steps: with the flat steps the headline frame takes
 // 52.4-52.5 ms instead of 53.3-53.4 (levels 1, 2 and 3 alike; raising the STEPS instead costs 0.5 ms), one rank's share at 8 ranks
@@ -107,8 +94,7 @@ struct RayFrame : Frame {
     const float* ray_org; const float* ray_dir; const long long* ray_seed;
 };
 // Where a kernel's primary rays come from: the frame's camera (makeRay, src/Lib.hs:107-114), the camera table of a multi-view frame,
-// or the caller's arrays.  Every kernel family is one __global__ template keyed by it ("One entry point per body"): FrameOf<SRC> is the frame it takes.
-constexpr int kSrcCamera = 0, kSrcViews = 1, kSrcRays = 2;
+// or the caller's arrays (kSrcCamera, kSrcViews, kSrcRays: sq_plan.h).  Every kernel family is one __global__ template keyed by it ("One entry point per body"): FrameOf<SRC> is the frame it takes.
 template <int SRC> using FrameOf = std::conditional_t<SRC == kSrcRays, RayFrame, Frame>;
 constexpr int kCamWords = 12;     // a view's entry in the camera table: pos[3], rot[9]
 struct ViewCam { f3 pos; float rot[9]; };
@@ -149,7 +135,7 @@ __device__ __forceinline__ long long primary_tile(const Frame& F, long long q) {
     return (j < F.local_rows && x < F.h) ? j * F.h + x : -1;
 }
 __host__ __device__ __forceinline__ long long primary_padded(const Frame& F) {
-    return (long long)((F.local_rows + F.tile_rows - 1) / F.tile_rows) * F.tiles_x * 64;
+    return (long long)((F.local_rows + F.tile_rows - 1) / F.tile_rows) * F.tiles_x * 64;   // the planner's twin: primary_padded_lanes (sq_plan.h)
 }
 __device__ __forceinline__ void pixel_coords(const Frame& F, long long pix, int& y, int& x) {
     const int j = (int)(pix / F.h);
@@ -1163,22 +1149,7 @@ struct TraceArgs {
                                  // pooled form: [1] iterations (waves), [2] lanes unwinding, [3] lanes descending,
                                  // [4] pair windows (waves), [5] pairs tested, [6] hits folded, [7] refill executions, [8] lanes refilled
 };
-// LDS carve-up of the trace kernel (bytes, all 16-B aligned), shared by host and device.
-struct TraceLds { uint32_t quads, refs, verts, trix, live, tab, stack, total; };
-__host__ __device__ inline TraceLds trace_lds_layout(int n_lds, bool resident, int n_verts, int n_tris,
-                                                     int block, int stack_cap, int stack_elem, bool pool) {
-    auto al = [](uint32_t b) { return (b + 15u) & ~15u; };
-    TraceLds L; uint32_t off = 0;
-    L.verts = off; off += resident ? al((uint32_t)n_verts * 16u) : 0u;     // first: a vertex's LDS address is its byte offset (ResidentTris)
-    L.quads = off; off += al((uint32_t)n_lds * (resident ? 32u : 48u));   // resident: 2 quads per branch; streaming: 3
-    L.refs = off;  off += resident ? al((uint32_t)n_lds * 8u) : 0u;
-    L.trix = off;  off += resident ? al((uint32_t)(n_tris + ResidentTris::kRunPad) * 8u) : 0u;  // + zero records: get_run may read past the last triangle
-    L.live = off;  off += al((uint32_t)(block / 64) * (uint32_t)(resident ? kChunkResident : kChunkStreaming) * (uint32_t)sizeof(LiveT));
-    L.tab = off;   off += pool ? al((uint32_t)block * kPoolWindows) : 0u;   // pooled form: one byte per lane and window in flight
-    L.stack = off; off += al((uint32_t)block * (uint32_t)stack_cap * (uint32_t)stack_elem);
-    L.total = off;
-    return L;
-}
+// (the LDS carve-up of the trace kernel, TraceLds and trace_lds_layout: sq_plan.h)
 
 __device__ __forceinline__ int wave_max(int v) {
 #pragma unroll
@@ -1964,7 +1935,6 @@ __global__ void __launch_bounds__(kBlock) sq_deep_fold(const SceneView S, const 
 // A filled table of generator words: entries [0, cover) (RngView), kRngPad bytes of padding behind them.  Nothing writes to a block
 // once it is filled, so a scene that adopts one only has to be ordered after `filled`, the event recorded behind the fill.
 struct RngTable { uint32_t* words = nullptr; size_t bytes = 0; int64_t cover = 0; hipEvent_t filled = nullptr; };
-constexpr int64_t kRngTableDefaultMb = 24576;   // option "rng_table_mb": 24 GiB = 2^31 seeds (squigly_hip.h)
 struct sq_device_scene {
     int device = 0;
     SceneView view{};
@@ -1977,8 +1947,7 @@ struct sq_device_scene {
     // timing of the dominant kernel
     std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
     double total_ms = 0; int64_t launches = 0;
-    // options
-    int64_t opt_timing = 0, opt_variant = 2, opt_slots = 512ll << 20, opt_straggler = 8, opt_trace_blocks_per_cu = 0, opt_resident = 1, opt_profile = 0, opt_lds_node_kb = 32;
+    Options opt;                  // sq_set_option (sq_plan.h)
     const char* last_kernel = "sq_trace_rays";
     sq_plan plan{}; bool has_plan = false;   // what the last frame's launch_frame chose (sq_last_plan)
     // second stream of the overlapped schedule (launch_frame) and its event pool
@@ -1987,24 +1956,20 @@ struct sq_device_scene {
     float* d_cams = nullptr; int64_t cams_cap = 0;
     // masked calls with second moments: Work::px_sum2, 3 floats per pixel (grow-only; no other call allocates or reads it)
     float* d_px_sum2 = nullptr; int64_t px_sum2_cap = 0;
-    int64_t opt_overlap = 0, opt_aux_blocks_per_cu = 0;
-    // the table of generator words (grow-only, allocated after the workspace; ensure_rng_table) and its budget in MB (0 = none)
+    // the table of generator words (grow-only, allocated after the workspace; ensure_rng_table; its budget: option "rng_table_mb")
     RngTable rng{};
-    int64_t opt_rng_table_mb = kRngTableDefaultMb;
     // caller-given lights (sq_scene_set_lights): the host copy (the reference's light until set, and after a reset), whether it was set,
     // the device table (kMaxLights entries, allocated on first need, filled in stream order) and whether it holds the host copy;
     // cast_carry = the wavefront form's carry of T, 3 floats per pixel at the end of the workspace block
     std::vector<sq_light> lights{ sq_light{ { 0.0f, 3.0f, -1.0f }, { 2.0f, 2.0f, 2.0f } } };
     bool lights_set = false, lights_staged = false;
     float* d_lights = nullptr; float* cast_carry = nullptr;
-    int64_t opt_cast_wavefront = 0;
     // caller-given path depth (sq_scene_set_depth) and option "deep"; d_deep = the wavefront form's per-slot state beyond the three-level
     // pipeline's (Deep: trail, oxy), allocated by the first deep call that needs it (grow-only; a scene that stays at depth 3 has none)
-    int32_t depth = 3; int64_t opt_deep = 0;
+    int32_t depth = 3;
     void* d_deep = nullptr; size_t deep_bytes = 0;
     // caller-given sky (sq_scene_set_sky): host state read by the next call's planning, like the depth; it travels by value (Sky)
     sq_sky sky{}; bool sky_set = false;
-    int64_t opt_pool = 1, opt_refill_min = 12, opt_flush_min = 40, opt_guided = 1, opt_primary_resident = 1, opt_pixel_major = -1, opt_cull = 1, opt_descend_extra = 2, opt_descend_lanes = 16, opt_primary_pooled = 0, opt_coresidency = 0, opt_trace_prio = 0, opt_aux_low_priority = 1, opt_aux_polite = 0, opt_primary_tiles = 1, opt_level1_cull = 1;
 };
 
 extern "C" int sq_scene_upload(const sq_scene* sc, int32_t device, sq_device_scene** out) {
@@ -2147,30 +2112,20 @@ extern "C" int32_t sq_shard_global_row(int32_t j, sq_shard sh) {
 
 namespace {
 
-// Carves the frame workspace out of one allocation (grow-only; allocation happens outside timed steps after warm-up).
+// Carves the frame workspace out of one allocation (grow-only; allocation happens outside timed steps after warm-up), by
+// workspace_layout's offsets (sq_plan.h).
 // If the device cannot give `slots` sample slots the request is halved (down to one sample per pixel): the frame
 // then simply runs in more batches.  A new block's statistics are cleared on `stream`, the call's own: in front of every kernel of the
 // call that counts into them, whichever stream the caller gave (a non-blocking one is not ordered against the null stream).
 int ensure_workspace(sq_device_scene* s, int64_t pixels, int64_t slots, hipStream_t stream) {
     if (pixels <= s->work_pixels && slots <= s->work_slots && s->d_work) return 0;
     pixels = std::max(pixels, s->work_pixels); slots = std::max(slots, s->work_slots);
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
     if (s->d_work) { cache_give(s->device, s->d_work, s->work_bytes); s->d_work = nullptr; s->work_pixels = s->work_slots = 0; }
     size_t block_bytes = 0;
-    size_t off = 0, o_cnt = 0, o_stats = 0, o_pix = 0, o_t0 = 0, o_tri0 = 0, o_sum = 0, o_mt = 0, o_mtri = 0, o_state = 0, o_org = 0, o_dir = 0, o_tri1 = 0, o_carry = 0;
+    WorkLayout L{};
     for (;;) {
-        off = 0;
-        auto take = [&](size_t bytes) { size_t o = off; off += al(bytes); return o; };
-        o_cnt = take(128 * sizeof(int32_t)); o_stats = take(kStatSlots * sizeof(unsigned long long));
-        o_pix = take(pixels * 4); o_t0 = take(pixels * 4); o_tri0 = take(pixels * 4); o_sum = take(pixels * 12);
-        o_mt = take(pixels * 4); o_mtri = take(pixels * 4);
-        // + pixels: the mirror rays' spare region behind the sample slots (state and the two ray quads)
-        o_state = take(slots + pixels); o_org = take((slots + pixels) * 16); o_dir = take((slots + pixels) * 16); o_tri1 = take(slots * 4);
-        o_carry = take(pixels * 12);                                    // behind everything else: no other array moves for it
-        // every array has its own, ordered place in the block: a slip here would be a GPU fault, not an error code
-        if (!(o_cnt < o_stats && o_stats < o_pix && o_pix < o_t0 && o_t0 < o_tri0 && o_tri0 < o_sum && o_sum < o_mt && o_mt < o_mtri &&
-              o_mtri < o_state && o_state < o_org && o_org < o_dir && o_dir < o_tri1 && o_tri1 < o_carry && o_carry < off))
-            return sq_set_error("internal error: frame workspace layout");
+        if (workspace_layout(pixels, slots, L)) return 1;
+        const size_t off = L.total;
         block_bytes = off;
         if ((s->d_work = cache_take(s->device, off, &block_bytes)) != nullptr) break;
         if (hipMalloc(&s->d_work, off) == hipSuccess) break;
@@ -2185,15 +2140,15 @@ int ensure_workspace(sq_device_scene* s, int64_t pixels, int64_t slots, hipStrea
     }
     char* base = (char*)s->d_work;
     Work& W = s->work;
-    int32_t* cnt = (int32_t*)(base + o_cnt);
+    int32_t* cnt = (int32_t*)(base + L.cnt);
     W.n_active = cnt; W.head[0] = cnt + 16; W.head[1] = cnt + 32;      // separate cache lines
-    W.stats = (unsigned long long*)(base + o_stats);
+    W.stats = (unsigned long long*)(base + L.stats);
     if (hipMemsetAsync(W.stats, 0, kStatSlots * sizeof(unsigned long long), stream) != hipSuccess) return sq_set_error("hipMemsetAsync failed");
-    W.px_pixel = (int32_t*)(base + o_pix); W.px_t0 = (float*)(base + o_t0); W.px_tri0 = (int32_t*)(base + o_tri0); W.px_sum = (float*)(base + o_sum);
-    W.px_mt = (float*)(base + o_mt); W.px_mtri = (int32_t*)(base + o_mtri);
-    W.state = (uint8_t*)(base + o_state); W.org = (float4*)(base + o_org); W.dir = (float4*)(base + o_dir); W.tri1 = (int32_t*)(base + o_tri1);
+    W.px_pixel = (int32_t*)(base + L.pix); W.px_t0 = (float*)(base + L.t0); W.px_tri0 = (int32_t*)(base + L.tri0); W.px_sum = (float*)(base + L.sum);
+    W.px_mt = (float*)(base + L.mt); W.px_mtri = (int32_t*)(base + L.mtri);
+    W.state = (uint8_t*)(base + L.state); W.org = (float4*)(base + L.org); W.dir = (float4*)(base + L.dir); W.tri1 = (int32_t*)(base + L.tri1);
     W.slot_capacity = slots;
-    s->cast_carry = (float*)(base + o_carry);
+    s->cast_carry = (float*)(base + L.carry);
     s->work_bytes = block_bytes; s->work_pixels = pixels; s->work_slots = slots;
     return 0;
 }
@@ -2205,7 +2160,7 @@ int ensure_workspace(sq_device_scene* s, int64_t pixels, int64_t slots, hipStrea
 // keeps the table it has (or none), and the lanes it does not cover compute their words.  grow = false (a radiance query, whose
 // seeds the host does not know) takes the table as it is.
 RngView ensure_rng_table(sq_device_scene* s, const Frame& F, hipStream_t stream, bool grow) {
-    const int64_t budget = s->opt_rng_table_mb << 20;
+    const int64_t budget = s->opt.rng_table_mb << 20;
     if (budget <= 0) return RngView{ nullptr, 0 };
     RngTable& T = s->rng;
     const int64_t want = grow ? sq_rng_table_cover(F.w, F.h, F.samples, budget) : 0;
@@ -2251,13 +2206,10 @@ int ensure_px_sum2(sq_device_scene* s, int64_t pixels) {
     s->px_sum2_cap = pixels;
     return 0;
 }
-// The bytes of Deep a slot takes under depth D: a triangle per bounce level, and from D = 4 on the x and y of the ray's origin;
-// under a sky also t of the ray that missed (DeepSky::tmiss), behind the trail.
-size_t deep_slot_bytes(int depth, bool sky) { return depth < 2 ? 0 : (size_t)(depth - 1) * 4 + (depth >= 4 ? 8 : 0) + (sky ? 4 : 0); }
-// The scene's Deep block: room for `slots` slots under `depth` (grow-only, freed as the camera table is: hipFree waits for the device,
+// The scene's Deep block: room for `slots` slots of slot_bytes each (deep_slot_bytes, sq_plan.h; grow-only, freed as the camera table is: hipFree waits for the device,
 // so a block an enqueued frame still uses is not freed under it).
-int ensure_deep(sq_device_scene* s, int64_t slots, int depth, bool sky) {
-    const size_t need = (size_t)slots * deep_slot_bytes(depth, sky);
+int ensure_deep(sq_device_scene* s, int64_t slots, size_t slot_bytes, int depth) {
+    const size_t need = (size_t)slots * slot_bytes;
     if (need <= s->deep_bytes) return 0;
     if (s->d_deep) { SQ_HIP(hipFree(s->d_deep)); s->d_deep = nullptr; s->deep_bytes = 0; }
     if (hipMalloc(&s->d_deep, need) != hipSuccess) { (void)hipGetLastError(); s->d_deep = nullptr; return sq_set_error("hipMalloc(%zu B) for the path trails of depth %d failed", need, depth); }
@@ -2305,10 +2257,10 @@ int stage_lights(sq_device_scene* s, const std::vector<sq_light>& lights, hipStr
 template <typename Fn>
 int timed_launch(sq_device_scene* s, Fn&& fn, const char* name, hipStream_t on) {
     hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (s->opt_timing) { SQ_HIP(hipEventCreate(&e0)); SQ_HIP(hipEventCreate(&e1)); SQ_HIP(hipEventRecord(e0, on)); }
+    if (s->opt.timing) { SQ_HIP(hipEventCreate(&e0)); SQ_HIP(hipEventCreate(&e1)); SQ_HIP(hipEventRecord(e0, on)); }
     fn();
     SQ_HIP(hipGetLastError());
-    if (s->opt_timing) {
+    if (s->opt.timing) {
         SQ_HIP(hipEventRecord(e1, on)); s->pending.emplace_back(e0, e1); s->last_kernel = name;
         if (s->pending.size() > 8192) SQ_HIP(sq_kernel_timing(s, nullptr, nullptr, nullptr) ? hipErrorUnknown : hipSuccess);   // fold, bounded memory
     }
@@ -2330,70 +2282,53 @@ int with_ad_sky(bool ad, bool sky, const SkyT& k, Fn&& fn) {
     return with_ad<CAN_AD>(ad, [&](auto AD) { return sky ? fn(AD, k) : fn(AD); });
 }
 
-// The persistent trace kernel of a frame's wavefront pipeline or of a ray query: its form and launch geometry (plan_trace).
-struct TracePlan {
-    bool resident = false, pool = false;
-    int n_lds = 0, stack_cap = 0, trace_blocks = 0, trace_threads = 0;
-    const void* trace_fn = nullptr;
-    size_t tr_lds = 0;
-};
-// Chooses the trace form -- resident, streaming six-wave or streaming plain -- its LDS layout and workgroups per CU, and fills the
-// trace fields of s->plan.  Refuses (an error code, nothing enqueued) a tree whose stacks do not fit the streaming form's LDS.
-// SRC: the frame's resident primary-ray kernels, whose static LDS is checked with the trace kernels' (an intersection query plans with kSrcCamera).
+// What the planner (sq_plan.h, sq_host.cpp) reads of a scene for `call`: its packed scalars, options, device and state.
+PlanInputs plan_inputs(const sq_device_scene* s, const Call& call, int stack_word) {
+    PlanInputs in;
+    const SceneView& v = s->view;
+    in.opt = s->opt;
+    in.scene.n_branches = v.n_branches; in.scene.n_verts = v.n_verts; in.scene.n_tris = v.n_tris; in.scene.height = v.height;
+    in.scene.has_trix = v.trix != nullptr; in.scene.stack_word = stack_word;
+    in.scene.packed_leaves = v.packed_leaves; in.scene.n_emitters = v.n_emitters; in.scene.nonneg_materials = v.nonneg_materials;
+    in.scene.finite_geometry = v.finite_geometry; in.scene.shortcut_depth = s->shortcut_depth; in.scene.level1_on = s->level1.on;
+    in.device.n_cu = s->n_cu;
+    in.state.depth = s->depth; in.state.sky_set = s->sky_set; in.state.lights_set = s->lights_set; in.state.n_lights = (int32_t)s->lights.size();
+    in.call = call;
+    return in;
+}
+// Plans the call (nothing here touches the device) and stores the public part as the scene's last plan: after a refusal what was planned
+// up to it, otherwise launched = 0 until the caller has ensured its buffers.
+int begin_call(sq_device_scene* s, const PlanInputs& in, CallPlan& C) {
+    const int rc = plan_call(in, C);
+    if (!C.planned) return rc;
+    s->plan = C.plan; s->plan.launched = 0; s->has_plan = true;
+    return rc;
+}
+// The scene view with the call's overrides applied.
+SceneView call_view(const sq_device_scene* s, const CallPlan& C) {
+    SceneView S = s->view;
+    if (C.cull_off) S.cull_o2max = -1.0f;                              // no ray is inside the culling limits: every leaf is tested
+    S.nonneg_materials = C.nonneg_materials; S.n_emitters = C.n_emitters;
+    return S;
+}
+
+// The planned trace kernel: (form, pool, profile) -> entry point.
+template <typename StackT>
+const void* trace_kernel(const CallPlan& C) {
+    if (C.dense) return (const void*)sq_trace_rays_dense<StackT>;
+    if (C.resident)
+        return C.pool ? (C.profile ? (const void*)sq_trace_rays<StackT, true, kResidentBlock, true, true> : (const void*)sq_trace_rays<StackT, true, kResidentBlock, false, true>)
+                      : (C.profile ? (const void*)sq_trace_rays<StackT, true, kResidentBlock, true, false> : (const void*)sq_trace_rays<StackT, true, kResidentBlock, false, false>);
+    return C.pool ? (C.profile ? (const void*)sq_trace_rays<StackT, false, kTraceBlock, true, true> : (const void*)sq_trace_rays<StackT, false, kTraceBlock, false, true>)
+                  : (C.profile ? (const void*)sq_trace_rays<StackT, false, kTraceBlock, true, false> : (const void*)sq_trace_rays<StackT, false, kTraceBlock, false, false>);
+}
+// What the trace kernel needs of the runtime before its first launch: its dynamic LDS above 64 KB, and the static-LDS check of the
+// resident kernels.  SRC: the frame's resident primary-ray kernels, checked with the trace kernels' (an intersection query: kSrcCamera).
 template <typename StackT, int SRC>
-int plan_trace(sq_device_scene* s, const SceneView& S, int stack_cap, TracePlan& T) {
-    sq_plan& P = s->plan;
-    // persistent trace kernel geometry.  Resident form: the whole scene (branches, leaves, unique vertices,
-    // 16-bit indexed triangles) plus every lane's stack fits in the 160 KB of one CU -> one 1024-thread
-    // workgroup per CU, no global traffic except ray fetch and hit store.  Streaming form otherwise.
-    const size_t lds_budget = 160 * 1024;
-    bool resident = false;
-    const bool pool = s->opt_pool != 0;
-    TraceLds L{};
-    if (s->opt_resident && S.trix) {
-        L = trace_lds_layout(S.n_branches, true, S.n_verts, S.n_tris, kResidentBlock, stack_cap, (int)sizeof(StackT), pool);
-        resident = L.total <= lds_budget && S.n_verts <= 4096;         // vertex byte offsets are 16-bit (ResidentTris)
-    }
-    int n_lds = S.n_branches, trace_blocks = 0, trace_threads = 0;
-    const void* trace_fn = nullptr;
-    if (resident) {
-        trace_fn = pool ? (s->opt_profile ? (const void*)sq_trace_rays<StackT, true, kResidentBlock, true, true> : (const void*)sq_trace_rays<StackT, true, kResidentBlock, false, true>)
-                        : (s->opt_profile ? (const void*)sq_trace_rays<StackT, true, kResidentBlock, true, false> : (const void*)sq_trace_rays<StackT, true, kResidentBlock, false, false>);
-        trace_blocks = s->n_cu; trace_threads = kResidentBlock;
-    } else {
-        const size_t max_node_bytes = (size_t)s->opt_lds_node_kb * 1024;     // top of the tree; the rest of LDS buys occupancy
-        const int n_lds_want = (int)std::min<size_t>((size_t)S.n_branches, max_node_bytes / 48);
-        const TraceLds L0 = trace_lds_layout(0, false, S.n_verts, S.n_tris, kTraceBlock, stack_cap, (int)sizeof(StackT), pool);   // stacks, live lists, window tables
-        if (L0.total > lds_budget) return sq_set_error("BIH height %d needs %u B of LDS per workgroup (max %zu)", S.height, L0.total, lds_budget);
-        // Three workgroups per CU (the six-wave build) when a third of the LDS holds a workgroup's stacks plus at least 4 KB of
-        // the tree's top (or all of it); otherwise two, or one, with up to lds_node_kb of tree each.
-        const size_t third = (lds_budget / 3) & ~(size_t)2047;            // 52 KB: the hardware allocates LDS in granules, and 3 x 53.3 KB rounded up does not fit
-        const bool dense_fits = L0.total + std::min<size_t>((size_t)S.n_branches * 48, 4096) + 16 <= third;
-        const bool dense = pool && !s->opt_profile && (s->opt_trace_blocks_per_cu == 0 ? dense_fits : s->opt_trace_blocks_per_cu == 3 && dense_fits);
-        int per_cu;
-        if (dense) {
-            per_cu = 3;
-            n_lds = (int)std::min<size_t>((size_t)n_lds_want, (third - L0.total - 16) / 48);
-        } else {
-            n_lds = n_lds_want;
-            while (n_lds > 0 && trace_lds_layout(n_lds, false, S.n_verts, S.n_tris, kTraceBlock, stack_cap, (int)sizeof(StackT), pool).total > lds_budget) n_lds /= 2;
-        }
-        L = trace_lds_layout(n_lds, false, S.n_verts, S.n_tris, kTraceBlock, stack_cap, (int)sizeof(StackT), pool);
-        if (!dense) {
-            per_cu = (int)std::max<size_t>(1, std::min<size_t>(2, lds_budget / L.total));    // the plain build's 86 VGPRs allow four waves per SIMD = two workgroups
-            if (s->opt_trace_blocks_per_cu > 0) per_cu = (int)std::min<int64_t>(s->opt_trace_blocks_per_cu, (int64_t)std::max<size_t>(1, lds_budget / L.total));
-        }
-        trace_fn = dense ? (const void*)sq_trace_rays_dense<StackT>
-                 : pool ? (s->opt_profile ? (const void*)sq_trace_rays<StackT, false, kTraceBlock, true, true> : (const void*)sq_trace_rays<StackT, false, kTraceBlock, false, true>)
-                        : (s->opt_profile ? (const void*)sq_trace_rays<StackT, false, kTraceBlock, true, false> : (const void*)sq_trace_rays<StackT, false, kTraceBlock, false, false>);
-        trace_blocks = s->n_cu * per_cu; trace_threads = kTraceBlock;
-    }
-    const size_t tr_lds = L.total;
-    P.trace_form = resident ? SQ_FORM_RESIDENT : trace_fn == (const void*)sq_trace_rays_dense<StackT> ? SQ_FORM_STREAMING_SIX_WAVE : SQ_FORM_STREAMING_PLAIN;
-    P.blocks_per_cu = trace_blocks / s->n_cu; P.n_lds = n_lds; P.trace_lds_bytes = (int32_t)tr_lds;
-    if (tr_lds > 64 * 1024) SQ_HIP(hipFuncSetAttribute(trace_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tr_lds));
-    static bool static_lds_checked = false;                           // per StackT instantiation; once per process is enough
-    if (resident && !static_lds_checked) {
+int prepare_trace(const CallPlan& C, const void* trace_fn) {
+    if (C.tr_lds > 64 * 1024) SQ_HIP(hipFuncSetAttribute(trace_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)C.tr_lds));
+    static bool static_lds_checked = false;                           // per instantiation; once per process is enough
+    if (C.resident && !static_lds_checked) {
         // ResidentTris takes a vertex's byte offset for its LDS address: the vertex table must sit at LDS address 0, i.e. the
         // kernels that stage a resident scene must own no static __shared__ (their dynamic LDS then starts at 0).  Checked here,
         // where a violation is an error code, rather than by the device-side trap, where it would be a GPU abort.
@@ -2408,199 +2343,125 @@ int plan_trace(sq_device_scene* s, const SceneView& S, int stack_cap, TracePlan&
         }
         static_lds_checked = true;
     }
-    T.resident = resident; T.pool = pool; T.n_lds = n_lds; T.stack_cap = stack_cap;
-    T.trace_blocks = trace_blocks; T.trace_threads = trace_threads; T.trace_fn = trace_fn; T.tr_lds = tr_lds;
     return 0;
 }
 
-// What a frame and an intersection query do first, alike: the scene view with the options applied, the per-lane stacks' size, and the
-// fixed part of s->plan.
-template <typename StackT>
-SceneView begin_plan(sq_device_scene* s, int& stack_cap, size_t& px_lds) {
-    SceneView S = s->view;
-    if (!s->opt_cull) S.cull_o2max = -1.0f;                            // no ray is inside the culling limits: every leaf is tested
-    stack_cap = std::max(S.height, 1);
-    px_lds = (size_t)kBlock * stack_cap * sizeof(StackT);
-    sq_plan& P = s->plan;
-    P = sq_plan{};
-    P.variant = (int32_t)s->opt_variant; P.stack_word_bytes = (int32_t)sizeof(StackT); P.height = S.height; P.stack_cap = stack_cap;
-    P.pixel_lds_bytes = (int32_t)px_lds; P.packed_leaves = S.packed_leaves; P.n_emitters = S.n_emitters;
-    P.trace_form = SQ_FORM_PER_PIXEL; P.primary_form = SQ_PRIMARY_NONE;
-    s->has_plan = true;
-    return S;
-}
-
 // One launch of the planned trace kernel over the queue of W: *W.n_active x kc slots (+ *W.n_active front slots with the mirror
-// rays).  queue_rays x kc sizes its reservations: a frame's pixels (every pixel may be active), a query chunk's rays.
-int launch_trace_kernel(sq_device_scene* s, const SceneView& S, const TracePlan& T, const Work& W, int64_t queue_rays, int kc, int level,
+// rays).  queue_rays x kc sizes its reservations (trace_launch, sq_plan.h): a frame's pixels (every pixel may be active), a query chunk's rays.
+int launch_trace_kernel(sq_device_scene* s, const SceneView& S, const CallPlan& C, const void* trace_fn, const Work& W, int64_t queue_rays, int kc, int level,
                         hipStream_t on, bool with_mirror_rays) {
-    const bool resident = T.resident;
-    const int trace_blocks = T.trace_blocks, trace_threads = T.trace_threads;
-    // a launch with few slots (the per-pixel mirror rays) takes small reservations, or only a few waves get any
-    const int max_chunk = resident ? kChunkResident : kChunkStreaming;
-    const int64_t per_wave = queue_rays * (int64_t)kc / std::max(1, trace_blocks * (trace_threads / 64));
-    const int chunk = (int)std::min<int64_t>(max_chunk, std::max<int64_t>(64, (per_wave / 8) / 64 * 64));
-    // queue order: a pixel's samples in a row pays once the triangles no longer fit the L2s (rays that start at one point
-    // share their first leaves: 1M-triangle scene +2.5 %), and costs 1-7 % below that (strided queue reads)
-    const bool pixel_major = s->opt_pixel_major < 0 ? (!resident && (size_t)S.n_tris * sizeof(DevTri) > ((size_t)4 << 20)) : s->opt_pixel_major != 0;
-    int guide_shift = 2;                                            // log2(4 x waves of the launch), rounded up
-    while ((1ll << guide_shift) < 4ll * trace_blocks * (trace_threads / 64)) ++guide_shift;
-    if (!((s->opt_guided >> level) & 1)) guide_shift = 62;         // bit 0: first bounce level (and the mirror / primary launches), bit 1: second
+    const Options& o = s->opt;
+    const TraceLaunch T = trace_launch(C, queue_rays, kc, level);
     TraceArgs A{ W.org, W.dir, W.state, level == 0 ? (int32_t)kRay1 : (int32_t)kRay2, (long long)s->work.slot_capacity, with_mirror_rays ? 1 : 0,
-                 W.n_active, kc, W.head[level], T.n_lds, T.stack_cap, (int32_t)s->opt_straggler, chunk, guide_shift,
-                 (int32_t)s->opt_refill_min, (int32_t)s->opt_flush_min, (int32_t)s->opt_descend_extra, (int32_t)s->opt_descend_lanes,
-                 (int32_t)(s->opt_coresidency ? 1 : 0), (int32_t)s->opt_trace_prio, (int32_t)pixel_major, W.stats };
+                 W.n_active, kc, W.head[level], C.n_lds, C.stack_cap, (int32_t)o.straggler_lanes, T.chunk, T.guide_shift,
+                 (int32_t)o.refill_min, (int32_t)o.flush_min, (int32_t)o.descend_extra, (int32_t)o.descend_lanes,
+                 (int32_t)(o.coresidency ? 1 : 0), (int32_t)o.trace_prio, (int32_t)T.pixel_major, W.stats };
     SceneView Sv = S;
     return timed_launch(s, [&] {
         void* kargs[] = { (void*)&Sv, (void*)&A };
-        (void)hipLaunchKernel(T.trace_fn, dim3(trace_blocks), dim3(trace_threads), kargs, T.tr_lds, on);
+        (void)hipLaunchKernel(trace_fn, dim3(C.trace_blocks), dim3(C.trace_threads), kargs, C.tr_lds, on);
     }, "sq_trace_rays", on);
 }
 
+// A frame: plan (plan_call), ensure its buffers, schedule for the slots the workspace got (plan_schedule), enqueue.  Every size, grid
+// and threshold comes from the plan; what is decided here needs HIP or the template arguments.
 // kSrcViews: a multi-view frame; `cams` (host, F.n_views of them) are staged into the scene's camera table F.cams once the frame is planned.
 // kSrcRays: a chunk of a radiance query (radiance_rays): a frame of one row whose "pixels" are the caller's rays F.ray_org / ray_dir / ray_seed.
 template <typename StackT, int SRC>
 int launch_frame(sq_device_scene* s, const FrameOf<SRC>& F, hipStream_t stream, const sq_camera* cams) {
-    int stack_cap; size_t px_lds;
-    SceneView S = begin_plan<StackT>(s, stack_cap, px_lds);
-    // nonneg_materials bounds the radiance below an absorbing surface for the reference's depth.  A deeper path nests more products,
-    // one of which may be inf where the bound still held: 0 * inf is NaN in the reference, so past the packer's shortcut_depth
-    // (sq_host.cpp, material_flags) the generic-depth kernels of this launch take no s == 0 shortcut.
-    if (!F.cast && s->depth > 3 && s->depth > s->shortcut_depth) S.nonneg_materials = 0;
-    // Under a sky neither the absorbing-surface shortcut nor the last ray's emitter pre-test is an identity as it stands (the last ray
-    // adds the sky when it misses; 0 * sky is NaN for an infinite sky): this launch's generic-depth kernels take neither.
-    const bool sky = !F.cast && s->sky_set;
-    if (sky) { S.nonneg_materials = 0; S.n_emitters = -1; s->plan.n_emitters = -1; }
+    Call call;
+    call.src = SRC; call.cast = F.cast != 0; call.masked = F.mask || F.sum2 || F.count; call.mom2 = F.sum2 != nullptr;
+    call.n_views = F.n_views; call.local_rows = F.local_rows; call.h = F.h; call.tile_rows = F.tile_rows; call.tiles_x = F.tiles_x;
+    call.k_begin = F.k_begin; call.k_end = F.k_end;
+    CallPlan C;
+    if (begin_call(s, plan_inputs(s, call, (int)sizeof(StackT)), C)) return 1;     // refused: no allocation, free or memset has happened
+    sq_plan& P = s->plan;
+    const SceneView S = call_view(s, C);
+    const bool ad = C.ad, sky = C.sky;
+    const int depth = s->depth, n_lights = C.in.state.n_lights, n_call = C.n_call;
+    const long long pixels = C.pixels;
+    const size_t px_lds = C.px_lds;
     Sky KS{};
     if (sky) { std::memcpy(KS.up, s->sky.up, sizeof KS.up); std::memcpy(KS.down, s->sky.down, sizeof KS.down); }
-    sq_plan& P = s->plan;
-    const long long pixels = (long long)F.n_views * F.local_rows * F.h;   // every view's pixels, view-major
-    const long long px_blocks = (pixels + kBlock - 1) / kBlock;
-    // a masked call (sq_render_rows_device_masked with a mask, second moments or counts) takes the AD instantiations of the kernels that
-    // decide who is active, and clears no buffer; every other call takes the instantiations, and the memsets, it always took
-    const bool ad = SRC == kSrcCamera && (F.mask || F.sum2 || F.count);
-    const bool mom2 = ad && F.sum2;
-    if (px_blocks > 0x7fffffffLL) return sq_set_error("image too large for one launch");
-    if (px_lds > 160 * 1024) return sq_set_error("BIH height %d needs %zu B of LDS stack per workgroup (max 163840)", S.height, px_lds);
-    // a cast frame: the per-lane form, or (option "cast_wavefront" with variant 2) the wavefront form with the lights as its samples
-    const bool cast_wave = F.cast && s->opt_variant == 2 && s->opt_cast_wavefront;
-    const int n_lights = (int)s->lights.size();
-    // a path-traced frame or query under a depth other than 3 (or under option "deep"): the generic-depth kernels
-    const int depth = s->depth;
-    const bool deep = !F.cast && (depth != 3 || s->opt_deep || sky);
     // The per-lane forms: one kernel, one lane per pixel.  The branches below choose the kernel and what follows S and F in its arguments.
     constexpr bool kCanAd = SRC == kSrcCamera;
     auto launch_per_lane = [&](auto kernel, const char* name, auto... args) -> int {
         if (px_lds > 64 * 1024) SQ_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)px_lds));
         P.launched = 1;
         if (stage_cams(s, F, cams, stream)) return 1;
-        return timed_launch(s, [&] { hipLaunchKernelGGL(kernel, dim3((unsigned)px_blocks), dim3(kBlock), px_lds, stream, S, F, args...); }, name, stream);
+        return timed_launch(s, [&] { hipLaunchKernelGGL(kernel, dim3((unsigned)C.px_blocks), dim3(kBlock), px_lds, stream, S, F, args...); }, name, stream);
     };
-    if (F.cast && !cast_wave && s->lights_set) {                       // caller-given lights: sq_cast_pixels beside sq_render_pixels
+    if (C.path == kPathLaneCast) {                                     // caller-given lights: sq_cast_pixels beside sq_render_pixels
         const Lights L{ s->d_lights, n_lights, nullptr, 0, n_lights };
         return with_ad<kCanAd>(ad, [&](auto AD) { return launch_per_lane(sq_cast_pixels<StackT, SRC, AD()>, "sq_cast_pixels", L); });
     }
-    if (s->opt_variant == 1 && deep)                                    // a depth other than 3, or a sky: sq_render_pixels_deep beside sq_render_pixels
+    if (C.path == kPathLaneDeep)                                       // a depth other than 3, or a sky: sq_render_pixels_deep beside sq_render_pixels
         return with_ad_sky<kCanAd>(ad, sky, KS, [&](auto AD, auto... K) {
             return launch_per_lane(sq_render_pixels_deep<StackT, SRC, AD(), decltype(K)...>, sizeof...(K) ? "sq_render_pixels_deep_sky" : "sq_render_pixels_deep", depth, K...);
         });
-    if (s->opt_variant == 1 || (F.cast && !cast_wave))
+    if (C.path == kPathLanePlain)
         return with_ad<kCanAd>(ad, [&](auto AD) { return launch_per_lane(sq_render_pixels<StackT, SRC, AD()>, "sq_render_pixels"); });
     // ---- wavefront pipeline ----
-    // the samples this call renders (a whole frame: F.samples); in a cast frame the lights take the samples' place in the slots
-    const int n_call = cast_wave ? n_lights : F.k_end - F.k_begin;
-    // at least one sample of every pixel per batch, never more slots than the call has samples
-    const int64_t slots = std::max<int64_t>(pixels, std::min<int64_t>(s->opt_slots, (int64_t)pixels * n_call));
-    if (ensure_workspace(s, pixels, slots, stream)) return 1;
-    if (mom2 && ensure_px_sum2(s, pixels)) return 1;
-    s->work.px_sum2 = mom2 ? s->d_px_sum2 : nullptr;
+    const bool cast_wave = C.path == kPathWaveCast, deep = C.path == kPathWaveDeep;
+    const void* const trace_fn = trace_kernel<StackT>(C);
+    if (prepare_trace<StackT, SRC>(C, trace_fn)) return 1;
+    if (ensure_workspace(s, pixels, C.slots, stream)) return 1;
+    if (C.need_sum2 && ensure_px_sum2(s, pixels)) return 1;
+    s->work.px_sum2 = C.need_sum2 ? s->d_px_sum2 : nullptr;
     const Work& W = s->work;
-    const int64_t have_slots = W.slot_capacity;
-    // Overlapped schedule: the sample batches alternate between two halves of the workspace ("tracks"); every
-    // trace launch stays on the caller's stream, in the order T1(a) T1(b) T2(a) T2(b), while the per-sample
-    // kernels (RNG + bounce, shading, accumulation) run on a second stream beside them, ordered by events.
-    // Opt-in (sq_set_option "overlap"): measured +3 % on the headline frame (105.5 -> 102.3 ms) -- the kernels do
-    // run side by side, but the chip is VALU-bound as a whole, so each slows the other down by what it gains;
-    // and trace-launch durations then include that interference, which blurs the per-kernel roofline figure.
-    const bool overlap = s->opt_overlap && !cast_wave && !deep && n_call >= 2 && have_slots >= 2 * pixels;
-    const int tracks = overlap ? 2 : 1;
-    const int64_t track_slots = have_slots / tracks;
+    if (C.need_lights && ensure_light_table(s)) return 1;
+    if (C.need_deep && ensure_deep(s, W.slot_capacity, C.deep_slot_bytes, depth)) return 1;
+    // the slots the workspace got (the allocation may have halved them): tracks, batches and, per launch, grids and reservations
+    const Schedule Sch = plan_schedule(C, W.slot_capacity);
+    const bool overlap = Sch.overlap;
+    const int batch = Sch.batch, n_real = Sch.n_real;
     Work Wt[2] = { W, W };
-    if (overlap) {
+    if (overlap) {                                                     // the second track: the other half of the slots, cursors of its own
         Work& V = Wt[1];
-        V.state += track_slots; V.org += track_slots; V.dir += track_slots; V.tri1 += track_slots;
+        V.state += Sch.track_slots; V.org += Sch.track_slots; V.dir += Sch.track_slots; V.tri1 += Sch.track_slots;
         V.head[0] = W.n_active + 64 + 16; V.head[1] = W.n_active + 64 + 32;
     }
-    // samples per batch: as many as a track holds, split evenly (few large launches: a small trace launch
-    // wastes its ramp-up and drain, and the second-bounce launches only carry a few percent of the slots)
-    const int max_batch = (int)std::max<int64_t>(1, std::min<int64_t>(n_call, track_slots / pixels));
-    const int n_batches = std::max(tracks, (n_call + max_batch - 1) / max_batch);
-    const int batch = (n_call + n_batches - 1) / n_batches;
-    TracePlan TP;
-    if (plan_trace<StackT, SRC>(s, S, stack_cap, TP)) return 1;
-    const int aux_blocks = s->n_cu * (int)(s->opt_aux_blocks_per_cu ? s->opt_aux_blocks_per_cu : 8);
-    // sq_accumulate, by second moments and by its loop form: the grouped loop when the shard has no more pixels than the launch has
-    // threads (every thread at most one pixel)
-    const bool acc_grouped = pixels <= (long long)aux_blocks * kBlock;
+    const int aux_blocks = C.aux_blocks;
+    // sq_accumulate, by second moments and by its loop form (acc_grouped: every thread at most one pixel)
     void (*const accumulate_kernel)(SceneView, Frame, Work, int, int) =
-        mom2 ? (acc_grouped ? &sq_accumulate<true, true> : &sq_accumulate<false, true>) : (acc_grouped ? &sq_accumulate<true> : &sq_accumulate<false>);
-    const bool resident = TP.resident, pool = TP.pool;
-    P.primary_form = (s->opt_primary_pooled && pool) ? SQ_PRIMARY_POOLED : (resident && s->opt_primary_resident) ? SQ_PRIMARY_RESIDENT : SQ_PRIMARY_PER_LANE;
-    // the per-lane primary pass is one launch with a thread per tile lane, padding included (a narrow frame's edge tiles are mostly
-    // padding: up to 64 lanes per pixel at h = 1), and a launch has at most 2^32 - 1 threads; the other two passes stride over a fixed grid
-    if (P.primary_form == SQ_PRIMARY_PER_LANE && (primary_padded(F) * F.n_views + kBlock - 1) / kBlock * kBlock > 0xffffffffLL)
-        return sq_set_error("image too large for one launch of the primary rays (%lld tile lanes; at most 2^32 - 1)", primary_padded(F) * F.n_views);
-    if (cast_wave && ensure_light_table(s)) return 1;
-    if (deep && ensure_deep(s, W.slot_capacity, depth, sky)) return 1;
+        C.mom2 ? (C.acc_grouped ? &sq_accumulate<true, true> : &sq_accumulate<false, true>) : (C.acc_grouped ? &sq_accumulate<true> : &sq_accumulate<false>);
     P.launched = 1;                                                    // planned; what follows fails only on HIP errors
-    // nothing is enqueued before this point, so a refusal above leaves every buffer as it was
+    // nothing is enqueued before this point, and a refused call has not come this far: it leaves every buffer as it was
     if (stage_cams(s, F, cams, stream)) return 1;                       // multi-view: before every kernel that reads the table (e_setup below)
     if (cast_wave && !s->lights_staged) {                               // never set: the table receives the reference's light
         if (stage_lights(s, s->lights, stream)) return 1;
         s->lights_staged = true;
     }
-    const RngView R = cast_wave ? RngView{ nullptr, 0 } : ensure_rng_table(s, F, stream, SRC != kSrcRays && !deep);   // allocated behind the workspace; its fill and the wait for it come before every sq_gen_bounce1 (e_setup below)
+    const RngView R = C.rng_table ? ensure_rng_table(s, F, stream, C.rng_grow) : RngView{ nullptr, 0 };   // allocated behind the workspace; its fill and the wait for it come before every sq_gen_bounce1 (e_setup below)
     // (a masked call's dead pixels keep what they hold: its primary kernels write the black of the live misses, store_live_miss)
     if (F.out_avg && !ad) SQ_HIP(hipMemsetAsync(F.out_avg, 0, (size_t)pixels * 3 * sizeof(float), stream));   // pixels whose primary ray misses: black
     if (F.out_rgb && !ad) SQ_HIP(hipMemsetAsync(F.out_rgb, 0, (size_t)pixels * 3, stream));
     SQ_HIP(hipMemsetAsync(W.n_active, 0, 128 * sizeof(int32_t), stream));
     // primary rays: once per pixel.  With a resident scene they are traced out of LDS as well ...
     if (P.primary_form == SQ_PRIMARY_RESIDENT) {
-        const TraceLds Lp = trace_lds_layout(S.n_branches, true, S.n_verts, S.n_tris, kResidentBlock, stack_cap, (int)sizeof(StackT), false);
-        const long long need = (primary_padded(F) * F.n_views + kResidentBlock - 1) / kResidentBlock;
         if (with_ad_sky<kCanAd>(ad, sky, KS, [&](auto AD, auto... K) -> int {
                 const auto kernel = sq_primary_resident<StackT, SRC, AD(), decltype(K)...>;
-                SQ_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)Lp.total));
-                hipLaunchKernelGGL(kernel, dim3((unsigned)std::min<long long>(s->n_cu, need)), dim3(kResidentBlock), Lp.total, stream, S, F, W, stack_cap, K...);
+                SQ_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)C.primary_lds));
+                hipLaunchKernelGGL(kernel, dim3((unsigned)C.primary_grid), dim3(kResidentBlock), C.primary_lds, stream, S, F, W, C.stack_cap, K...);
                 return 0;
             })) return 1;
     } else if (P.primary_form == SQ_PRIMARY_PER_LANE) {
         if (with_ad_sky<kCanAd>(ad, sky, KS, [&](auto AD, auto... K) -> int {
                 const auto kernel = sq_primary<StackT, SRC, AD(), decltype(K)...>;
                 if (px_lds > 64 * 1024) SQ_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)px_lds));
-                hipLaunchKernelGGL(kernel, dim3((unsigned)((primary_padded(F) * F.n_views + kBlock - 1) / kBlock)), dim3(kBlock), px_lds, stream, S, F, W, K...);
+                hipLaunchKernelGGL(kernel, dim3((unsigned)C.primary_grid), dim3(kBlock), px_lds, stream, S, F, W, K...);
                 return 0;
             })) return 1;
     }
     SQ_HIP(hipGetLastError());
-    // per-sample kernels that run one thread per active pixel: x covers the pixels, y splits a pixel's samples when the
-    // frame has too few pixels to fill the chip (one rank's share of a frame, small frames)
-    auto pp_grid = [&](int kc) {
-        // Overlapped schedules, option "aux_polite" = n > 0: the per-sample kernels get n workgroups per CU in all (grid-stride
-        // loops do the rest), few enough that a trace workgroup -- 16 waves, all of the CU's LDS, 4 x 104 VGPRs per SIMD -- can
-        // always be placed beside them, whichever kernel reaches a CU first.
-        if (overlap && s->opt_aux_polite > 0) return dim3((unsigned)(s->n_cu * (int)s->opt_aux_polite), 1u);
-        const long long bx = std::max<long long>(1, std::min<long long>((pixels + kBlock - 1) / kBlock, 1 << 20));
-        const long long want_threads = (long long)s->n_cu * 2048 * 2;
-        const long long ks = std::max<long long>(1, std::min<long long>(std::min(kc, 64), (want_threads + pixels - 1) / std::max<long long>(pixels, 1)));
-        return dim3((unsigned)bx, (unsigned)ks);
-    };
+    // per-sample kernels that run one thread per active pixel, for a batch of kc samples (pp_grid, sq_plan.h)
+    auto grid_of = [&](int kc) { const Grid2 g = pp_grid(C, Sch, kc); return dim3(g.x, g.y); };
     if (P.primary_form == SQ_PRIMARY_POOLED) {                          // ... or through the pooled trace kernel
         Work Wp = W; Wp.n_active = W.n_active + 48;                     // the launch's queue is the shard's pixels, not the active ones
         SQ_HIP(hipMemsetAsync(W.head[0], 0, 32 * sizeof(int32_t), stream));
         with_ad<kCanAd>(ad, [&](auto AD) { hipLaunchKernelGGL((sq_primary_gen<SRC, AD()>), dim3(aux_blocks), dim3(kBlock), 0, stream, F, W, pixels); return 0; });
         SQ_HIP(hipGetLastError());
-        if (launch_trace_kernel(s, S, TP, Wp, pixels, 1, 0, stream, false)) return 1;
+        if (launch_trace_kernel(s, S, C, trace_fn, Wp, pixels, 1, 0, stream, false)) return 1;
         with_ad_sky<kCanAd>(ad, sky, KS, [&](auto AD, auto... K) {
             hipLaunchKernelGGL((sq_primary_store<AD(), decltype(K)...>), dim3(aux_blocks), dim3(kBlock), 0, stream, F, W, pixels, K...);
             return 0;
@@ -2614,9 +2475,9 @@ int launch_frame(sq_device_scene* s, const FrameOf<SRC>& F, hipStream_t stream, 
             const int l0 = i * batch, kc = std::min(batch, n_lights - l0);
             const Lights L{ s->d_lights, n_lights, s->cast_carry, l0, l0 + kc };
             SQ_HIP(hipMemsetAsync(W.head[0], 0, 32 * sizeof(int32_t), stream));     // both dequeue cursors
-            hipLaunchKernelGGL(sq_cast_gen<SRC>, pp_grid(kc), dim3(kBlock), 0, stream, S, F, W, L);
+            hipLaunchKernelGGL(sq_cast_gen<SRC>, grid_of(kc), dim3(kBlock), 0, stream, S, F, W, L);
             SQ_HIP(hipGetLastError());
-            if (launch_trace_kernel(s, S, TP, W, pixels, kc, 0, stream, false)) return 1;
+            if (launch_trace_kernel(s, S, C, trace_fn, W, pixels, kc, 0, stream, false)) return 1;
             hipLaunchKernelGGL(sq_cast_fold<SRC>, dim3(aux_blocks), dim3(kBlock), 0, stream, S, F, W, L, l0 + kc == n_lights ? 1 : 0);
             SQ_HIP(hipGetLastError());
         }
@@ -2626,21 +2487,22 @@ int launch_frame(sq_device_scene* s, const FrameOf<SRC>& F, hipStream_t stream, 
         // Sample batch i holds the samples [k0, k0 + kc): ray 1 into the slots, then level by level a trace launch and the bounce behind
         // it, then the ordered fold.  Everything on the caller's stream ("overlap" is for the three-level pipeline).
         const long long cap = (long long)W.slot_capacity;
-        float2* const oxy = (float2*)s->d_deep;
-        int32_t* const trail = (int32_t*)((char*)s->d_deep + (depth >= 4 ? (size_t)cap * sizeof(float2) : 0));
-        const DeepSky DS{ KS, sky && depth >= 2 ? (float*)(trail + (size_t)(depth - 1) * cap) : nullptr };
+        const DeepLayout DL = deep_layout(depth, sky, cap);
+        float2* const oxy = (float2*)((char*)s->d_deep + DL.oxy);
+        int32_t* const trail = (int32_t*)((char*)s->d_deep + DL.trail);
+        const DeepSky DS{ KS, DL.has_tmiss ? (float*)((char*)s->d_deep + DL.tmiss) : nullptr };
         for (int i = 0; i * batch < n_call; ++i) {
             const int k0 = F.k_begin + i * batch, kc = std::min(batch, n_call - i * batch);
             if (depth >= 2) {
                 SQ_HIP(hipMemsetAsync(W.head[0], 0, 32 * sizeof(int32_t), stream));     // both dequeue cursors
-                hipLaunchKernelGGL(sq_deep_gen<SRC>, pp_grid(kc), dim3(kBlock), 0, stream, S, F, W, k0, kc, R);
+                hipLaunchKernelGGL(sq_deep_gen<SRC>, grid_of(kc), dim3(kBlock), 0, stream, S, F, W, k0, kc, R);
                 SQ_HIP(hipGetLastError());
             }
             for (int b = 1; b < depth; ++b) {
                 const Deep D{ depth, b, trail, oxy, cap };
                 if (b >= 3) SQ_HIP(hipMemsetAsync(W.head[0], 0, 32 * sizeof(int32_t), stream));   // a cursor's second use
-                if (launch_trace_kernel(s, S, TP, W, pixels, kc, (b - 1) & 1, stream, false)) return 1;
-                with_sky(sky, DS, [&](auto... K) { hipLaunchKernelGGL((sq_deep_bounce<SRC, decltype(K)...>), pp_grid(kc), dim3(kBlock), 0, stream, S, F, W, k0, kc, D, K...); return 0; });
+                if (launch_trace_kernel(s, S, C, trace_fn, W, pixels, kc, (b - 1) & 1, stream, false)) return 1;
+                with_sky(sky, DS, [&](auto... K) { hipLaunchKernelGGL((sq_deep_bounce<SRC, decltype(K)...>), grid_of(kc), dim3(kBlock), 0, stream, S, F, W, k0, kc, D, K...); return 0; });
                 SQ_HIP(hipGetLastError());
             }
             const Deep D{ depth, 0, trail, oxy, cap };
@@ -2652,23 +2514,20 @@ int launch_frame(sq_device_scene* s, const FrameOf<SRC>& F, hipStream_t stream, 
     // batch i holds the samples [k0_of(i), k0_of(i) + kc_of(i)) of [k_begin, k_end); the call's last batch ends the fold (sq_accumulate)
     auto k0_of = [&](int i) { return F.k_begin + i * batch; };
     auto kc_of = [&](int i) { return std::max(0, std::min(batch, n_call - i * batch)); };
-    int n_real = 0;
-    while (n_real < n_batches && kc_of(n_real) > 0) ++n_real;
     // The steps of batch i, each on the stream `on` and over the batch's track Wt[i & 1]; the schedules below say only which stream a
     // step goes on and which events order it.
     auto launched = []() -> int { SQ_HIP(hipGetLastError()); return 0; };
-    // Level-1 culling (sq_host.cpp, level1_tables): the three-level pipeline only, and only with the shortcuts its lemma builds on
+    // Level-1 culling (sq_host.cpp, level1_tables): where the plan says so
     Level1Cull L1 = s->level1;
-    L1.on = L1.on && s->opt_level1_cull && S.n_emitters >= 0 && S.nonneg_materials && S.finite_geometry;
-    P.level1_cull = L1.on;
+    L1.on = C.level1_cull;
     auto gen = [&](int i, hipStream_t on) -> int {
         SQ_HIP(hipMemsetAsync(Wt[i & 1].head[0], 0, 32 * sizeof(int32_t), on));     // both dequeue cursors
-        hipLaunchKernelGGL(sq_gen_bounce1<SRC>, pp_grid(kc_of(i)), dim3(kBlock), 0, on, S, F, Wt[i & 1], k0_of(i), kc_of(i), R, L1);
+        hipLaunchKernelGGL(sq_gen_bounce1<SRC>, grid_of(kc_of(i)), dim3(kBlock), 0, on, S, F, Wt[i & 1], k0_of(i), kc_of(i), R, L1);
         return launched();
     };
-    auto trace = [&](int i, int level, hipStream_t on, bool with_mirror) -> int { return launch_trace_kernel(s, S, TP, Wt[i & 1], pixels, kc_of(i), level, on, with_mirror); };
+    auto trace = [&](int i, int level, hipStream_t on, bool with_mirror) -> int { return launch_trace_kernel(s, S, C, trace_fn, Wt[i & 1], pixels, kc_of(i), level, on, with_mirror); };
     auto shade = [&](int i, hipStream_t on) -> int {
-        hipLaunchKernelGGL(sq_shade1<SRC>, pp_grid(kc_of(i)), dim3(kBlock), 0, on, S, F, Wt[i & 1], kc_of(i));
+        hipLaunchKernelGGL(sq_shade1<SRC>, grid_of(kc_of(i)), dim3(kBlock), 0, on, S, F, Wt[i & 1], kc_of(i));
         return launched();
     };
     auto accumulate = [&](int i, hipStream_t on, bool last) -> int {     // in batch order: the per-pixel sum is ordered (src/Lib.hs:88)
@@ -2700,7 +2559,7 @@ int launch_frame(sq_device_scene* s, const FrameOf<SRC>& F, hipStream_t stream, 
     }
     // The overlapped schedules give the mirror rays a launch of their own, before the tracks split.
     SQ_HIP(hipMemsetAsync(W.head[0], 0, 32 * sizeof(int32_t), stream));
-    if (mirror_gen(0) || launch_trace_kernel(s, S, TP, W, pixels, 1, 0, stream, false) || mirror_store(0)) return 1;
+    if (mirror_gen(0) || launch_trace_kernel(s, S, C, trace_fn, W, pixels, 1, 0, stream, false) || mirror_store(0)) return 1;
     if (!s->aux) {
         // The second stream carries the per-sample kernels (overlap 1) or the odd batches (overlap 2).  Lowest priority: when a
         // trace launch and a per-sample kernel become ready together, the trace workgroups (one per CU, all of its LDS) must be
@@ -2708,7 +2567,7 @@ int launch_frame(sq_device_scene* s, const FrameOf<SRC>& F, hipStream_t stream, 
         // for whole CUs to drain (rocprofv3 timeline, profiles/r03c_timeline_clocks_coresidency.txt).
         int least = 0, greatest = 0;
         SQ_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest));
-        if (s->opt_aux_low_priority) SQ_HIP(hipStreamCreateWithPriority(&s->aux, hipStreamNonBlocking, least));    // `least` = numerically largest = lowest priority
+        if (s->opt.aux_low_priority) SQ_HIP(hipStreamCreateWithPriority(&s->aux, hipStreamNonBlocking, least));    // `least` = numerically largest = lowest priority
         else SQ_HIP(hipStreamCreateWithFlags(&s->aux, hipStreamNonBlocking));
     }
     const hipStream_t X = s->aux;
@@ -2718,7 +2577,7 @@ int launch_frame(sq_device_scene* s, const FrameOf<SRC>& F, hipStream_t stream, 
         *e = s->events[next_event++];
         return 0;
     };
-    if (s->opt_overlap == 2) {
+    if (s->opt.overlap == 2) {
         // Two pipelines: even batches run start to end on the caller's stream, odd batches on the second stream.  A trace
         // launch needs a whole CU's LDS per workgroup, so the two tracks' launches do not share CUs: the later one's
         // workgroups move in as the earlier one's finish, which fills the ramp-down of every launch (a ray takes
@@ -2792,29 +2651,7 @@ int launch_frame(sq_device_scene* s, const FrameOf<SRC>& F, hipStream_t stream, 
 }  // namespace
 
 namespace {
-// The largest frames a call takes.  Pixel indices are 32-bit wherever they are stored (Work::px_pixel, Frame::view_pixels)
-// or divided (pixel_coords), so no call takes more than INT32_MAX pixels.  The wavefront form also indexes its active-pixel list and
-// its ray queue with 32-bit values that reach 3 x pixels (px_sum[3 * a]), pixels + one grid stride (the `a` loops) and twice the slots
-// (the trace kernel's cursor, with the mirror rays in front): they hold while pixels <= 2^29, which is also the cap of option "slots".
-constexpr int64_t kMaxCallPixels = INT32_MAX, kMaxWavefrontPixels = (int64_t)1 << 29;
-// Sets the refusal of a call of n_views x rows x h pixels that is too large for its form (wavefront: not the per-pixel kernel) and
-// returns non-zero; 0 when the size is fine.  Everything in 64 bits; touches no device.
-int refuse_frame_size(int64_t n_views, int64_t rows, int64_t h, bool wavefront) {
-    if (rows <= 0 || h <= 0 || n_views <= 0) return 0;
-    const int64_t view_rows = n_views * rows;                           // each factor is below 2^31: below 2^62
-    const bool huge = view_rows > kMaxCallPixels || view_rows * h > kMaxCallPixels;
-    const int64_t pixels = huge ? 0 : view_rows * h;
-    if (n_views > 1) {
-        if (huge) return sq_set_error("%lld views of %lld x %lld pixels exceed 2^31 - 1 pixels in one call", (long long)n_views, (long long)rows, (long long)h);
-        if (wavefront && pixels > kMaxWavefrontPixels)
-            return sq_set_error("%lld views of %lld x %lld pixels exceed 2^29 pixels in one call of the wavefront form (variant 1 takes 2^31 - 1)", (long long)n_views, (long long)rows, (long long)h);
-        return 0;
-    }
-    if (huge) return sq_set_error("%lld x %lld pixels exceed 2^31 - 1 pixels in one call", (long long)rows, (long long)h);
-    if (wavefront && pixels > kMaxWavefrontPixels)
-        return sq_set_error("%lld x %lld pixels exceed 2^29 pixels in one call of the wavefront form (variant 1 and cast frames take 2^31 - 1)", (long long)rows, (long long)h);
-    return 0;
-}
+// (the largest frames a call takes, kMaxCallPixels / kMaxWavefrontPixels, and refuse_frame_size: sq_plan.h)
 bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
     const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
     return x < y + nb && y < x + na;
@@ -2846,7 +2683,7 @@ int render_rows(sq_device_scene* s, const sq_camera* cam, int32_t n_views, int32
     if (rows < 0) return sq_set_error("bad shard {row_block=%d, shard=%d, n_shards=%d}", sh.row_block, sh.shard, sh.n_shards);
     if (rows == 0) return 0;                    // an empty shard (more shards than row blocks) has nothing to render
     if (!d_avg && !d_rgb && !d_sum) return sq_set_error("no output buffer");
-    if (refuse_frame_size(n_views, rows, h, s->opt_variant != 1 && (!cast || s->opt_cast_wavefront))) return 1;   // before any 32-bit product of rows and h, and before the device is touched
+    if (refuse_frame_size(n_views, rows, h, s->opt.variant != 1 && (!cast || s->opt.cast_wavefront))) return 1;   // before any 32-bit product of rows and h, and before the device is touched
     if (d_mask || d_sum2 || d_count) {   // a masked call: no two of its buffers may overlap (a live pixel's stores would be another pixel's mask, count or fold)
         const size_t px = (size_t)rows * (size_t)h;
         const NamedRange b[6] = { { "d_mask", d_mask, px }, { "d_sum", d_sum, px * 12 }, { "d_sum2", d_sum2, px * 12 }, { "d_count", d_count, px * 4 },
@@ -2860,13 +2697,13 @@ int render_rows(sq_device_scene* s, const sq_camera* cam, int32_t n_views, int32
     {   // primary-ray tiles: as tall as the adjacency of local rows allows (8 x 8 on a whole image, 2 x 32 with blocks of 2 rows)
         const int rb = sh.n_shards <= 1 ? 8 : sh.row_block;
         F.tile_rows = rb >= 8 && rb % 8 == 0 ? 8 : rb >= 4 && rb % 4 == 0 ? 4 : rb >= 2 && rb % 2 == 0 ? 2 : 1;
-        if (s->opt_primary_tiles == 0) F.tile_rows = 1;
+        if (s->opt.primary_tiles == 0) F.tile_rows = 1;
         const int tw = 64 / F.tile_rows;
         F.tiles_x = (h + tw - 1) / tw;
     }
     F.out_avg = d_avg; F.out_rgb = d_rgb;
     F.k_begin = k_begin; F.k_end = k_end; F.sum = d_sum;
-    F.diag = s->opt_coresidency ? std::max(1, s->n_cu - 8) : 0;   // "beside" = while all but a handful of the CUs hold a live trace workgroup
+    F.diag = s->opt.coresidency ? std::max(1, s->n_cu - 8) : 0;   // "beside" = while all but a handful of the CUs hold a live trace workgroup
     F.n_views = n_views; F.view_pixels = rows * h; F.cams = nullptr;
     F.mask = d_mask; F.sum2 = d_sum2; F.count = d_count;
     hipStream_t stream = (hipStream_t)hip_stream;
@@ -2961,7 +2798,6 @@ extern "C" int sq_render_views_device(sq_device_scene* s, const sq_camera* cams,
 }
 
 namespace {
-constexpr long long kLaneChunk = 1ll << 30;   // rays per launch of the per-lane query kernel (2^22 workgroups)
 // The query's rays [c0, c0 + m).
 RayQuery query_part(const RayQuery& Q, long long c0, long long m) {
     RayQuery C = Q;
@@ -2971,41 +2807,42 @@ RayQuery query_part(const RayQuery& Q, long long c0, long long m) {
     C.n = m;
     return C;
 }
-// sq_intersect_rays_device once its arguments are checked (Q.n > 0).  Plans like a frame (s->plan, the same LDS refusals), then
+// sq_intersect_rays_device once its arguments are checked (Q.n > 0).  Plans like a frame (plan_call: s->plan, the same LDS refusals), then
 // variant 1 runs the per-lane kernel and the default form runs chunks of stage -> one level of the trace kernel -> store.
 template <typename StackT>
 int intersect_rays(sq_device_scene* s, const RayQuery& Q, hipStream_t stream) {
-    int stack_cap; size_t px_lds;
-    const SceneView S = begin_plan<StackT>(s, stack_cap, px_lds);
+    Call call;
+    call.query = true; call.n_rays = Q.n;
+    CallPlan C;
+    if (begin_call(s, plan_inputs(s, call, (int)sizeof(StackT)), C)) return 1;
     sq_plan& P = s->plan;
-    if (s->opt_variant == 1) {
-        if (px_lds > 160 * 1024) return sq_set_error("BIH height %d needs %zu B of LDS stack per workgroup (max 163840)", S.height, px_lds);
+    const SceneView S = call_view(s, C);
+    if (C.path == kPathQueryLanes) {
+        const size_t px_lds = C.px_lds;
         if (px_lds > 64 * 1024) SQ_HIP(hipFuncSetAttribute((const void*)sq_intersect_lanes<StackT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)px_lds));
         P.launched = 1;
         for (long long c0 = 0; c0 < Q.n; c0 += kLaneChunk) {
-            const RayQuery C = query_part(Q, c0, std::min(kLaneChunk, Q.n - c0));
-            if (timed_launch(s, [&] { hipLaunchKernelGGL(sq_intersect_lanes<StackT>, dim3((unsigned)((C.n + kBlock - 1) / kBlock)), dim3(kBlock), px_lds, stream, S, C); },
+            const RayQuery Qc = query_part(Q, c0, std::min(kLaneChunk, Q.n - c0));
+            if (timed_launch(s, [&] { hipLaunchKernelGGL(sq_intersect_lanes<StackT>, dim3((unsigned)((Qc.n + kBlock - 1) / kBlock)), dim3(kBlock), px_lds, stream, S, Qc); },
                              "sq_intersect_lanes", stream)) return 1;
         }
         return 0;
     }
-    TracePlan TP;
-    if (plan_trace<StackT, kSrcCamera>(s, S, stack_cap, TP)) return 1;
-    // Chunks of at most `slots` rays (and what the workspace holds; the option caps the slots at 2^29, so a chunk's queue positions and
-    // the trace kernel's 32-bit cursor never overflow).  One slot per ray: 37 B, against 40 B of caller arrays per ray.
-    if (ensure_workspace(s, 1, std::min<int64_t>(s->opt_slots, Q.n), stream)) return 1;
+    const void* const trace_fn = trace_kernel<StackT>(C);
+    if (prepare_trace<StackT, kSrcCamera>(C, trace_fn)) return 1;
+    if (ensure_workspace(s, C.pixels, C.slots, stream)) return 1;
     const Work& W = s->work;
-    const long long chunk = std::min<long long>(s->opt_slots, W.slot_capacity);
+    const long long chunk = plan_schedule(C, W.slot_capacity).query_chunk;
     Work Wq = W; Wq.n_active = W.n_active + 48;                         // the launch's queue length, written by sq_rays_stage
     P.launched = 1;                                                    // planned; what follows fails only on HIP errors
     for (long long c0 = 0; c0 < Q.n; c0 += chunk) {
-        const RayQuery C = query_part(Q, c0, std::min(chunk, Q.n - c0));
-        const dim3 grid((unsigned)std::min<long long>((C.n + kBlock - 1) / kBlock, (long long)s->n_cu * 8));
+        const RayQuery Qc = query_part(Q, c0, std::min(chunk, Q.n - c0));
+        const dim3 grid((unsigned)std::min<long long>((Qc.n + kBlock - 1) / kBlock, (long long)s->n_cu * 8));
         SQ_HIP(hipMemsetAsync(W.head[0], 0, 32 * sizeof(int32_t), stream));     // both dequeue cursors
-        hipLaunchKernelGGL(sq_rays_stage, grid, dim3(kBlock), 0, stream, C, W);
+        hipLaunchKernelGGL(sq_rays_stage, grid, dim3(kBlock), 0, stream, Qc, W);
         SQ_HIP(hipGetLastError());
-        if (launch_trace_kernel(s, S, TP, Wq, C.n, 1, 0, stream, false)) return 1;
-        hipLaunchKernelGGL(sq_rays_store, grid, dim3(kBlock), 0, stream, C, W);
+        if (launch_trace_kernel(s, S, C, trace_fn, Wq, Qc.n, 1, 0, stream, false)) return 1;
+        hipLaunchKernelGGL(sq_rays_store, grid, dim3(kBlock), 0, stream, Qc, W);
         SQ_HIP(hipGetLastError());
     }
     return 0;
@@ -3056,13 +2893,6 @@ struct RadianceQuery {
     float* sum; float* avg; uint8_t* rgb;
     long long n;
 };
-// Rays per chunk of a query of n > 0 rays: every chunk is a frame of its own, so it stays within a frame's limits -- 2^29 "pixels" and
-// one sample of every pixel in the workspace's `slots` (1 .. 2^29) in the wavefront form, a launch of 2^30 lanes in the per-lane form.
-// Plain 64-bit host arithmetic: chunk c covers the rays [c * chunk, min(n, (c + 1) * chunk)), the last one may be short.
-long long radiance_chunk_rays(long long n, long long slots, bool wavefront) {
-    const long long cap = wavefront ? std::min<long long>(std::max<long long>(slots, 1), kMaxWavefrontPixels) : kLaneChunk;
-    return std::min(n, cap);
-}
 // The query's rays [c0, c0 + m): all six arrays advance together (elements, not bytes).
 RadianceQuery radiance_part(const RadianceQuery& Q, long long c0, long long m) {
     RadianceQuery C = Q;
@@ -3077,7 +2907,7 @@ RadianceQuery radiance_part(const RadianceQuery& Q, long long c0, long long m) {
 // chunk has the same plan, and the first is the largest, so a refusal comes from the first chunk, before anything is enqueued.
 template <typename StackT>
 int radiance_rays(sq_device_scene* s, const RadianceQuery& Q, int32_t k_begin, int32_t k_end, bool cast, hipStream_t stream) {
-    const long long chunk = radiance_chunk_rays(Q.n, s->opt_slots, s->opt_variant != 1 && (!cast || s->opt_cast_wavefront));
+    const long long chunk = radiance_chunk_rays(Q.n, s->opt.slots, s->opt.variant != 1 && (!cast || s->opt.cast_wavefront));
     for (long long c0 = 0; c0 < Q.n; c0 += chunk) {
         const RadianceQuery C = radiance_part(Q, c0, std::min(chunk, Q.n - c0));
         RayFrame F{};
@@ -3086,7 +2916,7 @@ int radiance_rays(sq_device_scene* s, const RadianceQuery& Q, int32_t k_begin, i
         F.tile_rows = 1; F.tiles_x = (int32_t)((C.n + 63) / 64);          // primary_padded: the chunk padded to whole waves
         F.out_avg = C.avg; F.out_rgb = C.rgb;
         F.k_begin = k_begin; F.k_end = k_end; F.sum = C.sum;
-        F.diag = s->opt_coresidency ? std::max(1, s->n_cu - 8) : 0;
+        F.diag = s->opt.coresidency ? std::max(1, s->n_cu - 8) : 0;
         F.n_views = 1; F.view_pixels = (int32_t)C.n; F.cams = nullptr;
         F.ray_org = C.org; F.ray_dir = C.dir; F.ray_seed = C.seed;
         if (launch_frame<StackT, kSrcRays>(s, F, stream, nullptr)) return 1;
@@ -3232,41 +3062,10 @@ extern "C" int sq_get_stats(sq_device_scene* s, uint64_t* out, int32_t n, int32_
 }
 extern "C" int sq_set_option(sq_device_scene* s, const char* key, int64_t value) {
     if (!s || !key) return sq_set_error("null argument");
-    if (!std::strcmp(key, "timing")) { s->opt_timing = value; return 0; }
-    if (!std::strcmp(key, "variant")) { if (value != 1 && value != 2) return sq_set_error("variant must be 1 (per-pixel kernel) or 2 (wavefront)"); s->opt_variant = value; return 0; }
-    if (!std::strcmp(key, "slots")) { if (value < 1 || value > (512ll << 20)) return sq_set_error("slots must be in 1..2^29"); s->opt_slots = value; return 0; }
-    if (!std::strcmp(key, "straggler_lanes")) { if (value < 0 || value > 63) return sq_set_error("straggler_lanes must be in 0..63"); s->opt_straggler = value; return 0; }
-    if (!std::strcmp(key, "resident")) { s->opt_resident = value ? 1 : 0; return 0; }
-    if (!std::strcmp(key, "profile")) { s->opt_profile = value ? 1 : 0; return 0; }
-    if (!std::strcmp(key, "lds_node_kb")) { if (value < 0 || value > 128) return sq_set_error("lds_node_kb must be in 0..128"); s->opt_lds_node_kb = value; return 0; }
-    if (!std::strcmp(key, "trace_blocks_per_cu")) { if (value < 0 || value > 8) return sq_set_error("trace_blocks_per_cu must be in 0..8"); s->opt_trace_blocks_per_cu = value; return 0; }
-    if (!std::strcmp(key, "overlap")) { if (value < 0 || value > 2) return sq_set_error("overlap must be 0, 1 or 2"); s->opt_overlap = value; return 0; }
-    if (!std::strcmp(key, "rng_table_mb")) { if (value < 0 || value > (1ll << 20)) return sq_set_error("rng_table_mb must be in 0..2^20"); s->opt_rng_table_mb = value; return 0; }
-    if (!std::strcmp(key, "cast_wavefront")) { s->opt_cast_wavefront = value ? 1 : 0; return 0; }
-    if (!std::strcmp(key, "deep")) { s->opt_deep = value ? 1 : 0; return 0; }
-    if (!std::strcmp(key, "pool")) { s->opt_pool = value ? 1 : 0; return 0; }
-    if (!std::strcmp(key, "guided")) { if (value < 0 || value > 3) return sq_set_error("guided must be in 0..3"); s->opt_guided = value; return 0; }
-    if (!std::strcmp(key, "primary_resident")) { s->opt_primary_resident = value ? 1 : 0; return 0; }
-    if (!std::strcmp(key, "cull")) { s->opt_cull = value ? 1 : 0; return 0; }
-    if (!std::strcmp(key, "level1_cull")) { s->opt_level1_cull = value ? 1 : 0; return 0; }
-    if (!std::strcmp(key, "incremental")) return 0;   // accepted, no effect: the incremental slab test was removed
-    if (!std::strcmp(key, "primary_tiles")) { s->opt_primary_tiles = value ? 1 : 0; return 0; }
-    if (!std::strcmp(key, "primary_pooled")) { s->opt_primary_pooled = value != 0; return 0; }
-    if (!std::strcmp(key, "coresidency")) { s->opt_coresidency = value != 0; return 0; }
-    if (!std::strcmp(key, "aux_polite")) { if (value < 0 || value > 8) return sq_set_error("aux_polite must be in 0..8"); s->opt_aux_polite = value; return 0; }
-    if (!std::strcmp(key, "trace_prio")) { if (value < 0 || value > 3) return sq_set_error("trace_prio must be in 0..3"); s->opt_trace_prio = value; return 0; }
-    if (!std::strcmp(key, "aux_low_priority")) {           // takes effect when the second stream is created (first overlapped frame)
-        s->opt_aux_low_priority = value != 0;
-        if (s->aux) { (void)hipStreamSynchronize(s->aux); (void)hipStreamDestroy(s->aux); s->aux = nullptr; }
-        return 0;
-    }
-    if (!std::strcmp(key, "descend_extra")) { if (value < 0 || value > 16) return sq_set_error("descend_extra must be in 0..16"); s->opt_descend_extra = value; return 0; }
-    if (!std::strcmp(key, "descend_lanes")) { if (value < 1 || value > 64) return sq_set_error("descend_lanes must be in 1..64"); s->opt_descend_lanes = value; return 0; }
-    if (!std::strcmp(key, "pixel_major")) { s->opt_pixel_major = value < 0 ? -1 : value != 0; return 0; }
-    if (!std::strcmp(key, "refill_min")) { if (value < 1 || value > 64) return sq_set_error("refill_min must be in 1..64"); s->opt_refill_min = value; return 0; }
-    if (!std::strcmp(key, "flush_min")) { if (value < 0 || value > 64) return sq_set_error("flush_min must be in 0..64"); s->opt_flush_min = value; return 0; }
-    if (!std::strcmp(key, "aux_blocks_per_cu")) { if (value < 0 || value > 16) return sq_set_error("aux_blocks_per_cu must be in 0..16"); s->opt_aux_blocks_per_cu = value; return 0; }
-    return sq_set_error("unknown option '%s'", key);
+    if (set_option(s->opt, key, value)) return 1;                       // names, ranges and messages: the option table (sq_host.cpp)
+    // "aux_low_priority" takes effect when the second stream is created (first overlapped frame)
+    if (!std::strcmp(key, "aux_low_priority") && s->aux) { (void)hipStreamSynchronize(s->aux); (void)hipStreamDestroy(s->aux); s->aux = nullptr; }
+    return 0;
 }
 
 // ---- one-shot entry points (the drop-in for src/Lib.hs:73-74) ----
@@ -3291,7 +3090,7 @@ int oneshot_part(const sq_scene* scene, const sq_camera* cam, int32_t samples, i
     const auto t0 = now();
     sq_device_scene* s = nullptr;
     if (sq_scene_upload(scene, P.device, &s)) return 1;
-    s->opt_rng_table_mb = 0;                    // one scene per frame: filling a table costs more than the one frame saves
+    s->opt.rng_table_mb = 0;                    // one scene per frame: filling a table costs more than the one frame saves
     const auto t1 = now();
     auto t2 = t1, t3 = t1, t4 = t1;
     const size_t npx = (size_t)rows * (size_t)h * 3;

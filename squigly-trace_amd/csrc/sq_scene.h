@@ -462,6 +462,7 @@ struct ResidentTris {           // whole scene resident in LDS: 16-bit indexed t
     }
     __device__ __forceinline__ int2 leaf(uint32_t ref) const { return make_int2((int)(ref & 0xFFFFFFu), (int)((ref >> 24) & 31u)); }
 };
+static_assert(ResidentTris::kRunPad == kTriRunPad, "trace_lds_layout (sq_plan.h) pads the resident triangle table by kTriRunPad");
 
 // ---- wave64 prefix scans on the DPP network (gfx9 DPP: row_shr inside rows of 16 lanes, then row_bcast:15 and
 // row_bcast:31 carry a row's total into the rows above).  Six VALU instructions, no LDS.  EXEC must be all ones.

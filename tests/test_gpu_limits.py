@@ -371,6 +371,33 @@ def test_campaign_seeds_with_streaming_tunables(sqt, O):
     assert not failures, failures[:5]
 
 
+def test_a_refused_call_touches_nothing(sqt, base):
+    """A call the planner refuses for LDS (a tree one taller than the streaming form takes, on a DeviceScene of its own) between two
+    renders of one 8 x 8 frame on a resident scene: the refusal has the recorded text and plan (tests/golden/plan_cases.json,
+    u16_height159: nothing launched, no trace form chosen), it comes before anything is allocated, freed or cleared, and the second
+    frame equals the first bit for bit."""
+    import json
+    bih0, cam, _, _ = base
+    with open(os.path.join(GOLDEN, "plan_cases.json")) as f:
+        rec = {c["name"]: c for c in json.load(f)["cases"]}["u16_height159"]
+    ds, tall = sqt.DeviceScene(bih0, 0), sqt.DeviceScene(TP.full_stack(bih0, 159, 0, TP.LEFT), 0)
+    try:
+        first = render(ds, cam, 2, 8, 8)
+        with pytest.raises(sqt.SquiglyError) as e:
+            render(tall, cam, 1, 1, 1)
+        assert str(e.value) == rec["refusal"] and "BIH height 159 needs" in rec["refusal"]
+        plan = tall.last_plan()
+        assert plan["launched"] == 0 and plan == rec["plan"]
+        assert (plan["trace_form"], plan["blocks_per_cu"], plan["n_lds"], plan["trace_lds_bytes"], plan["primary_form"]) == ("per_pixel", 0, 0, 0, "none")
+        assert tall.rng_table()[0] == 0 and not any(tall.stats())            # the refused scene holds no table and no workspace
+        again = render(ds, cam, 2, 8, 8)
+    finally:
+        ds.close()
+        tall.close()
+    assert np.array_equal(bits(again[0]), bits(first[0])) and np.array_equal(again[1], first[1])
+    assert plan["height"] == 159 and plan["stack_cap"] == 159
+
+
 def test_one_shot_call_on_a_tall_tree(sqt, base):
     bih0, cam, exp, (axis, side) = base
     ps = TP.full_stack(bih0, 150, axis, side)

@@ -392,8 +392,8 @@ def test_upload_checks_the_device_before_the_tree(sqt):
 # ---- sanitizers ----
 
 def test_packer_under_address_and_undefined_behaviour_sanitizers(tmp_path):
-    """tests/pack_main.cpp (its own main: load data/scene.obj, build, pack, read every array through the window, free) compiled
-    with sq_host.cpp under -fsanitize=address,undefined and run as a child process: exit 0, nothing on stderr."""
+    """tests/pack_main.cpp (its own main: load data/scene.obj, build, pack, read every array through the window, plan a handful of
+    calls through sq_plan_call, free) compiled with sq_host.cpp under -fsanitize=address,undefined and run as a child process: exit 0, nothing on stderr."""
     exe = str(tmp_path / "pack_main")
     csrc = os.path.join(ROOT, "squigly-trace_amd", "csrc")
     subprocess.check_call(["g++", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined",
@@ -401,4 +401,4 @@ def test_packer_under_address_and_undefined_behaviour_sanitizers(tmp_path):
                            os.path.join(csrc, "sq_host.cpp"), os.path.join(ROOT, "tests", "pack_main.cpp"), "-o", exe])
     r = subprocess.run([exe, os.path.join(DATA, "scene.obj"), DATA], capture_output=True)
     assert r.returncode == 0 and r.stderr == b"", (r.returncode, r.stderr[-2000:])
-    assert r.stdout.startswith(b"packed 13 arrays")
+    assert r.stdout.startswith(b"packed 13 arrays") and b"planned 10 calls" in r.stdout

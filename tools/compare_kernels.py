@@ -1,12 +1,13 @@
 #!/usr/bin/env python3
-"""Compare the gfx950 kernels of two builds by instruction stream.  CPU only.
+"""Compare the gfx950 kernels of two builds by instruction stream and resource figures.  CPU only.
 
     python tools/compare_kernels.py A B [--arch gfx950] [--objdump PATH]
 
 A and B are libraries (or any file with embedded clang offload bundles) or bare AMDGPU code objects.  The code objects of the
 architecture are taken out of each, disassembled with the ROCm tree's llvm-objdump, and every kernel's instruction text (comments
-and addresses stripped) is hashed.  The two sides are then matched as multisets of hashes, so a kernel that was only renamed
-counts as present in both.  Printed: the kernel counts, then every kernel without a counterpart with its instruction count.
+and addresses stripped) is hashed together with its resource figures from the code object's metadata (llvm-readelf --notes:
+VGPRs, AGPRs, SGPRs, spills, static LDS, scratch, kernel-argument bytes, workgroup size, dynamic stack).  The two sides are then
+matched as multisets of hashes, so a kernel that was only renamed counts as present in both.  Printed: the kernel counts, then every kernel without a counterpart with its instruction count.
 Exit status 0 when every kernel of either side has a counterpart, 1 otherwise.
 """
 import argparse
@@ -67,11 +68,34 @@ def code_objects(path, arch):
     return out
 
 
+RESOURCES = ("agpr_count", "group_segment_fixed_size", "kernarg_segment_size", "max_flat_workgroup_size", "private_segment_fixed_size",
+             "sgpr_count", "sgpr_spill_count", "uses_dynamic_stack", "vgpr_count", "vgpr_spill_count")
+
+
+def resources_of(notes):
+    """{mangled kernel name: "figure=value ..."} from the text of llvm-readelf --notes (one block per kernel, keys in order)."""
+    out, cur = {}, {}
+    for line in notes.splitlines():
+        m = re.match(r"^\s+(?:- )?\.([a-z_]+):\s+(\S+)\s*$", line)
+        if not m:
+            continue
+        key, val = m.groups()
+        if key == "agpr_count":                    # the first key of a kernel's block
+            cur = {}
+        if key in RESOURCES or key == "name":      # (an argument's .name comes before the kernel's own and is overwritten by it)
+            cur[key] = val
+        if key == "vgpr_spill_count":              # the last figure of a block
+            out[cur["name"]] = " ".join("%s=%s" % (k, cur.get(k, "?")) for k in RESOURCES)
+    return out
+
+
 def kernels_of(obj, objdump):
-    """{mangled kernel name: [instruction lines]} of one code object."""
+    """{mangled kernel name: [resource figures, instruction lines...]} of one code object."""
     with tempfile.NamedTemporaryFile(suffix=".co") as tmp:
         tmp.write(obj)
         tmp.flush()
+        readelf = os.path.join(os.path.dirname(objdump), "llvm-readelf")
+        figures = resources_of(subprocess.run([readelf, "--notes", tmp.name], check=True, capture_output=True, text=True).stdout)
         syms = subprocess.run([objdump, "-t", tmp.name], check=True, capture_output=True, text=True).stdout
         text = subprocess.run([objdump, "-d", "--no-show-raw-insn", "--no-leading-addr", tmp.name], check=True, capture_output=True, text=True).stdout
     is_kernel = {l.split()[-1][:-3] for l in syms.splitlines() if l.rstrip().endswith(".kd")}     # a kernel has a descriptor NAME.kd
@@ -89,6 +113,10 @@ def kernels_of(obj, objdump):
     for ins in out.values():                               # what fills the gap up to the next symbol's alignment is no part of the kernel
         while ins and ins[-1] in PADDING:
             ins.pop()
+    for name, ins in out.items():
+        if name not in figures:
+            raise SystemExit("no resource figures for kernel %s" % name)
+        ins.insert(0, figures[name])
     return out
 
 
@@ -97,7 +125,7 @@ def load(path, arch, objdump):
     out = []
     for obj in code_objects(path, arch):
         for name, ins in kernels_of(obj, objdump).items():
-            out.append((name, hashlib.sha256("\n".join(ins).encode()).hexdigest(), len(ins)))
+            out.append((name, hashlib.sha256("\n".join(ins).encode()).hexdigest(), len(ins) - 1))
     return out
 
 
@@ -140,7 +168,7 @@ def main():
     names = demangler()([k[0] for k in only_a + only_b])
     print("A: %s: %d kernels" % (args.a, len(A)))
     print("B: %s: %d kernels" % (args.b, len(B)))
-    print("in both, by instruction stream: %d" % both)
+    print("in both, by instruction stream and resource figures: %d" % both)
     for tag, ks in (("only in A", only_a), ("only in B", only_b)):
         print("%s: %d" % (tag, len(ks)))
         for name, _, n in sorted(ks, key=lambda k: names[k[0]]):
