@@ -15,6 +15,9 @@ import os
 import numpy as np
 import pyoracle as O
 
+from ray_oracle import make_radiance_families
+from scenes import BRIGHT_SQ
+
 f32 = np.float32
 MAX_DEPTH = 8
 
@@ -119,14 +122,12 @@ def fold_frame(trails_by_sample, depth, n=None):
 DATA = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "data")
 N_RAYS = 1000                      # per family
 FAMILIES = ("free", "surface", "to_light", "degenerate")
-ROTATED = b"0 7 0.75\n1.4 0.15 0.2\n"
 BIG = b"1" + b"0" * 40             # reads as +inf in float32
 
 
 def odd_sq():
     """The bright materials with an infinite `emissive`, a negative surfColor component and a zero surfColor (the lamp's): not every
     component is >= +0, so the exact shortcuts for absorbing surfaces are off, and inf * 0 = NaN reaches the folds."""
-    from test_gpu_raytrace import BRIGHT_SQ
     sq = BRIGHT_SQ.replace(b"emissive 0.5 0.3 0.6 0.9", b"emissive " + BIG + b" 0.3 0.6 0.9")
     sq = sq.replace(b"reflective 0.2 0.608420 0.508420 0.408420", b"reflective 0.2 0.608420 -0.508420 0.408420")
     assert sq.count(BIG) == 1 and b"-0.508420" in sq and b"reflective 0 0 0 0" in sq
@@ -135,7 +136,7 @@ def odd_sq():
 
 class Case:
     """One material set on data/scene.obj: product BIH, oracle BIH and its flattened triangles, and N_RAYS rays per family with seeds
-    that are small, huge and negative (tests/test_gpu_raytrace.make_families), each with its path to MAX_DEPTH.
+    that are small, huge and negative (ray_oracle.make_radiance_families), each with its path to MAX_DEPTH.
     The "free" family here is the first N_RAYS free rays of the generator whose ray 0 hits the scene: 38 % of the generator's free rays
     start outside the open room and hit nothing, which is black at every depth -- the other three families keep their misses."""
 
@@ -154,7 +155,6 @@ def first_hitting(ob, o, d, n):
 
 @functools.lru_cache(maxsize=None)
 def case(which):
-    from test_gpu_raytrace import BRIGHT_SQ, make_families
     sqt = importlib.import_module("squigly-trace_amd")
     obj = open(os.path.join(DATA, "scene.obj"), "rb").read()
     sq = {"bright": lambda: BRIGHT_SQ, "shipped": lambda: open(os.path.join(DATA, "scene.sq"), "rb").read(), "odd": odd_sq}[which]()
@@ -164,7 +164,7 @@ def case(which):
     c.otris = O.tris_from_text(obj, sq)
     c.ob = O.BIH(c.otris)
     c.flat = c.ob.flatten()
-    fam, seeds = make_families(c.bih, c.flat, {"bright": 12, "shipped": 11, "odd": 13}[which])
+    fam, seeds = make_radiance_families(c.bih, c.flat, {"bright": 12, "shipped": 11, "odd": 13}[which])
     keep = FAMILIES if which != "odd" else ("free",)
     n = N_RAYS if which != "odd" else 500
     c.families = keep

@@ -4,8 +4,8 @@ fuzz_gpu.make_scene / make_camera.  Seed N is the scene and camera that fuzz_gpu
 draws from default_rng(N), and everything else a case needs comes from a second generator, default_rng([N, 1]), in the order written
 in `case` (recorded seeds keep reproducing only while that order stays).
 
-Expected values come from the C oracle (O.BIH.render, intersectBIH, the trick-camera raytrace / raycast of tests/test_gpu_raytrace.py,
-O.tonemap) and from the two restatements that tests pin to it: tests/depth_restatement.py (any depth) and test_gpu_lights.Restatement
+Expected values come from the C oracle (O.BIH.render, intersectBIH, the trick-camera raytrace / raycast of tests/ray_oracle.py,
+O.tonemap) and from the two restatements that tests pin to it: tests/depth_restatement.py (any depth) and lights_restatement.Restatement
 (any lights).  tests/test_fuzz_features.py pins both on every seed of the pytest slice and judges what the slice covers, without a GPU;
 tests/test_gpu_fuzz_features.py runs the slice.  Every comparison is on bits with NaNs canonicalised, RGB8 exactly.
 
@@ -14,13 +14,13 @@ tests/test_gpu_fuzz_features.py runs the slice.  Every comparison is on bits wit
 prints one line per mismatch with the seed that reproduces it, and a summary.
 
 Two conventions of the ray batch.  The oracle reaches a caller-given ray through a camera whose rotation adds +0 to each direction
-component (tests/test_gpu_raytrace.py), so the radiance queries (raytrace, raycast) get the batch with every -0 direction component
+component (tests/ray_oracle.py), so the radiance queries (raytrace, raycast) get the batch with every -0 direction component
 made +0; `intersect`, whose oracle call takes the ray as it is, gets the batch unchanged.  And a ray batch's seeds have nothing to do
 with the frame's: the camera rays in it are rays like any other."""
+import functools
 import importlib
 import os
 import sys
-import time
 
 import numpy as np
 
@@ -31,37 +31,30 @@ for p in (HERE, ROOT, os.path.join(ROOT, "oracle")):
         sys.path.insert(0, p)
 import pyoracle as O  # noqa: E402
 
-O.lib()
-import fuzz_gpu as F  # noqa: E402  (loads the product library, as it does for its own campaign)
+import fuzz_gpu as F  # noqa: E402
 import depth_restatement as DR  # noqa: E402
 import sky_restatement as SR  # noqa: E402
-from test_gpu_lights import Restatement, avg_of, fold as fold_cast  # noqa: E402
-from test_gpu_rays import check_hits, oracle_hits  # noqa: E402
-from test_gpu_raytrace import oracle_raycast, oracle_raytrace, positive_zeros  # noqa: E402
+from bitcmp import canon, same  # noqa: E402
+import f32_folds  # noqa: E402
+from f32_folds import from_zero  # noqa: E402
+from lights_restatement import Restatement, avg_of, fold_cast  # noqa: E402
+from ray_oracle import check_hits, oracle_hits, oracle_raycast, oracle_raytrace, positive_zeros  # noqa: E402
+from render_options import DEFAULT_SLOTS  # noqa: E402
+from scenes import oracle_tris_of  # noqa: E402
 
-sqt = importlib.import_module("squigly-trace_amd")
+sqt = importlib.import_module("squigly-trace_amd")      # importing the package loads no library: F.load_libraries does, when a case runs
 f32 = np.float32
-canon = F.canon
+tonemaps = functools.partial(f32_folds.tonemaps, O)
 DEPTHS = (1, 2, 4, 5, 8)
 WHOLE = (None, 0, 1)
 # frame sides 1 .. 16, the larger ones more often: a light has to light and to shadow a hit pixel of the frame to count as seen, and
 # a path has to live to level 3 (tests/test_fuzz_features.py holds the slice to counts of both)
 SIDES = np.arange(1, 17)
 SIDE_WEIGHTS = np.where(SIDES >= 7, 3.0, 1.0) / np.where(SIDES >= 7, 3.0, 1.0).sum()
-DEFAULT_SLOTS = 512 << 20
 
 
 class Case:
     """One seed: scene, cameras, frame, depth, lights, mask, ray batch, options; and the oracle's tree of the scene."""
-
-
-def tonemaps(avg):
-    return np.array([O.tonemap(a) for a in avg.reshape(-1, 3)], np.uint8).reshape(avg.shape)
-
-
-def from_zero(r):
-    with np.errstate(all="ignore"):
-        return (f32(0) + r).astype(f32)                                 # a one-sample fold: 0 + r
 
 
 def light_pairs(table):
@@ -75,11 +68,7 @@ def case(seed):
     c.v, c.mats, c.mat, c.scale = F.make_scene(rng)
     c.camt = F.make_camera(rng, c.scale)
     v, scale = c.v, c.scale
-    ot = np.zeros(len(v), O.TRI_DTYPE)
-    ot["a"], ot["b"], ot["c"] = v[:, 0], v[:, 1], v[:, 2]
-    for f in ("reflective", "surf", "emissive", "emit"):
-        ot[f] = c.mats[f][c.mat]
-    c.ob = O.BIH(ot)
+    c.ob = O.BIH(oracle_tris_of(O, v, c.mats, c.mat))
     c.flat = c.ob.flatten()
     c.ocam = O.camera_from_text(c.camt)
 
@@ -215,16 +204,13 @@ def ray_paths(c):
 
 
 # ---- one case on the GPU -----------------------------------------------------------------------------------------------------
-def same(a, b):
-    return a.shape == b.shape and np.array_equal(canon(a), canon(np.ascontiguousarray(b, f32)))
-
-
 DEVICE_ERROR = []      # the first HIP error of this process: after one, no case touches the device again
 
 
 def run_case(seed):
     """Every check of the seed; returns the list of mismatch messages (empty: all equal).  A refusal is a mismatch."""
     import torch
+    F.load_libraries()
     if DEVICE_ERROR:
         raise RuntimeError(f"not run: the device reported an error earlier in this process ({DEVICE_ERROR[0]})")
     c = case(seed)
@@ -360,26 +346,9 @@ def describe(c):
             f"{len(c.ray_o)} rays, deep {c.deep}, cast_wavefront {c.cast_wavefront}, slots {c.slots}, {c.knobs}")
 
 
-def main():
-    budget = float(sys.argv[1]) if len(sys.argv) > 1 else 240.0
-    seed = int(sys.argv[2]) if len(sys.argv) > 2 else 0
-    t0 = time.time()
-    n = bad = 0
-    last = t0
-    while time.time() - t0 < budget:
-        msgs = run_case(seed)
-        n += 1
-        if msgs:
-            bad += 1
-            for m in msgs:
-                print(f"MISMATCH seed={seed}: {m}", flush=True)
-        if time.time() - last > 30:
-            last = time.time()
-            print(f"... {n} cases, {bad} mismatches, next seed {seed + 1}", flush=True)
-        seed += 1
-    print(f"fuzz_features: {n} cases in {time.time() - t0:.0f} s, {bad} mismatches (seeds {seed - n}..{seed - 1})", flush=True)
-    return 1 if bad else 0
+def main(budget=240.0, seed=0):
+    return F.campaign("fuzz_features", run_case, budget, seed)
 
 
 if __name__ == "__main__":
-    sys.exit(main())
+    sys.exit(main(float(sys.argv[1]) if len(sys.argv) > 1 else 240.0, int(sys.argv[2]) if len(sys.argv) > 2 else 0))

@@ -14,25 +14,43 @@ import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "oracle"))
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+for p in (HERE, ROOT, os.path.join(ROOT, "oracle")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
 import pyoracle as O  # noqa: E402
 
-O.lib()
-sqt = importlib.import_module("squigly-trace_amd")
-sqt.lib()
-import torch  # noqa: E402
+from bitcmp import canon  # noqa: E402
+from render_options import THREADS  # noqa: E402
+from scenes import oracle_tris_of  # noqa: E402
 
-THREADS = min(os.cpu_count() or 1, 16)
-BIG = "big" in sys.argv
+sqt = importlib.import_module("squigly-trace_amd")      # importing the two packages loads no library and touches no device
 
 
-def make_scene(rng, kinds=12):
+def load_libraries():
+    """Loads the checker and then the product library, in conftest.py's order; a case and main() call it, importing does not."""
+    O.lib()
+    sqt.lib()
+
+
+def room(r):
+    """The twelve triangles of the closed cube [-r, r]^3, as six quads."""
+    q = []
+    for ax in range(3):
+        for s in (-r, r):
+            a, b = [i for i in range(3) if i != ax]
+            p = np.zeros((4, 3)); p[:, ax] = s
+            p[:, a] = [-r, r, r, -r]; p[:, b] = [-r, -r, r, r]
+            q += [p[[0, 1, 2]], p[[0, 2, 3]]]
+    return q
+
+
+def make_scene(rng, kinds=12, big=False):
     kind = rng.integers(0, kinds)            # `kinds` < 10 replays seeds found before the later kinds were added
     scale = float(rng.choice([1e-3, 1.0, 1.0, 1.0, 50.0, 1e4]))
     if kind == 0:      # soup
-        n = int(rng.choice([3000, 8000, 20000] if BIG else [1, 2, 14, 15, 16, 40, 200, 1000, 3000]))
+        n = int(rng.choice([3000, 8000, 20000] if big else [1, 2, 14, 15, 16, 40, 200, 1000, 3000]))
         c = rng.uniform(-2, 2, (n, 1, 3))
         v = c + rng.normal(0, float(rng.choice([0.02, 0.3, 1.5])), (n, 3, 3))
     elif kind == 1:    # lattice: exact ties everywhere (centroids, planes, edges, coplanar faces)
@@ -47,14 +65,7 @@ def make_scene(rng, kinds=12):
         v = np.concatenate([base] * int(rng.integers(2, 6)))
         v = v[rng.permutation(len(v))]
     elif kind == 3:    # closed room of big quads + clutter (rays never escape: deep paths)
-        r = 3.0
-        q = []
-        for ax in range(3):
-            for s in (-r, r):
-                a, b = [i for i in range(3) if i != ax]
-                p = np.zeros((4, 3)); p[:, ax] = s
-                p[:, a] = [-r, r, r, -r]; p[:, b] = [-r, -r, r, r]
-                q += [p[[0, 1, 2]], p[[0, 2, 3]]]
+        q = room(3.0)
         n = int(rng.integers(0, 400))
         c = rng.uniform(-2, 2, (n, 1, 3))
         v = np.concatenate([np.array(q), c + rng.normal(0, 0.25, (n, 3, 3))])
@@ -73,14 +84,7 @@ def make_scene(rng, kinds=12):
         lamp = np.array([[[-1, -1, 1.5], [1, -1, 1.5], [0, 1, 1.5]]])
         v = np.concatenate(q + [lamp])
     elif kind == 7:    # mirror room: every path runs to the bounce limit, mirror rays of mirror rays
-        r = 2.0
-        q = []
-        for ax in range(3):
-            for sgn in (-r, r):
-                a, b = [i for i in range(3) if i != ax]
-                p = np.zeros((4, 3)); p[:, ax] = sgn
-                p[:, a] = [-r, r, r, -r]; p[:, b] = [-r, -r, r, r]
-                q += [p[[0, 1, 2]], p[[0, 2, 3]]]
+        q = room(2.0)
         n = int(rng.integers(0, 60))
         v = np.concatenate([np.array(q), rng.uniform(-1.5, 1.5, (n, 1, 3)) + rng.normal(0, 0.3, (n, 3, 3))])
     elif kind == 8:    # magnitudes that overflow or underflow inside the ray-triangle test (inf, NaN, denormals)
@@ -93,14 +97,7 @@ def make_scene(rng, kinds=12):
         for _ in range(int(rng.integers(1, 6))):
             v[rng.integers(0, n), rng.integers(0, 3), rng.integers(0, 3)] = rng.choice([np.nan, np.inf, -np.inf])
     elif kind == 11:   # closed room + clutter with LARGE FINITE material values (see below): radiance overflows to inf / NaN
-        r = 2.5
-        q = []
-        for ax in range(3):
-            for sgn in (-r, r):
-                a, b = [i for i in range(3) if i != ax]
-                p = np.zeros((4, 3)); p[:, ax] = sgn
-                p[:, a] = [-r, r, r, -r]; p[:, b] = [-r, -r, r, r]
-                q += [p[[0, 1, 2]], p[[0, 2, 3]]]
+        q = room(2.5)
         n = int(rng.integers(4, 120))
         v = np.concatenate([np.array(q), rng.uniform(-1.8, 1.8, (n, 1, 3)) + rng.normal(0, 0.5, (n, 3, 3))])
         scale = 1.0
@@ -193,19 +190,14 @@ def make_camera(rng, scale):
     return best[1]
 
 
-def canon(a):
-    """uint32 view with every NaN mapped to one pattern (IEEE leaves NaN payloads to the implementation)."""
-    u = np.ascontiguousarray(a).view(np.uint32).copy()
-    u[np.isnan(a)] = 0x7FC00000
-    return u
-
-
-def run_case(seed, kinds=12):
+def run_case(seed, kinds=12, big=False):
+    import torch
+    load_libraries()
     rng = np.random.default_rng(seed)
-    v, mats, mat, scale = make_scene(rng, kinds)
+    v, mats, mat, scale = make_scene(rng, kinds, big)
     camt = make_camera(rng, scale)
-    w, h = (int(rng.integers(40, 321)), int(rng.integers(40, 321))) if BIG else (int(rng.integers(1, 49)), int(rng.integers(1, 49)))
-    spp = int(rng.choice([5, 16, 33, 64] if BIG else [1, 2, 3, 7, 16, 40]))
+    w, h = (int(rng.integers(40, 321)), int(rng.integers(40, 321))) if big else (int(rng.integers(1, 49)), int(rng.integers(1, 49)))
+    spp = int(rng.choice([5, 16, 33, 64] if big else [1, 2, 3, 7, 16, 40]))
     cast = bool(rng.random() < 0.15)
     tris = np.zeros(len(v), sqt._native.TRI_DTYPE)
     tris["v0"], tris["v1"], tris["v2"], tris["mat"] = v[:, 0], v[:, 1], v[:, 2], mat
@@ -224,11 +216,7 @@ def run_case(seed, kinds=12):
         if not (np.array_equal(raw(bih.nodes), raw(host.nodes)) and np.array_equal(raw(bih.tris), raw(host.tris))
                 and np.array_equal(raw(bih.bounds), raw(host.bounds))):
             return "the device BIH build differs from the host build"
-    ot = np.zeros(len(v), O.TRI_DTYPE)
-    ot["a"], ot["b"], ot["c"] = v[:, 0], v[:, 1], v[:, 2]
-    for f in ("reflective", "surf", "emissive", "emit"):
-        ot[f] = mats[f][mat]
-    ob = O.BIH(ot)
+    ob = O.BIH(oracle_tris_of(O, v, mats, mat))
     if (bih.height, bih.num_leaves, bih.longest_leaf) != (ob.height, ob.num_leaves, ob.longest_leaf):
         return "tree shape differs (device build)" if on_device else "tree shape differs"
     cam_p, cam_o = sqt.camera_from_text(camt), O.camera_from_text(camt)
@@ -245,7 +233,7 @@ def run_case(seed, kinds=12):
     if seed >= 30000000:   # round-3 campaign seeds: the streaming form's plain (1, 2 workgroups per CU) and six-wave (0 = auto, 3) builds
         knobs["trace_blocks_per_cu"] = ((seed * 40503) >> 3) % 4
         knobs["guided"] = ((seed * 2654435761) >> 11) % 4          # per bounce level since round 3
-        if BIG:            # the overlapped schedules' scheduling options (BIG draws `overlap` below)
+        if big:            # the overlapped schedules' scheduling options (BIG draws `overlap` below)
             knobs["aux_polite"] = ((seed * 2246822519) >> 5) % 3
             knobs["trace_prio"] = (((seed * 3266489917) >> 4) % 2) * 2
     if seed >= 40000000:   # second round-3 campaign (merged branch records in the streaming form, one-region culling tests, ballot builtin)
@@ -260,7 +248,7 @@ def run_case(seed, kinds=12):
             ds.set_option(k, val)
         for variant in (2, 1):
             ds.set_option("variant", variant)
-            if BIG:
+            if big:
                 ds.set_option("overlap", int(rng.integers(0, 3)))
                 ds.set_option("slots", int(rng.choice([w * h, 3 * w * h + 17, 1 << 22])))
             a, r = ds.render_rows(cam_p, spp, w, h, cast=cast)
@@ -296,25 +284,30 @@ def run_case(seed, kinds=12):
     return None
 
 
-def main():
-    budget = float(sys.argv[1]) if len(sys.argv) > 1 else 240.0
-    seed = int(sys.argv[2]) if len(sys.argv) > 2 else 0
+def campaign(label, run, budget, seed):
+    """run(seed) -> its mismatch messages, on seed, seed + 1, ... for `budget` seconds: one line per mismatch and a summary; 1 if any."""
+    load_libraries()
     t0 = time.time()
     n = bad = 0
     last = t0
     while time.time() - t0 < budget:
-        msg = run_case(seed)
+        msgs = run(seed)
         n += 1
-        if msg:
-            bad += 1
-            print(f"MISMATCH seed={seed}: {msg}", flush=True)
+        bad += bool(msgs)
+        for m in msgs:
+            print(f"MISMATCH seed={seed}: {m}", flush=True)
         if time.time() - last > 30:
             last = time.time()
             print(f"... {n} cases, {bad} mismatches, next seed {seed + 1}", flush=True)
         seed += 1
-    print(f"fuzz: {n} cases in {time.time() - t0:.0f} s, {bad} mismatches (seeds {seed - n}..{seed - 1})", flush=True)
+    print(f"{label}: {n} cases in {time.time() - t0:.0f} s, {bad} mismatches (seeds {seed - n}..{seed - 1})", flush=True)
     return 1 if bad else 0
 
 
+def main(budget=240.0, seed=0, big=False):
+    return campaign("fuzz", lambda s: [m] if (m := run_case(s, big=big)) else [], budget, seed)
+
+
 if __name__ == "__main__":
-    sys.exit(main())
+    args = [a for a in sys.argv[1:] if a != "big"]
+    sys.exit(main(float(args[0]) if args else 240.0, int(args[1]) if len(args) > 1 else 0, big="big" in sys.argv[1:]))

@@ -9,7 +9,7 @@ import importlib
 
 import numpy as np
 import pyoracle as O
-from test_cull import mt_accepts, slab_passes
+from kernel_restatements import mt_accepts, slab_passes
 
 f32 = np.float32
 EPS = f32(0.0001)
@@ -177,3 +177,40 @@ def frame_prediction(sqt, T, ob, flat, cam, spp, w, h):
     fb = frame_first_bounces(ob, flat, cam, spp, w, h)
     nd = random_vectors(fb["n1"], fb["n2"])
     return fb, culled(T, emitters_of(flat), fb["p0"], fb["d1"], unit_float(fb["n1"]), nd)
+
+
+def soup(seed, n_emit, n=300, reflective=(0.0, 0.1, 0.3, 0.5, 0.8, 1.0), emit=(1.0, 0.8, 0.6), spread=0.35, emitter_size=None, cluster=None, zoned=None):
+    """A random triangle soup: materials 0 .. len(reflective)-1 diffuse / partly / always mirroring, the last material the lamp's
+    (absorbing, emissive), on n_emit triangles -- random ones, or (cluster = a point) the ones nearest to that point, so that the
+    emitters' box is a corner of the scene.  zoned = a point: only the sixth of the triangles nearest to it get a non-zero `reflective`
+    (mirrors everywhere would put every ray 1 inside the box of its mirror class).  Returns (tris, mats, oracle triangle records)."""
+    N = importlib.import_module("squigly-trace_amd._native")
+    rng = np.random.default_rng(seed)
+    c = rng.uniform(-1.5, 1.5, (n, 1, 3))
+    v = (c + rng.normal(0, spread, (n, 3, 3))).astype(f32)
+    nm = len(reflective)
+    mats = np.zeros(nm + 1, N.MAT_DTYPE)
+    mats["reflective"][:nm] = reflective
+    mats["surf"][:nm] = rng.uniform(0.2, 0.9, (nm, 3))
+    mats["emissive"][nm] = 25
+    mats["emit"][nm] = emit
+    mat = rng.integers(0, nm, n)
+    if zoned is not None:
+        mat[np.argsort(np.linalg.norm(c[:, 0] - np.asarray(zoned), axis=1))[n // 6:]] = 0
+    em = rng.choice(n, n_emit, replace=False)
+    if cluster is not None:
+        em = np.argsort(np.linalg.norm(c[:, 0] - np.asarray(cluster), axis=1))[:n_emit]
+    mat[em] = nm
+    if emitter_size is not None:
+        v[em] = (c[em] + rng.normal(0, emitter_size, (n_emit, 3, 3))).astype(f32)
+    if n_emit:                                                           # an emitter that shares an edge with a diffuse triangle, and one grazing it
+        a, b = em[0], np.flatnonzero(mat != nm)[0]
+        v[b, 0], v[b, 1] = v[a, 1], v[a, 0]
+        v[b, 2] = v[a, 2] + f32(1e-4) * rng.normal(0, 1, 3).astype(f32)
+    tris = np.zeros(n, N.TRI_DTYPE)
+    tris["v0"], tris["v1"], tris["v2"], tris["mat"] = v[:, 0], v[:, 1], v[:, 2], mat
+    ot = np.zeros(n, O.TRI_DTYPE)
+    ot["a"], ot["b"], ot["c"] = v[:, 0], v[:, 1], v[:, 2]
+    for f in ("reflective", "surf", "emissive", "emit"):
+        ot[f] = mats[f][mat]
+    return tris, mats, ot

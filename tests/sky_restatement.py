@@ -13,6 +13,7 @@ import numpy as np
 import pyoracle as O
 
 import depth_restatement as DR
+from scenes import ROTATED
 
 f32 = np.float32
 MAX_DEPTH = DR.MAX_DEPTH
@@ -114,7 +115,7 @@ def case_paths(c, k=0):
 @functools.lru_cache(maxsize=None)
 def frame_case(which, camera, w, h, spp):
     c = DR.case(which)
-    text = open(os.path.join(DR.DATA, "camera"), "rb").read() if camera == "camera" else DR.ROTATED
+    text = open(os.path.join(DR.DATA, "camera"), "rb").read() if camera == "camera" else ROTATED
     return frame_paths(c.ob, c.flat, O.camera_from_text(text), spp, w, h)
 
 

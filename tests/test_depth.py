@@ -10,9 +10,9 @@ import numpy as np
 import pytest
 
 import depth_restatement as DR
+from bitcmp import ibits, nan_eq
 from conftest import DATA, ROOT
-from test_gpu_raytrace import oracle_raytrace
-from test_gpu_rays import ibits, nan_eq
+from ray_oracle import oracle_raytrace
 
 f32 = np.float32
 

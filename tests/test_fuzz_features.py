@@ -5,7 +5,7 @@ import numpy as np
 import pytest
 
 import fuzz_features as FF
-from test_pack import pack
+from scenes import pack
 
 SEEDS = range(1000, 1400)
 canon = FF.canon

@@ -3,19 +3,25 @@ Adaptive, render_adaptive and the CLI's --adaptive): a masked range call renders
 for bit the oracle's left folds of r and r * r over its own prefix of the frame's samples (src/Lib.hs:85-88); every other pixel
 keeps what every buffer held.  All comparisons are on bits."""
 import ctypes as C
+import functools
 import os
 import sys
 
 import numpy as np
 import pytest
 
+import render_options as RO
+from bitcmp import canon, ibits
 from conftest import ROOT
-from test_gpu_progressive import DEFAULTS, OPTION_TUPLES, THREADS, canon, ibits, overflow_room, set_options, soup
+from f32_folds import avg_by_counts as avg_of, fold, tonemap_image
+from masked_calls import SENT, buffers, host, masked, oracle_samples
+from render_options import OPTION_TUPLES, option_kw
+from scenes import emitter_soup_scene as soup, overflow_room
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
-SENT = {"sums": 7.25, "sums2": 5.5, "avg": -3.5, "rgb": 123, "counts": 77}
-assert DEFAULTS["variant"] == 2
+set_options = functools.partial(RO.set_options, table=RO.FRAME)
+assert RO.FRAME["variant"] == 2
 
 
 @pytest.fixture(scope="module")
@@ -25,75 +31,6 @@ def dev(sqt, product_scene):
     ds = sqt.DeviceScene(bih, 0)
     yield ds
     ds.close()
-
-
-_SAMPLES = {}
-
-
-def oracle_samples(ob, cam_o, n, w, h, k_hi=None, cast=False, key=None):
-    """[k_hi, w, h, 3] float32: the radiance of sample k of pixel (y, x) of the n-sample frame (a cast frame: its cast colour)."""
-    k_hi = n if k_hi is None else k_hi
-    ck = (key, n, w, h, k_hi, cast)
-    if key is not None and ck in _SAMPLES:
-        return _SAMPLES[ck]
-    if cast:   # the cast colour of a pixel is the oracle's 1-sample cast frame (1 / 1 * c == c)
-        c, _, _ = ob.render(cam_o, 1, w, h, cast=True, threads=THREADS)
-        s = np.broadcast_to(c, (k_hi,) + c.shape).copy()
-    else:
-        s = np.array([[[ob.sample_radiance(cam_o, n, w, h, y, x, k) for x in range(h)] for y in range(w)] for k in range(k_hi)], f32)
-    if key is not None:
-        _SAMPLES[ck] = s
-    return s
-
-
-def fold(samples, a, b, s=None, q=None):
-    """The float32 left folds of r and of r * r (the product rounded before the add) over the samples [a, b), continued from s, q."""
-    s = np.zeros(samples.shape[1:], f32) if s is None else s.copy()
-    q = np.zeros(samples.shape[1:], f32) if q is None else q.copy()
-    with np.errstate(all="ignore"):
-        for k in range(a, b):
-            r = samples[k]
-            s = s + r
-            q = q + r * r
-    return s, q
-
-
-def tonemap_image(O, avg):
-    return np.array([[O.tonemap(tuple(float(v) for v in px)) for px in row] for row in avg], np.uint8)
-
-
-def avg_of(sums, counts):
-    with np.errstate(all="ignore"):
-        return (f32(1) / np.maximum(counts, 1).astype(f32))[..., None] * sums
-
-
-def buffers(rows, h):
-    """The five output buffers of a masked call, filled with sentinels."""
-    import torch
-    mk = lambda shape, dt, v: torch.full(shape, v, dtype=dt, device="cuda:0")  # noqa: E731
-    return {"sums": mk((rows, h, 3), torch.float32, SENT["sums"]), "sums2": mk((rows, h, 3), torch.float32, SENT["sums2"]),
-            "counts": mk((rows, h), torch.int32, SENT["counts"]), "avg": mk((rows, h, 3), torch.float32, SENT["avg"]),
-            "rgb": mk((rows, h, 3), torch.uint8, SENT["rgb"])}
-
-
-def masked(ds, cam, n, w, h, a, b, B, mask, with_counts=True, with_sums2=True, **kw):
-    import torch
-    m = None if mask is None else torch.from_numpy(np.ascontiguousarray(mask, np.uint8)).cuda()
-    ds.render_rows_masked(cam, n, w, h, a, b, B["sums"], mask=m, sums2=B["sums2"] if with_sums2 else None,
-                          counts=B["counts"] if with_counts else None, out_avg=B["avg"], out_rgb=B["rgb"], **kw)
-    torch.cuda.synchronize()
-
-
-def host(B):
-    return {k: v.cpu().numpy() for k, v in B.items()}
-
-
-def option_kw(opts):
-    if opts == "pool0":
-        return {"pool": 0}
-    if opts == "cast":
-        return {}
-    return dict(zip(("variant", "resident", "profile", "overlap", "primary_pooled"), opts))
 
 
 # ---- 1. null arguments are the range call --------------------------------------------------------------------------------

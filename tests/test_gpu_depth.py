@@ -10,58 +10,28 @@ import pytest
 
 import depth_restatement as DR
 import tree_padding as TP
-from conftest import DATA, GOLDEN
-from test_gpu_raytrace import ROTATED, primary_form_of, raytrace, set_options as set_ray_options
-from test_gpu_rays import SCENE_FORMS, ibits, nan_eq
+from bitcmp import ibits, nan_eq
+from conftest import GOLDEN
+from f32_folds import from_zero, tonemaps
+from ray_oracle import raytrace
+from render_options import FORM_IDS, PRIMARY_FORMS, SCENE_FORMS, primary_form_of, set_depth_options as set_options
+from scenes import camera, open_case
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
 DEPTHS = (1, 2, 4, 5, 8)            # 4 and 5 end on either parity of the alternating queue state; 8 reaches n_7
-FORM_IDS = [f"{f}-{'-'.join(f'{k}{v}' for k, v in o.items()) or 'default'}" for o, f in SCENE_FORMS]
-
-
-def set_options(ds, depth=3, deep=0, **opts):
-    set_ray_options(ds, **opts)
-    ds.set_option("deep", deep)
-    ds.set_option("cast_wavefront", 0)
-    ds.set_depth(depth)
-
-
-def from_zero(r):
-    with np.errstate(all="ignore"):
-        return (f32(0) + r).astype(f32)                               # a one-sample fold: 0 + r
-
-
-def camera(sqt, which):
-    return sqt.camera_from_text(open(os.path.join(DATA, "camera"), "rb").read() if which == "camera" else ROTATED)
-
-
-def tonemaps(O, avg):
-    return np.array([O.tonemap(a) for a in avg.reshape(-1, 3)], np.uint8).reshape(avg.shape)
-
-
-class Scene:
-    pass
-
-
-def open_case(sqt, which):
-    s = Scene()
-    s.c = DR.case(which)
-    s.paths = DR.case_paths(s.c)
-    s.ds = sqt.DeviceScene(s.c.bih, 0)
-    return s
 
 
 @pytest.fixture(scope="module")
 def bright(sqt):
-    s = open_case(sqt, "bright")
+    s = open_case(sqt, DR.case("bright"), DR.case_paths)
     yield s
     s.ds.close()
 
 
 @pytest.fixture(scope="module")
 def shipped(sqt):
-    s = open_case(sqt, "shipped")
+    s = open_case(sqt, DR.case("shipped"), DR.case_paths)
     yield s
     s.ds.close()
 
@@ -126,9 +96,6 @@ def test_a_fold_of_eight_samples_at_depth_5_in_ranges_and_batches(sqt, O, bright
 
 
 # ---- 3. frames -------------------------------------------------------------------------------------------------------
-PRIMARY_FORMS = (({}, "resident"), ({"primary_resident": 0}, "per_lane"), ({"primary_pooled": 1}, "pooled"), ({"variant": 1}, "none"))
-
-
 @pytest.mark.parametrize("cam_name", ("camera", "rotated"))
 @pytest.mark.parametrize("w, h", ((16, 24), (40, 72)))
 def test_a_frame_equals_the_restatements_frame_and_the_query_of_its_rays(sqt, O, bright, w, h, cam_name):
@@ -334,7 +301,7 @@ def test_depth_3_after_depth_5_is_the_golden_and_cast_ignores_the_depth(sqt, shi
 # ---- 9. streams ------------------------------------------------------------------------------------------------------
 def test_a_deep_frame_and_a_deep_query_on_a_gated_side_stream(sqt, O, product_scene, oracle_scene):
     import torch
-    import test_gpu_streams as S
+    import stream_harness as S
     env = S.Env(sqt, torch, O, product_scene[0], oracle_scene[0])
     try:
         for form in ("default", "variant1", "resident0"):

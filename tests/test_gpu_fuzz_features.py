@@ -11,13 +11,13 @@ import pytest
 import depth_restatement as DR
 import fuzz_features as FF
 from conftest import ROOT
-from test_gpu_lights import Restatement, avg_of, fold as fold_cast
-from test_gpu_rays import family_free
+from lights_restatement import Restatement, avg_of, fold_cast
+from ray_oracle import family_free
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
 BLOCK = 25
-# tools/gen_scenes.py's materials with light everywhere (as test_gpu_raytrace.BRIGHT_SQ): a path's radiance tells which surfaces it met
+# tools/gen_scenes.py's materials with light everywhere (as scenes.BRIGHT_SQ): a path's radiance tells which surfaces it met
 BRIGHT_BLOB_SQ = (b"newmtl Diffuse\nreflective 0 0.700000 0.600000 0.500000\nemissive 0.25 0.9 0.5 0.2\n\n"
                   b"newmtl Glossy\nreflective 0.2 0.500000 0.300000 0.200000\nemissive 0.125 0.2 0.9 0.4\n\n"
                   b"newmtl Mirror\nreflective 1 0.900000 0.800000 0.700000\nemissive 0.5 0.3 0.6 0.9\n\n"

@@ -13,13 +13,14 @@ import time
 import numpy as np
 import pytest
 
+from bitcmp import ibits
+from render_options import DEFAULT_SLOTS, THREADS
+
 pytestmark = pytest.mark.gpu
 f32 = np.float32
-THREADS = min(os.cpu_count() or 1, 16)
 GB = 1 << 30
 INT32_MAX = 2 ** 31 - 1
 N_RANDOM_ROWS = 64
-DEFAULT_SLOTS = 512 << 20
 
 
 # ---- memory ----------------------------------------------------------------------------------------------------------------
@@ -78,7 +79,7 @@ def oracle_row(ob, ocam, spp, w, h, y, cast):
 def bits_equal(t, a):
     """A device float32 tensor against a host float32 array, on bits."""
     import torch
-    want = torch.from_numpy(np.ascontiguousarray(a, f32).view(np.int32)).to(t.device)
+    want = torch.from_numpy(ibits(a)).to(t.device)
     return bool(torch.equal(t.contiguous().view(torch.int32), want))
 
 
@@ -402,7 +403,7 @@ def ray_block(sqt, ds, cam, ob, bih):
     """2^20 rays and the oracle's answer to each: the primary rays of a 1024 x 946 frame and the ray families of
     tests/test_gpu_rays.py (free space, on surfaces, axis-aligned and on split planes, degenerate)."""
     import torch
-    from test_gpu_rays import make_families, oracle_hits
+    from ray_oracle import make_families, oracle_hits
     if "rays" not in _BLOCK:
         fam = make_families(bih, 20)
         fo = np.concatenate([fam[k][0] for k in sorted(fam)]).astype(f32)

@@ -6,15 +6,12 @@ import numpy as np
 import pytest
 
 import level1_restatement as R
+from bitcmp import bits
 from conftest import DATA, GOLDEN
-from test_level1_cull import soup
+from level1_restatement import soup
 
 pytestmark = pytest.mark.gpu
 CULLED = 28                                                             # sq_get_stats slot
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 @pytest.fixture(scope="module")

@@ -4,17 +4,21 @@ for bit the formula of include/squigly_hip.h, in the per-lane form and in the wa
 The expected values come from the CPU oracle alone: rays from O.make_ray, hits (hit, tri, point, dist) from O.BIH.intersect, surface
 colours from O.BIH.flatten(), and the formula in numpy float32 with the header's parenthesisation (`restate`).  For the reference's
 light that restatement is bit-equal to O.BIH.render(..., cast=True) (test_the_reference_light_in_every_spelling checks it)."""
+import functools
 import itertools
 
 import numpy as np
 import pytest
 
+import render_options as RO
 import tree_padding as TP
+from bitcmp import nan_eq
+from lights_restatement import Restatement, as_light, avg_of, fold_cast as fold
+from scenes import ROTATED
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
 W = H = 24
-ROTATED = b"0 7 0.75\n1.4 0.15 0.2\n"
 # the six positions of the fixture; in the multi-light cases every light has an RGB power of its own, so that a permuted or a
 # dropped light changes bits
 POSITIONS = ((0, 3, -1), (0, 0, 0), (1.5, -2, 0.5), (-2, 1, 2), (0, 0, 4), (100, 100, 100))
@@ -26,78 +30,7 @@ THREE = (SIX[1], SIX[2], SIX[5])
 FORMS = (("variant1", {"variant": 1, "cast_wavefront": 0}), ("variant1_wavefront_asked", {"variant": 1, "cast_wavefront": 1}),
          ("per_lane", {"variant": 2, "cast_wavefront": 0}), ("wavefront", {"variant": 2, "cast_wavefront": 1}))
 BOTH = FORMS[2:]
-DEFAULTS = {"variant": 2, "cast_wavefront": 0, "resident": 1, "pool": 1, "primary_pooled": 0, "slots": 512 << 20, "overlap": 0}
-
-
-def nan_eq(a, b):
-    """Bit equality where any two NaNs count as equal (x86 and gfx950 NaN payloads differ)."""
-    a, b = np.ascontiguousarray(a, f32), np.ascontiguousarray(b, f32)
-    return (a.view(np.int32) == b.view(np.int32)) | (np.isnan(a) & np.isnan(b))
-
-
-def norm(v):
-    return np.sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2], dtype=f32)
-
-
-def as_light(light):
-    pos, power = light
-    return np.asarray(pos, f32), np.asarray(power, f32)
-
-
-class Restatement:
-    """The header's formula over the oracle's intersectBIH.  Primary hits are computed once per ray set and kept."""
-
-    def __init__(self, O, ob):
-        self.O, self.ob, self.flat = O, ob, ob.flatten()
-        self._primary = {}
-
-    def primary(self, key, rays):
-        """[(hit, point, surf)] of the rays; key names the ray set."""
-        if key not in self._primary:
-            out = []
-            for o, d in rays:
-                h = self.ob.intersect(o, d)
-                if h.hit:
-                    out.append((True, np.array([h.point.x, h.point.y, h.point.z], f32), np.asarray(self.flat[h.tri]["surf"], f32)))
-                else:
-                    out.append((False, None, None))
-            self._primary[key] = out
-        return self._primary[key]
-
-    def radiance(self, key, rays, lights):
-        """T per ray [n, 3] (zeros for a miss), and lit [n, m]: 1 lit, 0 shadowed, -1 the ray misses."""
-        prim = self.primary(key, rays)
-        lights = [as_light(li) for li in lights]
-        T = np.zeros((len(prim), 3), f32)
-        lit = np.full((len(prim), len(lights)), -1, np.int8)
-        with np.errstate(all="ignore"):
-            for i, (hit, p, surf) in enumerate(prim):
-                if not hit:
-                    continue
-                tot = None
-                for j, (pos, power) in enumerate(lights):
-                    dl = norm((p - pos).astype(f32))
-                    sh = self.ob.intersect(p, (pos - p).astype(f32))
-                    is_lit = not (sh.hit and not (f32(sh.dist) > dl))
-                    c = ((power / dl).astype(f32) * surf).astype(f32) if is_lit else np.zeros(3, f32)
-                    lit[i, j] = int(is_lit)
-                    tot = c if tot is None else (tot + c).astype(f32)
-                T[i] = tot
-        return T, lit
-
-
-def fold(T, k_begin, k_end, start=None):
-    """sum = sum + T per sample of [k_begin, k_end), from +0 or `start`."""
-    s = np.zeros_like(T) if start is None else start.copy()
-    with np.errstate(all="ignore"):
-        for _ in range(k_begin, k_end):
-            s = (s + T).astype(f32)
-    return s
-
-
-def avg_of(s, k_end):
-    with np.errstate(all="ignore"):
-        return ((f32(1) / f32(k_end)) * s).astype(f32)
+options = functools.partial(RO.set_options, table=RO.CAST)
 
 
 @pytest.fixture(scope="module")
@@ -107,11 +40,6 @@ def world(sqt, O, oracle_scene, product_scene):
     ds = sqt.DeviceScene(bih, 0)
     yield {"sqt": sqt, "O": O, "ob": ob, "ocam": ocam, "bih": bih, "cam": cam, "ds": ds, "R": Restatement(O, ob)}
     ds.close()
-
-
-def options(ds, **opts):
-    for k, v in {**DEFAULTS, **opts}.items():
-        ds.set_option(k, v)
 
 
 def shard_rows(sqt, w, shard):

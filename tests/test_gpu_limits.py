@@ -12,16 +12,14 @@ import numpy as np
 import pytest
 
 import tree_padding as TP
+from bitcmp import bits
 from conftest import DATA, GOLDEN
+from render_options import THREADS
+from scenes import LIMITS_H as H, LIMITS_W as W, big_leaf as _big_leaf, near_of, oracle_tris as _oracle_tris, tall_u32 as _tall_u32
 
 pytestmark = pytest.mark.gpu
-THREADS = min(os.cpu_count() or 1, 16)
-W, H, SPP = 32, 24, 2
+SPP = 2
 LDS = 160 * 1024
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 @pytest.fixture(scope="module")
@@ -31,11 +29,6 @@ def base(sqt, O):
     cam_p, cam_o = sqt.load_camera(os.path.join(DATA, "camera")), O.load_camera(os.path.join(DATA, "camera"))
     exp = {cast: ob.render(cam_o, 1 if cast else SPP, W, H, cast=cast, threads=THREADS)[:2] for cast in (False, True)}
     return bih, cam_p, exp, near_of(O, cam_o)
-
-
-def near_of(O, cam_o):
-    """(axis, side) that every primary ray of the W x H frame visits first (tree_padding.full_stack orients by it)."""
-    return TP.near_side([O.make_ray(W, H, y, x, cam_o)[1] for y in range(W) for x in range(H)])
 
 
 def render(ds, cam, spp, w, h, cast=False):
@@ -106,16 +99,6 @@ EXPECT = {
 }
 CONFIGS = {"variant1": {"variant": 1}, "default": {}, "plain": {"trace_blocks_per_cu": 2}, "stream_only": {"resident": 0},
            "pool0": {"pool": 0}}
-
-
-def _tall_u32(bih0, height, axis, side):
-    """tree_padding.full_stack of scene.obj at `height` under one more wrapper whose other child is a balanced empty subtree
-    that takes the branch count to exactly 0x9000: the deep branches of the scene and of the frame-filling chain come after
-    the empty subtree's in the device's breadth-first numbering, above 0x8000."""
-    nb0 = int(((bih0.nodes["kind"] & 3) != 3).sum())
-    inner = TP.full_stack_wrappers(bih0, height - 1, axis, side)
-    n_empty = 0x9000 - nb0 - len(inner) - 12 - 1
-    return TP.PaddedScene(bih0, {0: [(axis, side, ("balanced", n_empty))] + inner})
 
 
 @pytest.mark.parametrize("word", [2, 4])
@@ -198,14 +181,6 @@ def test_height_limits_per_form(sqt, O, base, word):
         ds.close()
     assert np.array_equal(bits(a), bits(np.load(os.path.join(GOLDEN, "scene_64x64_4spp_avg.npy"))))
     assert np.array_equal(r, np.load(os.path.join(GOLDEN, "scene_64x64_4spp_rgb8.npy")))
-
-
-def _oracle_tris(O, tris, mats):
-    ot = np.zeros(len(tris), O.TRI_DTYPE)
-    ot["a"], ot["b"], ot["c"] = tris["v0"], tris["v1"], tris["v2"]
-    for f in ("reflective", "surf", "emissive", "emit"):
-        ot[f] = mats[f][tris["mat"]]
-    return ot
 
 
 def test_branch_count_word_boundary(sqt, base):
@@ -312,23 +287,6 @@ def test_resident_vertex_limit(sqt, O, n_verts, form):
     plan = check_frame(sqt, bih, cam_p, exp, {})
     assert plan["trace_form"] == form, plan
     print(f"[limits] {n_verts} unique vertices: {plan['trace_form']}")
-
-
-def _big_leaf(sqt, O, base_bih, cam_o, count):
-    """scene.obj plus count - 1 copies of the triangle the centre ray hits, forming one leaf of `count` members: each copy
-    has a material of its own, so the winner of the exact ties (minimumBy keeps the first) shows in the image, and the last
-    copy sits 1e-6 nearer the camera, so it wins wherever it is tested -- only if the whole leaf is."""
-    o, d = O.make_ray(W, H, W // 2, H // 2, cam_o)
-    hit = O.BIH(O.tris_from_obj(os.path.join(DATA, "scene.obj"), DATA)).intersect(o, d).tri
-    mesh = sqt.Mesh.from_obj(os.path.join(DATA, "scene.obj"), DATA)
-    tris, mats = mesh.tris, mesh.materials
-    extra = np.zeros(count - 1, mats.dtype)
-    extra["surf"] = np.stack([np.linspace(0.2, 0.9, count - 1), np.linspace(0.9, 0.2, count - 1), np.full(count - 1, 0.5)], 1)
-    copies = np.repeat(base_bih.tris[hit:hit + 1], count - 1)
-    copies["mat"] = len(mats) + np.arange(count - 1)
-    for k in ("v0", "v1", "v2"):
-        copies[k][-1] = (copies[k][-1] - np.float32(1e-6) * d).astype(np.float32)
-    return np.concatenate([tris, copies]), np.concatenate([mats, extra])
 
 
 @pytest.mark.parametrize("count,resident,packed", [(31, True, 1), (32, False, 0)])

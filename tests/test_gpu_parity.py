@@ -9,14 +9,12 @@ import os
 import numpy as np
 import pytest
 
+from bitcmp import bits
 from conftest import DATA, GOLDEN, ROOT
+from render_options import THREADS
+from scenes import emitter_soup as _emitter_soup
 
 pytestmark = pytest.mark.gpu
-THREADS = min(os.cpu_count() or 1, 16)
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 @pytest.fixture(scope="module")
@@ -379,25 +377,6 @@ def test_config_c4_shard_of_eight(sqt, product_scene, oracle_scene, dev):
         assert np.array_equal(rgb[j:j + 1].cpu().numpy(), o8)
 
 
-def _emitter_soup(sqt, seed, n_emit):
-    """A soup of 400 triangles with diffuse, half-mirror and full-mirror materials and n_emit emitting triangles:
-    (tris, mats, v, mat).  tests/test_pack.py packs the same soups on the CPU."""
-    rng = np.random.default_rng(seed)
-    n = 400
-    c = rng.uniform(-1.5, 1.5, (n, 1, 3))
-    v = (c + rng.normal(0, 0.35, (n, 3, 3))).astype(np.float32)
-    mats = np.zeros(4, sqt._native.MAT_DTYPE)
-    mats["reflective"] = [0.0, 0.5, 1.0, 0.0]
-    mats["surf"] = [[0.7, 0.6, 0.5], [0.4, 0.8, 0.6], [0.9, 0.9, 0.9], [0.0, 0.0, 0.0]]
-    mats["emissive"] = [0, 0, 0, 25]
-    mats["emit"] = [[0, 0, 0], [0, 0, 0], [0, 0, 0], [1.0, 0.8, 0.6]]
-    mat = rng.integers(0, 3, n)
-    mat[rng.choice(n, n_emit, replace=False)] = 3
-    tris = np.zeros(n, sqt._native.TRI_DTYPE)
-    tris["v0"], tris["v1"], tris["v2"], tris["mat"] = v[:, 0], v[:, 1], v[:, 2], mat
-    return tris, mats, v, mat
-
-
 @pytest.mark.parametrize("seed,n_emit", [(1, 3), (2, 0), (3, 70), (4, 12), (5, 64), (6, 65)])
 def test_random_soups_with_mirrors_and_emitters(sqt, O, seed, n_emit):
     """Random triangle soups with diffuse, half-mirror, full-mirror and emissive triangles: exercises the
@@ -542,7 +521,7 @@ def test_overflowing_emission_defeats_the_absorbing_shortcut(sqt, O):
     product that overflows (31-digit literals in the .sq text; every component itself is finite) the reference computes
     0 * inf = NaN (src/Lib.hs:135) and so must the device.  Also large-but-finite products, where the bound
     max_surf * max_e + max_e decides."""
-    from test_oracle import overflow_room_obj
+    from scenes import overflow_room_obj
     obj = overflow_room_obj()
     cam_txt = b"0 0 0\n0 0 0\n"
     for emissive, emit in ((b"1" + b"0" * 30, b"1" + b"0" * 30), (b"1" + b"0" * 20, b"1" + b"0" * 19), (b"3" + b"0" * 38, b"0.5"), (b"7", b"1")):

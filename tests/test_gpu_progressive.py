@@ -2,34 +2,21 @@
 the CLI's --preview-every): a frame rendered in sample ranges equals the frame of one call bit for bit, in every kernel form
 and schedule, and every intermediate fold equals the oracle's left fold of its samples (src/Lib.hs:85-88)."""
 import ctypes as C
+import functools
 import os
 import sys
 
 import numpy as np
 import pytest
 
+import render_options as RO
+from bitcmp import canon, ibits
 from conftest import ROOT
+from render_options import OPTION_TUPLES, THREADS
+from scenes import emitter_soup_scene as soup, overflow_room
 
 pytestmark = pytest.mark.gpu
-THREADS = min(os.cpu_count() or 1, 16)
-
-# the option tuples test_kernel_variants_agree walks: (variant, resident, profile, overlap, primary_pooled)
-OPTION_TUPLES = ((1, 1, 0, 0, 0), (2, 1, 0, 0, 0), (2, 0, 0, 0, 0), (2, 1, 1, 0, 0), (2, 0, 1, 0, 0), (2, 1, 0, 1, 0), (2, 0, 0, 1, 0),
-                 (2, 1, 0, 0, 1), (2, 0, 0, 0, 1), (2, 1, 0, 2, 1))
-DEFAULTS = {"variant": 2, "resident": 1, "profile": 0, "overlap": 0, "primary_pooled": 0, "pool": 1, "slots": 512 << 20}
-
-
-def ibits(t):
-    """float bits of a CUDA / host tensor or array as an int32 numpy array."""
-    a = t.cpu().numpy() if hasattr(t, "cpu") else np.asarray(t)
-    return np.ascontiguousarray(a, np.float32).view(np.int32)
-
-
-def canon(a):
-    """float bits with every NaN as one pattern (IEEE leaves NaN payloads open)."""
-    b = ibits(a).copy()
-    b[np.isnan(np.asarray(a.cpu().numpy() if hasattr(a, "cpu") else a))] = 0x7FC00000
-    return b
+set_options = functools.partial(RO.set_options, table=RO.FRAME)
 
 
 @pytest.fixture(scope="module")
@@ -39,11 +26,6 @@ def dev(sqt, product_scene):
     ds = sqt.DeviceScene(bih, 0)
     yield ds
     ds.close()
-
-
-def set_options(ds, **opts):
-    for k, v in {**DEFAULTS, **opts}.items():
-        ds.set_option(k, v)
 
 
 def one_call(ds, cam, n, w, h, cast=False, shard=(None, 0, 1)):
@@ -149,43 +131,6 @@ def test_cast_sums_fold_the_oracle_cast_colour(sqt, O, product_scene, oracle_sce
     ob, ocam, _ = oracle_scene
     set_options(dev)
     oracle_fold_check(sqt, O, dev, cam, ob, ocam, 24, 20, 5, cast=True, bounds=[0, 2, 3, 5])
-
-
-def soup(sqt, O, seed, n_emit):
-    """A random triangle soup with diffuse, half-mirror, full-mirror and emissive triangles (as in
-    test_gpu_parity.test_random_soups_with_mirrors_and_emitters); the camera sees empty space around it."""
-    rng = np.random.default_rng(seed)
-    n = 400
-    c = rng.uniform(-1.5, 1.5, (n, 1, 3))
-    v = (c + rng.normal(0, 0.35, (n, 3, 3))).astype(np.float32)
-    mats = np.zeros(4, sqt._native.MAT_DTYPE)
-    mats["reflective"] = [0.0, 0.5, 1.0, 0.0]
-    mats["surf"] = [[0.7, 0.6, 0.5], [0.4, 0.8, 0.6], [0.9, 0.9, 0.9], [0.0, 0.0, 0.0]]
-    mats["emissive"] = [0, 0, 0, 25]
-    mats["emit"] = [[0, 0, 0], [0, 0, 0], [0, 0, 0], [1.0, 0.8, 0.6]]
-    mat = rng.integers(0, 3, n)
-    mat[rng.choice(n, n_emit, replace=False)] = 3
-    tris = np.zeros(n, sqt._native.TRI_DTYPE)
-    tris["v0"], tris["v1"], tris["v2"], tris["mat"] = v[:, 0], v[:, 1], v[:, 2], mat
-    ot = np.zeros(n, O.TRI_DTYPE)
-    ot["a"], ot["b"], ot["c"] = v[:, 0], v[:, 1], v[:, 2]
-    for f in ("reflective", "surf", "emissive", "emit"):
-        ot[f] = mats[f][mat]
-    cam_txt = b"-6 0.1 0.2\n0 0 0\n"
-    return sqt.BIH(sqt.Mesh.from_arrays(tris, mats)), O.BIH(ot), sqt.camera_from_text(cam_txt), O.camera_from_text(cam_txt)
-
-
-def overflow_room(sqt, O):
-    """The room of test_gpu_parity.test_overflowing_emission_defeats_the_absorbing_shortcut with an emission product that
-    overflows (1e30 * 1e30): the reference's 0 * inf = NaN reaches the fold."""
-    from test_oracle import overflow_room_obj
-    obj = overflow_room_obj()
-    big = b"1" + b"0" * 30
-    sq = (b"newmtl Black\nreflective 0 0 0 0\nemissive 0 0 0 0\n\n"
-          b"newmtl Sun\nreflective 0 0 0 0\nemissive " + big + b" " + big + b" " + big + b" " + big + b"\n")
-    cam_txt = b"0 0 0\n0 0 0\n"
-    return (sqt.BIH(sqt.Mesh.from_text(obj, sq)), O.BIH(O.tris_from_text(obj, sq)), sqt.camera_from_text(cam_txt),
-            O.camera_from_text(cam_txt))
 
 
 @pytest.mark.parametrize("which", ["soup", "overflow"])

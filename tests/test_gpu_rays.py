@@ -2,157 +2,23 @@
 ray's (tri, dist, point) is bit for bit the oracle's intersectBIH (src/BIH.hs:101-141), in every trace form and option, for rays far
 from the camera and bounce rays the frames trace: free space, axis-aligned, on split planes, non-finite and degenerate."""
 import ctypes as C
+import functools
 import os
 import sys
 
 import numpy as np
 import pytest
 
+import render_options as RO
 import tree_padding as TP
+from bitcmp import ibits
 from conftest import DATA, ROOT
+from ray_oracle import FAMILIES, N_FAMILY, cast_from_queries, check_hits, make_families, oracle_hits, query
+from render_options import SCENE_FORMS
 
 pytestmark = pytest.mark.gpu
-N_FAMILY = 20000
-FAMILIES = ("free", "surface", "axis", "degenerate")
-DEFAULTS = {"variant": 2, "resident": 1, "pool": 1, "trace_blocks_per_cu": 0, "profile": 0, "cull": 1, "slots": 512 << 20}
-# (options, expected trace form) of data/scene.obj
-SCENE_FORMS = (({"variant": 1}, "per_pixel"), ({}, "resident"), ({"pool": 0}, "resident"),
-               ({"resident": 0, "trace_blocks_per_cu": 3}, "streaming_six_wave"), ({"resident": 0, "trace_blocks_per_cu": 1}, "streaming_plain"),
-               ({"resident": 0, "pool": 0}, "streaming_plain"), ({"profile": 1}, "resident"))
 f32 = np.float32
-
-
-def ibits(a):
-    return np.ascontiguousarray(np.asarray(a, f32)).view(np.int32)
-
-
-def nan_eq(a, b):
-    """Bit equality where any two NaNs count as equal (x86 and gfx950 NaN payloads differ)."""
-    a, b = np.asarray(a, f32), np.asarray(b, f32)
-    return (ibits(a) == ibits(b)) | (np.isnan(a) & np.isnan(b))
-
-
-def set_options(ds, **opts):
-    for k, v in {**DEFAULTS, **opts}.items():
-        ds.set_option(k, v)
-
-
-# ---- ray families ----------------------------------------------------------------------------------------------------
-def unit_dirs(rng, n):
-    v = rng.normal(size=(n, 3))
-    return v / np.linalg.norm(v, axis=1, keepdims=True)
-
-
-def family_free(rng, bounds, n):
-    """Origins uniform in the root box grown by 20 %, directions uniform on the sphere with |d| log-uniform in [1e-3, 1e3]."""
-    lo, hi = bounds[:3].astype(np.float64), bounds[3:].astype(np.float64)
-    c, half = (lo + hi) / 2, (hi - lo) / 2 * 1.2
-    o = c + rng.uniform(-1, 1, (n, 3)) * half
-    d = unit_dirs(rng, n) * 10.0 ** rng.uniform(-3, 3, (n, 1))
-    return o.astype(f32), d.astype(f32)
-
-
-def family_surface(rng, tris, limits, n):
-    """Barycentric points on random triangles; a third of the directions with |d|^2 inside the culling limits, the rest |d| in
-    [1e-2, 1e2]."""
-    t = tris[rng.integers(0, len(tris), n)]
-    u, v = rng.uniform(0, 1, (2, n, 1)).astype(f32)
-    flip = (u + v) > 1
-    u, v = np.where(flip, 1 - u, u), np.where(flip, 1 - v, v)
-    o = (t["v0"] + u * (t["v1"] - t["v0"]) + v * (t["v2"] - t["v0"])).astype(f32)
-    _, d2min, d2max = limits
-    inside = np.arange(n) % 3 == 0
-    mag = np.where(inside[:, None], np.sqrt(rng.uniform(d2min * 1.001, d2max * 0.999, (n, 1))), 10.0 ** rng.uniform(-2, 2, (n, 1)))
-    return o, (unit_dirs(rng, n) * mag).astype(f32)
-
-
-def family_axis(rng, bounds, nodes, n):
-    """Directions along an axis (with signed zeros) and general ones; origins exactly on lmax / rmin planes of the tree's branches and
-    on the faces of the root box."""
-    lo, hi = bounds[:3], bounds[3:]
-    o = (lo + rng.uniform(-0.1, 1.1, (n, 3)).astype(f32) * (hi - lo)).astype(f32)
-    br = np.nonzero((nodes["kind"] & 3) != 3)[0]
-    pick = br[rng.integers(0, len(br), n)]
-    ax = nodes["kind"][pick] & 3
-    plane = np.where(rng.integers(0, 2, n) == 1, nodes["lmax"][pick], nodes["rmin"][pick]).astype(f32)
-    face = np.arange(n) % 4 == 3                              # a quarter on the root box's faces
-    fax = rng.integers(0, 3, n)
-    fval = np.where(rng.integers(0, 2, n) == 1, hi[fax], lo[fax]).astype(f32)
-    ax = np.where(face, fax, ax)
-    o[np.arange(n), ax] = np.where(face, fval, plane)
-    d = np.zeros((n, 3), f32)
-    k = rng.integers(0, 3, n)
-    mag = (10.0 ** rng.uniform(-1, 1, n)).astype(f32)
-    d[np.arange(n), k] = np.where(rng.integers(0, 2, n) == 1, mag, -mag)
-    zeros = np.where(rng.integers(0, 2, (n, 3)) == 1, f32(-0.0), f32(0.0))
-    d = np.where(d == 0, zeros, d)
-    general = np.arange(n) % 5 == 4                           # some rays leave the plane obliquely
-    d[general] = (unit_dirs(rng, int(general.sum())) * 1.1).astype(f32)
-    return o, d
-
-
-def family_degenerate(rng, bounds, n):
-    """d = 0, NaN or +-inf components in o or d, |o| ~ 1e30, |d| ~ 1e-30 and 1e30, mixed with ordinary rays."""
-    o, d = family_free(rng, bounds, n)
-    kind = np.arange(n) % 8
-    r = np.arange(n)
-    comp = rng.integers(0, 3, n)
-    specials = np.array([np.nan, np.inf, -np.inf], f32)[rng.integers(0, 3, n)]
-    zsign = np.where(rng.integers(0, 2, (n, 3)) == 1, f32(-0.0), f32(0.0))
-    d = np.where((kind == 0)[:, None], zsign, d)
-    o[r[kind == 1], comp[kind == 1]] = specials[kind == 1]
-    d[r[kind == 2], comp[kind == 2]] = specials[kind == 2]
-    o[kind == 3] = (unit_dirs(rng, int((kind == 3).sum())) * 1e30).astype(f32)
-    d[kind == 3] = -o[kind == 3] / f32(1e30)
-    d[kind == 4] = (unit_dirs(rng, int((kind == 4).sum())) * 1e-30).astype(f32)
-    d[kind == 5] = (unit_dirs(rng, int((kind == 5).sum())) * 1e30).astype(f32)
-    d[r[kind == 6], comp[kind == 6]] = np.float32(0.0)        # one zero component: an inf in 1/d
-    return o.astype(f32), d.astype(f32)
-
-
-def make_families(bih, seed):
-    rng = np.random.default_rng(seed)
-    b = bih.bounds
-    _, limits = bih.cull_boxes()
-    return {
-        "free": family_free(rng, b, N_FAMILY),
-        "surface": family_surface(rng, bih.tris, limits, N_FAMILY),
-        "axis": family_axis(rng, b, bih.nodes, N_FAMILY),
-        "degenerate": family_degenerate(rng, b, N_FAMILY),
-    }
-
-
-def oracle_hits(ob, o, d):
-    """(tri, dist, point) of the oracle's intersectBIH per ray; tri = -1 for Nothing."""
-    n = len(o)
-    tri = np.full(n, -1, np.int64)
-    dist = np.zeros(n, f32)
-    pt = np.zeros((n, 3), f32)
-    for i in range(n):
-        h = ob.intersect(o[i], d[i])
-        if h.hit:
-            tri[i], dist[i], pt[i] = h.tri, h.dist, (h.point.x, h.point.y, h.point.z)
-    return tri, dist, pt
-
-
-def query(ds, o, d, **kw):
-    import torch
-    h = ds.intersect(o, d, **kw)
-    torch.cuda.synchronize()
-    return tuple(None if t is None else t.cpu().numpy() for t in h)
-
-
-def check_hits(got, want, what):
-    """tri equal; on hits dist and point bit-equal (NaN = NaN); misses exactly tri -1, dist +inf, point +0."""
-    tri, dist, pt = got
-    etri, edist, ept = want
-    bad = tri != etri
-    assert not bad.any(), (what, "tri", int(bad.sum()), np.nonzero(bad)[0][:8])
-    hit = etri >= 0
-    assert nan_eq(dist[hit], edist[hit]).all(), (what, "dist", int((~nan_eq(dist[hit], edist[hit])).sum()))
-    assert nan_eq(pt[hit], ept[hit]).all(), (what, "point", int((~nan_eq(pt[hit], ept[hit])).any(-1).sum()))
-    assert (ibits(dist[~hit]) == ibits(np.float32(np.inf))).all(), (what, "miss dist")
-    assert (ibits(pt[~hit]) == 0).all(), (what, "miss point")
+set_options = functools.partial(RO.set_options, table=RO.RAY_QUERY)
 
 
 # ---- fixtures ------------------------------------------------------------------------------------------------------------
@@ -374,29 +240,6 @@ def test_camera_rays_equal_make_ray(sqt, O, scene, text, w, h, shard):
 
 
 # ---- 7. a cast frame rebuilt from two queries ------------------------------------------------------------------------
-def cast_from_queries(ds, bih, cam, spp, w, h, shard):
-    """src/Lib.hs:141-151 (raycast) and :85-88 (the sample fold) in numpy float32, from two intersect calls."""
-    o, d = ds.camera_rays(cam, w, h, shard=shard)
-    h0 = ds.intersect(o, d)
-    p0 = h0.point
-    light = np.array([0, 3, -1], f32)
-    p0n = p0.cpu().numpy()
-    sdir = (light - p0n).astype(f32)                          # light - p0: the shadow ray's direction
-    h1 = ds.intersect(p0, sdir)
-    tri0, tri1, dist1 = h0.tri.cpu().numpy(), h1.tri.cpu().numpy(), h1.dist.cpu().numpy()
-    v = (p0n - light).astype(f32)
-    dl = np.sqrt((v[..., 0] * v[..., 0] + v[..., 1] * v[..., 1]) + v[..., 2] * v[..., 2]).astype(f32)   # norm (p0 - light)
-    with np.errstate(all="ignore"):
-        lit = ~((tri1 >= 0) & ~(dist1 > dl))                  # maybe True (\pos -> dist pos > dl)
-        surf = bih.materials["surf"][bih.tris["mat"][np.where(tri0 >= 0, tri0, 0)]].astype(f32)
-        c = np.where(lit[..., None], (f32(2) / dl)[..., None] * surf, f32(0)).astype(f32)
-    s = np.zeros_like(c)
-    for _ in range(spp):
-        s = (s + c).astype(f32)
-    avg = (f32(1) / f32(spp)) * s
-    return np.where((tri0 >= 0)[..., None], avg, f32(0)).astype(f32)
-
-
 @pytest.mark.parametrize("spp", (1, 3))
 @pytest.mark.parametrize("shard", ((None, 0, 1), (2, 1, 3)))
 def test_cast_frame_equals_its_restatement_from_queries(sqt, scene, spp, shard):

@@ -7,141 +7,24 @@ rotation: pos = o, rot = [dx, dy, dz, 0, 0, 0, 0, 0, 0] makes rotVert return d f
 samples = N, x = seed div N, k = seed mod N the generator is mkTFGen seed.  A -0.0 direction component would come out as +0.0
 (-0 + 0), so the families below hold no negative-zero direction components."""
 import ctypes as C
+import functools
 import os
 
 import numpy as np
 import pytest
 
+import render_options as RO
 import tree_padding as TP
+from bitcmp import ibits, nan_eq
 from conftest import DATA, GOLDEN
-from test_gpu_rays import SCENE_FORMS, cast_from_queries, family_degenerate, family_free, family_surface, ibits, nan_eq, unit_dirs
+from f32_folds import fold_list as fold
+from ray_oracle import N_FAMILY, RADIANCE_FAMILIES as FAMILIES, cast_from_queries, make_radiance_families as make_families, oracle_raycast, oracle_raytrace, raytrace
+from render_options import FORM_IDS, SCENE_FORMS, primary_form_of
+from scenes import BRIGHT_SQ, ROTATED
 
 pytestmark = pytest.mark.gpu
-N_FAMILY = 20000
-FAMILIES = ("free", "surface", "to_light", "degenerate")
-DEFAULTS = {"variant": 2, "resident": 1, "pool": 1, "trace_blocks_per_cu": 0, "profile": 0, "cull": 1, "slots": 512 << 20,
-            "overlap": 0, "primary_pooled": 0, "primary_resident": 1, "pixel_major": -1}
-TRICK_SAMPLES = 1 << 30               # N of the trick camera: x = seed div N fits an int for |seed| < 2^60
-ROTATED = b"0 7 0.75\n1.4 0.15 0.2\n"
 f32 = np.float32
-
-# data/scene.sq with light everywhere: five of the six materials emit a little, each with a colour of its own, and every surface
-# colour but the lamp's is non-zero and distinct, so a path's radiance tells which surfaces it met.  The 1.0 and 0.2 mirrors stay.
-BRIGHT_SQ = b"""newmtl Material.004
-reflective 0 0.350408 0.250408 0.450408
-emissive 0.5 0.3 0.6 0.9
-
-newmtl Material.001
-reflective 0.2 0.043584 0.258515 0.321582
-emissive 0.25 0.9 0.5 0.2
-
-newmtl Material.003
-reflective 0.2 0.608420 0.508420 0.408420
-emissive 0.125 0.2 0.9 0.4
-
-newmtl Material.002
-reflective 0 0 0 0
-emissive 100 1 1 1
-
-newmtl Material
-reflective 0.2 0.515584 0.024571 0.104109
-emissive 0 0 0 0
-
-newmtl Material.005
-reflective 1 0.80000 0.70000 0.60000
-emissive 0.75 0.6 0.2 0.7
-"""
-
-
-def set_options(ds, **opts):
-    for k, v in {**DEFAULTS, **opts}.items():
-        ds.set_option(k, v)
-
-
-def primary_form_of(form, opts):
-    return "none" if form == "per_pixel" else "resident" if form == "resident" else "per_lane"
-
-
-# ---- the oracle's raytrace / raycast of any ray ----------------------------------------------------------------------
-def trick_camera(O, o, d):
-    cam = O.Camera()
-    cam.pos = O.V3(float(o[0]), float(o[1]), float(o[2]))
-    for j in range(9):
-        cam.rot[j] = float(d[j]) if j < 3 else 0.0
-    return cam
-
-
-def oracle_raytrace(O, ob, o, d, seeds, k=0):
-    """raytrace (mkTFGen (seed_i + k)) scene (Ray o_i d_i) 0 per ray, float32 [n, 3]."""
-    L = O.lib()
-    out = np.zeros((len(o), 3), f32)
-    buf = (C.c_float * 3)()
-    for i in range(len(o)):
-        x, kk = divmod(int(seeds[i]) + k, TRICK_SAMPLES)           # floor division: kk in [0, N) for negative seeds too
-        L.sqo_sample_radiance(ob._h, C.byref(trick_camera(O, o[i], d[i])), TRICK_SAMPLES, 1, 1, 0, x, kk, O.TRIG_CRD, 0, buf)
-        out[i] = buf[:]
-    return out
-
-
-def oracle_raycast(O, ob, o, d):
-    """1 * (0 + raycast scene (Ray o_i d_i)) per ray: the oracle's one-sample cast render of the trick camera."""
-    out = np.zeros((len(o), 3), f32)
-    for i in range(len(o)):
-        avg, _, _ = ob.render(trick_camera(O, o[i], d[i]), 1, 1, 1, cast=True, want_rgb=False)
-        out[i] = avg[0, 0]
-    return out
-
-
-def fold(rs):
-    """foldl (+) 0 over a list of [n, 3] float32 radiances, in float32."""
-    s = np.zeros_like(rs[0])
-    with np.errstate(all="ignore"):
-        for r in rs:
-            s = (s + r).astype(f32)
-    return s
-
-
-# ---- ray families ----------------------------------------------------------------------------------------------------
-def family_to_light(rng, bounds, otris, n):
-    """Origins uniform inside the root box; direction = (a random point on a random emissive triangle - origin) * 10^U(-1, 1)."""
-    lo, hi = bounds[:3].astype(np.float64), bounds[3:].astype(np.float64)
-    o = (lo + rng.uniform(0, 1, (n, 3)) * (hi - lo)).astype(f32)
-    em = np.nonzero((otris["emit"] != 0).any(-1))[0]
-    t = otris[em[rng.integers(0, len(em), n)]]
-    u, v = rng.uniform(0, 1, (2, n, 1))
-    flip = (u + v) > 1
-    u, v = np.where(flip, 1 - u, u), np.where(flip, 1 - v, v)
-    p = t["a"] + u * (t["b"] - t["a"]) + v * (t["c"] - t["a"])
-    d = (p - o) * 10.0 ** rng.uniform(-1, 1, (n, 1))
-    return o, d.astype(f32)
-
-
-def positive_zeros(d):
-    return np.where(d == 0, f32(0.0), d).astype(f32)               # -0.0 == 0: becomes +0.0
-
-
-def make_families(bih, otris, seed):
-    rng = np.random.default_rng(seed)
-    b = bih.bounds
-    _, limits = bih.cull_boxes()
-    fam = {
-        "free": family_free(rng, b, N_FAMILY),
-        "surface": family_surface(rng, bih.tris, limits, N_FAMILY),
-        "to_light": family_to_light(rng, b, otris, N_FAMILY),
-        "degenerate": family_degenerate(rng, b, N_FAMILY),
-    }
-    fam = {k: (np.ascontiguousarray(o, f32), positive_zeros(d)) for k, (o, d) in fam.items()}
-    for k, (o, d) in fam.items():
-        assert not (np.signbit(d) & (d == 0)).any(), k
-    seeds = {}
-    for k in FAMILIES:
-        s = np.empty(N_FAMILY, np.int64)
-        third = np.arange(N_FAMILY) % 3
-        s[third == 0] = rng.integers(0, 1 << 20, int((third == 0).sum()))
-        s[third == 1] = rng.integers(1 << 40, 1 << 60, int((third == 1).sum()))
-        s[third == 2] = -rng.integers(1, 1 << 60, int((third == 2).sum()))
-        seeds[k] = s
-    return fam, seeds
+set_options = functools.partial(RO.set_options, table=RO.RADIANCE)
 
 
 def nonzero_share(r):
@@ -196,13 +79,6 @@ def all_rays(c):
             np.concatenate([c.seeds[k] for k in FAMILIES]))
 
 
-def raytrace(ds, o, d, seeds, **kw):
-    import torch
-    r = ds.raytrace(o, d, seeds=seeds, **kw)
-    torch.cuda.synchronize()
-    return tuple(None if t is None else t.cpu().numpy() for t in r)
-
-
 def check_one_sample(c, what):
     o, d, s = all_rays(c)
     got = raytrace(c.ds, o, d, s)[0]
@@ -215,9 +91,6 @@ def check_one_sample(c, what):
 
 
 # ---- 1. one sample against the oracle --------------------------------------------------------------------------------
-FORM_IDS = [f"{f}-{'-'.join(f'{k}{v}' for k, v in o.items()) or 'default'}" for o, f in SCENE_FORMS]
-
-
 @pytest.mark.parametrize("which", ("shipped", "bright"))
 @pytest.mark.parametrize("opts, form", SCENE_FORMS, ids=FORM_IDS)
 def test_one_sample_equals_the_oracles_raytrace_in_every_form(request, which, opts, form):

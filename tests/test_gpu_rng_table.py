@@ -5,13 +5,14 @@ import numpy as np
 import pytest
 import torch
 
+from bitcmp import same_exact as same
 from conftest import GOLDEN
+from scenes import ROTATED
 
 pytestmark = pytest.mark.gpu
 DEFAULT_MB = 24576
 MB = 1 << 20
 HEADLINE = (1920, 1080, 256)          # rows, columns, samples
-ROTATED = b"0 7 0.75\n1.4 0.15 0.2\n"
 TILTED = b"0.5 6.5 1\n1.3 -0.2 0.1\n"
 
 
@@ -26,17 +27,6 @@ def ds(sqt, product_scene):
 @pytest.fixture(scope="module")
 def cam(product_scene):
     return product_scene[1]
-
-
-def same(a, b):
-    """Two results of one call: tensors (float32 as raw bits) or tuples of tensors / None."""
-    if a is None or b is None:
-        return a is None and b is None
-    if isinstance(a, (tuple, list)):
-        return len(a) == len(b) and all(same(x, y) for x, y in zip(a, b))
-    if a.dtype == torch.float32:
-        return torch.equal(a.view(torch.int32), b.view(torch.int32))
-    return torch.equal(a, b)
 
 
 def on_off(ds, call, mb=DEFAULT_MB):

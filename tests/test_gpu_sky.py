@@ -10,41 +10,18 @@ import pytest
 
 import depth_restatement as DR
 import sky_restatement as SR
+from bitcmp import ibits, nan_eq
 from conftest import DATA, GOLDEN, ROOT
-from test_gpu_depth import FORM_IDS, PRIMARY_FORMS, camera, from_zero, set_options as set_depth_options, tonemaps
-from test_gpu_raytrace import primary_form_of, raytrace
-from test_gpu_rays import SCENE_FORMS, ibits, nan_eq
+from f32_folds import from_zero, tonemaps
+from ray_oracle import raytrace
+from render_options import FORM_IDS, PRIMARY_FORMS, SCENE_FORMS, primary_form_of, set_sky_options as set_options
+from scenes import camera, open_case
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
 DEPTHS = (1, 2, 3, 4, 5, 8)
 INF_UP = ((np.inf, 0.5, 1.0), (0.75, 0.625, 0.5))
 ZERO = ((0.0, 0.0, 0.0), (0.0, 0.0, 0.0))
-
-
-def set_options(ds, sky=None, depth=3, deep=0, **opts):
-    set_depth_options(ds, depth=depth, deep=deep, **opts)
-    if sky is None:
-        ds.set_sky(None)
-    else:
-        ds.set_sky(*sky)
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and bool(nan_eq(a, b).all())
-
-
-class Scene:
-    pass
-
-
-def open_case(sqt, which):
-    s = Scene()
-    s.c = DR.case(which)
-    s.paths = SR.case_paths(s.c)
-    s.ds = sqt.DeviceScene(s.c.bih, 0)
-    s.want = {}
-    return s
 
 
 def expected(s, depth, sky):
@@ -56,14 +33,14 @@ def expected(s, depth, sky):
 
 @pytest.fixture(scope="module")
 def bright(sqt):
-    s = open_case(sqt, "bright")
+    s = open_case(sqt, DR.case("bright"), SR.case_paths)
     yield s
     s.ds.close()
 
 
 @pytest.fixture(scope="module")
 def shipped(sqt):
-    s = open_case(sqt, "shipped")
+    s = open_case(sqt, DR.case("shipped"), SR.case_paths)
     yield s
     s.ds.close()
 
@@ -398,7 +375,7 @@ def test_null_sky_through_the_c_call_and_the_getter(sqt, bright):
 # ---- 7. streams ------------------------------------------------------------------------------------------------------
 def test_a_sky_frame_and_a_sky_query_on_a_gated_side_stream(sqt, O, product_scene, oracle_scene):
     import torch
-    import test_gpu_streams as S
+    import stream_harness as S
     env = S.Env(sqt, torch, O, product_scene[0], oracle_scene[0])
     try:
         for form in ("default", "variant1", "resident0"):

@@ -4,18 +4,24 @@ and through the pixel's mirror ray.  Only the last two still carry a ray when sq
 of ray 1 (or -1) and sq_accumulate evaluates their radiance.  Every call form that shares these kernels must give, bit for bit,
 the oracle's left folds of r and r * r, its avg and its tonemap.
 
-Two random soups (test_gpu_progressive.soup: diffuse, half-mirror, full-mirror and absorbing emissive triangles, empty space all
+Two random soups (scenes.emitter_soup_scene: diffuse, half-mirror, full-mirror and absorbing emissive triangles, empty space all
 around) cover the fates between them: with 12 emissive triangles the last-bounce shortcut is on (a ray 2 is traced only when it can
 reach an emitter, and then it hits something), with 80 it is off (every ray 2 is traced, and most miss).  What the oracle can
 tell apart by value is asserted in test_the_scenes_cover_the_fates; a first bounce that misses, one from which no emitter can be
 reached and a traced ray 2 without light all give exactly s0*0 + e0 and are told apart only by the launch plan and the geometry."""
+import functools
+
 import numpy as np
 import pytest
 
-from test_gpu_adaptive import buffers, fold, masked, oracle_samples, tonemap_image
-from test_gpu_progressive import ibits, set_options, soup
+import render_options as RO
+from bitcmp import ibits
+from f32_folds import fold, tonemap_image
+from masked_calls import buffers, masked, oracle_samples
+from scenes import emitter_soup_scene as soup
 
 pytestmark = pytest.mark.gpu
+set_options = functools.partial(RO.set_options, table=RO.FRAME)
 f32 = np.float32
 W, H, N = 24, 20, 8                     # rows, columns, samples
 SECOND = b"-6 0.4 -0.3\n0.05 -0.04 0.02\n"

@@ -2,35 +2,30 @@
 batched call is bit for bit the single-view frame of cams[i] and the oracle's image, in every kernel form, schedule and option.
 Frames are small and odd (23 rows x 37 columns) so that the primary-ray tiles are padded at every view boundary."""
 import ctypes as C
+import functools
 import os
 
 import numpy as np
 import pytest
 
+import render_options as RO
+from bitcmp import ibits
 from conftest import DATA, ROOT
+from render_options import OPTION_TUPLES, THREADS
+from scenes import ROTATED, tall_u32 as _tall_u32
 
 pytestmark = pytest.mark.gpu
-THREADS = min(os.cpu_count() or 1, 16)
+set_options = functools.partial(RO.set_options, table=RO.VIEWS)
 W, H, SPP = 23, 37, 3
-
-# the option tuples of test_gpu_progressive.py: (variant, resident, profile, overlap, primary_pooled)
-OPTION_TUPLES = ((1, 1, 0, 0, 0), (2, 1, 0, 0, 0), (2, 0, 0, 0, 0), (2, 1, 1, 0, 0), (2, 0, 1, 0, 0), (2, 1, 0, 1, 0), (2, 0, 0, 1, 0),
-                 (2, 1, 0, 0, 1), (2, 0, 0, 0, 1), (2, 1, 0, 2, 1))
-DEFAULTS = {"variant": 2, "resident": 1, "profile": 0, "overlap": 0, "primary_pooled": 0, "pool": 1, "slots": 512 << 20, "cull": 1}
 
 CAMERA = open(os.path.join(DATA, "camera")).read().encode()
 CAM_TEXTS = {
     "camera": CAMERA,
     "moved": b"0.4 6.2 1.1\n1.5707963267948966 0 -0.09817477042468103\n",
-    "rotated": b"0 7 0.75\n1.4 0.15 0.2\n",
+    "rotated": ROTATED,
     "miss": b"0 7 0.75\n-1.5707963267948966 0 0\n",               # looks away from the scene: every primary ray misses
 }
 FIVE = ("camera", "moved", "rotated", "miss", "camera")               # the last one duplicates view 0
-
-
-def ibits(t):
-    a = t.cpu().numpy() if hasattr(t, "cpu") else np.asarray(t)
-    return np.ascontiguousarray(a, np.float32).view(np.int32)
 
 
 def cameras(sqt, O, texts):
@@ -42,11 +37,6 @@ def cameras(sqt, O, texts):
         assert np.array_equal(np.array(p.pos[:], np.float32).view(np.int32), pos.view(np.int32))
         assert np.array_equal(np.array(p.rot[:], np.float32).view(np.int32), rot.view(np.int32))
     return cp, co
-
-
-def set_options(ds, **opts):
-    for k, v in {**DEFAULTS, **opts}.items():
-        ds.set_option(k, v)
 
 
 def singles(ds, cams, n, w, h, cast=False, shard=(None, 0, 1)):
@@ -208,14 +198,6 @@ def test_64_small_views_on_distinct_cameras(sqt, dev):
 
 
 # ---- 8. 4-byte stack words -------------------------------------------------------------------------------------------
-def _tall_u32(TP, bih0, height, axis, side):
-    """tests/test_gpu_limits.py: scene.obj under padding that takes the branch count to exactly 0x9000."""
-    nb0 = int(((bih0.nodes["kind"] & 3) != 3).sum())
-    inner = TP.full_stack_wrappers(bih0, height - 1, axis, side)
-    n_empty = 0x9000 - nb0 - len(inner) - 12 - 1
-    return TP.PaddedScene(bih0, {0: [(axis, side, ("balanced", n_empty))] + inner})
-
-
 def test_views_with_4_byte_stack_words(sqt, O, product_scene, oracle_scene):
     import tree_padding as TP
     bih0, _, _ = product_scene
@@ -223,7 +205,7 @@ def test_views_with_4_byte_stack_words(sqt, O, product_scene, oracle_scene):
     texts = [CAM_TEXTS[k] for k in ("camera", "moved", "rotated")]
     cp, co = cameras(sqt, O, texts)
     axis, side = TP.near_side([O.make_ray(W, H, y, x, co[0])[1] for y in range(W) for x in range(H)])
-    ps = _tall_u32(TP, bih0, bih0.height + 9, axis, side)
+    ps = _tall_u32(bih0, bih0.height + 9, axis, side)
     assert ps.n_branches == 0x9000
     exp = [ob.render(c, SPP, W, H, threads=THREADS)[:2] for c in co]
     ds = sqt.DeviceScene(ps, 0)

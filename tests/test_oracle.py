@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 from conftest import DATA, GOLDEN
+from scenes import overflow_room_obj
 
 STATS = json.load(open(os.path.join(GOLDEN, "scene_stats.json")))
 
@@ -287,18 +288,6 @@ def test_atan_and_tonemap_accept_non_finite_input(O):
     assert tuple(O.tonemap((nan, nan, nan))) == (0, 0, 0)
     assert tuple(O.tonemap((0.0, 0.0, 0.0))) == (0, 0, 0)      # 0/0 = NaN scale: black
     assert tuple(O.tonemap((inf, 1.0, 0.0))) == (0, 0, 0)      # intensity 1 / inf = 0 scale, 0 * inf = NaN -> 0
-
-
-def overflow_room_obj():
-    """A closed cube room of absorbing walls (material Black) with a lamp quad (material Sun) inside, as .obj text."""
-    r = 3
-    corners = [(x, y, z) for x in (-r, r) for y in (-r, r) for z in (-r, r)]
-    quads = [(0, 1, 3, 2), (4, 6, 7, 5), (0, 4, 5, 1), (2, 3, 7, 6), (0, 2, 6, 4), (1, 5, 7, 3)]
-    out = ["mtllib scene.sq", "o Room"] + ["v %d %d %d" % c for c in corners] + ["usemtl Black", "s off"]
-    for a, b, c, d in quads:
-        out += ["f %d %d %d" % (a + 1, b + 1, c + 1), "f %d %d %d" % (a + 1, c + 1, d + 1)]
-    out += ["o Lamp", "v -2 2.5 -2", "v 2 2.5 -2", "v 2 2.5 2", "v -2 2.5 2", "usemtl Sun", "s off", "f 9 10 11", "f 9 11 12"]
-    return ("\n".join(out) + "\n").encode()
 
 
 def test_absorbing_surface_in_front_of_overflowing_radiance_is_nan(O):

@@ -20,36 +20,12 @@ import pytest
 
 import tree_padding as TP
 from conftest import DATA, GOLDEN, ROOT
+from scenes import ARRAYS, SCALARS, big_leaf as _big_leaf, emitter_soup as _emitter_soup, pack
 
-ARRAYS = ["branches", "leaves", "tris", "tri_mat", "surfs", "mats", "verts4", "trix", "rbranch", "emitters", "cull_child",
-          "cull_child16", "branches_m"]
-SCALARS = ["n_branches", "n_leaves", "height", "root_ref", "rroot", "packed_leaves", "nonneg_materials", "finite_geometry",
-           "n_emitters", "n_verts", "cull_o2max", "cull_d2min", "cull_d2max", "small_index"]
 LEAF_BIT, AXIS_MASK, RUN_PAD = 0x80000000, 0x60000000, 3
 BRANCH = np.dtype([("lo", "<f4", 3), ("lmax", "<f4"), ("hi", "<f4", 3), ("rmin", "<f4"), ("lmax2", "<f4"), ("rmin2", "<f4"),
                    ("left", "<u4"), ("right", "<u4")])
 SQ_TEXT = b"newmtl A\nreflective 0 1 1 1\nemissive 1 1 1 1\n"
-
-
-def pack(sqt, holder):
-    """sq_scene_pack of holder.scene (the holder keeps the arrays alive): ({array name: bytes}, {scalar name: int})."""
-    L, h = sqt.lib(), C.c_void_p()
-    sqt._native.check(L.sq_scene_pack(C.byref(holder.scene), C.byref(h)))
-    try:
-        arrays, scalars = {}, {}
-        for name in ARRAYS:
-            data, n = C.c_void_p(), C.c_size_t()
-            assert L.sq_packed_array(h, name.encode(), C.byref(data), C.byref(n)) == 0, name
-            arrays[name] = C.string_at(data, n.value) if n.value else b""
-        for name in SCALARS:
-            v = C.c_int64()
-            assert L.sq_packed_scalar(h, name.encode(), C.byref(v)) == 0, name
-            scalars[name] = v.value
-        assert L.sq_packed_array(h, b"rtail", C.byref(data), C.byref(n)) != 0          # unknown names are refused
-        assert L.sq_packed_scalar(h, b"incremental_ok", C.byref(v)) != 0
-    finally:
-        L.sq_packed_free(h)
-    return arrays, scalars
 
 
 def refusal(sqt, scene_ref, out_ref=None):
@@ -102,8 +78,6 @@ def disjoint_triangles(sqt, n):
 
 def fixture_scenes(sqt, O):
     """{name: object with .scene}: data/scene.obj and the smallest scenes on each side of every switch of the packer."""
-    from test_gpu_limits import _big_leaf
-    from test_gpu_parity import _emitter_soup
     base = sqt.BIH(sqt.Mesh.from_obj(os.path.join(DATA, "scene.obj"), DATA))
     cam_o = O.load_camera(os.path.join(DATA, "camera"))
     out = {"scene_obj": base,

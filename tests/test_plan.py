@@ -229,8 +229,8 @@ def test_deep_block_layout(sqt):
 
 def test_primary_grid_follows_the_tiled_enumeration(sqt):
     """The planner's copy of primary_padded (primary_padded_lanes, sq_plan.h) against the Python mirror of the kernels' own
-    (tests/test_primary_tiles.py): the per-lane primary pass is one thread per tile lane, the resident one strides over n_cu blocks."""
-    from test_primary_tiles import enumerate_pixels
+    (tests/kernel_restatements.py): the per-lane primary pass is one thread per tile lane, the resident one strides over n_cu blocks."""
+    from kernel_restatements import enumerate_pixels
     inp, _ = case_inputs(sqt, CASES["default_8x8"])
     for rows, h, tile_rows, views in ((1, 1, 8, 1), (7, 5, 1, 1), (9, 33, 1, 3), (135, 1080, 2, 1), (1080, 1920, 8, 1), (16, 31, 8, 2), (5, 640, 1, 1)):
         padded = enumerate_pixels(rows, h, tile_rows)[1]
@@ -275,3 +275,33 @@ def test_options_without_a_range_and_unknown_names(sqt):
     rc, _, _, err = plan_call(sqt, inp, outputs=["no_such_scalar"])
     assert rc == 2 and err == "no plan scalar 'no_such_scalar'"
     assert plan_call(sqt, dict(inp, n_cu=0))[0] == 2 and plan_call(sqt, dict(inp, depth=9))[0] == 2
+
+
+# ---- the option tables of the GPU tests (tests/render_options.py) ----------------------------------------------------------------
+# a wavefront frame, a cast frame, a ray query, a streaming form; and the last one again with 2^20 triangles, where pixel_major's
+# automatic setting (-1) chooses 1.  total_rays makes chunk_rays show the option `slots` itself, not the slots a small frame wants.
+TABLE_CASES = (("default_8x8", {}), ("cast", {}), ("intersect", {}), ("u16_height46_8x8", {}), ("u16_height46_8x8", {"n_tris": 1 << 20}))
+EVERY_SCALAR = OUT + WS + ["nonneg_materials", "n_emitters", "cull_off"]
+OTHER_VALUES = {"variant": (1,), "resident": (0,), "profile": (1,), "overlap": (1, 2), "primary_pooled": (1,), "pool": (0,), "slots": (64, 100),
+                "cull": (0,), "trace_blocks_per_cu": (1, 2, 3), "primary_resident": (0,), "pixel_major": (0, 1), "cast_wavefront": (1,)}
+
+
+def test_every_option_table_of_the_gpu_tests_states_the_librarys_defaults(sqt):
+    """An option that is not given takes its default (Options, csrc/sq_plan.h).  So a table states the defaults exactly when planning
+    with its keys given equals planning with none, on the plan and every scalar the window shows; and a key counts only if the
+    plan shows it: some other value of it changes some output of some case."""
+    import render_options as RO
+    keys = set().union(*RO.TABLES.values())
+    assert keys == set(OTHER_VALUES) and not keys & {"timing", "rng_table_mb", "aux_low_priority"}
+    base = []
+    for name, changed in TABLE_CASES:
+        inp, rays = case_inputs(sqt, CASES[name])
+        assert rays is None and not CASES[name]["options"]
+        inp = dict(inp, total_rays=1 << 30, **changed)
+        want = plan_call(sqt, inp, outputs=EVERY_SCALAR)[:3]
+        assert want[0] == 0
+        for tname, table in RO.TABLES.items():
+            assert plan_call(sqt, {**inp, **table}, outputs=EVERY_SCALAR)[:3] == want, (tname, name)
+        base.append((inp, want))
+    for key, values in OTHER_VALUES.items():
+        assert any(plan_call(sqt, {**inp, key: v}, outputs=EVERY_SCALAR)[:3] != want for inp, want in base for v in values), key

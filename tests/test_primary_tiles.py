@@ -5,23 +5,7 @@ this test also rules out duplicates, which parity cannot see (a pixel traced twi
 import numpy as np
 import pytest
 
-
-def tile_rows_for(n_shards, row_block):
-    rb = 8 if n_shards <= 1 else row_block
-    return 8 if rb >= 8 and rb % 8 == 0 else 4 if rb >= 4 and rb % 4 == 0 else 2 if rb >= 2 and rb % 2 == 0 else 1
-
-
-def enumerate_pixels(local_rows, h, tile_rows):
-    tw = 64 // tile_rows
-    tiles_x = (h + tw - 1) // tw
-    padded = ((local_rows + tile_rows - 1) // tile_rows) * tiles_x * 64
-    q = np.arange(padded, dtype=np.int64)
-    lane, tile = q & 63, q >> 6
-    ty, tx = tile // tiles_x, tile % tiles_x
-    jj, xx = lane // tw, lane % tw
-    j, x = ty * tile_rows + jj, tx * tw + xx
-    ok = (j < local_rows) & (x < h)
-    return np.where(ok, j * h + x, -1), padded
+from kernel_restatements import enumerate_pixels, tile_rows_for
 
 
 @pytest.mark.parametrize("local_rows,h,n_shards,row_block", [

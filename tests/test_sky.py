@@ -11,8 +11,9 @@ import pytest
 
 import depth_restatement as DR
 import sky_restatement as SR
+from bitcmp import ibits, nan_eq
 from conftest import DATA, ROOT
-from test_gpu_rays import ibits, nan_eq
+from scenes import ROTATED
 
 f32 = np.float32
 DEPTHS = (1, 2, 3, 4, 5, 8)
@@ -200,7 +201,7 @@ def test_absorbing_hits_stand_above_sky_misses(which):
 @pytest.mark.parametrize("cam_name, w, h", FRAMES)
 def test_the_bright_frames_have_hit_pixels_and_miss_pixels(O, cam_name, w, h):
     c = DR.case("bright")
-    cam = O.camera_from_text(open(os.path.join(DATA, "camera"), "rb").read() if cam_name == "camera" else DR.ROTATED)
+    cam = O.camera_from_text(open(os.path.join(DATA, "camera"), "rb").read() if cam_name == "camera" else ROTATED)
     hits = np.array([c.ob.intersect(*O.make_ray(w, h, y, x, cam)).hit for y in range(w) for x in range(h)], bool)
     print(f"bright {w} x {h}, {cam_name}: {int((~hits).sum())} of {w * h} primary rays miss")
     assert hits.sum() >= 20 and (~hits).sum() >= 20

@@ -1,5 +1,5 @@
 """CPU test that keeps the stream tests complete: every declaration of include/squigly_hip.h that takes a `void* hip_stream` is in
-tests/test_gpu_streams.STREAM_ENTRY_POINTS, which that module's parametrisation is built from, so an entry point with a stream
+tests/stream_harness.STREAM_ENTRY_POINTS, which that module's parametrisation is built from, so an entry point with a stream
 cannot be added without a test on a gated side stream."""
 import os
 import re
@@ -18,7 +18,7 @@ def _stream_declarations():
 
 
 def test_every_entry_point_with_a_stream_has_a_stream_test():
-    import test_gpu_streams as S                                  # importing it must not need a device
+    import stream_harness as S                                    # importing it must not need a device
     declared = _stream_declarations()
     assert len(declared) == len(set(declared)) and len(declared) >= 10, declared
     assert len(S.STREAM_ENTRY_POINTS) == len(set(S.STREAM_ENTRY_POINTS))

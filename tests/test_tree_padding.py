@@ -123,15 +123,15 @@ def test_rendered_rays_fill_the_stack(O, word):
     """The padding of the GPU height sweep keeps its frames: on the primary rays of the rendered frame, some ray holds
     height - 1 frames at a leaf -- the most a root-to-leaf path has, so a stack one frame short would overflow -- and some
     ray holds height - 5 at a leaf of the scene itself (the chain's frames under the scene's own).  No result changes."""
-    import test_gpu_limits as G
+    import scenes as G
     bih = sqt.BIH(sqt.Mesh.from_obj(os.path.join(DATA, "scene.obj"), DATA))
     cam_o = O.load_camera(os.path.join(DATA, "camera"))
-    o, d = _primary_rays(O, cam_o, G.W, G.H)
+    o, d = _primary_rays(O, cam_o, G.LIMITS_W, G.LIMITS_H)
     axis, side = G.near_of(O, cam_o)
     root = (bih.scene.root.lo[:], bih.scene.root.hi[:])
     plain = TP.Mirror(bih.nodes, bih.tris, *root).intersect(o, d)
     for h in EDGE_HEIGHTS[word]:
-        ps = TP.full_stack(bih, h, axis, side) if word == 2 else G._tall_u32(bih, h, axis, side)
+        ps = TP.full_stack(bih, h, axis, side) if word == 2 else G.tall_u32(bih, h, axis, side)
         assert ps.height == h
         m = TP.Mirror(ps.nodes, ps.tris, *root)
         got = m.intersect(o, d)
@@ -145,19 +145,19 @@ def test_rendered_rays_fill_the_stack(O, word):
 def test_big_leaf_shows_its_count_and_order(O, count):
     """The leaf of tests/test_gpu_limits.py::test_leaf_encoding_limit: its last member wins on some primary rays, and with
     the leaf one member short the first member (another material) wins there instead."""
-    import test_gpu_limits as G
+    import scenes as G
     base = sqt.BIH(sqt.Mesh.from_obj(os.path.join(DATA, "scene.obj"), DATA))
     cam_o = O.load_camera(os.path.join(DATA, "camera"))
-    tris, mats = G._big_leaf(sqt, O, base, cam_o, count)
+    tris, mats = G.big_leaf(sqt, O, base, cam_o, count)
     bih = sqt.BIH(sqt.Mesh.from_arrays(tris, mats))
     nodes = bih.nodes.copy()
     leaf = int(np.argmax(np.where((nodes["kind"] & 3) == 3, nodes["kind"] >> 2, -1)))
     first = int(nodes["link"][leaf])
     assert nodes["kind"][leaf] >> 2 == count
-    o, d = _primary_rays(O, cam_o, G.W, G.H)
+    o, d = _primary_rays(O, cam_o, G.LIMITS_W, G.LIMITS_H)
     root = (bih.scene.root.lo[:], bih.scene.root.hi[:])
     full = TP.Mirror(nodes, bih.tris, *root).intersect(o, d)
-    ob = O.BIH(G._oracle_tris(O, tris, mats))
+    ob = O.BIH(G.oracle_tris(O, tris, mats))
     assert np.array_equal(full[0], [r.tri if r.hit else -1 for r in (ob.intersect(o[k], d[k]) for k in range(len(o)))])
     last = full[0] == first + count - 1
     assert last.sum() >= 1

@@ -20,7 +20,7 @@ import sys
 
 import numpy as np
 
-from test_cull import mt_accepts
+from kernel_restatements import mt_accepts
 
 N = importlib.import_module("squigly-trace_amd._native")
 f32 = np.float32
