@@ -258,7 +258,14 @@ def test_device_primitives_bit_exact(sqt, O):
     got = sqt.debug_eval("tfgen3", seeds)
     want = np.array([O.tfgen_words(int(s))[:3] for s in seeds], np.uint32)
     assert np.array_equal(got, want)
-    c = np.concatenate([rng.uniform(0, 3, (20000, 3)), rng.uniform(0, 120, (2000, 3)), [[0, 0, 0], [100, 100, 100], [0, 0, 1], [np.inf, 1, 1]]]).astype(np.float32)
+    # skies and lights allow negative and NaN radiance: the two floor ... mod 256 forms on negative, -0, NaN and +-3e38 components, mixed
+    # per channel (every ordered triple of the specials, and specials among ordinary values)
+    specials = np.array([-0.0, -1e-30, -0.5, -1.0, -255.5, -3e38, 3e38, np.nan, -np.inf, 1e-30, 0.25], np.float32)
+    triples = np.stack(np.meshgrid(specials, specials, specials, indexing="ij"), -1).reshape(-1, 3)
+    mixed = rng.uniform(-3, 3, (4000, 3))
+    mixed[np.arange(4000), rng.integers(0, 3, 4000)] = specials[rng.integers(0, len(specials), 4000)]
+    c = np.concatenate([rng.uniform(0, 3, (20000, 3)), rng.uniform(0, 120, (2000, 3)), [[0, 0, 0], [100, 100, 100], [0, 0, 1], [np.inf, 1, 1]],
+                        rng.uniform(-120, 3, (4000, 3)), triples, mixed]).astype(np.float32)
     got = sqt.debug_eval("tonemap", c)
     want = np.array([O.tonemap(tuple(float(v) for v in row)) for row in c], np.uint8)
     assert np.array_equal(got, want)
