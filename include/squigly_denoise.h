@@ -1,0 +1,105 @@
+/* squigly_denoise.h — C-ABI of libsquigly_denoise.so: a variance- and geometry-guided edge-avoiding filter for the frames
+ * libsquigly_hip.so leaves on the device.
+ *
+ * The filter knows nothing of scenes, trees or generators: it maps device images to device images.  Its inputs are what the
+ * other library's calls leave behind: d_sum, d_sum2, d_count of sq_render_rows_device_masked (the variance), d_tri and d_point
+ * of sq_intersect_rays_device over sq_camera_rays_device (the guides).
+ *
+ * Conventions (squigly_hip.h's)
+ *  - plain C; every function that returns int returns 0 on success, non-zero on failure, and sq_denoise_last_error() then
+ *    holds a message (thread-local).  Nothing is written on failure, and a refused call enqueues nothing.
+ *  - a call only enqueues work on hip_stream, which may be any stream of `device`, non-blocking ones with work pending
+ *    included.  The library allocates nothing on the device and keeps no state: there is no HOST WAIT anywhere.
+ *  - images are rows x cols, row-major, laid out like d_avg (the project's "w rows x h columns"): a colour, normal or point
+ *    image has 3 floats per pixel, a variance or triangle image one value.
+ *  - values are not checked: NaN, infinite and negative inputs are inputs like any other.
+ *  - the arithmetic is pinned operation by operation (below; tests/denoise_restatement.py restates it in numpy), so every
+ *    kernel form gives the same bits.
+ */
+#ifndef SQUIGLY_DENOISE_H
+#define SQUIGLY_DENOISE_H
+#include <stddef.h>
+#include <stdint.h>
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+typedef struct {
+    int32_t passes;            /* 1..8; pass i uses step 2^i */
+    float   sigma_l, eps_l;    /* luminance stop, in standard deviations; floor */
+    float   sigma_p;           /* plane-distance stop, world units */
+    int32_t normal_squarings;  /* 0..8: normal weight = max(0, n_p.n_q)^(2^k) */
+    int32_t form;              /* 0 = choose per pass; 1.. = force one kernel form (tests, timing) */
+} sq_denoise_params;
+
+/* Kernel forms of a pass (params.form).  Every form gives the same bits. */
+#define SQ_DENOISE_FORM_AUTO   0   /* per pass: what sq_denoise_pass_form says */
+#define SQ_DENOISE_FORM_DIRECT 1   /* every tap is read from the workspace records (L1 / L2) */
+#define SQ_DENOISE_FORM_TILED  2   /* a 16 x 16 tile plus its halo of 2 * step pixels is staged in LDS; steps 1, 2 and 4 only:
+                                      a larger step takes the direct form even when this one is forced */
+#define SQ_DENOISE_N_FORMS     2
+
+const char* sq_denoise_last_error(void);
+/* Hash of the library's source, headers and flags (build.py: denoise_source_id). */
+const char* sq_denoise_build_id(void);
+/* The form form = 0 runs pass `pass` (step 2^pass) in; -1 when pass is not in 0..7. */
+int32_t sq_denoise_pass_form(int32_t pass);
+
+/* Bytes of workspace sq_denoise_device needs for a rows x cols image: four 16-byte records per pixel (normal + validity, point,
+ * and two of colour + variance that the passes go to and fro between).  0 when rows or cols < 1 or rows * cols > 2^31 - 1.
+ * Monotone in both arguments. */
+size_t sq_denoise_workspace_bytes(int32_t rows, int32_t cols);
+
+/* The variance of the pixel mean's luminance from a masked call's statistics, for n_pixels >= 0 pixels.  Every operation is
+ * one fp32 operation, in this order:
+ *     n = (float)count;   per channel c:  m_c = s_c / n;  d_c = q_c / n - m_c * m_c;  var_c = d_c > 0 ? d_c / (n - 1) : +0
+ *     v = (0.0625 * var_0 + 0.25 * var_1) + 0.0625 * var_2
+ * a pixel with count < 2 gets v = l * l with l = (0.25 * m_0 + 0.5 * m_1) + 0.25 * m_2, a pixel with count < 1 gets +0.
+ * d_var must not overlap an input.  Refused: a NULL pointer, n_pixels < 0, an overlap. */
+int sq_denoise_variance_device(int32_t device, int64_t n_pixels, const float* d_sum, const float* d_sum2,
+                               const int32_t* d_count, float* d_var, void* hip_stream);
+
+/* The filter.  Pass i = 0 .. passes-1 uses s = 2^i and maps (C_i, V_i) to (C_i+1, V_i+1); C_0 = d_color, V_0 = d_var, the last
+ * pair goes to d_out and d_out_var.  valid(p) = d_tri[p] >= 0; n_p, P_p = d_normal[p], d_point[p];
+ * l(c) = (0.25 * c.r + 0.5 * c.g) + 0.25 * c.b;  K = {0.375, 0.25, 0.0625};  G = {0.5, 0.25}.  Every operation is one fp32
+ * operation, in exactly this order:
+ *   a pixel that is not valid is copied through, colour and variance, bit for bit, in every pass.  For a valid p = (y, x):
+ *   with variance:  gs = gw = +0;  for dy = -1, 0, 1 (outer), dx = -1, 0, 1, q = (y+dy, x+dx) inside the image and valid:
+ *                       g = G[|dy|] * G[|dx|];  gs = gs + g * V_i[q];  gw = gw + g
+ *                   gv = gs / gw;  sd = sigma_l * sqrt(gv) + eps_l
+ *   sw = +0, sc = (+0, +0, +0), sv = +0;  taps dy = -2..2 (outer), dx = -2..2 (inner), q = (y + dy*s, x + dx*s); a tap outside the
+ *   image or not valid is left out, otherwise
+ *       kw = K[|dy|] * K[|dx|]
+ *       dn = (n_p.x*n_q.x + n_p.y*n_q.y) + n_p.z*n_q.z;  t = dn > 0 ? dn : +0;  t = t * t, normal_squarings times
+ *       e = P_q - P_p;  pd = (n_p.x*e.x + n_p.y*e.y) + n_p.z*e.z;  a = pd / sigma_p;  wz = 1 / (1 + a * a)
+ *       with variance:  b = (l(C_i[q]) - l(C_i[p])) / sd;  wl = 1 / (1 + b * b);  w = ((kw * t) * wz) * wl
+ *       without d_var:  w = (kw * t) * wz
+ *       sw = sw + w;  sc_c = sc_c + w * C_i[q]_c;  sv = sv + (w * w) * V_i[q]
+ *   if sw > 0:  C_i+1[p]_c = sc_c / sw,  V_i+1[p] = sv / (sw * sw);  otherwise (a NaN compares false) the pixel is copied through.
+ * A tap whose weight is zero is still added (0 * inf is the NaN the expression says).
+ *
+ * d_var and d_out_var are optional (NULL), d_out_var only with d_var.  d_out == d_color and d_out_var == d_var are allowed.
+ * d_work: work_bytes >= sq_denoise_workspace_bytes(rows, cols) bytes on the device, 16-byte aligned; its contents on entry do
+ * not matter and are undefined afterwards.
+ * Refused before anything is enqueued: a NULL required pointer; rows or cols < 1 or rows * cols > 2^31 - 1; passes,
+ * normal_squarings or form out of range; a sigma that is NaN or <= 0, eps_l NaN or < 0; d_out_var without d_var; work_bytes too
+ * small or d_work misaligned; any other overlap among the buffers or with the workspace. */
+int sq_denoise_device(int32_t device, int32_t rows, int32_t cols,
+                      const float* d_color, const float* d_var /* optional */,
+                      const int32_t* d_tri, const float* d_normal, const float* d_point,
+                      const sq_denoise_params* params,
+                      float* d_out, float* d_out_var /* optional, only with d_var */,
+                      void* d_work, size_t work_bytes, void* hip_stream);
+
+/* Measurement aid (tools/gpu_denoise.py): one stage of the call above on its own, so that it can be timed between two events.
+ * stage -1 is the pack pre-pass (inputs -> workspace records), stage i in 0..passes-1 is pass i, which reads the workspace as
+ * the stages before it left it.  Running the stages -1, 0, .., passes-1 in order is sq_denoise_device. */
+int sq_denoise_stage_device(int32_t device, int32_t rows, int32_t cols,
+                            const float* d_color, const float* d_var, const int32_t* d_tri, const float* d_normal,
+                            const float* d_point, const sq_denoise_params* params, float* d_out, float* d_out_var,
+                            void* d_work, size_t work_bytes, void* hip_stream, int32_t stage);
+
+#ifdef __cplusplus
+}
+#endif
+#endif

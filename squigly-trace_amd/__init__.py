@@ -7,6 +7,8 @@ from ._native import Camera, Shard, SquiglyError, lib, LIB_PATH, EXPORTED_SYMBOL
 from .scene import BIH, Mesh, load_camera, camera_from_text, rot_matrix_rads       # noqa: F401
 from .render import Settings, render, render_rgb8, render_f32, render_progressive, render_adaptive, render_views_rgb8   # noqa: F401
 from .png import write_png                                                          # noqa: F401
+# the filter: sqt.denoise is the function; its module is importlib.import_module("squigly-trace_amd.denoise")
+from .denoise import denoise, denoise_variance, denoise_frame, Guides                # noqa: F401
 
 
 def device_count() -> int:

@@ -1,4 +1,4 @@
-"""Build libsquigly_hip.so (HIP kernels for gfx950 + host side) in-tree with hipcc.
+"""Build libsquigly_hip.so (HIP kernels for gfx950 + host side) and libsquigly_denoise.so (the denoiser) in-tree with hipcc.
 
     python squigly-trace_amd/build.py [--force]
 
@@ -68,12 +68,48 @@ def stale():
 
 CLI = os.path.join(HERE, "bin", "squigly-trace")
 
+# The second library: the denoiser (include/squigly_denoise.h).  One source, the same FLAGS (its bits rest on -ffp-contract=off and
+# the correctly rounded divide / sqrt as the renderer's do), an id and a staleness check of its own: source_id() above does not see
+# it, so the main library's id -- and the counter files stamped with it -- do not move when the filter changes.
+DENOISE_OUT = os.path.join(HERE, "libsquigly_denoise.so")
+DENOISE_SOURCES = ["sq_denoise.hip"]
+DENOISE_HEADERS = ["sq_math.h", "sq_error.h", "../../include/squigly_denoise.h"]
+
+
+def denoise_source_id():
+    """First 16 hex digits of SHA-256 over the denoiser's source, its headers and the flags: what sq_denoise_build_id() returns."""
+    import hashlib
+    h = hashlib.sha256(b"denoise\0")
+    for f in sorted(DENOISE_SOURCES + DENOISE_HEADERS):
+        h.update(f.encode() + b"\0")
+        with open(os.path.join(CSRC, f), "rb") as fh:
+            h.update(fh.read())
+    h.update("\0".join(FLAGS).encode())
+    return h.hexdigest()[:16]
+
+
+def denoise_stale():
+    """As stale(), for libsquigly_denoise.so: it must carry the current denoise_source_id()."""
+    if not os.path.exists(DENOISE_OUT):
+        return True
+    with open(DENOISE_OUT, "rb") as f:
+        return denoise_source_id().encode() not in f.read()
+
+
+def build_denoise(force=False):
+    if not force and not denoise_stale():
+        return DENOISE_OUT
+    subprocess.check_call([hipcc()] + FLAGS + ['-DSQ_DENOISE_BUILD_ID="%s"' % denoise_source_id(), "-x", "hip"]
+                          + [os.path.join(CSRC, s) for s in DENOISE_SOURCES] + ["-o", DENOISE_OUT])
+    return DENOISE_OUT
+
 
 def build(force=False, extra=(), out=None):
     """out: build an experimental variant (extra -D flags) beside the product library; SQ_LIB_PATH selects it at load time."""
     if out is not None:
         subprocess.check_call([hipcc()] + FLAGS + list(extra) + id_flag(extra) + ["-x", "hip"] + [os.path.join(CSRC, s) for s in SOURCES] + ["-o", out])
         return out
+    build_denoise(force)
     if not force and not stale() and os.path.exists(CLI):
         return OUT
     cmd = [hipcc()] + FLAGS + list(extra) + id_flag(extra) + ["-x", "hip"] + [os.path.join(CSRC, s) for s in SOURCES] + ["-o", OUT]

@@ -42,6 +42,16 @@ def nonneg_float(text):
     return v
 
 
+def positive_float(text):
+    try:
+        v = float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError("expected a number > 0")
+    if not v > 0:
+        raise argparse.ArgumentTypeError("expected a number > 0")
+    return v
+
+
 def path_depth(text):
     try:
         v = int(text)
@@ -145,6 +155,9 @@ def build_parser():
     p.add_argument("--adaptive-step", type=positive_int, default=8, metavar="N", help="Samples per later step (default 8)")
     p.add_argument("--adaptive-eps", type=nonneg_float, default=1.0, metavar="E", help="Absolute floor of the rule, in squared radiance per channel (default 1.0)")
     p.add_argument("--counts", default=None, metavar="FILE", help="With --adaptive: write the per-pixel sample counts to FILE (.npy, int32)")
+    p.add_argument("--denoise", type=positive_float, nargs="?", const=True, default=None, metavar="SIGMA_L",
+                   help="With --adaptive: filter the finished frame on the device, guided by its first hits and its own variance; "
+                        "SIGMA_L is the luminance stop in standard deviations (default 4)")
     # not a flag of the reference: where the light of --cast is (the reference's is fixed at 0,3,-1 with power 2)
     p.add_argument("--light", type=parse_light, action="append", default=None, metavar="X,Y,Z[,P|,R,G,B]",
                    help="With --cast: a point light at X,Y,Z with power P (default 2) or R,G,B; repeat for several lights, "
@@ -169,6 +182,8 @@ def parse_args(argv=None):
         p.error("--adaptive cannot be combined with --views or --preview-every")
     if a.counts is not None and a.adaptive is None:
         p.error("--counts needs --adaptive")
+    if a.denoise is not None and a.adaptive is None:
+        p.error("--denoise needs --adaptive (the filter takes its variance from the adaptive frame's second moments)")
     if a.light is not None and not a.cast:
         p.error("--light needs --cast")
     if a.depth is not None and a.cast:
@@ -218,8 +233,10 @@ def main(argv=None):
         import numpy as np
         for done, live, spent, img, counts in render_adaptive(bih, cam, settings.samples, settings.dimensions, a.adaptive, eps=a.adaptive_eps,
                                                               first=a.adaptive_first, step=a.adaptive_step, cast=settings.cast, lights=a.light,
-                                                              depth=a.depth, sky=a.sky):
+                                                              depth=a.depth, sky=a.sky, denoise=a.denoise):
             print(f"Adaptive {done}/{settings.samples} live {live} spent {spent}")
+        if a.denoise is not None:
+            print("Denoised")
         write_png(settings.savePath, img)
         if a.counts is not None:
             with open(a.counts, "wb") as f:                     # the name as given (np.save would append .npy to a path)

@@ -1,0 +1,375 @@
+// sq_denoise.hip — libsquigly_denoise.so (include/squigly_denoise.h): a variance- and geometry-guided a-trous filter over device
+// images.  It knows nothing of scenes: device images in, device images out, a caller-given workspace, no state.
+//
+// A call is a pack pre-pass and `passes` filter passes.  The pre-pass turns the five input images into 16-byte records, so that a
+// tap is three dwordx4 loads instead of ten dword loads at a stride of 12 bytes:
+//     NV  normal.xyz, validity (1 / 0 as an integer)
+//     PT  point.xyz, 0
+//     CV  colour.rgb, variance         two of them: pass i reads CV[i & 1] and writes CV[~i & 1], the last pass writes d_out
+// Every input is read by the pre-pass alone, which is why d_out == d_color is allowed.
+//
+// The arithmetic of a pixel (filter_pixel) is written once, operation by operation as the header states it, and is the same for
+// every kernel form: a form only decides how a tap's records reach the lane (Direct: from the workspace; Tiled: from an LDS image
+// of the tile and its halo).  -ffp-contract=off and the correctly rounded divide / sqrt keep it equal to the numpy restatement.
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
+
+#include "sq_error.h"
+#include "sq_math.h"
+#include "../../include/squigly_denoise.h"
+
+#ifndef SQ_DENOISE_BUILD_ID
+#define SQ_DENOISE_BUILD_ID "unknown"
+#endif
+
+#define SQ_HIP(expr)                                                                             \
+    do {                                                                                         \
+        hipError_t e_ = (expr);                                                                  \
+        if (e_ != hipSuccess) return sq_set_error("%s failed: %s", #expr, hipGetErrorString(e_)); \
+    } while (0)
+
+namespace {
+
+constexpr int kBlock = 256;
+constexpr long long kMaxPixels = 0x7fffffffLL;
+constexpr int kMaxGrid = 1 << 16;          // blocks of a launch; the kernels stride over their tiles
+// Direct form: a block is 4 rows of 64 pixels, a wave one row segment (a tap of a wave is 1 KiB of consecutive records)
+constexpr int kDirW = 64, kDirH = 4;
+// Tiled form: a block is a 16 x 16 tile; its LDS image has a halo of 2 * step pixels
+constexpr int kTile = 16;
+constexpr int kTiledMaxStep = 4;           // (16 + 4 * 4)^2 records * 48 B = 48 KiB: three blocks per CU
+
+struct Filter { float sigma_l, eps_l, sigma_p; int squarings; };
+
+__device__ __forceinline__ float lum(float r, float g, float b) { return (0.25f * r + 0.5f * g) + 0.25f * b; }
+__device__ __forceinline__ bool rec_valid(const float4& nv) { return __float_as_int(nv.w) != 0; }
+
+// The pixel arithmetic of include/squigly_denoise.h.  S gives the records of the pixel at an offset from p:
+//   S.nv(oy, ox, nv)  false when that pixel is outside the image or not valid (nv is then undefined)
+//   S.pt(oy, ox), S.cv(oy, ox)  of a pixel nv() said true for
+// cvp: CV of p.  Returns CV of p after the pass.
+template <bool VAR, class Src>
+__device__ __forceinline__ float4 filter_pixel(const Src& S, const int s, const Filter& F, const float4 nvp, const float4 ptp, const float4 cvp) {
+    float sd = 0.0f;
+    if (VAR) {
+        float gs = 0.0f, gw = 0.0f;
+#pragma unroll
+        for (int dy = -1; dy <= 1; ++dy) {
+#pragma unroll
+            for (int dx = -1; dx <= 1; ++dx) {
+                float4 nq;
+                if (!S.nv(dy, dx, nq)) continue;
+                const float g = (dy == 0 ? 0.5f : 0.25f) * (dx == 0 ? 0.5f : 0.25f);
+                gs = gs + g * S.cv(dy, dx).w;
+                gw = gw + g;
+            }
+        }
+        const float gv = gs / gw;
+        sd = F.sigma_l * sq::fsqrt(gv) + F.eps_l;
+    }
+    const float lp = lum(cvp.x, cvp.y, cvp.z);
+    float sw = 0.0f, scr = 0.0f, scg = 0.0f, scb = 0.0f, sv = 0.0f;
+#pragma unroll
+    for (int dy = -2; dy <= 2; ++dy) {
+#pragma unroll
+        for (int dx = -2; dx <= 2; ++dx) {
+            float4 nq;
+            if (!S.nv(dy * s, dx * s, nq)) continue;
+            const float4 pq = S.pt(dy * s, dx * s);
+            const float4 cq = S.cv(dy * s, dx * s);
+            const float ky = dy == 0 ? 0.375f : (dy == 1 || dy == -1) ? 0.25f : 0.0625f;
+            const float kx = dx == 0 ? 0.375f : (dx == 1 || dx == -1) ? 0.25f : 0.0625f;
+            const float kw = ky * kx;
+            const float dn = (nvp.x * nq.x + nvp.y * nq.y) + nvp.z * nq.z;
+            float t = dn > 0.0f ? dn : 0.0f;
+            for (int k = 0; k < F.squarings; ++k) t = t * t;
+            const float ex = pq.x - ptp.x, ey = pq.y - ptp.y, ez = pq.z - ptp.z;
+            const float pd = (nvp.x * ex + nvp.y * ey) + nvp.z * ez;
+            const float a = pd / F.sigma_p;
+            const float wz = 1.0f / (1.0f + a * a);
+            float w = (kw * t) * wz;
+            if (VAR) {
+                const float b = (lum(cq.x, cq.y, cq.z) - lp) / sd;
+                const float wl = 1.0f / (1.0f + b * b);
+                w = w * wl;
+            }
+            sw = sw + w;
+            scr = scr + w * cq.x;
+            scg = scg + w * cq.y;
+            scb = scb + w * cq.z;
+            if (VAR) sv = sv + (w * w) * cq.w;
+        }
+    }
+    if (sw > 0.0f) return make_float4(scr / sw, scg / sw, scb / sw, VAR ? sv / (sw * sw) : cvp.w);
+    return cvp;
+}
+
+// Where a pass leaves a pixel: the other CV image, or (the last pass) the caller's outputs.
+__device__ __forceinline__ void store_pixel(const long long p, const float4 cv, float4* cv_out, float* out, float* out_var) {
+    if (out) {
+        out[3 * p + 0] = cv.x; out[3 * p + 1] = cv.y; out[3 * p + 2] = cv.z;
+        if (out_var) out_var[p] = cv.w;
+    } else {
+        cv_out[p] = cv;
+    }
+}
+
+// ---- pack pre-pass ----
+__global__ __launch_bounds__(kBlock) void sq_dn_pack(const long long n, const float* __restrict__ color, const float* __restrict__ var,
+                                                     const int32_t* __restrict__ tri, const float* __restrict__ normal,
+                                                     const float* __restrict__ point, float4* __restrict__ nv, float4* __restrict__ pt,
+                                                     float4* __restrict__ cv) {
+    for (long long p = (long long)blockIdx.x * kBlock + threadIdx.x; p < n; p += (long long)gridDim.x * kBlock) {
+        nv[p] = make_float4(normal[3 * p], normal[3 * p + 1], normal[3 * p + 2], __int_as_float(tri[p] >= 0 ? 1 : 0));
+        pt[p] = make_float4(point[3 * p], point[3 * p + 1], point[3 * p + 2], 0.0f);
+        cv[p] = make_float4(color[3 * p], color[3 * p + 1], color[3 * p + 2], var ? var[p] : 0.0f);
+    }
+}
+
+// ---- variance of the pixel mean's luminance ----
+__global__ __launch_bounds__(kBlock) void sq_dn_variance(const long long n, const float* __restrict__ sum, const float* __restrict__ sum2,
+                                                         const int32_t* __restrict__ count, float* __restrict__ var) {
+    for (long long p = (long long)blockIdx.x * kBlock + threadIdx.x; p < n; p += (long long)gridDim.x * kBlock) {
+        const int32_t c = count[p];
+        float v = 0.0f;
+        if (c >= 1) {
+            const float nf = (float)c;
+            float m[3], vc[3];
+            for (int k = 0; k < 3; ++k) {
+                m[k] = sum[3 * p + k] / nf;
+                const float d = sum2[3 * p + k] / nf - m[k] * m[k];
+                vc[k] = d > 0.0f ? d / (nf - 1.0f) : 0.0f;
+            }
+            if (c < 2) {
+                const float l = lum(m[0], m[1], m[2]);
+                v = l * l;
+            } else {
+                v = (0.0625f * vc[0] + 0.25f * vc[1]) + 0.0625f * vc[2];
+            }
+        }
+        var[p] = v;
+    }
+}
+
+// ---- direct form ----
+struct DirectSrc {
+    const float4* __restrict__ nv_; const float4* __restrict__ pt_; const float4* __restrict__ cv_;
+    long long y, x; int rows, cols;
+    __device__ __forceinline__ bool inside(int oy, int ox, long long& q) const {
+        const long long qy = y + oy, qx = x + ox;
+        q = qy * cols + qx;
+        return qy >= 0 && qy < rows && qx >= 0 && qx < cols;
+    }
+    __device__ __forceinline__ bool nv(int oy, int ox, float4& r) const {
+        long long q;
+        if (!inside(oy, ox, q)) return false;
+        r = nv_[q];
+        return rec_valid(r);
+    }
+    __device__ __forceinline__ float4 pt(int oy, int ox) const { return pt_[(y + oy) * cols + (x + ox)]; }
+    __device__ __forceinline__ float4 cv(int oy, int ox) const { return cv_[(y + oy) * cols + (x + ox)]; }
+};
+
+template <bool VAR>
+__global__ __launch_bounds__(kBlock) void sq_dn_pass_direct(const int rows, const int cols, const int s, const Filter F,
+                                                            const float4* __restrict__ nv, const float4* __restrict__ pt,
+                                                            const float4* __restrict__ cv_in, float4* __restrict__ cv_out,
+                                                            float* __restrict__ out, float* __restrict__ out_var,
+                                                            const long long tiles, const long long tiles_x) {
+    for (long long t = blockIdx.x; t < tiles; t += gridDim.x) {
+        const long long ty = t / tiles_x, tx = t - ty * tiles_x;
+        const long long x = tx * kDirW + (threadIdx.x & (kDirW - 1)), y = ty * kDirH + (threadIdx.x / kDirW);
+        if (x >= cols || y >= rows) continue;
+        const long long p = y * cols + x;
+        const float4 nvp = nv[p], cvp = cv_in[p];
+        float4 r = cvp;
+        if (rec_valid(nvp)) {
+            const DirectSrc S{ nv, pt, cv_in, y, x, rows, cols };
+            r = filter_pixel<VAR>(S, s, F, nvp, pt[p], cvp);
+        }
+        store_pixel(p, r, cv_out, out, out_var);
+    }
+}
+
+// ---- tiled form ----
+// The LDS image: (16 + 4 s)^2 pixels, three arrays of records.  A pixel outside the image is stored as not valid, so a tap needs
+// no bounds test of its own.
+struct TiledSrc {
+    const float4* nv_; const float4* pt_; const float4* cv_;
+    int at, w;              // p's index in the LDS image; the image's width
+    __device__ __forceinline__ bool nv(int oy, int ox, float4& r) const { r = nv_[at + oy * w + ox]; return rec_valid(r); }
+    __device__ __forceinline__ float4 pt(int oy, int ox) const { return pt_[at + oy * w + ox]; }
+    __device__ __forceinline__ float4 cv(int oy, int ox) const { return cv_[at + oy * w + ox]; }
+};
+
+template <bool VAR>
+__global__ __launch_bounds__(kBlock) void sq_dn_pass_tiled(const int rows, const int cols, const int s, const Filter F,
+                                                           const float4* __restrict__ nv, const float4* __restrict__ pt,
+                                                           const float4* __restrict__ cv_in, float4* __restrict__ cv_out,
+                                                           float* __restrict__ out, float* __restrict__ out_var,
+                                                           const long long tiles, const long long tiles_x) {
+    extern __shared__ float4 lds[];
+    const int halo = 2 * s, w = kTile + 2 * halo, n = w * w;
+    float4* l_nv = lds;
+    float4* l_pt = lds + n;
+    float4* l_cv = lds + 2 * n;
+    const int lx = threadIdx.x & (kTile - 1), ly = threadIdx.x / kTile;
+    for (long long t = blockIdx.x; t < tiles; t += gridDim.x) {
+        const long long ty = t / tiles_x, tx = t - ty * tiles_x;
+        const long long y0 = ty * kTile - halo, x0 = tx * kTile - halo;
+        for (int i = threadIdx.x; i < n; i += kBlock) {
+            const int iy = i / w, ix = i - iy * w;
+            const long long gy = y0 + iy, gx = x0 + ix;
+            float4 a = make_float4(0.0f, 0.0f, 0.0f, __int_as_float(0)), b = make_float4(0.0f, 0.0f, 0.0f, 0.0f), c = b;
+            if (gy >= 0 && gy < rows && gx >= 0 && gx < cols) {
+                const long long q = gy * cols + gx;
+                a = nv[q]; b = pt[q]; c = cv_in[q];
+            }
+            l_nv[i] = a; l_pt[i] = b; l_cv[i] = c;
+        }
+        __syncthreads();
+        const long long y = ty * kTile + ly, x = tx * kTile + lx;
+        if (x < cols && y < rows) {
+            const int at = (ly + halo) * w + (lx + halo);
+            const float4 nvp = l_nv[at], cvp = l_cv[at];
+            float4 r = cvp;
+            if (rec_valid(nvp)) {
+                const TiledSrc S{ l_nv, l_pt, l_cv, at, w };
+                r = filter_pixel<VAR>(S, s, F, nvp, l_pt[at], cvp);
+            }
+            store_pixel(y * cols + x, r, cv_out, out, out_var);
+        }
+        __syncthreads();        // the next tile's image overwrites this one
+    }
+}
+
+// The form of pass `pass` when the caller leaves the choice (form = 0): the tiled form wherever its LDS image fits.  Measured at
+// 1920 x 1080 (tools/gpu_denoise.py): 0.111 / 0.112 / 0.114 ms at steps 1 / 2 / 4 against 0.173 / 0.173 / 0.177 ms direct.
+int auto_form(int pass) { return (1 << pass) <= kTiledMaxStep ? SQ_DENOISE_FORM_TILED : SQ_DENOISE_FORM_DIRECT; }
+
+struct Span { const char* name; uintptr_t lo, hi; };
+bool overlap(const Span& a, const Span& b) { return a.lo < b.hi && b.lo < a.hi; }
+
+// Everything that can be refused, in the order of the header's list.  Touches neither the device nor a buffer.
+int check_call(int32_t rows, int32_t cols, const float* d_color, const float* d_var, const int32_t* d_tri, const float* d_normal,
+               const float* d_point, const sq_denoise_params* P, float* d_out, float* d_out_var, void* d_work, size_t work_bytes) {
+    if (!d_color || !d_tri || !d_normal || !d_point || !P || !d_out || !d_work)
+        return sq_set_error("null argument: d_color, d_tri, d_normal, d_point, params, d_out and d_work are required");
+    if (rows < 1 || cols < 1) return sq_set_error("rows and cols must be at least 1 (got %d x %d)", rows, cols);
+    if ((long long)rows * cols > kMaxPixels) return sq_set_error("%d x %d pixels exceed 2^31 - 1 pixels in one call", rows, cols);
+    if (P->passes < 1 || P->passes > 8) return sq_set_error("passes must be in 1..8 (got %d)", P->passes);
+    if (P->normal_squarings < 0 || P->normal_squarings > 8) return sq_set_error("normal_squarings must be in 0..8 (got %d)", P->normal_squarings);
+    if (P->form < 0 || P->form > SQ_DENOISE_N_FORMS) return sq_set_error("form must be in 0..%d (got %d)", SQ_DENOISE_N_FORMS, P->form);
+    if (!(P->sigma_l > 0.0f)) return sq_set_error("sigma_l must be a number > 0 (got %g)", (double)P->sigma_l);
+    if (!(P->sigma_p > 0.0f)) return sq_set_error("sigma_p must be a number > 0 (got %g)", (double)P->sigma_p);
+    if (!(P->eps_l >= 0.0f)) return sq_set_error("eps_l must be a number >= 0 (got %g)", (double)P->eps_l);
+    if (d_out_var && !d_var) return sq_set_error("d_out_var needs d_var: without a variance image there is none to filter");
+    const size_t need = sq_denoise_workspace_bytes(rows, cols);
+    if (work_bytes < need) return sq_set_error("work_bytes = %zu is too small: a %d x %d image needs %zu", work_bytes, rows, cols, need);
+    if ((uintptr_t)d_work % 16 != 0) return sq_set_error("d_work must be 16-byte aligned");
+    const uintptr_t n = (uintptr_t)((long long)rows * cols);
+    const Span spans[8] = {
+        { "d_color", (uintptr_t)d_color, (uintptr_t)d_color + 12 * n }, { "d_var", (uintptr_t)d_var, (uintptr_t)d_var + (d_var ? 4 * n : 0) },
+        { "d_tri", (uintptr_t)d_tri, (uintptr_t)d_tri + 4 * n }, { "d_normal", (uintptr_t)d_normal, (uintptr_t)d_normal + 12 * n },
+        { "d_point", (uintptr_t)d_point, (uintptr_t)d_point + 12 * n }, { "d_out", (uintptr_t)d_out, (uintptr_t)d_out + 12 * n },
+        { "d_out_var", (uintptr_t)d_out_var, (uintptr_t)d_out_var + (d_out_var ? 4 * n : 0) },
+        { "d_work", (uintptr_t)d_work, (uintptr_t)d_work + work_bytes } };
+    for (int i = 0; i < 8; ++i)
+        for (int j = i + 1; j < 8; ++j) {
+            if (!overlap(spans[i], spans[j])) continue;
+            if (i == 0 && j == 5 && spans[i].lo == spans[j].lo) continue;      // d_out == d_color
+            if (i == 1 && j == 6 && spans[i].lo == spans[j].lo) continue;      // d_out_var == d_var
+            return sq_set_error("%s and %s overlap (only d_out == d_color and d_out_var == d_var may share memory)", spans[i].name, spans[j].name);
+        }
+    return 0;
+}
+
+unsigned grid_for(long long units) { return (unsigned)(units < kMaxGrid ? units : kMaxGrid); }
+
+// Enqueues the stages [first, last] of a checked call: -1 = the pack pre-pass, i = pass i.
+int enqueue(int32_t device, int32_t rows, int32_t cols, const float* d_color, const float* d_var, const int32_t* d_tri,
+            const float* d_normal, const float* d_point, const sq_denoise_params& P, float* d_out, float* d_out_var, void* d_work,
+            void* hip_stream, int first, int last) {
+    SQ_HIP(hipSetDevice(device));
+    hipStream_t stream = (hipStream_t)hip_stream;
+    const long long n = (long long)rows * cols;
+    float4* nv = (float4*)d_work;
+    float4* pt = nv + n;
+    float4* cv[2] = { pt + n, pt + 2 * n };
+    const Filter F{ P.sigma_l, P.eps_l, P.sigma_p, P.normal_squarings };
+    for (int stage = first; stage <= last; ++stage) {
+        if (stage < 0) {
+            hipLaunchKernelGGL(sq_dn_pack, dim3(grid_for((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, n, d_color, d_var, d_tri,
+                               d_normal, d_point, nv, pt, cv[0]);
+            SQ_HIP(hipGetLastError());
+            continue;
+        }
+        const int s = 1 << stage;
+        const bool is_last = stage == P.passes - 1;
+        const float4* in = cv[stage & 1];
+        float4* out_cv = cv[(stage + 1) & 1];
+        float* out = is_last ? d_out : nullptr;
+        float* out_var = is_last ? d_out_var : nullptr;
+        int form = P.form == SQ_DENOISE_FORM_AUTO ? auto_form(stage) : P.form;
+        if (s > kTiledMaxStep) form = SQ_DENOISE_FORM_DIRECT;
+        if (form == SQ_DENOISE_FORM_TILED) {
+            const long long tx = ((long long)cols + kTile - 1) / kTile, ty = ((long long)rows + kTile - 1) / kTile;
+            const int w = kTile + 4 * s;
+            const size_t lds = (size_t)w * w * 3 * sizeof(float4);
+            if (d_var) hipLaunchKernelGGL(sq_dn_pass_tiled<true>, dim3(grid_for(tx * ty)), dim3(kBlock), lds, stream, rows, cols, s, F, nv, pt, in, out_cv, out, out_var, tx * ty, tx);
+            else       hipLaunchKernelGGL(sq_dn_pass_tiled<false>, dim3(grid_for(tx * ty)), dim3(kBlock), lds, stream, rows, cols, s, F, nv, pt, in, out_cv, out, out_var, tx * ty, tx);
+        } else {
+            const long long tx = ((long long)cols + kDirW - 1) / kDirW, ty = ((long long)rows + kDirH - 1) / kDirH;
+            if (d_var) hipLaunchKernelGGL(sq_dn_pass_direct<true>, dim3(grid_for(tx * ty)), dim3(kBlock), 0, stream, rows, cols, s, F, nv, pt, in, out_cv, out, out_var, tx * ty, tx);
+            else       hipLaunchKernelGGL(sq_dn_pass_direct<false>, dim3(grid_for(tx * ty)), dim3(kBlock), 0, stream, rows, cols, s, F, nv, pt, in, out_cv, out, out_var, tx * ty, tx);
+        }
+        SQ_HIP(hipGetLastError());
+    }
+    return 0;
+}
+
+}  // namespace
+
+extern "C" const char* sq_denoise_last_error(void) { return sq_error_buffer(); }
+extern "C" const char* sq_denoise_build_id(void) { return SQ_DENOISE_BUILD_ID; }
+extern "C" int32_t sq_denoise_pass_form(int32_t pass) { return pass < 0 || pass > 7 ? -1 : auto_form(pass); }
+
+extern "C" size_t sq_denoise_workspace_bytes(int32_t rows, int32_t cols) {
+    if (rows < 1 || cols < 1 || (long long)rows * cols > kMaxPixels) return 0;
+    return (size_t)rows * (size_t)cols * 4 * sizeof(float4);
+}
+
+extern "C" int sq_denoise_variance_device(int32_t device, int64_t n_pixels, const float* d_sum, const float* d_sum2,
+                                          const int32_t* d_count, float* d_var, void* hip_stream) {
+    if (!d_sum || !d_sum2 || !d_count || !d_var) return sq_set_error("null argument: d_sum, d_sum2, d_count and d_var are required");
+    if (n_pixels < 0) return sq_set_error("n_pixels must not be negative (got %lld)", (long long)n_pixels);
+    if (n_pixels > (int64_t)1 << 56) return sq_set_error("n_pixels = %lld is more than any device holds", (long long)n_pixels);
+    const uintptr_t n = (uintptr_t)n_pixels;
+    const Span out = { "d_var", (uintptr_t)d_var, (uintptr_t)d_var + 4 * n };
+    const Span in[3] = { { "d_sum", (uintptr_t)d_sum, (uintptr_t)d_sum + 12 * n }, { "d_sum2", (uintptr_t)d_sum2, (uintptr_t)d_sum2 + 12 * n },
+                         { "d_count", (uintptr_t)d_count, (uintptr_t)d_count + 4 * n } };
+    for (const Span& s : in)
+        if (overlap(out, s)) return sq_set_error("d_var and %s overlap", s.name);
+    if (n_pixels == 0) return 0;
+    SQ_HIP(hipSetDevice(device));
+    hipLaunchKernelGGL(sq_dn_variance, dim3(grid_for(((long long)n_pixels + kBlock - 1) / kBlock)), dim3(kBlock), 0, (hipStream_t)hip_stream,
+                       (long long)n_pixels, d_sum, d_sum2, d_count, d_var);
+    SQ_HIP(hipGetLastError());
+    return 0;
+}
+
+extern "C" int sq_denoise_device(int32_t device, int32_t rows, int32_t cols, const float* d_color, const float* d_var,
+                                 const int32_t* d_tri, const float* d_normal, const float* d_point, const sq_denoise_params* params,
+                                 float* d_out, float* d_out_var, void* d_work, size_t work_bytes, void* hip_stream) {
+    if (check_call(rows, cols, d_color, d_var, d_tri, d_normal, d_point, params, d_out, d_out_var, d_work, work_bytes)) return 1;
+    return enqueue(device, rows, cols, d_color, d_var, d_tri, d_normal, d_point, *params, d_out, d_out_var, d_work, hip_stream, -1, params->passes - 1);
+}
+
+extern "C" int sq_denoise_stage_device(int32_t device, int32_t rows, int32_t cols, const float* d_color, const float* d_var,
+                                       const int32_t* d_tri, const float* d_normal, const float* d_point, const sq_denoise_params* params,
+                                       float* d_out, float* d_out_var, void* d_work, size_t work_bytes, void* hip_stream, int32_t stage) {
+    if (check_call(rows, cols, d_color, d_var, d_tri, d_normal, d_point, params, d_out, d_out_var, d_work, work_bytes)) return 1;
+    if (stage < -1 || stage >= params->passes) return sq_set_error("stage must be in -1..%d (got %d)", params->passes - 1, stage);
+    return enqueue(device, rows, cols, d_color, d_var, d_tri, d_normal, d_point, *params, d_out, d_out_var, d_work, hip_stream, stage, stage);
+}

@@ -1,0 +1,228 @@
+"""ctypes binding of libsquigly_denoise.so (include/squigly_denoise.h) and the helpers around it.
+
+The filter maps device images to device images: colour and (optionally) the variance of its luminance in, guided by the first
+hit's triangle id, normal and point (DeviceScene.guides).  PyTorch is the plumbing (device memory, streams); every filtered pixel
+comes from the HIP kernels of csrc/sq_denoise.hip.  There is no fallback: a missing library raises.
+"""
+import collections
+import ctypes as C
+import os
+
+from . import _native as N
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+LIB_PATH = os.path.join(_HERE, "libsquigly_denoise.so")
+
+# include/squigly_denoise.h; sq_denoise_last_error and the functions a caller uses
+EXPORTED_SYMBOLS = ["sq_denoise_last_error", "sq_denoise_build_id", "sq_denoise_pass_form", "sq_denoise_workspace_bytes",
+                    "sq_denoise_variance_device", "sq_denoise_device", "sq_denoise_stage_device"]
+
+FORMS = {"auto": 0, "direct": 1, "tiled": 2}          # params.form (SQ_DENOISE_FORM_*)
+# The prototype's parameters.  sigma_p has no default here: it is a length of the scene (denoise_frame derives it).
+DEFAULTS = {"passes": 5, "sigma_l": 4.0, "eps_l": 1e-3, "normal_squarings": 3, "form": 0}
+
+Guides = collections.namedtuple("Guides", ["tri", "point", "normal", "surf", "emit"])
+Guides.__doc__ = """DeviceScene.guides: per pixel the first hit's triangle (int32, -1 = none), point, unit normal, and its material's surf
+and emissive *^ emit (float32 [rows, h, 3]; zeros where nothing is hit)."""
+
+
+class Params(C.Structure):
+    """sq_denoise_params."""
+    _fields_ = [("passes", C.c_int32), ("sigma_l", C.c_float), ("eps_l", C.c_float), ("sigma_p", C.c_float),
+                ("normal_squarings", C.c_int32), ("form", C.c_int32)]
+
+
+_lib = None
+
+
+def lib():
+    global _lib
+    if _lib is not None:
+        return _lib
+    if not os.path.exists(LIB_PATH):
+        raise ImportError(f"{LIB_PATH} is missing: build it with `python squigly-trace_amd/build.py` "
+                          "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
+    try:                     # as in _native.lib: torch's HIP runtime has to be the first one in the process
+        import torch  # noqa: F401
+    except ImportError:
+        pass
+    L = C.CDLL(LIB_PATH)
+    vp, i32 = C.c_void_p, C.c_int32
+    L.sq_denoise_last_error.restype = C.c_char_p
+    L.sq_denoise_build_id.restype = C.c_char_p
+    L.sq_denoise_pass_form.argtypes = [i32]
+    L.sq_denoise_pass_form.restype = i32
+    L.sq_denoise_workspace_bytes.argtypes = [i32, i32]
+    L.sq_denoise_workspace_bytes.restype = C.c_size_t
+    L.sq_denoise_variance_device.argtypes = [i32, C.c_int64, vp, vp, vp, vp, vp]
+    call = [i32, i32, i32, vp, vp, vp, vp, vp, C.POINTER(Params), vp, vp, vp, C.c_size_t, vp]
+    L.sq_denoise_device.argtypes = call
+    L.sq_denoise_stage_device.argtypes = call + [i32]
+    _lib = L
+    return L
+
+
+def check(rc):
+    if rc != 0:
+        raise N.SquiglyError(lib().sq_denoise_last_error().decode(errors="replace"))
+
+
+def build_id():
+    """sq_denoise_build_id(): hash of the sources and flags the loaded library was built from (build.py: denoise_source_id)."""
+    return lib().sq_denoise_build_id().decode()
+
+
+def workspace_bytes(rows, cols):
+    return int(lib().sq_denoise_workspace_bytes(int(rows), int(cols)))
+
+
+def make_params(sigma_p=None, **kw):
+    """sq_denoise_params from keyword arguments: DEFAULTS, sigma_p required; form by number or by name (FORMS)."""
+    unknown = set(kw) - set(DEFAULTS)
+    if unknown:
+        raise N.SquiglyError(f"unknown denoise parameter(s) {sorted(unknown)}: expected sigma_p and any of {sorted(DEFAULTS)}")
+    if sigma_p is None:
+        raise N.SquiglyError("sigma_p is required: the plane-distance stop in world units (denoise_frame derives it from the scene)")
+    p = dict(DEFAULTS, **kw)
+    form = p["form"]
+    if isinstance(form, str):
+        if form not in FORMS:
+            raise N.SquiglyError(f"form must be one of {sorted(FORMS)} or a number, got {form!r}")
+        form = FORMS[form]
+    return Params(int(p["passes"]), float(p["sigma_l"]), float(p["eps_l"]), float(sigma_p), int(p["normal_squarings"]), int(form))
+
+
+def _image(name, t, shape, dtype, dev):
+    import torch
+    if (not isinstance(t, torch.Tensor) or tuple(t.shape) != tuple(shape) or t.dtype != dtype or not t.is_contiguous()
+            or t.device != dev):
+        got = f"{t.dtype} {tuple(t.shape)} on {t.device}" if isinstance(t, torch.Tensor) else type(t).__name__
+        raise N.SquiglyError(f"{name} must be a contiguous {dtype} tensor of shape {tuple(shape)} on {dev}, got {got}")
+    return t
+
+
+def denoise(color, tri, normal, point, var=None, out=None, stream=None, **params):
+    """sq_denoise_device on device tensors; returns (out, out_var), out_var None without var.  Enqueued on `stream`.
+
+    color, normal, point: float32 [rows, cols, 3]; tri: int32 [rows, cols] (a pixel is filtered iff tri >= 0); var: float32
+    [rows, cols] or None.  out: a colour tensor, or (colour, variance) tensors, to receive the result (None = allocate); out may
+    be color itself, and the variance var itself.  params: sigma_p (required) and any of DEFAULTS.  The workspace is a tensor
+    allocated under the stream and handed back to the allocator, in the stream's order, when the call returns."""
+    import torch
+    if not isinstance(color, torch.Tensor) or color.dim() != 3 or color.shape[-1] != 3 or not color.is_cuda:
+        raise N.SquiglyError("color must be a float32 CUDA tensor of shape [rows, cols, 3]")
+    dev = color.device
+    rows, cols = int(color.shape[0]), int(color.shape[1])
+    P = make_params(**params)
+    f32 = torch.float32
+    _image("color", color, (rows, cols, 3), f32, dev)
+    _image("tri", tri, (rows, cols), torch.int32, dev)
+    _image("normal", normal, (rows, cols, 3), f32, dev)
+    _image("point", point, (rows, cols, 3), f32, dev)
+    if var is not None:
+        _image("var", var, (rows, cols), f32, dev)
+    out_c, out_v = out if isinstance(out, (tuple, list)) else (out, None)
+    if out_c is not None:
+        _image("out", out_c, (rows, cols, 3), f32, dev)
+    if out_v is not None:
+        if var is None:
+            raise N.SquiglyError("an output variance needs var")
+        _image("out variance", out_v, (rows, cols), f32, dev)
+    need = workspace_bytes(rows, cols)
+    if rows >= 1 and cols >= 1 and need == 0:
+        raise N.SquiglyError(f"{rows} x {cols} pixels exceed 2^31 - 1 pixels in one call")
+    st = stream if stream is not None else torch.cuda.current_stream(dev)
+    with torch.cuda.stream(st):      # outputs and workspace are allocated (and the workspace freed) in the order of the call's stream
+        if out_c is None:
+            out_c = torch.empty((rows, cols, 3), dtype=f32, device=dev)
+        if out_v is None and var is not None:
+            out_v = torch.empty((rows, cols), dtype=f32, device=dev)
+        work = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+        check(lib().sq_denoise_device(dev.index or 0, rows, cols, color.data_ptr(), var.data_ptr() if var is not None else None,
+                                      tri.data_ptr(), normal.data_ptr(), point.data_ptr(), C.byref(P), out_c.data_ptr(),
+                                      out_v.data_ptr() if out_v is not None else None, work.data_ptr(), need,
+                                      C.c_void_p(st.cuda_stream)))
+    return out_c, out_v
+
+
+def denoise_variance(sums, sums2, counts, stream=None):
+    """sq_denoise_variance_device: the variance of the pixel mean's luminance, float32 [...], from a masked call's statistics
+    (Adaptive.sums, .sums2 float32 [..., 3] and .counts int32 [...])."""
+    import torch
+    if not isinstance(counts, torch.Tensor) or not counts.is_cuda:
+        raise N.SquiglyError("counts must be an int32 CUDA tensor")
+    dev, shape = counts.device, tuple(counts.shape)
+    _image("counts", counts, shape, torch.int32, dev)
+    _image("sums", sums, shape + (3,), torch.float32, dev)
+    _image("sums2", sums2, shape + (3,), torch.float32, dev)
+    st = stream if stream is not None else torch.cuda.current_stream(dev)
+    with torch.cuda.stream(st):
+        var = torch.empty(shape, dtype=torch.float32, device=dev)
+        check(lib().sq_denoise_variance_device(dev.index or 0, counts.numel(), sums.data_ptr(), sums2.data_ptr(), counts.data_ptr(),
+                                               var.data_ptr(), C.c_void_p(st.cuda_stream)))
+    return var
+
+
+def default_sigma_p(bounds):
+    """The default plane-distance stop of a scene: 0.5 % of the diagonal of its root bounds (lo, hi as six numbers).  On
+    data/scene.obj -- the room, 4 x 4 x 4.23 -- that is 0.0353; the filter was prototyped there with 0.05, which is 0.7 % (pass
+    sigma_p=0.05 for the prototype's figures)."""
+    import math
+    b = [float(v) for v in bounds]
+    return 0.005 * math.sqrt(sum((b[3 + i] - b[i]) ** 2 for i in range(3)))
+
+
+def scene_guides(ds, cam, w, h, shard=(None, 0, 1), stream=None):
+    """DeviceScene.guides: camera_rays + intersect, then torch gathers from the scene's triangle and material arrays.  The normal
+    is the unit normal of Geometry.hs's `normal`, cross (b - a) (c - a) / its norm.  A convenience: not pinned to the bit."""
+    import numpy as np
+    import torch
+    dev = torch.device("cuda", ds.device)
+    st = stream if stream is not None else torch.cuda.current_stream(dev)
+    with torch.cuda.stream(st):
+        tables = getattr(ds, "_guide_tables", None)
+        if tables is None:        # per triangle: unit normal, surf, emissive *^ emit; one more row of zeros for "no hit"
+            t, m = ds.bih.tris, ds.bih.materials
+            with np.errstate(all="ignore"):
+                nrm = np.cross(t["v1"] - t["v0"], t["v2"] - t["v0"]).astype(np.float32)
+                nrm = nrm / np.sqrt((nrm * nrm).sum(-1, keepdims=True), dtype=np.float32)
+            mat = t["mat"]
+            surf = m["surf"][mat] if len(m) else np.zeros((len(t), 3), np.float32)
+            emit = (m["emissive"][mat][:, None] * m["emit"][mat]) if len(m) else np.zeros((len(t), 3), np.float32)
+            rows = [np.concatenate([np.asarray(a, np.float32).reshape(len(t), 3), np.zeros((1, 3), np.float32)]) for a in (nrm, surf, emit)]
+            tables = ds._guide_tables = tuple(torch.from_numpy(np.ascontiguousarray(r)).to(dev) for r in rows)
+        hits = ds.intersect(*ds.camera_rays(cam, w, h, shard, stream=st), want_dist=False, stream=st)
+        idx = torch.where(hits.tri >= 0, hits.tri, torch.full_like(hits.tri, tables[0].shape[0] - 1)).long()
+        normal, surf, emit = (tab[idx].contiguous() for tab in tables)
+    return Guides(hits.tri, hits.point, normal, surf, emit)
+
+
+def denoise_frame(ds, cam, w, h, avg, var=None, shard=(None, 0, 1), demodulate=True, guides=None, stream=None, **params):
+    """Filter the frame `avg` (float32 CUDA tensor [rows, h, 3]) of DeviceScene `ds` under its own guides; returns (out, out_var).
+
+    var: the variance of avg's luminance (denoise_variance) or None.  sigma_p defaults to default_sigma_p of the scene's root
+    bounds.  demodulate: the reference's shading makes every sample of a hit pixel surf0 * X + emissive0 *^ emit0 (src/Lib.hs:
+    127-137), so where all of surf is > 0 the helper filters X = (avg - emit) / surf -- the light arriving at the first hit, free
+    of the surface's own colour -- and multiplies back afterwards; the variance goes with it, divided by l(surf)^2 on the way in and
+    multiplied on the way out (exact for a grey surface, an estimate otherwise).  guides: what ds.guides(cam, w, h, shard) returned, to reuse it over frames of one camera."""
+    import torch
+    dev = torch.device("cuda", ds.device)
+    st = stream if stream is not None else torch.cuda.current_stream(dev)
+    if "sigma_p" not in params or params["sigma_p"] is None:
+        params["sigma_p"] = default_sigma_p(ds.bih.bounds)
+    make_params(**params)                    # refused before any device work
+    with torch.cuda.stream(st):
+        g = guides if guides is not None else scene_guides(ds, cam, w, h, shard, stream=st)
+        if not demodulate:
+            return denoise(avg, g.tri, g.normal, g.point, var=var, stream=st, **params)
+        ok = ((g.tri >= 0) & (g.surf > 0).all(-1))[..., None]
+        x = torch.where(ok, (avg - g.emit) / torch.where(ok, g.surf, torch.ones_like(g.surf)), avg)
+        if var is not None:
+            ls = (0.25 * g.surf[..., 0] + 0.5 * g.surf[..., 1]) + 0.25 * g.surf[..., 2]
+            scale = torch.where(ok[..., 0], ls * ls, torch.ones_like(ls))
+            var = var / scale
+        out, out_var = denoise(x, g.tri, g.normal, g.point, var=var, stream=st, **params)
+        out = torch.where(ok, out * g.surf + g.emit, out)
+        if out_var is not None:
+            out_var = out_var * scale
+    return out, out_var

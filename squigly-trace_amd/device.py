@@ -361,6 +361,13 @@ class DeviceScene:
                                               C.c_void_p(st.cuda_stream)))
         return o, d
 
+    def guides(self, cam, w, h, shard=(None, 0, 1), stream=None):
+        """What the denoiser is guided by (denoise.py): Guides(tri, point, normal, surf, emit) of every pixel's first hit, from
+        camera_rays + intersect and gathers from the scene's triangle and material arrays.  tri = -1 where nothing is hit, and the
+        other fields are zeros there.  A convenience, not pinned to the bit."""
+        from .denoise import scene_guides
+        return scene_guides(self, cam, w, h, shard, stream)
+
     def raytrace(self, origins, directions, seeds=None, samples=1, k_range=None, sums=None, want_avg=True, want_rgb=False,
                  stream=None):
         """Lib.raytrace of each ray (sq_raytrace_rays_device): returns Radiance(sum, avg, rgb) CUDA tensors, enqueued on `stream`.

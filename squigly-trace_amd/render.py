@@ -74,13 +74,26 @@ def render_progressive(bih, cam, samples, dimensions, step, cast=False, device=0
         ds.close()
 
 
+def denoise_options(denoise):
+    """denoise= of render_adaptive as keyword arguments of denoise_frame: True = the defaults, a number = sigma_l, a dict = itself."""
+    if denoise is True:
+        return {}
+    if isinstance(denoise, dict):
+        return dict(denoise)
+    if isinstance(denoise, (int, float)) and not isinstance(denoise, bool) and float(denoise) > 0:
+        return {"sigma_l": float(denoise)}
+    raise ValueError(f"denoise must be True, a sigma_l > 0 or a dict of denoise parameters, got {denoise!r}")
+
+
 def render_adaptive(bih, cam, samples, dimensions, tol, eps=1.0, first=8, step=8, cast=False, device=0, rule=None, lights=None,
-                    depth=None, sky=None):
+                    depth=None, sky=None, denoise=None):
     """The frame of render_rgb8 with adaptive sampling (DeviceScene, Adaptive): yields (done, live, spent, rgb8, counts) after
     every step -- the end of the range rendered, the pixels still live, the samples spent so far, the (w, h, 3) uint8 image and
     the (w, h) int32 per-pixel sample counts.  A pixel that stopped after n samples shows the mean of its first n samples, so
     with first >= samples (one step, every pixel live) the image is bit for bit that of render_rgb8.  lights, depth, sky: as in
-    render_progressive."""
+    render_progressive.  denoise (None = off; True, a sigma_l or a dict of denoise parameters): once the frame is finished, one more
+    tuple follows whose image is the frame filtered on the device (denoise_frame: the variance from the frame's own second moments,
+    the guides from its first hits) and tonemapped by the device's own tonemap; the tuples before it are unchanged."""
     from .device import Adaptive, DeviceScene          # torch: only the resident-scene path needs it
     w, h = dimensions
     if int(first) < 1 or int(step) < 1:
@@ -90,6 +103,7 @@ def render_adaptive(bih, cam, samples, dimensions, tol, eps=1.0, first=8, step=8
     if depth is not None:
         N.depth_value(depth)
     sky = N.sky_pair(sky)
+    dn = None if denoise is None or denoise is False else denoise_options(denoise)      # refused before anything is uploaded
     ds = DeviceScene(bih, device)
     try:
         if lights is not None:
@@ -99,9 +113,15 @@ def render_adaptive(bih, cam, samples, dimensions, tol, eps=1.0, first=8, step=8
         if sky is not None:
             ds.set_sky(sky[0], sky[1])
         a = Adaptive(ds, cam, samples, w, h, tol, eps=eps, first=first, step=step, cast=cast, rule=rule)
+        avg = None
         while not a.finished:
-            _, rgb = a.step()
+            avg, rgb = a.step()
             yield a.done, a.live, a.samples_spent, rgb.cpu().numpy(), a.counts.cpu().numpy()
+        if dn is not None and avg is not None:       # (a frame without pixels never steps: nothing to filter)
+            from .denoise import denoise_frame, denoise_variance
+            out, _ = denoise_frame(ds, cam, w, h, avg, var=denoise_variance(a.sums, a.sums2, a.counts), **dn)
+            img = N.debug_eval("tonemap", out.cpu().numpy().reshape(-1, 3), device=ds.device).reshape(tuple(out.shape))
+            yield a.done, a.live, a.samples_spent, img, a.counts.cpu().numpy()
     finally:
         ds.close()
 
