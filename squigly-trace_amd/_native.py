@@ -64,22 +64,27 @@ class SquiglyError(RuntimeError):
 _lib = None
 
 
-def lib():
-    global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
+def load(path):
+    """The shared library at `path` (this package's two load through here); ImportError when it was not built."""
+    if not os.path.exists(path):
         raise ImportError(
-            f"{LIB_PATH} is missing: build it with `python squigly-trace_amd/build.py` "
+            f"{path} is missing: build it with `python squigly-trace_amd/build.py` "
             "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
     # PyTorch (the plumbing for device buffers and streams) bundles its own HIP runtime.  It has to be the
-    # first HIP runtime loaded into the process: if libsquigly_hip.so pulls in the system one first, torch's
+    # first HIP runtime loaded into the process: if a library of ours pulls in the system one first, torch's
     # later initialisation reports "No HIP GPUs are available".
     try:
         import torch  # noqa: F401
     except ImportError:
         pass
-    L = C.CDLL(LIB_PATH)
+    return C.CDLL(path)
+
+
+def lib():
+    global _lib
+    if _lib is not None:
+        return _lib
+    L = load(LIB_PATH)
     vp, i32, sz = C.c_void_p, C.c_int32, C.c_size_t
     L.sq_last_error.restype = C.c_char_p
     L.sq_device_count.restype = i32
@@ -270,9 +275,21 @@ def build_id():
     return lib().sq_build_id().decode()
 
 
+def checked(rc, last_error, count=False):
+    """rc, the return value of a C-ABI call, or SquiglyError with what the library's `last_error` function says: non-zero is an
+    error; of a call that returns a count (count=True), a negative value is."""
+    if (rc < 0) if count else (rc != 0):
+        raise SquiglyError(last_error().decode(errors="replace"))
+    return rc
+
+
 def check(rc):
-    if rc != 0:
-        raise SquiglyError(lib().sq_last_error().decode(errors="replace"))
+    checked(rc, lib().sq_last_error)
+
+
+def count(n):
+    """The count a getter of libsquigly_hip.so returned; SquiglyError for a negative one."""
+    return checked(n, lib().sq_last_error, count=True)
 
 
 EXPORTED_SYMBOLS = [

@@ -9,6 +9,7 @@ import ctypes as C
 import os
 
 from . import _native as N
+from . import _plumbing as P
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libsquigly_denoise.so")
@@ -39,14 +40,7 @@ def lib():
     global _lib
     if _lib is not None:
         return _lib
-    if not os.path.exists(LIB_PATH):
-        raise ImportError(f"{LIB_PATH} is missing: build it with `python squigly-trace_amd/build.py` "
-                          "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
-    try:                     # as in _native.lib: torch's HIP runtime has to be the first one in the process
-        import torch  # noqa: F401
-    except ImportError:
-        pass
-    L = C.CDLL(LIB_PATH)
+    L = N.load(LIB_PATH)
     vp, i32 = C.c_void_p, C.c_int32
     L.sq_denoise_last_error.restype = C.c_char_p
     L.sq_denoise_build_id.restype = C.c_char_p
@@ -63,8 +57,7 @@ def lib():
 
 
 def check(rc):
-    if rc != 0:
-        raise N.SquiglyError(lib().sq_denoise_last_error().decode(errors="replace"))
+    N.checked(rc, lib().sq_denoise_last_error)
 
 
 def build_id():
@@ -92,15 +85,6 @@ def make_params(sigma_p=None, **kw):
     return Params(int(p["passes"]), float(p["sigma_l"]), float(p["eps_l"]), float(sigma_p), int(p["normal_squarings"]), int(form))
 
 
-def _image(name, t, shape, dtype, dev):
-    import torch
-    if (not isinstance(t, torch.Tensor) or tuple(t.shape) != tuple(shape) or t.dtype != dtype or not t.is_contiguous()
-            or t.device != dev):
-        got = f"{t.dtype} {tuple(t.shape)} on {t.device}" if isinstance(t, torch.Tensor) else type(t).__name__
-        raise N.SquiglyError(f"{name} must be a contiguous {dtype} tensor of shape {tuple(shape)} on {dev}, got {got}")
-    return t
-
-
 def denoise(color, tri, normal, point, var=None, out=None, stream=None, **params):
     """sq_denoise_device on device tensors; returns (out, out_var), out_var None without var.  Enqueued on `stream`.
 
@@ -113,35 +97,34 @@ def denoise(color, tri, normal, point, var=None, out=None, stream=None, **params
         raise N.SquiglyError("color must be a float32 CUDA tensor of shape [rows, cols, 3]")
     dev = color.device
     rows, cols = int(color.shape[0]), int(color.shape[1])
-    P = make_params(**params)
+    par = make_params(**params)
     f32 = torch.float32
-    _image("color", color, (rows, cols, 3), f32, dev)
-    _image("tri", tri, (rows, cols), torch.int32, dev)
-    _image("normal", normal, (rows, cols, 3), f32, dev)
-    _image("point", point, (rows, cols, 3), f32, dev)
+    P.tensor("color", color, (rows, cols, 3), f32, dev)
+    P.tensor("tri", tri, (rows, cols), torch.int32, dev)
+    P.tensor("normal", normal, (rows, cols, 3), f32, dev)
+    P.tensor("point", point, (rows, cols, 3), f32, dev)
     if var is not None:
-        _image("var", var, (rows, cols), f32, dev)
+        P.tensor("var", var, (rows, cols), f32, dev)
     out_c, out_v = out if isinstance(out, (tuple, list)) else (out, None)
     if out_c is not None:
-        _image("out", out_c, (rows, cols, 3), f32, dev)
+        P.tensor("out", out_c, (rows, cols, 3), f32, dev)
     if out_v is not None:
         if var is None:
             raise N.SquiglyError("an output variance needs var")
-        _image("out variance", out_v, (rows, cols), f32, dev)
+        P.tensor("out variance", out_v, (rows, cols), f32, dev)
     need = workspace_bytes(rows, cols)
     if rows >= 1 and cols >= 1 and need == 0:
         raise N.SquiglyError(f"{rows} x {cols} pixels exceed 2^31 - 1 pixels in one call")
-    st = stream if stream is not None else torch.cuda.current_stream(dev)
+    _, st = P.call_stream(dev, stream)
     with torch.cuda.stream(st):      # outputs and workspace are allocated (and the workspace freed) in the order of the call's stream
         if out_c is None:
             out_c = torch.empty((rows, cols, 3), dtype=f32, device=dev)
         if out_v is None and var is not None:
             out_v = torch.empty((rows, cols), dtype=f32, device=dev)
         work = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
-        check(lib().sq_denoise_device(dev.index or 0, rows, cols, color.data_ptr(), var.data_ptr() if var is not None else None,
-                                      tri.data_ptr(), normal.data_ptr(), point.data_ptr(), C.byref(P), out_c.data_ptr(),
-                                      out_v.data_ptr() if out_v is not None else None, work.data_ptr(), need,
-                                      C.c_void_p(st.cuda_stream)))
+        check(lib().sq_denoise_device(dev.index or 0, rows, cols, color.data_ptr(), P.ptr(var), tri.data_ptr(), normal.data_ptr(),
+                                      point.data_ptr(), C.byref(par), out_c.data_ptr(), P.ptr(out_v), work.data_ptr(), need,
+                                      P.stream_ptr(st)))
     return out_c, out_v
 
 
@@ -152,14 +135,14 @@ def denoise_variance(sums, sums2, counts, stream=None):
     if not isinstance(counts, torch.Tensor) or not counts.is_cuda:
         raise N.SquiglyError("counts must be an int32 CUDA tensor")
     dev, shape = counts.device, tuple(counts.shape)
-    _image("counts", counts, shape, torch.int32, dev)
-    _image("sums", sums, shape + (3,), torch.float32, dev)
-    _image("sums2", sums2, shape + (3,), torch.float32, dev)
-    st = stream if stream is not None else torch.cuda.current_stream(dev)
+    P.tensor("counts", counts, shape, torch.int32, dev)
+    P.tensor("sums", sums, shape + (3,), torch.float32, dev)
+    P.tensor("sums2", sums2, shape + (3,), torch.float32, dev)
+    _, st = P.call_stream(dev, stream)
     with torch.cuda.stream(st):
         var = torch.empty(shape, dtype=torch.float32, device=dev)
         check(lib().sq_denoise_variance_device(dev.index or 0, counts.numel(), sums.data_ptr(), sums2.data_ptr(), counts.data_ptr(),
-                                               var.data_ptr(), C.c_void_p(st.cuda_stream)))
+                                               var.data_ptr(), P.stream_ptr(st)))
     return var
 
 
@@ -177,8 +160,7 @@ def scene_guides(ds, cam, w, h, shard=(None, 0, 1), stream=None):
     is the unit normal of Geometry.hs's `normal`, cross (b - a) (c - a) / its norm.  A convenience: not pinned to the bit."""
     import numpy as np
     import torch
-    dev = torch.device("cuda", ds.device)
-    st = stream if stream is not None else torch.cuda.current_stream(dev)
+    dev, st = P.call_stream(ds.device, stream)
     with torch.cuda.stream(st):
         tables = getattr(ds, "_guide_tables", None)
         if tables is None:        # per triangle: unit normal, surf, emissive *^ emit; one more row of zeros for "no hit"
@@ -206,8 +188,7 @@ def denoise_frame(ds, cam, w, h, avg, var=None, shard=(None, 0, 1), demodulate=T
     of the surface's own colour -- and multiplies back afterwards; the variance goes with it, divided by l(surf)^2 on the way in and
     multiplied on the way out (exact for a grey surface, an estimate otherwise).  guides: what ds.guides(cam, w, h, shard) returned, to reuse it over frames of one camera."""
     import torch
-    dev = torch.device("cuda", ds.device)
-    st = stream if stream is not None else torch.cuda.current_stream(dev)
+    _, st = P.call_stream(ds.device, stream)
     if "sigma_p" not in params or params["sigma_p"] is None:
         params["sigma_p"] = default_sigma_p(ds.bih.bounds)
     make_params(**params)                    # refused before any device work

@@ -9,6 +9,8 @@ import ctypes as C
 import torch
 
 from . import _native as N
+from . import _plumbing as P
+from .scene import Owner
 
 Hits = collections.namedtuple("Hits", ["tri", "dist", "point"])
 Hits.__doc__ = """Results of DeviceScene.intersect: Maybe Intersection (src/Geometry.hs:71-75) per ray; tri = -1 is Nothing."""
@@ -67,9 +69,8 @@ def frame_seeds(samples, w, h, shard=(None, 0, 1), device=None):
     samples, w, h = int(samples), int(w), int(h)
     if samples < 1 or w < 1 or h < 1:
         raise N.SquiglyError(f"samples, width and height must be positive (got {samples}, {w}, {h})")
-    rb, si, ns = shard
-    rb, si, ns = int(w if rb is None else rb), int(si), int(ns)
-    if rb <= 0 or ns <= 0 or si < 0 or si >= ns:
+    rb, si, ns = P.shard_ints(w, shard)
+    if rb <= 0 or ns <= 0 or si < 0 or si >= ns:     # sq_shard_rows' own refusal, restated: no library's device side is needed here
         raise N.SquiglyError(f"bad shard {shard}")
     blocks = torch.arange(si, (w + rb - 1) // rb, ns, dtype=torch.int64, device=device)       # this shard's row blocks
     y = (blocks[:, None] * rb + torch.arange(rb, dtype=torch.int64, device=device)[None, :]).reshape(-1)
@@ -85,8 +86,13 @@ def _lead_count(lead):
     return n
 
 
-class DeviceScene:
+# The state a frame carries from call to call, per pixel [rows, h]: name -> (trailing shape, dtype)
+_STATE = {"sums": ((3,), torch.float32), "mask": ((), torch.uint8), "sums2": ((3,), torch.float32), "counts": ((), torch.int32)}
+
+
+class DeviceScene(Owner):
     """A BIH uploaded to one GPU (sq_scene_upload)."""
+    _free = "sq_scene_free"
 
     def __init__(self, bih, device=0):
         self.bih = bih                      # keeps the host arrays alive
@@ -108,18 +114,15 @@ class DeviceScene:
         numbers; None restores the reference's light (REFERENCE_LIGHT).  The update is enqueued on `stream` like a frame, and
         the argument may be reused as soon as the call returns."""
         table = None if lights is None else N.lights_array(lights)      # shape and count errors come before any device work
-        dev = torch.device("cuda", self.device)
-        st = stream if stream is not None else torch.cuda.current_stream(dev)
+        _, st = P.call_stream(self.device, stream)
         N.check(N.lib().sq_scene_set_lights(self._h, None if table is None else table.ctypes.data, 0 if table is None else len(table),
-                                            C.c_void_p(st.cuda_stream)))
+                                            P.stream_ptr(st)))
 
     @property
     def lights(self):
         """The scene's lights as a float32 numpy array [n, 6] (pos, power), from the library's copy (sq_scene_get_lights)."""
         import numpy as np
-        n = N.lib().sq_scene_get_lights(self._h, None, 0)
-        if n < 0:
-            raise N.SquiglyError(N.lib().sq_last_error().decode(errors="replace"))
+        n = N.count(N.lib().sq_scene_get_lights(self._h, None, 0))
         out = np.empty((n, 6), np.float32)
         N.lib().sq_scene_get_lights(self._h, out.ctypes.data, n)
         return out
@@ -134,10 +137,7 @@ class DeviceScene:
     @property
     def depth(self):
         """The scene's path depth (sq_scene_get_depth)."""
-        d = N.lib().sq_scene_get_depth(self._h)
-        if d < 0:
-            raise N.SquiglyError(N.lib().sq_last_error().decode(errors="replace"))
-        return int(d)
+        return int(N.count(N.lib().sq_scene_get_depth(self._h)))
 
     def set_sky(self, up, down=None):
         """The sky of the scene's path-traced frames and raytrace queries (sq_scene_set_sky): the radiance of a ray that leaves
@@ -157,9 +157,7 @@ class DeviceScene:
         """The scene's sky (sq_scene_get_sky): None, or (up, down), two tuples of three floats."""
         import numpy as np
         out = np.zeros((2, 3), np.float32)
-        r = N.lib().sq_scene_get_sky(self._h, out.ctypes.data)
-        if r < 0:
-            raise N.SquiglyError(N.lib().sq_last_error().decode(errors="replace"))
+        r = N.count(N.lib().sq_scene_get_sky(self._h, out.ctypes.data))
         return None if r == 0 else (tuple(float(v) for v in out[0]), tuple(float(v) for v in out[1]))
 
     def rng_table(self, first=0, count=0):
@@ -167,25 +165,17 @@ class DeviceScene:
         numpy array [count, 3])."""
         import numpy as np
         out = np.empty((int(count), 3), np.uint32)
-        cover = N.lib().sq_scene_rng_table(self._h, int(first), int(count), out.ctypes.data)
-        if cover < 0:
-            raise N.SquiglyError(N.lib().sq_last_error().decode(errors="replace"))
-        return int(cover), out
+        return int(N.count(N.lib().sq_scene_rng_table(self._h, int(first), int(count), out.ctypes.data))), out
 
     def _outputs(self, w, h, shard, want_avg, want_rgb, stream, out_avg, out_rgb, views=None, cast=False, frame=True):
         """(sq_shard, rows, out_avg, out_rgb, stream) of a render_rows* call: the shard's row count, the output tensors
         (allocated unless given or not wanted) and the stream (default: the device's current one).  views: the tensors get a
         leading dimension of that many views (render_views)."""
-        rb, si, ns = shard
-        sh = N.Shard(int(w if rb is None else rb), int(si), int(ns))
-        rows = N.lib().sq_shard_rows(w, sh)
-        if rows < 0:
-            raise N.SquiglyError(f"bad shard {shard}")
+        sh, rows = P.shard_rows(w, shard)
         if frame:                              # frame: a render call (camera_rays has no limit but memory)
             _check_frame_size(self, rows, h, cast, 1 if views is None else views)
-        dev = torch.device("cuda", self.device)
         shape = (rows, h, 3) if views is None else (views, rows, h, 3)
-        st = stream if stream is not None else torch.cuda.current_stream(dev)
+        dev, st = P.call_stream(self.device, stream)
         with torch.cuda.stream(st):      # allocated in the order of the call's stream: a block another stream still has work on is not taken
             if want_avg and out_avg is None:
                 out_avg = torch.empty(shape, dtype=torch.float32, device=dev)
@@ -193,18 +183,31 @@ class DeviceScene:
                 out_rgb = torch.empty(shape, dtype=torch.uint8, device=dev)
         return sh, rows, out_avg, out_rgb, st
 
+    def _frame_tensor(self, name, t, shape, dtype, says=None):
+        """t if it is a contiguous `dtype` tensor of `shape` on this device; SquiglyError otherwise (P.tensor)."""
+        return P.tensor(name, t, shape, dtype, torch.device("cuda", self.device), says)
+
+    def _rows_call(self, what, w, h, cast, shard, want_avg, want_rgb, stream, out_avg, out_rgb, says=None, **state):
+        """What the render_rows* methods do before their C call: _outputs, then, for the two that carry a fold, the refusal of a
+        missing sums in the name of the method `what`, and every state tensor given (sums, mask, sums2, counts, in that order)
+        held to the shard's shape.  Returns (sq_shard, out_avg, out_rgb, stream)."""
+        sh, rows, out_avg, out_rgb, st = self._outputs(w, h, shard, want_avg, want_rgb, stream, out_avg, out_rgb, cast=cast)
+        if "sums" in state and state["sums"] is None:
+            raise N.SquiglyError(f"{what} needs a sums tensor")
+        for name, t in state.items():
+            if t is not None:
+                self._frame_tensor(name, t, (rows, h) + _STATE[name][0], _STATE[name][1], says)
+        return sh, out_avg, out_rgb, st
+
     def render_rows(self, cam, samples, w, h, cast=False, shard=(None, 0, 1), want_avg=True, want_rgb=True,
                     stream=None, out_avg=None, out_rgb=None):
         """Enqueue the render of this shard's rows; returns (avg, rgb) CUDA tensors [rows, h, 3].
 
         shard = (row_block, shard_index, n_shards); row_block None = all rows in one block.
         """
-        sh, _, out_avg, out_rgb, st = self._outputs(w, h, shard, want_avg, want_rgb, stream, out_avg, out_rgb, cast=cast)
+        sh, out_avg, out_rgb, st = self._rows_call("render_rows", w, h, cast, shard, want_avg, want_rgb, stream, out_avg, out_rgb)
         N.check(N.lib().sq_render_rows_device(
-            self._h, C.byref(cam), samples, w, h, int(bool(cast)), sh,
-            out_avg.data_ptr() if out_avg is not None else None,
-            out_rgb.data_ptr() if out_rgb is not None else None,
-            C.c_void_p(st.cuda_stream)))
+            self._h, C.byref(cam), samples, w, h, int(bool(cast)), sh, P.ptr(out_avg), P.ptr(out_rgb), P.stream_ptr(st)))
         return out_avg, out_rgb
 
     def render_rows_range(self, cam, samples, w, h, k_begin, k_end, sums, cast=False, shard=(None, 0, 1), want_avg=True,
@@ -215,27 +218,12 @@ class DeviceScene:
         sums: float32 CUDA tensor [rows, h, 3] on this device, the per-pixel fold over [0, k_begin) on entry (ignored when
         k_begin == 0) and over [0, k_end) once the stream gets there.
         """
-        sh, rows, out_avg, out_rgb, st = self._outputs(w, h, shard, want_avg, want_rgb, stream, out_avg, out_rgb, cast=cast)
-        if sums is None:
-            raise N.SquiglyError("render_rows_range needs a sums tensor")
-        if (tuple(sums.shape) != (rows, h, 3) or sums.dtype != torch.float32 or not sums.is_contiguous()
-                or sums.device != torch.device("cuda", self.device)):
-            raise N.SquiglyError(f"sums must be a contiguous float32 tensor of shape {(rows, h, 3)} on cuda:{self.device}, "
-                                 f"got {sums.dtype} {tuple(sums.shape)} on {sums.device}")
+        sh, out_avg, out_rgb, st = self._rows_call("render_rows_range", w, h, cast, shard, want_avg, want_rgb, stream, out_avg, out_rgb,
+                                                   says="float32", sums=sums)
         N.check(N.lib().sq_render_rows_device_range(
             self._h, C.byref(cam), samples, w, h, int(bool(cast)), sh, int(k_begin), int(k_end), sums.data_ptr(),
-            out_avg.data_ptr() if out_avg is not None else None,
-            out_rgb.data_ptr() if out_rgb is not None else None,
-            C.c_void_p(st.cuda_stream)))
+            P.ptr(out_avg), P.ptr(out_rgb), P.stream_ptr(st)))
         return out_avg, out_rgb
-
-    def _frame_tensor(self, name, t, shape, dtype):
-        """t if it is a contiguous `dtype` tensor of `shape` on this device; SquiglyError otherwise."""
-        if (tuple(t.shape) != tuple(shape) or t.dtype != dtype or not t.is_contiguous()
-                or t.device != torch.device("cuda", self.device)):
-            raise N.SquiglyError(f"{name} must be a contiguous {dtype} tensor of shape {tuple(shape)} on cuda:{self.device}, "
-                                 f"got {t.dtype} {tuple(t.shape)} on {t.device}")
-        return t
 
     def render_rows_masked(self, cam, samples, w, h, k_begin, k_end, sums, mask=None, sums2=None, counts=None, cast=False,
                            shard=(None, 0, 1), want_avg=True, want_rgb=True, stream=None, out_avg=None, out_rgb=None):
@@ -248,45 +236,32 @@ class DeviceScene:
         With mask, sums2 and counts all None this is render_rows_range.
         """
         given_avg, given_rgb = out_avg is not None, out_rgb is not None
-        sh, rows, out_avg, out_rgb, st = self._outputs(w, h, shard, want_avg, want_rgb, stream, out_avg, out_rgb, cast=cast)
-        if sums is None:
-            raise N.SquiglyError("render_rows_masked needs a sums tensor")
-        self._frame_tensor("sums", sums, (rows, h, 3), torch.float32)
-        if mask is not None:
-            self._frame_tensor("mask", mask, (rows, h), torch.uint8)
-        if sums2 is not None:
-            self._frame_tensor("sums2", sums2, (rows, h, 3), torch.float32)
-        if counts is not None:
-            self._frame_tensor("counts", counts, (rows, h), torch.int32)
+        sh, out_avg, out_rgb, st = self._rows_call("render_rows_masked", w, h, cast, shard, want_avg, want_rgb, stream, out_avg, out_rgb,
+                                                   sums=sums, mask=mask, sums2=sums2, counts=counts)
         if mask is not None or sums2 is not None or counts is not None:      # a masked call clears nothing: no stale memory in fresh outputs
             with torch.cuda.stream(st):
                 if out_avg is not None and not given_avg:
                     out_avg.zero_()
                 if out_rgb is not None and not given_rgb:
                     out_rgb.zero_()
-        ptr = lambda t: t.data_ptr() if t is not None else None               # noqa: E731
         N.check(N.lib().sq_render_rows_device_masked(
-            self._h, C.byref(cam), samples, w, h, int(bool(cast)), sh, int(k_begin), int(k_end), ptr(mask), sums.data_ptr(),
-            ptr(sums2), ptr(counts), ptr(out_avg), ptr(out_rgb), C.c_void_p(st.cuda_stream)))
+            self._h, C.byref(cam), samples, w, h, int(bool(cast)), sh, int(k_begin), int(k_end), P.ptr(mask), sums.data_ptr(),
+            P.ptr(sums2), P.ptr(counts), P.ptr(out_avg), P.ptr(out_rgb), P.stream_ptr(st)))
         return out_avg, out_rgb
 
     def adaptive_update(self, sums, sums2, counts, mask, tol, eps, stream=None):
         """The built-in stopping rule (sq_adaptive_update_device) on the pixels whose mask byte is set: a converged pixel's byte
         is cleared.  Returns the number of pixels still live (waits for the stream).  A heuristic: see include/squigly_hip.h."""
-        dev = torch.device("cuda", self.device)
-        st = stream if stream is not None else torch.cuda.current_stream(dev)
+        dev, st = P.call_stream(self.device, stream)
         shape = tuple(mask.shape)
-        self._frame_tensor("mask", mask, shape, torch.uint8)
-        self._frame_tensor("sums", sums, shape + (3,), torch.float32)
-        self._frame_tensor("sums2", sums2, shape + (3,), torch.float32)
-        self._frame_tensor("counts", counts, shape, torch.int32)
+        for name, t in (("mask", mask), ("sums", sums), ("sums2", sums2), ("counts", counts)):
+            self._frame_tensor(name, t, shape + _STATE[name][0], _STATE[name][1])
         if mask.numel() == 0:
             return 0
         with torch.cuda.stream(st):
             live = torch.empty(1, dtype=torch.int32, device=dev)
             N.check(N.lib().sq_adaptive_update_device(self._h, int(mask.numel()), sums.data_ptr(), sums2.data_ptr(), counts.data_ptr(),
-                                                      float(tol), float(eps), mask.data_ptr(), live.data_ptr(),
-                                                      C.c_void_p(st.cuda_stream)))
+                                                      float(tol), float(eps), mask.data_ptr(), live.data_ptr(), P.stream_ptr(st)))
             st.synchronize()
             return int(live.item())
 
@@ -304,17 +279,12 @@ class DeviceScene:
         n = len(cams)
         k_end = int(samples) if k_end is None else int(k_end)
         sh, rows, out_avg, out_rgb, st = self._outputs(w, h, shard, want_avg, want_rgb, stream, out_avg, out_rgb, views=n, cast=cast)
-        if sums is not None and (tuple(sums.shape) != (n, rows, h, 3) or sums.dtype != torch.float32 or not sums.is_contiguous()
-                                 or sums.device != torch.device("cuda", self.device)):
-            raise N.SquiglyError(f"sums must be a contiguous float32 tensor of shape {(n, rows, h, 3)} on cuda:{self.device}, "
-                                 f"got {sums.dtype} {tuple(sums.shape)} on {sums.device}")
+        if sums is not None:
+            self._frame_tensor("sums", sums, (n, rows, h, 3), torch.float32, says="float32")
         table = (N.Camera * n)(*cams)
         N.check(N.lib().sq_render_views_device(
-            self._h, table, n, samples, w, h, int(bool(cast)), sh, int(k_begin), k_end,
-            sums.data_ptr() if sums is not None else None,
-            out_avg.data_ptr() if out_avg is not None else None,
-            out_rgb.data_ptr() if out_rgb is not None else None,
-            C.c_void_p(st.cuda_stream)))
+            self._h, table, n, samples, w, h, int(bool(cast)), sh, int(k_begin), k_end, P.ptr(sums), P.ptr(out_avg), P.ptr(out_rgb),
+            P.stream_ptr(st)))
         return out_avg, out_rgb
 
     def intersect(self, origins, directions, want_dist=True, want_point=True, stream=None, out=None):
@@ -327,25 +297,20 @@ class DeviceScene:
         out: Hits whose tensors (contiguous, right shape and dtype, on this device; None = allocate) receive the results.
         """
         shape = _ray_shape(origins, directions)
-        dev = torch.device("cuda", self.device)
-        st = stream if stream is not None else torch.cuda.current_stream(dev)
+        dev, st = P.call_stream(self.device, stream)
         lead = shape[:-1]
         out = Hits(*(out if out is not None else (None, None, None)))
         for name, t, want, tshape, dtype in (("tri", out.tri, True, lead, torch.int32), ("dist", out.dist, want_dist, lead, torch.float32),
                                              ("point", out.point, want_point, shape, torch.float32)):
-            if t is not None and want and (tuple(t.shape) != tuple(tshape) or t.dtype != dtype or not t.is_contiguous() or t.device != dev):
-                raise N.SquiglyError(f"out.{name} must be a contiguous {dtype} tensor of shape {tuple(tshape)} on {dev}, "
-                                     f"got {t.dtype} {tuple(t.shape)} on {t.device}")
+            if t is not None and want:
+                P.tensor(f"out.{name}", t, tshape, dtype, dev)
         with torch.cuda.stream(st):      # temporaries are allocated and freed in the order of the call's stream
-            o = torch.as_tensor(origins, device=dev).to(torch.float32).contiguous()
-            d = torch.as_tensor(directions, device=dev).to(torch.float32).contiguous()
+            o, d = P.rays_in(dev, origins, directions)
             tri = out.tri if out.tri is not None else torch.empty(lead, dtype=torch.int32, device=dev)
             dist = (out.dist if out.dist is not None else torch.empty(lead, dtype=torch.float32, device=dev)) if want_dist else None
             point = (out.point if out.point is not None else torch.empty(shape, dtype=torch.float32, device=dev)) if want_point else None
-            N.check(N.lib().sq_intersect_rays_device(
-                self._h, o.data_ptr(), d.data_ptr(), int(o.numel() // 3), tri.data_ptr(),
-                dist.data_ptr() if dist is not None else None, point.data_ptr() if point is not None else None,
-                C.c_void_p(st.cuda_stream)))
+            N.check(N.lib().sq_intersect_rays_device(self._h, o.data_ptr(), d.data_ptr(), int(o.numel() // 3), tri.data_ptr(), P.ptr(dist),
+                                                     P.ptr(point), P.stream_ptr(st)))
         return Hits(tri, dist, point)
 
     def camera_rays(self, cam, w, h, shard=(None, 0, 1), stream=None):
@@ -357,8 +322,7 @@ class DeviceScene:
         with torch.cuda.stream(st):      # as in _outputs: the rays are allocated in the order of the call's stream
             o = torch.empty((rows, h, 3), dtype=torch.float32, device=dev)
             d = torch.empty((rows, h, 3), dtype=torch.float32, device=dev)
-        N.check(N.lib().sq_camera_rays_device(self._h, C.byref(cam), int(w), int(h), sh, o.data_ptr(), d.data_ptr(),
-                                              C.c_void_p(st.cuda_stream)))
+        N.check(N.lib().sq_camera_rays_device(self._h, C.byref(cam), int(w), int(h), sh, o.data_ptr(), d.data_ptr(), P.stream_ptr(st)))
         return o, d
 
     def guides(self, cam, w, h, shard=(None, 0, 1), stream=None):
@@ -383,7 +347,6 @@ class DeviceScene:
         shape = _ray_shape(origins, directions)
         lead = shape[:-1]
         n = _lead_count(lead)
-        dev = torch.device("cuda", self.device)
         samples = int(samples)
         if samples < 1:
             raise N.SquiglyError(f"samples must be positive, got {samples}")
@@ -404,10 +367,9 @@ class DeviceScene:
             if not isinstance(sums, torch.Tensor):
                 raise N.SquiglyError("sums must be a CUDA tensor: it is updated in place")
             self._frame_tensor("sums", sums, shape, torch.float32)
-        st = stream if stream is not None else torch.cuda.current_stream(dev)
+        dev, st = P.call_stream(self.device, stream)
         with torch.cuda.stream(st):      # temporaries are allocated and freed in the order of the call's stream
-            o = torch.as_tensor(origins, device=dev).to(torch.float32).contiguous()
-            d = torch.as_tensor(directions, device=dev).to(torch.float32).contiguous()
+            o, d = P.rays_in(dev, origins, directions)
             if seeds is None:
                 sd = (samples * torch.arange(n, dtype=torch.int64, device=dev)).reshape(lead)
             else:
@@ -416,24 +378,20 @@ class DeviceScene:
                 sums = torch.empty(shape, dtype=torch.float32, device=dev)
             avg = torch.empty(shape, dtype=torch.float32, device=dev) if want_avg else None
             rgb = torch.empty(shape, dtype=torch.uint8, device=dev) if want_rgb else None
-            N.check(N.lib().sq_raytrace_rays_device(
-                self._h, o.data_ptr(), d.data_ptr(), sd.data_ptr(), n, k_begin, k_end, sums.data_ptr(),
-                avg.data_ptr() if avg is not None else None, rgb.data_ptr() if rgb is not None else None,
-                C.c_void_p(st.cuda_stream)))
+            N.check(N.lib().sq_raytrace_rays_device(self._h, o.data_ptr(), d.data_ptr(), sd.data_ptr(), n, k_begin, k_end, sums.data_ptr(),
+                                                    P.ptr(avg), P.ptr(rgb), P.stream_ptr(st)))
         return Radiance(sums, avg, rgb)
 
     def raycast(self, origins, directions, stream=None):
         """Lib.raycast of each ray (sq_raycast_rays_device) under the scene's lights (set_lights; the reference's light at
         (0, 3, -1) unless set): a float32 CUDA tensor [..., 3], zeros for a miss or a point every light is shadowed at.  origins, directions as in `intersect`."""
         shape = _ray_shape(origins, directions)
-        dev = torch.device("cuda", self.device)
-        st = stream if stream is not None else torch.cuda.current_stream(dev)
+        dev, st = P.call_stream(self.device, stream)
         with torch.cuda.stream(st):
-            o = torch.as_tensor(origins, device=dev).to(torch.float32).contiguous()
-            d = torch.as_tensor(directions, device=dev).to(torch.float32).contiguous()
+            o, d = P.rays_in(dev, origins, directions)
             rad = torch.empty(shape, dtype=torch.float32, device=dev)
             N.check(N.lib().sq_raycast_rays_device(self._h, o.data_ptr(), d.data_ptr(), _lead_count(shape[:-1]), rad.data_ptr(),
-                                                   C.c_void_p(st.cuda_stream)))
+                                                   P.stream_ptr(st)))
         return rad
 
     def enable_timing(self, on=True):
@@ -466,30 +424,7 @@ class DeviceScene:
     def reset_timing(self):
         N.lib().sq_kernel_timing_reset(self._h)
 
-    def close(self):
-        if getattr(self, "_h", None) and N is not None and N._lib is not None:
-            N._lib.sq_scene_free(self._h)
-        self._h = None
-
-    __del__ = close
-
-
-def _checkpoint_depth(dscene, depth):
-    """The path depth a Progressive / Adaptive frame runs under: the scene's.  depth: what a checkpoint carried (None = a fresh
-    frame, or a checkpoint from before depths existed, which is the scene's own); SquiglyError when the scene has another."""
-    have = dscene.depth
-    if depth is not None and N.depth_value(depth) != have:
-        raise N.SquiglyError(f"the checkpoint was rendered under depth {int(depth)}, the scene has depth {have}: "
-                             f"set_depth({int(depth)}) first")
-    return have
-
-
-def _same_depth(frame):
-    if frame.cast:
-        return
-    have = frame.dscene.depth
-    if have != frame.depth:
-        raise N.SquiglyError(f"the frame was begun under depth {frame.depth}, the scene now has depth {have}")
+    close = Owner._release
 
 
 SCENE_SKY = object()     # sky= of Progressive / Adaptive: a fresh frame, which runs under the scene's sky whatever it is
@@ -501,24 +436,54 @@ def _sky_bits(sky):
     return None if pair is None else pair.tobytes()
 
 
-def _checkpoint_sky(dscene, sky):
-    """The sky a Progressive / Adaptive frame runs under: the scene's.  sky: SCENE_SKY for a fresh frame, else what a checkpoint
-    carried (None = no sky); SquiglyError when the scene has another."""
-    have = dscene.sky
-    if sky is not SCENE_SKY and _sky_bits(sky) != _sky_bits(have):
-        raise N.SquiglyError(f"the checkpoint was rendered under the sky {sky!r}, the scene has {have!r}: set_sky first")
-    return have
+# What a path-traced frame runs under besides its own arguments, in the order it is checked: the attribute (of the scene and of the
+# frame), what the constructor takes for "a fresh frame", what two values are the same by, how a refusal words the frame's value and
+# the scene's, and the call that makes the scene match a checkpoint.
+_UNDER = (("depth", None, N.depth_value, lambda d: f"depth {int(d)}", lambda d: f"depth {d}", lambda d: f"set_depth({int(d)})"),
+          ("sky", SCENE_SKY, _sky_bits, lambda s: f"the sky {s!r}", repr, lambda s: "set_sky"))
 
 
-def _same_sky(frame):
-    if frame.cast:
-        return
-    have = frame.dscene.sky
-    if _sky_bits(have) != _sky_bits(frame.sky):
-        raise N.SquiglyError(f"the frame was begun under the sky {frame.sky!r}, the scene now has {have!r}")
+class _Frame:
+    """What Progressive and Adaptive share: the shard's rows, the size check, the depth and the sky the frame runs under, and
+    the adoption of a checkpoint's tensors."""
+
+    def _begin(self, dscene, cam, samples, w, h, cast, shard, **under):
+        """Sets the frame's fields and returns its row count.  under: depth and sky as the constructor got them -- what a checkpoint
+        carried (for the depth, None is also a checkpoint from before depths existed, which is the scene's own).  The frame runs
+        under the scene's; SquiglyError when a checkpoint was rendered under another.  A cast frame has no paths: it ignores the
+        depth and the sky, and its fields are None."""
+        _, rows = P.shard_rows(w, shard)
+        _check_frame_size(dscene, rows, h, cast)
+        for name, fresh, key, mine, theirs, fix in _UNDER:
+            have = None if cast else getattr(dscene, name)
+            if not cast and under[name] is not fresh and key(under[name]) != key(have):
+                raise N.SquiglyError(f"the checkpoint was rendered under {mine(under[name])}, the scene has {theirs(have)}: "
+                                     f"{fix(under[name])} first")
+            setattr(self, name, have)
+        self.dscene, self.cam, self.samples, self.w, self.h = dscene, cam, samples, int(w), int(h)
+        self.cast, self.shard = bool(cast), shard
+        self._dev = torch.device("cuda", dscene.device)
+        return rows
+
+    def _unchanged(self):
+        """SquiglyError when the scene's depth or sky is no longer what the frame was begun under."""
+        for name, _, key, mine, theirs, _ in () if self.cast else _UNDER:
+            was, have = getattr(self, name), getattr(self.dscene, name)
+            if key(have) != key(was):
+                raise N.SquiglyError(f"the frame was begun under {mine(was)}, the scene now has {theirs(have)}")
+
+    def _adopt(self, name, t, shape, dtype, fill=None):
+        """A checkpoint's tensor: a matching CUDA tensor as it is; anything else (a host copy) is copied to the device.  None: a
+        new tensor, filled with `fill` unless that is None."""
+        if t is None:
+            return torch.empty(shape, dtype=dtype, device=self._dev) if fill is None else torch.full(shape, fill, dtype=dtype, device=self._dev)
+        t = torch.as_tensor(t, dtype=dtype, device=self._dev).contiguous()
+        if tuple(t.shape) != shape:
+            raise ValueError(f"{name} must have shape {shape}, got {tuple(t.shape)}")
+        return t
 
 
-class Progressive:
+class Progressive(_Frame):
     """A frame rendered a few samples at a time (DeviceScene.render_rows_range), bit-exact to one render_rows call.
 
     Owns -- or adopts, to resume a checkpoint -- the [rows, h, 3] float32 fold `sums` and the count `done` of samples folded
@@ -537,25 +502,10 @@ class Progressive:
             raise ValueError(f"samples must be positive, got {samples}")
         if not 0 <= done <= samples:
             raise ValueError(f"done must be in [0, {samples}], got {done}")
-        rb, si, ns = shard
-        rows = N.lib().sq_shard_rows(w, N.Shard(int(w if rb is None else rb), int(si), int(ns)))
-        if rows < 0:
-            raise N.SquiglyError(f"bad shard {shard}")
-        _check_frame_size(dscene, rows, h, cast)
-        self.depth = None if cast else _checkpoint_depth(dscene, depth)      # a cast frame has no paths: it ignores the depth
-        self.sky = None if cast else _checkpoint_sky(dscene, sky)            # ... and the sky
-        dev = torch.device("cuda", dscene.device)
-        if sums is None:
-            if done:
-                raise ValueError("resuming (done > 0) needs the sums of the first `done` samples")
-            sums = torch.empty((rows, h, 3), dtype=torch.float32, device=dev)
-        else:   # adopts a matching CUDA tensor as it is; anything else (a host copy) is copied to the device
-            sums = torch.as_tensor(sums, dtype=torch.float32, device=dev).contiguous()
-            if tuple(sums.shape) != (rows, h, 3):
-                raise ValueError(f"sums must have shape {(rows, h, 3)}, got {tuple(sums.shape)}")
-        self.dscene, self.cam, self.samples, self.w, self.h = dscene, cam, samples, int(w), int(h)
-        self.cast, self.shard = bool(cast), shard
-        self._sums, self._done = sums, done
+        rows = self._begin(dscene, cam, samples, w, h, cast, shard, depth=depth, sky=sky)
+        if sums is None and done:
+            raise ValueError("resuming (done > 0) needs the sums of the first `done` samples")
+        self._sums, self._done = self._adopt("sums", sums, (rows, h, 3), torch.float32), done
 
     @property
     def sums(self):
@@ -577,8 +527,7 @@ class Progressive:
             raise RuntimeError(f"the frame is finished: all {self.samples} samples are rendered")
         if int(n) < 1:
             raise ValueError(f"a step renders at least one sample, got {n}")
-        _same_depth(self)
-        _same_sky(self)
+        self._unchanged()
         k_end = min(self._done + int(n), self.samples)
         avg, rgb = self.dscene.render_rows_range(self.cam, self.samples, self.w, self.h, self._done, k_end, self._sums,
                                                  cast=self.cast, shard=self.shard, stream=stream)
@@ -604,7 +553,7 @@ def rule_reference(sums, sums2, counts, mask, tol, eps):
     return ((np.asarray(mask) != 0) & ~converged).astype(np.uint8)
 
 
-class Adaptive:
+class Adaptive(_Frame):
     """A frame whose pixels stop receiving samples once a stopping rule calls them done (DeviceScene.render_rows_masked).
 
     Owns -- or adopts, to resume a checkpoint -- the folds `sums` and `sums2` [rows, h, 3], the per-pixel sample `counts` and
@@ -634,32 +583,13 @@ class Adaptive:
             raise ValueError("rule must be callable: (sums, sums2, counts, mask) -> mask")
         if done and (sums is None or sums2 is None or counts is None or mask is None):
             raise ValueError("resuming (done > 0) needs sums, sums2, counts and mask as the checkpoint left them")
-        rb, si, ns = shard
-        rows = N.lib().sq_shard_rows(w, N.Shard(int(w if rb is None else rb), int(si), int(ns)))
-        if rows < 0:
-            raise N.SquiglyError(f"bad shard {shard}")
-        _check_frame_size(dscene, rows, h, cast)
-        self.depth = None if cast else _checkpoint_depth(dscene, depth)      # a cast frame has no paths: it ignores the depth
-        self.sky = None if cast else _checkpoint_sky(dscene, sky)            # ... and the sky
-        dev = torch.device("cuda", dscene.device)
-
-        def adopt(name, t, shape, dtype, fill):   # a matching CUDA tensor as it is; a host copy is copied to the device
-            if t is None:
-                return torch.full(shape, fill, dtype=dtype, device=dev)
-            t = torch.as_tensor(t, dtype=dtype, device=dev).contiguous()
-            if tuple(t.shape) != shape:
-                raise ValueError(f"{name} must have shape {shape}, got {tuple(t.shape)}")
-            return t
-        self._sums = adopt("sums", sums, (rows, h, 3), torch.float32, 0)
-        self._sums2 = adopt("sums2", sums2, (rows, h, 3), torch.float32, 0)
-        self._counts = adopt("counts", counts, (rows, h), torch.int32, 0)
-        self._mask = adopt("mask", mask, (rows, h), torch.uint8, 1)
-        self.dscene, self.cam, self.samples, self.w, self.h = dscene, cam, samples, int(w), int(h)
-        self.tol, self.eps, self.first, self.step_size = tol, eps, first, step
-        self.cast, self.shard, self.rule = bool(cast), shard, rule
+        rows = self._begin(dscene, cam, samples, w, h, cast, shard, depth=depth, sky=sky)
+        for name, t, fill in (("sums", sums, 0), ("sums2", sums2, 0), ("counts", counts, 0), ("mask", mask, 1)):
+            setattr(self, "_" + name, self._adopt(name, t, (rows, h) + _STATE[name][0], _STATE[name][1], fill))
+        self.tol, self.eps, self.first, self.step_size, self.rule = tol, eps, first, step, rule
         self._done = done
-        self._avg = torch.zeros((rows, h, 3), dtype=torch.float32, device=dev)
-        self._rgb = torch.zeros((rows, h, 3), dtype=torch.uint8, device=dev)
+        self._avg = torch.zeros((rows, h, 3), dtype=torch.float32, device=self._dev)
+        self._rgb = torch.zeros((rows, h, 3), dtype=torch.uint8, device=self._dev)
         if done:
             self._restore_picture()
         self._live = self._count_live()
@@ -705,8 +635,7 @@ class Adaptive:
         if self.finished:
             raise RuntimeError("the frame is finished: no pixel is live" if self._live == 0
                                else f"the frame is finished: all {self.samples} samples are rendered")
-        _same_depth(self)
-        _same_sky(self)
+        self._unchanged()
         k_end = min(self._done + (self.first if self._done == 0 else self.step_size), self.samples)
         self.dscene.render_rows_masked(self.cam, self.samples, self.w, self.h, self._done, k_end, self._sums, mask=self._mask,
                                        sums2=self._sums2, counts=self._counts, cast=self.cast, shard=self.shard, stream=stream,
@@ -716,7 +645,7 @@ class Adaptive:
             self._live = self.dscene.adaptive_update(self._sums, self._sums2, self._counts, self._mask, self.tol, self.eps,
                                                      stream=stream)
         else:
-            st = stream if stream is not None else torch.cuda.current_stream(self._mask.device)
+            _, st = P.call_stream(self._mask.device, stream)
             with torch.cuda.stream(st):
                 new = torch.as_tensor(self.rule(self._sums, self._sums2, self._counts, self._mask), device=self._mask.device)
                 if tuple(new.shape) != tuple(self._mask.shape):

@@ -4,6 +4,7 @@
 Here `render(bih, cam, settings)` fills the same w-rows x h-columns RGB8 image through
 sq_render_rgb8 — the foreign call that replaces src/Lib.hs:73-74 — and writes the PNG.
 """
+import contextlib
 import ctypes as C
 from dataclasses import dataclass, field
 from typing import Tuple
@@ -43,6 +44,31 @@ def render_f32(bih, cam, samples, dimensions, cast=False) -> np.ndarray:
     return out
 
 
+def _resident(bih, device, lights, depth, sky):
+    """What the resident-scene wrappers share.  The call itself refuses a depth or a sky that is not one, before anything is
+    uploaded; the context manager it returns uploads the scene on entry (DeviceScene), sets those of lights, depth and sky that
+    are not None, and closes the scene on exit."""
+    if depth is not None:
+        N.depth_value(depth)
+    sky = N.sky_pair(sky)
+
+    @contextlib.contextmanager
+    def scene():
+        from .device import DeviceScene                # torch: only the resident-scene path needs it
+        ds = DeviceScene(bih, device)
+        try:
+            if lights is not None:
+                ds.set_lights(lights)
+            if depth is not None:
+                ds.set_depth(depth)
+            if sky is not None:
+                ds.set_sky(sky[0], sky[1])
+            yield ds
+        finally:
+            ds.close()
+    return scene()
+
+
 def render_progressive(bih, cam, samples, dimensions, step, cast=False, device=0, lights=None, depth=None, sky=None):
     """The frame of render_rgb8, `step` samples at a time: yields (done, rgb8) after every step, rgb8 being the (w, h, 3) uint8
     image of the first `done` samples.  The last image (done == samples) is bit for bit that of render_rgb8 (DeviceScene,
@@ -51,27 +77,15 @@ def render_progressive(bih, cam, samples, dimensions, step, cast=False, device=0
     what render_rgb8 computes); a depth is refused before anything is uploaded when it is not an integer in 1..8.  sky: the sky of a
     path-traced frame (DeviceScene.set_sky): three numbers (a constant sky) or (up, down); None = no sky, the reference's black.
     Refused before anything is uploaded when it is neither."""
-    from .device import DeviceScene, Progressive       # torch: only the resident-scene path needs it
+    from .device import Progressive                    # torch: only the resident-scene path needs it
     w, h = dimensions
     if int(step) < 1:
         raise ValueError(f"step must be positive, got {step}")
-    if depth is not None:
-        N.depth_value(depth)
-    sky = N.sky_pair(sky)
-    ds = DeviceScene(bih, device)
-    try:
-        if lights is not None:
-            ds.set_lights(lights)
-        if depth is not None:
-            ds.set_depth(depth)
-        if sky is not None:
-            ds.set_sky(sky[0], sky[1])
+    with _resident(bih, device, lights, depth, sky) as ds:
         p = Progressive(ds, cam, samples, w, h, cast=cast)
         while not p.finished:
             _, rgb = p.step(step)
             yield p.done, rgb.cpu().numpy()
-    finally:
-        ds.close()
 
 
 def denoise_options(denoise):
@@ -94,24 +108,15 @@ def render_adaptive(bih, cam, samples, dimensions, tol, eps=1.0, first=8, step=8
     render_progressive.  denoise (None = off; True, a sigma_l or a dict of denoise parameters): once the frame is finished, one more
     tuple follows whose image is the frame filtered on the device (denoise_frame: the variance from the frame's own second moments,
     the guides from its first hits) and tonemapped by the device's own tonemap; the tuples before it are unchanged."""
-    from .device import Adaptive, DeviceScene          # torch: only the resident-scene path needs it
+    from .device import Adaptive                       # torch: only the resident-scene path needs it
     w, h = dimensions
     if int(first) < 1 or int(step) < 1:
         raise ValueError(f"first and step must be positive, got {first}, {step}")
     if not float(tol) >= 0 or not float(eps) >= 0:
         raise ValueError(f"tol and eps must be numbers >= 0, got {tol}, {eps}")
-    if depth is not None:
-        N.depth_value(depth)
-    sky = N.sky_pair(sky)
+    scene = _resident(bih, device, lights, depth, sky)
     dn = None if denoise is None or denoise is False else denoise_options(denoise)      # refused before anything is uploaded
-    ds = DeviceScene(bih, device)
-    try:
-        if lights is not None:
-            ds.set_lights(lights)
-        if depth is not None:
-            ds.set_depth(depth)
-        if sky is not None:
-            ds.set_sky(sky[0], sky[1])
+    with scene as ds:
         a = Adaptive(ds, cam, samples, w, h, tol, eps=eps, first=first, step=step, cast=cast, rule=rule)
         avg = None
         while not a.finished:
@@ -122,8 +127,6 @@ def render_adaptive(bih, cam, samples, dimensions, tol, eps=1.0, first=8, step=8
             out, _ = denoise_frame(ds, cam, w, h, avg, var=denoise_variance(a.sums, a.sums2, a.counts), **dn)
             img = N.debug_eval("tonemap", out.cpu().numpy().reshape(-1, 3), device=ds.device).reshape(tuple(out.shape))
             yield a.done, a.live, a.samples_spent, img, a.counts.cpu().numpy()
-    finally:
-        ds.close()
 
 
 def render_views_rgb8(bih, cams, samples, dimensions, cast=False, device=0, lights=None, depth=None, sky=None) -> np.ndarray:
@@ -133,25 +136,13 @@ def render_views_rgb8(bih, cams, samples, dimensions, cast=False, device=0, ligh
     cams = list(cams)
     if not cams:
         raise ValueError("render_views_rgb8 needs at least one camera")
-    if depth is not None:
-        N.depth_value(depth)
-    sky = N.sky_pair(sky)
+    scene = _resident(bih, device, lights, depth, sky)
     import torch
-    from .device import DeviceScene
     w, h = dimensions
-    ds = DeviceScene(bih, device)
-    try:
-        if lights is not None:
-            ds.set_lights(lights)
-        if depth is not None:
-            ds.set_depth(depth)
-        if sky is not None:
-            ds.set_sky(sky[0], sky[1])
+    with scene as ds:
         _, rgb = ds.render_views(cams, samples, w, h, cast=cast, want_avg=False)
         torch.cuda.synchronize(ds.device)
         return rgb.cpu().numpy()
-    finally:
-        ds.close()
 
 
 def render(bih, cam, settings: Settings):

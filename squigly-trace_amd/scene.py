@@ -12,8 +12,31 @@ import numpy as np
 from . import _native as N
 
 
-class Mesh:
+def _records(address, n, dt):
+    """A copy of the n records of numpy dtype dt at `address` as an array (n = 0: the address is not looked at)."""
+    if n == 0:
+        return np.zeros(0, dt)
+    buf = (C.c_uint8 * (n * dt.itemsize)).from_address(address)
+    return np.frombuffer(buf, dtype=dt).copy()
+
+
+class Owner:
+    """Owns the C object behind the handle _h and hands it back, once, through the library function the subclass names in _free.
+    A method and not a function a subclass's module imports: __del__ may run while the interpreter shuts down, when a module's
+    globals are already None -- this module's N is looked at for that, and then the handle is only forgotten."""
+    _free = None
+
+    def _release(self):
+        if getattr(self, "_h", None) and N is not None and N._lib is not None:
+            getattr(N._lib, self._free)(self._h)
+        self._h = None
+
+    __del__ = _release
+
+
+class Mesh(Owner):
     """[Triangle] in loader order (Obj.trisFromObj)."""
+    _free = "sq_mesh_free"
 
     def __init__(self, handle):
         self._h = handle
@@ -50,27 +73,17 @@ class Mesh:
     @property
     def tris(self) -> np.ndarray:
         n = len(self)
-        if n == 0:
-            return np.zeros(0, N.TRI_DTYPE)
-        buf = (C.c_uint8 * (n * N.TRI_DTYPE.itemsize)).from_address(N.lib().sq_mesh_tris(self._h))
-        return np.frombuffer(buf, dtype=N.TRI_DTYPE).copy()
+        return _records(n and N.lib().sq_mesh_tris(self._h), n, N.TRI_DTYPE)
 
     @property
     def materials(self) -> np.ndarray:
         n = N.lib().sq_mesh_num_materials(self._h)
-        if n == 0:
-            return np.zeros(0, N.MAT_DTYPE)
-        buf = (C.c_uint8 * (n * N.MAT_DTYPE.itemsize)).from_address(N.lib().sq_mesh_materials(self._h))
-        return np.frombuffer(buf, dtype=N.MAT_DTYPE).copy()
-
-    def __del__(self):
-        if getattr(self, "_h", None) and N is not None and N._lib is not None:
-            N._lib.sq_mesh_free(self._h)
-        self._h = None
+        return _records(n and N.lib().sq_mesh_materials(self._h), n, N.MAT_DTYPE)
 
 
-class BIH:
+class BIH(Owner):
     """BIH.makeBIH result, flattened to the pre-order arrays of include/squigly_hip.h."""
+    _free = "sq_bih_free"
 
     def __init__(self, mesh: Mesh, device=None):
         """device=None: host build (sq_bih_build); device=k: the same tree built on GPU k (sq_bih_build_device)."""
@@ -87,23 +100,17 @@ class BIH:
     num_leaves = property(lambda s: N.lib().sq_bih_num_leaves(s._h))
     longest_leaf = property(lambda s: N.lib().sq_bih_longest_leaf(s._h))
 
-    def _view(self, ptr, n, dt):
-        if n == 0:
-            return np.zeros(0, dt)
-        buf = (C.c_uint8 * (n * dt.itemsize)).from_address(ptr)
-        return np.frombuffer(buf, dtype=dt).copy()
-
     @property
     def nodes(self):
-        return self._view(self.scene.nodes, self.scene.n_nodes, N.NODE_DTYPE)
+        return _records(self.scene.nodes, self.scene.n_nodes, N.NODE_DTYPE)
 
     @property
     def tris(self):
-        return self._view(self.scene.tris, self.scene.n_tris, N.TRI_DTYPE)
+        return _records(self.scene.tris, self.scene.n_tris, N.TRI_DTYPE)
 
     @property
     def materials(self):
-        return self._view(self.scene.mats, self.scene.n_mats, N.MAT_DTYPE)
+        return _records(self.scene.mats, self.scene.n_mats, N.MAT_DTYPE)
 
     @property
     def bounds(self):
@@ -115,11 +122,6 @@ class BIH:
         lim = np.empty(3, np.float32)
         N.check(N.lib().sq_cull_boxes(C.byref(self.scene), boxes.ctypes.data, lim.ctypes.data))
         return boxes, tuple(float(x) for x in lim)
-
-    def __del__(self):
-        if getattr(self, "_h", None) and N is not None and N._lib is not None:
-            N._lib.sq_bih_free(self._h)
-        self._h = None
 
 
 def load_camera(path) -> N.Camera:
