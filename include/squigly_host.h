@@ -72,8 +72,9 @@ uint32_t sq_half_outward(float x, int32_t up);
  * nonneg_materials, finite_geometry, n_emitters, n_verts, small_index, shortcut_depth (the largest path depth at which
  * nonneg_materials still holds; 0: none), and cull_o2max / cull_d2min / cull_d2max as the bits of the float.  The first-bounce
  * reduction (option "level1_cull"): array "level1" is the Level1Cull record sq_gen_bounce1 takes (csrc/sq_layout.h), scalars
- * level1_on (its preconditions hold) and level1_zero (s.surf * 0 + s.emit is bitwise +0 outside the emitter list).  An unknown
- * name returns non-zero. */
+ * level1_on (its preconditions hold) and level1_zero (s.surf * 0 + s.emit is bitwise +0 outside the emitter list); array
+ * "level1_cover" is the Level1Cover record behind SceneView::rtail (one record where level1_on, else empty): at most 8 boxes that
+ * hold the end point of every accepted first-bounce ray.  An unknown name returns non-zero. */
 typedef struct sq_packed sq_packed;
 int   sq_scene_pack(const sq_scene* scene, sq_packed** out);
 int   sq_packed_array(const sq_packed* p, const char* name, const void** data, size_t* bytes);

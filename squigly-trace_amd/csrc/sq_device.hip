@@ -117,6 +117,7 @@ extern "C" int sq_scene_upload(const sq_scene* sc, int32_t device, sq_device_sce
         f(v.surfs, P.surfs, false); f(v.mats, P.mats, false); f(v.verts4, P.verts4, false); f(v.trix, P.trix, false);
         f(v.rbranch, P.rbranch, false); f(v.emitters, P.emitters, false);
         f(v.cull_child, P.cull_child, true); f(v.cull_child16, P.cull_child16, true); f(v.branches_m, P.branches_m, true);
+        f(v.rtail, P.level1_cover, true);
     };
     auto slot = [](size_t bytes) { return ((bytes ? bytes : 16) + 255) & ~(size_t)255; };
     size_t arena_bytes = 0;
@@ -138,7 +139,7 @@ extern "C" int sq_scene_upload(const sq_scene* sc, int32_t device, sq_device_sce
     v.n_branches = P.nb; v.n_leaves = P.nl; v.n_tris = sc->n_tris; v.n_mats = sc->n_mats; v.n_verts = P.n_verts; v.n_emitters = P.n_emitters;
     v.height = P.height; v.nonneg_materials = P.nonneg_materials; v.finite_geometry = P.finite_geometry;
     v.cull_o2max = P.cull_limits[0]; v.cull_d2min = P.cull_limits[1]; v.cull_d2max = P.cull_limits[2];
-    v.rtail = nullptr; v.incremental_ok = 0;               // unread by every kernel (sq_scene.h)
+    v.incremental_ok = 0;                                  // unread by every kernel (sq_scene.h)
     *out = s;
     return 0;
 }

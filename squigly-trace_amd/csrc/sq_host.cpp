@@ -856,6 +856,31 @@ struct Packer {
     // every x of the box has |x - p0| <= scale = |g|_1 + |h|_1 (g = centre - p0, h = half extents), so "the box lies strictly on one
     // side of the plane" or "strictly on the negative side of w", each by more than 1e-9 scale, proves H misses the box.
     // tests/test_level1_cull.py restates all of this in numpy and searches for counter-examples against the oracle's mollerTrumbore.
+    //
+    // EXTENSION.  (3) may be replaced by
+    //   (4) for every box j of the cover (level1_cover below), the interval I_j of t in which ray 1 can end on a triangle of the box
+    //       misses the stretch [ta, tb] = { t >= 0 : some s has p0 + t d1 + s nd in B },  B = the emitters' box grown as in (3)
+    //       (an empty stretch satisfies this for every cover).
+    // Proof.  As above it is enough that no emitter accepts ray 2; suppose e does.  The traversal returned a triangle T that accepted
+    //   ray 1 -- no emitter by (1), scattering by (2) -- with computed parameter t^ > 0, and by the proof of (3) the line Y + s nd,
+    //   Y = p0 + t^ d1, meets B: t^ lies in the stretch.  The accepted test has the exact solution X = p0 + t d1 = v0 + u e1 + v e2 (the
+    //   kernels' rounded edges): X lies IN THE PLANE of the triangle T' = (v0, v0 + e1, v0 + e2) and within rho_T of T', so X - Z is a
+    //   vector of that plane for the nearest point Z of T', and its k-th component is at most rho_T s_k, s_k = sqrt(1 - n^_k^2) the
+    //   largest k-th component of a unit vector orthogonal to the unit normal n^.  X lies in the box of T' grown by rho_T s_k along axis
+    //   k, hence in the cover box j that holds it, hence t in the exact slab interval of that box for ray 1, which the computed fp32
+    //   interval [tmin_j, tmax_j] of the box grown by the slab test's own rounding contains (the culling lemma above).  And
+    //   |t^ - t| <= c_T + r_T |t| + 2.01u |t^|, c_T = 8u S E1 E2 / eps, S <= omax + V0, r_T <= 1/8.  t -> t + r|t| and t -> t - r|t| increase
+    //   with t, so t^ (1 - 2.01u) <= tmax_j + r_j |tmax_j| + c_j and, where t^ <= t (then 0 < t^ <= t), t^ >= tmin_j - (r_j + 2.01u) |tmin_j| -
+    //   c_j, r_j and c_j the largest of the box: t^ lies in I_j = [tmin_j - r'_j |tmin_j| - c'_j, tmax_j + r'_j |tmax_j| + c'_j], the table's
+    //   r' = r + 2e-6 and c' = c (1 + 1e-5) covering the 2.01u and the three fp32 operations of either end.  t^ in I_j and in the stretch
+    //   contradicts (4).                                                                                                          QED
+    // The stretch: a line with direction nd through x meets B = c +- h iff |n_k.(x - c)| <= sum_j |n_k,j| h_j for n_k = nd x e_k, k = 0, 1,
+    //   2 (B's projection along nd is a hexagon with these edge normals; the components of n_k are components of nd, exact).  For x = p0
+    //   + t d1 that is |t N_k - G_k| <= r_k, N = d1 x nd, G = (c - p0) x nd.  The kernel forms N, G, r in binary64 from the exact fp32
+    //   values (N_k: two exact products and one rounding; G_k, r_k within 1e-14 scale), widens every slab by 1e-9 scale and every
+    //   quotient by 1e-9 of itself (the quotients' own error is below 1e-15), lets a slab with |N_k| < 1e-6 constrain nothing, and rounds
+    //   ta down and tb up to fp32 by a factor 1 -+ 2^-20: the computed stretch contains the exact one.
+    // tests/test_level1_stretch.py restates (4) and searches for counter-examples against the oracle's traversal and mollerTrumbore.
     void level1_tables() {
         Level1Cull& L = P.level1; L = Level1Cull{};
         std::vector<char> emits((size_t)sc.n_tris, 0);
@@ -932,6 +957,88 @@ struct Packer {
         }
         L.o2max = P.cull_limits[0]; L.d2min = P.cull_limits[1]; L.d2max = P.cull_limits[2];
         L.on = 1;
+        level1_cover(emits, omax, 8.0 * u * (vmax_inf * (1.0 + 1e-6) + g1 + omax) + 1e-20);
+    }
+    // Condition (4)'s cover (the lemma's extension above).  Per non-emissive triangle T: the box of the kernels' triangle (v0, v0 + e1,
+    // v0 + e2 with the rounded edges, and the vertices themselves) grown along axis k by rho_T s_k, s_k = sqrt(1 - n^_k^2) the largest
+    // k-th component of a unit vector in T's plane, and by the slab test's own rounding.  Any grouping into boxes is valid; this one finds
+    // the walls and panels of a room: triangles thin on an axis are grouped by (axis, coordinate cell) -- the kMaxGroups largest groups, to
+    // bound the work --, the others by the octant of their centre, and the pair of boxes whose union adds the least volume is merged until
+    // kLevel1Boxes remain.  A box's r and c are the largest of its triangles', with room for the kernel's fp32 evaluation of the widened
+    // interval: three operations, each within u of a value no larger than 1.13 |t| + c, and the 2.01u |t^|.
+    void level1_cover(const std::vector<char>& emits, double omax, double slab_slack) {
+        const double u = kLemmaU, eps = kLemmaEps;
+        struct Box { double lo[3], hi[3], r, c; int64_t count; int axis; int64_t cell; };
+        auto join = [](const Box& a, const Box& b) {
+            Box o = a; o.count += b.count; o.r = std::max(a.r, b.r); o.c = std::max(a.c, b.c);
+            for (int k = 0; k < 3; ++k) { o.lo[k] = std::min(a.lo[k], b.lo[k]); o.hi[k] = std::max(a.hi[k], b.hi[k]); }
+            return o;
+        };
+        auto volume = [](const Box& a) { return (a.hi[0] - a.lo[0]) * (a.hi[1] - a.lo[1]) * (a.hi[2] - a.lo[2]); };
+        std::vector<Box> each;
+        double slo[3] = { 1e300, 1e300, 1e300 }, shi[3] = { -1e300, -1e300, -1e300 };
+        for (int32_t i = 0; i < sc.n_tris; ++i) {
+            if (emits[(size_t)i]) continue;
+            const sq_tri& t = sc.tris[i];
+            const TriNorms q = tri_norms(t);
+            const double rho = lemma_rho(q, omax);
+            double e1[3], e2[3];
+            for (int k = 0; k < 3; ++k) { e1[k] = (double)(t.v1[k] - t.v0[k]); e2[k] = (double)(t.v2[k] - t.v0[k]); }
+            const double n[3] = { e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0] };
+            const double nn = std::sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
+            Box b{}; b.count = 1; b.axis = 3; b.cell = 0;
+            b.r = 7.0 * u * q.P / eps; b.c = 8.0 * u * (omax + q.V0) * q.E1 * q.E2 / eps;
+            for (int k = 0; k < 3; ++k) {
+                const double across = std::sqrt(n[(k + 1) % 3] * n[(k + 1) % 3] + n[(k + 2) % 3] * n[(k + 2) % 3]);
+                // (n is within 3e-16 E1 E2 of the exact normal: above the sliver limit the quotient is good to 3e-10, below it s_k = 1)
+                const double s = nn > 1e-6 * q.E1 * q.E2 ? std::min(1.0, across / nn + 1e-6) : 1.0;
+                const double pts[5] = { (double)t.v0[k], (double)t.v1[k], (double)t.v2[k], (double)t.v0[k] + e1[k], (double)t.v0[k] + e2[k] };
+                b.lo[k] = *std::min_element(pts, pts + 5) - rho * s - slab_slack;
+                b.hi[k] = *std::max_element(pts, pts + 5) + rho * s + slab_slack;
+                slo[k] = std::min(slo[k], b.lo[k]); shi[k] = std::max(shi[k], b.hi[k]);
+            }
+            each.push_back(b);
+        }
+        const double extent = each.empty() ? 0.0 : std::max({ shi[0] - slo[0], shi[1] - slo[1], shi[2] - slo[2] });
+        for (Box& b : each) {
+            const double ex[3] = { b.hi[0] - b.lo[0], b.hi[1] - b.lo[1], b.hi[2] - b.lo[2] }, longest = std::max({ ex[0], ex[1], ex[2] });
+            for (int k = 2; k >= 0; --k) if (ex[k] <= 1e-4 * extent && ex[k] < 0.05 * longest) b.axis = k;
+            if (b.axis < 3) b.cell = (int64_t)std::floor(0.5 * (b.lo[b.axis] + b.hi[b.axis]) / std::max(1e-3 * extent, 1e-300) + 0.5);
+            else for (int k = 0; k < 3; ++k) b.cell |= (int64_t)(b.lo[k] + b.hi[k] >= slo[k] + shi[k]) << k;
+        }
+        std::stable_sort(each.begin(), each.end(), [](const Box& a, const Box& b) { return a.axis != b.axis ? a.axis < b.axis : a.cell < b.cell; });
+        std::vector<Box> boxes, octants;
+        for (size_t i = 0; i < each.size(); ++i) {
+            std::vector<Box>& to = each[i].axis < 3 ? boxes : octants;
+            if (i && each[i].axis == each[i - 1].axis && each[i].cell == each[i - 1].cell) to.back() = join(to.back(), each[i]);
+            else to.push_back(each[i]);
+        }
+        constexpr size_t kMaxGroups = 56;
+        if (boxes.size() > kMaxGroups) {                                  // the smaller groups join the octant of their centre
+            std::stable_sort(boxes.begin(), boxes.end(), [](const Box& a, const Box& b) { return a.count > b.count; });
+            for (size_t i = kMaxGroups; i < boxes.size(); ++i) octants.push_back(boxes[i]);
+            boxes.resize(kMaxGroups);
+        }
+        boxes.insert(boxes.end(), octants.begin(), octants.end());
+        while (boxes.size() > (size_t)kLevel1Boxes) {
+            size_t bi = 0, bj = 1; double best = INFINITY;
+            for (size_t i = 0; i < boxes.size(); ++i)
+                for (size_t j = i + 1; j < boxes.size(); ++j) {
+                    const double grow = volume(join(boxes[i], boxes[j])) - volume(boxes[i]) - volume(boxes[j]);
+                    if (grow < best) { best = grow; bi = i; bj = j; }
+                }
+            boxes[bi] = join(boxes[bi], boxes[bj]);
+            boxes.erase(boxes.begin() + (std::ptrdiff_t)bj);
+        }
+        if (boxes.empty()) return;                                        // no record: condition (4) is the stretch alone
+        Level1Cover V{};
+        V.n = (int32_t)boxes.size();
+        for (size_t j = 0; j < (size_t)kLevel1Boxes; ++j) {               // entries beyond n repeat the first: the kernel reads them all
+            const Box& b = boxes[j < boxes.size() ? j : 0];
+            V.r[j] = f_up(b.r + 2e-6); V.c[j] = f_up(b.c * (1.0 + 1e-5) + 1e-30);
+            for (int k = 0; k < 3; ++k) { V.box[j][k] = f_down(b.lo[k]); V.box[j][3 + k] = f_up(b.hi[k]); }
+        }
+        P.level1_cover.assign(1, V);
     }
     void geometry_flags() {                                 // v_min / v_max slabs need NaN-free planes
         bool fin = finite3(sc.root.lo) && finite3(sc.root.hi);
@@ -972,7 +1079,7 @@ extern "C" int sq_packed_array(const sq_packed* P, const char* name, const void*
     auto is = [&](const char* n, const auto& v) { if (!found && !std::strcmp(name, n)) { found = true; *data = v.data(); *bytes = v.size() * sizeof(v[0]); } };
     is("branches", P->branches); is("leaves", P->leaves); is("tris", P->tris); is("tri_mat", P->tri_mat); is("surfs", P->surfs);
     is("mats", P->mats); is("verts4", P->verts4); is("trix", P->trix); is("rbranch", P->rbranch); is("emitters", P->emitters);
-    is("cull_child", P->cull_child); is("cull_child16", P->cull_child16); is("branches_m", P->branches_m);
+    is("cull_child", P->cull_child); is("cull_child16", P->cull_child16); is("branches_m", P->branches_m); is("level1_cover", P->level1_cover);
     if (!found && !std::strcmp(name, "level1")) { found = true; *data = &P->level1; *bytes = sizeof P->level1; }
     return found ? 0 : sq_set_error("no packed array '%s'", name);
 }

@@ -148,9 +148,71 @@ __device__ __forceinline__ bool halfplane_misses_box(f3 p0, f3 d1, f3 nd, const 
     const double side = w[0] * g[0] + w[1] * g[1] + w[2] * g[2] + __builtin_fabs(w[0]) * h[0] + __builtin_fabs(w[1]) * h[1] + __builtin_fabs(w[2]) * h[2];
     return side < -tol;                                                 // the whole box behind ray 1, seen across nd
 }
+// Condition (4) of the lemma, for a sample (3) keeps: the stretch [ta, tb] of ray 1 from whose points the line along nd reaches the
+// box [lo - m, hi + m] -- three slabs in t, |t N_k - G_k| <= r_k with N = d1 x nd, G = g x nd, r_k = sum_j |(nd x e_k)_j| h_j -- is empty
+// on t >= 0, or misses ray 1's fp32 slab interval of every box of the cover V.  Binary64 on the exact fp32 values; each slab is widened
+// by 1e-9 of the scale and each quotient by 1e-9 of itself, and a slab whose |N_k| < 1e-6 constrains nothing.
+#ifndef SQ_LEVEL1_COVER
+#define SQ_LEVEL1_COVER 1               // 0: an experimental build without the cover (the stretch alone)
+#endif
+__device__ __forceinline__ bool stretch_misses_cover(f3 p0, f3 d1, f3 nd, const double* lo, const double* hi, double m, const uint4* cover) {
+    const double px[3] = { p0.x, p0.y, p0.z }, dx[3] = { d1.x, d1.y, d1.z }, nx[3] = { nd.x, nd.y, nd.z };
+    double g[3], h[3], scale = 0.0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { g[k] = 0.5 * (lo[k] + hi[k]) - px[k]; h[k] = 0.5 * (hi[k] - lo[k]) + m; scale += __builtin_fabs(g[k]) + h[k]; }
+    const double tol = 1e-9 * scale;
+    const double N[3] = { dx[1] * nx[2] - dx[2] * nx[1], dx[2] * nx[0] - dx[0] * nx[2], dx[0] * nx[1] - dx[1] * nx[0] };
+    const double G[3] = { g[1] * nx[2] - g[2] * nx[1], g[2] * nx[0] - g[0] * nx[2], g[0] * nx[1] - g[1] * nx[0] };
+    const double r[3] = { __builtin_fabs(nx[2]) * h[1] + __builtin_fabs(nx[1]) * h[2], __builtin_fabs(nx[2]) * h[0] + __builtin_fabs(nx[0]) * h[2],
+                          __builtin_fabs(nx[1]) * h[0] + __builtin_fabs(nx[0]) * h[1] };
+    // one division for the three quotients: 1 / N_k = (the product of the other two) / (the product of all), an unused N_k counting as 1
+    bool use[3]; double Nu[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { use[k] = __builtin_fabs(N[k]) >= 1e-6; Nu[k] = use[k] ? N[k] : 1.0; }
+    const double inv = 1.0 / ((Nu[0] * Nu[1]) * Nu[2]);
+    const double rc[3] = { inv * (Nu[1] * Nu[2]), inv * (Nu[0] * Nu[2]), inv * (Nu[0] * Nu[1]) };
+    double ta = 0.0, tb = (double)__builtin_inff();
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const double w = r[k] + tol;
+        const double q1 = (G[k] - w) * rc[k], q2 = (G[k] + w) * rc[k];
+        const double ql = __builtin_fmin(q1, q2), qh = __builtin_fmax(q1, q2);
+        ta = use[k] ? __builtin_fmax(ta, ql - 1e-9 * __builtin_fabs(ql)) : ta;
+        tb = use[k] ? __builtin_fmin(tb, qh + 1e-9 * __builtin_fabs(qh)) : tb;
+    }
+    if (ta > tb) return true;                                           // from no point of ray 1 does a line along nd reach the box
+    if (!SQ_LEVEL1_COVER || cover == nullptr) return false;
+    // the stretch as fp32 numbers, rounded outwards (0 <= ta <= tb here)
+    const float ta32 = ta > 1e-30 ? (float)(ta * (1.0 - 0x1p-20)) : 0.0f, tb32 = (float)(tb * (1.0 + 0x1p-20));
+    // 1 / d1 and -p0 / d1 as condition (2) formed them, computed again: kept alive across randomVector and the emitter loop they take
+    // six registers and the kernel spills (the empty asm keeps the optimiser from seeing the same quotients)
+    f3 dh = d1;
+    asm volatile("" : "+v"(dh.x), "+v"(dh.y), "+v"(dh.z));
+    const f3 df = sq::mk(1.0f / dh.x, 1.0f / dh.y, 1.0f / dh.z);
+    const f3 nodf = sq::mk(-p0.x * df.x, -p0.y * df.y, -p0.z * df.z);
+    const __attribute__((address_space(4))) float* V = (const __attribute__((address_space(4))) float*)cover;
+    // all kLevel1Boxes boxes, without a branch (the packer fills unused entries with copies of the first): a wave leaves a loop with an
+    // early exit only when its last lane does, and each turn of it waited for its own scalar loads
+    bool may_end = false;                                               // Level1Cover: n | r[] | c[] | box[][6]
+#pragma unroll
+    for (int j = 0; j < kLevel1Boxes; ++j) {
+        const float rj = V[4 + j], cj = V[4 + kLevel1Boxes + j];
+        const __attribute__((address_space(4))) float* b = V + 4 + 2 * kLevel1Boxes + 6 * j;
+        const float t1 = __builtin_fmaf(b[0], df.x, nodf.x), t2 = __builtin_fmaf(b[3], df.x, nodf.x);
+        const float t3 = __builtin_fmaf(b[1], df.y, nodf.y), t4 = __builtin_fmaf(b[4], df.y, nodf.y);
+        const float t5 = __builtin_fmaf(b[2], df.z, nodf.z), t6 = __builtin_fmaf(b[5], df.z, nodf.z);
+        const float tmin = vmax3(vmin(t1, t2), vmin(t3, t4), vmin(t5, t6));
+        const float tmax = vmin3(vmax(t1, t2), vmax(t3, t4), vmax(t5, t6));
+        // X's parameter t lies in [tmin, tmax]; the computed t^ within r |t| + c of it
+        const float tlo = (tmin - rj * __builtin_fabsf(tmin)) - cj, thi = (tmax + rj * __builtin_fabsf(tmax)) + cj;
+        may_end |= vmax(tlo, ta32) <= vmin(thi, tb32);                  // ray 1 may end on a triangle of this box, at a point of the stretch
+    }
+    return !may_end;
+}
 // May the scattered ray 1 = (p0, d1) of a sample whose generator goes on with n1, n2 be dropped, the sample finished as a
-// first-bounce miss?  Conditions (1)-(3) of the lemma; p0_ok: |p0|^2 is inside the lemma's limit (per pixel).
-__device__ __forceinline__ bool level1_culled(const SceneView& S, const Level1Cull& C, bool p0_ok, f3 p0, f3 d1, uint32_t n1, uint32_t n2) {
+// first-bounce miss?  1: by conditions (1)-(3) of the lemma, 2: by (1), (2) and (4), 0: no; p0_ok: |p0|^2 is inside the lemma's
+// limit (per pixel).
+__device__ __forceinline__ int level1_culled(const SceneView& S, const Level1Cull& C, bool p0_ok, f3 p0, f3 d1, uint32_t n1, uint32_t n2) {
     const float eps = 0.0001f, inf = __builtin_inff();
     // ray 1 inside the limits of sq_cull_boxes (as trav_begin decides Trav::cull)
     const f3 df = sq::mk(1.0f / d1.x, 1.0f / d1.y, 1.0f / d1.z);
@@ -183,10 +245,12 @@ __device__ __forceinline__ bool level1_culled(const SceneView& S, const Level1Cu
         const float a = sq::dot(e1, sq::cross(nd, e2));                 // moller_trumbore's `a` for (any origin, nd); -nd gives -a
         if (!(a > -eps && a < eps)) amin = sq::hmin(amin, __builtin_fabsf(a));
     }
-    if (amin == inf) return true;                                       // every emitter rejects +-nd by its determinant alone
-    if (!(amin < inf)) return false;
-    // (3)
-    return halfplane_misses_box(p0, d1, nd, C.em_lo, C.em_hi, C.em_rho * ((double)eps / (double)amin) + C.em_add);
+    if (amin == inf) return 1;                                          // every emitter rejects +-nd by its determinant alone
+    if (!(amin < inf)) return 0;
+    // (3), and (4) where it does not decide
+    const double m = C.em_rho * ((double)eps / (double)amin) + C.em_add;
+    if (halfplane_misses_box(p0, d1, nd, C.em_lo, C.em_hi, m)) return 1;
+    return stretch_misses_cover(p0, d1, nd, C.em_lo, C.em_hi, m, S.rtail) ? 2 : 0;
 }
 
 // Depth-0 bounce of every sample of the batch: RNG, bounceRay, ray 1 into slot sid (src/Lib.hs:133-134).
@@ -200,7 +264,7 @@ __device__ __forceinline__ bool level1_culled(const SceneView& S, const Level1Cu
 template <int SRC, typename FrameT>
 __device__ __forceinline__ void gen_bounce1_body(const SceneView& S, const FrameT& F, const Work& W, int k_base, int k_count, const RngView R, const Level1Cull& C) {
     const int A = *W.n_active;
-    unsigned int n_culled = 0;
+    unsigned int n_culled = 0, n_culled4 = 0;                           // by conditions (1)-(3), and by (4) where (3) did not decide
     diag_aux_wave(W, F.diag, true);
     const int n_runs = (k_count + kRngRun - 1) / kRngRun, runs_per_y = (n_runs + (int)gridDim.y - 1) / (int)gridDim.y;
     const int g_begin = min(n_runs, (int)blockIdx.y * runs_per_y), g_end = min(n_runs, g_begin + runs_per_y);
@@ -241,7 +305,10 @@ __device__ __forceinline__ void gen_bounce1_body(const SceneView& S, const Frame
                 }
                 const f3 d1 = scatter_dir(P.d0, P.s0, n0, n1);
                 // Level-1 culling: nothing ray 1 can hit changes the sample's radiance, which is that of a first-bounce miss
-                if (C.on && level1_culled(S, C, p0_ok, P.p0, d1, n1, n2)) { finish_level1(W, sid, -1); ++n_culled; continue; }
+                if (C.on) {
+                    const int why = level1_culled(S, C, p0_ok, P.p0, d1, n1, n2);
+                    if (why) { finish_level1(W, sid, -1); n_culled += why == 1; n_culled4 += why == 2; continue; }
+                }
                 W.state[sid] = kRay1;
                 W.org[sid] = make_float4(P.p0.x, P.p0.y, P.p0.z, __uint_as_float(n1));
                 W.dir[sid] = make_float4(d1.x, d1.y, d1.z, __uint_as_float(n2));
@@ -250,8 +317,9 @@ __device__ __forceinline__ void gen_bounce1_body(const SceneView& S, const Frame
     }
     if (C.on) {                                                         // rays culled, one atomic per wave (the loop above has ended for all its lanes)
 #pragma unroll
-        for (int o = 32; o > 0; o >>= 1) n_culled += __shfl_xor(n_culled, o);
+        for (int o = 32; o > 0; o >>= 1) { n_culled += __shfl_xor(n_culled, o); n_culled4 += __shfl_xor(n_culled4, o); }
         if ((threadIdx.x & 63) == 0 && n_culled) atomicAdd(&W.stats[kStatLevel1Culled], (unsigned long long)n_culled);
+        if ((threadIdx.x & 63) == 0 && n_culled4) atomicAdd(&W.stats[kStatLevel1Stretch], (unsigned long long)n_culled4);
     }
     diag_aux_wave(W, F.diag, false);
 }

@@ -48,5 +48,15 @@ struct Level1Cull {
     double em_lo[3], em_hi[3];               // bounding box of the emissive triangles' vertices
     double em_rho, em_add;                   // its margin for a ray 2 whose smallest accepted |determinant| is a: em_rho * (eps / a) + em_add
 };
+// The cover of the geometry ray 1 can end on (sq_host.cpp, "Level-1 culling", condition 4): at most kLevel1Boxes boxes that together
+// hold the exact point X in which an accepted ray 1 meets the plane of its triangle; the computed parameter t^ of the hit lies within
+// r |t| + c of X's parameter t.  One record in device memory behind SceneView::rtail, read by sq_gen_bounce1 alone, wave-uniformly.
+constexpr int kLevel1Boxes = 8;
+struct Level1Cover {
+    int32_t n; int32_t pad[3];               // distinct boxes, 1 .. kLevel1Boxes; the entries beyond them repeat the first
+    float r[kLevel1Boxes], c[kLevel1Boxes];  // per box: |t^ - t| <= r |t| + c for every triangle in it (the rounding of the widened interval included)
+    float box[kLevel1Boxes][6];              // lo.xyz, hi.xyz
+};
+static_assert(sizeof(Level1Cover) == 272, "the cover is seventeen 16-byte quads");
 constexpr int kTriRunPad = 3;   // zero triangles after the last one, so that a run of loads may start at any triangle (GlobalTris::kRunPad)
 }  // namespace sqd

@@ -31,7 +31,8 @@ struct PackedScene {
     int32_t shortcut_depth = 0;                     // the largest path depth (<= kDeepestPath) whose nested products nonneg_materials' bound covers
     float cull_limits[3] = { -1.0f, 0.25f, 1.5624f };   // SceneView::cull_o2max, cull_d2min, cull_d2max
     sqd::Level1Cull level1{};                       // the first-bounce reduction's tables; level1.on = its preconditions hold
-    bool level1_zero = false;                       // s.surf * 0 + s.emit is bitwise (+0, +0, +0) for every triangle outside `emitters`
+    std::vector<sqd::Level1Cover> level1_cover;     // one record where level1.on (SceneView::rtail), else empty
+    bool level1_zero = false;                      // s.surf * 0 + s.emit is bitwise (+0, +0, +0) for every triangle outside `emitters`
     bool small_index = false;                       // < 0x8000 branches and triangles: 2-byte stack words
 };
 
