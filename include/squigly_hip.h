@@ -365,8 +365,9 @@ void sq_kernel_timing_reset(sq_device_scene* s);
  * out[0] = rays traced; out[1..23] = lane-occupancy counters, rare-path counts and per-section wave cycles of the
  * profile build, filled only with option "profile" = 1 (tools/gpu_pool.py prints them); out[28] = first-bounce rays that
  * level-1 culling (option "level1_cull") did not queue by its conditions (1)-(3); out[29] = those that only its condition (4) kept off
- * the queue (no point of the ray from which the second bounce could reach an emitter lies in the cover of the geometry), so the rays
- * dropped are out[28] + out[29]. */
+ * the queue (no point of the ray from which the second bounce could reach an emitter lies in the cover of the geometry); out[30] =
+ * those that only its condition (5) kept off the queue (the ray may end on a mirror, but behind no mirror does it reach the image of
+ * the emitters), so the rays dropped are out[28] + out[29] + out[30]. */
 int  sq_get_stats(sq_device_scene* s, uint64_t* out, int32_t n, int32_t reset);
 /* Tunables; every setting produces identical bits.  Keys:
  *   "variant"            1 = one-lane-per-pixel kernel, 2 = wavefront pipeline (default)
@@ -417,7 +418,7 @@ int  sq_get_stats(sq_device_scene* s, uint64_t* out, int32_t n, int32_t reset);
  *   "level1_cull"        1 (default): a path-traced frame or query at depth 3 does not queue the scattered first-bounce ray of a
  *                        sample that provably ends with the radiance of a first-bounce miss (no emitter on the ray, no mirroring
  *                        surface on it, no emitter within reach of the second bounce: csrc/sq_host.cpp, level1_tables) -- no bit
- *                        changes; 0: every such ray is traced.  sq_get_stats slots 28 and 29 count the rays dropped, sq_last_plan says
+ *                        changes; 0: every such ray is traced.  sq_get_stats slots 28 to 30 count the rays dropped, sq_last_plan says
  *                        whether the frame used it
  *   "primary_tiles"      1 (default): the primary rays of a shard are enumerated in tiles (8 x 8 pixels on a whole image, 2 x 32 with
  *                        row blocks of 2) so that the 64 rays of a wave stay together in both image directions; 0: 64 pixels of a row

@@ -74,7 +74,10 @@ uint32_t sq_half_outward(float x, int32_t up);
  * reduction (option "level1_cull"): array "level1" is the Level1Cull record sq_gen_bounce1 takes (csrc/sq_layout.h), scalars
  * level1_on (its preconditions hold) and level1_zero (s.surf * 0 + s.emit is bitwise +0 outside the emitter list); array
  * "level1_cover" is the Level1Cover record behind SceneView::rtail (one record where level1_on, else empty): at most 8 boxes that
- * hold the end point of every accepted first-bounce ray.  An unknown name returns non-zero. */
+ * hold the end point of every accepted first-bounce ray; array "level1_mirror" is the Level1Mirror record that follows it on the device
+ * (one record wherever "level1_cover" has one): the mirror panels with their boxes and the images of the emitters' box, the rest boxes,
+ * the smallest `reflective` per cover box and the determinant floor of condition (5); n_panels = 0 where that condition is off.  An
+ * unknown name returns non-zero. */
 typedef struct sq_packed sq_packed;
 int   sq_scene_pack(const sq_scene* scene, sq_packed** out);
 int   sq_packed_array(const sq_packed* p, const char* name, const void** data, size_t* bytes);

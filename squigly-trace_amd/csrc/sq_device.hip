@@ -112,12 +112,18 @@ extern "C" int sq_scene_upload(const sq_scene* sc, int32_t device, sq_device_sce
     // (540 x 540 at 10 samples) those calls were a third of the call's time.  Every array starts on a 256-byte boundary.
     // The table: each SceneView member and its vector, in arena order; an empty optional array takes no room and stays nullptr.
     SceneView& v = s->view;
+    std::vector<unsigned char> tail;                       // level-1 culling's cover and, directly behind it, its mirror record
+    if (!P.level1_cover.empty()) {
+        tail.resize(sizeof(Level1Cover) + sizeof(Level1Mirror));
+        std::memcpy(tail.data(), P.level1_cover.data(), sizeof(Level1Cover));
+        std::memcpy(tail.data() + sizeof(Level1Cover), P.level1_mirror.data(), sizeof(Level1Mirror));
+    }
     auto arrays = [&](auto&& f) {
         f(v.branches, P.branches, false); f(v.leaves, P.leaves, false); f(v.tris, P.tris, false); f(v.tri_mat, P.tri_mat, false);
         f(v.surfs, P.surfs, false); f(v.mats, P.mats, false); f(v.verts4, P.verts4, false); f(v.trix, P.trix, false);
         f(v.rbranch, P.rbranch, false); f(v.emitters, P.emitters, false);
         f(v.cull_child, P.cull_child, true); f(v.cull_child16, P.cull_child16, true); f(v.branches_m, P.branches_m, true);
-        f(v.rtail, P.level1_cover, true);
+        f(v.rtail, tail, true);
     };
     auto slot = [](size_t bytes) { return ((bytes ? bytes : 16) + 255) & ~(size_t)255; };
     size_t arena_bytes = 0;

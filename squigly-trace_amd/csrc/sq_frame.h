@@ -232,6 +232,7 @@ constexpr uint8_t kDone = 0, kRay1 = 1, kMirror = 2, kRay2 = 3;
 constexpr int kDiagGauge = 24, kDiagWaves = 25, kDiagStartBeside = 26, kDiagEndBeside = 27;
 constexpr int kStatLevel1Culled = 28;       // sq_get_stats 28: first-bounce rays sq_gen_bounce1 did not queue (level-1 culling)
 constexpr int kStatLevel1Stretch = 29;      // sq_get_stats 29: those that only condition (4), the stretch against the cover, kept off the queue
+constexpr int kStatLevel1Mirror = 30;       // sq_get_stats 30: those that only condition (5), the mirrored ray 2's reach, kept off the queue
 
 // Appends `want` lanes of this wave to a list with one atomic: wave ballot + prefix rank.
 __device__ __forceinline__ int wave_append(int32_t* counter, bool want) {

@@ -14,10 +14,12 @@
 #include "sq_plan.h"
 
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <map>
 #include <string>
 #include <unordered_map>
 #include <vector>
@@ -881,6 +883,48 @@ struct Packer {
     //   quotient by 1e-9 of itself (the quotients' own error is below 1e-15), lets a slab with |N_k| < 1e-6 constrain nothing, and rounds
     //   ta down and tb up to fp32 by a factor 1 -+ 2^-20: the computed stretch contains the exact one.
     // tests/test_level1_stretch.py restates (4) and searches for counter-examples against the oracle's traversal and mollerTrumbore.
+    //
+    // MIRROR EXTENSION.  Where ray 1 passes the box of its mirror class, (2) may be replaced by
+    //   (5) with the record of level1_mirror below and un1 = unit_float(n1):  d2lo <= |d1|^2 <= d2hi;  ray 1 fails the slab test of every
+    //       rest box with rmax >= un1;  (d1.W_k)^2 >= thr2 |d1|^2 for every W_k;  for every panel p with val_p >= un1, ray 1's fp32 slab
+    //       intervals [pmin, pmax] of the panel's box and [imin, imax] of its image box have pmax < pmin, or pmax <= -back_p, or
+    //       imax < imin, or imax < pmin;  and (3) or (4) holds with the cover reduced to its boxes j with rmin_j < un1.
+    // Proof.  Let the traversal return T for ray 1, no emitter by (1), with computed parameter t^ > 0 and hit point p1.  It is enough
+    //   that no emitter accepts ray 2.
+    //   T scatters (reflective_T < un1): ray 2 = (p1, +-nd), and T lies in a box j of the cover with rmin_j <= reflective_T < un1.  The
+    //   proofs of (3) and (4) use of (2) only that T scatters, and (4)'s uses the box that holds T alone: they apply as they stand.
+    //   T mirrors (reflective_T >= un1): ray 2 = (p1, d2), d2 = fl(d1 - 2 (dn.d1) dn), dn the computed unit normal of T.  T is in no rest
+    //   box: its rmax >= reflective_T >= un1, the box contains T's culling box, and ray 1 fails its slab test, so mollerTrumbore rejects
+    //   T (the culling lemma).  So T is in a panel p, val_p = reflective_T >= un1.  Suppose emitter e accepts (p1, d2), determinant a^.
+    //   1. By the derivation of (4) the exact solution X = p0 + t d1 of ray 1's accepted test lies in the panel's box (a union of cover
+    //      boxes, grown in-plane), t in the exact slab interval of that box, which [pmin, pmax] contains: pmin <= t <= pmax.
+    //      |t^ - t| <= c_p + r_p |t| + 2.01u |t^| and t^ > 0 give t > -c_p / (1 - r_p) >= -1.15 c_p >= -back_p.  X lies in T's own plane,
+    //      within rho_T of a point of T', which is within h_p of the panel's plane Pi_p (unit normal n^_p); the two normals differ by
+    //      at most delta_p, so dist(X, Pi_p) <= h_p + rho_p delta_p =: hX.  With Y = p0 + t^ d1: |p1 - Y| <= delta1 (the proof of (3)) and
+    //      |Y - X| = |t^ - t| |d1| <= 1.25 c_p + r_p reach_p + 2.01u 1.3 (reach_p + 1.25 c_p), reach_p = omax + the box's farthest corner
+    //      >= |t| |d1| = |X - p0|: |p1 - X| <= e1_p, their sum.
+    //   2. |dn - +-n^_p| <= delta_p: the exact unit normal of T' is within the measured distance of n^_p, the fp32 cross product within
+    //      3.5u E1 E2 of the exact one (relative 4u E1 E2 / |n| after normalising, triangles with |n| <= 1e-4 E1 E2 being left to the
+    //      rest boxes), its fp32 normalisation within 8u.  With R_p = I - 2 n^_p n^_p^T: the exact d1 - 2 (dn.d1) dn differs from R_p d1 by
+    //      2 |(eps.d1) n^ + (n^.d1) eps + (eps.d1) eps| <= 4.01 delta_p |d1| (delta_p <= 1e-3), and the five fp32 operations add less than
+    //      16u |d1|: |d2 - R_p d1| <= kappa_p |d1|, kappa_p = 4.01 delta_p + 16u <= 4.1e-3.  Hence |d2|^2 lies inside [d2min, d2max] when
+    //      1.01 d2min <= |d1|^2 <= 0.99 d2max, which (5) checks, and the lemma of (3) applies to (p1, d2).
+    //   3. a^ is the fp32 value of d2.(e2 x e1) up to its sign, within 7u E1 E2 |d2| of it; d2.(e2 x e1) is within kappa_p |d1| |e2 x e1| of
+    //      (R_p d1).(e2 x e1) = d1.W, W = R_p (e2 x e1), which the list holds up to its sign and a deviation dev; the kernel's fp32 dot
+    //      product of d1 and the rounded W_k is within 4.1u |d1| |W_k| of the exact one.  err is the largest sum of these (|d1| >= 1/2
+    //      turns 7u 1.26 E1 E2 into 17.7u E1 E2 |d1|), so (d1.W_k)^2 >= thr2 |d1|^2, thr2 >= (a0 + err)^2 with room for the three fp32
+    //      roundings of the comparison, gives |a^| >= a0.  By the proof of (3) with alpha = a0 some exact Ye = p1 + s d2, s >= 0, lies
+    //      within (eps / a0) rho'_e + 6u (E1 + E2) of e: inside B0 = the emitters' box grown by m0 = em_rho eps / a0 + em_add.
+    //   4. Reflect in Pi_p: Ye' = R_Pi(p1) + s R_p d2 lies in the reflected B0.  |R_Pi(p1) - X| <= |p1 - X| + 2 dist(X, Pi_p) <= e1_p +
+    //      2 hX and |R_p d2 - d1| = |d2 - R_p d1| <= kappa_p |d1|, with s |d2| = |Ye - p1| <= far_p + e1_p (far_p the largest distance between
+    //      a point of the panel's box and one of B0) and |d1| / |d2| <= 1.01: the point Q = p0 + (t + s) d1 of ray 1's line is within
+    //      g_p = e1_p + 2 hX + 1.01 (far_p + e1_p) kappa_p of Ye'.
+    //   5. So ray 1's exact line passes the image box -- the bounds of the reflected corners of B0, grown by g_p and by the slab test's
+    //      own rounding 8u (|l| + omax) -- at the parameter tau = t + s >= t, and [imin, imax] contains its exact interval of that box:
+    //      imin <= imax, imax >= tau >= t >= pmin, with pmin <= pmax and pmax >= t > -back_p.  None of the four alternatives of (5) holds
+    //      for p: contradiction.                                                                                                  QED
+    // Every comparison of (5) is written so that a NaN keeps the sample.  How triangles are grouped into panels and rest boxes does not
+    // enter the proof.  tests/test_level1_mirror.py restates (5) and searches for counter-examples against the oracle.
     void level1_tables() {
         Level1Cull& L = P.level1; L = Level1Cull{};
         std::vector<char> emits((size_t)sc.n_tris, 0);
@@ -957,7 +1001,9 @@ struct Packer {
         }
         L.o2max = P.cull_limits[0]; L.d2min = P.cull_limits[1]; L.d2max = P.cull_limits[2];
         L.on = 1;
-        level1_cover(emits, omax, 8.0 * u * (vmax_inf * (1.0 + 1e-6) + g1 + omax) + 1e-20);
+        const double slab_slack = 8.0 * u * (vmax_inf * (1.0 + 1e-6) + g1 + omax) + 1e-20;
+        level1_cover(emits, omax, slab_slack);
+        level1_mirror(emits, omax, vmax, vmax_inf, delta1, slab_slack);
     }
     // Condition (4)'s cover (the lemma's extension above).  Per non-emissive triangle T: the box of the kernels' triangle (v0, v0 + e1,
     // v0 + e2 with the rounded edges, and the vertices themselves) grown along axis k by rho_T s_k, s_k = sqrt(1 - n^_k^2) the largest
@@ -966,37 +1012,44 @@ struct Packer {
     // bound the work --, the others by the octant of their centre, and the pair of boxes whose union adds the least volume is merged until
     // kLevel1Boxes remain.  A box's r and c are the largest of its triangles', with room for the kernel's fp32 evaluation of the widened
     // interval: three operations, each within u of a value no larger than 1.13 |t| + c, and the 2.01u |t^|.
-    void level1_cover(const std::vector<char>& emits, double omax, double slab_slack) {
+    struct CoverBox { double lo[3], hi[3], r, c, rmin; int64_t count; int axis; int64_t cell; };
+    // the box of one triangle, as the paragraph above grows it, with its r_T, c_T and `reflective`
+    CoverBox cover_box_of(int32_t i, double omax, double slab_slack) const {
         const double u = kLemmaU, eps = kLemmaEps;
-        struct Box { double lo[3], hi[3], r, c; int64_t count; int axis; int64_t cell; };
-        auto join = [](const Box& a, const Box& b) {
-            Box o = a; o.count += b.count; o.r = std::max(a.r, b.r); o.c = std::max(a.c, b.c);
-            for (int k = 0; k < 3; ++k) { o.lo[k] = std::min(a.lo[k], b.lo[k]); o.hi[k] = std::max(a.hi[k], b.hi[k]); }
-            return o;
-        };
-        auto volume = [](const Box& a) { return (a.hi[0] - a.lo[0]) * (a.hi[1] - a.lo[1]) * (a.hi[2] - a.lo[2]); };
+        const sq_tri& t = sc.tris[i];
+        const TriNorms q = tri_norms(t);
+        const double rho = lemma_rho(q, omax);
+        double e1[3], e2[3];
+        for (int k = 0; k < 3; ++k) { e1[k] = (double)(t.v1[k] - t.v0[k]); e2[k] = (double)(t.v2[k] - t.v0[k]); }
+        const double n[3] = { e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0] };
+        const double nn = std::sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
+        CoverBox b{}; b.count = 1; b.axis = 3; b.cell = 0; b.rmin = (double)P.surfs[(size_t)i].reflective;
+        b.r = 7.0 * u * q.P / eps; b.c = 8.0 * u * (omax + q.V0) * q.E1 * q.E2 / eps;
+        for (int k = 0; k < 3; ++k) {
+            const double across = std::sqrt(n[(k + 1) % 3] * n[(k + 1) % 3] + n[(k + 2) % 3] * n[(k + 2) % 3]);
+            // (n is within 3e-16 E1 E2 of the exact normal: above the sliver limit the quotient is good to 3e-10, below it s_k = 1)
+            const double s = nn > 1e-6 * q.E1 * q.E2 ? std::min(1.0, across / nn + 1e-6) : 1.0;
+            const double pts[5] = { (double)t.v0[k], (double)t.v1[k], (double)t.v2[k], (double)t.v0[k] + e1[k], (double)t.v0[k] + e2[k] };
+            b.lo[k] = *std::min_element(pts, pts + 5) - rho * s - slab_slack;
+            b.hi[k] = *std::max_element(pts, pts + 5) + rho * s + slab_slack;
+        }
+        return b;
+    }
+    static CoverBox join(const CoverBox& a, const CoverBox& b) {
+        CoverBox o = a; o.count += b.count; o.r = std::max(a.r, b.r); o.c = std::max(a.c, b.c); o.rmin = std::min(a.rmin, b.rmin);
+        for (int k = 0; k < 3; ++k) { o.lo[k] = std::min(a.lo[k], b.lo[k]); o.hi[k] = std::max(a.hi[k], b.hi[k]); }
+        return o;
+    }
+    static double volume(const CoverBox& a) { return (a.hi[0] - a.lo[0]) * (a.hi[1] - a.lo[1]) * (a.hi[2] - a.lo[2]); }
+    float cover_rmin[kLevel1Boxes] = {};                    // the smallest `reflective` in each box of the cover, for level1_mirror
+    void level1_cover(const std::vector<char>& emits, double omax, double slab_slack) {
+        using Box = CoverBox;
         std::vector<Box> each;
         double slo[3] = { 1e300, 1e300, 1e300 }, shi[3] = { -1e300, -1e300, -1e300 };
         for (int32_t i = 0; i < sc.n_tris; ++i) {
             if (emits[(size_t)i]) continue;
-            const sq_tri& t = sc.tris[i];
-            const TriNorms q = tri_norms(t);
-            const double rho = lemma_rho(q, omax);
-            double e1[3], e2[3];
-            for (int k = 0; k < 3; ++k) { e1[k] = (double)(t.v1[k] - t.v0[k]); e2[k] = (double)(t.v2[k] - t.v0[k]); }
-            const double n[3] = { e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0] };
-            const double nn = std::sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
-            Box b{}; b.count = 1; b.axis = 3; b.cell = 0;
-            b.r = 7.0 * u * q.P / eps; b.c = 8.0 * u * (omax + q.V0) * q.E1 * q.E2 / eps;
-            for (int k = 0; k < 3; ++k) {
-                const double across = std::sqrt(n[(k + 1) % 3] * n[(k + 1) % 3] + n[(k + 2) % 3] * n[(k + 2) % 3]);
-                // (n is within 3e-16 E1 E2 of the exact normal: above the sliver limit the quotient is good to 3e-10, below it s_k = 1)
-                const double s = nn > 1e-6 * q.E1 * q.E2 ? std::min(1.0, across / nn + 1e-6) : 1.0;
-                const double pts[5] = { (double)t.v0[k], (double)t.v1[k], (double)t.v2[k], (double)t.v0[k] + e1[k], (double)t.v0[k] + e2[k] };
-                b.lo[k] = *std::min_element(pts, pts + 5) - rho * s - slab_slack;
-                b.hi[k] = *std::max_element(pts, pts + 5) + rho * s + slab_slack;
-                slo[k] = std::min(slo[k], b.lo[k]); shi[k] = std::max(shi[k], b.hi[k]);
-            }
+            const Box b = cover_box_of(i, omax, slab_slack);
+            for (int k = 0; k < 3; ++k) { slo[k] = std::min(slo[k], b.lo[k]); shi[k] = std::max(shi[k], b.hi[k]); }
             each.push_back(b);
         }
         const double extent = each.empty() ? 0.0 : std::max({ shi[0] - slo[0], shi[1] - slo[1], shi[2] - slo[2] });
@@ -1037,8 +1090,200 @@ struct Packer {
             const Box& b = boxes[j < boxes.size() ? j : 0];
             V.r[j] = f_up(b.r + 2e-6); V.c[j] = f_up(b.c * (1.0 + 1e-5) + 1e-30);
             for (int k = 0; k < 3; ++k) { V.box[j][k] = f_down(b.lo[k]); V.box[j][3 + k] = f_up(b.hi[k]); }
+            cover_rmin[j] = (float)b.rmin;                                // (a `reflective` value, exact)
         }
         P.level1_cover.assign(1, V);
+    }
+    // Condition (5)'s record (the lemma's mirror extension above), written wherever the cover is; n_panels = 0 where the condition is off.
+    // Panels: non-emissive triangles with `reflective` > 0 (one with 0 mirrors only when unit_float(n1) is 0) are grouped by (value,
+    // unit normal up to sign in steps of 1e-3, offset along it in steps of 1e-3 of the scene's extent); a group of at least two triangles
+    // with at least a thousandth of the non-emissive area is a panel when its members lie within 1e-3 of the extent of their common plane
+    // and their computed unit normals within 1e-3 of its normal.  Everything else goes to the rest boxes, one per value, merged by least
+    // added volume down to kLevel1Rest.  Any grouping is valid; this one finds the walls of a room.
+    void level1_mirror(const std::vector<char>& emits, double omax, double vmax, double vmax_inf, double delta1, double slab_slack) {
+        if (P.level1_cover.empty()) return;
+        const Level1Cull& L = P.level1;
+        const double u = kLemmaU, eps = kLemmaEps;
+        Level1Mirror M{};
+        for (int j = 0; j < kLevel1Boxes; ++j) M.rmin[j] = cover_rmin[j];
+        for (int j = 0; j < kLevel1Rest; ++j) M.rest[j][6] = -1.0f;        // (an unused rest box applies to no sample)
+        P.level1_mirror.assign(1, M);                                      // off, until everything below has succeeded
+        if (P.emitters.empty()) return;
+        double slo[3] = { 1e300, 1e300, 1e300 }, shi[3] = { -1e300, -1e300, -1e300 };
+        for (int32_t i = 0; i < sc.n_tris; ++i)
+            for (const float* v : { sc.tris[i].v0, sc.tris[i].v1, sc.tris[i].v2 })
+                for (int k = 0; k < 3; ++k) { slo[k] = std::min(slo[k], (double)v[k]); shi[k] = std::max(shi[k], (double)v[k]); }
+        const double extent = std::max({ shi[0] - slo[0], shi[1] - slo[1], shi[2] - slo[2] });
+        if (!(extent > 0.0)) return;
+        // the exact normal of the kernels' triangle, its five points, and the bound on its COMPUTED unit normal: the fp32 cross product is
+        // within 3.5u E1 E2 of n, its fp32 normalisation within 8u of the unit vector
+        struct Tri { double n[3], nn, pts[5][3], dn_err, rho; };
+        auto tri_of = [&](int32_t i) {
+            const sq_tri& t = sc.tris[i];
+            const TriNorms q = tri_norms(t);
+            Tri r{};
+            double e1[3], e2[3];
+            for (int k = 0; k < 3; ++k) {
+                e1[k] = (double)(t.v1[k] - t.v0[k]); e2[k] = (double)(t.v2[k] - t.v0[k]);
+                r.pts[0][k] = t.v0[k]; r.pts[1][k] = t.v1[k]; r.pts[2][k] = t.v2[k]; r.pts[3][k] = (double)t.v0[k] + e1[k]; r.pts[4][k] = (double)t.v0[k] + e2[k];
+            }
+            const double n[3] = { e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0] };
+            r.nn = std::sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
+            const bool ok = r.nn > 1e-4 * q.E1 * q.E2;
+            int big = 0;
+            for (int k = 1; k < 3; ++k) if (std::fabs(n[k]) > std::fabs(n[big])) big = k;
+            for (int k = 0; k < 3; ++k) r.n[k] = ok ? n[k] / r.nn * (n[big] < 0 ? -1.0 : 1.0) : 0.0;
+            r.dn_err = ok ? 4.0 * u * q.E1 * q.E2 / r.nn + 8.0 * u : 1.0;
+            r.rho = lemma_rho(q, omax);
+            return r;
+        };
+        std::map<std::array<int64_t, 5>, std::vector<int32_t>> groups;
+        std::vector<int32_t> rest;
+        double area_all = 0.0;
+        for (int32_t i = 0; i < sc.n_tris; ++i) {
+            if (emits[(size_t)i]) continue;
+            const Tri t = tri_of(i);
+            area_all += t.nn;
+            const float val = P.surfs[(size_t)i].reflective;
+            if (!(val > 0.0f) || t.dn_err >= 1.0) { rest.push_back(i); continue; }
+            uint32_t vb; std::memcpy(&vb, &val, 4);
+            const double d = t.n[0] * t.pts[0][0] + t.n[1] * t.pts[0][1] + t.n[2] * t.pts[0][2];
+            groups[{ (int64_t)vb, (int64_t)std::floor(t.n[0] * 1e3 + 0.5), (int64_t)std::floor(t.n[1] * 1e3 + 0.5), (int64_t)std::floor(t.n[2] * 1e3 + 0.5),
+                     (int64_t)std::floor(d / (1e-3 * extent) + 0.5) }].push_back(i);
+        }
+        struct Panel { std::vector<int32_t> tris; double n[3], d, h, delta, rho; float val; };
+        std::vector<Panel> panels;
+        for (auto& [key, members] : groups) {
+            Panel p{}; p.val = P.surfs[(size_t)members[0]].reflective;
+            double area = 0.0, lo = 1e300, hi = -1e300;
+            for (int32_t i : members) { const Tri t = tri_of(i); area += t.nn; for (int k = 0; k < 3; ++k) p.n[k] += t.nn * t.n[k]; }
+            const double len = std::sqrt(p.n[0] * p.n[0] + p.n[1] * p.n[1] + p.n[2] * p.n[2]);
+            bool ok = members.size() >= 2 && area >= 1e-3 * area_all && len > 0.5 * area;
+            if (ok) {
+                for (int k = 0; k < 3; ++k) p.n[k] /= len;
+                for (int32_t i : members) {
+                    const Tri t = tri_of(i);
+                    for (const auto& x : t.pts) { const double s = p.n[0] * x[0] + p.n[1] * x[1] + p.n[2] * x[2]; lo = std::min(lo, s); hi = std::max(hi, s); }
+                    const double dv[3] = { t.n[0] - p.n[0], t.n[1] - p.n[1], t.n[2] - p.n[2] };
+                    p.delta = std::max(p.delta, std::sqrt(dv[0] * dv[0] + dv[1] * dv[1] + dv[2] * dv[2]) + t.dn_err + 1e-12);
+                    p.rho = std::max(p.rho, t.rho);
+                }
+                p.d = 0.5 * (lo + hi); p.h = 0.5 * (hi - lo) + 1e-12 * (vmax + 1.0);
+                ok = p.delta <= 1e-3 && p.h <= 1e-3 * extent;
+            }
+            if (ok) { p.tris = members; panels.push_back(std::move(p)); }
+            else rest.insert(rest.end(), members.begin(), members.end());
+        }
+        if (panels.empty() || panels.size() > (size_t)kLevel1Panels) return;
+        // the determinant floor and the emitters' margin at it: the floor that makes the margin 2e-3 of the emitters' extent
+        double em_ext = std::max({ L.em_hi[0] - L.em_lo[0], L.em_hi[1] - L.em_lo[1], L.em_hi[2] - L.em_lo[2] });
+        if (!(em_ext > 0.0)) em_ext = extent;
+        const double a0 = std::max(eps, L.em_rho * eps / (2e-3 * em_ext)), m0 = L.em_rho * (eps / a0) + L.em_add;
+        // W and err
+        struct Wk { double w[3], len; };
+        std::vector<Wk> ws;
+        double err = 0.0;
+        for (const Panel& p : panels) {
+            const double kappa = 4.01 * p.delta + 16.0 * u;
+            for (int32_t e : P.emitters) {
+                const sq_tri& t = sc.tris[e];
+                const TriNorms q = tri_norms(t);
+                double e1[3], e2[3];
+                for (int k = 0; k < 3; ++k) { e1[k] = (double)(t.v1[k] - t.v0[k]); e2[k] = (double)(t.v2[k] - t.v0[k]); }
+                const double nE[3] = { e2[1] * e1[2] - e2[2] * e1[1], e2[2] * e1[0] - e2[0] * e1[2], e2[0] * e1[1] - e2[1] * e1[0] };
+                const double f = 2.0 * (p.n[0] * nE[0] + p.n[1] * nE[1] + p.n[2] * nE[2]);
+                const double W[3] = { nE[0] - f * p.n[0], nE[1] - f * p.n[1], nE[2] - f * p.n[2] };
+                const double nEl = std::sqrt(nE[0] * nE[0] + nE[1] * nE[1] + nE[2] * nE[2]);
+                double dev = INFINITY; size_t at = ws.size();
+                for (size_t k = 0; k < ws.size(); ++k) {
+                    double dp = 0.0, dm = 0.0;
+                    for (int c = 0; c < 3; ++c) { dp += (W[c] - ws[k].w[c]) * (W[c] - ws[k].w[c]); dm += (W[c] + ws[k].w[c]) * (W[c] + ws[k].w[c]); }
+                    const double dk = std::sqrt(std::min(dp, dm));
+                    if (dk <= 1e-4 * ws[k].len && dk < dev) { dev = dk; at = k; }
+                }
+                if (at == ws.size()) {
+                    Wk w{};
+                    for (int c = 0; c < 3; ++c) { w.w[c] = (double)(float)W[c]; w.len += w.w[c] * w.w[c]; }   // as the kernel will read it
+                    w.len = std::sqrt(w.len);
+                    dev = 2.0 * u * (nEl + w.len);
+                    ws.push_back(w);
+                }
+                err = std::max(err, 4.1 * u * ws[at].len + dev + kappa * nEl * 1.0001 + 17.7 * u * q.E1 * q.E2 + 1e-30);
+            }
+        }
+        if (ws.size() > (size_t)kLevel1W) return;
+        // the boxes
+        const double B_lo[3] = { L.em_lo[0] - m0, L.em_lo[1] - m0, L.em_lo[2] - m0 }, B_hi[3] = { L.em_hi[0] + m0, L.em_hi[1] + m0, L.em_hi[2] + m0 };
+        bool finite_all = std::isfinite(a0) && std::isfinite(m0) && std::isfinite(err);
+        for (size_t j = 0; j < panels.size(); ++j) {
+            const Panel& p = panels[j];
+            CoverBox b = cover_box_of(p.tris[0], omax, slab_slack);
+            for (size_t i = 1; i < p.tris.size(); ++i) b = join(b, cover_box_of(p.tris[i], omax, slab_slack));
+            double corner = 0.0, far2 = 0.0;
+            for (int k = 0; k < 3; ++k) {
+                const double c = std::max(std::fabs(b.lo[k]), std::fabs(b.hi[k])), f = std::max(std::fabs(b.hi[k] - B_lo[k]), std::fabs(B_hi[k] - b.lo[k]));
+                corner += c * c; far2 += f * f;
+            }
+            const double reach = omax + std::sqrt(corner);
+            const double e1 = delta1 + 1.25 * b.c + b.r * reach + 2.01 * u * 1.3 * (reach + 1.25 * b.c);
+            const double hX = p.h + p.rho * p.delta, kappa = 4.01 * p.delta + 16.0 * u;
+            const double g = (e1 + 2.0 * hX + 1.01 * (std::sqrt(far2) + e1) * kappa) * (1.0 + 1e-9) + 1e-9 * (vmax + 1.0);
+            double ilo[3] = { 1e300, 1e300, 1e300 }, ihi[3] = { -1e300, -1e300, -1e300 }, big = 0.0;
+            for (int corner_i = 0; corner_i < 8; ++corner_i) {
+                double x[3];
+                for (int k = 0; k < 3; ++k) x[k] = (corner_i >> k & 1) ? B_hi[k] : B_lo[k];
+                const double s = 2.0 * (p.n[0] * x[0] + p.n[1] * x[1] + p.n[2] * x[2] - p.d);
+                for (int k = 0; k < 3; ++k) { const double y = x[k] - s * p.n[k]; ilo[k] = std::min(ilo[k], y); ihi[k] = std::max(ihi[k], y); }
+            }
+            for (int k = 0; k < 3; ++k) { ilo[k] -= g; ihi[k] += g; big = std::max({ big, std::fabs(ilo[k]), std::fabs(ihi[k]) }); }
+            const double slack = 8.0 * u * (big + omax) * 1.001 + 1e-20;
+            float* o = M.panel[j];
+            for (int k = 0; k < 3; ++k) {
+                o[k] = f_down(b.lo[k]); o[3 + k] = f_up(b.hi[k]); o[6 + k] = f_down(ilo[k] - slack); o[9 + k] = f_up(ihi[k] + slack);
+                finite_all = finite_all && std::isfinite(o[k]) && std::isfinite(o[3 + k]) && std::isfinite(o[6 + k]) && std::isfinite(o[9 + k]);
+            }
+            o[12] = f_up(1.15 * b.c * (1.0 + 1e-5) + 1e-30); o[13] = p.val;
+            finite_all = finite_all && std::isfinite(o[12]) && big <= 1048576.0;
+        }
+        // rest boxes: culling boxes (as the mirror classes') of everything non-emissive outside the panels, per value
+        std::vector<CoverBox> rb;                                          // (rmin holds the LARGEST value here)
+        for (int32_t i : rest) {
+            const sq_tri& t = sc.tris[i];
+            double m = lemma_rho(tri_norms(t), omax);
+            m += 8.0 * u * (vmax_inf + m + omax) + 1e-20;
+            CoverBox b{}; b.count = 1; b.rmin = (double)P.surfs[(size_t)i].reflective;
+            for (int k = 0; k < 3; ++k) {
+                b.lo[k] = std::min({ (double)t.v0[k], (double)t.v1[k], (double)t.v2[k] }) - m; b.hi[k] = std::max({ (double)t.v0[k], (double)t.v1[k], (double)t.v2[k] }) + m;
+            }
+            size_t at = 0;
+            while (at < rb.size() && rb[at].rmin != b.rmin) ++at;
+            if (at == rb.size()) rb.push_back(b); else { const double v = b.rmin; rb[at] = join(rb[at], b); rb[at].rmin = v; }
+        }
+        while (rb.size() > (size_t)kLevel1Rest) {
+            size_t bi = 0, bj = 1; double best = INFINITY;
+            for (size_t i = 0; i < rb.size(); ++i)
+                for (size_t j = i + 1; j < rb.size(); ++j) {
+                    const double grow = volume(join(rb[i], rb[j])) - volume(rb[i]) - volume(rb[j]);
+                    if (grow < best) { best = grow; bi = i; bj = j; }
+                }
+            const double v = std::max(rb[bi].rmin, rb[bj].rmin);
+            rb[bi] = join(rb[bi], rb[bj]); rb[bi].rmin = v;
+            rb.erase(rb.begin() + (std::ptrdiff_t)bj);
+        }
+        for (size_t j = 0; j < (size_t)kLevel1Rest && !rb.empty(); ++j) {
+            const CoverBox& b = rb[j < rb.size() ? j : 0];
+            for (int k = 0; k < 3; ++k) { M.rest[j][k] = f_down(b.lo[k]); M.rest[j][3 + k] = f_up(b.hi[k]); }
+            M.rest[j][6] = (float)b.rmin;
+        }
+        if (!finite_all) return;
+        for (size_t j = panels.size(); j < (size_t)kLevel1Panels; ++j) std::memcpy(M.panel[j], M.panel[0], sizeof M.panel[0]);
+        for (size_t k = 0; k < (size_t)kLevel1W; ++k)
+            for (int c = 0; c < 3; ++c) M.w[k][c] = (float)ws[k < ws.size() ? k : 0].w[c];
+        M.n_panels = (int32_t)panels.size(); M.n_rest = (int32_t)rb.size(); M.n_w = (int32_t)ws.size();
+        M.thr2 = f_up((a0 + err) * (a0 + err) * (1.0 + 1e-5));
+        M.d2lo = f_up((double)L.d2min * 1.01); M.d2hi = f_down((double)L.d2max * 0.99);
+        M.a0 = f_up(a0); M.m0 = f_up(m0);
+        P.level1_mirror.assign(1, M);
     }
     void geometry_flags() {                                 // v_min / v_max slabs need NaN-free planes
         bool fin = finite3(sc.root.lo) && finite3(sc.root.hi);
@@ -1080,6 +1325,7 @@ extern "C" int sq_packed_array(const sq_packed* P, const char* name, const void*
     is("branches", P->branches); is("leaves", P->leaves); is("tris", P->tris); is("tri_mat", P->tri_mat); is("surfs", P->surfs);
     is("mats", P->mats); is("verts4", P->verts4); is("trix", P->trix); is("rbranch", P->rbranch); is("emitters", P->emitters);
     is("cull_child", P->cull_child); is("cull_child16", P->cull_child16); is("branches_m", P->branches_m); is("level1_cover", P->level1_cover);
+    is("level1_mirror", P->level1_mirror);
     if (!found && !std::strcmp(name, "level1")) { found = true; *data = &P->level1; *bytes = sizeof P->level1; }
     return found ? 0 : sq_set_error("no packed array '%s'", name);
 }

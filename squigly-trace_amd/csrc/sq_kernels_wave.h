@@ -155,7 +155,11 @@ __device__ __forceinline__ bool halfplane_misses_box(f3 p0, f3 d1, f3 nd, const 
 #ifndef SQ_LEVEL1_COVER
 #define SQ_LEVEL1_COVER 1               // 0: an experimental build without the cover (the stretch alone)
 #endif
-__device__ __forceinline__ bool stretch_misses_cover(f3 p0, f3 d1, f3 nd, const double* lo, const double* hi, double m, const uint4* cover) {
+#ifndef SQ_LEVEL1_MIRROR
+#define SQ_LEVEL1_MIRROR 1              // experimental builds: 0 without condition (5), 2 with its panels' image boxes alone
+#endif
+// lim: only the boxes that hold a triangle with `reflective` < lim count (condition 5 asks for the ones that scatter under n1; +inf: all).
+__device__ __forceinline__ bool stretch_misses_cover(f3 p0, f3 d1, f3 nd, const double* lo, const double* hi, double m, const uint4* cover, float lim) {
     const double px[3] = { p0.x, p0.y, p0.z }, dx[3] = { d1.x, d1.y, d1.z }, nx[3] = { nd.x, nd.y, nd.z };
     double g[3], h[3], scale = 0.0;
 #pragma unroll
@@ -205,13 +209,69 @@ __device__ __forceinline__ bool stretch_misses_cover(f3 p0, f3 d1, f3 nd, const 
         const float tmax = vmin3(vmax(t1, t2), vmax(t3, t4), vmax(t5, t6));
         // X's parameter t lies in [tmin, tmax]; the computed t^ within r |t| + c of it
         const float tlo = (tmin - rj * __builtin_fabsf(tmin)) - cj, thi = (tmax + rj * __builtin_fabsf(tmax)) + cj;
-        may_end |= vmax(tlo, ta32) <= vmin(thi, tb32);                  // ray 1 may end on a triangle of this box, at a point of the stretch
+        // ray 1 may end on a triangle of this box, at a point of the stretch (Level1Mirror::rmin lies 8 floats behind the cover's end)
+        may_end |= vmax(tlo, ta32) <= vmin(thi, tb32) && (!SQ_LEVEL1_MIRROR || V[sizeof(Level1Cover) / 4 + 8 + j] < lim);
     }
     return !may_end;
 }
+// Ray 1's fp32 slab interval of the box b = lo.xyz, hi.xyz in constant memory, with the operations of cull_slab.
+__device__ __forceinline__ void slab_interval(const __attribute__((address_space(4))) float* b, f3 df, f3 nodf, float& tmin, float& tmax) {
+    const float t1 = __builtin_fmaf(b[0], df.x, nodf.x), t2 = __builtin_fmaf(b[3], df.x, nodf.x);
+    const float t3 = __builtin_fmaf(b[1], df.y, nodf.y), t4 = __builtin_fmaf(b[4], df.y, nodf.y);
+    const float t5 = __builtin_fmaf(b[2], df.z, nodf.z), t6 = __builtin_fmaf(b[5], df.z, nodf.z);
+    tmin = vmax3(vmin(t1, t2), vmin(t3, t4), vmin(t5, t6));
+    tmax = vmin3(vmax(t1, t2), vmax(t3, t4), vmax(t5, t6));
+}
+// Condition (5) of the lemma, its geometric half, for a sample whose ray 1 passes the box of its mirror class: no triangle that mirrors
+// under n1 can send ray 2 to an emitter.  Ray 1 misses every rest box that holds such a triangle; its direction keeps every mirrored
+// determinant above the floor; and for no panel of such triangles does ray 1, continued straight through the panel, reach the image of
+// the emitters' box behind it.  M: the Level1Mirror record; df, nodf, dd: 1 / d1, -p0 / d1 and |d1|^2 as condition (2) formed them.
+// Every comparison is written so that a NaN keeps the sample.
+__device__ __forceinline__ bool mirror_cannot_reach(const __attribute__((address_space(4))) float* M, f3 d1, f3 df, f3 nodf, float dd, float un1) {
+    const __attribute__((address_space(4))) int32_t* Mi = (const __attribute__((address_space(4))) int32_t*)M;
+    const int n_panels = Mi[0], n_w = Mi[2];
+    if (n_panels == 0) return false;
+    bool keep = !(dd >= M[4] && dd <= M[5]);
+    const __attribute__((address_space(4))) float* rest = M + 8 + kLevel1Boxes + 4 * kLevel1W;
+#pragma unroll
+    for (int j = 0; j < kLevel1Rest; ++j) {
+        float tmin, tmax;
+        slab_interval(rest + 8 * j, df, nodf, tmin, tmax);
+        keep |= rest[8 * j + 6] >= un1 && !(tmax <= 0 || tmin >= tmax);  // (cull_slab's `tmax > 0 && tmin < tmax`, a NaN keeping the sample)
+    }
+    const float floor2 = M[3] * dd;
+    for (int k = 0; k < n_w; ++k) {                                     // (wave-uniform: scene.obj has one)
+        const __attribute__((address_space(4))) float* w = M + 8 + kLevel1Boxes + 4 * k;
+        const float a = sq::dot(d1, sq::mk(w[0], w[1], w[2]));
+        keep |= !(a * a >= floor2);
+    }
+    const __attribute__((address_space(4))) float* panels = rest + 8 * kLevel1Rest;
+    // three panels at a time, without a branch among them (the packer fills unused entries with copies of the first); the groups in a
+    // wave-uniform loop of its own, so that a scene with nine panels pays for nine
+#pragma unroll 1
+    for (int j0 = 0; j0 < n_panels; j0 += 3) {
+        {
+#pragma unroll
+            for (int j = j0; j < j0 + 3; ++j) {
+                const __attribute__((address_space(4))) float* b = panels + 16 * j;
+                float pmin, pmax, imin, imax;
+                slab_interval(b + 6, df, nodf, imin, imax);
+#if SQ_LEVEL1_MIRROR == 2
+                const bool cannot = imax < imin || imax <= -b[12];      // (the image box alone: tau >= t > -back)
+#else
+                slab_interval(b, df, nodf, pmin, pmax);
+                // ray 1 cannot end on the panel, or its line passes the image box nowhere, or only before it can reach the panel
+                const bool cannot = pmax < pmin || pmax <= -b[12] || imax < imin || imax < pmin;
+#endif
+                keep |= b[13] >= un1 && !cannot;
+            }
+        }
+    }
+    return !keep;
+}
 // May the scattered ray 1 = (p0, d1) of a sample whose generator goes on with n1, n2 be dropped, the sample finished as a
-// first-bounce miss?  1: by conditions (1)-(3) of the lemma, 2: by (1), (2) and (4), 0: no; p0_ok: |p0|^2 is inside the lemma's
-// limit (per pixel).
+// first-bounce miss?  1: by conditions (1)-(3) of the lemma, 2: by (1), (2) and (4), 3: by (5) in the place of (2), 0: no; p0_ok:
+// |p0|^2 is inside the lemma's limit (per pixel).
 __device__ __forceinline__ int level1_culled(const SceneView& S, const Level1Cull& C, bool p0_ok, f3 p0, f3 d1, uint32_t n1, uint32_t n2) {
     const float eps = 0.0001f, inf = __builtin_inff();
     // ray 1 inside the limits of sq_cull_boxes (as trav_begin decides Trav::cull)
@@ -230,7 +290,13 @@ __device__ __forceinline__ int level1_culled(const SceneView& S, const Level1Cul
             for (int k = 0; k < 6; ++k) b[k] = C.class_box[c][k];
         }
     }
-    if (has && cull_slab(b, df, nodf)) return false;
+    bool mirror5 = false;                                               // (2) fails and (5) stands in for it
+    if (has && cull_slab(b, df, nodf)) {
+        if (!SQ_LEVEL1_MIRROR || !SQ_LEVEL1_COVER || S.rtail == nullptr) return 0;
+        const __attribute__((address_space(4))) float* M = (const __attribute__((address_space(4))) float*)S.rtail + sizeof(Level1Cover) / 4;
+        if (!mirror_cannot_reach(M, d1, df, nodf, dd, un1)) return 0;
+        mirror5 = true;
+    }
     // the direction of ray 2 up to its sign
     const f3 nd = random_vector(n1, n2);
     const float nn = sq::dot(nd, nd);
@@ -245,12 +311,18 @@ __device__ __forceinline__ int level1_culled(const SceneView& S, const Level1Cul
         const float a = sq::dot(e1, sq::cross(nd, e2));                 // moller_trumbore's `a` for (any origin, nd); -nd gives -a
         if (!(a > -eps && a < eps)) amin = sq::hmin(amin, __builtin_fabsf(a));
     }
-    if (amin == inf) return 1;                                          // every emitter rejects +-nd by its determinant alone
+    if (amin == inf) return mirror5 ? 3 : 1;                            // every emitter rejects +-nd by its determinant alone
     if (!(amin < inf)) return 0;
-    // (3), and (4) where it does not decide
+    // (3), and (4) where it does not decide; under (5) they answer for the triangles that scatter under n1 alone
     const double m = C.em_rho * ((double)eps / (double)amin) + C.em_add;
-    if (halfplane_misses_box(p0, d1, nd, C.em_lo, C.em_hi, m)) return 1;
-    return stretch_misses_cover(p0, d1, nd, C.em_lo, C.em_hi, m, S.rtail) ? 2 : 0;
+    // (the box is the scene's: seen as such, its centre and half extents are formed once per kernel and kept in binary64 across the
+    // sample loop, twelve registers of which some spill; the empty asm has them formed here)
+    double elo[3], ehi[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { elo[k] = C.em_lo[k]; ehi[k] = C.em_hi[k]; asm volatile("" : "+s"(elo[k]), "+s"(ehi[k])); }
+    if (halfplane_misses_box(p0, d1, nd, elo, ehi, m)) return mirror5 ? 3 : 1;
+    if (!stretch_misses_cover(p0, d1, nd, elo, ehi, m, S.rtail, mirror5 ? sq::unit_float(n1) : inf)) return 0;
+    return mirror5 ? 3 : 2;
 }
 
 // Depth-0 bounce of every sample of the batch: RNG, bounceRay, ray 1 into slot sid (src/Lib.hs:133-134).
@@ -264,7 +336,7 @@ __device__ __forceinline__ int level1_culled(const SceneView& S, const Level1Cul
 template <int SRC, typename FrameT>
 __device__ __forceinline__ void gen_bounce1_body(const SceneView& S, const FrameT& F, const Work& W, int k_base, int k_count, const RngView R, const Level1Cull& C) {
     const int A = *W.n_active;
-    unsigned int n_culled = 0, n_culled4 = 0;                           // by conditions (1)-(3), and by (4) where (3) did not decide
+    unsigned int n_culled = 0, n_culled4 = 0, n_culled5 = 0;            // by conditions (1)-(3), by (4) where (3) did not decide, by (5) alone
     diag_aux_wave(W, F.diag, true);
     const int n_runs = (k_count + kRngRun - 1) / kRngRun, runs_per_y = (n_runs + (int)gridDim.y - 1) / (int)gridDim.y;
     const int g_begin = min(n_runs, (int)blockIdx.y * runs_per_y), g_end = min(n_runs, g_begin + runs_per_y);
@@ -307,7 +379,7 @@ __device__ __forceinline__ void gen_bounce1_body(const SceneView& S, const Frame
                 // Level-1 culling: nothing ray 1 can hit changes the sample's radiance, which is that of a first-bounce miss
                 if (C.on) {
                     const int why = level1_culled(S, C, p0_ok, P.p0, d1, n1, n2);
-                    if (why) { finish_level1(W, sid, -1); n_culled += why == 1; n_culled4 += why == 2; continue; }
+                    if (why) { finish_level1(W, sid, -1); n_culled += why == 1; n_culled4 += why == 2; n_culled5 += why == 3; continue; }
                 }
                 W.state[sid] = kRay1;
                 W.org[sid] = make_float4(P.p0.x, P.p0.y, P.p0.z, __uint_as_float(n1));
@@ -317,13 +389,14 @@ __device__ __forceinline__ void gen_bounce1_body(const SceneView& S, const Frame
     }
     if (C.on) {                                                         // rays culled, one atomic per wave (the loop above has ended for all its lanes)
 #pragma unroll
-        for (int o = 32; o > 0; o >>= 1) { n_culled += __shfl_xor(n_culled, o); n_culled4 += __shfl_xor(n_culled4, o); }
+        for (int o = 32; o > 0; o >>= 1) { n_culled += __shfl_xor(n_culled, o); n_culled4 += __shfl_xor(n_culled4, o); n_culled5 += __shfl_xor(n_culled5, o); }
         if ((threadIdx.x & 63) == 0 && n_culled) atomicAdd(&W.stats[kStatLevel1Culled], (unsigned long long)n_culled);
         if ((threadIdx.x & 63) == 0 && n_culled4) atomicAdd(&W.stats[kStatLevel1Stretch], (unsigned long long)n_culled4);
+        if ((threadIdx.x & 63) == 0 && n_culled5) atomicAdd(&W.stats[kStatLevel1Mirror], (unsigned long long)n_culled5);
     }
     diag_aux_wave(W, F.diag, false);
 }
-// Four waves per SIMD (118 VGPRs, no scratch): with the level-1 culling test inlined, six (80 VGPRs) spill 38 registers and five
+// Four waves per SIMD (126 VGPRs with condition (5), no scratch): with the level-1 culling test inlined, six (80 VGPRs) spill 38 registers and five
 // (96) spill 22; the headline frame measured 43.2 / 42.1 / 41.7 ms at six / five / four
 constexpr int kGen1Waves = 4;
 template <int SRC>

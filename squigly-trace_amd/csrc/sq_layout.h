@@ -58,5 +58,24 @@ struct Level1Cover {
     float box[kLevel1Boxes][6];              // lo.xyz, hi.xyz
 };
 static_assert(sizeof(Level1Cover) == 272, "the cover is seventeen 16-byte quads");
+// Condition 5 (sq_host.cpp, "Level-1 culling", the mirror extension): for a sample whose ray 1 passes the box of its mirror class, what
+// a MIRRORED ray 2 can reach.  A panel is a set of non-emissive triangles of one `reflective` value `val` close to one plane: `box` holds
+// the exact point in which an accepted ray 1 meets the plane of one of them (a cover box), `image` the emitters' grown box reflected in
+// the panel's plane, and a ray 1 that ends on the panel at a computed t^ > 0 has its exact parameter t > -back.  A rest box is a culling
+// box of mirroring triangles outside every panel, the largest `reflective` among them rmax.  rmin[j]: the smallest `reflective` in box j
+// of the cover.  w: at most kLevel1W vectors with | |a^| - |d1.w| | <= err |d1| for the determinant a^ of every (mirrored ray 2,
+// emitter); thr2 >= (a0 + err)^2.  One record directly behind the cover (SceneView::rtail + 1 cover), read wave-uniformly.
+constexpr int kLevel1Panels = 12, kLevel1Rest = 4, kLevel1W = 8;
+struct Level1Mirror {
+    int32_t n_panels, n_rest, n_w;           // n_panels = 0: the condition is off for the scene.  Entries beyond a count repeat the first
+    float thr2;                              // the determinant floor: every (d1.w_k)^2 >= thr2 |d1|^2, or the sample is kept
+    float d2lo, d2hi;                        // |d1|^2 inside these keeps the mirrored |d2|^2 inside Level1Cull's d2min, d2max
+    float a0, m0;                            // the floor itself and the emitters' margin at it (what `image` was built with)
+    float rmin[kLevel1Boxes];
+    float w[kLevel1W][4];                    // xyz, unused
+    float rest[kLevel1Rest][8];              // lo.xyz, hi.xyz, rmax, unused
+    float panel[kLevel1Panels][16];          // box lo.xyz hi.xyz | image lo.xyz hi.xyz | back, val, unused x 2
+};
+static_assert(sizeof(Level1Mirror) == 1088, "the mirror record is sixty-eight 16-byte quads");
 constexpr int kTriRunPad = 3;   // zero triangles after the last one, so that a run of loads may start at any triangle (GlobalTris::kRunPad)
 }  // namespace sqd

@@ -32,6 +32,7 @@ struct PackedScene {
     float cull_limits[3] = { -1.0f, 0.25f, 1.5624f };   // SceneView::cull_o2max, cull_d2min, cull_d2max
     sqd::Level1Cull level1{};                       // the first-bounce reduction's tables; level1.on = its preconditions hold
     std::vector<sqd::Level1Cover> level1_cover;     // one record where level1.on (SceneView::rtail), else empty
+    std::vector<sqd::Level1Mirror> level1_mirror;   // one record wherever level1_cover has one, behind it on the device
     bool level1_zero = false;                      // s.surf * 0 + s.emit is bitwise (+0, +0, +0) for every triangle outside `emitters`
     bool small_index = false;                       // < 0x8000 branches and triangles: 2-byte stack words
 };

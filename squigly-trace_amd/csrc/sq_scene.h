@@ -50,7 +50,7 @@ struct SceneView {
     // skips the leaf's triangles -- mollerTrumbore would reject them all.  cull_o2max < 0: nothing is culled.
     float cull_o2max, cull_d2min, cull_d2max;
     const float4* cull_child; // streaming form: 4 quads per branch, the culling boxes (lo, hi) of its left and of its right child; or nullptr
-    const uint4* rtail;       // level-1 culling's cover of the geometry: one Level1Cover record (sq_layout.h), read by sq_gen_bounce1 alone; or nullptr
+    const uint4* rtail;       // level-1 culling's cover of the geometry and its mirror record: one Level1Cover, then one Level1Mirror (sq_layout.h), read by sq_gen_bounce1 alone; or nullptr
     const uint4* cull_child16; // 2 quads per branch, the same boxes as binary16 pairs (x, y, z, unused), left child then right; or nullptr
     const float4* branches_m;  // streaming form: the 48-byte branch record and the 32 bytes of its children's binary16 culling boxes as ONE
                                //   packed record of 5 quads (HybridNodes): a visit touches 1.5 lines on average instead of 2.3

@@ -405,8 +405,9 @@ class DeviceScene(Owner):
         return ms.value, n.value, (name.value or b"").decode()
 
     def stats(self, reset=False):
-        """Cumulative trace-kernel statistics: [rays traced, profile counters...] (synchronises); slots 28 and 29 = the first-bounce
-        rays that level-1 culling (option "level1_cull") did not queue: by its conditions (1)-(3), and by condition (4) alone."""
+        """Cumulative trace-kernel statistics: [rays traced, profile counters...] (synchronises); slots 28, 29 and 30 = the
+        first-bounce rays that level-1 culling (option "level1_cull") did not queue: by its conditions (1)-(3), by condition (4) alone and by
+        condition (5) alone."""
         out = (C.c_uint64 * 32)()
         N.check(N.lib().sq_get_stats(self._h, out, 32, int(reset)))
         return [int(v) for v in out]
