@@ -143,6 +143,7 @@ def case(seed):
     c.deep = int(rng.integers(0, 2))
     c.cast_wavefront = int(rng.integers(0, 2))
     c.slots = int(rng.choice([DEFAULT_SLOTS, c.w * c.h + 17]))          # the small one: samples and lights run in several batches
+    c.knobs["level1_cull"] = int(rng.integers(0, 2))                    # the last draw of this step: the ones before it stay what they were
     return c
 
 

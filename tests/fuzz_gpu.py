@@ -46,6 +46,14 @@ def room(r):
     return q
 
 
+def lattice(rng, k):
+    """A random subset, in random order, of the 3 k^3 unit right triangles on the faces of the cells of a k^3 grid centred on the origin."""
+    g = np.stack(np.meshgrid(np.arange(k), np.arange(k), np.arange(k), indexing="ij"), -1).reshape(-1, 1, 3).astype(np.float64)
+    offs = np.array([[[0, 0, 0], [1, 0, 0], [0, 1, 0]], [[0, 0, 0], [0, 1, 0], [0, 0, 1]], [[0, 0, 0], [0, 0, 1], [1, 0, 0]]], np.float64)
+    v = (g[:, None] + offs[None]).reshape(-1, 3, 3) - k / 2
+    return v[rng.permutation(len(v))[: int(rng.integers(1, len(v) + 1))]]
+
+
 def make_scene(rng, kinds=12, big=False):
     kind = rng.integers(0, kinds)            # `kinds` < 10 replays seeds found before the later kinds were added
     scale = float(rng.choice([1e-3, 1.0, 1.0, 1.0, 50.0, 1e4]))
@@ -54,11 +62,7 @@ def make_scene(rng, kinds=12, big=False):
         c = rng.uniform(-2, 2, (n, 1, 3))
         v = c + rng.normal(0, float(rng.choice([0.02, 0.3, 1.5])), (n, 3, 3))
     elif kind == 1:    # lattice: exact ties everywhere (centroids, planes, edges, coplanar faces)
-        k = int(rng.integers(2, 7))
-        g = np.stack(np.meshgrid(np.arange(k), np.arange(k), np.arange(k), indexing="ij"), -1).reshape(-1, 1, 3).astype(np.float64)
-        offs = np.array([[[0, 0, 0], [1, 0, 0], [0, 1, 0]], [[0, 0, 0], [0, 1, 0], [0, 0, 1]], [[0, 0, 0], [0, 0, 1], [1, 0, 0]]], np.float64)
-        v = (g[:, None] + offs[None]).reshape(-1, 3, 3) - k / 2
-        v = v[rng.permutation(len(v))[: int(rng.integers(1, len(v) + 1))]]
+        v = lattice(rng, int(rng.integers(2, 7)))
     elif kind == 2:    # duplicated and overlapping triangles (dist ties, COMBINE frames)
         n = int(rng.integers(1, 60))
         base = rng.uniform(-1.5, 1.5, (n, 3, 3))

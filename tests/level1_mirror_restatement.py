@@ -36,32 +36,40 @@ def mirror(sqt, holder):
         L.sq_packed_free(h)
 
 
-def mirror_cannot_reach(M, p0, d1, un1):
-    """The kernel's geometric half of condition (5); every comparison as the kernel writes it (a NaN keeps the sample)."""
+def mirror_cannot_reach(M, p0, d1, un1, why=None):
+    """The kernel's geometric half of condition (5); every comparison as the kernel writes it (a NaN keeps the sample).
+    why = a dict: it receives, per row, which of the four tests keep the sample -- "dd" (|d1|^2 outside its limits), "rest" (a rest box),
+    "floor" (a mirrored determinant below the floor), "panel" (a panel whose image can be reached) -- and "tail", the number of panel
+    entries beyond n_panels the kernel evaluates with its last group of three."""
     n = len(p0)
     if M is None or int(M["n_panels"]) == 0:
         return np.zeros(n, bool)
+    by = {k: np.zeros(n, bool) for k in ("dd", "rest", "floor", "panel")}
+    n_read = 3 * ((int(M["n_panels"]) + 2) // 3)                            # the kernel takes them three at a time
     with np.errstate(all="ignore"):
         dd = R.dot32(d1, d1)
-        keep = ~((dd >= M["d2lo"]) & (dd <= M["d2hi"]))
+        by["dd"] = ~((dd >= M["d2lo"]) & (dd <= M["d2hi"]))
         for j in range(REST):
             tmin, tmax = S.slab_interval(M["rest"][j][:6], p0, d1)
-            keep |= (M["rest"][j][6] >= un1) & ~((tmax <= 0) | (tmin >= tmax))
+            by["rest"] |= (M["rest"][j][6] >= un1) & ~((tmax <= 0) | (tmin >= tmax))
         floor2 = M["thr2"] * dd
         for k in range(int(M["n_w"])):
             a = R.dot32(d1, np.broadcast_to(M["w"][k][:3], d1.shape))
-            keep |= ~(a * a >= floor2)
-        for j in range(3 * ((int(M["n_panels"]) + 2) // 3)):                # the kernel takes them three at a time
+            by["floor"] |= ~(a * a >= floor2)
+        for j in range(n_read):
             b = M["panel"][j]
             pmin, pmax = S.slab_interval(b[0:6], p0, d1)
             imin, imax = S.slab_interval(b[6:12], p0, d1)
             cannot = (pmax < pmin) | (pmax <= -b[12]) | (imax < imin) | (imax < pmin)
-            keep |= (b[13] >= un1) & ~cannot
-    return ~keep
+            by["panel"] |= (b[13] >= un1) & ~cannot
+    if why is not None:
+        why.update(by, tail=n_read - int(M["n_panels"]))
+    return ~(by["dd"] | by["rest"] | by["floor"] | by["panel"])
 
 
-def stretch_misses_cover(V, M, p0, d1, nd, lo, hi, m, lim):
-    """Condition (4) restricted to the boxes of the cover whose smallest `reflective` is below lim (per row)."""
+def stretch_misses_cover(V, M, p0, d1, nd, lo, hi, m, lim, why=None):
+    """Condition (4) restricted to the boxes of the cover whose smallest `reflective` is below lim (per row).  why = a dict: it
+    receives the two alternatives per row, "empty" (no stretch) and "may_end" (ray 1 may end in a box, at a point of the stretch)."""
     ta, tb = S.stretch(p0, d1, nd, lo, hi, m)
     empty = ta > tb
     with np.errstate(all="ignore"):
@@ -74,12 +82,19 @@ def stretch_misses_cover(V, M, p0, d1, nd, lo, hi, m, lim):
             tlo = (tmin - V["r"][j] * np.abs(tmin)) - V["c"][j]
             thi = (tmax + V["r"][j] * np.abs(tmax)) + V["c"][j]
             may_end |= (np.fmax(tlo, ta32) <= np.fmin(thi, tb32)) & (M["rmin"][j] < lim)
+    if why is not None:
+        why.update(empty=empty, may_end=may_end)
     return empty | ~may_end
 
 
-def culled(T, V, M, em, p0, d1, un1, nd):
-    """(culled by (1)-(3), by (4) alone, by (5) alone) for scattered first-bounce rays; the three masks are disjoint."""
-    old, new4 = S.culled(T, V, em, p0, d1, un1, nd)
+def culled(T, V, M, em, p0, d1, un1, nd, why=None):
+    """(culled by (1)-(3), by (4) alone, by (5) alone) for scattered first-bounce rays; the three masks are disjoint.
+    why = a dict: it receives "four" (level1_stretch_restatement.culled's report), "mirror" = (rows mirror_cannot_reach judged, its
+    report) and "four_under_five" = (rows, stretch_misses_cover's report), each only where that test ran."""
+    four = {}
+    old, new4 = S.culled(T, V, em, p0, d1, un1, nd, why=four)
+    if why is not None:
+        why["four"] = four
     new5 = np.zeros(len(p0), bool)
     if not T["on"] or V is None or M is None:
         return old, new4, new5
@@ -92,21 +107,28 @@ def culled(T, V, M, em, p0, d1, un1, nd):
     cand = R.ray_in_limits(T, p0, d1) & c1 & ~R.condition2(T, p0, d1, un1) & (nn >= T["d2min"]) & (nn <= T["d2max"])
     sel = np.flatnonzero(cand)
     if len(sel):
-        cand[sel] = mirror_cannot_reach(M, p0[sel], d1[sel], un1[sel])
+        by = {}
+        cand[sel] = mirror_cannot_reach(M, p0[sel], d1[sel], un1[sel], why=by)
+        if why is not None and by:
+            why["mirror"] = (sel, by)
     new5 = cand & np.isinf(amin)
     sel = np.flatnonzero(cand & np.isfinite(amin))
     if len(sel):
+        by = {}
         half = R.halfplane_misses_box(p0[sel], d1[sel], nd[sel], T["em_lo"], T["em_hi"], m[sel])
-        new5[sel] = half | stretch_misses_cover(V, M, p0[sel], d1[sel], nd[sel], T["em_lo"], T["em_hi"], m[sel], un1[sel])
+        new5[sel] = half | stretch_misses_cover(V, M, p0[sel], d1[sel], nd[sel], T["em_lo"], T["em_hi"], m[sel], un1[sel], why=by)
+        if why is not None:
+            by["half"] = half
+            why["four_under_five"] = (sel, by)
     assert not (new5 & (old | new4)).any()
     return old, new4, new5
 
 
-def frame_prediction(sqt, T, V, M, ob, flat, cam, spp, w, h):
-    """(first-bounce rays, masks culled by (1)-(3), by (4) alone, by (5) alone) of a frame."""
+def frame_prediction(sqt, T, V, M, ob, flat, cam, spp, w, h, why=None):
+    """(first-bounce rays, masks culled by (1)-(3), by (4) alone, by (5) alone) of a frame; why: as `culled` fills it."""
     fb = R.frame_first_bounces(ob, flat, cam, spp, w, h)
     nd = R.random_vectors(fb["n1"], fb["n2"])
-    return (fb,) + culled(T, V, M, R.emitters_of(flat), fb["p0"], fb["d1"], R.unit_float(fb["n1"]), nd)
+    return (fb,) + culled(T, V, M, R.emitters_of(flat), fb["p0"], fb["d1"], R.unit_float(fb["n1"]), nd, why=why)
 
 
 def quad(origin, ex, ey):

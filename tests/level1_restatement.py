@@ -167,8 +167,9 @@ def frame_first_bounces(ob, flat, cam, spp, w, h):
                 if signum(dot(d, nrm)) == signum(dot(nd, nrm)):
                     nd = -nd
                 rows.append((y, x, k, p0, nd, words[1], words[2]))
-    cols = list(zip(*rows))
-    return {"y": np.array(cols[0]), "x": np.array(cols[1]), "k": np.array(cols[2]), "p0": np.array(cols[3], f32), "d1": np.array(cols[4], f32),
+    cols = list(zip(*rows)) or [()] * 7                                  # no first-bounce ray: empty arrays of the same dtypes and ranks
+    return {"y": np.array(cols[0], np.int64), "x": np.array(cols[1], np.int64), "k": np.array(cols[2], np.int64),
+            "p0": np.array(cols[3], f32).reshape(-1, 3), "d1": np.array(cols[4], f32).reshape(-1, 3),
             "n1": np.array(cols[5], np.uint32), "n2": np.array(cols[6], np.uint32)}
 
 

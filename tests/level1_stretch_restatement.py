@@ -70,10 +70,14 @@ def slab_interval(box, o, d):
     return np.minimum(tl, th).max(1), np.maximum(tl, th).min(1)
 
 
-def stretch_misses_cover(V, p0, d1, nd, lo, hi, m, use_cover=True):
-    """The kernel's condition (4).  V: the cover record or None; use_cover = False: the stretch alone (part (a) of the condition)."""
+def stretch_misses_cover(V, p0, d1, nd, lo, hi, m, use_cover=True, why=None):
+    """The kernel's condition (4).  V: the cover record or None; use_cover = False: the stretch alone (part (a) of the condition).
+    why = a dict: it receives the two alternatives per row, "empty" (no stretch) and "may_end" (ray 1 may end in a box of the cover, at
+    a point of the stretch)."""
     ta, tb = stretch(p0, d1, nd, lo, hi, m)
     empty = ta > tb
+    if why is not None:
+        why.update(empty=empty, may_end=np.ones(len(p0), bool))
     if V is None or not use_cover or int(V["n"]) == 0:
         return empty
     with np.errstate(all="ignore"):
@@ -86,12 +90,15 @@ def stretch_misses_cover(V, p0, d1, nd, lo, hi, m, use_cover=True):
             tlo = (tmin - V["r"][j] * np.abs(tmin)) - V["c"][j]
             thi = (tmax + V["r"][j] * np.abs(tmax)) + V["c"][j]
             may_end |= np.fmax(tlo, ta32) <= np.fmin(thi, tb32)          # v_max_f32 / v_min_f32 return the other operand for a NaN
+    if why is not None:
+        why.update(may_end=may_end)
     return empty | ~may_end
 
 
-def culled(T, V, em, p0, d1, un1, nd, use_cover=True):
+def culled(T, V, em, p0, d1, un1, nd, use_cover=True, why=None):
     """(culled by conditions (1)-(3), culled by (1), (2) and (4) alone) for scattered first-bounce rays, as level1_restatement.culled
-    takes them.  The two masks are disjoint: the kernel evaluates (4) only where (3) keeps the sample."""
+    takes them.  The two masks are disjoint: the kernel evaluates (4) only where (3) keeps the sample.  why = a dict: it receives "rows"
+    (the rows (4) judged) and stretch_misses_cover's report for them."""
     old = R.culled(T, em, p0, d1, un1, nd)
     if not T["on"]:
         return old, np.zeros(len(p0), bool)
@@ -105,7 +112,9 @@ def culled(T, V, em, p0, d1, un1, nd, use_cover=True):
     new = np.zeros(len(p0), bool)
     sel = np.flatnonzero(reach4)
     if len(sel):
-        new[sel] = stretch_misses_cover(V, p0[sel], d1[sel], nd[sel], T["em_lo"], T["em_hi"], m[sel], use_cover)
+        new[sel] = stretch_misses_cover(V, p0[sel], d1[sel], nd[sel], T["em_lo"], T["em_hi"], m[sel], use_cover, why=why)
+        if why is not None:
+            why["rows"] = sel
     return old, new
 
 

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 import fuzz_features as FF
+import level1_restatement
 from scenes import pack
 
 SEEDS = range(1000, 1400)
@@ -49,6 +50,8 @@ def table(sqt, O):
         _, _, _, lit = FF.cast_frame(c, FF.light_pairs(c.lights))
         r.lights_seen = bool(((lit == 1).any(0) & (lit == 0).any(0)).all())
         r.height = FF.product_bih(c).height
+        # the plan turns level-1 culling on for the three-level pipeline alone: with deep = 0, the depth-3 queries of the case run it
+        r.level1_knob = c.knobs["level1_cull"] if level1_restatement.tables(sqt, FF.product_bih(c))[1]["level1_on"] and not c.deep else None
         out.append(r)
     return out
 
@@ -80,6 +83,10 @@ COVERAGE = (
     ("at most 16 triangles", lambda r: r.tris <= 16, 20),
     ("every drawn light lights and shadows a hit pixel", lambda r: r.lights_seen, 50),
 )
+
+
+def test_level_1_culling_is_drawn_on_and_off_among_the_cases_whose_plan_turns_it_on(table):
+    assert {r.level1_knob for r in table} >= {0, 1}, [r.level1_knob for r in table].count(None)
 
 
 @pytest.mark.parametrize("what, fact, least", COVERAGE, ids=[c[0] for c in COVERAGE])

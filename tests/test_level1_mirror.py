@@ -12,10 +12,10 @@ import numpy as np
 import pytest
 
 import level1_mirror_restatement as M5
+import level1_rays as LR
 import level1_restatement as R
 import level1_stretch_restatement as S
-from depth_restatement import cross, dot
-from kernel_restatements import mt_accepts
+from level1_rays import uncovered
 
 sqt = importlib.import_module("squigly-trace_amd")
 DATA = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "data")
@@ -26,30 +26,9 @@ def bih_of(tris, mats):
     return sqt.BIH(sqt.Mesh.from_arrays(tris, mats))
 
 
-def emissive_of(ot):
-    return np.array([(f32(t["emissive"]) * t["emit"].astype(f32)).astype(f32).view(np.uint32).any() for t in ot])
-
-
 def scene_obj():
     import pyoracle as O
     return O.tris_from_obj(os.path.join(DATA, "scene.obj"), DATA), sqt.BIH(sqt.Mesh.from_obj(os.path.join(DATA, "scene.obj"), DATA))
-
-
-def holds(box, ot, sel):
-    """Per selected triangle: are its three vertices inside box (lo.xyz, hi.xyz)?"""
-    return np.all([((ot[f][sel] >= box[:3]) & (ot[f][sel] <= box[3:6])).all(1) for f in ("a", "b", "c")], 0)
-
-
-def uncovered(M, ot):
-    """The non-emissive triangles that lie neither in a panel of their own `reflective` value nor in a rest box that answers for it."""
-    dark = np.flatnonzero(~emissive_of(ot))
-    ok = np.zeros(len(dark), bool)
-    val = ot["reflective"][dark].astype(f32)
-    for j in range(int(M["n_panels"])):
-        ok |= (val == M["panel"][j][13]) & holds(M["panel"][j][:6], ot, dark)
-    for j in range(int(M["n_rest"])):
-        ok |= (val <= M["rest"][j][6]) & holds(M["rest"][j][:6], ot, dark)
-    return dark[~ok]
 
 
 def parallel_mirrors(n):
@@ -94,80 +73,12 @@ def test_every_mirroring_triangle_lies_in_a_panel_or_a_rest_box_and_the_count_li
                 assert M["n_panels"] == 0 and not new5.any(), (count, n)
 
 
-def mirror_dir(d, t):
-    """reflectRay of the oracle (src/Lib.hs:176-181) in float32, as tests/depth_restatement.py walks it."""
-    nrm = cross((t["b"] + -t["a"]).astype(f32), (t["c"] + -t["a"]).astype(f32))
-    dn = (nrm / f32(np.sqrt(dot(nrm, nrm)))).astype(f32)
-    return (d + -(f32(f32(2) * dot(dn, d)) * dn).astype(f32)).astype(f32)
-
-
-def unit(v):
-    return v / np.maximum(np.linalg.norm(v, axis=1), 1e-300)[:, None]
-
-
-def points_on(rng, ot, k):
-    """A point of each triangle k: inside it, on an edge or on a corner."""
-    a, b, c = (ot[f][k].astype(np.float64) for f in ("a", "b", "c"))
-    w = rng.dirichlet([1, 1, 1], len(k))
-    kind = rng.integers(0, 3, len(k))
-    w[kind == 1, 2] = 0; w[kind == 2, 1:] = 0
-    w /= w.sum(1)[:, None]
-    return w[:, :1] * a + w[:, 1:2] * b + w[:, 2:] * c
-
-
-def normals(ot, k):
-    n = np.cross(ot["b"][k].astype(np.float64) - ot["a"][k], ot["c"][k].astype(np.float64) - ot["a"][k])
-    return unit(n)
-
-
-def rays_ending_on_mirrors(rng, ot, mirrors, n, omax):
-    """Ray 1 through a point of a mirroring triangle -- inside, on an edge, on a corner --, any direction."""
-    k = rng.choice(mirrors, n)
-    p1 = points_on(rng, ot, k)
-    d1 = unit(rng.normal(0, 1, (n, 3))).astype(f32)
-    t = (10.0 ** rng.uniform(-3, np.log10(0.4 * omax), n))[:, None]
-    return (p1 - t * d1).astype(f32), d1
-
-
-def rays_mirrored_at_emitter_edges(rng, ot, mirrors, em, n, omax):
-    """Ray 1 whose mirror image in the plane of a mirroring triangle, taken from a point of it, passes just inside or outside an edge or
-    corner of an emitter."""
-    k = rng.choice(mirrors, n)
-    p1, nh = points_on(rng, ot, k), normals(ot, k)
-    e = np.array([[v.astype(np.float64) for v in t] for t in em])[rng.integers(0, len(em), n)]
-    ek = rng.integers(0, 3, n)
-    va, vb = e[np.arange(n), ek], e[np.arange(n), (ek + 1) % 3]
-    tgt = va + (rng.random(n) * (rng.random(n) < 0.7))[:, None] * (vb - va)
-    out = unit(tgt - e.mean(1))
-    tgt = tgt + (10.0 ** rng.uniform(-9, -1, n) * rng.choice([-1.0, 1.0], n))[:, None] * out
-    d2 = unit(tgt - p1)
-    d1 = (d2 - 2 * (d2 * nh).sum(1)[:, None] * nh).astype(f32)
-    t = (10.0 ** rng.uniform(-3, np.log10(0.4 * omax), n))[:, None]
-    return (p1 - t * d1).astype(f32), d1
-
-
-def rays_at_the_determinant_floor(rng, ot, mirrors, M, n, omax):
-    """Ray 1 through a point of a mirroring triangle whose |d1 . W| / |d1| lies within a few parts in a thousand of the floor, either side."""
-    k = rng.choice(mirrors, n)
-    p1 = points_on(rng, ot, k)
-    W = M["w"][rng.integers(0, int(M["n_w"]), n), :3].astype(np.float64)
-    wl = np.linalg.norm(W, axis=1)
-    c = np.sqrt(float(M["thr2"])) / wl * (1 + rng.uniform(-3e-3, 3e-3, n)) * rng.choice([-1.0, 1.0], n)
-    side = rng.normal(0, 1, (n, 3)); side = unit(side - (side * W).sum(1)[:, None] * W / (wl * wl)[:, None])
-    d1 = (c[:, None] * W / wl[:, None] + np.sqrt(np.maximum(1 - c * c, 0))[:, None] * side).astype(f32)
-    t = (10.0 ** rng.uniform(-3, np.log10(0.4 * omax), n))[:, None]
-    return (p1 - t * d1).astype(f32), d1
-
-
-def uniform_rays(rng, n, vmax):
-    return (rng.uniform(-vmax, vmax, (n, 3)) / np.sqrt(3)).astype(f32), unit(rng.normal(0, 1, (n, 3))).astype(f32)
-
-
 @pytest.mark.parametrize("name", ["scene.obj", "axis_soup", "tilted_soup"])
 def test_no_sample_condition_5_culls_reaches_an_emitter(name):
     """Counter-example search.  For every ray 1 condition (5) culls no emitter accepts ray 1, the oracle's traversal returns a miss or
     a non-emissive triangle, and no emitter's mollerTrumbore accepts the ray 2 the oracle forms from the hit point it computes: the
-    mirrored direction where the triangle mirrors under n1, +-nd where it scatters.  Both sides must be populated."""
+    mirrored direction where the triangle mirrors under n1, +-nd where it scatters (tests/level1_rays.py, search).  Both sides must be
+    populated."""
     import pyoracle as O
     rng = np.random.default_rng(20261020)
     if name == "scene.obj":
@@ -178,47 +89,9 @@ def test_no_sample_condition_5_culls_reaches_an_emitter(name):
     T, s = R.tables(sqt, bih)
     V, M = S.cover(sqt, bih), M5.mirror(sqt, bih)
     assert s["level1_on"] == 1 and M["n_panels"] > 0
-    em = R.emitters_of(ot)
     ob = O.BIH(ot)
-    flat = ob.flatten()
-    emissive = emissive_of(flat)
-    mirrors = np.flatnonzero(~emissive_of(ot) & (ot["reflective"] > 0))
-    top = float(ot["reflective"][mirrors].max())
-    omax = float(np.sqrt(T["o2max"]))
-    n = 12000
-    n_new5 = n_panel_hits = n_kept_accepted = n_floor_kept = 0
-    for which, (p0, d1) in (("ends", rays_ending_on_mirrors(rng, ot, mirrors, n, omax)), ("edges", rays_mirrored_at_emitter_edges(rng, ot, mirrors, em, n, omax)),
-                            ("floor", rays_at_the_determinant_floor(rng, ot, mirrors, M, n, omax)), ("uniform", uniform_rays(rng, n, omax / 2))):
-        un1 = (rng.random(n) * top * 1.2).astype(f32)
-        nd = unit(rng.normal(0, 1, (n, 3))).astype(f32)
-        old, new4, new5 = M5.culled(T, V, M, em, p0, d1, un1, nd)
-        n_new5 += int(new5.sum())
-        kept = np.flatnonzero(~old & ~new4 & ~new5)
-        if which == "floor":
-            n_floor_kept += len(kept)
-        for i in np.concatenate([np.flatnonzero(new5), kept[:500]]):
-            if new5[i]:
-                for v0, v1, v2 in em:                                    # condition (1)
-                    assert not mt_accepts(p0[i:i + 1], d1[i:i + 1], v0[None], v1[None], v2[None])[0][0], (name, which, int(i))
-            hit = ob.intersect(p0[i], d1[i])
-            if not hit.hit:
-                continue
-            t = flat[hit.tri]
-            if new5[i]:
-                assert not emissive[hit.tri], (name, which, int(i))
-            if emissive[hit.tri]:
-                continue
-            p1 = np.array([[hit.point.x, hit.point.y, hit.point.z]], f32)
-            mirrors_here = not (t["reflective"] < un1[i])
-            dirs = [mirror_dir(d1[i], t)] if mirrors_here else [nd[i], -nd[i]]
-            n_panel_hits += int(new5[i] and mirrors_here)
-            for d2 in dirs:
-                for v0, v1, v2 in em:
-                    acc, _ = mt_accepts(p1, d2[None], v0[None], v1[None], v2[None])
-                    if new5[i]:
-                        assert not acc[0], (name, which, int(i), p0[i], d1[i], un1[i], nd[i])
-                    else:
-                        n_kept_accepted += int(acc[0] and mirrors_here)
+    got = LR.search(rng, name, ot, ob, ob.flatten(), T, V, M, n=12000)
+    n, n_new5, n_panel_hits, n_kept_accepted, n_floor_kept = 12000, got["new5"], got["panel_hits"], got["kept_accepted"], got["floor_kept"]
     print(f"{name}: {n_new5} culled by (5) alone, {n_panel_hits} of them end on a triangle that mirrors; {n_kept_accepted} kept rays whose mirrored "
           f"ray 2 an emitter accepts; {n_floor_kept} of {n} rays at the determinant floor kept")
     assert n_panel_hits >= 200 and n_kept_accepted >= 20 and 0 < n_floor_kept < n, (n_new5, n_panel_hits, n_kept_accepted, n_floor_kept)
