@@ -417,7 +417,7 @@ int  sq_get_stats(sq_device_scene* s, uint64_t* out, int32_t n, int32_t reset);
  *                        changes; 0: every leaf the reference visits is tested
  *   "level1_cull"        1 (default): a path-traced frame or query at depth 3 does not queue the scattered first-bounce ray of a
  *                        sample that provably ends with the radiance of a first-bounce miss (no emitter on the ray, no mirroring
- *                        surface on it, no emitter within reach of the second bounce: csrc/sq_host.cpp, level1_tables) -- no bit
+ *                        surface on it, no emitter within reach of the second bounce: csrc/sq_pack_level1.h, build_level1) -- no bit
  *                        changes; 0: every such ray is traced.  sq_get_stats slots 28 to 30 count the rays dropped, sq_last_plan says
  *                        whether the frame used it
  *   "primary_tiles"      1 (default): the primary rays of a shard are enumerated in tiles (8 x 8 pixels on a whole image, 2 x 32 with

@@ -57,7 +57,7 @@ void sq_bih_free(sq_bih* b);
  * of scene->nodes (lo.xyz, hi.xyz; a branch gets the union of its children).  A ray with ray_limits[1] <= |d|^2 <=
  * ray_limits[2], |o|^2 <= ray_limits[0] and finite o, d, 1/d, o/d that FAILS the fp32 slab test of a node's box is
  * rejected by the reference's mollerTrumbore (src/Geometry.hs:117-142) for every triangle of that node, so the node
- * returns Nothing (src/BIH.hs:105-109) without testing them.  The error analysis is in csrc/sq_host.cpp; leaves it does
+ * returns Nothing (src/BIH.hs:105-109) without testing them.  The error analysis is in csrc/sq_cull_lemma.h; leaves it does
  * not cover get an infinite box, and ray_limits[0] < 0 says no ray may be culled.  The scene packer below calls this. */
 int  sq_cull_boxes(const sq_scene* scene, float* boxes, float ray_limits[3]);
 /* The binary16 encoding the resident kernels keep such a box in: the nearest value >= x (up != 0) or <= x, never subnormal. */

@@ -16,7 +16,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libsquigly_hip.so")
 SOURCES = ["sq_device.hip", "sq_bih_device.hip", "sq_host.cpp"]
-HEADERS = ["sq_math.h", "sq_error.h", "sq_scene.h", "sq_layout.h", "sq_pack.h", "sq_plan.h", "sq_host_types.h", "sq_frame.h", "sq_kernels_lane.h", "sq_kernels_wave.h", "sq_kernels_trace.h", "cli_main.cpp", "../../include/squigly_hip.h", "../../include/squigly_host.h"]
+HEADERS = ["sq_math.h", "sq_error.h", "sq_scene.h", "sq_layout.h", "sq_pack.h", "sq_plan.h", "sq_host_types.h", "sq_cull_lemma.h", "sq_pack_level1.h", "sq_pack_scene.h", "sq_plan_call.h", "sq_frame.h", "sq_kernels_lane.h", "sq_kernels_wave.h", "sq_kernels_trace.h", "cli_main.cpp", "../../include/squigly_hip.h", "../../include/squigly_host.h"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
          "-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt", "-fno-fast-math",
          # v_pk_mul_f32 / v_pk_add_f32 issue at ~9.5 cycles per wave on gfx950 against ~2.6 for the scalar forms

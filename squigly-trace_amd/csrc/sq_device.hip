@@ -53,7 +53,7 @@
 constexpr int kOneshotRowBlock = 2; // rows per block when a one-shot call shards a frame over devices (balance: squigly-trace_amd/dist.py)
 
 // ----------------------------------------------------------------------------------------------
-// Host: scene upload (validation and packing: sq_host.cpp, sq_pack.h)
+// Host: scene upload (validation and packing: sq_pack_scene.h, sq_pack.h)
 // ----------------------------------------------------------------------------------------------
 // A filled table of generator words: entries [0, cover) (RngView), kRngPad bytes of padding behind them.  Nothing writes to a block
 // once it is filled, so a scene that adopts one only has to be ordered after `filled`, the event recorded behind the fill.
@@ -412,7 +412,7 @@ int with_ad_sky(bool ad, bool sky, const SkyT& k, Fn&& fn) {
     return with_ad<CAN_AD>(ad, [&](auto AD) { return sky ? fn(AD, k) : fn(AD); });
 }
 
-// What the planner (sq_plan.h, sq_host.cpp) reads of a scene for `call`: its packed scalars, options, device and state.
+// What the planner (sq_plan.h, sq_plan_call.h) reads of a scene for `call`: its packed scalars, options, device and state.
 PlanInputs plan_inputs(const sq_device_scene* s, const Call& call, int stack_word) {
     PlanInputs in;
     const SceneView& v = s->view;
@@ -647,7 +647,7 @@ int launch_frame(sq_device_scene* s, const FrameOf<SRC>& F, hipStream_t stream, 
     // The steps of batch i, each on the stream `on` and over the batch's track Wt[i & 1]; the schedules below say only which stream a
     // step goes on and which events order it.
     auto launched = []() -> int { SQ_HIP(hipGetLastError()); return 0; };
-    // Level-1 culling (sq_host.cpp, level1_tables): where the plan says so
+    // Level-1 culling (sq_pack_level1.h, build_level1): where the plan says so
     Level1Cull L1 = s->level1;
     L1.on = C.level1_cull;
     auto gen = [&](int i, hipStream_t on) -> int {
@@ -1166,7 +1166,7 @@ extern "C" int sq_get_stats(sq_device_scene* s, uint64_t* out, int32_t n, int32_
 }
 extern "C" int sq_set_option(sq_device_scene* s, const char* key, int64_t value) {
     if (!s || !key) return sq_set_error("null argument");
-    if (set_option(s->opt, key, value)) return 1;                       // names, ranges and messages: the option table (sq_host.cpp)
+    if (set_option(s->opt, key, value)) return 1;                       // names, ranges and messages: the option table (sq_plan_call.h)
     // "aux_low_priority" takes effect when the second stream is created (first overlapped frame)
     if (!std::strcmp(key, "aux_low_priority") && s->aux) { (void)hipStreamSynchronize(s->aux); (void)hipStreamDestroy(s->aux); s->aux = nullptr; }
     return 0;

@@ -131,7 +131,7 @@ __global__ void __launch_bounds__(kBlock) sq_rng_fill(uint32_t* words, long long
     }
 }
 
-// Level-1 culling (sq_host.cpp, level1_tables, has the lemma): does the half-plane { p0 + t d1 + s nd : t >= 0, s real } provably
+// Level-1 culling (sq_pack_level1.h, build_level1, has the lemma): does the half-plane { p0 + t d1 + s nd : t >= 0, s real } provably
 // miss the box [lo - m, hi + m]?  Binary64 on the exact fp32 values; either separation must hold by more than 1e-9 of the scale.
 __device__ __forceinline__ bool halfplane_misses_box(f3 p0, f3 d1, f3 nd, const double* lo, const double* hi, double m) {
     const double px[3] = { p0.x, p0.y, p0.z }, dx[3] = { d1.x, d1.y, d1.z }, nx[3] = { nd.x, nd.y, nd.z };

@@ -1,5 +1,5 @@
 // sq_layout.h — the records and bit positions of the device-resident scene, free of any HIP include: what the host packer
-// (sq_host.cpp, sq_pack.h) writes and the kernels (sq_scene.h) read.  Citations are relative to the reference repository root.
+// (sq_pack_scene.h, sq_pack.h) writes and the kernels (sq_scene.h) read.  Citations are relative to the reference repository root.
 #pragma once
 #include <stdint.h>
 namespace sqd {
@@ -36,7 +36,7 @@ constexpr uint32_t kAxisMask = 3u << kAxisShift;               //   the LEFT wor
 // (5 of scene.obj's 1278 children).  The packer still sets them (the removed incremental slab test read them);
 // every reader masks them off.
 constexpr uint32_t kGrownLeft = 1u, kGrownRight = 2u;
-// The first-bounce reduction (sq_host.cpp, "Level-1 culling"; read by sq_gen_bounce1 alone, as a kernel argument of its own):
+// The first-bounce reduction (sq_pack_level1.h, "Level-1 culling"; read by sq_gen_bounce1 alone, as a kernel argument of its own):
 // a scattered ray 1 whose sample provably ends with the radiance of a first-bounce miss is never queued.
 constexpr int kLevel1Classes = 4;
 struct Level1Cull {
@@ -48,7 +48,7 @@ struct Level1Cull {
     double em_lo[3], em_hi[3];               // bounding box of the emissive triangles' vertices
     double em_rho, em_add;                   // its margin for a ray 2 whose smallest accepted |determinant| is a: em_rho * (eps / a) + em_add
 };
-// The cover of the geometry ray 1 can end on (sq_host.cpp, "Level-1 culling", condition 4): at most kLevel1Boxes boxes that together
+// The cover of the geometry ray 1 can end on (sq_pack_level1.h, "Level-1 culling", condition 4): at most kLevel1Boxes boxes that together
 // hold the exact point X in which an accepted ray 1 meets the plane of its triangle; the computed parameter t^ of the hit lies within
 // r |t| + c of X's parameter t.  One record in device memory behind SceneView::rtail, read by sq_gen_bounce1 alone, wave-uniformly.
 constexpr int kLevel1Boxes = 8;
@@ -58,7 +58,7 @@ struct Level1Cover {
     float box[kLevel1Boxes][6];              // lo.xyz, hi.xyz
 };
 static_assert(sizeof(Level1Cover) == 272, "the cover is seventeen 16-byte quads");
-// Condition 5 (sq_host.cpp, "Level-1 culling", the mirror extension): for a sample whose ray 1 passes the box of its mirror class, what
+// Condition 5 (sq_pack_level1.h, "Level-1 culling", the mirror extension): for a sample whose ray 1 passes the box of its mirror class, what
 // a MIRRORED ray 2 can reach.  A panel is a set of non-emissive triangles of one `reflective` value `val` close to one plane: `box` holds
 // the exact point in which an accepted ray 1 meets the plane of one of them (a cover box), `image` the emitters' grown box reflected in
 // the panel's plane, and a ray 1 that ends on the panel at a computed t^ > 0 has its exact parameter t > -back.  A rest box is a culling

@@ -1,4 +1,4 @@
-// sq_pack.h — the scene packer (sq_host.cpp): everything sq_scene_upload decides and lays out before it touches a device.
+// sq_pack.h — the scene packer (sq_pack_scene.h): everything sq_scene_upload decides and lays out before it touches a device.
 // Plain host C++, no HIP include, so it runs, is tested (tests/test_pack.py) and is sanitized on a CPU.
 #pragma once
 #include <cstdint>

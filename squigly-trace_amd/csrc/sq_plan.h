@@ -1,6 +1,6 @@
 // sq_plan.h — what a render or query call decides before it touches the device, free of any HIP include: the options, the planner's
 // inputs, the plan of a call (plan_call), the schedule for the slots its workspace got (plan_schedule) and the workspace's layout.
-// The planner itself is plain host C++ (sq_host.cpp): it runs, is tested (tests/test_plan.py, through sq_plan_call) and is sanitized on
+// The planner itself is plain host C++ (sq_plan_call.h): it runs, is tested (tests/test_plan.py, through sq_plan_call) and is sanitized on
 // a CPU.  sq_device.hip reads every size, grid and threshold from here; the trace kernels share trace_lds_layout with the host.
 #pragma once
 #include <stddef.h>
@@ -61,7 +61,7 @@ inline long long primary_padded_lanes(int local_rows, int tile_rows, int tiles_x
     return (long long)((local_rows + tile_rows - 1) / tile_rows) * tiles_x * 64;
 }
 
-// ---- options (sq_set_option; the table of names, ranges and messages is sq_host.cpp's kOptionTable) ----
+// ---- options (sq_set_option; the table of names, ranges and messages is sq_plan_call.h's kOptionTable) ----
 constexpr int64_t kRngTableDefaultMb = 24576;   // option "rng_table_mb": 24 GiB = 2^31 seeds (squigly_hip.h)
 struct Options {
     int64_t timing = 0, variant = 2, slots = 512ll << 20, straggler_lanes = 8, resident = 1, profile = 0, lds_node_kb = 32,

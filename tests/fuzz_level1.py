@@ -1,4 +1,4 @@
-"""Randomised parity campaign for level-1 culling (sq_gen_bounce1, level1_culled; the packer's level1_tables, level1_cover and
+"""Randomised parity campaign for level-1 culling (sq_gen_bounce1, level1_culled; the packer's build_level1, level1_cover and
 level1_mirror): random scenes with mirrors, random cameras inside them and small frames, through every call that runs sq_gen_bounce1,
 with option "level1_cull" at 1 and at 0.  Each frame is held to the C oracle bit for bit, and sq_get_stats slots 28, 29 and 30 -- the
 rays conditions (1)-(3), condition (4) alone and condition (5) alone drop -- to the counts the three restatements predict
@@ -47,7 +47,7 @@ CULLED, STRETCH, MIRROR = 28, 29, 30                    # sq_get_stats slots
 SIDES = np.arange(4, 17)
 SIDE_WEIGHTS = np.where(SIDES >= 10, 3.0, 1.0) / np.where(SIDES >= 10, 3.0, 1.0).sum()
 ROOM_SCALES = (0.05, 0.25, 1.0)
-# The packer's bound on a triangle is P = 1.25 |e1| |e2| <= 29 (sq_host.cpp, kLemmaPmax).  A wall triangle of room(2.0) has legs 4 and
+# The packer's bound on a triangle is P = 1.25 |e1| |e2| <= 29 (sq_cull_lemma.h, kLemmaPmax).  A wall triangle of room(2.0) has legs 4 and
 # 4 sqrt 2: P = 28.284 at scale 1, 28.990 at 1.0124 and 29.019 at 1.0129 -- a part in a thousand either side, far above float32 rounding
 P_UNDER, P_OVER = 1.0124, 1.0129
 EDGES = ("P_under", "P_over", "emit63", "emit64", "emit65", "groups12", "groups13", "w8", "w9", "five_values", "refl_2", "refl_neg",
@@ -270,7 +270,7 @@ def product_bih(c):
 
 def records(c):
     """(Level1Cull record, packer scalars, Level1Cover or None, Level1Mirror or None) of the case's scene, and c.plan_on: whether the
-    plan's rule turns level-1 culling on under option level1_cull = 1 for a depth-3 path-traced call (sq_host.cpp, plan_call)."""
+    plan's rule turns level-1 culling on under option level1_cull = 1 for a depth-3 path-traced call (sq_plan_call.h, plan_call)."""
     if not hasattr(c, "_records"):
         bih = product_bih(c)
         T, s = R.tables(sqt, bih)

@@ -91,5 +91,31 @@ def main():
     print("golden fixtures written to", G)
 
 
+def level1_records(commit):
+    """tests/golden/level1_records.json: the three level-1 records and their scalars, over tests/test_pack.py's level1_scenes(), as
+    the library that is loaded packs them -- the in-tree one, built by squigly-trace_amd/build.py at `commit`.
+
+        python tests/golden/make_golden.py level1_records "<commit> (<subject>)"
+    """
+    import importlib
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    sys.path.insert(0, ROOT)
+    import test_pack as TP
+    from scenes import pack_level1
+    sqt = importlib.import_module("squigly-trace_amd")
+    scenes = TP.level1_scenes(sqt, TP.fixture_scenes(sqt, O))
+    out = {"commit": commit,
+           "how": "sq_scene_pack of that commit's libsquigly_hip.so, built with build.py's compiler and flags; arrays level1, level1_cover and "
+                  "level1_mirror as sq_packed_array gives them (an empty array: no record), scalars as sq_packed_scalar gives them. "
+                  "Scenes: tests/test_pack.py, level1_scenes().",
+           "scenes": {name: TP.digest_of(*pack_level1(sqt, f)) for name, f in sorted(scenes.items())}}
+    with open(os.path.join(G, "level1_records.json"), "w") as f:
+        json.dump(out, f, indent=1)
+    print(len(out["scenes"]), "scenes written to", os.path.join(G, "level1_records.json"))
+
+
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:2] == ["level1_records"]:
+        level1_records(sys.argv[2])
+    else:
+        main()

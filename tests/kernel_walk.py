@@ -7,7 +7,7 @@ records which kernels each case dispatched (tests/golden/kernel_walk.json); test
 to that file plus UNREACHABLE, on the CPU.
 
 A kernel is named by the demangled spelling of its instantiation up to its argument list (`short_name`): "sq_rng_fill",
-"sq_primary<unsigned int, 0, true, Sky>".  What selects the template arguments (sq_device.hip: launch_frame, intersect_rays; sq_host.cpp:
+"sq_primary<unsigned int, 0, true, Sky>".  What selects the template arguments (sq_device.hip: launch_frame, intersect_rays; sq_plan_call.h:
 plan_call): StackT by the scene's index width (data/scene.obj: 2-byte stack words; scenes.tall_u32 of it: 4-byte), SRC by the call
 (0 a camera frame, 1 render_views, 2 raytrace / raycast), AD by a masked call, Sky / DeepSky by set_sky, and the body by the variant,
 the depth, the lights and the cast_wavefront / primary_* options.  A case names those keys, its claims follow from them (`claims`

@@ -1,4 +1,4 @@
-"""Condition (5) of level-1 culling (squigly-trace_amd/csrc/sq_host.cpp, level1_tables and level1_mirror; sq_kernels_wave.h,
+"""Condition (5) of level-1 culling (squigly-trace_amd/csrc/sq_pack_level1.h, build_level1 and level1_mirror; sq_kernels_wave.h,
 mirror_cannot_reach) restated in numpy, on top of tests/level1_restatement.py and tests/level1_stretch_restatement.py.
 
 A sample whose ray 1 PASSES the box of its mirror class -- condition (2) fails -- is still culled when no triangle that mirrors under n1

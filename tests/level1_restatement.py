@@ -1,4 +1,4 @@
-"""Level-1 culling (squigly-trace_amd/csrc/sq_host.cpp, level1_tables; sq_device.hip, level1_culled) restated in numpy.
+"""Level-1 culling (squigly-trace_amd/csrc/sq_pack_level1.h, build_level1; sq_device.hip, level1_culled) restated in numpy.
 
 The tables come from the packer's window (sq_packed_array "level1"); the three conditions are evaluated as the kernel evaluates
 them: mollerTrumbore and the slab test in float32, one rounding per operation (tests/test_cull.py), the half-plane test in
@@ -215,3 +215,13 @@ def soup(seed, n_emit, n=300, reflective=(0.0, 0.1, 0.3, 0.5, 0.8, 1.0), emit=(1
     for f in ("reflective", "surf", "emissive", "emit"):
         ot[f] = mats[f][mat]
     return tris, mats, ot
+
+
+# The soups more than one file names: the counter-example searches of tests/test_level1_cull.py ("soup", "soup_big_emitters": few
+# emitters, so that their box is not the whole soup and rays aimed beside them can be culled at all) and tests/test_level1_stretch.py
+# (the other three), and the recorded level-1 records of tests/test_pack.py.
+NAMED_SOUPS = {"soup": lambda: soup(12, 1),
+               "soup_big_emitters": lambda: soup(11, 2, emitter_size=0.9, cluster=(1.2, 1.2, -1.2)),
+               "one": lambda: soup(41, 1, zoned=(1.2, -1.2, -1.2), emitter_size=0.8),
+               "two_clustered": lambda: soup(42, 2, zoned=(-1.2, -1.2, -1.2), cluster=(1.2, 1.2, -1.2), emitter_size=0.6),
+               "many_clustered": lambda: soup(43, 12, zoned=(1.2, -1.2, -1.2), cluster=(-1.0, 1.0, 1.0))}

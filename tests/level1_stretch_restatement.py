@@ -1,4 +1,4 @@
-"""Condition (4) of level-1 culling (squigly-trace_amd/csrc/sq_host.cpp, level1_tables and level1_cover; sq_kernels_wave.h,
+"""Condition (4) of level-1 culling (squigly-trace_amd/csrc/sq_pack_level1.h, build_level1 and level1_cover; sq_kernels_wave.h,
 stretch_misses_cover) restated in numpy, on top of tests/level1_restatement.py.
 
 A sample that conditions (1) and (2) pass and (3) keeps is still culled when the stretch [ta, tb] of ray 1 -- the t >= 0 from whose

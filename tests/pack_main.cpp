@@ -1,9 +1,11 @@
 // pack_main.cpp — the scene packer as a stand-alone program, for a sanitizer build of the host code (tests/test_pack.py):
 //   g++ -std=c++17 -ffp-contract=off -fsanitize=address,undefined squigly-trace_amd/csrc/sq_host.cpp tests/pack_main.cpp
-//   ./a.out data/scene.obj data
+//   ./a.out data/scene.obj data [raw scene file ...]
 // Loads the scene, builds its BIH, packs it, reads every byte of every array and every scalar through the C-ABI window
 // (include/squigly_host.h), plans a handful of calls on the packed scene through the planner's window (sq_plan_call) and frees
-// everything.  Exit status 0 and an empty stderr mean nothing was reported.
+// everything; then builds, packs, reads and frees every raw scene file the same way.  A raw scene file is two int32 (triangles,
+// materials), then the sq_tri records, then the sq_material records, loaded through sq_mesh_from_arrays.  One line of output per
+// scene.  Exit status 0 and an empty stderr mean nothing was reported.
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -14,18 +16,29 @@
 
 static int fail(const char* what) { std::fprintf(stderr, "%s: %s\n", what, sq_error_buffer()); return 1; }
 
-int main(int argc, char** argv) {
-    if (argc != 3) { std::fprintf(stderr, "usage: %s scene.obj material-directory\n", argv[0]); return 2; }
-    sq_mesh* mesh = nullptr; sq_bih* bih = nullptr; sq_packed* packed = nullptr;
-    if (sq_mesh_from_obj(argv[1], argv[2], &mesh)) return fail("sq_mesh_from_obj");
+static int mesh_from_raw_file(const char* path, sq_mesh** mesh) {
+    std::FILE* f = std::fopen(path, "rb");
+    if (!f) { std::fprintf(stderr, "cannot open %s\n", path); return 1; }
+    int32_t n[2] = { 0, 0 };
+    bool ok = std::fread(n, sizeof n, 1, f) == 1 && n[0] >= 0 && n[1] >= 0;
+    std::vector<sq_tri> tris(ok ? (size_t)n[0] : 0); std::vector<sq_material> mats(ok ? (size_t)n[1] : 0);
+    ok = ok && std::fread(tris.data(), sizeof(sq_tri), tris.size(), f) == tris.size() && std::fread(mats.data(), sizeof(sq_material), mats.size(), f) == mats.size();
+    std::fclose(f);
+    if (!ok) { std::fprintf(stderr, "%s: not a raw scene file\n", path); return 1; }
+    return sq_mesh_from_arrays(tris.data(), n[0], mats.data(), n[1], mesh) ? fail("sq_mesh_from_arrays") : 0;
+}
+
+// build, pack, read everything, plan (the first scene only), free; takes the mesh over
+static int run_scene(sq_mesh* mesh, bool plan_calls) {
+    sq_bih* bih = nullptr; sq_packed* packed = nullptr;
     if (sq_bih_build(mesh, &bih)) return fail("sq_bih_build");
     sq_scene scene;
     sq_bih_scene(bih, &scene);
     if (sq_scene_pack(&scene, &packed)) return fail("sq_scene_pack");
     const char* arrays[] = { "branches", "leaves", "tris", "tri_mat", "surfs", "mats", "verts4", "trix", "rbranch", "emitters",
-                             "cull_child", "cull_child16", "branches_m" };
+                             "cull_child", "cull_child16", "branches_m", "level1", "level1_cover", "level1_mirror" };
     const char* scalars[] = { "n_branches", "n_leaves", "height", "root_ref", "rroot", "packed_leaves", "nonneg_materials", "finite_geometry",
-                              "n_emitters", "n_verts", "cull_o2max", "cull_d2min", "cull_d2max", "small_index", "shortcut_depth" };
+                              "n_emitters", "n_verts", "cull_o2max", "cull_d2min", "cull_d2max", "small_index", "shortcut_depth", "level1_zero", "level1_on" };
     size_t total = 0; uint64_t sum = 0; int n_arrays = 0;
     for (const char* name : arrays) {
         const void* data = nullptr; size_t bytes = 0;
@@ -80,6 +93,7 @@ int main(int argc, char** argv) {
     };
     int n_planned = 0;
     for (const PlannedCall& c : calls) {
+        if (!plan_calls) break;
         std::vector<const char*> names = base_names; std::vector<int64_t> values = base_values;
         names.insert(names.end(), c.names.begin(), c.names.end()); values.insert(values.end(), c.values.begin(), c.values.end());
         sq_plan plan; std::vector<int64_t> got((size_t)n_outs, -7);
@@ -92,5 +106,18 @@ int main(int argc, char** argv) {
     }
     sq_packed_free(packed); sq_bih_free(bih); sq_mesh_free(mesh);
     std::printf("packed %d arrays, %zu bytes, planned %d calls, byte sum %llu\n", n_arrays, total, n_planned, (unsigned long long)sum);
+    return 0;
+}
+
+int main(int argc, char** argv) {
+    if (argc < 3) { std::fprintf(stderr, "usage: %s scene.obj material-directory [raw scene file ...]\n", argv[0]); return 2; }
+    sq_mesh* mesh = nullptr;
+    if (sq_mesh_from_obj(argv[1], argv[2], &mesh)) return fail("sq_mesh_from_obj");
+    if (int rc = run_scene(mesh, true)) return rc;
+    for (int i = 3; i < argc; ++i) {
+        mesh = nullptr;
+        if (int rc = mesh_from_raw_file(argv[i], &mesh)) return rc;
+        if (int rc = run_scene(mesh, false)) return rc;
+    }
     return 0;
 }

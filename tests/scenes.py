@@ -194,3 +194,26 @@ def pack(sqt, holder):
     finally:
         L.sq_packed_free(h)
     return arrays, scalars
+
+
+LEVEL1_ARRAYS = ["level1", "level1_cover", "level1_mirror"]        # younger than the recorded digests of ARRAYS and SCALARS: a golden of their own
+LEVEL1_SCALARS = ["level1_on", "level1_zero", "shortcut_depth"]
+
+
+def pack_level1(sqt, holder):
+    """pack's sibling for the level-1 records: ({name: bytes} of LEVEL1_ARRAYS, {name: int} of LEVEL1_SCALARS)."""
+    L, h = sqt.lib(), C.c_void_p()
+    sqt._native.check(L.sq_scene_pack(C.byref(holder.scene), C.byref(h)))
+    try:
+        arrays, scalars = {}, {}
+        for name in LEVEL1_ARRAYS:
+            data, n = C.c_void_p(), C.c_size_t()
+            assert L.sq_packed_array(h, name.encode(), C.byref(data), C.byref(n)) == 0, name
+            arrays[name] = C.string_at(data, n.value) if n.value else b""
+        for name in LEVEL1_SCALARS:
+            v = C.c_int64()
+            assert L.sq_packed_scalar(h, name.encode(), C.byref(v)) == 0, name
+            scalars[name] = v.value
+    finally:
+        L.sq_packed_free(h)
+    return arrays, scalars

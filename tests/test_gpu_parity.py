@@ -389,7 +389,7 @@ def test_random_soups_with_mirrors_and_emitters(sqt, O, seed, n_emit):
     """Random triangle soups with diffuse, half-mirror, full-mirror and emissive triangles: exercises the
     once-per-pixel mirror ray, the last-bounce emitter test (few emitters), its off switch (70 > 64 emitters),
     a scene without emitters, occluded emitters, and COMBINE frames on overlapping geometry.  64 emitters is the longest
-    list the shortcut takes (csrc/sq_host.cpp, the packer's emitter_list), 65 turns it off."""
+    list the shortcut takes (csrc/sq_pack_scene.h, the packer's emitter_list), 65 turns it off."""
     tris, mats, v, mat = _emitter_soup(sqt, seed, n_emit)
     n = len(tris)
     bih = sqt.BIH(sqt.Mesh.from_arrays(tris, mats))

@@ -1,4 +1,4 @@
-"""Level-1 culling (squigly-trace_amd/csrc/sq_host.cpp, level1_tables): the lemma behind it, searched for counter-examples on the CPU.
+"""Level-1 culling (squigly-trace_amd/csrc/sq_pack_level1.h, build_level1): the lemma behind it, searched for counter-examples on the CPU.
 
 Claim: a scattered first-bounce ray (p0, d1) that passes the three conditions (tests/level1_restatement.py states them as the
 kernel does) belongs to a sample whose radiance is level0_radiance of its pixel: no emitter accepts ray 1, nothing ray 1 can hit
@@ -73,8 +73,7 @@ def oracle_tris(name):
     if name == "scene.obj":
         tris = O.tris_from_obj(os.path.join(DATA, "scene.obj"), DATA)
         return sqt.BIH(sqt.Mesh.from_obj(os.path.join(DATA, "scene.obj"), DATA)), tris
-    # few emitters, so that their box is not the whole soup and rays aimed beside them can be culled at all
-    t, m, ot = soup(11, 2, emitter_size=0.9, cluster=(1.2, 1.2, -1.2)) if name == "soup_big_emitters" else soup(12, 1)
+    t, m, ot = R.NAMED_SOUPS[name]()
     return bih_of(t, m), ot
 
 

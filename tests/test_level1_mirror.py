@@ -1,4 +1,4 @@
-"""Condition (5) of level-1 culling (squigly-trace_amd/csrc/sq_host.cpp, level1_tables and level1_mirror): the record the packer
+"""Condition (5) of level-1 culling (squigly-trace_amd/csrc/sq_pack_level1.h, build_level1 and level1_mirror): the record the packer
 builds, and the lemma's mirror extension searched for counter-examples on the CPU.
 
 Claim: a scattered first-bounce ray (p0, d1) that condition (1) passes, that is inside the ray limits and that condition (5) culls

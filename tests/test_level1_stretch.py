@@ -1,4 +1,4 @@
-"""Condition (4) of level-1 culling (squigly-trace_amd/csrc/sq_host.cpp, level1_tables and level1_cover): the cover the packer
+"""Condition (4) of level-1 culling (squigly-trace_amd/csrc/sq_pack_level1.h, build_level1 and level1_cover): the cover the packer
 builds, and the lemma's extension searched for counter-examples on the CPU.
 
 Claim: a scattered first-bounce ray (p0, d1) that conditions (1) and (2) pass and whose stretch -- the part of it from which the
@@ -106,10 +106,7 @@ def uniform_rays(rng, n, vmax):
     return p0, d1.astype(f32), nd.astype(f32)
 
 
-SCENES = {"one": lambda: soup(41, 1, zoned=(1.2, -1.2, -1.2), emitter_size=0.8),
-          "two_clustered": lambda: soup(42, 2, zoned=(-1.2, -1.2, -1.2), cluster=(1.2, 1.2, -1.2), emitter_size=0.6),
-          "many_clustered": lambda: soup(43, 12, zoned=(1.2, -1.2, -1.2), cluster=(-1.0, 1.0, 1.0)),
-          "scene.obj": None}
+SCENES = {**{k: R.NAMED_SOUPS[k] for k in ("one", "two_clustered", "many_clustered")}, "scene.obj": None}
 
 
 @pytest.mark.parametrize("name", list(SCENES))

@@ -1,8 +1,10 @@
-"""The scene packer (csrc/sq_host.cpp, sq_pack_scene) through its C-ABI window (sq_scene_pack, include/squigly_host.h): every
+"""The scene packer (csrc/sq_pack_scene.h, sq_pack_scene) through its C-ABI window (sq_scene_pack, include/squigly_host.h): every
 array sq_scene_upload copies to the device and every flag that chooses a kernel form, on the CPU.
 
 * bit-equality with the commit the packer was lifted from: tests/golden/pack_digests.json holds byte counts, SHA-256 digests
   and scalars of every fixture scene as that commit's sq_scene_upload produced them;
+* bit-equality of the three level-1 records (sq_pack_level1.h), which are younger than that commit, with the commit before their
+  builder was rewritten: tests/golden/level1_records.json, over the fixture scenes, the named soups and a slice of fuzz_level1;
 * structure, independent of that commit: the branch table decodes back to the caller's tree, the tables agree with each other;
 * the material and geometry flags on both sides of their bounds; every refusal with its exact text;
 * the packer under AddressSanitizer and UndefinedBehaviorSanitizer, as a stand-alone program (tests/pack_main.cpp).
@@ -18,9 +20,13 @@ import subprocess
 import numpy as np
 import pytest
 
+import fuzz_level1 as FL
+import level1_mirror_restatement as M5
+import level1_restatement as R
+import level1_stretch_restatement as S
 import tree_padding as TP
 from conftest import DATA, GOLDEN, ROOT
-from scenes import ARRAYS, SCALARS, big_leaf as _big_leaf, emitter_soup as _emitter_soup, pack
+from scenes import ARRAYS, LEVEL1_ARRAYS, LEVEL1_SCALARS, SCALARS, big_leaf as _big_leaf, emitter_soup as _emitter_soup, pack, pack_level1
 
 LEAF_BIT, AXIS_MASK, RUN_PAD = 0x80000000, 0x60000000, 3
 BRANCH = np.dtype([("lo", "<f4", 3), ("lmax", "<f4"), ("hi", "<f4", 3), ("rmin", "<f4"), ("lmax2", "<f4"), ("rmin2", "<f4"),
@@ -134,6 +140,80 @@ def test_packed_bytes_equal_the_recorded_ones(packed):
         for k in ARRAYS:
             assert got["arrays"][k] == want["arrays"][k], (name, k)
         assert got["scalars"] == want["scalars"], name
+
+
+# ---- the level-1 records: bit-equality with the commit before their builder was written once ----
+LEVEL1_FUZZ_SEEDS = tuple(range(3000, 3200))             # the pytest slice of tests/fuzz_level1.py: every EDGES scene at least twice
+
+
+def parallel_quads(n):
+    """fuzz_level1's "groups13" with n parallel mirror quads: more thin (axis, cell) groups than the cover's grouping keeps (56), which
+    no family of fuzz_level1 reaches -- a lattice has at most 15 planes, a soup 13 quads."""
+    q = [(M5.quad((-1.5, -1.5, -2.0 + 0.07 * k), (3, 0, 0), (0, 3, 0)), 1 + k % 2) for k in range(n)]
+    return M5.mirror_soup(57, 1, q, cluster=(1.2, 1.2, 2.6), emitter_size=0.5)
+
+
+def level1_scenes(sqt, fixtures):
+    """{name: object with .scene} of tests/golden/level1_records.json: the fixture scenes, the named soups of the level-1 tests and
+    fuzz_level1.case(seed) of LEVEL1_FUZZ_SEEDS, an edge scene with its edge in the name."""
+    out = dict(fixtures)
+    for name, make in R.NAMED_SOUPS.items():
+        out[name] = sqt.BIH(sqt.Mesh.from_arrays(*make()[:2]))
+    for name, make in (("axis_soup", M5.axis_soup), ("tilted_soup", M5.tilted_soup)):
+        out[name] = sqt.BIH(sqt.Mesh.from_arrays(*make()[0][:2]))
+    out["parallel_57"] = sqt.BIH(sqt.Mesh.from_arrays(*parallel_quads(57)[:2]))
+    for seed in LEVEL1_FUZZ_SEEDS:
+        c = FL.case(seed)
+        out[f"fuzz_{seed}" + (f"_{c.edge}" if c.edge else "")] = FL.product_bih(c)
+    return out
+
+
+@pytest.fixture(scope="module")
+def level1_packed(sqt, fixtures):
+    return {name: pack_level1(sqt, f) for name, f in level1_scenes(sqt, fixtures).items()}
+
+
+def test_level1_records_equal_the_recorded_ones(level1_packed):
+    """Arrays "level1", "level1_cover" and "level1_mirror" (byte count, SHA-256) and the scalars level1_on, level1_zero and
+    shortcut_depth of every scene are what the recorded commit's packer built (the JSON says which commit and how).  No scene is
+    skipped: a record that a cap turned off is pinned as it is."""
+    golden = json.load(open(os.path.join(GOLDEN, "level1_records.json")))
+    assert golden["commit"].startswith("092ca5d")
+    assert set(golden["scenes"]) == set(level1_packed)
+    for name, (arrays, scalars) in level1_packed.items():
+        got, want = digest_of(arrays, scalars), golden["scenes"][name]
+        assert set(want["arrays"]) == set(LEVEL1_ARRAYS) and set(want["scalars"]) == set(LEVEL1_SCALARS)
+        for k in LEVEL1_ARRAYS:
+            assert got["arrays"][k] == want["arrays"][k], (name, k)
+        assert got["scalars"] == want["scalars"], name
+
+
+def test_level1_scenes_sit_on_both_sides_of_every_switch(level1_packed):
+    """From the records alone: the recorded scenes hold both values of everything the builder of the three records branches on and
+    a record can show.  (What a record cannot show -- a merge loop that ran, the 56-group overflow -- was counted once at the
+    recorded commit: DESIGN.md 4.1, "Host side split by role".)"""
+    T, V, M, on = {}, {}, {}, {}
+    for name, (a, s) in level1_packed.items():
+        T[name] = np.frombuffer(a["level1"], R.LEVEL1)[0]
+        V[name] = np.frombuffer(a["level1_cover"], S.COVER)[0] if a["level1_cover"] else None
+        M[name] = np.frombuffer(a["level1_mirror"], M5.MIRROR)[0] if a["level1_mirror"] else None
+        on[name] = s["level1_on"]
+        assert on[name] == T[name]["on"] and (V[name] is None) == (M[name] is None), name
+    edge = lambda e: [n for n in level1_packed if n.startswith("fuzz_") and n.endswith("_" + e)]
+    assert set(on.values()) == {0, 1}
+    assert {int(T[n]["n_classes"]) for n in T if on[n]} == {1, 2, 3, 4}
+    covers = {int(V[n]["n"]) for n in V if V[n] is not None}
+    assert 8 in covers and min(covers) < 8
+    assert any(on[n] and V[n] is None for n in V)                             # on, and no cover at all
+    assert all(V[n] is None for n in V if not on[n])
+    for e, field, n in (("groups12", "n_panels", 12), ("w8", "n_w", 8)):      # at a cap: the record holds as many as fit
+        assert len(edge(e)) >= 2 and all(M[x] is not None and M[x]["n_panels"] > 0 and M[x][field] == n for x in edge(e)), e
+    for e in ("groups13", "w9"):                                              # one more: a cover, and condition (5) off
+        assert len(edge(e)) >= 2 and all(on[x] and M[x] is not None and M[x]["n_panels"] == 0 for x in edge(e)), e
+    assert {int(M[n]["n_rest"]) for n in M if M[n] is not None and M[n]["n_panels"] > 0} >= {0, 1, 4}
+    for e_on, e_off in (("emit64", "emit65"), ("P_under", "P_over")):
+        assert len(edge(e_on)) >= 2 and len(edge(e_off)) >= 2
+        assert all(on[x] for x in edge(e_on)) and not any(on[x] for x in edge(e_off)), (e_on, e_off)
 
 
 @pytest.mark.parametrize("n_mats,fits", [(65535, True), (65536, False)])
@@ -365,14 +445,28 @@ def test_upload_checks_the_device_before_the_tree(sqt):
 
 # ---- sanitizers ----
 
-def test_packer_under_address_and_undefined_behaviour_sanitizers(tmp_path):
+def test_packer_under_address_and_undefined_behaviour_sanitizers(sqt, tmp_path):
     """tests/pack_main.cpp (its own main: load data/scene.obj, build, pack, read every array through the window, plan a handful of
-    calls through sq_plan_call, free) compiled with sq_host.cpp under -fsanitize=address,undefined and run as a child process: exit 0, nothing on stderr."""
+    calls through sq_plan_call, free; then the same without the plans for every raw scene file) compiled with sq_host.cpp under
+    -fsanitize=address,undefined and run as a child process, once: exit 0, nothing on stderr.  The raw scene files are the edge scenes
+    of the recorded slice, fuzz_level1's seeds 3000 .. 3067 with seed % 4 == 3 -- each of EDGES once --, so that every early return of
+    the level-1 builder runs under the sanitizers."""
     exe = str(tmp_path / "pack_main")
     csrc = os.path.join(ROOT, "squigly-trace_amd", "csrc")
     subprocess.check_call(["g++", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined",
                            "-static-libasan", "-static-libubsan",      # the runtimes inside the program: nothing to order at load time
                            os.path.join(csrc, "sq_host.cpp"), os.path.join(ROOT, "tests", "pack_main.cpp"), "-o", exe])
-    r = subprocess.run([exe, os.path.join(DATA, "scene.obj"), DATA], capture_output=True)
+    files = []
+    for seed in range(3003, 3068, 4):
+        c = FL.case(seed)
+        tris = np.zeros(len(c.v), sqt._native.TRI_DTYPE)
+        tris["v0"], tris["v1"], tris["v2"], tris["mat"] = c.v[:, 0], c.v[:, 1], c.v[:, 2], c.mat
+        files.append(str(tmp_path / f"fuzz_{seed}_{c.edge}.raw"))
+        with open(files[-1], "wb") as f:
+            f.write(np.array([len(tris), len(c.mats)], "<i4").tobytes() + tris.tobytes() + c.mats.tobytes())
+    assert len(files) == len(FL.EDGES)
+    r = subprocess.run([exe, os.path.join(DATA, "scene.obj"), DATA] + files, capture_output=True)
     assert r.returncode == 0 and r.stderr == b"", (r.returncode, r.stderr[-2000:])
-    assert r.stdout.startswith(b"packed 13 arrays") and b"planned 10 calls" in r.stdout
+    lines = r.stdout.splitlines()
+    assert len(lines) == 1 + len(files) and all(line.startswith(b"packed 16 arrays") for line in lines), r.stdout
+    assert b"planned 10 calls" in lines[0]
