@@ -102,11 +102,16 @@ SQ_HD double asin_tail(double z) {   // sum_{k=1..24} C(2k,k)/(4^k(2k+1)) z^k
 }
 SQ_HD double dsqrt(double x) { return __builtin_sqrt(x); }
 SQ_HD double acos_(double x) {
-    double ax = __builtin_fabs(x);
-    if (ax <= 0.5) { double z = x * x; return 0x1.921fb54442d18p+0 - (x + x * asin_tail(z)); }
-    double z = (1.0 - ax) * 0.5;
-    double s = dsqrt(z);
-    double t = 2.0 * (s + s * asin_tail(z));
+    // The two ranges share the series: its argument is selected first and it is evaluated once, then either short tail follows.
+    // (Written as an if / else with a series in each arm, a wave whose lanes fall on both sides -- randomVector's 2v - 1 splits
+    // every wave in halves -- runs the 24 terms twice.)  Every lane does the operations it did, in their order, on the same values.
+    const double ax = __builtin_fabs(x);
+    const bool small = ax <= 0.5;
+    const double z = small ? x * x : (1.0 - ax) * 0.5;
+    const double q = asin_tail(z);
+    if (small) return 0x1.921fb54442d18p+0 - (x + x * q);
+    const double s = dsqrt(z);
+    const double t = 2.0 * (s + s * q);
     return (x > 0) ? t : (0x1.921fb54442d18p+1 - t);
 }
 SQ_HD double atan_tab(int k) {
