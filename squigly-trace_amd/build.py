@@ -1,4 +1,5 @@
-"""Build libsquigly_hip.so (HIP kernels for gfx950 + host side) and libsquigly_denoise.so (the denoiser) in-tree with hipcc.
+"""Build libsquigly_hip.so (HIP kernels for gfx950 + host side), libsquigly_denoise.so (the denoiser) and libsquigly_lens.so (jittered,
+thin-lens primary rays) in-tree with hipcc.
 
     python squigly-trace_amd/build.py [--force]
 
@@ -104,6 +105,45 @@ def build_denoise(force=False):
     return DENOISE_OUT
 
 
+# The third library: jittered, thin-lens primary rays (include/squigly_lens.h).  A client of libsquigly_hip.so's public C-ABI: it is
+# linked against that library and built after it, with the same FLAGS (its bits rest on them as the renderer's do) and an id and a
+# staleness check of its own, so source_id() above does not move when it changes.
+LENS_OUT = os.path.join(HERE, "libsquigly_lens.so")
+LENS_SOURCES = ["sq_lens.hip"]
+LENS_HEADERS = ["sq_math.h", "sq_error.h", "sq_lens_plan.h", "../../include/squigly_lens.h", "../../include/squigly_hip.h"]
+
+
+def lens_source_id(extra=()):
+    """First 16 hex digits of SHA-256 over the lens library's source, its headers, the flags and the extra -D options: what
+    sq_lens_build_id() returns."""
+    import hashlib
+    h = hashlib.sha256(b"lens\0")
+    for f in sorted(LENS_SOURCES + LENS_HEADERS):
+        h.update(f.encode() + b"\0")
+        with open(os.path.join(CSRC, f), "rb") as fh:
+            h.update(fh.read())
+    h.update("\0".join(FLAGS + sorted(extra)).encode())
+    return h.hexdigest()[:16]
+
+
+def lens_stale():
+    """As stale(), for libsquigly_lens.so: it must carry the current lens_source_id()."""
+    if not os.path.exists(LENS_OUT):
+        return True
+    with open(LENS_OUT, "rb") as f:
+        return lens_source_id().encode() not in f.read()
+
+
+def build_lens(force=False, extra=(), out=None):
+    """out: an experimental variant (extra -D flags) beside the product library; SQ_LENS_LIB_PATH selects it at load time."""
+    if out is None and not force and not lens_stale():
+        return LENS_OUT
+    subprocess.check_call([hipcc()] + FLAGS + list(extra) + ['-DSQ_LENS_BUILD_ID="%s"' % lens_source_id(extra), "-x", "hip"]
+                          + [os.path.join(CSRC, s) for s in LENS_SOURCES] + ["-o", out or LENS_OUT]
+                          + ["-L" + HERE, "-lsquigly_hip", "-Wl,-rpath,$ORIGIN"])
+    return out or LENS_OUT
+
+
 def build(force=False, extra=(), out=None):
     """out: build an experimental variant (extra -D flags) beside the product library; SQ_LIB_PATH selects it at load time."""
     if out is not None:
@@ -111,6 +151,7 @@ def build(force=False, extra=(), out=None):
         return out
     build_denoise(force)
     if not force and not stale() and os.path.exists(CLI):
+        build_lens(force)
         return OUT
     cmd = [hipcc()] + FLAGS + list(extra) + id_flag(extra) + ["-x", "hip"] + [os.path.join(CSRC, s) for s in SOURCES] + ["-o", OUT]
     subprocess.check_call(cmd)
@@ -123,6 +164,7 @@ def build(force=False, extra=(), out=None):
                            os.path.join(CSRC, "cli_main.cpp"), "-o", CLI,
                            "-L" + HERE, "-lsquigly_hip", "-L" + os.path.join(rocm, "lib"), "-lamdhip64", "-Wl,-rpath,$ORIGIN/..", "-Wl,-rpath,/opt/rocm/lib", "-Wl,-rpath," + os.path.join(rocm, "lib"),
                            "-Wl,--allow-shlib-undefined"])
+    build_lens(force)
     return OUT
 
 

@@ -10,7 +10,7 @@ import os
 import sys
 import time
 
-from . import BIH, Mesh, Settings, camera_from_text, lib, load_camera, render, render_adaptive, render_progressive, render_views_rgb8, write_png
+from . import BIH, Lens, Mesh, Settings, camera_from_text, lib, load_camera, render, render_adaptive, render_lens_rgb8, render_progressive, render_views_rgb8, write_png
 from ._native import SquiglyError
 
 
@@ -49,6 +49,30 @@ def positive_float(text):
         raise argparse.ArgumentTypeError("expected a number > 0")
     if not v > 0:
         raise argparse.ArgumentTypeError("expected a number > 0")
+    return v
+
+
+def unit_float(text):
+    try:
+        v = float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError("expected a number in 0..1")
+    if not 0 <= v <= 1:
+        raise argparse.ArgumentTypeError("expected a number in 0..1")
+    return v
+
+
+def finite_nonneg_float(text):
+    v = nonneg_float(text)
+    if v == float("inf"):
+        raise argparse.ArgumentTypeError("expected a finite number >= 0")
+    return v
+
+
+def finite_positive_float(text):
+    v = positive_float(text)
+    if v == float("inf"):
+        raise argparse.ArgumentTypeError("expected a finite number > 0")
     return v
 
 
@@ -170,7 +194,24 @@ def build_parser():
     p.add_argument("--sky", type=parse_sky, default=None, metavar="R,G,B[,R,G,B]",
                    help="Radiance of a ray that leaves the scene: looking up (+z), then looking down (-z; default the same: "
                         "a constant sky), blended by the ray's direction (default: none, black); not with --cast")
+    # not flags of the reference: a pixel integrates over its area, and the camera can have an aperture (include/squigly_lens.h)
+    p.add_argument("--aa", type=unit_float, nargs="?", const=1.0, default=None, metavar="J",
+                   help="Anti-aliasing: every primary ray starts from a point drawn from a square of side J pixels (default 1: a box "
+                        "filter over the pixel)")
+    p.add_argument("--subrays", type=positive_int, default=None, metavar="R",
+                   help="With --aa or --aperture: primary rays per pixel, a divisor of --samples (default: one per sample)")
+    p.add_argument("--aperture", type=finite_nonneg_float, default=None, metavar="A",
+                   help="Depth of field: radius of the lens in world units (default 0: a pinhole)")
+    p.add_argument("--focus", type=finite_positive_float, default=None, metavar="F",
+                   help="With --aperture: forward distance of the plane in focus (default 1)")
     return p
+
+
+def lens_of(a):
+    """The Lens of --aa / --aperture / --focus, or None when the frame has none of them."""
+    if a.aa is None and a.aperture is None:
+        return None
+    return Lens(jitter=0.0 if a.aa is None else a.aa, aperture=a.aperture or 0.0, focus=1.0 if a.focus is None else a.focus)
 
 
 def parse_args(argv=None):
@@ -190,6 +231,20 @@ def parse_args(argv=None):
         p.error("--depth cannot be combined with --cast (a cast image has no paths)")
     if a.sky is not None and a.cast:
         p.error("--sky cannot be combined with --cast (a cast image has no sky)")
+    if a.aa is None and a.aperture is None:
+        if a.subrays is not None:
+            p.error("--subrays needs --aa or --aperture")
+        if a.focus is not None:
+            p.error("--focus needs --aperture")
+    else:
+        if a.focus is not None and a.aperture is None:
+            p.error("--focus needs --aperture")
+        for flag, given in (("--cast", a.cast), ("--views", a.views is not None), ("--adaptive", a.adaptive is not None),
+                            ("--preview-every", a.preview_every is not None)):
+            if given:
+                p.error(f"--aa, --subrays, --aperture and --focus cannot be combined with {flag}")
+        if a.samples < 1 or a.samples % (a.subrays or a.samples):
+            p.error(f"--subrays must divide --samples (got {a.subrays} and {a.samples})")
     return a
 
 
@@ -241,6 +296,9 @@ def main(argv=None):
         if a.counts is not None:
             with open(a.counts, "wb") as f:                     # the name as given (np.save would append .npy to a path)
                 np.save(f, counts.astype(np.int32))
+    elif lens_of(a) is not None:
+        write_png(settings.savePath, render_lens_rgb8(bih, cam, settings.samples, settings.dimensions, lens=lens_of(a), subrays=a.subrays,
+                                                      depth=a.depth, sky=a.sky))
     elif a.preview_every is None and a.light is None and a.depth is None and a.sky is None:
         render(bih, cam, settings)
     elif a.preview_every is None:                               # caller-given lights, depths and skies live on a resident scene: one step of all samples

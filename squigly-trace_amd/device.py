@@ -332,6 +332,20 @@ class DeviceScene(Owner):
         from .denoise import scene_guides
         return scene_guides(self, cam, w, h, shard, stream)
 
+    def lens_rays(self, cam, lens, samples, subrays, w, h, shard=(None, 0, 1), r_range=None, stream=None):
+        """The jittered, thin-lens sub-rays of every pixel of the shard (lens.py, sq_lens_rays_device): (origins, directions, seeds),
+        float32 CUDA tensors [nb, rows, h, 3] and int64 [nb, rows, h] for the sub-rays r_range (default: all `subrays`)."""
+        from .lens import lens_rays
+        return lens_rays(self, cam, lens, samples, subrays, w, h, shard, r_range, stream)
+
+    def render_lens(self, cam, lens, samples, subrays, w, h, shard=(None, 0, 1), r_range=None, sums=None, want_sum2=False,
+                    want_avg=True, want_rgb=True, work_mb=None, stream=None):
+        """The anti-aliased, depth-of-field frame (lens.py, sq_lens_render_device): `subrays` primary rays per pixel, samples /
+        subrays samples on each, folded in sub-ray order; returns LensFrame(sum, sum2, avg, rgb).  See lens.render_lens."""
+        from . import lens as L
+        return L.render_lens(self, cam, lens, samples, subrays, w, h, shard, r_range, sums, want_sum2, want_avg, want_rgb,
+                             L.DEFAULT_WORK_MB if work_mb is None else work_mb, stream)
+
     def raytrace(self, origins, directions, seeds=None, samples=1, k_range=None, sums=None, want_avg=True, want_rgb=False,
                  stream=None):
         """Lib.raytrace of each ray (sq_raytrace_rays_device): returns Radiance(sum, avg, rgb) CUDA tensors, enqueued on `stream`.

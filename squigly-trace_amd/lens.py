@@ -1,0 +1,204 @@
+"""ctypes binding of libsquigly_lens.so (include/squigly_lens.h) and the helpers around it: anti-aliasing and depth of field.
+
+A lens frame gives every pixel R sub-rays -- jittered over the pixel's area, started on a thin lens -- and folds their radiances
+back in a fixed order.  PyTorch is the plumbing (device memory, streams); every ray comes from the HIP kernels of csrc/sq_lens.hip
+and every sample from libsquigly_hip.so's radiance query.  There is no fallback: a missing library raises.
+"""
+import collections
+import ctypes as C
+import math
+import os
+
+from . import _native as N
+from . import _plumbing as P
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+# SQ_LENS_LIB_PATH: development aid, loads an experimental build of the same library (build.py: build_lens(out=...))
+LIB_PATH = os.environ.get("SQ_LENS_LIB_PATH") or os.path.join(_HERE, "libsquigly_lens.so")
+
+# include/squigly_lens.h
+EXPORTED_SYMBOLS = ["sq_lens_last_error", "sq_lens_build_id", "sq_lens_work_bytes", "sq_lens_plan", "sq_lens_rays_device",
+                    "sq_lens_fold_device", "sq_lens_render_device"]
+
+MAX_INDEX = 2 ** 31 - 1          # pixels of a call and ray slots of a batch (the header's INDEX WIDTHS)
+DEFAULT_WORK_MB = 1024
+
+LensFrame = collections.namedtuple("LensFrame", ["sum", "sum2", "avg", "rgb"])
+LensFrame.__doc__ = """Results of DeviceScene.render_lens per pixel: the fold of the sub-ray sums, of their squares (None unless asked for),
+(1 / samples) * sum and its tonemap; CUDA tensors [rows, h, 3]."""
+
+
+class Lens(C.Structure):
+    """sq_lens: jitter (0..1, the side in pixels of the square a sub-ray's image point is drawn from; 1 = a box filter over the
+    pixel, 0 = makeRay's point), aperture (lens radius in world units, 0 = a pinhole) and focus (forward distance of the plane in
+    focus; read only when the aperture is open).  SquiglyError for values the library would refuse."""
+    _fields_ = [("jitter", C.c_float), ("aperture", C.c_float), ("focus", C.c_float)]
+
+    def __init__(self, jitter=1.0, aperture=0.0, focus=1.0):
+        vals = []
+        for name, v in (("jitter", jitter), ("aperture", aperture), ("focus", focus)):
+            if isinstance(v, bool) or not isinstance(v, (int, float)):
+                raise N.SquiglyError(f"{name} must be a number, got {v!r}")
+            vals.append(float(v))
+        j, a, f = vals
+        if not 0.0 <= j <= 1.0:
+            raise N.SquiglyError(f"jitter must be a number in [0, 1] (got {j!r})")
+        if not (a >= 0.0 and math.isfinite(a)):
+            raise N.SquiglyError(f"aperture must be a finite number >= 0 (got {a!r})")
+        if a > 0.0 and not (f > 0.0 and math.isfinite(f)):
+            raise N.SquiglyError(f"focus must be a finite number > 0 when the aperture is open (got {f!r})")
+        super().__init__(j, a, f)
+
+    def __repr__(self):
+        return f"Lens(jitter={self.jitter!r}, aperture={self.aperture!r}, focus={self.focus!r})"
+
+
+_lib = None
+
+
+def lib():
+    global _lib
+    if _lib is not None:
+        return _lib
+    N.lib()                                   # the library it is a client of, loaded from this package first
+    L = N.load(LIB_PATH)
+    vp, i32, i64, sz = C.c_void_p, C.c_int32, C.c_int64, C.c_size_t
+    L.sq_lens_last_error.restype = C.c_char_p
+    L.sq_lens_build_id.restype = C.c_char_p
+    L.sq_lens_work_bytes.argtypes = [i64, i32]
+    L.sq_lens_work_bytes.restype = sz
+    L.sq_lens_plan.argtypes = [i64, i32, i32, sz, vp, i32]
+    L.sq_lens_plan.restype = i32
+    frame = [C.POINTER(N.Camera), C.POINTER(Lens), i32, i32, i32, i32, i32, i32, N.Shard]
+    L.sq_lens_rays_device.argtypes = [i32] + frame + [vp, vp, vp, vp]
+    L.sq_lens_fold_device.argtypes = [i32, i64, i32, i32, i32, vp, vp, vp, vp, vp, vp]
+    L.sq_lens_render_device.argtypes = [vp] + frame + [vp, sz, vp, vp, vp, vp, vp]
+    _lib = L
+    return L
+
+
+def check(rc):
+    N.checked(rc, lib().sq_lens_last_error)
+
+
+def build_id():
+    """sq_lens_build_id(): hash of the sources and flags the loaded library was built from (build.py: lens_source_id)."""
+    return lib().sq_lens_build_id().decode()
+
+
+def work_bytes(pixels, subrays):
+    """sq_lens_work_bytes: the workspace of a batch of `subrays` sub-rays of `pixels` pixels; 0 beyond the index widths."""
+    return int(lib().sq_lens_work_bytes(int(pixels), int(subrays)))
+
+
+def plan(pixels, r_begin, r_end, work_bytes):
+    """sq_lens_plan: the batches [(r0, r1), ...] sq_lens_render_device runs the sub-ray range in; SquiglyError as the library says."""
+    n = N.checked(lib().sq_lens_plan(int(pixels), int(r_begin), int(r_end), int(work_bytes), None, 0), lib().sq_lens_last_error, count=True)
+    out = (C.c_int32 * (2 * n))()
+    lib().sq_lens_plan(int(pixels), int(r_begin), int(r_end), int(work_bytes), out, n)
+    return [(int(out[2 * i]), int(out[2 * i + 1])) for i in range(n)]
+
+
+def _int(name, v):
+    if isinstance(v, bool) or not isinstance(v, int):
+        try:
+            import numpy as np
+            ok = isinstance(v, np.integer)
+        except ImportError:
+            ok = False
+        if not ok:
+            raise N.SquiglyError(f"{name} must be an integer, got {v!r}")
+    return int(v)
+
+
+def frame_args(lens, samples, subrays, r_range=None):
+    """(samples, subrays, r_begin, r_end) of a lens frame as ints; SquiglyError, before any device work, for what the library
+    would refuse: a lens that is no Lens, samples or sub-rays below 1, sub-rays that do not divide the samples, a bad range."""
+    if not isinstance(lens, Lens):
+        raise N.SquiglyError(f"lens must be a Lens, got {type(lens).__name__}")
+    S, R = _int("samples", samples), _int("subrays", subrays)
+    if S < 1 or R < 1 or S >= 2 ** 31:
+        raise N.SquiglyError(f"samples and subrays must be at least 1 (got samples = {S}, subrays = {R})")
+    if S % R:
+        raise N.SquiglyError(f"the sub-rays must divide the samples (got samples = {S}, subrays = {R})")
+    if r_range is None:
+        r0, r1 = 0, R
+    else:
+        try:
+            r0, r1 = r_range
+        except (TypeError, ValueError):
+            raise N.SquiglyError(f"r_range must be (r_begin, r_end), got {r_range!r}")
+        r0, r1 = _int("r_range[0]", r0), _int("r_range[1]", r1)
+    if r0 < 0 or r1 <= r0 or r1 > R:
+        raise N.SquiglyError(f"bad sub-ray range [{r0}, {r1}) (need 0 <= r_begin < r_end <= subrays = {R})")
+    return S, R, r0, r1
+
+
+def _size_check(rows, h, subrays=1):
+    pixels = int(rows) * int(h)
+    if pixels > MAX_INDEX:
+        raise N.SquiglyError(f"{rows} x {h} pixels exceed 2^31 - 1 pixels in one call")
+    if pixels and subrays > MAX_INDEX // pixels:
+        raise N.SquiglyError(f"{subrays} sub-rays of {pixels} pixels exceed 2^31 - 1 ray slots in one batch")
+    return pixels
+
+
+def lens_rays(ds, cam, lens, samples, subrays, w, h, shard=(None, 0, 1), r_range=None, stream=None):
+    """DeviceScene.lens_rays: the sub-rays [r_begin, r_end) of every pixel of the shard (sq_lens_rays_device) as (origins,
+    directions, seeds): float32 CUDA tensors [nb, rows, h, 3] and int64 [nb, rows, h], nb = r_end - r_begin.  With them
+    ds.raytrace(origins, directions, seeds=seeds, samples=samples // subrays) is every sub-ray's sum."""
+    import torch
+    S, R, r0, r1 = frame_args(lens, samples, subrays, r_range)
+    sh, rows = P.shard_rows(int(w), shard)
+    _size_check(rows, h, r1 - r0)
+    dev, st = P.call_stream(ds.device, stream)
+    with torch.cuda.stream(st):
+        o = torch.empty((r1 - r0, rows, h, 3), dtype=torch.float32, device=dev)
+        d = torch.empty((r1 - r0, rows, h, 3), dtype=torch.float32, device=dev)
+        sd = torch.empty((r1 - r0, rows, h), dtype=torch.int64, device=dev)
+    check(lib().sq_lens_rays_device(ds.device, C.byref(cam), C.byref(lens), S, R, r0, r1, int(w), int(h), sh, o.data_ptr(), d.data_ptr(),
+                                    sd.data_ptr(), P.stream_ptr(st)))
+    return o, d, sd
+
+
+def render_lens(ds, cam, lens, samples, subrays, w, h, shard=(None, 0, 1), r_range=None, sums=None, want_sum2=False, want_avg=True,
+                want_rgb=True, work_mb=DEFAULT_WORK_MB, stream=None):
+    """DeviceScene.render_lens: the sub-rays r_range (default: all) of the lens frame (sq_lens_render_device); returns
+    LensFrame(sum, sum2, avg, rgb), enqueued on `stream`.
+
+    samples, subrays: S and R of include/squigly_lens.h; R divides S and S / R samples ride on each sub-ray.  sums: the fold so far
+    -- a float32 CUDA tensor [rows, h, 3], or a pair (sum, sum2) of them -- required when r_range starts above 0, updated in place,
+    allocated otherwise.  want_sum2: also fold the squares of the sub-ray sums (implied by a pair).  avg = (1 / samples) * sum of
+    the sub-rays folded so far and rgb its tonemap (None unless wanted).  work_mb: the most workspace, in MiB, the call allocates
+    (a tensor under the stream, handed back when the call returns): the frame runs in batches of as many whole sub-rays as fit,
+    and its bits do not depend on that.  Runs under the scene's depth and sky."""
+    import torch
+    S, R, r0, r1 = frame_args(lens, samples, subrays, r_range)
+    if isinstance(work_mb, bool) or not isinstance(work_mb, (int, float)) or not work_mb > 0 or not math.isfinite(work_mb):
+        raise N.SquiglyError(f"work_mb must be a number > 0, got {work_mb!r}")
+    sh, rows = P.shard_rows(int(w), shard)
+    pixels = _size_check(rows, h)
+    s1, s2 = sums if isinstance(sums, (tuple, list)) else (sums, None)
+    if s1 is None and (r0 > 0 or s2 is not None):
+        raise N.SquiglyError("render_lens needs the sums of the sub-rays [0, r_begin) when r_range starts above 0")
+    want_sum2 = bool(want_sum2) or s2 is not None
+    if want_sum2 and s2 is None and r0 > 0:
+        raise N.SquiglyError("render_lens needs sums = (sum, sum2) to carry second moments on from r_begin > 0")
+    dev, st = P.call_stream(ds.device, stream)
+    for name, t in (("sums", s1), ("sums2", s2)):
+        if t is not None:
+            P.tensor(name, t, (rows, h, 3), torch.float32, dev)
+    budget = int(work_mb * 2 ** 20)
+    need = work_bytes(pixels, r1 - r0) if pixels else 0
+    nbytes = min(need, budget) if need else budget
+    with torch.cuda.stream(st):      # outputs and workspace are allocated (and the workspace freed) in the order of the call's stream
+        if s1 is None:
+            s1 = torch.empty((rows, h, 3), dtype=torch.float32, device=dev)
+        if want_sum2 and s2 is None:
+            s2 = torch.empty((rows, h, 3), dtype=torch.float32, device=dev)
+        avg = torch.empty((rows, h, 3), dtype=torch.float32, device=dev) if want_avg else None
+        rgb = torch.empty((rows, h, 3), dtype=torch.uint8, device=dev) if want_rgb else None
+        work = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+        check(lib().sq_lens_render_device(ds._h, C.byref(cam), C.byref(lens), S, R, r0, r1, int(w), int(h), sh, work.data_ptr(), nbytes,
+                                          s1.data_ptr(), P.ptr(s2), P.ptr(avg), P.ptr(rgb), P.stream_ptr(st)))
+    return LensFrame(s1, s2, avg, rgb)

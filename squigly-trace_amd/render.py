@@ -145,6 +145,24 @@ def render_views_rgb8(bih, cams, samples, dimensions, cast=False, device=0, ligh
         return rgb.cpu().numpy()
 
 
+def render_lens_rgb8(bih, cam, samples, dimensions, lens=None, subrays=None, device=0, depth=None, sky=None, work_mb=None) -> np.ndarray:
+    """The image of render_rgb8 with anti-aliasing and depth of field (DeviceScene.render_lens): shape (w, h, 3) uint8.  lens: a
+    Lens (None = Lens(): a box filter over the pixel, no aperture).  subrays: primary rays per pixel, a divisor of samples (None =
+    samples, a ray per sample).  With Lens(jitter=0) and subrays=1 the image is bit for bit that of render_rgb8.  depth, sky: as in
+    render_progressive.  Refused before anything is uploaded: what lens.frame_args refuses."""
+    from .lens import Lens, frame_args
+    lens = Lens() if lens is None else lens
+    subrays = samples if subrays is None else subrays
+    frame_args(lens, samples, subrays)
+    scene = _resident(bih, device, None, depth, sky)
+    import torch
+    w, h = dimensions
+    with scene as ds:
+        out = ds.render_lens(cam, lens, samples, subrays, w, h, want_avg=False, work_mb=work_mb)
+        torch.cuda.synchronize(ds.device)
+        return out.rgb.cpu().numpy()
+
+
 def render(bih, cam, settings: Settings):
     """Lib.render: compute the image and write it to settings.savePath."""
     img = render_rgb8(bih, cam, settings.samples, settings.dimensions, settings.cast)
