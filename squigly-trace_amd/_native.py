@@ -209,7 +209,8 @@ def lights_array(lights):
 def depth_value(depth):
     """The int of a path depth (DeviceScene.set_depth, depth= of the render functions); SquiglyError for anything that is not an
     integer in 1 .. MAX_DEPTH (a bool and a float, integral or not, are not integers here)."""
-    if isinstance(depth, bool) or not isinstance(depth, (int, np.integer)):
+    from . import _plumbing as P              # (it imports this module)
+    if not P.is_integer(depth):
         raise SquiglyError(f"depth must be an integer in 1..{MAX_DEPTH}, got {depth!r}")
     if not 1 <= int(depth) <= MAX_DEPTH:
         raise SquiglyError(f"depth must be in 1..{MAX_DEPTH} (got {int(depth)})")

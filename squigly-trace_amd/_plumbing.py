@@ -5,7 +5,14 @@ torch is imported where it is used, so that the package imports without it (only
 """
 import ctypes as C
 
+import numpy as np
+
 from . import _native as N
+
+
+def is_integer(v):
+    """The rule for an argument that must be an integer: an int or a numpy integer; a bool and a float, integral or not, are neither."""
+    return not isinstance(v, bool) and isinstance(v, (int, np.integer))
 
 
 def call_stream(device, stream):

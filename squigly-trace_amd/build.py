@@ -17,7 +17,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libsquigly_hip.so")
 SOURCES = ["sq_device.hip", "sq_bih_device.hip", "sq_host.cpp"]
-HEADERS = ["sq_math.h", "sq_error.h", "sq_scene.h", "sq_layout.h", "sq_pack.h", "sq_plan.h", "sq_host_types.h", "sq_cull_lemma.h", "sq_pack_level1.h", "sq_pack_scene.h", "sq_plan_call.h", "sq_frame.h", "sq_kernels_lane.h", "sq_kernels_wave.h", "sq_kernels_trace.h", "cli_main.cpp", "../../include/squigly_hip.h", "../../include/squigly_host.h"]
+HEADERS = ["sq_math.h", "sq_error.h", "sq_call_checks.h", "sq_scene.h", "sq_layout.h", "sq_pack.h", "sq_plan.h", "sq_host_types.h", "sq_cull_lemma.h", "sq_pack_level1.h", "sq_pack_scene.h", "sq_plan_call.h", "sq_frame.h", "sq_kernels_lane.h", "sq_kernels_wave.h", "sq_kernels_trace.h", "cli_main.cpp", "../../include/squigly_hip.h", "../../include/squigly_host.h"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
          "-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt", "-fno-fast-math",
          # v_pk_mul_f32 / v_pk_add_f32 issue at ~9.5 cycles per wave on gfx950 against ~2.6 for the scalar forms
@@ -30,12 +30,35 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
          "-Wall", "-Wno-unused-function"]
 
 
-def source_id(extra=()):
-    """First 16 hex digits of SHA-256 over every source and header of the library, the flags and the extra -D options:
-    what sq_build_id() returns, and what tools/collect_profiles.py stamps its counter files with."""
+CLI = os.path.join(HERE, "bin", "squigly-trace")
+
+# The second library: the denoiser (include/squigly_denoise.h).  One source, the same FLAGS (its bits rest on -ffp-contract=off and
+# the correctly rounded divide / sqrt as the renderer's do) and an id of its own: the main library's id -- and the counter files
+# stamped with it -- do not move when the filter changes.
+DENOISE_OUT = os.path.join(HERE, "libsquigly_denoise.so")
+DENOISE_SOURCES = ["sq_denoise.hip"]
+DENOISE_HEADERS = ["sq_math.h", "sq_error.h", "sq_call_checks.h", "../../include/squigly_denoise.h"]
+
+# The third library: jittered, thin-lens primary rays (include/squigly_lens.h).  A client of libsquigly_hip.so's public C-ABI: it is
+# linked against that library and built after it, with the same FLAGS and an id of its own.
+LENS_OUT = os.path.join(HERE, "libsquigly_lens.so")
+LENS_SOURCES = ["sq_lens.hip"]
+LENS_HEADERS = ["sq_math.h", "sq_error.h", "sq_call_checks.h", "sq_lens_plan.h", "../../include/squigly_lens.h", "../../include/squigly_hip.h"]
+
+# One description per library.  macro: the -D that carries the id into the library (what sq_build_id(), sq_denoise_build_id() and
+# sq_lens_build_id() return); salt: what the id's hash starts from, so that no two libraries share an id; link: behind the output.
+MAIN = dict(out=OUT, sources=SOURCES, headers=HEADERS, macro="SQ_BUILD_ID", salt=b"", link=[])
+DENOISE = dict(out=DENOISE_OUT, sources=DENOISE_SOURCES, headers=DENOISE_HEADERS, macro="SQ_DENOISE_BUILD_ID", salt=b"denoise\0", link=[])
+LENS = dict(out=LENS_OUT, sources=LENS_SOURCES, headers=LENS_HEADERS, macro="SQ_LENS_BUILD_ID", salt=b"lens\0",
+            link=["-L" + HERE, "-lsquigly_hip", "-Wl,-rpath,$ORIGIN"])
+
+
+def lib_source_id(lib, extra=()):
+    """First 16 hex digits of SHA-256 over the library's salt, every source and header of it, the flags and the extra options: the
+    main library's is also what tools/collect_profiles.py stamps its counter files with."""
     import hashlib
-    h = hashlib.sha256()
-    for f in sorted(SOURCES + HEADERS):
+    h = hashlib.sha256(lib["salt"])
+    for f in sorted(lib["sources"] + lib["headers"]):
         h.update(f.encode() + b"\0")
         with open(os.path.join(CSRC, f), "rb") as fh:
             h.update(fh.read())
@@ -43,8 +66,21 @@ def source_id(extra=()):
     return h.hexdigest()[:16]
 
 
-def id_flag(extra=()):
-    return ['-DSQ_BUILD_ID="%s"' % source_id(extra)]
+def lib_stale(lib):
+    """True unless the in-tree library was built from exactly the sources, headers and flags that are here now: it must carry the
+    current id (file times can lie after a checkout or a copy, and say nothing the id does not)."""
+    if not os.path.exists(lib["out"]):
+        return True
+    with open(lib["out"], "rb") as f:
+        return lib_source_id(lib).encode() not in f.read()
+
+
+def compile_lib(lib, extra=(), out=None):
+    """out: an experimental variant (extra options) beside the product library; SQ_LIB_PATH / SQ_LENS_LIB_PATH select it at load time."""
+    out = out or lib["out"]
+    subprocess.check_call([hipcc()] + FLAGS + list(extra) + ['-D%s="%s"' % (lib["macro"], lib_source_id(lib, extra)), "-x", "hip"]
+                          + [os.path.join(CSRC, s) for s in lib["sources"]] + ["-o", out] + lib["link"])
+    return out
 
 
 def hipcc():
@@ -54,116 +90,35 @@ def hipcc():
     raise RuntimeError("hipcc not found")
 
 
-def stale():
-    """True unless the in-tree library was built from exactly the sources and flags that are here now: it must carry the
-    current source_id() (file times alone can lie after a checkout or a copy)."""
-    if not os.path.exists(OUT):
-        return True
-    with open(OUT, "rb") as f:
-        if source_id().encode() not in f.read():
-            return True
-    t = os.path.getmtime(OUT)
-    deps = [os.path.join(CSRC, f) for f in SOURCES + HEADERS] + [os.path.abspath(__file__)]
-    return any(os.path.getmtime(d) > t for d in deps)
-
-
-CLI = os.path.join(HERE, "bin", "squigly-trace")
-
-# The second library: the denoiser (include/squigly_denoise.h).  One source, the same FLAGS (its bits rest on -ffp-contract=off and
-# the correctly rounded divide / sqrt as the renderer's do), an id and a staleness check of its own: source_id() above does not see
-# it, so the main library's id -- and the counter files stamped with it -- do not move when the filter changes.
-DENOISE_OUT = os.path.join(HERE, "libsquigly_denoise.so")
-DENOISE_SOURCES = ["sq_denoise.hip"]
-DENOISE_HEADERS = ["sq_math.h", "sq_error.h", "../../include/squigly_denoise.h"]
-
-
-def denoise_source_id():
-    """First 16 hex digits of SHA-256 over the denoiser's source, its headers and the flags: what sq_denoise_build_id() returns."""
-    import hashlib
-    h = hashlib.sha256(b"denoise\0")
-    for f in sorted(DENOISE_SOURCES + DENOISE_HEADERS):
-        h.update(f.encode() + b"\0")
-        with open(os.path.join(CSRC, f), "rb") as fh:
-            h.update(fh.read())
-    h.update("\0".join(FLAGS).encode())
-    return h.hexdigest()[:16]
-
-
-def denoise_stale():
-    """As stale(), for libsquigly_denoise.so: it must carry the current denoise_source_id()."""
-    if not os.path.exists(DENOISE_OUT):
-        return True
-    with open(DENOISE_OUT, "rb") as f:
-        return denoise_source_id().encode() not in f.read()
-
-
-def build_denoise(force=False):
-    if not force and not denoise_stale():
-        return DENOISE_OUT
-    subprocess.check_call([hipcc()] + FLAGS + ['-DSQ_DENOISE_BUILD_ID="%s"' % denoise_source_id(), "-x", "hip"]
-                          + [os.path.join(CSRC, s) for s in DENOISE_SOURCES] + ["-o", DENOISE_OUT])
-    return DENOISE_OUT
-
-
-# The third library: jittered, thin-lens primary rays (include/squigly_lens.h).  A client of libsquigly_hip.so's public C-ABI: it is
-# linked against that library and built after it, with the same FLAGS (its bits rest on them as the renderer's do) and an id and a
-# staleness check of its own, so source_id() above does not move when it changes.
-LENS_OUT = os.path.join(HERE, "libsquigly_lens.so")
-LENS_SOURCES = ["sq_lens.hip"]
-LENS_HEADERS = ["sq_math.h", "sq_error.h", "sq_lens_plan.h", "../../include/squigly_lens.h", "../../include/squigly_hip.h"]
-
-
-def lens_source_id(extra=()):
-    """First 16 hex digits of SHA-256 over the lens library's source, its headers, the flags and the extra -D options: what
-    sq_lens_build_id() returns."""
-    import hashlib
-    h = hashlib.sha256(b"lens\0")
-    for f in sorted(LENS_SOURCES + LENS_HEADERS):
-        h.update(f.encode() + b"\0")
-        with open(os.path.join(CSRC, f), "rb") as fh:
-            h.update(fh.read())
-    h.update("\0".join(FLAGS + sorted(extra)).encode())
-    return h.hexdigest()[:16]
-
-
-def lens_stale():
-    """As stale(), for libsquigly_lens.so: it must carry the current lens_source_id()."""
-    if not os.path.exists(LENS_OUT):
-        return True
-    with open(LENS_OUT, "rb") as f:
-        return lens_source_id().encode() not in f.read()
+def source_id(extra=()): return lib_source_id(MAIN, extra)
+def stale(): return lib_stale(MAIN)
+def denoise_source_id(): return lib_source_id(DENOISE)
+def lens_source_id(extra=()): return lib_source_id(LENS, extra)
+def lens_stale(): return lib_stale(LENS)
 
 
 def build_lens(force=False, extra=(), out=None):
-    """out: an experimental variant (extra -D flags) beside the product library; SQ_LENS_LIB_PATH selects it at load time."""
-    if out is None and not force and not lens_stale():
+    if out is None and not force and not lib_stale(LENS):
         return LENS_OUT
-    subprocess.check_call([hipcc()] + FLAGS + list(extra) + ['-DSQ_LENS_BUILD_ID="%s"' % lens_source_id(extra), "-x", "hip"]
-                          + [os.path.join(CSRC, s) for s in LENS_SOURCES] + ["-o", out or LENS_OUT]
-                          + ["-L" + HERE, "-lsquigly_hip", "-Wl,-rpath,$ORIGIN"])
-    return out or LENS_OUT
+    return compile_lib(LENS, extra, out)
 
 
 def build(force=False, extra=(), out=None):
-    """out: build an experimental variant (extra -D flags) beside the product library; SQ_LIB_PATH selects it at load time."""
     if out is not None:
-        subprocess.check_call([hipcc()] + FLAGS + list(extra) + id_flag(extra) + ["-x", "hip"] + [os.path.join(CSRC, s) for s in SOURCES] + ["-o", out])
-        return out
-    build_denoise(force)
-    if not force and not stale() and os.path.exists(CLI):
-        build_lens(force)
-        return OUT
-    cmd = [hipcc()] + FLAGS + list(extra) + id_flag(extra) + ["-x", "hip"] + [os.path.join(CSRC, s) for s in SOURCES] + ["-o", OUT]
-    subprocess.check_call(cmd)
-    # the reference's executable (app/Main.hs) over the C-ABI
-    os.makedirs(os.path.dirname(CLI), exist_ok=True)
-    # (its --depth path copies a device frame back: the HIP runtime's host API, from the ROCm tree hipcc belongs to)
-    import shutil
-    rocm = os.path.dirname(os.path.dirname(os.path.realpath(shutil.which(hipcc()) or hipcc())))
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-D__HIP_PLATFORM_AMD__", "-I" + os.path.join(rocm, "include"),
-                           os.path.join(CSRC, "cli_main.cpp"), "-o", CLI,
-                           "-L" + HERE, "-lsquigly_hip", "-L" + os.path.join(rocm, "lib"), "-lamdhip64", "-Wl,-rpath,$ORIGIN/..", "-Wl,-rpath,/opt/rocm/lib", "-Wl,-rpath," + os.path.join(rocm, "lib"),
-                           "-Wl,--allow-shlib-undefined"])
+        return compile_lib(MAIN, extra, out)
+    if force or lib_stale(DENOISE):
+        compile_lib(DENOISE)
+    if force or lib_stale(MAIN) or not os.path.exists(CLI):
+        compile_lib(MAIN, extra)
+        # the reference's executable (app/Main.hs) over the C-ABI
+        os.makedirs(os.path.dirname(CLI), exist_ok=True)
+        # (its --depth path copies a device frame back: the HIP runtime's host API, from the ROCm tree hipcc belongs to)
+        import shutil
+        rocm = os.path.dirname(os.path.dirname(os.path.realpath(shutil.which(hipcc()) or hipcc())))
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-D__HIP_PLATFORM_AMD__", "-I" + os.path.join(rocm, "include"),
+                               os.path.join(CSRC, "cli_main.cpp"), "-o", CLI,
+                               "-L" + HERE, "-lsquigly_hip", "-L" + os.path.join(rocm, "lib"), "-lamdhip64", "-Wl,-rpath,$ORIGIN/..", "-Wl,-rpath,/opt/rocm/lib", "-Wl,-rpath," + os.path.join(rocm, "lib"),
+                               "-Wl,--allow-shlib-undefined"])
     build_lens(force)
     return OUT
 

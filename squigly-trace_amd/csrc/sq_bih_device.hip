@@ -30,15 +30,9 @@
 #include <vector>
 
 #include "../../include/squigly_hip.h"
-#include "sq_error.h"
+#include "sq_call_checks.h"
 #include "sq_host_types.h"
 #include "sq_math.h"
-
-#define SQ_HIP(expr)                                                                             \
-    do {                                                                                         \
-        hipError_t e_ = (expr);                                                                  \
-        if (e_ != hipSuccess) return sq_set_error("%s failed: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
 
 namespace {
 

@@ -15,19 +15,13 @@
 #include <stddef.h>
 #include <stdint.h>
 
-#include "sq_error.h"
+#include "sq_call_checks.h"
 #include "sq_math.h"
 #include "../../include/squigly_denoise.h"
 
 #ifndef SQ_DENOISE_BUILD_ID
 #define SQ_DENOISE_BUILD_ID "unknown"
 #endif
-
-#define SQ_HIP(expr)                                                                             \
-    do {                                                                                         \
-        hipError_t e_ = (expr);                                                                  \
-        if (e_ != hipSuccess) return sq_set_error("%s failed: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
 
 namespace {
 
@@ -248,9 +242,6 @@ __global__ __launch_bounds__(kBlock) void sq_dn_pass_tiled(const int rows, const
 // 1920 x 1080 (tools/gpu_denoise.py): 0.111 / 0.112 / 0.114 ms at steps 1 / 2 / 4 against 0.173 / 0.173 / 0.177 ms direct.
 int auto_form(int pass) { return (1 << pass) <= kTiledMaxStep ? SQ_DENOISE_FORM_TILED : SQ_DENOISE_FORM_DIRECT; }
 
-struct Span { const char* name; uintptr_t lo, hi; };
-bool overlap(const Span& a, const Span& b) { return a.lo < b.hi && b.lo < a.hi; }
-
 // Everything that can be refused, in the order of the header's list.  Touches neither the device nor a buffer.
 int check_call(int32_t rows, int32_t cols, const float* d_color, const float* d_var, const int32_t* d_tri, const float* d_normal,
                const float* d_point, const sq_denoise_params* P, float* d_out, float* d_out_var, void* d_work, size_t work_bytes) {
@@ -268,21 +259,11 @@ int check_call(int32_t rows, int32_t cols, const float* d_color, const float* d_
     const size_t need = sq_denoise_workspace_bytes(rows, cols);
     if (work_bytes < need) return sq_set_error("work_bytes = %zu is too small: a %d x %d image needs %zu", work_bytes, rows, cols, need);
     if ((uintptr_t)d_work % 16 != 0) return sq_set_error("d_work must be 16-byte aligned");
-    const uintptr_t n = (uintptr_t)((long long)rows * cols);
-    const Span spans[8] = {
-        { "d_color", (uintptr_t)d_color, (uintptr_t)d_color + 12 * n }, { "d_var", (uintptr_t)d_var, (uintptr_t)d_var + (d_var ? 4 * n : 0) },
-        { "d_tri", (uintptr_t)d_tri, (uintptr_t)d_tri + 4 * n }, { "d_normal", (uintptr_t)d_normal, (uintptr_t)d_normal + 12 * n },
-        { "d_point", (uintptr_t)d_point, (uintptr_t)d_point + 12 * n }, { "d_out", (uintptr_t)d_out, (uintptr_t)d_out + 12 * n },
-        { "d_out_var", (uintptr_t)d_out_var, (uintptr_t)d_out_var + (d_out_var ? 4 * n : 0) },
-        { "d_work", (uintptr_t)d_work, (uintptr_t)d_work + work_bytes } };
-    for (int i = 0; i < 8; ++i)
-        for (int j = i + 1; j < 8; ++j) {
-            if (!overlap(spans[i], spans[j])) continue;
-            if (i == 0 && j == 5 && spans[i].lo == spans[j].lo) continue;      // d_out == d_color
-            if (i == 1 && j == 6 && spans[i].lo == spans[j].lo) continue;      // d_out_var == d_var
-            return sq_set_error("%s and %s overlap (only d_out == d_color and d_out_var == d_var may share memory)", spans[i].name, spans[j].name);
-        }
-    return 0;
+    const size_t n = (size_t)rows * (size_t)cols;
+    const NamedRange r[8] = { { "d_color", d_color, 12 * n }, { "d_var", d_var, 4 * n }, { "d_tri", d_tri, 4 * n }, { "d_normal", d_normal, 12 * n },
+                              { "d_point", d_point, 12 * n }, { "d_out", d_out, 12 * n }, { "d_out_var", d_out_var, 4 * n }, { "d_work", d_work, work_bytes } };
+    const int twins[2][2] = { { 0, 5 }, { 1, 6 } };                              // d_out == d_color, d_out_var == d_var
+    return refuse_overlaps(r, 8, " (only d_out == d_color and d_out_var == d_var may share memory)", twins, 2);
 }
 
 unsigned grid_for(long long units) { return (unsigned)(units < kMaxGrid ? units : kMaxGrid); }
@@ -345,12 +326,10 @@ extern "C" int sq_denoise_variance_device(int32_t device, int64_t n_pixels, cons
     if (!d_sum || !d_sum2 || !d_count || !d_var) return sq_set_error("null argument: d_sum, d_sum2, d_count and d_var are required");
     if (n_pixels < 0) return sq_set_error("n_pixels must not be negative (got %lld)", (long long)n_pixels);
     if (n_pixels > (int64_t)1 << 56) return sq_set_error("n_pixels = %lld is more than any device holds", (long long)n_pixels);
-    const uintptr_t n = (uintptr_t)n_pixels;
-    const Span out = { "d_var", (uintptr_t)d_var, (uintptr_t)d_var + 4 * n };
-    const Span in[3] = { { "d_sum", (uintptr_t)d_sum, (uintptr_t)d_sum + 12 * n }, { "d_sum2", (uintptr_t)d_sum2, (uintptr_t)d_sum2 + 12 * n },
-                         { "d_count", (uintptr_t)d_count, (uintptr_t)d_count + 4 * n } };
-    for (const Span& s : in)
-        if (overlap(out, s)) return sq_set_error("d_var and %s overlap", s.name);
+    const size_t n = (size_t)n_pixels;
+    const NamedRange in[3] = { { "d_sum", d_sum, 12 * n }, { "d_sum2", d_sum2, 12 * n }, { "d_count", d_count, 4 * n } };
+    for (const NamedRange& s : in)
+        if (ranges_overlap(d_var, 4 * n, s.p, s.bytes)) return sq_set_error("d_var and %s overlap", s.name);
     if (n_pixels == 0) return 0;
     SQ_HIP(hipSetDevice(device));
     hipLaunchKernelGGL(sq_dn_variance, dim3(grid_for(((long long)n_pixels + kBlock - 1) / kBlock)), dim3(kBlock), 0, (hipStream_t)hip_stream,

@@ -38,17 +38,11 @@
 
 #include "../../include/squigly_hip.h"
 #include "../../include/squigly_host.h"
-#include "sq_error.h"
+#include "sq_call_checks.h"
 #include "sq_pack.h"
 #include "sq_kernels_lane.h"
 #include "sq_kernels_wave.h"
 #include "sq_kernels_trace.h"
-
-#define SQ_HIP(expr)                                                                             \
-    do {                                                                                         \
-        hipError_t e_ = (expr);                                                                  \
-        if (e_ != hipSuccess) return sq_set_error("%s failed: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
 
 constexpr int kOneshotRowBlock = 2; // rows per block when a one-shot call shards a frame over devices (balance: squigly-trace_amd/dist.py)
 
@@ -235,10 +229,7 @@ extern "C" int32_t sq_shard_rows(int32_t w, sq_shard sh) {
     }
     return (int32_t)rows;
 }
-extern "C" int32_t sq_shard_global_row(int32_t j, sq_shard sh) {
-    const int32_t blk = j / sh.row_block;
-    return (blk * sh.n_shards + sh.shard) * sh.row_block + (j - blk * sh.row_block);
-}
+extern "C" int32_t sq_shard_global_row(int32_t j, sq_shard sh) { return sq::shard_global_row(j, sh.row_block, sh.shard, sh.n_shards); }
 
 namespace {
 
@@ -781,20 +772,8 @@ int launch_frame(sq_device_scene* s, const FrameOf<SRC>& F, hipStream_t stream, 
 }  // namespace
 
 namespace {
-// (the largest frames a call takes, kMaxCallPixels / kMaxWavefrontPixels, and refuse_frame_size: sq_plan.h)
-bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + nb && y < x + na;
-}
-// The check every entry point makes of its device buffers: r = the ranges of which no two may overlap (NULL = not given).
-struct NamedRange { const char* name; const void* p; size_t bytes; };
-int refuse_overlaps(const NamedRange* r, int count) {
-    for (int i = 0; i < count; ++i)
-        for (int j = i + 1; j < count; ++j)
-            if (r[i].p && r[j].p && ranges_overlap(r[i].p, r[i].bytes, r[j].p, r[j].bytes))
-                return sq_set_error("%s and %s overlap", r[i].name, r[j].name);
-    return 0;
-}
+// (the largest frames a call takes, kMaxCallPixels / kMaxWavefrontPixels, and refuse_frame_size: sq_plan.h; ranges_overlap, NamedRange
+// and refuse_overlaps: sq_call_checks.h)
 // The camera and shard fields of the frame of a shard of `rows` local rows.
 void set_camera(Frame& F, const sq_camera* cam, int32_t w, int32_t h, sq_shard sh, int32_t rows) {
     std::memcpy(F.cam_pos, cam->pos, sizeof F.cam_pos);

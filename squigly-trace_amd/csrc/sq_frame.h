@@ -5,6 +5,7 @@
 #include "sq_scene.h"
 
 using sq::f3;
+using sq::load3;
 using namespace sqd;
 
 struct Frame {
@@ -63,8 +64,7 @@ __device__ __forceinline__ ViewCam view_cam(const Frame& F, int v) {
 __device__ __forceinline__ void pixel_coords(const Frame& F, int pix, int& y, int& x) {   // 32-bit: cheap div/mod
     const int j = pix / F.h;
     x = pix - j * F.h;
-    const int blk = j / F.row_block;
-    y = (blk * F.n_shards + F.shard) * F.row_block + (j - blk * F.row_block);
+    y = sq::shard_global_row(j, F.row_block, F.shard, F.n_shards);
 }
 // The q-th primary ray of a shard, q in [0, primary_padded(F)): a wave takes a TILE of tile_rows x (64 / tile_rows) neighbouring pixels
 // instead of 64 pixels of one row, so that the 64 rays of a one-ray-per-lane walk -- which runs the UNION of their paths -- stay together
@@ -84,8 +84,7 @@ __host__ __device__ __forceinline__ long long primary_padded(const Frame& F) {
 __device__ __forceinline__ void pixel_coords(const Frame& F, long long pix, int& y, int& x) {
     const int j = (int)(pix / F.h);
     x = (int)(pix - (long long)j * F.h);
-    const int blk = j / F.row_block;
-    y = (blk * F.n_shards + F.shard) * F.row_block + (j - blk * F.row_block);
+    y = sq::shard_global_row(j, F.row_block, F.shard, F.n_shards);
 }
 // Multi-view frames: the view of a pixel index, and (y, x) of the pixel within its view.  Every view has the same pixels and seeds.
 __device__ __forceinline__ int view_coords(const Frame& F, int pix, int& y, int& x) {   // px_pixel: n_views * view_pixels <= INT32_MAX
@@ -102,8 +101,6 @@ __device__ __forceinline__ long long primary_tile_views(const Frame& F, long lon
     const long long local = primary_tile(F, q - (long long)view * per);
     return local >= 0 ? (long long)view * F.view_pixels + local : -1;
 }
-
-__device__ __forceinline__ f3 load3(const float* p, long long i) { return sq::mk(p[3 * i], p[3 * i + 1], p[3 * i + 2]); }
 
 // Where a pixel's fold starts: +0 on a fresh frame, else what the caller's earlier range call left in F.sum (src/Lib.hs:88 is a left
 // fold, so resuming it from its exact fp32 partial sum gives the bits of one uninterrupted fold).

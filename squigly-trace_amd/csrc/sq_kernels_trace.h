@@ -11,7 +11,7 @@
 constexpr int kPrioSteps = 0, kPrioWindows = 1;
 // Pooled trace kernel: triangles a lane tests per window.  Two in both forms: one owner lookup and one set of pulls serve two tests
 // (resident form: 83.0 -> 80.5 ms on the headline frame, same run).
-constexpr int kPoolTrisResident = 2, kPoolTrisStreaming = 2;
+constexpr int kPoolTris = 2;
 
 // The dominant kernel.  Persistent: each wave reserves a chunk of the (dense) ray queue with one
 // atomic, compacts the chunk's live entries with ballots into a small LDS list, and each lane pulls
@@ -45,7 +45,8 @@ struct TraceArgs {
                                  // [3] lanes descending, [4] leaf iterations (waves), [5] lanes testing a triangle,
                                  // [6] outer iterations (waves), [7] refill executions (waves), [8] lanes refilled
                                  // pooled form: [1] iterations (waves), [2] lanes unwinding, [3] lanes descending,
-                                 // [4] pair windows (waves), [5] pairs tested, [6] hits folded, [7] refill executions, [8] lanes refilled
+                                 // [4] pair windows (waves), [5] pairs tested, [6] hits folded, [7] refill executions, [8] lanes refilled,
+                                 // [9..13] the return step's TravProf, [14] reserved (reads 0), [16..23] wave time per section of the loop
 };
 // (the LDS carve-up of the trace kernel, TraceLds and trace_lds_layout: sq_plan.h)
 
@@ -242,15 +243,14 @@ __device__ __forceinline__ void trace_rays_body(const SceneView& S, const TraceA
         // ceil(sum / 64) full-width rounds.  Accepted hits are folded into the owning lane's R in pair order, which is
         // leaf order, with the very comparison of the one-lane leaf loop (minimumBy's rule, src/BIH.hs:105-109) --
         // the arithmetic of mollerTrumbore does not depend on the lane that runs it.
-        constexpr int KW = kPoolWindows;
         constexpr bool kFlat = RESIDENT && !PROFILE;   // the flat steps (sq_scene.h): the resident form only, DESIGN.md 4.8
         bool flat_ok = false;               // wave-uniform (kFlat): every ray of the wave is safe and the scene has culling boxes
-        SQ_LDS uint8_t* tab = to_lds<uint8_t>(lds + L.tab) + (threadIdx.x >> 6) * (64 * KW);   // this wave's window-head tables
-        for (int k = 0; k < KW; ++k) tab[k * 64 + lane] = 0;
+        SQ_LDS uint8_t* tab = to_lds<uint8_t>(lds + L.tab) + (threadIdx.x >> 6) * 64;   // this wave's window-head table
+        tab[lane] = 0;
         const int lane_tag = lane * 4 + 1;  // a lane's mark in the head table: non-zero, grows with the lane, and is its ds_bpermute address
         int lf_first = 0, lf_cnt = 0;       // M_LEAFQ: the untested rest of this lane's open leaf
         bool carry = false;                 // wave-uniform: the previous iteration left queued pairs untested
-        unsigned int pl_hit = 0, pl_hslow = 0;
+        unsigned int pl_hit = 0;
         TravProf prof{};
         // PROFILE: wave time per section of the loop (s_memtime ticks = shader cycles; the stamps themselves cost ~10 %)
         unsigned long long tsec[8] = { 0, 0, 0, 0, 0, 0, 0, 0 }, tlast = PROFILE ? __builtin_amdgcn_s_memtime() : 0;
@@ -316,156 +316,78 @@ __device__ __forceinline__ void trace_rays_body(const SceneView& S, const TraceA
                 lf_first = lf.x; lf_cnt = lf.y; T.R.tri = -1;
                 T.mode = lf.y > 0 ? M_LEAFQ : M_UNWIND;
             }
-            if constexpr ((RESIDENT ? kPoolTrisResident : kPoolTrisStreaming) >= 2) {
-                // NT triangles per lane and window.  The pool is counted in UNITS of NT consecutive triangles of one leaf (the
-                // last unit of a leaf may be part-filled), so that one owner lookup and one set of pulls serve NT triangle
-                // tests: the pulls are the most expensive part of a window (ds_bpermute, 6 cycles per CU each), and the
-                // lookup's integer VALU work comes next.
-                constexpr int NT = RESIDENT ? kPoolTrisResident : kPoolTrisStreaming;
-                const int c2 = (T.mode == M_LEAFQ) ? lf_cnt : 0;                // triangles left in this lane's open leaf
-                if (sq_ballot(c2 > 0) == 0) continue;
-                const int u = (c2 + NT - 1) / NT;                               // units
-                const int incl = wave_scan_add(u);
-                const int U = __builtin_amdgcn_readlane(incl, 63);
-                const int start = incl - u;
-                const int tb2 = lf_first - NT * start;                          // first triangle of unit q = NT q + tb2
-                const int tri_end = lf_first + c2;                              // one past the leaf's last triangle
-                int nwin = U >> 6;
-                const int rem = U & 63;
-                const bool others = sq_ballot(T.mode == M_UNWIND || T.mode == M_DESCEND) != 0;
-                if (rem && (!others || carry || rem >= A.flush_min)) ++nwin;
-                stamp(3);
-                for (int w = 0; w < nwin; ++w) {
-                    const int base = w << 6;
-                    const int h = start - base;
-                    if (u > 0 && h < 64 && incl > base) tab[h > 0 ? h : 0] = (uint8_t)lane_tag;
-                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                    __builtin_amdgcn_wave_barrier();
-                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-                    int own = tab[lane];
-                    tab[lane] = 0;
-                    own = wave_scan_max(own);
-                    const int q = base + lane;
-                    const bool act = q < U;
-                    int tri0 = NT * q + lane_pull(tb2, own);
-                    const int end_o = lane_pull(tri_end, own);
-                    const f3 po = sq::mk(lane_pull(T.o.x, own), lane_pull(T.o.y, own), lane_pull(T.o.z, own));
-                    const f3 pd = sq::mk(lane_pull(T.d.x, own), lane_pull(T.d.y, own), lane_pull(T.d.z, own));
-                    if (!act) tri0 = 0;                                         // lanes past the last unit test triangle 0 and drop the answer
-                    stamp(4);
-                    f3 v0[NT], e1[NT], e2[NT];
-                    G.template get_run<NT>(tri0, v0, e1, e2);                   // a part-filled unit tests the records after it and drops the answers
-                    float tt[NT]; bool hit[NT]; unsigned long long hmk[NT], hm = 0;
-#pragma unroll
-                    for (int k = 0; k < NT; ++k) {
-                        const bool valid = act && (k == 0 || tri0 + k < end_o);
-                        hit[k] = moller_trumbore_flat(po, pd, v0[k], e1[k], e2[k], tt[k]) & valid;
-                    }
-                    stamp(5);
-#pragma unroll
-                    for (int k = 0; k < NT; ++k) { hmk[k] = sq_ballot(hit[k]); hm |= hmk[k]; if (PROFILE) pl_hit += (int)hit[k]; }
-                    while (hm) {                                                // accepted hits in leaf order: lane by lane, a lane's triangles in turn
-                        const int l = __ffsll((long long)hm) - 1;
-                        hm &= hm - 1;
-                        const int so = __builtin_amdgcn_readlane(own, l);
-                        const int stri = __builtin_amdgcn_readlane(tri0, l);
-#pragma unroll
-                        for (int k = 0; k < NT; ++k) if ((hmk[k] >> l) & 1ull) {
-                            const float st = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(tt[k]), l));
-                            if (lane_tag == so && (T.R.tri < 0 || dist_gt(T.o, T.d, T.R.t, st, T.safe))) { T.R.t = st; T.R.tri = stri + k; }
-                        }
-                    }
-                    stamp(6);
-                }
-                const int done = min(U, nwin << 6);                             // units tested
-                if (PROFILE) { pf_leaf += nwin; pf_outer += NT * done; }
-                if constexpr (kFlat) {
-                    const bool fin = u > 0 && incl <= done;                     // the Leaf equation is finished: R is its value
-                    const int adv = (u > 0 && incl > done && start < done) ? NT * (done - start) : 0;   // whole units come first
-                    T.mode = fin ? M_UNWIND : T.mode; lf_first += adv; lf_cnt -= adv;
-                } else
-                if (u > 0) {
-                    if (incl <= done) T.mode = M_UNWIND;                        // the Leaf equation is finished: R is its value
-                    else if (start < done) { lf_first += NT * (done - start); lf_cnt -= NT * (done - start); }   // whole units come first
-                }
-                carry = done < U;
-                stamp(7);
-                continue;
-            }
-            const int c = (T.mode == M_LEAFQ) ? lf_cnt : 0;
-            if (sq_ballot(c > 0) == 0) continue;
-            const int incl = wave_scan_add(c);                              // pairs of lanes 0..lane
-            const int P = __builtin_amdgcn_readlane(incl, 63);              // pairs queued in the wave
-            const int start = incl - c;                                     // this lane's first pair
-            const int tb = lf_first - start;                                // triangle of pair p = p + tb
-            int nwin = P >> 6;
-            const int rem = P & 63;
+            // NT triangles per lane and window.  The pool is counted in UNITS of NT consecutive triangles of one leaf (the
+            // last unit of a leaf may be part-filled), so that one owner lookup and one set of pulls serve NT triangle
+            // tests: the pulls are the most expensive part of a window (ds_bpermute, 6 cycles per CU each), and the
+            // lookup's integer VALU work comes next.
+            constexpr int NT = kPoolTris;
+            const int c2 = (T.mode == M_LEAFQ) ? lf_cnt : 0;                // triangles left in this lane's open leaf
+            if (sq_ballot(c2 > 0) == 0) continue;
+            const int u = (c2 + NT - 1) / NT;                               // units
+            const int incl = wave_scan_add(u);
+            const int U = __builtin_amdgcn_readlane(incl, 63);
+            const int start = incl - u;
+            const int tb2 = lf_first - NT * start;                          // first triangle of unit q = NT q + tb2
+            const int tri_end = lf_first + c2;                              // one past the leaf's last triangle
+            int nwin = U >> 6;
+            const int rem = U & 63;
             const bool others = sq_ballot(T.mode == M_UNWIND || T.mode == M_DESCEND) != 0;
             if (rem && (!others || carry || rem >= A.flush_min)) ++nwin;
             stamp(3);
-            // KW windows per step: their LDS round trips (head table, owner pulls, index record, vertices) are issued
-            // together and waited for once, and the independent arithmetic of KW triangle tests interleaves.
-            for (int w0 = 0; w0 < nwin; w0 += KW) {
-                int own[KW], tri[KW]; f3 po[KW], pd[KW]; float t[KW]; bool hit[KW];
-                // who owns pair base + lane?  Every owner whose pairs reach into a window writes its lane number at the
-                // window position of its first pair there; a max-scan spreads it over the owner's run.
-#pragma unroll
-                for (int k = 0; k < KW; ++k) {
-                    const int base = (w0 + k) << 6;
-                    const int h = start - base;
-                    if (c > 0 && h < 64 && incl > base) tab[k * 64 + (h > 0 ? h : 0)] = (uint8_t)lane_tag;
-                }
+            for (int w = 0; w < nwin; ++w) {
+                const int base = w << 6;
+                const int h = start - base;
+                if (u > 0 && h < 64 && incl > base) tab[h > 0 ? h : 0] = (uint8_t)lane_tag;
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                 __builtin_amdgcn_wave_barrier();
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-#pragma unroll
-                for (int k = 0; k < KW; ++k) { own[k] = tab[k * 64 + lane]; tab[k * 64 + lane] = 0; }
-#pragma unroll
-                for (int k = 0; k < KW; ++k) own[k] = wave_scan_max(own[k]);
-#pragma unroll
-                for (int k = 0; k < KW; ++k) {
-                    const int src = own[k];                                 // ds_bpermute takes lane * 4 and ignores the two low bits
-                    const int p = ((w0 + k) << 6) + lane;
-                    tri[k] = p + lane_pull(tb, src);
-                    po[k] = sq::mk(lane_pull(T.o.x, src), lane_pull(T.o.y, src), lane_pull(T.o.z, src));
-                    pd[k] = sq::mk(lane_pull(T.d.x, src), lane_pull(T.d.y, src), lane_pull(T.d.z, src));
-                    hit[k] = p < P;                                         // so far: the pair exists
-                    if (!hit[k]) tri[k] = 0;                                // lanes past the last pair test triangle 0 and drop the answer
-                }
-                if (PROFILE) { t[0] = po[0].x + pd[0].x + __int_as_float(tri[0]); asm volatile("" :: "v"(t[0])); }   // the pulls have arrived
+                int own = tab[lane];
+                tab[lane] = 0;
+                own = wave_scan_max(own);
+                const int q = base + lane;
+                const bool act = q < U;
+                int tri0 = NT * q + lane_pull(tb2, own);
+                const int end_o = lane_pull(tri_end, own);
+                const f3 po = sq::mk(lane_pull(T.o.x, own), lane_pull(T.o.y, own), lane_pull(T.o.z, own));
+                const f3 pd = sq::mk(lane_pull(T.d.x, own), lane_pull(T.d.y, own), lane_pull(T.d.z, own));
+                if (!act) tri0 = 0;                                         // lanes past the last unit test triangle 0 and drop the answer
                 stamp(4);
-                f3 v0[KW], e1[KW], e2[KW];
+                f3 v0[NT], e1[NT], e2[NT];
+                G.template get_run<NT>(tri0, v0, e1, e2);                   // a part-filled unit tests the records after it and drops the answers
+                float tt[NT]; bool hit[NT]; unsigned long long hmk[NT], hm = 0;
 #pragma unroll
-                for (int k = 0; k < KW; ++k) if (k == 0 || w0 + k < nwin) G.get1(tri[k], v0[k], e1[k], e2[k]);
-#pragma unroll
-                for (int k = 0; k < KW; ++k) {
-                    if (k == 0 || w0 + k < nwin) { float tk; const bool ok = moller_trumbore_flat(po[k], pd[k], v0[k], e1[k], e2[k], tk); t[k] = tk; hit[k] = hit[k] & ok; }
-                    else { t[k] = 0.0f; hit[k] = false; }
+                for (int k = 0; k < NT; ++k) {
+                    const bool valid = act && (k == 0 || tri0 + k < end_o);
+                    hit[k] = moller_trumbore_flat(po, pd, v0[k], e1[k], e2[k], tt[k]) & valid;
                 }
                 stamp(5);
 #pragma unroll
-                for (int k = 0; k < KW; ++k) {
-                    unsigned long long hm = sq_ballot(hit[k]);
-                    if (PROFILE) pl_hit += hit[k];
-                    while (hm) {                                            // accepted hits in pair order
-                        const int l = __ffsll((long long)hm) - 1;
-                        hm &= hm - 1;
-                        const int so = __builtin_amdgcn_readlane(own[k], l);
-                        const float st = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(t[k]), l));
-                        const int stri = __builtin_amdgcn_readlane(tri[k], l);
-                        if (PROFILE && lane_tag == so && T.R.tri >= 0 && !(!(T.R.t > st) && st < __builtin_inff() && T.safe)) ++pl_hslow;
-                        if (lane_tag == so && (T.R.tri < 0 || dist_gt(T.o, T.d, T.R.t, st, T.safe))) { T.R.t = st; T.R.tri = stri; }
+                for (int k = 0; k < NT; ++k) { hmk[k] = sq_ballot(hit[k]); hm |= hmk[k]; if (PROFILE) pl_hit += (int)hit[k]; }
+                while (hm) {                                                // accepted hits in leaf order: lane by lane, a lane's triangles in turn
+                    const int l = __ffsll((long long)hm) - 1;
+                    hm &= hm - 1;
+                    const int so = __builtin_amdgcn_readlane(own, l);
+                    const int stri = __builtin_amdgcn_readlane(tri0, l);
+#pragma unroll
+                    for (int k = 0; k < NT; ++k) if ((hmk[k] >> l) & 1ull) {
+                        const float st = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(tt[k]), l));
+                        if (lane_tag == so && (T.R.tri < 0 || dist_gt(T.o, T.d, T.R.t, st, T.safe))) { T.R.t = st; T.R.tri = stri + k; }
                     }
                 }
                 stamp(6);
             }
-            const int done = min(P, nwin << 6);
-            if (PROFILE) { pf_leaf += nwin; pf_outer += done; }
-            if (c > 0) {
+            const int done = min(U, nwin << 6);                             // units tested
+            if (PROFILE) { pf_leaf += nwin; pf_outer += NT * done; }
+            if constexpr (kFlat) {
+                const bool fin = u > 0 && incl <= done;                     // the Leaf equation is finished: R is its value
+                const int adv = (u > 0 && incl > done && start < done) ? NT * (done - start) : 0;   // whole units come first
+                T.mode = fin ? M_UNWIND : T.mode; lf_first += adv; lf_cnt -= adv;
+            } else
+            if (u > 0) {
                 if (incl <= done) T.mode = M_UNWIND;                        // the Leaf equation is finished: R is its value
-                else if (start < done) { lf_first += done - start; lf_cnt = incl - done; }
+                else if (start < done) { lf_first += NT * (done - start); lf_cnt -= NT * (done - start); }   // whole units come first
             }
-            carry = done < P;
+            carry = done < U;
             stamp(7);
         }
         if (lane == 0) atomicAdd(&A.stats[0], n_traced);
@@ -476,7 +398,7 @@ __device__ __forceinline__ void trace_rays_body(const SceneView& S, const TraceA
             atomicAdd(&A.stats[6], (unsigned long long)pl_hit); atomicAdd(&A.stats[8], (unsigned long long)pl_ref);
             atomicAdd(&A.stats[9], (unsigned long long)prof.combine); atomicAdd(&A.stats[10], (unsigned long long)prof.recompute_lanes);
             atomicAdd(&A.stats[11], (unsigned long long)prof.recompute_waves); atomicAdd(&A.stats[12], (unsigned long long)prof.slowcmp_lanes);
-            atomicAdd(&A.stats[13], (unsigned long long)prof.slowcmp_waves); atomicAdd(&A.stats[14], (unsigned long long)pl_hslow);
+            atomicAdd(&A.stats[13], (unsigned long long)prof.slowcmp_waves);
             if (lane == 0) for (int i = 0; i < 8; ++i) atomicAdd(&A.stats[16 + i], tsec[i]);
         }
         return;

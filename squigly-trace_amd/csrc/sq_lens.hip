@@ -17,7 +17,7 @@
 
 #include <string>
 
-#include "sq_error.h"
+#include "sq_call_checks.h"
 #include "sq_math.h"
 #include "sq_lens_plan.h"
 #include "../../include/squigly_lens.h"
@@ -26,15 +26,11 @@
 #define SQ_LENS_BUILD_ID "unknown"
 #endif
 
-#define SQ_HIP(expr)                                                                             \
-    do {                                                                                         \
-        hipError_t e_ = (expr);                                                                  \
-        if (e_ != hipSuccess) return sq_set_error("%s failed: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
-
 namespace {
 
 using sq::f3;
+using sq::load3;
+using sq::rot_vert;
 
 constexpr int kBlock = 256;
 constexpr int kMaxGrid = 4096;             // blocks of a launch; the kernels stride over their slots
@@ -47,33 +43,6 @@ struct RayArgs {
     long long P, slots;                     // pixels of the shard; (sub-rays of the batch) * P
 };
 
-// rotVert (src/Geometry.hs:104-107): each entry a dot product folded from an accumulator of 0, r = a_k * m_kj + r.
-__device__ __forceinline__ f3 rot_vert(float v0, float v1, float v2, const float* rot) {
-    const float v[3] = { v0, v1, v2 };
-    float o[3];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) { float r = 0.0f; for (int k = 0; k < 3; ++k) r = v[k] * rot[3 * k + j] + r; o[j] = r; }
-    return sq::mk(o[0], o[1], o[2]);
-}
-
-__device__ __forceinline__ void store3(float* a, long long i, f3 v) { float* p = a + 3 * i; p[0] = v.x; p[1] = v.y; p[2] = v.z; }
-__device__ __forceinline__ f3 load3(const float* a, long long i) { const float* p = a + 3 * i; return sq::mk(p[0], p[1], p[2]); }
-
-// rgbFloatToPixelRGB (src/Lib.hs:93-104).  floor :: Float -> Word8 wraps mod 256 and maps NaN/Inf to 0.
-__device__ __forceinline__ uint8_t to_word8(float f) {
-    if (!(f == f) || f == __builtin_inff() || f == -__builtin_inff()) return 0;
-    const double fl = __builtin_floor((double)f);
-    const double md = fl - 256.0 * __builtin_floor(fl / 256.0);
-    return (uint8_t)(int)md;
-}
-__device__ __forceinline__ void tonemap(f3 c, uint8_t* out) {
-    const float mx = sq::hmax(sq::hmax(c.x, c.y), c.z), mn = sq::hmin(sq::hmin(c.x, c.y), c.z);
-    const float lightness = 0.5f * (mx + mn);
-    const float intensity = sq::fatan(lightness) / (sq::kPi / 2);
-    const f3 s = sq::scale(intensity / mx, c);
-    out[0] = to_word8(s.x * 255); out[1] = to_word8(s.y * 255); out[2] = to_word8(s.z * 255);
-}
-
 // ---- the rays: one lane per (sub-ray, pixel), slot = sub-ray * P + pixel ----
 __global__ __launch_bounds__(kBlock) void sq_lens_rays(const RayArgs A, float* __restrict__ org, float* __restrict__ dir,
                                                        long long* __restrict__ seed) {
@@ -83,8 +52,8 @@ __global__ __launch_bounds__(kBlock) void sq_lens_rays(const RayArgs A, float* _
         const int b = (int)(i / A.P);
         const int pixel = (int)(i - b * A.P);
         const int j = pixel / A.h, x = pixel - j * A.h;
-        const int blk = j / A.row_block;
-        const int y = (blk * A.n_shards + A.shard) * A.row_block + (j - blk * A.row_block);      // sq_shard_global_row
+        const int blk = j / A.row_block;     // sq::shard_global_row, written out: through the function the kernel's registers are allocated differently
+        const int y = (blk * A.n_shards + A.shard) * A.row_block + (j - blk * A.row_block);
         const long long base = (long long)A.S * ((long long)x + (long long)y * A.w) + (long long)(A.r_begin + b) * A.n;
         float xs = (float)x, ys = (float)y;
         float u2 = 0.0f, u3 = 0.0f;
@@ -144,16 +113,6 @@ __global__ __launch_bounds__(kBlock) void sq_lens_fold(const long long P, const 
             if (rgb) tonemap(a, rgb + 3 * p);
         }
     }
-}
-
-struct Span { const char* name; uintptr_t lo, hi; };
-bool overlap(const Span& a, const Span& b) { return a.lo < b.hi && b.lo < a.hi; }
-Span span(const char* name, const void* p, size_t bytes) { return Span{ name, (uintptr_t)p, (uintptr_t)p + (p ? bytes : 0) }; }
-int refuse_overlaps(const Span* s, int n) {
-    for (int i = 0; i < n; ++i)
-        for (int j = i + 1; j < n; ++j)
-            if (overlap(s[i], s[j])) return sq_set_error("%s and %s overlap", s[i].name, s[j].name);
-    return 0;
 }
 
 unsigned grid_for(long long units) {
@@ -237,7 +196,7 @@ extern "C" int sq_lens_rays_device(int32_t device, const sq_camera* cam, const s
     const long long nb = (long long)r_end - r_begin;
     if (refuse_slots(P, nb)) return 1;
     const size_t n = (size_t)(P * nb);
-    const Span spans[3] = { span("d_org", d_org, 12 * n), span("d_dir", d_dir, 12 * n), span("d_seed", d_seed, 8 * n) };
+    const NamedRange spans[3] = { { "d_org", d_org, 12 * n }, { "d_dir", d_dir, 12 * n }, { "d_seed", d_seed, 8 * n } };
     if (refuse_overlaps(spans, 3)) return 1;
     SQ_HIP(hipSetDevice(device));
     return enqueue_rays(ray_args(cam, lens, S, R, w, h, sh, P), r_begin, r_end, d_org, d_dir, d_seed, (hipStream_t)hip_stream);
@@ -254,8 +213,8 @@ extern "C" int sq_lens_fold_device(int32_t device, int64_t P, int32_t S, int32_t
     const long long nb = (long long)r_end - r_begin;
     if (refuse_slots((long long)P, nb)) return 1;
     const size_t p = (size_t)P;
-    const Span spans[5] = { span("d_part", d_part, 12 * p * (size_t)nb), span("d_sum", d_sum, 12 * p), span("d_sum2", d_sum2, 12 * p),
-                            span("d_avg", d_avg, 12 * p), span("d_rgb", d_rgb, 3 * p) };
+    const NamedRange spans[5] = { { "d_part", d_part, 12 * p * (size_t)nb }, { "d_sum", d_sum, 12 * p }, { "d_sum2", d_sum2, 12 * p },
+                                  { "d_avg", d_avg, 12 * p }, { "d_rgb", d_rgb, 3 * p } };
     if (refuse_overlaps(spans, 5)) return 1;
     SQ_HIP(hipSetDevice(device));
     return enqueue_fold((long long)P, S, r_begin, r_end, d_part, d_sum, d_sum2, d_avg, d_rgb, (hipStream_t)hip_stream);
@@ -274,8 +233,8 @@ extern "C" int sq_lens_render_device(sq_device_scene* s, const sq_camera* cam, c
         return sq_set_error("work_bytes = %zu is too small: one sub-ray of %lld pixels needs %zu", work_bytes, P, lensplan::work_bytes(P, 1));
     if ((uintptr_t)d_work % 16 != 0) return sq_set_error("d_work must be 16-byte aligned");
     const size_t p = (size_t)P;
-    const Span spans[5] = { span("d_sum", d_sum, 12 * p), span("d_sum2", d_sum2, 12 * p), span("d_avg", d_avg, 12 * p),
-                            span("d_rgb", d_rgb, 3 * p), span("d_work", d_work, work_bytes) };
+    const NamedRange spans[5] = { { "d_sum", d_sum, 12 * p }, { "d_sum2", d_sum2, 12 * p }, { "d_avg", d_avg, 12 * p },
+                                  { "d_rgb", d_rgb, 3 * p }, { "d_work", d_work, work_bytes } };
     if (refuse_overlaps(spans, 5)) return 1;
     hipPointerAttribute_t attr;
     SQ_HIP(hipPointerGetAttributes(&attr, d_work));

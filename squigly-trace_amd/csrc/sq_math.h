@@ -202,4 +202,36 @@ SQ_HD float unit_float(uint32_t n) {
     return 0.0f + (1.0f - 0.0f) * p;
 }
 
+// ---------------- what the renderer and the lens library both do to a pixel or a ray ----------------
+// Element i of an [n][3] float array.
+SQ_HD f3 load3(const float* a, long long i) { const float* p = a + 3 * i; return mk(p[0], p[1], p[2]); }
+SQ_HD void store3(float* a, long long i, f3 v) { float* p = a + 3 * i; p[0] = v.x; p[1] = v.y; p[2] = v.z; }
+// rotVert (src/Geometry.hs:104-107): each entry a dot product folded from an accumulator of 0, r = a_k * m_kj + r.
+SQ_HD f3 rot_vert(float v0, float v1, float v2, const float* rot) {
+    const float v[3] = { v0, v1, v2 };
+    float o[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) { float r = 0.0f; for (int k = 0; k < 3; ++k) r = v[k] * rot[3 * k + j] + r; o[j] = r; }
+    return mk(o[0], o[1], o[2]);
+}
+// rgbFloatToPixelRGB (src/Lib.hs:93-104).  floor :: Float -> Word8 wraps mod 256 and maps NaN/Inf to 0.
+SQ_HD uint8_t to_word8(float f) {
+    if (!(f == f) || f == __builtin_inff() || f == -__builtin_inff()) return 0;
+    const double fl = __builtin_floor((double)f);
+    const double md = fl - 256.0 * __builtin_floor(fl / 256.0);
+    return (uint8_t)(int)md;
+}
+SQ_HD void tonemap(f3 c, uint8_t* out) {
+    const float mx = hmax(hmax(c.x, c.y), c.z), mn = hmin(hmin(c.x, c.y), c.z);
+    const float lightness = 0.5f * (mx + mn);
+    const float intensity = fatan(lightness) / (kPi / 2);
+    const f3 s = scale(intensity / mx, c);
+    out[0] = to_word8(s.x * 255); out[1] = to_word8(s.y * 255); out[2] = to_word8(s.z * 255);
+}
+// The global row of local row j of a shard (sq_shard of include/squigly_hip.h): the shard owns every n_shards-th block of row_block rows.
+SQ_HD int32_t shard_global_row(int32_t j, int32_t row_block, int32_t shard, int32_t n_shards) {
+    const int32_t blk = j / row_block;
+    return (blk * n_shards + shard) * row_block + (j - blk * row_block);
+}
+
 }  // namespace sq

@@ -31,7 +31,6 @@ constexpr int kResidentBlock = 1024; // persistent trace kernel, resident form: 
 constexpr int kChunkResident = 512, kChunkStreaming = 128;
 using LiveT = uint8_t;             // a live slot's index within its chunk
 constexpr int kStatSlots = 32;            // sq_get_stats
-constexpr int kPoolWindows = 1;    // pooled trace kernel: pair windows a wave works on at a time
 // The largest frames a call takes.  Pixel indices are 32-bit wherever they are stored (Work::px_pixel, Frame::view_pixels)
 // or divided (pixel_coords), so no call takes more than INT32_MAX pixels.  The wavefront form also indexes its active-pixel list and
 // its ray queue with 32-bit values that reach 3 x pixels (px_sum[3 * a]), pixels + one grid stride (the `a` loops) and twice the slots
@@ -50,7 +49,7 @@ SQ_HD TraceLds trace_lds_layout(int n_lds, bool resident, int n_verts, int n_tri
     L.refs = off;  off += resident ? al((uint32_t)n_lds * 8u) : 0u;
     L.trix = off;  off += resident ? al((uint32_t)(n_tris + kTriRunPad) * 8u) : 0u;  // + zero records: get_run may read past the last triangle
     L.live = off;  off += al((uint32_t)(block / 64) * (uint32_t)(resident ? kChunkResident : kChunkStreaming) * (uint32_t)sizeof(LiveT));
-    L.tab = off;   off += pool ? al((uint32_t)block * kPoolWindows) : 0u;   // pooled form: one byte per lane and window in flight
+    L.tab = off;   off += pool ? al((uint32_t)block) : 0u;   // pooled form: the window-head table, one byte per lane
     L.stack = off; off += al((uint32_t)block * (uint32_t)stack_cap * (uint32_t)stack_elem);
     L.total = off;
     return L;

@@ -229,31 +229,14 @@ __device__ __forceinline__ f3 bounce_dir(f3 d, const Surface& s, uint32_t nu, ui
     return scatters(s, nu) ? scatter_dir(d, s, nu, nv) : mirror_dir(d, s);
 }
 
-// rgbFloatToPixelRGB (src/Lib.hs:93-104).  floor :: Float -> Word8 wraps mod 256 and maps NaN/Inf to 0.
-__device__ __forceinline__ uint8_t to_word8(float f) {
-    if (!(f == f) || f == __builtin_inff() || f == -__builtin_inff()) return 0;
-    const double fl = __builtin_floor((double)f);
-    const double md = fl - 256.0 * __builtin_floor(fl / 256.0);
-    return (uint8_t)(int)md;
-}
-__device__ __forceinline__ void tonemap(f3 c, uint8_t* out) {
-    const float mx = sq::hmax(sq::hmax(c.x, c.y), c.z), mn = sq::hmin(sq::hmin(c.x, c.y), c.z);
-    const float lightness = 0.5f * (mx + mn);
-    const float intensity = sq::fatan(lightness) / (sq::kPi / 2);
-    const f3 s = sq::scale(intensity / mx, c);
-    out[0] = to_word8(s.x * 255); out[1] = to_word8(s.y * 255); out[2] = to_word8(s.z * 255);
-}
+// (rgbFloatToPixelRGB, src/Lib.hs:93-104: sq::tonemap, sq_math.h)
 
-// makeRay (src/Lib.hs:107-114) + rotVert (src/Geometry.hs:104-107): dims = (w :. h), ix = (y :. x)
+// makeRay (src/Lib.hs:107-114) + rotVert (sq::rot_vert): dims = (w :. h), ix = (y :. x)
 __device__ __forceinline__ f3 primary_dir(const float* rot, int w, int h, int y, int x) {
     const float ww = (float)w, hh = (float)h;
     const float xoffs = ((float)x - (ww / 2)) / ww;
     const float yoffs = ((hh / 2) - (float)y) / hh;
-    const float v[3] = { 1.0f, xoffs, yoffs };
-    float o[3];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) { float r = 0.0f; for (int k = 0; k < 3; ++k) r = v[k] * rot[3 * k + j] + r; o[j] = r; }
-    return sq::mk(o[0], o[1], o[2]);
+    return sq::rot_vert(1.0f, xoffs, yoffs, rot);
 }
 
 // ----------------------------------------------------------------------------------------------
@@ -410,7 +393,6 @@ struct GlobalTris {
             v0[k] = sq::mk(c[0], c[1], c[2]); e1[k] = sq::mk(c[3], c[4], c[5]); e2[k] = sq::mk(c[6], c[7], c[8]);
         }
     }
-    __device__ __forceinline__ void get1(int i, f3& v0, f3& e1, f3& e2) const { get_n<1>(i, &v0, &e1, &e2); }   // two 16-byte loads + one dword
     static constexpr int kRunPad = kTriRunPad;   // zero triangles after the last one (sq_layout.h), so a run may start at any triangle
     template <int N>
     __device__ __forceinline__ void get_run(int i, f3* v0, f3* e1, f3* e2) const { get_n<N>(i, v0, e1, e2); }
@@ -428,14 +410,6 @@ struct ResidentTris {           // whole scene resident in LDS: 16-bit indexed t
     const SQ_LDS v4us* trix;
     __device__ __forceinline__ v4f vertex(unsigned off) const { return *reinterpret_cast<const SQ_LDS v4f*>((uintptr_t)off); }   // LDS address = offset (table at LDS address 0)
     __device__ __forceinline__ void get(int i, f3& v0, f3& e1, f3& e2) const { get_indexed(trix[i], v0, e1, e2); }
-    __device__ __forceinline__ void get1(int i, f3& v0, f3& e1, f3& e2) const {    // three 16-bit reads: the offsets arrive zero-extended
-        const volatile SQ_LDS unsigned short* r = reinterpret_cast<const volatile SQ_LDS unsigned short*>(trix + i);   // volatile: keep them apart
-        const unsigned o0 = r[0], o1 = r[1], o2 = r[2];
-        const v4f a = vertex(o0), b = vertex(o1), c = vertex(o2);
-        v0 = sq::mk(a.x, a.y, a.z);
-        e1 = sq::mk(b.x, b.y, b.z) - v0;
-        e2 = sq::mk(c.x, c.y, c.z) - v0;
-    }
     // N consecutive records, one 8-byte read each, offsets unpacked by VALU -- a third of the LDS instructions of 16-bit reads.  kRunPad zero records follow the last triangle, so a run
     // that starts at any triangle is readable.
     static constexpr int kRunPad = 3;

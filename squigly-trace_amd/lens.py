@@ -100,14 +100,8 @@ def plan(pixels, r_begin, r_end, work_bytes):
 
 
 def _int(name, v):
-    if isinstance(v, bool) or not isinstance(v, int):
-        try:
-            import numpy as np
-            ok = isinstance(v, np.integer)
-        except ImportError:
-            ok = False
-        if not ok:
-            raise N.SquiglyError(f"{name} must be an integer, got {v!r}")
+    if not P.is_integer(v):
+        raise N.SquiglyError(f"{name} must be an integer, got {v!r}")
     return int(v)
 
 

@@ -45,9 +45,9 @@ for opts in ({"pool": 1, "refill_min": 8, "flush_min": 0}, {"pool": 1, "refill_m
     print(f"  per iteration: lanes returning {unw/(iters*64):.3f}, lanes branching {desc/(iters*64):.3f}, windows {wins/iters:.3f}, "
           f"window fill {pairs/max(wins*64,1):.3f}, hits per window {hits/max(wins,1):.3f}")
     print(f"  refill executions {refill} ({refill/iters:.4f} per iteration), lanes per refill {refl/max(refill,1):.2f}")
-    comb, rl, rw, sl, sw, hs = st[9:15]
+    comb, rl, rw, sl, sw = st[9:14]
     print(f"  returns: COMBINE pops {comb/rays:.3f} per ray; t recomputed {rl/rays:.3f} per ray, in {rw/iters:.3f} of the iterations; "
-          f"distance compare {sl/rays:.3f} per ray, in {sw/iters:.3f} of the iterations; slow compares in the hit fold {hs/rays:.4f} per ray")
+          f"distance compare {sl/rays:.3f} per ray, in {sw/iters:.3f} of the iterations")
     ts = st[16:24]; tot = sum(ts)
     names = ["store+refill", "return step", "branch step", "leaf open+scan", "owner lookup+pulls", "fetch+MT", "hit fold", "tail"]
     print("  wave cycles per iteration: " + ", ".join(f"{nm} {t/iters:.0f} ({100*t/tot:.0f}%)" for nm, t in zip(names, ts)) + f"; total {tot/iters:.0f}", flush=True)
