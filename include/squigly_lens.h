@@ -45,7 +45,8 @@
  * sq_render_rows_device's; with R = S, sum2 is then a masked call's sum2 under a full mask.  jitter = 1 is a box filter over the
  * pixel.  tests/lens_restatement.py restates the formula in numpy.
  *
- * Out of scope: cast frames; masked, adaptive and multi-view lens frames; the C++ command line.
+ * Out of scope: cast frames; multi-view lens frames; the C++ command line.  Masked and adaptive lens frames -- the same sub-rays for
+ * the live pixels of a mask only -- are libsquigly_mlens.so's (include/squigly_mlens.h).
  */
 #ifndef SQUIGLY_LENS_H
 #define SQUIGLY_LENS_H

@@ -24,7 +24,7 @@ def release_cached_memory() -> None:
 
 def __getattr__(name):
     # torch is only needed for the resident-scene path
-    if name in ("DeviceScene", "Progressive", "Adaptive", "Hits", "Radiance", "frame_seeds", "rule_reference", "frame_size_error", "MAX_CALL_PIXELS",
+    if name in ("DeviceScene", "Progressive", "Adaptive", "AdaptiveLens", "Hits", "Radiance", "frame_seeds", "rule_reference", "frame_size_error", "MAX_CALL_PIXELS",
                 "MAX_WAVEFRONT_PIXELS"):
         from . import device
         return getattr(device, name)

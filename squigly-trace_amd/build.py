@@ -1,5 +1,5 @@
-"""Build libsquigly_hip.so (HIP kernels for gfx950 + host side), libsquigly_denoise.so (the denoiser) and libsquigly_lens.so (jittered,
-thin-lens primary rays) in-tree with hipcc.
+"""Build libsquigly_hip.so (HIP kernels for gfx950 + host side), libsquigly_denoise.so (the denoiser), libsquigly_lens.so (jittered,
+thin-lens primary rays) and libsquigly_mlens.so (those rays for the live pixels of a mask) in-tree with hipcc.
 
     python squigly-trace_amd/build.py [--force]
 
@@ -43,14 +43,22 @@ DENOISE_HEADERS = ["sq_math.h", "sq_error.h", "sq_call_checks.h", "../../include
 # linked against that library and built after it, with the same FLAGS and an id of its own.
 LENS_OUT = os.path.join(HERE, "libsquigly_lens.so")
 LENS_SOURCES = ["sq_lens.hip"]
-LENS_HEADERS = ["sq_math.h", "sq_error.h", "sq_call_checks.h", "sq_lens_plan.h", "../../include/squigly_lens.h", "../../include/squigly_hip.h"]
+LENS_HEADERS = ["sq_math.h", "sq_error.h", "sq_call_checks.h", "sq_lens_plan.h", "sq_lens_ray.h", "../../include/squigly_lens.h", "../../include/squigly_hip.h"]
 
-# One description per library.  macro: the -D that carries the id into the library (what sq_build_id(), sq_denoise_build_id() and
-# sq_lens_build_id() return); salt: what the id's hash starts from, so that no two libraries share an id; link: behind the output.
+# The fourth library: the lens frame for the live pixels of a mask (include/squigly_mlens.h).  A client of libsquigly_hip.so like the
+# lens library, with which it shares the planner and a sub-ray's arithmetic (sq_lens_plan.h, sq_lens_ray.h) as headers, not as symbols.
+MLENS_OUT = os.path.join(HERE, "libsquigly_mlens.so")
+MLENS_SOURCES = ["sq_mlens.hip"]
+MLENS_HEADERS = ["sq_math.h", "sq_error.h", "sq_call_checks.h", "sq_lens_plan.h", "sq_lens_ray.h", "../../include/squigly_mlens.h",
+                 "../../include/squigly_lens.h", "../../include/squigly_hip.h"]
+
+# One description per library.  macro: the -D that carries the id into the library (what sq_build_id(), sq_denoise_build_id(),
+# sq_lens_build_id() and sq_mlens_build_id() return); salt: what the id's hash starts from, so that no two libraries share an id; link: behind the output.
 MAIN = dict(out=OUT, sources=SOURCES, headers=HEADERS, macro="SQ_BUILD_ID", salt=b"", link=[])
 DENOISE = dict(out=DENOISE_OUT, sources=DENOISE_SOURCES, headers=DENOISE_HEADERS, macro="SQ_DENOISE_BUILD_ID", salt=b"denoise\0", link=[])
 LENS = dict(out=LENS_OUT, sources=LENS_SOURCES, headers=LENS_HEADERS, macro="SQ_LENS_BUILD_ID", salt=b"lens\0",
             link=["-L" + HERE, "-lsquigly_hip", "-Wl,-rpath,$ORIGIN"])
+MLENS = dict(out=MLENS_OUT, sources=MLENS_SOURCES, headers=MLENS_HEADERS, macro="SQ_MLENS_BUILD_ID", salt=b"mlens\0", link=LENS["link"])
 
 
 def lib_source_id(lib, extra=()):
@@ -76,7 +84,7 @@ def lib_stale(lib):
 
 
 def compile_lib(lib, extra=(), out=None):
-    """out: an experimental variant (extra options) beside the product library; SQ_LIB_PATH / SQ_LENS_LIB_PATH select it at load time."""
+    """out: an experimental variant (extra options) beside the product library; SQ_LIB_PATH / SQ_LENS_LIB_PATH / SQ_MLENS_LIB_PATH select it at load time."""
     out = out or lib["out"]
     subprocess.check_call([hipcc()] + FLAGS + list(extra) + ['-D%s="%s"' % (lib["macro"], lib_source_id(lib, extra)), "-x", "hip"]
                           + [os.path.join(CSRC, s) for s in lib["sources"]] + ["-o", out] + lib["link"])
@@ -95,12 +103,20 @@ def stale(): return lib_stale(MAIN)
 def denoise_source_id(): return lib_source_id(DENOISE)
 def lens_source_id(extra=()): return lib_source_id(LENS, extra)
 def lens_stale(): return lib_stale(LENS)
+def mlens_source_id(extra=()): return lib_source_id(MLENS, extra)
+def mlens_stale(): return lib_stale(MLENS)
 
 
 def build_lens(force=False, extra=(), out=None):
     if out is None and not force and not lib_stale(LENS):
         return LENS_OUT
     return compile_lib(LENS, extra, out)
+
+
+def build_mlens(force=False, extra=(), out=None):
+    if out is None and not force and not lib_stale(MLENS):
+        return MLENS_OUT
+    return compile_lib(MLENS, extra, out)
 
 
 def build(force=False, extra=(), out=None):
@@ -120,6 +136,7 @@ def build(force=False, extra=(), out=None):
                                "-L" + HERE, "-lsquigly_hip", "-L" + os.path.join(rocm, "lib"), "-lamdhip64", "-Wl,-rpath,$ORIGIN/..", "-Wl,-rpath,/opt/rocm/lib", "-Wl,-rpath," + os.path.join(rocm, "lib"),
                                "-Wl,--allow-shlib-undefined"])
     build_lens(force)
+    build_mlens(force)
     return OUT
 
 

@@ -10,7 +10,8 @@
 // the fold's reads of one sub-ray's sums as well.
 //
 // The arithmetic is header's, operation by operation; -ffp-contract=off and the correctly rounded divide / sqrt keep it equal to
-// the numpy restatement (tests/lens_restatement.py).
+// the numpy restatement (tests/lens_restatement.py).  A sub-ray's own arithmetic is csrc/sq_lens_ray.h's, which libsquigly_mlens.so
+// (sq_mlens.hip: the same frame for the pixels of a list) includes too.
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
@@ -20,6 +21,7 @@
 #include "sq_call_checks.h"
 #include "sq_math.h"
 #include "sq_lens_plan.h"
+#include "sq_lens_ray.h"
 #include "../../include/squigly_lens.h"
 
 #ifndef SQ_LENS_BUILD_ID
@@ -30,58 +32,23 @@ namespace {
 
 using sq::f3;
 using sq::load3;
-using sq::rot_vert;
+using lensray::check_frame;
+using lensray::RayArgs;
+using lensray::ray_args;
+using lensray::refuse_slots;
 
 constexpr int kBlock = 256;
 constexpr int kMaxGrid = 4096;             // blocks of a launch; the kernels stride over their slots
 
-struct RayArgs {
-    float pos[3], rot[9];
-    float jitter, aperture, focus;
-    int S, n, r_begin;                      // samples per pixel, samples per sub-ray, first sub-ray of the batch
-    int w, h, row_block, shard, n_shards;
-    long long P, slots;                     // pixels of the shard; (sub-rays of the batch) * P
-};
-
 // ---- the rays: one lane per (sub-ray, pixel), slot = sub-ray * P + pixel ----
 __global__ __launch_bounds__(kBlock) void sq_lens_rays(const RayArgs A, float* __restrict__ org, float* __restrict__ dir,
                                                        long long* __restrict__ seed) {
-    const float ww = (float)A.w, hh = (float)A.h;
-    const bool plain = A.jitter == 0.0f && A.aperture == 0.0f;     // makeRay's ray: x + 0 * u is x for every draw u, so no draw is made
     for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < A.slots; i += (long long)gridDim.x * kBlock) {
         const int b = (int)(i / A.P);
-        const int pixel = (int)(i - b * A.P);
-        const int j = pixel / A.h, x = pixel - j * A.h;
-        const int blk = j / A.row_block;     // sq::shard_global_row, written out: through the function the kernel's registers are allocated differently
-        const int y = (blk * A.n_shards + A.shard) * A.row_block + (j - blk * A.row_block);
-        const long long base = (long long)A.S * ((long long)x + (long long)y * A.w) + (long long)(A.r_begin + b) * A.n;
-        float xs = (float)x, ys = (float)y;
-        float u2 = 0.0f, u3 = 0.0f;
-        if (!plain) {
-            uint64_t c[4];
-            sq::threefish256_key_only(~(uint64_t)base, c);
-            xs = (float)x + A.jitter * sq::unit_float((uint32_t)c[0]);
-            ys = (float)y + A.jitter * sq::unit_float((uint32_t)(c[0] >> 32));
-            u2 = sq::unit_float((uint32_t)c[1]);
-            u3 = sq::unit_float((uint32_t)(c[1] >> 32));
-        }
-        const float xoffs = (xs - (ww / 2)) / ww;
-        const float yoffs = ((hh / 2) - ys) / hh;
-        f3 o = sq::mk(A.pos[0], A.pos[1], A.pos[2]), d;
-        if (A.aperture == 0.0f) {
-            d = rot_vert(1.0f, xoffs, yoffs, A.rot);
-        } else {
-            const float rad = A.aperture * sq::fsqrt(u2);
-            const float th = 2 * sq::kPi * u3;
-            float sth, cth;
-            sq::fsincos(th, sth, cth);
-            const float lx = rad * cth, ly = rad * sth;
-            o = o + rot_vert(0.0f, lx, ly, A.rot);
-            d = rot_vert(1.0f, xoffs - lx / A.focus, yoffs - ly / A.focus, A.rot);
-        }
-        store3(org, i, o);
-        store3(dir, i, d);
-        seed[i] = base;
+        const lensray::Ray ray = lensray::sub_ray(A, (int)(i - b * A.P), A.r_begin + b);     // THE CONTRACT, csrc/sq_lens_ray.h
+        store3(org, i, ray.o);
+        store3(dir, i, ray.d);
+        seed[i] = ray.base;
     }
 }
 
@@ -118,45 +85,6 @@ __global__ __launch_bounds__(kBlock) void sq_lens_fold(const long long P, const 
 unsigned grid_for(long long units) {
     const long long blocks = (units + kBlock - 1) / kBlock;
     return (unsigned)(blocks < kMaxGrid ? blocks : kMaxGrid);
-}
-
-// What every ray-making call refuses about its frame, in the order of the header's list; *P_out = the shard's pixels (0: empty).
-int check_frame(const sq_camera* cam, const sq_lens* lens, int32_t S, int32_t R, int32_t r_begin, int32_t r_end, int32_t w, int32_t h,
-                sq_shard sh, long long* P_out) {
-    if (!cam || !lens) return sq_set_error("null argument: cam and lens are required");
-    if (S < 1 || R < 1) return sq_set_error("samples and sub-rays must be at least 1 (got S = %d, R = %d)", S, R);
-    if (S % R != 0) return sq_set_error("the sub-rays must divide the samples (got S = %d, R = %d)", S, R);
-    if (r_begin < 0 || r_end <= r_begin || r_end > R)
-        return sq_set_error("bad sub-ray range [%d, %d) (need 0 <= r_begin < r_end <= R = %d)", r_begin, r_end, R);
-    if (!(lens->jitter >= 0.0f && lens->jitter <= 1.0f)) return sq_set_error("jitter must be a number in [0, 1] (got %g)", (double)lens->jitter);
-    if (!(lens->aperture >= 0.0f && lens->aperture < __builtin_inff()))
-        return sq_set_error("aperture must be a finite number >= 0 (got %g)", (double)lens->aperture);
-    if (lens->aperture > 0.0f && !(lens->focus > 0.0f && lens->focus < __builtin_inff()))
-        return sq_set_error("focus must be a finite number > 0 when the aperture is open (got %g)", (double)lens->focus);
-    if (w < 1 || h < 1) return sq_set_error("w and h must be at least 1 (got %d x %d)", w, h);
-    const int32_t rows = sq_shard_rows(w, sh);
-    if (rows < 0) return sq_set_error("bad shard {row_block=%d, shard=%d, n_shards=%d}", sh.row_block, sh.shard, sh.n_shards);
-    const long long P = (long long)rows * h;
-    if (P > lensplan::kMaxIndex) return sq_set_error("%d x %d pixels exceed 2^31 - 1 pixels in one call", rows, h);
-    *P_out = P;
-    return 0;
-}
-
-int refuse_slots(long long P, long long nb) {
-    if (nb > lensplan::kMaxIndex / P)
-        return sq_set_error("%lld sub-rays of %lld pixels exceed 2^31 - 1 ray slots in one batch", nb, P);
-    return 0;
-}
-
-RayArgs ray_args(const sq_camera* cam, const sq_lens* lens, int32_t S, int32_t R, int32_t w, int32_t h, sq_shard sh, long long P) {
-    RayArgs A{};
-    for (int i = 0; i < 3; ++i) A.pos[i] = cam->pos[i];
-    for (int i = 0; i < 9; ++i) A.rot[i] = cam->rot[i];
-    A.jitter = lens->jitter; A.aperture = lens->aperture; A.focus = lens->focus;
-    A.S = S; A.n = S / R;
-    A.w = w; A.h = h; A.row_block = sh.row_block; A.shard = sh.shard; A.n_shards = sh.n_shards;
-    A.P = P;
-    return A;
 }
 
 // Enqueues the ray kernel for the sub-rays [r0, r1).

@@ -346,6 +346,22 @@ class DeviceScene(Owner):
         return L.render_lens(self, cam, lens, samples, subrays, w, h, shard, r_range, sums, want_sum2, want_avg, want_rgb,
                              L.DEFAULT_WORK_MB if work_mb is None else work_mb, stream)
 
+    def live_pixels(self, mask, counts, r_begin, stream=None):
+        """The live list of a masked lens step (mlens.py, sq_mlens_live_device): (index, n_live), int32 CUDA tensors -- the live
+        pixels in ascending order in the first n_live entries of index, and n_live itself, [1].  See mlens.live_pixels."""
+        from .mlens import live_pixels
+        return live_pixels(self, mask, counts, r_begin, stream)
+
+    def render_lens_masked(self, cam, lens, samples, subrays, w, h, r_begin, r_end, sums, index, n_live, sums2=None, counts=None,
+                           shard=(None, 0, 1), work_mb=None, out_avg=None, out_rgb=None, stream=None):
+        """render_lens for the listed pixels only (mlens.py, sq_mlens_render_device): the sub-rays [r_begin, r_end) of the first
+        n_live pixels of `index`, folded into their sums, sums2 and counts (in sub-rays); a pixel that is not listed costs no ray
+        and keeps what every buffer holds.  Returns (out_avg, out_rgb).  See mlens.render_lens_masked."""
+        from . import lens as L
+        from .mlens import render_lens_masked
+        return render_lens_masked(self, cam, lens, samples, subrays, w, h, r_begin, r_end, sums, index, n_live, sums2, counts, shard,
+                                  L.DEFAULT_WORK_MB if work_mb is None else work_mb, out_avg, out_rgb, stream)
+
     def raytrace(self, origins, directions, seeds=None, samples=1, k_range=None, sums=None, want_avg=True, want_rgb=False,
                  stream=None):
         """Lib.raytrace of each ray (sq_raytrace_rays_device): returns Radiance(sum, avg, rgb) CUDA tensors, enqueued on `stream`.
@@ -659,6 +675,110 @@ class Adaptive(_Frame):
         if self.rule is None:
             self._live = self.dscene.adaptive_update(self._sums, self._sums2, self._counts, self._mask, self.tol, self.eps,
                                                      stream=stream)
+        else:
+            _, st = P.call_stream(self._mask.device, stream)
+            with torch.cuda.stream(st):
+                new = torch.as_tensor(self.rule(self._sums, self._sums2, self._counts, self._mask), device=self._mask.device)
+                if tuple(new.shape) != tuple(self._mask.shape):
+                    raise ValueError(f"rule must return a mask of shape {tuple(self._mask.shape)}, got {tuple(new.shape)}")
+                self._mask.copy_((new != 0).to(torch.uint8))
+                self._live = self._count_live()
+        return self._avg, self._rgb
+
+
+class AdaptiveLens(_Frame):
+    """Adaptive for an anti-aliased, depth-of-field frame (DeviceScene.live_pixels, render_lens_masked): a pixel stops receiving
+    SUB-RAYS once the stopping rule calls it done, and a stopped pixel costs no ray.
+
+    The frame has `samples` samples and `subrays` sub-rays per pixel under `lens` (lens.py), n = samples / subrays samples on each
+    sub-ray.  Everything Adaptive counts in samples is counted in sub-rays here: `first` and `step`, `done`, and `counts` -- the
+    terms of `sums2` are sub-ray sums, and the rule's n must be the number of terms.  `sample_counts` is counts * n.  `step()`
+    lists the live pixels, renders their next sub-rays, applies the rule and returns the (avg, rgb) picture, in which a pixel that
+    stopped after c sub-rays keeps (1 / (c * n)) * sum: bit for bit render_lens over r_range = (0, c).  rule: a callable (sums,
+    sums2, counts, mask) -> new mask instead of the built-in one, which is DeviceScene.adaptive_update with tol and eps * n * n:
+    the sub-ray sums are n times a sample's size, so that is Adaptive's criterion on the pixel mean.  The gap guard, checkpoints,
+    depth= and sky= are Adaptive's.  work_mb: as in render_lens."""
+
+    def __init__(self, dscene, cam, lens, samples, subrays, w, h, tol, eps=1.0, first=1, step=1, shard=(None, 0, 1), rule=None,
+                 sums=None, sums2=None, counts=None, mask=None, done=0, depth=None, sky=SCENE_SKY, work_mb=None):
+        from .lens import frame_args
+        samples, subrays, _, _ = frame_args(lens, samples, subrays)
+        done, first, step = int(done), int(first), int(step)
+        tol, eps = float(tol), float(eps)
+        if not tol >= 0 or not eps >= 0:
+            raise ValueError(f"tol and eps must be numbers >= 0, got {tol}, {eps}")
+        if first < 1 or step < 1:
+            raise ValueError(f"first and step must be positive, got {first}, {step}")
+        if not 0 <= done <= subrays:
+            raise ValueError(f"done must be in [0, {subrays}], got {done}")
+        if rule is not None and not callable(rule):
+            raise ValueError("rule must be callable: (sums, sums2, counts, mask) -> mask")
+        if done and (sums is None or sums2 is None or counts is None or mask is None):
+            raise ValueError("resuming (done > 0) needs sums, sums2, counts and mask as the checkpoint left them")
+        rows = self._begin(dscene, cam, samples, w, h, False, shard, depth=depth, sky=sky)
+        for name, t, fill in (("sums", sums, 0), ("sums2", sums2, 0), ("counts", counts, 0), ("mask", mask, 1)):
+            setattr(self, "_" + name, self._adopt(name, t, (rows, h) + _STATE[name][0], _STATE[name][1], fill))
+        self.lens, self.subrays, self.n, self.work_mb = lens, subrays, samples // subrays, work_mb
+        self.tol, self.eps, self.first, self.step_size, self.rule = tol, eps, first, step, rule
+        self._done = done
+        self._avg = torch.zeros((rows, h, 3), dtype=torch.float32, device=self._dev)
+        self._rgb = torch.zeros((rows, h, 3), dtype=torch.uint8, device=self._dev)
+        if done:
+            self._restore_picture()
+        self._live = self._count_live()
+
+    _count_live = Adaptive._count_live
+
+    def _restore_picture(self):
+        """avg and rgb of a checkpoint: (1 / (float)(count * n)) *^ sum, as the call that last rendered the pixel wrote it."""
+        import numpy as np
+        c = self._counts.cpu().numpy().astype(np.int64) * self.n
+        s = self._sums.cpu().numpy()
+        with np.errstate(all="ignore"):
+            avg = (np.float32(1) / np.maximum(c, 1).astype(np.float32))[..., None] * s
+        avg[c == 0] = 0
+        rgb = N.debug_eval("tonemap", avg.reshape(-1, 3), device=self.dscene.device).reshape(avg.shape)
+        rgb[c == 0] = 0
+        self._avg.copy_(torch.from_numpy(np.ascontiguousarray(avg)))
+        self._rgb.copy_(torch.from_numpy(np.ascontiguousarray(rgb)))
+
+    sums = property(lambda self: self._sums, doc="Per-pixel fold of the sub-ray sums over the pixel's first counts sub-rays.")
+    sums2 = property(lambda self: self._sums2, doc="Per-pixel fold of s * s over the same sub-ray sums s.")
+    counts = property(lambda self: self._counts, doc="Sub-rays each pixel has received (int32 CUDA tensor [rows, h]).")
+    sample_counts = property(lambda self: self._counts * self.n, doc="Samples each pixel has received: counts * n.")
+    mask = property(lambda self: self._mask, doc="1 = the pixel is still live (uint8 CUDA tensor [rows, h]).")
+    done = property(lambda self: self._done, doc="End of the last sub-ray range rendered.")
+    live = property(lambda self: self._live, doc="Pixels the next step would render.")
+
+    @property
+    def finished(self):
+        return self._live == 0 or self._done >= self.subrays
+
+    @property
+    def samples_spent(self):
+        """Samples rendered so far, over all pixels (waits for the device)."""
+        return int(self._counts.sum(dtype=torch.int64).item()) * self.n
+
+    def step(self, stream=None):
+        """List the live pixels, render their next sub-rays and apply the rule; returns the (avg, rgb) CUDA tensors of the frame."""
+        if self.finished:
+            raise RuntimeError("the frame is finished: no pixel is live" if self._live == 0
+                               else f"the frame is finished: all {self.subrays} sub-rays are rendered")
+        self._unchanged()
+        r_end = min(self._done + (self.first if self._done == 0 else self.step_size), self.subrays)
+        index, _ = self.dscene.live_pixels(self._mask, self._counts, self._done, stream=stream)
+        # the list's length is the live count the last step (or the constructor) already brought to the host: no wait here
+        self.dscene.render_lens_masked(self.cam, self.lens, self.samples, self.subrays, self.w, self.h, self._done, r_end, self._sums,
+                                       index, self._live, sums2=self._sums2, counts=self._counts, shard=self.shard,
+                                       work_mb=self.work_mb, out_avg=self._avg, out_rgb=self._rgb, stream=stream)
+        self._done = r_end
+        if self.rule is None:
+            self.dscene.adaptive_update(self._sums, self._sums2, self._counts, self._mask, self.tol, self.eps * self.n * self.n,
+                                        stream=stream)
+            # the next list's length is the gap-guarded count, which is the rule's own unless a checkpoint brought a pixel with a gap
+            _, st = P.call_stream(self._mask.device, stream)
+            with torch.cuda.stream(st):
+                self._live = self._count_live()
         else:
             _, st = P.call_stream(self._mask.device, stream)
             with torch.cuda.stream(st):

@@ -100,20 +100,28 @@ def denoise_options(denoise):
 
 
 def render_adaptive(bih, cam, samples, dimensions, tol, eps=1.0, first=8, step=8, cast=False, device=0, rule=None, lights=None,
-                    depth=None, sky=None, denoise=None):
+                    depth=None, sky=None, denoise=None, lens=None, subrays=None):
     """The frame of render_rgb8 with adaptive sampling (DeviceScene, Adaptive): yields (done, live, spent, rgb8, counts) after
     every step -- the end of the range rendered, the pixels still live, the samples spent so far, the (w, h, 3) uint8 image and
     the (w, h) int32 per-pixel sample counts.  A pixel that stopped after n samples shows the mean of its first n samples, so
     with first >= samples (one step, every pixel live) the image is bit for bit that of render_rgb8.  lights, depth, sky: as in
     render_progressive.  denoise (None = off; True, a sigma_l or a dict of denoise parameters): once the frame is finished, one more
     tuple follows whose image is the frame filtered on the device (denoise_frame: the variance from the frame's own second moments,
-    the guides from its first hits) and tonemapped by the device's own tonemap; the tuples before it are unchanged."""
+    the guides from its first hits) and tonemapped by the device's own tonemap; the tuples before it are unchanged.
+    lens (a Lens; None = no lens, the function as it was) and subrays (None = samples): the anti-aliased, depth-of-field frame of
+    render_lens_rgb8, adaptively sampled in whole sub-rays (AdaptiveLens).  first and step stay in samples and must be multiples of
+    n = samples / subrays (ValueError); the yielded done, spent and counts are samples too; cast=True is refused.  denoise= then
+    filters with the variance of the sub-ray sums brought to the pixel mean's scale, denoise_variance(...) * (1 / (n * n))."""
     from .device import Adaptive                       # torch: only the resident-scene path needs it
     w, h = dimensions
     if int(first) < 1 or int(step) < 1:
         raise ValueError(f"first and step must be positive, got {first}, {step}")
     if not float(tol) >= 0 or not float(eps) >= 0:
         raise ValueError(f"tol and eps must be numbers >= 0, got {tol}, {eps}")
+    if lens is not None or subrays is not None:
+        yield from _render_adaptive_lens(bih, cam, samples, dimensions, tol, eps, first, step, cast, device, rule, lights, depth, sky,
+                                         denoise, lens, subrays)
+        return
     scene = _resident(bih, device, lights, depth, sky)
     dn = None if denoise is None or denoise is False else denoise_options(denoise)      # refused before anything is uploaded
     with scene as ds:
@@ -127,6 +135,37 @@ def render_adaptive(bih, cam, samples, dimensions, tol, eps=1.0, first=8, step=8
             out, _ = denoise_frame(ds, cam, w, h, avg, var=denoise_variance(a.sums, a.sums2, a.counts), **dn)
             img = N.debug_eval("tonemap", out.cpu().numpy().reshape(-1, 3), device=ds.device).reshape(tuple(out.shape))
             yield a.done, a.live, a.samples_spent, img, a.counts.cpu().numpy()
+
+
+def _render_adaptive_lens(bih, cam, samples, dimensions, tol, eps, first, step, cast, device, rule, lights, depth, sky, denoise, lens,
+                          subrays):
+    """render_adaptive with a lens: AdaptiveLens, its sub-ray units turned into samples for the caller."""
+    from .lens import frame_args
+    if lens is None:
+        raise ValueError("subrays needs a lens")
+    if cast:
+        raise ValueError("a lens frame is path-traced: cast=True is refused")
+    S, R, _, _ = frame_args(lens, samples, samples if subrays is None else subrays)
+    n = S // R
+    if int(first) % n or int(step) % n:
+        raise ValueError(f"first and step must be multiples of samples / subrays = {n}, got {first}, {step}")
+    scene = _resident(bih, device, lights, depth, sky)
+    dn = None if denoise is None or denoise is False else denoise_options(denoise)      # refused before anything is uploaded
+    from .device import AdaptiveLens
+    w, h = dimensions
+    with scene as ds:
+        a = AdaptiveLens(ds, cam, lens, S, R, w, h, tol, eps=eps, first=int(first) // n, step=int(step) // n, rule=rule)
+        avg = None
+        while not a.finished:
+            avg, rgb = a.step()
+            yield a.done * n, a.live, a.samples_spent, rgb.cpu().numpy(), a.sample_counts.cpu().numpy()
+        if dn is not None and avg is not None:
+            from .denoise import denoise_frame, denoise_variance
+            # the variance of the mean of sub-ray sums is n * n times that of the pixel mean, in every branch of the variance formula
+            var = denoise_variance(a.sums, a.sums2, a.counts) * (1 / (n * n))            # one float32 multiply
+            out, _ = denoise_frame(ds, cam, w, h, avg, var=var, **dn)
+            img = N.debug_eval("tonemap", out.cpu().numpy().reshape(-1, 3), device=ds.device).reshape(tuple(out.shape))
+            yield a.done * n, a.live, a.samples_spent, img, a.sample_counts.cpu().numpy()
 
 
 def render_views_rgb8(bih, cams, samples, dimensions, cast=False, device=0, lights=None, depth=None, sky=None) -> np.ndarray:
