@@ -43,14 +43,15 @@ DENOISE_HEADERS = ["sq_math.h", "sq_error.h", "sq_call_checks.h", "../../include
 # linked against that library and built after it, with the same FLAGS and an id of its own.
 LENS_OUT = os.path.join(HERE, "libsquigly_lens.so")
 LENS_SOURCES = ["sq_lens.hip"]
-LENS_HEADERS = ["sq_math.h", "sq_error.h", "sq_call_checks.h", "sq_lens_plan.h", "sq_lens_ray.h", "../../include/squigly_lens.h", "../../include/squigly_hip.h"]
+LENS_HEADERS = ["sq_math.h", "sq_error.h", "sq_call_checks.h", "sq_lens_plan.h", "sq_lens_ray.h", "sq_lens_frame.h", "../../include/squigly_lens.h",
+                "../../include/squigly_hip.h"]
 
 # The fourth library: the lens frame for the live pixels of a mask (include/squigly_mlens.h).  A client of libsquigly_hip.so like the
-# lens library, with which it shares the planner and a sub-ray's arithmetic (sq_lens_plan.h, sq_lens_ray.h) as headers, not as symbols.
+# lens library, with which it shares the planner, a sub-ray's arithmetic and the frame's kernels and batch loop (sq_lens_plan.h,
+# sq_lens_ray.h, sq_lens_frame.h) as headers, not as symbols.
 MLENS_OUT = os.path.join(HERE, "libsquigly_mlens.so")
 MLENS_SOURCES = ["sq_mlens.hip"]
-MLENS_HEADERS = ["sq_math.h", "sq_error.h", "sq_call_checks.h", "sq_lens_plan.h", "sq_lens_ray.h", "../../include/squigly_mlens.h",
-                 "../../include/squigly_lens.h", "../../include/squigly_hip.h"]
+MLENS_HEADERS = LENS_HEADERS + ["../../include/squigly_mlens.h"]
 
 # One description per library.  macro: the -D that carries the id into the library (what sq_build_id(), sq_denoise_build_id(),
 # sq_lens_build_id() and sq_mlens_build_id() return); salt: what the id's hash starts from, so that no two libraries share an id; link: behind the output.
@@ -107,16 +108,15 @@ def mlens_source_id(extra=()): return lib_source_id(MLENS, extra)
 def mlens_stale(): return lib_stale(MLENS)
 
 
-def build_lens(force=False, extra=(), out=None):
-    if out is None and not force and not lib_stale(LENS):
-        return LENS_OUT
-    return compile_lib(LENS, extra, out)
+def build_client(lib, force=False, extra=(), out=None):
+    """A client library of libsquigly_hip.so: compiled unless it is the in-tree product and carries the current id."""
+    if out is None and not force and not lib_stale(lib):
+        return lib["out"]
+    return compile_lib(lib, extra, out)
 
 
-def build_mlens(force=False, extra=(), out=None):
-    if out is None and not force and not lib_stale(MLENS):
-        return MLENS_OUT
-    return compile_lib(MLENS, extra, out)
+def build_lens(force=False, extra=(), out=None): return build_client(LENS, force, extra, out)
+def build_mlens(force=False, extra=(), out=None): return build_client(MLENS, force, extra, out)
 
 
 def build(force=False, extra=(), out=None):

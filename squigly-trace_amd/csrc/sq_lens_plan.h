@@ -1,6 +1,7 @@
 // sq_lens_plan.h — the GPU-free part of libsquigly_lens.so (include/squigly_lens.h): the workspace layout of a batch of sub-rays
-// and the batch plan of sq_lens_render_device.  Plain host C++: sq_lens.hip enqueues exactly what plan() lists, and
-// tests/lens_plan_main.cpp runs it under the sanitizers without a device.
+// and the batch plan of a frame.  Plain host C++: batch() is the one place that cuts a sub-ray range into batches, plan() lists
+// its batches and sq_lens_frame.h's render_batches enqueues them (over the pixels of a shard for libsquigly_lens.so, over those of
+// a list for libsquigly_mlens.so), and tests/lens_plan_main.cpp runs it under the sanitizers without a device.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -36,6 +37,14 @@ inline long long max_batch(long long P, size_t bytes) {
     return nb;
 }
 
+// The batches of the sub-rays [r_begin, r_end), nb >= 1 at a time: how many there are, and batch i of them.
+struct Batch { int32_t r0, r1; };
+inline int64_t batch_count(int32_t r_begin, int32_t r_end, long long nb) { return ((int64_t)r_end - r_begin + nb - 1) / nb; }
+inline Batch batch(int32_t r_begin, int32_t r_end, long long nb, int64_t i) {
+    const int64_t r0 = r_begin + i * nb;
+    return { (int32_t)r0, (int32_t)(r0 + nb < r_end ? r0 + nb : r_end) };
+}
+
 // sq_lens_plan.
 inline int32_t plan(long long P, int32_t r_begin, int32_t r_end, size_t bytes, int32_t* out_r, int32_t cap) {
     if (P < 1) { sq_set_error("P must be at least 1 (got %lld)", P); return -1; }
@@ -46,11 +55,11 @@ inline int32_t plan(long long P, int32_t r_begin, int32_t r_end, size_t bytes, i
         sq_set_error("work_bytes = %zu is too small: one sub-ray of %lld pixels needs %zu", bytes, P, work_bytes(P, 1));
         return -1;
     }
-    const int64_t span = (int64_t)r_end - r_begin, count = (span + nb - 1) / nb;
+    const int64_t count = batch_count(r_begin, r_end, nb);
     for (int64_t i = 0; out_r && i < count && i < cap; ++i) {
-        const int64_t r0 = r_begin + i * nb;
-        out_r[2 * i] = (int32_t)r0;
-        out_r[2 * i + 1] = (int32_t)(r0 + nb < r_end ? r0 + nb : r_end);
+        const Batch b = batch(r_begin, r_end, nb, i);
+        out_r[2 * i] = b.r0;
+        out_r[2 * i + 1] = b.r1;
     }
     return (int32_t)count;
 }

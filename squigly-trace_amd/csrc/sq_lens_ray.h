@@ -1,6 +1,6 @@
-// sq_lens_ray.h — what libsquigly_lens.so and libsquigly_mlens.so share about a lens frame, written once: THE CONTRACT of
-// include/squigly_lens.h for one (pixel, sub-ray) as a device function, the kernel arguments it reads, and the host checks of a
-// frame's arguments.  sq_lens.hip runs it over every pixel of a shard, sq_mlens.hip over the pixels of a list.
+// sq_lens_ray.h — what libsquigly_lens.so and libsquigly_mlens.so share about one sub-ray and about a call's arguments, written
+// once: THE CONTRACT of include/squigly_lens.h for one (pixel, sub-ray) as a device function, the kernel arguments it reads, and
+// the host checks of a frame's and of a fold's arguments.  The kernels that run it and the frame's batch loop are sq_lens_frame.h's.
 //
 // The arithmetic is the header's, operation by operation; -ffp-contract=off and the correctly rounded divide / sqrt keep it equal
 // to the numpy restatement (tests/lens_restatement.py).
@@ -81,6 +81,21 @@ inline int check_frame(const sq_camera* cam, const sq_lens* lens, int32_t S, int
     const long long P = (long long)rows * h;
     if (P > lensplan::kMaxIndex) return sq_set_error("%d x %d pixels exceed 2^31 - 1 pixels in one call", rows, h);
     *P_out = P;
+    return 0;
+}
+
+// What both fold calls refuse about their frame, in the order of their headers' lists.  R: NULL for sq_lens_fold_device, which
+// knows no R -- its range ends at S; sq_mlens_fold_device's ends at *R, which must divide S.
+inline int check_fold(const void* d_part, const void* d_sum, long long P, int32_t S, const int32_t* R, int32_t r_begin, int32_t r_end) {
+    if (!d_part || !d_sum) return sq_set_error("null argument: d_part and d_sum are required");
+    if (P < 1) return sq_set_error("P must be at least 1 (got %lld)", P);
+    if (!R && S < 1) return sq_set_error("samples must be at least 1 (got S = %d)", S);
+    if (R && (S < 1 || *R < 1)) return sq_set_error("samples and sub-rays must be at least 1 (got S = %d, R = %d)", S, *R);
+    if (R && S % *R != 0) return sq_set_error("the sub-rays must divide the samples (got S = %d, R = %d)", S, *R);
+    const int32_t end = R ? *R : S;
+    if (r_begin < 0 || r_end <= r_begin || r_end > end)
+        return sq_set_error("bad sub-ray range [%d, %d) (need 0 <= r_begin < r_end <= %c = %d)", r_begin, r_end, R ? 'R' : 'S', end);
+    if (P > lensplan::kMaxIndex) return sq_set_error("%lld pixels exceed 2^31 - 1 pixels in one call", P);
     return 0;
 }
 

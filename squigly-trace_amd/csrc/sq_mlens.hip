@@ -5,9 +5,10 @@
 //     sq_mlens_fold    one lane per list entry: the sub-ray sums into the listed pixel's sum, sum2, count, avg and tonemap
 // and the batches are those of sq_lens_plan.h over L.  The list comes from
 //     sq_mlens_live    the ordered compaction of the live pixels.
-// No allocation, no state.
+// No allocation, no state.  This file holds the compaction and the library's exports with their argument checks; the bodies of
+// the ray and fold kernels, their launches and the batch loop are csrc/sq_lens_frame.h's, instantiated here for a list.
 //
-// The ray slots are dense in list order, so org, dir, seed and part keep sq_lens.hip's access shape (a lane's 12 bytes in one
+// The ray slots are dense in list order, so org, dir, seed and part keep the dense frame's access shape (a lane's 12 bytes in one
 // dwordx3, a wave's 768 bytes consecutive); the per-pixel side is a gather and a scatter through the list, whose ascending order
 // keeps the pixels of a wave close.
 //
@@ -22,10 +23,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
-#include <string>
-
 #include "sq_call_checks.h"
-#include "sq_math.h"
+#include "sq_lens_frame.h"
 #include "sq_lens_plan.h"
 #include "sq_lens_ray.h"
 #include "../../include/squigly_mlens.h"
@@ -36,12 +35,9 @@
 
 namespace {
 
-using sq::f3;
-using sq::load3;
+using lensframe::kBlock;
+using lensframe::Pixels;
 using lensray::RayArgs;
-
-constexpr int kBlock = 256;
-constexpr int kMaxGrid = 4096;             // blocks of a launch; the ray and fold kernels stride over their slots
 
 constexpr int kLiveBlock = 1024;           // the compaction: 16 waves a workgroup,
 constexpr int kLiveWaves = kLiveBlock / 64;
@@ -112,20 +108,7 @@ __global__ __launch_bounds__(kLiveBlock) void sq_mlens_live(const long long P, c
 // ---- the rays: one lane per (sub-ray, list entry), slot = sub-ray * L + entry ----
 __global__ __launch_bounds__(kBlock) void sq_mlens_rays(const RayArgs A, const long long L, const int* __restrict__ index,
                                                         float* __restrict__ org, float* __restrict__ dir, long long* __restrict__ seed) {
-    for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < A.slots; i += (long long)gridDim.x * kBlock) {
-        const int b = (int)(i / L);
-        const int pixel = index[i - b * L];
-        lensray::Ray ray;
-        if (pixel < 0 || pixel >= A.P) {                     // a wrong list is no out-of-range pixel: a ray of zeros
-            ray.o = ray.d = sq::mk(0.0f, 0.0f, 0.0f);
-            ray.base = 0;
-        } else {
-            ray = lensray::sub_ray(A, pixel, A.r_begin + b);      // THE CONTRACT, csrc/sq_lens_ray.h
-        }
-        store3(org, i, ray.o);
-        store3(dir, i, ray.d);
-        seed[i] = ray.base;
-    }
+    lensframe::rays_body<true>(A, L, index, org, dir, seed);
 }
 
 // ---- the fold: one lane per list entry, the sub-ray sums part[b][entry] in the order of b, into the listed pixel ----
@@ -133,64 +116,13 @@ __global__ __launch_bounds__(kBlock) void sq_mlens_fold(const long long P, const
                                                         const float inv, const int* __restrict__ index, const float* __restrict__ part,
                                                         float* __restrict__ sum, float* __restrict__ sum2, int* __restrict__ count,
                                                         float* __restrict__ avg, uint8_t* __restrict__ rgb) {
-    for (long long j = (long long)blockIdx.x * kBlock + threadIdx.x; j < L; j += (long long)gridDim.x * kBlock) {
-        const long long p = index[j];
-        if (p < 0 || p >= P) continue;
-        f3 s, q;
-        int b = 0;
-        if (carry) {
-            s = load3(sum, p);
-            q = sum2 ? load3(sum2, p) : sq::mk(0.0f, 0.0f, 0.0f);
-        } else {
-            s = load3(part, j);
-            q = s * s;
-            b = 1;
-        }
-        for (; b < nb; ++b) {
-            const f3 t = load3(part, (long long)b * L + j);
-            s = s + t;
-            q = q + t * t;
-        }
-        store3(sum, p, s);
-        if (sum2) store3(sum2, p, q);
-        if (count) count[p] = r_end;
-        if (avg || rgb) {
-            const f3 a = sq::scale(inv, s);
-            if (avg) store3(avg, p, a);
-            if (rgb) tonemap(a, rgb + 3 * p);
-        }
-    }
-}
-
-unsigned grid_for(long long units) {
-    const long long blocks = (units + kBlock - 1) / kBlock;
-    return (unsigned)(blocks < kMaxGrid ? blocks : kMaxGrid);
+    lensframe::fold_body<true>(P, L, nb, carry, r_end, inv, index, part, sum, sum2, count, avg, rgb);
 }
 
 // What the three list-taking calls refuse about their list; P >= 1.
 int check_list(const int32_t* d_index, int64_t L, long long P) {
     if (!d_index) return sq_set_error("null argument: d_index is required");
     if (L < 0 || L > P) return sq_set_error("the list must hold between 0 and P = %lld pixels (got L = %lld)", P, (long long)L);
-    return 0;
-}
-
-int enqueue_rays(RayArgs A, long long L, int32_t r0, int32_t r1, const int32_t* d_index, float* d_org, float* d_dir, int64_t* d_seed,
-                 hipStream_t stream) {
-    A.r_begin = r0;
-    A.slots = (long long)(r1 - r0) * L;
-    static_assert(sizeof(long long) == sizeof(int64_t), "seed bases are 64-bit");
-    hipLaunchKernelGGL(sq_mlens_rays, dim3(grid_for(A.slots)), dim3(kBlock), 0, stream, A, L, (const int*)d_index, d_org, d_dir, (long long*)d_seed);
-    SQ_HIP(hipGetLastError());
-    return 0;
-}
-
-// n = S / R; count, avg and rgb may be NULL.
-int enqueue_fold(long long P, long long L, int32_t n, int32_t r0, int32_t r1, const int32_t* d_index, const float* d_part, float* d_sum,
-                 float* d_sum2, int32_t* d_count, float* d_avg, uint8_t* d_rgb, hipStream_t stream) {
-    const float inv = 1.0f / (float)((long long)r1 * n);
-    hipLaunchKernelGGL(sq_mlens_fold, dim3(grid_for(L)), dim3(kBlock), 0, stream, P, L, (int)(r1 - r0), r0 > 0 ? 1 : 0, (int)r1, inv,
-                       (const int*)d_index, d_part, d_sum, d_sum2, (int*)d_count, d_avg, d_rgb);
-    SQ_HIP(hipGetLastError());
     return 0;
 }
 
@@ -232,20 +164,14 @@ extern "C" int sq_mlens_rays_device(int32_t device, const sq_camera* cam, const 
     const NamedRange spans[4] = { { "d_index", d_index, 4 * (size_t)L }, { "d_org", d_org, 12 * n }, { "d_dir", d_dir, 12 * n }, { "d_seed", d_seed, 8 * n } };
     if (refuse_overlaps(spans, 4)) return 1;
     SQ_HIP(hipSetDevice(device));
-    return enqueue_rays(lensray::ray_args(cam, lens, S, R, w, h, sh, P), (long long)L, r_begin, r_end, d_index, d_org, d_dir, d_seed,
-                        (hipStream_t)hip_stream);
+    return lensframe::enqueue_rays<true>(sq_mlens_rays, lensray::ray_args(cam, lens, S, R, w, h, sh, P), Pixels{ P, (long long)L, d_index },
+                                         r_begin, r_end, d_org, d_dir, d_seed, (hipStream_t)hip_stream);
 }
 
 extern "C" int sq_mlens_fold_device(int32_t device, int64_t P, int32_t S, int32_t R, int32_t r_begin, int32_t r_end, const int32_t* d_index,
                                     int64_t L, const float* d_part, float* d_sum, float* d_sum2, int32_t* d_count, float* d_avg,
                                     uint8_t* d_rgb, void* hip_stream) {
-    if (!d_part || !d_sum) return sq_set_error("null argument: d_part and d_sum are required");
-    if (P < 1) return sq_set_error("P must be at least 1 (got %lld)", (long long)P);
-    if (S < 1 || R < 1) return sq_set_error("samples and sub-rays must be at least 1 (got S = %d, R = %d)", S, R);
-    if (S % R != 0) return sq_set_error("the sub-rays must divide the samples (got S = %d, R = %d)", S, R);
-    if (r_begin < 0 || r_end <= r_begin || r_end > R)
-        return sq_set_error("bad sub-ray range [%d, %d) (need 0 <= r_begin < r_end <= R = %d)", r_begin, r_end, R);
-    if (P > lensplan::kMaxIndex) return sq_set_error("%lld pixels exceed 2^31 - 1 pixels in one call", (long long)P);
+    if (lensray::check_fold(d_part, d_sum, (long long)P, S, &R, r_begin, r_end)) return 1;           // r_end <= R, and R divides S
     if (check_list(d_index, L, (long long)P)) return 1;
     if (L == 0) return 0;
     const long long nb = (long long)r_end - r_begin;
@@ -255,8 +181,9 @@ extern "C" int sq_mlens_fold_device(int32_t device, int64_t P, int32_t S, int32_
                                   { "d_sum2", d_sum2, 12 * p }, { "d_count", d_count, 4 * p }, { "d_avg", d_avg, 12 * p }, { "d_rgb", d_rgb, 3 * p } };
     if (refuse_overlaps(spans, 7)) return 1;
     SQ_HIP(hipSetDevice(device));
-    return enqueue_fold((long long)P, (long long)L, S / R, r_begin, r_end, d_index, d_part, d_sum, d_sum2, d_count, d_avg, d_rgb,
-                        (hipStream_t)hip_stream);
+    return lensframe::enqueue_fold<true>(sq_mlens_fold, Pixels{ (long long)P, (long long)L, d_index }, r_begin, r_end,
+                                         1.0f / (float)((long long)r_end * (S / R)), d_part, d_sum, d_sum2, d_count, d_avg, d_rgb,
+                                         (hipStream_t)hip_stream);
 }
 
 extern "C" int sq_mlens_render_device(sq_device_scene* s, const sq_camera* cam, const sq_lens* lens, int32_t S, int32_t R, int32_t r_begin,
@@ -270,39 +197,10 @@ extern "C" int sq_mlens_render_device(sq_device_scene* s, const sq_camera* cam, 
     if (P == 0) return 0;
     if (check_list(d_index, L, P)) return 1;
     if (L == 0) return 0;
-    const long long nb_max = lensplan::max_batch((long long)L, work_bytes);       // never more than 2^31 - 1 slots a batch
-    if (nb_max < 1)
-        return sq_set_error("work_bytes = %zu is too small: one sub-ray of %lld pixels needs %zu", work_bytes, (long long)L,
-                            lensplan::work_bytes((long long)L, 1));
-    if ((uintptr_t)d_work % 16 != 0) return sq_set_error("d_work must be 16-byte aligned");
     const size_t p = (size_t)P;
     const NamedRange spans[7] = { { "d_index", d_index, 4 * (size_t)L }, { "d_sum", d_sum, 12 * p }, { "d_sum2", d_sum2, 12 * p },
                                   { "d_count", d_count, 4 * p }, { "d_avg", d_avg, 12 * p }, { "d_rgb", d_rgb, 3 * p }, { "d_work", d_work, work_bytes } };
-    if (refuse_overlaps(spans, 7)) return 1;
-    hipPointerAttribute_t attr;
-    SQ_HIP(hipPointerGetAttributes(&attr, d_work));
-    const int device = attr.device;
-    hipStream_t stream = (hipStream_t)hip_stream;
-    const RayArgs A = lensray::ray_args(cam, lens, S, R, w, h, sh, P);
-    for (long long r0 = r_begin; r0 < r_end; r0 += nb_max) {           // sq_lens_plan's batches over L
-        const int32_t b0 = (int32_t)r0, b1 = (int32_t)(r0 + nb_max < r_end ? r0 + nb_max : r_end);
-        const long long slots = (long long)(b1 - b0) * L;
-        const lensplan::Layout lay = lensplan::layout(slots);
-        char* base = (char*)d_work;
-        float* org = (float*)(base + lay.org);
-        float* dir = (float*)(base + lay.dir);
-        float* part = (float*)(base + lay.sum);
-        int64_t* seed = (int64_t*)(base + lay.seed);
-        const bool last = b1 == r_end;
-        SQ_HIP(hipSetDevice(device));
-        if (enqueue_rays(A, (long long)L, b0, b1, d_index, org, dir, seed, stream)) return 1;
-        if (sq_raytrace_rays_device(s, org, dir, seed, slots, 0, S / R, part, nullptr, nullptr, hip_stream)) {
-            const std::string why = sq_last_error();                  // the two libraries may or may not share the message buffer
-            return sq_set_error("%s", why.c_str());
-        }
-        SQ_HIP(hipSetDevice(device));
-        if (enqueue_fold(P, (long long)L, S / R, b0, b1, d_index, part, d_sum, d_sum2, last ? d_count : nullptr, last ? d_avg : nullptr,
-                         last ? d_rgb : nullptr, stream)) return 1;
-    }
-    return 0;
+    return lensframe::render_batches<true>(sq_mlens_rays, sq_mlens_fold, s, lensray::ray_args(cam, lens, S, R, w, h, sh, P),
+                                           Pixels{ P, (long long)L, d_index }, r_begin, r_end, 1.0f / (float)((long long)r_end * (S / R)), d_work,
+                                           work_bytes, spans, 7, d_sum, d_sum2, d_count, d_avg, d_rgb, hip_stream);
 }

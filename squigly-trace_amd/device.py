@@ -584,23 +584,14 @@ def rule_reference(sums, sums2, counts, mask, tol, eps):
     return ((np.asarray(mask) != 0) & ~converged).astype(np.uint8)
 
 
-class Adaptive(_Frame):
-    """A frame whose pixels stop receiving samples once a stopping rule calls them done (DeviceScene.render_rows_masked).
+class _AdaptiveFrame(_Frame):
+    """What Adaptive and AdaptiveLens share: the four state tensors and their adoption from a checkpoint, the picture, the live
+    count under the gap guard, and a step's frame around the subclass's render call and built-in rule.  A subclass counts in a
+    unit of its own (`_unit`: samples; sub-rays) of which the frame has `_limit`, each worth `_per` samples."""
 
-    Owns -- or adopts, to resume a checkpoint -- the folds `sums` and `sums2` [rows, h, 3], the per-pixel sample `counts` and
-    the `mask` of live pixels [rows, h], and `done`, the end of the last range rendered.  `step()` renders the next range
-    (`first` samples, then `step` at a time) for the live pixels, applies the rule and returns the (avg, rgb) picture, in
-    which a pixel that stopped after n samples keeps the mean of its first n samples: bit for bit the reference's fold over
-    the first n samples of the `samples`-sample frame.  rule: a callable (sums, sums2, counts, mask) -> new mask instead of
-    the built-in rule (DeviceScene.adaptive_update with tol, eps), which is a heuristic -- a pixel that has seen nothing but
-    black after `first` samples stops.  A pixel the rule switches back on after it was left out of a range stays out: its
-    fold would have a gap.  To checkpoint, copy the four tensors, `done` and `depth` away and pass them back in (depth as in
-    Progressive: a scene under another path depth refuses to resume), and `sky` likewise as sky=.
-    """
-
-    def __init__(self, dscene, cam, samples, w, h, tol, eps=1.0, first=8, step=8, cast=False, shard=(None, 0, 1), rule=None,
-                 sums=None, sums2=None, counts=None, mask=None, done=0, depth=None, sky=SCENE_SKY):
-        samples, done, first, step = int(samples), int(done), int(first), int(step)
+    def _setup(self, dscene, cam, samples, w, h, cast, shard, limit, per, tol, eps, first, step, done, rule, state, depth, sky):
+        """state: the constructor's sums, sums2, counts and mask by name.  Refuses in the constructors' one order."""
+        done, first, step = int(done), int(first), int(step)
         tol, eps = float(tol), float(eps)
         if samples < 1:
             raise ValueError(f"samples must be positive, got {samples}")
@@ -608,15 +599,16 @@ class Adaptive(_Frame):
             raise ValueError(f"tol and eps must be numbers >= 0, got {tol}, {eps}")
         if first < 1 or step < 1:
             raise ValueError(f"first and step must be positive, got {first}, {step}")
-        if not 0 <= done <= samples:
-            raise ValueError(f"done must be in [0, {samples}], got {done}")
+        if not 0 <= done <= limit:
+            raise ValueError(f"done must be in [0, {limit}], got {done}")
         if rule is not None and not callable(rule):
             raise ValueError("rule must be callable: (sums, sums2, counts, mask) -> mask")
-        if done and (sums is None or sums2 is None or counts is None or mask is None):
+        if done and any(state[name] is None for name in _STATE):
             raise ValueError("resuming (done > 0) needs sums, sums2, counts and mask as the checkpoint left them")
         rows = self._begin(dscene, cam, samples, w, h, cast, shard, depth=depth, sky=sky)
-        for name, t, fill in (("sums", sums, 0), ("sums2", sums2, 0), ("counts", counts, 0), ("mask", mask, 1)):
-            setattr(self, "_" + name, self._adopt(name, t, (rows, h) + _STATE[name][0], _STATE[name][1], fill))
+        for name, fill in (("sums", 0), ("sums2", 0), ("counts", 0), ("mask", 1)):
+            setattr(self, "_" + name, self._adopt(name, state[name], (rows, h) + _STATE[name][0], _STATE[name][1], fill))
+        self._limit, self._per = limit, per
         self.tol, self.eps, self.first, self.step_size, self.rule = tol, eps, first, step, rule
         self._done = done
         self._avg = torch.zeros((rows, h, 3), dtype=torch.float32, device=self._dev)
@@ -632,11 +624,11 @@ class Adaptive(_Frame):
         return int(live.sum().item())
 
     def _restore_picture(self):
-        """avg and rgb of a checkpoint: (1 / (float)count) *^ sum, as the call that last rendered the pixel wrote it (numpy's
-        float32 division and product are the device's correctly rounded ones), and the device's own tonemap of it."""
+        """avg and rgb of a checkpoint: (1 / (float)(count * per)) *^ sum, as the call that last rendered the pixel wrote it
+        (numpy's float32 division and product are the device's correctly rounded ones), and the device's own tonemap of it."""
         import numpy as np
-        c = self._counts.cpu().numpy()
-        s = self._sums.cpu().numpy()
+        c = self._counts.cpu().numpy().astype(np.int64) * self._per
+        s =self._sums.cpu().numpy()
         with np.errstate(all="ignore"):
             avg = (np.float32(1) / np.maximum(c, 1).astype(np.float32))[..., None] * s
         avg[c == 0] = 0
@@ -645,48 +637,78 @@ class Adaptive(_Frame):
         self._avg.copy_(torch.from_numpy(np.ascontiguousarray(avg)))
         self._rgb.copy_(torch.from_numpy(np.ascontiguousarray(rgb)))
 
-    sums = property(lambda self: self._sums, doc="Per-pixel fold of the sample radiances over the pixel's first counts samples.")
-    sums2 = property(lambda self: self._sums2, doc="Per-pixel fold of r * r over the same samples.")
-    counts = property(lambda self: self._counts, doc="Samples each pixel has received (int32 CUDA tensor [rows, h]).")
+    sums = property(lambda self: self._sums, doc="Per-pixel fold of the radiances (of samples; of sub-ray sums) over the pixel's first counts units.")
+    sums2 = property(lambda self: self._sums2, doc="Per-pixel fold of their squares over the same units.")
+    counts = property(lambda self: self._counts, doc="Units (samples; sub-rays) each pixel has received (int32 CUDA tensor [rows, h]).")
     mask = property(lambda self: self._mask, doc="1 = the pixel is still live (uint8 CUDA tensor [rows, h]).")
-    done = property(lambda self: self._done, doc="End of the last sample range rendered.")
+    done = property(lambda self: self._done, doc="End of the last range (of samples; of sub-rays) rendered.")
     live = property(lambda self: self._live, doc="Pixels the next step would render.")
 
     @property
     def finished(self):
-        return self._live == 0 or self._done >= self.samples
+        return self._live == 0 or self._done >= self._limit
 
     @property
     def samples_spent(self):
         """Samples rendered so far, over all pixels (waits for the device)."""
-        return int(self._counts.sum(dtype=torch.int64).item())
+        return int(self._counts.sum(dtype=torch.int64).item()) * self._per
 
     def step(self, stream=None):
         """Render the next range for the live pixels and apply the rule; returns the (avg, rgb) CUDA tensors of the frame."""
         if self.finished:
             raise RuntimeError("the frame is finished: no pixel is live" if self._live == 0
-                               else f"the frame is finished: all {self.samples} samples are rendered")
+                               else f"the frame is finished: all {self._limit} {self._unit} are rendered")
         self._unchanged()
-        k_end = min(self._done + (self.first if self._done == 0 else self.step_size), self.samples)
-        self.dscene.render_rows_masked(self.cam, self.samples, self.w, self.h, self._done, k_end, self._sums, mask=self._mask,
-                                       sums2=self._sums2, counts=self._counts, cast=self.cast, shard=self.shard, stream=stream,
-                                       out_avg=self._avg, out_rgb=self._rgb)
-        self._done = k_end
+        end = min(self._done + (self.first if self._done == 0 else self.step_size), self._limit)
+        self._render(self._done, end, stream)
+        self._done = end
         if self.rule is None:
-            self._live = self.dscene.adaptive_update(self._sums, self._sums2, self._counts, self._mask, self.tol, self.eps,
-                                                     stream=stream)
+            self._builtin_rule(stream)
         else:
-            _, st = P.call_stream(self._mask.device, stream)
-            with torch.cuda.stream(st):
-                new = torch.as_tensor(self.rule(self._sums, self._sums2, self._counts, self._mask), device=self._mask.device)
-                if tuple(new.shape) != tuple(self._mask.shape):
-                    raise ValueError(f"rule must return a mask of shape {tuple(self._mask.shape)}, got {tuple(new.shape)}")
-                self._mask.copy_((new != 0).to(torch.uint8))
-                self._live = self._count_live()
+            self._callers_rule(stream)
         return self._avg, self._rgb
 
+    def _callers_rule(self, stream):
+        _, st = P.call_stream(self._mask.device, stream)
+        with torch.cuda.stream(st):
+            new = torch.as_tensor(self.rule(self._sums, self._sums2, self._counts, self._mask), device=self._mask.device)
+            if tuple(new.shape) != tuple(self._mask.shape):
+                raise ValueError(f"rule must return a mask of shape {tuple(self._mask.shape)}, got {tuple(new.shape)}")
+            self._mask.copy_((new != 0).to(torch.uint8))
+            self._live = self._count_live()
 
-class AdaptiveLens(_Frame):
+
+class Adaptive(_AdaptiveFrame):
+    """A frame whose pixels stop receiving samples once a stopping rule calls them done (DeviceScene.render_rows_masked).
+
+    Owns -- or adopts, to resume a checkpoint -- the folds `sums` and `sums2` [rows, h, 3], the per-pixel sample `counts` and
+    the `mask` of live pixels [rows, h], and `done`, the end of the last range rendered.  `step()` renders the next range
+    (`first` samples, then `step` at a time) for the live pixels, applies the rule and returns the (avg, rgb) picture, in
+    which a pixel that stopped after n samples keeps the mean of its first n samples: bit for bit the reference's fold over
+    the first n samples of the `samples`-sample frame.  rule: a callable (sums, sums2, counts, mask) -> new mask instead of
+    the built-in rule (DeviceScene.adaptive_update with tol, eps), which is a heuristic -- a pixel that has seen nothing but
+    black after `first` samples stops.  A pixel the rule switches back on after it was left out of a range stays out: its
+    fold would have a gap.  To checkpoint, copy the four tensors, `done` and `depth` away and pass them back in (depth as in
+    Progressive: a scene under another path depth refuses to resume), and `sky` likewise as sky=.
+    """
+    _unit = "samples"
+
+    def __init__(self, dscene, cam, samples, w, h, tol, eps=1.0, first=8, step=8, cast=False, shard=(None, 0, 1), rule=None,
+                 sums=None, sums2=None, counts=None, mask=None, done=0, depth=None, sky=SCENE_SKY):
+        samples = int(samples)
+        self._setup(dscene, cam, samples, w, h, cast, shard, samples, 1, tol, eps, first, step, done, rule,
+                    dict(sums=sums, sums2=sums2, counts=counts, mask=mask), depth, sky)
+
+    def _render(self, k_begin, k_end, stream):
+        self.dscene.render_rows_masked(self.cam, self.samples, self.w, self.h, k_begin, k_end, self._sums, mask=self._mask,
+                                       sums2=self._sums2, counts=self._counts, cast=self.cast, shard=self.shard, stream=stream,
+                                       out_avg=self._avg, out_rgb=self._rgb)
+
+    def _builtin_rule(self, stream):
+        self._live = self.dscene.adaptive_update(self._sums, self._sums2, self._counts, self._mask, self.tol, self.eps, stream=stream)
+
+
+class AdaptiveLens(_AdaptiveFrame):
     """Adaptive for an anti-aliased, depth-of-field frame (DeviceScene.live_pixels, render_lens_masked): a pixel stops receiving
     SUB-RAYS once the stopping rule calls it done, and a stopped pixel costs no ray.
 
@@ -698,93 +720,28 @@ class AdaptiveLens(_Frame):
     sums2, counts, mask) -> new mask instead of the built-in one, which is DeviceScene.adaptive_update with tol and eps * n * n:
     the sub-ray sums are n times a sample's size, so that is Adaptive's criterion on the pixel mean.  The gap guard, checkpoints,
     depth= and sky= are Adaptive's.  work_mb: as in render_lens."""
+    _unit = "sub-rays"
 
     def __init__(self, dscene, cam, lens, samples, subrays, w, h, tol, eps=1.0, first=1, step=1, shard=(None, 0, 1), rule=None,
                  sums=None, sums2=None, counts=None, mask=None, done=0, depth=None, sky=SCENE_SKY, work_mb=None):
         from .lens import frame_args
         samples, subrays, _, _ = frame_args(lens, samples, subrays)
-        done, first, step = int(done), int(first), int(step)
-        tol, eps = float(tol), float(eps)
-        if not tol >= 0 or not eps >= 0:
-            raise ValueError(f"tol and eps must be numbers >= 0, got {tol}, {eps}")
-        if first < 1 or step < 1:
-            raise ValueError(f"first and step must be positive, got {first}, {step}")
-        if not 0 <= done <= subrays:
-            raise ValueError(f"done must be in [0, {subrays}], got {done}")
-        if rule is not None and not callable(rule):
-            raise ValueError("rule must be callable: (sums, sums2, counts, mask) -> mask")
-        if done and (sums is None or sums2 is None or counts is None or mask is None):
-            raise ValueError("resuming (done > 0) needs sums, sums2, counts and mask as the checkpoint left them")
-        rows = self._begin(dscene, cam, samples, w, h, False, shard, depth=depth, sky=sky)
-        for name, t, fill in (("sums", sums, 0), ("sums2", sums2, 0), ("counts", counts, 0), ("mask", mask, 1)):
-            setattr(self, "_" + name, self._adopt(name, t, (rows, h) + _STATE[name][0], _STATE[name][1], fill))
         self.lens, self.subrays, self.n, self.work_mb = lens, subrays, samples // subrays, work_mb
-        self.tol, self.eps, self.first, self.step_size, self.rule = tol, eps, first, step, rule
-        self._done = done
-        self._avg = torch.zeros((rows, h, 3), dtype=torch.float32, device=self._dev)
-        self._rgb = torch.zeros((rows, h, 3), dtype=torch.uint8, device=self._dev)
-        if done:
-            self._restore_picture()
-        self._live = self._count_live()
+        self._setup(dscene, cam, samples, w, h, False, shard, subrays, self.n, tol, eps, first, step, done, rule,
+                    dict(sums=sums, sums2=sums2, counts=counts, mask=mask), depth, sky)
 
-    _count_live = Adaptive._count_live
-
-    def _restore_picture(self):
-        """avg and rgb of a checkpoint: (1 / (float)(count * n)) *^ sum, as the call that last rendered the pixel wrote it."""
-        import numpy as np
-        c = self._counts.cpu().numpy().astype(np.int64) * self.n
-        s = self._sums.cpu().numpy()
-        with np.errstate(all="ignore"):
-            avg = (np.float32(1) / np.maximum(c, 1).astype(np.float32))[..., None] * s
-        avg[c == 0] = 0
-        rgb = N.debug_eval("tonemap", avg.reshape(-1, 3), device=self.dscene.device).reshape(avg.shape)
-        rgb[c == 0] = 0
-        self._avg.copy_(torch.from_numpy(np.ascontiguousarray(avg)))
-        self._rgb.copy_(torch.from_numpy(np.ascontiguousarray(rgb)))
-
-    sums = property(lambda self: self._sums, doc="Per-pixel fold of the sub-ray sums over the pixel's first counts sub-rays.")
-    sums2 = property(lambda self: self._sums2, doc="Per-pixel fold of s * s over the same sub-ray sums s.")
-    counts = property(lambda self: self._counts, doc="Sub-rays each pixel has received (int32 CUDA tensor [rows, h]).")
     sample_counts = property(lambda self: self._counts * self.n, doc="Samples each pixel has received: counts * n.")
-    mask = property(lambda self: self._mask, doc="1 = the pixel is still live (uint8 CUDA tensor [rows, h]).")
-    done = property(lambda self: self._done, doc="End of the last sub-ray range rendered.")
-    live = property(lambda self: self._live, doc="Pixels the next step would render.")
 
-    @property
-    def finished(self):
-        return self._live == 0 or self._done >= self.subrays
-
-    @property
-    def samples_spent(self):
-        """Samples rendered so far, over all pixels (waits for the device)."""
-        return int(self._counts.sum(dtype=torch.int64).item()) * self.n
-
-    def step(self, stream=None):
-        """List the live pixels, render their next sub-rays and apply the rule; returns the (avg, rgb) CUDA tensors of the frame."""
-        if self.finished:
-            raise RuntimeError("the frame is finished: no pixel is live" if self._live == 0
-                               else f"the frame is finished: all {self.subrays} sub-rays are rendered")
-        self._unchanged()
-        r_end = min(self._done + (self.first if self._done == 0 else self.step_size), self.subrays)
-        index, _ = self.dscene.live_pixels(self._mask, self._counts, self._done, stream=stream)
+    def _render(self, r_begin, r_end, stream):
+        index, _ = self.dscene.live_pixels(self._mask, self._counts, r_begin, stream=stream)
         # the list's length is the live count the last step (or the constructor) already brought to the host: no wait here
-        self.dscene.render_lens_masked(self.cam, self.lens, self.samples, self.subrays, self.w, self.h, self._done, r_end, self._sums,
+        self.dscene.render_lens_masked(self.cam, self.lens, self.samples, self.subrays, self.w, self.h, r_begin, r_end, self._sums,
                                        index, self._live, sums2=self._sums2, counts=self._counts, shard=self.shard,
                                        work_mb=self.work_mb, out_avg=self._avg, out_rgb=self._rgb, stream=stream)
-        self._done = r_end
-        if self.rule is None:
-            self.dscene.adaptive_update(self._sums, self._sums2, self._counts, self._mask, self.tol, self.eps * self.n * self.n,
-                                        stream=stream)
-            # the next list's length is the gap-guarded count, which is the rule's own unless a checkpoint brought a pixel with a gap
-            _, st = P.call_stream(self._mask.device, stream)
-            with torch.cuda.stream(st):
-                self._live = self._count_live()
-        else:
-            _, st = P.call_stream(self._mask.device, stream)
-            with torch.cuda.stream(st):
-                new = torch.as_tensor(self.rule(self._sums, self._sums2, self._counts, self._mask), device=self._mask.device)
-                if tuple(new.shape) != tuple(self._mask.shape):
-                    raise ValueError(f"rule must return a mask of shape {tuple(self._mask.shape)}, got {tuple(new.shape)}")
-                self._mask.copy_((new != 0).to(torch.uint8))
-                self._live = self._count_live()
-        return self._avg, self._rgb
+
+    def _builtin_rule(self, stream):
+        self.dscene.adaptive_update(self._sums, self._sums2, self._counts, self._mask, self.tol, self.eps * self.n * self.n, stream=stream)
+        # the next list's length is the gap-guarded count, which is the rule's own unless a checkpoint brought a pixel with a gap
+        _, st = P.call_stream(self._mask.device, stream)
+        with torch.cuda.stream(st):
+            self._live = self._count_live()

@@ -56,6 +56,10 @@ class Lens(C.Structure):
 _lib = None
 
 
+# a frame in both lens libraries' calls: cam, lens, S, R, r_begin, r_end, w, h, shard
+FRAME_ARGTYPES = [C.POINTER(N.Camera), C.POINTER(Lens)] + 6 * [C.c_int32] + [N.Shard]
+
+
 def lib():
     global _lib
     if _lib is not None:
@@ -69,7 +73,7 @@ def lib():
     L.sq_lens_work_bytes.restype = sz
     L.sq_lens_plan.argtypes = [i64, i32, i32, sz, vp, i32]
     L.sq_lens_plan.restype = i32
-    frame = [C.POINTER(N.Camera), C.POINTER(Lens), i32, i32, i32, i32, i32, i32, N.Shard]
+    frame = FRAME_ARGTYPES
     L.sq_lens_rays_device.argtypes = [i32] + frame + [vp, vp, vp, vp]
     L.sq_lens_fold_device.argtypes = [i32, i64, i32, i32, i32, vp, vp, vp, vp, vp, vp]
     L.sq_lens_render_device.argtypes = [vp] + frame + [vp, sz, vp, vp, vp, vp, vp]
@@ -137,6 +141,19 @@ def _size_check(rows, h, subrays=1):
     return pixels
 
 
+def workspace(work_mb):
+    """work_mb of render_lens and render_lens_masked: SquiglyError unless it is a number > 0.  Returns sized(pixels, subrays): the
+    bytes of workspace the call hands the library for that many sub-rays of that many pixels -- all they need, at most work_mb MiB."""
+    if isinstance(work_mb, bool) or not isinstance(work_mb, (int, float)) or not work_mb > 0 or not math.isfinite(work_mb):
+        raise N.SquiglyError(f"work_mb must be a number > 0, got {work_mb!r}")
+    budget = int(work_mb * 2 ** 20)
+
+    def sized(pixels, subrays):
+        need = work_bytes(pixels, subrays) if pixels else 0
+        return min(need, budget) if need else budget
+    return sized
+
+
 def lens_rays(ds, cam, lens, samples, subrays, w, h, shard=(None, 0, 1), r_range=None, stream=None):
     """DeviceScene.lens_rays: the sub-rays [r_begin, r_end) of every pixel of the shard (sq_lens_rays_device) as (origins,
     directions, seeds): float32 CUDA tensors [nb, rows, h, 3] and int64 [nb, rows, h], nb = r_end - r_begin.  With them
@@ -168,8 +185,7 @@ def render_lens(ds, cam, lens, samples, subrays, w, h, shard=(None, 0, 1), r_ran
     and its bits do not depend on that.  Runs under the scene's depth and sky."""
     import torch
     S, R, r0, r1 = frame_args(lens, samples, subrays, r_range)
-    if isinstance(work_mb, bool) or not isinstance(work_mb, (int, float)) or not work_mb > 0 or not math.isfinite(work_mb):
-        raise N.SquiglyError(f"work_mb must be a number > 0, got {work_mb!r}")
+    sized = workspace(work_mb)
     sh, rows = P.shard_rows(int(w), shard)
     pixels = _size_check(rows, h)
     s1, s2 = sums if isinstance(sums, (tuple, list)) else (sums, None)
@@ -182,9 +198,7 @@ def render_lens(ds, cam, lens, samples, subrays, w, h, shard=(None, 0, 1), r_ran
     for name, t in (("sums", s1), ("sums2", s2)):
         if t is not None:
             P.tensor(name, t, (rows, h, 3), torch.float32, dev)
-    budget = int(work_mb * 2 ** 20)
-    need = work_bytes(pixels, r1 - r0) if pixels else 0
-    nbytes = min(need, budget) if need else budget
+    nbytes = sized(pixels, r1 - r0)
     with torch.cuda.stream(st):      # outputs and workspace are allocated (and the workspace freed) in the order of the call's stream
         if s1 is None:
             s1 = torch.empty((rows, h, 3), dtype=torch.float32, device=dev)

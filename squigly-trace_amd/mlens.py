@@ -6,7 +6,6 @@ memory, streams); the list, the rays and the fold come from the HIP kernels of c
 libsquigly_hip.so's radiance query.  There is no fallback: a missing library raises.
 """
 import ctypes as C
-import math
 import os
 
 from . import _native as N
@@ -33,7 +32,7 @@ def lib():
     vp, i32, i64, sz = C.c_void_p, C.c_int32, C.c_int64, C.c_size_t
     L.sq_mlens_last_error.restype = C.c_char_p
     L.sq_mlens_build_id.restype = C.c_char_p
-    frame = [C.POINTER(N.Camera), C.POINTER(LN.Lens), i32, i32, i32, i32, i32, i32, N.Shard]
+    frame = LN.FRAME_ARGTYPES
     L.sq_mlens_live_device.argtypes = [i32, i64, i32, vp, vp, vp, vp, vp]
     L.sq_mlens_rays_device.argtypes = [i32] + frame + [vp, i64, vp, vp, vp, vp]
     L.sq_mlens_fold_device.argtypes = [i32, i64, i32, i32, i32, i32, vp, i64, vp, vp, vp, vp, vp, vp, vp]
@@ -95,8 +94,7 @@ def render_lens_masked(ds, cam, lens, samples, subrays, w, h, r_begin, r_end, su
     the listed pixels.  Runs under the scene's depth and sky."""
     import torch
     S, R, r0, r1 = LN.frame_args(lens, samples, subrays, (r_begin, r_end))
-    if isinstance(work_mb, bool) or not isinstance(work_mb, (int, float)) or not work_mb > 0 or not math.isfinite(work_mb):
-        raise N.SquiglyError(f"work_mb must be a number > 0, got {work_mb!r}")
+    sized = LN.workspace(work_mb)
     sh, rows = P.shard_rows(int(w), shard)
     pixels = LN._size_check(rows, h)
     L = LN._int("n_live", n_live)
@@ -115,9 +113,7 @@ def render_lens_masked(ds, cam, lens, samples, subrays, w, h, r_begin, r_end, su
         raise N.SquiglyError(f"index must be a contiguous torch.int32 tensor of at least n_live = {L} entries on {dev}")
     if L == 0:
         return out_avg, out_rgb
-    budget = int(work_mb * 2 ** 20)
-    need = LN.work_bytes(L, r1 - r0)
-    nbytes = min(need, budget) if need else budget
+    nbytes = sized(L, r1 - r0)
     with torch.cuda.stream(st):      # the workspace is allocated (and freed) in the order of the call's stream
         work = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
         check(lib().sq_mlens_render_device(ds._h, C.byref(cam), C.byref(lens), S, R, r0, r1, int(w), int(h), sh, index.data_ptr(), L,

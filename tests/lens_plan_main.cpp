@@ -35,6 +35,16 @@ int main(int argc, char** argv) {
             if (lensplan::plan(P, r0, r1, bytes, shorter.data(), shown - 1) != count) return 4;
             if (shorter.back() != -7 || std::memcmp(shorter.data(), out.data(), 2 * (size_t)(shown - 1) * sizeof(int32_t)) != 0) return 5;
         }
+        // the batches a frame enqueues (csrc/sq_lens_frame.h walks batch_count / batch) are the ones plan() lists: every listed one,
+        // and the last one of a plan too long to list, which must end the range
+        const long long nb = lensplan::max_batch(P, bytes);
+        if (lensplan::batch_count(r0, r1, nb) != count) return 7;
+        for (int32_t i = 0; i < shown; ++i) {
+            const lensplan::Batch b = lensplan::batch(r0, r1, nb, i);
+            if (b.r0 != out[2 * i] || b.r1 != out[2 * i + 1] || b.r1 <= b.r0 || b.r1 - b.r0 > nb) return 8;
+            if (b.r0 != (i == 0 ? r0 : out[2 * i - 1])) return 9;
+        }
+        if (lensplan::batch(r0, r1, nb, (int64_t)count - 1).r1 != r1) return 10;
         std::printf("plan %d:", count);
         for (int32_t i = 0; i < shown; ++i) {
             const lensplan::Layout L = lensplan::layout(P * (out[2 * i + 1] - out[2 * i]));

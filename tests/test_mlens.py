@@ -94,6 +94,8 @@ def test_the_other_libraries_did_not_gain_it(sqt, lens, mlens):
     assert not mine & set(b.SOURCES + b.HEADERS + b.DENOISE_SOURCES + b.DENOISE_HEADERS + b.LENS_SOURCES + b.LENS_HEADERS)
     assert mine | {"sq_lens_plan.h", "sq_lens_ray.h", "../../include/squigly_lens.h"} <= set(b.MLENS_SOURCES + b.MLENS_HEADERS)
     assert "sq_lens_ray.h" in b.LENS_HEADERS                     # the contract is written once, and both ids follow it
+    assert "sq_lens_frame.h" in b.LENS_HEADERS and "sq_lens_frame.h" in b.MLENS_HEADERS      # ... and so are the kernels and the batch loop
+    assert "sq_lens_frame.h" not in b.SOURCES + b.HEADERS + b.DENOISE_SOURCES + b.DENOISE_HEADERS
     assert b.MLENS["link"] == b.LENS["link"] and b.MLENS["salt"] not in (b.LENS["salt"], b.MAIN["salt"], b.DENOISE["salt"])
     needed = subprocess.check_output(["readelf", "-d", mlens.LIB_PATH]).decode()
     assert "libsquigly_hip.so" in needed and "$ORIGIN" in needed and "libsquigly_lens" not in needed
@@ -111,7 +113,8 @@ def test_ids_are_separate(lens, mlens, sqt, tmp_path):
     before = ids()
     b.CSRC = str(tmp_path / "a" / "b" / "csrc")
     assert ids() == before
-    for name, moves in (("sq_mlens.hip", (3,)), ("../../include/squigly_mlens.h", (3,)), ("sq_lens_ray.h", (2, 3)), ("sq_lens_plan.h", (2, 3))):
+    for name, moves in (("sq_mlens.hip", (3,)), ("../../include/squigly_mlens.h", (3,)), ("sq_lens_ray.h", (2, 3)), ("sq_lens_plan.h", (2, 3)),
+                        ("sq_lens_frame.h", (2, 3))):
         with open(os.path.join(b.CSRC, name), "a") as fh:
             fh.write("// changed\n")
         after = ids()
