@@ -11,6 +11,8 @@ from .png import write_png                                                      
 from .denoise import denoise, denoise_variance, denoise_frame, Guides                # noqa: F401
 # anti-aliasing and depth of field: its module is importlib.import_module("squigly-trace_amd.lens")
 from .lens import Lens, LensFrame                                                    # noqa: F401
+# motion blur: its module is importlib.import_module("squigly-trace_amd.shutter")
+from .shutter import Motion                                                          # noqa: F401
 
 
 def device_count() -> int:

@@ -1,5 +1,6 @@
 """Build libsquigly_hip.so (HIP kernels for gfx950 + host side), libsquigly_denoise.so (the denoiser), libsquigly_lens.so (jittered,
-thin-lens primary rays) and libsquigly_mlens.so (those rays for the live pixels of a mask) in-tree with hipcc.
+thin-lens primary rays), libsquigly_mlens.so (those rays for the live pixels of a mask) and libsquigly_shutter.so (those rays, dense
+or listed, under a camera that moves during the exposure) in-tree with hipcc.
 
     python squigly-trace_amd/build.py [--force]
 
@@ -53,13 +54,20 @@ MLENS_OUT = os.path.join(HERE, "libsquigly_mlens.so")
 MLENS_SOURCES = ["sq_mlens.hip"]
 MLENS_HEADERS = LENS_HEADERS + ["../../include/squigly_mlens.h"]
 
+# The fifth library: motion blur (include/squigly_shutter.h).  A client of libsquigly_hip.so like the two lens libraries, whose headers
+# it shares as text, not as symbols; the pose of an instant (sq_shutter_pose.h) is its own.
+SHUTTER_OUT = os.path.join(HERE, "libsquigly_shutter.so")
+SHUTTER_SOURCES = ["sq_shutter.hip"]
+SHUTTER_HEADERS = LENS_HEADERS + ["sq_shutter_pose.h", "../../include/squigly_shutter.h"]
+
 # One description per library.  macro: the -D that carries the id into the library (what sq_build_id(), sq_denoise_build_id(),
-# sq_lens_build_id() and sq_mlens_build_id() return); salt: what the id's hash starts from, so that no two libraries share an id; link: behind the output.
+# sq_lens_build_id(), sq_mlens_build_id() and sq_shutter_build_id() return); salt: what the id's hash starts from, so that no two libraries share an id; link: behind the output.
 MAIN = dict(out=OUT, sources=SOURCES, headers=HEADERS, macro="SQ_BUILD_ID", salt=b"", link=[])
 DENOISE = dict(out=DENOISE_OUT, sources=DENOISE_SOURCES, headers=DENOISE_HEADERS, macro="SQ_DENOISE_BUILD_ID", salt=b"denoise\0", link=[])
 LENS = dict(out=LENS_OUT, sources=LENS_SOURCES, headers=LENS_HEADERS, macro="SQ_LENS_BUILD_ID", salt=b"lens\0",
             link=["-L" + HERE, "-lsquigly_hip", "-Wl,-rpath,$ORIGIN"])
 MLENS = dict(out=MLENS_OUT, sources=MLENS_SOURCES, headers=MLENS_HEADERS, macro="SQ_MLENS_BUILD_ID", salt=b"mlens\0", link=LENS["link"])
+SHUTTER = dict(out=SHUTTER_OUT, sources=SHUTTER_SOURCES, headers=SHUTTER_HEADERS, macro="SQ_SHUTTER_BUILD_ID", salt=b"shutter\0", link=LENS["link"])
 
 
 def lib_source_id(lib, extra=()):
@@ -85,7 +93,7 @@ def lib_stale(lib):
 
 
 def compile_lib(lib, extra=(), out=None):
-    """out: an experimental variant (extra options) beside the product library; SQ_LIB_PATH / SQ_LENS_LIB_PATH / SQ_MLENS_LIB_PATH select it at load time."""
+    """out: an experimental variant (extra options) beside the product library; SQ_LIB_PATH / SQ_LENS_LIB_PATH / SQ_MLENS_LIB_PATH / SQ_SHUTTER_LIB_PATH select it at load time."""
     out = out or lib["out"]
     subprocess.check_call([hipcc()] + FLAGS + list(extra) + ['-D%s="%s"' % (lib["macro"], lib_source_id(lib, extra)), "-x", "hip"]
                           + [os.path.join(CSRC, s) for s in lib["sources"]] + ["-o", out] + lib["link"])
@@ -106,6 +114,8 @@ def lens_source_id(extra=()): return lib_source_id(LENS, extra)
 def lens_stale(): return lib_stale(LENS)
 def mlens_source_id(extra=()): return lib_source_id(MLENS, extra)
 def mlens_stale(): return lib_stale(MLENS)
+def shutter_source_id(extra=()): return lib_source_id(SHUTTER, extra)
+def shutter_stale(): return lib_stale(SHUTTER)
 
 
 def build_client(lib, force=False, extra=(), out=None):
@@ -117,6 +127,7 @@ def build_client(lib, force=False, extra=(), out=None):
 
 def build_lens(force=False, extra=(), out=None): return build_client(LENS, force, extra, out)
 def build_mlens(force=False, extra=(), out=None): return build_client(MLENS, force, extra, out)
+def build_shutter(force=False, extra=(), out=None): return build_client(SHUTTER, force, extra, out)
 
 
 def build(force=False, extra=(), out=None):
@@ -137,6 +148,7 @@ def build(force=False, extra=(), out=None):
                                "-Wl,--allow-shlib-undefined"])
     build_lens(force)
     build_mlens(force)
+    build_shutter(force)
     return OUT
 
 

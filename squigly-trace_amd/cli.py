@@ -10,7 +10,7 @@ import os
 import sys
 import time
 
-from . import BIH, Lens, Mesh, Settings, camera_from_text, lib, load_camera, render, render_adaptive, render_lens_rgb8, render_progressive, render_views_rgb8, write_png
+from . import BIH, Lens, Mesh, Motion, Settings, camera_from_text, lib, load_camera, render, render_adaptive, render_lens_rgb8, render_progressive, render_views_rgb8, write_png
 from ._native import SquiglyError
 
 
@@ -204,13 +204,31 @@ def build_parser():
                    help="Depth of field: radius of the lens in world units (default 0: a pinhole)")
     p.add_argument("--focus", type=finite_positive_float, default=None, metavar="F",
                    help="With --aperture: forward distance of the plane in focus (default 1)")
+    # not flags of the reference: the camera moves while the shutter is open (include/squigly_shutter.h)
+    p.add_argument("--shutter-camera", type=camera_text, default=None, metavar="FILE",
+                   help="Motion blur: a camera file with the pose as the shutter closes; --camera is the pose as it opens, and the "
+                        "primary rays of a pixel (--subrays) are as many consecutive instants in between")
+    p.add_argument("--shutter-jitter", type=unit_float, default=None, metavar="T",
+                   help="With --shutter-camera: how much of its own part of the exposure a primary ray's instant is drawn from, "
+                        "0..1 (default 1)")
     return p
 
 
+def camera_text(path):
+    """The text of a camera file, checked to be one."""
+    try:
+        with open(path, "rb") as f:
+            text = f.read()
+        camera_from_text(text)
+    except Exception as e:                                      # a missing file, or whatever the library says about its text
+        raise argparse.ArgumentTypeError(f"{path}: {e}")
+    return text
+
+
 def lens_of(a):
-    """The Lens of --aa / --aperture / --focus, or None when the frame has none of them."""
+    """The Lens of --aa / --aperture / --focus, or None when the frame has none of them; --shutter-camera alone means Lens(jitter=0)."""
     if a.aa is None and a.aperture is None:
-        return None
+        return Lens(jitter=0.0) if a.shutter_camera is not None else None
     return Lens(jitter=0.0 if a.aa is None else a.aa, aperture=a.aperture or 0.0, focus=1.0 if a.focus is None else a.focus)
 
 
@@ -231,9 +249,11 @@ def parse_args(argv=None):
         p.error("--depth cannot be combined with --cast (a cast image has no paths)")
     if a.sky is not None and a.cast:
         p.error("--sky cannot be combined with --cast (a cast image has no sky)")
-    if a.aa is None and a.aperture is None:
+    if a.shutter_jitter is not None and a.shutter_camera is None:
+        p.error("--shutter-jitter needs --shutter-camera")
+    if a.aa is None and a.aperture is None and a.shutter_camera is None:
         if a.subrays is not None:
-            p.error("--subrays needs --aa or --aperture")
+            p.error("--subrays needs --aa, --aperture or --shutter-camera")
         if a.focus is not None:
             p.error("--focus needs --aperture")
     else:
@@ -242,7 +262,7 @@ def parse_args(argv=None):
         for flag, given in (("--cast", a.cast), ("--views", a.views is not None), ("--adaptive", a.adaptive is not None),
                             ("--preview-every", a.preview_every is not None)):
             if given:
-                p.error(f"--aa, --subrays, --aperture and --focus cannot be combined with {flag}")
+                p.error(f"--aa, --subrays, --aperture, --focus and --shutter-camera cannot be combined with {flag}")
         if a.samples < 1 or a.samples % (a.subrays or a.samples):
             p.error(f"--subrays must divide --samples (got {a.subrays} and {a.samples})")
     return a
@@ -297,8 +317,12 @@ def main(argv=None):
             with open(a.counts, "wb") as f:                     # the name as given (np.save would append .npy to a path)
                 np.save(f, counts.astype(np.int32))
     elif lens_of(a) is not None:
+        motion = None
+        if a.shutter_camera is not None:
+            with open(settings.cameraPath, "rb") as f:
+                motion = Motion(f.read(), a.shutter_camera, 1.0 if a.shutter_jitter is None else a.shutter_jitter)
         write_png(settings.savePath, render_lens_rgb8(bih, cam, settings.samples, settings.dimensions, lens=lens_of(a), subrays=a.subrays,
-                                                      depth=a.depth, sky=a.sky))
+                                                      depth=a.depth, sky=a.sky, motion=motion))
     elif a.preview_every is None and a.light is None and a.depth is None and a.sky is None:
         render(bih, cam, settings)
     elif a.preview_every is None:                               # caller-given lights, depths and skies live on a resident scene: one step of all samples

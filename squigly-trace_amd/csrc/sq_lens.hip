@@ -39,7 +39,7 @@ using lensray::refuse_slots;
 // ---- the rays: one lane per (sub-ray, pixel), slot = sub-ray * P + pixel ----
 __global__ __launch_bounds__(kBlock) void sq_lens_rays(const RayArgs A, float* __restrict__ org, float* __restrict__ dir,
                                                        long long* __restrict__ seed) {
-    lensframe::rays_body<false>(A, A.P, nullptr, org, dir, seed);
+    lensframe::rays_body<false>(A, A.P, nullptr, org, dir, seed, lensray::StaticRay{});
 }
 
 // ---- the fold: one lane per pixel, the sub-ray sums part[b][pixel] in the order of b ----

@@ -6,13 +6,16 @@
 // scatter through the list, and the fold also stores the pixel's sub-ray count.  The choice is made when the kernel is compiled,
 // so the dense kernels carry no load of an index, no bounds test and no count store.
 //
-// Each library defines its own two __global__ kernels as calls of the bodies and hands them to the functions below.
+// Each library defines its own two __global__ kernels as calls of the bodies and hands them to the functions below.  The ray of a
+// lane is a parameter of the ray kernel's body, chosen when the kernel is compiled like Listed: lensray::StaticRay for the frame's
+// one camera, libsquigly_shutter.so's own for a camera that moves during the exposure -- the static kernels carry none of that.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
 
 #include <string>
+#include <type_traits>
 
 #include "sq_call_checks.h"
 #include "sq_lens_plan.h"
@@ -35,9 +38,9 @@ inline unsigned grid_for(long long units) {
 }
 
 // ---- the rays: one lane per (sub-ray, entry), slot = sub-ray * L + entry; the entry is the pixel, or names it through the list ----
-template <bool Listed>
+template <bool Listed, typename RayOf>
 __device__ __forceinline__ void rays_body(const RayArgs& A, const long long L, const int* __restrict__ index, float* __restrict__ org,
-                                          float* __restrict__ dir, long long* __restrict__ seed) {
+                                          float* __restrict__ dir, long long* __restrict__ seed, const RayOf ray_of) {
     for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < A.slots; i += (long long)gridDim.x * kBlock) {
         const int b = (int)(i / L);
         lensray::Ray ray;
@@ -47,10 +50,10 @@ __device__ __forceinline__ void rays_body(const RayArgs& A, const long long L, c
                 ray.o = ray.d = sq::mk(0.0f, 0.0f, 0.0f);
                 ray.base = 0;
             } else {
-                ray = lensray::sub_ray(A, pixel, A.r_begin + b);      // THE CONTRACT, csrc/sq_lens_ray.h
+                ray = ray_of(A, pixel, A.r_begin + b);                // THE CONTRACT, csrc/sq_lens_ray.h
             }
         } else {
-            ray = lensray::sub_ray(A, (int)(i - b * L), A.r_begin + b);
+            ray = ray_of(A, (int)(i - b * L), A.r_begin + b);
         }
         store3(org, i, ray.o);
         store3(dir, i, ray.d);
@@ -101,6 +104,17 @@ __device__ __forceinline__ void fold_body(const long long P, const long long L, 
 // What a frame is made over: the P pixels of the shard (L = P, index = NULL), or the first L entries of a list of them.
 struct Pixels { long long P, L; const int32_t* index; };
 
+// Launches a ray kernel.  `kernel` is the __global__ function itself when it takes RayArgs and the buffers only; a library whose
+// ray kernel takes more (libsquigly_shutter.so: the motion) hands in an object that is called with the grid, the stream and those
+// arguments, and launches its kernel itself.
+template <typename Kernel, typename... Args>
+void launch_rays(Kernel kernel, unsigned grid, hipStream_t stream, Args... args) {
+    if constexpr (std::is_pointer_v<Kernel>)
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), 0, stream, args...);
+    else
+        kernel(grid, stream, args...);
+}
+
 // Enqueues `kernel`, the library's ray kernel, for the sub-rays [r0, r1).
 template <bool Listed, typename Kernel>
 int enqueue_rays(Kernel kernel, RayArgs A, Pixels px, int32_t r0, int32_t r1, float* d_org, float* d_dir, int64_t* d_seed, hipStream_t stream) {
@@ -108,9 +122,9 @@ int enqueue_rays(Kernel kernel, RayArgs A, Pixels px, int32_t r0, int32_t r1, fl
     A.slots = (long long)(r1 - r0) * px.L;
     static_assert(sizeof(long long) == sizeof(int64_t), "seed bases are 64-bit");
     if constexpr (Listed)
-        hipLaunchKernelGGL(kernel, dim3(grid_for(A.slots)), dim3(kBlock), 0, stream, A, px.L, (const int*)px.index, d_org, d_dir, (long long*)d_seed);
+        launch_rays(kernel, grid_for(A.slots), stream, A, px.L, (const int*)px.index, d_org, d_dir, (long long*)d_seed);
     else
-        hipLaunchKernelGGL(kernel, dim3(grid_for(A.slots)), dim3(kBlock), 0, stream, A, d_org, d_dir, (long long*)d_seed);
+        launch_rays(kernel, grid_for(A.slots), stream, A, d_org, d_dir, (long long*)d_seed);
     SQ_HIP(hipGetLastError());
     return 0;
 }

@@ -25,10 +25,26 @@ struct RayArgs {
 struct Ray { sq::f3 o, d; long long base; };
 
 #if defined(__HIPCC__)
+// The camera a sub-ray is made under.  The arithmetic of a sub-ray is one text (sub_ray below); whose camera it is under is a
+// parameter chosen when the kernel is compiled:
+//     camera.plain(A)                      whether the frame makes no draw at all
+//     camera(A, r, plain, c, moved)        the Camera of sub-ray r; c is the Threefish block of ~base, drawn unless plain; moved is
+//                                          12 floats of the lane's own a camera that depends on the sub-ray may return pointers into
+struct Camera { const float* pos; const float* rot; };
+
+// The frame's one camera: RayArgs' pos and rot, whatever the sub-ray.
+struct StaticCamera {
+    __device__ __forceinline__ bool plain(const RayArgs& A) const {
+        return A.jitter == 0.0f && A.aperture == 0.0f;     // makeRay's ray: x + 0 * u is x for every draw u, so no draw is made
+    }
+    __device__ __forceinline__ Camera operator()(const RayArgs& A, int, bool, const uint64_t*, float*) const { return Camera{ A.pos, A.rot }; }
+};
+
 // o, d and base of sub-ray r of local pixel `pixel` of the shard.
-__device__ __forceinline__ Ray sub_ray(const RayArgs& A, int pixel, int r) {
+template <typename CameraOf>
+__device__ __forceinline__ Ray sub_ray(const RayArgs& A, int pixel, int r, const CameraOf& camera_of) {
     const float ww = (float)A.w, hh = (float)A.h;
-    const bool plain = A.jitter == 0.0f && A.aperture == 0.0f;     // makeRay's ray: x + 0 * u is x for every draw u, so no draw is made
+    const bool plain = camera_of.plain(A);
     const int j = pixel / A.h, x = pixel - j * A.h;
     const int blk = j / A.row_block;     // sq::shard_global_row, written out: through the function the kernel's registers are allocated differently
     const int y = (blk * A.n_shards + A.shard) * A.row_block + (j - blk * A.row_block);
@@ -36,8 +52,8 @@ __device__ __forceinline__ Ray sub_ray(const RayArgs& A, int pixel, int r) {
     ray.base = (long long)A.S * ((long long)x + (long long)y * A.w) + (long long)r * A.n;
     float xs = (float)x, ys = (float)y;
     float u2 = 0.0f, u3 = 0.0f;
+    uint64_t c[4];
     if (!plain) {
-        uint64_t c[4];
         sq::threefish256_key_only(~(uint64_t)ray.base, c);
         xs = (float)x + A.jitter * sq::unit_float((uint32_t)c[0]);
         ys = (float)y + A.jitter * sq::unit_float((uint32_t)(c[0] >> 32));
@@ -46,20 +62,30 @@ __device__ __forceinline__ Ray sub_ray(const RayArgs& A, int pixel, int r) {
     }
     const float xoffs = (xs - (ww / 2)) / ww;
     const float yoffs = ((hh / 2) - ys) / hh;
-    ray.o = sq::mk(A.pos[0], A.pos[1], A.pos[2]);
+    float moved[12];
+    const Camera cam = camera_of(A, r, plain, c, moved);
+    ray.o = sq::mk(cam.pos[0], cam.pos[1], cam.pos[2]);
     if (A.aperture == 0.0f) {
-        ray.d = sq::rot_vert(1.0f, xoffs, yoffs, A.rot);
+        ray.d = sq::rot_vert(1.0f, xoffs, yoffs, cam.rot);
     } else {
         const float rad = A.aperture * sq::fsqrt(u2);
         const float th = 2 * sq::kPi * u3;
         float sth, cth;
         sq::fsincos(th, sth, cth);
         const float lx = rad * cth, ly = rad * sth;
-        ray.o = ray.o + sq::rot_vert(0.0f, lx, ly, A.rot);
-        ray.d = sq::rot_vert(1.0f, xoffs - lx / A.focus, yoffs - ly / A.focus, A.rot);
+        ray.o = ray.o + sq::rot_vert(0.0f, lx, ly, cam.rot);
+        ray.d = sq::rot_vert(1.0f, xoffs - lx / A.focus, yoffs - ly / A.focus, cam.rot);
     }
     return ray;
 }
+
+// The per-lane ray function lensframe::rays_body is given: sub_ray under the library's camera.
+template <typename CameraOf>
+struct RayUnder {
+    CameraOf camera_of;
+    __device__ __forceinline__ Ray operator()(const RayArgs& A, int pixel, int r) const { return sub_ray(A, pixel, r, camera_of); }
+};
+using StaticRay = RayUnder<StaticCamera>;
 #endif
 
 // What every ray-making call refuses about its frame, in the order of the header's list; *P_out = the shard's pixels (0: empty).

@@ -108,7 +108,7 @@ __global__ __launch_bounds__(kLiveBlock) void sq_mlens_live(const long long P, c
 // ---- the rays: one lane per (sub-ray, list entry), slot = sub-ray * L + entry ----
 __global__ __launch_bounds__(kBlock) void sq_mlens_rays(const RayArgs A, const long long L, const int* __restrict__ index,
                                                         float* __restrict__ org, float* __restrict__ dir, long long* __restrict__ seed) {
-    lensframe::rays_body<true>(A, L, index, org, dir, seed);
+    lensframe::rays_body<true>(A, L, index, org, dir, seed, lensray::StaticRay{});
 }
 
 // ---- the fold: one lane per list entry, the sub-ray sums part[b][entry] in the order of b, into the listed pixel ----

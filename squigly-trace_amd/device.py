@@ -362,6 +362,30 @@ class DeviceScene(Owner):
         return render_lens_masked(self, cam, lens, samples, subrays, w, h, r_begin, r_end, sums, index, n_live, sums2, counts, shard,
                                   L.DEFAULT_WORK_MB if work_mb is None else work_mb, out_avg, out_rgb, stream)
 
+    def shutter_rays(self, motion, lens, samples, subrays, w, h, shard=(None, 0, 1), r_range=None, stream=None):
+        """lens_rays under a camera that moves during the exposure (shutter.py, sq_shutter_rays_device): sub-ray r of a pixel is
+        made under the pose of its own instant of `motion` (a Motion).  See shutter.shutter_rays."""
+        from .shutter import shutter_rays
+        return shutter_rays(self, motion, lens, samples, subrays, w, h, shard, r_range, stream)
+
+    def render_shutter(self, motion, lens, samples, subrays, w, h, shard=(None, 0, 1), r_range=None, sums=None, want_sum2=False,
+                       want_avg=True, want_rgb=True, work_mb=None, stream=None):
+        """The motion-blurred frame (shutter.py, sq_shutter_render_device): render_lens whose `subrays` primary rays per pixel are
+        as many consecutive instants of `motion`; returns LensFrame(sum, sum2, avg, rgb).  See shutter.render_shutter."""
+        from . import lens as L
+        from .shutter import render_shutter
+        return render_shutter(self, motion, lens, samples, subrays, w, h, shard, r_range, sums, want_sum2, want_avg, want_rgb,
+                              L.DEFAULT_WORK_MB if work_mb is None else work_mb, stream)
+
+    def render_shutter_masked(self, motion, lens, samples, subrays, w, h, r_begin, r_end, sums, index, n_live, sums2=None, counts=None,
+                              shard=(None, 0, 1), work_mb=None, out_avg=None, out_rgb=None, stream=None):
+        """render_lens_masked under a moving camera (shutter.py, sq_shutter_render_device with the list of live_pixels).  Returns
+        (out_avg, out_rgb).  See shutter.render_shutter_masked."""
+        from . import lens as L
+        from .shutter import render_shutter_masked
+        return render_shutter_masked(self, motion, lens, samples, subrays, w, h, r_begin, r_end, sums, index, n_live, sums2, counts,
+                                     shard, L.DEFAULT_WORK_MB if work_mb is None else work_mb, out_avg, out_rgb, stream)
+
     def raytrace(self, origins, directions, seeds=None, samples=1, k_range=None, sums=None, want_avg=True, want_rgb=False,
                  stream=None):
         """Lib.raytrace of each ray (sq_raytrace_rays_device): returns Radiance(sum, avg, rgb) CUDA tensors, enqueued on `stream`.
@@ -708,6 +732,18 @@ class Adaptive(_AdaptiveFrame):
         self._live = self.dscene.adaptive_update(self._sums, self._sums2, self._counts, self._mask, self.tol, self.eps, stream=stream)
 
 
+NO_MOTION_RECORD = object()     # checkpoint_motion= of AdaptiveLens: a fresh frame, or a checkpoint that is trusted to match
+
+
+def _motion_bits(motion):
+    """A motion as bytes, so that two motions are the same when their bits are; None = a static camera."""
+    return None if motion is None else motion.key()
+
+
+def _motion_words(motion):
+    return "no motion" if motion is None else f"the motion {motion!r}"
+
+
 class AdaptiveLens(_AdaptiveFrame):
     """Adaptive for an anti-aliased, depth-of-field frame (DeviceScene.live_pixels, render_lens_masked): a pixel stops receiving
     SUB-RAYS once the stopping rule calls it done, and a stopped pixel costs no ray.
@@ -719,13 +755,26 @@ class AdaptiveLens(_AdaptiveFrame):
     stopped after c sub-rays keeps (1 / (c * n)) * sum: bit for bit render_lens over r_range = (0, c).  rule: a callable (sums,
     sums2, counts, mask) -> new mask instead of the built-in one, which is DeviceScene.adaptive_update with tol and eps * n * n:
     the sub-ray sums are n times a sample's size, so that is Adaptive's criterion on the pixel mean.  The gap guard, checkpoints,
-    depth= and sky= are Adaptive's.  work_mb: as in render_lens."""
+    depth= and sky= are Adaptive's.  work_mb: as in render_lens.
+
+    motion (a Motion; None = the frame as it was, under `cam`): the frame is motion-blurred -- every step goes through
+    render_shutter_masked and `cam` is not read.  The frame records the motion as it records depth and sky: `motion` is part of a
+    checkpoint, to be passed back in, and a checkpoint (done > 0) resumed under another motion -- compared by bits -- or under none
+    is refused with checkpoint_motion=, which is what the checkpoint carried (the default, NO_MOTION_RECORD, is a fresh frame)."""
     _unit = "sub-rays"
 
     def __init__(self, dscene, cam, lens, samples, subrays, w, h, tol, eps=1.0, first=1, step=1, shard=(None, 0, 1), rule=None,
-                 sums=None, sums2=None, counts=None, mask=None, done=0, depth=None, sky=SCENE_SKY, work_mb=None):
+                 sums=None, sums2=None, counts=None, mask=None, done=0, depth=None, sky=SCENE_SKY, work_mb=None, motion=None,
+                 checkpoint_motion=NO_MOTION_RECORD):
         from .lens import frame_args
         samples, subrays, _, _ = frame_args(lens, samples, subrays)
+        if motion is not None:
+            from .shutter import motion_arg
+            motion_arg(motion)
+        if checkpoint_motion is not NO_MOTION_RECORD and _motion_bits(checkpoint_motion) != _motion_bits(motion):
+            raise N.SquiglyError(f"the checkpoint was rendered under {_motion_words(checkpoint_motion)}, the frame is given "
+                                 f"{_motion_words(motion)}: pass the checkpoint's motion as motion=")
+        self.motion = motion
         self.lens, self.subrays, self.n, self.work_mb = lens, subrays, samples // subrays, work_mb
         self._setup(dscene, cam, samples, w, h, False, shard, subrays, self.n, tol, eps, first, step, done, rule,
                     dict(sums=sums, sums2=sums2, counts=counts, mask=mask), depth, sky)
@@ -735,6 +784,11 @@ class AdaptiveLens(_AdaptiveFrame):
     def _render(self, r_begin, r_end, stream):
         index, _ = self.dscene.live_pixels(self._mask, self._counts, r_begin, stream=stream)
         # the list's length is the live count the last step (or the constructor) already brought to the host: no wait here
+        if self.motion is not None:
+            self.dscene.render_shutter_masked(self.motion, self.lens, self.samples, self.subrays, self.w, self.h, r_begin, r_end,
+                                              self._sums, index, self._live, sums2=self._sums2, counts=self._counts, shard=self.shard,
+                                              work_mb=self.work_mb, out_avg=self._avg, out_rgb=self._rgb, stream=stream)
+            return
         self.dscene.render_lens_masked(self.cam, self.lens, self.samples, self.subrays, self.w, self.h, r_begin, r_end, self._sums,
                                        index, self._live, sums2=self._sums2, counts=self._counts, shard=self.shard,
                                        work_mb=self.work_mb, out_avg=self._avg, out_rgb=self._rgb, stream=stream)

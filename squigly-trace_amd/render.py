@@ -100,7 +100,7 @@ def denoise_options(denoise):
 
 
 def render_adaptive(bih, cam, samples, dimensions, tol, eps=1.0, first=8, step=8, cast=False, device=0, rule=None, lights=None,
-                    depth=None, sky=None, denoise=None, lens=None, subrays=None):
+                    depth=None, sky=None, denoise=None, lens=None, subrays=None, motion=None):
     """The frame of render_rgb8 with adaptive sampling (DeviceScene, Adaptive): yields (done, live, spent, rgb8, counts) after
     every step -- the end of the range rendered, the pixels still live, the samples spent so far, the (w, h, 3) uint8 image and
     the (w, h) int32 per-pixel sample counts.  A pixel that stopped after n samples shows the mean of its first n samples, so
@@ -111,16 +111,18 @@ def render_adaptive(bih, cam, samples, dimensions, tol, eps=1.0, first=8, step=8
     lens (a Lens; None = no lens, the function as it was) and subrays (None = samples): the anti-aliased, depth-of-field frame of
     render_lens_rgb8, adaptively sampled in whole sub-rays (AdaptiveLens).  first and step stay in samples and must be multiples of
     n = samples / subrays (ValueError); the yielded done, spent and counts are samples too; cast=True is refused.  denoise= then
-    filters with the variance of the sub-ray sums brought to the pixel mean's scale, denoise_variance(...) * (1 / (n * n))."""
+    filters with the variance of the sub-ray sums brought to the pixel mean's scale, denoise_variance(...) * (1 / (n * n)).
+    motion (a Motion; needs a lens): the lens frame under a camera that moves during the exposure (AdaptiveLens(motion=)); cam is then
+    not read, and denoise= takes its guides from motion.pose(0.5) -- a convenience, not pinned to the bit."""
     from .device import Adaptive                       # torch: only the resident-scene path needs it
     w, h = dimensions
     if int(first) < 1 or int(step) < 1:
         raise ValueError(f"first and step must be positive, got {first}, {step}")
     if not float(tol) >= 0 or not float(eps) >= 0:
         raise ValueError(f"tol and eps must be numbers >= 0, got {tol}, {eps}")
-    if lens is not None or subrays is not None:
+    if lens is not None or subrays is not None or motion is not None:
         yield from _render_adaptive_lens(bih, cam, samples, dimensions, tol, eps, first, step, cast, device, rule, lights, depth, sky,
-                                         denoise, lens, subrays)
+                                         denoise, lens, subrays, motion)
         return
     scene = _resident(bih, device, lights, depth, sky)
     dn = None if denoise is None or denoise is False else denoise_options(denoise)      # refused before anything is uploaded
@@ -138,11 +140,14 @@ def render_adaptive(bih, cam, samples, dimensions, tol, eps=1.0, first=8, step=8
 
 
 def _render_adaptive_lens(bih, cam, samples, dimensions, tol, eps, first, step, cast, device, rule, lights, depth, sky, denoise, lens,
-                          subrays):
+                          subrays, motion=None):
     """render_adaptive with a lens: AdaptiveLens, its sub-ray units turned into samples for the caller."""
     from .lens import frame_args
     if lens is None:
-        raise ValueError("subrays needs a lens")
+        raise ValueError("subrays and motion need a lens")
+    if motion is not None:
+        from .shutter import motion_arg
+        motion_arg(motion)
     if cast:
         raise ValueError("a lens frame is path-traced: cast=True is refused")
     S, R, _, _ = frame_args(lens, samples, samples if subrays is None else subrays)
@@ -154,7 +159,7 @@ def _render_adaptive_lens(bih, cam, samples, dimensions, tol, eps, first, step, 
     from .device import AdaptiveLens
     w, h = dimensions
     with scene as ds:
-        a = AdaptiveLens(ds, cam, lens, S, R, w, h, tol, eps=eps, first=int(first) // n, step=int(step) // n, rule=rule)
+        a = AdaptiveLens(ds, cam, lens, S, R, w, h, tol, eps=eps, first=int(first) // n, step=int(step) // n, rule=rule, motion=motion)
         avg = None
         while not a.finished:
             avg, rgb = a.step()
@@ -163,7 +168,7 @@ def _render_adaptive_lens(bih, cam, samples, dimensions, tol, eps, first, step, 
             from .denoise import denoise_frame, denoise_variance
             # the variance of the mean of sub-ray sums is n * n times that of the pixel mean, in every branch of the variance formula
             var = denoise_variance(a.sums, a.sums2, a.counts) * (1 / (n * n))            # one float32 multiply
-            out, _ = denoise_frame(ds, cam, w, h, avg, var=var, **dn)
+            out, _ = denoise_frame(ds, cam if motion is None else motion.pose(0.5), w, h, avg, var=var, **dn)
             img = N.debug_eval("tonemap", out.cpu().numpy().reshape(-1, 3), device=ds.device).reshape(tuple(out.shape))
             yield a.done * n, a.live, a.samples_spent, img, a.sample_counts.cpu().numpy()
 
@@ -184,20 +189,28 @@ def render_views_rgb8(bih, cams, samples, dimensions, cast=False, device=0, ligh
         return rgb.cpu().numpy()
 
 
-def render_lens_rgb8(bih, cam, samples, dimensions, lens=None, subrays=None, device=0, depth=None, sky=None, work_mb=None) -> np.ndarray:
+def render_lens_rgb8(bih, cam, samples, dimensions, lens=None, subrays=None, device=0, depth=None, sky=None, work_mb=None,
+                     motion=None) -> np.ndarray:
     """The image of render_rgb8 with anti-aliasing and depth of field (DeviceScene.render_lens): shape (w, h, 3) uint8.  lens: a
     Lens (None = Lens(): a box filter over the pixel, no aperture).  subrays: primary rays per pixel, a divisor of samples (None =
     samples, a ray per sample).  With Lens(jitter=0) and subrays=1 the image is bit for bit that of render_rgb8.  depth, sky: as in
-    render_progressive.  Refused before anything is uploaded: what lens.frame_args refuses."""
+    render_progressive.  motion (a Motion): the frame under a camera that moves during the exposure (DeviceScene.render_shutter); cam
+    is then not read.  Refused before anything is uploaded: what lens.frame_args and shutter.motion_arg refuse."""
     from .lens import Lens, frame_args
     lens = Lens() if lens is None else lens
     subrays = samples if subrays is None else subrays
     frame_args(lens, samples, subrays)
+    if motion is not None:
+        from .shutter import motion_arg
+        motion_arg(motion)
     scene = _resident(bih, device, None, depth, sky)
     import torch
     w, h = dimensions
     with scene as ds:
-        out = ds.render_lens(cam, lens, samples, subrays, w, h, want_avg=False, work_mb=work_mb)
+        if motion is None:
+            out = ds.render_lens(cam, lens, samples, subrays, w, h, want_avg=False, work_mb=work_mb)
+        else:
+            out = ds.render_shutter(motion, lens, samples, subrays, w, h, want_avg=False, work_mb=work_mb)
         torch.cuda.synchronize(ds.device)
         return out.rgb.cpu().numpy()
 
