@@ -99,6 +99,9 @@ extern "C" int sq_scene_upload(const sq_scene* sc, int32_t device, sq_device_sce
     SQ_HIP(hipSetDevice(device));
     sq_device_scene* s = new sq_device_scene;
     s->device = device; s->height = P.height; s->small_index = P.small_index; s->shortcut_depth = P.shortcut_depth; s->level1 = P.level1;
+    // SQ_AUTO_OVERLAP=0 / 1: the scene's default of option "auto_overlap", read once per scene (a profiling run of a program that sets
+    // no options pins the serial schedule with it: per-kernel times and counters are those of launches that run alone)
+    if (const char* env = std::getenv("SQ_AUTO_OVERLAP")) s->opt.auto_overlap = std::atoi(env) != 0;
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) s->n_cu = prop.multiProcessorCount;
     // One arena for every array of the scene: one hipMalloc, one host-packed hipMemcpy and (sq_scene_free) one hipFree
@@ -665,10 +668,11 @@ int launch_frame(sq_device_scene* s, const FrameOf<SRC>& F, hipStream_t stream, 
         hipLaunchKernelGGL(sq_mirror1_store, dim3(aux_blocks), dim3(kBlock), 0, stream, W, base);
         return launched();
     };
-    if (!overlap) {
-        // Plain schedule: everything on the caller's stream, batch after batch.  The mirror rays ride in front of batch 0, level 0
-        // (slots behind the sample slots, dequeued first) instead of having a launch, and a ramp-down, of their own.
-        const long long front = (long long)W.slot_capacity;
+    // Where the mirror rays ride (Schedule::mirror_rides): in front of batch 0, level 0 (slots behind the sample slots of both tracks,
+    // dequeued first) instead of having a launch, and a ramp-down, of their own.
+    const long long front = (long long)W.slot_capacity;
+    if (Sch.kind == kSchedSerial) {
+        // Plain schedule: everything on the caller's stream, batch after batch.
         for (int i = 0; i < n_real; ++i) {
             if (gen(i, stream)) return 1;
             if (i == 0 && mirror_gen(front)) return 1;
@@ -678,9 +682,11 @@ int launch_frame(sq_device_scene* s, const FrameOf<SRC>& F, hipStream_t stream, 
         }
         return 0;
     }
-    // The overlapped schedules give the mirror rays a launch of their own, before the tracks split.
-    SQ_HIP(hipMemsetAsync(W.head[0], 0, 32 * sizeof(int32_t), stream));
-    if (mirror_gen(0) || launch_trace_kernel(s, S, C, trace_fn, W, pixels, 1, 0, stream, false) || mirror_store(0)) return 1;
+    // The overlapped schedules a caller asks for give the mirror rays a launch of their own, before the tracks split.
+    if (!Sch.mirror_rides) {
+        SQ_HIP(hipMemsetAsync(W.head[0], 0, 32 * sizeof(int32_t), stream));
+        if (mirror_gen(0) || launch_trace_kernel(s, S, C, trace_fn, W, pixels, 1, 0, stream, false) || mirror_store(0)) return 1;
+    }
     if (!s->aux) {
         // The second stream carries the per-sample kernels (overlap 1) or the odd batches (overlap 2).  Lowest priority: when a
         // trace launch and a per-sample kernel become ready together, the trace workgroups (one per CU, all of its LDS) must be
@@ -698,21 +704,32 @@ int launch_frame(sq_device_scene* s, const FrameOf<SRC>& F, hipStream_t stream, 
         *e = s->events[next_event++];
         return 0;
     };
-    if (s->opt.overlap == 2) {
+    if (Sch.kind == kSchedPipelines) {
         // Two pipelines: even batches run start to end on the caller's stream, odd batches on the second stream.  A trace
         // launch needs a whole CU's LDS per workgroup, so the two tracks' launches do not share CUs: the later one's
         // workgroups move in as the earlier one's finish, which fills the ramp-down of every launch (a ray takes
         // 150-300 us from fetch to hit, and a launch ends when its slowest rays do) and overlaps the per-sample kernels
-        // of one track with the trace launches of the other.  Only the accumulation is ordered across tracks (src/Lib.hs:88).
+        // of one track with the trace launches of the other.  Only the accumulation is ordered across tracks (src/Lib.hs:88) -- and,
+        // where the mirror rays ride with batch 0, the second track's first shading behind their store: sq_shade1 reads the per-pixel
+        // mirror hit, sq_gen_bounce1 and the trace launches do not.  A track's later batches never dequeue the front slots again.
         std::vector<hipEvent_t> eAcc((size_t)n_real);
         for (int i = 0; i < n_real; ++i) if (new_event(&eAcc[(size_t)i])) return 1;
-        hipEvent_t e_setup2, e_done2;
-        if (new_event(&e_setup2) || new_event(&e_done2)) return 1;
+        hipEvent_t e_setup2, e_done2, e_mirror = nullptr;
+        if (new_event(&e_setup2) || new_event(&e_done2) || (Sch.mirror_rides && new_event(&e_mirror))) return 1;
         SQ_HIP(hipEventRecord(e_setup2, stream));
         SQ_HIP(hipStreamWaitEvent(X, e_setup2, 0));
         for (int i = 0; i < n_real; ++i) {
             const hipStream_t on = (i & 1) ? X : stream;
-            if (gen(i, on) || trace(i, 0, on, false) || shade(i, on) || trace(i, 1, on, false)) return 1;
+            const bool ride = Sch.mirror_rides && i == 0;                // batch 0 is on the caller's stream, as the mirror kernels are
+            if (gen(i, on)) return 1;
+            if (ride && mirror_gen(front)) return 1;
+            if (trace(i, 0, on, ride)) return 1;
+            if (ride) {
+                if (mirror_store(front)) return 1;
+                SQ_HIP(hipEventRecord(e_mirror, stream));
+            }
+            if (Sch.mirror_rides && i == 1) SQ_HIP(hipStreamWaitEvent(X, e_mirror, 0));
+            if (shade(i, on) || trace(i, 1, on, false)) return 1;
             if (i > 0) SQ_HIP(hipStreamWaitEvent(on, eAcc[(size_t)i - 1], 0));
             if (accumulate(i, on, i == n_real - 1)) return 1;
             SQ_HIP(hipEventRecord(eAcc[(size_t)i], on));

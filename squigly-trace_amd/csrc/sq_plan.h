@@ -62,12 +62,15 @@ inline long long primary_padded_lanes(int local_rows, int tile_rows, int tiles_x
 
 // ---- options (sq_set_option; the table of names, ranges and messages is sq_plan_call.h's kOptionTable) ----
 constexpr int64_t kRngTableDefaultMb = 24576;   // option "rng_table_mb": 24 GiB = 2^31 seeds (squigly_hip.h)
+// Option "auto_overlap_slots": the sample slots (pixels x samples of the call) from which a call of the three-level pipeline is planned as
+// two pipelines without being asked to (plan_schedule).  Measured, DESIGN.md 4.2: profiles/r14b_auto_overlap_threshold.txt.
+constexpr int64_t kAutoOverlapSlots = 1ll << 26;
 struct Options {
     int64_t timing = 0, variant = 2, slots = 512ll << 20, straggler_lanes = 8, resident = 1, profile = 0, lds_node_kb = 32,
             trace_blocks_per_cu = 0, overlap = 0, rng_table_mb = kRngTableDefaultMb, cast_wavefront = 0, deep = 0, pool = 1, guided = 1,
             primary_resident = 1, cull = 1, level1_cull = 1, primary_tiles = 1, primary_pooled = 0, coresidency = 0, aux_polite = 0,
             trace_prio = 0, aux_low_priority = 1, descend_extra = 2, descend_lanes = 16, pixel_major = -1, refill_min = 12, flush_min = 40,
-            aux_blocks_per_cu = 0;
+            aux_blocks_per_cu = 0, auto_overlap = 1, auto_overlap_slots = kAutoOverlapSlots, batches_per_track = 1, mirror_ride = 0;
 };
 // Sets option `key` of O: 0, or sq_set_error with the option's own message (a value outside its range) or "unknown option".
 int set_option(Options& O, const char* key, int64_t value);
@@ -125,7 +128,12 @@ int refuse_frame_size(int64_t n_views, int64_t rows, int64_t h, bool wavefront);
 long long radiance_chunk_rays(long long n, long long slots, bool wavefront);
 
 // ---- what depends on the slots the workspace actually got (the allocation may have halved them) ----
+// The schedule's kind: everything on the caller's stream; the per-sample kernels on the second stream beside the trace launches; two
+// pipelines, even batches on the caller's stream and odd ones on the second.
+constexpr int kSchedSerial = 0, kSchedAux = 1, kSchedPipelines = 2;
 struct Schedule {
+    int kind = kSchedSerial;                      // what launch_frame enqueues; overlap = kind != kSchedSerial
+    bool mirror_rides = true;                     // the per-pixel mirror rays: at the head of batch 0's first trace launch, or (false) in a launch of their own
     bool overlap = false; int tracks = 1; int64_t track_slots = 0;
     int batch = 0, n_batches = 0, n_real = 0;     // samples per batch; batches the split counts; batches that hold a sample
     long long query_chunk = 0;                    // an intersection query: rays per chunk

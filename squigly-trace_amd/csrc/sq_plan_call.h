@@ -52,6 +52,10 @@ const OptionRow kOptionTable[] = {
     { "refill_min", &Options::refill_min, kRange, 1, 64, "refill_min must be in 1..64" },
     { "flush_min", &Options::flush_min, kRange, 0, 64, "flush_min must be in 0..64" },
     { "aux_blocks_per_cu", &Options::aux_blocks_per_cu, kRange, 0, 16, "aux_blocks_per_cu must be in 0..16" },
+    { "auto_overlap", &Options::auto_overlap, kBool, 0, 1, nullptr },           // environment default: SQ_AUTO_OVERLAP (sq_scene_upload)
+    { "auto_overlap_slots", &Options::auto_overlap_slots, kRange, 1, 1ll << 62, "auto_overlap_slots must be in 1..2^62" },
+    { "batches_per_track", &Options::batches_per_track, kRange, 1, 64, "batches_per_track must be in 1..64" },
+    { "mirror_ride", &Options::mirror_ride, kBool, 0, 1, nullptr },
 };
 }  // namespace
 
@@ -245,22 +249,40 @@ Schedule plan_schedule(const CallPlan& C, int64_t have_slots) {
     if (C.path == kPathQueryWave) { D.query_chunk = std::min<long long>(o.slots, have_slots); return D; }
     if (C.path != kPathWaveCast && C.path != kPathWaveDeep && C.path != kPathPipeline) return D;
     const long long pixels = C.pixels; const int n_call = C.n_call;
-    // Overlapped schedule: the sample batches alternate between two halves of the workspace ("tracks"); every
-    // trace launch stays on the caller's stream, in the order T1(a) T1(b) T2(a) T2(b), while the per-sample
-    // kernels (RNG + bounce, shading, accumulation) run on a second stream beside them, ordered by events.
-    // Opt-in (sq_set_option "overlap"): measured +3 % on the headline frame (105.5 -> 102.3 ms) -- the kernels do
-    // run side by side, but the chip is VALU-bound as a whole, so each slows the other down by what it gains;
-    // and trace-launch durations then include that interference, which blurs the per-kernel roofline figure.
-    const bool overlap = o.overlap && C.path == kPathPipeline && n_call >= 2 && have_slots >= 2 * pixels;
+    // Overlapped schedules: the sample batches alternate between two halves of the workspace ("tracks").  Asked for by option
+    // "overlap": 1 keeps every trace launch on the caller's stream, in the order T1(a) T1(b) T2(a) T2(b), with the per-sample kernels
+    // (RNG + bounce, shading, accumulation) on a second stream beside them, ordered by events; 2 runs each track as a pipeline of
+    // its own, even batches on the caller's stream and odd ones on the second.  Both give the mirror rays a launch of their own.
+    // Chosen without being asked (option "auto_overlap", on by default): two pipelines, once the call is large enough to gain --
+    // pixels x samples reaches option "auto_overlap_slots".  Its mirror rays have a launch of their own too; option "mirror_ride" puts
+    // them at the head of batch 0's first trace launch instead, as in the serial schedule (0.25-0.4 ms faster on the headline frame in
+    // every paired run, which is short of the landing rule: DESIGN.md 6).  The two tracks' launches fill each other's ramp-downs and hide the
+    // memory-bound sq_shade1 and sq_accumulate of one track under the other's trace launches; a small frame
+    // has no tail worth filling and pays for the events and the second stream instead.  Co-running launches slow each other
+    // down, so what "timing", the roofline and a kernel trace say per kernel holds for the serial schedule only: the profiling
+    // tools pin it (auto_overlap = 0, or SQ_AUTO_OVERLAP=0 in the environment).
+    const bool can_overlap = C.path == kPathPipeline && n_call >= 2 && have_slots >= 2 * pixels;
+    const bool automatic = can_overlap && !o.overlap && o.auto_overlap && (int64_t)pixels * n_call >= o.auto_overlap_slots;
+    const int kind = !can_overlap ? kSchedSerial : automatic ? kSchedPipelines : (int)o.overlap;
+    const bool overlap = kind != kSchedSerial;
     const int tracks = overlap ? 2 : 1;
     const int64_t track_slots = have_slots / tracks;
     // samples per batch: as many as a track holds, split evenly (few large launches: a small trace launch
     // wastes its ramp-up and drain, and the second-bounce launches only carry a few percent of the slots)
     const int max_batch = (int)std::max<int64_t>(1, std::min<int64_t>(n_call, track_slots / pixels));
-    const int n_batches = std::max(tracks, (n_call + max_batch - 1) / max_batch);
-    const int batch = (n_call + n_batches - 1) / n_batches;
+    const int min_batches = automatic ? (int)std::min<int64_t>(n_call, tracks * o.batches_per_track) : tracks;
+    int n_batches = std::max(min_batches, (n_call + max_batch - 1) / max_batch);
+    int batch = (n_call + n_batches - 1) / n_batches;
+    // The automatic schedule keeps a batch to the generator table's runs of four samples (a batch that starts inside a run reads its
+    // entries as twelve dword loads, not three dwordx4): rounded up where the track holds it, else down; only the call's last batch is
+    // ragged.  A track that holds fewer than four samples of every pixel cannot.
+    if (automatic && n_call >= 8 && max_batch >= 4) {
+        batch = std::min((batch + 3) / 4 * 4, max_batch / 4 * 4);
+        n_batches = std::max(tracks, (n_call + batch - 1) / batch);
+    }
     int n_real = 0;
     while (n_real < n_batches && std::max(0, std::min(batch, n_call - n_real * batch)) > 0) ++n_real;
+    D.kind = kind; D.mirror_rides = !overlap || (automatic && o.mirror_ride);
     D.overlap = overlap; D.tracks = tracks; D.track_slots = track_slots; D.batch = batch; D.n_batches = n_batches; D.n_real = n_real;
     return D;
 }
@@ -387,7 +409,7 @@ extern "C" int sq_plan_call(const char* const* in_names, const int64_t* in_value
         { "acc_grouped", C.acc_grouped }, { "level1_cull", C.level1_cull }, { "deep_slot_bytes", (int64_t)C.deep_slot_bytes }, { "need_lights", C.need_lights },
         { "need_sum2", C.need_sum2 }, { "need_deep", C.need_deep }, { "rng_table", C.rng_table }, { "rng_grow", C.rng_grow },
         { "chunk_rays", total_rays > 0 ? radiance_chunk_rays(total_rays, in.opt.slots, in.opt.variant != 1 && (!F.cast || in.opt.cast_wavefront)) : 0 },
-        { "have_slots", have }, { "overlap", D.overlap }, { "tracks", D.tracks }, { "track_slots", D.track_slots }, { "batch", D.batch },
+        { "have_slots", have }, { "schedule", D.kind }, { "mirror_rides", D.mirror_rides }, { "overlap", D.overlap }, { "tracks", D.tracks }, { "track_slots", D.track_slots }, { "batch", D.batch },
         { "n_batches", D.n_batches }, { "n_real", D.n_real }, { "query_chunk", D.query_chunk }, { "tail_kc", tail_kc },
         { "pp_grid_x", g.x }, { "pp_grid_y", g.y }, { "tail_pp_grid_x", gt.x }, { "tail_pp_grid_y", gt.y },
         { "chunk_0", t0.chunk }, { "chunk_1", t1.chunk }, { "guide_shift_0", t0.guide_shift }, { "guide_shift_1", t1.guide_shift },

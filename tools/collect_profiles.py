@@ -14,6 +14,7 @@ what = set(sys.argv[2:]) or {"headline", "c3", "c5"}
 OUT = os.path.join(ROOT, "gpurun_out", f"profiles_{tag}")
 os.makedirs(OUT, exist_ok=True)
 env = dict(os.environ, TMPDIR="/tmp")
+env.setdefault("SQ_AUTO_OVERLAP", "0")          # per-kernel times and counters are those of the serial schedule: every launch runs alone
 sys.path.insert(0, ROOT)
 BUILD_ID = importlib.import_module("squigly-trace_amd").build_id()     # the library these counters are collected on (no HIP call)
 

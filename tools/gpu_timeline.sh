@@ -3,6 +3,7 @@
 #   usage: bash tools/gpu_timeline.sh <tag> [gpu_frames.py args...]
 TAG=$1; shift
 export TMPDIR=/tmp
+export SQ_AUTO_OVERLAP=${SQ_AUTO_OVERLAP:-0}   # per-kernel figures are those of the serial schedule: every launch runs alone
 cd "$(dirname "$0")/.."
 rm -rf gpurun_out/tl_$TAG
 timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d gpurun_out/tl_$TAG -- python tools/gpu_frames.py "$@" > gpurun_out/tl_$TAG.log 2>&1

@@ -3,6 +3,7 @@
 #   usage: bash tools/kernel_times.sh <tag> <lib.so|product> [gpu_frames.py args...]
 TAG=$1; LIB=$2; shift 2
 export TMPDIR=/tmp
+export SQ_AUTO_OVERLAP=${SQ_AUTO_OVERLAP:-0}   # per-kernel figures are those of the serial schedule: every launch runs alone
 cd "$(dirname "$0")/.."
 [ "$LIB" != product ] && export SQ_LIB_PATH=$PWD/squigly-trace_amd/$LIB
 rm -rf gpurun_out/kt_$TAG

@@ -8,6 +8,7 @@ TAG=$1; shift
 OUT=$GRAFT_REPO_ROOT/gpurun_out/pmcm_$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
+export SQ_AUTO_OVERLAP=${SQ_AUTO_OVERLAP:-0}   # per-kernel figures are those of the serial schedule: every launch runs alone
 cd $GRAFT_REPO_ROOT
 i=0
 for CTRS in "GRBM_GUI_ACTIVE GRBM_TA_BUSY TA_TA_BUSY_sum TA_FLAT_READ_WAVEFRONTS_sum" \
