@@ -1,6 +1,7 @@
 """Build libsquigly_hip.so (HIP kernels for gfx950 + host side), libsquigly_denoise.so (the denoiser), libsquigly_lens.so (jittered,
-thin-lens primary rays), libsquigly_mlens.so (those rays for the live pixels of a mask) and libsquigly_shutter.so (those rays, dense
-or listed, under a camera that moves during the exposure) in-tree with hipcc.
+thin-lens primary rays), libsquigly_mlens.so (those rays for the live pixels of a mask), libsquigly_shutter.so (those rays, dense
+or listed, under a camera that moves during the exposure) and libsquigly_temporal.so (temporal accumulation over a sequence of
+frames) in-tree with hipcc.
 
     python squigly-trace_amd/build.py [--force]
 
@@ -60,14 +61,23 @@ SHUTTER_OUT = os.path.join(HERE, "libsquigly_shutter.so")
 SHUTTER_SOURCES = ["sq_shutter.hip"]
 SHUTTER_HEADERS = LENS_HEADERS + ["sq_shutter_pose.h", "../../include/squigly_shutter.h"]
 
+# The sixth library: temporal accumulation (include/squigly_temporal.h).  Like the denoiser it maps device images to device images
+# and is not linked against the main library, whose header it reads for sq_camera alone; the arithmetic of a pixel
+# (sq_temporal_pixel.h) is its own.
+TEMPORAL_OUT = os.path.join(HERE, "libsquigly_temporal.so")
+TEMPORAL_SOURCES = ["sq_temporal.hip"]
+TEMPORAL_HEADERS = ["sq_math.h", "sq_error.h", "sq_call_checks.h", "sq_temporal_pixel.h", "../../include/squigly_temporal.h",
+                    "../../include/squigly_hip.h"]
+
 # One description per library.  macro: the -D that carries the id into the library (what sq_build_id(), sq_denoise_build_id(),
-# sq_lens_build_id(), sq_mlens_build_id() and sq_shutter_build_id() return); salt: what the id's hash starts from, so that no two libraries share an id; link: behind the output.
+# sq_lens_build_id(), sq_mlens_build_id(), sq_shutter_build_id() and sq_temporal_build_id() return); salt: what the id's hash starts from, so that no two libraries share an id; link: behind the output.
 MAIN = dict(out=OUT, sources=SOURCES, headers=HEADERS, macro="SQ_BUILD_ID", salt=b"", link=[])
 DENOISE = dict(out=DENOISE_OUT, sources=DENOISE_SOURCES, headers=DENOISE_HEADERS, macro="SQ_DENOISE_BUILD_ID", salt=b"denoise\0", link=[])
 LENS = dict(out=LENS_OUT, sources=LENS_SOURCES, headers=LENS_HEADERS, macro="SQ_LENS_BUILD_ID", salt=b"lens\0",
             link=["-L" + HERE, "-lsquigly_hip", "-Wl,-rpath,$ORIGIN"])
 MLENS = dict(out=MLENS_OUT, sources=MLENS_SOURCES, headers=MLENS_HEADERS, macro="SQ_MLENS_BUILD_ID", salt=b"mlens\0", link=LENS["link"])
 SHUTTER = dict(out=SHUTTER_OUT, sources=SHUTTER_SOURCES, headers=SHUTTER_HEADERS, macro="SQ_SHUTTER_BUILD_ID", salt=b"shutter\0", link=LENS["link"])
+TEMPORAL = dict(out=TEMPORAL_OUT, sources=TEMPORAL_SOURCES, headers=TEMPORAL_HEADERS, macro="SQ_TEMPORAL_BUILD_ID", salt=b"temporal\0", link=[])
 
 
 def lib_source_id(lib, extra=()):
@@ -116,6 +126,8 @@ def mlens_source_id(extra=()): return lib_source_id(MLENS, extra)
 def mlens_stale(): return lib_stale(MLENS)
 def shutter_source_id(extra=()): return lib_source_id(SHUTTER, extra)
 def shutter_stale(): return lib_stale(SHUTTER)
+def temporal_source_id(): return lib_source_id(TEMPORAL)
+def temporal_stale(): return lib_stale(TEMPORAL)
 
 
 def build_client(lib, force=False, extra=(), out=None):
@@ -128,6 +140,11 @@ def build_client(lib, force=False, extra=(), out=None):
 def build_lens(force=False, extra=(), out=None): return build_client(LENS, force, extra, out)
 def build_mlens(force=False, extra=(), out=None): return build_client(MLENS, force, extra, out)
 def build_shutter(force=False, extra=(), out=None): return build_client(SHUTTER, force, extra, out)
+
+
+def build_temporal(force=False):
+    """The temporal library: compiled unless the in-tree product carries the current id.  (No client of the main library.)"""
+    return build_client(TEMPORAL, force)
 
 
 def build(force=False, extra=(), out=None):
@@ -149,6 +166,7 @@ def build(force=False, extra=(), out=None):
     build_lens(force)
     build_mlens(force)
     build_shutter(force)
+    build_temporal(force)
     return OUT
 
 

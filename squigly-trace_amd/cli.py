@@ -10,7 +10,7 @@ import os
 import sys
 import time
 
-from . import BIH, Lens, Mesh, Motion, Settings, camera_from_text, lib, load_camera, render, render_adaptive, render_lens_rgb8, render_progressive, render_views_rgb8, write_png
+from . import BIH, Lens, Mesh, Motion, Settings, camera_from_text, lib, load_camera, render, render_adaptive, render_lens_rgb8, render_progressive, render_sequence, render_views_rgb8, write_png
 from ._native import SquiglyError
 
 
@@ -211,6 +211,13 @@ def build_parser():
     p.add_argument("--shutter-jitter", type=unit_float, default=None, metavar="T",
                    help="With --shutter-camera: how much of its own part of the exposure a primary ray's instant is drawn from, "
                         "0..1 (default 1)")
+    # not flags of the reference: the frames of a camera move, accumulated from frame to frame (include/squigly_temporal.h)
+    p.add_argument("--sequence", type=views_file, default=None, metavar="FILE",
+                   help="Render every camera of FILE (pairs of camera lines, as for --views) as one frame of a sequence, --samples "
+                        "samples each, into <savepath stem>_<i:04d><ext>; -c is not read")
+    p.add_argument("--temporal", type=unit_float, nargs="?", const=True, default=None, metavar="ALPHA_MIN",
+                   help="With --sequence: accumulate every frame over the frames before it, reprojected through its first hits; "
+                        "ALPHA_MIN is the least weight of the new frame (default 0.1)")
     return p
 
 
@@ -241,7 +248,18 @@ def parse_args(argv=None):
         p.error("--adaptive cannot be combined with --views or --preview-every")
     if a.counts is not None and a.adaptive is None:
         p.error("--counts needs --adaptive")
-    if a.denoise is not None and a.adaptive is None:
+    if a.temporal is not None and a.sequence is None:
+        p.error("--temporal needs --sequence")
+    if a.temporal is not None and (a.adaptive is not None or a.aa is not None):
+        p.error("--temporal cannot be combined with --adaptive or --aa")
+    if a.sequence is not None:
+        for flag, given in (("--cast", a.cast), ("--views", a.views is not None), ("--adaptive", a.adaptive is not None),
+                            ("--preview-every", a.preview_every is not None), ("--light", a.light is not None)):
+            if given:
+                p.error(f"--sequence cannot be combined with {flag}")
+        if a.samples < 1:
+            p.error("--sequence needs --samples >= 1")
+    if a.denoise is not None and a.adaptive is None and a.sequence is None:
         p.error("--denoise needs --adaptive (the filter takes its variance from the adaptive frame's second moments)")
     if a.light is not None and not a.cast:
         p.error("--light needs --cast")
@@ -260,7 +278,7 @@ def parse_args(argv=None):
         if a.focus is not None and a.aperture is None:
             p.error("--focus needs --aperture")
         for flag, given in (("--cast", a.cast), ("--views", a.views is not None), ("--adaptive", a.adaptive is not None),
-                            ("--preview-every", a.preview_every is not None)):
+                            ("--preview-every", a.preview_every is not None), ("--sequence", a.sequence is not None)):
             if given:
                 p.error(f"--aa, --subrays, --aperture, --focus and --shutter-camera cannot be combined with {flag}")
         if a.samples < 1 or a.samples % (a.subrays or a.samples):
@@ -272,7 +290,7 @@ def main(argv=None):
     a = parse_args(argv)
     settings = Settings(samples=a.samples, dimensions=a.dimensions, savePath=a.savepath, objPath=a.objpath,
                         cameraPath=a.camerapath, debug=a.debug, debugPath=a.debugpath, cast=a.cast)
-    cam = load_camera(settings.cameraPath) if a.views is None else None   # app/Main.hs:38
+    cam = load_camera(settings.cameraPath) if a.views is None and a.sequence is None else None   # app/Main.hs:38
     mesh = Mesh.from_obj(settings.objPath, "./data")            # loadTris, app/Main.hs:58-61 + src/Obj.hs:52
     if settings.debug:                                          # src/Obj.hs:55-57: print (head objs); print mats
         first, mats = mesh.debug_show()
@@ -304,6 +322,13 @@ def main(argv=None):
         for path, img in zip(view_paths(settings.savePath, len(imgs)), imgs):
             write_png(path, img)
         print(f"Wrote {len(imgs)} views to {view_paths(settings.savePath, 1)[0]} ...")
+    elif a.sequence is not None:
+        paths = view_paths(settings.savePath, len(a.sequence))
+        frames = render_sequence(bih, a.sequence, settings.samples, settings.dimensions, temporal=a.temporal is not None, denoise=a.denoise,
+                                 depth=a.depth, sky=a.sky, **({} if a.temporal is None or a.temporal is True else {"alpha_min": a.temporal}))
+        for path, img in zip(paths, frames):
+            write_png(path, img)
+        print(f"Wrote {len(paths)} frames to {paths[0]} ...")
     elif a.adaptive is not None:
         import numpy as np
         for done, live, spent, img, counts in render_adaptive(bih, cam, settings.samples, settings.dimensions, a.adaptive, eps=a.adaptive_eps,

@@ -1,0 +1,177 @@
+// sq_temporal.hip — libsquigly_temporal.so (include/squigly_temporal.h): temporal accumulation over device images.  It knows nothing
+// of scenes: device images and a caller-given history block in, device images and the next block out, no state.
+//
+// One kernel does a frame.  A thread is a pixel, a wave 64 consecutive columns of a row (a block is 4 such row segments), so that the
+// plain reads and writes of a wave are one span of memory each and a tap's loads of one plane of the previous block are close to
+// contiguous: under a slow camera the 64 lanes of a wave reproject into one or two row segments of the previous frame.  The block of
+// a frame is three planes of 16-byte records (CV colour + variance, NL normal + length, PT point + triangle), so a tap is three
+// dwordx4 loads, and the twelve loads of a pixel's four taps are issued together, before any tap is judged (sq_temporal_pixel.h).
+// No LDS: the four taps of neighbouring lanes overlap, and L1 / L2 serve the re-reads.
+//
+// The arithmetic of a pixel is csrc/sq_temporal_pixel.h, the text the host's sq_temporal_project compiles too.  -ffp-contract=off
+// and the correctly rounded divide keep it equal to the numpy restatement.
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
+
+#include "sq_call_checks.h"
+#include "sq_temporal_pixel.h"
+#include "../../include/squigly_temporal.h"
+
+#ifndef SQ_TEMPORAL_BUILD_ID
+#define SQ_TEMPORAL_BUILD_ID "unknown"
+#endif
+
+namespace {
+
+using temporalpix::Rec;
+
+constexpr int kBlock = 256;
+constexpr long long kMaxPixels = 0x7fffffffLL;
+constexpr int kMaxGrid = 2048;             // blocks of a launch: 8 per CU; the kernels stride over their tiles
+constexpr int kTileW = 64, kTileH = 4;     // a block is 4 rows of 64 pixels, a wave one row segment
+
+struct Cam { float pos[3]; float rot[9]; };
+
+// d_color / d_out and d_var / d_out_var may be the same memory: a thread reads its own pixel of the inputs before it writes its
+// own pixel of the outputs, and none of the four is __restrict__.
+__global__ __launch_bounds__(kBlock) void sq_tp_accumulate(const int rows, const int cols, const float* color, const float* var,
+                                                           const int32_t* __restrict__ tri, const float* __restrict__ normal,
+                                                           const float* __restrict__ point, const float* __restrict__ alpha,
+                                                           const Cam cam, const Rec* __restrict__ prev, const temporalpix::Params P,
+                                                           Rec* __restrict__ next, float* out, float* out_var,
+                                                           int32_t* __restrict__ out_len, const long long tiles, const long long tiles_x) {
+    const long long n = (long long)rows * cols;
+    const Rec* p_cv = prev;
+    const Rec* p_nl = prev ? prev + n : nullptr;
+    const Rec* p_pt = prev ? prev + 2 * n : nullptr;
+    for (long long t = blockIdx.x; t < tiles; t += gridDim.x) {
+        const long long ty = t / tiles_x, tx = t - ty * tiles_x;
+        const long long x = tx * kTileW + (threadIdx.x & (kTileW - 1)), y = ty * kTileH + (threadIdx.x / kTileW);
+        if (x >= cols || y >= rows) continue;
+        const long long p = y * cols + x;
+        const float cr = color[3 * p], cg = color[3 * p + 1], cb = color[3 * p + 2], v = var[p];
+        const int32_t tr = tri[p];
+        const float nx = normal[3 * p], ny = normal[3 * p + 1], nz = normal[3 * p + 2];
+        const float px = point[3 * p], py = point[3 * p + 1], pz = point[3 * p + 2];
+        const float al = alpha ? alpha[p] : -1.0f;
+        const temporalpix::Pixel r = temporalpix::accumulate(p_cv, p_nl, p_pt, rows, cols, cam.pos, cam.rot, P, cr, cg, cb, v, tr,
+                                                             nx, ny, nz, px, py, pz, alpha != nullptr, al);
+        next[p] = Rec{ r.r, r.g, r.b, r.v };
+        next[n + p] = Rec{ nx, ny, nz, temporalpix::int_bits(r.len) };
+        next[2 * n + p] = Rec{ px, py, pz, temporalpix::int_bits(tr) };
+        out[3 * p] = r.r; out[3 * p + 1] = r.g; out[3 * p + 2] = r.b;
+        out_var[p] = r.v;
+        if (out_len) out_len[p] = r.len;
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void sq_tp_unpack(const long long n, const Rec* __restrict__ hist, float* __restrict__ color,
+                                                       float* __restrict__ var, int32_t* __restrict__ len, int32_t* __restrict__ tri,
+                                                       float* __restrict__ normal, float* __restrict__ point) {
+    for (long long p = (long long)blockIdx.x * kBlock + threadIdx.x; p < n; p += (long long)gridDim.x * kBlock) {
+        if (color || var) {
+            const Rec cv = hist[p];
+            if (color) { color[3 * p] = cv.x; color[3 * p + 1] = cv.y; color[3 * p + 2] = cv.z; }
+            if (var) var[p] = cv.w;
+        }
+        if (normal || len) {
+            const Rec nl = hist[n + p];
+            if (normal) { normal[3 * p] = nl.x; normal[3 * p + 1] = nl.y; normal[3 * p + 2] = nl.z; }
+            if (len) len[p] = temporalpix::bits_int(nl.w);
+        }
+        if (point || tri) {
+            const Rec pt = hist[2 * n + p];
+            if (point) { point[3 * p] = pt.x; point[3 * p + 1] = pt.y; point[3 * p + 2] = pt.z; }
+            if (tri) tri[p] = temporalpix::bits_int(pt.w);
+        }
+    }
+}
+
+int check_size(int32_t rows, int32_t cols) {
+    if (rows < 1 || cols < 1) return sq_set_error("rows and cols must be at least 1 (got %d x %d)", rows, cols);
+    if ((long long)rows * cols > kMaxPixels) return sq_set_error("%d x %d pixels exceed 2^31 - 1 pixels in one call", rows, cols);
+    return 0;
+}
+
+// Everything that can be refused, in the order of the header's list.  Touches neither the device nor a buffer.
+int check_accumulate(int32_t rows, int32_t cols, const float* d_color, const float* d_var, const int32_t* d_tri, const float* d_normal,
+                     const float* d_point, const float* d_alpha, const sq_camera* prev_cam, const void* d_prev,
+                     const sq_temporal_params* P, void* d_next, float* d_out, float* d_out_var, int32_t* d_out_len) {
+    if (!d_color || !d_var || !d_tri || !d_normal || !d_point || !P || !d_next || !d_out || !d_out_var)
+        return sq_set_error("null argument: d_color, d_var, d_tri, d_normal, d_point, params, d_next, d_out and d_out_var are required");
+    if (d_prev && !prev_cam) return sq_set_error("null argument: prev_cam is required with d_prev (the camera the previous block was rendered under)");
+    if (check_size(rows, cols)) return 1;
+    if (!(P->alpha_min >= 0.0f && P->alpha_min <= 1.0f)) return sq_set_error("alpha_min must be a number in 0..1 (got %g)", (double)P->alpha_min);
+    if (P->max_history < 1 || P->max_history > 65536) return sq_set_error("max_history must be in 1..65536 (got %d)", P->max_history);
+    if (!(P->sigma_p >= 0.0f)) return sq_set_error("sigma_p must be a number >= 0 (got %g)", (double)P->sigma_p);
+    if (P->cos_n != P->cos_n) return sq_set_error("cos_n must be a number (got %g)", (double)P->cos_n);
+    if ((uintptr_t)d_prev % 16 != 0) return sq_set_error("d_prev must be 16-byte aligned");
+    if ((uintptr_t)d_next % 16 != 0) return sq_set_error("d_next must be 16-byte aligned");
+    const size_t n = (size_t)rows * (size_t)cols, hb = sq_temporal_history_bytes(rows, cols);
+    const NamedRange r[11] = { { "d_color", d_color, 12 * n }, { "d_var", d_var, 4 * n }, { "d_tri", d_tri, 4 * n }, { "d_normal", d_normal, 12 * n },
+                               { "d_point", d_point, 12 * n }, { "d_alpha", d_alpha, 4 * n }, { "d_prev", d_prev, hb }, { "d_next", d_next, hb },
+                               { "d_out", d_out, 12 * n }, { "d_out_var", d_out_var, 4 * n }, { "d_out_len", d_out_len, 4 * n } };
+    const int twins[2][2] = { { 0, 8 }, { 1, 9 } };                              // d_out == d_color, d_out_var == d_var
+    return refuse_overlaps(r, 11, " (only d_out == d_color and d_out_var == d_var may share memory)", twins, 2);
+}
+
+unsigned grid_for(long long units) { return (unsigned)(units < kMaxGrid ? units : kMaxGrid); }
+
+}  // namespace
+
+extern "C" const char* sq_temporal_last_error(void) { return sq_error_buffer(); }
+extern "C" const char* sq_temporal_build_id(void) { return SQ_TEMPORAL_BUILD_ID; }
+
+extern "C" size_t sq_temporal_history_bytes(int32_t rows, int32_t cols) {
+    if (rows < 1 || cols < 1 || (long long)rows * cols > kMaxPixels) return 0;
+    return (size_t)rows * (size_t)cols * 3 * sizeof(Rec);
+}
+
+extern "C" int sq_temporal_project(const sq_camera* prev, int32_t w, int32_t h, const float point[3], float* fx, float* fy) {
+    if (!prev || !point || !fx || !fy) { sq_set_error("null argument: prev, point, fx and fy are required"); return -1; }
+    if (w < 1 || h < 1) { sq_set_error("w and h must be at least 1 (got %d x %d)", w, h); return -1; }
+    float x, y;
+    const bool ok = temporalpix::project(prev->pos, prev->rot, (float)w, (float)h, point[0], point[1], point[2], x, y);
+    *fx = x; *fy = y;
+    return ok ? 1 : 0;
+}
+
+extern "C" int sq_temporal_accumulate_device(int32_t device, int32_t rows, int32_t cols, const float* d_color, const float* d_var,
+                                             const int32_t* d_tri, const float* d_normal, const float* d_point, const float* d_alpha,
+                                             const sq_camera* prev_cam, const void* d_prev, const sq_temporal_params* params,
+                                             void* d_next, float* d_out, float* d_out_var, int32_t* d_out_len, void* hip_stream) {
+    if (check_accumulate(rows, cols, d_color, d_var, d_tri, d_normal, d_point, d_alpha, prev_cam, d_prev, params, d_next, d_out, d_out_var,
+                         d_out_len))
+        return 1;
+    SQ_HIP(hipSetDevice(device));
+    Cam cam = {};
+    if (d_prev) {
+        for (int i = 0; i < 3; ++i) cam.pos[i] = prev_cam->pos[i];
+        for (int i = 0; i < 9; ++i) cam.rot[i] = prev_cam->rot[i];
+    }
+    const temporalpix::Params P{ params->alpha_min, params->max_history, params->sigma_p, params->cos_n };
+    const long long tx = ((long long)cols + kTileW - 1) / kTileW, ty = ((long long)rows + kTileH - 1) / kTileH;
+    hipLaunchKernelGGL(sq_tp_accumulate, dim3(grid_for(tx * ty)), dim3(kBlock), 0, (hipStream_t)hip_stream, rows, cols, d_color, d_var,
+                       d_tri, d_normal, d_point, d_alpha, cam, (const Rec*)d_prev, P, (Rec*)d_next, d_out, d_out_var, d_out_len, tx * ty, tx);
+    SQ_HIP(hipGetLastError());
+    return 0;
+}
+
+extern "C" int sq_temporal_unpack_device(int32_t device, int32_t rows, int32_t cols, const void* d_hist, float* d_color, float* d_var,
+                                         int32_t* d_len, int32_t* d_tri, float* d_normal, float* d_point, void* hip_stream) {
+    if (!d_hist) return sq_set_error("null argument: d_hist is required");
+    if (!d_color && !d_var && !d_len && !d_tri && !d_normal && !d_point)
+        return sq_set_error("no output: give at least one of d_color, d_var, d_len, d_tri, d_normal and d_point");
+    if (check_size(rows, cols)) return 1;
+    if ((uintptr_t)d_hist % 16 != 0) return sq_set_error("d_hist must be 16-byte aligned");
+    const size_t n = (size_t)rows * (size_t)cols;
+    const NamedRange r[7] = { { "d_hist", d_hist, sq_temporal_history_bytes(rows, cols) }, { "d_color", d_color, 12 * n }, { "d_var", d_var, 4 * n },
+                              { "d_len", d_len, 4 * n }, { "d_tri", d_tri, 4 * n }, { "d_normal", d_normal, 12 * n }, { "d_point", d_point, 12 * n } };
+    if (refuse_overlaps(r, 7)) return 1;
+    SQ_HIP(hipSetDevice(device));
+    hipLaunchKernelGGL(sq_tp_unpack, dim3(grid_for(((long long)n + kBlock - 1) / kBlock)), dim3(kBlock), 0, (hipStream_t)hip_stream,
+                       (long long)n, (const Rec*)d_hist, d_color, d_var, d_len, d_tri, d_normal, d_point);
+    SQ_HIP(hipGetLastError());
+    return 0;
+}

@@ -1,0 +1,106 @@
+// sq_temporal_pixel.h — the arithmetic of one pixel of a temporal accumulation (include/squigly_temporal.h), written once for the
+// host and the device: sq_temporal_project compiles `project` with the host compiler, every lane of libsquigly_temporal.so's kernel
+// compiles all of it with the device compiler, and tests/temporal_main.cpp compiles it with g++ under the sanitizers.  Only the
+// temporal library lists this header.
+//
+// Every operation is one fp32 operation in the order of the header's contract (tests/temporal_restatement.py restates it in numpy);
+// -ffp-contract=off and the correctly rounded divide keep the two equal.  Nothing is skipped for a zero weight: 0 * inf is NaN here too.
+#pragma once
+#include <stdint.h>
+
+#include "sq_math.h"
+
+namespace temporalpix {
+
+// A 16-byte record of the history block.  Three planes of them: CV colour.rgb + variance, NL normal.xyz + length (an int32's bits),
+// PT point.xyz + triangle (an int32's bits).
+struct alignas(16) Rec { float x, y, z, w; };
+
+SQ_HD float int_bits(int32_t i) { float f; __builtin_memcpy(&f, &i, sizeof f); return f; }
+SQ_HD int32_t bits_int(float f) { int32_t i; __builtin_memcpy(&i, &f, sizeof i); return i; }
+
+struct Params { float alpha_min; int32_t max_history; float sigma_p, cos_n; };
+
+// The inverse of makeRay (src/Lib.hs:107-114) for the world point (px, py, pz) under the camera (pos, rot) of an image of ww rows
+// and hh columns: fx is the column, fy the row.  False when the point does not project (behind the camera, or more than a pixel
+// outside the image; a NaN compares false); fx and fy are then whatever the arithmetic left.
+SQ_HD bool project(const float* pos, const float* rot, float ww, float hh, float px, float py, float pz, float& fx, float& fy) {
+    const float ex = px - pos[0], ey = py - pos[1], ez = pz - pos[2];
+    const float k0 = (ex * rot[0] + ey * rot[1]) + ez * rot[2];
+    const float k1 = (ex * rot[3] + ey * rot[4]) + ez * rot[5];
+    const float k2 = (ex * rot[6] + ey * rot[7]) + ez * rot[8];
+    fx = 0.0f; fy = 0.0f;
+    if (!(k0 > 0.0f)) return false;
+    const float xo = k1 / k0, yo = k2 / k0;
+    fx = xo * ww + ww / 2.0f;
+    fy = hh / 2.0f - yo * hh;
+    return fx >= -1.0f && fx < hh && fy >= -1.0f && fy < ww;
+}
+
+struct Pixel { float r, g, b, v; int32_t len; };
+
+// The pixel's result from its inputs and the previous block (cv, nl, pt: the three planes; nullptr = no history).  alpha < 0 never
+// raises a (the caller passes -1 without d_alpha: a >= alpha_min >= 0 > -1).
+SQ_HD Pixel accumulate(const Rec* cv, const Rec* nl, const Rec* pt, int32_t rows, int32_t cols, const float* pos, const float* rot,
+                       const Params& P, float cr, float cg, float cb, float v, int32_t tri, float nx, float ny, float nz,
+                       float px, float py, float pz, bool has_alpha, float alpha) {
+    Pixel out = { cr, cg, cb, v, 1 };
+    if (!cv || tri < 0) return out;
+    float fx, fy;
+    if (!project(pos, rot, (float)rows, (float)cols, px, py, pz, fx, fy)) return out;
+    const float x0 = __builtin_floorf(fx), y0 = __builtin_floorf(fy);
+    const float tx = fx - x0, ty = fy - y0;
+    const long long ix = (long long)x0, iy = (long long)y0;
+    float sw = 0.0f, sr = 0.0f, sg = 0.0f, sb = 0.0f, sv = 0.0f;
+    int32_t m = 0x7fffffff;
+    // The twelve records of the four taps are loaded first, each from an address that does not depend on another load: a tap's three
+    // loads one behind the other, each behind the test of the one before, left the kernel waiting for twelve round trips a pixel.  A
+    // tap outside the image reads pixel 0 and is left out below.
+    bool in[4];
+    Rec pqs[4], nqs[4], cqs[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        const long long qy = iy + (t >> 1), qx = ix + (t & 1);
+        in[t] = qy >= 0 && qy < rows && qx >= 0 && qx < cols;
+        const long long q = in[t] ? qy * cols + qx : 0;
+        pqs[t] = pt[q];
+        nqs[t] = nl[q];
+        cqs[t] = cv[q];
+    }
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const Rec pq = pqs[2 * j + i], nq = nqs[2 * j + i], cq = cqs[2 * j + i];
+            if (!in[2 * j + i] || bits_int(pq.w) < 0) continue;
+            const float bw = (i ? tx : 1.0f - tx) * (j ? ty : 1.0f - ty);
+            const float dn = (nx * nq.x + ny * nq.y) + nz * nq.z;
+            if (!(dn >= P.cos_n)) continue;
+            const float dx = pq.x - px, dy = pq.y - py, dz = pq.z - pz;
+            const float pd = (nx * dx + ny * dy) + nz * dz;
+            if (!(__builtin_fabsf(pd) <= P.sigma_p)) continue;
+            sw = sw + bw;
+            sr = sr + bw * cq.x;
+            sg = sg + bw * cq.y;
+            sb = sb + bw * cq.z;
+            sv = sv + bw * cq.w;
+            const int32_t lq = bits_int(nq.w);
+            m = lq < m ? lq : m;
+        }
+    }
+    if (!(sw > 0.0f)) return out;
+    const float hr = sr / sw, hg = sg / sw, hb = sb / sw, hv = sv / sw;
+    const int32_t m1 = (int32_t)((uint32_t)m + 1u);
+    float a = 1.0f / (float)m1;
+    if (a < P.alpha_min) a = P.alpha_min;
+    if (has_alpha && a < alpha) a = alpha;
+    out.r = hr + a * (cr - hr);
+    out.g = hg + a * (cg - hg);
+    out.b = hb + a * (cb - hb);
+    const float om = 1.0f - a;
+    out.v = (om * om) * hv + (a * a) * v;
+    out.len = m1 < P.max_history ? m1 : P.max_history;
+    return out;
+}
+
+}  // namespace temporalpix

@@ -215,6 +215,33 @@ def render_lens_rgb8(bih, cam, samples, dimensions, lens=None, subrays=None, dev
         return out.rgb.cpu().numpy()
 
 
+def render_sequence(bih, cams, spp, dimensions, temporal=True, denoise=None, device=0, depth=None, sky=None, period=64, alpha_min=0.1,
+                    max_history=32):
+    """The frames of a camera move, `spp` samples each (DeviceScene, Temporal: one device, the scene uploaded once): yields the
+    (w, h, 3) uint8 image of every camera of `cams`, in order.  temporal=True accumulates every frame over the ones before it
+    (libsquigly_temporal.so); temporal=False shows each frame's own samples -- the same samples, so the two can be compared.
+    Frame f takes the samples [(f mod period) * spp, + spp) of the (spp * period)-sample frame.  denoise (None = off; True, a
+    sigma_l or a dict of denoise parameters): every frame is filtered on the device after the accumulation.  depth, sky: as in
+    render_progressive.  The images are a preview's (temporal.tonemap), not pinned to the bit.  Refused before anything is uploaded:
+    no camera, and what Temporal refuses of spp, period, alpha_min and max_history."""
+    cams = list(cams)
+    if not cams:
+        raise ValueError("render_sequence needs at least one camera")
+    from .temporal import _temporal_args
+    _temporal_args(spp, period, alpha_min, max_history)
+    dn = None if denoise is None or denoise is False else denoise_options(denoise)      # refused before anything is uploaded
+    scene = _resident(bih, device, None, depth, sky)
+    w, h = dimensions
+    with scene as ds:
+        from .temporal import Temporal                 # torch: only the resident-scene path needs it
+        t = Temporal(ds, w, h, spp, period=period, alpha_min=alpha_min, max_history=max_history, denoise=dn)
+        for cam in cams:
+            _, _, _, rgb = t.step(cam)
+            if not temporal:
+                t.forget()
+            yield rgb.cpu().numpy()
+
+
 def render(bih, cam, settings: Settings):
     """Lib.render: compute the image and write it to settings.savePath."""
     img = render_rgb8(bih, cam, settings.samples, settings.dimensions, settings.cast)
