@@ -13,6 +13,8 @@ from .denoise import denoise, denoise_variance, denoise_frame, Guides           
 from .lens import Lens, LensFrame                                                    # noqa: F401
 # motion blur: its module is importlib.import_module("squigly-trace_amd.shutter")
 from .shutter import Motion                                                          # noqa: F401
+# the display stage: its module is importlib.import_module("squigly-trace_amd.film")
+from .film import Film                                                               # noqa: F401
 
 
 def device_count() -> int:

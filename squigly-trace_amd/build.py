@@ -1,7 +1,7 @@
 """Build libsquigly_hip.so (HIP kernels for gfx950 + host side), libsquigly_denoise.so (the denoiser), libsquigly_lens.so (jittered,
 thin-lens primary rays), libsquigly_mlens.so (those rays for the live pixels of a mask), libsquigly_shutter.so (those rays, dense
-or listed, under a camera that moves during the exposure) and libsquigly_temporal.so (temporal accumulation over a sequence of
-frames) in-tree with hipcc.
+or listed, under a camera that moves during the exposure), libsquigly_temporal.so (temporal accumulation over a sequence of
+frames) and libsquigly_film.so (exposure, tone curve and quantisation of a frame) in-tree with hipcc.
 
     python squigly-trace_amd/build.py [--force]
 
@@ -69,8 +69,15 @@ TEMPORAL_SOURCES = ["sq_temporal.hip"]
 TEMPORAL_HEADERS = ["sq_math.h", "sq_error.h", "sq_call_checks.h", "sq_temporal_pixel.h", "../../include/squigly_temporal.h",
                     "../../include/squigly_hip.h"]
 
+# The seventh library: the display stage (include/squigly_film.h).  Device images to device images like the denoiser and the temporal
+# library, and no client of the main library; the arithmetic of a pixel (sq_film_pixel.h) is its own, and sq_math.h is read for the
+# reference's tonemap.
+FILM_OUT = os.path.join(HERE, "libsquigly_film.so")
+FILM_SOURCES = ["sq_film.hip"]
+FILM_HEADERS = ["sq_math.h", "sq_error.h", "sq_call_checks.h", "sq_film_pixel.h", "../../include/squigly_film.h"]
+
 # One description per library.  macro: the -D that carries the id into the library (what sq_build_id(), sq_denoise_build_id(),
-# sq_lens_build_id(), sq_mlens_build_id(), sq_shutter_build_id() and sq_temporal_build_id() return); salt: what the id's hash starts from, so that no two libraries share an id; link: behind the output.
+# sq_lens_build_id(), sq_mlens_build_id(), sq_shutter_build_id(), sq_temporal_build_id() and sq_film_build_id() return); salt: what the id's hash starts from, so that no two libraries share an id; link: behind the output.
 MAIN = dict(out=OUT, sources=SOURCES, headers=HEADERS, macro="SQ_BUILD_ID", salt=b"", link=[])
 DENOISE = dict(out=DENOISE_OUT, sources=DENOISE_SOURCES, headers=DENOISE_HEADERS, macro="SQ_DENOISE_BUILD_ID", salt=b"denoise\0", link=[])
 LENS = dict(out=LENS_OUT, sources=LENS_SOURCES, headers=LENS_HEADERS, macro="SQ_LENS_BUILD_ID", salt=b"lens\0",
@@ -78,6 +85,7 @@ LENS = dict(out=LENS_OUT, sources=LENS_SOURCES, headers=LENS_HEADERS, macro="SQ_
 MLENS = dict(out=MLENS_OUT, sources=MLENS_SOURCES, headers=MLENS_HEADERS, macro="SQ_MLENS_BUILD_ID", salt=b"mlens\0", link=LENS["link"])
 SHUTTER = dict(out=SHUTTER_OUT, sources=SHUTTER_SOURCES, headers=SHUTTER_HEADERS, macro="SQ_SHUTTER_BUILD_ID", salt=b"shutter\0", link=LENS["link"])
 TEMPORAL = dict(out=TEMPORAL_OUT, sources=TEMPORAL_SOURCES, headers=TEMPORAL_HEADERS, macro="SQ_TEMPORAL_BUILD_ID", salt=b"temporal\0", link=[])
+FILM = dict(out=FILM_OUT, sources=FILM_SOURCES, headers=FILM_HEADERS, macro="SQ_FILM_BUILD_ID", salt=b"film\0", link=[])
 
 
 def lib_source_id(lib, extra=()):
@@ -128,6 +136,8 @@ def shutter_source_id(extra=()): return lib_source_id(SHUTTER, extra)
 def shutter_stale(): return lib_stale(SHUTTER)
 def temporal_source_id(): return lib_source_id(TEMPORAL)
 def temporal_stale(): return lib_stale(TEMPORAL)
+def film_source_id(extra=()): return lib_source_id(FILM, extra)
+def film_stale(): return lib_stale(FILM)
 
 
 def build_client(lib, force=False, extra=(), out=None):
@@ -145,6 +155,12 @@ def build_shutter(force=False, extra=(), out=None): return build_client(SHUTTER,
 def build_temporal(force=False):
     """The temporal library: compiled unless the in-tree product carries the current id.  (No client of the main library.)"""
     return build_client(TEMPORAL, force)
+
+
+def build_film(force=False, extra=(), out=None):
+    """The film library: compiled unless the in-tree product carries the current id.  (No client of the main library.)  extra, out:
+    a variant beside it, e.g. -DSQ_FILM_HIST_FOLD=0 (tools/gpu_film.py measures the histogram's folding forms that way)."""
+    return build_client(FILM, force, extra, out)
 
 
 def build(force=False, extra=(), out=None):
@@ -167,6 +183,7 @@ def build(force=False, extra=(), out=None):
     build_mlens(force)
     build_shutter(force)
     build_temporal(force)
+    build_film(force)
     return OUT
 
 

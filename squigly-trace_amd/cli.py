@@ -218,7 +218,35 @@ def build_parser():
     p.add_argument("--temporal", type=unit_float, nargs="?", const=True, default=None, metavar="ALPHA_MIN",
                    help="With --sequence: accumulate every frame over the frames before it, reprojected through its first hits; "
                         "ALPHA_MIN is the least weight of the new frame (default 0.1)")
+    # not flags of the reference: how the float frame becomes bytes, on the device (include/squigly_film.h).  They need a mode that
+    # has such a frame on the device: --adaptive with --denoise, or --sequence
+    p.add_argument("--film", choices=FILM_CURVES, default=None, metavar="CURVE",
+                   help="With --adaptive --denoise or --sequence: the tone curve of the image, one of " + ", ".join(FILM_CURVES)
+                        + " (default reference: the renderer's own bytes)")
+    p.add_argument("--exposure", type=finite_positive_float, default=None, metavar="E", help="With --film: the frame is multiplied by E first (default 1)")
+    p.add_argument("--auto-exposure", type=finite_positive_float, nargs="?", const=0.18, default=None, metavar="KEY",
+                   help="With --film: meter every frame on the device and bring its median luminance to KEY (default 0.18); in a "
+                        "--sequence the exposure follows from frame to frame")
+    p.add_argument("--white", type=positive_float, default=None, metavar="W", help="With --film reinhard: the luminance that becomes white (default: none)")
+    p.add_argument("--srgb", action="store_true", help="With --film other than reference: encode the image with the sRGB transfer function")
+    p.add_argument("--dither", action="store_true", help="With --film other than reference: ordered 8 x 8 dither before the bytes are taken")
     return p
+
+
+FILM_CURVES = ("reference", "atan", "reinhard", "filmic", "linear")
+AUTO_EXPOSURE_RATE = 0.25                    # of a --sequence: how far the exposure moves towards a frame's target
+
+
+def film_of(a):
+    """The Film of --film and the flags that go with it, or None without them."""
+    if a.film is None:
+        return None
+    from .film import Film, srgb_lut
+    auto = None
+    if a.auto_exposure is not None:
+        auto = dict(key=a.auto_exposure, rate=AUTO_EXPOSURE_RATE if a.sequence is not None else 1.0)
+    return Film(curve=a.film, exposure=1.0 if a.exposure is None else a.exposure, white=float("inf") if a.white is None else a.white,
+                lut=srgb_lut() if a.srgb else None, dither=a.dither, auto=auto)
 
 
 def camera_text(path):
@@ -261,6 +289,19 @@ def parse_args(argv=None):
             p.error("--sequence needs --samples >= 1")
     if a.denoise is not None and a.adaptive is None and a.sequence is None:
         p.error("--denoise needs --adaptive (the filter takes its variance from the adaptive frame's second moments)")
+    film_flags = [flag for flag, given in (("--exposure", a.exposure is not None), ("--auto-exposure", a.auto_exposure is not None),
+                                           ("--white", a.white is not None), ("--srgb", a.srgb), ("--dither", a.dither)) if given]
+    if film_flags and a.film is None:
+        p.error(f"{film_flags[0]} needs --film")
+    if a.film is not None:
+        if a.sequence is None and (a.adaptive is None or a.denoise is None):
+            p.error("--film needs a float frame on the device: --adaptive with --denoise, or --sequence")
+        if a.film == "reference" and (a.srgb or a.dither):
+            p.error("--film reference takes neither --srgb nor --dither (it is the renderer's own conversion to bytes)")
+        if a.white is not None and a.film != "reinhard":
+            p.error("--white needs --film reinhard")
+        if a.exposure is not None and a.auto_exposure is not None:
+            p.error("--exposure cannot be combined with --auto-exposure")
     if a.light is not None and not a.cast:
         p.error("--light needs --cast")
     if a.depth is not None and a.cast:
@@ -325,7 +366,8 @@ def main(argv=None):
     elif a.sequence is not None:
         paths = view_paths(settings.savePath, len(a.sequence))
         frames = render_sequence(bih, a.sequence, settings.samples, settings.dimensions, temporal=a.temporal is not None, denoise=a.denoise,
-                                 depth=a.depth, sky=a.sky, **({} if a.temporal is None or a.temporal is True else {"alpha_min": a.temporal}))
+                                 depth=a.depth, sky=a.sky, film=film_of(a),
+                                 **({} if a.temporal is None or a.temporal is True else {"alpha_min": a.temporal}))
         for path, img in zip(paths, frames):
             write_png(path, img)
         print(f"Wrote {len(paths)} frames to {paths[0]} ...")
@@ -333,7 +375,7 @@ def main(argv=None):
         import numpy as np
         for done, live, spent, img, counts in render_adaptive(bih, cam, settings.samples, settings.dimensions, a.adaptive, eps=a.adaptive_eps,
                                                               first=a.adaptive_first, step=a.adaptive_step, cast=settings.cast, lights=a.light,
-                                                              depth=a.depth, sky=a.sky, denoise=a.denoise):
+                                                              depth=a.depth, sky=a.sky, denoise=a.denoise, film=film_of(a)):
             print(f"Adaptive {done}/{settings.samples} live {live} spent {spent}")
         if a.denoise is not None:
             print("Denoised")

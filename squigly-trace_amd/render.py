@@ -100,7 +100,7 @@ def denoise_options(denoise):
 
 
 def render_adaptive(bih, cam, samples, dimensions, tol, eps=1.0, first=8, step=8, cast=False, device=0, rule=None, lights=None,
-                    depth=None, sky=None, denoise=None, lens=None, subrays=None, motion=None):
+                    depth=None, sky=None, denoise=None, lens=None, subrays=None, motion=None, film=None):
     """The frame of render_rgb8 with adaptive sampling (DeviceScene, Adaptive): yields (done, live, spent, rgb8, counts) after
     every step -- the end of the range rendered, the pixels still live, the samples spent so far, the (w, h, 3) uint8 image and
     the (w, h) int32 per-pixel sample counts.  A pixel that stopped after n samples shows the mean of its first n samples, so
@@ -113,16 +113,21 @@ def render_adaptive(bih, cam, samples, dimensions, tol, eps=1.0, first=8, step=8
     n = samples / subrays (ValueError); the yielded done, spent and counts are samples too; cast=True is refused.  denoise= then
     filters with the variance of the sub-ray sums brought to the pixel mean's scale, denoise_variance(...) * (1 / (n * n)).
     motion (a Motion; needs a lens): the lens frame under a camera that moves during the exposure (AdaptiveLens(motion=)); cam is then
-    not read, and denoise= takes its guides from motion.pose(0.5) -- a convenience, not pinned to the bit."""
+    not read, and denoise= takes its guides from motion.pose(0.5) -- a convenience, not pinned to the bit.
+    film (a Film; needs denoise): the last tuple's image is developed by it on the device (libsquigly_film.so) and leaves the device
+    only as bytes; None = the device's own tonemap through the debug hook, as before.  Film() gives the same bytes."""
     from .device import Adaptive                       # torch: only the resident-scene path needs it
+    from .film import film_arg
     w, h = dimensions
+    if film_arg(film) is not None and (denoise is None or denoise is False):
+        raise ValueError("film needs denoise: only the filtered frame is developed (the steps before it are the renderer's own bytes)")
     if int(first) < 1 or int(step) < 1:
         raise ValueError(f"first and step must be positive, got {first}, {step}")
     if not float(tol) >= 0 or not float(eps) >= 0:
         raise ValueError(f"tol and eps must be numbers >= 0, got {tol}, {eps}")
     if lens is not None or subrays is not None or motion is not None:
         yield from _render_adaptive_lens(bih, cam, samples, dimensions, tol, eps, first, step, cast, device, rule, lights, depth, sky,
-                                         denoise, lens, subrays, motion)
+                                         denoise, lens, subrays, motion, film)
         return
     scene = _resident(bih, device, lights, depth, sky)
     dn = None if denoise is None or denoise is False else denoise_options(denoise)      # refused before anything is uploaded
@@ -135,12 +140,20 @@ def render_adaptive(bih, cam, samples, dimensions, tol, eps=1.0, first=8, step=8
         if dn is not None and avg is not None:       # (a frame without pixels never steps: nothing to filter)
             from .denoise import denoise_frame, denoise_variance
             out, _ = denoise_frame(ds, cam, w, h, avg, var=denoise_variance(a.sums, a.sums2, a.counts), **dn)
-            img = N.debug_eval("tonemap", out.cpu().numpy().reshape(-1, 3), device=ds.device).reshape(tuple(out.shape))
+            img = _developed(ds, out, film)
             yield a.done, a.live, a.samples_spent, img, a.counts.cpu().numpy()
 
 
+def _developed(ds, out, film):
+    """The uint8 image of a filtered device frame: film's, which leaves the device as bytes only, or -- film None -- the device's
+    own tonemap through the debug hook (a host round trip of the float frame)."""
+    if film is not None:
+        return film(out).cpu().numpy()
+    return N.debug_eval("tonemap", out.cpu().numpy().reshape(-1, 3), device=ds.device).reshape(tuple(out.shape))
+
+
 def _render_adaptive_lens(bih, cam, samples, dimensions, tol, eps, first, step, cast, device, rule, lights, depth, sky, denoise, lens,
-                          subrays, motion=None):
+                          subrays, motion=None, film=None):
     """render_adaptive with a lens: AdaptiveLens, its sub-ray units turned into samples for the caller."""
     from .lens import frame_args
     if lens is None:
@@ -169,7 +182,7 @@ def _render_adaptive_lens(bih, cam, samples, dimensions, tol, eps, first, step, 
             # the variance of the mean of sub-ray sums is n * n times that of the pixel mean, in every branch of the variance formula
             var = denoise_variance(a.sums, a.sums2, a.counts) * (1 / (n * n))            # one float32 multiply
             out, _ = denoise_frame(ds, cam if motion is None else motion.pose(0.5), w, h, avg, var=var, **dn)
-            img = N.debug_eval("tonemap", out.cpu().numpy().reshape(-1, 3), device=ds.device).reshape(tuple(out.shape))
+            img = _developed(ds, out, film)
             yield a.done * n, a.live, a.samples_spent, img, a.sample_counts.cpu().numpy()
 
 
@@ -216,29 +229,36 @@ def render_lens_rgb8(bih, cam, samples, dimensions, lens=None, subrays=None, dev
 
 
 def render_sequence(bih, cams, spp, dimensions, temporal=True, denoise=None, device=0, depth=None, sky=None, period=64, alpha_min=0.1,
-                    max_history=32):
+                    max_history=32, film=None):
     """The frames of a camera move, `spp` samples each (DeviceScene, Temporal: one device, the scene uploaded once): yields the
     (w, h, 3) uint8 image of every camera of `cams`, in order.  temporal=True accumulates every frame over the ones before it
     (libsquigly_temporal.so); temporal=False shows each frame's own samples -- the same samples, so the two can be compared.
     Frame f takes the samples [(f mod period) * spp, + spp) of the (spp * period)-sample frame.  denoise (None = off; True, a
     sigma_l or a dict of denoise parameters): every frame is filtered on the device after the accumulation.  depth, sky: as in
-    render_progressive.  The images are a preview's (temporal.tonemap), not pinned to the bit.  Refused before anything is uploaded:
-    no camera, and what Temporal refuses of spp, period, alpha_min and max_history."""
+    render_progressive.  The images are a preview's (temporal.tonemap), not pinned to the bit, unless film (a Film) is given: every
+    frame is then developed by it on the device (libsquigly_film.so; with Film(auto=...) the exposure adapts from frame to frame under
+    temporal=True; under temporal=False the film's exposure state is forgotten after every frame as the history is -- film.reset() --
+    so that every frame is exposed at its own target and the frames stay independent).
+    Refused before anything is uploaded: no camera, and what Temporal refuses of spp, period, alpha_min and max_history."""
     cams = list(cams)
     if not cams:
         raise ValueError("render_sequence needs at least one camera")
     from .temporal import _temporal_args
     _temporal_args(spp, period, alpha_min, max_history)
+    from .film import film_arg
+    film_arg(film)
     dn = None if denoise is None or denoise is False else denoise_options(denoise)      # refused before anything is uploaded
     scene = _resident(bih, device, None, depth, sky)
     w, h = dimensions
     with scene as ds:
         from .temporal import Temporal                 # torch: only the resident-scene path needs it
-        t = Temporal(ds, w, h, spp, period=period, alpha_min=alpha_min, max_history=max_history, denoise=dn)
+        t = Temporal(ds, w, h, spp, period=period, alpha_min=alpha_min, max_history=max_history, denoise=dn, film=film)
         for cam in cams:
             _, _, _, rgb = t.step(cam)
             if not temporal:
                 t.forget()
+                if film is not None:
+                    film.reset()
             yield rgb.cpu().numpy()
 
 

@@ -238,7 +238,8 @@ class Temporal:
     before it (DeviceScene.render_rows_masked, denoise_variance, DeviceScene.guides, accumulate and, optionally, the filter).
 
     step(cam) renders frame f = `frames` and returns (avg, var, length, rgb): the accumulated colour [w, h, 3] and the variance of
-    its luminance [w, h] (float32), the history length of every pixel (int32) and a tonemapped preview (uint8; tonemap()).  The
+    its luminance [w, h] (float32), the history length of every pixel (int32) and a tonemapped preview (uint8; tonemap(), or
+    film= (a Film): the image it develops on the device, pinned to the bit).  The
     frame's samples are the range [(f mod period) * spp, + spp) of the (spp * period)-sample frame, so that consecutive frames
     take different seeds: with equal seeds a still camera would add nothing.  `noisy` is the frame's own spp-sample mean.
     The history lives in demodulated space (denoise_frame's: X = (avg - emit) / surf where all of surf is > 0), a pixel's alpha is
@@ -250,12 +251,14 @@ class Temporal:
     Whole frames on one device; path-traced frames only."""
 
     def __init__(self, ds, w, h, spp, period=64, alpha_min=0.1, max_history=32, denoise=None, demodulate=True, depth=None, sky=None,
-                 sigma_p=None, cos_n=0.9, history=None, camera=None, frames=0):
+                 sigma_p=None, cos_n=0.9, history=None, camera=None, frames=0, film=None):
         import torch
         from . import device as D
         from .denoise import default_sigma_p, make_params as denoise_params
         from .render import denoise_options
         _temporal_args(spp, period, alpha_min, max_history)
+        from .film import film_arg
+        self.film = film_arg(film)
         if not P.is_integer(frames) or int(frames) < 0:
             raise ValueError(f"frames must be a non-negative integer, got {frames!r}")
         if (history is None) != (camera is None):
@@ -329,7 +332,7 @@ class Temporal:
             if ok is not None:
                 out = torch.where(ok, out * g.surf + g.emit, out)
                 out_var = out_var * scale
-            rgb = tonemap(out)
+            rgb = tonemap(out) if self.film is None else self.film(out, stream=st)
         self._cur, self._cam, self.noisy = nxt, N.Camera.from_buffer_copy(bytes(cam)), noisy
         self.frames += 1
         return out, out_var, length, rgb
