@@ -293,6 +293,56 @@ def count(n):
     return checked(n, lib().sq_last_error, count=True)
 
 
+class Binding:
+    """One of the package's other shared libraries, bound once: where it is, how it is loaded, and the two functions
+    every library has, sq_<name>_last_error and sq_<name>_build_id.  A module takes its LIB_PATH, lib, check and build_id from here:
+
+        LIB_PATH, lib, check, build_id = N.Binding("libsquigly_lens.so", "sq_lens_", _declare, env="SQ_LENS_LIB_PATH", client=True)
+
+    file: the library's name beside this file; env: an environment variable that names another build of the same library (a
+    development aid: build.py's compile_lib(..., out=...)); declare(L): sets the argtypes and restypes of the library's own functions;
+    client: the library is linked against libsquigly_hip.so, which is then loaded from this package first."""
+
+    def __init__(self, file, prefix, declare, env=None, client=False):
+        self.path = (os.environ.get(env) if env else None) or os.path.join(_HERE, file)
+        self.prefix, self.declare, self.client, self._lib = prefix, declare, client, None
+
+    def __iter__(self):
+        return iter((self.path, self.lib, self.check, self.build_id))
+
+    def load(self, path):
+        """The build of the library at `path`, with its prototypes declared (a variant beside the product's)."""
+        if self.client:
+            lib()
+        L = load(path)
+        getattr(L, self.prefix + "last_error").restype = C.c_char_p
+        getattr(L, self.prefix + "build_id").restype = C.c_char_p
+        self.declare(L)
+        return L
+
+    def lib(self):
+        if self._lib is None:
+            self._lib = self.load(self.path)
+        return self._lib
+
+    def check(self, rc):
+        checked(rc, getattr(self.lib(), self.prefix + "last_error"))
+
+    def entry(self, name):
+        """The library's function `name` as a call that raises SquiglyError with the library's message when it returns non-zero.
+        Made once per entry point, at import: the library is loaded by the first call, not here."""
+        err = self.prefix + "last_error"
+
+        def call(*args):
+            L = self.lib()
+            checked(getattr(L, name)(*args), getattr(L, err))
+        return call
+
+    def build_id(self):
+        """sq_<name>_build_id(): hash of the sources and flags the loaded library was built from (build.py: lib_source_id)."""
+        return getattr(self.lib(), self.prefix + "build_id")().decode()
+
+
 EXPORTED_SYMBOLS = [
     # include/squigly_hip.h
     "sq_render_rgb8", "sq_render_f32", "sq_scene_upload", "sq_scene_free", "sq_shard_rows",

@@ -6,13 +6,9 @@ comes from the HIP kernels of csrc/sq_denoise.hip.  There is no fallback: a miss
 """
 import collections
 import ctypes as C
-import os
 
 from . import _native as N
 from . import _plumbing as P
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(_HERE, "libsquigly_denoise.so")
 
 # include/squigly_denoise.h; sq_denoise_last_error and the functions a caller uses
 EXPORTED_SYMBOLS = ["sq_denoise_last_error", "sq_denoise_build_id", "sq_denoise_pass_form", "sq_denoise_workspace_bytes",
@@ -33,17 +29,8 @@ class Params(C.Structure):
                 ("normal_squarings", C.c_int32), ("form", C.c_int32)]
 
 
-_lib = None
-
-
-def lib():
-    global _lib
-    if _lib is not None:
-        return _lib
-    L = N.load(LIB_PATH)
+def _declare(L):
     vp, i32 = C.c_void_p, C.c_int32
-    L.sq_denoise_last_error.restype = C.c_char_p
-    L.sq_denoise_build_id.restype = C.c_char_p
     L.sq_denoise_pass_form.argtypes = [i32]
     L.sq_denoise_pass_form.restype = i32
     L.sq_denoise_workspace_bytes.argtypes = [i32, i32]
@@ -52,17 +39,9 @@ def lib():
     call = [i32, i32, i32, vp, vp, vp, vp, vp, C.POINTER(Params), vp, vp, vp, C.c_size_t, vp]
     L.sq_denoise_device.argtypes = call
     L.sq_denoise_stage_device.argtypes = call + [i32]
-    _lib = L
-    return L
 
 
-def check(rc):
-    N.checked(rc, lib().sq_denoise_last_error)
-
-
-def build_id():
-    """sq_denoise_build_id(): hash of the sources and flags the loaded library was built from (build.py: denoise_source_id)."""
-    return lib().sq_denoise_build_id().decode()
+LIB_PATH, lib, check, build_id = N.Binding("libsquigly_denoise.so", "sq_denoise_", _declare)
 
 
 def workspace_bytes(rows, cols):
@@ -179,6 +158,32 @@ def scene_guides(ds, cam, w, h, shard=(None, 0, 1), stream=None):
     return Guides(hits.tri, hits.point, normal, surf, emit)
 
 
+def demodulated(g, avg, var=None):
+    """(x, var, how) of a frame `avg` under its guides g: where a pixel is hit and all of surf is > 0, x = (avg - emit) / surf --
+    the light arriving at the first hit, free of the surface's own colour -- and the variance of its luminance divided by l(surf)^2
+    (exact for a grey surface, an estimate otherwise; None stays None); elsewhere both are as given.  how: what remodulated needs.
+    Call it under the call's stream.  denoise_frame and Temporal.step share it, operation for operation."""
+    import torch
+    ok = ((g.tri >= 0) & (g.surf > 0).all(-1))[..., None]
+    x = torch.where(ok, (avg - g.emit) / torch.where(ok, g.surf, torch.ones_like(g.surf)), avg)
+    scale = None
+    if var is not None:
+        ls = (0.25 * g.surf[..., 0] + 0.5 * g.surf[..., 1]) + 0.25 * g.surf[..., 2]
+        scale = torch.where(ok[..., 0], ls * ls, torch.ones_like(ls))
+        var = var / scale
+    return x, var, (ok, scale)
+
+
+def remodulated(g, out, out_var, how):
+    """(out, out_var) multiplied back: out * surf + emit and out_var * l(surf)^2 where demodulated divided (out_var None stays None)."""
+    import torch
+    ok, scale = how
+    out = torch.where(ok, out * g.surf + g.emit, out)
+    if out_var is not None:
+        out_var = out_var * scale
+    return out, out_var
+
+
 def denoise_frame(ds, cam, w, h, avg, var=None, shard=(None, 0, 1), demodulate=True, guides=None, stream=None, **params):
     """Filter the frame `avg` (float32 CUDA tensor [rows, h, 3]) of DeviceScene `ds` under its own guides; returns (out, out_var).
 
@@ -196,14 +201,5 @@ def denoise_frame(ds, cam, w, h, avg, var=None, shard=(None, 0, 1), demodulate=T
         g = guides if guides is not None else scene_guides(ds, cam, w, h, shard, stream=st)
         if not demodulate:
             return denoise(avg, g.tri, g.normal, g.point, var=var, stream=st, **params)
-        ok = ((g.tri >= 0) & (g.surf > 0).all(-1))[..., None]
-        x = torch.where(ok, (avg - g.emit) / torch.where(ok, g.surf, torch.ones_like(g.surf)), avg)
-        if var is not None:
-            ls = (0.25 * g.surf[..., 0] + 0.5 * g.surf[..., 1]) + 0.25 * g.surf[..., 2]
-            scale = torch.where(ok[..., 0], ls * ls, torch.ones_like(ls))
-            var = var / scale
-        out, out_var = denoise(x, g.tri, g.normal, g.point, var=var, stream=st, **params)
-        out = torch.where(ok, out * g.surf + g.emit, out)
-        if out_var is not None:
-            out_var = out_var * scale
-    return out, out_var
+        x, var, how = demodulated(g, avg, var)
+        return remodulated(g, *denoise(x, g.tri, g.normal, g.point, var=var, stream=st, **params), how)

@@ -342,9 +342,8 @@ class DeviceScene(Owner):
                     want_avg=True, want_rgb=True, work_mb=None, stream=None):
         """The anti-aliased, depth-of-field frame (lens.py, sq_lens_render_device): `subrays` primary rays per pixel, samples /
         subrays samples on each, folded in sub-ray order; returns LensFrame(sum, sum2, avg, rgb).  See lens.render_lens."""
-        from . import lens as L
-        return L.render_lens(self, cam, lens, samples, subrays, w, h, shard, r_range, sums, want_sum2, want_avg, want_rgb,
-                             L.DEFAULT_WORK_MB if work_mb is None else work_mb, stream)
+        from .lens import render_lens
+        return render_lens(self, cam, lens, samples, subrays, w, h, shard, r_range, sums, want_sum2, want_avg, want_rgb, work_mb, stream)
 
     def live_pixels(self, mask, counts, r_begin, stream=None):
         """The live list of a masked lens step (mlens.py, sq_mlens_live_device): (index, n_live), int32 CUDA tensors -- the live
@@ -357,10 +356,9 @@ class DeviceScene(Owner):
         """render_lens for the listed pixels only (mlens.py, sq_mlens_render_device): the sub-rays [r_begin, r_end) of the first
         n_live pixels of `index`, folded into their sums, sums2 and counts (in sub-rays); a pixel that is not listed costs no ray
         and keeps what every buffer holds.  Returns (out_avg, out_rgb).  See mlens.render_lens_masked."""
-        from . import lens as L
         from .mlens import render_lens_masked
         return render_lens_masked(self, cam, lens, samples, subrays, w, h, r_begin, r_end, sums, index, n_live, sums2, counts, shard,
-                                  L.DEFAULT_WORK_MB if work_mb is None else work_mb, out_avg, out_rgb, stream)
+                                  work_mb, out_avg, out_rgb, stream)
 
     def shutter_rays(self, motion, lens, samples, subrays, w, h, shard=(None, 0, 1), r_range=None, stream=None):
         """lens_rays under a camera that moves during the exposure (shutter.py, sq_shutter_rays_device): sub-ray r of a pixel is
@@ -372,19 +370,17 @@ class DeviceScene(Owner):
                        want_avg=True, want_rgb=True, work_mb=None, stream=None):
         """The motion-blurred frame (shutter.py, sq_shutter_render_device): render_lens whose `subrays` primary rays per pixel are
         as many consecutive instants of `motion`; returns LensFrame(sum, sum2, avg, rgb).  See shutter.render_shutter."""
-        from . import lens as L
         from .shutter import render_shutter
-        return render_shutter(self, motion, lens, samples, subrays, w, h, shard, r_range, sums, want_sum2, want_avg, want_rgb,
-                              L.DEFAULT_WORK_MB if work_mb is None else work_mb, stream)
+        return render_shutter(self, motion, lens, samples, subrays, w, h, shard, r_range, sums, want_sum2, want_avg, want_rgb, work_mb,
+                              stream)
 
     def render_shutter_masked(self, motion, lens, samples, subrays, w, h, r_begin, r_end, sums, index, n_live, sums2=None, counts=None,
                               shard=(None, 0, 1), work_mb=None, out_avg=None, out_rgb=None, stream=None):
         """render_lens_masked under a moving camera (shutter.py, sq_shutter_render_device with the list of live_pixels).  Returns
         (out_avg, out_rgb).  See shutter.render_shutter_masked."""
-        from . import lens as L
         from .shutter import render_shutter_masked
         return render_shutter_masked(self, motion, lens, samples, subrays, w, h, r_begin, r_end, sums, index, n_live, sums2, counts,
-                                     shard, L.DEFAULT_WORK_MB if work_mb is None else work_mb, out_avg, out_rgb, stream)
+                                     shard, work_mb, out_avg, out_rgb, stream)
 
     def raytrace(self, origins, directions, seeds=None, samples=1, k_range=None, sums=None, want_avg=True, want_rgb=False,
                  stream=None):

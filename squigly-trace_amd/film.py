@@ -7,15 +7,11 @@ There is no fallback: a missing library raises.
 """
 import ctypes as C
 import math
-import os
 
 import numpy as np
 
 from . import _native as N
 from . import _plumbing as P
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(_HERE, "libsquigly_film.so")
 
 # include/squigly_film.h
 EXPORTED_SYMBOLS = ["sq_film_last_error", "sq_film_build_id", "sq_film_histogram_device", "sq_film_expose_device", "sq_film_develop_device"]
@@ -36,35 +32,16 @@ class Params(C.Structure):
     _fields_ = [("exposure", C.c_float), ("curve", C.c_int32), ("white", C.c_float), ("n_lut", C.c_int32), ("dither", C.c_int32)]
 
 
-_lib = None
-
-
-def load(path):
-    """The library at `path` with its argument types declared (tools/gpu_film.py loads a variant build beside the product's)."""
-    L = N.load(path)
+def _declare(L):
     vp, i32 = C.c_void_p, C.c_int32
-    L.sq_film_last_error.restype = C.c_char_p
-    L.sq_film_build_id.restype = C.c_char_p
     L.sq_film_histogram_device.argtypes = [i32, i32, i32, vp, vp, vp]
     L.sq_film_expose_device.argtypes = [i32, vp, C.POINTER(Meter), vp, vp, vp]
     L.sq_film_develop_device.argtypes = [i32, i32, i32, vp, vp, C.POINTER(Params), vp, vp, vp, vp]
-    return L
 
 
-def lib():
-    global _lib
-    if _lib is None:
-        _lib = load(LIB_PATH)
-    return _lib
-
-
-def check(rc):
-    N.checked(rc, lib().sq_film_last_error)
-
-
-def build_id():
-    """sq_film_build_id(): hash of the sources and flags the loaded library was built from (build.py: film_source_id)."""
-    return lib().sq_film_build_id().decode()
+_B = N.Binding("libsquigly_film.so", "sq_film_", _declare)
+LIB_PATH, lib, check, build_id = _B
+load = _B.load           # load(path): a variant build with its argument types declared (tools/gpu_film.py loads one beside the product's)
 
 
 def _number(name, v):

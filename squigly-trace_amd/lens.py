@@ -3,18 +3,16 @@
 A lens frame gives every pixel R sub-rays -- jittered over the pixel's area, started on a thin lens -- and folds their radiances
 back in a fixed order.  PyTorch is the plumbing (device memory, streams); every ray comes from the HIP kernels of csrc/sq_lens.hip
 and every sample from libsquigly_hip.so's radiance query.  There is no fallback: a missing library raises.
+
+The three drivers of a lens frame -- frame_rays, frame_dense, frame_listed -- are written here once; mlens.py and shutter.py call
+them with their own entry point, the struct their frames begin with (the camera, or a motion) and the name their messages carry.
 """
 import collections
 import ctypes as C
 import math
-import os
 
 from . import _native as N
 from . import _plumbing as P
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-# SQ_LENS_LIB_PATH: development aid, loads an experimental build of the same library (build.py: build_lens(out=...))
-LIB_PATH = os.environ.get("SQ_LENS_LIB_PATH") or os.path.join(_HERE, "libsquigly_lens.so")
 
 # include/squigly_lens.h
 EXPORTED_SYMBOLS = ["sq_lens_last_error", "sq_lens_build_id", "sq_lens_work_bytes", "sq_lens_plan", "sq_lens_rays_device",
@@ -53,22 +51,12 @@ class Lens(C.Structure):
         return f"Lens(jitter={self.jitter!r}, aperture={self.aperture!r}, focus={self.focus!r})"
 
 
-_lib = None
-
-
 # a frame in both lens libraries' calls: cam, lens, S, R, r_begin, r_end, w, h, shard
 FRAME_ARGTYPES = [C.POINTER(N.Camera), C.POINTER(Lens)] + 6 * [C.c_int32] + [N.Shard]
 
 
-def lib():
-    global _lib
-    if _lib is not None:
-        return _lib
-    N.lib()                                   # the library it is a client of, loaded from this package first
-    L = N.load(LIB_PATH)
+def _declare(L):
     vp, i32, i64, sz = C.c_void_p, C.c_int32, C.c_int64, C.c_size_t
-    L.sq_lens_last_error.restype = C.c_char_p
-    L.sq_lens_build_id.restype = C.c_char_p
     L.sq_lens_work_bytes.argtypes = [i64, i32]
     L.sq_lens_work_bytes.restype = sz
     L.sq_lens_plan.argtypes = [i64, i32, i32, sz, vp, i32]
@@ -77,17 +65,12 @@ def lib():
     L.sq_lens_rays_device.argtypes = [i32] + frame + [vp, vp, vp, vp]
     L.sq_lens_fold_device.argtypes = [i32, i64, i32, i32, i32, vp, vp, vp, vp, vp, vp]
     L.sq_lens_render_device.argtypes = [vp] + frame + [vp, sz, vp, vp, vp, vp, vp]
-    _lib = L
-    return L
 
 
-def check(rc):
-    N.checked(rc, lib().sq_lens_last_error)
-
-
-def build_id():
-    """sq_lens_build_id(): hash of the sources and flags the loaded library was built from (build.py: lens_source_id)."""
-    return lib().sq_lens_build_id().decode()
+# SQ_LENS_LIB_PATH: development aid, loads an experimental build of the same library (build.py: compile_lib(LIBS["lens"], out=...))
+_B = N.Binding("libsquigly_lens.so", "sq_lens_", _declare, env="SQ_LENS_LIB_PATH", client=True)
+LIB_PATH, lib, check, build_id = _B
+_RAYS, _RENDER = _B.entry("sq_lens_rays_device"), _B.entry("sq_lens_render_device")
 
 
 def work_bytes(pixels, subrays):
@@ -142,8 +125,11 @@ def _size_check(rows, h, subrays=1):
 
 
 def workspace(work_mb):
-    """work_mb of render_lens and render_lens_masked: SquiglyError unless it is a number > 0.  Returns sized(pixels, subrays): the
-    bytes of workspace the call hands the library for that many sub-rays of that many pixels -- all they need, at most work_mb MiB."""
+    """work_mb of the frame calls (None = DEFAULT_WORK_MB: the one place that default is resolved): SquiglyError unless it is a
+    number > 0.  Returns sized(pixels, subrays): the bytes of workspace the call hands the library for that many sub-rays of that
+    many pixels -- all they need, at most work_mb MiB."""
+    if work_mb is None:
+        work_mb = DEFAULT_WORK_MB
     if isinstance(work_mb, bool) or not isinstance(work_mb, (int, float)) or not work_mb > 0 or not math.isfinite(work_mb):
         raise N.SquiglyError(f"work_mb must be a number > 0, got {work_mb!r}")
     budget = int(work_mb * 2 ** 20)
@@ -154,10 +140,12 @@ def workspace(work_mb):
     return sized
 
 
-def lens_rays(ds, cam, lens, samples, subrays, w, h, shard=(None, 0, 1), r_range=None, stream=None):
-    """DeviceScene.lens_rays: the sub-rays [r_begin, r_end) of every pixel of the shard (sq_lens_rays_device) as (origins,
-    directions, seeds): float32 CUDA tensors [nb, rows, h, 3] and int64 [nb, rows, h], nb = r_end - r_begin.  With them
-    ds.raytrace(origins, directions, seeds=seeds, samples=samples // subrays) is every sub-ray's sum."""
+# ---- the three drivers of a lens frame.  entry: a library's entry point as a checked call (Binding.entry); head: the struct the
+# frame's arguments begin with, the camera or a motion (which its caller has held to its own rules first); list_slot: the entry point
+# takes a pixel list (and counts), which a dense call leaves empty. ----
+def frame_rays(entry, head, ds, lens, samples, subrays, w, h, shard, r_range, stream, list_slot=False):
+    """(origins, directions, seeds) of the sub-rays r_range of every pixel of the shard: float32 CUDA tensors [nb, rows, h, 3] and
+    int64 [nb, rows, h], nb = r_end - r_begin."""
     import torch
     S, R, r0, r1 = frame_args(lens, samples, subrays, r_range)
     sh, rows = P.shard_rows(int(w), shard)
@@ -167,22 +155,15 @@ def lens_rays(ds, cam, lens, samples, subrays, w, h, shard=(None, 0, 1), r_range
         o = torch.empty((r1 - r0, rows, h, 3), dtype=torch.float32, device=dev)
         d = torch.empty((r1 - r0, rows, h, 3), dtype=torch.float32, device=dev)
         sd = torch.empty((r1 - r0, rows, h), dtype=torch.int64, device=dev)
-    check(lib().sq_lens_rays_device(ds.device, C.byref(cam), C.byref(lens), S, R, r0, r1, int(w), int(h), sh, o.data_ptr(), d.data_ptr(),
-                                    sd.data_ptr(), P.stream_ptr(st)))
+    entry(ds.device, C.byref(head), C.byref(lens), S, R, r0, r1, int(w), int(h), sh, *((None, 0) if list_slot else ()), o.data_ptr(),
+          d.data_ptr(), sd.data_ptr(), P.stream_ptr(st))
     return o, d, sd
 
 
-def render_lens(ds, cam, lens, samples, subrays, w, h, shard=(None, 0, 1), r_range=None, sums=None, want_sum2=False, want_avg=True,
-                want_rgb=True, work_mb=DEFAULT_WORK_MB, stream=None):
-    """DeviceScene.render_lens: the sub-rays r_range (default: all) of the lens frame (sq_lens_render_device); returns
-    LensFrame(sum, sum2, avg, rgb), enqueued on `stream`.
-
-    samples, subrays: S and R of include/squigly_lens.h; R divides S and S / R samples ride on each sub-ray.  sums: the fold so far
-    -- a float32 CUDA tensor [rows, h, 3], or a pair (sum, sum2) of them -- required when r_range starts above 0, updated in place,
-    allocated otherwise.  want_sum2: also fold the squares of the sub-ray sums (implied by a pair).  avg = (1 / samples) * sum of
-    the sub-rays folded so far and rgb its tonemap (None unless wanted).  work_mb: the most workspace, in MiB, the call allocates
-    (a tensor under the stream, handed back when the call returns): the frame runs in batches of as many whole sub-rays as fit,
-    and its bits do not depend on that.  Runs under the scene's depth and sky."""
+def frame_dense(entry, says, head, ds, lens, samples, subrays, w, h, shard, r_range, sums, want_sum2, want_avg, want_rgb, work_mb, stream,
+                list_slot=False):
+    """The sub-rays r_range (default: all) of the frame for every pixel of the shard; returns LensFrame(sum, sum2, avg, rgb), enqueued
+    on `stream`.  says: the method's name in its messages.  The arguments are render_lens'."""
     import torch
     S, R, r0, r1 = frame_args(lens, samples, subrays, r_range)
     sized = workspace(work_mb)
@@ -190,10 +171,10 @@ def render_lens(ds, cam, lens, samples, subrays, w, h, shard=(None, 0, 1), r_ran
     pixels = _size_check(rows, h)
     s1, s2 = sums if isinstance(sums, (tuple, list)) else (sums, None)
     if s1 is None and (r0 > 0 or s2 is not None):
-        raise N.SquiglyError("render_lens needs the sums of the sub-rays [0, r_begin) when r_range starts above 0")
+        raise N.SquiglyError(f"{says} needs the sums of the sub-rays [0, r_begin) when r_range starts above 0")
     want_sum2 = bool(want_sum2) or s2 is not None
     if want_sum2 and s2 is None and r0 > 0:
-        raise N.SquiglyError("render_lens needs sums = (sum, sum2) to carry second moments on from r_begin > 0")
+        raise N.SquiglyError(f"{says} needs sums = (sum, sum2) to carry second moments on from r_begin > 0")
     dev, st = P.call_stream(ds.device, stream)
     for name, t in (("sums", s1), ("sums2", s2)):
         if t is not None:
@@ -207,6 +188,61 @@ def render_lens(ds, cam, lens, samples, subrays, w, h, shard=(None, 0, 1), r_ran
         avg = torch.empty((rows, h, 3), dtype=torch.float32, device=dev) if want_avg else None
         rgb = torch.empty((rows, h, 3), dtype=torch.uint8, device=dev) if want_rgb else None
         work = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
-        check(lib().sq_lens_render_device(ds._h, C.byref(cam), C.byref(lens), S, R, r0, r1, int(w), int(h), sh, work.data_ptr(), nbytes,
-                                          s1.data_ptr(), P.ptr(s2), P.ptr(avg), P.ptr(rgb), P.stream_ptr(st)))
+        entry(ds._h, C.byref(head), C.byref(lens), S, R, r0, r1, int(w), int(h), sh, *((None, 0) if list_slot else ()), work.data_ptr(),
+              nbytes, s1.data_ptr(), P.ptr(s2), *((None,) if list_slot else ()), P.ptr(avg), P.ptr(rgb), P.stream_ptr(st))
     return LensFrame(s1, s2, avg, rgb)
+
+
+def frame_listed(entry, says, head, ds, lens, samples, subrays, w, h, r_begin, r_end, sums, index, n_live, sums2, counts, shard, work_mb,
+                 out_avg, out_rgb, stream):
+    """The sub-rays [r_begin, r_end) of the frame for the first n_live pixels of the list `index`; returns (out_avg, out_rgb) as
+    given.  says: the method's name in its messages.  The arguments are render_lens_masked's."""
+    import torch
+    S, R, r0, r1 = frame_args(lens, samples, subrays, (r_begin, r_end))
+    sized = workspace(work_mb)
+    sh, rows = P.shard_rows(int(w), shard)
+    pixels = _size_check(rows, h)
+    L = _int("n_live", n_live)
+    if L < 0 or L > pixels:
+        raise N.SquiglyError(f"n_live must be between 0 and the frame's {pixels} pixels (got {L})")
+    if sums is None:
+        raise N.SquiglyError(f"{says} needs a sums tensor")
+    dev, st = P.call_stream(ds.device, stream)
+    for name, t, shape, dtype in (("sums", sums, (rows, h, 3), torch.float32), ("sums2", sums2, (rows, h, 3), torch.float32),
+                                  ("counts", counts, (rows, h), torch.int32), ("out_avg", out_avg, (rows, h, 3), torch.float32),
+                                  ("out_rgb", out_rgb, (rows, h, 3), torch.uint8)):
+        if t is not None:
+            P.tensor(name, t, shape, dtype, dev)
+    if (not isinstance(index, torch.Tensor) or index.dtype != torch.int32 or index.dim() != 1 or not index.is_contiguous()
+            or index.device != dev or index.numel() < L):
+        raise N.SquiglyError(f"index must be a contiguous torch.int32 tensor of at least n_live = {L} entries on {dev}")
+    if L == 0:
+        return out_avg, out_rgb
+    nbytes = sized(L, r1 - r0)
+    with torch.cuda.stream(st):      # the workspace is allocated (and freed) in the order of the call's stream
+        work = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+        entry(ds._h, C.byref(head), C.byref(lens), S, R, r0, r1, int(w), int(h), sh, index.data_ptr(), L, work.data_ptr(), nbytes,
+              sums.data_ptr(), P.ptr(sums2), P.ptr(counts), P.ptr(out_avg), P.ptr(out_rgb), P.stream_ptr(st))
+    return out_avg, out_rgb
+
+
+def lens_rays(ds, cam, lens, samples, subrays, w, h, shard=(None, 0, 1), r_range=None, stream=None):
+    """DeviceScene.lens_rays: the sub-rays [r_begin, r_end) of every pixel of the shard (sq_lens_rays_device) as (origins,
+    directions, seeds): float32 CUDA tensors [nb, rows, h, 3] and int64 [nb, rows, h], nb = r_end - r_begin.  With them
+    ds.raytrace(origins, directions, seeds=seeds, samples=samples // subrays) is every sub-ray's sum."""
+    return frame_rays(_RAYS, cam, ds, lens, samples, subrays, w, h, shard, r_range, stream)
+
+
+def render_lens(ds, cam, lens, samples, subrays, w, h, shard=(None, 0, 1), r_range=None, sums=None, want_sum2=False, want_avg=True,
+                want_rgb=True, work_mb=None, stream=None):
+    """DeviceScene.render_lens: the sub-rays r_range (default: all) of the lens frame (sq_lens_render_device); returns
+    LensFrame(sum, sum2, avg, rgb), enqueued on `stream`.
+
+    samples, subrays: S and R of include/squigly_lens.h; R divides S and S / R samples ride on each sub-ray.  sums: the fold so far
+    -- a float32 CUDA tensor [rows, h, 3], or a pair (sum, sum2) of them -- required when r_range starts above 0, updated in place,
+    allocated otherwise.  want_sum2: also fold the squares of the sub-ray sums (implied by a pair).  avg = (1 / samples) * sum of
+    the sub-rays folded so far and rgb its tonemap (None unless wanted).  work_mb: the most workspace, in MiB, the call allocates
+    (a tensor under the stream, handed back when the call returns; None = DEFAULT_WORK_MB): the frame runs in batches of as many
+    whole sub-rays as fit, and its bits do not depend on that.  Runs under the scene's depth and sky."""
+    return frame_dense(_RENDER, "render_lens", cam, ds, lens, samples, subrays, w, h, shard, r_range, sums, want_sum2, want_avg, want_rgb,
+                       work_mb, stream)

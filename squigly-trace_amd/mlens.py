@@ -6,48 +6,29 @@ memory, streams); the list, the rays and the fold come from the HIP kernels of c
 libsquigly_hip.so's radiance query.  There is no fallback: a missing library raises.
 """
 import ctypes as C
-import os
 
 from . import _native as N
 from . import _plumbing as P
 from . import lens as LN
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-# SQ_MLENS_LIB_PATH: development aid, loads an experimental build of the same library (build.py: build_mlens(out=...))
-LIB_PATH = os.environ.get("SQ_MLENS_LIB_PATH") or os.path.join(_HERE, "libsquigly_mlens.so")
-
 # include/squigly_mlens.h
 EXPORTED_SYMBOLS = ["sq_mlens_last_error", "sq_mlens_build_id", "sq_mlens_live_device", "sq_mlens_rays_device", "sq_mlens_fold_device",
                     "sq_mlens_render_device"]
 
-_lib = None
 
-
-def lib():
-    global _lib
-    if _lib is not None:
-        return _lib
-    N.lib()                                   # the library it is a client of, loaded from this package first
-    L = N.load(LIB_PATH)
+def _declare(L):
     vp, i32, i64, sz = C.c_void_p, C.c_int32, C.c_int64, C.c_size_t
-    L.sq_mlens_last_error.restype = C.c_char_p
-    L.sq_mlens_build_id.restype = C.c_char_p
     frame = LN.FRAME_ARGTYPES
     L.sq_mlens_live_device.argtypes = [i32, i64, i32, vp, vp, vp, vp, vp]
     L.sq_mlens_rays_device.argtypes = [i32] + frame + [vp, i64, vp, vp, vp, vp]
     L.sq_mlens_fold_device.argtypes = [i32, i64, i32, i32, i32, i32, vp, i64, vp, vp, vp, vp, vp, vp, vp]
     L.sq_mlens_render_device.argtypes = [vp] + frame + [vp, i64, vp, sz, vp, vp, vp, vp, vp, vp]
-    _lib = L
-    return L
 
 
-def check(rc):
-    N.checked(rc, lib().sq_mlens_last_error)
-
-
-def build_id():
-    """sq_mlens_build_id(): hash of the sources and flags the loaded library was built from (build.py: mlens_source_id)."""
-    return lib().sq_mlens_build_id().decode()
+# SQ_MLENS_LIB_PATH: development aid, loads an experimental build of the same library (build.py: compile_lib(LIBS["mlens"], out=...))
+_B = N.Binding("libsquigly_mlens.so", "sq_mlens_", _declare, env="SQ_MLENS_LIB_PATH", client=True)
+LIB_PATH, lib, check, build_id = _B
+_RENDER = _B.entry("sq_mlens_render_device")
 
 
 def live_pixels(ds, mask, counts, r_begin, stream=None):
@@ -84,7 +65,7 @@ def live_pixels(ds, mask, counts, r_begin, stream=None):
 
 
 def render_lens_masked(ds, cam, lens, samples, subrays, w, h, r_begin, r_end, sums, index, n_live, sums2=None, counts=None,
-                       shard=(None, 0, 1), work_mb=LN.DEFAULT_WORK_MB, out_avg=None, out_rgb=None, stream=None):
+                       shard=(None, 0, 1), work_mb=None, out_avg=None, out_rgb=None, stream=None):
     """DeviceScene.render_lens_masked: the sub-rays [r_begin, r_end) of the lens frame for the first n_live pixels of the list
     `index` (sq_mlens_render_device); returns (out_avg, out_rgb) as given.
 
@@ -92,31 +73,5 @@ def render_lens_masked(ds, cam, lens, samples, subrays, w, h, r_begin, r_end, su
     for the listed pixels only; counts are SUB-RAYS, and avg = (1 / (r_end * samples / subrays)) * sum.  index: int32 CUDA tensor,
     strictly ascending in its first n_live entries (live_pixels); n_live: an int from the host.  work_mb: as in render_lens, over
     the listed pixels.  Runs under the scene's depth and sky."""
-    import torch
-    S, R, r0, r1 = LN.frame_args(lens, samples, subrays, (r_begin, r_end))
-    sized = LN.workspace(work_mb)
-    sh, rows = P.shard_rows(int(w), shard)
-    pixels = LN._size_check(rows, h)
-    L = LN._int("n_live", n_live)
-    if L < 0 or L > pixels:
-        raise N.SquiglyError(f"n_live must be between 0 and the frame's {pixels} pixels (got {L})")
-    if sums is None:
-        raise N.SquiglyError("render_lens_masked needs a sums tensor")
-    dev, st = P.call_stream(ds.device, stream)
-    for name, t, shape, dtype in (("sums", sums, (rows, h, 3), torch.float32), ("sums2", sums2, (rows, h, 3), torch.float32),
-                                  ("counts", counts, (rows, h), torch.int32), ("out_avg", out_avg, (rows, h, 3), torch.float32),
-                                  ("out_rgb", out_rgb, (rows, h, 3), torch.uint8)):
-        if t is not None:
-            P.tensor(name, t, shape, dtype, dev)
-    if (not isinstance(index, torch.Tensor) or index.dtype != torch.int32 or index.dim() != 1 or not index.is_contiguous()
-            or index.device != dev or index.numel() < L):
-        raise N.SquiglyError(f"index must be a contiguous torch.int32 tensor of at least n_live = {L} entries on {dev}")
-    if L == 0:
-        return out_avg, out_rgb
-    nbytes = sized(L, r1 - r0)
-    with torch.cuda.stream(st):      # the workspace is allocated (and freed) in the order of the call's stream
-        work = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
-        check(lib().sq_mlens_render_device(ds._h, C.byref(cam), C.byref(lens), S, R, r0, r1, int(w), int(h), sh, index.data_ptr(), L,
-                                           work.data_ptr(), nbytes, sums.data_ptr(), P.ptr(sums2), P.ptr(counts), P.ptr(out_avg),
-                                           P.ptr(out_rgb), P.stream_ptr(st)))
-    return out_avg, out_rgb
+    return LN.frame_listed(_RENDER, "render_lens_masked", cam, ds, lens, samples, subrays, w, h, r_begin, r_end, sums, index, n_live, sums2,
+                           counts, shard, work_mb, out_avg, out_rgb, stream)

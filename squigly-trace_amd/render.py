@@ -99,6 +99,11 @@ def denoise_options(denoise):
     raise ValueError(f"denoise must be True, a sigma_l > 0 or a dict of denoise parameters, got {denoise!r}")
 
 
+def denoise_arg(denoise):
+    """denoise= of render_adaptive, render_sequence and Temporal: None (None or False: off), or denoise_options of it."""
+    return None if denoise is None or denoise is False else denoise_options(denoise)
+
+
 def render_adaptive(bih, cam, samples, dimensions, tol, eps=1.0, first=8, step=8, cast=False, device=0, rule=None, lights=None,
                     depth=None, sky=None, denoise=None, lens=None, subrays=None, motion=None, film=None):
     """The frame of render_rgb8 with adaptive sampling (DeviceScene, Adaptive): yields (done, live, spent, rgb8, counts) after
@@ -116,7 +121,7 @@ def render_adaptive(bih, cam, samples, dimensions, tol, eps=1.0, first=8, step=8
     not read, and denoise= takes its guides from motion.pose(0.5) -- a convenience, not pinned to the bit.
     film (a Film; needs denoise): the last tuple's image is developed by it on the device (libsquigly_film.so) and leaves the device
     only as bytes; None = the device's own tonemap through the debug hook, as before.  Film() gives the same bytes."""
-    from .device import Adaptive                       # torch: only the resident-scene path needs it
+    from .device import Adaptive, AdaptiveLens         # torch: only the resident-scene path needs it
     from .film import film_arg
     w, h = dimensions
     if film_arg(film) is not None and (denoise is None or denoise is False):
@@ -125,23 +130,42 @@ def render_adaptive(bih, cam, samples, dimensions, tol, eps=1.0, first=8, step=8
         raise ValueError(f"first and step must be positive, got {first}, {step}")
     if not float(tol) >= 0 or not float(eps) >= 0:
         raise ValueError(f"tol and eps must be numbers >= 0, got {tol}, {eps}")
+    n = None                                           # samples on a sub-ray: an AdaptiveLens counts in sub-rays, the caller in samples
     if lens is not None or subrays is not None or motion is not None:
-        yield from _render_adaptive_lens(bih, cam, samples, dimensions, tol, eps, first, step, cast, device, rule, lights, depth, sky,
-                                         denoise, lens, subrays, motion, film)
-        return
+        from .lens import frame_args
+        if lens is None:
+            raise ValueError("subrays and motion need a lens")
+        if motion is not None:
+            from .shutter import motion_arg
+            motion_arg(motion)
+        if cast:
+            raise ValueError("a lens frame is path-traced: cast=True is refused")
+        S, R, _, _ = frame_args(lens, samples, samples if subrays is None else subrays)
+        n = S // R
+        if int(first) % n or int(step) % n:
+            raise ValueError(f"first and step must be multiples of samples / subrays = {n}, got {first}, {step}")
     scene = _resident(bih, device, lights, depth, sky)
-    dn = None if denoise is None or denoise is False else denoise_options(denoise)      # refused before anything is uploaded
+    dn = denoise_arg(denoise)                          # refused before anything is uploaded
     with scene as ds:
-        a = Adaptive(ds, cam, samples, w, h, tol, eps=eps, first=first, step=step, cast=cast, rule=rule)
+        if n is None:
+            a = Adaptive(ds, cam, samples, w, h, tol, eps=eps, first=first, step=step, cast=cast, rule=rule)
+            done, counts = (lambda: a.done), (lambda: a.counts)
+        else:
+            a = AdaptiveLens(ds, cam, lens, S, R, w, h, tol, eps=eps, first=int(first) // n, step=int(step) // n, rule=rule, motion=motion)
+            done, counts = (lambda: a.done * n), (lambda: a.sample_counts)
         avg = None
         while not a.finished:
             avg, rgb = a.step()
-            yield a.done, a.live, a.samples_spent, rgb.cpu().numpy(), a.counts.cpu().numpy()
+            yield done(), a.live, a.samples_spent, rgb.cpu().numpy(), counts().cpu().numpy()
         if dn is not None and avg is not None:       # (a frame without pixels never steps: nothing to filter)
             from .denoise import denoise_frame, denoise_variance
-            out, _ = denoise_frame(ds, cam, w, h, avg, var=denoise_variance(a.sums, a.sums2, a.counts), **dn)
+            var = denoise_variance(a.sums, a.sums2, a.counts)
+            if n is not None:
+                # the variance of the mean of sub-ray sums is n * n times that of the pixel mean, in every branch of the variance formula
+                var = var * (1 / (n * n))                                                    # one float32 multiply
+            out, _ = denoise_frame(ds, cam if motion is None else motion.pose(0.5), w, h, avg, var=var, **dn)
             img = _developed(ds, out, film)
-            yield a.done, a.live, a.samples_spent, img, a.counts.cpu().numpy()
+            yield done(), a.live, a.samples_spent, img, counts().cpu().numpy()
 
 
 def _developed(ds, out, film):
@@ -150,40 +174,6 @@ def _developed(ds, out, film):
     if film is not None:
         return film(out).cpu().numpy()
     return N.debug_eval("tonemap", out.cpu().numpy().reshape(-1, 3), device=ds.device).reshape(tuple(out.shape))
-
-
-def _render_adaptive_lens(bih, cam, samples, dimensions, tol, eps, first, step, cast, device, rule, lights, depth, sky, denoise, lens,
-                          subrays, motion=None, film=None):
-    """render_adaptive with a lens: AdaptiveLens, its sub-ray units turned into samples for the caller."""
-    from .lens import frame_args
-    if lens is None:
-        raise ValueError("subrays and motion need a lens")
-    if motion is not None:
-        from .shutter import motion_arg
-        motion_arg(motion)
-    if cast:
-        raise ValueError("a lens frame is path-traced: cast=True is refused")
-    S, R, _, _ = frame_args(lens, samples, samples if subrays is None else subrays)
-    n = S // R
-    if int(first) % n or int(step) % n:
-        raise ValueError(f"first and step must be multiples of samples / subrays = {n}, got {first}, {step}")
-    scene = _resident(bih, device, lights, depth, sky)
-    dn = None if denoise is None or denoise is False else denoise_options(denoise)      # refused before anything is uploaded
-    from .device import AdaptiveLens
-    w, h = dimensions
-    with scene as ds:
-        a = AdaptiveLens(ds, cam, lens, S, R, w, h, tol, eps=eps, first=int(first) // n, step=int(step) // n, rule=rule, motion=motion)
-        avg = None
-        while not a.finished:
-            avg, rgb = a.step()
-            yield a.done * n, a.live, a.samples_spent, rgb.cpu().numpy(), a.sample_counts.cpu().numpy()
-        if dn is not None and avg is not None:
-            from .denoise import denoise_frame, denoise_variance
-            # the variance of the mean of sub-ray sums is n * n times that of the pixel mean, in every branch of the variance formula
-            var = denoise_variance(a.sums, a.sums2, a.counts) * (1 / (n * n))            # one float32 multiply
-            out, _ = denoise_frame(ds, cam if motion is None else motion.pose(0.5), w, h, avg, var=var, **dn)
-            img = _developed(ds, out, film)
-            yield a.done * n, a.live, a.samples_spent, img, a.sample_counts.cpu().numpy()
 
 
 def render_views_rgb8(bih, cams, samples, dimensions, cast=False, device=0, lights=None, depth=None, sky=None) -> np.ndarray:
@@ -247,7 +237,7 @@ def render_sequence(bih, cams, spp, dimensions, temporal=True, denoise=None, dev
     _temporal_args(spp, period, alpha_min, max_history)
     from .film import film_arg
     film_arg(film)
-    dn = None if denoise is None or denoise is False else denoise_options(denoise)      # refused before anything is uploaded
+    dn = denoise_arg(denoise)                          # refused before anything is uploaded
     scene = _resident(bih, device, None, depth, sky)
     w, h = dimensions
     with scene as ds:

@@ -7,13 +7,9 @@ raises.
 """
 import collections
 import ctypes as C
-import os
 
 from . import _native as N
 from . import _plumbing as P
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(_HERE, "libsquigly_temporal.so")
 
 # include/squigly_temporal.h
 EXPORTED_SYMBOLS = ["sq_temporal_last_error", "sq_temporal_build_id", "sq_temporal_history_bytes", "sq_temporal_project",
@@ -32,34 +28,17 @@ class Params(C.Structure):
     _fields_ = [("alpha_min", C.c_float), ("max_history", C.c_int32), ("sigma_p", C.c_float), ("cos_n", C.c_float)]
 
 
-_lib = None
-
-
-def lib():
-    global _lib
-    if _lib is not None:
-        return _lib
-    L = N.load(LIB_PATH)
+def _declare(L):
     vp, i32 = C.c_void_p, C.c_int32
-    L.sq_temporal_last_error.restype = C.c_char_p
-    L.sq_temporal_build_id.restype = C.c_char_p
     L.sq_temporal_history_bytes.argtypes = [i32, i32]
     L.sq_temporal_history_bytes.restype = C.c_size_t
     L.sq_temporal_project.argtypes = [C.POINTER(N.Camera), i32, i32, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.sq_temporal_accumulate_device.argtypes = [i32, i32, i32, vp, vp, vp, vp, vp, vp, C.POINTER(N.Camera), vp, C.POINTER(Params),
                                                 vp, vp, vp, vp, vp]
     L.sq_temporal_unpack_device.argtypes = [i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]
-    _lib = L
-    return L
 
 
-def check(rc):
-    N.checked(rc, lib().sq_temporal_last_error)
-
-
-def build_id():
-    """sq_temporal_build_id(): hash of the sources and flags the loaded library was built from (build.py: temporal_source_id)."""
-    return lib().sq_temporal_build_id().decode()
+LIB_PATH, lib, check, build_id = N.Binding("libsquigly_temporal.so", "sq_temporal_", _declare)
 
 
 def history_bytes(rows, cols):
@@ -255,7 +234,7 @@ class Temporal:
         import torch
         from . import device as D
         from .denoise import default_sigma_p, make_params as denoise_params
-        from .render import denoise_options
+        from .render import denoise_arg
         _temporal_args(spp, period, alpha_min, max_history)
         from .film import film_arg
         self.film = film_arg(film)
@@ -267,7 +246,7 @@ class Temporal:
         self.params = dict(alpha_min=float(alpha_min), max_history=int(max_history), cos_n=float(cos_n),
                            sigma_p=default_sigma_p(ds.bih.bounds) if sigma_p is None else float(sigma_p))
         make_params(**self.params)
-        self.denoise = None if denoise is None or denoise is False else denoise_options(denoise)
+        self.denoise = denoise_arg(denoise)
         if self.denoise is not None:
             self.denoise.setdefault("sigma_p", self.params["sigma_p"])
             denoise_params(**self.denoise)                       # refused before any device work
@@ -304,7 +283,7 @@ class Temporal:
     def step(self, cam, stream=None):
         """Render the next frame under `cam` and accumulate it; returns (avg, var, length, rgb).  Enqueued on `stream`."""
         import torch
-        from .denoise import denoise, denoise_variance
+        from .denoise import demodulated, denoise, denoise_variance, remodulated
         self._frame._unchanged()
         ds, w, h = self.ds, self.w, self.h
         _, st = P.call_stream(self._dev, stream)
@@ -317,21 +296,16 @@ class Temporal:
             noisy = self._sums / float(self.spp)
             var = denoise_variance(self._sums, self._sums2, self._counts, stream=st)
             g = ds.guides(cam, w, h, stream=st)
-            x, ok = noisy, None
-            if self.demodulate:                                   # denoise_frame's demodulation, operation for operation
-                ok = ((g.tri >= 0) & (g.surf > 0).all(-1))[..., None]
-                x = torch.where(ok, (noisy - g.emit) / torch.where(ok, g.surf, torch.ones_like(g.surf)), noisy)
-                ls = (0.25 * g.surf[..., 0] + 0.5 * g.surf[..., 1]) + 0.25 * g.surf[..., 2]
-                scale = torch.where(ok[..., 0], ls * ls, torch.ones_like(ls))
-                var = var / scale
+            x, how = noisy, None
+            if self.demodulate:                                   # denoise_frame's demodulation
+                x, var, how = demodulated(g, noisy, var)
             nxt = 1 if self._cur == 0 else 0
             out, out_var, length = accumulate(x, var, g, self._cam, self.history, self._blocks[nxt], alpha=frame_alpha(ds, g.tri),
                                               stream=st, **self.params)
             if self.denoise is not None:
                 out, out_var = denoise(out, g.tri, g.normal, g.point, var=out_var, stream=st, **self.denoise)
-            if ok is not None:
-                out = torch.where(ok, out * g.surf + g.emit, out)
-                out_var = out_var * scale
+            if how is not None:
+                out, out_var = remodulated(g, out, out_var, how)
             rgb = tonemap(out) if self.film is None else self.film(out, stream=st)
         self._cur, self._cam, self.noisy = nxt, N.Camera.from_buffer_copy(bytes(cam)), noisy
         self.frames += 1

@@ -2,7 +2,6 @@
 pixels, and the quality of the specified filter -- the numpy restatement -- on the project's own scene."""
 import ctypes as C
 import importlib
-import importlib.util
 import os
 import re
 import subprocess
@@ -11,6 +10,7 @@ import numpy as np
 import pytest
 
 import denoise_restatement as R
+import library_surface as LS
 from denoise_room import room
 from render_options import THREADS
 
@@ -26,29 +26,9 @@ def dn(sqt):
     return mod
 
 
-def build_module():
-    spec = importlib.util.spec_from_file_location("sq_build_for_denoise_test", os.path.join(ROOT, "squigly-trace_amd", "build.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-def header_functions():
-    text = open(os.path.join(ROOT, "include", "squigly_denoise.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return set(re.findall(r"\b(sq_denoise_[a-z0-9_]+)\s*\(", text))
-
-
 def test_header_functions_are_exported(dn):
-    declared = header_functions()
-    assert declared == set(dn.EXPORTED_SYMBOLS)
+    declared = LS.check_exports(dn, "squigly_denoise.h", "sq_denoise_")      # (and nothing of the other libraries' leaks out of this one)
     assert {"sq_denoise_device", "sq_denoise_variance_device", "sq_denoise_workspace_bytes", "sq_denoise_last_error"} <= declared
-    nm = subprocess.check_output(["nm", "-D", "--defined-only", dn.LIB_PATH]).decode()
-    exported = set(re.findall(r" T (sq_[a-z0-9_]+)", nm))
-    assert declared <= exported, declared - exported
-    assert exported <= declared, exported - declared           # and nothing of the other library's leaks out of this one
-    for name in declared:
-        assert getattr(dn.lib(), name) is not None
 
 
 def test_main_library_did_not_gain_the_denoiser(sqt):
@@ -60,21 +40,12 @@ def test_main_library_did_not_gain_the_denoiser(sqt):
 
 
 def test_ids_are_separate(dn, sqt, tmp_path):
-    b = build_module()
-    assert "sq_denoise.hip" not in b.SOURCES + b.HEADERS and "../../include/squigly_denoise.h" not in b.HEADERS
-    assert dn.build_id() == b.denoise_source_id() != b.source_id()
+    b = LS.build_module()
+    assert "sq_denoise.hip" not in LS.files(b, "main") and "../../include/squigly_denoise.h" not in LS.files(b, "main")
+    assert dn.build_id() == b.lib_source_id(b.LIBS["denoise"]) != b.source_id()
     assert sqt.build_id() == b.source_id()
-    # source_id() reads only its own list, denoise_source_id() only the other: moving the lists to a copy of csrc/ in which the
-    # filter's source differs changes the second id and not the first
-    import shutil
-    shutil.copytree(os.path.join(ROOT, "squigly-trace_amd", "csrc"), tmp_path / "a" / "b" / "csrc")
-    shutil.copytree(os.path.join(ROOT, "include"), tmp_path / "a" / "include")
-    before = b.source_id(), b.denoise_source_id()
-    b.CSRC = str(tmp_path / "a" / "b" / "csrc")
-    assert (b.source_id(), b.denoise_source_id()) == before
-    with open(os.path.join(b.CSRC, "sq_denoise.hip"), "a") as fh:
-        fh.write("// changed\n")
-    assert b.source_id() == before[0] and b.denoise_source_id() != before[1]
+    # every id reads only its own lists: in a copy of csrc/ in which the filter's source differs, the filter's id moves and no other
+    LS.check_ids(b, "denoise", dn, sqt, tmp_path, [("sq_denoise.hip", {"denoise"}), ("../../include/squigly_denoise.h", {"denoise"})])
 
 
 def test_workspace_bytes_is_monotone(dn):

@@ -3,7 +3,6 @@ refusals, and the specified arithmetic -- the numpy restatement -- held against 
 csrc/sq_film_pixel.h (the text the kernels compile), built plainly and under the sanitizers."""
 import ctypes as C
 import importlib
-import importlib.util
 import os
 import re
 import shutil
@@ -13,6 +12,7 @@ import numpy as np
 import pytest
 
 import film_restatement as R
+import library_surface as LS
 from bitcmp import same
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -28,56 +28,22 @@ def fm(sqt):
     return mod
 
 
-def build_module():
-    spec = importlib.util.spec_from_file_location("sq_build_for_film_test", os.path.join(ROOT, "squigly-trace_amd", "build.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-def header_functions():
-    text = open(os.path.join(ROOT, "include", "squigly_film.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return set(re.findall(r"\b(sq_film_[a-z0-9_]+)\s*\(", text))
-
-
 def test_header_functions_are_exported(fm):
-    declared = header_functions()
-    assert declared == set(fm.EXPORTED_SYMBOLS)
+    declared = LS.check_exports(fm, "squigly_film.h", "sq_film_")            # (and nothing of another library's leaks out of this one)
     assert {"sq_film_histogram_device", "sq_film_expose_device", "sq_film_develop_device", "sq_film_build_id", "sq_film_last_error"} == declared
-    nm = subprocess.check_output(["nm", "-D", "--defined-only", fm.LIB_PATH]).decode()
-    exported = set(re.findall(r" T (sq_[a-z0-9_]+)", nm))
-    assert exported == declared, exported ^ declared           # and nothing of another library's leaks out of this one
-    for name in declared:
-        assert getattr(fm.lib(), name) is not None
-    needed = subprocess.check_output(["readelf", "-d", fm.LIB_PATH]).decode()
-    assert "libsquigly_hip" not in needed                      # not a client of the main library
+    LS.check_client(fm.LIB_PATH, False)                        # not a client of the main library
 
 
 def test_seven_ids_are_distinct_and_an_edit_moves_only_the_films(fm, sqt, tmp_path):
-    b = build_module()
-    ids = lambda: (b.source_id(), b.denoise_source_id(), b.lens_source_id(), b.mlens_source_id(), b.shutter_source_id(),  # noqa: E731
-                   b.temporal_source_id(), b.film_source_id())
-    before = ids()
-    assert len(set(before)) == 7
-    assert fm.build_id() == before[6] and sqt.build_id() == before[0]
-    assert not b.film_stale()
-    others = b.SOURCES + b.HEADERS + b.DENOISE_HEADERS + b.SHUTTER_HEADERS + b.TEMPORAL_HEADERS
+    b = LS.build_module()
+    assert list(b.LIBS) == ["denoise", "main", "lens", "mlens", "shutter", "temporal", "film"]     # seven, in the order they are built
+    others = LS.files(b, "main") + b.LIBS["denoise"]["headers"] + b.LIBS["shutter"]["headers"] + b.LIBS["temporal"]["headers"]
     assert "sq_film.hip" not in others and "sq_film_pixel.h" not in others and "../../include/squigly_film.h" not in others
-    assert b.FILM["salt"] == b"film\0" and b.FILM["macro"] == "SQ_FILM_BUILD_ID" and b.FILM["link"] == []
-    shutil.copytree(os.path.join(ROOT, "squigly-trace_amd", "csrc"), tmp_path / "a" / "b" / "csrc")
-    shutil.copytree(os.path.join(ROOT, "include"), tmp_path / "a" / "include")
-    b.CSRC = str(tmp_path / "a" / "b" / "csrc")
-    assert ids() == before
-    with open(os.path.join(b.CSRC, "sq_film.hip"), "a") as fh:
-        fh.write("// changed\n")
-    after = ids()
-    assert after[:6] == before[:6] and after[6] != before[6]
-    with open(os.path.join(b.CSRC, "sq_film_pixel.h"), "a") as fh:
-        fh.write("// changed\n")
-    assert ids()[:6] == before[:6] and ids()[6] != after[6]
+    film = b.LIBS["film"]
+    assert film["salt"] == b"film\0" and film["macro"] == "SQ_FILM_BUILD_ID" and film["link"] == []
+    after = LS.check_ids(b, "film", fm, sqt, tmp_path, [("sq_film.hip", {"film"}), ("sq_film_pixel.h", {"film"})])
     # a variant build (tools/gpu_film.py's folding forms) has an id of its own
-    assert b.film_source_id(["-DSQ_FILM_HIST_FOLD=0"]) != ids()[6]
+    assert b.lib_source_id(film, ["-DSQ_FILM_HIST_FOLD=0"]) != after["film"]
 
 
 # ---- refusals: nothing here reaches a device, the pointers are numbers that are never followed ----

@@ -3,7 +3,6 @@ meet, what its inputs cover, and the surface of libsquigly_lens.so -- the batch 
 of its own), the header, the exports, the ids, every refusal that needs no device, the Python layer's refusals and the CLI's flags."""
 import ctypes as C
 import importlib
-import importlib.util
 import os
 import re
 import subprocess
@@ -12,6 +11,7 @@ import numpy as np
 import pytest
 
 import lens_restatement as LR
+import library_surface as LS
 from render_options import THREADS
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -34,13 +34,6 @@ def lens(sqt):
 @pytest.fixture(scope="module")
 def room():
     return LR.room()
-
-
-def build_module():
-    spec = importlib.util.spec_from_file_location("sq_build_for_lens_test", os.path.join(ROOT, "squigly-trace_amd", "build.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
 
 
 # ---- (a) no jitter, no aperture: makeRay's ray and the frame's seeds ----
@@ -161,21 +154,10 @@ def header_text():
     return open(os.path.join(ROOT, "include", "squigly_lens.h")).read()
 
 
-def header_functions():
-    text = re.sub(r"/\*.*?\*/", "", header_text(), flags=re.S)
-    return set(re.findall(r"\b(sq_lens_[a-z0-9_]+)\s*\(", text))
-
-
 def test_header_functions_are_exported(lens):
-    declared = header_functions()
-    assert declared == set(lens.EXPORTED_SYMBOLS)
+    declared = LS.check_exports(lens, "squigly_lens.h", "sq_lens_")          # (and nothing of the other libraries' leaks out of this one)
     assert {"sq_lens_rays_device", "sq_lens_fold_device", "sq_lens_render_device", "sq_lens_plan", "sq_lens_work_bytes",
             "sq_lens_last_error", "sq_lens_build_id"} == declared
-    nm = subprocess.check_output(["nm", "-D", "--defined-only", lens.LIB_PATH]).decode()
-    exported = set(re.findall(r" T (sq_[a-z0-9_]+)", nm))
-    assert exported == declared, exported ^ declared          # and nothing of the other library's leaks out of this one
-    for name in declared:
-        assert getattr(lens.lib(), name) is not None
 
 
 def test_header_carries_the_contract():
@@ -204,31 +186,17 @@ def test_main_library_did_not_gain_the_lens(sqt, lens):
     assert not [s for s in sqt.EXPORTED_SYMBOLS if "lens" in s]
     nm = subprocess.check_output(["nm", "-D", "--defined-only", sqt.LIB_PATH]).decode()
     assert "sq_lens" not in nm
-    b = build_module()
+    b = LS.build_module()
     mine = {"sq_lens.hip", "sq_lens_plan.h", "../../include/squigly_lens.h"}
-    assert not mine & set(b.SOURCES + b.HEADERS + b.DENOISE_SOURCES + b.DENOISE_HEADERS)
-    assert mine <= set(b.LENS_SOURCES + b.LENS_HEADERS)
-    needed = subprocess.check_output(["readelf", "-d", lens.LIB_PATH]).decode()
-    assert "libsquigly_hip.so" in needed and "$ORIGIN" in needed                # a client of the main library, found beside it
+    assert not mine & set(LS.files(b, "main", "denoise"))
+    assert mine <= set(LS.files(b, "lens"))
+    LS.check_client(lens.LIB_PATH, True)                                        # a client of the main library, found beside it
 
 
 def test_ids_are_separate(lens, sqt, tmp_path):
-    b = build_module()
-    assert lens.build_id() == b.lens_source_id() and not b.lens_stale()
-    assert len({b.lens_source_id(), b.source_id(), b.denoise_source_id()}) == 3
-    assert sqt.build_id() == b.source_id()
-    import shutil
-    shutil.copytree(os.path.join(ROOT, "squigly-trace_amd", "csrc"), tmp_path / "a" / "b" / "csrc")
-    shutil.copytree(os.path.join(ROOT, "include"), tmp_path / "a" / "include")
-    before = b.source_id(), b.denoise_source_id(), b.lens_source_id()
-    b.CSRC = str(tmp_path / "a" / "b" / "csrc")
-    assert (b.source_id(), b.denoise_source_id(), b.lens_source_id()) == before
-    for name in ("sq_lens.hip", "sq_lens_plan.h"):
-        with open(os.path.join(b.CSRC, name), "a") as fh:
-            fh.write("// changed\n")
-        after = b.source_id(), b.denoise_source_id(), b.lens_source_id()
-        assert after[:2] == before[:2] and after[2] != before[2]
-        before = after
+    # the main library's and the denoiser's ids stay; the planner is text the two later lens libraries share, and their ids follow it
+    LS.check_ids(LS.build_module(), "lens", lens, sqt, tmp_path,
+                 [("sq_lens.hip", {"lens"}), ("sq_lens_plan.h", {"lens", "mlens", "shutter"})])
 
 
 # ---- the planner ----

@@ -4,7 +4,6 @@ no device -- the Python layer's refusals, render_adaptive(lens=None) as the code
 pins from being vacuous."""
 import ctypes as C
 import importlib
-import importlib.util
 import os
 import re
 import subprocess
@@ -13,6 +12,7 @@ import numpy as np
 import pytest
 
 import lens_restatement as LR
+import library_surface as LS
 import mlens_restatement as MR
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -32,13 +32,6 @@ def mlens(sqt):
 def lens(sqt):
     mod = importlib.import_module("squigly-trace_amd.lens")
     mod.lib()
-    return mod
-
-
-def build_module():
-    spec = importlib.util.spec_from_file_location("sq_build_for_mlens_test", os.path.join(ROOT, "squigly-trace_amd", "build.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
     return mod
 
 
@@ -71,16 +64,9 @@ def test_header_carries_the_contract_and_the_pins():
 
 
 def test_header_functions_are_exported(mlens):
-    text = re.sub(r"/\*.*?\*/", "", header_text(), flags=re.S)
-    declared = set(re.findall(r"\b(sq_mlens_[a-z0-9_]+)\s*\(", text))
-    assert declared == set(mlens.EXPORTED_SYMBOLS)
+    declared = LS.check_exports(mlens, "squigly_mlens.h", "sq_mlens_")       # (no planner export, nothing of the other libraries')
     assert declared == {"sq_mlens_last_error", "sq_mlens_build_id", "sq_mlens_live_device", "sq_mlens_rays_device", "sq_mlens_fold_device",
                         "sq_mlens_render_device"}
-    nm = subprocess.check_output(["nm", "-D", "--defined-only", mlens.LIB_PATH]).decode()
-    exported = set(re.findall(r" T (sq_[a-z0-9_]+)", nm))
-    assert exported == declared, exported ^ declared          # no planner export, nothing of the other libraries'
-    for name in declared:
-        assert getattr(mlens.lib(), name) is not None
 
 
 def test_the_other_libraries_did_not_gain_it(sqt, lens, mlens):
@@ -89,37 +75,24 @@ def test_the_other_libraries_did_not_gain_it(sqt, lens, mlens):
     assert not [s for s in sqt.EXPORTED_SYMBOLS + lens.EXPORTED_SYMBOLS if "mlens" in s]
     for path in (sqt.LIB_PATH, lens.LIB_PATH):
         assert "sq_mlens" not in subprocess.check_output(["nm", "-D", "--defined-only", path]).decode(), path
-    b = build_module()
+    b = LS.build_module()
     mine = {"sq_mlens.hip", "../../include/squigly_mlens.h"}
-    assert not mine & set(b.SOURCES + b.HEADERS + b.DENOISE_SOURCES + b.DENOISE_HEADERS + b.LENS_SOURCES + b.LENS_HEADERS)
-    assert mine | {"sq_lens_plan.h", "sq_lens_ray.h", "../../include/squigly_lens.h"} <= set(b.MLENS_SOURCES + b.MLENS_HEADERS)
-    assert "sq_lens_ray.h" in b.LENS_HEADERS                     # the contract is written once, and both ids follow it
-    assert "sq_lens_frame.h" in b.LENS_HEADERS and "sq_lens_frame.h" in b.MLENS_HEADERS      # ... and so are the kernels and the batch loop
-    assert "sq_lens_frame.h" not in b.SOURCES + b.HEADERS + b.DENOISE_SOURCES + b.DENOISE_HEADERS
-    assert b.MLENS["link"] == b.LENS["link"] and b.MLENS["salt"] not in (b.LENS["salt"], b.MAIN["salt"], b.DENOISE["salt"])
-    needed = subprocess.check_output(["readelf", "-d", mlens.LIB_PATH]).decode()
-    assert "libsquigly_hip.so" in needed and "$ORIGIN" in needed and "libsquigly_lens" not in needed
+    assert not mine & set(LS.files(b, "main", "denoise", "lens"))
+    assert mine | {"sq_lens_plan.h", "sq_lens_ray.h", "../../include/squigly_lens.h"} <= set(LS.files(b, "mlens"))
+    assert "sq_lens_ray.h" in b.LIBS["lens"]["headers"]          # the contract is written once, and both ids follow it
+    assert "sq_lens_frame.h" in b.LIBS["lens"]["headers"] and "sq_lens_frame.h" in b.LIBS["mlens"]["headers"]      # ... and so are the kernels and the batch loop
+    assert "sq_lens_frame.h" not in LS.files(b, "main", "denoise")
+    assert b.LIBS["mlens"]["link"] == b.LIBS["lens"]["link"]
+    assert b.LIBS["mlens"]["salt"] not in (b.LIBS["lens"]["salt"], b.LIBS["main"]["salt"], b.LIBS["denoise"]["salt"])
+    LS.check_client(mlens.LIB_PATH, True, never=("libsquigly_lens",))
 
 
 def test_ids_are_separate(lens, mlens, sqt, tmp_path):
-    b = build_module()
-    assert mlens.build_id() == b.mlens_source_id() and not b.mlens_stale()
-    assert len({b.mlens_source_id(), b.lens_source_id(), b.source_id(), b.denoise_source_id()}) == 4
-    assert sqt.build_id() == b.source_id() and lens.build_id() == b.lens_source_id()
-    import shutil
-    shutil.copytree(os.path.join(ROOT, "squigly-trace_amd", "csrc"), tmp_path / "a" / "b" / "csrc")
-    shutil.copytree(os.path.join(ROOT, "include"), tmp_path / "a" / "include")
-    ids = lambda: (b.source_id(), b.denoise_source_id(), b.lens_source_id(), b.mlens_source_id())  # noqa: E731
-    before = ids()
-    b.CSRC = str(tmp_path / "a" / "b" / "csrc")
-    assert ids() == before
-    for name, moves in (("sq_mlens.hip", (3,)), ("../../include/squigly_mlens.h", (3,)), ("sq_lens_ray.h", (2, 3)), ("sq_lens_plan.h", (2, 3)),
-                        ("sq_lens_frame.h", (2, 3))):
-        with open(os.path.join(b.CSRC, name), "a") as fh:
-            fh.write("// changed\n")
-        after = ids()
-        assert [i for i in range(4) if after[i] != before[i]] == list(moves), name
-        before = after
+    b = LS.build_module()
+    assert lens.build_id() == b.lib_source_id(b.LIBS["lens"])
+    own, shared = {"mlens"}, {"lens", "mlens", "shutter"}        # (the shutter library reads the lens libraries' shared text too)
+    LS.check_ids(b, "mlens", mlens, sqt, tmp_path, [("sq_mlens.hip", own), ("../../include/squigly_mlens.h", own), ("sq_lens_ray.h", shared),
+                                                    ("sq_lens_plan.h", shared), ("sq_lens_frame.h", shared)])
 
 
 # ---- refusals: nothing here reaches a device, the buffer pointers are numbers that are never followed ----

@@ -15,4 +15,4 @@ def test_the_file_holds_the_cases_of_both_groups_and_no_others():
 
 
 def test_cpu_refusals_are_the_recorded_ones(sqt):
-    assert PR.check("cpu", PR.Env(sqt)) == len(PR.CASES["cpu"]) > 150
+    assert PR.check("cpu", PR.Env(sqt)) == len(PR.CASES["cpu"]) > 745

@@ -4,7 +4,6 @@ sq_shutter_pose against the restatement (also under the sanitizers, as a program
 the Python layer's refusals and the CLI's flags."""
 import ctypes as C
 import importlib
-import importlib.util
 import os
 import re
 import subprocess
@@ -13,6 +12,7 @@ import numpy as np
 import pytest
 
 import lens_restatement as LR
+import library_surface as LS
 import shutter_restatement as SH
 from bitcmp import nan_eq
 
@@ -45,13 +45,6 @@ def lens(sqt):
 def mlens(sqt):
     mod = importlib.import_module("squigly-trace_amd.mlens")
     mod.lib()
-    return mod
-
-
-def build_module():
-    spec = importlib.util.spec_from_file_location("sq_build_for_shutter_test", os.path.join(ROOT, "squigly-trace_amd", "build.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
     return mod
 
 
@@ -138,23 +131,9 @@ def test_header_carries_the_contract():
         assert word in text, word
 
 
-def declared_in(header, prefix):
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", header)).read(), flags=re.S)
-    return set(re.findall(r"\b(%s[a-z0-9_]+)\s*\(" % prefix, text))
-
-
-def exported_by(path):
-    nm = subprocess.check_output(["nm", "-D", "--defined-only", path]).decode()
-    return set(re.findall(r" T (sq_[a-z0-9_]+)", nm))
-
-
 def test_header_functions_are_exported(shutter):
-    declared = declared_in("squigly_shutter.h", "sq_shutter_")
-    assert declared == set(shutter.EXPORTED_SYMBOLS)
+    declared = LS.check_exports(shutter, "squigly_shutter.h", "sq_shutter_")   # (no planner, fold or list export: those stay the lens libraries')
     assert declared == {"sq_shutter_last_error", "sq_shutter_build_id", "sq_shutter_pose", "sq_shutter_rays_device", "sq_shutter_render_device"}
-    assert exported_by(shutter.LIB_PATH) == declared           # no planner, fold or list export: those stay the lens libraries'
-    for name in declared:
-        assert getattr(shutter.lib(), name) is not None
 
 
 def test_the_other_libraries_did_not_gain_it(sqt, lens, mlens, shutter):
@@ -165,42 +144,29 @@ def test_the_other_libraries_did_not_gain_it(sqt, lens, mlens, shutter):
     for path in (sqt.LIB_PATH, denoise.LIB_PATH, lens.LIB_PATH, mlens.LIB_PATH):
         assert "sq_shutter" not in subprocess.check_output(["nm", "-D", "--defined-only", path]).decode(), path
     # the two lens libraries export what they exported, and declare what they declared
-    assert exported_by(lens.LIB_PATH) == set(lens.EXPORTED_SYMBOLS) == declared_in("squigly_lens.h", "sq_lens_") == {
+    assert LS.exported_by(lens.LIB_PATH) == set(lens.EXPORTED_SYMBOLS) == LS.declared_in("squigly_lens.h", "sq_lens_") == {
         "sq_lens_rays_device", "sq_lens_fold_device", "sq_lens_render_device", "sq_lens_plan", "sq_lens_work_bytes", "sq_lens_last_error",
         "sq_lens_build_id"}
-    assert exported_by(mlens.LIB_PATH) == set(mlens.EXPORTED_SYMBOLS) == declared_in("squigly_mlens.h", "sq_mlens_") == {
+    assert LS.exported_by(mlens.LIB_PATH) == set(mlens.EXPORTED_SYMBOLS) == LS.declared_in("squigly_mlens.h", "sq_mlens_") == {
         "sq_mlens_last_error", "sq_mlens_build_id", "sq_mlens_live_device", "sq_mlens_rays_device", "sq_mlens_fold_device",
         "sq_mlens_render_device"}
-    b = build_module()
+    b = LS.build_module()
     mine = {"sq_shutter.hip", "sq_shutter_pose.h", "../../include/squigly_shutter.h"}
-    others = b.SOURCES + b.HEADERS + b.DENOISE_SOURCES + b.DENOISE_HEADERS + b.LENS_SOURCES + b.LENS_HEADERS + b.MLENS_SOURCES + b.MLENS_HEADERS
-    assert not mine & set(others)
-    assert mine | {"sq_lens_plan.h", "sq_lens_ray.h", "sq_lens_frame.h", "../../include/squigly_lens.h"} <= set(b.SHUTTER_SOURCES + b.SHUTTER_HEADERS)
-    assert b.SHUTTER["link"] == b.LENS["link"] and b.SHUTTER["salt"] == b"shutter\0" and b.SHUTTER["macro"] == "SQ_SHUTTER_BUILD_ID"
-    assert b.SHUTTER["salt"] not in (b.LENS["salt"], b.MLENS["salt"], b.MAIN["salt"], b.DENOISE["salt"])
-    needed = subprocess.check_output(["readelf", "-d", shutter.LIB_PATH]).decode()
-    assert "libsquigly_hip.so" in needed and "$ORIGIN" in needed and "libsquigly_lens" not in needed and "libsquigly_mlens" not in needed
+    assert not mine & set(LS.files(b, "main", "denoise", "lens", "mlens"))
+    assert mine | {"sq_lens_plan.h", "sq_lens_ray.h", "sq_lens_frame.h", "../../include/squigly_lens.h"} <= set(LS.files(b, "shutter"))
+    sh = b.LIBS["shutter"]
+    assert sh["link"] == b.LIBS["lens"]["link"] and sh["salt"] == b"shutter\0" and sh["macro"] == "SQ_SHUTTER_BUILD_ID"
+    assert sh["salt"] not in [b.LIBS[n]["salt"] for n in ("lens", "mlens", "main", "denoise")]
+    LS.check_client(shutter.LIB_PATH, True, never=("libsquigly_lens", "libsquigly_mlens"))
 
 
 def test_ids_are_separate(lens, mlens, shutter, sqt, tmp_path):
-    b = build_module()
-    assert shutter.build_id() == b.shutter_source_id() and not b.shutter_stale()
-    assert len({b.shutter_source_id(), b.mlens_source_id(), b.lens_source_id(), b.source_id(), b.denoise_source_id()}) == 5
-    assert sqt.build_id() == b.source_id() and lens.build_id() == b.lens_source_id() and mlens.build_id() == b.mlens_source_id()
-    import shutil
-    shutil.copytree(os.path.join(ROOT, "squigly-trace_amd", "csrc"), tmp_path / "a" / "b" / "csrc")
-    shutil.copytree(os.path.join(ROOT, "include"), tmp_path / "a" / "include")
-    ids = lambda: (b.source_id(), b.denoise_source_id(), b.lens_source_id(), b.mlens_source_id(), b.shutter_source_id())  # noqa: E731
-    before = ids()
-    b.CSRC = str(tmp_path / "a" / "b" / "csrc")
-    assert ids() == before
-    for name, moves in (("sq_shutter.hip", (4,)), ("sq_shutter_pose.h", (4,)), ("../../include/squigly_shutter.h", (4,)),
-                        ("sq_lens_ray.h", (2, 3, 4)), ("sq_lens_frame.h", (2, 3, 4)), ("../../include/squigly_mlens.h", (3,))):
-        with open(os.path.join(b.CSRC, name), "a") as fh:
-            fh.write("// changed\n")
-        after = ids()
-        assert [i for i in range(5) if after[i] != before[i]] == list(moves), name
-        before = after
+    b = LS.build_module()
+    assert lens.build_id() == b.lib_source_id(b.LIBS["lens"]) and mlens.build_id() == b.lib_source_id(b.LIBS["mlens"])
+    own, shared = {"shutter"}, {"lens", "mlens", "shutter"}
+    LS.check_ids(b, "shutter", shutter, sqt, tmp_path,
+                 [("sq_shutter.hip", own), ("sq_shutter_pose.h", own), ("../../include/squigly_shutter.h", own), ("sq_lens_ray.h", shared),
+                  ("sq_lens_frame.h", shared), ("../../include/squigly_mlens.h", {"mlens"})])
 
 
 # ---- (c) sq_shutter_pose ----

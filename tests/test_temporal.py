@@ -3,7 +3,6 @@ against the numpy restatement and under the sanitizers, and what the specified a
 two-plane synthetic frames and on the project's own scene rendered by the oracle."""
 import ctypes as C
 import importlib
-import importlib.util
 import os
 import re
 import shutil
@@ -13,6 +12,7 @@ import numpy as np
 import pytest
 
 import denoise_restatement as DR
+import library_surface as LS
 import temporal_restatement as R
 import temporal_room as TR
 from bitcmp import bits, same
@@ -30,55 +30,21 @@ def tp(sqt):
     return mod
 
 
-def build_module():
-    spec = importlib.util.spec_from_file_location("sq_build_for_temporal_test", os.path.join(ROOT, "squigly-trace_amd", "build.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-def header_functions():
-    text = open(os.path.join(ROOT, "include", "squigly_temporal.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return set(re.findall(r"\b(sq_temporal_[a-z0-9_]+)\s*\(", text))
-
-
 def test_header_functions_are_exported(tp):
-    declared = header_functions()
-    assert declared == set(tp.EXPORTED_SYMBOLS)
+    declared = LS.check_exports(tp, "squigly_temporal.h", "sq_temporal_")    # (and nothing of another library's leaks out of this one)
     assert {"sq_temporal_accumulate_device", "sq_temporal_unpack_device", "sq_temporal_project", "sq_temporal_history_bytes"} <= declared
-    nm = subprocess.check_output(["nm", "-D", "--defined-only", tp.LIB_PATH]).decode()
-    exported = set(re.findall(r" T (sq_[a-z0-9_]+)", nm))
-    assert declared <= exported, declared - exported
-    assert exported <= declared, exported - declared           # and nothing of another library's leaks out of this one
-    for name in declared:
-        assert getattr(tp.lib(), name) is not None
     # not a client of the main library: it reads its header for sq_camera and calls nothing of it
-    needed = subprocess.check_output(["readelf", "-d", tp.LIB_PATH]).decode()
-    assert "libsquigly_hip" not in needed
+    LS.check_client(tp.LIB_PATH, False)
 
 
 def test_six_ids_are_distinct_and_an_edit_moves_only_its_own(tp, sqt, tmp_path):
-    b = build_module()
-    ids = lambda: (b.source_id(), b.denoise_source_id(), b.lens_source_id(), b.mlens_source_id(), b.shutter_source_id(),  # noqa: E731
-                   b.temporal_source_id())
-    before = ids()
-    assert len(set(before)) == 6
-    assert tp.build_id() == before[5] and sqt.build_id() == before[0]
-    assert not b.temporal_stale()
-    assert "sq_temporal.hip" not in b.SOURCES + b.HEADERS and "sq_temporal_pixel.h" not in b.HEADERS + b.DENOISE_HEADERS + b.SHUTTER_HEADERS
-    assert b.TEMPORAL["salt"] == b"temporal\0" and b.TEMPORAL["macro"] == "SQ_TEMPORAL_BUILD_ID" and b.TEMPORAL["link"] == []
-    shutil.copytree(os.path.join(ROOT, "squigly-trace_amd", "csrc"), tmp_path / "a" / "b" / "csrc")
-    shutil.copytree(os.path.join(ROOT, "include"), tmp_path / "a" / "include")
-    b.CSRC = str(tmp_path / "a" / "b" / "csrc")
-    assert ids() == before
-    with open(os.path.join(b.CSRC, "sq_temporal.hip"), "a") as fh:
-        fh.write("// changed\n")
-    after = ids()
-    assert after[:5] == before[:5] and after[5] != before[5]
-    with open(os.path.join(b.CSRC, "sq_temporal_pixel.h"), "a") as fh:
-        fh.write("// changed\n")
-    assert ids()[:5] == before[:5] and ids()[5] != after[5]
+    b = LS.build_module()                                     # (six when this library landed; the table has grown since)
+    assert len(b.LIBS) >= 6
+    assert "sq_temporal.hip" not in LS.files(b, "main")
+    assert "sq_temporal_pixel.h" not in b.LIBS["main"]["headers"] + b.LIBS["denoise"]["headers"] + b.LIBS["shutter"]["headers"]
+    t = b.LIBS["temporal"]
+    assert t["salt"] == b"temporal\0" and t["macro"] == "SQ_TEMPORAL_BUILD_ID" and t["link"] == []
+    LS.check_ids(b, "temporal", tp, sqt, tmp_path, [("sq_temporal.hip", {"temporal"}), ("sq_temporal_pixel.h", {"temporal"})])
 
 
 def test_history_bytes_is_monotone(tp):

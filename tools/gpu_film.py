@@ -8,7 +8,7 @@ differences.
 
     python tools/gpu_film.py [--rows 1080 --cols 1920 --spp 16 --reps 30 --out FILE.json]
 
-The variant builds are made with squigly-trace_amd/build.py when they are missing (build_film(extra=["-DSQ_FILM_HIST_FOLD=k"], out=...)).
+The variant builds are made with squigly-trace_amd/build.py when they are missing (compile_lib(LIBS["film"], ["-DSQ_FILM_HIST_FOLD=k"], out)).
 Prints one JSON object; every time is in milliseconds.  Needs a GPU: there is no fallback."""
 import argparse
 import ctypes as C
@@ -51,9 +51,9 @@ def variant_libs(fm):
     for k in FOLDS:
         path = os.path.join(PKG, f"libsquigly_film_fold{k}.so")
         extra = [f"-DSQ_FILM_HIST_FOLD={k}"]
-        want = b.film_source_id(extra).encode()
+        want = b.lib_source_id(b.LIBS["film"], extra).encode()
         if not os.path.exists(path) or want not in open(path, "rb").read():
-            b.build_film(extra=extra, out=path)
+            b.compile_lib(b.LIBS["film"], extra, path)
         libs[k] = fm.load(path)
     return libs
 
