@@ -136,7 +136,8 @@ def default_sigma_p(bounds):
 
 def scene_guides(ds, cam, w, h, shard=(None, 0, 1), stream=None):
     """DeviceScene.guides: camera_rays + intersect, then torch gathers from the scene's triangle and material arrays.  The normal
-    is the unit normal of Geometry.hs's `normal`, cross (b - a) (c - a) / its norm.  A convenience: not pinned to the bit."""
+    is the unit normal of Geometry.hs's `normal`, cross (b - a) (c - a) / its norm, in numpy float32 over the packed triangles: tri and point are intersect's, and normal, surf and
+    emit are the rows of those tables, which tests/fuzz_lens.py restates from the oracle's triangles and compares bit for bit."""
     import numpy as np
     import torch
     dev, st = P.call_stream(ds.device, stream)
@@ -144,12 +145,12 @@ def scene_guides(ds, cam, w, h, shard=(None, 0, 1), stream=None):
         tables = getattr(ds, "_guide_tables", None)
         if tables is None:        # per triangle: unit normal, surf, emissive *^ emit; one more row of zeros for "no hit"
             t, m = ds.bih.tris, ds.bih.materials
-            with np.errstate(all="ignore"):
+            mat = t["mat"]
+            with np.errstate(all="ignore"):                   # (a degenerate triangle's normal is NaN, a huge emissive times emit inf)
                 nrm = np.cross(t["v1"] - t["v0"], t["v2"] - t["v0"]).astype(np.float32)
                 nrm = nrm / np.sqrt((nrm * nrm).sum(-1, keepdims=True), dtype=np.float32)
-            mat = t["mat"]
+                emit = (m["emissive"][mat][:, None] * m["emit"][mat]) if len(m) else np.zeros((len(t), 3), np.float32)
             surf = m["surf"][mat] if len(m) else np.zeros((len(t), 3), np.float32)
-            emit = (m["emissive"][mat][:, None] * m["emit"][mat]) if len(m) else np.zeros((len(t), 3), np.float32)
             rows = [np.concatenate([np.asarray(a, np.float32).reshape(len(t), 3), np.zeros((1, 3), np.float32)]) for a in (nrm, surf, emit)]
             tables = ds._guide_tables = tuple(torch.from_numpy(np.ascontiguousarray(r)).to(dev) for r in rows)
         hits = ds.intersect(*ds.camera_rays(cam, w, h, shard, stream=st), want_dist=False, stream=st)
