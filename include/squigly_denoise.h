@@ -99,6 +99,56 @@ int sq_denoise_stage_device(int32_t device, int32_t rows, int32_t cols,
                             const float* d_point, const sq_denoise_params* params, float* d_out, float* d_out_var,
                             void* d_work, size_t work_bytes, void* hip_stream, int32_t stage);
 
+/* ---- Sparse frames: trace a lattice of pixels and the holes, fill the rest from the guides ----
+ *
+ * The seed of a sample does not depend on the call, so a pixel that sq_render_rows_device_masked traces under the mask below holds
+ * bit for bit what the dense frame holds there; only the pixels filled in are new arithmetic.  Every operation is one fp32 operation,
+ * in exactly this order; integers are int32.
+ *
+ * The lattice of stride s (1..16) and offset (oy, ox), 0 <= oy, ox < s, is the set of pixels (y, x) with (y - oy) % s == 0 and
+ * (x - ox) % s == 0.  For a pixel p = (y, x) that is not on the lattice, sw(p), sc(p) and sv(p) are
+ *     yl = floor((y - oy) / s) * s + oy;  xl likewise          (floor division: yl may be < 0)
+ *     ty = (float)(y - yl) / (float)s;    tx = (float)(x - xl) / (float)s
+ *     sw = +0;  sc = (+0, +0, +0);  sv = +0
+ *     taps j = 0, 1 (outer), i = 0, 1 (inner):  q = (yl + j*s, xl + i*s); a tap outside the image is left out.
+ *       if tri[p] >= 0 the tap is accepted only if all of these hold (a NaN compares false):
+ *           tri[q] >= 0
+ *           dn = (n_p.x*n_q.x + n_p.y*n_q.y) + n_p.z*n_q.z   and  dn >= cos_n
+ *           d = P_q - P_p;  pd = (n_p.x*d.x + n_p.y*d.y) + n_p.z*d.z   and  fabsf(pd) <= sigma_p
+ *       if tri[p] < 0 the tap is accepted only if tri[q] < 0: sky is filled in from sky.
+ *       for an accepted tap:
+ *           bw = (i ? tx : 1 - tx) * (j ? ty : 1 - ty)
+ *           sw = sw + bw;  sc_c = sc_c + bw * C[q]_c;  sv = sv + bw * V[q]
+ * A tap whose weight is zero is still added (0 * inf is the NaN the expression says).
+ *
+ * Both calls: no workspace, no allocation, no state, no host wait, any stream.  Refused before anything is enqueued: a NULL required
+ * pointer; rows or cols < 1 or rows * cols > 2^31 - 1; stride outside 1..16; oy or ox outside [0, stride); sigma_p NaN or < 0; cos_n
+ * NaN; d_out_var without d_var; any overlap among the buffers.
+ * Out of scope: lens, shutter, adaptive and cast frames as the sparse renderer, shards and several devices, and a history weight
+ * that favours traced over filled-in pixels (the Python driver, temporal.py, renders whole path-traced frames on one device). */
+typedef struct {
+    float sigma_p;             /* plane-distance stop, world units; >= 0 */
+    float cos_n;               /* least n_p . n_q of an accepted tap */
+} sq_denoise_sparse_params;
+
+/* Which pixels have to be traced.  d_mask[p] (uint8, rows * cols) = 1 if p is on the lattice, or if sw(p) > 0 is false -- a hole: a
+ * pixel no traced neighbour may speak for; 0 otherwise.  It reads the guides alone, so the mask exists before anything is rendered,
+ * and one masked render call serves the lattice and the holes together. */
+int sq_denoise_sparse_mask_device(int32_t device, int32_t rows, int32_t cols, int32_t stride, int32_t oy, int32_t ox,
+                                  const int32_t* d_tri, const float* d_normal, const float* d_point,
+                                  const sq_denoise_sparse_params* params, uint8_t* d_mask, void* hip_stream);
+
+/* Fills in the pixels that were not traced.  A pixel that is on the lattice or has d_mask[p] != 0 is copied through, colour and
+ * variance, bit for bit.  Any other pixel gets out_c = sc_c / sw and out_v = sv / sw if sw(p) > 0, and is copied through as well if
+ * not -- under the mask above there is no such pixel; this makes the call total for any mask.  Colour and variance are loaded only
+ * at pixels that are copied through and at lattice pixels (the taps): under the mask above, only where the masked call rendered.
+ * d_var and d_out_var are optional (NULL), d_out_var only with d_var.  d_out and d_out_var overlap no input. */
+int sq_denoise_upsample_device(int32_t device, int32_t rows, int32_t cols, int32_t stride, int32_t oy, int32_t ox,
+                               const float* d_color, const float* d_var /* optional */,
+                               const int32_t* d_tri, const float* d_normal, const float* d_point, const uint8_t* d_mask,
+                               const sq_denoise_sparse_params* params,
+                               float* d_out, float* d_out_var /* optional, only with d_var */, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -86,6 +86,16 @@ def path_depth(text):
     return v
 
 
+def lattice_stride(text):
+    try:
+        v = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError("expected an integer in 1..16")
+    if not 1 <= v <= 16:
+        raise argparse.ArgumentTypeError("expected an integer in 1..16")
+    return v
+
+
 def parse_light(text):
     """A point light of --light: X,Y,Z (power 2, the reference's), X,Y,Z,P or X,Y,Z,R,G,B -> ((x, y, z), (r, g, b)).  The value may
     stand in parentheses, (X,Y,Z), which keeps a negative X from looking like an option on the command line."""
@@ -218,6 +228,11 @@ def build_parser():
     p.add_argument("--temporal", type=unit_float, nargs="?", const=True, default=None, metavar="ALPHA_MIN",
                    help="With --sequence: accumulate every frame over the frames before it, reprojected through its first hits; "
                         "ALPHA_MIN is the least weight of the new frame (default 0.1)")
+    # not a flag of the reference: sparse frames (include/squigly_denoise.h: the lattice moves from frame to frame)
+    p.add_argument("--sparse", type=lattice_stride, default=None, metavar="S",
+                   help="With --sequence: trace only every S-th pixel of every S-th row of a frame (1..16; the lattice moves from "
+                        "frame to frame) and the pixels no traced neighbour can stand for, and fill the rest in from their traced "
+                        "neighbours on the same surface")
     # not flags of the reference: how the float frame becomes bytes, on the device (include/squigly_film.h).  They need a mode that
     # has such a frame on the device: --adaptive with --denoise, or --sequence
     p.add_argument("--film", choices=FILM_CURVES, default=None, metavar="CURVE",
@@ -280,6 +295,8 @@ def parse_args(argv=None):
         p.error("--temporal needs --sequence")
     if a.temporal is not None and (a.adaptive is not None or a.aa is not None):
         p.error("--temporal cannot be combined with --adaptive or --aa")
+    if a.sparse is not None and a.sequence is None:
+        p.error("--sparse needs --sequence (a sparse frame's lattice moves from frame to frame)")
     if a.sequence is not None:
         for flag, given in (("--cast", a.cast), ("--views", a.views is not None), ("--adaptive", a.adaptive is not None),
                             ("--preview-every", a.preview_every is not None), ("--light", a.light is not None)):
@@ -366,7 +383,7 @@ def main(argv=None):
     elif a.sequence is not None:
         paths = view_paths(settings.savePath, len(a.sequence))
         frames = render_sequence(bih, a.sequence, settings.samples, settings.dimensions, temporal=a.temporal is not None, denoise=a.denoise,
-                                 depth=a.depth, sky=a.sky, film=film_of(a),
+                                 depth=a.depth, sky=a.sky, film=film_of(a), sparse=a.sparse,
                                  **({} if a.temporal is None or a.temporal is True else {"alpha_min": a.temporal}))
         for path, img in zip(paths, frames):
             write_png(path, img)

@@ -11,12 +11,16 @@
 // The arithmetic of a pixel (filter_pixel) is written once, operation by operation as the header states it, and is the same for
 // every kernel form: a form only decides how a tap's records reach the lane (Direct: from the workspace; Tiled: from an LDS image
 // of the tile and its halo).  -ffp-contract=off and the correctly rounded divide / sqrt keep it equal to the numpy restatement.
+//
+// Sparse frames (sq_denoise_sparse_mask_device, sq_denoise_upsample_device) are two kernels of their own further down: no workspace,
+// the caller's images as they are, and a pixel's arithmetic from sq_upsample_pixel.h, the text the host test program compiles too.
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
 
 #include "sq_call_checks.h"
 #include "sq_math.h"
+#include "sq_upsample_pixel.h"
 #include "../../include/squigly_denoise.h"
 
 #ifndef SQ_DENOISE_BUILD_ID
@@ -238,6 +242,36 @@ __global__ __launch_bounds__(kBlock) void sq_dn_pass_tiled(const int rows, const
     }
 }
 
+// ---- sparse frames: which pixels to trace, and the others from their traced neighbours (sq_upsample_pixel.h) ----
+// One lane per pixel, a wave on 64 consecutive columns of a row (the direct form's tiles): a lane's own guide loads are contiguous
+// across the wave, and the four taps of s neighbouring lanes are the same lattice pixels, so their lines come from L1 / L2.
+__global__ __launch_bounds__(kBlock) void sq_dn_sparse_mask(const upspix::Lattice L, const upspix::Stops K, const upspix::Guides G,
+                                                            uint8_t* __restrict__ mask, const long long tiles, const long long tiles_x) {
+    for (long long t = blockIdx.x; t < tiles; t += gridDim.x) {
+        const long long ty = t / tiles_x, tx = t - ty * tiles_x;
+        const long long x = tx * kDirW + (threadIdx.x & (kDirW - 1)), y = ty * kDirH + (threadIdx.x / kDirW);
+        if (x >= L.cols || y >= L.rows) continue;
+        mask[y * L.cols + x] = upspix::live(L, K, G, (int32_t)y, (int32_t)x);
+    }
+}
+
+template <bool VAR>
+__global__ __launch_bounds__(kBlock) void sq_dn_upsample(const upspix::Lattice L, const upspix::Stops K, const upspix::Guides G,
+                                                         const upspix::Image I, const uint8_t* __restrict__ mask,
+                                                         float* __restrict__ out, float* __restrict__ out_var, const long long tiles,
+                                                         const long long tiles_x) {
+    for (long long t = blockIdx.x; t < tiles; t += gridDim.x) {
+        const long long ty = t / tiles_x, tx = t - ty * tiles_x;
+        const long long x = tx * kDirW + (threadIdx.x & (kDirW - 1)), y = ty * kDirH + (threadIdx.x / kDirW);
+        if (x >= L.cols || y >= L.rows) continue;
+        const long long p = y * L.cols + x;
+        float c[3], v = 0.0f;
+        upspix::upsample<VAR>(L, K, G, I, mask, (int32_t)y, (int32_t)x, c, &v);
+        out[3 * p + 0] = c[0]; out[3 * p + 1] = c[1]; out[3 * p + 2] = c[2];
+        if (VAR && out_var) out_var[p] = v;
+    }
+}
+
 // The form of pass `pass` when the caller leaves the choice (form = 0): the tiled form wherever its LDS image fits.  Measured at
 // 1920 x 1080 (tools/gpu_denoise.py): 0.111 / 0.112 / 0.114 ms at steps 1 / 2 / 4 against 0.173 / 0.173 / 0.177 ms direct.
 int auto_form(int pass) { return (1 << pass) <= kTiledMaxStep ? SQ_DENOISE_FORM_TILED : SQ_DENOISE_FORM_DIRECT; }
@@ -310,6 +344,38 @@ int enqueue(int32_t device, int32_t rows, int32_t cols, const float* d_color, co
     return 0;
 }
 
+// What both sparse calls refuse of the lattice, the stops and the guides; then the overlaps among r[0 .. count).
+int check_sparse(int32_t rows, int32_t cols, int32_t s, int32_t oy, int32_t ox, const sq_denoise_sparse_params* P, const NamedRange* r, int count) {
+    if (rows < 1 || cols < 1) return sq_set_error("rows and cols must be at least 1 (got %d x %d)", rows, cols);
+    if ((long long)rows * cols > kMaxPixels) return sq_set_error("%d x %d pixels exceed 2^31 - 1 pixels in one call", rows, cols);
+    if (s < 1 || s > upspix::kMaxStride) return sq_set_error("stride must be in 1..%d (got %d)", upspix::kMaxStride, s);
+    if (oy < 0 || oy >= s || ox < 0 || ox >= s) return sq_set_error("offset must be in [0, stride) both ways (got (%d, %d) at stride %d)", oy, ox, s);
+    if (!(P->sigma_p >= 0.0f)) return sq_set_error("sigma_p must be a number >= 0 (got %g)", (double)P->sigma_p);
+    if (P->cos_n != P->cos_n) return sq_set_error("cos_n must be a number (got %g)", (double)P->cos_n);
+    return refuse_overlaps(r, count);
+}
+
+int enqueue_sparse(int32_t device, int32_t rows, int32_t cols, int32_t s, int32_t oy, int32_t ox, const sq_denoise_sparse_params& P,
+                   const int32_t* d_tri, const float* d_normal, const float* d_point, const float* d_color, const float* d_var,
+                   const uint8_t* d_mask_in, uint8_t* d_mask_out, float* d_out, float* d_out_var, void* hip_stream) {
+    SQ_HIP(hipSetDevice(device));
+    hipStream_t stream = (hipStream_t)hip_stream;
+    const upspix::Lattice L{ rows, cols, s, oy, ox };
+    const upspix::Stops K{ P.sigma_p, P.cos_n };
+    const upspix::Guides G{ d_tri, d_normal, d_point };
+    const long long tx = ((long long)cols + kDirW - 1) / kDirW, ty = ((long long)rows + kDirH - 1) / kDirH;
+    const dim3 grid(grid_for(tx * ty)), block(kBlock);
+    if (d_mask_out) {
+        hipLaunchKernelGGL(sq_dn_sparse_mask, grid, block, 0, stream, L, K, G, d_mask_out, tx * ty, tx);
+    } else {
+        const upspix::Image I{ d_color, d_var };
+        if (d_var) hipLaunchKernelGGL(sq_dn_upsample<true>, grid, block, 0, stream, L, K, G, I, d_mask_in, d_out, d_out_var, tx * ty, tx);
+        else       hipLaunchKernelGGL(sq_dn_upsample<false>, grid, block, 0, stream, L, K, G, I, d_mask_in, d_out, d_out_var, tx * ty, tx);
+    }
+    SQ_HIP(hipGetLastError());
+    return 0;
+}
+
 }  // namespace
 
 extern "C" const char* sq_denoise_last_error(void) { return sq_error_buffer(); }
@@ -351,4 +417,31 @@ extern "C" int sq_denoise_stage_device(int32_t device, int32_t rows, int32_t col
     if (check_call(rows, cols, d_color, d_var, d_tri, d_normal, d_point, params, d_out, d_out_var, d_work, work_bytes)) return 1;
     if (stage < -1 || stage >= params->passes) return sq_set_error("stage must be in -1..%d (got %d)", params->passes - 1, stage);
     return enqueue(device, rows, cols, d_color, d_var, d_tri, d_normal, d_point, *params, d_out, d_out_var, d_work, hip_stream, stage, stage);
+}
+
+extern "C" int sq_denoise_sparse_mask_device(int32_t device, int32_t rows, int32_t cols, int32_t stride, int32_t oy, int32_t ox,
+                                             const int32_t* d_tri, const float* d_normal, const float* d_point,
+                                             const sq_denoise_sparse_params* params, uint8_t* d_mask, void* hip_stream) {
+    if (!d_tri || !d_normal || !d_point || !params || !d_mask)
+        return sq_set_error("null argument: d_tri, d_normal, d_point, params and d_mask are required");
+    const size_t n = rows > 0 && cols > 0 ? (size_t)rows * (size_t)cols : 0;
+    const NamedRange r[4] = { { "d_tri", d_tri, 4 * n }, { "d_normal", d_normal, 12 * n }, { "d_point", d_point, 12 * n }, { "d_mask", d_mask, n } };
+    if (check_sparse(rows, cols, stride, oy, ox, params, r, 4)) return 1;
+    return enqueue_sparse(device, rows, cols, stride, oy, ox, *params, d_tri, d_normal, d_point, nullptr, nullptr, nullptr, d_mask, nullptr,
+                          nullptr, hip_stream);
+}
+
+extern "C" int sq_denoise_upsample_device(int32_t device, int32_t rows, int32_t cols, int32_t stride, int32_t oy, int32_t ox,
+                                          const float* d_color, const float* d_var, const int32_t* d_tri, const float* d_normal,
+                                          const float* d_point, const uint8_t* d_mask, const sq_denoise_sparse_params* params,
+                                          float* d_out, float* d_out_var, void* hip_stream) {
+    if (!d_color || !d_tri || !d_normal || !d_point || !d_mask || !params || !d_out)
+        return sq_set_error("null argument: d_color, d_tri, d_normal, d_point, d_mask, params and d_out are required");
+    if (d_out_var && !d_var) return sq_set_error("d_out_var needs d_var: without a variance image there is none to fill in");
+    const size_t n = rows > 0 && cols > 0 ? (size_t)rows * (size_t)cols : 0;
+    const NamedRange r[8] = { { "d_color", d_color, 12 * n }, { "d_var", d_var, 4 * n }, { "d_tri", d_tri, 4 * n }, { "d_normal", d_normal, 12 * n },
+                              { "d_point", d_point, 12 * n }, { "d_mask", d_mask, n }, { "d_out", d_out, 12 * n }, { "d_out_var", d_out_var, 4 * n } };
+    if (check_sparse(rows, cols, stride, oy, ox, params, r, 8)) return 1;
+    return enqueue_sparse(device, rows, cols, stride, oy, ox, *params, d_tri, d_normal, d_point, d_color, d_var, d_mask, nullptr, d_out,
+                          d_out_var, hip_stream);
 }

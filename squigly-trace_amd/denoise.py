@@ -3,6 +3,9 @@
 The filter maps device images to device images: colour and (optionally) the variance of its luminance in, guided by the first
 hit's triangle id, normal and point (DeviceScene.guides).  PyTorch is the plumbing (device memory, streams); every filtered pixel
 comes from the HIP kernels of csrc/sq_denoise.hip.  There is no fallback: a missing library raises.
+
+Sparse frames live here too (sparse_mask, upsample, lattice_offset): under the same guides, which pixels of a frame have to be traced
+-- a lattice and the holes -- and every other pixel from its traced neighbours on the same surface.
 """
 import collections
 import ctypes as C
@@ -12,7 +15,8 @@ from . import _plumbing as P
 
 # include/squigly_denoise.h; sq_denoise_last_error and the functions a caller uses
 EXPORTED_SYMBOLS = ["sq_denoise_last_error", "sq_denoise_build_id", "sq_denoise_pass_form", "sq_denoise_workspace_bytes",
-                    "sq_denoise_variance_device", "sq_denoise_device", "sq_denoise_stage_device"]
+                    "sq_denoise_variance_device", "sq_denoise_device", "sq_denoise_stage_device",
+                    "sq_denoise_sparse_mask_device", "sq_denoise_upsample_device"]
 
 FORMS = {"auto": 0, "direct": 1, "tiled": 2}          # params.form (SQ_DENOISE_FORM_*)
 # The prototype's parameters.  sigma_p has no default here: it is a length of the scene (denoise_frame derives it).
@@ -29,8 +33,19 @@ class Params(C.Structure):
                 ("normal_squarings", C.c_int32), ("form", C.c_int32)]
 
 
+class SparseParams(C.Structure):
+    """sq_denoise_sparse_params."""
+    _fields_ = [("sigma_p", C.c_float), ("cos_n", C.c_float)]
+
+
+MAX_STRIDE = 16               # of a sparse frame's lattice
+SPARSE_COS_N = 0.9            # the temporal stage's
+
+
 def _declare(L):
     vp, i32 = C.c_void_p, C.c_int32
+    L.sq_denoise_sparse_mask_device.argtypes = [i32] * 6 + [vp, vp, vp, C.POINTER(SparseParams), vp, vp]
+    L.sq_denoise_upsample_device.argtypes = [i32] * 6 + [vp] * 6 + [C.POINTER(SparseParams), vp, vp, vp]
     L.sq_denoise_pass_form.argtypes = [i32]
     L.sq_denoise_pass_form.restype = i32
     L.sq_denoise_workspace_bytes.argtypes = [i32, i32]
@@ -123,6 +138,108 @@ def denoise_variance(sums, sums2, counts, stream=None):
         check(lib().sq_denoise_variance_device(dev.index or 0, counts.numel(), sums.data_ptr(), sums2.data_ptr(), counts.data_ptr(),
                                                var.data_ptr(), P.stream_ptr(st)))
     return var
+
+
+def stride_arg(stride):
+    """The stride of a sparse frame's lattice as an int; ValueError unless it is an integer in 1..MAX_STRIDE."""
+    if not P.is_integer(stride) or not 1 <= int(stride) <= MAX_STRIDE:
+        raise ValueError(f"stride must be an integer in 1..{MAX_STRIDE}, got {stride!r}")
+    return int(stride)
+
+
+def lattice_args(stride, offset):
+    """(s, oy, ox) of a lattice as ints; ValueError unless stride is an integer in 1..MAX_STRIDE and offset a pair of integers in [0, s)."""
+    s = stride_arg(stride)
+    try:
+        oy, ox = offset
+    except (TypeError, ValueError):
+        raise ValueError(f"offset must be a pair (oy, ox), got {offset!r}")
+    if not P.is_integer(oy) or not P.is_integer(ox) or not (0 <= int(oy) < s and 0 <= int(ox) < s):
+        raise ValueError(f"offset must be a pair of integers in [0, {s}), got {offset!r}")
+    return s, int(oy), int(ox)
+
+
+def lattice_offset(frame, stride):
+    """The offset (oy, ox) of frame `frame` of a sequence at stride s: with j = frame % s^2, oy = j % s and ox = (j // s + j % s) % s.
+    Every offset comes up once in s^2 frames, and the row offset changes with every frame: for s = 2 the order is (0, 0), (1, 1),
+    (0, 1), (1, 0)."""
+    s = stride_arg(stride)
+    if not P.is_integer(frame) or int(frame) < 0:
+        raise ValueError(f"frame must be a non-negative integer, got {frame!r}")
+    j = int(frame) % (s * s)
+    return j % s, (j // s + j % s) % s
+
+
+def _sparse_params(sigma_p, cos_n):
+    if sigma_p is None:
+        raise N.SquiglyError("sigma_p is required: the plane-distance stop in world units (default_sigma_p of the scene's bounds)")
+    return SparseParams(float(sigma_p), float(cos_n))
+
+
+def _guide_tensors(guides, dev=None):
+    """(rows, cols, device) of guides (anything with .tri, .normal, .point), whose three tensors are checked."""
+    import torch
+    tri = getattr(guides, "tri", None)
+    if not isinstance(tri, torch.Tensor) or tri.dim() != 2 or not tri.is_cuda:
+        raise N.SquiglyError("guides.tri must be an int32 CUDA tensor of shape [rows, cols]")
+    dev = tri.device if dev is None else dev
+    rows, cols = int(tri.shape[0]), int(tri.shape[1])
+    P.tensor("guides.tri", tri, (rows, cols), torch.int32, dev)
+    P.tensor("guides.normal", guides.normal, (rows, cols, 3), torch.float32, dev)
+    P.tensor("guides.point", guides.point, (rows, cols, 3), torch.float32, dev)
+    return rows, cols, dev
+
+
+def sparse_mask(guides, stride, offset, sigma_p=None, cos_n=SPARSE_COS_N, stream=None):
+    """sq_denoise_sparse_mask_device: the pixels a sparse frame has to trace, a uint8 CUDA tensor [rows, cols] -- 1 on the lattice
+    of `stride` and `offset` = (oy, ox) and at the holes (pixels none of whose lattice neighbours lies on their surface), 0 elsewhere.
+    guides: anything with .tri, .normal and .point (DeviceScene.guides).  sigma_p is required (default_sigma_p of the scene).  Pass
+    the result to DeviceScene.render_rows_masked(mask=) and then, with what that rendered, to upsample.  Enqueued on `stream`."""
+    import torch
+    s, oy, ox = lattice_args(stride, offset)
+    par = _sparse_params(sigma_p, cos_n)
+    rows, cols, dev = _guide_tensors(guides)
+    _, st = P.call_stream(dev, stream)
+    with torch.cuda.stream(st):
+        mask = torch.empty((rows, cols), dtype=torch.uint8, device=dev)
+        check(lib().sq_denoise_sparse_mask_device(dev.index or 0, rows, cols, s, oy, ox, guides.tri.data_ptr(), guides.normal.data_ptr(),
+                                                  guides.point.data_ptr(), C.byref(par), mask.data_ptr(), P.stream_ptr(st)))
+    return mask
+
+
+def upsample(color, guides, mask, stride, offset, var=None, out=None, stream=None, sigma_p=None, cos_n=SPARSE_COS_N):
+    """sq_denoise_upsample_device: the frame `color` (float32 [rows, cols, 3], meaningful where mask is set) with every other pixel
+    filled in from its lattice neighbours on the same surface; returns (out, out_var), out_var None without var.  mask: what
+    sparse_mask returned for the same guides, stride, offset, sigma_p and cos_n.  var: float32 [rows, cols] or None.  out: a colour
+    tensor, or (colour, variance) tensors, to receive the result (None = allocate); they overlap no input.  Enqueued on `stream`."""
+    import torch
+    s, oy, ox = lattice_args(stride, offset)
+    par = _sparse_params(sigma_p, cos_n)
+    if not isinstance(color, torch.Tensor) or color.dim() != 3 or color.shape[-1] != 3 or not color.is_cuda:
+        raise N.SquiglyError("color must be a float32 CUDA tensor of shape [rows, cols, 3]")
+    rows, cols, dev = _guide_tensors(guides, color.device)
+    f32 = torch.float32
+    P.tensor("color", color, (rows, cols, 3), f32, dev)
+    P.tensor("mask", mask, (rows, cols), torch.uint8, dev)
+    if var is not None:
+        P.tensor("var", var, (rows, cols), f32, dev)
+    out_c, out_v = out if isinstance(out, (tuple, list)) else (out, None)
+    if out_c is not None:
+        P.tensor("out", out_c, (rows, cols, 3), f32, dev)
+    if out_v is not None:
+        if var is None:
+            raise N.SquiglyError("an output variance needs var")
+        P.tensor("out variance", out_v, (rows, cols), f32, dev)
+    _, st = P.call_stream(dev, stream)
+    with torch.cuda.stream(st):
+        if out_c is None:
+            out_c = torch.empty((rows, cols, 3), dtype=f32, device=dev)
+        if out_v is None and var is not None:
+            out_v = torch.empty((rows, cols), dtype=f32, device=dev)
+        check(lib().sq_denoise_upsample_device(dev.index or 0, rows, cols, s, oy, ox, color.data_ptr(), P.ptr(var), guides.tri.data_ptr(),
+                                               guides.normal.data_ptr(), guides.point.data_ptr(), mask.data_ptr(), C.byref(par),
+                                               out_c.data_ptr(), P.ptr(out_v), P.stream_ptr(st)))
+    return out_c, out_v
 
 
 def default_sigma_p(bounds):

@@ -219,7 +219,7 @@ def render_lens_rgb8(bih, cam, samples, dimensions, lens=None, subrays=None, dev
 
 
 def render_sequence(bih, cams, spp, dimensions, temporal=True, denoise=None, device=0, depth=None, sky=None, period=64, alpha_min=0.1,
-                    max_history=32, film=None):
+                    max_history=32, film=None, sparse=None):
     """The frames of a camera move, `spp` samples each (DeviceScene, Temporal: one device, the scene uploaded once): yields the
     (w, h, 3) uint8 image of every camera of `cams`, in order.  temporal=True accumulates every frame over the ones before it
     (libsquigly_temporal.so); temporal=False shows each frame's own samples -- the same samples, so the two can be compared.
@@ -229,12 +229,18 @@ def render_sequence(bih, cams, spp, dimensions, temporal=True, denoise=None, dev
     frame is then developed by it on the device (libsquigly_film.so; with Film(auto=...) the exposure adapts from frame to frame under
     temporal=True; under temporal=False the film's exposure state is forgotten after every frame as the history is -- film.reset() --
     so that every frame is exposed at its own target and the frames stay independent).
-    Refused before anything is uploaded: no camera, and what Temporal refuses of spp, period, alpha_min and max_history."""
+    sparse (None = off; a stride S in 1..16): every frame traces only a lattice of its pixels, which moves from frame to frame, and
+    the holes, and fills the others in from their traced neighbours (Temporal(sparse=S)).
+    Refused before anything is uploaded: no camera, what Temporal refuses of spp, period, alpha_min and max_history, and a sparse
+    that is no stride."""
     cams = list(cams)
     if not cams:
         raise ValueError("render_sequence needs at least one camera")
     from .temporal import _temporal_args
     _temporal_args(spp, period, alpha_min, max_history)
+    if sparse is not None:
+        from .denoise import stride_arg
+        stride_arg(sparse)
     from .film import film_arg
     film_arg(film)
     dn = denoise_arg(denoise)                          # refused before anything is uploaded
@@ -242,7 +248,7 @@ def render_sequence(bih, cams, spp, dimensions, temporal=True, denoise=None, dev
     w, h = dimensions
     with scene as ds:
         from .temporal import Temporal                 # torch: only the resident-scene path needs it
-        t = Temporal(ds, w, h, spp, period=period, alpha_min=alpha_min, max_history=max_history, denoise=dn, film=film)
+        t = Temporal(ds, w, h, spp, period=period, alpha_min=alpha_min, max_history=max_history, denoise=dn, film=film, sparse=sparse)
         for cam in cams:
             _, _, _, rgb = t.step(cam)
             if not temporal:
@@ -250,6 +256,55 @@ def render_sequence(bih, cams, spp, dimensions, temporal=True, denoise=None, dev
                 if film is not None:
                     film.reset()
             yield rgb.cpu().numpy()
+
+
+def render_sparse(bih, cam, samples, dimensions, stride, offset=(0, 0), denoise=None, film=None, device=0, depth=None, sky=None,
+                  sigma_p=None, cos_n=0.9, demodulate=True) -> np.ndarray:
+    """The frame of render_rgb8 traced sparsely: only the pixels of the lattice of `stride` and `offset` = (oy, ox), and the holes
+    between them, are traced (denoise.sparse_mask, DeviceScene.render_rows_masked); every other pixel is filled in from its traced
+    neighbours on the same surface (denoise.upsample), in demodulated space unless demodulate=False.  Shape (w, h, 3) uint8.  A
+    traced pixel holds the dense frame's average bit for bit; with stride 1 the whole frame does.  sigma_p (None =
+    denoise.default_sigma_p of the scene) and cos_n are the stops of a neighbour.  denoise (None = off; True, a sigma_l or a dict of
+    denoise parameters) filters the filled-in frame with the variance of its own second moments; film (a Film) develops it on the
+    device, None = the device's own tonemap.  depth, sky: as in render_progressive.  Path-traced frames, whole, on one device.
+    Refused before anything is uploaded: a stride outside 1..16, an offset outside [0, stride), samples < 1."""
+    from .denoise import lattice_args
+    from .film import film_arg
+    lattice_args(stride, offset)
+    if isinstance(samples, bool) or int(samples) < 1:
+        raise ValueError(f"samples must be a positive integer, got {samples!r}")
+    film = film_arg(film)
+    dn = denoise_arg(denoise)
+    scene = _resident(bih, device, None, depth, sky)
+    w, h = dimensions
+    with scene as ds:
+        import importlib
+        import torch
+        D = importlib.import_module(__package__ + ".denoise")           # (the package's own `denoise` is the function)
+        sp = D.default_sigma_p(ds.bih.bounds) if sigma_p is None else float(sigma_p)
+        if dn is not None:
+            dn.setdefault("sigma_p", sp)
+            D.make_params(**dn)
+        lattice = dict(stride=stride, offset=offset, sigma_p=sp, cos_n=cos_n)
+        dev = torch.device("cuda", ds.device)
+        g = ds.guides(cam, w, h)
+        live = D.sparse_mask(g, **lattice)
+        rows = int(live.shape[0])
+        sums = torch.zeros((rows, h, 3), dtype=torch.float32, device=dev)
+        sums2 = torch.zeros_like(sums) if dn is not None else None
+        avg, _ = ds.render_rows_masked(cam, samples, w, h, 0, samples, sums, mask=live, sums2=sums2, want_rgb=False)
+        var = None
+        if dn is not None:
+            var = D.denoise_variance(sums, sums2, torch.full((rows, h), int(samples), dtype=torch.int32, device=dev))
+        x, how = avg, None
+        if demodulate:
+            x, var, how = D.demodulated(g, avg, var)
+        out, out_var = D.upsample(x, g, live, var=var, **lattice)
+        if dn is not None:
+            out, out_var = D.denoise(out, g.tri, g.normal, g.point, var=out_var, **dn)
+        if how is not None:
+            out, _ = D.remodulated(g, out, out_var, how)
+        return _developed(ds, out, film)
 
 
 def render(bih, cam, settings: Settings):

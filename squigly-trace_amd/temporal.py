@@ -227,15 +227,22 @@ class Temporal:
     same guides before the result is remodulated; the history holds the unfiltered accumulation.
     A checkpoint is (history, camera, frames) -- copy them away and pass them back in as history=, camera=, frames= -- and
     depth, sky as in Progressive (sky=None: a fresh sequence under the scene's own sky).  reset() starts a new sequence.
+    sparse (None = every pixel is traced, the calls as they were; S = a stride in 1..16): a sparse frame.  step then takes the guides
+    first, traces only the pixels of denoise.sparse_mask at lattice_offset(frames, S) -- the lattice, which moves from frame to frame
+    so that every pixel is traced once in S * S frames, and the holes -- and fills the others in from their traced neighbours on the
+    same surface (denoise.upsample; sigma_p and cos_n are the accumulation's) after the demodulation and before the accumulation.  A
+    traced pixel holds what the dense frame holds there, bit for bit.  `noisy` is then meaningful on the live pixels only, and `live`
+    is the frame's mask (uint8 [w, h]; None without sparse).
     Whole frames on one device; path-traced frames only."""
 
     def __init__(self, ds, w, h, spp, period=64, alpha_min=0.1, max_history=32, denoise=None, demodulate=True, depth=None, sky=None,
-                 sigma_p=None, cos_n=0.9, history=None, camera=None, frames=0, film=None):
+                 sigma_p=None, cos_n=0.9, history=None, camera=None, frames=0, film=None, sparse=None):
         import torch
         from . import device as D
-        from .denoise import default_sigma_p, make_params as denoise_params
+        from .denoise import default_sigma_p, make_params as denoise_params, stride_arg
         from .render import denoise_arg
         _temporal_args(spp, period, alpha_min, max_history)
+        self.sparse = None if sparse is None else stride_arg(sparse)
         from .film import film_arg
         self.film = film_arg(film)
         if not P.is_integer(frames) or int(frames) < 0:
@@ -260,7 +267,7 @@ class Temporal:
         self._sums2 = torch.zeros((rows, self.h, 3), dtype=torch.float32, device=dev)
         self._counts = torch.full((rows, self.h), self.spp, dtype=torch.int32, device=dev)
         self._blocks = [_new_block(rows, self.h, dev), _new_block(rows, self.h, dev)]
-        self._cur, self._cam, self.frames, self.noisy = None, None, int(frames), None
+        self._cur, self._cam, self.frames, self.noisy, self.live = None, None, int(frames), None, None
         if history is not None:
             t = torch.as_tensor(history, dtype=torch.uint8, device=dev).contiguous()
             if tuple(t.shape) != tuple(self._blocks[0].shape):
@@ -283,7 +290,7 @@ class Temporal:
     def step(self, cam, stream=None):
         """Render the next frame under `cam` and accumulate it; returns (avg, var, length, rgb).  Enqueued on `stream`."""
         import torch
-        from .denoise import demodulated, denoise, denoise_variance, remodulated
+        from .denoise import demodulated, denoise, denoise_variance, lattice_offset, remodulated, sparse_mask, upsample
         self._frame._unchanged()
         ds, w, h = self.ds, self.w, self.h
         _, st = P.call_stream(self._dev, stream)
@@ -291,14 +298,23 @@ class Temporal:
         with torch.cuda.stream(st):
             self._sums.zero_()
             self._sums2.zero_()
-            ds.render_rows_masked(cam, self.spp * self.period, w, h, k0, k0 + self.spp, self._sums, sums2=self._sums2,
+            g = live = None
+            if self.sparse is not None:                           # the guides first: they say which pixels are traced
+                g = ds.guides(cam, w, h, stream=st)
+                lattice = dict(stride=self.sparse, offset=lattice_offset(self.frames, self.sparse), sigma_p=self.params["sigma_p"],
+                               cos_n=self.params["cos_n"])
+                live = sparse_mask(g, stream=st, **lattice)
+            ds.render_rows_masked(cam, self.spp * self.period, w, h, k0, k0 + self.spp, self._sums, mask=live, sums2=self._sums2,
                                   want_avg=False, want_rgb=False, stream=st)
             noisy = self._sums / float(self.spp)
             var = denoise_variance(self._sums, self._sums2, self._counts, stream=st)
-            g = ds.guides(cam, w, h, stream=st)
+            if g is None:
+                g = ds.guides(cam, w, h, stream=st)
             x, how = noisy, None
             if self.demodulate:                                   # denoise_frame's demodulation
                 x, var, how = demodulated(g, noisy, var)
+            if live is not None:                                  # the pixels that were not traced, from their traced neighbours
+                x, var = upsample(x, g, live, var=var, stream=st, **lattice)
             nxt = 1 if self._cur == 0 else 0
             out, out_var, length = accumulate(x, var, g, self._cam, self.history, self._blocks[nxt], alpha=frame_alpha(ds, g.tri),
                                               stream=st, **self.params)
@@ -307,6 +323,6 @@ class Temporal:
             if how is not None:
                 out, out_var = remodulated(g, out, out_var, how)
             rgb = tonemap(out) if self.film is None else self.film(out, stream=st)
-        self._cur, self._cam, self.noisy = nxt, N.Camera.from_buffer_copy(bytes(cam)), noisy
+        self._cur, self._cam, self.noisy, self.live = nxt, N.Camera.from_buffer_copy(bytes(cam)), noisy, live
         self.frames += 1
         return out, out_var, length, rgb
