@@ -149,6 +149,67 @@ int sq_denoise_upsample_device(int32_t device, int32_t rows, int32_t cols, int32
                                const sq_denoise_sparse_params* params,
                                float* d_out, float* d_out_var /* optional, only with d_var */, void* hip_stream);
 
+/* ---- Glare and white balance: a bloom pyramid ahead of the film stage ----
+ *
+ * The frame is exposed and white-balanced, what of it is brighter than `threshold` is carried down a pyramid of `levels` levels and
+ * up again, and the sum is added to the exposed frame: the float frame squigly_film.h's develop call then takes at exposure 1.
+ * The conventions are this header's: nothing is enqueued on a refusal; no allocation, no state, no host wait, any stream; images are
+ * rows x cols x 3 floats with rows * cols <= 2^31 - 1; values are not checked.  Every operation is one fp32 operation, in exactly the
+ * order written; integers are int32 and byte offsets 64-bit.
+ *
+ * Level sizes: r_-1 = rows, c_-1 = cols; r_k = (r_k-1 + 1) / 2 and c_k likewise, so no level is ever empty.
+ *
+ * Exposed pixel:  e = d_exposure ? *d_exposure : params->exposure;  x_c = (e * c_c) * gain_c
+ *
+ * Bright pass, per full-resolution pixel:
+ *     L = (0.25 * x.r + 0.5 * x.g) + 0.25 * x.b
+ *     m = L < ceiling ? L : ceiling
+ *     s = L > threshold ? (m - threshold) / L : +0
+ *     b_c = s * x_c;   b_c = +0 if !(b_c >= 0);   b_c = ceiling if b_c > ceiling
+ * NaN, negative and infinite values therefore stay in their own pixel: every b lies in [0, ceiling].
+ *
+ * Down step D: a fine image p of r x c gives (r + 1) / 2 x (c + 1) / 2.  All coordinates are clamped to the fine image, so every tap
+ * always takes part.  With a = 0.125 and b = 0.375:
+ *     fine row j, output column x:  h(j, x) = (a * p(j, 2x-1) + b * p(j, 2x)) + (b * p(j, 2x+1) + a * p(j, 2x+2))
+ *     output row y:                 D(y, x) = (a * h(2y-1, x) + b * h(2y, x)) + (b * h(2y+1, x) + a * h(2y+2, x)),   per component
+ *     B_0 = D(b),  B_k = D(B_k-1)
+ *
+ * Up step U: a coarse image p of R x C gives a fine size r x c.
+ *     y0 = (y - 1) >> 1 (arithmetic shift: -1 at y = 0),  y1 = y0 + 1,  both clamped to [0, R - 1]
+ *     ay = (y & 1) ? 0.75 : 0.25,  by = 1 - ay;   columns likewise
+ *     U(y, x) = ay * (ax * p(y0, x0) + bx * p(y0, x1)) + by * (ax * p(y1, x0) + bx * p(y1, x1))
+ *
+ * Glare:  A_levels-1 = B_levels-1;   A_k = B_k + spread * U(A_k+1) for k = levels-2 .. 0
+ *     levels >= 1:  out_c = x_c + strength * U(A_0)_c at full resolution
+ *     levels == 0:  out_c = x_c; nothing else runs, and d_work may be NULL.
+ *
+ * d_out == d_color, the exact same pointer, is allowed: the last kernel reads d_color at its own pixel only.
+ * d_work: work_bytes >= sq_denoise_glare_work_bytes(rows, cols, levels) bytes on the device, 16-byte aligned; its contents on entry
+ * do not matter and are undefined afterwards.
+ * Refused before anything is enqueued: a NULL required pointer; rows or cols < 1 or rows * cols > 2^31 - 1; levels or form out of
+ * range; threshold NaN, negative or infinite; ceiling not finite or not > threshold; spread or strength NaN, negative or infinite;
+ * with levels >= 1, work_bytes too small, or d_work NULL or not 16-byte aligned; any overlap among d_color, d_exposure, d_out and
+ * d_work other than d_out == d_color.
+ * Out of scope: lens-flare streaks and diffraction spikes, per-level colour tints, shards and several devices. */
+typedef struct {
+    float   exposure;    /* read when d_exposure is NULL */
+    float   gain[3];     /* white balance: per-channel factors */
+    float   threshold;   /* >= 0, finite: exposed luminance above which a pixel glares */
+    float   ceiling;     /* > threshold, finite: what a glaring value saturates at (fireflies, inf) */
+    int32_t levels;      /* 0..8 pyramid levels; 0 = exposure and white balance only */
+    float   spread;      /* >= 0, finite: weight of each coarser level in the one above it */
+    float   strength;    /* >= 0, finite: weight of the glare in the result */
+    int32_t form;        /* 0 = choose; 1 = direct; 2 = LDS-tiled (SQ_DENOISE_FORM_*; every form gives the same bits) */
+} sq_denoise_glare_params;
+
+/* Bytes of workspace the call below needs: 16 * sum over k < levels of r_k * c_k, a 16-byte record per level pixel.  0 for levels = 0,
+ * for rows or cols < 1 or rows * cols > 2^31 - 1, and for levels outside 0..8.  Monotone in all three arguments. */
+size_t sq_denoise_glare_work_bytes(int32_t rows, int32_t cols, int32_t levels);
+int    sq_denoise_glare_device(int32_t device, int32_t rows, int32_t cols, const float* d_color,
+                               const float* d_exposure /* optional, one device float: sq_film_expose_device's */,
+                               const sq_denoise_glare_params* params, float* d_out,
+                               void* d_work, size_t work_bytes, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

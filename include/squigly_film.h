@@ -15,8 +15,9 @@
  *  - the arithmetic is pinned operation by operation (below; tests/film_restatement.py restates it in numpy, and the text of
  *    csrc/sq_film_pixel.h is one for the host and the device).
  *
- * Out of scope: bloom and glare; white balance; the C++ command line; shards and more than one GPU; film on the main library's own
- * out_rgb (sq_render_rows_device and its kin keep the reference's tonemap).
+ * Out of scope: the C++ command line; shards and more than one GPU; film on the main library's own out_rgb (sq_render_rows_device
+ * and its kin keep the reference's tonemap).  Glare and white balance come before this stage: squigly_denoise.h's
+ * sq_denoise_glare_device makes the exposed frame that develop then takes at exposure 1.
  *
  * The contract.  Every operation is one fp32 operation, in exactly this order.
  *

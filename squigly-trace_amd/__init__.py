@@ -14,7 +14,7 @@ from .lens import Lens, LensFrame                                               
 # motion blur: its module is importlib.import_module("squigly-trace_amd.shutter")
 from .shutter import Motion                                                          # noqa: F401
 # the display stage: its module is importlib.import_module("squigly-trace_amd.film")
-from .film import Film                                                               # noqa: F401
+from .film import Film, Glare                                                              # noqa: F401
 
 
 def device_count() -> int:

@@ -53,8 +53,8 @@ def _library(name, sources, headers, client=False):
 # with it -- do not move when another library changes.
 
 # the denoiser (include/squigly_denoise.h): device images to device images; the arithmetic of a sparse frame's pixel
-# (sq_upsample_pixel.h) is its own
-_library("denoise", ["sq_denoise.hip"], COMMON_HEADERS + ["sq_upsample_pixel.h", "../../include/squigly_denoise.h"])
+# (sq_upsample_pixel.h) and of the glare stage's (sq_glare_pixel.h) are its own
+_library("denoise", ["sq_denoise.hip"], COMMON_HEADERS + ["sq_glare_pixel.h", "sq_upsample_pixel.h", "../../include/squigly_denoise.h"])
 # the renderer: HIP kernels and the host side (include/squigly_hip.h, include/squigly_host.h); build() makes the CLI with it
 _library("main", ["sq_device.hip", "sq_bih_device.hip", "sq_host.cpp"],
          COMMON_HEADERS + ["sq_scene.h", "sq_layout.h", "sq_pack.h", "sq_plan.h", "sq_host_types.h", "sq_cull_lemma.h", "sq_pack_level1.h",

@@ -245,7 +245,51 @@ def build_parser():
     p.add_argument("--white", type=positive_float, default=None, metavar="W", help="With --film reinhard: the luminance that becomes white (default: none)")
     p.add_argument("--srgb", action="store_true", help="With --film other than reference: encode the image with the sRGB transfer function")
     p.add_argument("--dither", action="store_true", help="With --film other than reference: ordered 8 x 8 dither before the bytes are taken")
+    # glare and white balance ahead of the curve (include/squigly_denoise.h: sq_denoise_glare_device)
+    p.add_argument("--bloom", type=finite_nonneg_float, nargs="?", const=0.1, default=None, metavar="STRENGTH",
+                   help="With --film other than reference: add the glare of what is brighter than --bloom-threshold to the frame, "
+                        "at STRENGTH (default 0.1)")
+    p.add_argument("--bloom-threshold", type=finite_nonneg_float, default=None, metavar="T",
+                   help="With --bloom: the exposed luminance above which a pixel glares (default 1)")
+    p.add_argument("--bloom-levels", type=bloom_levels, default=None, metavar="N", help="With --bloom: levels of the glare's pyramid, 1..8 (default 5)")
+    p.add_argument("--white-balance", type=parse_balance, default=None, metavar="R,G,B",
+                   help="With --film other than reference: multiply the frame's channels by R, G and B before the curve. A value that "
+                        "starts with a minus sign is written --white-balance=-1,2,3 or --white-balance '(-1,2,3)'")
     return p
+
+
+def bloom_levels(text):
+    try:
+        v = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError("expected an integer in 1..8")
+    if not 1 <= v <= 8:
+        raise argparse.ArgumentTypeError("expected an integer in 1..8")
+    return v
+
+
+def parse_balance(text):
+    """The factors of --white-balance: R,G,B, in parentheses or not -> (r, g, b)."""
+    try:
+        v = [float(t) for t in text.strip("()").split(",")]
+    except ValueError:
+        v = []
+    if len(v) != 3:
+        raise argparse.ArgumentTypeError("expected R,G,B")
+    return tuple(v)
+
+
+BLOOM_CEILING = 16.0                         # what a glaring value saturates at, in thresholds (a threshold of 0: in units of 1)
+
+
+def glare_of(a):
+    """The Glare of --bloom and the flags that go with it, or None without --bloom."""
+    if a.bloom is None:
+        return None
+    from .film import Glare
+    t = 1.0 if a.bloom_threshold is None else a.bloom_threshold
+    return Glare(threshold=t, ceiling=BLOOM_CEILING * (t if t > 0 else 1.0), levels=5 if a.bloom_levels is None else a.bloom_levels,
+                 strength=a.bloom)
 
 
 FILM_CURVES = ("reference", "atan", "reinhard", "filmic", "linear")
@@ -261,7 +305,7 @@ def film_of(a):
     if a.auto_exposure is not None:
         auto = dict(key=a.auto_exposure, rate=AUTO_EXPOSURE_RATE if a.sequence is not None else 1.0)
     return Film(curve=a.film, exposure=1.0 if a.exposure is None else a.exposure, white=float("inf") if a.white is None else a.white,
-                lut=srgb_lut() if a.srgb else None, dither=a.dither, auto=auto)
+                lut=srgb_lut() if a.srgb else None, dither=a.dither, auto=auto, glare=glare_of(a), balance=a.white_balance)
 
 
 def camera_text(path):
@@ -307,14 +351,24 @@ def parse_args(argv=None):
     if a.denoise is not None and a.adaptive is None and a.sequence is None:
         p.error("--denoise needs --adaptive (the filter takes its variance from the adaptive frame's second moments)")
     film_flags = [flag for flag, given in (("--exposure", a.exposure is not None), ("--auto-exposure", a.auto_exposure is not None),
-                                           ("--white", a.white is not None), ("--srgb", a.srgb), ("--dither", a.dither)) if given]
+                                           ("--white", a.white is not None), ("--srgb", a.srgb), ("--dither", a.dither),
+                                           ("--bloom", a.bloom is not None), ("--bloom-threshold", a.bloom_threshold is not None),
+                                           ("--bloom-levels", a.bloom_levels is not None), ("--white-balance", a.white_balance is not None)) if given]
     if film_flags and a.film is None:
         p.error(f"{film_flags[0]} needs --film")
+    if a.bloom is None and (a.bloom_threshold is not None or a.bloom_levels is not None):
+        p.error("--bloom-threshold and --bloom-levels need --bloom")
     if a.film is not None:
         if a.sequence is None and (a.adaptive is None or a.denoise is None):
             p.error("--film needs a float frame on the device: --adaptive with --denoise, or --sequence")
         if a.film == "reference" and (a.srgb or a.dither):
             p.error("--film reference takes neither --srgb nor --dither (it is the renderer's own conversion to bytes)")
+        if a.film == "reference" and (a.bloom is not None or a.white_balance is not None):
+            p.error("--film reference takes neither --bloom nor --white-balance (it is the renderer's own conversion to bytes)")
+        try:
+            glare_of(a)
+        except SquiglyError as e:
+            p.error(f"--bloom: {e}")
         if a.white is not None and a.film != "reinhard":
             p.error("--white needs --film reinhard")
         if a.exposure is not None and a.auto_exposure is not None:

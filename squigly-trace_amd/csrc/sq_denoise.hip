@@ -20,6 +20,7 @@
 
 #include "sq_call_checks.h"
 #include "sq_math.h"
+#include "sq_glare_pixel.h"
 #include "sq_upsample_pixel.h"
 #include "../../include/squigly_denoise.h"
 
@@ -376,7 +377,284 @@ int enqueue_sparse(int32_t device, int32_t rows, int32_t cols, int32_t s, int32_
     return 0;
 }
 
+// ---- glare: a bloom pyramid, and exposure and white balance, ahead of the film stage (sq_glare_pixel.h) ----
+// The workspace holds the levels B_0 .. B_levels-1 one after the other, a 16-byte record (r, g, b, 0) per level pixel; the up steps
+// turn B_k into A_k in place.  Five kernels:
+//   down<BRIGHT = true>   colour -> B_0: exposure, gain and the bright pass of the 16 fine pixels of an output, then the down step
+//   down<BRIGHT = false>  B_k-1 -> B_k: the down step over records
+//   up_add                A_k+1, B_k -> A_k, in place on level k: a lane writes only the record it read
+//   composite<true>       colour, A_0 -> d_out, four pixels a lane where d_color and d_out are 16-byte aligned, else one
+//   composite<false>      levels = 0: exposure and gain alone
+// The down kernels have two forms, which give the same bits because h(j, x) depends on the fine row and the output column alone:
+//   direct  a lane gathers its 4 x 4 fine pixels itself (a wave on 64 consecutive output columns, as the direct filter pass)
+//   tiled   a workgroup stages the 34 x 34 fine pixels of its 16 x 16 outputs in LDS once (bright-passed once each, not four times),
+//           planar -- one float plane a channel, rows 35 floats apart so that the two fine rows a 32-lane group reads at stride 2
+//           fall on banks of opposite parity -- then the horizontal four-tap into a second LDS image (rows 24 floats apart: the
+//           two tile rows of a 32-lane group read rows 48 floats = 16 banks apart), then the vertical one.
+namespace gp = glarepix;
+
+constexpr int kGlTile = 16;                       // outputs of a tiled workgroup, both ways
+constexpr int kGlIn = 2 * kGlTile + 2;            // fine pixels it stages, both ways: 2 * 16 and one more on either side
+constexpr int kGlInStride = kGlIn + 1;            // odd
+constexpr int kGlHStride = 24;
+
+// The fine image of a down step: the bright pass of the caller's colour image, or the records of the level before.
+struct BrightSrc {
+    const float* __restrict__ color; float e; gp::Glare G; int32_t cols;
+    __device__ __forceinline__ sq::f3 operator()(int32_t j, int32_t i) const {
+        return gp::bright(G, gp::exposed(e, G, sq::load3(color, (long long)j * cols + i)));
+    }
+};
+struct RecordSrc {
+    const float4* __restrict__ rec; int32_t cols;
+    __device__ __forceinline__ sq::f3 operator()(int32_t j, int32_t i) const {
+        const float4 v = rec[(long long)j * cols + i];
+        return sq::mk(v.x, v.y, v.z);
+    }
+};
+
+template <bool BRIGHT>
+__global__ __launch_bounds__(kBlock) void sq_gl_down_direct(const int32_t r, const int32_t c, const float* __restrict__ color,
+                                                            const float* __restrict__ d_exposure, const float exposure, const gp::Glare G,
+                                                            const float4* __restrict__ fine, float4* __restrict__ coarse,
+                                                            const long long tiles, const long long tiles_x) {
+    const int32_t R = gp::half_up(r), C = gp::half_up(c);
+    const float e = BRIGHT ? (d_exposure ? *d_exposure : exposure) : 0.0f;
+    for (long long t = blockIdx.x; t < tiles; t += gridDim.x) {
+        const long long ty = t / tiles_x, tx = t - ty * tiles_x;
+        const long long x = tx * kDirW + (threadIdx.x & (kDirW - 1)), y = ty * kDirH + (threadIdx.x / kDirW);
+        if (x >= C || y >= R) continue;
+        sq::f3 v;
+        if (BRIGHT) v = gp::down(BrightSrc{ color, e, G, c }, r, c, (int32_t)y, (int32_t)x);
+        else v = gp::down(RecordSrc{ fine, c }, r, c, (int32_t)y, (int32_t)x);
+        coarse[y * C + x] = make_float4(v.x, v.y, v.z, 0.0f);
+    }
+}
+
+template <bool BRIGHT>
+__global__ __launch_bounds__(kBlock) void sq_gl_down_tiled(const int32_t r, const int32_t c, const float* __restrict__ color,
+                                                           const float* __restrict__ d_exposure, const float exposure, const gp::Glare G,
+                                                           const float4* __restrict__ fine, float4* __restrict__ coarse,
+                                                           const long long tiles, const long long tiles_x) {
+    __shared__ float l_in[3][kGlIn * kGlInStride];
+    __shared__ float l_h[3][kGlIn * kGlHStride];
+    const int32_t R = gp::half_up(r), C = gp::half_up(c);
+    const float e = BRIGHT ? (d_exposure ? *d_exposure : exposure) : 0.0f;
+    const int lx = threadIdx.x & (kGlTile - 1), ly = threadIdx.x / kGlTile;
+    for (long long t = blockIdx.x; t < tiles; t += gridDim.x) {
+        const long long ty = t / tiles_x, tx = t - ty * tiles_x;
+        // cell (iy, ix) of the LDS image holds the fine pixel (y0 + iy, x0 + ix), clamped to the fine image as the taps are: a tap
+        // then needs no clamp of its own, and no load leaves the image
+        const long long y0 = 2 * ty * kGlTile - 1, x0 = 2 * tx * kGlTile - 1;
+        for (int i = threadIdx.x; i < kGlIn * kGlIn; i += kBlock) {
+            const int iy = i / kGlIn, ix = i - iy * kGlIn;
+            const long long gy = y0 + iy, gx = x0 + ix;
+            const int32_t j = (int32_t)(gy < 0 ? 0 : gy > r - 1 ? r - 1 : gy), k = (int32_t)(gx < 0 ? 0 : gx > c - 1 ? c - 1 : gx);
+            sq::f3 v;
+            if (BRIGHT) v = BrightSrc{ color, e, G, c }(j, k);
+            else v = RecordSrc{ fine, c }(j, k);
+            const int at = iy * kGlInStride + ix;
+            l_in[0][at] = v.x; l_in[1][at] = v.y; l_in[2][at] = v.z;
+        }
+        __syncthreads();
+        for (int i = threadIdx.x; i < kGlIn * kGlTile; i += kBlock) {          // h(j, x) of the 34 fine rows and 16 output columns
+            const int iy = i / kGlTile, ox = i - iy * kGlTile;
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch) {
+                const float* p = &l_in[ch][iy * kGlInStride + 2 * ox];
+                l_h[ch][iy * kGlHStride + ox] = gp::tap4(p[0], p[1], p[2], p[3]);
+            }
+        }
+        __syncthreads();
+        const long long y = ty * kGlTile + ly, x = tx * kGlTile + lx;
+        if (x < C && y < R) {
+            float o[3];
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch) {
+                const float* q = &l_h[ch][2 * ly * kGlHStride + lx];
+                o[ch] = gp::tap4(q[0], q[kGlHStride], q[2 * kGlHStride], q[3 * kGlHStride]);
+            }
+            coarse[y * C + x] = make_float4(o[0], o[1], o[2], 0.0f);
+        }
+        __syncthreads();        // the next tile's image overwrites this one
+    }
+}
+
+// A_k = B_k + spread * U(A_k+1), in place on level k (r x c); the coarse level is R x C.
+__global__ __launch_bounds__(kBlock) void sq_gl_up_add(const int32_t r, const int32_t c, const int32_t R, const int32_t C,
+                                                       const float4* __restrict__ coarse, float4* __restrict__ fine, const float spread,
+                                                       const long long tiles, const long long tiles_x) {
+    for (long long t = blockIdx.x; t < tiles; t += gridDim.x) {
+        const long long ty = t / tiles_x, tx = t - ty * tiles_x;
+        const long long x = tx * kDirW + (threadIdx.x & (kDirW - 1)), y = ty * kDirH + (threadIdx.x / kDirW);
+        if (x >= c || y >= r) continue;
+        const sq::f3 u = gp::up(RecordSrc{ coarse, C }, R, C, (int32_t)y, (int32_t)x);
+        const float4 b = fine[y * c + x];
+        const sq::f3 a = gp::add_scaled(sq::mk(b.x, b.y, b.z), spread, u);
+        fine[y * c + x] = make_float4(a.x, a.y, a.z, 0.0f);
+    }
+}
+
+// One pixel of d_out from the colour c at pixel p: x + strength * U(A_0), or x alone.
+template <bool GLARE>
+__device__ __forceinline__ sq::f3 composite_pixel(const long long p, const int32_t cols, const float e, const gp::Glare& G, const sq::f3 c,
+                                                  const float4* __restrict__ a0, const int32_t R, const int32_t C) {
+    const sq::f3 x = gp::exposed(e, G, c);
+    if (!GLARE) return x;
+    const uint32_t y = (uint32_t)p / (uint32_t)cols;                // p <= 2^31 - 2
+    const uint32_t xx = (uint32_t)p - y * (uint32_t)cols;
+    return gp::add_scaled(x, G.strength, gp::up(RecordSrc{ a0, C }, R, C, (int32_t)y, (int32_t)xx));
+}
+
+// d_out may be d_color (no __restrict__ on either): a lane reads the colour of its own pixels alone, before it writes them.
+// One pixel a lane: asks nothing of the pointers.
+template <bool GLARE>
+__global__ __launch_bounds__(kBlock) void sq_gl_composite1(const long long n, const int32_t cols, const float* color,
+                                                           const float* __restrict__ d_exposure, const float exposure, const gp::Glare G,
+                                                           const float4* __restrict__ a0, const int32_t R, const int32_t C, float* out) {
+    const float e = d_exposure ? *d_exposure : exposure;
+    for (long long p = (long long)blockIdx.x * kBlock + threadIdx.x; p < n; p += (long long)gridDim.x * kBlock)
+        sq::store3(out, p, composite_pixel<GLARE>(p, cols, e, G, sq::load3(color, p), a0, R, C));
+}
+
+// Four consecutive pixels a lane: color and out are 16-byte aligned.  The n % 4 pixels at the end are taken one a lane by the first
+// lanes of workgroup 0.
+template <bool GLARE>
+__global__ __launch_bounds__(kBlock) void sq_gl_composite4(const long long n, const int32_t cols, const float* color,
+                                                           const float* __restrict__ d_exposure, const float exposure, const gp::Glare G,
+                                                           const float4* __restrict__ a0, const int32_t R, const int32_t C, float* out) {
+    const float e = d_exposure ? *d_exposure : exposure;
+    const long long quads = n / 4;
+    for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < quads; i += (long long)gridDim.x * kBlock) {
+        const float4* src = reinterpret_cast<const float4*>(color) + 3 * i;
+        const float4 a = src[0], b = src[1], c = src[2];
+        const float in[12] = { a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, c.x, c.y, c.z, c.w };
+        float o[12];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const sq::f3 v = composite_pixel<GLARE>(4 * i + k, cols, e, G, sq::mk(in[3 * k], in[3 * k + 1], in[3 * k + 2]), a0, R, C);
+            o[3 * k] = v.x; o[3 * k + 1] = v.y; o[3 * k + 2] = v.z;
+        }
+        float4* dst = reinterpret_cast<float4*>(out) + 3 * i;
+        dst[0] = make_float4(o[0], o[1], o[2], o[3]);
+        dst[1] = make_float4(o[4], o[5], o[6], o[7]);
+        dst[2] = make_float4(o[8], o[9], o[10], o[11]);
+    }
+    const long long p = 4 * quads + threadIdx.x;
+    if (blockIdx.x == 0 && p < n) sq::store3(out, p, composite_pixel<GLARE>(p, cols, e, G, sq::load3(color, p), a0, R, C));
+}
+
+// The form of the down step into level k when the caller leaves the choice (form = 0).  Measured (tools/gpu_glare.py, DESIGN.md 4.27,
+// three rounds in turn): bright-and-down with the composite takes 0.0508 ms tiled against 0.0590 ms direct at 1080 x 1920 and 0.401
+// against 0.552 ms at 4320 x 7680, the direct form's own spread being 0.0003 and 0.0008 ms; the coarse levels together take 0.035 ms
+// tiled against 0.030 ms direct and 0.137 against 0.133 ms: there the tiled form does not pay.
+int auto_glare_form(int level) { return level == 0 ? SQ_DENOISE_FORM_TILED : SQ_DENOISE_FORM_DIRECT; }
+
+struct GlareLevels { int32_t rows[gp::kMaxLevels], cols[gp::kMaxLevels]; size_t at[gp::kMaxLevels]; size_t bytes; };
+
+// r_k, c_k, the byte offset of level k in the workspace, and the bytes of all of them.
+GlareLevels glare_levels(int32_t rows, int32_t cols, int32_t levels) {
+    GlareLevels L = {};
+    int32_t r = rows, c = cols;
+    for (int k = 0; k < levels; ++k) {
+        r = gp::half_up(r); c = gp::half_up(c);
+        L.rows[k] = r; L.cols[k] = c; L.at[k] = L.bytes;
+        L.bytes += sizeof(float4) * (size_t)r * (size_t)c;
+    }
+    return L;
+}
+
+bool finite_nonneg(float v) { return v >= 0.0f && v < __builtin_inff(); }
+
+// Everything sq_denoise_glare_device refuses, in the order of the header's list.  Touches neither the device nor a buffer.
+int check_glare(int32_t rows, int32_t cols, const float* d_color, const float* d_exposure, const sq_denoise_glare_params* P, float* d_out,
+                void* d_work, size_t work_bytes) {
+    if (!d_color || !P || !d_out) return sq_set_error("null argument: d_color, params and d_out are required");
+    if (rows < 1 || cols < 1) return sq_set_error("rows and cols must be at least 1 (got %d x %d)", rows, cols);
+    if ((long long)rows * cols > kMaxPixels) return sq_set_error("%d x %d pixels exceed 2^31 - 1 pixels in one call", rows, cols);
+    if (P->levels < 0 || P->levels > gp::kMaxLevels) return sq_set_error("levels must be in 0..%d (got %d)", gp::kMaxLevels, P->levels);
+    if (P->form < 0 || P->form > SQ_DENOISE_N_FORMS) return sq_set_error("form must be in 0..%d (got %d)", SQ_DENOISE_N_FORMS, P->form);
+    if (!finite_nonneg(P->threshold)) return sq_set_error("threshold must be a finite number >= 0 (got %g)", (double)P->threshold);
+    if (!(P->ceiling > P->threshold && P->ceiling < __builtin_inff()))
+        return sq_set_error("ceiling must be a finite number > threshold (got %g, threshold %g)", (double)P->ceiling, (double)P->threshold);
+    if (!finite_nonneg(P->spread)) return sq_set_error("spread must be a finite number >= 0 (got %g)", (double)P->spread);
+    if (!finite_nonneg(P->strength)) return sq_set_error("strength must be a finite number >= 0 (got %g)", (double)P->strength);
+    if (P->levels >= 1) {
+        if (!d_work) return sq_set_error("null argument: d_work is required with levels >= 1");
+        const size_t need = sq_denoise_glare_work_bytes(rows, cols, P->levels);
+        if (work_bytes < need)
+            return sq_set_error("work_bytes = %zu is too small: %d levels of a %d x %d image need %zu", work_bytes, P->levels, rows, cols, need);
+        if ((uintptr_t)d_work % 16 != 0) return sq_set_error("d_work must be 16-byte aligned");
+    }
+    const size_t n = (size_t)rows * (size_t)cols;
+    const NamedRange r[4] = { { "d_color", d_color, 12 * n }, { "d_exposure", d_exposure, 4 }, { "d_out", d_out, 12 * n }, { "d_work", d_work, work_bytes } };
+    const int twins[1][2] = { { 0, 2 } };                                        // d_out == d_color
+    return refuse_overlaps(r, 4, " (only d_out == d_color may share memory)", twins, 1);
+}
+
+template <bool BRIGHT>
+void launch_glare_down(int form, int32_t r, int32_t c, const float* color, const float* d_exposure, float exposure, const gp::Glare& G,
+                       const float4* fine, float4* coarse, hipStream_t stream) {
+    const long long R = gp::half_up(r), C = gp::half_up(c);
+    if (form == SQ_DENOISE_FORM_TILED) {
+        const long long tx = (C + kGlTile - 1) / kGlTile, ty = (R + kGlTile - 1) / kGlTile;
+        hipLaunchKernelGGL(sq_gl_down_tiled<BRIGHT>, dim3(grid_for(tx * ty)), dim3(kBlock), 0, stream, r, c, color, d_exposure, exposure, G, fine,
+                           coarse, tx * ty, tx);
+    } else {
+        const long long tx = (C + kDirW - 1) / kDirW, ty = (R + kDirH - 1) / kDirH;
+        hipLaunchKernelGGL(sq_gl_down_direct<BRIGHT>, dim3(grid_for(tx * ty)), dim3(kBlock), 0, stream, r, c, color, d_exposure, exposure, G, fine,
+                           coarse, tx * ty, tx);
+    }
+}
+
+int enqueue_glare(int32_t device, int32_t rows, int32_t cols, const float* d_color, const float* d_exposure, const sq_denoise_glare_params& P,
+                  float* d_out, void* d_work, void* hip_stream) {
+    SQ_HIP(hipSetDevice(device));
+    hipStream_t stream = (hipStream_t)hip_stream;
+    const gp::Glare G{ { P.gain[0], P.gain[1], P.gain[2] }, P.threshold, P.ceiling, P.spread, P.strength };
+    const long long n = (long long)rows * cols;
+    const GlareLevels L = glare_levels(rows, cols, P.levels);
+    float4* level[gp::kMaxLevels] = {};
+    for (int k = 0; k < P.levels; ++k) level[k] = (float4*)((char*)d_work + L.at[k]);
+    for (int k = 0; k < P.levels; ++k) {
+        const int form = P.form == SQ_DENOISE_FORM_AUTO ? auto_glare_form(k) : P.form;
+        if (k == 0) launch_glare_down<true>(form, rows, cols, d_color, d_exposure, P.exposure, G, nullptr, level[0], stream);
+        else launch_glare_down<false>(form, L.rows[k - 1], L.cols[k - 1], nullptr, nullptr, 0.0f, G, level[k - 1], level[k], stream);
+        SQ_HIP(hipGetLastError());
+    }
+    for (int k = P.levels - 2; k >= 0; --k) {
+        const long long tx = ((long long)L.cols[k] + kDirW - 1) / kDirW, ty = ((long long)L.rows[k] + kDirH - 1) / kDirH;
+        hipLaunchKernelGGL(sq_gl_up_add, dim3(grid_for(tx * ty)), dim3(kBlock), 0, stream, L.rows[k], L.cols[k], L.rows[k + 1], L.cols[k + 1],
+                           level[k + 1], level[k], P.spread, tx * ty, tx);
+        SQ_HIP(hipGetLastError());
+    }
+    const bool wide = (uintptr_t)d_color % 16 == 0 && (uintptr_t)d_out % 16 == 0;
+    const long long lanes = wide ? (n + 3) / 4 : n;
+    const dim3 grid(grid_for((lanes + kBlock - 1) / kBlock)), block(kBlock);
+    const int32_t R0 = P.levels ? L.rows[0] : 0, C0 = P.levels ? L.cols[0] : 0;
+    if (P.levels) {
+        if (wide) hipLaunchKernelGGL(sq_gl_composite4<true>, grid, block, 0, stream, n, cols, d_color, d_exposure, P.exposure, G, level[0], R0, C0, d_out);
+        else      hipLaunchKernelGGL(sq_gl_composite1<true>, grid, block, 0, stream, n, cols, d_color, d_exposure, P.exposure, G, level[0], R0, C0, d_out);
+    } else {
+        if (wide) hipLaunchKernelGGL(sq_gl_composite4<false>, grid, block, 0, stream, n, cols, d_color, d_exposure, P.exposure, G, level[0], R0, C0, d_out);
+        else      hipLaunchKernelGGL(sq_gl_composite1<false>, grid, block, 0, stream, n, cols, d_color, d_exposure, P.exposure, G, level[0], R0, C0, d_out);
+    }
+    SQ_HIP(hipGetLastError());
+    return 0;
+}
+
 }  // namespace
+
+extern "C" size_t sq_denoise_glare_work_bytes(int32_t rows, int32_t cols, int32_t levels) {
+    if (rows < 1 || cols < 1 || (long long)rows * cols > kMaxPixels || levels < 0 || levels > gp::kMaxLevels) return 0;
+    return glare_levels(rows, cols, levels).bytes;
+}
+
+extern "C" int sq_denoise_glare_device(int32_t device, int32_t rows, int32_t cols, const float* d_color, const float* d_exposure,
+                                       const sq_denoise_glare_params* params, float* d_out, void* d_work, size_t work_bytes, void* hip_stream) {
+    if (check_glare(rows, cols, d_color, d_exposure, params, d_out, d_work, work_bytes)) return 1;
+    return enqueue_glare(device, rows, cols, d_color, d_exposure, *params, d_out, d_work, hip_stream);
+}
 
 extern "C" const char* sq_denoise_last_error(void) { return sq_error_buffer(); }
 extern "C" const char* sq_denoise_build_id(void) { return SQ_DENOISE_BUILD_ID; }

@@ -6,6 +6,9 @@ comes from the HIP kernels of csrc/sq_denoise.hip.  There is no fallback: a miss
 
 Sparse frames live here too (sparse_mask, upsample, lattice_offset): under the same guides, which pixels of a frame have to be traced
 -- a lattice and the holes -- and every other pixel from its traced neighbours on the same surface.
+
+So does the glare stage (glare, glare_work_bytes, make_glare_params): exposure, white balance and a bloom pyramid over a float frame,
+ahead of film.develop.
 """
 import collections
 import ctypes as C
@@ -16,7 +19,8 @@ from . import _plumbing as P
 # include/squigly_denoise.h; sq_denoise_last_error and the functions a caller uses
 EXPORTED_SYMBOLS = ["sq_denoise_last_error", "sq_denoise_build_id", "sq_denoise_pass_form", "sq_denoise_workspace_bytes",
                     "sq_denoise_variance_device", "sq_denoise_device", "sq_denoise_stage_device",
-                    "sq_denoise_sparse_mask_device", "sq_denoise_upsample_device"]
+                    "sq_denoise_sparse_mask_device", "sq_denoise_upsample_device",
+                    "sq_denoise_glare_work_bytes", "sq_denoise_glare_device"]
 
 FORMS = {"auto": 0, "direct": 1, "tiled": 2}          # params.form (SQ_DENOISE_FORM_*)
 # The prototype's parameters.  sigma_p has no default here: it is a length of the scene (denoise_frame derives it).
@@ -38,6 +42,14 @@ class SparseParams(C.Structure):
     _fields_ = [("sigma_p", C.c_float), ("cos_n", C.c_float)]
 
 
+class GlareParams(C.Structure):
+    """sq_denoise_glare_params."""
+    _fields_ = [("exposure", C.c_float), ("gain", C.c_float * 3), ("threshold", C.c_float), ("ceiling", C.c_float), ("levels", C.c_int32),
+                ("spread", C.c_float), ("strength", C.c_float), ("form", C.c_int32)]
+
+
+MAX_GLARE_LEVELS = 8
+GLARE_DEFAULTS = {"threshold": 1.0, "ceiling": 16.0, "levels": 5, "spread": 0.5, "strength": 0.1}
 MAX_STRIDE = 16               # of a sparse frame's lattice
 SPARSE_COS_N = 0.9            # the temporal stage's
 
@@ -46,6 +58,9 @@ def _declare(L):
     vp, i32 = C.c_void_p, C.c_int32
     L.sq_denoise_sparse_mask_device.argtypes = [i32] * 6 + [vp, vp, vp, C.POINTER(SparseParams), vp, vp]
     L.sq_denoise_upsample_device.argtypes = [i32] * 6 + [vp] * 6 + [C.POINTER(SparseParams), vp, vp, vp]
+    L.sq_denoise_glare_work_bytes.argtypes = [i32, i32, i32]
+    L.sq_denoise_glare_work_bytes.restype = C.c_size_t
+    L.sq_denoise_glare_device.argtypes = [i32, i32, i32, vp, vp, C.POINTER(GlareParams), vp, vp, C.c_size_t, vp]
     L.sq_denoise_pass_form.argtypes = [i32]
     L.sq_denoise_pass_form.restype = i32
     L.sq_denoise_workspace_bytes.argtypes = [i32, i32]
@@ -240,6 +255,94 @@ def upsample(color, guides, mask, stride, offset, var=None, out=None, stream=Non
                                                guides.normal.data_ptr(), guides.point.data_ptr(), mask.data_ptr(), C.byref(par),
                                                out_c.data_ptr(), P.ptr(out_v), P.stream_ptr(st)))
     return out_c, out_v
+
+
+def glare_work_bytes(rows, cols, levels):
+    """sq_denoise_glare_work_bytes: 16 bytes per pixel of the pyramid's levels; 0 for levels 0 and for what the call refuses."""
+    return int(lib().sq_denoise_glare_work_bytes(int(rows), int(cols), int(levels)))
+
+
+def _glare_number(name, v):
+    import numpy as np
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+        raise N.SquiglyError(f"{name} must be a number, got {v!r}")
+    with np.errstate(over="ignore"):
+        return float(np.float32(v))           # as the library will see it: 1e39 is infinite there, and 1 + 1e-9 is 1
+
+
+def make_glare_params(exposure=1.0, gain=(1.0, 1.0, 1.0), threshold=1.0, ceiling=16.0, levels=5, spread=0.5, strength=0.1, form=0):
+    """sq_denoise_glare_params; what the library would refuse of them is refused here, before any device work.  form by number or by
+    name (FORMS)."""
+    import math
+    try:
+        g = [_glare_number("gain", v) for v in gain]
+    except TypeError:
+        g = []
+    if len(g) != 3:
+        raise N.SquiglyError(f"gain must be three numbers (r, g, b), got {gain!r}")
+    t, c = _glare_number("threshold", threshold), _glare_number("ceiling", ceiling)
+    if not 0 <= t < math.inf:
+        raise N.SquiglyError(f"threshold must be a finite number >= 0, got {threshold!r}")
+    if not t < c < math.inf:
+        raise N.SquiglyError(f"ceiling must be a finite number > threshold, got {ceiling!r}")
+    if not P.is_integer(levels) or not 0 <= int(levels) <= MAX_GLARE_LEVELS:
+        raise N.SquiglyError(f"levels must be an integer in 0..{MAX_GLARE_LEVELS}, got {levels!r}")
+    s, w = _glare_number("spread", spread), _glare_number("strength", strength)
+    if not 0 <= s < math.inf:
+        raise N.SquiglyError(f"spread must be a finite number >= 0, got {spread!r}")
+    if not 0 <= w < math.inf:
+        raise N.SquiglyError(f"strength must be a finite number >= 0, got {strength!r}")
+    if isinstance(form, str):
+        if form not in FORMS:
+            raise N.SquiglyError(f"form must be one of {sorted(FORMS)} or a number, got {form!r}")
+        form = FORMS[form]
+    if not P.is_integer(form) or not 0 <= int(form) <= 2:
+        raise N.SquiglyError(f"form must be one of {sorted(FORMS)} or a number in 0..2, got {form!r}")
+    return GlareParams(_glare_number("exposure", exposure), (C.c_float * 3)(*g), t, c, int(levels), s, w, int(form))
+
+
+def glare(color, exposure=1.0, gain=(1.0, 1.0, 1.0), threshold=1.0, ceiling=16.0, levels=5, spread=0.5, strength=0.1, form=0, out=None,
+          work=None, stream=None):
+    """sq_denoise_glare_device on device tensors: the frame `color` (float32 [..., cols, 3]; leading dimensions are rows) times
+    `exposure` -- a number, or a float32 CUDA tensor of one element (film.expose()) -- and the white balance `gain`, plus `strength`
+    times the glare of what is brighter than `threshold`: a float32 tensor of color's shape, which film.develop takes at exposure 1.
+    levels = 0: exposure and gain alone.  out: the tensor to receive the result (None = allocate); it may be color itself.  work: a
+    uint8 CUDA tensor of at least glare_work_bytes(rows, cols, levels) bytes, 16-byte aligned (None = allocated under the stream and
+    handed back in its order).  Enqueued on `stream`."""
+    import torch
+    if (not isinstance(color, torch.Tensor) or color.dim() < 2 or color.shape[-1] != 3 or color.dtype != torch.float32 or not color.is_cuda
+            or not color.is_contiguous()):
+        got = f"{color.dtype} {tuple(color.shape)} on {color.device}" if isinstance(color, torch.Tensor) else type(color).__name__
+        raise N.SquiglyError(f"color must be a contiguous torch.float32 CUDA tensor of shape [..., cols, 3], got {got}")
+    dev, cols = color.device, int(color.shape[-2])
+    rows = int(color.numel() // (3 * cols)) if cols else 0
+    if rows < 1 or cols < 1:
+        raise N.SquiglyError(f"rows and cols must be at least 1 (got {rows} x {cols})")
+    if rows * cols > 2 ** 31 - 1:
+        raise N.SquiglyError(f"{rows} x {cols} pixels exceed 2^31 - 1 pixels in one call")
+    e_t = exposure if isinstance(exposure, torch.Tensor) else None
+    if e_t is not None:
+        P.tensor("exposure", e_t, (1,), torch.float32, dev)
+    par = make_glare_params(1.0 if e_t is not None else exposure, gain, threshold, ceiling, levels, spread, strength, form)
+    if out is not None:
+        P.tensor("out", out, tuple(color.shape), torch.float32, dev)
+    need = glare_work_bytes(rows, cols, par.levels)
+    if work is not None:
+        if not isinstance(work, torch.Tensor) or work.dim() != 1 or work.dtype != torch.uint8 or work.device != dev or not work.is_contiguous():
+            raise N.SquiglyError(f"work must be a contiguous torch.uint8 tensor of at least {need} bytes on {dev}")
+        if work.numel() < need:
+            raise N.SquiglyError(f"work holds {work.numel()} bytes: {par.levels} levels of a {rows} x {cols} image need {need}")
+        if par.levels and work.data_ptr() % 16:
+            raise N.SquiglyError("work must be 16-byte aligned")
+    _, st = P.call_stream(dev, stream)
+    with torch.cuda.stream(st):      # the result and an absent workspace are allocated (and the workspace freed) in the order of the call's stream
+        if out is None:
+            out = torch.empty(tuple(color.shape), dtype=torch.float32, device=dev)
+        if work is None and par.levels:
+            work = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+        check(lib().sq_denoise_glare_device(dev.index or 0, rows, cols, color.data_ptr(), P.ptr(e_t), C.byref(par), out.data_ptr(),
+                                            P.ptr(work) if par.levels else None, work.numel() if par.levels else 0, P.stream_ptr(st)))
+    return out
 
 
 def default_sigma_p(bounds):

@@ -198,6 +198,48 @@ def develop(color, exposure=1.0, curve="reference", white=math.inf, lut=None, di
     return (rgb, disp) if want_display else rgb
 
 
+class Glare:
+    """The glare of a Film (denoise.glare's parameters): what of the exposed frame is brighter than `threshold` -- saturating at `ceiling` --
+    is carried down `levels` pyramid levels and up again, each coarser level weighing `spread` in the one above it, and added to the
+    frame at `strength`.  A value object: what the library would refuse is refused here."""
+    __slots__ = ("threshold", "ceiling", "levels", "spread", "strength")
+
+    def __init__(self, threshold=1.0, ceiling=16.0, levels=5, spread=0.5, strength=0.1):
+        from .denoise import make_glare_params
+        make_glare_params(threshold=threshold, ceiling=ceiling, levels=levels, spread=spread, strength=strength)
+        for name, v in (("threshold", threshold), ("ceiling", ceiling), ("spread", spread), ("strength", strength)):
+            object.__setattr__(self, name, float(v))
+        object.__setattr__(self, "levels", int(levels))
+
+    def __setattr__(self, name, value):
+        raise AttributeError("a Glare does not change: make another")
+
+    def params(self):
+        return {name: getattr(self, name) for name in self.__slots__}
+
+    def __eq__(self, other):
+        return isinstance(other, Glare) and self.params() == other.params()
+
+    def __hash__(self):
+        return hash(tuple(self.params().values()))
+
+    def __repr__(self):
+        return "Glare(" + ", ".join(f"{k}={v!r}" for k, v in self.params().items()) + ")"
+
+
+def balance_arg(balance):
+    """balance= of a Film: None, or three numbers (the white balance's factors for r, g, b) as floats."""
+    if balance is None:
+        return None
+    try:
+        b = tuple(_number("balance", v) for v in balance)
+    except TypeError:
+        b = ()
+    if len(b) != 3:
+        raise N.SquiglyError(f"balance must be None or three numbers (r, g, b), got {balance!r}")
+    return b
+
+
 class Film:
     """The display stage as an object: film(avg) is the uint8 image of the float32 CUDA frame avg, developed on avg's device without a
     host wait.  curve, exposure, white, dither: develop's.  lut: a table as a numpy array or a tensor (srgb_lut(), gamma_lut(g)); it
@@ -207,10 +249,16 @@ class Film:
     film's own one-float state and develop under that exposure, so a sequence adapts at `rate` per frame.  exposure_state: that
     state (a Python float; None before the first frame; reading it waits for the device), settable for checkpoints; reset() forgets
     it.  The state lives on the device of the first frame: a frame from another device is refused until reset(), never exposed from
-    nothing without a word.  Film() is the reference curve at exposure 1: the bytes the renderer itself writes."""
+    nothing without a word.  Film() is the reference curve at exposure 1: the bytes the renderer itself writes.
+    glare (a Glare) and balance (three white-balance factors), both None by default: with either, the frame is metered as before --
+    unbloomed and unbalanced -- then denoise.glare makes the exposed, balanced frame with its glare (none without a Glare) in a
+    tensor of its own, and develop takes that at exposure 1, which is exact."""
 
-    def __init__(self, curve="reference", exposure=1.0, white=math.inf, lut=None, dither=False, auto=None):
+    def __init__(self, curve="reference", exposure=1.0, white=math.inf, lut=None, dither=False, auto=None, glare=None, balance=None):
         self.curve, self.exposure, self.white, self.dither = curve, exposure, white, dither
+        if glare is not None and not isinstance(glare, Glare):
+            raise N.SquiglyError(f"glare must be None or a Glare, got {glare!r}")
+        self.glare, self.balance = glare, balance_arg(balance)
         if lut is not None and not hasattr(lut, "is_cuda"):
             lut = np.ascontiguousarray(lut, np.float32)
             if lut.ndim != 1 or not 2 <= lut.shape[0] <= 65536:
@@ -275,6 +323,10 @@ class Film:
                     self._state = torch.full((1,), 0.0 if self._pending is None else self._pending, dtype=torch.float32, device=dev)
                     self._pending = None
                 e = expose(histogram(avg, stream=st), prev=self._state, out=self._state, stream=st, **self.auto)
+            if self.glare is not None or self.balance is not None:
+                from .denoise import glare
+                g = self.glare.params() if self.glare is not None else {"levels": 0}
+                avg, e = glare(avg, exposure=e, gain=self.balance or (1.0, 1.0, 1.0), stream=st, **g), 1.0
             return develop(avg, exposure=e, curve=self.curve, white=self.white, lut=lut, dither=self.dither, stream=st)
 
     __call__ = film
