@@ -12,6 +12,7 @@ import glare_restatement as R
 import temporal_room as TR
 from bitcmp import same
 from conftest import DATA
+from guarded_alloc import GUARD, guarded, untouched     # (behind d_out and behind the workspace)
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
@@ -22,7 +23,6 @@ f32 = np.float32
 SIZES = [(1, 1), (1, 2), (2, 1), (3, 5), (16, 16), (17, 33), (31, 32), (33, 130), (37, 70)]
 SIZE_IDS = [f"{r}x{c}" for r, c in SIZES]
 LEVELS = (0, 1, 2, 3, 8)
-GUARD = 64                    # floats behind d_out and behind the workspace that must stay as they were
 SETTINGS = dict(gain=(1.5, 1.0, 0.6), threshold=0.5, ceiling=8.0, spread=0.6, strength=0.3)
 
 
@@ -46,20 +46,6 @@ def fm(sqt, torch):
 
 def dev(torch, a):
     return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def guarded(torch, shape, skip, fill):
-    """(view, whole): a float32 tensor of `shape` that starts `skip` floats into its allocation and ends GUARD floats before its end,
-    all of it filled with `fill`."""
-    n = int(np.prod(shape))
-    whole = torch.full((skip + n + GUARD,), fill, dtype=torch.float32, device="cuda")
-    return whole[skip:skip + n].view(*shape), whole
-
-
-def untouched(whole, skip, n, fill):
-    h = whole.cpu().numpy()
-    rest = np.concatenate([h[:skip], h[skip + n:]])
-    return len(rest) == skip + GUARD and (np.isnan(rest).all() if np.isnan(fill) else (rest == f32(fill)).all())
 
 
 def run(torch, dn, px, skip, levels, form, exposure, in_place=False, **settings):
