@@ -4,8 +4,10 @@
  *
  * The library knows nothing of scenes, trees or generators: it maps device images to device images.  Its inputs are what the other
  * libraries' calls leave behind: the frame's mean colour, the variance of sq_denoise_variance_device, and d_tri, d_point and the
- * unit normal of the first hit (DeviceScene.guides).  The geometry is static, so the world-space points of two frames are compared
- * directly: there are no motion vectors.
+ * unit normal of the first hit (DeviceScene.guides).  sq_temporal_accumulate_device takes the geometry as static: the world-space
+ * points of two frames are compared directly.  sq_temporal_accumulate_moving_device (below) takes rigid objects that move between
+ * two frames: a pixel's point and normal go back through its object's transform first, and a clamp to the neighbourhood's colours
+ * answers the light that a moving object changes on surfaces that did not move.
  *
  * Conventions (squigly_denoise.h's)
  *  - plain C; every function that returns int returns 0 on success, non-zero on failure, and sq_temporal_last_error() then holds
@@ -20,8 +22,9 @@
  *
  * Whole frames on one device only: a shard's pixels reproject into rows it does not hold.
  *
- * Out of scope: shards and more than one GPU; lens, shutter and adaptive frames as the per-frame renderer; cast frames; moving
- * geometry; neighbourhood colour clamping; the C++ command line.
+ * Out of scope: shards and more than one GPU; lens, shutter and adaptive frames as the per-frame renderer; cast frames; deforming
+ * meshes and per-vertex motion (objects are rigid); moving lights and a sky that changes; a history length that shortens where the
+ * clamp bites; the C++ command line.
  *
  * The history block is opaque to callers: sq_temporal_history_bytes(rows, cols) bytes, 16-byte aligned, three planes of 16-byte
  * records, a record per pixel in each (colour.rgb + variance; normal.xyz + length; point.xyz + triangle), so that a bilinear tap
@@ -51,6 +54,27 @@
  *       a = alpha_min if a < alpha_min;  then a = d_alpha[p] if d_alpha is given and a < d_alpha[p]
  *       out_c = hc + a * (c - hc);  om = 1 - a;  out_v = (om * om) * hv + (a * a) * v;  len = min(m + 1, max_history)
  *   The next block holds out_c, out_v, len and the CURRENT guides (tri, n_p, P_p), whichever branch was taken.
+ *
+ * The moving call's contract is the one above with these additions, each operation again one fp32 operation in this order.
+ *   Objects (d_object with n_tris, d_back with n_objects; both or neither).  d_object[t] is the rigid object of triangle t of the
+ *   CURRENT scene (an index < 0: static); d_back holds 12 floats an object, the row-major 3 x 4 B = [L | t] that takes a world point
+ *   of the current frame to where the same surface point was in the previous frame.  For a pixel with tri >= 0, when d_prev is given:
+ *       o = (tri < n_tris) ? d_object[tri] : -1
+ *       if 0 <= o < n_objects:  P'_i = ((L_i0 * P.x + L_i1 * P.y) + L_i2 * P.z) + t_i;  n'_i = (L_i0 * n.x + L_i1 * n.y) + L_i2 * n.z
+ *       otherwise P' = P_p and n' = n_p, bit for bit.
+ *   n' is not renormalised.  P' and n' take the place of P_p and n_p in the projection, in dn, in d = P_q - P' and in pd.  The next
+ *   block still holds the current guides.  An index outside its table is never read through: a wrong index is data, not a fault.
+ *   Clamp (clamp = { radius, k }; NULL = off).  The window is the taps q = (y + j, x + i), j = -radius .. radius (outer),
+ *   i = -radius .. radius (inner); only taps inside the image with tri[q] >= 0 count.  Per channel of the CURRENT d_color, the sums
+ *   from +0 and n counted in fp32 (n = n + 1):
+ *       s = s + C_q;  s2 = s2 + C_q * C_q
+ *       mu = s / n;  vr = s2 / n - mu * mu;  vr = 0 unless vr > 0;  sd = sqrtf(vr);  ks = k * sd;  lo = mu - ks;  hi = mu + ks
+ *   and after hc = sc / sw, before the blend, per channel:  if (hc < lo) hc = lo;  if (hc > hi) hc = hi  (a NaN compares false and
+ *   leaves hc alone).  hv, a and len stay as they are.  The window is read only where history is blended.
+ *   Flags (d_out_flags): bit 0 history was blended; bit 1 some channel was clamped; bit 2 the pixel went back through an object
+ *   (d_prev given, tri >= 0, 0 <= o < n_objects -- whether or not it then found history).
+ *   With d_object, d_back, clamp and d_out_flags all NULL the call writes the bytes of sq_temporal_accumulate_device, the next
+ *   block included.
  */
 #ifndef SQUIGLY_TEMPORAL_H
 #define SQUIGLY_TEMPORAL_H
@@ -98,6 +122,39 @@ int sq_temporal_accumulate_device(int32_t device, int32_t rows, int32_t cols,
                                   const sq_temporal_params* params,
                                   void* d_next /* history block */, float* d_out, float* d_out_var,
                                   int32_t* d_out_len /* optional */, void* hip_stream);
+
+typedef struct {
+    int32_t radius;   /* 1..3: the window is (2 radius + 1)^2 taps */
+    float   k;        /* >= 0: the bounds are mu -/+ k standard deviations; +inf clamps nothing where sd > 0 */
+} sq_temporal_clamp;
+
+/* Kernel forms of the clamp's window (form).  Every form gives the same bits. */
+#define SQ_TEMPORAL_FORM_AUTO   0   /* the library's choice */
+#define SQ_TEMPORAL_FORM_DIRECT 1   /* every tap of the window is read from d_color and d_tri (L1 / L2) */
+#define SQ_TEMPORAL_FORM_TILED  2   /* the tile and its halo of `radius` pixels are staged in LDS once */
+#define SQ_TEMPORAL_N_FORMS     2
+
+#define SQ_TEMPORAL_FLAG_BLENDED 1
+#define SQ_TEMPORAL_FLAG_CLAMPED 2
+#define SQ_TEMPORAL_FLAG_MOVED   4
+
+/* sq_temporal_accumulate_device under geometry that moves (the contract's additions above): d_object (n_tris int32) and d_back
+ * (n_objects * 12 floats) go together, clamp and d_out_flags (rows * cols bytes) are optional; form is read under a clamp only.
+ * Refused before anything is enqueued: everything sq_temporal_accumulate_device refuses; n_tris or n_objects < 0; one of d_object
+ * and d_back without the other; a table pointer with a count of 0; clamp.radius outside 1..3, clamp.k NaN or < 0; form outside
+ * 0..2; any overlap that involves d_object, d_back or d_out_flags; and, under a clamp, d_out == d_color (neighbours are read;
+ * d_out_var == d_var stays allowed). */
+int sq_temporal_accumulate_moving_device(int32_t device, int32_t rows, int32_t cols,
+                                         const float* d_color, const float* d_var,
+                                         const int32_t* d_tri, const float* d_normal, const float* d_point,
+                                         const float* d_alpha /* optional */,
+                                         const sq_camera* prev_cam, const void* d_prev /* optional history block */,
+                                         const sq_temporal_params* params,
+                                         const int32_t* d_object /* optional */, int32_t n_tris,
+                                         const float* d_back /* optional */, int32_t n_objects,
+                                         const sq_temporal_clamp* clamp /* optional */, int32_t form,
+                                         void* d_next /* history block */, float* d_out, float* d_out_var,
+                                         int32_t* d_out_len /* optional */, uint8_t* d_out_flags /* optional */, void* hip_stream);
 
 /* A history block as plain images, for tests and checkpoints: every output is optional (NULL), but at least one must be given.
  * Refused: d_hist NULL or misaligned, no output, a bad size, any overlap. */

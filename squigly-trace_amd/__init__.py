@@ -4,8 +4,8 @@ Import with importlib (the directory name contains a hyphen):
     sqt = importlib.import_module("squigly-trace_amd")
 """
 from ._native import Camera, Shard, SquiglyError, lib, LIB_PATH, EXPORTED_SYMBOLS, debug_eval, build_id, REFERENCE_LIGHT, MAX_LIGHTS  # noqa: F401
-from .scene import BIH, Mesh, load_camera, camera_from_text, rot_matrix_rads       # noqa: F401
-from .render import Settings, render, render_rgb8, render_f32, render_progressive, render_adaptive, render_views_rgb8, render_lens_rgb8, render_sequence, render_sparse   # noqa: F401
+from .scene import BIH, Mesh, load_camera, camera_from_text, rot_matrix_rads, moved_mesh       # noqa: F401
+from .render import Settings, render, render_rgb8, render_f32, render_progressive, render_adaptive, render_views_rgb8, render_lens_rgb8, render_sequence, render_sparse, render_moving_sequence   # noqa: F401
 from .png import write_png                                                          # noqa: F401
 # the filter: sqt.denoise is the function; its module is importlib.import_module("squigly-trace_amd.denoise")
 from .denoise import denoise, denoise_variance, denoise_frame, Guides                # noqa: F401

@@ -10,7 +10,7 @@ import os
 import sys
 import time
 
-from . import BIH, Lens, Mesh, Motion, Settings, camera_from_text, lib, load_camera, render, render_adaptive, render_lens_rgb8, render_progressive, render_sequence, render_views_rgb8, write_png
+from . import BIH, Lens, Mesh, Motion, Settings, camera_from_text, lib, load_camera, render, render_adaptive, render_lens_rgb8, render_moving_sequence, render_progressive, render_sequence, render_views_rgb8, write_png
 from ._native import SquiglyError
 
 
@@ -157,6 +157,31 @@ def views_file(path):
         raise argparse.ArgumentTypeError(f"{path}: {e}")
 
 
+def poses_file(path):
+    """--poses: a float array [frames, materials, 3, 4] from a .npy file (never a pickle)."""
+    import numpy as np
+    try:
+        poses = np.load(path, allow_pickle=False)
+    except (OSError, ValueError) as e:
+        raise argparse.ArgumentTypeError(f"cannot read {path}: {e}")
+    if poses.ndim != 4 or poses.shape[2:] != (3, 4) or poses.dtype.kind != "f" or not np.isfinite(poses).all():
+        raise argparse.ArgumentTypeError(f"{path}: expected a finite float array of shape [frames, materials, 3, 4], got "
+                                         f"{poses.dtype} {poses.shape}")
+    return poses
+
+
+def history_clamp(text):
+    """--history-clamp K[,RADIUS] as Temporal's clamp: (k, radius)."""
+    parts = text.split(",")
+    try:
+        k, radius = float(parts[0]), (int(parts[1]) if len(parts) == 2 else 1)
+        if len(parts) > 2 or not k >= 0 or not 1 <= radius <= 3:
+            raise ValueError
+    except ValueError:
+        raise argparse.ArgumentTypeError("expected K[,RADIUS] with K >= 0 and RADIUS in 1..3")
+    return k, radius
+
+
 def view_paths(save_path, n):
     """Where the CLI writes the images of n views: <savepath stem>_<i:04d><ext>."""
     stem, ext = os.path.splitext(save_path)
@@ -228,6 +253,14 @@ def build_parser():
     p.add_argument("--temporal", type=unit_float, nargs="?", const=True, default=None, metavar="ALPHA_MIN",
                    help="With --sequence: accumulate every frame over the frames before it, reprojected through its first hits; "
                         "ALPHA_MIN is the least weight of the new frame (default 0.1)")
+    # geometry that moves rigidly from frame to frame, and the clamp that goes with it (sq_temporal_accumulate_moving_device)
+    p.add_argument("--poses", type=poses_file, default=None, metavar="FILE.npy",
+                   help="With --sequence --temporal: a float array [frames, materials, 3, 4], the pose [R | t] of every material of "
+                        "the scene in every frame (world = R local + t); every frame's scene is built from the moved mesh and its "
+                        "history is reprojected through the move")
+    p.add_argument("--history-clamp", type=history_clamp, default=None, metavar="K[,RADIUS]",
+                   help="With --sequence --temporal: hold the history's colour to K standard deviations around the mean of the frame's "
+                        "(2 RADIUS + 1)^2 neighbourhood before it is blended (RADIUS 1..3, default 1)")
     # not a flag of the reference: sparse frames (include/squigly_denoise.h: the lattice moves from frame to frame)
     p.add_argument("--sparse", type=lattice_stride, default=None, metavar="S",
                    help="With --sequence: trace only every S-th pixel of every S-th row of a frame (1..16; the lattice moves from "
@@ -341,6 +374,14 @@ def parse_args(argv=None):
         p.error("--temporal cannot be combined with --adaptive or --aa")
     if a.sparse is not None and a.sequence is None:
         p.error("--sparse needs --sequence (a sparse frame's lattice moves from frame to frame)")
+    for flag, given in (("--poses", a.poses is not None), ("--history-clamp", a.history_clamp is not None)):
+        if given and (a.sequence is None or a.temporal is None):
+            p.error(f"{flag} needs --sequence --temporal")
+    if a.poses is not None:
+        if a.sparse is not None:
+            p.error("--poses cannot be combined with --sparse")
+        if len(a.poses) != len(a.sequence):
+            p.error(f"--poses holds {len(a.poses)} frames, --sequence {len(a.sequence)} cameras")
     if a.sequence is not None:
         for flag, given in (("--cast", a.cast), ("--views", a.views is not None), ("--adaptive", a.adaptive is not None),
                             ("--preview-every", a.preview_every is not None), ("--light", a.light is not None)):
@@ -436,9 +477,13 @@ def main(argv=None):
         print(f"Wrote {len(imgs)} views to {view_paths(settings.savePath, 1)[0]} ...")
     elif a.sequence is not None:
         paths = view_paths(settings.savePath, len(a.sequence))
-        frames = render_sequence(bih, a.sequence, settings.samples, settings.dimensions, temporal=a.temporal is not None, denoise=a.denoise,
-                                 depth=a.depth, sky=a.sky, film=film_of(a), sparse=a.sparse,
-                                 **({} if a.temporal is None or a.temporal is True else {"alpha_min": a.temporal}))
+        more = {} if a.temporal is None or a.temporal is True else {"alpha_min": a.temporal}
+        if a.poses is not None:
+            frames = render_moving_sequence(mesh, a.sequence, a.poses, settings.samples, settings.dimensions, clamp=a.history_clamp,
+                                            denoise=a.denoise, depth=a.depth, sky=a.sky, film=film_of(a), **more)
+        else:
+            frames = render_sequence(bih, a.sequence, settings.samples, settings.dimensions, temporal=a.temporal is not None, denoise=a.denoise,
+                                     depth=a.depth, sky=a.sky, film=film_of(a), sparse=a.sparse, clamp=a.history_clamp, **more)
         for path, img in zip(paths, frames):
             write_png(path, img)
         print(f"Wrote {len(paths)} frames to {paths[0]} ...")

@@ -6,7 +6,8 @@
 // contiguous: under a slow camera the 64 lanes of a wave reproject into one or two row segments of the previous frame.  The block of
 // a frame is three planes of 16-byte records (CV colour + variance, NL normal + length, PT point + triangle), so a tap is three
 // dwordx4 loads, and the twelve loads of a pixel's four taps are issued together, before any tap is judged (sq_temporal_pixel.h).
-// No LDS: the four taps of neighbouring lanes overlap, and L1 / L2 serve the re-reads.
+// No LDS for the taps: the four taps of neighbouring lanes overlap, and L1 / L2 serve the re-reads.  (The moving call's clamp window
+// is another matter: below.)
 //
 // The arithmetic of a pixel is csrc/sq_temporal_pixel.h, the text the host's sq_temporal_project compiles too.  -ffp-contract=off
 // and the correctly rounded divide keep it equal to the numpy restatement.
@@ -66,6 +67,107 @@ __global__ __launch_bounds__(kBlock) void sq_tp_accumulate(const int rows, const
     }
 }
 
+// ---- moving geometry and the clamp (sq_temporal_accumulate_moving_device).  sq_tp_accumulate above stays the old entry point's own.
+//
+// The same tile and the same twelve loads; ahead of them a moved pixel takes two dependent loads (its triangle's object, then the
+// object's twelve floats, which a wave mostly shares).  The clamp's window is up to 49 taps of colour and triangle a pixel, in two
+// forms that give the same bits (the window's order is pinned, sq_temporal_pixel.h): kClampDirect reads every tap from memory,
+// kClampTiled stages the tile and its halo of `radius` pixels in LDS once -- (4 + 2r) x (64 + 2r) records of colour and a hit flag,
+// 11200 bytes at r = 3 -- and reads the taps from there.  A tap that does not count (outside the image, or no hit) is staged with
+// flag 0, so the image's borders need no second test.
+constexpr int kClampNone = 0, kClampDirect = SQ_TEMPORAL_FORM_DIRECT, kClampTiled = SQ_TEMPORAL_FORM_TILED;
+constexpr int kMaxRadius = 3;
+constexpr int kHaloRecs = (kTileH + 2 * kMaxRadius) * (kTileW + 2 * kMaxRadius);
+
+struct Moving {
+    const int32_t* object; const float* back;      // both or neither
+    int32_t n_tris, n_objects;
+    temporalpix::Clamp clamp;                        // read by the clamped instantiations only
+};
+
+template <int kClamp>
+__global__ __launch_bounds__(kBlock) void sq_tp_accumulate_moving(const int rows, const int cols, const float* color, const float* var,
+                                                                  const int32_t* __restrict__ tri, const float* __restrict__ normal,
+                                                                  const float* __restrict__ point, const float* __restrict__ alpha,
+                                                                  const Cam cam, const Rec* __restrict__ prev, const temporalpix::Params P,
+                                                                  const Moving M, Rec* __restrict__ next, float* out, float* out_var,
+                                                                  int32_t* __restrict__ out_len, uint8_t* __restrict__ out_flags,
+                                                                  const long long tiles, const long long tiles_x) {
+    __shared__ Rec halo[kClamp == kClampTiled ? kHaloRecs : 1];
+    const long long n = (long long)rows * cols;
+    const Rec* p_cv = prev;
+    const Rec* p_nl = prev ? prev + n : nullptr;
+    const Rec* p_pt = prev ? prev + 2 * n : nullptr;
+    const int r = kClamp == kClampNone ? 0 : M.clamp.radius;
+    const int halo_w = kTileW + 2 * r;
+    const int lx = threadIdx.x & (kTileW - 1), ly = threadIdx.x / kTileW;
+    for (long long t = blockIdx.x; t < tiles; t += gridDim.x) {          // (the trip count is the block's: every thread meets every barrier)
+        const long long ty = t / tiles_x, tx = t - ty * tiles_x;
+        if (kClamp == kClampTiled) {
+            __syncthreads();                                             // the last tile's taps have been read
+            for (int e = threadIdx.x; e < halo_w * (kTileH + 2 * r); e += kBlock) {
+                const int hy = e / halo_w, hx = e - hy * halo_w;
+                const long long gy = ty * kTileH + hy - r, gx = tx * kTileW + hx - r;
+                Rec c = { 0.0f, 0.0f, 0.0f, 0.0f };
+                if (gy >= 0 && gy < rows && gx >= 0 && gx < cols) {
+                    const long long q = gy * cols + gx;
+                    if (tri[q] >= 0) c = Rec{ color[3 * q], color[3 * q + 1], color[3 * q + 2], 1.0f };
+                }
+                halo[e] = c;
+            }
+            __syncthreads();
+        }
+        const long long x = tx * kTileW + lx, y = ty * kTileH + ly;
+        if (x >= cols || y >= rows) continue;
+        const long long p = y * cols + x;
+        const float cr = color[3 * p], cg = color[3 * p + 1], cb = color[3 * p + 2], v = var[p];
+        const int32_t tr = tri[p];
+        const float nx = normal[3 * p], ny = normal[3 * p + 1], nz = normal[3 * p + 2];
+        const float px = point[3 * p], py = point[3 * p + 1], pz = point[3 * p + 2];
+        const float al = alpha ? alpha[p] : -1.0f;
+        float B[12];
+        bool moved = false;
+        if (M.object && prev && tr >= 0) {                               // an index outside its table is never read through
+            const int32_t o = tr < M.n_tris ? M.object[tr] : -1;
+            if (o >= 0 && o < M.n_objects) {
+                moved = true;
+#pragma unroll
+                for (int i = 0; i < 12; ++i) B[i] = M.back[12LL * o + i];
+            }
+        }
+        uint32_t flags;
+        temporalpix::Pixel res;
+        if (kClamp == kClampTiled) {
+            const Rec* centre = halo + (ly + r) * halo_w + (lx + r);
+            res = temporalpix::accumulate_moving(p_cv, p_nl, p_pt, rows, cols, cam.pos, cam.rot, P, cr, cg, cb, v, tr, nx, ny, nz, px, py, pz,
+                                                 alpha != nullptr, al, moved, B, &M.clamp,
+                                                 [&](int j, int i, float* c) {
+                                                     const Rec h = centre[j * halo_w + i];
+                                                     c[0] = h.x; c[1] = h.y; c[2] = h.z;
+                                                     return h.w != 0.0f;
+                                                 }, flags);
+        } else {
+            res = temporalpix::accumulate_moving(p_cv, p_nl, p_pt, rows, cols, cam.pos, cam.rot, P, cr, cg, cb, v, tr, nx, ny, nz, px, py, pz,
+                                                 alpha != nullptr, al, moved, B, kClamp == kClampNone ? nullptr : &M.clamp,
+                                                 [&](int j, int i, float* c) {
+                                                     const long long qy = y + j, qx = x + i;
+                                                     if (qy < 0 || qy >= rows || qx < 0 || qx >= cols) return false;
+                                                     const long long q = qy * cols + qx;
+                                                     if (tri[q] < 0) return false;
+                                                     c[0] = color[3 * q]; c[1] = color[3 * q + 1]; c[2] = color[3 * q + 2];
+                                                     return true;
+                                                 }, flags);
+        }
+        next[p] = Rec{ res.r, res.g, res.b, res.v };
+        next[n + p] = Rec{ nx, ny, nz, temporalpix::int_bits(res.len) };
+        next[2 * n + p] = Rec{ px, py, pz, temporalpix::int_bits(tr) };
+        out[3 * p] = res.r; out[3 * p + 1] = res.g; out[3 * p + 2] = res.b;
+        out_var[p] = res.v;
+        if (out_len) out_len[p] = res.len;
+        if (out_flags) out_flags[p] = (uint8_t)flags;
+    }
+}
+
 __global__ __launch_bounds__(kBlock) void sq_tp_unpack(const long long n, const Rec* __restrict__ hist, float* __restrict__ color,
                                                        float* __restrict__ var, int32_t* __restrict__ len, int32_t* __restrict__ tri,
                                                        float* __restrict__ normal, float* __restrict__ point) {
@@ -116,6 +218,35 @@ int check_accumulate(int32_t rows, int32_t cols, const float* d_color, const flo
     return refuse_overlaps(r, 11, " (only d_out == d_color and d_out_var == d_var may share memory)", twins, 2);
 }
 
+// Radius 3 is the widest window the tiled form's LDS holds; what the auto form is, is DESIGN.md 4.28's measurement.
+int auto_clamp_form() { return SQ_TEMPORAL_FORM_TILED; }
+
+// What the moving call refuses beyond check_accumulate, in the order of the header's list.
+int check_moving(int32_t rows, int32_t cols, const float* d_color, const float* d_var, const int32_t* d_tri, const float* d_normal,
+                 const float* d_point, const float* d_alpha, const void* d_prev, const int32_t* d_object, int32_t n_tris, const float* d_back,
+                 int32_t n_objects, const sq_temporal_clamp* clamp, int32_t form, void* d_next, float* d_out, float* d_out_var,
+                 int32_t* d_out_len, uint8_t* d_out_flags) {
+    if (n_tris < 0 || n_objects < 0) return sq_set_error("n_tris and n_objects must not be negative (got %d and %d)", n_tris, n_objects);
+    if ((d_object == nullptr) != (d_back == nullptr))
+        return sq_set_error("d_object and d_back go together: both NULL (nothing moves) or both given");
+    if (d_object && n_tris == 0) return sq_set_error("d_object is given with n_tris = 0");
+    if (d_back && n_objects == 0) return sq_set_error("d_back is given with n_objects = 0");
+    if (clamp) {
+        if (clamp->radius < 1 || clamp->radius > kMaxRadius) return sq_set_error("clamp.radius must be in 1..3 (got %d)", clamp->radius);
+        if (!(clamp->k >= 0.0f)) return sq_set_error("clamp.k must be a number >= 0 (got %g)", (double)clamp->k);
+    }
+    if (form < SQ_TEMPORAL_FORM_AUTO || form > SQ_TEMPORAL_N_FORMS) return sq_set_error("form must be in 0..%d (got %d)", SQ_TEMPORAL_N_FORMS, form);
+    const size_t n = (size_t)rows * (size_t)cols, hb = sq_temporal_history_bytes(rows, cols);
+    const NamedRange r[14] = { { "d_color", d_color, 12 * n }, { "d_var", d_var, 4 * n }, { "d_tri", d_tri, 4 * n }, { "d_normal", d_normal, 12 * n },
+                               { "d_point", d_point, 12 * n }, { "d_alpha", d_alpha, 4 * n }, { "d_prev", d_prev, hb }, { "d_next", d_next, hb },
+                               { "d_out", d_out, 12 * n }, { "d_out_var", d_out_var, 4 * n }, { "d_out_len", d_out_len, 4 * n },
+                               { "d_object", d_object, 4 * (size_t)n_tris }, { "d_back", d_back, 48 * (size_t)n_objects },
+                               { "d_out_flags", d_out_flags, n } };
+    const int twins[2][2] = { { 1, 9 }, { 0, 8 } };                              // under a clamp neighbours' colours are read: only the first
+    return refuse_overlaps(r, 14, clamp ? " (under a clamp only d_out_var == d_var may share memory)"
+                                        : " (only d_out == d_color and d_out_var == d_var may share memory)", twins, clamp ? 1 : 2);
+}
+
 unsigned grid_for(long long units) { return (unsigned)(units < kMaxGrid ? units : kMaxGrid); }
 
 }  // namespace
@@ -154,6 +285,36 @@ extern "C" int sq_temporal_accumulate_device(int32_t device, int32_t rows, int32
     const long long tx = ((long long)cols + kTileW - 1) / kTileW, ty = ((long long)rows + kTileH - 1) / kTileH;
     hipLaunchKernelGGL(sq_tp_accumulate, dim3(grid_for(tx * ty)), dim3(kBlock), 0, (hipStream_t)hip_stream, rows, cols, d_color, d_var,
                        d_tri, d_normal, d_point, d_alpha, cam, (const Rec*)d_prev, P, (Rec*)d_next, d_out, d_out_var, d_out_len, tx * ty, tx);
+    SQ_HIP(hipGetLastError());
+    return 0;
+}
+
+extern "C" int sq_temporal_accumulate_moving_device(int32_t device, int32_t rows, int32_t cols, const float* d_color, const float* d_var,
+                                                    const int32_t* d_tri, const float* d_normal, const float* d_point, const float* d_alpha,
+                                                    const sq_camera* prev_cam, const void* d_prev, const sq_temporal_params* params,
+                                                    const int32_t* d_object, int32_t n_tris, const float* d_back, int32_t n_objects,
+                                                    const sq_temporal_clamp* clamp, int32_t form, void* d_next, float* d_out,
+                                                    float* d_out_var, int32_t* d_out_len, uint8_t* d_out_flags, void* hip_stream) {
+    if (check_accumulate(rows, cols, d_color, d_var, d_tri, d_normal, d_point, d_alpha, prev_cam, d_prev, params, d_next, d_out, d_out_var,
+                         d_out_len) ||
+        check_moving(rows, cols, d_color, d_var, d_tri, d_normal, d_point, d_alpha, d_prev, d_object, n_tris, d_back, n_objects, clamp, form,
+                     d_next, d_out, d_out_var, d_out_len, d_out_flags))
+        return 1;
+    SQ_HIP(hipSetDevice(device));
+    Cam cam = {};
+    if (d_prev) {
+        for (int i = 0; i < 3; ++i) cam.pos[i] = prev_cam->pos[i];
+        for (int i = 0; i < 9; ++i) cam.rot[i] = prev_cam->rot[i];
+    }
+    const temporalpix::Params P{ params->alpha_min, params->max_history, params->sigma_p, params->cos_n };
+    const Moving M{ d_object, d_back, n_tris, n_objects, clamp ? temporalpix::Clamp{ clamp->radius, clamp->k } : temporalpix::Clamp{ 0, 0.0f } };
+    // without history nothing is blended, so nothing is clamped: the window is not read at all
+    const int how = !clamp || !d_prev ? kClampNone : form == SQ_TEMPORAL_FORM_AUTO ? auto_clamp_form() : form;
+    const long long tx = ((long long)cols + kTileW - 1) / kTileW, ty = ((long long)rows + kTileH - 1) / kTileH;
+    auto* kernel = how == kClampTiled ? sq_tp_accumulate_moving<kClampTiled>
+                 : how == kClampDirect ? sq_tp_accumulate_moving<kClampDirect> : sq_tp_accumulate_moving<kClampNone>;
+    hipLaunchKernelGGL(kernel, dim3(grid_for(tx * ty)), dim3(kBlock), 0, (hipStream_t)hip_stream, rows, cols, d_color, d_var, d_tri, d_normal,
+                       d_point, d_alpha, cam, (const Rec*)d_prev, P, M, (Rec*)d_next, d_out, d_out_var, d_out_len, d_out_flags, tx * ty, tx);
     SQ_HIP(hipGetLastError());
     return 0;
 }

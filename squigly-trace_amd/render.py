@@ -219,7 +219,7 @@ def render_lens_rgb8(bih, cam, samples, dimensions, lens=None, subrays=None, dev
 
 
 def render_sequence(bih, cams, spp, dimensions, temporal=True, denoise=None, device=0, depth=None, sky=None, period=64, alpha_min=0.1,
-                    max_history=32, film=None, sparse=None):
+                    max_history=32, film=None, sparse=None, clamp=None):
     """The frames of a camera move, `spp` samples each (DeviceScene, Temporal: one device, the scene uploaded once): yields the
     (w, h, 3) uint8 image of every camera of `cams`, in order.  temporal=True accumulates every frame over the ones before it
     (libsquigly_temporal.so); temporal=False shows each frame's own samples -- the same samples, so the two can be compared.
@@ -230,7 +230,7 @@ def render_sequence(bih, cams, spp, dimensions, temporal=True, denoise=None, dev
     temporal=True; under temporal=False the film's exposure state is forgotten after every frame as the history is -- film.reset() --
     so that every frame is exposed at its own target and the frames stay independent).
     sparse (None = off; a stride S in 1..16): every frame traces only a lattice of its pixels, which moves from frame to frame, and
-    the holes, and fills the others in from their traced neighbours (Temporal(sparse=S)).
+    the holes, and fills the others in from their traced neighbours (Temporal(sparse=S)).  clamp: Temporal's (None = off).
     Refused before anything is uploaded: no camera, what Temporal refuses of spp, period, alpha_min and max_history, and a sparse
     that is no stride."""
     cams = list(cams)
@@ -238,6 +238,8 @@ def render_sequence(bih, cams, spp, dimensions, temporal=True, denoise=None, dev
         raise ValueError("render_sequence needs at least one camera")
     from .temporal import _temporal_args
     _temporal_args(spp, period, alpha_min, max_history)
+    from .temporal import clamp_arg
+    clamp_arg(clamp)
     if sparse is not None:
         from .denoise import stride_arg
         stride_arg(sparse)
@@ -248,7 +250,8 @@ def render_sequence(bih, cams, spp, dimensions, temporal=True, denoise=None, dev
     w, h = dimensions
     with scene as ds:
         from .temporal import Temporal                 # torch: only the resident-scene path needs it
-        t = Temporal(ds, w, h, spp, period=period, alpha_min=alpha_min, max_history=max_history, denoise=dn, film=film, sparse=sparse)
+        t = Temporal(ds, w, h, spp, period=period, alpha_min=alpha_min, max_history=max_history, denoise=dn, film=film, sparse=sparse,
+                     clamp=clamp)
         for cam in cams:
             _, _, _, rgb = t.step(cam)
             if not temporal:
@@ -256,6 +259,52 @@ def render_sequence(bih, cams, spp, dimensions, temporal=True, denoise=None, dev
                 if film is not None:
                     film.reset()
             yield rgb.cpu().numpy()
+
+
+MOVING_BUILD_DEVICE_FROM = 50000     # triangles from which a frame's tree is built on the device (DESIGN.md 4.28's measurement)
+
+
+def render_moving_sequence(mesh, cams, poses, spp, dimensions, temporal=True, clamp=None, denoise=None, device=0, depth=None, sky=None,
+                           period=64, alpha_min=0.1, max_history=32, film=None, build=None):
+    """render_sequence under geometry that moves rigidly: `mesh` is the scene in its rest pose and poses [frames, n_materials, 3, 4]
+    gives every material's pose [R | t] (world = R local + t) in every frame -- the objects are the materials.  Per frame the mesh
+    is moved (moved_mesh), its tree built, the scene uploaded (a DeviceScene per frame: nothing is refitted in place) and stepped
+    with the move from the frame before (Temporal.step(cam, scene=, back=back_transforms(...))).  Yields the (w, h, 3) uint8 image
+    of every frame.  clamp: Temporal's (None = off).  build: "host" or "device", where a frame's tree is built; None = on the device
+    from MOVING_BUILD_DEVICE_FROM triangles up.  temporal=False shows each frame's own samples.
+    Refused before anything is uploaded: no camera, poses that are not a [len(cams), n_materials, 3, 4] array, what Temporal
+    refuses of its numbers, a build that is neither."""
+    from .scene import BIH, moved_mesh
+    cams = list(cams)
+    if not cams:
+        raise ValueError("render_moving_sequence needs at least one camera")
+    poses = np.asarray(poses, np.float64)
+    if poses.shape != (len(cams), len(mesh.materials), 3, 4):
+        raise ValueError(f"poses must have shape ({len(cams)}, {len(mesh.materials)}, 3, 4): a pose per frame and material, got {poses.shape}")
+    if build not in (None, "host", "device"):
+        raise ValueError(f"build must be 'host', 'device' or None, got {build!r}")
+    from .temporal import _temporal_args, back_transforms, clamp_arg
+    _temporal_args(spp, period, alpha_min, max_history)
+    clamp_arg(clamp)
+    from .film import film_arg
+    film_arg(film)
+    dn = denoise_arg(denoise)
+    on_device = build == "device" or (build is None and len(mesh) >= MOVING_BUILD_DEVICE_FROM)
+    w, h = dimensions
+    t = None
+    for f, cam in enumerate(cams):
+        bih = BIH(moved_mesh(mesh, poses[f]), device=device if on_device else None)
+        with _resident(bih, device, None, depth, sky) as ds:
+            if t is None:
+                from .temporal import Temporal
+                t = Temporal(ds, w, h, spp, period=period, alpha_min=alpha_min, max_history=max_history, denoise=dn, film=film, clamp=clamp)
+            _, _, _, rgb = t.step(cam, scene=ds, back=None if f == 0 else back_transforms(poses[f - 1], poses[f]))
+            if not temporal:
+                t.forget()
+                if film is not None:
+                    film.reset()
+            img = rgb.cpu().numpy()                  # (waits for the frame: its scene may close)
+        yield img
 
 
 def render_sparse(bih, cam, samples, dimensions, stride, offset=(0, 0), denoise=None, film=None, device=0, depth=None, sky=None,

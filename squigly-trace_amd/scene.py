@@ -81,6 +81,22 @@ class Mesh(Owner):
         return _records(n and N.lib().sq_mesh_materials(self._h), n, N.MAT_DTYPE)
 
 
+def moved_mesh(mesh, poses):
+    """A Mesh (from_arrays) with the pose of material m applied to every triangle of material m: poses is [n_materials, 3, 4],
+    rows [R | t] with world = R local + t, so an identity row leaves a material's triangles where they are, bit for bit.  Computed
+    in float64 and rounded to float32 once.  The triangles keep their order and their materials."""
+    poses = np.asarray(poses, np.float64)
+    mats = mesh.materials
+    if poses.ndim != 3 or poses.shape != (len(mats), 3, 4):
+        raise ValueError(f"poses must have shape ({len(mats)}, 3, 4): a pose per material, got {poses.shape}")
+    tris = np.array(mesh.tris, dtype=N.TRI_DTYPE)
+    M = poses[tris["mat"]]                                                     # [n_tris, 3, 4]
+    for v in ("v0", "v1", "v2"):
+        p = tris[v].astype(np.float64)
+        tris[v] = (np.einsum("nij,nj->ni", M[:, :, :3], p) + M[:, :, 3]).astype(np.float32)
+    return Mesh.from_arrays(tris, np.array(mats, dtype=N.MAT_DTYPE))
+
+
 class BIH(Owner):
     """BIH.makeBIH result, flattened to the pre-order arrays of include/squigly_hip.h."""
     _free = "sq_bih_free"
