@@ -28,8 +28,8 @@
  *
  * The history block is opaque to callers: sq_temporal_history_bytes(rows, cols) bytes, 16-byte aligned, three planes of 16-byte
  * records, a record per pixel in each (colour.rgb + variance; normal.xyz + length; point.xyz + triangle), so that a bilinear tap
- * is three 16-byte loads and a wave's loads of one plane are contiguous.  Only sq_temporal_accumulate_device writes one, and a block
- * that it did not write is not a history (its lengths are taken as they are).  Callers go to and fro between two blocks.
+ * is three 16-byte loads and a wave's loads of one plane are contiguous.  Only the two accumulate calls write one, and a block
+ * that neither wrote is not a history (its lengths are taken as they are).  Callers go to and fro between two blocks.
  *
  * The contract.  Every operation is one fp32 operation, in exactly this order.  For the pixel p = (row y, column x): colour c,
  * variance v, triangle tri, normal n_p, point P_p; ww = (float)rows, hh = (float)cols.

@@ -1,7 +1,7 @@
 // sq_temporal_pixel.h — the arithmetic of one pixel of a temporal accumulation (include/squigly_temporal.h), written once for the
 // host and the device: sq_temporal_project compiles `project` with the host compiler, every lane of libsquigly_temporal.so's kernel
-// compiles all of it with the device compiler, and tests/temporal_main.cpp compiles it with g++ under the sanitizers.  Only the
-// temporal library lists this header.
+// compiles all of it with the device compiler, and tests/temporal_main.cpp (`project`) and tests/moving_main.cpp (`accumulate`, the
+// static and the moving call's pixel alike) compile it with g++ under the sanitizers.  Only the temporal library lists this header.
 //
 // Every operation is one fp32 operation in the order of the header's contract (tests/temporal_restatement.py restates it in numpy);
 // -ffp-contract=off and the correctly rounded divide keep the two equal.  Nothing is skipped for a zero weight: 0 * inf is NaN here too.
@@ -39,73 +39,7 @@ SQ_HD bool project(const float* pos, const float* rot, float ww, float hh, float
 
 struct Pixel { float r, g, b, v; int32_t len; };
 
-// The pixel's result from its inputs and the previous block (cv, nl, pt: the three planes; nullptr = no history).  alpha < 0 never
-// raises a (the caller passes -1 without d_alpha: a >= alpha_min >= 0 > -1).
-SQ_HD Pixel accumulate(const Rec* cv, const Rec* nl, const Rec* pt, int32_t rows, int32_t cols, const float* pos, const float* rot,
-                       const Params& P, float cr, float cg, float cb, float v, int32_t tri, float nx, float ny, float nz,
-                       float px, float py, float pz, bool has_alpha, float alpha) {
-    Pixel out = { cr, cg, cb, v, 1 };
-    if (!cv || tri < 0) return out;
-    float fx, fy;
-    if (!project(pos, rot, (float)rows, (float)cols, px, py, pz, fx, fy)) return out;
-    const float x0 = __builtin_floorf(fx), y0 = __builtin_floorf(fy);
-    const float tx = fx - x0, ty = fy - y0;
-    const long long ix = (long long)x0, iy = (long long)y0;
-    float sw = 0.0f, sr = 0.0f, sg = 0.0f, sb = 0.0f, sv = 0.0f;
-    int32_t m = 0x7fffffff;
-    // The twelve records of the four taps are loaded first, each from an address that does not depend on another load: a tap's three
-    // loads one behind the other, each behind the test of the one before, left the kernel waiting for twelve round trips a pixel.  A
-    // tap outside the image reads pixel 0 and is left out below.
-    bool in[4];
-    Rec pqs[4], nqs[4], cqs[4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-        const long long qy = iy + (t >> 1), qx = ix + (t & 1);
-        in[t] = qy >= 0 && qy < rows && qx >= 0 && qx < cols;
-        const long long q = in[t] ? qy * cols + qx : 0;
-        pqs[t] = pt[q];
-        nqs[t] = nl[q];
-        cqs[t] = cv[q];
-    }
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const Rec pq = pqs[2 * j + i], nq = nqs[2 * j + i], cq = cqs[2 * j + i];
-            if (!in[2 * j + i] || bits_int(pq.w) < 0) continue;
-            const float bw = (i ? tx : 1.0f - tx) * (j ? ty : 1.0f - ty);
-            const float dn = (nx * nq.x + ny * nq.y) + nz * nq.z;
-            if (!(dn >= P.cos_n)) continue;
-            const float dx = pq.x - px, dy = pq.y - py, dz = pq.z - pz;
-            const float pd = (nx * dx + ny * dy) + nz * dz;
-            if (!(__builtin_fabsf(pd) <= P.sigma_p)) continue;
-            sw = sw + bw;
-            sr = sr + bw * cq.x;
-            sg = sg + bw * cq.y;
-            sb = sb + bw * cq.z;
-            sv = sv + bw * cq.w;
-            const int32_t lq = bits_int(nq.w);
-            m = lq < m ? lq : m;
-        }
-    }
-    if (!(sw > 0.0f)) return out;
-    const float hr = sr / sw, hg = sg / sw, hb = sb / sw, hv = sv / sw;
-    const int32_t m1 = (int32_t)((uint32_t)m + 1u);
-    float a = 1.0f / (float)m1;
-    if (a < P.alpha_min) a = P.alpha_min;
-    if (has_alpha && a < alpha) a = alpha;
-    out.r = hr + a * (cr - hr);
-    out.g = hg + a * (cg - hg);
-    out.b = hb + a * (cb - hb);
-    const float om = 1.0f - a;
-    out.v = (om * om) * hv + (a * a) * v;
-    out.len = m1 < P.max_history ? m1 : P.max_history;
-    return out;
-}
-
-// ---- moving geometry and the clamp: sq_temporal_accumulate_moving_device.  `accumulate` above is the old entry point's and stays
-// as it is; what follows restates its taps with the moved point and normal in their place.
-
+// What the moving call adds to a pixel: the way back through its object's move, and the clamp.
 struct Clamp { int32_t radius; float k; };
 struct Bounds { float lo[3], hi[3]; };
 
@@ -153,14 +87,17 @@ SQ_HD Bounds window_bounds(const Clamp& K, Tap tap) {
     return b;
 }
 
-// `accumulate` with the point and the normal taken through B (12 floats, read only if `moved`; otherwise the pixel is static: P' = P
-// and n' = n, bit for bit) and the history colour held to the window's bounds (K; nullptr = no clamp).  flags receives the bits of d_out_flags.  The
-// window is read only where history is blended.
+// The pixel's result from its inputs and the previous block (cv, nl, pt: the three planes; nullptr = no history), for both calls.
+// alpha < 0 never raises a (the caller passes -1 without d_alpha: a >= alpha_min >= 0 > -1).  The point and the normal are taken
+// through B (12 floats, read only if `moved`; otherwise the pixel is static: P' = P and n' = n, bit for bit) and the history colour
+// is held to the window's bounds (K; nullptr = no clamp, and `tap` is then never called).  flags receives the bits of d_out_flags.
+// The window is read only where history is blended.  The old call's pixel is moved = false and K = nullptr.  (`moved` and B stay two
+// arguments: handed `moved ? B : nullptr` the device compiler keeps the transform in scratch.)
 template <class Tap>
-SQ_HD Pixel accumulate_moving(const Rec* cv, const Rec* nl, const Rec* pt, int32_t rows, int32_t cols, const float* pos, const float* rot,
-                              const Params& P, float cr, float cg, float cb, float v, int32_t tri, float nx, float ny, float nz,
-                              float px, float py, float pz, bool has_alpha, float alpha, bool moved, const float* B, const Clamp* K,
-                              Tap tap, uint32_t& flags) {
+SQ_HD Pixel accumulate(const Rec* cv, const Rec* nl, const Rec* pt, int32_t rows, int32_t cols, const float* pos, const float* rot,
+                       const Params& P, float cr, float cg, float cb, float v, int32_t tri, float nx, float ny, float nz,
+                       float px, float py, float pz, bool has_alpha, float alpha, bool moved, const float* B, const Clamp* K,
+                       Tap tap, uint32_t& flags) {
     Pixel out = { cr, cg, cb, v, 1 };
     flags = 0u;
     if (!cv || tri < 0) return out;
@@ -175,10 +112,13 @@ SQ_HD Pixel accumulate_moving(const Rec* cv, const Rec* nl, const Rec* pt, int32
     const long long ix = (long long)x0, iy = (long long)y0;
     float sw = 0.0f, sr = 0.0f, sg = 0.0f, sb = 0.0f, sv = 0.0f;
     int32_t m = 0x7fffffff;
+    // The twelve records of the four taps are loaded first, each from an address that does not depend on another load: a tap's three
+    // loads one behind the other, each behind the test of the one before, left the kernel waiting for twelve round trips a pixel.  A
+    // tap outside the image reads pixel 0 and is left out below.
     bool in[4];
     Rec pqs[4], nqs[4], cqs[4];
 #pragma unroll
-    for (int t = 0; t < 4; ++t) {                        // the twelve loads first, as in accumulate
+    for (int t = 0; t < 4; ++t) {
         const long long qy = iy + (t >> 1), qx = ix + (t & 1);
         in[t] = qy >= 0 && qy < rows && qx >= 0 && qx < cols;
         const long long q = in[t] ? qy * cols + qx : 0;

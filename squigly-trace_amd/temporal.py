@@ -206,25 +206,23 @@ def accumulate(color, var, guides, prev_cam, prev, nxt, alpha=None, out=None, st
             out_v = torch.empty((rows, cols), dtype=f32, device=dev)
         if out_l is None:
             out_l = torch.empty((rows, cols), dtype=torch.int32, device=dev)
-        if moving:
-            if back is not None and not back.is_cuda:          # through pinned memory: the copy only enqueues, behind the stream's work
-                back = back.pin_memory().to(dev, non_blocking=True)
-            if back is not None:
-                P.tensor("back", back, (int(back.shape[0]), 12), f32, dev)
-            flags = torch.empty((rows, cols), dtype=torch.uint8, device=dev) if want_flags else None
-            cl = None if clamp is None else Clamp(clamp[1], clamp[0])
-            check(lib().sq_temporal_accumulate_moving_device(
-                dev.index or 0, rows, cols, color.data_ptr(), var.data_ptr(), guides.tri.data_ptr(), guides.normal.data_ptr(),
-                guides.point.data_ptr(), P.ptr(alpha), None if prev_cam is None else C.byref(prev_cam), P.ptr(prev), C.byref(par),
-                P.ptr(objects), 0 if objects is None else int(objects.shape[0]), P.ptr(back), 0 if back is None else int(back.shape[0]),
-                None if cl is None else C.byref(cl), FORMS[form], nxt.data_ptr(), out_c.data_ptr(), out_v.data_ptr(), out_l.data_ptr(),
-                P.ptr(flags), P.stream_ptr(st)))
-            return (out_c, out_v, out_l, flags) if want_flags else (out_c, out_v, out_l)
-        check(lib().sq_temporal_accumulate_device(dev.index or 0, rows, cols, color.data_ptr(), var.data_ptr(), guides.tri.data_ptr(),
-                                                  guides.normal.data_ptr(), guides.point.data_ptr(), P.ptr(alpha),
-                                                  None if prev_cam is None else C.byref(prev_cam), P.ptr(prev), C.byref(par),
-                                                  nxt.data_ptr(), out_c.data_ptr(), out_v.data_ptr(), out_l.data_ptr(), P.stream_ptr(st)))
-    return out_c, out_v, out_l
+        # what both entry points take, ahead of and behind the moving call's own arguments
+        head = (dev.index or 0, rows, cols, color.data_ptr(), var.data_ptr(), guides.tri.data_ptr(), guides.normal.data_ptr(),
+                guides.point.data_ptr(), P.ptr(alpha), None if prev_cam is None else C.byref(prev_cam), P.ptr(prev), C.byref(par))
+        tail = (nxt.data_ptr(), out_c.data_ptr(), out_v.data_ptr(), out_l.data_ptr())
+        if not moving:
+            check(lib().sq_temporal_accumulate_device(*head, *tail, P.stream_ptr(st)))
+            return out_c, out_v, out_l
+        if back is not None and not back.is_cuda:          # through pinned memory: the copy only enqueues, behind the stream's work
+            back = back.pin_memory().to(dev, non_blocking=True)
+        if back is not None:
+            P.tensor("back", back, (int(back.shape[0]), 12), f32, dev)
+        flags = torch.empty((rows, cols), dtype=torch.uint8, device=dev) if want_flags else None
+        cl = None if clamp is None else Clamp(clamp[1], clamp[0])
+        check(lib().sq_temporal_accumulate_moving_device(
+            *head, P.ptr(objects), 0 if objects is None else int(objects.shape[0]), P.ptr(back), 0 if back is None else int(back.shape[0]),
+            None if cl is None else C.byref(cl), FORMS[form], *tail, P.ptr(flags), P.stream_ptr(st)))
+    return (out_c, out_v, out_l, flags) if want_flags else (out_c, out_v, out_l)
 
 
 def unpack(hist, rows, cols, stream=None):

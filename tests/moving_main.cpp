@@ -1,5 +1,5 @@
-// moving_main.cpp — csrc/sq_temporal_pixel.h's accumulate_moving, the text every lane of libsquigly_temporal.so's moving kernel
-// compiles, as a program of its own over host memory, so that it can run under the sanitizers without anything else in the process
+// moving_main.cpp — csrc/sq_temporal_pixel.h's accumulate, the text every lane of libsquigly_temporal.so's accumulate kernel compiles
+// for the static and the moving call alike, as a program of its own over host memory, so that it can run under the sanitizers without anything else in the process
 // (tests/test_moving.py builds it plainly and with -fsanitize=address,undefined and compares its output with the numpy restatement).
 // Every table is a heap block of exactly its size, so a read through a wrong index is the sanitizer's to report.
 //
@@ -83,7 +83,7 @@ int main(int argc, char** argv) {
                 if (o >= 0 && o < n_objects) { B = back.data() + 12 * (size_t)o; moved = true; }
             }
             uint32_t flags;
-            const temporalpix::Pixel r = temporalpix::accumulate_moving(
+            const temporalpix::Pixel r = temporalpix::accumulate(
                 has_prev ? cv.data() : nullptr, nl.data(), pt.data(), rows, cols, cam, cam + 3, P, color[3 * p], color[3 * p + 1], color[3 * p + 2],
                 var[p], tr, normal[3 * p], normal[3 * p + 1], normal[3 * p + 2], point[3 * p], point[3 * p + 1], point[3 * p + 2], has_alpha,
                 has_alpha ? alpha[p] : -1.0f, moved, B, K.radius ? &K : nullptr,

@@ -250,30 +250,39 @@ def test_more_tiles_than_blocks(sqt, torch, tp):
 @pytest.mark.parametrize("rows, cols", [(5, 7), (17, 67), (48, 64)], ids=["5x7", "17x67", "48x64"])
 def test_the_anchor(sqt, torch, tp, rows, cols):
     """With d_object, d_back, clamp and d_out_flags all NULL the new entry point writes the bytes of
-    sq_temporal_accumulate_device: out, out_var, out_len and the whole next block, with and without history and d_alpha."""
+    sq_temporal_accumulate_device: out, out_var, out_len and the whole next block, with and without history and d_alpha.  So it
+    does with d_out_flags alone given -- the moving kernel without a clamp, where the other two calls run the static one -- and the
+    flags are then the restatement's."""
     cur, prev, pcam = frames_for(rows, cols, 400 + rows)
     color, var, g = gpu_frame(torch, cur)
-    alpha = dev(torch, np.random.default_rng(rows).random((rows, cols)).astype(f32))
-    pblk = first_block(torch, tp, prev)
+    alpha_host = np.random.default_rng(rows).random((rows, cols)).astype(f32)
+    alpha = dev(torch, alpha_host)
+    pblk, pwant = first_block(torch, tp, prev), R.first_block(*prev)
     par, cam, L = tp.make_params(sigma_p=SIGMA_P), cam_of(sqt, pcam), tp.lib()
     for prev_blk in (None, pblk):
         for al in (None, alpha):
             res = []
-            for new in (False, True):
+            for how in ("old", "new", "flags"):
                 nxt = torch.full((tp.history_bytes(rows, cols),), 0xA5, dtype=torch.uint8, device="cuda")
                 out = torch.empty((rows, cols, 3), dtype=torch.float32, device="cuda")
                 out_v = torch.empty((rows, cols), dtype=torch.float32, device="cuda")
                 out_l = torch.empty((rows, cols), dtype=torch.int32, device="cuda")
+                flags = torch.full((rows, cols), 0xA5, dtype=torch.uint8, device="cuda") if how == "flags" else None
                 head = (0, rows, cols, color.data_ptr(), var.data_ptr(), g.tri.data_ptr(), g.normal.data_ptr(), g.point.data_ptr(),
                         tp.P.ptr(al), None if prev_blk is None else C.byref(cam), tp.P.ptr(prev_blk), C.byref(par))
                 tail = (nxt.data_ptr(), out.data_ptr(), out_v.data_ptr(), out_l.data_ptr())
-                if new:
-                    tp.check(L.sq_temporal_accumulate_moving_device(*head, None, 0, None, 0, None, 0, *tail, None, None))
-                else:
+                if how == "old":
                     tp.check(L.sq_temporal_accumulate_device(*head, *tail, None))
+                else:
+                    tp.check(L.sq_temporal_accumulate_moving_device(*head, None, 0, None, 0, None, 0, *tail, tp.P.ptr(flags), None))
                 torch.cuda.synchronize()
                 res.append((nxt, out, out_v, out_l))
-            assert all(same_exact(a, b) for a, b in zip(*res)), (rows, cols, prev_blk is not None, al is not None)
+            label = (rows, cols, prev_blk is not None, al is not None)
+            assert all(same_exact(a, b) for a, b in zip(res[0], res[1])), label
+            assert all(same_exact(a, b) for a, b in zip(res[0], res[2])), label + ("flags given",)
+            want = M.accumulate(*cur, None if prev_blk is None else pcam, None if prev_blk is None else pwant,
+                                alpha=None if al is None else alpha_host, sigma_p=SIGMA_P)
+            assert np.array_equal(flags.cpu().numpy(), want["flags"]), label + ("flags",)
 
 
 def test_python_layer_refusals(sqt, torch, tp):

@@ -242,10 +242,23 @@ def main_cases():
         yield (f"{rows}x{cols}-plain", cur, PREV_CAM, pb, None, None, None, None, params)
 
 
+def static_cases():
+    """(label, cur, prev_cam, prev block, alpha, params): what the old entry point takes -- no tables, no clamp -- on the same two
+    frames (NaN and infinite colours among them), with and without a previous block and alpha."""
+    params = dict(R.DEFAULTS, sigma_p=SIGMA_P)
+    for rows, cols in ((5, 7), (17, 67)):
+        cur, prev = R.synthetic(rows, cols, 21, CAM, 0.01), R.synthetic(rows, cols, 22, PREV_CAM, 0.01)
+        alpha = np.random.default_rng(23).random((rows, cols)).astype(f32)
+        for pcam, pb in ((None, None), (PREV_CAM, R.first_block(*prev))):
+            for a in (None, alpha):
+                yield (f"{rows}x{cols}-static-prev{pb is not None}-alpha{a is not None}", cur, pcam, pb, a, params)
+
+
 @pytest.mark.parametrize("sanitized", [False, True], ids=["plain", "asan-ubsan"])
 def test_the_pixel_header_as_a_program(tmp_path, sanitized):
     """tests/moving_main.cpp (its own main over csrc/sq_temporal_pixel.h, the text the kernel compiles) built with g++ plainly and
-    with -fsanitize=address,undefined, run as a program: exit 0, nothing on stderr, and the restatement's bits."""
+    with -fsanitize=address,undefined, run as a program: exit 0, nothing on stderr, and the restatement's bits.  The static cases
+    (no tables, radius 0: what the old entry point runs) are held to the old contract's restatement itself."""
     exe = str(tmp_path / "moving_main")
     flags = ["-fsanitize=address,undefined", "-static-libasan", "-static-libubsan"] if sanitized else ["-O1"]
     subprocess.check_call(["g++", "-std=c++17", "-ffp-contract=off"] + flags + [os.path.join(ROOT, "tests", "moving_main.cpp"), "-o", exe],
@@ -263,6 +276,20 @@ def test_the_pixel_header_as_a_program(tmp_path, sanitized):
         assert np.array_equal(got["len"], want["len"]) and np.array_equal(got["flags"], want["flags"]), label
         seen |= int(np.bitwise_or.reduce(want["flags"].reshape(-1)))
     assert seen == M.BLENDED | M.CLAMPED | M.MOVED
+    blended = 0
+    for label, cur, pcam, pb, alpha, params in static_cases():
+        src, dst = str(tmp_path / "in.bin"), str(tmp_path / "out.bin")
+        pack(src, cur, pcam, pb, alpha, None, None, None, params)
+        r = subprocess.run([exe, src, dst], capture_output=True)
+        assert r.returncode == 0 and r.stderr == b"", (label, r.returncode, r.stderr[-2000:])
+        got = unpack(dst, *cur[2].shape)
+        want = R.accumulate(*cur, pcam, pb, alpha=alpha, **params)
+        assert same(got["color"], want["color"]) and same(got["var"], want["var"]) and np.array_equal(got["len"], want["len"]), label
+        # (max_history > 1: a blend is len >= 2, and without one the frame's own colour comes back)
+        assert np.array_equal(got["flags"], np.where(want["len"] > 1, M.BLENDED, 0).astype(np.uint8)), label
+        assert same(got["color"][want["len"] == 1], cur[0][want["len"] == 1]), label
+        blended += int((want["len"] > 1).sum())
+    assert blended > 100
 
 
 # ---- the clamp's properties, on the restatement ----

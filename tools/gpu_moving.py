@@ -1,7 +1,7 @@
 """Times sq_temporal_accumulate_moving_device (libsquigly_temporal.so) on the GPU at 1920 x 1080, and what a scene that changes every
 frame costs around it.  One job, every case interleaved over `--rounds` rounds so that the spread is the job's own:
 
-  calls     the old call, the new call with nothing given, with tables, with each clamp radius in each kernel form, through the
+  calls     the old call, the new call with d_out_flags alone (the moving kernel without a clamp), with tables, with each clamp radius in each kernel form, through the
             C-ABI, ten calls between two device events (warm, median of --reps; the median, least and greatest of the rounds'
             medians), beside a device copy of the call's compulsory bytes; with --parent-lib, the old call of another build of
             the library (the parent commit's) on the same buffers in the same rounds; and two calls through the Python layer, one
@@ -79,7 +79,8 @@ def call_cases(torch, sqt, tp, a):
         return call
     # Through the C-ABI, BATCH calls between two device events: a call of a tenth of a millisecond is shorter than the Python
     # layer's checks in front of it, and one call between two events measures the host.
-    cases = {"old_call": old(L), "new_call_nothing_given": moving(), "objects": moving(objects=objects, back=back)}
+    # (every moving() case gives d_out_flags: with nothing at all given the new call runs the old call's kernel)
+    cases = {"old_call": old(L), "new_call_flags_only": moving(), "objects": moving(objects=objects, back=back)}
     for radius in (1, 2, 3):
         for form in ("direct", "tiled"):
             cases[f"clamp_r{radius}_{form}"] = moving(clamp=(1.0, radius), form=form)
